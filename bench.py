@@ -17,6 +17,9 @@ same multi-rank driver, and `hmm` (every rank its own samples, aggregate genes/s
 The same line carries `roofline` (E-step kernel, HIP-event time measured in the library on its
 own stream), `cpu_baseline` (the numpy oracle, 1 core, bounded sample) and an `hmm` object with
 the reconstruct numbers for BASELINE.json configs[2].
+
+--dump-outputs DIR writes what the timed paths computed in their last step (EM theta and expected counts, HMM posteriors,
+Viterbi path and calls) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -80,7 +83,14 @@ def parse():
                          "paths through it (the collectives, stream ordering and raw-pointer tensor views on hardware)")
     ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end `gbrs quantify` + `gbrs reconstruct` wall-clock measurement")
     ap.add_argument("--e2e-format", default="h5", choices=["h5", "npz", "both"])
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed paths computed in their last step as DIR/<name>.npy (float64, at most 64 MB in "
+                         "all): theta and expected counts of the headline EM, posteriors, Viterbi path and calls of the "
+                         "HMM pass; the inputs are seeded, so two builds can be compared output for output")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 class DevArray:
@@ -90,10 +100,12 @@ class DevArray:
         self.__cuda_array_interface__ = dict(shape=(n,), typestr="<f8", data=(ptr, False), version=2)
 
 
-def timed_region(args, run_steps, barrier, world, torch, dist, dev):
+def timed_region(args, run_steps, barrier, world, torch, dist, dev, reset=None):
     """W untimed warmup steps, then exactly K steps between two barriers (+ device synchronisation), max over ranks - twice:
     first on the chip as the setup left it (`cold`: the form of rounds 1-3), then again after --preroll-ms of the same steps,
-    untimed.  Returns (dt of the second region, dict describing the first and the pre-roll)."""
+    untimed.  `reset` (untimed, behind the pre-roll) puts the state back where the first region started, so that the second
+    region computes the same W + K iterations whatever number of steps the pre-roll took.  Returns (dt of the second region,
+    dict describing the first and the pre-roll)."""
     def once():
         run_steps(args.warmup)
         barrier()
@@ -117,12 +129,42 @@ def timed_region(args, run_steps, barrier, world, torch, dist, dev):
     run_steps(n_pre)
     barrier()
     pre_ms = (time.perf_counter() - t0) * 1e3
+    if reset is not None:
+        reset()
     dt = once()
     return dt, dict(cold_start=cold, preroll=dict(steps=n_pre, ms=pre_ms, asked_ms=args.preroll_ms,
-                                                  note="untimed EM steps in front of the warmup steps of the reported region"))
+                                                  note="untimed EM steps in front of the warmup steps of the reported region" +
+                                                       ("; the state is prepared again behind them" if reset is not None else "")))
 
 
-def em_bench(args, rank, world, torch, dist, keep_host=False):
+DUMP_LIMIT_BYTES = 64_000_000
+DUMP_SEED = 20261015
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write every array as DIR/<name>.npy in float64.  When they would take more than `limit` bytes together, every array
+    is cut to the same fraction of its elements: a flat sample at sorted positions drawn with a fixed seed, so that two runs
+    of the same command write the same positions.  Returns {name: shape written}."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    budget = limit - 4096 * len(arrays)                     # .npy headers
+    total = 8 * sum(a.size for a in arrays.values())
+    frac = min(1.0, budget / total) if total else 1.0
+    written = {}
+    for name in sorted(arrays):
+        a = arrays[name]
+        out = a.astype(np.float64)
+        if frac < 1.0:
+            k = int(a.size * frac)
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, size=k, replace=False))
+            out = out.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), out)
+        written[name] = out.shape
+    return written
+
+
+def em_bench(args, rank, world, torch, dist, keep_host=False, want_outputs=False):
     from gbrs_amd import _lib, synth, synth_torch
     from gbrs_amd.engine import EmEngine
     dev = f"cuda:{torch.cuda.current_device()}"
@@ -168,12 +210,18 @@ def em_bench(args, rank, world, torch, dist, keep_host=False):
         # run the library on torch's current stream: E-step -> all-reduce -> M-step are then ordered
         # on the device and the loop below never synchronises with the host
         eng.set_stream(torch.cuda.current_stream().cuda_stream)
+
+    def prepare():
+        nonlocal acc_t
+        if not use_dist:
+            eng.prepare(0.0)
+            return
         p, n = eng.prepare_partial()
-        acc_t = torch.as_tensor(DevArray(p, n), device=dev)
+        if acc_t is None:
+            acc_t = torch.as_tensor(DevArray(p, n), device=dev)
         dist.all_reduce(acc_t)
         eng.finish_prepare(0.0)
-    else:
-        eng.prepare(0.0)
+    prepare()
 
     def run_steps(k):
         if not use_dist:
@@ -185,10 +233,12 @@ def em_bench(args, rank, world, torch, dist, keep_host=False):
             eng.finish_step(want_err=False)
         eng.sync()
 
-    dt, region = timed_region(args, run_steps, barrier, world, torch, dist, dev)
+    dt, region = timed_region(args, run_steps, barrier, world, torch, dist, dev, reset=prepare)
     inf = eng.info()
     res = dict(dt=dt, region=region, t_gen=t_gen, t_create=t_create, t_create_host=t_host, N=n_entries, info=inf, host=host,
                mean_loci_per_read=prob.get("mean_loci_per_read"))
+    if want_outputs:                  # what the last timed step left for a caller (EMfactory's allelic expression and counts)
+        res["outputs"] = dict(em_theta=eng.theta(), em_expected_counts=eng.expected_counts())
     # ---- outside the timed region: is the state the timed steps produced a valid EM state? ----------
     res["check"] = em_state_check(torch, [eng.expected_counts()], float(args.rows) * world)
     if world == 1 and not args.no_check:
@@ -331,7 +381,7 @@ def pipelined_setup(args, rank, world, torch, dist):
     return state, err
 
 
-def em_bench_pipelined(args, rank, world, torch, dist, state):
+def em_bench_pipelined(args, rank, world, torch, dist, state, want_outputs=False):
     """N > 1: every rank holds one shard of rows, cut into two locus ranges with an engine each, so that
     the RCCL all-reduce of one range overlaps the E-step of the other (gbrs_amd.dist.PipelinedShardedEM).
     Runs after all ranks agreed that their setup succeeded: a failure from here on is fatal."""
@@ -389,7 +439,11 @@ def em_bench_pipelined(args, rank, world, torch, dist, state):
             dist.barrier()
         torch.cuda.synchronize()
 
-    dt, region = timed_region(args, drv.step, barrier, world, torch, dist, dev)
+    dt, region = timed_region(args, drv.step, barrier, world, torch, dist, dev, reset=lambda: drv.prepare(0.0))
+    outputs = None
+    if want_outputs:                  # the two locus ranges side by side, as PipelinedShardedEM.theta() returns them
+        import numpy as np
+        outputs = dict(em_theta=drv.theta(), em_expected_counts=np.concatenate([e.expected_counts() for e in engs], axis=1))
     check = em_state_check(torch, [e.expected_counts() for e in engs], float(args.rows) * world)
     # time to solution through the same two-engine loop: prepare, then the reference's stopping rule (EMfactory.py:266-278)
     # over both locus ranges on the device (gbrs_em_pair_check), looked at every 8 iterations; max over ranks
@@ -421,7 +475,7 @@ def em_bench_pipelined(args, rank, world, torch, dist, state):
         e.close()
     return dict(dt=dt, region=region, t_gen=state["t_gen"], t_create=state["t_create"], t_create_host=None, N=state["N"],
                 info=infos[0], infos=infos, estep_ms=estep_ms, step_ms=step_ms, l_split=state["l_split"],
-                check=check, **({"solve": solve} if solve else {}))
+                check=check, **({"solve": solve} if solve else {}), **({"outputs": outputs} if outputs else {}))
 
 
 def em_state_check(torch, counts_list, expect_total):
@@ -509,7 +563,7 @@ def replica_bench(args, rank, world, torch, dist):
                          f"(abundances, gene sizes, reads) on every rank")
 
 
-def hmm_bench_ranks(args, rank, world, torch, dist):
+def hmm_bench_ranks(args, rank, world, torch, dist, outputs=None):
     """N > 1: the HMM is independent per (sample, chromosome) (gbrs_utils.py:498-599) - replicas only, no collective.
     Every rank runs its own samples through the same pass as the N = 1 line (one sample: the CLI's shape; a batch that
     fills the chip); genes/s = all ranks' gene x sample units / the slowest rank's pass time."""
@@ -520,7 +574,7 @@ def hmm_bench_ranks(args, rank, world, torch, dist):
             continue
         if world > 1:
             dist.barrier()
-        b = hmm_bench(args, torch, ns=ns, with_cpu=False, sample_seed=1 + rank)
+        b = hmm_bench(args, torch, ns=ns, with_cpu=False, sample_seed=1 + rank, outputs=outputs if key == "single" else None)
         ms = max_over_ranks(b["ms_per_pass"], torch, dist, world, dev)
         wall = max_over_ranks(b["wall_clock"]["ms_per_pass"], torch, dist, world, dev)
         units = b["genes"] * ns * world
@@ -592,7 +646,7 @@ def em_cpu_baseline(args, host=None):
                        f"rule); host has {os.cpu_count()} cores, reference is single-threaded")
 
 
-def hmm_bench(args, torch, ns=None, with_cpu=True, sample_seed=1):
+def hmm_bench(args, torch, ns=None, with_cpu=True, sample_seed=1, outputs=None):
     import numpy as np
     from gbrs_amd import synth
     from gbrs_amd.hmm import DiplotypeHMM
@@ -638,6 +692,10 @@ def hmm_bench(args, torch, ns=None, with_cpu=True, sample_seed=1):
     for ci in range(len(chroms)):                   # what `gbrs reconstruct` keeps: posteriors, path, calls (sample 0)
         hmm.get(ci, 0)
     fetch_ms = (time.perf_counter() - t0) * 1e3
+    if outputs is not None:           # what the last timed pass left for a caller: every sample, the chromosomes end to end
+        got = [[hmm.get(ci, si) for ci in range(len(chroms))] for si in range(ns)]
+        for k, axis in (("gamma", 1), ("states", 0), ("calls", 0)):
+            outputs["hmm_" + k] = np.stack([np.concatenate([g[k] for g in per], axis=axis) for per in got])
     units = prob.num_genes * ns
     S_ = HH * (HH + 1) // 2
     # 16 S^2 bytes of transition tables per gene (shared by the samples of a batch) + 64 S per gene x sample
@@ -800,6 +858,8 @@ def main():
 
     em = None
     path = "single-engine"
+    want_outputs = bool(args.dump_outputs) and rank == 0
+    outputs = {}
     path_note = None
     if (world > 1 or args.force_overlap_path) and not args.no_overlap and not args.merge:
         state, err = pipelined_setup(args, rank, world, torch, dist)
@@ -808,7 +868,8 @@ def main():
             dist.all_reduce(ok, op=dist.ReduceOp.MIN)
         if int(ok.item()) == 1:
             path = "pipelined"
-            em = em_bench_pipelined(args, rank, world, torch, dist, state)   # a failure here is fatal
+            em = em_bench_pipelined(args, rank, world, torch, dist, state,   # a failure here is fatal
+                                    want_outputs=want_outputs)
         else:
             if state is not None:
                 for e in state["engs"]:
@@ -819,7 +880,8 @@ def main():
             print(f"[bench] rank {rank}: {path_note}", file=sys.stderr, flush=True)
     want_full_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline and cpu_full_size(args)
     if em is None:
-        em = em_bench(args, rank, world, torch, dist, keep_host=want_full_cpu)
+        em = em_bench(args, rank, world, torch, dist, keep_host=want_full_cpu, want_outputs=want_outputs)
+    outputs.update(em.pop("outputs", None) or {})
     inf = em["info"]
     infos = em.get("infos", [inf])
     ms_per_step = em["dt"] / args.steps * 1e3
@@ -926,7 +988,7 @@ def main():
         if not args.no_replicas and not args.merge:
             line["replicas"] = replica_bench(args, rank, world, torch, dist)
         if not args.no_hmm:
-            line["hmm"] = hmm_bench_ranks(args, rank, world, torch, dist)
+            line["hmm"] = hmm_bench_ranks(args, rank, world, torch, dist, outputs=outputs if want_outputs else None)
     if rank == 0:
         if not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = em_cpu_baseline(args, em.pop("host", None))
@@ -975,9 +1037,13 @@ def main():
                              "priced_bytes": v_priced, "traffic": None},
                 "time_to_solution": v.get("solve"), "state_check": v.get("check")}
         if not args.no_hmm and world == 1:
-            line["hmm"] = hmm_bench(args, torch)
+            line["hmm"] = hmm_bench(args, torch, outputs=outputs if want_outputs else None)
         if e2e is not None:
             line["end_to_end"] = e2e
+        if want_outputs:
+            written = dump_outputs(args.dump_outputs, outputs)
+            print(f"[bench] wrote {', '.join(f'{k}{s}' for k, s in written.items())} to {args.dump_outputs}",
+                  file=sys.stderr, flush=True)
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()

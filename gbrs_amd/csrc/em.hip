@@ -460,6 +460,7 @@ csc_rowstat_kernel(uint64_t n, uint32_t ncols, uint32_t L, const uint64_t *__res
 }
 
 #include "em_tiles.inc"
+#include "em_models.inc"
 
 }  // namespace gbrs
 
@@ -527,6 +528,16 @@ struct gbrs_em {
     int pair_hist_cap = 0;
     hipEvent_t pair_ev_mstep = nullptr;    // recorded after every M-step of a handle in pair mode
     hipEvent_t pair_ev_err = nullptr;      // recorded after the pair's error pass (first handle)
+
+    // Multiread models 1-3 (gbrs_em_set_groups, em_models.inc).  Genes: the groups, then every locus in no group as a
+    // gene of its own; members ascending.  rank_* map a column h*L + l to its place in the sort order of model 1
+    // (gene, haplotype, locus) and of models 2/3 (gene, locus, haplotype); inv_* map it back to l*32 + h.
+    bool grouped = false;
+    uint32_t n_genes = 0;
+    DevBuf<uint32_t> gene_ptr, gene_mem, locus_gene, row_ptr;
+    DevBuf<uint32_t> rank_m1, inv_m1, rank_m23, inv_m23;
+    GroupedOrder order_m1, order_m23;               // built at the first step of a model that uses it
+    DevBuf<double> gene_tot, gene_hap_tot, locus_tot, fac;   // T (genes), Y (genes x H), U (L), per-entry factors (N)
 
     int red_blocks() const { return (int)std::min<uint64_t>(RED_BLOCKS, (L + RED_THREADS - 1) / RED_THREADS); }
 };
@@ -1016,6 +1027,62 @@ int em_ensure_hist(gbrs_em *em, int cap) {
     return GBRS_OK;
 }
 
+// ---- multiread models 1-3 (em_models.inc) ------------------------------------------------------------------------
+int em_check_model(const gbrs_em *em, int model) {
+    if (model < 1 || model > 4) return fail(GBRS_ERR_INVALID, "The read normalization model should be 1, 2, 3, or 4.");
+    if (model == 4) return GBRS_OK;
+    if (em->flags & GBRS_EM_DETERMINISTIC)
+        return fail(GBRS_ERR_UNSUPPORTED, "multiread model %d has no bit-reproducible form (GBRS_EM_DETERMINISTIC)", model);
+    if (!em->grouped)
+        return fail(GBRS_ERR_UNSUPPORTED, "multiread model %d needs gene groups: create the handle with "
+                                          "GBRS_EM_GROUPED_MODELS and call gbrs_em_set_groups", model);
+    return GBRS_OK;
+}
+
+int em_ensure_order(gbrs_em *em, int model) {
+    GroupedOrder &o = model == 1 ? em->order_m1 : em->order_m23;
+    if (o.built) return GBRS_OK;
+    GBRS_TRY(em_flush_err(em));
+    return build_grouped_order(o, em->R, em->L, em->H, em->N, em->ent_row.p, em->col_ptr.p,
+                               model == 1 ? em->rank_m1.p : em->rank_m23.p, model == 1 ? em->inv_m1.p : em->inv_m23.p,
+                               em->stream);
+}
+
+// One step of model 1, 2 or 3 (the order must be built); `ev` (3 events, nullable) times it as em_one_step does.
+int em_model_step(gbrs_em *em, int model, double target_err, hipEvent_t *ev = nullptr) {
+    GBRS_TRY(em_flush_err(em));
+    const GroupedOrder &o = model == 1 ? em->order_m1 : em->order_m23;
+    const bool timed = ev != nullptr && em->time_steps;
+    if (timed) GBRS_HIP_CHECK(hipEventRecord(ev[0], em->stream));
+    const uint32_t nt = std::max(em->L, em->n_genes);
+    hipLaunchKernelGGL(model_totals_kernel, dim3((nt + 255) / 256), dim3(256), 0, em->stream, em->L, em->H, em->n_genes,
+                       em->gene_ptr.p, em->gene_mem.p, em->theta.p, em->gene_tot.p, em->gene_hap_tot.p, em->locus_tot.p,
+                       em->scalars.p);
+    GBRS_HIP_CHECK(hipMemsetAsync(em->acc.p, 0, em->acc.bytes(), em->stream));
+    if (em->N) {
+        const dim3 rgrid((unsigned)((em->R + 255) / 256));
+        const double *cnt = em->has_count ? em->count.p : (const double *)nullptr;
+#define GBRS_LAUNCH_ROWS(M)                                                                                             \
+        hipLaunchKernelGGL(model_row_kernel<M>, rgrid, dim3(256), 0, em->stream, em->R, em->H, em->row_ptr.p, o.lh.p,   \
+                           o.src.p, em->locus_gene.p, em->theta.p, em->gene_tot.p, em->gene_hap_tot.p, em->locus_tot.p, \
+                           cnt, em->fac.p, em->scalars.p)
+        if (model == 1) GBRS_LAUNCH_ROWS(1);
+        else if (model == 2) GBRS_LAUNCH_ROWS(2);
+        else GBRS_LAUNCH_ROWS(3);
+#undef GBRS_LAUNCH_ROWS
+        hipLaunchKernelGGL(model_col_kernel, dim3((unsigned)((em->N + 255) / 256)), dim3(256), 0, em->stream, em->N,
+                           em->H * em->L, em->L, em->H, em->col_ptr.p, em->fac.p, em->acc.p, em->scalars.p);
+    }
+    GBRS_HIP_CHECK(hipGetLastError());
+    if (timed) GBRS_HIP_CHECK(hipEventRecord(ev[1], em->stream));
+    em->acc_needs_extra = false;
+    GBRS_TRY(em_finish_step(em, target_err, /* defer */ false, /* fused */ false));
+    // the tile layout's Model-4 steps write A only for the loci they have sums for and expect 0 elsewhere
+    if (em->layout == 1) GBRS_HIP_CHECK(hipMemsetAsync(em->acc.p, 0, em->acc.bytes(), em->stream));
+    if (timed) GBRS_HIP_CHECK(hipEventRecord(ev[2], em->stream));
+    return GBRS_OK;
+}
+
 // Concatenate the per-haplotype CSC arrays on the device: column id c = h*L + l, col_ptr[c] is the
 // offset of the column's first entry in ent_row.  Validates monotone indptr and (host inputs) row ids.
 // allowed (host, nullable): uint32[L], bit h set = the entries of (haplotype h, locus l) stay; the other columns
@@ -1210,13 +1277,15 @@ int em_create_impl(uint64_t R, uint32_t L, uint32_t H, const uint32_t *const *in
         // the CSC copy and the per-row denominators are only needed by layout 0 (and, until
         // gbrs_em_set_initial_values has run, when the caller announced stored values)
         em->keep_csc = (flags & GBRS_EM_KEEP_CSC) != 0;
+        // (models 1-3 build their layout from the row ids: GBRS_EM_GROUPED_MODELS keeps them)
+        const bool keep_rows = (flags & GBRS_EM_GROUPED_MODELS) != 0;
         if (!em->keep_csc) {
             if (em->tl.retain_temporaries) {  // one-shot process: left to the handle's destructor (common.h, DeferFrees)
                 DeferFrees with_the_layout(&em->tl.retired, &em->tl.retired_bytes);
-                em->ent_row.release();
+                if (!keep_rows) em->ent_row.release();
                 em->den.release();
             } else {
-                em->ent_row.release();
+                if (!keep_rows) em->ent_row.release();
                 em->den.release();
             }
         }
@@ -1397,7 +1466,7 @@ int gbrs_em_set_initial_values(gbrs_em_t *em, const double *const *values) {
     }
     em->has_init = true;
     if (em->layout == 1 && em->keep_csc) {     // the tiled layout needs neither array from here on
-        em->ent_row.release();
+        if (!(em->flags & GBRS_EM_GROUPED_MODELS)) em->ent_row.release();
         em->den.release();
         em->col_ptr_src.release();
         em->keep_csc = false;
@@ -1494,16 +1563,110 @@ int gbrs_em_step(gbrs_em_t *em, int n_iters, double *err_sum_out) {
     return GBRS_OK;
 }
 
+int gbrs_em_step_model(gbrs_em_t *em, int model, int n_iters, double *err_sum_out) {
+    RoctxRange roctx_range("gbrs_em_step_model");
+    if (!em) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    GBRS_TRY(em_check_model(em, model));
+    if (model == 4) return gbrs_em_step(em, n_iters, err_sum_out);
+    if (!em->prepared) return fail(GBRS_ERR_STATE, "prepare() has not been called");
+    GBRS_TRY(select_device(em->device));
+    if (em->stopped) GBRS_TRY(em_reset_scalars(em, true));     // as gbrs_em_step: a step asked for is applied
+    GBRS_TRY(em_ensure_order(em, model));
+    hipEvent_t ev[3] = {em->ev0, em->ev1, em->ev2};
+    for (int i = 0; i < n_iters; ++i) GBRS_TRY(em_model_step(em, model, -1.0, i == 0 ? ev : nullptr));
+    EmScalars host;
+    GBRS_TRY(em_check_float(em, host));
+    if (n_iters > 0) em_read_times(em);
+    if (err_sum_out) *err_sum_out = host.err_sum;
+    return GBRS_OK;
+}
+
+int gbrs_em_set_groups(gbrs_em_t *em, int64_t G, const int64_t *group_ptr, const int64_t *members) {
+    RoctxRange roctx_range("gbrs_em_set_groups");
+    if (!em || G < 0 || (G > 0 && (!group_ptr || !members))) return fail(GBRS_ERR_INVALID, "bad argument");
+    if (!(em->flags & GBRS_EM_GROUPED_MODELS))
+        return fail(GBRS_ERR_STATE, "the handle was not created with GBRS_EM_GROUPED_MODELS");
+    if (em->N && !em->ent_row.p) return fail(GBRS_ERR_STATE, "the handle no longer holds the CSC row ids");
+    const uint32_t L = em->L, H = em->H;
+    if (em->N >= 0xFFFFFFFFull || L >= (1u << 27))
+        return fail(GBRS_ERR_UNSUPPORTED, "the grouped layout holds at most 2^32 - 1 entries of at most 2^27 loci");
+    if (G > 0 && group_ptr[0] != 0) return fail(GBRS_ERR_INVALID, "group_ptr[0] != 0");
+    for (int64_t g = 0; g < G; ++g)
+        if (group_ptr[g + 1] < group_ptr[g]) return fail(GBRS_ERR_INVALID, "group_ptr not monotone");
+    GBRS_TRY(select_device(em->device));
+    // genes: the groups in order (members ascending, a repeat inside a group counted once), then every locus in no
+    // group as a gene of its own, in locus order
+    std::vector<int64_t> gene(L, -1);
+    std::vector<std::vector<uint32_t>> mem((size_t)G);
+    for (int64_t g = 0; g < G; ++g)
+        for (int64_t k = group_ptr[g]; k < group_ptr[g + 1]; ++k) {
+            const int64_t l = members[k];
+            if (l < 0 || l >= (int64_t)L) return fail(GBRS_ERR_INVALID, "group member %lld out of range", (long long)l);
+            if (gene[l] == g) continue;
+            if (gene[l] >= 0)
+                return fail(GBRS_ERR_INVALID, "locus %lld is in two groups (%lld and %lld)", (long long)l,
+                            (long long)gene[l], (long long)g);
+            gene[l] = g;
+            mem[g].push_back((uint32_t)l);
+        }
+    std::vector<uint32_t> gptr{0}, gmem, lgene(L), pos(L);
+    gmem.reserve(L);
+    for (int64_t g = 0; g < G; ++g) {
+        std::sort(mem[g].begin(), mem[g].end());
+        for (uint32_t l : mem[g]) { lgene[l] = (uint32_t)(gptr.size() - 1); pos[l] = (uint32_t)gmem.size(); gmem.push_back(l); }
+        gptr.push_back((uint32_t)gmem.size());
+    }
+    for (uint32_t l = 0; l < L; ++l)
+        if (gene[l] < 0) { lgene[l] = (uint32_t)(gptr.size() - 1); pos[l] = (uint32_t)gmem.size(); gmem.push_back(l); gptr.push_back((uint32_t)gmem.size()); }
+    const uint32_t n_genes = (uint32_t)(gptr.size() - 1);
+    // sort ranks of the columns: (gene, locus, haplotype) = pos*H + h; (gene, haplotype, locus) inside the gene's block
+    const size_t HL = (size_t)H * L;
+    std::vector<uint32_t> r23(HL), i23(HL), r1(HL), i1(HL);
+    for (uint32_t l = 0; l < L; ++l) {
+        const uint32_t g = lgene[l], start = gptr[g], size = gptr[g + 1] - start;
+        for (uint32_t h = 0; h < H; ++h) {
+            const uint32_t a = pos[l] * H + h, b = start * H + h * size + (pos[l] - start);
+            r23[(size_t)h * L + l] = a;
+            i23[a] = l * 32u + h;
+            r1[(size_t)h * L + l] = b;
+            i1[b] = l * 32u + h;
+        }
+    }
+    em->grouped = false;
+    em->order_m1.built = em->order_m23.built = false;
+    auto up = [&](DevBuf<uint32_t> &d, const std::vector<uint32_t> &v) -> int {
+        GBRS_TRY(d.alloc(std::max<size_t>(v.size(), 1)));
+        if (!v.empty()) GBRS_HIP_CHECK(hipMemcpyAsync(d.p, v.data(), v.size() * 4, hipMemcpyHostToDevice, em->stream));
+        return GBRS_OK;
+    };
+    GBRS_TRY(up(em->gene_ptr, gptr));
+    GBRS_TRY(up(em->gene_mem, gmem));
+    GBRS_TRY(up(em->locus_gene, lgene));
+    GBRS_TRY(up(em->rank_m23, r23));
+    GBRS_TRY(up(em->inv_m23, i23));
+    GBRS_TRY(up(em->rank_m1, r1));
+    GBRS_TRY(up(em->inv_m1, i1));
+    GBRS_TRY(em->gene_tot.alloc(n_genes));
+    GBRS_TRY(em->gene_hap_tot.alloc((size_t)n_genes * H));
+    GBRS_TRY(em->locus_tot.alloc(L));
+    GBRS_TRY(em->fac.alloc(std::max<uint64_t>(em->N, 1)));
+    GBRS_HIP_CHECK(hipStreamSynchronize(em->stream));       // (the host vectors go out of scope)
+    em->n_genes = n_genes;
+    GBRS_TRY(build_row_ptr(em->row_ptr, em->R, em->N, em->ent_row.p, em->stream));
+    GBRS_TRY(build_grouped_order(em->order_m23, em->R, L, H, em->N, em->ent_row.p, em->col_ptr.p, em->rank_m23.p,
+                                 em->inv_m23.p, em->stream));
+    em->grouped = true;
+    return GBRS_OK;
+}
+
 int gbrs_em_run(gbrs_em_t *em, int model, double tol, int max_iters, int *n_iters_out,
                 double *err_hist, int err_hist_cap, double *elapsed_s) {
     RoctxRange roctx_range("gbrs_em_run");
     if (!em) return fail(GBRS_ERR_INVALID, "handle is NULL");
-    if (model < 1 || model > 4)
-        return fail(GBRS_ERR_INVALID, "The read normalization model should be 1, 2, 3, or 4.");
-    if (model != 4)
-        return fail(GBRS_ERR_UNSUPPORTED, "multiread model %d is not implemented by the HIP path (only Model 4)", model);
+    GBRS_TRY(em_check_model(em, model));
     if (!em->prepared) return fail(GBRS_ERR_STATE, "prepare() has not been called");
     GBRS_TRY(select_device(em->device));
+    if (model != 4) GBRS_TRY(em_ensure_order(em, model));
     if (max_iters < 0) max_iters = 0;
     GBRS_TRY(em_ensure_hist(em, std::max(max_iters, 1)));
     GBRS_TRY(em_reset_scalars(em, false));
@@ -1523,7 +1686,8 @@ int gbrs_em_run(gbrs_em_t *em, int model, double tol, int max_iters, int *n_iter
             const int nb = std::min(batch, max_iters - done);
             hipEvent_t ev[3] = {em->ev0, em->ev1, em->ev2};
             for (int i = 0; i < nb; ++i) {     // the run's first step is timed; a batch's last error pass is not deferred
-                GBRS_TRY(em_one_step(em, target, first ? ev : nullptr, i + 1 < nb));
+                if (model == 4) GBRS_TRY(em_one_step(em, target, first ? ev : nullptr, i + 1 < nb));
+                else GBRS_TRY(em_model_step(em, model, target, first ? ev : nullptr));
                 first = false;
             }
             GBRS_TRY(em_check_float(em, host));

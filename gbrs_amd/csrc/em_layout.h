@@ -173,6 +173,20 @@ int build_tile_layout(TileLayout &out, uint64_t R, uint32_t L, uint32_t H, uint6
 // E-step kernel (theta row and sums in registers, 0/1 doubles from the LDS tables, six waves per SIMD) instead of the
 // 16-haplotype one (128 registers, four waves per SIMD, theta from LDS for every word).
 
+// Grouped row layout of multiread models 1-3 (em_models.inc, gbrs_em_set_groups): the stored entries sorted by
+// (row, rank), rank[c] a position in [0, H*L) the caller gives every column c = h*L + l (gene-major, so a read's
+// entries of one gene - and inside it of one locus, or of one haplotype - are contiguous).  row_ptr (R + 1) is shared by
+// every order of one handle (the rows are the primary key).
+struct GroupedOrder {
+    DevBuf<uint32_t> lh;     // N: l * 32 + h of the sorted entry
+    DevBuf<uint32_t> src;    // N: its index in the CSC arrays (where the row pass stores its factor)
+    bool built = false;
+};
+int build_row_ptr(DevBuf<uint32_t> &row_ptr, uint64_t R, uint64_t N, const uint32_t *ent_row, hipStream_t s);
+// rank / rank_lh: DEVICE uint32[H*L], column -> rank and rank -> l * 32 + h.  Needs N < 2^32 and L < 2^27.
+int build_grouped_order(GroupedOrder &out, uint64_t R, uint32_t L, uint32_t H, uint64_t N, const uint32_t *ent_row,
+                        const uint64_t *col_ptr, const uint32_t *rank, const uint32_t *rank_lh, hipStream_t s);
+
 // `gbrs compress`: equivalence classes of identical rows, in first-seen order.
 struct CompressResult {
     uint64_t num_ecs = 0, n_entries = 0;

@@ -1718,6 +1718,84 @@ return GBRS_OK;
 
 }  // namespace gbrs
 
+// ---- grouped row layout of multiread models 1-3 ----------------------------------------------------------------------
+namespace gbrs {
+namespace {
+
+__global__ void __launch_bounds__(256)
+row_hist_kernel(uint64_t n, const uint32_t *__restrict__ ent_row, uint32_t *__restrict__ cnt) {
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n) atomicAdd(&cnt[ent_row[k]], 1u);
+}
+
+// key = row << rank_bits | rank[column], value = the entry's CSC index
+__global__ void __launch_bounds__(256)
+grouped_key_kernel(uint64_t n, uint32_t ncols, const uint64_t *__restrict__ col_ptr, const uint32_t *__restrict__ ent_row,
+                   const uint32_t *__restrict__ rank, unsigned rank_bits, uint64_t *__restrict__ key,
+                   uint32_t *__restrict__ val) {
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k - (threadIdx.x & 63) >= n) return;
+    const bool live = k < n;
+    const uint32_t c = entry_column(col_ptr, ncols, live ? k : n - 1, n);
+    if (!live) return;
+    key[k] = ((uint64_t)ent_row[k] << rank_bits) | rank[c];
+    val[k] = (uint32_t)k;
+}
+
+__global__ void __launch_bounds__(256)
+grouped_lh_kernel(uint64_t n, const uint64_t *__restrict__ key, uint64_t mask, const uint32_t *__restrict__ rank_lh,
+                  uint32_t *__restrict__ lh) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n) lh[j] = rank_lh[key[j] & mask];
+}
+
+}  // namespace
+
+int build_row_ptr(DevBuf<uint32_t> &row_ptr, uint64_t R, uint64_t N, const uint32_t *ent_row, hipStream_t s) {
+    Scratch sc;
+    DevBuf<uint32_t> cnt;
+    GBRS_TRY(cnt.alloc(R + 1));
+    GBRS_TRY(row_ptr.alloc(R + 1));
+    GBRS_HIP_CHECK(hipMemsetAsync(cnt.p, 0, cnt.bytes(), s));
+    if (N) hipLaunchKernelGGL(row_hist_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, N, ent_row, cnt.p);
+    GBRS_HIP_CHECK(hipGetLastError());
+    GBRS_TRY(exclusive_scan(sc, cnt.p, row_ptr.p, R + 1, s));      // (the last count is 0: row_ptr[R] = N)
+    GBRS_HIP_CHECK(hipStreamSynchronize(s));
+    return GBRS_OK;
+}
+
+int build_grouped_order(GroupedOrder &out, uint64_t R, uint32_t L, uint32_t H, uint64_t N, const uint32_t *ent_row,
+                        const uint64_t *col_ptr, const uint32_t *rank, const uint32_t *rank_lh, hipStream_t s) {
+    out.built = false;
+    if (N >= 0xFFFFFFFFull || L >= (1u << 27))
+        return fail(GBRS_ERR_UNSUPPORTED, "the grouped layout holds at most 2^32 - 1 entries of at most 2^27 loci");
+    GBRS_TRY(out.lh.alloc(std::max<uint64_t>(N, 1)));
+    GBRS_TRY(out.src.alloc(std::max<uint64_t>(N, 1)));
+    if (N) {
+        const uint32_t ncols = H * L;
+        const unsigned rank_bits = bits_for(ncols - 1), end_bit = rank_bits + bits_for(R - 1);
+        Scratch sc;
+        DevBuf<uint64_t> kin, kout;
+        DevBuf<uint32_t> vin;
+        GBRS_TRY(kin.alloc(N));
+        GBRS_TRY(kout.alloc(N));
+        GBRS_TRY(vin.alloc(N));
+        const unsigned grid = (unsigned)((N + 255) / 256);
+        hipLaunchKernelGGL(grouped_key_kernel, dim3(grid), dim3(256), 0, s, N, ncols, col_ptr, ent_row, rank, rank_bits,
+                           kin.p, vin.p);
+        GBRS_HIP_CHECK(hipGetLastError());
+        GBRS_TRY(sort_pairs(sc, kin.p, kout.p, vin.p, out.src.p, N, end_bit, s));
+        hipLaunchKernelGGL(grouped_lh_kernel, dim3(grid), dim3(256), 0, s, N, kout.p, (uint64_t(1) << rank_bits) - 1,
+                           rank_lh, out.lh.p);
+        GBRS_HIP_CHECK(hipGetLastError());
+        GBRS_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    out.built = true;
+    return GBRS_OK;
+}
+
+}  // namespace gbrs
+
 // gbrs_warm_up (common.hip): loads this file's code object
 namespace gbrs {
 __global__ void warm_layout_kernel() {}

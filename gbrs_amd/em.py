@@ -1,10 +1,10 @@
 """EMfactory: the reference's EM driver interface backed by libgbrs_hip.so.
 
 Same constructor, method names, argument meaning, printed progress table and error behaviour as
-emase/EMfactory.py:15-392 for the Model-4 path that `gbrs quantify` drives
-(gbrs/emase_utils.py:282-316).  All arithmetic of prepare / run happens in HIP kernels through
-the C ABI in include/gbrs_hip.h; this module never computes an EM quantity on the host and has
-no CPU fallback.
+emase/EMfactory.py:15-392 for the paths that `gbrs quantify` drives
+(gbrs/emase_utils.py:282-316): Model 4, and models 1-3 (`-M 1|2|3`, which need gene groups).  All
+arithmetic of prepare / run happens in HIP kernels through the C ABI in include/gbrs_hip.h; this
+module never computes an EM quantity on the host and has no CPU fallback.
 """
 from __future__ import annotations
 
@@ -21,16 +21,17 @@ class EMfactory:
 
     def __init__(self, alignments, device: int = 0, merge_identical_rows: bool = False,
                  csc_layout: bool = False, extra_flags: int = 0, deterministic: bool = False,
-                 one_shot: bool = False):
+                 one_shot: bool = False, grouped_models: bool = False):
         self.probability = alignments
         self.grp_conv_mat = None          # kept for attribute parity; groups live in probability
-        self.t2t_mat = None               # Models 1-3 only (EMfactory.py:48-59): never built
+        self.t2t_mat = None               # Models 1-3 (EMfactory.py:48-59): the device holds the groups instead
         self.target_lengths = None
         self.device = device
         self.flags = (_lib.GBRS_EM_MERGE_IDENTICAL_ROWS if merge_identical_rows else 0) | \
                      (_lib.GBRS_EM_LAYOUT_CSC if csc_layout else 0) | \
                      (_lib.GBRS_EM_DETERMINISTIC if deterministic else 0) | \
-                     (_lib.GBRS_EM_ONE_SHOT if one_shot else 0) | int(extra_flags)   # tuning switches of gbrs_hip.h
+                     (_lib.GBRS_EM_ONE_SHOT if one_shot else 0) | \
+                     (_lib.GBRS_EM_GROUPED_MODELS if grouped_models else 0) | int(extra_flags)   # tuning switches of gbrs_hip.h
         self._h = None
         self._theta = None                # host copy of allelic_expression (H x L)
         self._theta_dirty = False         # host copy edited, device not yet updated
@@ -64,6 +65,9 @@ class EMfactory:
             # the file stores alignment values: they fix the starting point (EMfactory.py:95-98)
             vals = [np.ascontiguousarray(v, dtype=np.float64) for v in vals]
             _lib.check(lib.gbrs_em_set_initial_values(h, _lib.ptr_table(vals)))
+        if (self.flags & _lib.GBRS_EM_GROUPED_MODELS) and apm.num_groups:
+            gptr, mem = apm.group_csr()
+            _lib.check(lib.gbrs_em_set_groups(h, int(apm.num_groups), _lib.ptr(gptr), _lib.ptr(mem)))
 
     def close(self):
         if self._h is not None:
@@ -157,17 +161,29 @@ class EMfactory:
         """A single EM step (EMfactory.py:214-232)."""
         self._check_model(model)
         self._require()
+        self._ready_for(model)
         self._push()
-        _lib.check(_lib.load().gbrs_em_step(self._h, 1, None))
+        lib = _lib.load()
+        _lib.check(lib.gbrs_em_step(self._h, 1, None) if model == 4 else lib.gbrs_em_step_model(self._h, int(model), 1, None))
         self._theta = None
 
-    @staticmethod
-    def _check_model(model):
+    def _check_model(self, model):
         if model not in (1, 2, 3, 4):
             raise RuntimeError('The read normalization model should be 1, 2, 3, or 4.')
-        if model != 4:
-            raise RuntimeError(f'Multiread model {model} is not implemented by the MI355X path '
-                               '(only Model 4: Gene*Isoform*Allele).')
+        if model != 4 and not self.probability.num_groups:
+            # the reference's normalize_reads raises the first part (AlignmentPropertyMatrix.py:348)
+            raise RuntimeError(f'Group information matrix is missing: multiread model {model} is not implemented '
+                               'without gene groups.')
+
+    def _ready_for(self, model):
+        """Models 1-3 step on the grouped layout: a handle built without it is rebuilt once, theta carried over."""
+        if model == 4 or (self.flags & _lib.GBRS_EM_GROUPED_MODELS):
+            return
+        theta = self.allelic_expression.copy()
+        self.flags |= _lib.GBRS_EM_GROUPED_MODELS
+        self.close()
+        self._create()
+        self.allelic_expression = theta
 
     def run(self, model: int, tol: float = 0.001, max_iters: int = 999, verbose: bool = True) -> None:
         """Runs EM iterations (EMfactory.py:234-287): the whole loop, stopping rule included, executes
@@ -175,6 +191,7 @@ class EMfactory:
         np.seterr(all='raise', under='ignore')      # the state the reference leaves numpy in
         self._check_model(model)
         self._require()
+        self._ready_for(model)
         self._push()
         cap = max(int(max_iters), 1)
         hist = np.zeros(cap, dtype=np.float64)

@@ -295,7 +295,8 @@ def quantify(alignment_file: str, group_file: str = None, length_file: str = Non
 
     logger.info('Running EMASE')
     t0 = clock()
-    em = EMfactory(aln_mat, device=device, merge_identical_rows=merge_identical_rows, one_shot=one_shot)
+    em = EMfactory(aln_mat, device=device, merge_identical_rows=merge_identical_rows, one_shot=one_shot,
+                   grouped_models=multiread_model != 4)
     if target_lengths is not None:
         em.set_target_lengths(target_lengths)
         em.prepare(pseudocount=pseudocount)

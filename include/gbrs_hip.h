@@ -40,7 +40,8 @@ enum gbrs_status {
     GBRS_ERR_NO_DEVICE = -3,    /* no gfx950 device visible: there is NO CPU fallback      */
     GBRS_ERR_FLOAT = -4,        /* 0/0 or overflow where the reference's np.seterr(all='raise')
                                    (EMfactory.py:256) raises FloatingPointError              */
-    GBRS_ERR_UNSUPPORTED = -5,  /* models 1-3 (EMfactory.py:160-203): out of scope         */
+    GBRS_ERR_UNSUPPORTED = -5,  /* not available on this handle or in this mode: models 1-3
+                                   without gbrs_em_set_groups, or with GBRS_EM_DETERMINISTIC */
     GBRS_ERR_STATE = -6         /* call order violated (e.g. run before prepare)           */
 };
 
@@ -107,6 +108,9 @@ typedef struct gbrs_em gbrs_em_t;
  * (count given or identical rows merged); gbrs_em_info.num_locus_sets says how many it found (0: not taken).  The flag keeps one word per
  * (read, locus) pair whatever the sample. */
 #define GBRS_EM_NO_LOCUS_SETS 512u
+/* Multiread models 1-3 (EMfactory.py:160-203): the handle keeps the CSC row ids after create, so that
+ * gbrs_em_set_groups can build the grouped row layout those models step on.  Model 4 is unaffected. */
+#define GBRS_EM_GROUPED_MODELS 1024u
 
 /*
  * Replaces: AlignmentPropertyMatrix(h5file=...) as consumed by EMfactory.__init__
@@ -168,7 +172,25 @@ int gbrs_em_prepare(gbrs_em_t *em, double pseudocount);
  * at the stopping rule; err_sum_out (nullable) receives the last step's total TPM change. */
 int gbrs_em_step(gbrs_em_t *em, int n_iters, double *err_sum_out);
 
-/* Replaces EMfactory.run (EMfactory.py:234-287).  model must be 4.  Stops when
+/* Gene groups for multiread models 1-3 (handle created with GBRS_EM_GROUPED_MODELS, else GBRS_ERR_STATE).
+ * group_ptr int64[G+1], members int64[..] locus ids, as for gbrs_em_group_sums; a locus in no group is a gene of
+ * its own (EMfactory.py:48-59: t2t_mat is the identity there).  A locus in two groups is GBRS_ERR_INVALID.
+ * Builds the grouped row layout on the device: every stored entry (after a `-G` mask) sorted by (read, gene,
+ * locus, haplotype), or by (read, gene, haplotype, locus) for Model 1 (built at its first step). */
+int gbrs_em_set_groups(gbrs_em_t *em, int64_t num_groups, const int64_t *group_ptr, const int64_t *members);
+
+/* n_iters EM steps of multiread model `model` (1-4; 4 is gbrs_em_step).  With the factor
+ *   f = 1 (model 4), T_g / S[r,g] (3), U_l T_g / (V[r,l] W[r,g]) (2), Y[h,g] T_g / (X[r,g,h] Z[r,g]) (1)
+ * of a stored entry (read r, haplotype h, locus l in gene g) and D_r = sum of T_g over the genes read r touches,
+ *   A[h,l] = sum_r count[r] f / D_r,  theta' = theta * A / len,  expected counts = theta * A,
+ * where T_g, Y[h,g], U_l are gene, gene-haplotype and locus totals of theta and S, V, W, X, Z the sums of theta
+ * over a read's entries of one gene / one locus, of U over the loci / of Y over the haplotypes a read touches in a
+ * gene, of theta over a read's entries of one gene and haplotype.  An entry whose theta is 0 takes no
+ * part (the reference eliminates zeros before each division).  Models 1-3 need gbrs_em_set_groups
+ * (GBRS_ERR_UNSUPPORTED without it, or with GBRS_EM_DETERMINISTIC). */
+int gbrs_em_step_model(gbrs_em_t *em, int model, int n_iters, double *err_sum_out);
+
+/* Replaces EMfactory.run (EMfactory.py:234-287).  model 1-4 (1-3: see gbrs_em_step_model).  Stops when
  * err_sum <= 1e6*tol or after max_iters steps.  err_hist (nullable) receives up to
  * err_hist_cap per-iteration err_sum values (the numbers the reference prints); elapsed_s (nullable,
  * same capacity) the wall-clock seconds since the start of the run at which each iteration was

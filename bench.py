@@ -10,16 +10,24 @@ DO-shaped sample of BASELINE.json configs[1]: 40M reads x 8 haplotypes x 120k is
 (SURVEY.md §8d generator), resident in HBM before the timed region.  With N > 1 every rank holds
 its own 40M-read shard of a pooled sample (reads sharded, weak scaling) and the ranks exchange
 the H*L expected-count vector with one RCCL all-reduce per iteration; the value
-reported is shard-iterations/s summed over ranks.  The N > 1 line also carries `replicas` (configs[3] as
-SURVEY §8e reads it: one independent sample per GPU, samples/s, no collective), `time_to_solution` through the
-same multi-rank driver, and `hmm` (every rank its own samples, aggregate genes/s, no collective).
+reported is shard-iterations/s summed over ranks.
 
-The same line carries `roofline` (E-step kernel, HIP-event time measured in the library on its
-own stream), `cpu_baseline` (the numpy oracle, 1 core, bounded sample) and an `hmm` object with
-the reconstruct numbers for BASELINE.json configs[2].
+A plain run does what that headline needs and nothing else: it builds the sample and its layout, warms up, times the K
+steps, writes --dump-outputs and prints the line, which carries the setup times, the state check of the timed steps and
+`roofline` (E-step kernel, HIP-event time of the timed steps measured in the library on its own stream: the
+single-engine path at N = 1).
+
+--full adds everything else, each part skipped again by its --no-* switch: the end-to-end `gbrs quantify` +
+`gbrs reconstruct` pipeline, `time_to_solution`, the tiles-vs-CSC comparison in `state_check`, `cpu_baseline` (the
+numpy oracle, 1 core), the merged-rows and multi-isoform EM lines and an `hmm` object with the reconstruct numbers for
+BASELINE.json configs[2].  At N > 1 it adds `replicas` (configs[3] as SURVEY §8e reads it: one independent sample per GPU,
+samples/s, no collective), `time_to_solution` through the same multi-rank driver, `hmm` (every rank its own samples,
+aggregate genes/s, no collective); there and on the two-engine path it adds the per-launch E-step time behind
+`roofline`.
 
 --dump-outputs DIR writes what the timed paths computed in their last step (EM theta and expected counts, HMM posteriors,
-Viterbi path and calls) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
+Viterbi path and calls) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.  A
+plain run makes the one-sample HMM pass only for these arrays, the same pass and sample that --full reports.
 """
 from __future__ import annotations
 
@@ -48,6 +56,9 @@ def parse():
                     help="untimed EM steps for this long in front of the W warmup steps, so that the K timed steps run at the clock the "
                          "chip settles on under this load (it needs ~25 ms, profiles/r03_short_run_clock.txt); the K steps after W "
                          "warmup steps on the chip as the setup left it are timed first and reported as `cold_start`; 0 = only those")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline as well (see the module docstring; several "
+                         "minutes at N = 1); the --no-* switches below skip parts of it")
     ap.add_argument("--rows", type=int, default=40_000_000, help="reads per GPU")
     ap.add_argument("--haps", type=int, default=8)
     ap.add_argument("--loci", type=int, default=120_000)
@@ -241,7 +252,7 @@ def em_bench(args, rank, world, torch, dist, keep_host=False, want_outputs=False
         res["outputs"] = dict(em_theta=eng.theta(), em_expected_counts=eng.expected_counts())
     # ---- outside the timed region: is the state the timed steps produced a valid EM state? ----------
     res["check"] = em_state_check(torch, [eng.expected_counts()], float(args.rows) * world)
-    if world == 1 and not args.no_check:
+    if args.full and world == 1 and not args.no_check:
         # the same sample through the plain CSC kernels (two passes, global atomics: a different code
         # path with a different summation order) must give the same theta after 3 iterations
         import numpy as np
@@ -263,7 +274,7 @@ def em_bench(args, rank, world, torch, dist, keep_host=False, want_outputs=False
         # put the engine back where the timed steps left off is not needed: what follows re-prepares
     del prob
     torch.cuda.empty_cache()
-    if world == 1 and not args.merge:
+    if args.full and world == 1 and not args.merge:
         # time to solution with the reference's default stopping rule (tol = 1e-4 TPM units)
         eng.prepare(0.0)
         torch.cuda.synchronize()
@@ -271,7 +282,7 @@ def em_bench(args, rank, world, torch, dist, keep_host=False, want_outputs=False
         n_it, hist = eng.run(model=4, tol=1e-4, max_iters=999)
         res["solve"] = dict(iterations=n_it, ms=(time.perf_counter() - t1) * 1e3,
                             final_err_sum=float(hist[-1]) if n_it else None)
-    if use_dist and world > 1 and not args.no_solve:
+    if args.full and use_dist and world > 1 and not args.no_solve:
         # N > 1 on one engine per GPU: gbrs_amd.dist.ShardedEM with the all-reduce in line on the engine's stream
         from gbrs_amd.dist import ShardedEM
 
@@ -296,6 +307,8 @@ def em_bench(args, rank, world, torch, dist, keep_host=False, want_outputs=False
     if world == 1:
         res["estep_ms"] = inf.last_estep_ms
         res["step_ms"] = inf.last_step_ms
+    elif not args.full:
+        res["estep_ms"] = res["step_ms"] = None
     else:
         # per-launch E-step time: one un-pipelined timed step group without the collective
         eng.step(min(args.steps, 10))
@@ -448,7 +461,7 @@ def em_bench_pipelined(args, rank, world, torch, dist, state, want_outputs=False
     # time to solution through the same two-engine loop: prepare, then the reference's stopping rule (EMfactory.py:266-278)
     # over both locus ranges on the device (gbrs_em_pair_check), looked at every 8 iterations; max over ranks
     solve = None
-    if not args.no_solve:
+    if args.full and not args.no_solve:
         drv.prepare(0.0)
         barrier()
         t1 = time.perf_counter()
@@ -462,15 +475,16 @@ def em_bench_pipelined(args, rank, world, torch, dist, state, want_outputs=False
         solve = dict(iterations=n_it, ms=ms, final_err_sum=drv.err_history[-1] if drv.err_history else None,
                      path="PipelinedShardedEM.run (two engines per rank, pair stopping rule on the device)",
                      rows_in_the_pool=args.rows * world)
-    # per-launch E-step time of the two halves: local steps without the collective
-    estep_ms = step_ms = 0.0
-    infos = []
-    for e in engs:
-        e.step(min(args.steps, 10))
-        inf = e.info()
-        estep_ms += inf.last_estep_ms
-        step_ms += inf.last_step_ms
-        infos.append(inf)
+    # per-launch E-step time of the two halves (--full): local steps without the collective
+    estep_ms = step_ms = None
+    if args.full:
+        estep_ms = step_ms = 0.0
+        for e in engs:
+            e.step(min(args.steps, 10))
+            inf = e.info()
+            estep_ms += inf.last_estep_ms
+            step_ms += inf.last_step_ms
+    infos = [e.info() for e in engs]
     for e in engs:
         e.close()
     return dict(dt=dt, region=region, t_gen=state["t_gen"], t_create=state["t_create"], t_create_host=None, N=state["N"],
@@ -809,7 +823,7 @@ def main():
     if world != args.gpus:
         raise SystemExit(f"bench.py: --gpus {args.gpus} but the launcher started WORLD_SIZE={world} ranks")
     e2e = None
-    if world == 1 and not args.no_e2e and not args.merge and args.rows == 40_000_000 and args.haps == 8 \
+    if args.full and world == 1 and not args.no_e2e and not args.merge and args.rows == 40_000_000 and args.haps == 8 \
             and args.variant == "survey":
         # End-to-end `gbrs quantify` + `gbrs reconstruct` (file in -> reports out) as fresh child processes,
         # measured BEFORE this process opens the GPU: a second process holding a device context slows the
@@ -878,7 +892,7 @@ def main():
             torch.cuda.empty_cache()
             path_note = f"two-engine setup declined on some rank (this rank: {err}); one engine per GPU"
             print(f"[bench] rank {rank}: {path_note}", file=sys.stderr, flush=True)
-    want_full_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline and cpu_full_size(args)
+    want_full_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and cpu_full_size(args)
     if em is None:
         em = em_bench(args, rank, world, torch, dist, keep_host=want_full_cpu, want_outputs=want_outputs)
     outputs.update(em.pop("outputs", None) or {})
@@ -890,7 +904,7 @@ def main():
     moved = sum(int(i.bytes_per_iter) for i in infos)
     estep_bytes = sum(int(i.estep_bytes) for i in infos)
     words = sum(int(i.num_device_words) for i in infos)
-    estep_s = em["estep_ms"] * 1e-3
+    estep_s = (em["estep_ms"] or 0.0) * 1e-3             # None: N > 1 without --full (no per-launch E-step time)
     # price on min(B_iter, bytes actually moved) so a smaller device format never inflates the fraction
     priced_estep = min(algo, estep_bytes)
     priced_step = min(algo, moved)
@@ -983,19 +997,19 @@ def main():
                     line["roofline"][k] = pt[key][k]
     except (OSError, ValueError):
         pass
-    if world > 1:
+    if args.full and world > 1:
         # the rest of BASELINE.json's metric at N > 1 (every rank takes part: the timings are max-over-ranks)
         if not args.no_replicas and not args.merge:
             line["replicas"] = replica_bench(args, rank, world, torch, dist)
         if not args.no_hmm:
             line["hmm"] = hmm_bench_ranks(args, rank, world, torch, dist, outputs=outputs if want_outputs else None)
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = em_cpu_baseline(args, em.pop("host", None))
             line["speedup_vs_cpu"] = value / line["cpu_baseline"]["value"]
-        elif world > 1:
+        elif args.full and world > 1:
             line["cpu_baseline"] = None        # rank 0 at N = 1 only (the driver's N = 1 run carries it)
-        if not args.merge and not args.no_merged_line and world == 1:
+        if args.full and not args.merge and not args.no_merged_line and world == 1:
             import copy
             a2 = copy.copy(args)
             a2.merge = True
@@ -1009,7 +1023,7 @@ def main():
                 "estep_kernel_ms": m["estep_ms"], "device_rows": int(m["info"].num_device_rows),
                 "device_words": int(m["info"].num_device_words), "layout_bytes": int(m["info"].bytes_per_iter),
                 "state_check": m.get("check")}
-        if not args.merge and not args.no_multi_isoform_line and world == 1 and args.variant == "survey":
+        if args.full and not args.merge and not args.no_multi_isoform_line and world == 1 and args.variant == "survey":
             import copy
             a3 = copy.copy(args)
             a3.variant = "multi_isoform"
@@ -1036,8 +1050,12 @@ def main():
                              "frac": v_priced / v_estep_s / 1e9 / HBM_PEAK_GBS if v_estep_s > 0 else None,
                              "priced_bytes": v_priced, "traffic": None},
                 "time_to_solution": v.get("solve"), "state_check": v.get("check")}
-        if not args.no_hmm and world == 1:
+        if args.full and not args.no_hmm and world == 1:
             line["hmm"] = hmm_bench(args, torch, outputs=outputs if want_outputs else None)
+        elif not args.full and not args.no_hmm and want_outputs:
+            # a plain run makes the HMM pass only for the arrays --dump-outputs writes: the pass and sample (rank 0's) whose
+            # outputs --full writes, none of its figures in the line
+            hmm_bench(args, torch, ns=None if world == 1 else 1, with_cpu=False, outputs=outputs)
         if e2e is not None:
             line["end_to_end"] = e2e
         if want_outputs:

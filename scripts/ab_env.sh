@@ -6,7 +6,7 @@ shift 2
 i=0
 for X in "${VARS[@]}"; do
   for rep in a b; do
-  env $X timeout -k 10 300 python bench.py --no-e2e --no-cpu-baseline --no-hmm --no-merged-line --no-multi-isoform-line "$@" > $OUT/v${i}_$rep.log 2>&1
+  env $X timeout -k 10 300 python bench.py --full --no-e2e --no-cpu-baseline --no-hmm --no-merged-line --no-multi-isoform-line "$@" > $OUT/v${i}_$rep.log 2>&1
   python - "$X" "$OUT/v${i}_$rep.log" <<'PY'
 import json, sys
 try:

@@ -8,7 +8,7 @@ i=0
 for X in ${GBRS_ABLATIONS:-"-DGBRS_FULL" "-DGBRS_ABLATE_ATOMICS" "-DGBRS_ABLATE_FLUSH" "-DGBRS_ABLATE_ROWSUM" "-DGBRS_ABLATE_BATCHES" "-DGBRS_ABLATE_PROLOGUE"}; do
   N=v${i}_$(echo "$X" | sed 's/-DGBRS_//g; s/ABLATE_//g; s/ /+/g')
   GBRS_HIPCC_EXTRA="$X" python -c "import __graft_entry__ as g; g.build()" > /dev/null 2>&1
-  timeout -k 10 200 python bench.py --steps 200 --warmup 20 --no-e2e --no-check --no-hmm --no-cpu-baseline --no-merged-line > $OUT/${N}.log 2>&1
+  timeout -k 10 200 python bench.py --full --steps 200 --warmup 20 --no-e2e --no-check --no-hmm --no-cpu-baseline --no-merged-line > $OUT/${N}.log 2>&1
   python - $OUT/${N}.log "$X" <<'PY'
 import json, sys
 try:

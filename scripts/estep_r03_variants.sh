@@ -9,7 +9,7 @@ for SPEC in "${VARS[@]}"; do
   N=v${i}
   GBRS_HIPCC_EXTRA="$X" python -c "import __graft_entry__ as g; g.build()" > $OUT/build_$N.log 2>&1 || echo "BUILD FAILED: $X"
   for rep in a b; do
-  env $E timeout -k 10 200 python bench.py --steps ${STEPS:-200} --warmup ${WARM:-20} --no-e2e --no-cpu-baseline --no-hmm --no-merged-line --no-multi-isoform-line $BENCH_ARGS > $OUT/${N}_$rep.log 2>&1
+  env $E timeout -k 10 200 python bench.py --full --steps ${STEPS:-200} --warmup ${WARM:-20} --no-e2e --no-cpu-baseline --no-hmm --no-merged-line --no-multi-isoform-line $BENCH_ARGS > $OUT/${N}_$rep.log 2>&1
   python - "$SPEC" "$OUT/${N}_$rep.log" <<'PY'
 import json, sys
 try:

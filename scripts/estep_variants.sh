@@ -3,7 +3,7 @@
 OUT=${1:-gpurun_out/variants}; mkdir -p $OUT
 build() { GBRS_HIPCC_EXTRA="$1" python -c "import __graft_entry__ as g; g.build()" > $OUT/build.log 2>&1 || echo "BUILD FAILED: $1"; }
 bench() {  # name, bench flags, [extra bench args]
-  timeout -k 10 200 python bench.py --steps 200 --warmup 20 --no-e2e --no-cpu-baseline --no-hmm --no-merged-line --flags $2 $3 > $OUT/$1.log 2>&1
+  timeout -k 10 200 python bench.py --full --steps 200 --warmup 20 --no-e2e --no-cpu-baseline --no-hmm --no-merged-line --flags $2 $3 > $OUT/$1.log 2>&1
   python - "$1" "$OUT/$1.log" <<'PY'
 import json, sys
 try:

@@ -3,7 +3,7 @@
 OUT=$(realpath -m ${1:-gpurun_out/hmmprof}); B=${2:-64}; R=$PWD; mkdir -p $OUT; export TMPDIR=/tmp; cd /tmp
 for SER in 1 0; do
   export GBRS_TUNING_HMM_SERIAL=$SER
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ser$SER -- python3 $R/bench.py --rows 200000 --steps 2 --warmup 1 --no-cpu-baseline --no-merged-line --no-e2e --no-check --hmm-batch $B --hmm-batch-large 0 --hmm-reps 3 > $OUT/ser$SER.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ser$SER -- python3 $R/bench.py --full --rows 200000 --steps 2 --warmup 1 --no-cpu-baseline --no-merged-line --no-e2e --no-check --hmm-batch $B --hmm-batch-large 0 --hmm-reps 3 > $OUT/ser$SER.log 2>&1
   echo "== serial=$SER"; python3 - $OUT/ser$SER <<'PY'
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + "/*/*_kernel_stats.csv")[0]

@@ -4,7 +4,7 @@
 # MFMA sweeps / the samples-on-lanes delta chain, 0 = never)
 OUT=${1:-gpurun_out/hmmb}; B=${2:-64}; shift 2; mkdir -p $OUT
 for V in "$@"; do set -- $V; M=$1; D=${2:-0}
-  GBRS_TUNING_HMM_DLANES=$D GBRS_TUNING_HMM_MFMA=$M timeout -k 10 300 python bench.py --rows 200000 --steps 2 --warmup 1 --no-cpu-baseline --no-merged-line --no-e2e --hmm-batch $B --hmm-batch-large 0 --hmm-reps 3 > $OUT/b${B}_m${M}_d${D}.log 2>&1
+  GBRS_TUNING_HMM_DLANES=$D GBRS_TUNING_HMM_MFMA=$M timeout -k 10 300 python bench.py --full --rows 200000 --steps 2 --warmup 1 --no-cpu-baseline --no-merged-line --no-e2e --hmm-batch $B --hmm-batch-large 0 --hmm-reps 3 > $OUT/b${B}_m${M}_d${D}.log 2>&1
   python - $OUT/b${B}_m${M}_d${D}.log $B "min $M dlanes $D" <<'PY'
 import json, sys
 try:

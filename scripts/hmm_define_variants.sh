@@ -7,7 +7,7 @@ for DEF in "$@"; do I=$((I+1))
   rm -f gbrs_amd/csrc/build/hmm.o
   GBRS_HIPCC_EXTRA="$DEF" python -c "import __graft_entry__ as g; g.build()" > $OUT/build$I.log 2>&1 || { echo "BUILD FAILED: $DEF"; continue; }
   for B in $BATCHES; do
-    timeout -k 10 300 python bench.py --rows 200000 --steps 2 --warmup 1 --no-cpu-baseline --no-merged-line --no-e2e --hmm-batch $B --hmm-batch-large 0 --hmm-reps 3 > $OUT/v${I}_b$B.log 2>&1
+    timeout -k 10 300 python bench.py --full --rows 200000 --steps 2 --warmup 1 --no-cpu-baseline --no-merged-line --no-e2e --hmm-batch $B --hmm-batch-large 0 --hmm-reps 3 > $OUT/v${I}_b$B.log 2>&1
     python - $OUT/v${I}_b$B.log $B "$DEF" <<'PY'
 import json, sys
 try:

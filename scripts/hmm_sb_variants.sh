@@ -3,7 +3,7 @@
 OUT=${1:-gpurun_out/hmmsb}; B=${2:-256}; mkdir -p $OUT
 for SB in 4 8; do
   GBRS_HIPCC_EXTRA="-DHMM_SB=$SB" python -c "import __graft_entry__ as g; g.build()" > $OUT/build.log 2>&1 || echo BUILD FAILED
-  timeout -k 10 300 python bench.py --rows 200000 --steps 2 --warmup 1 --no-cpu-baseline --no-merged-line --no-e2e --hmm-batch $B --hmm-batch-large 0 --hmm-reps 3 > $OUT/sb$SB.log 2>&1
+  timeout -k 10 300 python bench.py --full --rows 200000 --steps 2 --warmup 1 --no-cpu-baseline --no-merged-line --no-e2e --hmm-batch $B --hmm-batch-large 0 --hmm-reps 3 > $OUT/sb$SB.log 2>&1
   python - $OUT/sb$SB.log $SB <<'PY'
 import json, sys
 try:

@@ -2,10 +2,11 @@
 # Single-sample HMM time under environment switches (GPU box).  Usage: scripts/hmm_single_ab.sh "<ENV=..>;<ENV=..>" [bench args]
 IFS=';' read -ra VARS <<< "$1"
 shift
+LOG=$(mktemp)
 for X in "${VARS[@]}"; do
   for rep in a b; do
-  env $X timeout -k 10 300 python bench.py --no-e2e --no-cpu-baseline --no-merged-line --no-multi-isoform-line --no-check --steps 20 --warmup 5 --hmm-batch 0 --hmm-batch-large 0 "$@" > /tmp/hmm_ab.log 2>&1
-  python - "$X" /tmp/hmm_ab.log <<'PY'
+  env $X timeout -k 10 300 python bench.py --full --no-e2e --no-cpu-baseline --no-merged-line --no-multi-isoform-line --no-check --steps 20 --warmup 5 --hmm-batch 0 --hmm-batch-large 0 "$@" > $LOG 2>&1
+  python - "$X" $LOG <<'PY'
 import json, sys
 try:
     d = json.loads(open(sys.argv[2]).read().strip().split("\n")[-1])["hmm"]
@@ -16,3 +17,4 @@ except Exception as e:
 PY
   done
 done
+rm -f $LOG

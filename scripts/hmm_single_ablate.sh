@@ -8,7 +8,7 @@ for DEF in "$@"; do I=$((I+1))
   rm -f gbrs_amd/csrc/build/hmm.o
   GBRS_HIPCC_EXTRA="$DEF" python -c "import __graft_entry__ as g; g.build()" > $OUT/build$I.log 2>&1 || { echo "BUILD FAILED: $DEF"; continue; }
   rm -rf $OUT/kt$I
-  (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt$I -- python3 $R/bench.py --rows 200000 --steps 2 --warmup 1 --no-cpu-baseline --no-merged-line --no-e2e --hmm-batch 0 --hmm-batch-large 0 --hmm-reps 21 > $OUT/v$I.log 2>&1)
+  (cd "$TMPDIR" && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt$I -- python3 $R/bench.py --full --rows 200000 --steps 2 --warmup 1 --no-cpu-baseline --no-merged-line --no-e2e --hmm-batch 0 --hmm-batch-large 0 --hmm-reps 21 > $OUT/v$I.log 2>&1)
   python - "$DEF" $OUT/kt$I <<'PY'
 import csv, glob, sys
 out = []

@@ -5,7 +5,7 @@ I=0
 for DEF in "$@"; do I=$((I+1))
   rm -f gbrs_amd/csrc/build/hmm.o
   GBRS_HIPCC_EXTRA="$DEF" python -c "import __graft_entry__ as g; g.build()" > $OUT/build$I.log 2>&1 || { echo "BUILD FAILED: $DEF"; continue; }
-  timeout -k 10 300 python bench.py --rows 200000 --steps 2 --warmup 1 --no-cpu-baseline --no-merged-line --no-e2e --hmm-batch 0 --hmm-batch-large 0 > $OUT/v$I.log 2>&1
+  timeout -k 10 300 python bench.py --full --rows 200000 --steps 2 --warmup 1 --no-cpu-baseline --no-merged-line --no-e2e --hmm-batch 0 --hmm-batch-large 0 > $OUT/v$I.log 2>&1
   python - $OUT/v$I.log "$DEF" <<'PY'
 import json, sys
 try:

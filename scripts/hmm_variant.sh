@@ -4,5 +4,5 @@
 OUT=$1; shift
 mkdir -p $(dirname $OUT)
 GBRS_HIPCC_EXTRA="$*" python -c "import __graft_entry__ as g; g.build()" > /dev/null 2>&1
-python bench.py --rows 200000 --steps 2 --warmup 1 --no-cpu-baseline --no-merged-line > $OUT 2>&1
+python bench.py --full --rows 200000 --steps 2 --warmup 1 --no-cpu-baseline --no-merged-line > $OUT 2>&1
 GBRS_HIPCC_EXTRA="-DGBRS_FULL" python -c "import __graft_entry__ as g; g.build()" > /dev/null 2>&1

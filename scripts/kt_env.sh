@@ -10,7 +10,7 @@ cd /tmp
 i=0
 for X in "${VARS[@]}"; do
   for kv in $X; do export "$kv"; done
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/v$i -- python3 $R/bench.py --no-e2e --no-cpu-baseline --no-hmm --no-merged-line --no-multi-isoform-line --no-check "$@" > $OUT/v$i.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/v$i -- python3 $R/bench.py --full --no-e2e --no-cpu-baseline --no-hmm --no-merged-line --no-multi-isoform-line --no-check "$@" > $OUT/v$i.log 2>&1
   echo "== $X"
   f=$(find $OUT/v$i -name "*kernel_stats.csv" | head -1)
   python3 - "$f" <<'PY'

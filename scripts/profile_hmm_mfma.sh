@@ -2,7 +2,7 @@
 # rocprofv3 kernel trace + MFMA / VALU counter pass for the 256-sample HMM line (GPU box).  Usage: bash scripts/profile_hmm_mfma.sh OUTDIR
 OUT=$(realpath -m ${1:-gpurun_out/prof_hmm_mfma}); R=$PWD
 mkdir -p $OUT; export TMPDIR=/tmp; cd /tmp
-ARGS="--rows 200000 --steps 2 --warmup 1 --no-cpu-baseline --no-merged-line --no-e2e --no-check --hmm-samples 256 --hmm-batch 0 --hmm-batch-large 0 --hmm-reps 2"
+ARGS="--full --rows 200000 --steps 2 --warmup 1 --no-cpu-baseline --no-merged-line --no-e2e --no-check --hmm-samples 256 --hmm-batch 0 --hmm-batch-large 0 --hmm-reps 2"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- python3 $R/bench.py $ARGS > $OUT/kt.log 2>&1
 rocprofv3 --pmc SQ_INSTS_VALU_MFMA_F64 SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_BUSY_CYCLES SQ_WAVES GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmc -- python3 $R/bench.py $ARGS > $OUT/pmc.log 2>&1
 cd $R

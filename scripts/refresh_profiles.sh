@@ -14,21 +14,21 @@ if [ $PART = a ]; then
 python -m pytest tests -m gpu -q > $O/pytest_gpu.log 2>&1
 python -c "import __graft_entry__ as g; g.smoke()" >> $O/pytest_gpu.log 2>&1
 tail -3 $O/pytest_gpu.log
-python bench.py > $O/bench_default.log 2> $O/bench_default.err
-python bench.py --steps 20 --warmup 5 --no-e2e --no-hmm --no-cpu-baseline --no-merged-line --no-multi-isoform-line > $O/bench_steps20.log 2>&1
-python bench.py --no-e2e --no-hmm --no-cpu-baseline --no-merged-line --no-multi-isoform-line --flags 32 > $O/bench_deterministic_C2.log 2>&1
-python bench.py --no-e2e --rows 25000000 --haps 16 --loci 200000 --steps 20 --warmup 2 --no-hmm --no-cpu-baseline --no-merged-line --no-multi-isoform-line > $O/bench_C5_shard_25M_x16.log 2>&1
-python bench.py --no-e2e --rows 200000 --steps 2 --warmup 1 --no-cpu-baseline --no-merged-line --no-multi-isoform-line --hmm-haps 16 --hmm-batch 8 > $O/bench_hmm_16founders.log 2>&1
+python bench.py --full > $O/bench_default.log 2> $O/bench_default.err
+python bench.py --full --steps 20 --warmup 5 --no-e2e --no-hmm --no-cpu-baseline --no-merged-line --no-multi-isoform-line > $O/bench_steps20.log 2>&1
+python bench.py --full --no-e2e --no-hmm --no-cpu-baseline --no-merged-line --no-multi-isoform-line --flags 32 > $O/bench_deterministic_C2.log 2>&1
+python bench.py --full --no-e2e --rows 25000000 --haps 16 --loci 200000 --steps 20 --warmup 2 --no-hmm --no-cpu-baseline --no-merged-line --no-multi-isoform-line > $O/bench_C5_shard_25M_x16.log 2>&1
+python bench.py --full --no-e2e --rows 200000 --steps 2 --warmup 1 --no-cpu-baseline --no-merged-line --no-multi-isoform-line --hmm-haps 16 --hmm-batch 8 > $O/bench_hmm_16founders.log 2>&1
 for f in bench_steps20 bench_deterministic_C2 bench_C5_shard_25M_x16; do summ $O/$f.log; done
 fi
 if [ $PART = b ]; then
-python bench.py --gpus 2 --backend gloo --steps 10 --warmup 2 --no-cpu-baseline --hmm-batch-large 0 --no-multi-isoform-line > $O/bench_gloo_2ranks.log 2>&1
-python bench.py --no-e2e --no-hmm --no-cpu-baseline --no-merged-line --no-multi-isoform-line --rccl-selftest --no-overlap > $O/bench_rccl_selftest_single.log 2>&1
-python bench.py --no-e2e --no-hmm --no-cpu-baseline --no-merged-line --no-multi-isoform-line --rccl-selftest --force-overlap-path > $O/bench_rccl_selftest_pipelined.log 2>&1
+python bench.py --full --gpus 2 --backend gloo --steps 10 --warmup 2 --no-cpu-baseline --hmm-batch-large 0 --no-multi-isoform-line > $O/bench_gloo_2ranks.log 2>&1
+python bench.py --full --no-e2e --no-hmm --no-cpu-baseline --no-merged-line --no-multi-isoform-line --rccl-selftest --no-overlap > $O/bench_rccl_selftest_single.log 2>&1
+python bench.py --full --no-e2e --no-hmm --no-cpu-baseline --no-merged-line --no-multi-isoform-line --rccl-selftest --force-overlap-path > $O/bench_rccl_selftest_pipelined.log 2>&1
 for f in bench_gloo_2ranks bench_rccl_selftest_single bench_rccl_selftest_pipelined; do summ $O/$f.log; done
 python scripts/next_rows_bench.py > $O/next_rows.json 2> $O/next_rows.err
 export TMPDIR=/tmp; cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/kt -- python3 $R/bench.py --no-e2e --no-cpu-baseline > $R/$O/kt.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/kt -- python3 $R/bench.py --full --no-e2e --no-cpu-baseline > $R/$O/kt.log 2>&1
 cd $R
 python scripts/summarize_prof.py $O > $O/kernel_stats.txt
 cp $O/kt/*/*_kernel_stats.csv $O/kernel_stats.csv

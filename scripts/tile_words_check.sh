@@ -9,7 +9,7 @@ for DEF in "$@"; do I=$((I+1))
   GBRS_HIPCC_EXTRA="$DEF" python -c "import __graft_entry__ as g; g.build()" > $OUT/build.log 2>&1 || { echo "BUILD FAILED $DEF"; continue; }
   for V in "c5 --rows 25000000 --haps 16 --loci 200000 --steps 50 --warmup 5" "merge --merge --steps 300 --warmup 30" "det --flags 32 --steps 50 --warmup 5" "c2 --steps 500 --warmup 50"; do
     set -- $V; N=$1; shift
-    timeout -k 10 250 python bench.py --no-e2e --no-cpu-baseline --no-hmm --no-merged-line "$@" > $OUT/v${I}_$N.log 2>&1
+    timeout -k 10 250 python bench.py --full --no-e2e --no-cpu-baseline --no-hmm --no-merged-line "$@" > $OUT/v${I}_$N.log 2>&1
     python - "$DEF" $N $OUT/v${I}_$N.log <<'PY'
 import json, sys
 try:

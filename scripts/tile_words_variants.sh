@@ -4,7 +4,7 @@
 OUT=${1:-gpurun_out/tilewords}; shift; mkdir -p $OUT
 python -c "import __graft_entry__ as g; g.build()" > $OUT/build.log 2>&1 || { echo "BUILD FAILED"; exit 1; }
 for W in "$@"; do
-  GBRS_TUNING_TILE_WORDS=$W timeout -k 10 200 python bench.py --steps 300 --warmup 30 --no-e2e --no-cpu-baseline --no-hmm --no-merged-line > $OUT/w$W.log 2>&1
+  GBRS_TUNING_TILE_WORDS=$W timeout -k 10 200 python bench.py --full --steps 300 --warmup 30 --no-e2e --no-cpu-baseline --no-hmm --no-merged-line > $OUT/w$W.log 2>&1
   python - $W $OUT/w$W.log <<'PY'
 import json, sys
 try:

@@ -3,5 +3,5 @@
 OUT=$1; shift
 mkdir -p $(dirname $OUT)
 GBRS_HIPCC_EXTRA="$*" python -c "import __graft_entry__ as g; g.build()" > /dev/null 2>&1
-python bench.py --steps 40 --warmup 4 --no-hmm --no-cpu-baseline > $OUT 2>&1
+python bench.py --full --steps 40 --warmup 4 --no-hmm --no-cpu-baseline > $OUT 2>&1
 GBRS_HIPCC_EXTRA="-DGBRS_FULL" python -c "import __graft_entry__ as g; g.build()" > /dev/null 2>&1

@@ -76,6 +76,16 @@ def test_parse_steps_and_dump_outputs(monkeypatch):
         bench.parse()
 
 
+def test_parse_full_is_off_unless_asked(monkeypatch):
+    """A plain run times the headline alone; --full adds the rest, and the --no-* switches still pick parts of it."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-hmm", "--steps", "7"])
+    a = bench.parse()
+    assert a.full and a.no_hmm and not a.no_check and a.steps == 7
+
+
 def test_dump_outputs_writes_float64_files(tmp_path):
     import numpy as np
 

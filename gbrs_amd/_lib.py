@@ -23,6 +23,7 @@ EXPORTS = [
     "gbrs_em_set_stream",
     "gbrs_em_sync", "gbrs_em_pair_begin", "gbrs_em_pair_check", "gbrs_em_pair_status", "gbrs_em_info", "gbrs_alignment_counts",
     "gbrs_counts_create", "gbrs_counts_get", "gbrs_counts_destroy", "gbrs_em_destroy",
+    "gbrs_shard_plan", "gbrs_shard_index", "gbrs_shard_gather",
     "gbrs_hmm_create", "gbrs_hmm_set_expression", "gbrs_hmm_set_eprob", "gbrs_hmm_run",
     "gbrs_hmm_get", "gbrs_hmm_info", "gbrs_hmm_destroy", "gbrs_interpolate", "gbrs_genoprob_dosage",
     "gbrs_compress_create", "gbrs_compress_get", "gbrs_compress_destroy",
@@ -135,6 +136,9 @@ def load():
         "gbrs_counts_get": [vp, vp, u32, vp, vp, vp],
         "gbrs_counts_destroy": [vp],
         "gbrs_em_destroy": [vp],
+        "gbrs_shard_plan": [u64, u32, u32, pp, pp, i32, i32, vp],
+        "gbrs_shard_index": [u64, u32, u32, pp, pp, u64, u64, i32, pp, vp],
+        "gbrs_shard_gather": [u64, u32, u32, pp, pp, u64, u64, u32, pp, i32, vp, pp, pp, C.POINTER(u64)],
         "gbrs_hmm_create": [i32, i32, vp, vp, pp, i32, pp],
         "gbrs_hmm_set_expression": [vp, i32, pp, pp, pp, dbl, dbl],
         "gbrs_hmm_set_eprob": [vp, i32, pp],

@@ -46,6 +46,12 @@ def build_parser():
     q.add_argument('--device', type=int, default=0, help='HIP device ordinal (extension)')
     q.add_argument('--merge-identical-rows', action='store_true',
                    help='merge identical reads into weighted rows on the device (extension)')
+    q.add_argument('--gpus', type=int, default=None,
+                   help='shard the reads over N ranks, one process per GPU (extension; gbrs_amd/sharded.py)')
+    q.add_argument('--devices', default=None,
+                   help='with --gpus N: N comma-separated device ordinals (default --device + rank)')
+    q.add_argument('--dist-backend', choices=('nccl', 'gloo'), default='nccl',
+                   help='with --gpus: collective backend, nccl = RCCL (default); gloo allows two ranks on one GPU')
     r = sub.add_parser('reconstruct', help='reconstruct the genome based upon gene-level TPM quantities')
     r.add_argument('-e', '--expr-file', dest='expression_file', required=True, type=_existing)
     r.add_argument('-t', '--tprob-file', required=True, type=_existing)
@@ -115,6 +121,11 @@ def main(argv=None) -> int:
         if args.command == 'quantify':
             if args.multiread_model not in (1, 2, 3, 4):
                 raise RuntimeError('-M, --multiread-model must be one of 1, 2, 3, or 4')
+        if args.command == 'quantify' and args.gpus is not None:
+            # N child processes, one per rank; this process opens no device
+            from .sharded import launch
+            launch(args, sys.argv[1:] if argv is None else list(argv), stages)
+        elif args.command == 'quantify':
             from .quantify import quantify
             quantify(alignment_file=args.alignment_file, group_file=args.group_file,
                      length_file=args.length_file, genotype_file=args.genotype_file, outbase=args.outbase,

@@ -1801,3 +1801,6 @@ namespace gbrs {
 __global__ void warm_layout_kernel() {}
 void warm_layout(hipStream_t st) { hipLaunchKernelGGL(warm_layout_kernel, dim3(1), dim3(64), 0, st); }
 }  // namespace gbrs
+
+// ---- row sharding of one sample over the ranks of `gbrs quantify --gpus N` ---------------------------------------------
+#include "em_shard.inc"

@@ -298,6 +298,36 @@ int gbrs_counts_get(gbrs_counts_t *c, const int32_t *locus_group, uint32_t num_o
                     double *aln_counts, double *allele_unique, double *locus_unique);
 int gbrs_counts_destroy(gbrs_counts_t *c);
 
+/* ------------------------------------------------------------------------------------------
+ * Row sharding of one sample over N ranks (`gbrs quantify --gpus N`), on the device.
+ * indptr / indices are host tables of H DEVICE pointers to the sample's CSC arrays (as for
+ * gbrs_em_create_device); every result equals gbrs_amd.dist.shard_rows bit for bit.  The calls
+ * are synchronous.  A row id >= num_rows or a malformed column pointer table is GBRS_ERR_INVALID.
+ * ---------------------------------------------------------------------------------------- */
+/* bounds (host uint64[world + 1]): row blocks balanced by entry count, bounds[k] =
+ * searchsorted(cum, total * k / world, 'left') over the per-row entry counts (cum[0] = 0),
+ * bounds[0] = 0, bounds[world] = num_rows.  1 <= world <= 64. */
+int gbrs_shard_plan(uint64_t num_rows, uint32_t num_loci, uint32_t num_haps,
+                    const uint32_t *const *indptr, const uint32_t *const *indices,
+                    int world, int device, uint64_t *bounds);
+/* Column pointers of the rows [r0, r1): indptr_out[h] device uint32[L + 1] (caller-allocated);
+ * nnz_out (host uint64[H]) the entries kept per haplotype. */
+int gbrs_shard_index(uint64_t num_rows, uint32_t num_loci, uint32_t num_haps,
+                     const uint32_t *const *indptr, const uint32_t *const *indices,
+                     uint64_t r0, uint64_t r1, int device,
+                     uint32_t *const *indptr_out, uint64_t *nnz_out);
+/* The kept entries of the rows [r0, r1): indices_out[h] device uint32[nnz_local[h]] with row ids
+ * re-based to r0 (column order kept) and, when values (device double tables aligned with indices)
+ * is not NULL, values_out[h] device double[nnz_local[h]].  nnz_local (host) is what
+ * gbrs_shard_index reported; a mismatch is GBRS_ERR_INVALID and nothing is written.
+ * l_split in (0, L): *straddling = the number of local rows with entries in loci on both sides
+ * of l_split; l_split = 0: not asked (straddling may be NULL). */
+int gbrs_shard_gather(uint64_t num_rows, uint32_t num_loci, uint32_t num_haps,
+                      const uint32_t *const *indptr, const uint32_t *const *indices,
+                      uint64_t r0, uint64_t r1, uint32_t l_split, const double *const *values,
+                      int device, const uint64_t *nnz_local, uint32_t *const *indices_out,
+                      double *const *values_out, uint64_t *straddling);
+
 int gbrs_em_destroy(gbrs_em_t *em);
 
 /* `gbrs compress` numeric body (gbrs/emase_utils.py:60-103): rows with identical alignment patterns

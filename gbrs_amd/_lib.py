@@ -27,6 +27,8 @@ EXPORTS = [
     "gbrs_hmm_create", "gbrs_hmm_set_expression", "gbrs_hmm_set_eprob", "gbrs_hmm_run",
     "gbrs_hmm_get", "gbrs_hmm_info", "gbrs_hmm_destroy", "gbrs_interpolate", "gbrs_genoprob_dosage",
     "gbrs_compress_create", "gbrs_compress_get", "gbrs_compress_destroy",
+    "gbrs_bam_open", "gbrs_bam_references", "gbrs_bam_set_reference_map", "gbrs_bam_convert", "gbrs_bam_get",
+    "gbrs_bam_scan_records", "gbrs_bam_destroy",
     "gbrs_format_double", "gbrs_write_locus_table", "gbrs_parse_length_table", "gbrs_parse_genotype_table",
     "gbrs_decode_chunks", "gbrs_inflate_backend", "gbrs_zip_directory", "gbrs_npz_stack", "gbrs_zip_read_members", "gbrs_parse_number_table",
 ]
@@ -151,6 +153,8 @@ def load():
         "gbrs_compress_create": [u64, u32, u32, pp, pp, vp, i32, pp, C.POINTER(u64), vp],
         "gbrs_compress_get": [vp, pp, pp, vp],
         "gbrs_compress_destroy": [vp],
+        "gbrs_bam_convert": [vp, i32, C.POINTER(u64), C.POINTER(u32), vp, vp],
+        "gbrs_bam_get": [vp, pp, pp, vp],
     }
     sigs.update(_host_signatures())
     for name, args in sigs.items():
@@ -166,7 +170,7 @@ def load():
 
 
 def _host_signatures():
-    """The host-only entry points of the library (gbrs_amd/csrc/hostio.hip)."""
+    """The host-only entry points of the library (gbrs_amd/csrc/hostio.hip, bamio.hip)."""
     vp, i32, u32, u64, i64, dbl = C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_int64, C.c_double
     return {
         "gbrs_format_double": [dbl, C.c_char_p],
@@ -179,6 +183,11 @@ def _host_signatures():
         "gbrs_parse_length_table": [C.c_char_p, i64, C.c_char_p, vp, i64, C.c_char_p, vp, i32, dbl, vp],
         "gbrs_parse_genotype_table": [C.c_char_p, i64, C.c_char_p, vp, i64, C.c_char_p, vp, i32, vp, vp, i32, vp,
                                       C.POINTER(i64)],
+        "gbrs_bam_open": [C.c_char_p, i32, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)],
+        "gbrs_bam_references": [vp, vp, u64, vp, vp],
+        "gbrs_bam_set_reference_map": [vp, u64, vp, vp, u32, u32],
+        "gbrs_bam_scan_records": [vp, u64, vp, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(u64)],
+        "gbrs_bam_destroy": [vp],
         "gbrs_write_locus_table": [C.c_char_p, C.c_char_p, vp, i64, i32, i64, i64, vp, C.c_char_p, vp, C.c_char_p, vp, vp],
     }
 

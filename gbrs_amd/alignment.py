@@ -23,7 +23,8 @@ import numpy as np
 
 class AlignmentPropertyMatrix:
     def __init__(self, shape=None, indptr=None, indices=None, count=None, haplotype_names=None,
-                 locus_names=None, grpfile=None, h5file=None, npzfile=None, values=None, on_names=None):
+                 locus_names=None, grpfile=None, h5file=None, npzfile=None, values=None, on_names=None,
+                 read_names=None):
         """`on_names(self)` (optional) is called once the haplotype and locus names are known - for an HDF5 file that is
         before the large index arrays are decoded, so the caller can parse name-keyed side files meanwhile."""
         self.hname = None
@@ -33,6 +34,8 @@ class AlignmentPropertyMatrix:
         self.groups = None
         self.num_groups = 0
         self.count = None
+        self.rname = None           # fixed-width bytes array [R] of read names (`gbrs bam2emase` sets it); never loaded:
+        #                             emase_h5.read_rname / read_rname_npz fetch it from a file on request
         self.values = None          # per-haplotype float64 arrays aligned with indices, or None = all ones
         self.haplotype_mask = None  # uint32[L], bit h = (h, l) kept: a `-G` mask the device applies (set_haplotype_mask)
         groups_thread = None
@@ -99,6 +102,10 @@ class AlignmentPropertyMatrix:
                 if len(locus_names) != L:
                     raise RuntimeError('The number of names does not match to the matrix shape.')
                 self.lname = list(locus_names)
+            if read_names is not None:
+                if len(read_names) != R:
+                    raise RuntimeError('The number of names does not match to the matrix shape.')
+                self.rname = np.asarray(read_names, dtype='S')
         self._finish_init()
         if grpfile is not None and groups_thread is None:
             self.load_groups(grpfile)
@@ -232,6 +239,8 @@ class AlignmentPropertyMatrix:
             out['hname'] = np.array(self.hname)
         if self.lname is not None:
             out['lname'] = np.array(self.lname)
+        if self.rname is not None:
+            out['rname'] = np.asarray(self.rname, dtype='S')
         np.savez_compressed(path, **out)
 
     def save(self, h5file, **kw):
@@ -240,6 +249,16 @@ class AlignmentPropertyMatrix:
         from . import emase_h5
         self.apply_haplotype_mask()
         emase_h5.save(self, h5file, **kw)
+
+
+def read_rname(path):
+    """The read names of an EMASE file written by `gbrs bam2emase` (bytes array [R]), or None when it holds none.
+    load_alignment leaves them alone: nothing downstream of the conversion looks a read up by name."""
+    if str(path).endswith('.npz'):
+        with np.load(path) as z:
+            return z['rname'] if 'rname' in z.files else None
+    from . import emase_h5
+    return emase_h5.read_rname(path)
 
 
 def load_alignment(path, grpfile=None, on_names=None):

@@ -1,4 +1,4 @@
-"""`gbrs` command line for the two MI355X subcommands: same flags, defaults and log-and-continue
+"""`gbrs` command line for the MI355X subcommands: same flags, defaults and log-and-continue
 error behaviour as gbrs/commands.py:108-183 (`quantify`) and :153-183 (`reconstruct`).  argparse
 instead of Typer so the GPU box needs nothing beyond the standard library."""
 from __future__ import annotations
@@ -82,6 +82,19 @@ def build_parser():
     cp.add_argument('-c', '--comp-lib', default='zlib')
     cp.add_argument('-v', '--verbose', action='count', default=0)
     cp.add_argument('--device', type=int, default=0)
+    # -h is the reference's haplotype flag here (gbrs/commands.py:38), so this subparser gets --help alone
+    b2 = sub.add_parser('bam2emase', help='convert a BAM file to the EMASE format', add_help=False)
+    b2.add_argument('--help', action='help', help='show this help message and exit')
+    b2.add_argument('-i', '--alignment-file', required=True, type=_existing)
+    b2.add_argument('-h', '--haplotype-char', dest='haplotypes', action='append', default=None,
+                    help='haplotype, either one per -h option, i.e. -h A -h B -h C, or a shortcut -h A,B,C')
+    b2.add_argument('-m', '--locus-ids', dest='locusid_file', required=True, type=_existing)
+    b2.add_argument('-o', '--output', dest='output_file', default=None)
+    b2.add_argument('-d', '--delim', default='_')
+    b2.add_argument('--index-dtype', default='uint32')
+    b2.add_argument('--data-dtype', default='uint8')
+    b2.add_argument('-v', '--verbose', action='count', default=0)
+    b2.add_argument('--device', type=int, default=0, help='HIP device ordinal (extension)')
     wk = sub.add_parser('worker', help='(extension) quantify -> reconstruct -> quantify -G of many samples in one resident process')
     wk.add_argument('--jobs', required=True, type=_existing, help='JSON list of samples, see gbrs_amd/worker.py')
     wk.add_argument('-v', '--verbose', action='count', default=0)
@@ -149,6 +162,13 @@ def main(argv=None) -> int:
             from .compress import compress
             files = [f for x in args.emase_files for f in x.split(',')]
             compress(emase_files=files, output_file=args.output_file, comp_lib=args.comp_lib, device=args.device)
+        elif args.command == 'bam2emase':
+            from .bam2emase import bam2emase
+            haplotypes = [h for x in (args.haplotypes or []) for h in x.split(',')]
+            kw = {} if args.output_file is None else {'output_file': args.output_file}     # the function's default otherwise
+            bam2emase(alignment_file=args.alignment_file, haplotypes=haplotypes, locusid_file=args.locusid_file,
+                      delim=args.delim, index_dtype=args.index_dtype, data_dtype=args.data_dtype, device=args.device,
+                      stage_times=stages, **kw)
         elif args.command == 'interpolate':
             from .postproc import interpolate
             interpolate(genoprob_file=args.genoprob_file, grid_file=args.grid_file, gpos_file=args.gpos_file,

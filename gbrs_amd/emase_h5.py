@@ -504,6 +504,24 @@ def load_into(apm, path, on_names=None):
         lib.H5Fclose(f)
 
 
+def read_rname(path):
+    """/rname of an EMASE file (fixed-width bytes [R]) or None; load_into does not read it."""
+    lib = _load()
+    f = lib.H5Fopen(os.fsencode(path), H5F_ACC_RDONLY, H5P_DEFAULT)
+    if f < 0:
+        raise OSError(f'cannot open {path} as HDF5')
+    try:
+        root = _check(lib.H5Gopen2(f, b'/', H5P_DEFAULT), 'open /')
+        try:
+            if lib.H5Lexists(root, b'rname', H5P_DEFAULT) <= 0:
+                return None
+            return _read_dataset(root, 'rname').ravel()
+        finally:
+            lib.H5Gclose(root)
+    finally:
+        lib.H5Fclose(f)
+
+
 # ------------------------------------------------------------------------------------------ writer
 
 def _write_str_attr(loc, name, value: bytes):
@@ -600,6 +618,8 @@ def save(apm, path, title=None, complib='zlib', incidence_only=True, shallow=Fal
                 _write_str_attr(root, 'hname', pickle.dumps(list(apm.hname), 0))
             if apm.lname is not None:
                 _write_carray(root, 'lname', np.array(apm.lname, dtype='S'), 'Locus Names')
+            if getattr(apm, 'rname', None) is not None:
+                _write_carray(root, 'rname', np.asarray(apm.rname, dtype='S'), 'Read Names')
         lib.H5Gclose(root)
     finally:
         lib.H5Fclose(f)

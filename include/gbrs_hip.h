@@ -347,6 +347,42 @@ int gbrs_compress_get(gbrs_compress_t *c, uint32_t *const *indptr_out, uint32_t 
                       double *count_out);
 int gbrs_compress_destroy(gbrs_compress_t *c);
 
+/* `gbrs bam2emase` (emase/AlignmentMatrixFactory.py:26-142): a BAM file -> the per-haplotype CSC incidence
+ * matrices of the EMASE format plus the sorted distinct read names.
+ *   open       reads the BGZF/BAM header (host only).  n_ref / ref_names_len size the buffers of
+ *              gbrs_bam_references: the names one after another without terminators, name k at
+ *              names[name_off[k] .. name_off[k+1]), name_off uint64[n_ref + 1], ref_len uint32[n_ref] or NULL.
+ *              threads <= 0: GBRS_IO_THREADS or the machine's count; never more than 16 inflate threads.
+ *   set_reference_map   hap[k], locus[k] of reference sequence k, as the caller split its name; a sequence no
+ *              kept record may use has hap[k] = 0xFFFFFFFF and locus[k] = the reason: 1 the name does not split
+ *              into (locus, haplotype), 2 unknown haplotype, 3 unknown locus.
+ *   convert    one pass over the file on the host (inflate + parse; per record only the name, refID and flag
+ *              are looked at), then on the device: rank the distinct names of ALL records bytewise (= the
+ *              order of Python's sorted() for ASCII names), read id = rank; every record whose flag word is
+ *              neither exactly 4 nor exactly 8 (an equality test, as in the reference, not a bit test) gives
+ *              the entry (read id, locus) of its haplotype; duplicates are stored once.  The first such record
+ *              without a reference sequence or with an unusable one is GBRS_ERR_INVALID, its sequence named in
+ *              the message.  Out: num_reads, name_width (longest name, at least 1), nnz_per_hap uint64[H],
+ *              stage_seconds double[3] (read, rank, build; NULL allowed).  GBRS_ERR_NO_DEVICE without a
+ *              device - there is no CPU fallback; GBRS_ERR_UNSUPPORTED when 2^32 or more reads or entries of
+ *              one haplotype, or when (haplotype, locus, read id) does not fit 64 bits.
+ *   get        indptr_out[h] uint32[L + 1], indices_out[h] uint32[nnz_per_hap[h]] (read ids ascending inside a
+ *              column), rname_out char[num_reads * name_width] zero padded (NULL to skip).
+ *   scan_records   host only, for small files and tests: refID, flag and name of every record in file order.
+ *              Arrays of `cap` entries (name_off: cap + 1), names as in gbrs_bam_references; n_records and
+ *              names_len report the full sizes, so a first call with cap = 0 sizes the second. */
+typedef struct gbrs_bam gbrs_bam_t;
+int gbrs_bam_open(const char *path, int32_t threads, gbrs_bam_t **out, uint64_t *n_ref, uint64_t *ref_names_len);
+int gbrs_bam_references(gbrs_bam_t *b, char *names, uint64_t names_cap, uint64_t *name_off, uint32_t *ref_len);
+int gbrs_bam_set_reference_map(gbrs_bam_t *b, uint64_t n_ref, const uint32_t *hap, const uint32_t *locus,
+                               uint32_t num_haps, uint32_t num_loci);
+int gbrs_bam_convert(gbrs_bam_t *b, int device, uint64_t *num_reads, uint32_t *name_width, uint64_t *nnz_per_hap,
+                     double *stage_seconds);
+int gbrs_bam_get(gbrs_bam_t *b, uint32_t *const *indptr_out, uint32_t *const *indices_out, char *rname_out);
+int gbrs_bam_scan_records(gbrs_bam_t *b, uint64_t cap, int32_t *refid, uint32_t *flag, uint64_t *name_off, char *names,
+                          uint64_t names_cap, uint64_t *n_records, uint64_t *names_len);
+int gbrs_bam_destroy(gbrs_bam_t *b);
+
 /* ------------------------------------------------------------------------------------------
  * HMM: per-chromosome forward-backward + Viterbi over the S = H(H+1)/2 diplotype states.
  * ---------------------------------------------------------------------------------------- */

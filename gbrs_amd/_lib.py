@@ -29,6 +29,8 @@ EXPORTS = [
     "gbrs_compress_create", "gbrs_compress_get", "gbrs_compress_destroy",
     "gbrs_bam_open", "gbrs_bam_references", "gbrs_bam_set_reference_map", "gbrs_bam_convert", "gbrs_bam_get",
     "gbrs_bam_scan_records", "gbrs_bam_destroy",
+    "gbrs_matops_create", "gbrs_matops_intersect", "gbrs_matops_append_rows", "gbrs_matops_keep_unique_rows",
+    "gbrs_matops_mask_columns", "gbrs_matops_sizes", "gbrs_matops_get", "gbrs_matops_destroy",
     "gbrs_format_double", "gbrs_write_locus_table", "gbrs_parse_length_table", "gbrs_parse_genotype_table",
     "gbrs_decode_chunks", "gbrs_inflate_backend", "gbrs_zip_directory", "gbrs_npz_stack", "gbrs_zip_read_members", "gbrs_parse_number_table",
 ]
@@ -155,6 +157,14 @@ def load():
         "gbrs_compress_destroy": [vp],
         "gbrs_bam_convert": [vp, i32, C.POINTER(u64), C.POINTER(u32), vp, vp],
         "gbrs_bam_get": [vp, pp, pp, vp],
+        "gbrs_matops_create": [u64, u32, u32, pp, pp, i32, pp],
+        "gbrs_matops_intersect": [vp, pp, pp],
+        "gbrs_matops_append_rows": [vp, u64, pp, pp],
+        "gbrs_matops_keep_unique_rows": [vp, vp, u32, i32, vp],
+        "gbrs_matops_mask_columns": [vp, vp],
+        "gbrs_matops_sizes": [vp, C.POINTER(u64), vp, C.POINTER(u32)],
+        "gbrs_matops_get": [vp, pp, pp],
+        "gbrs_matops_destroy": [vp],
     }
     sigs.update(_host_signatures())
     for name, args in sigs.items():

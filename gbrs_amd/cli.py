@@ -95,6 +95,33 @@ def build_parser():
     b2.add_argument('--data-dtype', default='uint8')
     b2.add_argument('-v', '--verbose', action='count', default=0)
     b2.add_argument('--device', type=int, default=0, help='HIP device ordinal (extension)')
+    # structure edits of an EMASE file (emase/commands.py:75-257, gbrs/commands.py:342-366; gbrs_amd/matops.py)
+    ca = sub.add_parser('get-common-alignments', help='get the common alignments')
+    ca.add_argument('-i', '--emase-file', dest='emase_files', action='append', required=True)
+    ca.add_argument('-o', '--output', dest='output_file', default=None)
+    ca.add_argument('-c', '--comp-lib', default='zlib')
+    cb = sub.add_parser('combine', help='combine EMASE files')
+    cb.add_argument('-i', '--emase-file', dest='emase_files', action='append', required=True)
+    cb.add_argument('-o', '--output', dest='output_file', required=True)
+    cb.add_argument('-c', '--comp-lib', default='zlib')
+    pu = sub.add_parser('pull-out-unique-reads', help='keep the alignments of uniquely aligning reads')
+    pu.add_argument('-i', '--alignment-file', required=True, type=_existing)
+    pu.add_argument('-o', '--output', dest='output_file', required=True)
+    pu.add_argument('-g', '--group-file', type=_existing, default=None)
+    pu.add_argument('-s', '--shallow', action='store_true')
+    pu.add_argument('-a', '--ignore-alleles', action='store_true')
+    cn = sub.add_parser('count-alignments', help='count alignments')
+    cn.add_argument('-i', '--alignment-file', required=True, type=_existing)
+    cn.add_argument('-g', '--group-file', required=True, type=_existing)
+    cn.add_argument('-o', '--outbase', default='emase')
+    sn = sub.add_parser('stencil', help='apply genotype calls to multi-way alignment incidence matrix')
+    sn.add_argument('-i', '--alignment-file', required=True, type=_existing)
+    sn.add_argument('-G', '--genotype', dest='genotype_file', required=True, type=_existing)
+    sn.add_argument('-g', '--group-file', type=_existing, default=None)
+    sn.add_argument('-o', '--output', dest='output_file', default=None)
+    for p in (ca, cb, pu, cn, sn):
+        p.add_argument('-v', '--verbose', action='count', default=0)
+        p.add_argument('--device', type=int, default=0, help='HIP device ordinal (extension)')
     wk = sub.add_parser('worker', help='(extension) quantify -> reconstruct -> quantify -G of many samples in one resident process')
     wk.add_argument('--jobs', required=True, type=_existing, help='JSON list of samples, see gbrs_amd/worker.py')
     wk.add_argument('-v', '--verbose', action='count', default=0)
@@ -169,6 +196,28 @@ def main(argv=None) -> int:
             bam2emase(alignment_file=args.alignment_file, haplotypes=haplotypes, locusid_file=args.locusid_file,
                       delim=args.delim, index_dtype=args.index_dtype, data_dtype=args.data_dtype, device=args.device,
                       stage_times=stages, **kw)
+        elif args.command in ('get-common-alignments', 'combine'):
+            from . import matops
+            files = [f for x in args.emase_files for f in x.split(',')]
+            for f in files:
+                if not os.path.isfile(f):
+                    raise FileNotFoundError(f"File '{f}' does not exist.")
+            edit = matops.get_common_alignments if args.command == 'get-common-alignments' else matops.combine
+            edit(emase_files=[os.path.realpath(f) for f in files], output_file=args.output_file,
+                 comp_lib=args.comp_lib, device=args.device, stage_times=stages)
+        elif args.command == 'pull-out-unique-reads':
+            from .matops import pull_out_unique_reads
+            pull_out_unique_reads(alignment_file=args.alignment_file, output_file=args.output_file,
+                                  group_file=args.group_file, shallow=args.shallow,
+                                  ignore_alleles=args.ignore_alleles, device=args.device, stage_times=stages)
+        elif args.command == 'count-alignments':
+            from .matops import count_alignments
+            count_alignments(alignment_file=args.alignment_file, group_file=args.group_file, outbase=args.outbase,
+                             device=args.device)
+        elif args.command == 'stencil':
+            from .matops import stencil
+            stencil(alignment_file=args.alignment_file, genotype_file=args.genotype_file, group_file=args.group_file,
+                    output_file=args.output_file, device=args.device, stage_times=stages)
         elif args.command == 'interpolate':
             from .postproc import interpolate
             interpolate(genoprob_file=args.genoprob_file, grid_file=args.grid_file, gpos_file=args.gpos_file,

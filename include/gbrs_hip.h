@@ -347,6 +347,46 @@ int gbrs_compress_get(gbrs_compress_t *c, uint32_t *const *indptr_out, uint32_t 
                       double *count_out);
 int gbrs_compress_destroy(gbrs_compress_t *c);
 
+/* Structure edits of one sample's incidence tensor, resident on the device: the numeric bodies of
+ * `get-common-alignments` (emase/emase_utils.py:236-274 with Sparse3DMatrix.__mul__, Sparse3DMatrix.py:168-180),
+ * `combine` (emase_utils.py:73-111, Sparse3DMatrix.py:383-398, AlignmentPropertyMatrix.py:461-476),
+ * `pull-out-unique-reads` (emase_utils.py:277-317, AlignmentPropertyMatrix.py:372-413) and `stencil`
+ * (gbrs/emase_utils.py:110-177: `multiply(gtmask, axis=2)` + `eliminate_zeros()`, saved instead of quantified).
+ * Only the structure is held (every stored entry counts as present, whatever its value).
+ *   create            uploads the arrays (as for gbrs_em_create: any order inside a column, no duplicates).
+ *   intersect         m := the entries of m that b holds too (b: host arrays of the same R, L, H) - the elementwise
+ *                     product of two incidence tensors.
+ *   append_rows       m := the rows of m, then the num_rows_b rows of b (their ids shifted by R of m); R grows.
+ *   keep_unique_rows  drops every entry of a row that is not unique.  A row is unique when all its entries carry one
+ *                     key: the locus for ignore_haplotype != 0 (nnz of the haplotype sum == 1,
+ *                     AlignmentPropertyMatrix.py:398-403), (haplotype, locus) otherwise (exactly one alignment,
+ *                     :405-410).  With locus_group (int32[L], -1 = in no group; num_groups = G) the locus is replaced
+ *                     by its group - the test on the matrix after bundle(reset=True) - entries of loci in no group
+ *                     take no part in it, and the filter is applied to the isoform-level entries
+ *                     (pull_alignments_from on the original matrix, emase_utils.py:299-308).  A row without any
+ *                     counted entry is not unique.  keep_out (nullable) uint8[R]: 1 = the row stayed.
+ *   mask_columns      drops the columns (h, l) with bit h of allowed[l] clear (allowed: host uint32[L]), what
+ *                     gbrs_em_create_masked does before the EM.
+ *   sizes / get       R, the entries per haplotype, and sorted_inputs = how many haplotype arrays given so far did not
+ *                     have ascending columns and went through the radix sort (any pointer may be NULL);
+ *                     indptr_out[h] uint32[L + 1], indices_out[h] uint32[nnz_per_hap[h]].
+ * Every operand's row ids are range-checked on the device before a kernel indexes with them and its column pointer
+ * tables are checked on the host (GBRS_ERR_INVALID); the row ids of every result ascend inside every column (what
+ * scipy returns for the four operations); 2^32 or more rows, or entries of one haplotype, is GBRS_ERR_UNSUPPORTED;
+ * there is no CPU fallback (GBRS_ERR_NO_DEVICE).  After a failed edit the handle is only good for destroy. */
+typedef struct gbrs_matops gbrs_matops_t;
+int gbrs_matops_create(uint64_t num_rows, uint32_t num_loci, uint32_t num_haps, const uint32_t *const *indptr,
+                       const uint32_t *const *indices, int device, gbrs_matops_t **out);
+int gbrs_matops_intersect(gbrs_matops_t *m, const uint32_t *const *indptr_b, const uint32_t *const *indices_b);
+int gbrs_matops_append_rows(gbrs_matops_t *m, uint64_t num_rows_b, const uint32_t *const *indptr_b,
+                            const uint32_t *const *indices_b);
+int gbrs_matops_keep_unique_rows(gbrs_matops_t *m, const int32_t *locus_group, uint32_t num_groups,
+                                 int ignore_haplotype, uint8_t *keep_out);
+int gbrs_matops_mask_columns(gbrs_matops_t *m, const uint32_t *allowed);
+int gbrs_matops_sizes(gbrs_matops_t *m, uint64_t *num_rows, uint64_t *nnz_per_hap, uint32_t *sorted_inputs);
+int gbrs_matops_get(gbrs_matops_t *m, uint32_t *const *indptr_out, uint32_t *const *indices_out);
+int gbrs_matops_destroy(gbrs_matops_t *m);
+
 /* `gbrs bam2emase` (emase/AlignmentMatrixFactory.py:26-142): a BAM file -> the per-haplotype CSC incidence
  * matrices of the EMASE format plus the sorted distinct read names.
  *   open       reads the BGZF/BAM header (host only).  n_ref / ref_names_len size the buffers of

@@ -79,7 +79,7 @@ class HmmInfo(C.Structure):
         ("num_states", C.c_int32), ("n_samples", C.c_int32),
         ("last_run_ms", C.c_double),
         ("last_delta_blocks", C.c_int32), ("last_delta_longest_fixup", C.c_int32),
-        ("last_delta_fallbacks", C.c_int32), ("reserved0", C.c_int32),
+        ("last_delta_fallbacks", C.c_int32), ("last_delta_tie_fallbacks", C.c_int32),
     ]
 
 

@@ -2233,13 +2233,62 @@ hmm_outputs_kernel(int S, int OUT_ROWS /* (sample, gene) rows per workgroup */, 
 // in LDS) to find its true entry state, walks its chunk once more and writes the path.
 constexpr int BT_B = 64;
 
+// Blocked scan (S = 36) only: is the path the one the sequential chain takes?  What a block of the scan stores for a gene is
+// the sequential chain's vector minus ONE constant, up to an error per state.  By rank convergence the fix-up of block v
+// accepted the block where its chain differed from the chain started on what block v - 1 STORED by a spread of at most
+// tol = tol_abs + tol_rel * mag; the recursion d -> e + max(T + d) does not widen a spread; but block v - 1's vector carries
+// the spreads accepted before it, so in the worst case they add up along the chromosome: block v is within v * tol, and any
+// block within n_blocks * tol (at most 64 blocks).  In practice an accepted spread is rounding (the paths have merged or they
+// have not), far below tol_abs = 1e-9; the bound does not rely on that.  The roundings of the steps (one ulp each, a block is
+// ~40 genes) and of the constants stay far inside tol_rel * mag = 450 ulp per block, and the max-plus operators carry rounding
+// only.  `mag` is taken here in the block's own frame and by the fix-up in the frame of the block before: both are vectors
+// that start near zero and fall a few units per gene of ONE block, so tol_rel * mag is ~1e-11 on either side, a hundredth of
+// tol_abs - the factor n_blocks on tol_abs carries the bound, the relative term only keeps it scale free.  So two candidates
+// of a decision v[k] = delta[k][gene] + T[gene][state after][k] (delta[:, n-1] itself for the last state) are off by at most
+// 2 * n_blocks * tol against each other.  A decision won by more than that falls the same way in the sequential chain, and
+// if every decision of the path is, the path is the sequential chain's, by induction from the last state.
+// backtrace_write_kernel, which has the path in hand, takes best minus second best of every decision (one lane each) and
+// raises the chromosome's flag otherwise: then the sequential chain decides (exact ties by its first-index rule).  A
+// negative tol_abs (the tests' forced fallback) switches the check off: every cut chromosome is recomputed there anyway.
+constexpr int BT_TIE_S = 36;
+struct TieCheck {
+    const double *delta = nullptr, *tprob = nullptr;    // [sample][gene][S] as the blocks left it; the plain tables [to][from]
+    const int32_t *first_block = nullptr;               // [n_chrom + 1]: a chromosome of one block is the sequential chain itself
+    const int32_t *fail = nullptr;                      // [sample][chromosome], or null: already recomputed by the sequential chain
+    int32_t *tie = nullptr;                             // [sample][chromosome] flags; null: no check
+    double tol_abs = 0.0, tol_rel = 0.0;
+};
+
+__device__ __forceinline__ bool decision_is_close(const double *__restrict__ d, const double *__restrict__ t_row, double tol_abs,
+                                                  double tol_rel /* both times the chromosome's number of blocks */) {
+    constexpr int S = BT_TIE_S;
+    double v[S];
+#pragma unroll
+    for (int k = 0; k < S; ++k) v[k] = d[k];
+    if (t_row) {
+#pragma unroll
+        for (int k = 0; k < S; ++k) v[k] += t_row[k];
+    }
+    double best = -INFINITY, second = -INFINITY, mag = 0.0;
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+        second = fmax(second, fmin(best, v[k]));         // an equal value counts: a tie has margin 0
+        best = fmax(best, v[k]);
+        const double a = fabs(v[k]);
+        mag = fmax(mag, a < INFINITY ? a : 0.0);
+    }
+    return !(best - second > 2.0 * (tol_abs + tol_rel * mag));
+}
+
 __global__ void __launch_bounds__(64)
 backtrace_maps_kernel(int S, int64_t bp_per_sample, int64_t chunks_per_sample,
                       const ChromDesc *__restrict__ chroms, const uint16_t *__restrict__ bp,
-                      uint16_t *__restrict__ exit_map) {
+                      uint16_t *__restrict__ exit_map,
+                      const int32_t *__restrict__ only_if = nullptr /* [sample][chromosome]: walk only where set */) {
     extern __shared__ uint16_t stage[];        // BT_B * S
     const ChromDesc cd = chroms[blockIdx.y];
     const int sample = blockIdx.z;
+    if (only_if && !only_if[(int64_t)sample * gridDim.y + blockIdx.y]) return;
     const int m = min(cd.n_genes, cd.n_trans);
     const int lo = blockIdx.x * BT_B;
     if (lo >= m) return;
@@ -2259,11 +2308,14 @@ backtrace_write_kernel(int S, int64_t genes_per_sample, int64_t bp_per_sample, i
                        int64_t chunks_per_sample, int n_chrom, const ChromDesc *__restrict__ chroms,
                        const uint16_t *__restrict__ bp, const uint16_t *__restrict__ exit_map,
                        const int32_t *__restrict__ last_state, int32_t *__restrict__ states,
-                       int32_t *__restrict__ calls, int chrom_base /* the launch covers chromosomes chrom_base + blockIdx.y */) {
+                       int32_t *__restrict__ calls, int chrom_base /* the launch covers chromosomes chrom_base + blockIdx.y */,
+                       const int32_t *__restrict__ only_if = nullptr /* [sample][chromosome]: write only where set */,
+                       TieCheck tc = TieCheck{}) {
     extern __shared__ uint16_t stage[];        // max(BT_B, chunks above) * S maps, then BT_B path entries
     const int chrom = chrom_base + (int)blockIdx.y;
     const ChromDesc cd = chroms[chrom];
     const int sample = blockIdx.z;
+    if (only_if && !only_if[(int64_t)sample * n_chrom + chrom]) return;
     const int n = cd.n_genes;
     const int m = min(n, cd.n_trans);
     const int n_chunks = (m + BT_B - 1) / BT_B;
@@ -2290,6 +2342,7 @@ backtrace_write_kernel(int S, int64_t genes_per_sample, int64_t bp_per_sample, i
     uint16_t *rows = stage, *path = stage + BT_B * S;
     for (int x = threadIdx.x; x < (hi - lo) * S; x += 64) rows[x] = BP[x];
     __syncthreads();
+    const int entry = sid;                     // the state after this chunk's last row
     if (threadIdx.x == 0)
         for (int t = hi - lo - 1; t >= 0; --t) {
             sid = rows[t * S + sid];
@@ -2301,9 +2354,26 @@ backtrace_write_kernel(int S, int64_t genes_per_sample, int64_t bp_per_sample, i
         ST[lo + t] = v;
         CL[lo + t] = v;
     }
+    const int n_blocks = tc.tie ? tc.first_block[chrom + 1] - tc.first_block[chrom] : 0;
+    if (tc.tie && S == BT_TIE_S && n_blocks > 1) {
+        const int64_t flag = (int64_t)sample * n_chrom + chrom;
+        if (tc.fail && tc.fail[flag]) return;
+        tc.tol_abs *= n_blocks;
+        tc.tol_rel *= n_blocks;
+        const double *D = tc.delta + ((int64_t)sample * genes_per_sample + cd.gene_off) * S;
+        bool hit = false;
+        for (int t = threadIdx.x; t < hi - lo; t += 64) {
+            const int after = t + 1 < hi - lo ? path[t + 1] : entry;
+            hit |= decision_is_close(D + (int64_t)(lo + t) * S, tc.tprob + ((cd.trans_off + lo + t) * S + after) * (int64_t)S,
+                                     tc.tol_abs, tc.tol_rel);
+        }
+        if (c == 0 && threadIdx.x == 63) hit |= decision_is_close(D + (int64_t)(n - 1) * S, nullptr, tc.tol_abs, tc.tol_rel);
+        if (hit) tc.tie[flag] = 1;
+    }
 }
 
 #include "hmm_blocked.inc"
+static_assert(BT_TIE_S == BS_S, "the path check of backtrace_write_kernel is the blocked scan's");
 
 // Backpointers for many samples (S = 36): the SAMPLES on the lanes.  viterbi_bp_kernel gives a sample's 36 targets a
 // lane each, so every lane re-reads the sample's delta row from memory (36 loads per lane and sample, two or three
@@ -2456,6 +2526,7 @@ struct gbrs_hmm {
     bool last_blocked = false;                // the last run's backward chains started from injected vectors
     RowMap delta_rows{0, 1};                  // how the last run laid `delta` out ([sample][gene], or [gene][sample] for the large batches)
     bool last_delta_spec = false;             // the last run's delta came from the rank-convergence scheme: delta_apply_kernel is due
+    bool last_tie_check = false;              // the last run's backtrace checked the margins of its path (dspec_tie holds its flags)
     DevBuf<BlockRange> d_ranges[2];
     DevBuf<int32_t> d_first_block[2];         // blocks of chromosome c: first_block[c] .. first_block[c+1]
     DevBuf<int32_t> d_vorder[2];              // block indices, the directly chained ones first (n_head of them)
@@ -2463,6 +2534,7 @@ struct gbrs_hmm {
     std::vector<BlockRange> h_ranges0;        // host copy of d_ranges[0]
     DevBuf<double> dspec_c;                   // rank-convergence delta: every block's constant against the block before it,
     DevBuf<int32_t> dspec_g, dspec_fail;      // the gene from which its stored values stand, per (sample, chromosome) failure flags
+    DevBuf<int32_t> dspec_tie;                // per (sample, chromosome): a decision of the path inside the error of the blocks' vectors
     hipStream_t stream_h[3] = {nullptr, nullptr, nullptr};   // the direct chains of alpha / backward / delta
     hipEvent_t ev_head[3] = {nullptr, nullptr, nullptr};
     // Pipelined batch pass (round 4, hmm_launch_groups): the chromosomes in two groups of consecutive chromosomes, each with
@@ -2734,6 +2806,7 @@ int hmm_prepare_blocks(gbrs_hmm *h) {
         GBRS_TRY(h->inj_f.alloc(nb * S)); GBRS_TRY(h->inj_b.alloc(nb * S)); GBRS_TRY(h->inj_d.alloc(nb * S));
         GBRS_TRY(h->dspec_c.alloc(nb)); GBRS_TRY(h->dspec_g.alloc(nb));
         GBRS_TRY(h->dspec_fail.alloc((size_t)h->n_samples * h->n_chrom));
+        GBRS_TRY(h->dspec_tie.alloc((size_t)h->n_samples * h->n_chrom));
         h->blk_samples = h->n_samples;
     }
     return GBRS_OK;
@@ -2829,6 +2902,7 @@ int hmm_launch_groups(gbrs_hmm *h) {
     h->logs_ready = false;
     h->free_backward = true;
     h->last_blocked = false;
+    h->last_tie_check = false;
     GBRS_HIP_CHECK(hipEventRecord(h->gev_start, sa));
     GBRS_HIP_CHECK(hipEventRecord(h->ev[1], sa));
     const int ns = h->n_samples;
@@ -2930,12 +3004,14 @@ int hmm_launch(gbrs_hmm *h) {
     const dim3 bt_grid(bt_chunks, h->n_chrom, h->n_samples);
     const size_t bt_maps_lds = (size_t)BT_B * S * sizeof(uint16_t);
     const size_t bt_write_lds = ((size_t)std::max(BT_B, bt_chunks) * S + BT_B) * sizeof(uint16_t);
+    TieCheck tie_check;                        // set by the blocked scan: the backtrace then checks the margins of its path
     auto launch_backtrace = [&](hipStream_t st) {
         hipLaunchKernelGGL(backtrace_maps_kernel, bt_grid, dim3(64), bt_maps_lds, st, S, h->total_bp,
-                           h->total_chunks, h->d_chroms.p, h->bp.p, h->bt_exit.p);
+                           h->total_chunks, h->d_chroms.p, h->bp.p, h->bt_exit.p, (const int32_t *)nullptr);
         hipLaunchKernelGGL(backtrace_write_kernel, bt_grid, dim3(64), bt_write_lds, st, S, h->total_genes,
                            h->total_bp, h->total_genes + h->n_chrom, h->total_chunks, h->n_chrom, h->d_chroms.p,
-                           h->bp.p, h->bt_exit.p, h->last_state.p, h->states.p, h->calls.p, 0);
+                           h->bp.p, h->bt_exit.p, h->last_state.p, h->states.p, h->calls.p, 0, (const int32_t *)nullptr,
+                           tie_check);
     };
     const dim3 unit_grid(h->n_chrom, h->n_samples);
     hipStream_t sa = h->stream, sb = h->stream_b, sc = h->stream_c;
@@ -2956,6 +3032,7 @@ int hmm_launch(gbrs_hmm *h) {
         //                            B  free-running backward
         //                            C  delta -> backpointers -> backtrace
         std::function<void(hipStream_t)> launch_alpha, launch_back, launch_delta;
+        std::function<void(hipStream_t)> launch_tie_fallback;      // blocked scan only: behind the pass, when a flag is up
         if constexpr (WAVE) {
             constexpr int SS = SS_WAVE;
             // Few samples: one sample per wave (latency).  Many samples: HMM_SB samples share each wave's
@@ -3139,7 +3216,8 @@ int hmm_launch(gbrs_hmm *h) {
                             (void)hipStreamWaitEvent(st, h->ev_ops[1], 0);
                         }
                         hipLaunchKernelGGL(delta_guess_kernel, bgrid, dim3(64), 0, st, h->total_genes, h->n_vb, h->n_chrom,
-                                           h->d_ranges[0].p, h->eprob.p, h->inj_d.p, h->dspec_c.p, h->dspec_g.p, h->dspec_fail.p);
+                                           h->d_ranges[0].p, h->eprob.p, h->inj_d.p, h->dspec_c.p, h->dspec_g.p, h->dspec_fail.p,
+                                           h->dspec_tie.p);
                         chains(st, 0, h->n_blk[0]);
                         hipLaunchKernelGGL(delta_fixup_kernel<SS>, bgrid, dim3(64), 0, st, h->total_genes, h->n_vb, h->n_chrom,
                                            h->d_ranges[0].p, h->tprob_q.p, h->eprob.p, h->delta.p, h->dspec_c.p, h->dspec_g.p,
@@ -3150,6 +3228,7 @@ int hmm_launch(gbrs_hmm *h) {
                                            h->n_chrom, 0, (const int32_t *)h->dspec_fail.p, h->bp.p, h->total_bp);
                         return;
                     }
+                    (void)hipMemsetAsync(h->dspec_tie.p, 0, (size_t)h->n_samples * h->n_chrom * sizeof(int32_t), st);
                     if (h->n_head[0]) {
                         (void)hipStreamWaitEvent(h->stream_h[2], h->ev_fork, 0);
                         chains(h->stream_h[2], 0, h->n_head[0]);
@@ -3169,6 +3248,33 @@ int hmm_launch(gbrs_hmm *h) {
                                    h->init_vec.p, h->xsum.p, h->invz.p, h->delta.p, h->last_state.p, (const double *)nullptr,
                                    h->n_chrom, 0, (const int32_t *)nullptr, (uint16_t *)nullptr, (int64_t)0);
             };
+            // The blocked scan's vectors are the sequential chain's up to rounding (and, by rank convergence, up to the fix-up's
+            // acceptance spread), so a decision of the backtrace that the sequential chain takes by less than that - an exact
+            // tie, which its first-index rule decides, or a near-tie - may fall the other way.  The backtrace checks the
+            // margins of the path it writes (TieCheck) and raises the chromosome's flag where one is that close; the host reads
+            // the flags when the pass is done, and only if one is up do the unblocked chain and the backtrace run again, for the
+            // flagged chromosomes (three launches that would idle through every other pass).
+            if (blocked && !dlanes) {                   // launch_delta takes the samples-on-lanes chain first: no blocks' vectors then
+                tie_check.delta = h->delta.p;
+                tie_check.tprob = h->tprob.p;
+                tie_check.first_block = h->d_first_block[0].p;
+                tie_check.fail = delta_spec ? h->dspec_fail.p : nullptr;
+                tie_check.tie = h->dspec_tie.p;
+                tie_check.tol_abs = delta_tol_abs;
+                tie_check.tol_rel = delta_tol_rel;
+                launch_tie_fallback = [=](hipStream_t st) {
+                    hipLaunchKernelGGL(kf_delta, wave_grid, dim3(64), 0, st, h->n_samples, h->total_genes,
+                                       h->d_chroms.p, h->d_order.p, h->tprob_q.p, h->pprob.p, h->eprob.p, h->peprob.p,
+                                       h->init_vec.p, h->xsum.p, h->invz.p, h->delta.p, h->last_state.p, (const double *)nullptr,
+                                       h->n_chrom, 0, (const int32_t *)h->dspec_tie.p, h->bp.p, h->total_bp);
+                    hipLaunchKernelGGL(backtrace_maps_kernel, bt_grid, dim3(64), bt_maps_lds, st, S, h->total_bp,
+                                       h->total_chunks, h->d_chroms.p, h->bp.p, h->bt_exit.p, (const int32_t *)h->dspec_tie.p);
+                    hipLaunchKernelGGL(backtrace_write_kernel, bt_grid, dim3(64), bt_write_lds, st, S, h->total_genes,
+                                       h->total_bp, h->total_genes + h->n_chrom, h->total_chunks, h->n_chrom, h->d_chroms.p,
+                                       h->bp.p, h->bt_exit.p, h->last_state.p, h->states.p, h->calls.p, 0,
+                                       (const int32_t *)h->dspec_tie.p);
+                };
+            }
         } else {
             const dim3 quad_grid(h->n_samples, h->n_chrom), quad_block(threads);
             launch_alpha = [=](hipStream_t st) {
@@ -3240,7 +3346,7 @@ int hmm_launch(gbrs_hmm *h) {
         if (h->last_delta_spec)                       // behind everything that reads the blocks' vectors as the fix-up left them
             hipLaunchKernelGGL(delta_apply_kernel, dim3(h->n_blk[0], h->n_samples), dim3(64), 0, sc, h->total_genes, h->n_vb,
                                h->n_chrom, h->d_ranges[0].p, h->d_first_block[0].p, h->dspec_c.p, h->dspec_g.p,
-                               h->dspec_fail.p, h->delta.p);
+                               h->dspec_fail.p, h->dspec_tie.p, h->delta.p);
         GBRS_HIP_CHECK(hipEventRecord(h->ev_c, sc));
         GBRS_HIP_CHECK(hipStreamWaitEvent(sa, h->ev_b, 0));
         if (!skipped('p')) launch_posterior(h, sa);   // the posterior is scale free: no beta correction needed
@@ -3258,6 +3364,22 @@ int hmm_launch(gbrs_hmm *h) {
         if (hipEventElapsedTime(&ms, h->ev_fork, h->ev[3]) == hipSuccess) h->t_bwd = ms;
         if (hipEventElapsedTime(&ms, h->ev_c1, h->ev_c) == hipSuccess) h->t_bt = ms;
         if (hipEventElapsedTime(&ms, h->ev[1], h->ev[4]) == hipSuccess) h->t_run = ms;
+        h->last_tie_check = tie_check.tie && !skipped('v');
+        if (h->last_tie_check) {
+            std::vector<int32_t> tie((size_t)h->n_samples * h->n_chrom);
+            GBRS_HIP_CHECK(hipMemcpy(tie.data(), h->dspec_tie.p, tie.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+            if (std::any_of(tie.begin(), tie.end(), [](int32_t f) { return f != 0; })) {
+                GBRS_HIP_CHECK(hipEventRecord(h->ev_c1, sc));
+                launch_tie_fallback(sc);
+                GBRS_HIP_CHECK(hipEventRecord(h->ev_c, sc));
+                GBRS_HIP_CHECK(hipGetLastError());
+                GBRS_HIP_CHECK(hipStreamSynchronize(sc));
+                if (hipEventElapsedTime(&ms, h->ev_c1, h->ev_c) == hipSuccess) {      // part of the pass: in its times
+                    h->t_bt += ms;
+                    h->t_run += ms;
+                }
+            }
+        }
         return GBRS_OK;
     } else {
         hipLaunchKernelGGL((forward_viterbi_kernel<KMAX, MAXT, EXACT>), dim3(h->n_chrom, h->n_samples, 2), dim3(threads),
@@ -3566,12 +3688,21 @@ int gbrs_hmm_info(gbrs_hmm_t *h, gbrs_hmm_info_t *info) {
     info->last_run_ms = h->t_run;
     info->num_states = h->S;
     info->n_samples = h->n_samples;
+    std::vector<int32_t> tie((size_t)h->n_samples * h->n_chrom, 0);
+    if (h->last_tie_check && h->n_blk[0] > 0) {
+        // blocked scan, either delta scheme: chromosomes that a close decision of the path sent to the unblocked chain
+        GBRS_TRY(select_device(h->device));
+        GBRS_HIP_CHECK(hipMemcpy(tie.data(), h->dspec_tie.p, tie.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int32_t t : tie) info->last_delta_tie_fallbacks += t != 0;
+    }
     if (h->last_delta_spec && h->n_blk[0] > 0) {
         // how the rank-convergence delta of the last run went: blocks fixed up, the longest fix-up, chains recomputed
         GBRS_TRY(select_device(h->device));
+        // (a chromosome counts as recomputed whether a fix-up or a close decision of its path sent it to the unblocked chain)
         std::vector<int32_t> g((size_t)h->n_vb * h->n_samples), f((size_t)h->n_samples * h->n_chrom);
         GBRS_HIP_CHECK(hipMemcpy(g.data(), h->dspec_g.p, g.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
         GBRS_HIP_CHECK(hipMemcpy(f.data(), h->dspec_fail.p, f.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (size_t x = 0; x < f.size(); ++x) f[x] |= tie[x];
         int blocks = 0, longest = 0, fallbacks = 0;
         for (int s = 0; s < h->n_samples; ++s) {
             for (int v = 0; v < h->n_blk[0]; ++v) {

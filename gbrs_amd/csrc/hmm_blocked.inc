@@ -421,6 +421,10 @@ combine_maxplus_kernel(int64_t genes_per_sample, int n_blocks, const BlockRange 
 //      constant, which is all the backpointers (argmax_k(delta[k] + T[j][k])), the backtrace and argmax(delta[:, n-1]) need;
 //   4. delta_apply_kernel (after the backpointers): adds the running sums of the constants, so that `delta` holds the
 //      values of the sequential recursion (rounding of a different association, ~1e-15 relative, as with the operators).
+//   5. the backtrace (backtrace_write_kernel, TieCheck) takes best minus second best of every decision of the path it writes:
+//      a decision closer than twice the fix-up's acceptance spread - an exact tie, a near-tie: the stored vectors cannot
+//      decide it as the sequential chain does - raises the chromosome's flag, and the host, which reads the flags when the
+//      pass is done, sends the chromosome through the unblocked chain and the backtrace once more.
 // A block whose fix-up reaches its last gene without meeting the stored values (a stretch of genes without information as
 // long as a block) raises the chromosome's flag, and the unblocked chain kernel, launched behind the fix-up and idle
 // otherwise (`only_if`), recomputes that chromosome.  Measured on the synthetic samples: SURVEY's tables converge within
@@ -430,7 +434,7 @@ combine_maxplus_kernel(int64_t genes_per_sample, int n_blocks, const BlockRange 
 __global__ void __launch_bounds__(64)
 delta_guess_kernel(int64_t genes_per_sample, int n_slots, int n_chrom, const BlockRange *__restrict__ ranges,
                    const double *__restrict__ eprob, double *__restrict__ inject, double *__restrict__ c_rel,
-                   int32_t *__restrict__ gstar, int32_t *__restrict__ fail) {
+                   int32_t *__restrict__ gstar, int32_t *__restrict__ fail, int32_t *__restrict__ tie) {
     constexpr int S = BS_S;
     const BlockRange r = ranges[blockIdx.x];
     const int j = threadIdx.x, sample = blockIdx.y;
@@ -438,7 +442,7 @@ delta_guess_kernel(int64_t genes_per_sample, int n_slots, int n_chrom, const Blo
     if (j == 0) {
         c_rel[slot] = 0.0;
         gstar[slot] = r.lo;
-        if (r.lo == 0) fail[sample * n_chrom + r.chrom] = 0;
+        if (r.lo == 0) fail[sample * n_chrom + r.chrom] = tie[sample * n_chrom + r.chrom] = 0;
     }
     if (r.lo == 0 || j >= S) return;
     inject[slot * S + j] = eprob[((int64_t)sample * genes_per_sample + r.gene_off + r.lo - 1) * S + j];
@@ -529,11 +533,12 @@ delta_fixup_kernel(int64_t genes_per_sample, int n_slots, int n_chrom, const Blo
 __global__ void __launch_bounds__(64)
 delta_apply_kernel(int64_t genes_per_sample, int n_slots, int n_chrom, const BlockRange *__restrict__ ranges,
                    const int32_t *__restrict__ first_block, const double *__restrict__ c_rel,
-                   const int32_t *__restrict__ gstar, const int32_t *__restrict__ fail, double *__restrict__ delta) {
+                   const int32_t *__restrict__ gstar, const int32_t *__restrict__ fail, const int32_t *__restrict__ tie,
+                   double *__restrict__ delta) {
     constexpr int S = BS_S;
     const BlockRange r = ranges[blockIdx.x];
     const int sample = blockIdx.y;
-    if (r.lo == 0 || fail[sample * n_chrom + r.chrom]) return;
+    if (r.lo == 0 || fail[sample * n_chrom + r.chrom] || tie[sample * n_chrom + r.chrom]) return;   // recomputed: the chain's own values
     const int64_t base = (int64_t)sample * n_slots;
     double c_prev = 0.0;
     for (int u = first_block[r.chrom]; u < (int)blockIdx.x; ++u) c_prev += c_rel[base + u];

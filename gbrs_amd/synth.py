@@ -197,13 +197,15 @@ def diplotype_names(hap_names):
     return [a + b for a, b in combinations_with_replacement(hap_names, 2)]
 
 
-def _recombination_tables(rng, H, nt, structural_zeros=True):
+def _recombination_tables(rng, H, nt, structural_zeros=True, jitter=0.05):
     """DO-shaped log transition tables [nt, S, S] (T[i][to, from]): between neighbouring genes each of the
     two chromosomes of a diplotype keeps its founder with probability 1 - r and switches to one of the
     other H - 1 founders with probability r, r log-uniform over 1e-15 .. 1e-2 per interval (gene-dense
     stretches are near-deterministic, a few intervals recombine freely).  So a table holds entries from
     ~1 down to r^2 / (H-1)^2 ~ 1e-32, and - when `structural_zeros` - every fourth interval forbids double
-    switches outright (probability 0, log = -inf), as a table built by thresholding would."""
+    switches outright (probability 0, log = -inf), as a table built by thresholding would.
+    `jitter` scales every entry by 1 + jitter * U(0, 1), which breaks the exact symmetry of the model under founder
+    relabelling; jitter=0 draws nothing and keeps it, so that symmetric candidates of a Viterbi decision tie."""
     S = H * (H + 1) // 2
     pairs = list(combinations_with_replacement(range(H), 2))
     # number of founder changes between unordered pairs: best matching of the two chromosomes
@@ -216,7 +218,8 @@ def _recombination_tables(rng, H, nt, structural_zeros=True):
     for i in range(nt):
         q = r[i] / (H - 1)
         P = np.where(change == 0, (1.0 - r[i]) ** 2, np.where(change == 1, q * (1.0 - r[i]), q * q))
-        P = P * (1.0 + 0.05 * rng.random((S, S)))          # break the exact symmetry of the model
+        if jitter:
+            P = P * (1.0 + jitter * rng.random((S, S)))    # break the exact symmetry of the model
         if structural_zeros and i % 4 == 1:
             P = np.where(change == 2, 0.0, P)
         T[i] = P / P.sum(axis=0, keepdims=True)            # column-stochastic: sum over `to`
@@ -225,11 +228,12 @@ def _recombination_tables(rng, H, nt, structural_zeros=True):
 
 
 def make_hmm_problem(H=8, genes_per_chrom=None, chroms=None, seed=SEED_HMM,
-                     tprob_len_minus_one=False, style="benign", expressed_fraction=0.5) -> HmmProblem:
+                     tprob_len_minus_one=False, style="benign", expressed_fraction=0.5, jitter=0.05) -> HmmProblem:
     """style "benign": SURVEY 8d's tables (eye + 0.01 U, log entries -5 .. 0).  style "do": recombination-
     shaped tables with entries down to ~1e-32 and structural zeros (_recombination_tables).
     expressed_fraction: probability that a haplotype of a gene is expressed at all (low values give many
-    genes under the expression threshold, whose emission is the prior)."""
+    genes under the expression threshold, whose emission is the prior).  jitter: see _recombination_tables
+    (style "do" only); 0 keeps the tables exactly symmetric under founder relabelling."""
     rng = np.random.default_rng(seed)
     if genes_per_chrom is None:
         genes_per_chrom = MOUSE_GENES
@@ -245,7 +249,7 @@ def make_hmm_problem(H=8, genes_per_chrom=None, chroms=None, seed=SEED_HMM,
         gene_ids[c] = ids
         nt = n - 1 if tprob_len_minus_one else n
         if style == "do":
-            tprob[c] = _recombination_tables(rng, H, nt)
+            tprob[c] = _recombination_tables(rng, H, nt, jitter=jitter)
         else:
             T = np.eye(S)[None, :, :] + 0.01 * rng.random((nt, S, S))
             T /= T.sum(axis=1, keepdims=True)          # column-stochastic: sum over `to`

@@ -482,8 +482,11 @@ typedef struct gbrs_hmm_info {
     double   last_run_ms;
     /* Blocked scan (1-4 samples): the Viterbi values of the last run by rank convergence - blocks whose values were
      * matched to the block before them, the longest such fix-up in genes, and (sample, chromosome) pairs that were
-     * recomputed by the sequential chain because a block did not converge.  0 on every other path. */
-    int32_t  last_delta_blocks, last_delta_longest_fixup, last_delta_fallbacks, reserved0;
+     * recomputed by the sequential chain because a block did not converge or because a decision of the Viterbi path
+     * was closer than the error of the blocks' values (an exact tie, a near-tie).  0 on every other path.
+     * last_delta_tie_fallbacks: those of the pairs that were recomputed for a close decision alone (also counted when the
+     * blocked scan takes its Viterbi values from max-plus block operators, where the first three stay 0). */
+    int32_t  last_delta_blocks, last_delta_longest_fixup, last_delta_fallbacks, last_delta_tie_fallbacks;
 } gbrs_hmm_info_t;
 int gbrs_hmm_info(gbrs_hmm_t *hmm, gbrs_hmm_info_t *info);
 

@@ -14,6 +14,20 @@ What it does, per case:
   * runs oracle/em_oracle.py / oracle/hmm_oracle.py on the same input and asserts the results
     are bit-identical to the reference's (this is what pins the oracle),
   * writes inputs + expected outputs as a small .npz fixture (data only, no reference text).
+
+HMM cases: hmm_*.npz come from the generator's default tables, whose jitter removes every tie (tests/test_oracle_golden.py
+asserts a wide margin at every argmax of them).  hmmtie_*.npz (`--only hmm_tie`, hmm_tie_case) are the opposite: DO-shaped
+tables without the jitter, exactly symmetric under founder relabelling, with
+  (a) chromosomes in which no gene reaches the expression threshold (tprob of length n, of length n - 1, a single gene),
+  (b) 3-5 weakly expressed genes of one founder in an otherwise silent chromosome, with and without specificity entries,
+  (c) leading and trailing silent runs around randomly expressed genes,
+  (d) several founders with bit-equal expression in genes without specificity entries,
+at 8 founders, and (a) + (b) at 4 and 16.  There the reference's backtrace takes argmax over bit-identical candidates
+(np.argmax's first-index rule decides the call) or over candidates that differ in the last bits.  The tables are stored in
+the fixture: np.log may differ in the last bit between machines, and here the last bit is the test.  Per file the run prints
+the number of decisions with margin 0, in (0, slack] (tests/hmm_ties.py) and in all, and asserts what
+tests/test_hmm_ties_cpu.py repeats: an exact tie in every file, at most 5 % of a file's decisions inside the slack, a decision
+in (0, slack] somewhere in the set, and in hmmtie_h8_silent_only exact ties only, and only in the silent chromosomes.
 """
 import os
 import shutil
@@ -210,6 +224,15 @@ def hmm_case(name, H, genes_per_chrom, seed, len_minus_one, extra_fai_chrom=True
     prob = synth.make_hmm_problem(H=H, genes_per_chrom=genes_per_chrom, seed=seed,
                                   tprob_len_minus_one=len_minus_one, style=style,
                                   expressed_fraction=expressed_fraction)
+    hmm_reference_case("hmm_" + name, prob, len_minus_one, extra_fai_chrom)
+    print(f"hmm_{name}: H={H} genes={genes_per_chrom} len-1={len_minus_one}")
+
+
+def hmm_reference_case(stem, prob, len_minus_one, extra_fai_chrom=True):
+    """The reference's unmodified reconstruct() on `prob` through temporary files, the oracle pinned to it bit for
+    bit, inputs and expected outputs written to tests/golden/<stem>.npz.  Returns the oracle's per-chromosome arrays."""
+    H = len(prob.hap_names)
+    name = stem
     case_dir = os.path.join(WORK, name)
     os.makedirs(case_dir)
     # ref.fa.fai fixes the chromosome order; one chromosome without tprob exercises the skip
@@ -269,8 +292,90 @@ def hmm_case(name, H, genes_per_chrom, seed, len_minus_one, extra_fai_chrom=True
         out[f"avecs_{c}"] = np.array([prob.avecs.get(g, np.zeros((H, H))) for g in ids])
         for k in ("eprob", "alpha", "scaler", "beta", "gamma", "delta", "states", "calls"):
             out[f"{k}_{c}"] = res[c][k]
-    np.savez_compressed(os.path.join(GOLD, f"hmm_{name}.npz"), **out)
-    print(f"hmm_{name}: H={H} genes={genes_per_chrom} len-1={len_minus_one}")
+    np.savez_compressed(os.path.join(GOLD, f"{stem}.npz"), **out)
+    return res
+
+def tie_decision_counts(prob, res):
+    """Per chromosome (decisions with margin exactly 0, with 0 < margin <= slack, all decisions) along the reference's
+    path; the slack is tests/hmm_ties.py's."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import hmm_ties
+    counts = {}
+    for c in prob.chroms:
+        margins, slacks = hmm_ties.decision_table(prob.tprob[c], res[c]["delta"], res[c]["states"])
+        counts[c] = (int((margins == 0).sum()), int(((margins > 0) & (margins <= slacks)).sum()), len(margins))
+    return counts
+
+
+def hmm_tie_case(name, H, chrom_specs, seed, silent_only=False):
+    """A fixture whose Viterbi decisions include exact ties: DO-shaped tables WITHOUT the generator's jitter (exactly
+    symmetric under founder relabelling, as real DO tables are) and the degenerate expression of real samples.
+    chrom_specs: one dict per chromosome -
+      n                  genes
+      kind               "ordinary" (as drawn), "silent" (no gene reaches the expression threshold), "weak" (silent but
+                         for `weak` genes in which one founder is weakly expressed), "runs" (as drawn between a leading
+                         and a trailing silent run of `run` genes), "equal" (bit-equal expression of `founders` in the
+                         genes lo..hi, all of them in the rest when `rest_all`)
+      minus_one          tprob of length n - 1 instead of n
+      expressed_fraction of the draw ("ordinary", "runs")
+      avecs              "drawn" (default), "none" or "all": which genes have a specificity entry
+    Same flow as hmm_case.  Asserts the conditions of the fixture set that hold per file (tests/test_hmm_ties_cpu.py
+    repeats them) and returns the file's (zero, near, total) counts."""
+    rng = np.random.default_rng(seed)
+    probs = [synth.make_hmm_problem(H=H, genes_per_chrom=[sp["n"] for sp in chrom_specs], seed=seed + 1000 * k, style="do",
+                                    expressed_fraction=ef, jitter=0)
+             for k, ef in enumerate(sorted({sp.get("expressed_fraction", 0.5) for sp in chrom_specs}))]
+    by_ef = dict(zip(sorted({sp.get("expressed_fraction", 0.5) for sp in chrom_specs}), probs))
+    prob = probs[0]
+    silent_chroms = set()
+    for c, sp in zip(prob.chroms, chrom_specs):
+        ids, n = prob.gene_ids[c], sp["n"]
+        src = by_ef[sp.get("expressed_fraction", 0.5)]
+        prob.tprob[c] = src.tprob[c][:n - 1] if sp.get("minus_one") else src.tprob[c]
+        e = np.array([src.expr[g] for g in ids])
+        kind = sp["kind"]
+        if kind == "silent":
+            e[:] = 0.0
+            silent_chroms.add(c)
+        elif kind == "weak":
+            e[:] = 0.0
+            f = int(rng.integers(0, H))
+            for i in rng.choice(n, size=sp["weak"], replace=False):
+                e[i, f] = 1.5 + 3.0 * rng.random()
+        elif kind == "runs":
+            e[:sp["run"]] = 0.0
+            e[n - sp["run"]:] = 0.0
+        elif kind == "equal":
+            e[:] = 1.0 if sp.get("rest_all") else 0.0
+            e[sp["lo"]:sp["hi"]] = 0.0
+            e[sp["lo"]:sp["hi"], sp["founders"]] = 5.0
+        else:
+            assert kind == "ordinary", kind
+        mode = sp.get("avecs", "none" if kind == "equal" else "drawn")
+        for i, g in enumerate(ids):
+            prob.expr[g] = e[i]
+            prob.avecs.pop(g, None)
+            if mode == "all" or (mode == "drawn" and g in src.avecs):
+                a = src.avecs.get(g)
+                if a is None:
+                    a = np.eye(H) + 0.05 * rng.random((H, H))
+                    a = a / a.sum(axis=1, keepdims=True)
+                prob.avecs[g] = a
+    res = hmm_reference_case("hmmtie_" + name, prob, np.array([bool(sp.get("minus_one")) for sp in chrom_specs]))
+    counts = tie_decision_counts(prob, res)
+    zero, near, total = (sum(v[k] for v in counts.values()) for k in range(3))
+    print(f"hmmtie_{name}: H={H} genes={[sp['n'] for sp in chrom_specs]}  decisions with margin 0: {zero}, "
+          f"in (0, slack]: {near}, in all: {total}   per chromosome {list(counts.values())}")
+    assert zero >= 1, f"hmmtie_{name}: no exact tie"
+    assert zero + near <= 0.05 * total, f"hmmtie_{name}: {zero + near} of {total} decisions inside the slack"
+    if silent_only:
+        assert near == 0, f"hmmtie_{name}: a decision inside the slack that is not an exact tie"
+        assert all(counts[c][0] == 0 for c in prob.chroms if c not in silent_chroms), \
+            f"hmmtie_{name}: an exact tie outside the chromosomes whose genes all take the prior emission"
+    size = os.path.getsize(os.path.join(GOLD, f"hmmtie_{name}.npz"))
+    assert size <= 1 << 20, f"hmmtie_{name}.npz is {size} bytes"
+    return zero, near, total
+
 
 # ----------------------------------------------------------------------------- alignment counts
 
@@ -480,6 +585,37 @@ def main():
             hmm_case("h8_do_sparse_expr", 8, [90, 40], 37, False, style="do", expressed_fraction=0.12)
             hmm_case("h4_do_full", 4, [50, 21], 38, False, style="do")
         if only == "hmm_do":
+            return
+        if only in (None, "hmm_tie"):
+            # exact ties and decisions inside the rounding of delta (hmm_tie_case): jitter-free DO tables with (a) silent
+            # chromosomes, (b) a few weakly expressed genes of one founder, (c) silent runs at both ends, (d) founders with
+            # bit-equal expression; 4 and 16 founders with (a) + (b)
+            silent = [dict(n=40, kind="silent"), dict(n=35, kind="silent", minus_one=True), dict(n=1, kind="silent")]
+            tot = [
+                hmm_tie_case("h8_silent_only", 8, silent + [
+                    dict(n=60, kind="ordinary"),
+                    dict(n=80, kind="runs", run=17, expressed_fraction=0.5),
+                    dict(n=90, kind="runs", run=20, expressed_fraction=0.12)], 61, silent_only=True),
+                hmm_tie_case("h8_weak", 8, [
+                    dict(n=60, kind="weak", weak=4, avecs="none"), dict(n=60, kind="weak", weak=4, avecs="all"),
+                    dict(n=75, kind="weak", weak=3, avecs="none"), dict(n=50, kind="weak", weak=5, avecs="none", minus_one=True),
+                    dict(n=45, kind="weak", weak=5, avecs="drawn")], 62),
+                hmm_tie_case("h8_equal_founders", 8, [
+                    dict(n=60, kind="equal", lo=10, hi=50, founders=[0, 3]),
+                    dict(n=70, kind="equal", lo=20, hi=45, founders=[1, 2, 6], rest_all=True),
+                    dict(n=50, kind="equal", lo=0, hi=50, founders=list(range(8))),
+                    dict(n=60, kind="ordinary")], 63),
+                hmm_tie_case("h4_silent_weak", 4, [
+                    dict(n=30, kind="silent"), dict(n=22, kind="silent", minus_one=True), dict(n=1, kind="silent"),
+                    dict(n=40, kind="weak", weak=4, avecs="none"), dict(n=40, kind="weak", weak=3, avecs="all"),
+                    dict(n=50, kind="ordinary")], 64),
+                hmm_tie_case("h16_silent_weak", 16, [
+                    dict(n=25, kind="silent"), dict(n=20, kind="silent", minus_one=True), dict(n=1, kind="silent"),
+                    dict(n=25, kind="weak", weak=4, avecs="none"), dict(n=25, kind="weak", weak=3, avecs="all"),
+                    dict(n=25, kind="ordinary")], 65),
+            ]
+            assert sum(t[1] for t in tot) >= 1, "no fixture has a decision with 0 < margin <= slack"
+        if only == "hmm_tie":
             return
         if only in (None, "em_mask_values"):
             # stored values under a `-G` mask: multiply(gtmask, axis=2) keeps the surviving entries' values

@@ -31,6 +31,7 @@ EXPORTS = [
     "gbrs_bam_scan_records", "gbrs_bam_destroy",
     "gbrs_matops_create", "gbrs_matops_intersect", "gbrs_matops_append_rows", "gbrs_matops_keep_unique_rows",
     "gbrs_matops_mask_columns", "gbrs_matops_sizes", "gbrs_matops_get", "gbrs_matops_destroy",
+    "gbrs_matops_shared_counts", "gbrs_matops_shared_counts_get", "gbrs_matops_shared_counts_info",
     "gbrs_format_double", "gbrs_write_locus_table", "gbrs_parse_length_table", "gbrs_parse_genotype_table",
     "gbrs_decode_chunks", "gbrs_inflate_backend", "gbrs_zip_directory", "gbrs_npz_stack", "gbrs_zip_read_members", "gbrs_parse_number_table",
 ]
@@ -165,6 +166,10 @@ def load():
         "gbrs_matops_sizes": [vp, C.POINTER(u64), vp, C.POINTER(u32)],
         "gbrs_matops_get": [vp, pp, pp],
         "gbrs_matops_destroy": [vp],
+        "gbrs_matops_shared_counts": [vp, vp, u32, C.POINTER(u64)],
+        "gbrs_matops_shared_counts_get": [vp, vp, vp, vp],
+        "gbrs_matops_shared_counts_info": [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u32),
+                                           C.POINTER(u64), C.POINTER(u64), C.POINTER(dbl)],
     }
     sigs.update(_host_signatures())
     for name, args in sigs.items():

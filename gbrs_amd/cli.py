@@ -114,12 +114,21 @@ def build_parser():
     cn.add_argument('-i', '--alignment-file', required=True, type=_existing)
     cn.add_argument('-g', '--group-file', required=True, type=_existing)
     cn.add_argument('-o', '--outbase', default='emase')
+    sr = sub.add_parser('count-shared-multireads-pairwise', help='count shared multiread pairwise alignments')
+    sr.add_argument('-i', '--alignment-file', required=True, type=_existing)
+    sr.add_argument('-g', '--group-file', required=True, type=_existing)
+    sr.add_argument('-o', '--outbase', default='emase')
+    sr.add_argument('--separate-outputs', action='store_true',
+                    help='(extension) write the isoform-level matrix to <outbase>.isoforms.shared_read_counts.npz and the '
+                         'gene-level matrix to <outbase>.genes.shared_read_counts.npz.  By default both levels go to the '
+                         'isoforms name, as in the reference, so the gene-level matrix overwrites the isoform-level one '
+                         'and the isoform-level matrix is lost')
     sn = sub.add_parser('stencil', help='apply genotype calls to multi-way alignment incidence matrix')
     sn.add_argument('-i', '--alignment-file', required=True, type=_existing)
     sn.add_argument('-G', '--genotype', dest='genotype_file', required=True, type=_existing)
     sn.add_argument('-g', '--group-file', type=_existing, default=None)
     sn.add_argument('-o', '--output', dest='output_file', default=None)
-    for p in (ca, cb, pu, cn, sn):
+    for p in (ca, cb, pu, cn, sr, sn):
         p.add_argument('-v', '--verbose', action='count', default=0)
         p.add_argument('--device', type=int, default=0, help='HIP device ordinal (extension)')
     wk = sub.add_parser('worker', help='(extension) quantify -> reconstruct -> quantify -G of many samples in one resident process')
@@ -214,6 +223,11 @@ def main(argv=None) -> int:
             from .matops import count_alignments
             count_alignments(alignment_file=args.alignment_file, group_file=args.group_file, outbase=args.outbase,
                              device=args.device)
+        elif args.command == 'count-shared-multireads-pairwise':
+            from .matops import count_shared_multireads_pairwise
+            count_shared_multireads_pairwise(alignment_file=args.alignment_file, group_file=args.group_file,
+                                             outbase=args.outbase, device=args.device, stage_times=stages,
+                                             separate_outputs=args.separate_outputs)
         elif args.command == 'stencil':
             from .matops import stencil
             stencil(alignment_file=args.alignment_file, genotype_file=args.genotype_file, group_file=args.group_file,

@@ -1,5 +1,5 @@
 // rocPRIM scans and radix sorts with one reusable temporary buffer, shared by the translation units that
-// build layouts on the device (em_layout.hip, bam.hip).
+// build layouts on the device (em_layout.hip, bam.hip, matops.hip).
 #pragma once
 #include "common.h"
 
@@ -67,6 +67,31 @@ int sort_pairs_bits(Scratch &sc, const K *kin, K *kout, const uint32_t *vin, uin
     GBRS_PRIM(rocprim::radix_sort_pairs(nullptr, bytes, kin, kout, vin, vout, n, begin_bit, end_bit, s));
     GBRS_TRY(sc.reserve(bytes));
     GBRS_PRIM(rocprim::radix_sort_pairs(sc.buf.p, bytes, kin, kout, vin, vout, n, begin_bit, end_bit, s));
+    return GBRS_OK;
+}
+
+// distinct values of a sorted array, in order; *count_out (device) receives how many
+inline int unique_keys64(Scratch &sc, const uint64_t *in, uint64_t *out, uint64_t *count_out, size_t n, hipStream_t s) {
+    if (n == 0) return GBRS_OK;
+    size_t bytes = 0;
+    GBRS_PRIM(rocprim::unique(nullptr, bytes, in, out, count_out, n, rocprim::equal_to<uint64_t>(), s));
+    GBRS_TRY(sc.reserve(bytes));
+    GBRS_PRIM(rocprim::unique(sc.buf.p, bytes, in, out, count_out, n, rocprim::equal_to<uint64_t>(), s));
+    return GBRS_OK;
+}
+
+// segmented sum over runs of equal keys (keys sorted): distinct keys, their uint32 sums, *count_out (device) = runs.
+// Integer addition: the result does not depend on how the runs are cut into blocks.
+template <typename ValueIt>
+int sum_by_key64(Scratch &sc, const uint64_t *kin, ValueIt vin, uint64_t *kout, uint32_t *vout, uint64_t *count_out,
+                 size_t n, hipStream_t s) {
+    if (n == 0) return GBRS_OK;
+    size_t bytes = 0;
+    GBRS_PRIM(rocprim::reduce_by_key(nullptr, bytes, kin, vin, n, kout, vout, count_out, rocprim::plus<uint32_t>(),
+                                     rocprim::equal_to<uint64_t>(), s));
+    GBRS_TRY(sc.reserve(bytes));
+    GBRS_PRIM(rocprim::reduce_by_key(sc.buf.p, bytes, kin, vin, n, kout, vout, count_out, rocprim::plus<uint32_t>(),
+                                     rocprim::equal_to<uint64_t>(), s));
     return GBRS_OK;
 }
 

@@ -1,6 +1,7 @@
 """Commands that edit the structure of an alignment incidence tensor and write it back in the EMASE format:
 `get-common-alignments`, `combine`, `pull-out-unique-reads` (emase/emase_utils.py:236-274, :73-111, :277-317), `stencil`
-(gbrs/emase_utils.py:110-177) and the `count-alignments` wrapper (emase/emase_utils.py:114-139).  Same argument names,
+(gbrs/emase_utils.py:110-177), the `count-alignments` wrapper (emase/emase_utils.py:114-139) and
+`count-shared-multireads-pairwise` (emase/emase_utils.py:142-176), which reads the tensor and writes count matrices.  Same argument names,
 defaults and log lines as the reference plus `device`; the edits run in HIP (gbrs_matops_*, gbrs_amd/csrc/matops.hip) and
 there is no CPU fallback.  Everything that needs no device - shapes, read names, stored values, group files - is checked
 before the first device call.  `stage_times` (optional dict, as for bam2emase) receives the wall-clock seconds of the
@@ -62,6 +63,33 @@ class MatOps:
             raise RuntimeError('The haplotype mask does not match to the matrix shape.')
         _lib.check(self._lib.gbrs_matops_mask_columns(self._h, _lib.ptr(allowed)))
 
+    def shared_counts(self, locus_group=None, num_groups=0):
+        """(indptr int64[n + 1], indices int32[nnz], data float64[nnz], n) of C = P^T P in CSR form, both triangles,
+        column ids ascending inside every row: C[i, j] = the reads with an entry at columns i and j in any haplotype.
+        A column is a locus (n = L), or with locus_group (int[L], -1 = in no group) a group (n = num_groups).  The
+        tensor is left as it is; shared_counts_info() tells how the call went."""
+        group = _checked_group_map(locus_group, self.L)
+        n = self.L if group is None else int(num_groups)
+        nnz = C.c_uint64(0)
+        _lib.check(self._lib.gbrs_matops_shared_counts(self._h, _lib.ptr(group), int(num_groups) if group is not None else 0,
+                                                       C.byref(nnz)))
+        indptr = np.zeros(n + 1, dtype=np.uint64)
+        indices = np.zeros(nnz.value, dtype=np.uint32)
+        data = np.zeros(nnz.value, dtype=np.float64)
+        _lib.check(self._lib.gbrs_matops_shared_counts_get(self._h, _lib.ptr(indptr), _lib.ptr(indices), _lib.ptr(data)))
+        return indptr.astype(np.int64), indices.astype(np.int32 if n <= 0x7FFFFFFF else np.int64), data, n
+
+    def shared_counts_info(self):
+        """The last shared_counts call: columns, distinct (read, column) entries, pairs emitted, batches, the pair
+        budget of a batch, peak device bytes of the call (sampled) and its milliseconds on the device."""
+        n, ent, pairs, budget, peak = (C.c_uint64(0) for _ in range(5))
+        batches, ms = C.c_uint32(0), C.c_double(0.0)
+        _lib.check(self._lib.gbrs_matops_shared_counts_info(self._h, C.byref(n), C.byref(ent), C.byref(pairs),
+                                                            C.byref(batches), C.byref(budget), C.byref(peak), C.byref(ms)))
+        return dict(num_columns=int(n.value), pattern_entries=int(ent.value), pairs_emitted=int(pairs.value),
+                    batches=int(batches.value), pair_budget=int(budget.value), peak_device_bytes=int(peak.value),
+                    device_ms=float(ms.value))
+
     def sizes(self):
         """(R, entries per haplotype uint64[H], haplotype arrays given so far that needed the radix sort)."""
         R, srt = C.c_uint64(0), C.c_uint32(0)
@@ -93,6 +121,16 @@ class MatOps:
             self.close()
         except Exception:
             pass
+
+
+def _checked_group_map(locus_group, L):
+    """The locus-to-group map as contiguous int32[L] (None stays None); another shape is refused here, on the host."""
+    if locus_group is None:
+        return None
+    group = np.ascontiguousarray(locus_group, dtype=np.int32)
+    if group.shape != (L,):
+        raise RuntimeError('The locus-to-group map does not match to the matrix shape.')
+    return group
 
 
 class _Stages:
@@ -328,4 +366,77 @@ def count_alignments(alignment_file: str, group_file: str, outbase: str = 'emase
             path = f'{outbase}.{level}s.alignment_counts'
             logger.info(f'Generating {level} Alignment Counts: {path}')
             report_alignment_counts(apm, path, grp_wise=grp_wise, device=device, counter=counter)
+    logger.info('Done')
+
+
+def save_shared_counts(path: str, indptr, indices, data, n: int) -> str:
+    """One shared-read-count matrix as `<path>` (`.npz` is appended when missing, as numpy does).  Always the plain
+    members `indptr`, `indices`, `data` and `shape` of the n x n CSR matrix, readable with allow_pickle=False.  Where
+    scipy can be imported also `counts`, what the reference's `np.savez_compressed(name, counts=cnt_mat)` leaves: a 0-d
+    object array with the pickled float64 `scipy.sparse.csr_matrix`.  Without scipy `counts` is left out and one
+    warning says so.  Needs no device.  Returns the path written."""
+    if not path.endswith('.npz'):
+        path += '.npz'
+    indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+    indices = np.ascontiguousarray(indices, dtype=np.int32 if n <= 0x7FFFFFFF else np.int64)
+    data = np.ascontiguousarray(data, dtype=np.float64)
+    if indptr.shape != (n + 1,) or indices.shape != data.shape or int(indptr[-1]) != len(data):
+        raise RuntimeError('The count matrix arrays do not match to its shape.')
+    members = dict(indptr=indptr, indices=indices, data=data, shape=np.array([n, n], dtype=np.int64))
+    try:
+        from scipy.sparse import csr_matrix
+    except ImportError:
+        logger.warning(f'scipy is not available: {path} holds indptr/indices/data/shape only, not the pickled '
+                       '`counts` matrix.')
+    else:
+        members['counts'] = csr_matrix((data, indices, indptr), shape=(n, n))
+    np.savez_compressed(path, **members)
+    return path
+
+
+def shared_counts_paths(outbase: str = 'emase', separate_outputs: bool = False):
+    """(isoform-level path, gene-level path) without `.npz`.  The reference gives both levels one name
+    (emase/emase_utils.py:164, :171), so its gene-level matrix overwrites the isoform-level one; that is the default."""
+    iso = f'{outbase}.isoforms.shared_read_counts'
+    return iso, (f'{outbase}.genes.shared_read_counts' if separate_outputs else iso)
+
+
+def count_shared_multireads_pairwise(alignment_file: str, group_file: str, outbase: str = 'emase', device: int = 0,
+                                     stage_times: dict = None, separate_outputs: bool = False) -> None:
+    """For every pair of loci, then for every pair of genes, the number of reads that align to both, in any haplotype
+    (emase/emase_utils.py:142-176); the diagonal holds the reads per locus / gene.  Stored values are ignored (an
+    entry counts as present) and so is a `count` vector: every row counts once, as in the reference.  By default a run
+    leaves what the reference leaves - `<outbase>.isoforms.shared_read_counts.npz` holding the GENE-level matrix, which
+    has overwritten the isoform-level one; `separate_outputs` keeps both (`...isoforms...` and `...genes...`)."""
+    logger.info(f'Alignment File: {alignment_file}')
+    logger.info(f'Group File: {group_file}')
+    logger.info(f'Outbase: {outbase}')
+    if group_file is None:
+        raise RuntimeError('count-shared-multireads-pairwise needs a group file.')
+    st = _Stages(stage_times)
+    _lib.warm_up_device_async(device)
+    logger.info(f'Loading EMASE file: {alignment_file}')
+    apm = load_alignment(alignment_file, grpfile=group_file)
+    logger.debug(f'Number Loci: {apm.num_loci}')
+    logger.debug(f'Number Haplotypes: {apm.num_haplotypes}')
+    logger.debug(f'Number Reads: {apm.num_reads}')
+    from .counts import _group_map
+    group, _ = _group_map(apm)                       # a locus in two groups is refused before the device is opened
+    if apm.count is not None:
+        logger.info('The alignment file carries a count vector; as in the reference it is ignored and every row counts once.')
+    outfile1, outfile2 = shared_counts_paths(outbase, separate_outputs)
+    st.mark('load')
+    with MatOps(apm, device=device) as dev:
+        st.mark('upload')
+        for level, path, grp in (('isoform', outfile1, None), ('genes', outfile2, group)):
+            logger.info(f'Generating {level} Shared Read Counts: {path}')
+            indptr, indices, data, n = dev.shared_counts(grp, apm.num_groups if grp is not None else 0)
+            info = dev.shared_counts_info()
+            logger.debug(f'{n} columns, {len(data)} stored counts, {info["pairs_emitted"]} pairs in {info["batches"]} '
+                         f'batches, {info["device_ms"]:.1f} ms on the device')
+            if stage_times is not None:
+                stage_times[f'shared_counts_{level}'] = dict(info, nnz=int(len(data)))
+            st.mark('kernels')
+            save_shared_counts(path, indptr, indices, data, n)
+            st.mark('write')
     logger.info('Done')

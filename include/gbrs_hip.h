@@ -373,7 +373,28 @@ int gbrs_compress_destroy(gbrs_compress_t *c);
  * Every operand's row ids are range-checked on the device before a kernel indexes with them and its column pointer
  * tables are checked on the host (GBRS_ERR_INVALID); the row ids of every result ascend inside every column (what
  * scipy returns for the four operations); 2^32 or more rows, or entries of one haplotype, is GBRS_ERR_UNSUPPORTED;
- * there is no CPU fallback (GBRS_ERR_NO_DEVICE).  After a failed edit the handle is only good for destroy. */
+ * there is no CPU fallback (GBRS_ERR_NO_DEVICE).  After a failed edit the handle is only good for destroy.
+ *
+ * `count-shared-multireads-pairwise` (emase/emase_utils.py:142-176: `hapsum.T * hapsum` with the stored values set to
+ * one) reads the tensor and leaves it untouched:
+ *   shared_counts      C = P^T P for the tensor as it stands, P the R x n pattern matrix: P[r, c] = 1 when row r has a
+ *                      stored entry at column c in any haplotype.  locus_group NULL: n = L, a column is a locus.
+ *                      Otherwise (int32[L], -1 = in no group; num_groups = G >= 1) n = G, a column is a group - the
+ *                      matrix after _bundle_inline(reset=True) - and entries of loci in no group drop out.  C[i][i] is
+ *                      the number of rows at column i, C[i][j] the number of rows at both.  Every row counts once.
+ *                      The result stays on the device until the next shared_counts call or destroy; nnz_out
+ *                      (nullable) receives its number of stored entries.  Counts are added up as 32-bit integers (a
+ *                      count is at most R < 2^32) without atomics: exact, and identical from run to run.
+ *   shared_counts_get  the result as CSR with both triangles, the column ids ascending inside every row and no stored
+ *                      zero: indptr_out uint64[n + 1], indices_out uint32[nnz], data_out double[nnz].
+ *   shared_counts_info how the last shared_counts call went (any pointer may be NULL): n, the distinct (row, column)
+ *                      entries of P, the pairs (i <= j) emitted, the batches they were emitted and reduced in, the pair
+ *                      budget of a batch, the peak of device bytes the call held (sampled after its large allocations)
+ *                      and the milliseconds between its first and last device operation.
+ * The pairs of all rows form one index space that is cut into batches of at most `budget` pairs, so the memory is
+ * bounded whatever the sample and a single row with more pairs than the budget is split like any other stretch.  The
+ * budget is 1/64 of the free device memory, in pairs, between 2^20 and 2^31; GBRS_SHARED_PAIR_BUDGET=<pairs> overrides
+ * it (GBRS_ERR_INVALID when it is not a positive integer).  get and info before any shared_counts: GBRS_ERR_INVALID. */
 typedef struct gbrs_matops gbrs_matops_t;
 int gbrs_matops_create(uint64_t num_rows, uint32_t num_loci, uint32_t num_haps, const uint32_t *const *indptr,
                        const uint32_t *const *indices, int device, gbrs_matops_t **out);
@@ -385,6 +406,11 @@ int gbrs_matops_keep_unique_rows(gbrs_matops_t *m, const int32_t *locus_group, u
 int gbrs_matops_mask_columns(gbrs_matops_t *m, const uint32_t *allowed);
 int gbrs_matops_sizes(gbrs_matops_t *m, uint64_t *num_rows, uint64_t *nnz_per_hap, uint32_t *sorted_inputs);
 int gbrs_matops_get(gbrs_matops_t *m, uint32_t *const *indptr_out, uint32_t *const *indices_out);
+int gbrs_matops_shared_counts(gbrs_matops_t *m, const int32_t *locus_group, uint32_t num_groups, uint64_t *nnz_out);
+int gbrs_matops_shared_counts_get(gbrs_matops_t *m, uint64_t *indptr_out, uint32_t *indices_out, double *data_out);
+int gbrs_matops_shared_counts_info(gbrs_matops_t *m, uint64_t *num_columns, uint64_t *pattern_entries,
+                                   uint64_t *pairs_emitted, uint32_t *batches, uint64_t *pair_budget,
+                                   uint64_t *peak_device_bytes, double *device_ms);
 int gbrs_matops_destroy(gbrs_matops_t *m);
 
 /* `gbrs bam2emase` (emase/AlignmentMatrixFactory.py:26-142): a BAM file -> the per-haplotype CSC incidence

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("GBRS_TUNING_LIB") or os.path.join(_HERE, "libgbrs_hip
 EXPORTS = [
     "gbrs_last_error", "gbrs_abi_version", "gbrs_device_count", "gbrs_warm_up",
     "gbrs_em_create", "gbrs_em_create_device", "gbrs_em_create_masked", "gbrs_em_create_masked_device", "gbrs_em_set_initial_values", "gbrs_em_prepare", "gbrs_em_step", "gbrs_em_run",
-    "gbrs_em_set_groups", "gbrs_em_step_model",
+    "gbrs_em_set_groups", "gbrs_em_step_model", "gbrs_em_posterior",
     "gbrs_em_get", "gbrs_em_set_theta", "gbrs_em_group_sums", "gbrs_em_estep_partial",
     "gbrs_em_finish_step", "gbrs_em_prepare_partial", "gbrs_em_finish_prepare", "gbrs_em_stream",
     "gbrs_em_set_stream",
@@ -56,6 +56,7 @@ GBRS_EM_SIDE_BY_SIDE = 128
 GBRS_EM_ONE_SHOT = 256
 GBRS_EM_NO_LOCUS_SETS = 512
 GBRS_EM_GROUPED_MODELS = 1024
+GBRS_EM_POSTERIOR = 2048
 
 
 class EmInfo(C.Structure):
@@ -123,6 +124,7 @@ def load():
         "gbrs_em_run": [vp, i32, dbl, i32, C.POINTER(i32), vp, i32, vp],
         "gbrs_em_set_groups": [vp, i64, vp, vp],
         "gbrs_em_step_model": [vp, i32, i32, C.POINTER(dbl)],
+        "gbrs_em_posterior": [vp, u32, vp, u64],
         "gbrs_em_get": [vp, vp, vp],
         "gbrs_em_set_theta": [vp, vp],
         "gbrs_em_group_sums": [vp, i64, vp, vp, i32, vp],

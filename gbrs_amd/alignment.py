@@ -224,7 +224,9 @@ class AlignmentPropertyMatrix:
         finally:
             z.close()
 
-    def save_npz(self, path):
+    def save_npz(self, path, values=None, **_ignored):
+        """`values` (optional): a sequence of H arrays or a callable `h -> array` written as `values{h}` in place of
+        self.values."""
         self.apply_haplotype_mask()
         out = dict(shape=np.asarray(self.shape, dtype=np.int64))
         for h in range(self.num_haplotypes):
@@ -232,7 +234,7 @@ class AlignmentPropertyMatrix:
             out[f'indices{h}'] = self.indices[h]
         if self.count is not None:
             out['count'] = self.count
-        if self.values is not None:
+        if values is None and self.values is not None:
             for h in range(self.num_haplotypes):
                 out[f'values{h}'] = self.values[h]
         if self.hname is not None:
@@ -241,11 +243,27 @@ class AlignmentPropertyMatrix:
             out['lname'] = np.array(self.lname)
         if self.rname is not None:
             out['rname'] = np.asarray(self.rname, dtype='S')
-        np.savez_compressed(path, **out)
+        if values is None:
+            np.savez_compressed(path, **out)
+            return
+        # one haplotype's values on the host at a time: the members are written one by one
+        import zipfile
+        from . import emase_h5
+        provider = emase_h5.value_provider(values, self.num_haplotypes)
+        with zipfile.ZipFile(path, 'w', compression=zipfile.ZIP_DEFLATED, allowZip64=True) as z:
+            def put(name, arr):
+                with z.open(name + '.npy', 'w', force_zip64=True) as fh:
+                    np.lib.format.write_array(fh, np.asanyarray(arr), allow_pickle=False)
+            for name, arr in out.items():
+                put(name, arr)
+            for h in range(self.num_haplotypes):
+                put(f'values{h}', emase_h5.fetch_values(provider, self, h))
 
     def save(self, h5file, **kw):
+        """`values=` (a sequence or a callable `h -> array`, with incidence_only=False for an .h5) writes these
+        per-haplotype values, lined up with the masked index arrays, in place of self.values."""
         if str(h5file).endswith('.npz'):
-            return self.save_npz(h5file)
+            return self.save_npz(h5file, values=kw.get('values'))
         from . import emase_h5
         self.apply_haplotype_mask()
         emase_h5.save(self, h5file, **kw)

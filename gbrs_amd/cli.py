@@ -41,7 +41,12 @@ def build_parser():
     q.add_argument('-m', '--max-iters', type=int, default=999)
     q.add_argument('-t', '--tolerance', type=float, default=0.0001)
     q.add_argument('-a', '--report-alignment-counts', action='store_true')
-    q.add_argument('-w', '--report-posterior', action='store_true')
+    q.add_argument('-w', '--report-posterior', action='store_true',
+                   help='write <outbase>.posterior.h5.  As in the reference the file holds the alignment structure '
+                        'alone (incidence_only), no posterior values: see --posterior-values')
+    q.add_argument('--posterior-values', action='store_true',
+                   help='(extension, implies -w) <outbase>.posterior.h5 carries the read-level posterior of every stored '
+                        'alignment in the last E-step as /h*/data, computed on the device')
     q.add_argument('-v', '--verbose', action='count', default=0)
     q.add_argument('--device', type=int, default=0, help='HIP device ordinal (extension)')
     q.add_argument('--merge-identical-rows', action='store_true',
@@ -181,7 +186,8 @@ def main(argv=None) -> int:
                      multiread_model=args.multiread_model, pseudocount=args.pseudocount,
                      max_iters=args.max_iters, tolerance=args.tolerance,
                      report_alignment_counts=args.report_alignment_counts,
-                     report_posterior=args.report_posterior, device=args.device,
+                     report_posterior=args.report_posterior or args.posterior_values,
+                     posterior_values=args.posterior_values, device=args.device,
                      merge_identical_rows=args.merge_identical_rows, stage_times=stages,
                      one_shot=True)         # the command builds one handle and exits: GBRS_EM_ONE_SHOT
         elif args.command == 'worker':

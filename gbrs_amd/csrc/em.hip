@@ -459,6 +459,60 @@ csc_rowstat_kernel(uint64_t n, uint32_t ncols, uint32_t L, const uint64_t *__res
     if (k < n) atomicAdd(&nnz_row[ent_row[k]], 1u);
 }
 
+// ------------------------------------------------------------------------------------------
+// Read-level posteriors (gbrs_em_posterior, GBRS_EM_POSTERIOR).  The E-steps above never form the posterior of a
+// stored entry; these passes do, after the fact, on the kept CSC arrays and the theta the last step started from, so
+// the result is the same whichever layout the EM itself ran on.
+// ------------------------------------------------------------------------------------------
+
+// theta before a step.  Launched behind the previous step's error pass, so a step that the stopping rule turned into
+// a no-op leaves the kept theta alone, as it leaves theta alone.
+__global__ void __launch_bounds__(256)
+keep_theta_kernel(uint64_t n, const double *__restrict__ theta, double *__restrict__ kept,
+                  const EmScalars *__restrict__ sc) {
+    if (sc->stop) return;
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) kept[i] = theta[i];
+}
+
+// Model 4: D_r = sum of the kept theta over the read's entries (csc_den_kernel on the kept theta, no stop flag)
+__global__ void __launch_bounds__(256)
+post_den_kernel(uint64_t n, uint32_t ncols, uint32_t L, uint32_t H, const uint64_t *__restrict__ col_ptr,
+                const uint32_t *__restrict__ ent_row, const double *__restrict__ kept, double *__restrict__ den) {
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k - (threadIdx.x & 63) >= n) return;
+    const bool live = k < n;
+    const uint32_t c = entry_column(col_ptr, ncols, live ? k : n - 1, n);
+    if (!live) return;
+    const uint32_t h = c / L, l = c - h * L;
+    atomicAdd(&den[ent_row[k]], kept[(size_t)l * H + h]);
+}
+
+// One double per entry of haplotype `hap`: the entries [k0, k1) of the CSC arrays, out[k - k0].  A wavefront holds 64
+// consecutive entries, nearly always of one column (entry_column), so theta is one broadcast load, the row ids and
+// the output are coalesced streams and the denominators (model 4) or the step's factors (models 1-3) the gather.
+//   model 4     theta / D_r
+//   models 1-3  theta * fac / count[r]: model_row_kernel stored fac = count[r] f / D_r at the entry (0 where theta is 0)
+template <bool MODEL4>
+__global__ void __launch_bounds__(256)
+post_value_kernel(uint64_t k0, uint64_t k1, uint32_t ncols, uint32_t L, uint32_t H, uint32_t hap,
+                  const uint64_t *__restrict__ col_ptr, const uint32_t *__restrict__ ent_row,
+                  const double *__restrict__ kept, const double *__restrict__ den, const double *__restrict__ fac,
+                  const double *__restrict__ count, double *__restrict__ out) {
+    const uint64_t k = k0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k - (threadIdx.x & 63) >= k1) return;
+    const bool live = k < k1;
+    const uint32_t c = entry_column(col_ptr, ncols, live ? k : k1 - 1, k1);
+    if (!live) return;
+    const uint32_t l = c - hap * L;
+    const double t = kept[(size_t)l * H + hap];
+    const uint32_t r = ent_row[k];
+    double v;
+    if (MODEL4) v = t == 0.0 ? 0.0 : t / den[r];
+    else v = t * (fac[k] / (count ? count[r] : 1.0));
+    out[k - k0] = v;
+}
+
 #include "em_tiles.inc"
 #include "em_models.inc"
 
@@ -538,6 +592,12 @@ struct gbrs_em {
     DevBuf<uint32_t> rank_m1, inv_m1, rank_m23, inv_m23;
     GroupedOrder order_m1, order_m23;               // built at the first step of a model that uses it
     DevBuf<double> gene_tot, gene_hap_tot, locus_tot, fac;   // T (genes), Y (genes x H), U (L), per-entry factors (N)
+
+    // Read-level posteriors (GBRS_EM_POSTERIOR, gbrs_em_posterior): theta before the last step, the per-read
+    // denominators of that step (model 4; made at the first request after it) and one haplotype's values.
+    DevBuf<double> theta_kept, post_den, post_vals;  // L*H locus-major ; R ; the longest haplotype's entries
+    int post_model = 0;                              // model of the last step through gbrs_em_step / _step_model / _run; 0: none
+    bool post_den_valid = false;
 
     int red_blocks() const { return (int)std::min<uint64_t>(RED_BLOCKS, (L + RED_THREADS - 1) / RED_THREADS); }
 };
@@ -957,11 +1017,26 @@ int em_finish_step(gbrs_em *em, double target_err, bool defer = false, bool fuse
     return GBRS_OK;
 }
 
+// GBRS_EM_POSTERIOR: theta before the step that is about to be enqueued.  The deferred error pass of the previous step
+// runs first, so that the copy sees that step's stop flag.
+int em_keep_theta(gbrs_em *em, int model) {
+    if (!(em->flags & GBRS_EM_POSTERIOR)) return GBRS_OK;
+    GBRS_TRY(em_flush_err(em));
+    const uint64_t n = (uint64_t)em->L * em->H;
+    hipLaunchKernelGGL(keep_theta_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, em->stream, n, em->theta.p,
+                       em->theta_kept.p, em->scalars.p);
+    GBRS_HIP_CHECK(hipGetLastError());
+    em->post_model = model;
+    em->post_den_valid = false;
+    return GBRS_OK;
+}
+
 // One iteration; `ev` (3 events) times it.  An event record is a barrier packet that costs the
 // queue ~4 us of idle time on this hardware, so callers time a sample of the iterations (every
 // EM_TIME_STRIDE-th), not each one.
 constexpr int EM_TIME_STRIDE = 8;
 int em_one_step(gbrs_em *em, double target_err, hipEvent_t *ev = nullptr, bool defer_err = false) {
+    GBRS_TRY(em_keep_theta(em, 4));
     const bool timed = ev != nullptr && em->time_steps;
     if (timed) GBRS_HIP_CHECK(hipEventRecord(ev[0], em->stream));
     // ev[1] closes the E-step kernel itself (tile layout: before the gather; CSC layout: after the pass)
@@ -1051,6 +1126,7 @@ int em_ensure_order(gbrs_em *em, int model) {
 // One step of model 1, 2 or 3 (the order must be built); `ev` (3 events, nullable) times it as em_one_step does.
 int em_model_step(gbrs_em *em, int model, double target_err, hipEvent_t *ev = nullptr) {
     GBRS_TRY(em_flush_err(em));
+    GBRS_TRY(em_keep_theta(em, model));
     const GroupedOrder &o = model == 1 ? em->order_m1 : em->order_m23;
     const bool timed = ev != nullptr && em->time_steps;
     if (timed) GBRS_HIP_CHECK(hipEventRecord(ev[0], em->stream));
@@ -1206,6 +1282,10 @@ int em_create_impl(uint64_t R, uint32_t L, uint32_t H, const uint32_t *const *in
     em->msum_cap = (uint32_t)(((uint64_t)L * H + RED_THREADS - 1) / RED_THREADS * 2 + L + RED_BLOCKS);   // elementwise + light workgroups + one per many-slot locus
     GBRS_TRY(em->msums.alloc(2 * (size_t)em->msum_cap + ERR_BLOCKS));
     GBRS_TRY(em->scalars.alloc(1));
+    if (flags & GBRS_EM_POSTERIOR) {
+        GBRS_TRY(em->theta_kept.alloc(LH));
+        GBRS_TRY(em->post_den.alloc(R));
+    }
     GBRS_HIP_CHECK(hipMemset(em->scalars.p, 0, sizeof(EmScalars)));
     GBRS_HIP_CHECK(hipMemset(em->theta.p, 0, em->theta.bytes()));
     GBRS_HIP_CHECK(hipMemset(em->acc.p, 0, em->acc.bytes()));
@@ -1277,8 +1357,9 @@ int em_create_impl(uint64_t R, uint32_t L, uint32_t H, const uint32_t *const *in
         // the CSC copy and the per-row denominators are only needed by layout 0 (and, until
         // gbrs_em_set_initial_values has run, when the caller announced stored values)
         em->keep_csc = (flags & GBRS_EM_KEEP_CSC) != 0;
-        // (models 1-3 build their layout from the row ids: GBRS_EM_GROUPED_MODELS keeps them)
-        const bool keep_rows = (flags & GBRS_EM_GROUPED_MODELS) != 0;
+        // (models 1-3 build their layout from the row ids: GBRS_EM_GROUPED_MODELS keeps them; the posterior passes
+        // walk them: GBRS_EM_POSTERIOR keeps them)
+        const bool keep_rows = (flags & (GBRS_EM_GROUPED_MODELS | GBRS_EM_POSTERIOR)) != 0;
         if (!em->keep_csc) {
             if (em->tl.retain_temporaries) {  // one-shot process: left to the handle's destructor (common.h, DeferFrees)
                 DeferFrees with_the_layout(&em->tl.retired, &em->tl.retired_bytes);
@@ -1403,6 +1484,7 @@ namespace {
 int em_prepare_partial(gbrs_em *em) {
     GBRS_TRY(select_device(em->device));
     GBRS_TRY(em_reset_scalars(em, false));
+    em->post_model = 0;                       // no E-step since this prepare: nothing for gbrs_em_posterior
     if (em->has_init) {                       // stored alignment values: their normalised column sums
         GBRS_HIP_CHECK(hipMemcpyAsync(em->acc.p, em->acc_init.p, em->acc.bytes(), hipMemcpyDeviceToDevice, em->stream));
         em->acc_needs_extra = false;
@@ -1466,7 +1548,7 @@ int gbrs_em_set_initial_values(gbrs_em_t *em, const double *const *values) {
     }
     em->has_init = true;
     if (em->layout == 1 && em->keep_csc) {     // the tiled layout needs neither array from here on
-        if (!(em->flags & GBRS_EM_GROUPED_MODELS)) em->ent_row.release();
+        if (!(em->flags & (GBRS_EM_GROUPED_MODELS | GBRS_EM_POSTERIOR))) em->ent_row.release();
         em->den.release();
         em->col_ptr_src.release();
         em->keep_csc = false;
@@ -1721,6 +1803,59 @@ int gbrs_em_get(gbrs_em_t *em, double *theta, double *expected_counts) {
         GBRS_HIP_CHECK(hipMemcpyAsync(dst, em->scratch_hl.p, LH * sizeof(double), hipMemcpyDeviceToHost, em->stream));
         GBRS_HIP_CHECK(hipStreamSynchronize(em->stream));
     }
+    return GBRS_OK;
+}
+
+int gbrs_em_posterior(gbrs_em_t *em, uint32_t hap, double *out, uint64_t out_len) {
+    RoctxRange roctx_range("gbrs_em_posterior");
+    if (!em) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (!(em->flags & GBRS_EM_POSTERIOR))
+        return fail(GBRS_ERR_STATE, "the handle was not created with GBRS_EM_POSTERIOR");
+    if (em->post_model == 0) return fail(GBRS_ERR_STATE, "no EM step has run since prepare: there is no posterior yet");
+    if (hap >= em->H) return fail(GBRS_ERR_INVALID, "haplotype %u >= num_haps %u", hap, em->H);
+    GBRS_TRY(select_device(em->device));
+    GBRS_TRY(em_flush_err(em));
+    const uint32_t L = em->L, H = em->H, ncols = H * L;
+    uint64_t k0 = 0, k1 = 0;                   // the haplotype's columns are one piece of the concatenated arrays
+    GBRS_HIP_CHECK(hipMemcpyAsync(&k0, em->col_ptr.p + (size_t)hap * L, sizeof(k0), hipMemcpyDeviceToHost, em->stream));
+    GBRS_HIP_CHECK(hipMemcpyAsync(&k1, em->col_ptr.p + (size_t)(hap + 1) * L, sizeof(k1), hipMemcpyDeviceToHost, em->stream));
+    GBRS_HIP_CHECK(hipStreamSynchronize(em->stream));
+    if (k1 < k0 || k1 > em->N) return fail(GBRS_ERR_STATE, "the kept column pointers are damaged");
+    const uint64_t n_h = k1 - k0;
+    if (out_len != n_h)
+        return fail(GBRS_ERR_INVALID, "out_len is %llu, haplotype %u has %llu stored entries", (unsigned long long)out_len,
+                    hap, (unsigned long long)n_h);
+    if (n_h == 0) return GBRS_OK;
+    if (!out) return fail(GBRS_ERR_INVALID, "out is NULL");
+    if (!em->ent_row.p) return fail(GBRS_ERR_STATE, "the handle no longer holds the CSC row ids");
+    const bool model4 = em->post_model == 4;
+    if (!model4 && !em->fac.p) return fail(GBRS_ERR_STATE, "the handle holds no factors of a model %d step", em->post_model);
+    if (model4 && !em->post_den_valid) {       // once per step, shared by the calls for the H haplotypes
+        GBRS_HIP_CHECK(hipMemsetAsync(em->post_den.p, 0, em->post_den.bytes(), em->stream));
+        hipLaunchKernelGGL(post_den_kernel, dim3((unsigned)((em->N + 255) / 256)), dim3(256), 0, em->stream, em->N, ncols,
+                           L, H, em->col_ptr.p, em->ent_row.p, em->theta_kept.p, em->post_den.p);
+        GBRS_HIP_CHECK(hipGetLastError());
+        em->post_den_valid = true;
+    }
+    if (em->post_vals.n < n_h) {               // one haplotype's values at a time: sized for the longest one
+        std::vector<uint64_t> cp((size_t)ncols + 1);
+        GBRS_HIP_CHECK(hipMemcpy(cp.data(), em->col_ptr.p, cp.size() * 8, hipMemcpyDeviceToHost));
+        uint64_t longest = 0;
+        for (uint32_t h = 0; h < H; ++h) longest = std::max(longest, cp[(size_t)(h + 1) * L] - cp[(size_t)h * L]);
+        GBRS_HIP_CHECK(hipStreamSynchronize(em->stream));
+        GBRS_TRY(em->post_vals.alloc(longest));
+    }
+    const dim3 grid((unsigned)((n_h + 255) / 256));
+    const double *cnt = em->has_count ? em->count.p : (const double *)nullptr;
+    if (model4)
+        hipLaunchKernelGGL(post_value_kernel<true>, grid, dim3(256), 0, em->stream, k0, k1, ncols, L, H, hap, em->col_ptr.p,
+                           em->ent_row.p, em->theta_kept.p, em->post_den.p, (const double *)nullptr, cnt, em->post_vals.p);
+    else
+        hipLaunchKernelGGL(post_value_kernel<false>, grid, dim3(256), 0, em->stream, k0, k1, ncols, L, H, hap, em->col_ptr.p,
+                           em->ent_row.p, em->theta_kept.p, (const double *)nullptr, em->fac.p, cnt, em->post_vals.p);
+    GBRS_HIP_CHECK(hipGetLastError());
+    GBRS_HIP_CHECK(hipMemcpyAsync(out, em->post_vals.p, n_h * sizeof(double), hipMemcpyDeviceToHost, em->stream));
+    GBRS_HIP_CHECK(hipStreamSynchronize(em->stream));
     return GBRS_OK;
 }
 

@@ -21,6 +21,9 @@
 //                         CSC position
 //   model_col_kernel      the CSC entries in order: a column's factors are summed across the wavefront before one
 //                         atomic per column chunk (as csc_acc_kernel)
+// The factors stay in `fac` until the next step of one of these models (a step the stopping rule turned into a no-op
+// leaves them alone): gbrs_em_posterior (em.hip, post_value_kernel) reads them back, divides the count out again and
+// multiplies by the theta the step started from.
 
 __global__ void __launch_bounds__(256)
 model_totals_kernel(uint32_t L, uint32_t H, uint32_t n_genes, const uint32_t *__restrict__ gene_ptr,

@@ -21,7 +21,7 @@ class EMfactory:
 
     def __init__(self, alignments, device: int = 0, merge_identical_rows: bool = False,
                  csc_layout: bool = False, extra_flags: int = 0, deterministic: bool = False,
-                 one_shot: bool = False, grouped_models: bool = False):
+                 one_shot: bool = False, grouped_models: bool = False, keep_posterior: bool = False):
         self.probability = alignments
         self.grp_conv_mat = None          # kept for attribute parity; groups live in probability
         self.t2t_mat = None               # Models 1-3 (EMfactory.py:48-59): the device holds the groups instead
@@ -31,7 +31,8 @@ class EMfactory:
                      (_lib.GBRS_EM_LAYOUT_CSC if csc_layout else 0) | \
                      (_lib.GBRS_EM_DETERMINISTIC if deterministic else 0) | \
                      (_lib.GBRS_EM_ONE_SHOT if one_shot else 0) | \
-                     (_lib.GBRS_EM_GROUPED_MODELS if grouped_models else 0) | int(extra_flags)   # tuning switches of gbrs_hip.h
+                     (_lib.GBRS_EM_GROUPED_MODELS if grouped_models else 0) | \
+                     (_lib.GBRS_EM_POSTERIOR if keep_posterior else 0) | int(extra_flags)   # tuning switches of gbrs_hip.h
         self._h = None
         self._theta = None                # host copy of allelic_expression (H x L)
         self._theta_dirty = False         # host copy edited, device not yet updated
@@ -138,6 +139,26 @@ class EMfactory:
         _lib.check(_lib.load().gbrs_em_get(self._h, None, _lib.ptr(out)))
         return out
 
+    def posterior(self, hid: int) -> np.ndarray:
+        """float64[nnz_h]: the posterior of every stored entry of haplotype `hid` in the last E-step - what the
+        reference's probability.data[hid] holds after a step - in the order of the (masked) indices[hid].  Needs
+        keep_posterior=True and at least one step since prepare()."""
+        self._require()
+        apm = self.probability
+        hid = int(hid)
+        if not 0 <= hid < apm.num_haplotypes:
+            raise RuntimeError(f'Haplotype {hid} is out of range: the matrix has {apm.num_haplotypes}.')
+        ptr = apm.indptr[hid]
+        mask = apm.haplotype_mask
+        if mask is None:
+            nnz = int(ptr[-1])
+        else:               # a pending `-G` mask: the device dropped the columns, the host arrays still hold them
+            keep = ((mask >> np.uint32(hid)) & 1).astype(bool)
+            nnz = int(np.diff(ptr.astype(np.int64))[keep].sum())
+        out = np.empty(nnz, dtype=np.float64)
+        _lib.check(_lib.load().gbrs_em_posterior(self._h, hid, _lib.ptr(out), nnz))
+        return out
+
     def _group_sums(self, which):
         apm = self.probability
         if not apm.num_groups:
@@ -232,10 +253,18 @@ class EMfactory:
                 self._theta_dirty = True
         write_locus_table(filename, self.probability.hname, names, values, reorder, notes, pool=self.report_pool)
 
-    def export_posterior_probability(self, filename: str, title: str = 'Posterior Probability') -> None:
+    def export_posterior_probability(self, filename: str, title: str = 'Posterior Probability',
+                                     values: bool = False) -> None:
         """The reference saves with incidence_only=True (EMfactory.py:392 ->
-        AlignmentPropertyMatrix.py:484), i.e. the structure without posterior values."""
-        self.probability.save(filename, title=title)
+        AlignmentPropertyMatrix.py:484), i.e. the structure without posterior values.
+        values=True (extension, needs keep_posterior=True): the file carries /h*/data with the posteriors of the
+        last E-step, fetched from the device one haplotype at a time (incidence_only=False, the reference's own
+        layout for stored values)."""
+        if not values:
+            self.probability.save(filename, title=title)
+            return
+        self._require()
+        self.probability.save(filename, title=title, incidence_only=False, values=self.posterior)
 
 
 def _print_progress(err_history, stamps):

@@ -584,11 +584,31 @@ def _group_attrs(g, title=''):
     _write_str_attr(g, 'TITLE', title.encode())
 
 
-def save(apm, path, title=None, complib='zlib', incidence_only=True, shallow=False, **_ignored):
+def value_provider(values, num_haplotypes):
+    """`h -> float64 array` of a per-haplotype value provider: a callable as it is, a sequence through its items,
+    None as None."""
+    if values is None or callable(values):
+        return values
+    if len(values) != num_haplotypes:
+        raise RuntimeError('The number of value arrays does not match to the matrix shape.')
+    return values.__getitem__
+
+
+def fetch_values(provider, apm, h):
+    """Haplotype h's values from a provider, checked against the index array they line up with."""
+    v = np.ascontiguousarray(provider(h), dtype=np.float64)
+    if v.shape != (len(apm.indices[h]),):
+        raise RuntimeError(f'The values of haplotype {h} do not match the index array.')
+    return v
+
+
+def save(apm, path, title=None, complib='zlib', incidence_only=True, shallow=False, values=None, **_ignored):
     """Write the EMASE h5 layout (Sparse3DMatrix.save :400-444 + AlignmentPropertyMatrix.save :478-525).
     incidence_only=True (the reference's default) writes the structure alone; False adds /h*/data with
-    `apm.values` (ones when the matrix has none)."""
+    `values` - a sequence of H arrays or a callable `h -> array`, asked for one haplotype at a time so that the
+    host never holds more than one of them - else `apm.values` (ones when the matrix has none)."""
     lib = _load()
+    provider = value_provider(values, apm.shape[1])
     f = lib.H5Fcreate(os.fsencode(path), H5F_ACC_TRUNC, H5P_DEFAULT, H5P_DEFAULT)
     if f < 0:
         raise OSError(f'cannot create {path}')
@@ -608,8 +628,12 @@ def save(apm, path, title=None, complib='zlib', incidence_only=True, shallow=Fal
             _write_carray(g, 'indices', apm.indices[h].astype(np.uint32))
             if not incidence_only:
                 vals = getattr(apm, 'values', None)
-                _write_carray(g, 'data', np.ones(len(apm.indices[h])) if vals is None
-                              else np.asarray(vals[h], dtype=np.float64))
+                if provider is not None:
+                    data = fetch_values(provider, apm, h)
+                else:
+                    data = np.ones(len(apm.indices[h])) if vals is None else np.asarray(vals[h], dtype=np.float64)
+                _write_carray(g, 'data', data)
+                del data
             lib.H5Gclose(g)
         if apm.count is not None:
             _write_carray(root, 'count', np.asarray(apm.count, dtype=np.float64), 'Equivalence Class Counts')

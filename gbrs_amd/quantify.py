@@ -204,7 +204,8 @@ def diplotype_mask(aln_mat, calls):
     return allowed, gnotes, tnotes
 
 
-def _write_expression_reports(em, outbase, with_groups, isoform_notes, gene_notes, report_posterior):
+def _write_expression_reports(em, outbase, with_groups, isoform_notes, gene_notes, report_posterior,
+                              posterior_values=False):
     """The 2-5 files `gbrs quantify` leaves behind, in the reference's order (the isoform TPM report
     comes first because it rescales theta in place, which the later reports inherit)."""
     def emit(label, suffix, writer, **kw):
@@ -215,17 +216,17 @@ def _write_expression_reports(em, outbase, with_groups, isoform_notes, gene_note
     from .em import ReportPool
     em.report_pool = ReportPool()           # the tables are formatted and written while the next one is being fetched
     try:
-        _emit_reports(emit, em, with_groups, isoform_notes, gene_notes, report_posterior)
+        _emit_reports(emit, em, with_groups, isoform_notes, gene_notes, report_posterior, posterior_values)
     finally:
         pool, em.report_pool = em.report_pool, None
         pool.finish()
 
 
-def _emit_reports(emit, em, with_groups, isoform_notes, gene_notes, report_posterior):
+def _emit_reports(emit, em, with_groups, isoform_notes, gene_notes, report_posterior, posterior_values=False):
     emit('isoform TPMs', 'isoforms.tpm', em.report_depths, tpm=True, notes=isoform_notes)
     emit('isoform Read Counts', 'isoforms.expected_read_counts', em.report_read_counts, notes=isoform_notes)
     if report_posterior:
-        emit('Posterior Probabilities', 'posterior.h5', em.export_posterior_probability)
+        emit('Posterior Probabilities', 'posterior.h5', em.export_posterior_probability, values=posterior_values)
     if with_groups:
         emit('gene TPMs', 'genes.tpm', em.report_depths, tpm=True, grp_wise=True, notes=gene_notes)
         emit('gene Read Counts', 'genes.expected_read_counts', em.report_read_counts, grp_wise=True,
@@ -237,12 +238,19 @@ def quantify(alignment_file: str, group_file: str = None, length_file: str = Non
              pseudocount: float = 0.0, max_iters: int = 999, tolerance: float = 0.0001,
              report_alignment_counts: bool = False, report_posterior: bool = False,
              device: int = 0, merge_identical_rows: bool = False, stage_times: dict = None,
-             one_shot: bool = False, alignment=None, target_lengths=None) -> None:
+             one_shot: bool = False, alignment=None, target_lengths=None,
+             posterior_values: bool = False) -> None:
     """Quantify allele-specific expression from an EMASE alignment file.  `stage_times` (optional
     dict) receives the wall-clock seconds of the stages: load, mask, em_setup, em_run, reports,
     alignment_counts.  `alignment` / `target_lengths` (extension, gbrs_amd.worker): the file's contents as
     load_alignment() and read_length_file() return them, when a resident process has them already - the
-    multiway and the diploid pass of one sample read the same file."""
+    multiway and the diploid pass of one sample read the same file.  `posterior_values` (extension, implies
+    report_posterior): `<outbase>.posterior.h5` carries the read-level posteriors of the last E-step in /h*/data
+    instead of the structure alone."""
+    if posterior_values and merge_identical_rows:
+        raise RuntimeError('--posterior-values is not available with --merge-identical-rows: the merged rows are not '
+                           'the rows of the posterior file')
+    report_posterior = report_posterior or posterior_values
     clock = time.perf_counter
     marks = stage_times if stage_times is not None else {}
     group_file = _default_support_file(
@@ -296,7 +304,7 @@ def quantify(alignment_file: str, group_file: str = None, length_file: str = Non
     logger.info('Running EMASE')
     t0 = clock()
     em = EMfactory(aln_mat, device=device, merge_identical_rows=merge_identical_rows, one_shot=one_shot,
-                   grouped_models=multiread_model != 4)
+                   grouped_models=multiread_model != 4, keep_posterior=posterior_values)
     if target_lengths is not None:
         em.set_target_lengths(target_lengths)
         em.prepare(pseudocount=pseudocount)
@@ -313,7 +321,8 @@ def quantify(alignment_file: str, group_file: str = None, length_file: str = Non
     marks['em_iterations'] = em.num_iters
 
     t0 = clock()
-    _write_expression_reports(em, outbase, group_file is not None, isoform_notes, gene_notes, report_posterior)
+    _write_expression_reports(em, outbase, group_file is not None, isoform_notes, gene_notes, report_posterior,
+                              posterior_values)
     em.close()
     marks['reports'] = clock() - t0
 

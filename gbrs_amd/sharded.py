@@ -41,6 +41,8 @@ def check_args(args):
     if args.multiread_model != 4:
         raise RuntimeError(f'--gpus: multiread model {args.multiread_model} is not available on the sharded path '
                            '(models 1-3 run on one GPU)')
+    if getattr(args, 'posterior_values', False):
+        raise RuntimeError('--gpus: --posterior-values is not available on the sharded path')
     if args.report_posterior:
         raise RuntimeError('--gpus: -w/--report-posterior is not available on the sharded path')
     if args.merge_identical_rows:

@@ -111,6 +111,11 @@ typedef struct gbrs_em gbrs_em_t;
 /* Multiread models 1-3 (EMfactory.py:160-203): the handle keeps the CSC row ids after create, so that
  * gbrs_em_set_groups can build the grouped row layout those models step on.  Model 4 is unaffected. */
 #define GBRS_EM_GROUPED_MODELS 1024u
+/* Read-level posteriors (gbrs_em_posterior).  The handle keeps the CSC row ids and column pointers after create
+ * (after a `-G` mask; the arrays GBRS_EM_GROUPED_MODELS keeps, shared when both are set) and copies theta into a
+ * second H*L buffer before every EM step: the theta that step's E-step used.  Without the flag a handle allocates
+ * and launches exactly what it did before the flag existed. */
+#define GBRS_EM_POSTERIOR 2048u
 
 /*
  * Replaces: AlignmentPropertyMatrix(h5file=...) as consumed by EMfactory.__init__
@@ -206,6 +211,20 @@ int gbrs_em_run(gbrs_em_t *em, int model, double tol, int max_iters,
  * this call or gbrs_em_group_sums asks for it.  They stay those of the last iteration when gbrs_em_set_theta replaces
  * theta afterwards (the reports rescale theta to TPM first).  Either pointer may be NULL. */
 int gbrs_em_get(gbrs_em_t *em, double *theta, double *expected_counts);
+
+/* The posterior of every stored entry of haplotype `hap` in the most recent E-step (handle created with
+ * GBRS_EM_POSTERIOR): what the reference's probability.data[hap] holds after a step.  out is a HOST array
+ * double[nnz_hap], nnz_hap being the entries of the haplotype after a `-G` mask; the values come in the order of
+ * the (masked) indices[hap] given to create: surviving columns in locus order, the entries of a column in the order
+ * they were uploaded.  For an entry (read r, haplotype h, locus l) the value is theta_before[h,l] * f / D_r with f
+ * and D_r as for gbrs_em_step_model, for whichever model (1-4) the last step ran and theta_before the theta that
+ * step started from; `count` plays no part.  An entry whose theta_before is 0 gets exactly 0.0.  The result does
+ * not depend on the layout the EM runs on.  The first call after a step computes the per-read denominators
+ * (model 4) once; calls for the other haplotypes reuse them until the next step.  Models 1-3 divide the count back
+ * out of the per-entry factors the step stored, so a read whose count is 0 has no defined posterior there (NaN).
+ * GBRS_ERR_STATE without the flag or when no step has run since prepare; GBRS_ERR_INVALID for hap >= num_haps or
+ * out_len != nnz_hap. */
+int gbrs_em_posterior(gbrs_em_t *em, uint32_t hap, double *out, uint64_t out_len);
 
 /* Overwrite theta (H x L), e.g. to resume from a checkpoint. */
 int gbrs_em_set_theta(gbrs_em_t *em, const double *theta);

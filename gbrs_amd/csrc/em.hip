@@ -535,6 +535,7 @@ struct gbrs_em {
     uint32_t flags = 0;
 
     int layout = 0;               // 0 = csc-direct, 1 = packed row tiles
+    uint32_t lead_mask = ~0u;     // ANDed with a tile header's n_one by tile_estep_kernel; 0: one batch loop for every batch
     uint32_t persist_groups = 0;  // > 0: the E-step of a step runs on this many persistent workgroups (em_tiles.inc)
     uint32_t view = 1;            // 2: the tile layout is built over half-loci (em_layout.h): tL() loci of tH() haplotypes
     uint32_t tH() const { return H / view; }
@@ -644,10 +645,11 @@ int em_estep_tiles_h(gbrs_em *em) {
         const dim3 grid((unsigned)tl.n_tiles + ea.n_err_blocks), block(TILE_THREADS);
         const double *ww = tl.weighted ? tl.word_weight.p : (const double *)nullptr;
         const SetArgs sets{em->tL(), tl.n_sets ? tl.set_ptr.p : nullptr, tl.set_members.p, tl.dest_list.p, tl.dict_b.p, tl.dest_b.p};
+        const uint32_t lead_mask = em->lead_mask;
 #define GBRS_LAUNCH_TILES(W, D)                                                                                        \
         hipLaunchKernelGGL((tile_estep_kernel<HT, W, ONES, D>), grid, block, 0, em->stream, em->tH(), tl.tiles.p, tl.words.p, \
                            tl.dict.p, ww, em->theta.p, tl.partials.p, tl.slot_dest.p, em->acc.p, em->scalars.p,       \
-                           (uint32_t)tl.n_tiles, ea, sets)
+                           (uint32_t)tl.n_tiles, ea, sets, lead_mask)
         if (!ONES && !tl.deterministic && em->persist_groups > 0 && HT > 0 && HT <= 8) {
             // persistent workgroups (em_tiles.inc): as many as the chip holds at once, each walking several tiles with the
             // next tile's header, dictionary and theta fetched under the current tile's batch loop
@@ -668,7 +670,7 @@ int em_estep_tiles_h(gbrs_em *em) {
             // no row of the layout has more than one word (single-locus reads, or locus sets): no row sums at all
             hipLaunchKernelGGL((tile_estep_kernel<HT == 8 ? 8 : 1, false, ONES, false, HT == 8>), grid, block, 0, em->stream, em->tH(),
                                tl.tiles.p, tl.words.p, tl.dict.p, ww, em->theta.p, tl.partials.p, tl.slot_dest.p, em->acc.p,
-                               em->scalars.p, (uint32_t)tl.n_tiles, ea, sets);
+                               em->scalars.p, (uint32_t)tl.n_tiles, ea, sets, lead_mask);
 #endif
         } else {
             if (tl.weighted) GBRS_LAUNCH_TILES(true, false); else GBRS_LAUNCH_TILES(false, false);
@@ -1034,7 +1036,7 @@ int em_keep_theta(gbrs_em *em, int model) {
 // One iteration; `ev` (3 events) times it.  An event record is a barrier packet that costs the
 // queue ~4 us of idle time on this hardware, so callers time a sample of the iterations (every
 // EM_TIME_STRIDE-th), not each one.
-constexpr int EM_TIME_STRIDE = 8;
+constexpr int EM_TIME_STRIDE = 8, EM_TIME_SAMPLES = 16;
 int em_one_step(gbrs_em *em, double target_err, hipEvent_t *ev = nullptr, bool defer_err = false) {
     GBRS_TRY(em_keep_theta(em, 4));
     const bool timed = ev != nullptr && em->time_steps;
@@ -1352,6 +1354,10 @@ int em_create_impl(uint64_t R, uint32_t L, uint32_t H, const uint32_t *const *in
             unsigned groups = per_cu * (unsigned)std::max(n_cu, 1) / share;
             if (const char *g = std::getenv("GBRS_TUNING_PERSISTENT_GROUPS"); g && std::atoi(g) > 0) groups = (unsigned)std::atoi(g);
             em->persist_groups = (env && std::atoi(env) != 0) ? std::max(groups, 1u) : 0u;
+            // GBRS_TUNING_NO_PHASE_SPLIT=1: the E-step takes every tile's n_one as 0 - one batch loop, as before the headers
+            // had the field (A/B in one build, and the cross-check of the two-loop form in the tests)
+            const char *no_split = std::getenv("GBRS_TUNING_NO_PHASE_SPLIT");
+            em->lead_mask = (no_split && std::atoi(no_split) != 0) ? 0u : ~0u;
         }
         stg.mark("build_tile_layout");
         // the CSC copy and the per-row denominators are only needed by layout 0 (and, until
@@ -1616,15 +1622,18 @@ int gbrs_em_step(gbrs_em_t *em, int n_iters, double *err_sum_out) {
     // a run that met its stopping rule left the device's stop flag set; a step asked for by hand is applied anyway
     // (EMfactory.update_allelic_expression knows no stopping rule)
     if (em->stopped) GBRS_TRY(em_reset_scalars(em, true));
-    const int timed = em->time_steps ? std::min((n_iters + EM_TIME_STRIDE - 1) / EM_TIME_STRIDE, 64) : 0;
+    // (and at most EM_TIME_SAMPLES of them, spread over the call, the first iteration included: 500 iterations timed on
+    // every eighth paid ~1.5 us each for the records)
+    const int stride = std::max(EM_TIME_STRIDE, (n_iters + EM_TIME_SAMPLES - 1) / EM_TIME_SAMPLES);
+    const int timed = em->time_steps ? (n_iters + stride - 1) / stride : 0;
     while ((int)em->ev_pool.size() < 3 * timed) {
         hipEvent_t e;
         GBRS_HIP_CHECK(hipEventCreate(&e));
         em->ev_pool.push_back(e);
     }
     for (int i = 0; i < n_iters; ++i) {
-        const int slot = i / EM_TIME_STRIDE;
-        const bool t = i % EM_TIME_STRIDE == 0 && slot < timed;
+        const int slot = i / stride;
+        const bool t = i % stride == 0 && slot < timed;
         GBRS_TRY(em_one_step(em, -1.0, t ? &em->ev_pool[3 * slot] : nullptr, i + 1 < n_iters));
     }
     EmScalars host;

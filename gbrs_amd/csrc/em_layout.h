@@ -87,10 +87,17 @@ constexpr int HEAVY_SLOTS = 16;                // loci with more slots get a who
 
 struct TileHdr {
     uint32_t batch_base;   // first batch of the tile in `words`
-    uint32_t n_batches;
+    uint16_t n_batches;
+    uint16_t n_one;        // the tile's first n_one batches hold one-word rows only (stream order, unweighted: the B of
+                           // tile_pad_kernel's run of one-word rows; 0: nothing is known about the tile's batches).  An empty
+                           // cell of these batches carries the dictionary index of the cell above it (same lane, batch
+                           // before) and no haplotype bit, see fill_one_word_cells_kernel
     uint32_t dict_base;    // first slot / dictionary entry of the tile
     uint32_t dict_count;   // D
 };
+static_assert(sizeof(TileHdr) == 16, "a tile header is one 16-byte scalar load");
+// a tile's rows of one length that does not divide 64 can pad to just under twice its words: still 16 bits of batches
+static_assert(2 * (GBRS_TILE_CAP / 64) < 65536, "TileHdr::n_batches is 16 bits");
 
 // what the E-step kernel needs to know about locus sets (null set_ptr: the layout has none)
 struct SetArgs {

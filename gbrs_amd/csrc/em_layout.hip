@@ -534,12 +534,14 @@ __global__ void tile_start_kernel(uint64_t m_rows, uint64_t n_tiles, const uint3
 // B = ceil(n / (64/w)) whole batches in which lane group g (w lanes) holds rows g*B .. g*B+B-1 of the
 // run at batches 0 .. B-1: whichever batches a wavefront owns, each of its lanes walks a
 // contiguous piece of the sorted rows.
+// n_one[t]: the batches of the tile's run of one-word rows - the rows sort by length, so they are the tile's first
+// (TileHdr::n_one); 0 in the other row orders.
 __global__ void tile_pad_kernel(uint64_t n_tiles, int streams, const uint32_t *__restrict__ tile_row,
                                 const uint32_t *__restrict__ npm, uint32_t *__restrict__ rowpad,
-                                uint32_t *__restrict__ nbatch) {
+                                uint32_t *__restrict__ nbatch, uint32_t *__restrict__ n_one) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_tiles) return;
-    uint32_t off = 0;
+    uint32_t off = 0, one = 0;
     const uint32_t end = tile_row[t + 1];
     uint32_t m = tile_row[t];
     while (m < end) {
@@ -549,6 +551,7 @@ __global__ void tile_pad_kernel(uint64_t n_tiles, int streams, const uint32_t *_
             while (e < end && npm[e] == cnt) ++e;
             const uint32_t n = e - m, G = 64u / cnt, B = (n + G - 1) / G;
             off = (off + 63u) & ~63u;
+            if (cnt == 1u && off == 0u) one = B;
             for (uint32_t k = 0; k < n; ++k) rowpad[m + k] = off + (k % B) * 64u + (k / B) * cnt;
             off += B * 64u;
             m = e;
@@ -560,6 +563,7 @@ __global__ void tile_pad_kernel(uint64_t n_tiles, int streams, const uint32_t *_
         }
     }
     nbatch[t] = (off + 63u) >> 6;
+    n_one[t] = one;
 }
 
 // Per-tile dictionaries = the distinct loci (and locus sets) of a tile's rows, ascending.  Built from ONE radix sort of
@@ -589,13 +593,13 @@ __global__ void dict_emit_kernel(uint64_t n, const uint64_t *__restrict__ skeys,
 }
 
 __global__ void tile_hdr_kernel(uint64_t n_tiles, uint32_t dcap, uint32_t n_slots, const uint32_t *__restrict__ batch_base,
-                                const uint32_t *__restrict__ nbatch, const uint32_t *__restrict__ dict_base,
-                                TileHdr *__restrict__ hdr, BuildFlags *flags) {
+                                const uint32_t *__restrict__ nbatch, const uint32_t *__restrict__ n_one,
+                                const uint32_t *__restrict__ dict_base, TileHdr *__restrict__ hdr, BuildFlags *flags) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_tiles) return;
     const uint32_t db = dict_base[t], d = (t + 1 < n_tiles ? dict_base[t + 1] : n_slots) - db;
     if (d > dcap) flags->dict_overflow = 1;
-    hdr[t] = TileHdr{batch_base[t], nbatch[t], db, d};
+    hdr[t] = TileHdr{batch_base[t], (uint16_t)nbatch[t], (uint16_t)n_one[t], db, d};
 }
 
 // one thread per (merged) row: emit its words at the padded position
@@ -623,6 +627,26 @@ __global__ void emit_words_kernel(uint64_t m_rows, uint32_t H, const uint32_t *_
         words[base + j] = pmask[p0 + j] | (j << H) | ((cnt - 1 - j) << (H + PB)) | (lo << (H + 2 * PB));
         if (word_weight) word_weight[base + j] = row_weight[m];
     }
+}
+
+// The empty cells of a tile's leading one-word batches (TileHdr::n_one).  Lane g of the run holds its rows g*B .. g*B+B-1
+// at batches 0 .. B-1, so only the lane of the run's last row ends early (the lanes after it are empty altogether and
+// stay all-zero words: dictionary entry 0).  That lane's empty cells take the dictionary index of its last row and no
+// haplotype bit: still padding to every reader (no bit, nothing added), and a lane that walks down the run never meets
+// a change of entry that is not one.  One thread per (tile, lane).
+__global__ void fill_one_word_cells_kernel(uint64_t n_tiles, uint32_t H, const TileHdr *__restrict__ hdr,
+                                           uint32_t *__restrict__ words) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_tiles * 64) return;
+    const TileHdr th = hdr[i >> 6];
+    const uint32_t B = th.n_one;
+    if (B < 2) return;
+    uint32_t *w = words + (uint64_t)th.batch_base * 64 + (i & 63u);
+    if (w[0] == 0u || w[(uint64_t)(B - 1) * 64] != 0u) return;        // an empty lane / a full one
+    uint32_t b = B - 1;
+    while (w[(uint64_t)(b - 1) * 64] == 0u) --b;                      // (ends at batch 0 at the latest: its word is not zero)
+    const uint32_t fill = w[(uint64_t)(b - 1) * 64] & ~((1u << (H + 2 * pos_bits(H))) - 1u);
+    for (; b < B; ++b) w[(uint64_t)b * 64] = fill;
 }
 
 __global__ void iota_kernel(uint64_t n, uint32_t *__restrict__ v) {
@@ -1497,10 +1521,12 @@ int build_tile_layout(TileLayout &out, uint64_t R, uint32_t L_in, uint32_t H, ui
     tflag.release();
     stg.mark("7b row order");
     // 8. padding so that no row straddles a batch, batch offsets
-    DevBuf<uint32_t> rowpad, nbatch, batch_base;
-    GBRS_TRY(rowpad.alloc(M)); GBRS_TRY(nbatch.alloc(T)); GBRS_TRY(batch_base.alloc(T));
+    DevBuf<uint32_t> rowpad, nbatch, n_one, batch_base;
+    GBRS_TRY(rowpad.alloc(M)); GBRS_TRY(nbatch.alloc(T)); GBRS_TRY(n_one.alloc(T)); GBRS_TRY(batch_base.alloc(T));
     hipLaunchKernelGGL(tile_pad_kernel, dim3(grid_for(T, 64)), dim3(64), 0, s, T, streams ? 1 : 0, tile_row.p, npm.p, rowpad.p,
-                       nbatch.p);
+                       nbatch.p, n_one.p);
+    // (the weighted kernels do not split their batch loop: their headers say nothing about the leading batches)
+    if (out.weighted) GBRS_HIP_CHECK(hipMemsetAsync(n_one.p, 0, T * 4, s));
     GBRS_TRY(exclusive_scan(sc, nbatch.p, batch_base.p, T, s));
     uint32_t NB = 0;
     GBRS_TRY(fetch_last_plus(batch_base.p, nbatch.p, T, NB, s));
@@ -1528,8 +1554,8 @@ int build_tile_layout(TileLayout &out, uint64_t R, uint32_t L_in, uint32_t H, ui
         GBRS_TRY(out.dict.alloc(std::max<uint32_t>(NS, 1)));
         hipLaunchKernelGGL(dict_emit_kernel, dim3(grid_for(W)), dim3(256), 0, s, (uint64_t)W, dkey2.p, dflag.p, dpos.p, out.dict.p,
                            dict_base.p);
-        hipLaunchKernelGGL(tile_hdr_kernel, dim3(grid_for(T)), dim3(256), 0, s, T, dcap, NS, batch_base.p, nbatch.p, dict_base.p,
-                           out.tiles.p, d_flags.p);
+        hipLaunchKernelGGL(tile_hdr_kernel, dim3(grid_for(T)), dim3(256), 0, s, T, dcap, NS, batch_base.p, nbatch.p, n_one.p,
+                           dict_base.p, out.tiles.p, d_flags.p);
         GBRS_TRY(read_flags());
         if (hf.dict_overflow) return fail(GBRS_ERR_INVALID, "internal error: a tile dictionary overflowed its capacity");
     }
@@ -1545,8 +1571,10 @@ int build_tile_layout(TileLayout &out, uint64_t R, uint32_t L_in, uint32_t H, ui
                        hrow.p, rowstart.p, ploc.p, pmask.p, rowpad.p, out.words.p,
                        out.weighted ? out.row_weight.p : (const double *)nullptr,
                        out.weighted ? out.word_weight.p : (double *)nullptr);
+    if (streams && !out.weighted)
+        hipLaunchKernelGGL(fill_one_word_cells_kernel, dim3(grid_for(T * 64)), dim3(256), 0, s, T, H, out.tiles.p, out.words.p);
     GBRS_HIP_CHECK(hipStreamSynchronize(s));
-    dict_base.release(); batch_base.release(); nbatch.release();
+    dict_base.release(); batch_base.release(); nbatch.release(); n_one.release();
     rowpad.release(); tincl.release(); npm.release(); wordoff.release(); tile_row.release();
     hrow.release(); rowstart.release(); ploc.release(); pmask.release();
     out.row_weight.release();

@@ -17,7 +17,8 @@
 //   pos   PB bits    words of the same row to the left of this one
 //   rem   PB bits    words of the same row to the right of this one
 //   idx              index into the tile's dictionary
-// An all-zero word is padding (a one-word row with no haplotype: contributes nothing).
+// A word without a haplotype bit is padding (a one-word row with no haplotype: contributes nothing): all zero, or - in a
+// tile's leading one-word batches - with the dictionary index of the cell above it (TileHdr::n_one).
 
 #ifndef GBRS_ESTEP_WAVES16
 #define GBRS_ESTEP_WAVES16 4          // the same for more than 8 haplotypes
@@ -123,10 +124,14 @@ __device__ __forceinline__ double fast_recip(double d) {
 
 // Per-lane accumulation state: the partial sums of the locus the lane is currently on (c), the
 // ones of the locus it just left (pc, "pending"), and the float-error flag.
+typedef double theta_pair_t __attribute__((ext_vector_type(2)));
 template <int HC>
 struct LaneAcc {
     double c[HC], pc[HC];
-    double th[HC];     // estep_theta_regs: theta of the lane's current locus (pc is then unused)
+    // estep_theta_regs: theta of the lane's current locus (pc is then unused), as the 16-byte pairs the LDS reads deliver:
+    // one register tuple per read wherever the value lives (kept as single doubles, the kernel with two batch loops held
+    // the row twice - as tuples inside a loop, as doubles between the loops - and went to scratch)
+    theta_pair_t th[(HC + 1) / 2];
     uint32_t cidx, pidx;
     uint64_t bad;      // lanes that met a row without abundance, as a wave-uniform ballot word: scalar ORs, no vector
                        // work (and an integer on purpose: as a loop-carried bool - an i1 lane mask - hipcc 7.2 mis-lowered it)
@@ -187,7 +192,14 @@ __device__ __forceinline__ void load_theta16(const double *__restrict__ s_theta,
     }
 }
 
-template <int HT, bool WEIGHTED, int HC, bool DET, int UB, bool ONEWORD = false>
+// LEAD: a batch of the tile's leading run of one-word rows (TileHdr::n_one): no row sum, like ONEWORD; and in the kernel that
+// keeps theta in registers the batch neither looks for padding words nor votes on a zero denominator:
+//   * an empty cell of these batches has no haplotype bit and the dictionary index of the cell above it (em_layout.hip,
+//     fill_one_word_cells_kernel), so it multiplies 0.0 into everything and hands nothing in; the cells of a lane that is
+//     empty from the top are on entry 0 - one hand-in of nothing, and entry 0's theta row is a valid LDS row;
+//   * a real row without abundance still divides the smallest normal number (the v_max_f64 guard) and so adds >= 4.49e307
+//     to at least one of the tile's sums: the tile epilogue, which walks the sums anyway, raises the float error there.
+template <int HT, bool WEIGHTED, int HC, bool DET, int UB, bool ONEWORD = false, bool LEAD = false>
 __device__ __forceinline__ void tile_batches(const uint32_t (&w)[UB], const double (&wt)[UB], int H, int PB, int lane,
                                              const double *__restrict__ s_theta, double *__restrict__ my_acc,
                                              LaneAcc<HC> &st, const int (&zlo)[32], const double2 *__restrict__ s_ftab,
@@ -195,6 +207,7 @@ __device__ __forceinline__ void tile_batches(const uint32_t (&w)[UB], const doub
     constexpr bool ZLO = estep_uses_zlo(UB);
     constexpr bool FTAB = estep_uses_ftab(UB, HT);
     constexpr bool TREG = estep_theta_regs(UB, HT, DET) && HC >= 8;
+    constexpr bool DIET = LEAD && TREG;
     const uint32_t hmask = (1u << H) - 1u, pmask = (1u << PB) - 1u;
     uint32_t mask[UB], idx[UB];
     int pos[UB], rem[UB];
@@ -211,12 +224,12 @@ __device__ __forceinline__ void tile_batches(const uint32_t (&w)[UB], const doub
     }
     uint64_t real_lanes0 = 0;                                    // TREG: lanes whose word is not padding
     (void)real_lanes0;
-    if constexpr (TREG) real_lanes0 = wave_ballot(mask[0] != 0);
+    if constexpr (TREG && !DIET) real_lanes0 = wave_ballot(mask[0] != 0);
     if constexpr (TREG) {
         // A lane that moves on to another locus hands the sums of the one it leaves to LDS (H atomics under the
         // branch's exec mask) and fetches the new locus's theta row, before the word's own arithmetic.
-        const bool miss = (mask[0] != 0) & (idx[0] != st.cidx);
-        const uint64_t miss_lanes = real_lanes0 & wave_ballot(idx[0] != st.cidx);
+        const bool miss = DIET ? idx[0] != st.cidx : (mask[0] != 0) & (idx[0] != st.cidx);
+        const uint64_t miss_lanes = DIET ? wave_ballot(idx[0] != st.cidx) : real_lanes0 & wave_ballot(idx[0] != st.cidx);
         if (miss_lanes != 0) {
             if (miss) {
                 // (requesting the new locus's theta row - and the word's 0/1 doubles - before the old sums are handed in, so
@@ -233,9 +246,8 @@ __device__ __forceinline__ void tile_batches(const uint32_t (&w)[UB], const doub
                 constexpr int DPT = theta_planar(8) ? lds_theta_doubles(WEIGHTED, 8) / 8 : 1;
                 const double2 *t2 = theta_planar(8) ? reinterpret_cast<const double2 *>(s_theta) + idx[0]
                                                     : reinterpret_cast<const double2 *>(s_theta + idx[0] * 8);
-                const double2 a = t2[0], cc = t2[DPT], e = t2[2 * DPT], g = t2[3 * DPT];
-                st.th[0] = a.x; st.th[1] = a.y; st.th[2] = cc.x; st.th[3] = cc.y;
-                st.th[4] = e.x; st.th[5] = e.y; st.th[6] = g.x; st.th[7] = g.y;
+                const theta_pair_t *tv = reinterpret_cast<const theta_pair_t *>(t2);
+                st.th[0] = tv[0]; st.th[1] = tv[DPT]; st.th[2] = tv[2 * DPT]; st.th[3] = tv[3 * DPT];
             }
         }
     }
@@ -252,8 +264,8 @@ __device__ __forceinline__ void tile_batches(const uint32_t (&w)[UB], const doub
             constexpr int DP = theta_planar(8) ? lds_theta_doubles(WEIGHTED, 8) / 8 : 1;      // pairs per plane
             const double2 *t2 = theta_planar(8) ? reinterpret_cast<const double2 *>(s_theta) + idx[u]
                                                 : reinterpret_cast<const double2 *>(tp);      // 64-byte aligned row
-            const double2 a = TREG ? make_double2(st.th[0], st.th[1]) : t2[0], cc = TREG ? make_double2(st.th[2], st.th[3]) : t2[DP],
-                          e = TREG ? make_double2(st.th[4], st.th[5]) : t2[2 * DP], g = TREG ? make_double2(st.th[6], st.th[7]) : t2[3 * DP];
+            const double2 a = TREG ? make_double2(st.th[0].x, st.th[0].y) : t2[0], cc = TREG ? make_double2(st.th[1].x, st.th[1].y) : t2[DP],
+                          e = TREG ? make_double2(st.th[2].x, st.th[2].y) : t2[2 * DP], g = TREG ? make_double2(st.th[3].x, st.th[3].y) : t2[3 * DP];
             // two chains of four to halve the dependent-FMA latency
             double s0, s1;
             if constexpr (FTAB) {
@@ -324,7 +336,7 @@ __device__ __forceinline__ void tile_batches(const uint32_t (&w)[UB], const doub
 #if defined(GBRS_ABLATE_ROWSUM)
     if (true) {
 #else
-    if (ONEWORD || !wave_any(multi != 0)) {       // ONEWORD: the layout holds no row of more than one word at all
+    if (ONEWORD || LEAD || !wave_any(multi != 0)) {       // ONEWORD: the layout holds no row of more than one word at all
 #endif
 #pragma unroll
         for (int u = 0; u < UB; ++u) den[u] = s[u];
@@ -363,7 +375,7 @@ __device__ __forceinline__ void tile_batches(const uint32_t (&w)[UB], const doub
             // discarded) divide the smallest normal number instead - one v_max_f64 keeps 1/den finite, and a padding
             // word's 0.0 factors turn it into nothing; the real-word lanes are the ballot taken at the top of the batch.
             // (Only in the kernel that has registers to spare: the 16-haplotype form spills with it.)
-            st.bad |= real_lanes0 & wave_ballot(!ok);
+            if constexpr (!DIET) st.bad |= real_lanes0 & wave_ballot(!ok);      // (DIET: the tile epilogue finds it in the sums)
             double dsafe;
             asm("v_max_f64 %0, %1, %2" : "=v"(dsafe) : "v"(den[u]), "s"(2.2250738585072014e-308));   // (scalar operand: no registers)
             r = fast_recip(dsafe);
@@ -494,7 +506,8 @@ tile_estep_kernel(uint32_t Hrt, const TileHdr *__restrict__ tiles, const uint32_
                   const uint32_t *__restrict__ dict, const double *__restrict__ word_weight,
                   const double *__restrict__ theta, double *__restrict__ partials,
                   const uint32_t *__restrict__ slot_dest, double *__restrict__ acc_direct,
-                  EmScalars *__restrict__ sc, uint32_t n_tiles, ErrArgs ea, SetArgs sets) {
+                  EmScalars *__restrict__ sc, uint32_t n_tiles, ErrArgs ea, SetArgs sets,
+                  uint32_t lead_mask /* ~0: the headers' n_one is used; 0: one loop for every batch */) {
     constexpr int LDS_ACC_DOUBLES = lds_acc_doubles(WEIGHTED, HT);
     __shared__ __attribute__((aligned(16))) double s_theta[lds_theta_doubles(WEIGHTED, HT)];
     __shared__ __attribute__((aligned(16))) double2 s_ftab[32];      // [16] pairs (bit0, bit1) of a nibble, [16] pairs (bit2, bit3)
@@ -537,6 +550,15 @@ tile_estep_kernel(uint32_t Hrt, const TileHdr *__restrict__ tiles, const uint32_
     constexpr int UB = estep_batches(WEIGHTED, HT), PD = WEIGHTED ? GBRS_WEIGHTED_PD : (HT == 16 ? GBRS_H16_PD : GBRS_RAW_PD);
     const uint32_t b0 = (uint32_t)(((uint64_t)th.n_batches * wave) / TILE_WAVES);
     const uint32_t b1 = (uint32_t)(((uint64_t)th.n_batches * (wave + 1)) / TILE_WAVES);
+    // Two loops over this wavefront's batches: the whole rings of it that lie in the tile's leading one-word batches
+    // (TileHdr::n_one) through the LEAD form of tile_batches, the rest through the general one.  What the general form asks of
+    // every batch - is any row longer than a word, is this word padding, is a denominator zero - the layout has answered for
+    // those batches once.  The switch falls on a ring boundary; the lanes' state carries over, and the arithmetic and
+    // its association are the single loop's.
+    constexpr bool SPLIT = HT > 0 && HT <= 8 && !WEIGHTED && !DET;
+    const uint32_t n_lead = SPLIT ? ((uint32_t)th.n_one & lead_mask) : 0u;
+    uint32_t bm = b0;
+    if (SPLIT && n_lead > b0) bm = b0 + ((min(b1, n_lead) - b0) / PD) * PD;
     // The ring is filled through a buffer descriptor of this wavefront's run [tile base, batch b1): the address is
     // one 32-bit vector offset advanced once per PD batches (the slot is an immediate), and a batch past the
     // run reads as zero words through the descriptor's range check - no branch, no select.
@@ -650,20 +672,42 @@ tile_estep_kernel(uint32_t Hrt, const TileHdr *__restrict__ tiles, const uint32_
         if constexpr (estep_uses_zlo(estep_batches(WEIGHTED, HT))) asm volatile("v_mov_b32 %0, 0" : "=v"(zlo[k]));
         else zlo[k] = 0;
     }
-    const uint32_t misfit_bits = pair_misfit_bits(H, PB, lane);
     LaneAcc<HC> st;
 #pragma unroll
     for (int h = 0; h < HC; ++h) st.c[h] = st.pc[h] = 0.0;
     if constexpr (estep_theta_regs(UB, HT, DET)) {
 #pragma unroll
-        for (int h = 0; h < HC; ++h) st.th[h] = 0.0;       // finite: a padding word multiplies it by 0.0
+        for (int h = 0; h < HC / 2; ++h) st.th[h] = theta_pair_t{0.0, 0.0};       // finite: a padding word multiplies it by 0.0
     }
     st.cidx = st.pidx = 0xFFFFFFFFu;
     st.bad = 0;
+    if constexpr (SPLIT) {
+        for (uint32_t b = b0; b < bm; b += PD) {
+#pragma unroll
+            for (int tt = 0; tt < PD; ++tt) {
+                const uint32_t w[1] = {ring[tt]};
+                const double wt[1] = {1.0};
+                ring[tt] = load_word(PD + tt);                         // refill PD batches ahead
+                tile_batches<HT, false, HC, false, 1, ONEWORD, true>(w, wt, H, PB, lane, s_theta, my_acc, st, zlo, s_ftab, 0u);
+            }
+            voff += PD * 256;
+            asm volatile("" : "+v"(voff));
+        }
+        if constexpr (estep_theta_regs(UB, HT, DET)) {
+            // (opaque: the theta registers of the two loops are then one set inside each loop, not a pair of them)
+#pragma unroll
+            for (int h = 0; h < HC / 2; ++h) asm volatile("" : "+v"(st.th[h]));
+        }
+    }
+    // (what only the general form needs is made here, behind the first loop, from an opaque copy of the lane: it is not
+    // carried in a register through that loop)
+    int lane_g = lane;
+    if constexpr (SPLIT) asm volatile("" : "+v"(lane_g));
+    const uint32_t misfit_bits = pair_misfit_bits(H, PB, lane_g);
 #if defined(GBRS_ABLATE_BATCHES)
-    for (uint32_t b = b0; b < b0; b += PD) {
+    for (uint32_t b = bm; b < bm; b += PD) {
 #else
-    for (uint32_t b = b0; b < b1; b += PD) {
+    for (uint32_t b = bm; b < b1; b += PD) {
 #endif
 #pragma unroll
         for (int tt = 0; tt < PD / UB; ++tt) {
@@ -718,6 +762,11 @@ tile_estep_kernel(uint32_t Hrt, const TileHdr *__restrict__ tiles, const uint32_
     asm volatile("" : "+v"(tix));           // opaque: nothing of the epilogue's index arithmetic is hoisted above the batch loop
     for (uint32_t i = tix; i < DH; i += TILE_THREADS) {
         double a = sum_copies<false>(s_acc, i, K, stride);
+        // a row without abundance in the tile's leading one-word batches (tile_batches, LEAD): not flagged where it was
+        // divided, it left >= 4.49e307 in a sum - as do inf and NaN; a legitimate sum is at most the number of reads.
+        // (The one difference from the in-loop flag: a denormal denominator, whose reciprocal was inf before and is
+        // 4.49e307 now, is reported.)
+        if (SPLIT && estep_theta_regs(UB, HT, DET) && n_lead != 0 && !(a < 4e307)) sc->float_error = 1;
 #if defined(GBRS_ABLATE_ATOMICS) || defined(GBRS_ABLATE_BATCHES)
         a = 1.0;                                  // timing-only builds: keep theta finite
 #endif
@@ -885,7 +934,7 @@ tile_estep_persistent_kernel(uint32_t Hrt, const TileHdr *__restrict__ tiles, co
     for (int h = 0; h < HC; ++h) st.c[h] = st.pc[h] = 0.0;
     if constexpr (estep_theta_regs(UB, HT, false)) {
 #pragma unroll
-        for (int h = 0; h < HC; ++h) st.th[h] = 0.0;
+        for (int h = 0; h < HC / 2; ++h) st.th[h] = theta_pair_t{0.0, 0.0};
     }
     st.cidx = st.pidx = 0xFFFFFFFFu;
     st.bad = 0;

@@ -32,6 +32,9 @@ EXPORTS = [
     "gbrs_matops_create", "gbrs_matops_intersect", "gbrs_matops_append_rows", "gbrs_matops_keep_unique_rows",
     "gbrs_matops_mask_columns", "gbrs_matops_sizes", "gbrs_matops_get", "gbrs_matops_destroy",
     "gbrs_matops_shared_counts", "gbrs_matops_shared_counts_get", "gbrs_matops_shared_counts_info",
+    "gbrs_tensor_create", "gbrs_tensor_set_groups", "gbrs_tensor_reset", "gbrs_tensor_multiply",
+    "gbrs_tensor_multiply_tensor", "gbrs_tensor_normalize", "gbrs_tensor_sum_reads", "gbrs_tensor_sum_loci",
+    "gbrs_tensor_copy", "gbrs_tensor_values", "gbrs_tensor_set_values", "gbrs_tensor_nnz", "gbrs_tensor_destroy",
     "gbrs_format_double", "gbrs_write_locus_table", "gbrs_parse_length_table", "gbrs_parse_genotype_table",
     "gbrs_decode_chunks", "gbrs_inflate_backend", "gbrs_zip_directory", "gbrs_npz_stack", "gbrs_zip_read_members", "gbrs_parse_number_table",
 ]
@@ -172,6 +175,19 @@ def load():
         "gbrs_matops_shared_counts_get": [vp, vp, vp, vp],
         "gbrs_matops_shared_counts_info": [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u32),
                                            C.POINTER(u64), C.POINTER(u64), C.POINTER(dbl)],
+        "gbrs_tensor_create": [u64, u32, u32, pp, pp, pp, vp, i32, pp],
+        "gbrs_tensor_set_groups": [vp, i64, vp, vp],
+        "gbrs_tensor_reset": [vp],
+        "gbrs_tensor_multiply": [vp, i32, vp, u64],
+        "gbrs_tensor_multiply_tensor": [vp, vp],
+        "gbrs_tensor_normalize": [vp, i32],
+        "gbrs_tensor_sum_reads": [vp, vp],
+        "gbrs_tensor_sum_loci": [vp, vp],
+        "gbrs_tensor_copy": [vp, pp],
+        "gbrs_tensor_values": [vp, u32, vp, vp, u64],
+        "gbrs_tensor_set_values": [vp, u32, vp, u64],
+        "gbrs_tensor_nnz": [vp, vp],
+        "gbrs_tensor_destroy": [vp],
     }
     sigs.update(_host_signatures())
     for name, args in sigs.items():

@@ -195,6 +195,12 @@ class AlignmentPropertyMatrix:
                 self.values[h] = np.ascontiguousarray(self.values[h][keep])
             self.indptr[h] = np.concatenate(([0], np.cumsum(np.where(keep_col, width, 0)))).astype(np.uint32)
 
+    def on_device(self, device=0):
+        """The tensor with its values on the device (gbrs_amd.tensor.DeviceTensor): reset / multiply / normalize_reads /
+        sum / copy of the reference's AlignmentPropertyMatrix."""
+        from .tensor import DeviceTensor
+        return DeviceTensor(self, device=device)
+
     @property
     def nnz(self):
         self.apply_haplotype_mask()

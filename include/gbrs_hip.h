@@ -432,6 +432,52 @@ int gbrs_matops_shared_counts_info(gbrs_matops_t *m, uint64_t *num_columns, uint
                                    uint64_t *peak_device_bytes, double *device_ms);
 int gbrs_matops_destroy(gbrs_matops_t *m);
 
+/* The alignment tensor with values, and the arithmetic the reference builds every model from (emase/Sparse3DMatrix.py
+ * reset :220-228, multiply :314-377, copy; emase/AlignmentPropertyMatrix.py sum :275-303, normalize_reads :305-370).
+ * A tensor is the stored entries (read r, haplotype h, locus l) of the per-haplotype CSC arrays with one double each,
+ * `count` (nullable) and gene groups (optional).  The structure never changes after create; copy() shares it by reference
+ * count, so a handle and its copies may be destroyed in any order.  They also share one stream and the structure's
+ * scratch buffers: drive a tensor and its copies from one thread.
+ *   create      values: NULL (every entry 1) or H pointers, values[h] lined up with indices[h].  Row ids are checked
+ *               against num_rows.  GBRS_ERR_UNSUPPORTED with 2^32 - 1 or more entries or 2^27 or more loci.
+ *   set_groups  the genes of normalize(GROUP | HAPLOGROUP): the groups, then every locus in no group as a gene of its own
+ *               (validation and messages as gbrs_em_set_groups).  Without the call every locus is a gene of its own.  The
+ *               genes belong to the structure: they change for every copy.
+ *   reset       v = 1
+ *   multiply    form 1: v *= m[l], m_len = L           (multiplier 1-D, axis 1)
+ *               form 2: v *= m[r], m_len = R           (1-D, axis 2)
+ *               form 3: v *= m[r*H + h], m_len = R*H   (2-D dense R x H, axis 0)
+ *               form 4: v *= m[h*L + l], m_len = H*L   (2-D H x L, axis 2)
+ *               m is a host array; any other form or length is GBRS_ERR_INVALID.
+ *   multiply_tensor   v *= other's v; other must share t's structure (t itself or a copy), else GBRS_ERR_UNSUPPORTED
+ *   normalize   axis 0 LOCUS, 1 HAPLOTYPE, 2 READ, 3 GROUP, 4 HAPLOGROUP: v /= the sum over the read's entries of the same
+ *               locus / haplotype / read / gene / gene and haplotype.  LOCUS, GROUP and HAPLOGROUP first eliminate every
+ *               entry whose value is 0 (the reference's eliminate_zeros()): it keeps 0 through every later operation,
+ *               reset included, and no longer counts in nnz.  A live entry over a zero sum is left unchanged and the call
+ *               returns GBRS_ERR_FLOAT after the other reads have been normalised.
+ *   sum_reads   out (H x L) = sum over the reads of count[r] * v (count 1 when absent).  Float atomics: the last bits
+ *               depend on the order of arrival.  Every other operation here is bit-identical from run to run.
+ *   sum_loci    out (R x H) = sum over the loci of v
+ *   values / set_values   one haplotype's values in the order of indices[h] (len = its number of stored entries);
+ *               live (nullable, uint8) = 1 where the entry is not eliminated.  set_values leaves eliminated entries 0.
+ *   nnz         live entries per haplotype, uint64[H] */
+typedef struct gbrs_tensor gbrs_tensor_t;
+int gbrs_tensor_create(uint64_t num_rows, uint32_t num_loci, uint32_t num_haps, const uint32_t *const *indptr,
+                       const uint32_t *const *indices, const double *const *values /* nullable: ones */,
+                       const double *count /* nullable */, int device, gbrs_tensor_t **out);
+int gbrs_tensor_set_groups(gbrs_tensor_t *t, int64_t num_groups, const int64_t *group_ptr, const int64_t *members);
+int gbrs_tensor_reset(gbrs_tensor_t *t);
+int gbrs_tensor_multiply(gbrs_tensor_t *t, int form, const double *m, uint64_t m_len);
+int gbrs_tensor_multiply_tensor(gbrs_tensor_t *t, const gbrs_tensor_t *other);
+int gbrs_tensor_normalize(gbrs_tensor_t *t, int axis);
+int gbrs_tensor_sum_reads(gbrs_tensor_t *t, double *out_HxL);
+int gbrs_tensor_sum_loci(gbrs_tensor_t *t, double *out_RxH);
+int gbrs_tensor_copy(gbrs_tensor_t *t, gbrs_tensor_t **out);
+int gbrs_tensor_values(gbrs_tensor_t *t, uint32_t hap, double *out, uint8_t *live /* nullable */, uint64_t len);
+int gbrs_tensor_set_values(gbrs_tensor_t *t, uint32_t hap, const double *v, uint64_t len);
+int gbrs_tensor_nnz(gbrs_tensor_t *t, uint64_t *per_hap);
+int gbrs_tensor_destroy(gbrs_tensor_t *t);
+
 /* `gbrs bam2emase` (emase/AlignmentMatrixFactory.py:26-142): a BAM file -> the per-haplotype CSC incidence
  * matrices of the EMASE format plus the sorted distinct read names.
  *   open       reads the BGZF/BAM header (host only).  n_ref / ref_names_len size the buffers of

@@ -18,6 +18,8 @@ EXPORTS = [
     "gbrs_last_error", "gbrs_abi_version", "gbrs_device_count", "gbrs_warm_up",
     "gbrs_em_create", "gbrs_em_create_device", "gbrs_em_create_masked", "gbrs_em_create_masked_device", "gbrs_em_set_initial_values", "gbrs_em_prepare", "gbrs_em_step", "gbrs_em_run",
     "gbrs_em_set_groups", "gbrs_em_step_model", "gbrs_em_posterior",
+    "gbrs_em_resample", "gbrs_em_weights", "gbrs_em_resample_info",
+    "gbrs_em_bootstrap_begin", "gbrs_em_bootstrap_add", "gbrs_em_bootstrap_get",
     "gbrs_em_get", "gbrs_em_set_theta", "gbrs_em_group_sums", "gbrs_em_estep_partial",
     "gbrs_em_finish_step", "gbrs_em_prepare_partial", "gbrs_em_finish_prepare", "gbrs_em_stream",
     "gbrs_em_set_stream",
@@ -60,6 +62,8 @@ GBRS_EM_ONE_SHOT = 256
 GBRS_EM_NO_LOCUS_SETS = 512
 GBRS_EM_GROUPED_MODELS = 1024
 GBRS_EM_POSTERIOR = 2048
+GBRS_EM_RESAMPLE = 4096
+GBRS_RESAMPLE_BASE = 0xFFFFFFFF
 
 
 class EmInfo(C.Structure):
@@ -128,6 +132,12 @@ def load():
         "gbrs_em_set_groups": [vp, i64, vp, vp],
         "gbrs_em_step_model": [vp, i32, i32, C.POINTER(dbl)],
         "gbrs_em_posterior": [vp, u32, vp, u64],
+        "gbrs_em_resample": [vp, u64, u32],
+        "gbrs_em_weights": [vp, vp],
+        "gbrs_em_resample_info": [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)],
+        "gbrs_em_bootstrap_begin": [vp, i64, vp, vp],
+        "gbrs_em_bootstrap_add": [vp, vp, vp, vp, vp],
+        "gbrs_em_bootstrap_get": [vp, i32, C.POINTER(u32), vp, vp, vp, vp, vp, vp, vp, vp],
         "gbrs_em_get": [vp, vp, vp],
         "gbrs_em_set_theta": [vp, vp],
         "gbrs_em_group_sums": [vp, i64, vp, vp, i32, vp],

@@ -47,6 +47,13 @@ def build_parser():
     q.add_argument('--posterior-values', action='store_true',
                    help='(extension, implies -w) <outbase>.posterior.h5 carries the read-level posterior of every stored '
                         'alignment in the last E-step as /h*/data, computed on the device')
+    q.add_argument('--bootstrap', type=int, default=None, metavar='B',
+                   help='(extension) after the ordinary run, B >= 2 bootstrap refits on reads resampled on the device; '
+                        'writes <outbase>.isoforms.bootstrap.npz and, with a group file, <outbase>.genes.bootstrap.npz '
+                        '(means and standard deviations of TPM and expected read counts)')
+    q.add_argument('--bootstrap-seed', type=int, default=0, metavar='S', help='with --bootstrap: seed of the draw (default 0)')
+    q.add_argument('--keep-replicates', action='store_true',
+                   help='with --bootstrap: the files also carry tpm and expected_read_counts of every replicate (B x H x n)')
     q.add_argument('-v', '--verbose', action='count', default=0)
     q.add_argument('--device', type=int, default=0, help='HIP device ordinal (extension)')
     q.add_argument('--merge-identical-rows', action='store_true',
@@ -175,6 +182,8 @@ def main(argv=None) -> int:
         if args.command == 'quantify':
             if args.multiread_model not in (1, 2, 3, 4):
                 raise RuntimeError('-M, --multiread-model must be one of 1, 2, 3, or 4')
+            from .quantify import check_bootstrap_args
+            check_bootstrap_args(args.bootstrap, args.merge_identical_rows, args.gpus)
         if args.command == 'quantify' and args.gpus is not None:
             # N child processes, one per rank; this process opens no device
             from .sharded import launch
@@ -189,6 +198,8 @@ def main(argv=None) -> int:
                      report_posterior=args.report_posterior or args.posterior_values,
                      posterior_values=args.posterior_values, device=args.device,
                      merge_identical_rows=args.merge_identical_rows, stage_times=stages,
+                     bootstrap=args.bootstrap, bootstrap_seed=args.bootstrap_seed,
+                     keep_replicates=args.keep_replicates,
                      one_shot=True)         # the command builds one handle and exits: GBRS_EM_ONE_SHOT
         elif args.command == 'worker':
             from .worker import main as worker_main

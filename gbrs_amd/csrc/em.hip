@@ -369,7 +369,7 @@ __global__ void __launch_bounds__(256)
 csc_acc_kernel(uint64_t n, uint32_t ncols, uint32_t L, uint32_t H,
                const uint64_t *__restrict__ col_ptr, const uint32_t *__restrict__ ent_row,
                const double *__restrict__ count, const double *__restrict__ den,
-               double *__restrict__ acc, EmScalars *__restrict__ sc) {
+               double *__restrict__ acc, EmScalars *__restrict__ sc, uint32_t relax_zero_weight) {
     if (!ONES && sc->stop) return;
     const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k - (threadIdx.x & 63) >= n) return;
@@ -380,7 +380,8 @@ csc_acc_kernel(uint64_t n, uint32_t ncols, uint32_t L, uint32_t H,
         const uint32_t r = ent_row[k];
         const double d = den[r];
         const double cnt = count ? count[r] : 1.0;
-        if (d > 0.0) w = cnt / d; else sc->float_error = 1;
+        // (resampling handles: a zero-weight row takes no part, its own zero denominator is no float error)
+        if (d > 0.0) w = cnt / d; else if (!(relax_zero_weight && cnt == 0.0)) sc->float_error = 1;
     }
     const uint32_t c0 = __shfl(c, 0, WAVE);
     if (__all(c == c0)) {
@@ -515,6 +516,7 @@ post_value_kernel(uint64_t k0, uint64_t k1, uint32_t ncols, uint32_t L, uint32_t
 
 #include "em_tiles.inc"
 #include "em_models.inc"
+#include "em_resample.inc"
 
 }  // namespace gbrs
 
@@ -600,6 +602,22 @@ struct gbrs_em {
     int post_model = 0;                              // model of the last step through gbrs_em_step / _step_model / _run; 0: none
     bool post_den_valid = false;
 
+    // Bootstrap replicates (GBRS_EM_RESAMPLE, em_resample.inc).  `count` holds the CURRENT row weights (what the CSC,
+    // models 1-3 and posterior kernels read); base_count the file's counts as integers (absent: every row counts once);
+    // big_rows the rows whose count is above resample_cut (a workgroup each in the draw).
+    bool resample = false, has_base = false;
+    DevBuf<uint32_t> base_count, big_rows;
+    uint32_t n_big = 0, resample_cut = 256;
+    // replicate statistics (gbrs_em_bootstrap_begin / _add / _get): level 0 isoforms, 1 genes; quantity 0 TPM, 1 counts
+    struct Stats {
+        bool active = false;
+        uint32_t n = 0;
+        int64_t G = 0;
+        DevBuf<int64_t> gptr, gmem;
+        DevBuf<double> theta_sum;
+        DevBuf<double> cur[2][2], mean[2][2], m2[2][2], tot_mean[2][2], tot_m2[2][2];
+    } stats;
+
     int red_blocks() const { return (int)std::min<uint64_t>(RED_BLOCKS, (L + RED_THREADS - 1) / RED_THREADS); }
 };
 
@@ -644,7 +662,8 @@ int em_estep_tiles_h(gbrs_em *em) {
         em->err_pending = false;
         const dim3 grid((unsigned)tl.n_tiles + ea.n_err_blocks), block(TILE_THREADS);
         const double *ww = tl.weighted ? tl.word_weight.p : (const double *)nullptr;
-        const SetArgs sets{em->tL(), tl.n_sets ? tl.set_ptr.p : nullptr, tl.set_members.p, tl.dest_list.p, tl.dict_b.p, tl.dest_b.p};
+        const SetArgs sets{em->tL(), tl.n_sets ? tl.set_ptr.p : nullptr, tl.set_members.p, tl.dest_list.p, tl.dict_b.p, tl.dest_b.p,
+                           em->resample ? 1u : 0u};
         const uint32_t lead_mask = em->lead_mask;
 #define GBRS_LAUNCH_TILES(W, D)                                                                                        \
         hipLaunchKernelGGL((tile_estep_kernel<HT, W, ONES, D>), grid, block, 0, em->stream, em->tH(), tl.tiles.p, tl.words.p, \
@@ -697,11 +716,11 @@ int em_estep_tiles(gbrs_em *em, bool materialize, bool skip_gather = false) {
         if (tl.deterministic)
             hipLaunchKernelGGL(long_rows_estep_serial_kernel<ONES>, dim3(1), dim3(64), 0, em->stream, tl.n_long, em->tH(),
                                tl.long_ptr.p, tl.long_loc.p, tl.long_mask.p, tl.long_weight.p, em->theta.p,
-                               tl.acc_extra.p, em->scalars.p);
+                               tl.acc_extra.p, em->scalars.p, em->resample ? 1u : 0u);
         else
             hipLaunchKernelGGL(long_rows_estep_kernel<ONES>, dim3((unsigned)((tl.n_long + 3) / 4)), dim3(256), 0, em->stream,
                                tl.n_long, em->tH(), tl.long_ptr.p, tl.long_loc.p, tl.long_mask.p, tl.long_weight.p,
-                               em->theta.p, tl.acc_extra.p, em->scalars.p);
+                               em->theta.p, tl.acc_extra.p, em->scalars.p, em->resample ? 1u : 0u);
     }
     if (em->ev_after_estep) {
         GBRS_HIP_CHECK(hipEventRecord(em->ev_after_estep, em->stream));
@@ -743,7 +762,7 @@ int em_estep(gbrs_em *em, bool materialize = false) {
                        em->H, em->col_ptr.p, em->ent_row.p, em->theta.p, em->den.p, em->scalars.p);
     hipLaunchKernelGGL(csc_acc_kernel<ONES>, dim3(grid), dim3(256), 0, em->stream, n, ncols, em->L,
                        em->H, em->col_ptr.p, em->ent_row.p, em->has_count ? em->count.p : nullptr,
-                       em->den.p, em->acc.p, em->scalars.p);
+                       em->den.p, em->acc.p, em->scalars.p, em->resample ? 1u : 0u);
     GBRS_HIP_CHECK(hipGetLastError());
     return GBRS_OK;
 }
@@ -1253,12 +1272,18 @@ int em_create_impl(uint64_t R, uint32_t L, uint32_t H, const uint32_t *const *in
     if (H < 1 || H > 32 || L < 1 || R < 1 || R > 0xFFFFFFFFull)
         return fail(GBRS_ERR_INVALID, "The shape must be a tuple of three positive integers (H <= 32, R < 2^32).");
     if (!indptr || !indices) return fail(GBRS_ERR_INVALID, "indptr/indices tables are NULL");
+    const bool resample = (flags & GBRS_EM_RESAMPLE) != 0;
+    if (resample && (flags & (GBRS_EM_MERGE_IDENTICAL_ROWS | GBRS_EM_SIDE_BY_SIDE)))
+        return fail(GBRS_ERR_UNSUPPORTED, "GBRS_EM_RESAMPLE draws a weight per file row: not available with "
+                                          "GBRS_EM_MERGE_IDENTICAL_ROWS or GBRS_EM_SIDE_BY_SIDE");
     GBRS_TRY(select_device(device));
     gbrs_em *em = new gbrs_em();
     struct Guard { gbrs_em *p; ~Guard() { if (p) gbrs_em_destroy(p); } } guard{em};
     em->device = device;
     em->R = R; em->L = L; em->H = H; em->flags = flags;
-    em->has_count = count != nullptr;
+    em->has_count = count != nullptr || resample;       // (a resampling handle is a weighted one: base weights of count or ones)
+    em->resample = resample;
+    em->has_base = resample && count != nullptr;
     em->has_len = eff_len != nullptr;
     GBRS_HIP_CHECK(hipStreamCreateWithFlags(&em->stream, hipStreamDefault));
     GBRS_HIP_CHECK(hipEventCreate(&em->ev0));
@@ -1294,9 +1319,39 @@ int em_create_impl(uint64_t R, uint32_t L, uint32_t H, const uint32_t *const *in
     GBRS_HIP_CHECK(hipMemset(em->partials.p, 0, em->partials.bytes()));
     GBRS_HIP_CHECK(hipMemset(em->msums.p, 0, em->msums.bytes()));
     GBRS_HIP_CHECK(hipMemset(em->counts.p, 0, em->counts.bytes()));
-    if (count) {
-        GBRS_TRY(em->count.alloc(R));
-        GBRS_HIP_CHECK(hipMemcpy(em->count.p, count, R * sizeof(double), kind));
+    if (count || resample) GBRS_TRY(em->count.alloc(R));
+    if (count) GBRS_HIP_CHECK(hipMemcpy(em->count.p, count, R * sizeof(double), kind));
+    if (resample) {
+        const unsigned rgrid = (unsigned)((R + 255) / 256);
+        if (count) {
+            DevBuf<int> bad;
+            GBRS_TRY(bad.alloc(1));
+            GBRS_TRY(em->base_count.alloc(R));
+            GBRS_HIP_CHECK(hipMemsetAsync(bad.p, 0, sizeof(int), em->stream));
+            hipLaunchKernelGGL(resample_base_kernel, dim3(rgrid), dim3(256), 0, em->stream, R, em->count.p, em->base_count.p, bad.p);
+            int hbad = 0;
+            GBRS_HIP_CHECK(hipMemcpyAsync(&hbad, bad.p, sizeof(int), hipMemcpyDeviceToHost, em->stream));
+            GBRS_HIP_CHECK(hipStreamSynchronize(em->stream));
+            if (hbad)
+                return fail(GBRS_ERR_INVALID, "GBRS_EM_RESAMPLE needs integer counts in [0, 2^32): a row is drawn count[r] times");
+            if (const char *env = std::getenv("GBRS_TUNING_RESAMPLE_CUT"); env && std::atoi(env) > 0)
+                em->resample_cut = (uint32_t)std::atoi(env);
+            DevBuf<uint32_t> n_big;
+            GBRS_TRY(n_big.alloc(1));
+            for (int pass = 0; pass < 2; ++pass) {
+                GBRS_HIP_CHECK(hipMemsetAsync(n_big.p, 0, 4, em->stream));
+                hipLaunchKernelGGL(resample_big_rows_kernel, dim3(rgrid), dim3(256), 0, em->stream, R, em->base_count.p,
+                                   em->resample_cut, n_big.p, pass ? em->big_rows.p : (uint32_t *)nullptr);
+                GBRS_HIP_CHECK(hipMemcpyAsync(&em->n_big, n_big.p, 4, hipMemcpyDeviceToHost, em->stream));
+                GBRS_HIP_CHECK(hipStreamSynchronize(em->stream));
+                if (em->n_big == 0) break;
+                if (pass == 0) GBRS_TRY(em->big_rows.alloc(em->n_big));
+            }
+        } else {
+            hipLaunchKernelGGL(resample_draw_kernel<true>, dim3(rgrid), dim3(256), 0, em->stream, R, (const uint32_t *)nullptr,
+                               0u, 0u, 0u, 0u, em->count.p);
+        }
+        GBRS_HIP_CHECK(hipGetLastError());
     }
     if (eff_len) {
         GBRS_TRY(em->eff_len.alloc(LH));
@@ -1319,10 +1374,11 @@ int em_create_impl(uint64_t R, uint32_t L, uint32_t H, const uint32_t *const *in
         int row_order = 2;
         if (flags & GBRS_EM_FORCE_INTERLEAVE) row_order = 1;
         else if (flags & GBRS_EM_NO_STREAMS) {
-            const bool distinct = count != nullptr || (flags & GBRS_EM_MERGE_IDENTICAL_ROWS);
+            const bool distinct = em->has_count || (flags & GBRS_EM_MERGE_IDENTICAL_ROWS);
             row_order = (distinct && !(flags & GBRS_EM_NO_INTERLEAVE)) ? 1 : 0;
         }
         em->tl.retain_temporaries = (flags & GBRS_EM_ONE_SHOT) != 0;
+        em->tl.keep_row_ids = resample;
         // 16 haplotypes as half-loci on the 8-haplotype kernels (em_layout.h; the review's "two halves of 8"): built, parity-green,
         // NO gain - one GPU's shard of config 5: E-step 0.1518 ms against 0.1525 (the words double, the cost per word halves) and
         // the iteration 0.1997 against 0.1744 (gather and M-step as two launches over every element).  GBRS_TUNING_HALF_LOCI=1
@@ -1330,14 +1386,14 @@ int em_create_impl(uint64_t R, uint32_t L, uint32_t H, const uint32_t *const *in
         {
             const char *env = std::getenv("GBRS_TUNING_HALF_LOCI");
             const bool want = env ? std::atoi(env) != 0 : false;
-            const bool weighted = count != nullptr || (flags & GBRS_EM_MERGE_IDENTICAL_ROWS);
+            const bool weighted = em->has_count || (flags & GBRS_EM_MERGE_IDENTICAL_ROWS);
             em->view = (H == 16 && want && !weighted && !(flags & GBRS_EM_DETERMINISTIC) && (uint64_t)L * 2 < (1u << 27)) ? 2u : 1u;
         }
         GBRS_TRY(build_tile_layout(em->tl, R, em->tL(), em->tH(), n, em->ent_row.p, em->col_ptr.p,
-                                   count ? em->count.p : nullptr, (flags & GBRS_EM_MERGE_IDENTICAL_ROWS) != 0,
+                                   em->has_count ? em->count.p : nullptr, (flags & GBRS_EM_MERGE_IDENTICAL_ROWS) != 0,
                                    row_order, (flags & GBRS_EM_DETERMINISTIC) != 0,
                                    em->stream, (flags & GBRS_EM_SIDE_BY_SIDE) ? 2u : 1u,
-                                   (flags & GBRS_EM_NO_LOCUS_SETS) == 0 && !count &&
+                                   (flags & GBRS_EM_NO_LOCUS_SETS) == 0 && !em->has_count &&
                                        !(flags & GBRS_EM_MERGE_IDENTICAL_ROWS),     // (weighted rows: their tiles are dictionary-bound)
                                    0, em->view));
         em->layout = 1;
@@ -1502,6 +1558,9 @@ int em_prepare_partial(gbrs_em *em) {
 
 int gbrs_em_set_initial_values(gbrs_em_t *em, const double *const *values) {
     if (!em || !values) return fail(GBRS_ERR_INVALID, "NULL argument");
+    if (em->resample)
+        return fail(GBRS_ERR_UNSUPPORTED, "stored alignment values are not available on a GBRS_EM_RESAMPLE handle: their "
+                                          "cached column sums would carry the count they were made with");
     if (!em->ent_row.p || !em->den.p)
         return fail(GBRS_ERR_STATE, "the handle no longer holds the CSC arrays: create it with GBRS_EM_KEEP_CSC "
                                     "and call gbrs_em_set_initial_values once, before prepare");
@@ -2111,6 +2170,163 @@ int gbrs_alignment_counts(uint64_t R, uint32_t L, uint32_t H, const uint32_t *co
     const int st = gbrs_counts_get(c, locus_group, num_out_loci, aln_counts, allele_unique, locus_unique);
     (void)gbrs_counts_destroy(c);
     return st;
+}
+
+// ---- bootstrap replicates (GBRS_EM_RESAMPLE; kernels in em_resample.inc) ------------------------------------------
+int gbrs_em_resample(gbrs_em_t *em, uint64_t seed, uint32_t replicate) {
+    RoctxRange roctx_range("gbrs_em_resample");
+    if (!em) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (!em->resample) return fail(GBRS_ERR_STATE, "the handle was not created with GBRS_EM_RESAMPLE");
+    GBRS_TRY(select_device(em->device));
+    GBRS_TRY(em_flush_err(em));
+    const uint64_t R = em->R;
+    const unsigned rgrid = (unsigned)((R + 255) / 256);
+    const uint32_t *base = em->has_base ? em->base_count.p : (const uint32_t *)nullptr;
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    if (replicate == GBRS_RESAMPLE_BASE) {
+        hipLaunchKernelGGL(resample_draw_kernel<true>, dim3(rgrid), dim3(256), 0, em->stream, R, base, 0u, 0u, 0u, 0u, em->count.p);
+    } else {
+        hipLaunchKernelGGL(resample_draw_kernel<false>, dim3(rgrid), dim3(256), 0, em->stream, R, base, em->resample_cut,
+                           replicate, k0, k1, em->count.p);
+        if (em->n_big)
+            hipLaunchKernelGGL(resample_big_kernel, dim3(em->n_big), dim3(256), 0, em->stream, em->n_big, em->big_rows.p, base,
+                               replicate, k0, k1, em->count.p);
+    }
+    // the weights onto every structure the handle steps on: the tiles' words and the long rows (the CSC, models 1-3 and
+    // posterior kernels read `count` itself; prepare runs on the same structures)
+    const TileLayout &tl = em->tl;
+    if (em->layout == 1 && tl.word_row.n)
+        hipLaunchKernelGGL(install_weights_kernel, dim3((unsigned)((tl.word_row.n + 255) / 256)), dim3(256), 0, em->stream,
+                           (uint64_t)tl.word_row.n, tl.word_row.p, em->count.p, tl.word_weight.p);
+    if (em->layout == 1 && tl.long_row.n)
+        hipLaunchKernelGGL(install_weights_kernel, dim3((unsigned)((tl.long_row.n + 255) / 256)), dim3(256), 0, em->stream,
+                           (uint64_t)tl.long_row.n, tl.long_row.p, em->count.p, tl.long_weight.p);
+    GBRS_HIP_CHECK(hipGetLastError());
+    em->prepared = false;                     // theta belongs to other weights: prepare comes next
+    em->post_model = 0;
+    GBRS_HIP_CHECK(hipStreamSynchronize(em->stream));
+    return GBRS_OK;
+}
+
+int gbrs_em_weights(gbrs_em_t *em, double *out) {
+    if (!em || !out) return fail(GBRS_ERR_INVALID, "NULL argument");
+    if (!em->resample) return fail(GBRS_ERR_STATE, "the handle was not created with GBRS_EM_RESAMPLE");
+    GBRS_TRY(select_device(em->device));
+    GBRS_HIP_CHECK(hipMemcpyAsync(out, em->count.p, em->R * sizeof(double), hipMemcpyDeviceToHost, em->stream));
+    GBRS_HIP_CHECK(hipStreamSynchronize(em->stream));
+    return GBRS_OK;
+}
+
+int gbrs_em_resample_info(gbrs_em_t *em, uint64_t *extra_device_bytes, uint64_t *num_big_rows, uint32_t *cut) {
+    if (!em) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (!em->resample) return fail(GBRS_ERR_STATE, "the handle was not created with GBRS_EM_RESAMPLE");
+    if (extra_device_bytes)
+        *extra_device_bytes = em->base_count.bytes() + em->big_rows.bytes() + em->tl.word_row.bytes() + em->tl.long_row.bytes() +
+                              (em->has_base ? 0 : em->count.bytes() + em->tl.word_weight.bytes() + em->tl.long_weight.bytes());
+    if (num_big_rows) *num_big_rows = em->n_big;
+    if (cut) *cut = em->resample_cut;
+    return GBRS_OK;
+}
+
+int gbrs_em_bootstrap_begin(gbrs_em_t *em, int64_t G, const int64_t *group_ptr, const int64_t *members) {
+    if (!em) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (G < 0 || (G > 0 && (!group_ptr || !members))) return fail(GBRS_ERR_INVALID, "bad group arguments");
+    GBRS_TRY(select_device(em->device));
+    gbrs_em::Stats &st = em->stats;
+    st.active = false;
+    st.n = 0;
+    st.G = G;
+    if (G > 0) {
+        const int64_t nm = group_ptr[G];
+        for (int64_t g = 0; g < G; ++g)
+            if (group_ptr[g + 1] < group_ptr[g]) return fail(GBRS_ERR_INVALID, "group_ptr not monotone");
+        for (int64_t k = 0; k < nm; ++k)
+            if (members[k] < 0 || members[k] >= (int64_t)em->L)
+                return fail(GBRS_ERR_INVALID, "group member %lld out of range", (long long)members[k]);
+        GBRS_TRY(st.gptr.alloc(G + 1));
+        GBRS_TRY(st.gmem.alloc(std::max<int64_t>(nm, 1)));
+        GBRS_HIP_CHECK(hipMemcpy(st.gptr.p, group_ptr, (G + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+        if (nm) GBRS_HIP_CHECK(hipMemcpy(st.gmem.p, members, nm * sizeof(int64_t), hipMemcpyHostToDevice));
+    }
+    GBRS_TRY(st.theta_sum.alloc(1));
+    for (int level = 0; level < 2; ++level) {
+        const size_t n = level == 0 ? em->L : (size_t)G;
+        for (int q = 0; q < 2; ++q) {
+            GBRS_TRY(st.cur[level][q].alloc(n * em->H));
+            GBRS_TRY(st.mean[level][q].alloc(n * em->H));
+            GBRS_TRY(st.m2[level][q].alloc(n * em->H));
+            GBRS_TRY(st.tot_mean[level][q].alloc(n));
+            GBRS_TRY(st.tot_m2[level][q].alloc(n));
+        }
+    }
+    st.active = true;
+    return GBRS_OK;
+}
+
+int gbrs_em_bootstrap_add(gbrs_em_t *em, double *tpm, double *counts, double *gene_tpm, double *gene_counts) {
+    if (!em) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    gbrs_em::Stats &st = em->stats;
+    if (!st.active) return fail(GBRS_ERR_STATE, "gbrs_em_bootstrap_begin has not been called");
+    if (!em->prepared) return fail(GBRS_ERR_STATE, "prepare() has not been called");
+    if ((gene_tpm || gene_counts) && st.G == 0) return fail(GBRS_ERR_INVALID, "gene-level values were asked for without groups");
+    GBRS_TRY(select_device(em->device));
+    GBRS_TRY(em_flush_err(em));
+    GBRS_TRY(em_refresh_counts(em));
+    const uint32_t L = em->L, H = em->H;
+    const uint64_t HL = (uint64_t)L * H;
+    hipStream_t s = em->stream;
+    st.n += 1;
+    hipLaunchKernelGGL(stats_sum_kernel, dim3(1), dim3(1024), 0, s, HL, em->theta.p, st.theta_sum.p);
+    hipLaunchKernelGGL(stats_current_kernel, dim3((unsigned)((HL + 255) / 256)), dim3(256), 0, s, L, H, em->theta.p, em->counts.p,
+                       st.theta_sum.p, st.cur[0][0].p, st.cur[0][1].p);
+    for (int q = 0; q < 2; ++q) {
+        hipLaunchKernelGGL(stats_fold_kernel, dim3((L + 255) / 256), dim3(256), 0, s, (uint64_t)L, H, st.n, st.cur[0][q].p,
+                           st.mean[0][q].p, st.m2[0][q].p, st.tot_mean[0][q].p, st.tot_m2[0][q].p);
+        if (st.G > 0) {
+            const int64_t total = st.G * (int64_t)H;
+            hipLaunchKernelGGL(stats_group_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, L, H, st.G, st.gptr.p,
+                               st.gmem.p, st.cur[0][q].p, st.cur[1][q].p);
+            hipLaunchKernelGGL(stats_fold_kernel, dim3((unsigned)((st.G + 255) / 256)), dim3(256), 0, s, (uint64_t)st.G, H, st.n,
+                               st.cur[1][q].p, st.mean[1][q].p, st.m2[1][q].p, st.tot_mean[1][q].p, st.tot_m2[1][q].p);
+        }
+    }
+    GBRS_HIP_CHECK(hipGetLastError());
+    double *outs[2][2] = {{tpm, counts}, {gene_tpm, gene_counts}};
+    for (int level = 0; level < 2; ++level)
+        for (int q = 0; q < 2; ++q)
+            if (outs[level][q] && st.cur[level][q].n)
+                GBRS_HIP_CHECK(hipMemcpyAsync(outs[level][q], st.cur[level][q].p, st.cur[level][q].bytes(), hipMemcpyDeviceToHost, s));
+    GBRS_HIP_CHECK(hipStreamSynchronize(s));
+    return GBRS_OK;
+}
+
+int gbrs_em_bootstrap_get(gbrs_em_t *em, int level, uint32_t *num_replicates, double *tpm_mean, double *tpm_sd,
+                          double *count_mean, double *count_sd, double *tpm_total_mean, double *tpm_total_sd,
+                          double *count_total_mean, double *count_total_sd) {
+    if (!em) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    gbrs_em::Stats &st = em->stats;
+    if (!st.active) return fail(GBRS_ERR_STATE, "gbrs_em_bootstrap_begin has not been called");
+    if (level != 0 && level != 1) return fail(GBRS_ERR_INVALID, "level is 0 (isoforms) or 1 (genes)");
+    if (level == 1 && st.G == 0) return fail(GBRS_ERR_INVALID, "gene-level statistics were asked for without groups");
+    if (num_replicates) *num_replicates = st.n;
+    if (st.n == 0) return fail(GBRS_ERR_STATE, "no replicate has been added");
+    GBRS_TRY(select_device(em->device));
+    GBRS_HIP_CHECK(hipStreamSynchronize(em->stream));
+    // the standard deviation with B - 1 in the denominator (one replicate: NaN, as numpy.std(ddof=1) gives)
+    const double denom = (double)st.n - 1.0;
+    auto fetch = [&](const DevBuf<double> &mean, const DevBuf<double> &m2, double *mean_out, double *sd_out) -> int {
+        if (mean_out && mean.n) GBRS_HIP_CHECK(hipMemcpy(mean_out, mean.p, mean.bytes(), hipMemcpyDeviceToHost));
+        if (sd_out && m2.n) {
+            GBRS_HIP_CHECK(hipMemcpy(sd_out, m2.p, m2.bytes(), hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < m2.n; ++i) sd_out[i] = std::sqrt(sd_out[i] / denom);
+        }
+        return GBRS_OK;
+    };
+    GBRS_TRY(fetch(st.mean[level][0], st.m2[level][0], tpm_mean, tpm_sd));
+    GBRS_TRY(fetch(st.mean[level][1], st.m2[level][1], count_mean, count_sd));
+    GBRS_TRY(fetch(st.tot_mean[level][0], st.tot_m2[level][0], tpm_total_mean, tpm_total_sd));
+    GBRS_TRY(fetch(st.tot_mean[level][1], st.tot_m2[level][1], count_total_mean, count_total_sd));
+    return GBRS_OK;
 }
 
 int gbrs_em_destroy(gbrs_em_t *em) {

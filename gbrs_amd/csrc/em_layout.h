@@ -104,6 +104,7 @@ struct SetArgs {
     uint32_t n_loci;                 // number of loci (the encoded dictionary does not need it; kept for checks)
     const uint32_t *set_ptr, *set_members, *dest_list;
     const uint32_t *dict_b, *dest_b; // per slot: second member / second destination of a two-member set
+    uint32_t relax_zero_weight;      // resampling handle (GBRS_EM_RESAMPLE): a zero-weight row's zero denominator is no float error
 };
 
 struct TileLayout {
@@ -139,6 +140,11 @@ struct TileLayout {
     DevBuf<uint32_t> long_loc, long_mask;
     DevBuf<double> long_weight;      // n_long
     DevBuf<double> acc_extra;        // L*H, global-atomic target of the long-row kernel
+    // Resampling handles (GBRS_EM_RESAMPLE): the file row behind every word (0xFFFFFFFF: padding) and every long row, so
+    // that new row weights can be written over word_weight / long_weight in place (install_weights, em.hip)
+    bool keep_row_ids = false;
+    DevBuf<uint32_t> word_row;       // n_batches * 64
+    DevBuf<uint32_t> long_row;       // n_long
     // Locus sets (GBRS_EM_NO_LOCUS_SETS switches them off).  A read whose alignments to several loci all carry the same
     // haplotype mask contributes  sum_h m_h * (theta[l1,h] + theta[l2,h] + ...)  to its denominator and the same v to every
     // one of those loci: the set {l1, l2, ...} behaves like one locus with theta = the sum of its members'.  The build

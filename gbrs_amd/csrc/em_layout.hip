@@ -608,7 +608,8 @@ __global__ void emit_words_kernel(uint64_t m_rows, uint32_t H, const uint32_t *_
                                   const uint32_t *__restrict__ hrow, const uint32_t *__restrict__ rowstart,
                                   const uint32_t *__restrict__ ploc, const uint32_t *__restrict__ pmask,
                                   const uint32_t *__restrict__ rowpad, uint32_t *__restrict__ words,
-                                  const double *__restrict__ row_weight, double *__restrict__ word_weight) {
+                                  const double *__restrict__ row_weight, double *__restrict__ word_weight,
+                                  const uint32_t *__restrict__ row_orig, uint32_t *__restrict__ word_row) {
     const uint64_t m = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= m_rows) return;
     const TileHdr th = hdr[tincl[m] - 1];
@@ -626,6 +627,7 @@ __global__ void emit_words_kernel(uint64_t m_rows, uint32_t H, const uint32_t *_
         }
         words[base + j] = pmask[p0 + j] | (j << H) | ((cnt - 1 - j) << (H + PB)) | (lo << (H + 2 * PB));
         if (word_weight) word_weight[base + j] = row_weight[m];
+        if (word_row) word_row[base + j] = row_orig[r];          // resampling handle: the file row the word's weight comes from
     }
 }
 
@@ -751,12 +753,13 @@ __global__ void locus_class_kernel(uint32_t L, const uint32_t *__restrict__ slot
 __global__ void long_rows_kernel(uint64_t n_long, uint64_t first, const uint32_t *__restrict__ srow,
                                  const uint32_t *__restrict__ rowstart, const uint32_t *__restrict__ row_orig,
                                  const double *__restrict__ count, uint64_t *__restrict__ len,
-                                 double *__restrict__ weight) {
+                                 double *__restrict__ weight, uint32_t *__restrict__ long_row) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_long) return;
     const uint32_t r = srow[first + i];
     len[i] = rowstart[r + 1] - rowstart[r];
     weight[i] = count ? count[row_orig[r]] : 1.0;
+    if (long_row) long_row[i] = row_orig[r];
 }
 
 __global__ void long_copy_kernel(uint64_t n_long, uint64_t first, const uint32_t *__restrict__ srow,
@@ -1099,6 +1102,7 @@ int build_tile_layout(TileLayout &out, uint64_t R, uint32_t L_in, uint32_t H, ui
     out.n_sets = 0;
     out.n_dest_rows = 0;
     const bool interleave = row_order == 1, streams = row_order == 2;
+    const bool keep_row_ids = out.keep_row_ids && !merge;      // (a merged row has no single file row)
     if (H > 16) return fail(GBRS_ERR_INVALID, "the tiled layout packs the haplotype mask in 16 bits (H <= 16)");
     if (N >= 0xFFFFFFFFull || L >= (1u << 27))
         return fail(GBRS_ERR_INVALID, "the tiled layout needs N < 2^32 entries and L < 2^27 loci per handle");
@@ -1419,8 +1423,9 @@ int build_tile_layout(TileLayout &out, uint64_t R, uint32_t L_in, uint32_t H, ui
         GBRS_TRY(llen.alloc(n_long));
         GBRS_TRY(out.long_ptr.alloc(n_long + 1));
         GBRS_TRY(out.long_weight.alloc(n_long));
+        if (keep_row_ids) GBRS_TRY(out.long_row.alloc(n_long));
         hipLaunchKernelGGL(long_rows_kernel, dim3(grid_for(n_long)), dim3(256), 0, s, n_long, n_short, srow.p, rowstart.p,
-                           row_orig.p, count, llen.p, out.long_weight.p);
+                           row_orig.p, count, llen.p, out.long_weight.p, keep_row_ids ? out.long_row.p : (uint32_t *)nullptr);
         GBRS_TRY(exclusive_scan(sc, llen.p, out.long_ptr.p, n_long, s));
         uint64_t tot = 0;
         GBRS_TRY(fetch_last_plus(out.long_ptr.p, llen.p, n_long, tot, s));
@@ -1432,7 +1437,8 @@ int build_tile_layout(TileLayout &out, uint64_t R, uint32_t L_in, uint32_t H, ui
         GBRS_TRY(out.acc_extra.alloc((size_t)L_in * H));
         GBRS_HIP_CHECK(hipStreamSynchronize(s));
     }
-    srow.release(); row_orig.release();
+    srow.release();
+    if (!keep_row_ids) row_orig.release();      // (a resampling handle's words remember their file rows: emit_words_kernel)
     if (M == 0) { GBRS_HIP_CHECK(hipStreamSynchronize(s)); return GBRS_OK; }
     stg.mark("6 long rows");
     // 7. tiles
@@ -1567,16 +1573,21 @@ int build_tile_layout(TileLayout &out, uint64_t R, uint32_t L_in, uint32_t H, ui
         GBRS_TRY(out.word_weight.alloc((size_t)NB * 64));
         GBRS_HIP_CHECK(hipMemsetAsync(out.word_weight.p, 0, out.word_weight.bytes(), s));
     }
+    if (keep_row_ids) {
+        GBRS_TRY(out.word_row.alloc((size_t)NB * 64));
+        GBRS_HIP_CHECK(hipMemsetAsync(out.word_row.p, 0xFF, out.word_row.bytes(), s));      // padding cells: no row
+    }
     hipLaunchKernelGGL(emit_words_kernel, dim3(grid_for(M)), dim3(256), 0, s, M, H, tincl.p, out.tiles.p, out.dict.p,
                        hrow.p, rowstart.p, ploc.p, pmask.p, rowpad.p, out.words.p,
                        out.weighted ? out.row_weight.p : (const double *)nullptr,
-                       out.weighted ? out.word_weight.p : (double *)nullptr);
+                       out.weighted ? out.word_weight.p : (double *)nullptr,
+                       keep_row_ids ? row_orig.p : (const uint32_t *)nullptr, keep_row_ids ? out.word_row.p : (uint32_t *)nullptr);
     if (streams && !out.weighted)
         hipLaunchKernelGGL(fill_one_word_cells_kernel, dim3(grid_for(T * 64)), dim3(256), 0, s, T, H, out.tiles.p, out.words.p);
     GBRS_HIP_CHECK(hipStreamSynchronize(s));
     dict_base.release(); batch_base.release(); nbatch.release(); n_one.release();
     rowpad.release(); tincl.release(); npm.release(); wordoff.release(); tile_row.release();
-    hrow.release(); rowstart.release(); ploc.release(); pmask.release();
+    hrow.release(); rowstart.release(); ploc.release(); pmask.release(); row_orig.release();
     out.row_weight.release();
     // Launch order of the tiles: the ones with the most batches first, so that the launch's last round - when most
     // of the chip has run out of tiles - is made of the short ones (tiles that end at the dictionary limit have

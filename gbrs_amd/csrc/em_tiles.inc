@@ -203,7 +203,7 @@ template <int HT, bool WEIGHTED, int HC, bool DET, int UB, bool ONEWORD = false,
 __device__ __forceinline__ void tile_batches(const uint32_t (&w)[UB], const double (&wt)[UB], int H, int PB, int lane,
                                              const double *__restrict__ s_theta, double *__restrict__ my_acc,
                                              LaneAcc<HC> &st, const int (&zlo)[32], const double2 *__restrict__ s_ftab,
-                                             uint32_t misfit_bits) {
+                                             uint32_t misfit_bits, uint32_t relax_zero_weight = 0u) {
     constexpr bool ZLO = estep_uses_zlo(UB);
     constexpr bool FTAB = estep_uses_ftab(UB, HT);
     constexpr bool TREG = estep_theta_regs(UB, HT, DET) && HC >= 8;
@@ -370,17 +370,23 @@ __device__ __forceinline__ void tile_batches(const uint32_t (&w)[UB], const doub
     for (int u = 0; u < UB; ++u) {
         const bool ok = den[u] > 0.0;
         double r;
+        // resampling handles (GBRS_EM_RESAMPLE, a wave-uniform kernel argument): a row whose weight is 0 takes no part, so a
+        // zero denominator of its own is no float error; its words still add 0.0 * (a finite reciprocal)
+        uint64_t counted = ~0ull;
+        if constexpr (WEIGHTED) {
+            if (relax_zero_weight) counted = wave_ballot(wt[u] != 0.0);
+        }
         if constexpr (GBRS_RECIP_GUARD_MAX && TREG) {
             // padding words (no haplotype bit: den 0) and rows without abundance (flagged here, the step's result is then
             // discarded) divide the smallest normal number instead - one v_max_f64 keeps 1/den finite, and a padding
             // word's 0.0 factors turn it into nothing; the real-word lanes are the ballot taken at the top of the batch.
             // (Only in the kernel that has registers to spare: the 16-haplotype form spills with it.)
-            if constexpr (!DIET) st.bad |= real_lanes0 & wave_ballot(!ok);      // (DIET: the tile epilogue finds it in the sums)
+            if constexpr (!DIET) st.bad |= real_lanes0 & wave_ballot(!ok) & counted;      // (DIET: the tile epilogue finds it in the sums)
             double dsafe;
             asm("v_max_f64 %0, %1, %2" : "=v"(dsafe) : "v"(den[u]), "s"(2.2250738585072014e-308));   // (scalar operand: no registers)
             r = fast_recip(dsafe);
         } else {
-            st.bad |= wave_ballot(mask[u] != 0) & wave_ballot(!ok);
+            st.bad |= wave_ballot(mask[u] != 0) & wave_ballot(!ok) & counted;
             // padding words (no haplotype bit: den 0) and rows without abundance (flagged above, the step's result
             // is then discarded) divide a value in [1, 2) instead: one select on the high half keeps 1/den
             // finite, and a padding word's 0.0 factors turn it into nothing
@@ -721,7 +727,7 @@ tile_estep_kernel(uint32_t Hrt, const TileHdr *__restrict__ tiles, const uint32_
                 ring[slot] = load_word(PD + slot);                     // refill PD batches ahead
                 if (WEIGHTED) wring[slot] = load_weight(PD + slot);
             }
-            if (b + tt * UB < b1) tile_batches<HT, WEIGHTED, HC, DET, UB, ONEWORD>(w, wt, H, PB, lane, s_theta, my_acc, st, zlo, s_ftab, misfit_bits);
+            if (b + tt * UB < b1) tile_batches<HT, WEIGHTED, HC, DET, UB, ONEWORD>(w, wt, H, PB, lane, s_theta, my_acc, st, zlo, s_ftab, misfit_bits, WEIGHTED ? sets.relax_zero_weight : 0u);
         }
         voff += PD * 256;
         asm volatile("" : "+v"(voff));      // keep it one register: the slots stay immediates of the loads
@@ -1012,7 +1018,7 @@ tile_estep_persistent_kernel(uint32_t Hrt, const TileHdr *__restrict__ tiles, co
                     ring[slot] = load_word(PD + slot);
                     if (WEIGHTED) wring[slot] = load_weight(PD + slot);
                 }
-                if (b + tt * UB < b1) tile_batches<HT, WEIGHTED, HC, false, UB, ONEWORD>(w, wt, H, PB, lane, s_theta, my_acc, st, zlo, s_ftab, misfit_bits);
+                if (b + tt * UB < b1) tile_batches<HT, WEIGHTED, HC, false, UB, ONEWORD>(w, wt, H, PB, lane, s_theta, my_acc, st, zlo, s_ftab, misfit_bits, WEIGHTED ? sets.relax_zero_weight : 0u);
             }
             voff += PD * 256;
             asm volatile("" : "+v"(voff));
@@ -1108,7 +1114,7 @@ __global__ void __launch_bounds__(256)
 long_rows_estep_kernel(uint64_t n_long, uint32_t H, const uint64_t *__restrict__ long_ptr,
                        const uint32_t *__restrict__ long_loc, const uint32_t *__restrict__ long_mask,
                        const double *__restrict__ long_weight, const double *__restrict__ theta,
-                       double *__restrict__ acc_extra, EmScalars *__restrict__ sc) {
+                       double *__restrict__ acc_extra, EmScalars *__restrict__ sc, uint32_t relax_zero_weight) {
     if (!ONES && sc->stop) return;
     const uint64_t row = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (row >= n_long) return;
@@ -1123,7 +1129,8 @@ long_rows_estep_kernel(uint64_t n_long, uint32_t H, const uint64_t *__restrict__
     }
     const double den = wave_sum_all(s);
     if (!(den > 0.0)) {
-        if (lane == 0) sc->float_error = 1;
+        // (resampling handles: a zero-weight row takes no part, its own zero denominator is no float error)
+        if (lane == 0 && !(relax_zero_weight && long_weight[row] == 0.0)) sc->float_error = 1;
         return;
     }
     const double v = long_weight[row] / den;
@@ -1143,7 +1150,7 @@ __global__ void __launch_bounds__(64)
 long_rows_estep_serial_kernel(uint64_t n_long, uint32_t H, const uint64_t *__restrict__ long_ptr,
                               const uint32_t *__restrict__ long_loc, const uint32_t *__restrict__ long_mask,
                               const double *__restrict__ long_weight, const double *__restrict__ theta,
-                              double *__restrict__ acc_extra, EmScalars *__restrict__ sc) {
+                              double *__restrict__ acc_extra, EmScalars *__restrict__ sc, uint32_t relax_zero_weight) {
     if (!ONES && sc->stop) return;
     const int lane = threadIdx.x & 63;
     for (uint64_t row = 0; row < n_long; ++row) {
@@ -1157,7 +1164,7 @@ long_rows_estep_serial_kernel(uint64_t n_long, uint32_t H, const uint64_t *__res
         }
         const double den = wave_sum_all(s);
         if (!(den > 0.0)) {
-            if (lane == 0) sc->float_error = 1;
+            if (lane == 0 && !(relax_zero_weight && long_weight[row] == 0.0)) sc->float_error = 1;
             continue;
         }
         const double v = long_weight[row] / den;

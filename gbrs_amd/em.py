@@ -21,8 +21,11 @@ class EMfactory:
 
     def __init__(self, alignments, device: int = 0, merge_identical_rows: bool = False,
                  csc_layout: bool = False, extra_flags: int = 0, deterministic: bool = False,
-                 one_shot: bool = False, grouped_models: bool = False, keep_posterior: bool = False):
+                 one_shot: bool = False, grouped_models: bool = False, keep_posterior: bool = False,
+                 resample: bool = False):
         self.probability = alignments
+        # GBRS_EM_DETERMINISTIC=1 in the environment: the bit-reproducible E-step for every handle on the tile layout
+        deterministic = deterministic or (os.getenv('GBRS_EM_DETERMINISTIC') == '1' and not csc_layout)
         self.grp_conv_mat = None          # kept for attribute parity; groups live in probability
         self.t2t_mat = None               # Models 1-3 (EMfactory.py:48-59): the device holds the groups instead
         self.target_lengths = None
@@ -32,7 +35,8 @@ class EMfactory:
                      (_lib.GBRS_EM_DETERMINISTIC if deterministic else 0) | \
                      (_lib.GBRS_EM_ONE_SHOT if one_shot else 0) | \
                      (_lib.GBRS_EM_GROUPED_MODELS if grouped_models else 0) | \
-                     (_lib.GBRS_EM_POSTERIOR if keep_posterior else 0) | int(extra_flags)   # tuning switches of gbrs_hip.h
+                     (_lib.GBRS_EM_POSTERIOR if keep_posterior else 0) | \
+                     (_lib.GBRS_EM_RESAMPLE if resample else 0) | int(extra_flags)   # tuning switches of gbrs_hip.h
         self._h = None
         self._theta = None                # host copy of allelic_expression (H x L)
         self._theta_dirty = False         # host copy edited, device not yet updated
@@ -158,6 +162,125 @@ class EMfactory:
         out = np.empty(nnz, dtype=np.float64)
         _lib.check(_lib.load().gbrs_em_posterior(self._h, hid, _lib.ptr(out), nnz))
         return out
+
+    # ------------------------------------------------------------------ bootstrap replicates (extension)
+    def resample(self, seed: int, replicate: int) -> None:
+        """Draws the row weights of bootstrap replicate `replicate` on the device (Poisson(count[r]) per row, a function
+        of (seed, replicate, row id, count) alone) and installs them on the handle; replicate=_lib.GBRS_RESAMPLE_BASE puts
+        the base weights back.  Needs resample=True.  reprepare() and run() come next."""
+        self._require()
+        _lib.check(_lib.load().gbrs_em_resample(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(replicate) & 0xFFFFFFFF))
+        self._theta = None
+        self._theta_dirty = False
+
+    def weights(self) -> np.ndarray:
+        """float64[R]: the current row weights of a resampling handle, in file row order."""
+        self._require()
+        out = np.empty(self.probability.shape[2], dtype=np.float64)
+        _lib.check(_lib.load().gbrs_em_weights(self._h, _lib.ptr(out)))
+        return out
+
+    def reprepare(self, pseudocount: float = 0.0) -> None:
+        """prepare()'s starting point again on the handle as it stands (after resample()), without rebuilding it."""
+        self._require()
+        _lib.check(_lib.load().gbrs_em_prepare(self._h, float(pseudocount)))
+        self._theta = None
+        self._theta_dirty = False
+
+    def bootstrap_begin(self) -> None:
+        """Clears the replicate statistics on the device; gene level when the alignments carry groups."""
+        self._require()
+        apm = self.probability
+        if apm.num_groups:
+            gptr, mem = apm.group_csr()
+            _lib.check(_lib.load().gbrs_em_bootstrap_begin(self._h, int(apm.num_groups), _lib.ptr(gptr), _lib.ptr(mem)))
+        else:
+            _lib.check(_lib.load().gbrs_em_bootstrap_begin(self._h, 0, None, None))
+
+    def bootstrap_add(self, keep: bool = False):
+        """Folds the handle's current result into the statistics as one more replicate.  keep: returns this replicate's
+        values as they were folded in, {'tpm', 'expected_read_counts'} (H x L) and with groups {'gene_tpm',
+        'gene_expected_read_counts'} (H x G)."""
+        self._require()
+        self._push()
+        apm = self.probability
+        L, H, R = apm.shape
+        G = int(apm.num_groups or 0)
+        out = {}
+        if keep:
+            out['tpm'] = np.empty((H, L))
+            out['expected_read_counts'] = np.empty((H, L))
+            if G:
+                out['gene_tpm'] = np.empty((H, G))
+                out['gene_expected_read_counts'] = np.empty((H, G))
+        _lib.check(_lib.load().gbrs_em_bootstrap_add(self._h, _lib.ptr(out.get('tpm')), _lib.ptr(out.get('expected_read_counts')),
+                                                     _lib.ptr(out.get('gene_tpm')), _lib.ptr(out.get('gene_expected_read_counts'))))
+        return out if keep else None
+
+    def bootstrap_get(self, grp_wise: bool = False) -> dict:
+        """Means and standard deviations (B - 1 in the denominator) over the replicates added so far: tpm_mean, tpm_sd,
+        count_mean, count_sd (H x n), tpm_total_mean, tpm_total_sd, count_total_mean, count_total_sd (n), num_replicates."""
+        self._require()
+        apm = self.probability
+        H = apm.num_haplotypes
+        n = int(apm.num_groups) if grp_wise else apm.num_loci
+        if grp_wise and not n:
+            raise RuntimeError('No group information is available.')
+        res = {k: np.empty((H, n)) for k in ('tpm_mean', 'tpm_sd', 'count_mean', 'count_sd')}
+        res.update({k: np.empty(n) for k in ('tpm_total_mean', 'tpm_total_sd', 'count_total_mean', 'count_total_sd')})
+        nrep = C.c_uint32(0)
+        _lib.check(_lib.load().gbrs_em_bootstrap_get(
+            self._h, 1 if grp_wise else 0, C.byref(nrep), _lib.ptr(res['tpm_mean']), _lib.ptr(res['tpm_sd']),
+            _lib.ptr(res['count_mean']), _lib.ptr(res['count_sd']), _lib.ptr(res['tpm_total_mean']),
+            _lib.ptr(res['tpm_total_sd']), _lib.ptr(res['count_total_mean']), _lib.ptr(res['count_total_sd'])))
+        res['num_replicates'] = int(nrep.value)
+        return res
+
+    def bootstrap(self, model: int, replicates: int, seed: int = 0, pseudocount: float = 0.0, tol: float = 0.001,
+                  max_iters: int = 999, keep: bool = False) -> dict:
+        """`replicates` bootstrap refits: resample -> prepare -> run -> accumulate for b = 0 .. replicates - 1, everything on
+        the device.  Returns {'isoforms': statistics, 'genes': statistics (with groups), 'num_iters': int32[B]} and, with
+        keep, 'tpm' / 'expected_read_counts' (B x H x L) and 'gene_tpm' / 'gene_expected_read_counts' (B x H x G).  The
+        base weights are back on the handle when it returns."""
+        np.seterr(all='raise', under='ignore')
+        self._check_model(model)
+        self._require()
+        if not (self.flags & _lib.GBRS_EM_RESAMPLE):
+            raise RuntimeError('bootstrap() needs an EMfactory built with resample=True.')
+        B = int(replicates)
+        if B < 1:
+            raise RuntimeError('The number of bootstrap replicates must be positive.')
+        self._ready_for_resampling(model)
+        lib = _lib.load()
+        self.bootstrap_begin()
+        num_iters = np.zeros(B, dtype=np.int32)
+        kept = {}
+        n_it = C.c_int(0)
+        try:
+            for b in range(B):
+                self.resample(seed, b)
+                self.reprepare(pseudocount)
+                _lib.check(lib.gbrs_em_run(self._h, int(model), float(tol), int(max_iters), C.byref(n_it), None, 0, None))
+                num_iters[b] = n_it.value
+                vals = self.bootstrap_add(keep=keep)
+                if keep:
+                    for k, v in vals.items():
+                        kept.setdefault(k, []).append(v)
+        finally:
+            self.resample(seed, _lib.GBRS_RESAMPLE_BASE)
+        self.num_iters = int(num_iters[-1])
+        res = {'isoforms': self.bootstrap_get(False), 'num_iters': num_iters}
+        if self.probability.num_groups:
+            res['genes'] = self.bootstrap_get(True)
+        for k, v in kept.items():
+            res[k] = np.stack(v)
+        return res
+
+    def _ready_for_resampling(self, model):
+        if model != 4 and not (self.flags & _lib.GBRS_EM_GROUPED_MODELS):
+            self.flags |= _lib.GBRS_EM_GROUPED_MODELS
+            self.close()
+            self._create()
 
     def _group_sums(self, which):
         apm = self.probability

@@ -239,14 +239,18 @@ def quantify(alignment_file: str, group_file: str = None, length_file: str = Non
              report_alignment_counts: bool = False, report_posterior: bool = False,
              device: int = 0, merge_identical_rows: bool = False, stage_times: dict = None,
              one_shot: bool = False, alignment=None, target_lengths=None,
-             posterior_values: bool = False) -> None:
+             posterior_values: bool = False, bootstrap: int = None, bootstrap_seed: int = 0,
+             keep_replicates: bool = False) -> None:
     """Quantify allele-specific expression from an EMASE alignment file.  `stage_times` (optional
     dict) receives the wall-clock seconds of the stages: load, mask, em_setup, em_run, reports,
     alignment_counts.  `alignment` / `target_lengths` (extension, gbrs_amd.worker): the file's contents as
     load_alignment() and read_length_file() return them, when a resident process has them already - the
     multiway and the diploid pass of one sample read the same file.  `posterior_values` (extension, implies
     report_posterior): `<outbase>.posterior.h5` carries the read-level posteriors of the last E-step in /h*/data
-    instead of the structure alone."""
+    instead of the structure alone.  `bootstrap` (extension): after the ordinary run and its reports, B bootstrap
+    refits on device-resampled reads (run_bootstrap) leave `<outbase>.isoforms.bootstrap.npz` and, with a group file,
+    `<outbase>.genes.bootstrap.npz`."""
+    check_bootstrap_args(bootstrap, merge_identical_rows)
     if posterior_values and merge_identical_rows:
         raise RuntimeError('--posterior-values is not available with --merge-identical-rows: the merged rows are not '
                            'the rows of the posterior file')
@@ -268,7 +272,8 @@ def quantify(alignment_file: str, group_file: str = None, length_file: str = Non
         logger.info(f'{label}: {value}')
 
     from . import _lib
-    _lib.warm_up_device_async(device)      # HIP start-up overlaps with reading the files
+    if bootstrap is None:                  # (--bootstrap refuses a file with stored values before it opens a device)
+        _lib.warm_up_device_async(device)  # HIP start-up overlaps with reading the files
     t0 = clock()
     logger.info(f'Loading EMASE file: {alignment_file}')
     # the length table only needs the names, which an HDF5 file yields before its index arrays are decoded: it is
@@ -287,6 +292,11 @@ def quantify(alignment_file: str, group_file: str = None, length_file: str = Non
     else:
         aln_mat = load_alignment(alignment_file, grpfile=group_file, on_names=names_known)
     marks['load'] = clock() - t0
+    if bootstrap is not None:
+        if aln_mat.values is not None:
+            raise RuntimeError('--bootstrap is not available for a file with stored alignment values: they fix the '
+                               'starting point of one fit, not of a resampled one')
+        _lib.warm_up_device_async(device)
 
     t0 = clock()
     gene_notes = isoform_notes = None
@@ -342,4 +352,63 @@ def quantify(alignment_file: str, group_file: str = None, length_file: str = Non
                 logger.info(f'Generating {level} Alignment Counts: {path}')
                 write_counts(fresh, path, grp_wise=grp_wise, device=device, counter=counter)
         marks['alignment_counts'] = clock() - t0
+
+    if bootstrap is not None:
+        t0 = clock()
+        run_bootstrap(aln_mat, em.target_lengths, outbase, group_file is not None, int(bootstrap), int(bootstrap_seed),
+                      bool(keep_replicates), multiread_model, pseudocount, tolerance, max_iters, device)
+        marks['bootstrap'] = clock() - t0
     logger.debug('Done')
+
+
+def check_bootstrap_args(bootstrap, merge_identical_rows=False, gpus=None):
+    """The combinations `--bootstrap` refuses, before any file is read or device opened."""
+    if bootstrap is None:
+        return
+    if int(bootstrap) < 2:
+        raise RuntimeError(f'--bootstrap needs at least 2 replicates, got {bootstrap}')
+    if merge_identical_rows:
+        raise RuntimeError('--bootstrap is not available with --merge-identical-rows: the reads are resampled, and a '
+                           'merged row is no read')
+    if gpus is not None:
+        raise RuntimeError('--gpus: --bootstrap is not available on the sharded path')
+
+
+BOOTSTRAP_STATISTICS = ('tpm_mean', 'tpm_sd', 'count_mean', 'count_sd', 'tpm_total_mean', 'tpm_total_sd',
+                        'count_total_mean', 'count_total_sd')
+
+
+def run_bootstrap(aln_mat, target_lengths, outbase, with_groups, replicates, seed, keep_replicates, multiread_model,
+                  pseudocount, tolerance, max_iters, device=0):
+    """B bootstrap replicates of the quantification on a resampling handle built like the command's own (same `-G`
+    mask, lengths and groups): replicate b refits the file in which every read occurs Poisson(count) times, drawn on
+    the device from (seed, b, read id).  Writes `<outbase>.isoforms.bootstrap.npz` and, with groups,
+    `<outbase>.genes.bootstrap.npz`: names, haplotypes, num_replicates, seed, multiread_model, num_iters, the means
+    and standard deviations (B - 1) of TPM and expected read counts per (haplotype, name) and of their totals per
+    name, and with keep_replicates `tpm` and `expected_read_counts` of every replicate (B x H x n)."""
+    logger.info(f'Running {replicates} bootstrap replicates (seed {seed})')
+    em = EMfactory(aln_mat, device=device, resample=True, grouped_models=multiread_model != 4)
+    try:
+        if target_lengths is not None:
+            em.set_target_lengths(target_lengths)
+        em.prepare(pseudocount=pseudocount)
+        res = em.bootstrap(multiread_model, replicates, seed=seed, pseudocount=pseudocount, tol=tolerance,
+                           max_iters=max_iters, keep=keep_replicates)
+    finally:
+        em.close()
+    levels = [('isoforms', aln_mat.lname, 'isoforms', 'tpm', 'expected_read_counts')]
+    if with_groups and 'genes' in res:
+        levels.append(('genes', aln_mat.gname, 'genes', 'gene_tpm', 'gene_expected_read_counts'))
+    for label, names, key, tpm_key, cnt_key in levels:
+        path = f'{outbase}.{label}.bootstrap.npz'
+        logger.info(f'Generating {label} bootstrap statistics: {path}')
+        out = dict(names=np.asarray(names), haplotypes=np.asarray(aln_mat.hname), num_replicates=np.int64(replicates),
+                   seed=np.uint64(seed & 0xFFFFFFFFFFFFFFFF), multiread_model=np.int64(multiread_model),
+                   num_iters=res['num_iters'])
+        for k in BOOTSTRAP_STATISTICS:
+            out[k] = res[key][k]
+        if keep_replicates:
+            out['tpm'] = res[tpm_key]
+            out['expected_read_counts'] = res[cnt_key]
+        with open(path, 'wb') as fh:
+            np.savez(fh, **out)

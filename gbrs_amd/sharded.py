@@ -47,6 +47,8 @@ def check_args(args):
         raise RuntimeError('--gpus: -w/--report-posterior is not available on the sharded path')
     if args.merge_identical_rows:
         raise RuntimeError('--gpus: --merge-identical-rows is not available on the sharded path')
+    if getattr(args, 'bootstrap', None) is not None:
+        raise RuntimeError('--gpus: --bootstrap is not available on the sharded path (the replicates run on one GPU)')
     try:
         devices = device_list(args)
     except ValueError:

@@ -116,6 +116,16 @@ typedef struct gbrs_em gbrs_em_t;
  * second H*L buffer before every EM step: the theta that step's E-step used.  Without the flag a handle allocates
  * and launches exactly what it did before the flag existed. */
 #define GBRS_EM_POSTERIOR 2048u
+/* Bootstrap replicates (gbrs_em_resample).  The handle is built as a weighted one - base weights of `count`, or ones -
+ * and keeps what it needs to write other row weights over them in place: the base count as integers and the file row
+ * behind every word of the tiles and every long row.  GBRS_ERR_UNSUPPORTED with GBRS_EM_MERGE_IDENTICAL_ROWS or
+ * GBRS_EM_SIDE_BY_SIDE; GBRS_ERR_INVALID for a count that is negative, not an integer or >= 2^32;
+ * gbrs_em_set_initial_values on such a handle is GBRS_ERR_UNSUPPORTED.  On such a handle a row whose weight is 0 takes no
+ * part: it adds nothing, and a zero denominator of its own is no float error.  Without the flag a handle allocates and
+ * launches exactly what it did before the flag existed. */
+#define GBRS_EM_RESAMPLE 4096u
+/* `replicate` of gbrs_em_resample that puts the base weights back */
+#define GBRS_RESAMPLE_BASE 0xFFFFFFFFu
 
 /*
  * Replaces: AlignmentPropertyMatrix(h5file=...) as consumed by EMfactory.__init__
@@ -225,6 +235,39 @@ int gbrs_em_get(gbrs_em_t *em, double *theta, double *expected_counts);
  * GBRS_ERR_STATE without the flag or when no step has run since prepare; GBRS_ERR_INVALID for hap >= num_haps or
  * out_len != nnz_hap. */
 int gbrs_em_posterior(gbrs_em_t *em, uint32_t hap, double *out, uint64_t out_len);
+
+/* Bootstrap replicates (handle created with GBRS_EM_RESAMPLE, else GBRS_ERR_STATE).
+ *   resample  draws the weights of replicate `replicate` on the device and installs them in every structure the handle
+ *             steps on (tile words, long rows, the per-row array of the CSC, models 1-3 and posterior kernels - prepare
+ *             uses the same).  Row r gets  w = sum_{k < c_r} P(u_k):  c_r = count[r] (1 without a count vector), u_k word
+ *             k mod 4 of Philox4x32-10 with counter (r & 0xFFFFFFFF, r >> 32, k div 4, replicate) and key
+ *             (seed & 0xFFFFFFFF, seed >> 32), P(u) = the number of j in 0..12 with u >= floor(2^32 sum_{i<=j} e^-1/i!):
+ *             Poisson(c_r) by inversion, an integer, a function of (seed, replicate, r, c_r) alone - the same on every
+ *             layout and under every `-G` mask.  A replicate is the quantification of the file in which row r occurs w
+ *             times.  replicate == GBRS_RESAMPLE_BASE restores the base weights exactly.  The caller then runs
+ *             gbrs_em_prepare and gbrs_em_run as on any handle.
+ *   weights   the current weights in file row order, double[R] (rows a `-G` mask emptied included).
+ *   resample_info   device bytes the flag added to the handle, rows whose count is above the cut (a workgroup each in
+ *             the draw) and the cut (any pointer may be NULL). */
+int gbrs_em_resample(gbrs_em_t *em, uint64_t seed, uint32_t replicate);
+int gbrs_em_weights(gbrs_em_t *em, double *out);
+int gbrs_em_resample_info(gbrs_em_t *em, uint64_t *extra_device_bytes, uint64_t *num_big_rows, uint32_t *cut);
+
+/* Replicate statistics on the device (any handle).
+ *   begin  clears them; groups as for gbrs_em_group_sums, num_groups = 0: isoform level only.
+ *   add    folds the handle's current result in as one more replicate: TPM = theta * (1e6 / sum of theta), the expected
+ *          read counts of the last E-step, their per-locus totals over the haplotypes, and with groups the same at gene
+ *          level (the members' values added in member order).  Running mean and sum of squared deviations (Welford),
+ *          updated in replicate order; every sum has a fixed order, so the statistics are bit-reproducible for a given
+ *          sequence of thetas.  tpm, counts (H x L), gene_tpm, gene_counts (H x G), any nullable: the values of this
+ *          replicate as they were folded in.
+ *   get    level 0 isoforms / 1 genes (n = L / G): means and standard deviations with B - 1 in the denominator,
+ *          (H x n) and, for the totals, n; any pointer may be NULL. */
+int gbrs_em_bootstrap_begin(gbrs_em_t *em, int64_t num_groups, const int64_t *group_ptr, const int64_t *members);
+int gbrs_em_bootstrap_add(gbrs_em_t *em, double *tpm, double *counts, double *gene_tpm, double *gene_counts);
+int gbrs_em_bootstrap_get(gbrs_em_t *em, int level, uint32_t *num_replicates, double *tpm_mean, double *tpm_sd,
+                          double *count_mean, double *count_sd, double *tpm_total_mean, double *tpm_total_sd,
+                          double *count_total_mean, double *count_total_sd);
 
 /* Overwrite theta (H x L), e.g. to resume from a checkpoint. */
 int gbrs_em_set_theta(gbrs_em_t *em, const double *theta);

@@ -1,7 +1,10 @@
 """`gbrs bam2emase` on the MI355X path: same arguments, log lines and output file as
 emase/emase_utils.py:26-70 + emase/AlignmentMatrixFactory.py:26-142, without pysam, PyTables or temporary
 files.  The BAM file is inflated and parsed by the library's host reader (gbrs_bam_open / bamio.hip); ranking
-the read names and building the per-haplotype CSC matrices runs in HIP (gbrs_bam_convert / bam.hip)."""
+the read names and building the per-haplotype CSC matrices runs in HIP (gbrs_bam_convert / bam.hip).
+
+`gbrs bam2ec` (extension) goes from one or more BAM files straight to the file `gbrs compress` writes: the
+read-level matrices stay on the device and the read names are never gathered (gbrs_ecset_* / bam.hip)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -136,6 +139,80 @@ def bam_to_matrix(alignment_file, haplotypes, loci, delim='_', device=0, stage_t
         raise RuntimeError(f'{alignment_file} holds no alignment records.')
     return AlignmentPropertyMatrix(shape=(len(loci), len(hname), len(rname)), indptr=ip, indices=ix,
                                    haplotype_names=hname, locus_names=loci, read_names=rname)
+
+
+def bam_to_classes(alignment_files, haplotypes, loci, delim='_', device=0, stage_times=None, threads=0):
+    """BAM file(s) -> AlignmentPropertyMatrix of equivalence classes with counts: what bam_to_matrix on every file
+    followed by compress over the files' reads, one file after the other, gives (the same name in two files is
+    two reads).  Only the class matrix leaves the device.  stage_times gets read / rank / classes, summed over the
+    files."""
+    if len(loci) >= 1 << 32:
+        raise RuntimeError('2^32 or more loci do not fit uint32 index arrays.')
+    lib = _lib.load()
+    hname = list(haplotypes) if len(haplotypes) > 0 else ['h0']
+    L, H = len(loci), len(hname)
+    total = np.zeros(3, dtype=np.float64)
+    e = C.c_void_p()
+    _lib.check(lib.gbrs_ecset_create(L, H, device, C.byref(e)))
+    try:
+        for path in alignment_files:
+            with BamFile(path, threads=threads) as bam:
+                _, hap, loc = bam.reference_map(haplotypes, loci, delim)
+                _lib.check(lib.gbrs_bam_set_reference_map(bam._h, len(hap), _lib.ptr(hap), _lib.ptr(loc), H, L))
+                n, secs = C.c_uint64(0), np.zeros(3, dtype=np.float64)
+                _lib.check(lib.gbrs_ecset_add_bam(e, bam._h, C.byref(n), _lib.ptr(secs)))
+                total += secs
+            if n.value == 0:
+                raise RuntimeError(f'{path} holds no alignment records.')
+        R, G = C.c_uint64(0), C.c_uint64(0)
+        nnz = np.zeros(H, dtype=np.uint64)
+        _lib.check(lib.gbrs_ecset_sizes(e, C.byref(R), C.byref(G), _lib.ptr(nnz)))
+        ip = [np.zeros(L + 1, dtype=np.uint32) for _ in range(H)]
+        ix = [np.zeros(int(nnz[k]), dtype=np.uint32) for k in range(H)]
+        count = np.zeros(int(G.value), dtype=np.float64)
+        _lib.check(lib.gbrs_ecset_get(e, _lib.ptr_table(ip), _lib.ptr_table(ix), _lib.ptr(count) if G.value else None))
+    finally:
+        lib.gbrs_ecset_destroy(e)
+        if stage_times is not None:
+            stage_times['read'], stage_times['rank'], stage_times['classes'] = (float(x) for x in total)
+    return AlignmentPropertyMatrix(shape=(L, H, max(int(G.value), 1)), indptr=ip, indices=ix,
+                                   count=count if G.value else np.zeros(1), haplotype_names=hname, locus_names=loci)
+
+
+def bam2ec(alignment_files, haplotypes, locusid_file, output_file, delim='_', comp_lib='zlib', index_dtype='uint32',
+           device=0, stage_times=None):
+    """BAM file(s) -> the equivalence-class file of `gbrs compress` in one pass (extension): member for member what
+    bam2emase() on every file and compress() over the results write, with the rules of bam2emase() per file and
+    the files' reads one after the other.  No intermediate file, no read names, no CPU fallback."""
+    for x in alignment_files:
+        logger.info(f'BAM File: {x}')
+    logger.info(f'Locus ID File: {locusid_file}')
+    logger.info(f'Output File: {output_file}')
+    logger.info(f'Haplotypes: {haplotypes}')
+    logger.info(f'Delimiter: {delim}')
+    logger.info(f'Index dtype: {index_dtype}')
+    logger.info(f'Compression Library: {comp_lib}')
+    if np.dtype(index_dtype) != np.uint32:
+        raise RuntimeError(f'--index-dtype {index_dtype}: the index arrays of this implementation are uint32.')
+    if len(alignment_files) == 0:
+        raise RuntimeError('No BAM file was given.')
+    init = _lib.warm_up_device_async(device)          # the runtime starts while the first file is inflated
+    logger.info(f'Parsing Locus ID File: {locusid_file}')
+    loci = get_names(locusid_file)
+    for x in alignment_files:
+        logger.info(f'Parsing BAM File: {x}')
+    ec = bam_to_classes(list(alignment_files), list(haplotypes), loci, delim=delim, device=device,
+                        stage_times=stage_times)
+    init.join()
+    logger.debug(f'Number Loci: {ec.num_loci}')
+    logger.debug(f'Number Haplotypes: {ec.num_haplotypes}')
+    logger.debug(f'Number ECs: {ec.num_reads}')
+    logger.info(f'Saving EMASE Formatted File: {output_file}')
+    t0 = time.time()
+    ec.save(output_file, complib=comp_lib)
+    if stage_times is not None:
+        stage_times['write'] = time.time() - t0
+    logger.info('Done')
 
 
 def bam2emase(alignment_file, haplotypes, locusid_file, output_file='alignments.transcriptome.h5', delim='_',

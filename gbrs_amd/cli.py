@@ -27,6 +27,11 @@ def _existing(path):
     return os.path.realpath(path)
 
 
+def _existing_or_list(path):
+    """One file is checked here, like every other input; a comma list is split and checked by the command."""
+    return path if ',' in path else _existing(path)
+
+
 def build_parser():
     ap = argparse.ArgumentParser(prog='gbrs', description='GBRS numeric core on AMD MI355X')
     sub = ap.add_subparsers(dest='command', required=True)
@@ -107,6 +112,20 @@ def build_parser():
     b2.add_argument('--data-dtype', default='uint8')
     b2.add_argument('-v', '--verbose', action='count', default=0)
     b2.add_argument('--device', type=int, default=0, help='HIP device ordinal (extension)')
+    be = sub.add_parser('bam2ec', add_help=False,
+                        help='(extension) convert BAM file(s) to equivalence classes: bam2emase + compress in one pass')
+    be.add_argument('--help', action='help', help='show this help message and exit')
+    be.add_argument('-i', '--alignment-file', dest='alignment_files', action='append', required=True, type=_existing_or_list,
+                    help='BAM file, one per -i option (the lanes of a sample), or a shortcut -i a.bam,b.bam')
+    be.add_argument('-h', '--haplotype-char', dest='haplotypes', action='append', default=None,
+                    help='haplotype, either one per -h option, i.e. -h A -h B -h C, or a shortcut -h A,B,C')
+    be.add_argument('-m', '--locus-ids', dest='locusid_file', required=True, type=_existing)
+    be.add_argument('-o', '--output', dest='output_file', required=True)
+    be.add_argument('-d', '--delim', default='_')
+    be.add_argument('-c', '--comp-lib', default='zlib')
+    be.add_argument('--index-dtype', default='uint32')
+    be.add_argument('-v', '--verbose', action='count', default=0)
+    be.add_argument('--device', type=int, default=0, help='HIP device ordinal (extension)')
     # structure edits of an EMASE file (emase/commands.py:75-257, gbrs/commands.py:342-366; gbrs_amd/matops.py)
     ca = sub.add_parser('get-common-alignments', help='get the common alignments')
     ca.add_argument('-i', '--emase-file', dest='emase_files', action='append', required=True)
@@ -222,6 +241,16 @@ def main(argv=None) -> int:
             bam2emase(alignment_file=args.alignment_file, haplotypes=haplotypes, locusid_file=args.locusid_file,
                       delim=args.delim, index_dtype=args.index_dtype, data_dtype=args.data_dtype, device=args.device,
                       stage_times=stages, **kw)
+        elif args.command == 'bam2ec':
+            from .bam2emase import bam2ec
+            files = [f for x in args.alignment_files for f in x.split(',')]
+            for f in files:
+                if not os.path.isfile(f):
+                    raise FileNotFoundError(f"File '{f}' does not exist.")
+            haplotypes = [h for x in (args.haplotypes or []) for h in x.split(',')]
+            bam2ec(alignment_files=[os.path.realpath(f) for f in files], haplotypes=haplotypes,
+                   locusid_file=args.locusid_file, output_file=args.output_file, delim=args.delim,
+                   comp_lib=args.comp_lib, index_dtype=args.index_dtype, device=args.device, stage_times=stages)
         elif args.command in ('get-common-alignments', 'combine'):
             from . import matops
             files = [f for x in args.emase_files for f in x.split(',')]

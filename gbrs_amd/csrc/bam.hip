@@ -1,4 +1,6 @@
-// Device stages of `gbrs bam2emase`: rank the read names, build the per-haplotype CSC incidence matrices.
+// Device stages of `gbrs bam2emase`: rank the read names, build the per-haplotype CSC incidence matrices; and of
+// `gbrs bam2ec` (gbrs_ecset_*, at the end of the file): the same two stages without the names, then the equivalence
+// classes of the file from the arrays where they lie, merged into the classes of the files before it.
 // rocPRIM provides the radix sorts and scans (prim.h); the kernels around them are written here.
 //
 // Names.  The host pass (bamio.hip) hands over C candidate names (every record's name, except that a record
@@ -16,6 +18,7 @@
 // through the per-reference table; a sort, a neighbour compare and a scan leave each (haplotype, locus, read)
 // once, in CSC order: the low words are `indices`, and the positions where the column changes are `indptr`.
 #include "bamio.h"
+#include "em_layout.h"
 #include "prim.h"
 
 #include <algorithm>
@@ -205,8 +208,10 @@ double seconds_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 
-// candidates -> rank[candidate] (device), rname (device), R
-int rank_names(gbrs_bam *b, Scratch &sc, DevBuf<uint32_t> &rank, DevResult &res, hipStream_t s) {
+// candidates -> rank[candidate] (device), R and, when `rname` is given, the sorted distinct names (device).
+// rname == nullptr (gbrs_ecset_add_bam): the pass ends with scatter_rank_kernel - no name array is allocated,
+// gathered or copied
+int rank_names(gbrs_bam *b, Scratch &sc, DevBuf<uint32_t> &rank, DevBuf<unsigned char> *rname, hipStream_t s) {
     const uint64_t C = b->cand_off.size() - 1;
     const uint32_t width = std::max<uint32_t>(b->max_name, 1), W = (width + 7) / 8;
     if (W > MAX_PLANES) return fail(GBRS_ERR_INVALID, "a read name of %u bytes (the format allows 254)", b->max_name);
@@ -267,11 +272,13 @@ int rank_names(gbrs_bam *b, Scratch &sc, DevBuf<uint32_t> &rank, DevResult &res,
     GBRS_TRY(rank.alloc(C));
     hipLaunchKernelGGL(scatter_rank_kernel, dim3(capped_grid(C)), dim3(256), 0, s, C, perm.p, id.p, rank.p);
     GBRS_HIP_CHECK(hipGetLastError());
-    GBRS_TRY(res.rname.alloc(R * width));
-    GBRS_HIP_CHECK(hipMemsetAsync(res.rname.p, 0, R * width, s));
-    hipLaunchKernelGGL(gather_rname_kernel, dim3(capped_grid(C * W)), dim3(256), 0, s, C, W, width, R, planes.p, perm.p, id.p,
-                       flag.p, res.rname.p);
-    GBRS_HIP_CHECK(hipGetLastError());
+    if (rname) {
+        GBRS_TRY(rname->alloc(R * width));
+        GBRS_HIP_CHECK(hipMemsetAsync(rname->p, 0, R * width, s));
+        hipLaunchKernelGGL(gather_rname_kernel, dim3(capped_grid(C * W)), dim3(256), 0, s, C, W, width, R, planes.p, perm.p, id.p,
+                           flag.p, rname->p);
+        GBRS_HIP_CHECK(hipGetLastError());
+    }
     GBRS_HIP_CHECK(hipStreamSynchronize(s));
     b->num_reads = R;
     b->name_width = width;
@@ -298,7 +305,10 @@ int report_bad_record(gbrs_bam *b, uint64_t j) {
     }
 }
 
-int build_matrix(gbrs_bam *b, Scratch &sc, const DevBuf<uint32_t> &rank, DevResult &res, hipStream_t s) {
+// idx / col_ptr: the entries' read ids in CSC order and the H * L + 1 column offsets, both on the device (left
+// unallocated when no record is kept); b->col_ptr receives the offsets on the host
+int build_matrix(gbrs_bam *b, Scratch &sc, const DevBuf<uint32_t> &rank, DevBuf<uint32_t> &idx, DevBuf<uint64_t> &col_ptr,
+                 hipStream_t s) {
     const uint64_t N = b->recs.size(), C = b->cand_off.size() - 1, R = b->num_reads, n_ref = b->ref_names.size();
     const uint64_t ncols = (uint64_t)b->num_haps * b->num_loci;
     const unsigned rbits = bits_for(R - 1), cbits = bits_for(ncols - 1);
@@ -308,7 +318,7 @@ int build_matrix(gbrs_bam *b, Scratch &sc, const DevBuf<uint32_t> &rank, DevResu
     b->col_ptr.assign(ncols + 1, 0);
     if (N == 0) return GBRS_OK;
     DevBuf<Rec> recs;
-    DevBuf<uint64_t> refmap, kin, kout, col_ptr;
+    DevBuf<uint64_t> refmap, kin, kout;
     DevBuf<unsigned long long> first_bad;
     DevBuf<uint32_t> flag, pos;
     std::vector<uint64_t> h_map(std::max<uint64_t>(n_ref, 1), REF_UNUSABLE);
@@ -339,9 +349,9 @@ int build_matrix(gbrs_bam *b, Scratch &sc, const DevBuf<uint32_t> &rank, DevResu
     GBRS_TRY(exclusive_scan(sc, flag.p, pos.p, N, s));
     uint32_t n_unique = 0;
     GBRS_TRY(fetch_last_plus(pos.p, flag.p, N, n_unique, s));
-    GBRS_TRY(res.idx.alloc(n_unique));
+    GBRS_TRY(idx.alloc(n_unique));
     GBRS_TRY(col_ptr.alloc(ncols + 1));
-    hipLaunchKernelGGL(compact_kernel, dim3(capped_grid(N)), dim3(256), 0, s, N, kout.p, flag.p, pos.p, rbits, ncols, res.idx.p, col_ptr.p);
+    hipLaunchKernelGGL(compact_kernel, dim3(capped_grid(N)), dim3(256), 0, s, N, kout.p, flag.p, pos.p, rbits, ncols, idx.p, col_ptr.p);
     GBRS_HIP_CHECK(hipGetLastError());
     GBRS_HIP_CHECK(hipMemcpyAsync(b->col_ptr.data(), col_ptr.p, (ncols + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     GBRS_HIP_CHECK(hipStreamSynchronize(s));
@@ -349,8 +359,83 @@ int build_matrix(gbrs_bam *b, Scratch &sc, const DevBuf<uint32_t> &rank, DevResu
     return GBRS_OK;
 }
 
+// ---- gbrs_ecset: equivalence classes of several BAM files, merged on the device ---------------------------------
+// The set and a file's classes are both class matrices in CSC form (column c = h * L + l, class ids ascending inside
+// a column).  Stacking the file's classes below the set's - their ids raised by the set's class count - needs no
+// sort: every row of the addend comes after every row of the set, so column c of the stack is the set's column c
+// followed by the addend's.  out_ptr = a_ptr + b_ptr gives the columns' places.
+__global__ void __launch_bounds__(256)
+ecset_merge_ptr_kernel(uint64_t n_ptr, const uint64_t *__restrict__ a_ptr, const uint64_t *__restrict__ b_ptr,
+                       uint64_t *__restrict__ out_ptr) {
+    for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < n_ptr; c += (uint64_t)gridDim.x * blockDim.x)
+        out_ptr[c] = a_ptr[c] + b_ptr[c];
+}
+
+// One operand's entries to their places in the stack: entry k of column c moves up by the entries the OTHER operand
+// has before it - for the set (after = 0) the addend's columns before c, other_ptr[c]; for the addend (after = 1) the
+// set's columns up to and including c, other_ptr[c + 1].  A wavefront's entries are consecutive in every pass of the
+// loop (the stride is a multiple of 256), which is what entry_column needs; dst < n_out holds by construction
+// (k - own_ptr[c] < own_ptr[c + 1] - own_ptr[c]) and is checked because the offsets are read from memory.
+__global__ void __launch_bounds__(256)
+ecset_merge_copy_kernel(uint64_t n, uint32_t ncols, const uint64_t *__restrict__ own_ptr, const uint64_t *__restrict__ other_ptr,
+                        uint32_t after, const uint32_t *__restrict__ idx, uint32_t id_offset, uint64_t n_out,
+                        uint32_t *__restrict__ out) {
+    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t c = entry_column(own_ptr, ncols, k, n);
+        const uint64_t dst = k + other_ptr[c + after];
+        if (dst < n_out) out[dst] = idx[k] + id_offset;
+    }
+}
+
+// set := classes of (set's classes, then the addend's classes), weights = the two count vectors one after the other.
+// The set's classes are distinct rows, so in first-seen order each keeps its id; an addend class equal to one of them
+// adds its count there, the others follow in their own order - the first-occurrence order over the concatenated reads.
+int merge_classes(CompressResult &set, CompressResult &add, uint32_t L, uint32_t H, hipStream_t s) {
+    const uint64_t G1 = set.num_ecs, G2 = add.num_ecs, E1 = set.n_entries, E2 = add.n_entries, ncols = (uint64_t)H * L;
+    if (G1 + G2 > 0xFFFFFFFFull) return fail(GBRS_ERR_UNSUPPORTED, "more than 2^32 - 1 equivalence classes to merge");
+    DevBuf<uint32_t> idx;
+    DevBuf<uint64_t> ptr;
+    DevBuf<double> cnt;
+    GBRS_TRY(idx.alloc(E1 + E2));
+    GBRS_TRY(ptr.alloc(ncols + 1));
+    GBRS_TRY(cnt.alloc(G1 + G2));
+    hipLaunchKernelGGL(ecset_merge_ptr_kernel, dim3(capped_grid(ncols + 1)), dim3(256), 0, s, ncols + 1, set.col_ptr.p, add.col_ptr.p, ptr.p);
+    GBRS_HIP_CHECK(hipGetLastError());
+    if (E1) {
+        hipLaunchKernelGGL(ecset_merge_copy_kernel, dim3(capped_grid(E1)), dim3(256), 0, s, E1, (uint32_t)ncols, set.col_ptr.p,
+                           add.col_ptr.p, 0u, set.indices.p, 0u, E1 + E2, idx.p);
+        GBRS_HIP_CHECK(hipGetLastError());
+    }
+    if (E2) {
+        hipLaunchKernelGGL(ecset_merge_copy_kernel, dim3(capped_grid(E2)), dim3(256), 0, s, E2, (uint32_t)ncols, add.col_ptr.p,
+                           set.col_ptr.p, 1u, add.indices.p, (uint32_t)G1, E1 + E2, idx.p);
+        GBRS_HIP_CHECK(hipGetLastError());
+    }
+    GBRS_HIP_CHECK(hipMemcpyAsync(cnt.p, set.count.p, G1 * sizeof(double), hipMemcpyDeviceToDevice, s));
+    GBRS_HIP_CHECK(hipMemcpyAsync(cnt.p + G1, add.count.p, G2 * sizeof(double), hipMemcpyDeviceToDevice, s));
+    GBRS_HIP_CHECK(hipStreamSynchronize(s));
+    add.indices.release();
+    add.col_ptr.release();
+    add.count.release();
+    CompressResult merged;                       // the set stays as it is until the merge has succeeded
+    GBRS_TRY(compress_device(merged, G1 + G2, L, H, E1 + E2, idx.p, ptr.p, cnt.p, s));
+    set.num_ecs = merged.num_ecs;
+    set.n_entries = merged.n_entries;
+    set.col_ptr.swap(merged.col_ptr);
+    set.indices.swap(merged.indices);
+    set.count.swap(merged.count);
+    return GBRS_OK;
+}
+
 }  // namespace
 }  // namespace gbrs
+
+struct gbrs_ecset {
+    int device = 0;
+    uint32_t L = 0, H = 0;
+    uint64_t num_reads = 0;
+    gbrs::CompressResult res;                    // num_ecs == 0: no file has been added
+};
 
 extern "C" {
 
@@ -383,11 +468,12 @@ int gbrs_bam_convert(gbrs_bam_t *b, int device, uint64_t *num_reads, uint32_t *n
         hipStream_t s = nullptr;
         Scratch sc;
         DevBuf<uint32_t> rank;
+        DevBuf<uint64_t> col_ptr;
         t0 = std::chrono::steady_clock::now();
-        rc = rank_names(b, sc, rank, *res, s);
+        rc = rank_names(b, sc, rank, &res->rname, s);
         if (stage_seconds) stage_seconds[1] = seconds_since(t0);
         t0 = std::chrono::steady_clock::now();
-        if (rc == GBRS_OK) rc = build_matrix(b, sc, rank, *res, s);
+        if (rc == GBRS_OK) rc = build_matrix(b, sc, rank, res->idx, col_ptr, s);
         if (stage_seconds) stage_seconds[2] = seconds_since(t0);
     }
     bam_release_collected(b);
@@ -426,6 +512,127 @@ int gbrs_bam_get(gbrs_bam_t *b, uint32_t *const *indptr_out, uint32_t *const *in
     }
     if (rname_out && b->num_reads)
         GBRS_HIP_CHECK(hipMemcpy(rname_out, res->rname.p, b->num_reads * (uint64_t)b->name_width, hipMemcpyDeviceToHost));
+    return GBRS_OK;
+}
+
+int gbrs_ecset_create(uint32_t num_loci, uint32_t num_haps, int device, gbrs_ecset_t **out) {
+    using namespace gbrs;
+    if (!out) return fail(GBRS_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (num_haps < 1 || num_haps > 16 || num_loci < 1 || num_loci >= (1u << 27))
+        return fail(GBRS_ERR_INVALID, "compress needs 1 <= H <= 16 and 1 <= L < 2^27 loci");
+    GBRS_TRY(select_device(device));
+    gbrs_ecset *e = new gbrs_ecset();
+    e->device = device;
+    e->L = num_loci;
+    e->H = num_haps;
+    *out = e;
+    return GBRS_OK;
+}
+
+int gbrs_ecset_add_bam(gbrs_ecset_t *e, gbrs_bam_t *b, uint64_t *num_reads_of_file, double *stage_seconds) {
+    using namespace gbrs;
+    if (!e || !b || !num_reads_of_file) return fail(GBRS_ERR_INVALID, "bad argument");
+    if (!b->map_set) return fail(GBRS_ERR_STATE, "gbrs_bam_set_reference_map has not been called");
+    if (b->num_loci != e->L || b->num_haps != e->H)
+        return fail(GBRS_ERR_INVALID, "%s: the reference map has %u loci x %u haplotypes, the set %u x %u", b->path.c_str(),
+                    b->num_loci, b->num_haps, e->L, e->H);
+    GBRS_TRY(select_device(e->device));
+    if (b->dev && b->dev_free) b->dev_free(b->dev);      // (an earlier gbrs_bam_convert: the handle keeps nothing on the device)
+    b->dev = nullptr;
+    b->converted = false;
+    RoctxRange range("gbrs_ecset_add_bam");
+    *num_reads_of_file = 0;
+    if (stage_seconds) stage_seconds[0] = stage_seconds[1] = stage_seconds[2] = 0.0;
+    auto t0 = std::chrono::steady_clock::now();
+    GBRS_TRY(bam_collect(b));
+    if (stage_seconds) stage_seconds[0] = seconds_since(t0);
+    if (b->cand_off.size() < 2) {                        // no record at all: nothing to add
+        bam_release_collected(b);
+        return GBRS_OK;
+    }
+    hipStream_t s = nullptr;
+    const uint64_t ncols = (uint64_t)e->H * e->L;
+    CompressResult file;
+    int rc = GBRS_OK;
+    {
+        Scratch sc;
+        DevBuf<uint32_t> rank, idx;
+        DevBuf<uint64_t> col_ptr;
+        t0 = std::chrono::steady_clock::now();
+        rc = rank_names(b, sc, rank, nullptr, s);
+        if (stage_seconds) stage_seconds[1] = seconds_since(t0);
+        t0 = std::chrono::steady_clock::now();
+        if (rc == GBRS_OK) rc = build_matrix(b, sc, rank, idx, col_ptr, s);
+        bam_release_collected(b);
+        if (rc != GBRS_OK) return rc;
+        rank.release();
+        sc.buf.release();
+        if (!col_ptr.p) {                                // no kept record: every read is in the empty class
+            GBRS_TRY(col_ptr.alloc(ncols + 1));
+            GBRS_HIP_CHECK(hipMemsetAsync(col_ptr.p, 0, col_ptr.bytes(), s));
+        }
+        GBRS_TRY(compress_device(file, b->num_reads, e->L, e->H, idx.n, idx.p, col_ptr.p, nullptr, s));
+    }
+    if (e->res.num_ecs == 0) {
+        e->res.num_ecs = file.num_ecs;
+        e->res.n_entries = file.n_entries;
+        e->res.col_ptr.swap(file.col_ptr);
+        e->res.indices.swap(file.indices);
+        e->res.count.swap(file.count);
+    } else {
+        GBRS_TRY(merge_classes(e->res, file, e->L, e->H, s));
+    }
+    if (stage_seconds) stage_seconds[2] = seconds_since(t0);
+    e->num_reads += b->num_reads;
+    *num_reads_of_file = b->num_reads;
+    return GBRS_OK;
+}
+
+int gbrs_ecset_sizes(gbrs_ecset_t *e, uint64_t *num_reads, uint64_t *num_ecs, uint64_t *nnz_per_hap) {
+    using namespace gbrs;
+    if (!e || !num_reads || !num_ecs || !nnz_per_hap) return fail(GBRS_ERR_INVALID, "bad argument");
+    *num_reads = e->num_reads;
+    *num_ecs = e->res.num_ecs;
+    for (uint32_t h = 0; h < e->H; ++h) nnz_per_hap[h] = 0;
+    if (e->res.num_ecs == 0) return GBRS_OK;
+    GBRS_TRY(select_device(e->device));
+    const uint64_t L = e->L;
+    std::vector<uint64_t> cp((size_t)e->H * L + 1);
+    GBRS_HIP_CHECK(hipMemcpy(cp.data(), e->res.col_ptr.p, cp.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    for (uint32_t h = 0; h < e->H; ++h) nnz_per_hap[h] = cp[(h + 1) * L] - cp[h * L];
+    return GBRS_OK;
+}
+
+int gbrs_ecset_get(gbrs_ecset_t *e, uint32_t *const *indptr_out, uint32_t *const *indices_out, double *count_out) {
+    using namespace gbrs;
+    if (!e || !indptr_out || !indices_out) return fail(GBRS_ERR_INVALID, "bad argument");
+    const uint64_t L = e->L;
+    for (uint32_t h = 0; h < e->H; ++h)
+        if (!indptr_out[h]) return fail(GBRS_ERR_INVALID, "output buffer %u is NULL", h);
+    if (e->res.num_ecs == 0) {
+        for (uint32_t h = 0; h < e->H; ++h)
+            for (uint64_t l = 0; l <= L; ++l) indptr_out[h][l] = 0;
+        return GBRS_OK;
+    }
+    GBRS_TRY(select_device(e->device));
+    std::vector<uint64_t> cp((size_t)e->H * L + 1);
+    GBRS_HIP_CHECK(hipMemcpy(cp.data(), e->res.col_ptr.p, cp.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    for (uint32_t h = 0; h < e->H; ++h) {
+        const uint64_t base = cp[h * L], n = cp[(h + 1) * L] - base;
+        if (n && !indices_out[h]) return fail(GBRS_ERR_INVALID, "output buffer %u is NULL", h);
+        for (uint64_t l = 0; l <= L; ++l) indptr_out[h][l] = (uint32_t)(cp[h * L + l] - base);
+        if (n) GBRS_HIP_CHECK(hipMemcpy(indices_out[h], e->res.indices.p + base, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    if (count_out) GBRS_HIP_CHECK(hipMemcpy(count_out, e->res.count.p, e->res.num_ecs * sizeof(double), hipMemcpyDeviceToHost));
+    return GBRS_OK;
+}
+
+int gbrs_ecset_destroy(gbrs_ecset_t *e) {
+    if (e) {
+        (void)hipSetDevice(e->device);
+        delete e;
+    }
     return GBRS_OK;
 }
 

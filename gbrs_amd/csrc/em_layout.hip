@@ -914,6 +914,55 @@ __global__ void ec_permute_count_kernel(uint64_t n, const uint32_t *__restrict__
     if (i < n) out[newid[i]] = w[i];
 }
 
+// Two different rows may share a 64-bit row key.  The sort is stable in the row id, so their copies interleave
+// (A B A B) and merge_flag_kernel, which compares neighbours only, starts a segment at each of them.  The four kernels
+// below join the segments of equal rows inside one key run; they run only when some segment starts inside a run.
+__global__ void ec_run_split_kernel(uint64_t n, const uint64_t *__restrict__ skey, const uint32_t *__restrict__ head,
+                                    uint32_t *__restrict__ n_split) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > 0 && i < n && head[i] && skey[i] == skey[i - 1]) atomicAdd(n_split, 1u);
+}
+
+__global__ void ec_segment_pos_kernel(uint64_t n, const uint32_t *__restrict__ head, const uint32_t *__restrict__ hincl,
+                                      uint32_t *__restrict__ segpos) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && head[i]) segpos[hincl[i] - 1] = (uint32_t)i;
+}
+
+// alias[m] = the first segment of m's key run that holds the same row (m itself when there is none before it)
+__global__ void ec_segment_alias_kernel(uint64_t n_seg, const uint32_t *__restrict__ segpos, const uint64_t *__restrict__ skey,
+                                        const uint32_t *__restrict__ srow, const uint32_t *__restrict__ rowstart,
+                                        const uint32_t *__restrict__ ploc, const uint32_t *__restrict__ pmask,
+                                        uint32_t *__restrict__ alias, uint32_t *__restrict__ keep) {
+    const uint64_t m = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= n_seg) return;
+    const uint32_t i = segpos[m], rb = srow[i];
+    const uint64_t k = skey[i];
+    uint32_t a = (uint32_t)m;
+    for (uint64_t m2 = m; m2-- > 0;) {
+        const uint32_t j = segpos[m2];
+        if (skey[j] != k) break;
+        const uint32_t ra = srow[j];
+        if (!same_loci(rowstart, ploc, ra, rb)) continue;
+        const uint32_t pa = rowstart[ra], pb = rowstart[rb], cnt = rowstart[ra + 1] - pa;
+        bool eq = true;
+        for (uint32_t j2 = 0; j2 < cnt; ++j2) eq &= pmask[pa + j2] == pmask[pb + j2];
+        if (eq) a = (uint32_t)m2;
+    }
+    alias[m] = a;
+    keep[m] = a == (uint32_t)m;
+}
+
+// every sorted row gets the ordinal of its kept segment; a joined segment's first row stops being a head
+__global__ void ec_regroup_kernel(uint64_t n, const uint32_t *__restrict__ alias, const uint32_t *__restrict__ kidx,
+                                  uint32_t *__restrict__ head, uint32_t *__restrict__ hincl) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t m = hincl[i] - 1, a = alias[m];
+    if (a != m) head[i] = 0;
+    hincl[i] = kidx[a] + 1;
+}
+
 __global__ void ec_count_entries_kernel(uint64_t n_short, const uint32_t *__restrict__ head, const uint32_t *__restrict__ srow,
                                         const uint32_t *__restrict__ rowstart, const uint32_t *__restrict__ pmask,
                                         uint32_t *__restrict__ nent) {
@@ -1032,10 +1081,27 @@ int compress_device(CompressResult &out, uint64_t R, uint32_t L, uint32_t H, uin
         hipLaunchKernelGGL(merge_flag_kernel, dim3(grid_for(R1)), dim3(256), 0, s, R1, 1, skey.p, srow.p, rowstart.p, ploc.p,
                            pmask.p, head.p);
         GBRS_TRY(inclusive_scan(sc, head.p, hincl.p, R1, s));
-        uint32_t m32 = 0;
+        DevBuf<uint32_t> d_split;
+        GBRS_TRY(d_split.alloc(1));
+        GBRS_HIP_CHECK(hipMemsetAsync(d_split.p, 0, 4, s));
+        hipLaunchKernelGGL(ec_run_split_kernel, dim3(grid_for(R1)), dim3(256), 0, s, R1, skey.p, head.p, d_split.p);
+        uint32_t m32 = 0, n_split = 0;
         GBRS_HIP_CHECK(hipMemcpyAsync(&m32, hincl.p + R1 - 1, 4, hipMemcpyDeviceToHost, s));
+        GBRS_HIP_CHECK(hipMemcpyAsync(&n_split, d_split.p, 4, hipMemcpyDeviceToHost, s));
         GBRS_HIP_CHECK(hipStreamSynchronize(s));
         M = m32;
+        if (n_split) {   // different rows under one key: join the segments that hold the same row
+            DevBuf<uint32_t> segpos, alias, keep, kidx;
+            GBRS_TRY(segpos.alloc(M)); GBRS_TRY(alias.alloc(M)); GBRS_TRY(keep.alloc(M)); GBRS_TRY(kidx.alloc(M));
+            hipLaunchKernelGGL(ec_segment_pos_kernel, dim3(grid_for(R1)), dim3(256), 0, s, R1, head.p, hincl.p, segpos.p);
+            hipLaunchKernelGGL(ec_segment_alias_kernel, dim3(grid_for(M)), dim3(256), 0, s, M, segpos.p, skey.p, srow.p, rowstart.p,
+                               ploc.p, pmask.p, alias.p, keep.p);
+            GBRS_TRY(exclusive_scan(sc, keep.p, kidx.p, M, s));
+            GBRS_TRY(fetch_last_plus(kidx.p, keep.p, M, m32, s));
+            hipLaunchKernelGGL(ec_regroup_kernel, dim3(grid_for(R1)), dim3(256), 0, s, R1, alias.p, kidx.p, head.p, hincl.p);
+            GBRS_HIP_CHECK(hipStreamSynchronize(s));
+            M = m32;
+        }
     }
     // classes: M from rows with alignments (+1 for the empty key if any row is empty)
     DevBuf<uint32_t> minrow;

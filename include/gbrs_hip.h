@@ -557,6 +557,27 @@ int gbrs_bam_scan_records(gbrs_bam_t *b, uint64_t cap, int32_t *refid, uint32_t 
                           uint64_t names_cap, uint64_t *n_records, uint64_t *names_len);
 int gbrs_bam_destroy(gbrs_bam_t *b);
 
+/* `gbrs bam2ec` (extension): one or more BAM files -> the equivalence classes `gbrs bam2emase` on every file followed
+ * by `gbrs compress -i f1 -i f2 ...` gives, without the read-level matrices or the read names leaving the device.
+ *   create     an empty set for num_loci x num_haps (1 <= H <= 16, L < 2^27: the limits of compress).
+ *   add_bam    b: opened, its reference map set with the same L and H (else GBRS_ERR_INVALID; no map: GBRS_ERR_STATE).
+ *              Reads the file and ranks its names as convert does, builds the file's classes from the resident CSC
+ *              arrays, and appends the file's reads after those already in the set: classes stay in first-occurrence
+ *              order over all reads added so far, counts are numbers of reads, reads without a kept record form the
+ *              empty class.  The same name in two files is two reads.  num_reads_of_file = 0 (and an unchanged set)
+ *              for a file without any record.  stage_seconds double[3]: read, rank, classes (NULL allowed).  Record
+ *              errors as for convert.  After a failure the set holds what it held before.  The bam handle keeps
+ *              nothing on the device.
+ *   sizes      reads added, classes, entries per haplotype (uint64[H]); all zero for an empty set.
+ *   get        indptr_out[h] uint32[L + 1], indices_out[h] uint32[nnz_per_hap[h]] (class ids ascending inside a
+ *              column), count_out double[num_ecs] (NULL to skip).  An empty set has zero classes. */
+typedef struct gbrs_ecset gbrs_ecset_t;
+int gbrs_ecset_create(uint32_t num_loci, uint32_t num_haps, int device, gbrs_ecset_t **out);
+int gbrs_ecset_add_bam(gbrs_ecset_t *e, gbrs_bam_t *b, uint64_t *num_reads_of_file, double *stage_seconds);
+int gbrs_ecset_sizes(gbrs_ecset_t *e, uint64_t *num_reads, uint64_t *num_ecs, uint64_t *nnz_per_hap);
+int gbrs_ecset_get(gbrs_ecset_t *e, uint32_t *const *indptr_out, uint32_t *const *indices_out, double *count_out);
+int gbrs_ecset_destroy(gbrs_ecset_t *e);
+
 /* ------------------------------------------------------------------------------------------
  * HMM: per-chromosome forward-backward + Viterbi over the S = H(H+1)/2 diplotype states.
  * ---------------------------------------------------------------------------------------- */

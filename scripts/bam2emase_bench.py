@@ -11,9 +11,15 @@
      does per record, without pysam's own cost) on a subsample, scaled linearly to the full record count and
      labelled as scaled.
 
+`--bam2ec` times `gbrs bam2ec` instead, in the same job and on the same generated file: `bam2ec` on the file, `bam2ec`
+on the file given twice (the lane merge), the two-step path it replaces (`bam2emase` to an .h5, then `compress`), one
+`bam2ec` run under `rocprofv3 --kernel-trace --stats`, and the device memory in use above the idle level while `bam2ec`
+runs (sampled every few milliseconds from this process).  Every step is a fresh process under its own time limit; the
+first one that fails ends the job.  The files of the one-step and the two-step path are compared member by member.
+
 Prints one JSON object.  Needs an MI355X.  Usage:
     python scripts/bam2emase_bench.py [--reads N] [--per-read K] [--haps H] [--loci L] [--format npz|h5]
-                                      [--workdir DIR] [--keep] [--no-profile] [--json OUT]
+                                      [--workdir DIR] [--keep] [--no-profile] [--json OUT] [--bam2ec]
 """
 from __future__ import annotations
 
@@ -143,6 +149,170 @@ def kernel_stats(prof_dir):
     return {k: dict(calls=c, ms=round(ns / 1e6, 3)) for k, (c, ns) in sorted(out.items(), key=lambda kv: -kv[1][1])}
 
 
+class DeviceMemoryWatch:
+    """Device memory in use on device 0, polled from a thread of this process while a child runs (hipMemGetInfo counts
+    every process's allocations).  peak_above_idle_bytes is the largest reading minus the reading before the child
+    started, so it includes the child's runtime context; None when the runtime could not be asked."""
+
+    def __init__(self, interval=0.004):
+        import ctypes
+        import threading
+        self.interval, self.peak, self.idle, self.samples = interval, None, None, 0
+        self._stop = threading.Event()
+        self._thread = None
+        try:
+            self._hip = ctypes.CDLL('libamdhip64.so')
+            self._free, self._total = ctypes.c_size_t(0), ctypes.c_size_t(0)
+            if self._hip.hipSetDevice(0) != 0 or self._used() is None:
+                self._hip = None
+        except OSError:
+            self._hip = None
+
+    def _used(self):
+        import ctypes
+        if self._hip.hipMemGetInfo(ctypes.byref(self._free), ctypes.byref(self._total)) != 0:
+            return None
+        return self._total.value - self._free.value
+
+    def _poll(self):
+        self._hip.hipSetDevice(0)
+        while not self._stop.is_set():
+            u = self._used()
+            if u is not None:
+                self.peak = u if self.peak is None else max(self.peak, u)
+                self.samples += 1
+            time.sleep(self.interval)
+
+    def __enter__(self):
+        import threading
+        if self._hip is not None:
+            self.idle = self._used()
+            self._thread = threading.Thread(target=self._poll, daemon=True)
+            self._thread.start()
+        return self
+
+    def __exit__(self, *exc):
+        self._stop.set()
+        if self._thread is not None:
+            self._thread.join()
+
+    @property
+    def peak_above_idle_bytes(self):
+        return None if self.peak is None or self.idle is None else max(0, self.peak - self.idle)
+
+
+def run_staged(cmd, stage_file, limit_s, watch_memory=False):
+    """One fresh process under a time limit -> dict(wall_s, stages..., [peak_device_bytes_above_idle]) or dict(failed=...)."""
+    env = dict(os.environ, PYTHONPATH=ROOT, GBRS_STAGE_TIMES=stage_file, GBRS_T0=repr(time.time()))
+    if os.path.exists(stage_file):
+        os.remove(stage_file)
+    watch = DeviceMemoryWatch() if watch_memory else None
+    t0 = time.time()
+    try:
+        if watch is not None:
+            with watch:
+                r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=limit_s)
+        else:
+            r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=limit_s)
+    except subprocess.TimeoutExpired:
+        return dict(failed=f'time limit of {limit_s} s')
+    wall = time.time() - t0
+    st = {}
+    if os.path.exists(stage_file):
+        with open(stage_file) as fh:
+            st = json.load(fh)
+    if r.returncode != 0 or 'error' in st or not st:
+        return dict(failed=st.get('error', f'exit status {r.returncode}: {r.stderr[-500:]}'))
+    out = dict(wall_s=round(wall, 3), **{k: round(v, 4) for k, v in st.items()})
+    if watch is not None:
+        out['peak_device_bytes_above_idle'] = watch.peak_above_idle_bytes
+        out['memory_samples'] = watch.samples
+    return out
+
+
+def files_equal(a, b):
+    """The class files of the one-step and the two-step path, member by member."""
+    import numpy as np
+    from gbrs_amd.alignment import load_alignment, read_rname
+    x, y = load_alignment(a), load_alignment(b)
+    same = x.shape == y.shape and x.hname == y.hname and x.lname == y.lname and read_rname(a) is None
+    same = same and x.count is not None and y.count is not None and np.array_equal(x.count, y.count)
+    for h in range(x.shape[1]):
+        same = same and np.array_equal(x.indptr[h], y.indptr[h]) and np.array_equal(x.indices[h], y.indices[h])
+    return bool(same), int(x.shape[2]), float(x.count.sum())
+
+
+def bench_bam2ec(args, res, workdir, bam, ids, hname):
+    py = [sys.executable, '-m', 'gbrs_amd']
+    common = ['-m', ids, '-h', ','.join(hname)]
+    stage_file = os.path.join(workdir, 'stages.json')
+    one, twice = os.path.join(workdir, 'one.compressed.h5'), os.path.join(workdir, 'twice.compressed.h5')
+    mid, two = os.path.join(workdir, 'sample.h5'), os.path.join(workdir, 'two.compressed.h5')
+    limit = max(120, int(args.reads / 100_000))                       # 400 s at 40M reads: ten times what a step takes
+    steps = [('bam2ec', py + ['bam2ec', '-i', bam] + common + ['-o', one], True, 2),
+             ('bam2ec_file_twice', py + ['bam2ec', '-i', bam, '-i', bam] + common + ['-o', twice], True, 1),
+             ('bam2emase', py + ['bam2emase', '-i', bam] + common + ['-o', mid], False, 1),
+             ('compress', py + ['compress', '-i', mid, '-o', two], False, 1)]
+    for name, cmd, watch, times in steps:
+        runs = []
+        for _ in range(times):
+            print(f'[bench] {name} ...', file=sys.stderr, flush=True)
+            r = run_staged(cmd, stage_file, limit, watch_memory=watch)
+            if 'failed' in r:
+                res[name] = r
+                return 1
+            runs.append(r)
+        res[name] = dict(min(runs, key=lambda x: x['wall_s']), runs=len(runs))
+    res['two_step_wall_s'] = round(res['bam2emase']['wall_s'] + res['compress']['wall_s'], 3)
+    res['output_bytes'] = dict(bam2ec=os.path.getsize(one), bam2ec_file_twice=os.path.getsize(twice),
+                               bam2emase=os.path.getsize(mid), compress=os.path.getsize(two))
+    same, n_ecs, n_reads = files_equal(one, two)
+    res['bam2ec_equals_two_step'], res['num_ecs'], res['count_sum'] = same, n_ecs, n_reads
+    if not args.no_profile and shutil.which('rocprofv3'):
+        env = dict(os.environ, PYTHONPATH=ROOT, GBRS_ORDERLY_EXIT='1')           # the tracer writes at exit
+        for key, step in (('profile', steps[0]), ('profile_file_twice', steps[1])):
+            print(f'[bench] {step[0]} under rocprofv3 ...', file=sys.stderr, flush=True)
+            prof = os.path.join(workdir, key)
+            try:
+                r = subprocess.run(['rocprofv3', '--kernel-trace', '--stats', '--output-format', 'csv', '-d', prof, '--'] + step[1],
+                                   env=env, cwd=workdir, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                                   timeout=2 * limit)
+            except subprocess.TimeoutExpired:
+                res[key] = dict(rc='time limit')
+                return 1
+            k = kernel_stats(prof)
+            res[key] = dict(rc=r.returncode, kernels=k, device_ms_total=round(sum(v['ms'] for v in k.values()), 3),
+                            stage_device_ms=stage_device_ms(prof),
+                            gather_rname_kernel_calls=sum(v['calls'] for n, v in k.items() if 'gather_rname' in n))
+            if r.returncode != 0:
+                return 1
+    return 0 if same else 1
+
+
+def stage_device_ms(prof_dir):
+    """Device time of the rank and the classes stage of `bam2ec` from the kernel trace, in dispatch order: a file's rank
+    stage starts with pack_names_kernel, its classes stage with record_keys_kernel.  None without a trace."""
+    rows = []
+    for f in glob.glob(os.path.join(prof_dir, '**', '*kernel_trace.csv'), recursive=True):
+        with open(f) as fh:
+            for row in csv.DictReader(fh):
+                try:
+                    rows.append((int(row['Start_Timestamp']), int(row['End_Timestamp']), row['Kernel_Name']))
+                except (KeyError, ValueError):
+                    return None
+    if not rows:
+        return None
+    rows.sort()
+    out, stage = dict(before=0.0, rank=0.0, classes=0.0), 'before'
+    for t0, t1, name in rows:
+        if 'pack_names_kernel' in name:
+            stage = 'rank'
+        elif 'record_keys_kernel' in name:
+            stage = 'classes'
+        out[stage] += (t1 - t0) / 1e6
+    return {k: round(v, 3) for k, v in out.items()}
+
+
 def python_loop_seconds(reads, per, haps, loci):
     """The restatement's per-record loop (set of names, sorted, dict look-ups, split, two appends) on `reads` reads."""
     import numpy as np
@@ -175,6 +345,7 @@ def main():
     ap.add_argument('--python-reads', type=int, default=100_000, help='reads of the pure-Python loop (0 = skip)')
     ap.add_argument('--procs', type=int, default=int(os.environ.get('OMP_NUM_THREADS', '16')))
     ap.add_argument('--json', default=None)
+    ap.add_argument('--bam2ec', action='store_true', help='time `gbrs bam2ec` against `bam2emase` + `compress` (see above)')
     args = ap.parse_args()
     workdir = args.workdir or tempfile.mkdtemp(prefix='bam2emase_bench_')
     os.makedirs(workdir, exist_ok=True)
@@ -185,6 +356,17 @@ def main():
                name_bytes=NAME_W, bam_bytes=os.path.getsize(bam), inflated_bytes=plain,
                generate_s=round(time.time() - t0, 2), format=args.format,
                configs1_records=360_000_000, below_configs1=args.reads * args.per_read < 360_000_000)
+    if args.bam2ec:
+        res['format'] = 'h5'
+        rc = bench_bam2ec(args, res, workdir, bam, ids, hname)
+        if not args.keep and args.workdir is None:
+            shutil.rmtree(workdir, ignore_errors=True)
+        text = json.dumps(res)
+        if args.json:
+            with open(args.json, 'w') as fh:
+                fh.write(text + '\n')
+        print(text, flush=True)
+        return rc
     out = os.path.join(workdir, f'sample.{args.format}')
     stage_file = os.path.join(workdir, 'stages.json')
     cmd = [sys.executable, '-m', 'gbrs_amd', 'bam2emase', '-i', bam, '-m', ids, '-h', ','.join(hname), '-o', out]

@@ -64,6 +64,7 @@ GBRS_EM_NO_LOCUS_SETS = 512
 GBRS_EM_GROUPED_MODELS = 1024
 GBRS_EM_POSTERIOR = 2048
 GBRS_EM_RESAMPLE = 4096
+GBRS_EM_NO_RUN_WORDS = 8192
 GBRS_RESAMPLE_BASE = 0xFFFFFFFF
 
 
@@ -73,7 +74,7 @@ class EmInfo(C.Structure):
         ("num_device_words", C.c_uint64), ("bytes_per_iter", C.c_uint64),
         ("algorithmic_bytes", C.c_uint64), ("last_estep_ms", C.c_double),
         ("last_step_ms", C.c_double), ("num_loci", C.c_uint32), ("num_haps", C.c_uint32),
-        ("layout", C.c_uint32), ("reserved", C.c_uint32),
+        ("layout", C.c_uint32), ("num_folded_rows", C.c_uint32),
         ("num_tiles", C.c_uint64), ("num_slots", C.c_uint64), ("num_long_rows", C.c_uint64),
         ("num_heavy_loci", C.c_uint64), ("num_light_loci", C.c_uint64), ("estep_bytes", C.c_uint64),
         ("retained_build_bytes", C.c_uint64),

@@ -1395,7 +1395,7 @@ int em_create_impl(uint64_t R, uint32_t L, uint32_t H, const uint32_t *const *in
                                    em->stream, (flags & GBRS_EM_SIDE_BY_SIDE) ? 2u : 1u,
                                    (flags & GBRS_EM_NO_LOCUS_SETS) == 0 && !em->has_count &&
                                        !(flags & GBRS_EM_MERGE_IDENTICAL_ROWS),     // (weighted rows: their tiles are dictionary-bound)
-                                   0, em->view));
+                                   0, em->view, (flags & GBRS_EM_NO_RUN_WORDS) == 0));
         em->layout = 1;
         {
             // persistent E-step workgroups: one per place the chip has for them (tile_estep_kernel's launch bounds: 3 per CU
@@ -2064,7 +2064,8 @@ int gbrs_em_info(gbrs_em_t *em, gbrs_em_info_t *info) {
     info->estep_bytes = 8 * em->N + 8 * em->R * 3 + 8 * HL * 2;
     if (em->layout == 1) {
         const TileLayout &tl = em->tl;
-        info->num_device_rows = tl.n_rows + tl.n_long;
+        info->num_device_rows = tl.n_rows + tl.n_folded + tl.n_long;     // every read the layout represents
+        info->num_folded_rows = (uint32_t)tl.n_folded;
         info->num_tiles = tl.n_tiles;
         info->num_slots = tl.n_slots;
         info->num_long_rows = tl.n_long;

@@ -5,6 +5,10 @@
 //            bits [0,H) mask; PB bits pos = words of the row before this one; PB bits rem = words
 //            of the row after it; the rest = index into the tile's dictionary.  PB = 5 (rows of up
 //            to 32 loci) for H <= 8, 4 (16 loci) for H <= 16.
+//            A one-word row has pos = rem = 0, and in a tile's leading one-word batches (TileHdr::n_one) those 2 PB bits
+//            are ONE field: the number of FURTHER identical reads - same dictionary entry, same mask - the word stands
+//            for (the fold of build_tile_layout's step 5; it adds (1 + count) / den once).  0 everywhere in a layout that
+//            did not fold, so the kernels have no switch for it; 0 in the padding cells of those batches, always.
 //   batch  = 64 consecutive words = what one wavefront takes per step; rows never straddle a
 //            batch (zero words pad the tail), so a batch is self-contained.
 //   tile   = a run of batches processed by one workgroup with one locus dictionary of at most
@@ -91,7 +95,8 @@ struct TileHdr {
     uint16_t n_one;        // the tile's first n_one batches hold one-word rows only (stream order, unweighted: the B of
                            // tile_pad_kernel's run of one-word rows; 0: nothing is known about the tile's batches).  An empty
                            // cell of these batches carries the dictionary index of the cell above it (same lane, batch
-                           // before) and no haplotype bit, see fill_one_word_cells_kernel
+                           // before) and no haplotype bit, see fill_one_word_cells_kernel.  In these batches a word's pos /
+                           // rem bits are a repeat count (the word format above)
     uint32_t dict_base;    // first slot / dictionary entry of the tile
     uint32_t dict_count;   // D
 };
@@ -111,7 +116,8 @@ struct TileLayout {
     // sizes
     uint64_t n_pairs = 0;        // (row, locus) pairs = unpadded words
     uint64_t n_rows_in = 0;      // rows with at least one alignment
-    uint64_t n_rows = 0;         // rows in the layout (after optional merging), short rows only
+    uint64_t n_rows = 0;         // rows in the layout (after optional merging / folding), short rows only
+    uint64_t n_folded = 0;       // one-word reads without a word of their own: counted by an identical read's word (0: no fold)
     uint64_t n_long = 0;         // rows with more than MAX_ROW_WORDS loci
     uint64_t n_tiles = 0, n_batches = 0, n_slots = 0, n_heavy = 0, n_light = 0;
     uint32_t d_max = 0;          // dictionary capacity used when cutting tiles
@@ -178,7 +184,7 @@ int build_tile_layout(TileLayout &out, uint64_t R, uint32_t L, uint32_t H, uint6
                       bool merge_identical_rows, int row_order /* 0 sorted, 1 interleaved, 2 streams */,
                       bool deterministic, hipStream_t stream, unsigned side_by_side = 1 /* handles sharing the device */,
                       bool locus_sets = false, uint32_t dict_cap = 0 /* > 0: at most this many loci per tile dictionary */,
-                      uint32_t view_factor = 1);
+                      uint32_t view_factor = 1, bool run_words = true /* false: never fold identical one-word reads */);
 // view_factor = 2 (round 4, 16 haplotypes): the layout is built over HALF-LOCI - locus l's haplotypes 0-7 are "locus" 2l,
 // its haplotypes 8-15 "locus" 2l + 1, L and H passed here are 2 L and 8.  The locus-major vectors (theta, A, lengths:
 // element l * 16 + h) are element for element the half-locus view's (2l + h / 8) * 8 + h % 8, so nothing outside the layout

@@ -26,6 +26,7 @@ struct BuildFlags {
     unsigned int dict_overflow;  // a tile dictionary exceeded its capacity (internal error)
     unsigned int bad_row;        // row id >= R
     unsigned int n_long;         // rows with more than max_row_words(H) loci
+    unsigned int long_pairs;     // their (row, locus) pairs: what the tiles do not hold
 };
 
 // Every wavefront takes a contiguous span of KEY_SPAN entries: one full search for the column of its
@@ -398,6 +399,7 @@ __global__ void row_key_kernel(uint64_t nrows, uint32_t max_row, unsigned loc_sh
     if (b - a > max_row) {
         key[r] = ~0ull;
         atomicAdd(&flags->n_long, 1u);
+        atomicAdd(&flags->long_pairs, b - a);
         return;
     }
     uint32_t hl = 0x811c9dc5u, hm = 0x01000193u;
@@ -421,7 +423,8 @@ __device__ __forceinline__ bool same_loci(const uint32_t *__restrict__ rowstart,
     return true;
 }
 
-// head[i] = 1 when sorted row i starts a new (merged) row
+// head[i] = 1 when sorted row i starts a new (merged) row.  merge = 1: identical rows join; merge = 2 (the fold of identical
+// one-word reads, em_layout.h): rows join only when both are exactly one (locus, mask) pair and the pairs are equal
 __global__ void merge_flag_kernel(uint64_t n, int merge, const uint64_t *__restrict__ skey,
                                   const uint32_t *__restrict__ srow, const uint32_t *__restrict__ rowstart,
                                   const uint32_t *__restrict__ ploc, const uint32_t *__restrict__ pmask,
@@ -429,7 +432,11 @@ __global__ void merge_flag_kernel(uint64_t n, int merge, const uint64_t *__restr
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     uint32_t f = 1;
-    if (merge && i > 0 && skey[i] == skey[i - 1]) {
+    if (merge == 2 && i > 0 && skey[i] == skey[i - 1]) {
+        const uint32_t ra = srow[i - 1], rb = srow[i];
+        const uint32_t a = rowstart[ra], b = rowstart[rb];
+        if (rowstart[ra + 1] - a == 1u && rowstart[rb + 1] - b == 1u && ploc[a] == ploc[b] && pmask[a] == pmask[b]) f = 0;
+    } else if (merge == 1 && i > 0 && skey[i] == skey[i - 1]) {
         const uint32_t ra = srow[i - 1], rb = srow[i];
         if (same_loci(rowstart, ploc, ra, rb)) {
             const uint32_t a = rowstart[ra], b = rowstart[rb], cnt = rowstart[ra + 1] - a;
@@ -441,15 +448,28 @@ __global__ void merge_flag_kernel(uint64_t n, int merge, const uint64_t *__restr
     head[i] = f;
 }
 
-// per sorted row: merged ordinal m = incl[i] - 1; accumulate weights, record representative
+// The fold's runs are cut every `cap` rows (what a word's count field holds): hpos is the position of the last head at or
+// before row i (a max-scan of run_head_pos_kernel's output), and every cap-th row of a run becomes a head of its own
+__global__ void run_head_pos_kernel(uint64_t n, const uint32_t *__restrict__ head, uint32_t *__restrict__ pos) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) pos[i] = head[i] ? (uint32_t)i : 0u;
+}
+
+__global__ void run_cut_kernel(uint64_t n, uint32_t cap, const uint32_t *__restrict__ hpos, uint32_t *__restrict__ head) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && ((uint32_t)i - hpos[i]) % cap == 0u) head[i] = 1u;
+}
+
+// per sorted row: merged ordinal m = incl[i] - 1; accumulate weights (merge) or the repeat count (fold), record representative
 __global__ void merged_rows_kernel(uint64_t n, const uint32_t *__restrict__ head, const uint32_t *__restrict__ hincl,
                                    const uint32_t *__restrict__ srow, const uint32_t *__restrict__ row_orig,
                                    const double *__restrict__ count, uint32_t *__restrict__ hrow,
-                                   double *__restrict__ weight) {
+                                   double *__restrict__ weight, uint32_t *__restrict__ repeat) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint32_t m = hincl[i] - 1;
     if (head[i]) hrow[m] = srow[i];
+    if (repeat) atomicAdd(&repeat[m], 1u);
     if (weight) atomicAdd(&weight[m], count ? count[row_orig[srow[i]]] : 1.0);
 }
 
@@ -511,14 +531,16 @@ __global__ void stream_key_kernel(uint64_t m_rows, const uint32_t *__restrict__ 
 
 __global__ void permute_rows_kernel(uint64_t m_rows, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ hrow,
                                     const uint32_t *__restrict__ npm, const double *__restrict__ weight,
-                                    uint32_t *__restrict__ hrow2, uint32_t *__restrict__ npm2,
-                                    double *__restrict__ weight2) {
+                                    const uint32_t *__restrict__ repeat, uint32_t *__restrict__ hrow2,
+                                    uint32_t *__restrict__ npm2, double *__restrict__ weight2,
+                                    uint32_t *__restrict__ repeat2) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= m_rows) return;
     const uint32_t m = perm[i];
     hrow2[i] = hrow[m];
     npm2[i] = npm[m];
     if (weight) weight2[i] = weight[m];
+    if (repeat) repeat2[i] = repeat[m];
 }
 
 __global__ void tile_start_kernel(uint64_t m_rows, uint64_t n_tiles, const uint32_t *__restrict__ tflag,
@@ -602,14 +624,16 @@ __global__ void tile_hdr_kernel(uint64_t n_tiles, uint32_t dcap, uint32_t n_slot
     hdr[t] = TileHdr{batch_base[t], (uint16_t)nbatch[t], (uint16_t)n_one[t], db, d};
 }
 
-// one thread per (merged) row: emit its words at the padded position
+// one thread per (merged) row: emit its words at the padded position.  repeat (the fold, em_layout.h): a one-word row's
+// pos / rem field - zero otherwise - takes the number of further identical reads the word stands for
 __global__ void emit_words_kernel(uint64_t m_rows, uint32_t H, const uint32_t *__restrict__ tincl,
                                   const TileHdr *__restrict__ hdr, const uint32_t *__restrict__ dict,
                                   const uint32_t *__restrict__ hrow, const uint32_t *__restrict__ rowstart,
                                   const uint32_t *__restrict__ ploc, const uint32_t *__restrict__ pmask,
                                   const uint32_t *__restrict__ rowpad, uint32_t *__restrict__ words,
                                   const double *__restrict__ row_weight, double *__restrict__ word_weight,
-                                  const uint32_t *__restrict__ row_orig, uint32_t *__restrict__ word_row) {
+                                  const uint32_t *__restrict__ row_orig, uint32_t *__restrict__ word_row,
+                                  const uint32_t *__restrict__ repeat) {
     const uint64_t m = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= m_rows) return;
     const TileHdr th = hdr[tincl[m] - 1];
@@ -625,7 +649,9 @@ __global__ void emit_words_kernel(uint64_t m_rows, uint32_t H, const uint32_t *_
             const uint32_t mid = (lo + hi) >> 1;
             if (d[mid] < l) lo = mid + 1; else hi = mid;
         }
-        words[base + j] = pmask[p0 + j] | (j << H) | ((cnt - 1 - j) << (H + PB)) | (lo << (H + 2 * PB));
+        uint32_t w = pmask[p0 + j] | (j << H) | ((cnt - 1 - j) << (H + PB)) | (lo << (H + 2 * PB));
+        if (repeat && cnt == 1u) w |= (repeat[m] - 1u) << H;
+        words[base + j] = w;
         if (word_weight) word_weight[base + j] = row_weight[m];
         if (word_row) word_row[base + j] = row_orig[r];          // resampling handle: the file row the word's weight comes from
     }
@@ -635,7 +661,9 @@ __global__ void emit_words_kernel(uint64_t m_rows, uint32_t H, const uint32_t *_
 // at batches 0 .. B-1, so only the lane of the run's last row ends early (the lanes after it are empty altogether and
 // stay all-zero words: dictionary entry 0).  That lane's empty cells take the dictionary index of its last row and no
 // haplotype bit: still padding to every reader (no bit, nothing added), and a lane that walks down the run never meets
-// a change of entry that is not one.  One thread per (tile, lane).
+// a change of entry that is not one.  Their pos / rem field - a repeat count in these batches - is 0: the first loop
+// multiplies a padding word's 4.49e307 by 1 + count, and inf times the 0.0 of a clear haplotype bit would be NaN.
+// One thread per (tile, lane).
 __global__ void fill_one_word_cells_kernel(uint64_t n_tiles, uint32_t H, const TileHdr *__restrict__ hdr,
                                            uint32_t *__restrict__ words) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1163,7 +1191,7 @@ int compress_device(CompressResult &out, uint64_t R, uint32_t L, uint32_t H, uin
 int build_tile_layout(TileLayout &out, uint64_t R, uint32_t L_in, uint32_t H, uint64_t N,
                       const uint32_t *ent_row, const uint64_t *col_ptr, const double *count,
                       bool merge, int row_order, bool deterministic, hipStream_t s, unsigned side_by_side, bool locus_sets,
-                      uint32_t dict_cap, uint32_t view_factor) {
+                      uint32_t dict_cap, uint32_t view_factor, bool run_words) {
     uint32_t L = L_in;                     // grows by the number of locus sets in step 3b
     out.n_sets = 0;
     out.n_dest_rows = 0;
@@ -1197,7 +1225,7 @@ int build_tile_layout(TileLayout &out, uint64_t R, uint32_t L_in, uint32_t H, ui
         return fail(GBRS_ERR_UNSUPPORTED, "the deterministic tile layout has no room for a row's loci at H = %u", H);
     const uint32_t dseg = out.d_max - max_row_words(H);
     out.weighted = merge || count != nullptr;
-    out.n_pairs = out.n_rows = out.n_rows_in = out.n_long = out.n_tiles = out.n_batches = out.n_slots = 0;
+    out.n_pairs = out.n_rows = out.n_rows_in = out.n_long = out.n_tiles = out.n_batches = out.n_slots = out.n_folded = 0;
     GBRS_TRY(out.slot_ptr.alloc((size_t)L + 1));
     GBRS_HIP_CHECK(hipMemsetAsync(out.slot_ptr.p, 0, out.slot_ptr.bytes(), s));
     GBRS_TRY(out.locus_class.alloc(L));
@@ -1457,25 +1485,64 @@ int build_tile_layout(TileLayout &out, uint64_t R, uint32_t L_in, uint32_t H, ui
     const uint64_t n_long = hf.n_long, n_short = R1 - n_long;
     out.n_long = n_long;
     stg.mark("4 order rows");
-    // 5. optional merge of identical adjacent rows + weights
-    DevBuf<uint32_t> head, hincl, hrow;
+    // 5. optional merge of identical adjacent rows + weights - or the fold of identical one-word reads (em_layout.h): the
+    // reads of one (dictionary entry, mask) class that the sort left next to each other keep one row with a repeat count,
+    // cut every FOLD_CAP rows.  The fold exists where the E-step kernels read the count: the leading one-word batches of the
+    // stream order's unweighted tiles (TileHdr::n_one) of the haplotype counts with a kernel instance of their own.
+    bool fold = run_words && streams && !out.weighted && !deterministic && view_factor == 1 &&
+                (H == 1 || H == 2 || H == 4 || H == 8);
+    const char *fold_env = std::getenv("GBRS_TUNING_RUN_WORDS");
+    if (fold_env && std::atoi(fold_env) == 0) fold = false;
+    const uint32_t FOLD_CAP = 1u << (2 * pos_bits((int)H));
+    DevBuf<uint32_t> head, hincl, hrow, repeat;
     uint64_t M = n_short;
     if (n_short) {
         GBRS_TRY(head.alloc(n_short)); GBRS_TRY(hincl.alloc(n_short));
-        hipLaunchKernelGGL(merge_flag_kernel, dim3(grid_for(n_short)), dim3(256), 0, s, n_short, merge ? 1 : 0, skey.p,
-                           srow.p, rowstart.p, ploc.p, pmask.p, head.p);
-        GBRS_TRY(inclusive_scan(sc, head.p, hincl.p, n_short, s));
         uint32_t m32 = 0;
-        GBRS_HIP_CHECK(hipMemcpyAsync(&m32, hincl.p + n_short - 1, 4, hipMemcpyDeviceToHost, s));
-        GBRS_HIP_CHECK(hipStreamSynchronize(s));
+        for (;;) {
+            hipLaunchKernelGGL(merge_flag_kernel, dim3(grid_for(n_short)), dim3(256), 0, s, n_short, fold ? 2 : (merge ? 1 : 0),
+                               skey.p, srow.p, rowstart.p, ploc.p, pmask.p, head.p);
+            if (fold) {
+                DevBuf<uint32_t> hpos;
+                GBRS_TRY(hpos.alloc(n_short));
+                hipLaunchKernelGGL(run_head_pos_kernel, dim3(grid_for(n_short)), dim3(256), 0, s, n_short, head.p, hincl.p);
+                size_t bytes = 0;
+                GBRS_PRIM(rocprim::inclusive_scan(nullptr, bytes, hincl.p, hpos.p, (size_t)n_short, rocprim::maximum<uint32_t>(), s));
+                GBRS_TRY(sc.reserve(bytes));
+                GBRS_PRIM(rocprim::inclusive_scan(sc.buf.p, bytes, hincl.p, hpos.p, (size_t)n_short, rocprim::maximum<uint32_t>(), s));
+                hipLaunchKernelGGL(run_cut_kernel, dim3(grid_for(n_short)), dim3(256), 0, s, n_short, FOLD_CAP, hpos.p, head.p);
+                GBRS_HIP_CHECK(hipStreamSynchronize(s));      // hpos goes out of scope
+            }
+            GBRS_TRY(inclusive_scan(sc, head.p, hincl.p, n_short, s));
+            GBRS_HIP_CHECK(hipMemcpyAsync(&m32, hincl.p + n_short - 1, 4, hipMemcpyDeviceToHost, s));
+            GBRS_HIP_CHECK(hipStreamSynchronize(s));
+            if (!fold) break;
+            // Worth it?  The fold pays by the words it takes away, and a launch still wants a tile of TILE_WORDS words for
+            // every resident workgroup place of the chip (the places of the tile-size rule in step 7): a sample smaller
+            // than that is launch-bound and keeps one word per read.  GBRS_TUNING_RUN_WORDS=1 / 0 forces the choice.
+            const uint64_t words_in = out.n_pairs - hf.long_pairs, folded = n_short - m32, words_left = words_in - folded;
+            int dev = 0, n_cu = 0;
+            GBRS_HIP_CHECK(hipGetDevice(&dev));
+            GBRS_HIP_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
+            const uint64_t places = (uint64_t)TILE_ROUNDS_MIN * 3u * (uint64_t)std::max(n_cu, 1);
+            bool take = folded * 100 >= words_in * 15 && words_left * side_by_side / places >= (uint64_t)TILE_WORDS;
+            if (fold_env) take = true;             // (0 was handled above)
+            if (take) { out.n_folded = folded; break; }
+            fold = false;                          // the flags again, one row per read
+        }
         M = m32;
         GBRS_TRY(hrow.alloc(M));
+        if (fold) {
+            GBRS_TRY(repeat.alloc(M));
+            GBRS_HIP_CHECK(hipMemsetAsync(repeat.p, 0, repeat.bytes(), s));
+        }
         if (out.weighted) {
             GBRS_TRY(out.row_weight.alloc(M));
             GBRS_HIP_CHECK(hipMemsetAsync(out.row_weight.p, 0, out.row_weight.bytes(), s));
         }
         hipLaunchKernelGGL(merged_rows_kernel, dim3(grid_for(n_short)), dim3(256), 0, s, n_short, head.p, hincl.p, srow.p,
-                           row_orig.p, count, hrow.p, out.weighted ? out.row_weight.p : nullptr);
+                           row_orig.p, count, hrow.p, out.weighted ? out.row_weight.p : nullptr,
+                           fold ? repeat.p : (uint32_t *)nullptr);
         GBRS_HIP_CHECK(hipStreamSynchronize(s));
         head.release(); hincl.release();
     }
@@ -1548,7 +1615,7 @@ int build_tile_layout(TileLayout &out, uint64_t R, uint32_t L_in, uint32_t H, ui
     stg.mark("7 tiles");
     // 7b. interleave the locus lists inside each tile (tile membership and sizes are unchanged)
     if (interleave || streams) {
-        DevBuf<uint32_t> gflag, gpos, gstart, gord, ident, perm, hrow2, npm2;
+        DevBuf<uint32_t> gflag, gpos, gstart, gord, ident, perm, hrow2, npm2, repeat2;
         DevBuf<uint64_t> ikey, ikey2;
         DevBuf<double> weight2;
         if (interleave) {
@@ -1579,9 +1646,11 @@ int build_tile_layout(TileLayout &out, uint64_t R, uint32_t L_in, uint32_t H, ui
         stg.mark("7b-d release");
         GBRS_TRY(hrow2.alloc(M)); GBRS_TRY(npm2.alloc(M));
         if (out.weighted) GBRS_TRY(weight2.alloc(M));
+        if (fold) GBRS_TRY(repeat2.alloc(M));
         hipLaunchKernelGGL(permute_rows_kernel, dim3(grid_for(M)), dim3(256), 0, s, M, perm.p, hrow.p, npm.p,
-                           out.weighted ? out.row_weight.p : (const double *)nullptr, hrow2.p, npm2.p,
-                           out.weighted ? weight2.p : (double *)nullptr);
+                           out.weighted ? out.row_weight.p : (const double *)nullptr, fold ? repeat.p : (const uint32_t *)nullptr,
+                           hrow2.p, npm2.p, out.weighted ? weight2.p : (double *)nullptr, fold ? repeat2.p : (uint32_t *)nullptr);
+        if (fold) GBRS_HIP_CHECK(hipMemcpyAsync(repeat.p, repeat2.p, M * 4, hipMemcpyDeviceToDevice, s));
         GBRS_HIP_CHECK(hipMemcpyAsync(hrow.p, hrow2.p, M * 4, hipMemcpyDeviceToDevice, s));
         GBRS_HIP_CHECK(hipMemcpyAsync(npm.p, npm2.p, M * 4, hipMemcpyDeviceToDevice, s));
         if (out.weighted)
@@ -1647,13 +1716,14 @@ int build_tile_layout(TileLayout &out, uint64_t R, uint32_t L_in, uint32_t H, ui
                        hrow.p, rowstart.p, ploc.p, pmask.p, rowpad.p, out.words.p,
                        out.weighted ? out.row_weight.p : (const double *)nullptr,
                        out.weighted ? out.word_weight.p : (double *)nullptr,
-                       keep_row_ids ? row_orig.p : (const uint32_t *)nullptr, keep_row_ids ? out.word_row.p : (uint32_t *)nullptr);
+                       keep_row_ids ? row_orig.p : (const uint32_t *)nullptr, keep_row_ids ? out.word_row.p : (uint32_t *)nullptr,
+                       fold ? repeat.p : (const uint32_t *)nullptr);
     if (streams && !out.weighted)
         hipLaunchKernelGGL(fill_one_word_cells_kernel, dim3(grid_for(T * 64)), dim3(256), 0, s, T, H, out.tiles.p, out.words.p);
     GBRS_HIP_CHECK(hipStreamSynchronize(s));
     dict_base.release(); batch_base.release(); nbatch.release(); n_one.release();
     rowpad.release(); tincl.release(); npm.release(); wordoff.release(); tile_row.release();
-    hrow.release(); rowstart.release(); ploc.release(); pmask.release(); row_orig.release();
+    hrow.release(); rowstart.release(); ploc.release(); pmask.release(); row_orig.release(); repeat.release();
     out.row_weight.release();
     // Launch order of the tiles: the ones with the most batches first, so that the launch's last round - when most
     // of the chip has run out of tiles - is made of the short ones (tiles that end at the dictionary limit have

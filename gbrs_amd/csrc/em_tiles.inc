@@ -19,6 +19,11 @@
 //   idx              index into the tile's dictionary
 // A word without a haplotype bit is padding (a one-word row with no haplotype: contributes nothing): all zero, or - in a
 // tile's leading one-word batches - with the dictionary index of the cell above it (TileHdr::n_one).
+// In a tile's leading one-word batches (batch index < TileHdr::n_one) pos = rem = 0 by construction, and the 2 PB bits of
+// the two fields are ONE field instead: the number of FURTHER identical reads the word stands for (the fold of
+// em_layout.h; 0 everywhere in a layout that did not fold, and 0 in padding words).  Such a word adds v = (1 + count) / den.
+// Every kernel instance that can meet an unweighted tile of 1, 2, 4 or 8 haplotypes reads those batches that way: the LEAD
+// form of tile_batches always, the general form when its caller says `count_form` (wave-uniform: the batch index).
 
 #ifndef GBRS_ESTEP_WAVES16
 #define GBRS_ESTEP_WAVES16 4          // the same for more than 8 haplotypes
@@ -203,7 +208,9 @@ template <int HT, bool WEIGHTED, int HC, bool DET, int UB, bool ONEWORD = false,
 __device__ __forceinline__ void tile_batches(const uint32_t (&w)[UB], const double (&wt)[UB], int H, int PB, int lane,
                                              const double *__restrict__ s_theta, double *__restrict__ my_acc,
                                              LaneAcc<HC> &st, const int (&zlo)[32], const double2 *__restrict__ s_ftab,
-                                             uint32_t misfit_bits, uint32_t relax_zero_weight = 0u) {
+                                             uint32_t misfit_bits, uint32_t relax_zero_weight = 0u,
+                                             bool count_form = false /* general form: a batch below TileHdr::n_one */) {
+    constexpr bool COUNTS = HT > 0 && HT <= 8 && !WEIGHTED && !DET && UB == 1;     // the instances that meet count fields
     constexpr bool ZLO = estep_uses_zlo(UB);
     constexpr bool FTAB = estep_uses_ftab(UB, HT);
     constexpr bool TREG = estep_theta_regs(UB, HT, DET) && HC >= 8;
@@ -215,11 +222,13 @@ __device__ __forceinline__ void tile_batches(const uint32_t (&w)[UB], const doub
     double f8[UB][8], f16[UB][16];          // HT == 8 / 16 with GBRS_MASK_ZLO: the words' 0/1 doubles
     (void)f8;
     (void)f16;
+    // a counted batch's pos / rem bits are a repeat count (read where v is made): the row-length logic sees them cleared
+    const uint32_t count_bits = (COUNTS && !LEAD && count_form) ? ((1u << (2 * PB)) - 1u) << H : 0u;     // wave-uniform
 #pragma unroll
     for (int u = 0; u < UB; ++u) {
         mask[u] = w[u] & hmask;
-        pos[u] = (w[u] >> H) & pmask;
-        rem[u] = (w[u] >> (H + PB)) & pmask;
+        pos[u] = ((w[u] & ~count_bits) >> H) & pmask;
+        rem[u] = ((w[u] & ~count_bits) >> (H + PB)) & pmask;
         idx[u] = w[u] >> (H + 2 * PB);
     }
     uint64_t real_lanes0 = 0;                                    // TREG: lanes whose word is not padding
@@ -332,7 +341,7 @@ __device__ __forceinline__ void tile_batches(const uint32_t (&w)[UB], const doub
     double den[UB];
     // (pos and rem are adjacent bit fields of the word: one AND finds a row of more than one word)
     const uint32_t fields = (pmask | (pmask << PB)) << H;
-    const uint32_t multi = (UB == 1 ? w[0] : (w[0] | w[UB - 1])) & fields;
+    const uint32_t multi = (UB == 1 ? w[0] : (w[0] | w[UB - 1])) & fields & ~count_bits;
 #if defined(GBRS_ABLATE_ROWSUM)
     if (true) {
 #else
@@ -346,7 +355,7 @@ __device__ __forceinline__ void tile_batches(const uint32_t (&w)[UB], const doub
 #pragma unroll
         for (int u = 0; u < UB; ++u) {
             const double other = quad_swap_pairs(s[u]);
-            den[u] = s[u] + (((w[u] & fields) != 0) ? other : 0.0);
+            den[u] = s[u] + (((w[u] & fields & ~count_bits) != 0) ? other : 0.0);
         }
     } else {
         // running sum over the pos words to my left ...
@@ -393,6 +402,11 @@ __device__ __forceinline__ void tile_batches(const uint32_t (&w)[UB], const doub
             r = fast_recip(__hiloint2double(ok ? __double2hiint(den[u]) : 0x3FF00000, __double2loint(den[u])));
         }
         if (WEIGHTED) r *= wt[u];
+        if constexpr (COUNTS) {
+            // the word and the further reads it stands for: one field extract, one convert, one FMA - the same arithmetic in
+            // both forms (a general-form batch past n_one skips it: its fields are positions)
+            if (LEAD || count_form) r = fma(r, (double)((w[u] >> H) & ((1u << (2 * PB)) - 1u)), r);
+        }
         v[u] = r;
     }
 #pragma unroll
@@ -727,7 +741,10 @@ tile_estep_kernel(uint32_t Hrt, const TileHdr *__restrict__ tiles, const uint32_
                 ring[slot] = load_word(PD + slot);                     // refill PD batches ahead
                 if (WEIGHTED) wring[slot] = load_weight(PD + slot);
             }
-            if (b + tt * UB < b1) tile_batches<HT, WEIGHTED, HC, DET, UB, ONEWORD>(w, wt, H, PB, lane, s_theta, my_acc, st, zlo, s_ftab, misfit_bits, WEIGHTED ? sets.relax_zero_weight : 0u);
+            // (a leading one-word batch that this loop takes - the last 0-3 of a wavefront's share, or every one of them
+            // without the split - carries repeat counts: the header's n_one itself, whatever lead_mask says)
+            if (b + tt * UB < b1) tile_batches<HT, WEIGHTED, HC, DET, UB, ONEWORD>(w, wt, H, PB, lane, s_theta, my_acc, st, zlo, s_ftab, misfit_bits, WEIGHTED ? sets.relax_zero_weight : 0u,
+                                                                                   SPLIT && b + tt * UB < (uint32_t)th.n_one);
         }
         voff += PD * 256;
         asm volatile("" : "+v"(voff));      // keep it one register: the slots stay immediates of the loads
@@ -1018,7 +1035,9 @@ tile_estep_persistent_kernel(uint32_t Hrt, const TileHdr *__restrict__ tiles, co
                     ring[slot] = load_word(PD + slot);
                     if (WEIGHTED) wring[slot] = load_weight(PD + slot);
                 }
-                if (b + tt * UB < b1) tile_batches<HT, WEIGHTED, HC, false, UB, ONEWORD>(w, wt, H, PB, lane, s_theta, my_acc, st, zlo, s_ftab, misfit_bits, WEIGHTED ? sets.relax_zero_weight : 0u);
+                // (one loop here: a batch below the header's n_one is read in count form, see the word decode above)
+                if (b + tt * UB < b1) tile_batches<HT, WEIGHTED, HC, false, UB, ONEWORD>(w, wt, H, PB, lane, s_theta, my_acc, st, zlo, s_ftab, misfit_bits, WEIGHTED ? sets.relax_zero_weight : 0u,
+                                                                                         PF && !WEIGHTED && b + tt * UB < (uint32_t)th.n_one);
             }
             voff += PD * 256;
             asm volatile("" : "+v"(voff));

@@ -64,7 +64,9 @@ typedef struct gbrs_em gbrs_em_t;
 #define GBRS_EM_DEFAULT 0u
 /* Merge rows with identical alignment patterns into one weighted row while building the device
  * layout (what `gbrs compress`, gbrs/emase_utils.py:60-103, does as a separate command).  Same
- * fixed point; off by default so that every input row is processed every iteration. */
+ * fixed point; off by default: the default layout keeps its rows unweighted and counts every read
+ * in every iteration (identical one-word reads may share one word that carries their number, see
+ * GBRS_EM_NO_RUN_WORDS). */
 #define GBRS_EM_MERGE_IDENTICAL_ROWS 1u
 /* Keep the reference's CSC arrays as the device layout (two passes with global float64 atomics).
  * The default is the packed-row-tile layout; this one is the simple cross-check. */
@@ -124,6 +126,15 @@ typedef struct gbrs_em gbrs_em_t;
  * part: it adds nothing, and a zero denominator of its own is no float error.  Without the flag a handle allocates and
  * launches exactly what it did before the flag existed. */
 #define GBRS_EM_RESAMPLE 4096u
+/* Run words off.  By default reads that are ONE word in the tiles (one locus, or one locus set) and identical - same entry,
+ * same haplotype mask - may share a word: each of them adds the same 1/den to its locus in every iteration, so the
+ * word carries how many further reads it stands for (up to 1,023 at <= 8 haplotypes) and adds (1 + n)/den once.  Nothing
+ * becomes weighted and every read is counted; the result agrees with the one-word-per-read form up to the association of
+ * the sums.  The layout takes the fold for unweighted stream-order handles of 1, 2, 4 or 8 haplotypes (never with `count`,
+ * GBRS_EM_MERGE_IDENTICAL_ROWS, GBRS_EM_RESAMPLE or GBRS_EM_DETERMINISTIC) when it removes >= 15 % of the words and the words
+ * left still give every resident workgroup place of the device a full tile; gbrs_em_info.num_folded_rows says how many
+ * reads have no word of their own (0: not taken).  The flag keeps one word per read whatever the sample. */
+#define GBRS_EM_NO_RUN_WORDS 8192u
 /* `replicate` of gbrs_em_resample that puts the base weights back */
 #define GBRS_RESAMPLE_BASE 0xFFFFFFFFu
 
@@ -314,7 +325,7 @@ int gbrs_em_pair_status(gbrs_em_t *a, gbrs_em_t *b, int *iters_done, int *stoppe
 typedef struct gbrs_em_info {
     uint64_t num_rows;          /* R as given                                               */
     uint64_t num_entries;       /* N = sum_h nnz_h                                          */
-    uint64_t num_device_rows;   /* rows in the device layout (== R unless merged)           */
+    uint64_t num_device_rows;   /* reads the device layout represents (== R unless merged)  */
     uint64_t num_device_words;  /* 32-bit (row, locus) words streamed per E-step            */
     uint64_t bytes_per_iter;    /* bytes the E+M step kernels move per iteration (layout)   */
     uint64_t algorithmic_bytes; /* 4N + 4(R+1) [+8R] + 8HL*2 [+8HL]             */
@@ -322,7 +333,10 @@ typedef struct gbrs_em_info {
     double   last_step_ms;      /* steps: every 8th of a gbrs_em_step call) / of a full step */
     uint32_t num_loci, num_haps;
     uint32_t layout;            /* 0 = csc-direct, 1 = packed row tiles                     */
-    uint32_t reserved;
+    uint32_t num_folded_rows;   /* layout 1: one-word reads counted by an identical read's word instead of a word of
+                                   their own; 0: the fold was not taken (GBRS_EM_NO_RUN_WORDS).  The slot was
+                                   `reserved` (always 0): the struct keeps its size and offsets; the tile layout
+                                   holds fewer than 2^32 entries, so 32 bits do                        */
     uint64_t num_tiles;         /* layout 1: workgroup tiles                                */
     uint64_t num_slots;         /* layout 1: (tile, locus) partial-sum slots                */
     uint64_t num_long_rows;     /* layout 1: rows handled by the long-row kernel            */

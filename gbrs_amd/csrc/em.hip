@@ -1410,7 +1410,7 @@ int em_create_impl(uint64_t R, uint32_t L, uint32_t H, const uint32_t *const *in
             unsigned groups = per_cu * (unsigned)std::max(n_cu, 1) / share;
             if (const char *g = std::getenv("GBRS_TUNING_PERSISTENT_GROUPS"); g && std::atoi(g) > 0) groups = (unsigned)std::atoi(g);
             em->persist_groups = (env && std::atoi(env) != 0) ? std::max(groups, 1u) : 0u;
-            // GBRS_TUNING_NO_PHASE_SPLIT=1: the E-step takes every tile's n_one as 0 - one batch loop, as before the headers
+            // GBRS_TUNING_NO_PHASE_SPLIT=1: the E-step takes every tile's n_one and n_two as 0 - one batch loop, as before the headers
             // had the field (A/B in one build, and the cross-check of the two-loop form in the tests)
             const char *no_split = std::getenv("GBRS_TUNING_NO_PHASE_SPLIT");
             em->lead_mask = (no_split && std::atoi(no_split) != 0) ? 0u : ~0u;
@@ -2064,7 +2064,7 @@ int gbrs_em_info(gbrs_em_t *em, gbrs_em_info_t *info) {
     info->estep_bytes = 8 * em->N + 8 * em->R * 3 + 8 * HL * 2;
     if (em->layout == 1) {
         const TileLayout &tl = em->tl;
-        info->num_device_rows = tl.n_rows + tl.n_folded + tl.n_long;     // every read the layout represents
+        info->num_device_rows = tl.n_rows + tl.n_folded + tl.n_folded_two + tl.n_long;     // every read the layout represents
         info->num_folded_rows = (uint32_t)tl.n_folded;
         info->num_tiles = tl.n_tiles;
         info->num_slots = tl.n_slots;
@@ -2093,6 +2093,13 @@ int gbrs_em_info(gbrs_em_t *em, gbrs_em_info_t *info) {
     info->layout = em->layout;
     info->retained_build_bytes = em->tl.retired_bytes;
     info->num_locus_sets = em->layout == 1 ? em->tl.n_sets : 0;
+    return GBRS_OK;
+}
+
+int gbrs_em_fold_counts(gbrs_em_t *em, uint64_t *one_word_reads, uint64_t *two_word_reads) {
+    if (!em || !one_word_reads || !two_word_reads) return fail(GBRS_ERR_INVALID, "NULL argument");
+    *one_word_reads = em->layout == 1 ? em->tl.n_folded : 0;
+    *two_word_reads = em->layout == 1 ? em->tl.n_folded_two : 0;
     return GBRS_OK;
 }
 

@@ -9,6 +9,9 @@
 //            are ONE field: the number of FURTHER identical reads - same dictionary entry, same mask - the word stands
 //            for (the fold of build_tile_layout's step 5; it adds (1 + count) / den once).  0 everywhere in a layout that
 //            did not fold, so the kernels have no switch for it; 0 in the padding cells of those batches, always.
+//            The same holds for the tile's run of two-word rows (TileHdr::n_two): a row of that run sits on an (even, odd)
+//            lane pair, so its words' pos / rem bits are implied by the lane's parity and BOTH words carry the repeat
+//            count of the row instead - the reads with the same two (locus, mask) pairs it stands for beside itself.
 //   batch  = 64 consecutive words = what one wavefront takes per step; rows never straddle a
 //            batch (zero words pad the tail), so a batch is self-contained.
 //   tile   = a run of batches processed by one workgroup with one locus dictionary of at most
@@ -98,9 +101,23 @@ struct TileHdr {
                            // before) and no haplotype bit, see fill_one_word_cells_kernel.  In these batches a word's pos /
                            // rem bits are a repeat count (the word format above)
     uint32_t dict_base;    // first slot / dictionary entry of the tile
-    uint32_t dict_count;   // D
+    uint32_t dict_n_two;   // D in the low 16 bits, n_two in the high 16 (dict_count(), n_two()).  n_two INVARIANT: every batch with index in [n_one, n_one + n_two) holds only two-word rows on (even, odd)
+                           // lane pairs, or padding pairs, and its words' 2 PB bits are a repeat count, not positions (the B of
+                           // tile_pad_kernel's run of two-word rows when that run starts exactly at batch n_one; 0 otherwise, and
+                           // 0 in every layout that has no n_one or whose kernels do not read counts: weighted, deterministic,
+                           // half-locus view, 16 or a generic number of haplotypes).  A lane pair that ends early carries, lane
+                           // by lane, the dictionary index of the cell above it, no haplotype bit and a count of 0; lane pairs
+                           // that are empty from the top stay all-zero
+    __host__ __device__ uint32_t dict_count() const { return dict_n_two & 0xFFFFu; }
+    __host__ __device__ uint32_t n_two() const { return dict_n_two >> 16; }
+    // (a kernel instance that never meets a layout with n_two - weighted, deterministic, 16 or a generic number of
+    // haplotypes - takes the whole word as D: no mask, the code it had when the word was dict_count alone)
+    template <bool COUNTED> __host__ __device__ uint32_t dict_count_of() const { return COUNTED ? dict_count() : dict_n_two; }
 };
 static_assert(sizeof(TileHdr) == 16, "a tile header is one 16-byte scalar load");
+// the largest dictionary any layout cuts is the LDS theta image at one haplotype
+static_assert(GBRS_LDS_DOUBLES < 65536 && GBRS_LDS_DOUBLES_WEIGHTED < 65536 && GBRS_LDS_DOUBLES_H16 < 65536,
+              "TileHdr::dict_count is 16 bits");
 // a tile's rows of one length that does not divide 64 can pad to just under twice its words: still 16 bits of batches
 static_assert(2 * (GBRS_TILE_CAP / 64) < 65536, "TileHdr::n_batches is 16 bits");
 
@@ -118,6 +135,7 @@ struct TileLayout {
     uint64_t n_rows_in = 0;      // rows with at least one alignment
     uint64_t n_rows = 0;         // rows in the layout (after optional merging / folding), short rows only
     uint64_t n_folded = 0;       // one-word reads without a word of their own: counted by an identical read's word (0: no fold)
+    uint64_t n_folded_two = 0;   // two-word reads without words of their own: counted by an identical read's two words
     uint64_t n_long = 0;         // rows with more than MAX_ROW_WORDS loci
     uint64_t n_tiles = 0, n_batches = 0, n_slots = 0, n_heavy = 0, n_light = 0;
     uint32_t d_max = 0;          // dictionary capacity used when cutting tiles
@@ -184,7 +202,7 @@ int build_tile_layout(TileLayout &out, uint64_t R, uint32_t L, uint32_t H, uint6
                       bool merge_identical_rows, int row_order /* 0 sorted, 1 interleaved, 2 streams */,
                       bool deterministic, hipStream_t stream, unsigned side_by_side = 1 /* handles sharing the device */,
                       bool locus_sets = false, uint32_t dict_cap = 0 /* > 0: at most this many loci per tile dictionary */,
-                      uint32_t view_factor = 1, bool run_words = true /* false: never fold identical one-word reads */);
+                      uint32_t view_factor = 1, bool run_words = true /* false: never fold identical one- or two-word reads */);
 // view_factor = 2 (round 4, 16 haplotypes): the layout is built over HALF-LOCI - locus l's haplotypes 0-7 are "locus" 2l,
 // its haplotypes 8-15 "locus" 2l + 1, L and H passed here are 2 L and 8.  The locus-major vectors (theta, A, lengths:
 // element l * 16 + h) are element for element the half-locus view's (2l + h / 8) * 8 + h % 8, so nothing outside the layout

@@ -424,7 +424,8 @@ __device__ __forceinline__ bool same_loci(const uint32_t *__restrict__ rowstart,
 }
 
 // head[i] = 1 when sorted row i starts a new (merged) row.  merge = 1: identical rows join; merge = 2 (the fold of identical
-// one-word reads, em_layout.h): rows join only when both are exactly one (locus, mask) pair and the pairs are equal
+// one-word reads, em_layout.h): rows join only when both are exactly one (locus, mask) pair and the pairs are equal;
+// merge = 3: the same, and rows that are both exactly two (locus, mask) pairs and equal pair for pair join too
 __global__ void merge_flag_kernel(uint64_t n, int merge, const uint64_t *__restrict__ skey,
                                   const uint32_t *__restrict__ srow, const uint32_t *__restrict__ rowstart,
                                   const uint32_t *__restrict__ ploc, const uint32_t *__restrict__ pmask,
@@ -432,10 +433,14 @@ __global__ void merge_flag_kernel(uint64_t n, int merge, const uint64_t *__restr
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     uint32_t f = 1;
-    if (merge == 2 && i > 0 && skey[i] == skey[i - 1]) {
+    if (merge >= 2 && i > 0 && skey[i] == skey[i - 1]) {
         const uint32_t ra = srow[i - 1], rb = srow[i];
         const uint32_t a = rowstart[ra], b = rowstart[rb];
-        if (rowstart[ra + 1] - a == 1u && rowstart[rb + 1] - b == 1u && ploc[a] == ploc[b] && pmask[a] == pmask[b]) f = 0;
+        const uint32_t na = rowstart[ra + 1] - a, nb = rowstart[rb + 1] - b;
+        if (na == 1u && nb == 1u && ploc[a] == ploc[b] && pmask[a] == pmask[b]) f = 0;
+        if (merge == 3 && na == 2u && nb == 2u && ploc[a] == ploc[b] && pmask[a] == pmask[b] && ploc[a + 1] == ploc[b + 1] &&
+            pmask[a + 1] == pmask[b + 1])
+            f = 0;
     } else if (merge == 1 && i > 0 && skey[i] == skey[i - 1]) {
         const uint32_t ra = srow[i - 1], rb = srow[i];
         if (same_loci(rowstart, ploc, ra, rb)) {
@@ -458,6 +463,19 @@ __global__ void run_head_pos_kernel(uint64_t n, const uint32_t *__restrict__ hea
 __global__ void run_cut_kernel(uint64_t n, uint32_t cap, const uint32_t *__restrict__ hpos, uint32_t *__restrict__ head) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n && ((uint32_t)i - hpos[i]) % cap == 0u) head[i] = 1u;
+}
+
+// the fold's two-word reads that lost their words to a neighbour (after the cut): one atomic per wavefront
+__global__ void folded_two_kernel(uint64_t n, const uint32_t *__restrict__ head, const uint32_t *__restrict__ srow,
+                                  const uint32_t *__restrict__ rowstart, unsigned long long *__restrict__ total) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool mine = false;
+    if (i < n && !head[i]) {
+        const uint32_t r = srow[i];
+        mine = rowstart[r + 1] - rowstart[r] == 2u;
+    }
+    const unsigned long long b = __ballot(mine);
+    if ((threadIdx.x & 63) == 0 && b != 0) atomicAdd(total, (unsigned long long)__popcll(b));
 }
 
 // per sorted row: merged ordinal m = incl[i] - 1; accumulate weights (merge) or the repeat count (fold), record representative
@@ -557,13 +575,14 @@ __global__ void tile_start_kernel(uint64_t m_rows, uint64_t n_tiles, const uint3
 // run at batches 0 .. B-1: whichever batches a wavefront owns, each of its lanes walks a
 // contiguous piece of the sorted rows.
 // n_one[t]: the batches of the tile's run of one-word rows - the rows sort by length, so they are the tile's first
-// (TileHdr::n_one); 0 in the other row orders.
+// (TileHdr::n_one); 0 in the other row orders.  n_two[t]: the batches of the run of two-word rows when it starts exactly at
+// batch n_one[t] (TileHdr::n_two; the caller clears it for the layouts whose kernels do not read counts).
 __global__ void tile_pad_kernel(uint64_t n_tiles, int streams, const uint32_t *__restrict__ tile_row,
                                 const uint32_t *__restrict__ npm, uint32_t *__restrict__ rowpad,
-                                uint32_t *__restrict__ nbatch, uint32_t *__restrict__ n_one) {
+                                uint32_t *__restrict__ nbatch, uint32_t *__restrict__ n_one, uint32_t *__restrict__ n_two) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_tiles) return;
-    uint32_t off = 0, one = 0;
+    uint32_t off = 0, one = 0, two = 0;
     const uint32_t end = tile_row[t + 1];
     uint32_t m = tile_row[t];
     while (m < end) {
@@ -574,6 +593,7 @@ __global__ void tile_pad_kernel(uint64_t n_tiles, int streams, const uint32_t *_
             const uint32_t n = e - m, G = 64u / cnt, B = (n + G - 1) / G;
             off = (off + 63u) & ~63u;
             if (cnt == 1u && off == 0u) one = B;
+            if (cnt == 2u && off == one * 64u) two = B;
             for (uint32_t k = 0; k < n; ++k) rowpad[m + k] = off + (k % B) * 64u + (k / B) * cnt;
             off += B * 64u;
             m = e;
@@ -586,6 +606,7 @@ __global__ void tile_pad_kernel(uint64_t n_tiles, int streams, const uint32_t *_
     }
     nbatch[t] = (off + 63u) >> 6;
     n_one[t] = one;
+    n_two[t] = two;
 }
 
 // Per-tile dictionaries = the distinct loci (and locus sets) of a tile's rows, ascending.  Built from ONE radix sort of
@@ -616,16 +637,19 @@ __global__ void dict_emit_kernel(uint64_t n, const uint64_t *__restrict__ skeys,
 
 __global__ void tile_hdr_kernel(uint64_t n_tiles, uint32_t dcap, uint32_t n_slots, const uint32_t *__restrict__ batch_base,
                                 const uint32_t *__restrict__ nbatch, const uint32_t *__restrict__ n_one,
-                                const uint32_t *__restrict__ dict_base, TileHdr *__restrict__ hdr, BuildFlags *flags) {
+                                const uint32_t *__restrict__ n_two, const uint32_t *__restrict__ dict_base,
+                                TileHdr *__restrict__ hdr, BuildFlags *flags) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_tiles) return;
     const uint32_t db = dict_base[t], d = (t + 1 < n_tiles ? dict_base[t + 1] : n_slots) - db;
     if (d > dcap) flags->dict_overflow = 1;
-    hdr[t] = TileHdr{batch_base[t], (uint16_t)nbatch[t], (uint16_t)n_one[t], db, d};
+    hdr[t] = TileHdr{batch_base[t], (uint16_t)nbatch[t], (uint16_t)n_one[t], db, d | (n_two[t] << 16)};
 }
 
 // one thread per (merged) row: emit its words at the padded position.  repeat (the fold, em_layout.h): a one-word row's
-// pos / rem field - zero otherwise - takes the number of further identical reads the word stands for
+// pos / rem field - zero otherwise - takes the number of further identical reads the word stands for.  In a tile with a
+// counted run of two-word rows (TileHdr::n_two) both words of such a row carry the row's count in that field instead of
+// their positions (0 without a fold): the lane's parity says which word of the pair it is
 __global__ void emit_words_kernel(uint64_t m_rows, uint32_t H, const uint32_t *__restrict__ tincl,
                                   const TileHdr *__restrict__ hdr, const uint32_t *__restrict__ dict,
                                   const uint32_t *__restrict__ hrow, const uint32_t *__restrict__ rowstart,
@@ -644,13 +668,14 @@ __global__ void emit_words_kernel(uint64_t m_rows, uint32_t H, const uint32_t *_
     const uint32_t *d = dict + th.dict_base;
     for (uint32_t j = 0; j < cnt; ++j) {
         const uint32_t l = ploc[p0 + j];
-        uint32_t lo = 0, hi = th.dict_count;          // lower_bound; l is present by construction
+        uint32_t lo = 0, hi = th.dict_count();          // lower_bound; l is present by construction
         while (lo < hi) {
             const uint32_t mid = (lo + hi) >> 1;
             if (d[mid] < l) lo = mid + 1; else hi = mid;
         }
         uint32_t w = pmask[p0 + j] | (j << H) | ((cnt - 1 - j) << (H + PB)) | (lo << (H + 2 * PB));
-        if (repeat && cnt == 1u) w |= (repeat[m] - 1u) << H;
+        if (cnt == 2u && th.n_two() != 0u) w = pmask[p0 + j] | (lo << (H + 2 * PB));
+        if (repeat && (cnt == 1u || (cnt == 2u && th.n_two() != 0u))) w |= (repeat[m] - 1u) << H;
         words[base + j] = w;
         if (word_weight) word_weight[base + j] = row_weight[m];
         if (word_row) word_row[base + j] = row_orig[r];          // resampling handle: the file row the word's weight comes from
@@ -669,14 +694,18 @@ __global__ void fill_one_word_cells_kernel(uint64_t n_tiles, uint32_t H, const T
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_tiles * 64) return;
     const TileHdr th = hdr[i >> 6];
-    const uint32_t B = th.n_one;
-    if (B < 2) return;
-    uint32_t *w = words + (uint64_t)th.batch_base * 64 + (i & 63u);
-    if (w[0] == 0u || w[(uint64_t)(B - 1) * 64] != 0u) return;        // an empty lane / a full one
-    uint32_t b = B - 1;
-    while (w[(uint64_t)(b - 1) * 64] == 0u) --b;                      // (ends at batch 0 at the latest: its word is not zero)
-    const uint32_t fill = w[(uint64_t)(b - 1) * 64] & ~((1u << (H + 2 * pos_bits(H))) - 1u);
-    for (; b < B; ++b) w[(uint64_t)b * 64] = fill;
+    // (the run of two-word rows, TileHdr::n_two, is laid out the same way on lane PAIRS - the two lanes of the pair that
+    // ends early end at the same batch, so each of them fills its own cells exactly as a lane of the one-word run does)
+    for (int run = 0; run < 2; ++run) {
+        const uint32_t B = run == 0 ? th.n_one : th.n_two();
+        if (B < 2) continue;
+        uint32_t *w = words + ((uint64_t)th.batch_base + (run == 0 ? 0u : th.n_one)) * 64 + (i & 63u);
+        if (w[0] == 0u || w[(uint64_t)(B - 1) * 64] != 0u) continue;      // an empty lane / a full one
+        uint32_t b = B - 1;
+        while (w[(uint64_t)(b - 1) * 64] == 0u) --b;                      // (ends at batch 0 at the latest: its word is not zero)
+        const uint32_t fill = w[(uint64_t)(b - 1) * 64] & ~((1u << (H + 2 * pos_bits(H))) - 1u);
+        for (; b < B; ++b) w[(uint64_t)b * 64] = fill;
+    }
 }
 
 __global__ void iota_kernel(uint64_t n, uint32_t *__restrict__ v) {
@@ -1225,7 +1254,7 @@ int build_tile_layout(TileLayout &out, uint64_t R, uint32_t L_in, uint32_t H, ui
         return fail(GBRS_ERR_UNSUPPORTED, "the deterministic tile layout has no room for a row's loci at H = %u", H);
     const uint32_t dseg = out.d_max - max_row_words(H);
     out.weighted = merge || count != nullptr;
-    out.n_pairs = out.n_rows = out.n_rows_in = out.n_long = out.n_tiles = out.n_batches = out.n_slots = out.n_folded = 0;
+    out.n_pairs = out.n_rows = out.n_rows_in = out.n_long = out.n_tiles = out.n_batches = out.n_slots = out.n_folded = out.n_folded_two = 0;
     GBRS_TRY(out.slot_ptr.alloc((size_t)L + 1));
     GBRS_HIP_CHECK(hipMemsetAsync(out.slot_ptr.p, 0, out.slot_ptr.bytes(), s));
     GBRS_TRY(out.locus_class.alloc(L));
@@ -1488,11 +1517,18 @@ int build_tile_layout(TileLayout &out, uint64_t R, uint32_t L_in, uint32_t H, ui
     // 5. optional merge of identical adjacent rows + weights - or the fold of identical one-word reads (em_layout.h): the
     // reads of one (dictionary entry, mask) class that the sort left next to each other keep one row with a repeat count,
     // cut every FOLD_CAP rows.  The fold exists where the E-step kernels read the count: the leading one-word batches of the
-    // stream order's unweighted tiles (TileHdr::n_one) of the haplotype counts with a kernel instance of their own.
-    bool fold = run_words && streams && !out.weighted && !deterministic && view_factor == 1 &&
-                (H == 1 || H == 2 || H == 4 || H == 8);
+    // stream order's unweighted tiles (TileHdr::n_one) of the haplotype counts with a kernel instance of their own.  Reads
+    // of exactly two words fold the same way (fold_mode 3): their run of a tile follows its one-word batches on lane pairs
+    // (TileHdr::n_two), where the lane's parity stands for a word's position and both words carry the row's count.
+    // GBRS_TUNING_RUN_WORDS: 0 no fold, 1 the one-word fold alone, 2 both folds - forced; unset: the rule below.
+    const bool counted_pairs = streams && !out.weighted && !deterministic && view_factor == 1 &&
+                               (H == 1 || H == 2 || H == 4 || H == 8);       // the kernels that read TileHdr::n_two
+    bool fold = run_words && counted_pairs;
     const char *fold_env = std::getenv("GBRS_TUNING_RUN_WORDS");
     if (fold_env && std::atoi(fold_env) == 0) fold = false;
+    int fold_mode = (fold_env && std::atoi(fold_env) == 1) ? 2 : 3;          // merge_flag_kernel's mode: 3 both folds, 2 one-word
+    DevBuf<unsigned long long> two_total;
+    unsigned long long folded_two = 0;
     const uint32_t FOLD_CAP = 1u << (2 * pos_bits((int)H));
     DevBuf<uint32_t> head, hincl, hrow, repeat;
     uint64_t M = n_short;
@@ -1500,7 +1536,7 @@ int build_tile_layout(TileLayout &out, uint64_t R, uint32_t L_in, uint32_t H, ui
         GBRS_TRY(head.alloc(n_short)); GBRS_TRY(hincl.alloc(n_short));
         uint32_t m32 = 0;
         for (;;) {
-            hipLaunchKernelGGL(merge_flag_kernel, dim3(grid_for(n_short)), dim3(256), 0, s, n_short, fold ? 2 : (merge ? 1 : 0),
+            hipLaunchKernelGGL(merge_flag_kernel, dim3(grid_for(n_short)), dim3(256), 0, s, n_short, fold ? fold_mode : (merge ? 1 : 0),
                                skey.p, srow.p, rowstart.p, ploc.p, pmask.p, head.p);
             if (fold) {
                 DevBuf<uint32_t> hpos;
@@ -1517,18 +1553,30 @@ int build_tile_layout(TileLayout &out, uint64_t R, uint32_t L_in, uint32_t H, ui
             GBRS_HIP_CHECK(hipMemcpyAsync(&m32, hincl.p + n_short - 1, 4, hipMemcpyDeviceToHost, s));
             GBRS_HIP_CHECK(hipStreamSynchronize(s));
             if (!fold) break;
-            // Worth it?  The fold pays by the words it takes away, and a launch still wants a tile of TILE_WORDS words for
-            // every resident workgroup place of the chip (the places of the tile-size rule in step 7): a sample smaller
-            // than that is launch-bound and keeps one word per read.  GBRS_TUNING_RUN_WORDS=1 / 0 forces the choice.
-            const uint64_t words_in = out.n_pairs - hf.long_pairs, folded = n_short - m32, words_left = words_in - folded;
+            folded_two = 0;
+            if (fold_mode == 3) {
+                if (!two_total.p) GBRS_TRY(two_total.alloc(1));
+                GBRS_HIP_CHECK(hipMemsetAsync(two_total.p, 0, 8, s));
+                hipLaunchKernelGGL(folded_two_kernel, dim3(grid_for(n_short)), dim3(256), 0, s, n_short, head.p, srow.p, rowstart.p,
+                                   two_total.p);
+                GBRS_HIP_CHECK(hipMemcpyAsync(&folded_two, two_total.p, 8, hipMemcpyDeviceToHost, s));
+                GBRS_HIP_CHECK(hipStreamSynchronize(s));
+            }
+            // Worth it?  The fold pays by the words it takes away - one for a one-word read, two for a two-word read - and a
+            // launch still wants a tile of TILE_WORDS words for every resident workgroup place of the chip (the places of the
+            // tile-size rule in step 7): a sample smaller than that is launch-bound and keeps one word per read (both folds are
+            // tried first, then the one-word fold alone).  GBRS_TUNING_RUN_WORDS=2 / 1 / 0 forces the choice.
+            const uint64_t words_in = out.n_pairs - hf.long_pairs, folded_rows = n_short - m32, folded = folded_rows + folded_two,
+                           words_left = words_in - folded;
             int dev = 0, n_cu = 0;
             GBRS_HIP_CHECK(hipGetDevice(&dev));
             GBRS_HIP_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
             const uint64_t places = (uint64_t)TILE_ROUNDS_MIN * 3u * (uint64_t)std::max(n_cu, 1);
             bool take = folded * 100 >= words_in * 15 && words_left * side_by_side / places >= (uint64_t)TILE_WORDS;
             if (fold_env) take = true;             // (0 was handled above)
-            if (take) { out.n_folded = folded; break; }
-            fold = false;                          // the flags again, one row per read
+            if (take) { out.n_folded = folded_rows - folded_two; out.n_folded_two = folded_two; break; }
+            if (fold_mode == 3) fold_mode = 2;     // the flags again: the one-word fold alone,
+            else fold = false;                     // then one row per read
         }
         M = m32;
         GBRS_TRY(hrow.alloc(M));
@@ -1662,12 +1710,13 @@ int build_tile_layout(TileLayout &out, uint64_t R, uint32_t L_in, uint32_t H, ui
     tflag.release();
     stg.mark("7b row order");
     // 8. padding so that no row straddles a batch, batch offsets
-    DevBuf<uint32_t> rowpad, nbatch, n_one, batch_base;
-    GBRS_TRY(rowpad.alloc(M)); GBRS_TRY(nbatch.alloc(T)); GBRS_TRY(n_one.alloc(T)); GBRS_TRY(batch_base.alloc(T));
+    DevBuf<uint32_t> rowpad, nbatch, n_one, n_two, batch_base;
+    GBRS_TRY(rowpad.alloc(M)); GBRS_TRY(nbatch.alloc(T)); GBRS_TRY(n_one.alloc(T)); GBRS_TRY(n_two.alloc(T)); GBRS_TRY(batch_base.alloc(T));
     hipLaunchKernelGGL(tile_pad_kernel, dim3(grid_for(T, 64)), dim3(64), 0, s, T, streams ? 1 : 0, tile_row.p, npm.p, rowpad.p,
-                       nbatch.p, n_one.p);
+                       nbatch.p, n_one.p, n_two.p);
     // (the weighted kernels do not split their batch loop: their headers say nothing about the leading batches)
     if (out.weighted) GBRS_HIP_CHECK(hipMemsetAsync(n_one.p, 0, T * 4, s));
+    if (!counted_pairs) GBRS_HIP_CHECK(hipMemsetAsync(n_two.p, 0, T * 4, s));
     GBRS_TRY(exclusive_scan(sc, nbatch.p, batch_base.p, T, s));
     uint32_t NB = 0;
     GBRS_TRY(fetch_last_plus(batch_base.p, nbatch.p, T, NB, s));
@@ -1695,7 +1744,7 @@ int build_tile_layout(TileLayout &out, uint64_t R, uint32_t L_in, uint32_t H, ui
         GBRS_TRY(out.dict.alloc(std::max<uint32_t>(NS, 1)));
         hipLaunchKernelGGL(dict_emit_kernel, dim3(grid_for(W)), dim3(256), 0, s, (uint64_t)W, dkey2.p, dflag.p, dpos.p, out.dict.p,
                            dict_base.p);
-        hipLaunchKernelGGL(tile_hdr_kernel, dim3(grid_for(T)), dim3(256), 0, s, T, dcap, NS, batch_base.p, nbatch.p, n_one.p,
+        hipLaunchKernelGGL(tile_hdr_kernel, dim3(grid_for(T)), dim3(256), 0, s, T, dcap, NS, batch_base.p, nbatch.p, n_one.p, n_two.p,
                            dict_base.p, out.tiles.p, d_flags.p);
         GBRS_TRY(read_flags());
         if (hf.dict_overflow) return fail(GBRS_ERR_INVALID, "internal error: a tile dictionary overflowed its capacity");
@@ -1721,7 +1770,7 @@ int build_tile_layout(TileLayout &out, uint64_t R, uint32_t L_in, uint32_t H, ui
     if (streams && !out.weighted)
         hipLaunchKernelGGL(fill_one_word_cells_kernel, dim3(grid_for(T * 64)), dim3(256), 0, s, T, H, out.tiles.p, out.words.p);
     GBRS_HIP_CHECK(hipStreamSynchronize(s));
-    dict_base.release(); batch_base.release(); nbatch.release(); n_one.release();
+    dict_base.release(); batch_base.release(); nbatch.release(); n_one.release(); n_two.release();
     rowpad.release(); tincl.release(); npm.release(); wordoff.release(); tile_row.release();
     hrow.release(); rowstart.release(); ploc.release(); pmask.release(); row_orig.release(); repeat.release();
     out.row_weight.release();

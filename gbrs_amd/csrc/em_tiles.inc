@@ -24,6 +24,10 @@
 // em_layout.h; 0 everywhere in a layout that did not fold, and 0 in padding words).  Such a word adds v = (1 + count) / den.
 // Every kernel instance that can meet an unweighted tile of 1, 2, 4 or 8 haplotypes reads those batches that way: the LEAD
 // form of tile_batches always, the general form when its caller says `count_form` (wave-uniform: the batch index).
+// The batches behind them, index in [n_one, n_one + TileHdr::n_two), hold two-word rows on (even, odd) lane pairs only (or
+// padding pairs): the lane's parity is the word's position, the 2 PB bits of BOTH words are the row's repeat count, and
+// den = s + s of the partner lane with no vote at all.  The LEAD form takes them under its wave-uniform `pair` argument,
+// the general form under count_form = 2.
 
 #ifndef GBRS_ESTEP_WAVES16
 #define GBRS_ESTEP_WAVES16 4          // the same for more than 8 haplotypes
@@ -209,8 +213,11 @@ __device__ __forceinline__ void tile_batches(const uint32_t (&w)[UB], const doub
                                              const double *__restrict__ s_theta, double *__restrict__ my_acc,
                                              LaneAcc<HC> &st, const int (&zlo)[32], const double2 *__restrict__ s_ftab,
                                              uint32_t misfit_bits, uint32_t relax_zero_weight = 0u,
-                                             bool count_form = false /* general form: a batch below TileHdr::n_one */) {
+                                             int count_form = 0 /* general form: 1 a batch below TileHdr::n_one, 2 a batch of
+                                                                   the counted two-word run behind it; wave-uniform */,
+                                             bool pair = false /* LEAD form: a batch of the counted two-word run; wave-uniform */) {
     constexpr bool COUNTS = HT > 0 && HT <= 8 && !WEIGHTED && !DET && UB == 1;     // the instances that meet count fields
+    constexpr bool PAIRS = COUNTS && !ONEWORD;                                     // ... and counted two-word runs
     constexpr bool ZLO = estep_uses_zlo(UB);
     constexpr bool FTAB = estep_uses_ftab(UB, HT);
     constexpr bool TREG = estep_theta_regs(UB, HT, DET) && HC >= 8;
@@ -223,7 +230,7 @@ __device__ __forceinline__ void tile_batches(const uint32_t (&w)[UB], const doub
     (void)f8;
     (void)f16;
     // a counted batch's pos / rem bits are a repeat count (read where v is made): the row-length logic sees them cleared
-    const uint32_t count_bits = (COUNTS && !LEAD && count_form) ? ((1u << (2 * PB)) - 1u) << H : 0u;     // wave-uniform
+    const uint32_t count_bits = (COUNTS && !LEAD && count_form != 0) ? ((1u << (2 * PB)) - 1u) << H : 0u;     // wave-uniform
 #pragma unroll
     for (int u = 0; u < UB; ++u) {
         mask[u] = w[u] & hmask;
@@ -342,6 +349,12 @@ __device__ __forceinline__ void tile_batches(const uint32_t (&w)[UB], const doub
     // (pos and rem are adjacent bit fields of the word: one AND finds a row of more than one word)
     const uint32_t fields = (pmask | (pmask << PB)) << H;
     const uint32_t multi = (UB == 1 ? w[0] : (w[0] | w[UB - 1])) & fields & ~count_bits;
+    if (PAIRS && (LEAD ? pair : count_form == 2)) {
+        // a counted batch of two-word rows: every lane's row total is its s plus its partner's, padding pairs included
+        // (0 + 0, which the reciprocal's guard keeps finite and the 0.0 factors of the clear haplotype bits erase)
+#pragma unroll
+        for (int u = 0; u < UB; ++u) den[u] = s[u] + quad_swap_pairs(s[u]);
+    } else
 #if defined(GBRS_ABLATE_ROWSUM)
     if (true) {
 #else
@@ -405,7 +418,7 @@ __device__ __forceinline__ void tile_batches(const uint32_t (&w)[UB], const doub
         if constexpr (COUNTS) {
             // the word and the further reads it stands for: one field extract, one convert, one FMA - the same arithmetic in
             // both forms (a general-form batch past n_one skips it: its fields are positions)
-            if (LEAD || count_form) r = fma(r, (double)((w[u] >> H) & ((1u << (2 * PB)) - 1u)), r);
+            if (LEAD || count_form != 0) r = fma(r, (double)((w[u] >> H) & ((1u << (2 * PB)) - 1u)), r);
         }
         v[u] = r;
     }
@@ -576,7 +589,12 @@ tile_estep_kernel(uint32_t Hrt, const TileHdr *__restrict__ tiles, const uint32_
     // those batches once.  The switch falls on a ring boundary; the lanes' state carries over, and the arithmetic and
     // its association are the single loop's.
     constexpr bool SPLIT = HT > 0 && HT <= 8 && !WEIGHTED && !DET;
-    const uint32_t n_lead = SPLIT ? ((uint32_t)th.n_one & lead_mask) : 0u;
+    // The counted run of two-word rows behind them (TileHdr::n_two) goes through the same first loop: a batch at or past
+    // n_one takes the pair form of the row sum under a wave-uniform scalar, so a ring that holds the last one-word batches
+    // and the first two-word ones needs no loop of its own (three copies of the batch loop - one-word, pair, general -
+    // would leave that ring, and the registers of a third copy, to the general form).
+    const uint32_t n_one = SPLIT ? (uint32_t)th.n_one : 0u;
+    const uint32_t n_lead = SPLIT ? ((n_one + (ONEWORD ? 0u : th.n_two())) & lead_mask) : 0u;
     uint32_t bm = b0;
     if (SPLIT && n_lead > b0) bm = b0 + ((min(b1, n_lead) - b0) / PD) * PD;
     // The ring is filled through a buffer descriptor of this wavefront's run [tile base, batch b1): the address is
@@ -602,7 +620,7 @@ tile_estep_kernel(uint32_t Hrt, const TileHdr *__restrict__ tiles, const uint32_
         ring[u] = load_word(u);
         if (WEIGHTED) wring[u] = load_weight(u);
     }
-    const uint32_t DH = th.dict_count * H;
+    const uint32_t DH = th.template dict_count_of<SPLIT>() * H;
     const uint32_t stride = DH | 1u;                       // odd: copies fall on different banks
     uint32_t K = LDS_ACC_DOUBLES / stride;
     K = K >= 64 ? 64u : (1u << (31 - __clz((int)K)));       // power of two, 1..64
@@ -708,7 +726,8 @@ tile_estep_kernel(uint32_t Hrt, const TileHdr *__restrict__ tiles, const uint32_
                 const uint32_t w[1] = {ring[tt]};
                 const double wt[1] = {1.0};
                 ring[tt] = load_word(PD + tt);                         // refill PD batches ahead
-                tile_batches<HT, false, HC, false, 1, ONEWORD, true>(w, wt, H, PB, lane, s_theta, my_acc, st, zlo, s_ftab, 0u);
+                tile_batches<HT, false, HC, false, 1, ONEWORD, true>(w, wt, H, PB, lane, s_theta, my_acc, st, zlo, s_ftab, 0u, 0u, 0,
+                                                                     !ONEWORD && b + tt >= n_one);
             }
             voff += PD * 256;
             asm volatile("" : "+v"(voff));
@@ -741,10 +760,10 @@ tile_estep_kernel(uint32_t Hrt, const TileHdr *__restrict__ tiles, const uint32_
                 ring[slot] = load_word(PD + slot);                     // refill PD batches ahead
                 if (WEIGHTED) wring[slot] = load_weight(PD + slot);
             }
-            // (a leading one-word batch that this loop takes - the last 0-3 of a wavefront's share, or every one of them
-            // without the split - carries repeat counts: the header's n_one itself, whatever lead_mask says)
+            // (a counted batch that this loop takes - the last 0-3 of a wavefront's share of them, or every one of them
+            // without the split - carries repeat counts: the header's n_one and n_two themselves, whatever lead_mask says)
             if (b + tt * UB < b1) tile_batches<HT, WEIGHTED, HC, DET, UB, ONEWORD>(w, wt, H, PB, lane, s_theta, my_acc, st, zlo, s_ftab, misfit_bits, WEIGHTED ? sets.relax_zero_weight : 0u,
-                                                                                   SPLIT && b + tt * UB < (uint32_t)th.n_one);
+                                                                                   !SPLIT ? 0 : (b + tt * UB < n_one ? 1 : (!ONEWORD && b + tt * UB < n_one + th.n_two() ? 2 : 0)));
         }
         voff += PD * 256;
         asm volatile("" : "+v"(voff));      // keep it one register: the slots stay immediates of the loads
@@ -935,7 +954,7 @@ tile_estep_persistent_kernel(uint32_t Hrt, const TileHdr *__restrict__ tiles, co
     for (uint32_t i = threadIdx.x; i < (uint32_t)LDS_ACC_DOUBLES; i += TILE_THREADS) s_acc[i] = 0.0;
     {
         // theta of the first tile: nothing to hide it behind
-        const uint32_t DH0 = th.dict_count * H;
+        const uint32_t DH0 = th.template dict_count_of<(PF && !WEIGHTED)>() * H;
         for (uint32_t i = threadIdx.x; i < DH0; i += TILE_THREADS) {
             const uint32_t j = i / H, h = i - j * H;
             const uint32_t e = dict[th.dict_base + j], e2 = sets.set_ptr ? sets.dict_b[th.dict_base + j] : 0u;
@@ -972,7 +991,7 @@ tile_estep_persistent_kernel(uint32_t Hrt, const TileHdr *__restrict__ tiles, co
         const uint32_t tn = rn * G + ((rn & 1u) ? G - 1u - me : me);
         const bool has_next = tn < n_tiles;                                   // the same for the whole workgroup
         const TileHdr thn = tiles[has_next ? tn : t];                          // scalar load, back long before it is used
-        const uint32_t DH = th.dict_count * H;
+        const uint32_t DH = th.template dict_count_of<(PF && !WEIGHTED)>() * H;
         const uint32_t stride = DH | 1u;
         uint32_t K = LDS_ACC_DOUBLES / stride;
         K = K >= 64 ? 64u : (1u << (31 - __clz((int)K)));
@@ -988,7 +1007,7 @@ tile_estep_persistent_kernel(uint32_t Hrt, const TileHdr *__restrict__ tiles, co
             GBRS_OPAQUE_TID(tix);
             const uint32_t myj = tix / (uint32_t)H, myh = tix - myj * (uint32_t)H;
             if (pf_phase == 0) {
-                const uint32_t at = thn.dict_base + min(myj, thn.dict_count - 1u);
+                const uint32_t at = thn.dict_base + min(myj, thn.template dict_count_of<(PF && !WEIGHTED)>() - 1u);
                 pf_e = dict[at];
                 pf_e2 = sets.set_ptr ? sets.dict_b[at] : 0u;
                 pf_phase = 1;
@@ -1008,7 +1027,7 @@ tile_estep_persistent_kernel(uint32_t Hrt, const TileHdr *__restrict__ tiles, co
                     pf_t0 = big ? -1.0 : (pair ? pf_t0 + pf_t1 : pf_t0);        // (theta is never negative)
                 }
                 if constexpr (EPF) {
-                    const uint32_t at = th.dict_base + min(myj, th.dict_count - 1u);
+                    const uint32_t at = th.dict_base + min(myj, th.template dict_count_of<(PF && !WEIGHTED)>() - 1u);
                     ep_d = slot_dest[at];
                     ep_d2 = sets.set_ptr ? sets.dest_b[at] : 0u;
                 }
@@ -1017,7 +1036,7 @@ tile_estep_persistent_kernel(uint32_t Hrt, const TileHdr *__restrict__ tiles, co
         };
         GBRS_DIAG_PSTAMP(t, 0);
 #if defined(GBRS_DIAG_TILE_TIMES)
-        if (g_tile_stamps && threadIdx.x == 0) g_tile_stamps[(size_t)t * 8 + 7] = ((unsigned long long)th.dict_count << 32) | th.n_batches;
+        if (g_tile_stamps && threadIdx.x == 0) g_tile_stamps[(size_t)t * 8 + 7] = ((unsigned long long)th.template dict_count_of<(PF && !WEIGHTED)>() << 32) | th.n_batches;
 #endif
         for (uint32_t b = b0; b < b1; b += PD) {
             if constexpr (PF) {
@@ -1035,9 +1054,10 @@ tile_estep_persistent_kernel(uint32_t Hrt, const TileHdr *__restrict__ tiles, co
                     ring[slot] = load_word(PD + slot);
                     if (WEIGHTED) wring[slot] = load_weight(PD + slot);
                 }
-                // (one loop here: a batch below the header's n_one is read in count form, see the word decode above)
+                // (one loop here: a batch below the header's n_one, or of the counted two-word run behind it, is read in count
+                // form, see the word decode above)
                 if (b + tt * UB < b1) tile_batches<HT, WEIGHTED, HC, false, UB, ONEWORD>(w, wt, H, PB, lane, s_theta, my_acc, st, zlo, s_ftab, misfit_bits, WEIGHTED ? sets.relax_zero_weight : 0u,
-                                                                                         PF && !WEIGHTED && b + tt * UB < (uint32_t)th.n_one);
+                                                                                         !(PF && !WEIGHTED) ? 0 : (b + tt * UB < (uint32_t)th.n_one ? 1 : (!ONEWORD && b + tt * UB < (uint32_t)th.n_one + th.n_two() ? 2 : 0)));
             }
             voff += PD * 256;
             asm volatile("" : "+v"(voff));
@@ -1100,7 +1120,7 @@ tile_estep_persistent_kernel(uint32_t Hrt, const TileHdr *__restrict__ tiles, co
         if (!has_next) break;
         // ---- theta of the next tile into LDS: my element from the registers, the rest (tiles with more than TILE_THREADS
         // elements, larger sets) gathered now
-        const uint32_t DHn = thn.dict_count * H;
+        const uint32_t DHn = thn.template dict_count_of<(PF && !WEIGHTED)>() * H;
         GBRS_OPAQUE_TID(tix_n);
         bool from_regs = false;
         if constexpr (PF) {

@@ -129,6 +129,12 @@ class EmEngine:
         _lib.check(_lib.load().gbrs_em_info(self._h, C.byref(inf)))
         return inf
 
+    def fold_counts(self):
+        """(one-word reads, two-word reads) that an identical read's words count (gbrs_em_fold_counts)."""
+        one, two = C.c_uint64(0), C.c_uint64(0)
+        _lib.check(_lib.load().gbrs_em_fold_counts(self._h, C.byref(one), C.byref(two)))
+        return int(one.value), int(two.value)
+
     # ---- multi-GPU building blocks -----------------------------------------------------------
     def _partial(self, fn):
         p = C.c_void_p()

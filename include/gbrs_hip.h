@@ -128,7 +128,8 @@ typedef struct gbrs_em gbrs_em_t;
 #define GBRS_EM_RESAMPLE 4096u
 /* Run words off.  By default reads that are ONE word in the tiles (one locus, or one locus set) and identical - same entry,
  * same haplotype mask - may share a word: each of them adds the same 1/den to its locus in every iteration, so the
- * word carries how many further reads it stands for (up to 1,023 at <= 8 haplotypes) and adds (1 + n)/den once.  Nothing
+ * word carries how many further reads it stands for (up to 1,023 at <= 8 haplotypes) and adds (1 + n)/den once.  Reads of
+ * exactly TWO words that are identical pair for pair share their two words the same way (gbrs_em_fold_counts).  Nothing
  * becomes weighted and every read is counted; the result agrees with the one-word-per-read form up to the association of
  * the sums.  The layout takes the fold for unweighted stream-order handles of 1, 2, 4 or 8 haplotypes (never with `count`,
  * GBRS_EM_MERGE_IDENTICAL_ROWS, GBRS_EM_RESAMPLE or GBRS_EM_DETERMINISTIC) when it removes >= 15 % of the words and the words
@@ -334,7 +335,8 @@ typedef struct gbrs_em_info {
     uint32_t num_loci, num_haps;
     uint32_t layout;            /* 0 = csc-direct, 1 = packed row tiles                     */
     uint32_t num_folded_rows;   /* layout 1: one-word reads counted by an identical read's word instead of a word of
-                                   their own; 0: the fold was not taken (GBRS_EM_NO_RUN_WORDS).  The slot was
+                                   their own (two-word reads: gbrs_em_fold_counts); 0: the fold was not taken
+                                   (GBRS_EM_NO_RUN_WORDS).  The slot was
                                    `reserved` (always 0): the struct keeps its size and offsets; the tile layout
                                    holds fewer than 2^32 entries, so 32 bits do                        */
     uint64_t num_tiles;         /* layout 1: workgroup tiles                                */
@@ -350,6 +352,10 @@ typedef struct gbrs_em_info {
     uint64_t num_locus_sets;       /* distinct locus sets of the tile layout (GBRS_EM_NO_LOCUS_SETS: 0) */
 } gbrs_em_info_t;
 int gbrs_em_info(gbrs_em_t *em, gbrs_em_info_t *info);
+/* Reads without words of their own in the tile layout, by kind: one_word_reads is gbrs_em_info.num_folded_rows (reads of one
+ * locus or one locus set counted by an identical read's word); two_word_reads are reads of exactly two (locus, mask) pairs
+ * counted by an identical read's two words.  Both 0 when the fold was not taken and for the CSC layout. */
+int gbrs_em_fold_counts(gbrs_em_t *em, uint64_t *one_word_reads, uint64_t *two_word_reads);
 
 /* `--report-alignment-counts` (emase/AlignmentPropertyMatrix.py:389-459), stand-alone (the
  * reference reloads the alignment file for it, gbrs/emase_utils.py:318-331).  Inputs as for

@@ -31,7 +31,7 @@ EXPORTS = [
     "gbrs_compress_create", "gbrs_compress_get", "gbrs_compress_destroy",
     "gbrs_bam_open", "gbrs_bam_references", "gbrs_bam_set_reference_map", "gbrs_bam_convert", "gbrs_bam_get",
     "gbrs_bam_scan_records", "gbrs_bam_destroy",
-    "gbrs_ecset_create", "gbrs_ecset_add_bam", "gbrs_ecset_sizes", "gbrs_ecset_get", "gbrs_ecset_destroy",
+    "gbrs_ecset_create", "gbrs_ecset_add_bam", "gbrs_ecset_add_bam_pair", "gbrs_ecset_sizes", "gbrs_ecset_get", "gbrs_ecset_destroy",
     "gbrs_matops_create", "gbrs_matops_intersect", "gbrs_matops_append_rows", "gbrs_matops_keep_unique_rows",
     "gbrs_matops_mask_columns", "gbrs_matops_sizes", "gbrs_matops_get", "gbrs_matops_destroy",
     "gbrs_matops_shared_counts", "gbrs_matops_shared_counts_get", "gbrs_matops_shared_counts_info",
@@ -178,6 +178,7 @@ def load():
         "gbrs_bam_get": [vp, pp, pp, vp],
         "gbrs_ecset_create": [u32, u32, i32, C.POINTER(vp)],
         "gbrs_ecset_add_bam": [vp, vp, C.POINTER(u64), vp],
+        "gbrs_ecset_add_bam_pair": [vp, vp, vp, C.POINTER(u64), vp],
         "gbrs_ecset_sizes": [vp, C.POINTER(u64), C.POINTER(u64), vp],
         "gbrs_ecset_get": [vp, pp, pp, vp],
         "gbrs_ecset_destroy": [vp],

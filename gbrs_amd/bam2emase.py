@@ -4,7 +4,8 @@ files.  The BAM file is inflated and parsed by the library's host reader (gbrs_b
 the read names and building the per-haplotype CSC matrices runs in HIP (gbrs_bam_convert / bam.hip).
 
 `gbrs bam2ec` (extension) goes from one or more BAM files straight to the file `gbrs compress` writes: the
-read-level matrices stay on the device and the read names are never gathered (gbrs_ecset_* / bam.hip)."""
+read-level matrices stay on the device and the read names are never gathered (gbrs_ecset_* / bam.hip).  With
+`--mate-file` the two ends of a paired-end sample are intersected there as well (gbrs_ecset_add_bam_pair)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -20,6 +21,7 @@ logger = logging.getLogger('gbrs')
 
 _UNUSABLE = 0xFFFFFFFF
 _NOT_TWO_PARTS, _UNKNOWN_HAPLOTYPE, _UNKNOWN_LOCUS = 1, 2, 3
+_INCOMPATIBLE = "The read ID's are not compatible."      # emase/emase_utils.py:262-264
 
 
 def get_names(id_file):
@@ -141,6 +143,20 @@ def bam_to_matrix(alignment_file, haplotypes, loci, delim='_', device=0, stage_t
                                    haplotype_names=hname, locus_names=loci, read_names=rname)
 
 
+def _download_classes(lib, e, hname, loci):
+    """The classes of a gbrs_ecset as an AlignmentPropertyMatrix with counts."""
+    L, H = len(loci), len(hname)
+    R, G = C.c_uint64(0), C.c_uint64(0)
+    nnz = np.zeros(H, dtype=np.uint64)
+    _lib.check(lib.gbrs_ecset_sizes(e, C.byref(R), C.byref(G), _lib.ptr(nnz)))
+    ip = [np.zeros(L + 1, dtype=np.uint32) for _ in range(H)]
+    ix = [np.zeros(int(nnz[k]), dtype=np.uint32) for k in range(H)]
+    count = np.zeros(int(G.value), dtype=np.float64)
+    _lib.check(lib.gbrs_ecset_get(e, _lib.ptr_table(ip), _lib.ptr_table(ix), _lib.ptr(count) if G.value else None))
+    return AlignmentPropertyMatrix(shape=(L, H, max(int(G.value), 1)), indptr=ip, indices=ix,
+                                   count=count if G.value else np.zeros(1), haplotype_names=hname, locus_names=loci)
+
+
 def bam_to_classes(alignment_files, haplotypes, loci, delim='_', device=0, stage_times=None, threads=0):
     """BAM file(s) -> AlignmentPropertyMatrix of equivalence classes with counts: what bam_to_matrix on every file
     followed by compress over the files' reads, one file after the other, gives (the same name in two files is
@@ -164,19 +180,58 @@ def bam_to_classes(alignment_files, haplotypes, loci, delim='_', device=0, stage
                 total += secs
             if n.value == 0:
                 raise RuntimeError(f'{path} holds no alignment records.')
-        R, G = C.c_uint64(0), C.c_uint64(0)
-        nnz = np.zeros(H, dtype=np.uint64)
-        _lib.check(lib.gbrs_ecset_sizes(e, C.byref(R), C.byref(G), _lib.ptr(nnz)))
-        ip = [np.zeros(L + 1, dtype=np.uint32) for _ in range(H)]
-        ix = [np.zeros(int(nnz[k]), dtype=np.uint32) for k in range(H)]
-        count = np.zeros(int(G.value), dtype=np.float64)
-        _lib.check(lib.gbrs_ecset_get(e, _lib.ptr_table(ip), _lib.ptr_table(ix), _lib.ptr(count) if G.value else None))
+        ec = _download_classes(lib, e, hname, loci)
     finally:
         lib.gbrs_ecset_destroy(e)
         if stage_times is not None:
             stage_times['read'], stage_times['rank'], stage_times['classes'] = (float(x) for x in total)
-    return AlignmentPropertyMatrix(shape=(L, H, max(int(G.value), 1)), indptr=ip, indices=ix,
-                                   count=count if G.value else np.zeros(1), haplotype_names=hname, locus_names=loci)
+    return ec
+
+
+def paired_bam_to_classes(alignment_files, mate_files, haplotypes, loci, delim='_', device=0, stage_times=None, threads=0):
+    """Paired-end BAM files, aligned one end at a time -> AlignmentPropertyMatrix of equivalence classes with counts:
+    what bam_to_matrix on both ends of every pair, get_common_alignments on the two and compress over the pairs'
+    results, one pair after the other, give.  mate_files[k] is the second end of alignment_files[k].  Both ends of
+    a pair must name the same reads (no suffix is stripped), else ValueError with the reference's sentence; an
+    alignment is kept iff both ends have it, and a read left without any is a read of the empty class.  Only the
+    class matrix leaves the device.  stage_times gets read / rank / common / classes, summed over the pairs."""
+    if len(loci) >= 1 << 32:
+        raise RuntimeError('2^32 or more loci do not fit uint32 index arrays.')
+    if len(alignment_files) != len(mate_files):
+        raise RuntimeError(f'{len(alignment_files)} BAM file(s) but {len(mate_files)} mate file(s): every BAM file '
+                           'needs its second end.')
+    lib = _lib.load()
+    hname = list(haplotypes) if len(haplotypes) > 0 else ['h0']
+    L, H = len(loci), len(hname)
+    total = np.zeros(4, dtype=np.float64)
+    e = C.c_void_p()
+    _lib.check(lib.gbrs_ecset_create(L, H, device, C.byref(e)))
+    try:
+        for path, mate in zip(alignment_files, mate_files):
+            with BamFile(path, threads=threads) as first, BamFile(mate, threads=threads) as second:
+                _, hap, loc = first.reference_map(haplotypes, loci, delim)
+                _lib.check(lib.gbrs_bam_set_reference_map(first._h, len(hap), _lib.ptr(hap), _lib.ptr(loc), H, L))
+                if second.references != first.references:      # (two ends aligned to one index share the header's list)
+                    _, hap, loc = second.reference_map(haplotypes, loci, delim)
+                _lib.check(lib.gbrs_bam_set_reference_map(second._h, len(hap), _lib.ptr(hap), _lib.ptr(loc), H, L))
+                n, secs = C.c_uint64(0), np.zeros(4, dtype=np.float64)
+                status = lib.gbrs_ecset_add_bam_pair(e, first._h, second._h, C.byref(n), _lib.ptr(secs))
+                total += secs
+                if status == _lib.GBRS_ERR_INVALID:
+                    msg = lib.gbrs_last_error().decode(errors='replace')
+                    if msg.startswith(_INCOMPATIBLE):
+                        logger.error(msg)
+                        raise ValueError(msg)
+                _lib.check(status)
+            if n.value == 0:
+                raise RuntimeError(f'{path} and {mate} hold no alignment records.')
+        ec = _download_classes(lib, e, hname, loci)
+    finally:
+        lib.gbrs_ecset_destroy(e)
+        if stage_times is not None:
+            for k, name in enumerate(('read', 'rank', 'common', 'classes')):
+                stage_times[name] = float(total[k])
+    return ec
 
 
 def bam2ec(alignment_files, haplotypes, locusid_file, output_file, delim='_', comp_lib='zlib', index_dtype='uint32',
@@ -203,6 +258,47 @@ def bam2ec(alignment_files, haplotypes, locusid_file, output_file, delim='_', co
         logger.info(f'Parsing BAM File: {x}')
     ec = bam_to_classes(list(alignment_files), list(haplotypes), loci, delim=delim, device=device,
                         stage_times=stage_times)
+    init.join()
+    logger.debug(f'Number Loci: {ec.num_loci}')
+    logger.debug(f'Number Haplotypes: {ec.num_haplotypes}')
+    logger.debug(f'Number ECs: {ec.num_reads}')
+    logger.info(f'Saving EMASE Formatted File: {output_file}')
+    t0 = time.time()
+    ec.save(output_file, complib=comp_lib)
+    if stage_times is not None:
+        stage_times['write'] = time.time() - t0
+    logger.info('Done')
+
+
+def bam2ec_paired(alignment_files, mate_files, haplotypes, locusid_file, output_file, delim='_', comp_lib='zlib',
+                  index_dtype='uint32', device=0, stage_times=None):
+    """`gbrs bam2ec --mate-file`: paired-end BAM file(s), aligned one end at a time -> the equivalence-class file
+    in one pass: member for member what bam2emase() on both ends, get_common_alignments() on the two and compress()
+    over the pairs write (rules of paired_bam_to_classes).  No intermediate file, no CPU fallback."""
+    for x in alignment_files:
+        logger.info(f'BAM File: {x}')
+    for x in mate_files:
+        logger.info(f'Mate BAM File: {x}')
+    logger.info(f'Locus ID File: {locusid_file}')
+    logger.info(f'Output File: {output_file}')
+    logger.info(f'Haplotypes: {haplotypes}')
+    logger.info(f'Delimiter: {delim}')
+    logger.info(f'Index dtype: {index_dtype}')
+    logger.info(f'Compression Library: {comp_lib}')
+    if np.dtype(index_dtype) != np.uint32:
+        raise RuntimeError(f'--index-dtype {index_dtype}: the index arrays of this implementation are uint32.')
+    if len(alignment_files) == 0:
+        raise RuntimeError('No BAM file was given.')
+    if len(alignment_files) != len(mate_files):
+        raise RuntimeError(f'{len(alignment_files)} BAM file(s) but {len(mate_files)} mate file(s): every BAM file '
+                           'needs its second end.')
+    init = _lib.warm_up_device_async(device)          # the runtime starts while the first file is inflated
+    logger.info(f'Parsing Locus ID File: {locusid_file}')
+    loci = get_names(locusid_file)
+    for x, y in zip(alignment_files, mate_files):
+        logger.info(f'Parsing BAM Files: {x} + {y}')
+    ec = paired_bam_to_classes(list(alignment_files), list(mate_files), list(haplotypes), loci, delim=delim,
+                               device=device, stage_times=stage_times)
     init.join()
     logger.debug(f'Number Loci: {ec.num_loci}')
     logger.debug(f'Number Haplotypes: {ec.num_haplotypes}')

@@ -117,6 +117,10 @@ def build_parser():
     be.add_argument('--help', action='help', help='show this help message and exit')
     be.add_argument('-i', '--alignment-file', dest='alignment_files', action='append', required=True, type=_existing_or_list,
                     help='BAM file, one per -i option (the lanes of a sample), or a shortcut -i a.bam,b.bam')
+    be.add_argument('-I', '--mate-file', dest='mate_files', action='append', default=None, type=_existing_or_list,
+                    help='paired-end samples aligned one end at a time: the BAM file of the second end, one per -I option '
+                         'or a shortcut -I a.bam,b.bam; the k-th is the mate of the k-th -i, and only alignments that both '
+                         'ends have are kept (bam2emase on each end + get-common-alignments + compress in one pass)')
     be.add_argument('-h', '--haplotype-char', dest='haplotypes', action='append', default=None,
                     help='haplotype, either one per -h option, i.e. -h A -h B -h C, or a shortcut -h A,B,C')
     be.add_argument('-m', '--locus-ids', dest='locusid_file', required=True, type=_existing)
@@ -242,15 +246,25 @@ def main(argv=None) -> int:
                       delim=args.delim, index_dtype=args.index_dtype, data_dtype=args.data_dtype, device=args.device,
                       stage_times=stages, **kw)
         elif args.command == 'bam2ec':
-            from .bam2emase import bam2ec
+            from .bam2emase import bam2ec, bam2ec_paired
             files = [f for x in args.alignment_files for f in x.split(',')]
-            for f in files:
+            mates = None if args.mate_files is None else [f for x in args.mate_files for f in x.split(',')]
+            for f in files + (mates or []):
                 if not os.path.isfile(f):
                     raise FileNotFoundError(f"File '{f}' does not exist.")
             haplotypes = [h for x in (args.haplotypes or []) for h in x.split(',')]
-            bam2ec(alignment_files=[os.path.realpath(f) for f in files], haplotypes=haplotypes,
-                   locusid_file=args.locusid_file, output_file=args.output_file, delim=args.delim,
-                   comp_lib=args.comp_lib, index_dtype=args.index_dtype, device=args.device, stage_times=stages)
+            if mates is not None:
+                if len(mates) != len(files):
+                    raise RuntimeError(f'{len(files)} -i/--alignment-file but {len(mates)} -I/--mate-file: every BAM file '
+                                       'needs its second end.')
+                bam2ec_paired(alignment_files=[os.path.realpath(f) for f in files],
+                              mate_files=[os.path.realpath(f) for f in mates], haplotypes=haplotypes,
+                              locusid_file=args.locusid_file, output_file=args.output_file, delim=args.delim,
+                              comp_lib=args.comp_lib, index_dtype=args.index_dtype, device=args.device, stage_times=stages)
+            else:
+                bam2ec(alignment_files=[os.path.realpath(f) for f in files], haplotypes=haplotypes,
+                       locusid_file=args.locusid_file, output_file=args.output_file, delim=args.delim,
+                       comp_lib=args.comp_lib, index_dtype=args.index_dtype, device=args.device, stage_times=stages)
         elif args.command in ('get-common-alignments', 'combine'):
             from . import matops
             files = [f for x in args.emase_files for f in x.split(',')]

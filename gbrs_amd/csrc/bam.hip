@@ -1,6 +1,8 @@
 // Device stages of `gbrs bam2emase`: rank the read names, build the per-haplotype CSC incidence matrices; and of
 // `gbrs bam2ec` (gbrs_ecset_*, at the end of the file): the same two stages without the names, then the equivalence
-// classes of the file from the arrays where they lie, merged into the classes of the files before it.
+// classes of the file from the arrays where they lie, merged into the classes of the files before it; for a
+// paired-end sample (gbrs_ecset_add_bam_pair) both ends are converted, their sorted names compared and the entries
+// both ends have kept, all on the device, before the class build.
 // rocPRIM provides the radix sorts and scans (prim.h); the kernels around them are written here.
 //
 // Names.  The host pass (bamio.hip) hands over C candidate names (every record's name, except that a record
@@ -387,6 +389,177 @@ ecset_merge_copy_kernel(uint64_t n, uint32_t ncols, const uint64_t *__restrict__
     }
 }
 
+// ---- gbrs_ecset_add_bam_pair: the two ends of a paired-end sample ------------------------------------------------
+// Both ends' sorted distinct names lie on the device as R x width bytes, zero padded.  One thread per (sorted
+// position, 8-byte piece), the piece running fastest, so a wavefront reads neighbouring bytes of both arrays; a
+// piece is compared as the big-endian word pack_names_kernel would make of it, each array padded with zeros to the
+// wider one's width.  first_diff keeps the smallest position whose names differ (the first differing lane of a
+// wavefront holds the wavefront's smallest, so one atomic per wavefront and pass); every load is inside R x width.
+__global__ void __launch_bounds__(256)
+pair_names_differ_kernel(uint64_t R, uint32_t W, const unsigned char *__restrict__ a, uint32_t width_a,
+                         const unsigned char *__restrict__ b, uint32_t width_b, unsigned long long *first_diff) {
+    const uint64_t total = R * W;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t i = t / W;
+        const uint32_t at = (uint32_t)(t - i * W) * 8;
+        const unsigned char *na = a + i * width_a, *nb = b + i * width_b;
+        uint64_t wa = 0, wb = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < 8; ++k) {
+            const uint32_t p = at + k;
+            wa |= (uint64_t)(p < width_a ? na[p] : 0) << (56 - 8 * k);
+            wb |= (uint64_t)(p < width_b ? nb[p] : 0) << (56 - 8 * k);
+        }
+        const bool differ = wa != wb;
+        const uint64_t any = __ballot(differ);
+        if (differ && (threadIdx.x & 63) == (unsigned)__builtin_ctzll(any)) atomicMin(first_diff, (unsigned long long)i);
+    }
+}
+
+// flag[k] = entry k of the first end (column c, read r) is an entry of the second end too: bisection for r inside
+// the second end's column c, whose read ids ascend.  One lane per entry; the column is found once per wavefront
+// (entry_column: the wavefront's entries are consecutive in every pass, the stride being a multiple of 256).
+// flag[n] = 0 closes the exclusive scan, so that pos[n] is the number of common entries.  n >= 1.
+__global__ void __launch_bounds__(256)
+pair_common_flag_kernel(uint64_t n, uint32_t ncols, const uint64_t *__restrict__ a_ptr, const uint32_t *__restrict__ a_idx,
+                        const uint64_t *__restrict__ b_ptr, const uint32_t *__restrict__ b_idx, uint64_t n_b,
+                        uint32_t *__restrict__ flag) {
+    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k <= n; k += (uint64_t)gridDim.x * blockDim.x) {
+        const bool live = k < n;
+        const uint32_t c = entry_column(a_ptr, ncols, live ? k : n - 1, n);
+        uint32_t f = 0;
+        if (live) {
+            const uint32_t r = a_idx[k];
+            uint64_t lo = min(b_ptr[c], n_b), hi = min(b_ptr[c + 1], n_b);     // first j in [lo, hi) with b_idx[j] >= r
+            const uint64_t end = hi;
+            while (lo < hi) {
+                const uint64_t mid = lo + ((hi - lo) >> 1);
+                if (b_idx[mid] < r) lo = mid + 1; else hi = mid;
+            }
+            f = (lo < end && b_idx[lo] == r) ? 1u : 0u;
+        }
+        flag[k] = f;
+    }
+}
+
+// pos = exclusive scan of flag over n + 1 entries: the common entries to their places
+__global__ void __launch_bounds__(256)
+pair_common_compact_kernel(uint64_t n, const uint32_t *__restrict__ a_idx, const uint32_t *__restrict__ flag,
+                           const uint32_t *__restrict__ pos, uint64_t n_out, uint32_t *__restrict__ out) {
+    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t p = pos[k];
+        if (flag[k] && p < n_out) out[p] = a_idx[k];
+    }
+}
+
+// column c of the common structure starts after the common entries before the first end's column c: pos[a_ptr[c]],
+// whichever columns were emptied (a_ptr[ncols] = n, pos[n] = the total)
+__global__ void __launch_bounds__(256)
+pair_common_ptr_kernel(uint64_t n_ptr, const uint64_t *__restrict__ a_ptr, const uint32_t *__restrict__ pos, uint64_t n,
+                       uint64_t *__restrict__ out_ptr) {
+    for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < n_ptr; c += (uint64_t)gridDim.x * blockDim.x)
+        out_ptr[c] = pos[min(a_ptr[c], n)];
+}
+
+// one end of a pair, converted: what stays on the device until the pair has been added
+struct PairEnd {
+    uint64_t R = 0;
+    uint32_t width = 1;
+    DevBuf<unsigned char> rname;                 // R x width, sorted
+    DevBuf<uint32_t> idx;                        // unallocated when no record is kept
+    DevBuf<uint64_t> col_ptr;
+};
+
+// rank_names + build_matrix of a collected file; the conversion's temporaries are gone when this returns
+int convert_end(gbrs_bam *b, PairEnd &end, double *rank_seconds, double *build_seconds, hipStream_t s) {
+    Scratch sc;
+    DevBuf<uint32_t> rank;
+    auto t0 = std::chrono::steady_clock::now();
+    int rc = rank_names(b, sc, rank, &end.rname, s);
+    *rank_seconds += seconds_since(t0);
+    t0 = std::chrono::steady_clock::now();
+    if (rc == GBRS_OK) rc = build_matrix(b, sc, rank, end.idx, end.col_ptr, s);
+    *build_seconds += seconds_since(t0);
+    bam_release_collected(b);
+    end.R = b->num_reads;
+    end.width = b->name_width;
+    return rc;
+}
+
+std::string name_at(const std::vector<unsigned char> &bytes) {
+    size_t n = bytes.size();
+    while (n && bytes[n - 1] == 0) --n;
+    return std::string((const char *)bytes.data(), n);
+}
+
+// GBRS_OK when both ends hold the same sorted distinct names; else the reference's sentence and the first sorted
+// position at which they differ.  Of the two names there, the smaller one occurs in its own file only.
+int check_pair_names(const gbrs_bam *fa, const PairEnd &a, const gbrs_bam *fb, const PairEnd &b, hipStream_t s) {
+    const uint64_t R = std::min(a.R, b.R);
+    const uint32_t W = (std::max(a.width, b.width) + 7) / 8;
+    DevBuf<unsigned long long> first_diff;
+    GBRS_TRY(first_diff.alloc(1));
+    GBRS_HIP_CHECK(hipMemsetAsync(first_diff.p, 0xFF, sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(pair_names_differ_kernel, dim3(capped_grid(R * W)), dim3(256), 0, s, R, W, a.rname.p, a.width, b.rname.p,
+                       b.width, first_diff.p);
+    GBRS_HIP_CHECK(hipGetLastError());
+    unsigned long long at = 0;
+    GBRS_HIP_CHECK(hipMemcpyAsync(&at, first_diff.p, sizeof(at), hipMemcpyDeviceToHost, s));
+    GBRS_HIP_CHECK(hipStreamSynchronize(s));
+    if (at == ~0ull && a.R == b.R) return GBRS_OK;      // (equal names have equal lengths: the widths agree as well)
+    const uint64_t p = std::min<uint64_t>(at, R);
+    std::vector<unsigned char> na, nb;
+    if (p < a.R) {
+        na.resize(a.width);
+        GBRS_HIP_CHECK(hipMemcpy(na.data(), a.rname.p + p * a.width, a.width, hipMemcpyDeviceToHost));
+    }
+    if (p < b.R) {
+        nb.resize(b.width);
+        GBRS_HIP_CHECK(hipMemcpy(nb.data(), b.rname.p + p * b.width, b.width, hipMemcpyDeviceToHost));
+    }
+    const std::string sa = name_at(na), sb = name_at(nb);
+    const bool from_a = p >= b.R || (p < a.R && sa < sb);
+    return fail(GBRS_ERR_INVALID,
+                "The read ID's are not compatible. %s holds %llu reads and %s %llu; the sorted read names first differ at position "
+                "%llu: '%s' is in %s only.",
+                fa->path.c_str(), (unsigned long long)a.R, fb->path.c_str(), (unsigned long long)b.R, (unsigned long long)p,
+                (from_a ? sa : sb).c_str(), (from_a ? fa : fb)->path.c_str());
+}
+
+// idx / col_ptr := the entries both ends have, in CSC order (idx stays unallocated when there is none)
+int common_entries(const PairEnd &a, const PairEnd &b, uint64_t ncols, DevBuf<uint32_t> &idx, DevBuf<uint64_t> &col_ptr,
+                   hipStream_t s) {
+    GBRS_TRY(col_ptr.alloc(ncols + 1));
+    const uint64_t n = a.idx.n;
+    if (n == 0 || b.idx.n == 0) {
+        GBRS_HIP_CHECK(hipMemsetAsync(col_ptr.p, 0, col_ptr.bytes(), s));
+        return GBRS_OK;
+    }
+    Scratch sc;
+    DevBuf<uint32_t> flag, pos;
+    GBRS_TRY(flag.alloc(n + 1));
+    GBRS_TRY(pos.alloc(n + 1));
+    hipLaunchKernelGGL(pair_common_flag_kernel, dim3(capped_grid(n + 1)), dim3(256), 0, s, n, (uint32_t)ncols, a.col_ptr.p, a.idx.p,
+                       b.col_ptr.p, b.idx.p, (uint64_t)b.idx.n, flag.p);
+    GBRS_HIP_CHECK(hipGetLastError());
+    GBRS_TRY(exclusive_scan(sc, flag.p, pos.p, n + 1, s));
+    uint32_t n_common = 0;
+    GBRS_HIP_CHECK(hipMemcpyAsync(&n_common, pos.p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    GBRS_HIP_CHECK(hipStreamSynchronize(s));
+    if (n_common > n) return fail(GBRS_ERR_HIP, "internal error: more common entries than entries");
+    if (n_common) {
+        GBRS_TRY(idx.alloc(n_common));
+        hipLaunchKernelGGL(pair_common_compact_kernel, dim3(capped_grid(n)), dim3(256), 0, s, n, a.idx.p, flag.p, pos.p,
+                           (uint64_t)n_common, idx.p);
+        GBRS_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(pair_common_ptr_kernel, dim3(capped_grid(ncols + 1)), dim3(256), 0, s, ncols + 1, a.col_ptr.p, pos.p, n,
+                       col_ptr.p);
+    GBRS_HIP_CHECK(hipGetLastError());
+    GBRS_HIP_CHECK(hipStreamSynchronize(s));
+    return GBRS_OK;
+}
+
 // set := classes of (set's classes, then the addend's classes), weights = the two count vectors one after the other.
 // The set's classes are distinct rows, so in first-seen order each keeps its id; an addend class equal to one of them
 // adds its count there, the others follow in their own order - the first-occurrence order over the concatenated reads.
@@ -586,6 +759,93 @@ int gbrs_ecset_add_bam(gbrs_ecset_t *e, gbrs_bam_t *b, uint64_t *num_reads_of_fi
     if (stage_seconds) stage_seconds[2] = seconds_since(t0);
     e->num_reads += b->num_reads;
     *num_reads_of_file = b->num_reads;
+    return GBRS_OK;
+}
+
+int gbrs_ecset_add_bam_pair(gbrs_ecset_t *e, gbrs_bam_t *first, gbrs_bam_t *second, uint64_t *num_reads_of_pair,
+                            double *stage_seconds) {
+    using namespace gbrs;
+    if (!e || !first || !second || !num_reads_of_pair) return fail(GBRS_ERR_INVALID, "bad argument");
+    if (first == second) return fail(GBRS_ERR_INVALID, "the two ends of a pair need a handle each");
+    gbrs_bam *ends[2] = {first, second};
+    for (gbrs_bam *b : ends)
+        if (!b->map_set) return fail(GBRS_ERR_STATE, "gbrs_bam_set_reference_map has not been called");
+    for (gbrs_bam *b : ends)
+        if (b->num_loci != e->L || b->num_haps != e->H)
+            return fail(GBRS_ERR_INVALID, "%s: the reference map has %u loci x %u haplotypes, the set %u x %u", b->path.c_str(),
+                        b->num_loci, b->num_haps, e->L, e->H);
+    GBRS_TRY(select_device(e->device));
+    for (gbrs_bam *b : ends) {                           // (an earlier gbrs_bam_convert: the handles keep nothing on the device)
+        if (b->dev && b->dev_free) b->dev_free(b->dev);
+        b->dev = nullptr;
+        b->converted = false;
+    }
+    RoctxRange range("gbrs_ecset_add_bam_pair");
+    *num_reads_of_pair = 0;
+    double unused[4];
+    double *secs = stage_seconds ? stage_seconds : unused;     // read, rank, common, classes (the matrices count as classes, as in add_bam)
+    secs[0] = secs[1] = secs[2] = secs[3] = 0.0;
+    hipStream_t s = nullptr;
+    const uint64_t ncols = (uint64_t)e->H * e->L;
+    auto t0 = std::chrono::steady_clock::now();
+    int rc = bam_collect(first);
+    secs[0] += seconds_since(t0);
+    if (rc != GBRS_OK) return rc;
+    const bool first_empty = first->cand_off.size() < 2;
+    PairEnd a, b;
+    if (first_empty) bam_release_collected(first);
+    else {
+        RoctxRange r("pair_first_end");
+        GBRS_TRY(convert_end(first, a, &secs[1], &secs[3], s));
+    }
+    t0 = std::chrono::steady_clock::now();
+    rc = bam_collect(second);
+    secs[0] += seconds_since(t0);
+    if (rc != GBRS_OK) return rc;
+    const bool second_empty = second->cand_off.size() < 2;
+    if (first_empty || second_empty) {
+        bam_release_collected(second);
+        if (first_empty && second_empty) return GBRS_OK; // no record at all in either end: nothing to add
+        return fail(GBRS_ERR_INVALID, "The read ID's are not compatible. %s holds no record, %s does.",
+                    (first_empty ? first : second)->path.c_str(), (first_empty ? second : first)->path.c_str());
+    }
+    {
+        RoctxRange r("pair_second_end");
+        GBRS_TRY(convert_end(second, b, &secs[1], &secs[3], s));
+    }
+    CompressResult file;
+    {
+        DevBuf<uint32_t> idx;
+        DevBuf<uint64_t> col_ptr;
+        t0 = std::chrono::steady_clock::now();
+        {
+            RoctxRange r("pair_common");
+            rc = check_pair_names(first, a, second, b, s);
+            a.rname.release();
+            b.rname.release();
+            if (rc == GBRS_OK) rc = common_entries(a, b, ncols, idx, col_ptr, s);
+        }
+        secs[2] = seconds_since(t0);
+        if (rc != GBRS_OK) return rc;
+        b.idx.release();
+        b.col_ptr.release();
+        a.idx.release();
+        a.col_ptr.release();
+        t0 = std::chrono::steady_clock::now();
+        GBRS_TRY(compress_device(file, a.R, e->L, e->H, idx.n, idx.p, col_ptr.p, nullptr, s));
+    }
+    if (e->res.num_ecs == 0) {
+        e->res.num_ecs = file.num_ecs;
+        e->res.n_entries = file.n_entries;
+        e->res.col_ptr.swap(file.col_ptr);
+        e->res.indices.swap(file.indices);
+        e->res.count.swap(file.count);
+    } else {
+        GBRS_TRY(merge_classes(e->res, file, e->L, e->H, s));
+    }
+    secs[3] += seconds_since(t0);
+    e->num_reads += a.R;
+    *num_reads_of_pair = a.R;
     return GBRS_OK;
 }
 

@@ -588,12 +588,25 @@ int gbrs_bam_destroy(gbrs_bam_t *b);
  *              for a file without any record.  stage_seconds double[3]: read, rank, classes (NULL allowed).  Record
  *              errors as for convert.  After a failure the set holds what it held before.  The bam handle keeps
  *              nothing on the device.
+ *   add_bam_pair   the two ends of a paired-end sample, aligned one end at a time: adds what bam2emase on each end,
+ *              `get-common-alignments -i first -i second` and compress give.  Both handles as for add_bam (same statuses).
+ *              Each end's read ids are the ranks of its own distinct names; the two sorted name arrays must be equal
+ *              byte for byte, else GBRS_ERR_INVALID with a message that starts "The read ID's are not compatible." and
+ *              goes on to the first sorted position at which they differ, the name there and the file it is from (one
+ *              end without any record against one with records is incompatible as well).  An entry (haplotype, locus,
+ *              read) is kept iff both ends have it; a read left without entries is a read of the empty class.
+ *              num_reads_of_pair = 0 and an unchanged set when neither file holds a record.  stage_seconds double[4]:
+ *              read, rank, common (name check + intersection), classes (NULL allowed).  Record errors name the
+ *              offending file.  After a failure the set holds what it held before; the handles keep nothing on the
+ *              device.  add_bam and add_bam_pair may be mixed on one set.
  *   sizes      reads added, classes, entries per haplotype (uint64[H]); all zero for an empty set.
  *   get        indptr_out[h] uint32[L + 1], indices_out[h] uint32[nnz_per_hap[h]] (class ids ascending inside a
  *              column), count_out double[num_ecs] (NULL to skip).  An empty set has zero classes. */
 typedef struct gbrs_ecset gbrs_ecset_t;
 int gbrs_ecset_create(uint32_t num_loci, uint32_t num_haps, int device, gbrs_ecset_t **out);
 int gbrs_ecset_add_bam(gbrs_ecset_t *e, gbrs_bam_t *b, uint64_t *num_reads_of_file, double *stage_seconds);
+int gbrs_ecset_add_bam_pair(gbrs_ecset_t *e, gbrs_bam_t *first, gbrs_bam_t *second, uint64_t *num_reads_of_pair,
+                            double *stage_seconds);
 int gbrs_ecset_sizes(gbrs_ecset_t *e, uint64_t *num_reads, uint64_t *num_ecs, uint64_t *nnz_per_hap);
 int gbrs_ecset_get(gbrs_ecset_t *e, uint32_t *const *indptr_out, uint32_t *const *indices_out, double *count_out);
 int gbrs_ecset_destroy(gbrs_ecset_t *e);

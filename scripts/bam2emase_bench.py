@@ -17,9 +17,17 @@ on the file given twice (the lane merge), the two-step path it replaces (`bam2em
 runs (sampled every few milliseconds from this process).  Every step is a fresh process under its own time limit; the
 first one that fails ends the job.  The files of the one-step and the two-step path are compared member by member.
 
+`--paired` times `gbrs bam2ec --mate-file` on a paired-end sample aligned one end at a time.  Beside the generated file
+it writes a second-end file with the same read names in which every read keeps a seeded subset of its records (its first
+record always; one of four seeded subsets, so the classes stay a small multiple of the loci), then runs, as fresh
+processes in the same job: `bam2ec -i first -I second` (twice, the faster run counts; device memory sampled as above),
+the four-command chain it replaces (`bam2emase` on either end, `get-common-alignments`, `compress`), and one paired
+run under `rocprofv3 --kernel-trace --stats`.  The two class files are compared member by member; the exit status is 0
+only if they are equal and the one command took less wall clock than the chain.
+
 Prints one JSON object.  Needs an MI355X.  Usage:
     python scripts/bam2emase_bench.py [--reads N] [--per-read K] [--haps H] [--loci L] [--format npz|h5]
-                                      [--workdir DIR] [--keep] [--no-profile] [--json OUT] [--bam2ec]
+                                      [--workdir DIR] [--keep] [--no-profile] [--json OUT] [--bam2ec | --paired]
 """
 from __future__ import annotations
 
@@ -61,9 +69,11 @@ def read_names(ids):
 
 def slice_records(args):
     """Worker: records of reads [r0, r1) -> BGZF bytes in `part`.  Read number k of the file is named after
-    (k * 2654435761) mod 2^40, so the file is not in name order."""
+    (k * 2654435761) mod 2^40, so the file is not in name order.  An eighth item that is true makes the slice one of
+    the second end (`--paired`): the same records, of which every read keeps one of four seeded subsets."""
     import numpy as np
-    r0, r1, per, haps, loci, seed, part = args
+    r0, r1, per, haps, loci, seed, part = args[:7]
+    mate = len(args) > 7 and args[7]
     rng = np.random.default_rng([seed, r0])
     n = r1 - r0
     ids = (np.arange(r0, r1, dtype=np.int64) * 2654435761) % (1 << 40)
@@ -91,6 +101,10 @@ def slice_records(args):
     seq = rng.integers(0, 4, size=(n, SEQ // 2, 2))                      # the same read sequence in all its records
     rec['seq'] = np.repeat(((1 << seq[:, :, 0]) << 4 | (1 << seq[:, :, 1])).astype(np.uint8), per, axis=0)
     rec['qual'] = np.repeat(rng.choice(np.array([2, 14, 27, 37, 37, 37], dtype=np.uint8), size=(n, SEQ)), per, axis=0)
+    if mate:
+        masks = np.random.default_rng([seed, 2]).random((4, per)) < 0.7
+        masks[:, 0] = True                                               # a read keeps its first record in every subset
+        rec = rec[masks[np.random.default_rng([seed, r0, 2]).integers(0, 4, size=n)].reshape(-1)]
     plain = rec.tobytes()
     with open(part, 'wb') as fh:
         for at in range(0, len(plain), 0xFF00):
@@ -102,7 +116,7 @@ def slice_records(args):
     return len(plain)
 
 
-def write_bam(path, reads, per, haps, loci, seed, procs):
+def write_bam(path, reads, per, haps, loci, seed, procs, mate=False):
     lname = [f'T{l:07d}' for l in range(loci)]
     hname = [chr(65 + h) for h in range(haps)]
     text = b'@HD\tVN:1.6\tSO:unsorted\n'
@@ -113,7 +127,8 @@ def write_bam(path, reads, per, haps, loci, seed, procs):
             head += [struct.pack('<i', len(n) + 1), n, b'\x00', struct.pack('<i', 3000)]
     head = b''.join(head)
     step = max(1, min(250_000, (reads + procs - 1) // procs))
-    jobs = [(r0, min(reads, r0 + step), per, haps, loci, seed, f'{path}.part{k}') for k, r0 in enumerate(range(0, reads, step))]
+    jobs = [(r0, min(reads, r0 + step), per, haps, loci, seed, f'{path}.part{k}') + ((True,) if mate else ())
+            for k, r0 in enumerate(range(0, reads, step))]
     plain = len(head)
     with open(path, 'wb') as out:
         for at in range(0, len(head), 0xFF00):
@@ -125,9 +140,9 @@ def write_bam(path, reads, per, haps, loci, seed, procs):
         with ProcessPoolExecutor(max_workers=procs) as pool:
             for job, n in zip(jobs, pool.map(slice_records, jobs)):
                 plain += n
-                with open(job[-1], 'rb') as fh:
+                with open(job[6], 'rb') as fh:
                     shutil.copyfileobj(fh, out, 1 << 24)
-                os.remove(job[-1])
+                os.remove(job[6])
         out.write(EOF_BLOCK)
     ids = os.path.join(os.path.dirname(path), 'locus_ids.tsv')
     with open(ids, 'w') as fh:
@@ -289,6 +304,54 @@ def bench_bam2ec(args, res, workdir, bam, ids, hname):
     return 0 if same else 1
 
 
+def bench_paired(args, res, workdir, bam, mate, ids, hname):
+    py = [sys.executable, '-m', 'gbrs_amd']
+    common = ['-m', ids, '-h', ','.join(hname)]
+    stage_file = os.path.join(workdir, 'stages.json')
+    one, four = os.path.join(workdir, 'one.compressed.h5'), os.path.join(workdir, 'four.compressed.h5')
+    end1, end2, both = (os.path.join(workdir, f'{k}.h5') for k in ('end1', 'end2', 'common'))
+    limit = max(120, int(args.reads / 100_000))
+    chain = ('bam2emase_first', 'bam2emase_second', 'get_common_alignments', 'compress')
+    steps = [('bam2ec_paired', py + ['bam2ec', '-i', bam, '--mate-file', mate] + common + ['-o', one], True, 2),
+             (chain[0], py + ['bam2emase', '-i', bam] + common + ['-o', end1], False, 1),
+             (chain[1], py + ['bam2emase', '-i', mate] + common + ['-o', end2], False, 1),
+             (chain[2], py + ['get-common-alignments', '-i', end1, '-i', end2, '-o', both], False, 1),
+             (chain[3], py + ['compress', '-i', both, '-o', four], False, 1)]
+    for name, cmd, watch, times in steps:
+        runs = []
+        for _ in range(times):
+            print(f'[bench] {name} ...', file=sys.stderr, flush=True)
+            r = run_staged(cmd, stage_file, limit, watch_memory=watch)
+            if 'failed' in r:
+                res[name] = r
+                return 1
+            runs.append(r)
+        res[name] = dict(min(runs, key=lambda x: x['wall_s']), runs=len(runs))
+    res['chain_wall_s'] = round(sum(res[k]['wall_s'] for k in chain), 3)
+    res['output_bytes'] = dict(bam2ec_paired=os.path.getsize(one), bam2emase_first=os.path.getsize(end1),
+                               bam2emase_second=os.path.getsize(end2), get_common_alignments=os.path.getsize(both),
+                               compress=os.path.getsize(four))
+    same, n_ecs, n_reads = files_equal(one, four)
+    res['paired_equals_chain'], res['num_ecs'], res['count_sum'] = same, n_ecs, n_reads
+    res['paired_below_chain'] = res['bam2ec_paired']['wall_s'] < res['chain_wall_s']
+    if not args.no_profile and shutil.which('rocprofv3'):
+        env = dict(os.environ, PYTHONPATH=ROOT, GBRS_ORDERLY_EXIT='1')           # the tracer writes at exit
+        print('[bench] bam2ec_paired under rocprofv3 ...', file=sys.stderr, flush=True)
+        prof = os.path.join(workdir, 'profile')
+        try:
+            r = subprocess.run(['rocprofv3', '--kernel-trace', '--stats', '--output-format', 'csv', '-d', prof, '--'] + steps[0][1],
+                               env=env, cwd=workdir, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                               timeout=2 * limit)
+        except subprocess.TimeoutExpired:
+            res['profile'] = dict(rc='time limit')
+            return 1
+        k = kernel_stats(prof)
+        res['profile'] = dict(rc=r.returncode, kernels=k, device_ms_total=round(sum(v['ms'] for v in k.values()), 3))
+        if r.returncode != 0:
+            return 1
+    return 0 if same and res['paired_below_chain'] else 1
+
+
 def stage_device_ms(prof_dir):
     """Device time of the rank and the classes stage of `bam2ec` from the kernel trace, in dispatch order: a file's rank
     stage starts with pack_names_kernel, its classes stage with record_keys_kernel.  None without a trace."""
@@ -346,7 +409,11 @@ def main():
     ap.add_argument('--procs', type=int, default=int(os.environ.get('OMP_NUM_THREADS', '16')))
     ap.add_argument('--json', default=None)
     ap.add_argument('--bam2ec', action='store_true', help='time `gbrs bam2ec` against `bam2emase` + `compress` (see above)')
+    ap.add_argument('--paired', action='store_true',
+                    help='time `gbrs bam2ec --mate-file` against the four-command chain it replaces (see above)')
     args = ap.parse_args()
+    if args.bam2ec and args.paired:
+        ap.error('--bam2ec and --paired are two jobs')
     workdir = args.workdir or tempfile.mkdtemp(prefix='bam2emase_bench_')
     os.makedirs(workdir, exist_ok=True)
     bam = os.path.join(workdir, 'sample.bam')
@@ -356,9 +423,16 @@ def main():
                name_bytes=NAME_W, bam_bytes=os.path.getsize(bam), inflated_bytes=plain,
                generate_s=round(time.time() - t0, 2), format=args.format,
                configs1_records=360_000_000, below_configs1=args.reads * args.per_read < 360_000_000)
-    if args.bam2ec:
+    if args.paired:
+        t0 = time.time()
+        mate = os.path.join(workdir, 'sample_2.bam')
+        _, _, plain2 = write_bam(mate, args.reads, args.per_read, args.haps, args.loci, 20, args.procs, mate=True)
+        res.update(mate_bam_bytes=os.path.getsize(mate), mate_inflated_bytes=plain2, mate_records=(plain2 - plain) // 229
+                   + args.reads * args.per_read, mate_generate_s=round(time.time() - t0, 2))
+    if args.bam2ec or args.paired:
         res['format'] = 'h5'
-        rc = bench_bam2ec(args, res, workdir, bam, ids, hname)
+        rc = (bench_paired(args, res, workdir, bam, mate, ids, hname) if args.paired else
+              bench_bam2ec(args, res, workdir, bam, ids, hname))
         if not args.keep and args.workdir is None:
             shutil.rmtree(workdir, ignore_errors=True)
         text = json.dumps(res)

@@ -11,6 +11,10 @@ import numpy as np
 
 
 def interpolate(x_gene, gamma, x_grid):
+    """Assumes what the reference's inputs satisfy: the gene positions are ascending (duplicates are allowed: a query
+    on a repeated position takes the segment that ends at the first of them, as searchsorted's side='left' gives it),
+    positive, and the last grid point + 1 is not below the last gene, so that the knots need no sorting (interp1d would
+    sort them; `gbrs_amd.postproc.interpolate_arrays` does)."""
     x = np.append([0.0], np.asarray(x_gene, dtype=float))
     x = np.append(x, [x_grid[-1] + 1.0])
     y = np.hstack((gamma[:, 0][:, np.newaxis], gamma))

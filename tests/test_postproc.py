@@ -64,5 +64,12 @@ def test_postproc_hip_files(path, tmp_path, monkeypatch):
     a = np.loadtxt(tmp_path / "export.tsv", skiprows=1, delimiter="\t")
     b = np.loadtxt(ref.split("\n")[1:-1], delimiter="\t")
     np.testing.assert_allclose(a, b, atol=1.01e-6)          # %.6f text: at most one unit in the last place
+    # the dosage product itself, on the reference's own grid-level rows: both are length-S sums of non-negative
+    # products, each within S 2^-53 of the exact sum whatever the order
+    from gbrs_amd import _lib
+    rows = np.ascontiguousarray(np.vstack([g[f"interp_{c}"].T for c in chroms]), dtype=np.float64)
+    dosage = np.empty((rows.shape[0], H))
+    _lib.check(_lib.load().gbrs_genoprob_dosage(H, rows.shape[0], _lib.ptr(rows), _lib.ptr(dosage), 0))
+    np.testing.assert_allclose(dosage, g["dosage"], rtol=2 * rows.shape[1] * 2.0 ** -53, atol=0)
     with pytest.raises(ValueError, match="interpolation range"):
         interpolate_arrays(g[f"xgene_{chroms[0]}"], g[f"gamma_{chroms[0]}"], np.array([-1.0, 2.0]))

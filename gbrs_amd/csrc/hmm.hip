@@ -8,13 +8,13 @@
 // workgroup barrier per gene.  No dense contraction is reshaped for MFMA: the path is exp/log
 // and latency bound.
 #include "common.h"
+#include "hmm_route.h"
 
 #include <algorithm>
 #include <cfloat>
 #include <climits>
 #include <cmath>
 #include <cstdlib>
-#include <functional>
 
 namespace gbrs {
 
@@ -2382,9 +2382,6 @@ static_assert(BT_TIE_S == BS_S, "the path check of backtrace_write_kernel is the
 // loads), the transition block is read from LDS at wave-uniform addresses (one broadcast b128 read per two entries), and
 // a (target, source) pair is four vector instructions: add, compare, maximum, select of the index.  Four targets make one
 // 8-byte store of the sample's backpointer row.  First maximum, as np.argmax.
-#ifndef HMM_BPL_MIN
-#define HMM_BPL_MIN 32        // samples from which viterbi_bp_lanes_kernel replaces viterbi_bp_kernel
-#endif
 constexpr int BPL_WAVES = 4;
 template <int SS>
 __global__ void __launch_bounds__(64 * BPL_WAVES)
@@ -2501,7 +2498,6 @@ struct gbrs_hmm {
     int max_bp_rows = 0;                      // max over chromosomes of min(n_genes, n_trans)
     bool have_eprob = false, ran = false;
     bool pe_ready = false;                    // peprob = exp(eprob) is current (the emission kernels write both)
-    bool free_backward = false;               // last run used the free-running backward sweep (beta needs bcorr)
     bool logs_ready = false;                  // alpha / beta / scaler of the last run have been made (hmm_make_logs)
     DevBuf<ChromDesc> d_chroms;
     DevBuf<int32_t> d_order;                  // chromosome indices, longest first
@@ -2523,10 +2519,10 @@ struct gbrs_hmm {
     // the backward one closes every chromosome with such a block.  [0] forward, [1] backward.
     int n_vb = 0, blk_samples = 0;            // n_vb: the larger of the two block counts (buffers are sized by it)
     int n_blk[2] = {0, 0}, n_head[2] = {0, 0};
-    bool last_blocked = false;                // the last run's backward chains started from injected vectors
-    RowMap delta_rows{0, 1};                  // how the last run laid `delta` out ([sample][gene], or [gene][sample] for the large batches)
-    bool last_delta_spec = false;             // the last run's delta came from the rank-convergence scheme: delta_apply_kernel is due
-    bool last_tie_check = false;              // the last run's backtrace checked the margins of its path (dspec_tie holds its flags)
+    // The last run's route.  What later calls read from it: free_backward() - beta needs bcorr; Blocked - the backward chains
+    // started from injected vectors; BlockedRank - gbrs_hmm_info reports how the fix-ups went; tie_check - dspec_tie holds
+    // the flags of the backtrace's margin check; delta_interleaved - how `delta` is laid out.
+    HmmRoute last;
     DevBuf<BlockRange> d_ranges[2];
     DevBuf<int32_t> d_first_block[2];         // blocks of chromosome c: first_block[c] .. first_block[c+1]
     DevBuf<int32_t> d_vorder[2];              // block indices, the directly chained ones first (n_head of them)
@@ -2554,6 +2550,9 @@ struct gbrs_hmm {
 
 namespace {
 
+static_assert(MF_S == 36, "hmm_route.h names the 36-state kernels' state count by its number");
+HmmShape hmm_shape(const gbrs_hmm *h) { return HmmShape{h->S, h->H, h->n_samples, h->n_chrom, h->total_trans}; }
+
 int hmm_alloc_samples(gbrs_hmm *h, int n_samples) {
     if (n_samples == h->n_samples && h->eprob.p) return GBRS_OK;
     const size_t gs = (size_t)h->total_genes * n_samples;
@@ -2575,18 +2574,7 @@ int hmm_alloc_samples(gbrs_hmm *h, int n_samples) {
     return GBRS_OK;
 }
 
-// posterior_kernel / hmm_outputs_kernel over every (sample, gene) row of the handle
-void launch_posterior(gbrs_hmm *h, hipStream_t st) {
-    const int S = h->S;
-    const int64_t rows = h->total_genes * h->n_samples;
-    const int out_rows = std::max(1, 1024 / S), per_block = out_rows * POST_GROUPS;
-    const dim3 grid((unsigned)((rows + per_block - 1) / per_block)), block(((out_rows * S + 63) / 64) * 64);
-    const size_t lds = (size_t)POST_GROUPS * (out_rows * S + out_rows) * sizeof(double);
-    hipLaunchKernelGGL(posterior_kernel, grid, block, lds, st, S, out_rows, rows, h->xsum.p, h->peprob.p, h->invz.p,
-                       h->bhat.p, h->gamma.p, (int64_t)0, h->total_genes, h->total_genes);
-}
-
-// the same over the genes [gene_begin, gene_begin + range_len) of every sample
+// posterior_kernel over the genes [gene_begin, gene_begin + range_len) of every sample
 void launch_posterior_range(gbrs_hmm *h, hipStream_t st, int64_t gene_begin, int64_t range_len) {
     const int S = h->S;
     const int64_t rows = range_len * h->n_samples;
@@ -2598,13 +2586,16 @@ void launch_posterior_range(gbrs_hmm *h, hipStream_t st, int64_t gene_begin, int
                        h->bhat.p, h->gamma.p, gene_begin, range_len, h->total_genes);
 }
 
+void launch_posterior(gbrs_hmm *h, hipStream_t st) { launch_posterior_range(h, st, 0, h->total_genes); }
+
+// hmm_outputs_kernel over every (sample, gene) row of the handle
 void launch_logs(gbrs_hmm *h, int parts, hipStream_t st) {
     const int S = h->S;
     const int64_t rows = h->total_genes * h->n_samples;
     const int out_rows = std::max(1, 1024 / S);
     const dim3 grid((unsigned)((rows + out_rows - 1) / out_rows)), block(((out_rows * S + 63) / 64) * 64);
     hipLaunchKernelGGL(hmm_outputs_kernel, grid, block, 0, st, S, out_rows, rows, parts, h->eprob.p, h->xsum.p,
-                       h->invz.p, h->bhat.p, h->free_backward ? h->bcorr.p : (const double *)nullptr,
+                       h->invz.p, h->bhat.p, h->last.free_backward() ? h->bcorr.p : (const double *)nullptr,
                        h->alpha.p, h->scaler.p, h->beta.p);
 }
 
@@ -2619,9 +2610,9 @@ int hmm_make_logs(gbrs_hmm *h) {
     if (!h->alpha.p) GBRS_TRY(h->alpha.alloc(gs * h->S));
     if (!h->beta.p) GBRS_TRY(h->beta.alloc(gs * h->S));
     if (!h->scaler.p) GBRS_TRY(h->scaler.alloc(gs));
-    if (h->free_backward) {
+    if (h->last.free_backward()) {
         if (!h->bcorr.p) GBRS_TRY(h->bcorr.alloc(gs));
-        if (h->last_blocked)            // the blocks' backward chains become one free-running chain again (hmm_blocked.inc)
+        if (h->last.sweep == HmmSweep::Blocked)            // the blocks' backward chains become one free-running chain again (hmm_blocked.inc)
             hipLaunchKernelGGL(blocked_bscale_fix_kernel, dim3(h->n_blk[1], h->n_samples), dim3(64), 0, h->stream, h->total_genes,
                                h->n_vb, h->d_ranges[1].p, h->peprob.p, h->bhat.p, h->inj_b.p, h->bscale.p);
         hipLaunchKernelGGL(beta_corr_kernel, dim3(h->n_samples, h->n_chrom), dim3(256), 0, h->stream, h->total_genes,
@@ -2649,18 +2640,8 @@ int hmm_make_logs(gbrs_hmm *h) {
 #ifndef HMM_SB
 #define HMM_SB 2          // samples per wave in large batches (n_samples >= HMM_BATCH_MIN)
 #endif
-#ifndef HMM_BATCH_MIN
-#define HMM_BATCH_MIN 24  // below this every sample gets waves of its own (measured: 16 samples 3.4 vs 3.6 ms, 32 samples 5.1 vs 4.8 ms)
-#endif
 #ifndef HMM_NSET_B
 #define HMM_NSET_B 3      // register sets of the HMM_SB-samples-per-wave recursions
-#endif
-#ifndef HMM_MFMA_MIN
-#define HMM_MFMA_MIN 64   // 36 states, at least this many samples: alpha and backward sweeps of 16 samples per wave on MFMA (see the kernels' comment)
-#endif
-#ifndef HMM_DLANES_MIN
-#define HMM_DLANES_MIN 64 // 36 states, at least this many samples: delta chain with the samples on the lanes (measured with the MFMA sweeps beside it:
-                          // 8-32 samples the one-state-per-lane kernels win, 64 a wash, 128: 10.3 vs 12.1 ms, 256: 19.4 vs 22.1 ms)
 #endif
 #ifndef HMM_NSET_M
 #define HMM_NSET_M 3      // register sets (transition blocks in flight) of the MFMA sweeps
@@ -2668,55 +2649,13 @@ int hmm_make_logs(gbrs_hmm *h) {
 #ifndef HMM_NSET_M2
 #define HMM_NSET_M2 3     // the same with two sample groups per wavefront
 #endif
-#ifndef HMM_MFMA_NG2_MIN
-#define HMM_MFMA_NG2_MIN (1 << 30)   // samples from which a wavefront of the MFMA sweeps carries two groups of 16: never by
-#endif                               // default - measured (round 4): 256 samples 16.3-16.7 ms either way, 128: 9.2 -> 12.0, 64: 6.9 -> 9.3
 
-#ifndef HMM_BLOCKED_MAX
-#define HMM_BLOCKED_MAX 4     // 36 states, at most this many samples: the blocked scan (the sum-product operators cost 36 columns per block and sample;
-                              // round 4, Viterbi values by rank convergence: 0.63 / 1.01 / 1.51 / 1.85 ms at 1 / 2 / 3 / 4 samples against 1.9-2.0 on the
-                              // chains; 5 samples 2.25 against 2.0)
-#endif
-#ifndef HMM_DELTA_AFTER_OPS
-#define HMM_DELTA_AFTER_OPS 0     // measured: 0.653 against 0.630 ms (the operators do not get faster without the delta chains beside them)
-#endif
-#ifndef HMM_DELTA_INTERLEAVED
-#define HMM_DELTA_INTERLEAVED 0     // delta as [gene][sample] for the large batches: parity-green, no gain (15.72 against 15.73 ms), off
-#endif
-#ifndef HMM_BP_AFTER_SWEEPS
-#define HMM_BP_AFTER_SWEEPS 0
-#endif
-#ifndef HMM_XCD_SPAN
-#define HMM_XCD_SPAN 2        // XCDs a chromosome's sample groups are spread over under GBRS_TUNING_HMM_XCD (1, 2 or 4)
-#endif
-#ifndef HMM_XCD_GRIDS
-#define HMM_XCD_GRIDS 0       // batch chain kernels on XCD-aware 1-D grids (GBRS_TUNING_HMM_XCD)
-#endif
-#ifndef HMM_DELTA_SPEC
-#define HMM_DELTA_SPEC 1      // blocked scan: Viterbi values by rank convergence (one chain per block + fix-up) instead of max-plus block operators
-#endif
-#ifndef HMM_BLOCK_GENES
-#define HMM_BLOCK_GENES 40    // genes per block aimed at (at most HMM_BLOCKS_MAX blocks per chromosome)
-#endif
-#ifndef HMM_BLOCKS_MAX
-#define HMM_BLOCKS_MAX 64
-#endif
-
-// The block structures of the handle's chromosomes and the buffers of the blocked scan for n_samples samples.
-#ifndef HMM_HEAD_PERCENT
-#define HMM_HEAD_PERCENT 0    // share of a chromosome's genes that is chained directly while the operators of the rest are built.
-                              // Round 4: built (GBRS_TUNING_HMM_HEAD=20..60), parity-green, SLOWER - beside the operator kernels,
-                              // which keep every CU and the memory system busy, a directly chained block runs at ~1.7 us per step
-                              // instead of 0.4 (wave priority, s_setprio 3, did not change that): 40k genes, one sample 1.06 ms without,
-                              // 1.19 / 1.42 / 1.64 / 1.85 ms with 20 / 30 / 40 / 50 % (profiles/r04_hmm_experiments.txt)
-#endif
-int hmm_prepare_blocks(gbrs_hmm *h) {
+// The block structures of the handle's chromosomes (cut once, by the tuning of the first run that needs them) and the
+// buffers of the blocked scan for n_samples samples.
+int hmm_prepare_blocks(gbrs_hmm *h, const HmmTuning &t) {
     const int S = h->S;
     if (h->n_vb == 0) {
-        int block_genes = HMM_BLOCK_GENES, blocks_max = HMM_BLOCKS_MAX, head_pct = HMM_HEAD_PERCENT;
-        if (const char *env = std::getenv("GBRS_TUNING_HMM_BLOCK_GENES"); env && std::atoi(env) > 1) block_genes = std::atoi(env);
-        if (const char *env = std::getenv("GBRS_TUNING_HMM_BLOCKS_MAX"); env && std::atoi(env) > 0) blocks_max = std::atoi(env);
-        if (const char *env = std::getenv("GBRS_TUNING_HMM_HEAD"); env) head_pct = std::max(0, std::min(90, std::atoi(env)));
+        const int block_genes = t.block_genes, blocks_max = t.blocks_max, head_pct = t.head_pct;
         std::vector<ChromDesc> vf, vb;
         for (int dir = 0; dir < 2; ++dir) {
             std::vector<BlockRange> ranges;
@@ -2827,17 +2766,7 @@ int hmm_flush_emission(gbrs_hmm *h) {
     return GBRS_OK;
 }
 
-#ifndef HMM_PIPE_MIN
-// Samples from which a batch pass runs as two pipelined chromosome groups (emission of group 2 beside the sweeps of group 1).
-// Parity-green and measured slower on one MI355X (256 samples 19.75-19.88 against 16.43-16.53 ms, 128: 13.14-13.18 against
-// 9.21-9.31; profiles/r04_hmm_experiments.txt item 4), so never by default: GBRS_TUNING_HMM_PIPELINE=<samples> switches it on.
-#define HMM_PIPE_MIN (1 << 30)
-#endif
-#ifndef HMM_PIPE_FIRST_PERCENT
-#define HMM_PIPE_FIRST_PERCENT 30   // share of the genes in the group that goes first (the one with the longest chromosome)
-#endif
-
-int hmm_prepare_groups(gbrs_hmm *h) {
+int hmm_prepare_groups(gbrs_hmm *h, const HmmTuning &t) {
     if (h->n_groups) return GBRS_OK;
     const int nc = h->n_chrom;
     // two runs of consecutive chromosomes (a group's genes are one range of the gene axis); the cut that puts about
@@ -2845,9 +2774,7 @@ int hmm_prepare_groups(gbrs_hmm *h) {
     int longest = 0;
     for (int c = 1; c < nc; ++c)
         if (h->chroms[c].n_genes > h->chroms[longest].n_genes) longest = c;
-    int pct = HMM_PIPE_FIRST_PERCENT;
-    if (const char *env = std::getenv("GBRS_TUNING_HMM_PIPE_FIRST"); env && std::atoi(env) > 0 && std::atoi(env) < 100) pct = std::atoi(env);
-    const int64_t want = h->total_genes * pct / 100;
+    const int64_t want = h->total_genes * t.pipe_first_pct / 100;
     int cut = 1;
     if (2 * (int64_t)h->chroms[longest].gene_off <= h->total_genes) {      // longest in the front half: first group = [0, cut)
         int64_t acc = 0;
@@ -2887,27 +2814,78 @@ int hmm_prepare_groups(gbrs_hmm *h) {
     return GBRS_OK;
 }
 
+// ---- launches shared by the one-group pass (hmm_launch) and the pipelined one (hmm_launch_groups) -------------------
+
+// how a run on route r lays `delta` out
+RowMap delta_rows(const gbrs_hmm *h, const HmmRoute &r) {
+    return r.delta_interleaved ? RowMap{1, h->n_samples} : RowMap{h->total_genes, 1};
+}
+
+// S = 36: the MFMA operands of exp(T) and its transpose, made on first use (one-off table work: outside the run's timing)
+int hmm_prepare_mfma_tables(gbrs_hmm *h) {
+    if (h->amat_f.p) return GBRS_OK;
+    GBRS_TRY(h->amat_f.alloc((size_t)h->total_trans * MF_BLK));
+    GBRS_TRY(h->amat_b.alloc((size_t)h->total_trans * MF_BLK));
+    hipLaunchKernelGGL(mfma_blocks_kernel, dim3(4096), dim3(256), 0, h->stream, h->total_trans, h->tprob.p, h->amat_f.p, h->amat_b.p);
+    return GBRS_OK;
+}
+
+// The backpointer rows of the chromosomes [c_lo, c_lo + n_chrom) from their delta rows, by the kernel the route names;
+// max_bp: the longest backpointer run among them.  This one launches the kernels that serve any state count ...
+void launch_backpointers(gbrs_hmm *h, const HmmRoute &r, hipStream_t st, int c_lo, int n_chrom, int max_bp) {
+    const int S = h->S, ns = h->n_samples;
+    if (max_bp <= 0) return;
+    if (r.bp == HmmBp::Lanes) {
+        const int per_wg = std::min(64 * BPL_WAVES, ((ns + 63) / 64) * 64);
+        hipLaunchKernelGGL((viterbi_bp_lanes_kernel<MF_S>), dim3(max_bp, n_chrom, (ns + per_wg - 1) / per_wg), dim3(per_wg), 0, st, ns,
+                           delta_rows(h, r), h->total_bp, h->d_chroms.p + c_lo, h->tprob.p, h->delta.p, h->bp.p);
+    } else if (r.bp == HmmBp::Generic) {
+        hipLaunchKernelGGL(viterbi_bp_kernel, dim3(max_bp, n_chrom), dim3(256), (size_t)S * (S + 1) * sizeof(double), st, S, ns,
+                           h->total_genes, h->total_bp, h->d_chroms.p + c_lo, h->tprob.p, h->delta.p, h->bp.p);
+    }                        // (WithSweep, Chains: written beside the delta values)
+}
+
+// ... and this one those of a chain family as well (QUAD_K: KMAX of the quad chains, 0 for the wave family)
+template <int SS_WAVE, int QUAD_K>
+void launch_backpointers(gbrs_hmm *h, const HmmRoute &r, hipStream_t st, int max_bp) {
+    if (max_bp <= 0) return;
+    if constexpr (QUAD_K > 0) {
+        if (r.bp == HmmBp::Quad)
+            hipLaunchKernelGGL((viterbi_bp_quad_kernel<QUAD_K>), dim3(max_bp, h->n_chrom), dim3(((h->S * 4 + 63) / 64) * 64), 0, st,
+                               h->n_samples, h->total_genes, h->total_bp, h->d_chroms.p, h->tprob_q.p, h->delta.p, h->bp.p);
+    } else {
+        if (r.bp == HmmBp::Wave)
+            hipLaunchKernelGGL((viterbi_bp_wave_kernel<SS_WAVE>), dim3((max_bp + BPW_ROWS - 1) / BPW_ROWS, h->n_chrom), dim3(64), 0, st,
+                               h->n_samples, h->total_genes, h->total_bp, h->d_chroms.p, h->tprob_q.p, h->delta.p, h->bp.p);
+    }
+    launch_backpointers(h, r, st, 0, h->n_chrom, max_bp);
+}
+
+// The backtrace of the chromosomes [c_lo, c_lo + n_chrom): per-chunk exit maps, then states and calls.  only_if
+// ([sample][chromosome] flags, all chromosomes only): walk and write where set; tc: the margins of the path are checked.
+void launch_backtrace(gbrs_hmm *h, hipStream_t st, int c_lo, int n_chrom, int max_bp, const int32_t *only_if, const TieCheck &tc) {
+    const int S = h->S;
+    const int bt_chunks = std::max(1, (max_bp + BT_B - 1) / BT_B);
+    const dim3 bt_grid(bt_chunks, n_chrom, h->n_samples);
+    hipLaunchKernelGGL(backtrace_maps_kernel, bt_grid, dim3(64), (size_t)BT_B * S * sizeof(uint16_t), st, S, h->total_bp,
+                       h->total_chunks, h->d_chroms.p + c_lo, h->bp.p, h->bt_exit.p, only_if);
+    hipLaunchKernelGGL(backtrace_write_kernel, bt_grid, dim3(64), ((size_t)std::max(BT_B, bt_chunks) * S + BT_B) * sizeof(uint16_t),
+                       st, S, h->total_genes, h->total_bp, h->total_genes + h->n_chrom, h->total_chunks, h->n_chrom,
+                       h->d_chroms.p, h->bp.p, h->bt_exit.p, h->last_state.p, h->states.p, h->calls.p, c_lo, only_if, tc);
+}
+
 // A large batch of 36-state samples as two pipelined chromosome groups (see gbrs_hmm above).  Same kernels, same
 // arithmetic and stored quantities as the one-group pass of hmm_launch - only the launches are per group.
-int hmm_launch_groups(gbrs_hmm *h) {
-    constexpr int S = MF_S;
-    GBRS_TRY(hmm_prepare_groups(h));
-    h->delta_rows = RowMap{(int64_t)h->total_genes, 1};
+int hmm_launch_groups(gbrs_hmm *h, const HmmRoute &r, const HmmTuning &t) {
+    GBRS_TRY(hmm_prepare_groups(h, t));
     hipStream_t sa = h->stream;
-    if (!h->amat_f.p) {
-        GBRS_TRY(h->amat_f.alloc((size_t)h->total_trans * MF_BLK));
-        GBRS_TRY(h->amat_b.alloc((size_t)h->total_trans * MF_BLK));
-        hipLaunchKernelGGL(mfma_blocks_kernel, dim3(4096), dim3(256), 0, sa, h->total_trans, h->tprob.p, h->amat_f.p, h->amat_b.p);
-    }
+    GBRS_TRY(hmm_prepare_mfma_tables(h));
     h->logs_ready = false;
-    h->free_backward = true;
-    h->last_blocked = false;
-    h->last_tie_check = false;
+    h->last = r;
     GBRS_HIP_CHECK(hipEventRecord(h->gev_start, sa));
     GBRS_HIP_CHECK(hipEventRecord(h->ev[1], sa));
     const int ns = h->n_samples;
-    int bpl_min = HMM_BPL_MIN;
-    if (const char *env = std::getenv("GBRS_TUNING_HMM_BPLANES"); env) bpl_min = std::atoi(env) > 0 ? std::atoi(env) : INT_MAX;
+    const RowMap rows{h->total_genes, 1};
     for (int g = 0; g < 2; ++g) {
         hipStream_t s0 = g == 0 ? h->stream : h->stream_g[0], s1 = g == 0 ? h->stream_b : h->stream_g[1],
                     s2 = g == 0 ? h->stream_c : h->stream_g[2];
@@ -2928,35 +2906,18 @@ int hmm_launch_groups(gbrs_hmm *h) {
         GBRS_HIP_CHECK(hipStreamWaitEvent(s1, h->gev_em[g], 0));
         GBRS_HIP_CHECK(hipStreamWaitEvent(s2, h->gev_em[g], 0));
         const dim3 mfma_grid((ns + 15) / 16, ncg);
-        hipLaunchKernelGGL((alpha_mfma_kernel<HMM_NSET_M, 1>), mfma_grid, dim3(64), 0, s0, ns, RowMap{h->total_genes, 1}, h->d_chroms.p, ord,
+        hipLaunchKernelGGL((alpha_mfma_kernel<HMM_NSET_M, 1>), mfma_grid, dim3(64), 0, s0, ns, rows, h->d_chroms.p, ord,
                            h->amat_f.p, h->eprob.p, h->peprob.p, h->init_vec.p, h->xsum.p, h->invz.p);
         if (g == 0) GBRS_HIP_CHECK(hipEventRecord(h->ev[2], s0));
-        hipLaunchKernelGGL((backward_mfma_kernel<HMM_NSET_M, 1>), mfma_grid, dim3(64), 0, s1, ns, RowMap{h->total_genes, 1}, h->d_chroms.p, ord,
+        hipLaunchKernelGGL((backward_mfma_kernel<HMM_NSET_M, 1>), mfma_grid, dim3(64), 0, s1, ns, rows, h->d_chroms.p, ord,
                            h->amat_b.p, h->peprob.p, h->bhat.p, h->bscale.p);
         GBRS_HIP_CHECK(hipEventRecord(h->gev_b[g], s1));
         hipLaunchKernelGGL(delta_lanes_kernel, dim3((ns + DL_SAMPLES - 1) / DL_SAMPLES, ncg), dim3(64 * DL_WAVES), 0, s2, ns,
-                           RowMap{h->total_genes, 1}, RowMap{h->total_genes, 1}, h->d_chroms.p, ord, h->tprob.p, h->eprob.p, h->init_vec.p, h->delta.p, h->last_state.p,
+                           rows, rows, h->d_chroms.p, ord, h->tprob.p, h->eprob.p, h->init_vec.p, h->delta.p, h->last_state.p,
                            h->n_chrom);
-        if (h->grp_max_bp[g] > 0) {
-            if (ns >= bpl_min) {
-                const int per_wg = std::min(64 * BPL_WAVES, ((ns + 63) / 64) * 64);
-                hipLaunchKernelGGL((viterbi_bp_lanes_kernel<MF_S>), dim3(h->grp_max_bp[g], ncg, (ns + per_wg - 1) / per_wg), dim3(per_wg), 0,
-                                   s2, ns, RowMap{h->total_genes, 1}, h->total_bp, h->d_chroms.p + c_lo, h->tprob.p, h->delta.p, h->bp.p);
-            } else {
-                hipLaunchKernelGGL(viterbi_bp_kernel, dim3(h->grp_max_bp[g], ncg), dim3(256), (size_t)S * (S + 1) * sizeof(double), s2,
-                                   S, ns, h->total_genes, h->total_bp, h->d_chroms.p + c_lo, h->tprob.p, h->delta.p, h->bp.p);
-            }
-        }
+        launch_backpointers(h, r, s2, c_lo, ncg, h->grp_max_bp[g]);
         if (g == 0) GBRS_HIP_CHECK(hipEventRecord(h->ev_c1, s2));
-        {
-            const int bt_chunks = std::max(1, (h->grp_max_bp[g] + BT_B - 1) / BT_B);
-            const dim3 bt_grid(bt_chunks, ncg, ns);
-            hipLaunchKernelGGL(backtrace_maps_kernel, bt_grid, dim3(64), (size_t)BT_B * S * sizeof(uint16_t), s2, S, h->total_bp,
-                               h->total_chunks, h->d_chroms.p + c_lo, h->bp.p, h->bt_exit.p);
-            hipLaunchKernelGGL(backtrace_write_kernel, bt_grid, dim3(64), ((size_t)std::max(BT_B, bt_chunks) * S + BT_B) * sizeof(uint16_t),
-                               s2, S, h->total_genes, h->total_bp, h->total_genes + h->n_chrom, h->total_chunks, h->n_chrom,
-                               h->d_chroms.p, h->bp.p, h->bt_exit.p, h->last_state.p, h->states.p, h->calls.p, c_lo);
-        }
+        launch_backtrace(h, s2, c_lo, ncg, h->grp_max_bp[g], nullptr, TieCheck{});
         GBRS_HIP_CHECK(hipEventRecord(h->gev_c[g], s2));
         GBRS_HIP_CHECK(hipStreamWaitEvent(s0, h->gev_b[g], 0));
         launch_posterior_range(h, s0, gene_lo, gene_hi - gene_lo);
@@ -2981,45 +2942,234 @@ int hmm_launch_groups(gbrs_hmm *h) {
     return GBRS_OK;
 }
 
-// SS_WAVE > 0: the single-wave chain kernels for that (even, <= 64) state count; otherwise KMAX / MAXT /
-// EXACT select the quad chains (EXACT, S = 4*KMAX > 64) or the generic multi-wave kernels.
-template <int SS_WAVE, int KMAX, int MAXT, bool EXACT>
-int hmm_launch(gbrs_hmm *h) {
-    if (h->emission_pending) {
-        // a large 36-state batch whose emission gbrs_hmm_set_expression left to this run: two pipelined chromosome groups,
-        // provided the batch takes the kernels that pass is made of (MFMA sweeps, samples-on-lanes delta chain)
-        if constexpr (SS_WAVE == MF_S) {
-            int mfma_min = HMM_MFMA_MIN, dl_min = HMM_DLANES_MIN;
-            if (const char *env = std::getenv("GBRS_TUNING_HMM_MFMA"); env) mfma_min = std::atoi(env) > 0 ? std::atoi(env) : INT_MAX;
-            if (const char *env = std::getenv("GBRS_TUNING_HMM_DLANES"); env) dl_min = std::atoi(env) > 0 ? std::atoi(env) : INT_MAX;
-            const char *ng = std::getenv("GBRS_TUNING_HMM_MFMA_NG");
-            if (h->n_samples >= mfma_min && h->n_samples >= dl_min && !(ng && std::atoi(ng) == 2)) return hmm_launch_groups(h);
-        }
-        GBRS_TRY(hmm_flush_emission(h));
+// ---- the three chains of a one-group pass, one function per sweep family; `st` is the chain's stream ---------------
+
+// XCD-aware 1-D grid for `groups` sample groups per chromosome (RowMap::place)
+dim3 xcd_grid(const gbrs_hmm *h, const HmmRoute &r, unsigned groups, RowMap &rmap) {
+    rmap.xcd_groups = (int32_t)groups;
+    rmap.n_order = h->n_chrom;
+    rmap.xcd_span = r.xcd_span;
+    const unsigned sets = 8u / (unsigned)r.xcd_span, per = (groups + r.xcd_span - 1) / r.xcd_span;
+    return dim3(8u * per * (unsigned)((h->n_chrom + sets - 1) / sets));
+}
+
+// rows of the per-sample arrays as the batch kernels address them
+RowMap chain_rows(const gbrs_hmm *h, const HmmRoute &r) {
+    return r.chain_interleaved ? RowMap{1, h->n_samples} : RowMap{h->total_genes, 1};
+}
+
+// grid of the MFMA sweeps: 16 * mfma_groups samples per wavefront; `rows` takes the XCD placement, if any
+dim3 mfma_grid(const gbrs_hmm *h, const HmmRoute &r, RowMap &rows) {
+    const dim3 grid((h->n_samples + 16 * r.mfma_groups - 1) / (16 * r.mfma_groups), h->n_chrom);
+    return (r.xcd_mask & 1) ? xcd_grid(h, r, grid.x, rows) : grid;
+}
+
+void alpha_mfma(gbrs_hmm *h, const HmmRoute &r, hipStream_t st) {
+    auto k = r.mfma_groups == 2 ? &alpha_mfma_kernel<HMM_NSET_M2, 2> : &alpha_mfma_kernel<HMM_NSET_M, 1>;
+    RowMap rows = chain_rows(h, r);
+    const dim3 grid = mfma_grid(h, r, rows);
+    hipLaunchKernelGGL(k, grid, dim3(64), 0, st, h->n_samples, rows, h->d_chroms.p, h->d_order.p, h->amat_f.p, h->eprob.p,
+                       h->peprob.p, h->init_vec.p, h->xsum.p, h->invz.p);
+}
+
+void back_mfma(gbrs_hmm *h, const HmmRoute &r, hipStream_t st) {
+    auto k = r.mfma_groups == 2 ? &backward_mfma_kernel<HMM_NSET_M2, 2> : &backward_mfma_kernel<HMM_NSET_M, 1>;
+    RowMap rows = chain_rows(h, r);
+    const dim3 grid = mfma_grid(h, r, rows);
+    hipLaunchKernelGGL(k, grid, dim3(64), 0, st, h->n_samples, rows, h->d_chroms.p, h->d_order.p, h->amat_b.p, h->peprob.p,
+                       h->bhat.p, h->bscale.p);
+}
+
+void delta_lanes(gbrs_hmm *h, const HmmRoute &r, hipStream_t st) {
+    RowMap rows = chain_rows(h, r);
+    dim3 grid((h->n_samples + DL_SAMPLES - 1) / DL_SAMPLES, h->n_chrom);
+    if (r.xcd_mask & 2) grid = xcd_grid(h, r, grid.x, rows);
+    hipLaunchKernelGGL(delta_lanes_kernel, grid, dim3(64 * DL_WAVES), 0, st, h->n_samples, rows, delta_rows(h, r), h->d_chroms.p,
+                       h->d_order.p, h->tprob.p, h->eprob.p, h->init_vec.p, h->delta.p, h->last_state.p, h->n_chrom);
+}
+
+dim3 wave_grid(const gbrs_hmm *h, const HmmRoute &r) {
+    return dim3(r.batched ? (h->n_samples + HMM_SB - 1) / HMM_SB : h->n_samples, h->n_chrom);
+}
+
+// forward_wave_kernel over whole chromosomes: the alpha or the delta chain by the instance k.  only_if / with_bp: the
+// fallback chains of the blocked scan, which run where a flag is set and write the backpointers in the same pass over T.
+template <class Kernel>
+void launch_forward_wave(gbrs_hmm *h, const HmmRoute &r, Kernel k, hipStream_t st, const int32_t *only_if = nullptr,
+                         bool with_bp = false) {
+    hipLaunchKernelGGL(k, wave_grid(h, r), dim3(64), 0, st, h->n_samples, h->total_genes, h->d_chroms.p, h->d_order.p,
+                       h->tprob_q.p, h->pprob.p, h->eprob.p, h->peprob.p, h->init_vec.p, h->xsum.p, h->invz.p, h->delta.p,
+                       h->last_state.p, (const double *)nullptr, h->n_chrom, 0, only_if, with_bp ? h->bp.p : (uint16_t *)nullptr,
+                       with_bp ? h->total_bp : (int64_t)0);
+}
+
+template <int SS>
+void alpha_wave(gbrs_hmm *h, const HmmRoute &r, hipStream_t st) {
+    launch_forward_wave(h, r, r.batched ? &forward_wave_kernel<SS, HMM_NSET_B, HMM_SB, 0, 18> : &forward_wave_kernel<SS, HMM_NSET, 1, 0, HMM_HOIST_A>, st);
+}
+
+template <int SS>
+void delta_wave(gbrs_hmm *h, const HmmRoute &r, hipStream_t st) {
+    launch_forward_wave(h, r, r.batched ? &forward_wave_kernel<SS, HMM_NSET_B, HMM_SB, 1, 18> : &forward_wave_kernel<SS, HMM_NSET, 1, 1, HMM_HOIST_D>, st);
+}
+
+template <int SS>
+void back_wave(gbrs_hmm *h, const HmmRoute &r, hipStream_t st) {
+    auto k = r.batched ? &backward_wave_kernel<SS, HMM_NSET_B, HMM_SB> : &backward_wave_kernel<SS, HMM_NSET, 1>;
+    hipLaunchKernelGGL(k, wave_grid(h, r), dim3(64), 0, st, h->n_samples, h->total_genes, h->d_chroms.p, h->d_order.p,
+                       h->pprob_t.p, h->peprob.p, h->bhat.p, h->bscale.p, (const double *)nullptr, 0);
+}
+
+// The blocked scan's chains (~40 steps each, ~1,000 wavefronts per kernel; two register sets, fewer hoisted reads)
+// over the forward blocks d_vorder[0][first .. first + count), started from the boundary vectors `inject`.
+template <class Kernel>
+void launch_block_chains(gbrs_hmm *h, Kernel k, hipStream_t st, int first, int count, const double *inject, bool with_bp) {
+    if (count > 0)
+        hipLaunchKernelGGL(k, dim3(h->n_samples, count), dim3(64), 0, st, h->n_samples, h->total_genes, h->d_vfwd.p,
+                           h->d_vorder[0].p + first, h->tprob_q.p, h->pprob.p, h->eprob.p, h->peprob.p, h->init_vec.p, h->xsum.p,
+                           h->invz.p, h->delta.p, h->last_state.p, inject, h->n_chrom, h->n_vb, (const int32_t *)nullptr,
+                           with_bp ? h->bp.p : (uint16_t *)nullptr, with_bp ? h->total_bp : (int64_t)0);
+}
+
+template <int SS>
+void alpha_blocked(gbrs_hmm *h, hipStream_t st) {
+    auto k = &forward_wave_kernel<SS, 2, 1, 0, HMM_HOIST_BLK>;
+    // the directly chained blocks on a stream of their own, beside the operators of the others; the combine
+    // starts from what those chains stored
+    if (h->n_head[0]) {
+        (void)hipStreamWaitEvent(h->stream_h[0], h->ev_fork, 0);
+        launch_block_chains(h, k, h->stream_h[0], 0, h->n_head[0], h->inj_f.p, false);
+        (void)hipEventRecord(h->ev_head[0], h->stream_h[0]);
     }
-    const int S = h->S;
-    const int threads = ((S * 4 + 63) / 64) * 64;
-    const int64_t rows = h->total_genes * h->n_samples;
-    const int bt_chunks = std::max(1, (h->max_bp_rows + BT_B - 1) / BT_B);
-    const dim3 bt_grid(bt_chunks, h->n_chrom, h->n_samples);
-    const size_t bt_maps_lds = (size_t)BT_B * S * sizeof(uint16_t);
-    const size_t bt_write_lds = ((size_t)std::max(BT_B, bt_chunks) * S + BT_B) * sizeof(uint16_t);
-    TieCheck tie_check;                        // set by the blocked scan: the backtrace then checks the margins of its path
-    auto launch_backtrace = [&](hipStream_t st) {
-        hipLaunchKernelGGL(backtrace_maps_kernel, bt_grid, dim3(64), bt_maps_lds, st, S, h->total_bp,
-                           h->total_chunks, h->d_chroms.p, h->bp.p, h->bt_exit.p, (const int32_t *)nullptr);
-        hipLaunchKernelGGL(backtrace_write_kernel, bt_grid, dim3(64), bt_write_lds, st, S, h->total_genes,
-                           h->total_bp, h->total_genes + h->n_chrom, h->total_chunks, h->n_chrom, h->d_chroms.p,
-                           h->bp.p, h->bt_exit.p, h->last_state.p, h->states.p, h->calls.p, 0, (const int32_t *)nullptr,
-                           tie_check);
+    hipLaunchKernelGGL((blockmat_mfma_kernel<0>), dim3(h->n_blk[0], h->n_samples), dim3(64), 0, st, h->total_genes,
+                       h->n_vb, h->d_ranges[0].p, h->amat_f.p, h->peprob.p, h->g_f.p, h->e_f.p);
+    (void)hipEventRecord(h->ev_ops[0], st);
+    if (h->n_head[0]) (void)hipStreamWaitEvent(st, h->ev_head[0], 0);
+    hipLaunchKernelGGL((combine_sumprod_kernel<0>), dim3(h->n_chrom, h->n_samples), dim3(64), 0, st, h->total_genes,
+                       h->n_vb, h->d_ranges[0].p, h->d_first_block[0].p, h->g_f.p, h->e_f.p, h->init_vec.p, h->eprob.p,
+                       h->peprob.p, h->xsum.p, h->inj_f.p);
+    launch_block_chains(h, k, st, h->n_head[0], h->n_blk[0] - h->n_head[0], h->inj_f.p, false);
+}
+
+template <int SS>
+void back_blocked(gbrs_hmm *h, hipStream_t st) {
+    auto chains = [&](hipStream_t q, int first, int count) {
+        if (count > 0)
+            hipLaunchKernelGGL((backward_wave_kernel<SS, 2, 1>), dim3(h->n_samples, count), dim3(64), 0, q, h->n_samples, h->total_genes,
+                               h->d_vbwd.p, h->d_vorder[1].p + first, h->pprob_t.p, h->peprob.p, h->bhat.p, h->bscale.p,
+                               h->inj_b.p, h->n_vb);
     };
-    const dim3 unit_grid(h->n_chrom, h->n_samples);
-    hipStream_t sa = h->stream, sb = h->stream_b, sc = h->stream_c;
-    if (const char *env = std::getenv("GBRS_TUNING_HMM_SERIAL"); env && std::atoi(env)) sb = sc = sa;
+    if (h->n_head[1]) {
+        (void)hipStreamWaitEvent(h->stream_h[1], h->ev_fork, 0);
+        chains(h->stream_h[1], 0, h->n_head[1]);
+        (void)hipEventRecord(h->ev_head[1], h->stream_h[1]);
+    }
+    hipLaunchKernelGGL((blockmat_mfma_kernel<1>), dim3(h->n_blk[1], h->n_samples), dim3(64), 0, st, h->total_genes,
+                       h->n_vb, h->d_ranges[1].p, h->amat_b.p, h->peprob.p, h->g_b.p, h->e_b.p);
+    (void)hipEventRecord(h->ev_ops[1], st);
+    if (h->n_head[1]) (void)hipStreamWaitEvent(st, h->ev_head[1], 0);
+    hipLaunchKernelGGL((combine_sumprod_kernel<1>), dim3(h->n_chrom, h->n_samples), dim3(64), 0, st, h->total_genes,
+                       h->n_vb, h->d_ranges[1].p, h->d_first_block[1].p, h->g_b.p, h->e_b.p, h->init_vec.p, h->eprob.p,
+                       h->peprob.p, h->bhat.p, h->inj_b.p);
+    chains(st, h->n_head[1], h->n_blk[1] - h->n_head[1]);
+}
+
+// rank convergence instead of block operators (hmm_blocked.inc): guess -> chains in all blocks -> fix-up in
+// all blocks -> the unblocked chain for the chromosomes whose flag a fix-up raised (idle otherwise)
+template <int SS>
+void delta_blocked_rank(gbrs_hmm *h, const HmmRoute &r, hipStream_t st) {
+    const dim3 bgrid(h->n_blk[0], h->n_samples);
+    if (r.delta_after_ops) {
+        (void)hipStreamWaitEvent(st, h->ev_ops[0], 0);
+        (void)hipStreamWaitEvent(st, h->ev_ops[1], 0);
+    }
+    hipLaunchKernelGGL(delta_guess_kernel, bgrid, dim3(64), 0, st, h->total_genes, h->n_vb, h->n_chrom,
+                       h->d_ranges[0].p, h->eprob.p, h->inj_d.p, h->dspec_c.p, h->dspec_g.p, h->dspec_fail.p,
+                       h->dspec_tie.p);
+    launch_block_chains(h, &forward_wave_kernel<SS, 2, 1, 1, HMM_HOIST_BLK, true>, st, 0, h->n_blk[0], h->inj_d.p, true);
+    hipLaunchKernelGGL(delta_fixup_kernel<SS>, bgrid, dim3(64), 0, st, h->total_genes, h->n_vb, h->n_chrom,
+                       h->d_ranges[0].p, h->tprob_q.p, h->eprob.p, h->delta.p, h->dspec_c.p, h->dspec_g.p,
+                       h->dspec_fail.p, r.tol_abs, r.tol_rel, h->bp.p, h->total_bp);
+    launch_forward_wave(h, r, &forward_wave_kernel<SS, HMM_NSET, 1, 1, HMM_HOIST_D, true>, st, h->dspec_fail.p, true);
+}
+
+// max-plus block operators (round 3)
+template <int SS>
+void delta_blocked_ops(gbrs_hmm *h, hipStream_t st) {
+    auto k = &forward_wave_kernel<SS, 2, 1, 1, HMM_HOIST_BLK, true>;
+    (void)hipMemsetAsync(h->dspec_tie.p, 0, (size_t)h->n_samples * h->n_chrom * sizeof(int32_t), st);
+    if (h->n_head[0]) {
+        (void)hipStreamWaitEvent(h->stream_h[2], h->ev_fork, 0);
+        launch_block_chains(h, k, h->stream_h[2], 0, h->n_head[0], h->inj_d.p, true);
+        (void)hipEventRecord(h->ev_head[2], h->stream_h[2]);
+    }
+    hipLaunchKernelGGL(blockmat_maxplus_kernel, dim3(h->n_blk[0], h->n_samples), dim3(64 * MP_WAVES), 0, st,
+                       h->total_genes, h->n_vb, h->d_ranges[0].p, h->tprob.p, h->eprob.p, h->g_d.p);
+    if (h->n_head[0]) (void)hipStreamWaitEvent(st, h->ev_head[2], 0);
+    hipLaunchKernelGGL(combine_maxplus_kernel, dim3(h->n_chrom, h->n_samples), dim3(64), 0, st, h->total_genes,
+                       h->n_vb, h->d_ranges[0].p, h->d_first_block[0].p, h->g_d.p, h->init_vec.p, h->eprob.p,
+                       h->delta.p, h->inj_d.p);
+    launch_block_chains(h, k, st, h->n_head[0], h->n_blk[0] - h->n_head[0], h->inj_d.p, true);
+}
+
+// S = 136: the quad chains; MODE 0 alpha, 1 delta, 2 backward
+template <int KMAX, int MODE>
+void chain_quad(gbrs_hmm *h, hipStream_t st) {
+    const double *table = MODE == 0 ? h->pprob.p : MODE == 1 ? h->tprob_q.p : h->pprob_t.p;
+    hipLaunchKernelGGL((group_chain_kernel<4, KMAX, 1, 1, MODE>), dim3(h->n_samples, h->n_chrom), dim3(((h->S * 4 + 63) / 64) * 64), 0,
+                       st, h->total_genes, h->d_chroms.p, h->d_order.p, table, MODE == 1 ? h->eprob.p : h->peprob.p, h->eprob.p,
+                       h->init_vec.p, MODE == 0 ? h->xsum.p : MODE == 1 ? h->delta.p : h->bhat.p,
+                       MODE == 2 ? h->bscale.p : h->invz.p, h->last_state.p);
+}
+
+template <int SS_WAVE, int QUAD_K>
+void launch_alpha(gbrs_hmm *h, const HmmRoute &r, hipStream_t st) {
+    if constexpr (SS_WAVE > 0) {
+        if (r.sweep == HmmSweep::Mfma) alpha_mfma(h, r, st);
+        else if (r.sweep == HmmSweep::Blocked) alpha_blocked<SS_WAVE>(h, st);
+        else alpha_wave<SS_WAVE>(h, r, st);
+    } else {
+        chain_quad<QUAD_K, 0>(h, st);
+    }
+}
+
+template <int SS_WAVE, int QUAD_K>
+void launch_back(gbrs_hmm *h, const HmmRoute &r, hipStream_t st) {
+    if constexpr (SS_WAVE > 0) {
+        if (r.sweep == HmmSweep::Mfma) back_mfma(h, r, st);
+        else if (r.sweep == HmmSweep::Blocked) back_blocked<SS_WAVE>(h, st);
+        else back_wave<SS_WAVE>(h, r, st);
+    } else {
+        chain_quad<QUAD_K, 2>(h, st);
+    }
+}
+
+template <int SS_WAVE, int QUAD_K>
+void launch_delta(gbrs_hmm *h, const HmmRoute &r, hipStream_t st) {
+    if constexpr (SS_WAVE > 0) {
+        if (r.delta == HmmDelta::Lanes) delta_lanes(h, r, st);
+        else if (r.delta == HmmDelta::BlockedRank) delta_blocked_rank<SS_WAVE>(h, r, st);
+        else if (r.delta == HmmDelta::BlockedOps) delta_blocked_ops<SS_WAVE>(h, st);
+        else delta_wave<SS_WAVE>(h, r, st);
+    } else {
+        chain_quad<QUAD_K, 1>(h, st);
+    }
+}
+
+// SS_WAVE > 0: the single-wave chain kernels for that (even, <= 64) state count; otherwise KMAX / MAXT /
+// EXACT select the quad chains (EXACT, S = 4*KMAX > 64) or the generic multi-wave kernels.  r: hmm_route() of this
+// handle and batch - its family is the one the template arguments stand for.
+template <int SS_WAVE, int KMAX, int MAXT, bool EXACT>
+int hmm_launch(gbrs_hmm *h, const HmmRoute &r, const HmmTuning &t) {
     constexpr bool WAVE = SS_WAVE > 0;                // the single-wave recursions (tables in lane order)
     constexpr bool QUAD = !WAVE && EXACT && KMAX * 4 > 64 && KMAX % 2 == 0;   // S = 136: the quad chains (tables in lane order)
+    const int S = h->S;
+    const int64_t rows = h->total_genes * h->n_samples;
+    hipStream_t sa = h->stream, sb = r.serial ? sa : h->stream_b, sc = r.serial ? sa : h->stream_c;
+    if (r.sweep == HmmSweep::Blocked) GBRS_TRY(hmm_prepare_blocks(h, t));
+    if (r.sweep == HmmSweep::Blocked || r.sweep == HmmSweep::Mfma) GBRS_TRY(hmm_prepare_mfma_tables(h));
     h->logs_ready = false;
-    h->free_backward = WAVE || QUAD;                  // those sweeps rescale on their own (beta_corr_kernel)
+    h->last = r;
     GBRS_HIP_CHECK(hipEventRecord(h->ev[1], sa));
     if (!h->pe_ready) {                               // caller-supplied emissions (gbrs_hmm_set_eprob)
         hipLaunchKernelGGL(exp_emission_kernel, dim3((unsigned)((rows * S + 255) / 256)), dim3(256), 0, sa,
@@ -3031,325 +3181,44 @@ int hmm_launch(gbrs_hmm *h) {
         // occupy 40 CUs per chain):  A  alpha -> [join B] beta correction + outputs
         //                            B  free-running backward
         //                            C  delta -> backpointers -> backtrace
-        std::function<void(hipStream_t)> launch_alpha, launch_back, launch_delta;
-        std::function<void(hipStream_t)> launch_tie_fallback;      // blocked scan only: behind the pass, when a flag is up
-        if constexpr (WAVE) {
-            constexpr int SS = SS_WAVE;
-            // Few samples: one sample per wave (latency).  Many samples: HMM_SB samples share each wave's
-            // transition registers (half the block loads per sample; measured best of 1-8 at 64 samples).
-            const bool batched = h->n_samples >= HMM_BATCH_MIN;
-            const dim3 wave_grid(batched ? (h->n_samples + HMM_SB - 1) / HMM_SB : h->n_samples, h->n_chrom);
-            auto k_alpha = batched ? &forward_wave_kernel<SS, HMM_NSET_B, HMM_SB, 0, 18> : &forward_wave_kernel<SS, HMM_NSET, 1, 0, HMM_HOIST_A>;
-            auto k_delta = batched ? &forward_wave_kernel<SS, HMM_NSET_B, HMM_SB, 1, 18> : &forward_wave_kernel<SS, HMM_NSET, 1, 1, HMM_HOIST_D>;
-            auto k_back = batched ? &backward_wave_kernel<SS, HMM_NSET_B, HMM_SB> : &backward_wave_kernel<SS, HMM_NSET, 1>;
-            // the blocked scan's chains (~40 steps each, ~1,000 wavefronts per kernel): two register sets, fewer hoisted reads
-            auto kb_alpha = &forward_wave_kernel<SS, 2, 1, 0, HMM_HOIST_BLK>;
-            auto kb_delta = &forward_wave_kernel<SS, 2, 1, 1, HMM_HOIST_BLK, true>;          // backpointers in the same pass over T
-            auto kf_delta = &forward_wave_kernel<SS, HMM_NSET, 1, 1, HMM_HOIST_D, true>;       // the fallback chain behind the fix-up
-            auto kb_back = &backward_wave_kernel<SS, 2, 1>;
-            // GBRS_TUNING_HMM_MFMA = smallest batch that takes the MFMA sweeps (0: never) - the parity tests run them at 16
-            int mfma_min = HMM_MFMA_MIN;
-            if (const char *env = std::getenv("GBRS_TUNING_HMM_MFMA"); env) mfma_min = std::atoi(env) > 0 ? std::atoi(env) : INT_MAX;
-            const bool mfma = SS == MF_S && h->n_samples >= mfma_min && h->total_trans > 0;
-            // GBRS_TUNING_HMM_BLOCKED = largest batch that takes the blocked scan (0: never)
-            int blocked_max = HMM_BLOCKED_MAX;
-            if (const char *env = std::getenv("GBRS_TUNING_HMM_BLOCKED"); env) blocked_max = std::atoi(env);
-            const bool blocked = SS == MF_S && !mfma && h->n_samples <= blocked_max && h->total_trans > 0;
-            if (blocked) GBRS_TRY(hmm_prepare_blocks(h));
-            h->last_blocked = blocked;
-            h->last_delta_spec = false;
-            if ((mfma || blocked) && !h->amat_f.p) {
-                GBRS_TRY(h->amat_f.alloc((size_t)h->total_trans * MF_BLK));
-                GBRS_TRY(h->amat_b.alloc((size_t)h->total_trans * MF_BLK));
-                hipLaunchKernelGGL(mfma_blocks_kernel, dim3(4096), dim3(256), 0, sa, h->total_trans, h->tprob.p,
-                                   h->amat_f.p, h->amat_b.p);
-                GBRS_HIP_CHECK(hipEventRecord(h->ev[1], sa));        // one-off table work stays outside the run's timing
-            }
-            // sample groups of 16 per wavefront of the MFMA sweeps: 2 from HMM_MFMA_NG2_MIN samples on (GBRS_TUNING_HMM_MFMA_NG = 1 / 2 forces)
-            int mfma_ng = h->n_samples >= HMM_MFMA_NG2_MIN ? 2 : 1;
-            if (const char *env = std::getenv("GBRS_TUNING_HMM_MFMA_NG"); env && (std::atoi(env) == 1 || std::atoi(env) == 2)) mfma_ng = std::atoi(env);
-            const dim3 mfma_grid((h->n_samples + 16 * mfma_ng - 1) / (16 * mfma_ng), h->n_chrom);
-            // rows of the per-sample arrays as the batch kernels address them; GBRS_DIAG_HMM_INTERLEAVED=1 (diagnostic builds; timing only - the
-            // other kernels keep [sample][gene], so the results are wrong): [gene][sample], a step's 16 rows contiguous
-            RowMap chain_rows{h->total_genes, 1};
-#if defined(GBRS_DIAG_BUILD)                     // never in the product library: the switch gives wrong results
-            if (const char *env = std::getenv("GBRS_DIAG_HMM_INTERLEAVED"); env && std::atoi(env)) chain_rows = RowMap{1, h->n_samples};
-#endif
-            // GBRS_TUNING_HMM_XCD=1: the batch chain kernels on XCD-aware 1-D grids (RowMap::place)
-            const int xcd_mask = [] { const char *env = std::getenv("GBRS_TUNING_HMM_XCD"); return env ? std::atoi(env) : HMM_XCD_GRIDS; }();   // 1: sweeps, 2: delta chain
-            int xcd_span = HMM_XCD_SPAN;
-            if (const char *env = std::getenv("GBRS_TUNING_HMM_XCD_SPAN"); env && (std::atoi(env) == 1 || std::atoi(env) == 2 || std::atoi(env) == 4)) xcd_span = std::atoi(env);
-            auto xcd_grid = [&](unsigned groups, RowMap &rmap) {
-                rmap.xcd_groups = (int32_t)groups;
-                rmap.n_order = h->n_chrom;
-                rmap.xcd_span = xcd_span;
-                const unsigned sets = 8u / (unsigned)xcd_span, per = (groups + xcd_span - 1) / xcd_span;
-                return dim3(8u * per * (unsigned)((h->n_chrom + sets - 1) / sets));
-            };
-            RowMap mfma_rows = chain_rows, dl_rows = chain_rows;
-            const dim3 mfma_launch = (xcd_mask & 1) ? xcd_grid(mfma_grid.x, mfma_rows) : mfma_grid;
-            const dim3 dl_grid((h->n_samples + DL_SAMPLES - 1) / DL_SAMPLES, h->n_chrom);
-            const dim3 dl_launch = (xcd_mask & 2) ? xcd_grid(dl_grid.x, dl_rows) : dl_grid;
-            // delta as [gene][sample] when both its writer and its reader are the samples-on-lanes kernels (a step's / a
-            // gene's rows contiguous: the backpointer kernel reads one page per gene instead of one per lane); gbrs_hmm_get
-            // copies a sample's rows out with a stride.  GBRS_TUNING_HMM_DELTA_ROWS=1 switches it on (measured: no gain).
-            {
-                int bplm = HMM_BPL_MIN;
-                if (const char *env = std::getenv("GBRS_TUNING_HMM_BPLANES"); env) bplm = std::atoi(env) > 0 ? std::atoi(env) : INT_MAX;
-                bool il = HMM_DELTA_INTERLEAVED != 0;
-                if (const char *env = std::getenv("GBRS_TUNING_HMM_DELTA_ROWS"); env) il = std::atoi(env) != 0;
-                const bool both = SS == MF_S && h->total_trans > 0 && h->n_samples >= bplm &&
-                                  h->n_samples >= [] { int d = HMM_DLANES_MIN; if (const char *e = std::getenv("GBRS_TUNING_HMM_DLANES"); e) d = std::atoi(e) > 0 ? std::atoi(e) : INT_MAX; return d; }();
-                h->delta_rows = il && both ? RowMap{1, h->n_samples} : RowMap{chain_rows.sample_stride, chain_rows.gene_stride};
-            }
-            launch_alpha = [=](hipStream_t st) {
-                if (mfma) {
-                    auto k = mfma_ng == 2 ? &alpha_mfma_kernel<HMM_NSET_M2, 2> : &alpha_mfma_kernel<HMM_NSET_M, 1>;
-                    hipLaunchKernelGGL(k, mfma_launch, dim3(64), 0, st, h->n_samples, mfma_rows,
-                                       h->d_chroms.p, h->d_order.p, h->amat_f.p, h->eprob.p, h->peprob.p, h->init_vec.p,
-                                       h->xsum.p, h->invz.p);
-                    return;
-                }
-                if (blocked) {
-                    // the directly chained blocks on a stream of their own, beside the operators of the others; the combine
-                    // starts from what those chains stored
-                    auto chains = [&](hipStream_t q, int first, int count) {
-                        if (count > 0)
-                            hipLaunchKernelGGL(kb_alpha, dim3(h->n_samples, count), dim3(64), 0, q, h->n_samples, h->total_genes,
-                                               h->d_vfwd.p, h->d_vorder[0].p + first, h->tprob_q.p, h->pprob.p, h->eprob.p, h->peprob.p,
-                                               h->init_vec.p, h->xsum.p, h->invz.p, h->delta.p, h->last_state.p, h->inj_f.p, h->n_chrom,
-                                               h->n_vb, (const int32_t *)nullptr, (uint16_t *)nullptr, (int64_t)0);
-                    };
-                    if (h->n_head[0]) {
-                        (void)hipStreamWaitEvent(h->stream_h[0], h->ev_fork, 0);
-                        chains(h->stream_h[0], 0, h->n_head[0]);
-                        (void)hipEventRecord(h->ev_head[0], h->stream_h[0]);
-                    }
-                    hipLaunchKernelGGL((blockmat_mfma_kernel<0>), dim3(h->n_blk[0], h->n_samples), dim3(64), 0, st, h->total_genes,
-                                       h->n_vb, h->d_ranges[0].p, h->amat_f.p, h->peprob.p, h->g_f.p, h->e_f.p);
-                    (void)hipEventRecord(h->ev_ops[0], st);
-                    if (h->n_head[0]) (void)hipStreamWaitEvent(st, h->ev_head[0], 0);
-                    hipLaunchKernelGGL((combine_sumprod_kernel<0>), dim3(h->n_chrom, h->n_samples), dim3(64), 0, st, h->total_genes,
-                                       h->n_vb, h->d_ranges[0].p, h->d_first_block[0].p, h->g_f.p, h->e_f.p, h->init_vec.p, h->eprob.p,
-                                       h->peprob.p, h->xsum.p, h->inj_f.p);
-                    chains(st, h->n_head[0], h->n_blk[0] - h->n_head[0]);
-                    return;
-                }
-                hipLaunchKernelGGL(k_alpha, wave_grid, dim3(64), 0, st, h->n_samples, h->total_genes,
-                                   h->d_chroms.p, h->d_order.p, h->tprob_q.p, h->pprob.p, h->eprob.p, h->peprob.p,
-                                   h->init_vec.p, h->xsum.p, h->invz.p, h->delta.p, h->last_state.p, (const double *)nullptr,
-                                   h->n_chrom, 0, (const int32_t *)nullptr, (uint16_t *)nullptr, (int64_t)0);
-            };
-            launch_back = [=](hipStream_t st) {
-                if (mfma) {
-                    auto k = mfma_ng == 2 ? &backward_mfma_kernel<HMM_NSET_M2, 2> : &backward_mfma_kernel<HMM_NSET_M, 1>;
-                    hipLaunchKernelGGL(k, mfma_launch, dim3(64), 0, st, h->n_samples,
-                                       mfma_rows, h->d_chroms.p, h->d_order.p, h->amat_b.p, h->peprob.p, h->bhat.p,
-                                       h->bscale.p);
-                    return;
-                }
-                if (blocked) {
-                    auto chains = [&](hipStream_t q, int first, int count) {
-                        if (count > 0)
-                            hipLaunchKernelGGL(kb_back, dim3(h->n_samples, count), dim3(64), 0, q, h->n_samples, h->total_genes,
-                                               h->d_vbwd.p, h->d_vorder[1].p + first, h->pprob_t.p, h->peprob.p, h->bhat.p, h->bscale.p,
-                                               h->inj_b.p, h->n_vb);
-                    };
-                    if (h->n_head[1]) {
-                        (void)hipStreamWaitEvent(h->stream_h[1], h->ev_fork, 0);
-                        chains(h->stream_h[1], 0, h->n_head[1]);
-                        (void)hipEventRecord(h->ev_head[1], h->stream_h[1]);
-                    }
-                    hipLaunchKernelGGL((blockmat_mfma_kernel<1>), dim3(h->n_blk[1], h->n_samples), dim3(64), 0, st, h->total_genes,
-                                       h->n_vb, h->d_ranges[1].p, h->amat_b.p, h->peprob.p, h->g_b.p, h->e_b.p);
-                    (void)hipEventRecord(h->ev_ops[1], st);
-                    if (h->n_head[1]) (void)hipStreamWaitEvent(st, h->ev_head[1], 0);
-                    hipLaunchKernelGGL((combine_sumprod_kernel<1>), dim3(h->n_chrom, h->n_samples), dim3(64), 0, st, h->total_genes,
-                                       h->n_vb, h->d_ranges[1].p, h->d_first_block[1].p, h->g_b.p, h->e_b.p, h->init_vec.p, h->eprob.p,
-                                       h->peprob.p, h->bhat.p, h->inj_b.p);
-                    chains(st, h->n_head[1], h->n_blk[1] - h->n_head[1]);
-                    return;
-                }
-                hipLaunchKernelGGL(k_back, wave_grid, dim3(64), 0, st, h->n_samples, h->total_genes,
-                                   h->d_chroms.p, h->d_order.p, h->pprob_t.p, h->peprob.p, h->bhat.p, h->bscale.p,
-                                   (const double *)nullptr, 0);
-            };
-            // GBRS_TUNING_HMM_DLANES = smallest batch that takes the samples-on-lanes delta chain (0: never)
-            int dl_min = HMM_DLANES_MIN;
-            if (const char *env = std::getenv("GBRS_TUNING_HMM_DLANES"); env) dl_min = std::atoi(env) > 0 ? std::atoi(env) : INT_MAX;
-            const bool dlanes = SS == MF_S && h->n_samples >= dl_min && h->total_trans > 0;
-            // GBRS_TUNING_HMM_DELTA_SPEC=0: the blocked scan's delta through max-plus block operators (round 3) instead of rank
-            // convergence; GBRS_TUNING_HMM_DELTA_TOL=<absolute tolerance> (negative: no block ever converges - every chromosome
-            // takes the fallback chain; the tests use it)
-            bool delta_spec = blocked && HMM_DELTA_SPEC != 0;
-            if (const char *env = std::getenv("GBRS_TUNING_HMM_DELTA_SPEC"); env) delta_spec = blocked && std::atoi(env) != 0;
-            double delta_tol_abs = 1e-9, delta_tol_rel = 1e-13;
-            if (const char *env = std::getenv("GBRS_TUNING_HMM_DELTA_TOL"); env) {
-                delta_tol_abs = std::atof(env);
-                if (delta_tol_abs < 0.0) delta_tol_rel = 0.0;
-            }
-            h->last_delta_spec = delta_spec;
-            launch_delta = [=](hipStream_t st) {
-                if (dlanes) {
-                    hipLaunchKernelGGL(delta_lanes_kernel, dl_launch, dim3(64 * DL_WAVES), 0, st,
-                                       h->n_samples, dl_rows, h->delta_rows, h->d_chroms.p, h->d_order.p, h->tprob.p, h->eprob.p,
-                                       h->init_vec.p, h->delta.p, h->last_state.p, h->n_chrom);
-                    return;
-                }
-                if (blocked) {
-                    auto chains = [&](hipStream_t q, int first, int count) {
-                        if (count > 0)
-                            hipLaunchKernelGGL(kb_delta, dim3(h->n_samples, count), dim3(64), 0, q, h->n_samples, h->total_genes,
-                                               h->d_vfwd.p, h->d_vorder[0].p + first, h->tprob_q.p, h->pprob.p, h->eprob.p, h->peprob.p,
-                                               h->init_vec.p, h->xsum.p, h->invz.p, h->delta.p, h->last_state.p, h->inj_d.p, h->n_chrom,
-                                               h->n_vb, (const int32_t *)nullptr, h->bp.p, h->total_bp);
-                    };
-                    if (delta_spec) {
-                        // rank convergence instead of block operators (hmm_blocked.inc): guess -> chains in all blocks -> fix-up in
-                        // all blocks -> the unblocked chain for the chromosomes whose flag a fix-up raised (idle otherwise)
-                        const dim3 bgrid(h->n_blk[0], h->n_samples);
-                        // GBRS_TUNING_HMM_DELTA_AFTER_OPS=1: the delta side (the short one) behind the two operator kernels instead
-                        // of beside them - measured: the operators are no faster alone (backward side 0.556 against 0.563 ms) and
-                        // the forward side gets longer (0.549 against 0.496): off.
-                        if (const char *env = std::getenv("GBRS_TUNING_HMM_DELTA_AFTER_OPS"); env ? std::atoi(env) != 0 : HMM_DELTA_AFTER_OPS != 0) {
-                            (void)hipStreamWaitEvent(st, h->ev_ops[0], 0);
-                            (void)hipStreamWaitEvent(st, h->ev_ops[1], 0);
-                        }
-                        hipLaunchKernelGGL(delta_guess_kernel, bgrid, dim3(64), 0, st, h->total_genes, h->n_vb, h->n_chrom,
-                                           h->d_ranges[0].p, h->eprob.p, h->inj_d.p, h->dspec_c.p, h->dspec_g.p, h->dspec_fail.p,
-                                           h->dspec_tie.p);
-                        chains(st, 0, h->n_blk[0]);
-                        hipLaunchKernelGGL(delta_fixup_kernel<SS>, bgrid, dim3(64), 0, st, h->total_genes, h->n_vb, h->n_chrom,
-                                           h->d_ranges[0].p, h->tprob_q.p, h->eprob.p, h->delta.p, h->dspec_c.p, h->dspec_g.p,
-                                           h->dspec_fail.p, delta_tol_abs, delta_tol_rel, h->bp.p, h->total_bp);
-                        hipLaunchKernelGGL(kf_delta, wave_grid, dim3(64), 0, st, h->n_samples, h->total_genes,
-                                           h->d_chroms.p, h->d_order.p, h->tprob_q.p, h->pprob.p, h->eprob.p, h->peprob.p,
-                                           h->init_vec.p, h->xsum.p, h->invz.p, h->delta.p, h->last_state.p, (const double *)nullptr,
-                                           h->n_chrom, 0, (const int32_t *)h->dspec_fail.p, h->bp.p, h->total_bp);
-                        return;
-                    }
-                    (void)hipMemsetAsync(h->dspec_tie.p, 0, (size_t)h->n_samples * h->n_chrom * sizeof(int32_t), st);
-                    if (h->n_head[0]) {
-                        (void)hipStreamWaitEvent(h->stream_h[2], h->ev_fork, 0);
-                        chains(h->stream_h[2], 0, h->n_head[0]);
-                        (void)hipEventRecord(h->ev_head[2], h->stream_h[2]);
-                    }
-                    hipLaunchKernelGGL(blockmat_maxplus_kernel, dim3(h->n_blk[0], h->n_samples), dim3(64 * MP_WAVES), 0, st,
-                                       h->total_genes, h->n_vb, h->d_ranges[0].p, h->tprob.p, h->eprob.p, h->g_d.p);
-                    if (h->n_head[0]) (void)hipStreamWaitEvent(st, h->ev_head[2], 0);
-                    hipLaunchKernelGGL(combine_maxplus_kernel, dim3(h->n_chrom, h->n_samples), dim3(64), 0, st, h->total_genes,
-                                       h->n_vb, h->d_ranges[0].p, h->d_first_block[0].p, h->g_d.p, h->init_vec.p, h->eprob.p,
-                                       h->delta.p, h->inj_d.p);
-                    chains(st, h->n_head[0], h->n_blk[0] - h->n_head[0]);
-                    return;
-                }
-                hipLaunchKernelGGL(k_delta, wave_grid, dim3(64), 0, st, h->n_samples, h->total_genes,
-                                   h->d_chroms.p, h->d_order.p, h->tprob_q.p, h->pprob.p, h->eprob.p, h->peprob.p,
-                                   h->init_vec.p, h->xsum.p, h->invz.p, h->delta.p, h->last_state.p, (const double *)nullptr,
-                                   h->n_chrom, 0, (const int32_t *)nullptr, (uint16_t *)nullptr, (int64_t)0);
-            };
-            // The blocked scan's vectors are the sequential chain's up to rounding (and, by rank convergence, up to the fix-up's
-            // acceptance spread), so a decision of the backtrace that the sequential chain takes by less than that - an exact
-            // tie, which its first-index rule decides, or a near-tie - may fall the other way.  The backtrace checks the
-            // margins of the path it writes (TieCheck) and raises the chromosome's flag where one is that close; the host reads
-            // the flags when the pass is done, and only if one is up do the unblocked chain and the backtrace run again, for the
-            // flagged chromosomes (three launches that would idle through every other pass).
-            if (blocked && !dlanes) {                   // launch_delta takes the samples-on-lanes chain first: no blocks' vectors then
-                tie_check.delta = h->delta.p;
-                tie_check.tprob = h->tprob.p;
-                tie_check.first_block = h->d_first_block[0].p;
-                tie_check.fail = delta_spec ? h->dspec_fail.p : nullptr;
-                tie_check.tie = h->dspec_tie.p;
-                tie_check.tol_abs = delta_tol_abs;
-                tie_check.tol_rel = delta_tol_rel;
-                launch_tie_fallback = [=](hipStream_t st) {
-                    hipLaunchKernelGGL(kf_delta, wave_grid, dim3(64), 0, st, h->n_samples, h->total_genes,
-                                       h->d_chroms.p, h->d_order.p, h->tprob_q.p, h->pprob.p, h->eprob.p, h->peprob.p,
-                                       h->init_vec.p, h->xsum.p, h->invz.p, h->delta.p, h->last_state.p, (const double *)nullptr,
-                                       h->n_chrom, 0, (const int32_t *)h->dspec_tie.p, h->bp.p, h->total_bp);
-                    hipLaunchKernelGGL(backtrace_maps_kernel, bt_grid, dim3(64), bt_maps_lds, st, S, h->total_bp,
-                                       h->total_chunks, h->d_chroms.p, h->bp.p, h->bt_exit.p, (const int32_t *)h->dspec_tie.p);
-                    hipLaunchKernelGGL(backtrace_write_kernel, bt_grid, dim3(64), bt_write_lds, st, S, h->total_genes,
-                                       h->total_bp, h->total_genes + h->n_chrom, h->total_chunks, h->n_chrom, h->d_chroms.p,
-                                       h->bp.p, h->bt_exit.p, h->last_state.p, h->states.p, h->calls.p, 0,
-                                       (const int32_t *)h->dspec_tie.p);
-                };
-            }
-        } else {
-            const dim3 quad_grid(h->n_samples, h->n_chrom), quad_block(threads);
-            launch_alpha = [=](hipStream_t st) {
-                hipLaunchKernelGGL((group_chain_kernel<4, KMAX, 1, 1, 0>), quad_grid, quad_block, 0, st, h->total_genes,
-                                   h->d_chroms.p, h->d_order.p, h->pprob.p, h->peprob.p, h->eprob.p, h->init_vec.p,
-                                   h->xsum.p, h->invz.p, h->last_state.p);
-            };
-            launch_back = [=](hipStream_t st) {
-                hipLaunchKernelGGL((group_chain_kernel<4, KMAX, 1, 1, 2>), quad_grid, quad_block, 0, st, h->total_genes,
-                                   h->d_chroms.p, h->d_order.p, h->pprob_t.p, h->peprob.p, h->eprob.p, h->init_vec.p,
-                                   h->bhat.p, h->bscale.p, h->last_state.p);
-            };
-            launch_delta = [=](hipStream_t st) {
-                hipLaunchKernelGGL((group_chain_kernel<4, KMAX, 1, 1, 1>), quad_grid, quad_block, 0, st, h->total_genes,
-                                   h->d_chroms.p, h->d_order.p, h->tprob_q.p, h->eprob.p, h->eprob.p, h->init_vec.p,
-                                   h->delta.p, h->invz.p, h->last_state.p);
-            };
+        constexpr int QUAD_K = QUAD ? KMAX : 0;
+        // The blocked scan's backtrace checks the margins of the path it writes (TieCheck) and raises the chromosome's flag
+        // where a decision is inside the error of the blocks' vectors; the host reads the flags when the pass is done, and
+        // only if one is up do the unblocked chain and the backtrace run again, for the flagged chromosomes (three launches
+        // that would idle through every other pass).
+        TieCheck tie_check;
+        if (r.tie_check) {
+            tie_check.delta = h->delta.p;
+            tie_check.tprob = h->tprob.p;
+            tie_check.first_block = h->d_first_block[0].p;
+            tie_check.fail = r.delta == HmmDelta::BlockedRank ? h->dspec_fail.p : nullptr;
+            tie_check.tie = h->dspec_tie.p;
+            tie_check.tol_abs = r.tol_abs;
+            tie_check.tol_rel = r.tol_rel;
         }
-        const size_t bp_lds = (size_t)S * (S + 1) * sizeof(double);
-        // GBRS_TUNING_HMM_BPLANES = smallest batch that takes the samples-on-lanes backpointer kernel (0: never)
-        int bpl_min = HMM_BPL_MIN;
-        if (const char *env = std::getenv("GBRS_TUNING_HMM_BPLANES"); env) bpl_min = std::atoi(env) > 0 ? std::atoi(env) : INT_MAX;
         GBRS_HIP_CHECK(hipEventRecord(h->ev_fork, sa));
         GBRS_HIP_CHECK(hipStreamWaitEvent(sb, h->ev_fork, 0));
         GBRS_HIP_CHECK(hipStreamWaitEvent(sc, h->ev_fork, 0));
-        // GBRS_DIAG_HMM_SKIP=<letters of a, b, c, p, v> (diagnostic builds, -DGBRS_DIAG_BUILD; timing only: wrong results): leave the alpha / backward / delta chain, the
-        // posterior, the backpointers + backtrace out of the pass
-#if defined(GBRS_DIAG_BUILD)                         // never in the product library: the switch gives wrong results
-        const char *skip = std::getenv("GBRS_DIAG_HMM_SKIP");
-#else
-        const char *skip = nullptr;
-#endif
-        auto skipped = [&](char c) { return skip && std::strchr(skip, c) != nullptr; };
-        if (!skipped('a')) launch_alpha(sa);
+        if (!t.skips('a')) launch_alpha<SS_WAVE, QUAD_K>(h, r, sa);
         GBRS_HIP_CHECK(hipEventRecord(h->ev[2], sa));
-        if (const char *env = std::getenv("GBRS_TUNING_HMM_BACK_AFTER"); env && std::atoi(env))
-            GBRS_HIP_CHECK(hipStreamWaitEvent(sb, h->ev[2], 0));
-        if (!skipped('b')) launch_back(sb);
+        if (r.back_after) GBRS_HIP_CHECK(hipStreamWaitEvent(sb, h->ev[2], 0));
+        if (!t.skips('b')) launch_back<SS_WAVE, QUAD_K>(h, r, sb);
         GBRS_HIP_CHECK(hipEventRecord(h->ev_b, sb));
-        if (!skipped('c')) launch_delta(sc);
-        // GBRS_TUNING_HMM_BP_AFTER=1: the backpointer kernel (one sample per lane: a cache line and a page per lane and load)
-        // behind the sweeps instead of beside them
-        if (const char *env = std::getenv("GBRS_TUNING_HMM_BP_AFTER"); env ? std::atoi(env) != 0 : HMM_BP_AFTER_SWEEPS != 0) {
+        if (!t.skips('c')) launch_delta<SS_WAVE, QUAD_K>(h, r, sc);
+        if (r.bp_after) {
             GBRS_HIP_CHECK(hipStreamWaitEvent(sc, h->ev[2], 0));
             GBRS_HIP_CHECK(hipStreamWaitEvent(sc, h->ev_b, 0));
         }
-        if (h->max_bp_rows > 0 && !h->last_blocked && !skipped('v')) {     // the blocked scan's delta chains write the backpointers themselves
-            if constexpr (QUAD)
-                hipLaunchKernelGGL((viterbi_bp_quad_kernel<KMAX>), dim3(h->max_bp_rows, h->n_chrom), dim3(threads), 0,
-                                   sc, h->n_samples, h->total_genes, h->total_bp, h->d_chroms.p, h->tprob_q.p,
-                                   h->delta.p, h->bp.p);
-            else if (WAVE && h->n_samples <= 4) {
-                if constexpr (WAVE)
-                    hipLaunchKernelGGL((viterbi_bp_wave_kernel<(WAVE ? SS_WAVE : 2)>), dim3((h->max_bp_rows + BPW_ROWS - 1) / BPW_ROWS, h->n_chrom),
-                                       dim3(64), 0, sc, h->n_samples, h->total_genes, h->total_bp, h->d_chroms.p,
-                                       h->tprob_q.p, h->delta.p, h->bp.p);
-            } else if (WAVE && SS_WAVE == MF_S && h->n_samples >= bpl_min) {
-                const int per_wg = std::min(64 * BPL_WAVES, ((h->n_samples + 63) / 64) * 64);
-                hipLaunchKernelGGL((viterbi_bp_lanes_kernel<MF_S>), dim3(h->max_bp_rows, h->n_chrom, (h->n_samples + per_wg - 1) / per_wg),
-                                   dim3(per_wg), 0, sc, h->n_samples, h->delta_rows, h->total_bp, h->d_chroms.p, h->tprob.p,
-                                   h->delta.p, h->bp.p);
-            } else
-                hipLaunchKernelGGL(viterbi_bp_kernel, dim3(h->max_bp_rows, h->n_chrom), dim3(256),
-                                   bp_lds, sc, S, h->n_samples, h->total_genes,
-                                   h->total_bp, h->d_chroms.p, h->tprob.p, h->delta.p, h->bp.p);
-        }
+        if (!t.skips('v')) launch_backpointers<SS_WAVE, QUAD_K>(h, r, sc, h->max_bp_rows);
         GBRS_HIP_CHECK(hipEventRecord(h->ev_c1, sc));
-        if (!skipped('v')) launch_backtrace(sc);
-        if (h->last_delta_spec)                       // behind everything that reads the blocks' vectors as the fix-up left them
+        if (!t.skips('v')) launch_backtrace(h, sc, 0, h->n_chrom, h->max_bp_rows, nullptr, tie_check);
+        if (r.delta == HmmDelta::BlockedRank)         // behind everything that reads the blocks' vectors as the fix-up left them
             hipLaunchKernelGGL(delta_apply_kernel, dim3(h->n_blk[0], h->n_samples), dim3(64), 0, sc, h->total_genes, h->n_vb,
                                h->n_chrom, h->d_ranges[0].p, h->d_first_block[0].p, h->dspec_c.p, h->dspec_g.p,
                                h->dspec_fail.p, h->dspec_tie.p, h->delta.p);
         GBRS_HIP_CHECK(hipEventRecord(h->ev_c, sc));
         GBRS_HIP_CHECK(hipStreamWaitEvent(sa, h->ev_b, 0));
-        if (!skipped('p')) launch_posterior(h, sa);   // the posterior is scale free: no beta correction needed
+        if (!t.skips('p')) launch_posterior(h, sa);   // the posterior is scale free: no beta correction needed
         GBRS_HIP_CHECK(hipEventRecord(h->ev[3], sa));
         GBRS_HIP_CHECK(hipStreamWaitEvent(sa, h->ev_c, 0));
         GBRS_HIP_CHECK(hipEventRecord(h->ev[4], sa));
@@ -3364,35 +3233,38 @@ int hmm_launch(gbrs_hmm *h) {
         if (hipEventElapsedTime(&ms, h->ev_fork, h->ev[3]) == hipSuccess) h->t_bwd = ms;
         if (hipEventElapsedTime(&ms, h->ev_c1, h->ev_c) == hipSuccess) h->t_bt = ms;
         if (hipEventElapsedTime(&ms, h->ev[1], h->ev[4]) == hipSuccess) h->t_run = ms;
-        h->last_tie_check = tie_check.tie && !skipped('v');
-        if (h->last_tie_check) {
-            std::vector<int32_t> tie((size_t)h->n_samples * h->n_chrom);
-            GBRS_HIP_CHECK(hipMemcpy(tie.data(), h->dspec_tie.p, tie.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-            if (std::any_of(tie.begin(), tie.end(), [](int32_t f) { return f != 0; })) {
-                GBRS_HIP_CHECK(hipEventRecord(h->ev_c1, sc));
-                launch_tie_fallback(sc);
-                GBRS_HIP_CHECK(hipEventRecord(h->ev_c, sc));
-                GBRS_HIP_CHECK(hipGetLastError());
-                GBRS_HIP_CHECK(hipStreamSynchronize(sc));
-                if (hipEventElapsedTime(&ms, h->ev_c1, h->ev_c) == hipSuccess) {      // part of the pass: in its times
-                    h->t_bt += ms;
-                    h->t_run += ms;
+        if constexpr (WAVE) {
+            if (r.tie_check) {
+                std::vector<int32_t> tie((size_t)h->n_samples * h->n_chrom);
+                GBRS_HIP_CHECK(hipMemcpy(tie.data(), h->dspec_tie.p, tie.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+                if (std::any_of(tie.begin(), tie.end(), [](int32_t f) { return f != 0; })) {
+                    GBRS_HIP_CHECK(hipEventRecord(h->ev_c1, sc));
+                    launch_forward_wave(h, r, &forward_wave_kernel<SS_WAVE, HMM_NSET, 1, 1, HMM_HOIST_D, true>, sc, h->dspec_tie.p, true);
+                    launch_backtrace(h, sc, 0, h->n_chrom, h->max_bp_rows, h->dspec_tie.p, TieCheck{});
+                    GBRS_HIP_CHECK(hipEventRecord(h->ev_c, sc));
+                    GBRS_HIP_CHECK(hipGetLastError());
+                    GBRS_HIP_CHECK(hipStreamSynchronize(sc));
+                    if (hipEventElapsedTime(&ms, h->ev_c1, h->ev_c) == hipSuccess) {      // part of the pass: in its times
+                        h->t_bt += ms;
+                        h->t_run += ms;
+                    }
                 }
             }
         }
         return GBRS_OK;
     } else {
+        const int threads = ((S * 4 + 63) / 64) * 64;
         hipLaunchKernelGGL((forward_viterbi_kernel<KMAX, MAXT, EXACT>), dim3(h->n_chrom, h->n_samples, 2), dim3(threads),
                            2 * S * sizeof(double), sa, S, h->total_genes, h->total_bp, h->d_chroms.p,
                            h->tprob.p, h->pprob.p, h->eprob.p, h->peprob.p, h->init_vec.p, h->xsum.p,
                            h->invz.p, h->delta.p, h->bp.p, h->last_state.p);
         GBRS_HIP_CHECK(hipEventRecord(h->ev[2], sa));
-        hipLaunchKernelGGL((backward_kernel<KMAX, MAXT, EXACT>), unit_grid, dim3(threads),
+        hipLaunchKernelGGL((backward_kernel<KMAX, MAXT, EXACT>), dim3(h->n_chrom, h->n_samples), dim3(threads),
                            2 * S * sizeof(double), sa, S, h->total_genes, h->d_chroms.p, h->pprob_t.p,
                            h->peprob.p, h->invz.p, h->bhat.p);
         launch_posterior(h, sa);
         GBRS_HIP_CHECK(hipEventRecord(h->ev[3], sa));
-        launch_backtrace(sa);
+        launch_backtrace(h, sa, 0, h->n_chrom, h->max_bp_rows, nullptr, TieCheck{});
         GBRS_HIP_CHECK(hipEventRecord(h->ev[4], sa));
         GBRS_HIP_CHECK(hipGetLastError());
         GBRS_HIP_CHECK(hipStreamSynchronize(sa));
@@ -3558,11 +3430,8 @@ int gbrs_hmm_set_expression(gbrs_hmm_t *h, int n_samples, const double *const *e
     // Large 36-state batches: the emission kernel is left to the run, which launches it per chromosome group in front of
     // that group's chains (hmm_launch_groups) - the second group's emission then runs beside the first group's chains.
     // GBRS_TUNING_HMM_PIPELINE = smallest batch that does so (0: never).
-    int pipe_min = HMM_PIPE_MIN;
-    if (const char *env = std::getenv("GBRS_TUNING_HMM_PIPELINE"); env) pipe_min = std::atoi(env) > 0 ? std::atoi(env) : INT_MAX;
-    h->emission_pending = false;
-    if (H == EM_LANES && h->S == MF_S && n_samples >= pipe_min && n_samples >= EM_BATCH_MIN && h->n_chrom >= 2 && h->total_trans > 0) {
-        h->emission_pending = true;
+    h->emission_pending = hmm_defers_emission(hmm_shape(h), hmm_tuning_from_env(), H == EM_LANES && n_samples >= EM_BATCH_MIN);
+    if (h->emission_pending) {
         h->em_thr = expr_threshold;
         h->em_sigma = sigma;
     } else if (H == EM_LANES && n_samples >= EM_BATCH_MIN) {
@@ -3614,17 +3483,24 @@ int gbrs_hmm_run(gbrs_hmm_t *h) {
     if (!h->have_eprob) return fail(GBRS_ERR_STATE, "no expression / emission data set");
     GBRS_TRY(select_device(h->device));
     const int S = h->S;
+    const HmmTuning t = hmm_tuning_from_env();
+    const HmmRoute r = hmm_route(hmm_shape(h), t, h->emission_pending);
     int rc;
-    // 4 lanes per state, KMAX = ceil(S / 4); the two production shapes (DO: H = 8, CC-style:
-    // H = 16) divide evenly and get predicate-free instantiations
-    if (S == 36) rc = hmm_launch<36, 9, 192, true>(h);            // 8 founders
-    else if (S == 28) rc = hmm_launch<28, 12, 192, false>(h);     // 7
-    else if (S == 10) rc = hmm_launch<10, 12, 192, false>(h);     // 4
-    else if (S == 6) rc = hmm_launch<6, 12, 192, false>(h);       // 3
-    else if (S == 136) rc = hmm_launch<0, 34, 576, true>(h);      // 16
-    else if (S <= 48) rc = hmm_launch<0, 12, 192, false>(h);
-    else if (S <= 64) rc = hmm_launch<0, 16, 256, false>(h);
-    else rc = hmm_launch<0, 34, 576, false>(h);        // S <= 136 (MAX_H = 16)
+    if (r.grouped) {
+        rc = hmm_launch_groups(h, r, t);
+    } else {
+        GBRS_TRY(hmm_flush_emission(h));      // a deferred emission on a route that is not made of the grouped pass's kernels
+        // 4 lanes per state, KMAX = ceil(S / 4); the two production shapes (DO: H = 8, CC-style:
+        // H = 16) divide evenly and get predicate-free instantiations
+        if (S == 36) rc = hmm_launch<36, 9, 192, true>(h, r, t);            // 8 founders
+        else if (S == 28) rc = hmm_launch<28, 12, 192, false>(h, r, t);     // 7
+        else if (S == 10) rc = hmm_launch<10, 12, 192, false>(h, r, t);     // 4
+        else if (S == 6) rc = hmm_launch<6, 12, 192, false>(h, r, t);       // 3
+        else if (S == 136) rc = hmm_launch<0, 34, 576, true>(h, r, t);      // 16
+        else if (S <= 48) rc = hmm_launch<0, 12, 192, false>(h, r, t);
+        else if (S <= 64) rc = hmm_launch<0, 16, 256, false>(h, r, t);
+        else rc = hmm_launch<0, 34, 576, false>(h, r, t);        // S <= 136 (MAX_H = 16)
+    }
     if (rc == GBRS_OK) h->ran = true;
     return rc;
 }
@@ -3653,8 +3529,8 @@ int gbrs_hmm_get(gbrs_hmm_t *h, int sample, int chrom, double *gamma, int32_t *s
     if (alpha) GBRS_TRY(fetch_t(h->alpha.p, alpha));
     if (beta) GBRS_TRY(fetch_t(h->beta.p, beta));
     if (delta) {
-        if (h->delta_rows.gene_stride > 1) {         // [gene][sample]: the sample's rows are gene_stride rows apart
-            const RowMap &m = h->delta_rows;
+        if (h->last.delta_interleaved) {             // [gene][sample]: the sample's rows are gene_stride rows apart
+            const RowMap m = delta_rows(h, h->last);
             GBRS_HIP_CHECK(hipMemcpy2D(tmp.data(), (size_t)S * sizeof(double),
                                        h->delta.p + ((size_t)sample * m.sample_stride + (size_t)cd.gene_off * m.gene_stride) * S,
                                        (size_t)m.gene_stride * S * sizeof(double), (size_t)S * sizeof(double), (size_t)n,
@@ -3689,13 +3565,13 @@ int gbrs_hmm_info(gbrs_hmm_t *h, gbrs_hmm_info_t *info) {
     info->num_states = h->S;
     info->n_samples = h->n_samples;
     std::vector<int32_t> tie((size_t)h->n_samples * h->n_chrom, 0);
-    if (h->last_tie_check && h->n_blk[0] > 0) {
+    if (h->last.tie_check && h->n_blk[0] > 0) {
         // blocked scan, either delta scheme: chromosomes that a close decision of the path sent to the unblocked chain
         GBRS_TRY(select_device(h->device));
         GBRS_HIP_CHECK(hipMemcpy(tie.data(), h->dspec_tie.p, tie.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
         for (int32_t t : tie) info->last_delta_tie_fallbacks += t != 0;
     }
-    if (h->last_delta_spec && h->n_blk[0] > 0) {
+    if (h->last.delta == HmmDelta::BlockedRank && h->n_blk[0] > 0) {
         // how the rank-convergence delta of the last run went: blocks fixed up, the longest fix-up, chains recomputed
         GBRS_TRY(select_device(h->device));
         // (a chromosome counts as recomputed whether a fix-up or a close decision of its path sent it to the unblocked chain)

@@ -174,6 +174,40 @@ def test_blocked_scan_two_samples_all_delta_routes(delta_route, monkeypatch):
     hmm.close()
 
 
+def test_lanes_delta_chain_goes_before_the_blocked_scan(monkeypatch):
+    """Two samples with both the blocked scan and the samples-on-lanes delta chain switched on for them: the lanes chain
+    writes no backpointers and leaves no blocks' vectors, so the route is not blocked and a backpointer kernel runs
+    (hmm_route.h).  States, calls and delta equal those of the plain wave chains."""
+    from gbrs_amd import synth
+    from gbrs_amd.hmm import DiplotypeHMM
+    prob = synth.make_hmm_problem(H=8, genes_per_chrom=[60, 45], seed=9)
+    chroms = prob.chroms
+    rng = np.random.default_rng(5)
+    ha = [np.array([g in prob.avecs for g in prob.gene_ids[c]], dtype=np.uint8) for c in chroms]
+    av = [np.array([prob.avecs.get(g, np.zeros((8, 8))) for g in prob.gene_ids[c]]) for c in chroms]
+    e0 = [np.array([prob.expr[g] for g in prob.gene_ids[c]]) for c in chroms]
+    ex = [np.stack([e, rng.gamma(1.0, 5.0, size=e.shape) * (rng.random(e.shape) < 0.3)]) for e in e0]
+    routes = {"lanes": {"GBRS_TUNING_HMM_BLOCKED": "2", "GBRS_TUNING_HMM_DLANES": "1", "GBRS_TUNING_HMM_MFMA": "0",
+                        "GBRS_TUNING_HMM_BLOCK_GENES": "5"},
+              "wave": {"GBRS_TUNING_HMM_BLOCKED": "0", "GBRS_TUNING_HMM_DLANES": "0"}}
+    res = {}
+    for name, env in routes.items():
+        with monkeypatch.context() as m:
+            for k, v in env.items():
+                m.setenv(k, v)
+            hmm = DiplotypeHMM(8, chroms, [len(prob.gene_ids[c]) for c in chroms], [prob.tprob[c] for c in chroms])
+            hmm.set_expression(ex, av, ha, 1.5, 0.12)
+            hmm.run()
+            assert hmm.info().last_delta_blocks == 0
+            res[name] = [[hmm.get(ci, sample=s, want=("states", "calls", "delta")) for ci in range(2)] for s in range(2)]
+            hmm.close()
+    for s in range(2):
+        for a, b in zip(res["wave"][s], res["lanes"][s]):
+            np.testing.assert_array_equal(b["states"], a["states"])
+            np.testing.assert_array_equal(b["calls"], a["calls"])
+            np.testing.assert_allclose(b["delta"], a["delta"], rtol=1e-10, atol=1e-9)
+
+
 def test_blocked_scan_equals_the_unblocked_chains_at_size(monkeypatch):
     """40k genes, 20 chromosomes, one sample: the blocked scan (64 blocks per long chromosome) against the unblocked
     chains of the same library - posteriors, log-domain arrays and delta at 1e-9, Viterbi path identical."""

@@ -28,6 +28,7 @@ EXPORTS = [
     "gbrs_shard_plan", "gbrs_shard_index", "gbrs_shard_gather",
     "gbrs_hmm_create", "gbrs_hmm_set_expression", "gbrs_hmm_set_eprob", "gbrs_hmm_run",
     "gbrs_hmm_get", "gbrs_hmm_info", "gbrs_hmm_destroy", "gbrs_interpolate", "gbrs_genoprob_dosage",
+    "gbrs_ri_transition_tables", "gbrs_alignment_spec",
     "gbrs_compress_create", "gbrs_compress_get", "gbrs_compress_destroy",
     "gbrs_bam_open", "gbrs_bam_references", "gbrs_bam_set_reference_map", "gbrs_bam_convert", "gbrs_bam_get",
     "gbrs_bam_scan_records", "gbrs_bam_destroy",
@@ -171,6 +172,8 @@ def load():
         "gbrs_hmm_destroy": [vp],
         "gbrs_interpolate": [i32, i32, vp, vp, i32, vp, vp, i32],
         "gbrs_genoprob_dosage": [i32, i64, vp, vp, i32],
+        "gbrs_ri_transition_tables": [vp, vp, vp, i64, dbl, dbl, i32, vp],
+        "gbrs_alignment_spec": [vp, vp, vp, i64, i32, dbl, i32, vp, vp, vp, vp],
         "gbrs_compress_create": [u64, u32, u32, pp, pp, vp, i32, pp, C.POINTER(u64), vp],
         "gbrs_compress_get": [vp, pp, pp, vp],
         "gbrs_compress_destroy": [vp],

@@ -163,7 +163,20 @@ def build_parser():
     sn.add_argument('-G', '--genotype', dest='genotype_file', required=True, type=_existing)
     sn.add_argument('-g', '--group-file', type=_existing, default=None)
     sn.add_argument('-o', '--output', dest='output_file', default=None)
-    for p in (ca, cb, pu, cn, sr, sn):
+    # the two inputs of reconstruct (gbrs/commands.py:282-339; gbrs_amd/hmm_inputs.py)
+    tp = sub.add_parser('get-transition-prob', help='calculate the transition probabilities between markers')
+    tp.add_argument('-i', '--marker-file', required=True, type=_existing)
+    tp.add_argument('-s', '--haplotypes', default='A,B')
+    tp.add_argument('-m', '--mating-scheme', default='RI')
+    tp.add_argument('-g', '--gamma-scale', type=float, default=0.01)
+    tp.add_argument('-e', '--epsilon', type=float, default=0.000001)
+    tp.add_argument('-o', '--output', dest='output_file', default='tranprob.npz')
+    sp = sub.add_parser('get-alignment-spec', help='get the alignment specificity of the parental strains')
+    sp.add_argument('-i', '--sample-file', required=True, type=_existing)
+    sp.add_argument('-s', '--parental-strains', dest='haplotypes', action='append', required=True,
+                    help='parental strain, either one per -s option, i.e. -s A -s B, or a shortcut -s A,B')
+    sp.add_argument('-m', '--min-expr', type=float, default=2.0)
+    for p in (ca, cb, pu, cn, sr, sn, tp, sp):
         p.add_argument('-v', '--verbose', action='count', default=0)
         p.add_argument('--device', type=int, default=0, help='HIP device ordinal (extension)')
     wk = sub.add_parser('worker', help='(extension) quantify -> reconstruct -> quantify -G of many samples in one resident process')
@@ -292,6 +305,16 @@ def main(argv=None) -> int:
             from .matops import stencil
             stencil(alignment_file=args.alignment_file, genotype_file=args.genotype_file, group_file=args.group_file,
                     output_file=args.output_file, device=args.device, stage_times=stages)
+        elif args.command == 'get-transition-prob':
+            from .hmm_inputs import get_transition_prob
+            get_transition_prob(marker_file=args.marker_file, haplotypes=args.haplotypes,
+                                mating_scheme=args.mating_scheme, gamma_scale=args.gamma_scale, epsilon=args.epsilon,
+                                output_file=args.output_file, device=args.device, stage_times=stages)
+        elif args.command == 'get-alignment-spec':
+            from .hmm_inputs import get_alignment_spec
+            strains = [s for x in args.haplotypes for s in x.split(',')]
+            get_alignment_spec(sample_file=args.sample_file, haplotypes=strains, min_expr=args.min_expr,
+                               device=args.device, stage_times=stages)
         elif args.command == 'interpolate':
             from .postproc import interpolate
             interpolate(genoprob_file=args.genoprob_file, grid_file=args.grid_file, gpos_file=args.gpos_file,

@@ -692,6 +692,31 @@ int gbrs_interpolate(int num_states, int n_points, const double *x, const double
  * (S x H) matrix 0.5 * (founder count in diplotype) -> n_rows x H founder dosages. */
 int gbrs_genoprob_dosage(int num_haps, int64_t n_rows, const double *gprob, double *out, int device);
 
+/* `gbrs get-transition-prob` numeric body for the `RI` mating scheme (gbrs/gbrs_utils.py:101-187 ris_step, forward
+ * direction; :269-290): the log transition tables of two-founder recombinant inbred lines by sib mating, all
+ * chromosomes in one launch.  cm holds the markers' cM positions, chromosome c's at [chrom_ptr[c], chrom_ptr[c+1]) in
+ * file order; is_x[c] != 0 selects the X-chromosome formulas.  A chromosome of n_c markers has max(n_c - 1, 0)
+ * intervals d = cm[m+1] - cm[m], every d < epsilon (zero and negative steps too) replaced by epsilon, and no interval
+ * reaches across a chromosome boundary.  out receives 9 doubles per interval, the chromosomes one after the other: the
+ * (3 x 3) natural-log table in the reference's element order ([dt1][dt2] = ris_step(gen_left = dt1, gen_right = dt2)
+ * over AA, AB, BB), each entry log(a) - log(1 + gamma) as two logarithms and a subtraction.  chrom_ptr must start at 0 and not decrease (GBRS_ERR_INVALID); no
+ * interval at all is a success without a launch (out may then be NULL). */
+int gbrs_ri_transition_tables(const double *cm, const int64_t *chrom_ptr /* num_chroms + 1 */,
+                              const uint8_t *is_x /* num_chroms */, int64_t num_chroms, double gamma_scale,
+                              double epsilon, int device, double *out /* 9 * sum_c max(n_c - 1, 0) */);
+
+/* `gbrs get-alignment-spec` numeric body (gbrs/gbrs_utils.py:335-372): tables is [F][num_genes][num_strains], one
+ * (genes x strains) TPM table per report file that exists, the files of strain i at [strain_ptr[i], strain_ptr[i+1]);
+ * strain_div[i] is the number of files the strain lists (missing ones included, >= its tables).  Per strain the tables
+ * are added in file order starting from 0 and divided once by strain_div[i]: row i of axes[g] (G x S x S).  ases[g][i]
+ * (G x S) is that row summed left to right; avecs[g] row i is the row divided by its Euclidean norm when its sum exceeds
+ * 1e-6, else the row itself; has_avec[g] = 1 when some ases[g][i] > min_expr (the reference writes avecs[g] only then).
+ * axes and ases are bit-identical to numpy's; avecs differs by the rounding of the norm.  num_strains outside 1..32 is
+ * GBRS_ERR_UNSUPPORTED; num_genes == 0 is a success without a launch. */
+int gbrs_alignment_spec(const double *tables, const int64_t *strain_ptr /* num_strains + 1 */,
+                        const int64_t *strain_div /* num_strains */, int64_t num_genes, int num_strains, double min_expr,
+                        int device, double *axes, double *ases, double *avecs, uint8_t *has_avec);
+
 /* ------------------------------------------------------------------------------------------
  * Report text (host side, no device work): the `locus <haplotypes> total [notes]` tables of
  * EMfactory.report_read_counts / report_depths (emase/EMfactory.py:289-380).

@@ -60,9 +60,6 @@ def em_case(rng):
 
 
 def hmm_case(rng):
-    from gbrs_amd import synth
-    from gbrs_amd.hmm import DiplotypeHMM
-    from oracle import hmm_oracle
     H = int(rng.choice([2, 3, 4, 5, 7, 8, 8, 8, 9, 16]))
     nch = int(rng.integers(1, 6))
     lens = [int(x) for x in rng.integers(1, 90 if H == 16 else 400, size=nch)]
@@ -79,7 +76,31 @@ def hmm_case(rng):
               "GBRS_TUNING_HMM_DELTA_TOL": str(rng.choice(["1e-9", "1e-9", "-1"])),
               "GBRS_TUNING_HMM_DELTA_ROWS": str(int(rng.integers(0, 2))),
               "GBRS_TUNING_HMM_XCD": str(int(rng.choice([0, 0, 1, 2, 3])))}
+    # 8 founders at 25 or 40 samples, half of the draws: the MFMA, DLANES and BPLANES thresholds as the library has them,
+    # so that the pass takes the two-samples-per-wave chains (tests/hmm_batched_cases.py) instead of main()'s MFMA sweeps
+    thresholds = ("GBRS_TUNING_HMM_MFMA", "GBRS_TUNING_HMM_DLANES", "GBRS_TUNING_HMM_BPLANES")
+    library_thresholds = H == 8 and ns in (25, 40) and bool(rng.integers(0, 2))
+    if library_thresholds:
+        del tuning["GBRS_TUNING_HMM_BPLANES"]
+    pinned = {k: os.environ.get(k) for k in thresholds}
     os.environ.update(tuning)
+    if library_thresholds:
+        for k in thresholds:
+            os.environ.pop(k, None)
+    try:
+        desc = hmm_case_run(rng, H, lens, ns)
+    finally:
+        for k, v in pinned.items():
+            if v is not None and k not in tuning:
+                os.environ[k] = v
+    return (desc + f" thresholds={'library' if library_thresholds else 'pinned'} "
+            + " ".join(f"{k[16:].lower()}={v}" for k, v in tuning.items()))
+
+
+def hmm_case_run(rng, H, lens, ns):
+    from gbrs_amd import synth
+    from gbrs_amd.hmm import DiplotypeHMM
+    from oracle import hmm_oracle
     style = str(rng.choice(["benign", "do"])) if H == 8 else "benign"
     minus_one = bool(rng.integers(0, 2))
     seed = int(rng.integers(1, 1 << 30))
@@ -107,8 +128,7 @@ def hmm_case(rng):
                 np.testing.assert_allclose(r[k], res[c][k], rtol=1e-9, atol=1e-9)
             np.testing.assert_allclose(r["gamma"], res[c]["gamma"], rtol=1e-8, atol=1e-300)
     hmm.close()
-    return (f"HMM H={H} lens={lens} samples={ns} tprob_n-1={minus_one} tables={style} "
-            + " ".join(f"{k[16:].lower()}={v}" for k, v in tuning.items()))
+    return f"HMM H={H} lens={lens} samples={ns} tprob_n-1={minus_one} tables={style}"
 
 
 def main():

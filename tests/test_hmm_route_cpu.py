@@ -10,6 +10,7 @@ import subprocess
 
 import pytest
 
+import hmm_batched_cases
 from conftest import ROOT
 
 PREFIX = "GBRS_TUNING_HMM_"
@@ -57,6 +58,26 @@ def test_36_states_blocked_scan_up_to_4_samples(driver, n_samples):
                                                   (31, 1, "generic"), (32, 1, "lanes"), (63, 1, "lanes")])
 def test_36_states_wave_chains(driver, n_samples, batched, bp):
     expect(route(driver, 8, n_samples), "wave", "wave", bp, batched=batched)
+
+
+def batched_case_route(driver, c):
+    got = route(driver, c.founders, c.n_samples, **{k[len(PREFIX):]: v for k, v in c.env.items()})
+    return {k: got[k] for k in ("sweep", "delta", "bp", "batched")}
+
+
+@pytest.mark.parametrize("case", hmm_batched_cases.CASES, ids=hmm_batched_cases.case_id)
+def test_batched_case_table_routes(driver, case):
+    """Every row of tests/hmm_batched_cases.py resolves to the route it names: tests/test_hmm_batched_wave_gpu.py runs
+    these rows to cover the kernels behind that route.  A row that fails here no longer reaches them - re-aim it."""
+    assert all(k.startswith(PREFIX) for k in case.env)
+    assert batched_case_route(driver, case) == dict(sweep=case.sweep, delta=case.delta, bp=case.bp, batched=str(case.batched))
+
+
+def test_batched_case_table_covers_both_backpointer_kernels(driver):
+    """Behind the two-samples-per-wave delta chain with the library's defaults: viterbi_bp_kernel and
+    viterbi_bp_lanes_kernel each read its rows in some row of the table."""
+    got = [batched_case_route(driver, c) for c in hmm_batched_cases.CASES if c.founders == 8 and not c.env]
+    assert {r["bp"] for r in got if r["batched"] == "1" and r["delta"] == "wave"} >= {"generic", "lanes"}
 
 
 @pytest.mark.parametrize("n_samples", [64, 65, 256])

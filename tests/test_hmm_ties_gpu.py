@@ -6,6 +6,7 @@ the argmax rules: the calls must be the reference's, ties included.  Tier B lets
 decision that the reference takes inside the rounding of its own emission may then fall on another of the tied
 candidates, and on no other state.  Tier C compares the blocked scan with the unblocked chain at size."""
 import functools
+import os
 
 import numpy as np
 import pytest
@@ -34,11 +35,24 @@ PLAIN_CHAINS = {"unblocked"}
 # batches: MFMA sweeps from 16 samples, the samples-on-lanes delta chain from 16, the samples-on-lanes backpointers from 5.
 # Their delta chains (one wave per sample below 16 samples, samples on lanes from there) are plain chains.
 BATCH = {BLK + "MFMA": "16", BLK + "DLANES": "16", BLK + "BPLANES": "5"}
+# and with the library's defaults, 25 and 40 samples (mfma_ng = 0 in the batch tests' rows): the two-samples-per-wave chains
+# (tests/hmm_batched_cases.py), the same template as the one-sample-per-wave chain and as plain.  The tie samples sit in a
+# wave's first slot (0, 16), in its second slot (15, 39) and alone in the last wave (24).
+BATCH_ROWS = [(5, 1), (21, 1), (21, 2), (37, 1), (37, 2), pytest.param(25, 0, id="25-defaults"), pytest.param(40, 0, id="40-defaults")]
 
 
 def set_route(monkeypatch, env):
     for k, v in env.items():
         monkeypatch.setenv(k, v)
+
+
+def set_batch_route(monkeypatch, mfma_ng):
+    if mfma_ng:
+        set_route(monkeypatch, dict(BATCH, **{BLK + "MFMA_NG": str(mfma_ng)}))
+        return
+    for k in list(os.environ):
+        if k.startswith((BLK, "GBRS_DIAG_HMM_")):
+            monkeypatch.delenv(k, raising=False)
 
 
 def oracle_sample(H, tables, eprobs):
@@ -236,10 +250,10 @@ BATCH_KEYS_A = ["cc"] + H8_FILES              # tier A: the class-constant probl
 BATCH_KEYS_B = H8_FILES                       # tier B: the fixtures (the class-constant problem has no expression)
 
 
-@pytest.mark.parametrize("n_samples,mfma_ng", [(5, 1), (21, 1), (21, 2), (37, 1), (37, 2)])
+@pytest.mark.parametrize("n_samples,mfma_ng", BATCH_ROWS)
 @pytest.mark.parametrize("key", BATCH_KEYS_A, ids=fid)
 def test_tier_a_batches(key, n_samples, mfma_ng, monkeypatch):
-    set_route(monkeypatch, dict(BATCH, **{BLK + "MFMA_NG": str(mfma_ng)}))
+    set_batch_route(monkeypatch, mfma_ng)
     hmm, _, members = run_batch(key, n_samples, "A")
     assert sum(1 for m in members if m[2]) == len(tie_slots(n_samples))
     for s, expected, _ in members:
@@ -328,10 +342,10 @@ def test_tier_b_fixtures_one_sample_routes(path, route, monkeypatch):
     hmm.close()
 
 
-@pytest.mark.parametrize("n_samples,mfma_ng", [(5, 1), (21, 1), (21, 2), (37, 1), (37, 2)])
+@pytest.mark.parametrize("n_samples,mfma_ng", BATCH_ROWS)
 @pytest.mark.parametrize("key", BATCH_KEYS_B, ids=fid)
 def test_tier_b_batches(key, n_samples, mfma_ng, monkeypatch):
-    set_route(monkeypatch, dict(BATCH, **{BLK + "MFMA_NG": str(mfma_ng)}))
+    set_batch_route(monkeypatch, mfma_ng)
     hmm, tables, members = run_batch(key, n_samples, "B")
     for s, expected, is_tie in members:
         check_eps_optimal(hmm, s, tables, expected, f"{fid(key)} sample {s} of {n_samples}",

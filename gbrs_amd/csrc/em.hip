@@ -1297,6 +1297,15 @@ int em_create_impl(uint64_t R, uint32_t L, uint32_t H, const uint32_t *const *in
                         (allowed && (flags & GBRS_EM_KEEP_CSC)) ? &em->col_ptr_src : nullptr, em->stream));
     stg.mark("upload csc");
     em->N = n;
+    // everything that is known before the build: em_plan.h (the tuning variables are read here, once per create)
+    EmShape shape;
+    shape.H = H; shape.L = L; shape.R = R; shape.N = n; shape.flags = flags; shape.counts_given = count != nullptr;
+    GBRS_HIP_CHECK(hipDeviceGetAttribute(&shape.n_cu, hipDeviceAttributeMultiprocessorCount, device));
+    shape.tile_words = TILE_WORDS; shape.tile_words_max = TILE_WORDS_MAX; shape.tile_rounds_min = TILE_ROUNDS_MIN;
+    if (H <= 16) shape.dict = dict_limits(em_weighted(flags, count != nullptr), (int)H);     // (more: the CSC kernels)
+    if (H == 16) shape.dict_half = dict_limits(false, 8);
+    const EmPlan plan = em_plan(shape, em_tuning_from_env());
+    em->view = plan.view; em->persist_groups = plan.persist_groups; em->lead_mask = plan.lead_mask; em->resample_cut = plan.resample_cut;
     const size_t LH = (size_t)L * H;
     GBRS_TRY(em->den.alloc(R));
     GBRS_TRY(em->theta.alloc(LH));
@@ -1334,8 +1343,6 @@ int em_create_impl(uint64_t R, uint32_t L, uint32_t H, const uint32_t *const *in
             GBRS_HIP_CHECK(hipStreamSynchronize(em->stream));
             if (hbad)
                 return fail(GBRS_ERR_INVALID, "GBRS_EM_RESAMPLE needs integer counts in [0, 2^32): a row is drawn count[r] times");
-            if (const char *env = std::getenv("GBRS_TUNING_RESAMPLE_CUT"); env && std::atoi(env) > 0)
-                em->resample_cut = (uint32_t)std::atoi(env);
             DevBuf<uint32_t> n_big;
             GBRS_TRY(n_big.alloc(1));
             for (int pass = 0; pass < 2; ++pass) {
@@ -1363,58 +1370,14 @@ int em_create_impl(uint64_t R, uint32_t L, uint32_t H, const uint32_t *const *in
     GBRS_HIP_CHECK(hipDeviceSynchronize());
     GBRS_TRY(check_row_ids(n, em->ent_row.p, R, em->stream));
     stg.mark("vectors, checks");
-    if ((flags & GBRS_EM_DETERMINISTIC) && ((flags & GBRS_EM_LAYOUT_CSC) || H > 16 || n >= 0xFFFFFFFFull))
+    if ((flags & GBRS_EM_DETERMINISTIC) && !plan.tiled)
         return fail(GBRS_ERR_UNSUPPORTED, "GBRS_EM_DETERMINISTIC needs the tiled layout (H <= 16, not GBRS_EM_LAYOUT_CSC): "
                                           "the CSC kernels accumulate with global float atomics");
-    if (!(flags & GBRS_EM_LAYOUT_CSC) && H <= 16 && n < 0xFFFFFFFFull) {
-        // Row order inside a tile: the stream order (gbrs_hip.h) by default - every lane walks a
-        // contiguous piece of the tile's sorted rows, so it stays on one locus list for long stretches
-        // (E-step on C2: raw reads 0.158 -> 0.152 ms, merged distinct rows 0.110 -> 0.056 ms against
-        // the interleaved order that used to be their default).
-        int row_order = 2;
-        if (flags & GBRS_EM_FORCE_INTERLEAVE) row_order = 1;
-        else if (flags & GBRS_EM_NO_STREAMS) {
-            const bool distinct = em->has_count || (flags & GBRS_EM_MERGE_IDENTICAL_ROWS);
-            row_order = (distinct && !(flags & GBRS_EM_NO_INTERLEAVE)) ? 1 : 0;
-        }
+    if (plan.tiled) {
         em->tl.retain_temporaries = (flags & GBRS_EM_ONE_SHOT) != 0;
         em->tl.keep_row_ids = resample;
-        // 16 haplotypes as half-loci on the 8-haplotype kernels (em_layout.h; the review's "two halves of 8"): built, parity-green,
-        // NO gain - one GPU's shard of config 5: E-step 0.1518 ms against 0.1525 (the words double, the cost per word halves) and
-        // the iteration 0.1997 against 0.1744 (gather and M-step as two launches over every element).  GBRS_TUNING_HALF_LOCI=1
-        // switches it on; weighted rows and the deterministic mode never take it.
-        {
-            const char *env = std::getenv("GBRS_TUNING_HALF_LOCI");
-            const bool want = env ? std::atoi(env) != 0 : false;
-            const bool weighted = em->has_count || (flags & GBRS_EM_MERGE_IDENTICAL_ROWS);
-            em->view = (H == 16 && want && !weighted && !(flags & GBRS_EM_DETERMINISTIC) && (uint64_t)L * 2 < (1u << 27)) ? 2u : 1u;
-        }
-        GBRS_TRY(build_tile_layout(em->tl, R, em->tL(), em->tH(), n, em->ent_row.p, em->col_ptr.p,
-                                   em->has_count ? em->count.p : nullptr, (flags & GBRS_EM_MERGE_IDENTICAL_ROWS) != 0,
-                                   row_order, (flags & GBRS_EM_DETERMINISTIC) != 0,
-                                   em->stream, (flags & GBRS_EM_SIDE_BY_SIDE) ? 2u : 1u,
-                                   (flags & GBRS_EM_NO_LOCUS_SETS) == 0 && !em->has_count &&
-                                       !(flags & GBRS_EM_MERGE_IDENTICAL_ROWS),     // (weighted rows: their tiles are dictionary-bound)
-                                   0, em->view, (flags & GBRS_EM_NO_RUN_WORDS) == 0));
+        GBRS_TRY(build_tile_layout(em->tl, R, n, em->ent_row.p, em->col_ptr.p, em->has_count ? em->count.p : nullptr, em->stream, plan));
         em->layout = 1;
-        {
-            // persistent E-step workgroups: one per place the chip has for them (tile_estep_kernel's launch bounds: 3 per CU
-            // for unweighted rows of <= 8 haplotypes, else 2), shared between handles that run side by side
-            // GBRS_TUNING_PERSISTENT=1 switches them on: built, parity-green and measured in round 4 - 8-10 % SLOWER than one
-            // workgroup per tile on the C2 sample (profiles/r04_estep_experiments.txt), so off by default
-            const char *env = std::getenv("GBRS_TUNING_PERSISTENT");
-            int n_cu = 0;
-            GBRS_HIP_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
-            const unsigned per_cu = (em->tl.weighted || em->tH() > 8) ? 2u : 3u;
-            const unsigned share = (flags & GBRS_EM_SIDE_BY_SIDE) ? 2u : 1u;
-            unsigned groups = per_cu * (unsigned)std::max(n_cu, 1) / share;
-            if (const char *g = std::getenv("GBRS_TUNING_PERSISTENT_GROUPS"); g && std::atoi(g) > 0) groups = (unsigned)std::atoi(g);
-            em->persist_groups = (env && std::atoi(env) != 0) ? std::max(groups, 1u) : 0u;
-            // GBRS_TUNING_NO_PHASE_SPLIT=1: the E-step takes every tile's n_one and n_two as 0 - one batch loop, as before the headers
-            // had the field (A/B in one build, and the cross-check of the two-loop form in the tests)
-            const char *no_split = std::getenv("GBRS_TUNING_NO_PHASE_SPLIT");
-            em->lead_mask = (no_split && std::atoi(no_split) != 0) ? 0u : ~0u;
-        }
         stg.mark("build_tile_layout");
         // the CSC copy and the per-row denominators are only needed by layout 0 (and, until
         // gbrs_em_set_initial_values has run, when the caller announced stored values)

@@ -24,6 +24,7 @@
 //            inverted index in the tile-major numbering.
 #pragma once
 #include "common.h"
+#include "em_plan.h"
 
 #include <vector>
 
@@ -195,16 +196,18 @@ struct TileLayout {
     }
 };
 
+// the limits above as em_plan.h takes them
+inline EmDictLimits dict_limits(bool weighted, int H) {
+    return {(uint32_t)max_row_words(H), dict_index_limit(H), (uint32_t)lds_theta_doubles(weighted, H), det_dict_cap(H, weighted)};
+}
+
 // ent_row / col_ptr: the concatenated CSC arrays already on the device (column c = h*L + l).
-// count: device pointer or nullptr.  Returns GBRS_OK or a status with the message set.
-int build_tile_layout(TileLayout &out, uint64_t R, uint32_t L, uint32_t H, uint64_t N,
-                      const uint32_t *ent_row, const uint64_t *col_ptr, const double *count,
-                      bool merge_identical_rows, int row_order /* 0 sorted, 1 interleaved, 2 streams */,
-                      bool deterministic, hipStream_t stream, unsigned side_by_side = 1 /* handles sharing the device */,
-                      bool locus_sets = false, uint32_t dict_cap = 0 /* > 0: at most this many loci per tile dictionary */,
-                      uint32_t view_factor = 1, bool run_words = true /* false: never fold identical one- or two-word reads */);
-// view_factor = 2 (round 4, 16 haplotypes): the layout is built over HALF-LOCI - locus l's haplotypes 0-7 are "locus" 2l,
-// its haplotypes 8-15 "locus" 2l + 1, L and H passed here are 2 L and 8.  The locus-major vectors (theta, A, lengths:
+// count: device pointer or nullptr.  plan: what gbrs_em_create* resolved before the build (em_plan.h) - the layout's loci
+// and haplotypes are plan.tL and plan.tH.  Returns GBRS_OK or a status with the message set.
+int build_tile_layout(TileLayout &out, uint64_t R, uint64_t N, const uint32_t *ent_row, const uint64_t *col_ptr,
+                      const double *count, hipStream_t stream, const EmPlan &plan);
+// plan.view = 2 (round 4, 16 haplotypes): the layout is built over HALF-LOCI - locus l's haplotypes 0-7 are "locus" 2l,
+// its haplotypes 8-15 "locus" 2l + 1, plan.tL and plan.tH are 2 L and 8.  The locus-major vectors (theta, A, lengths:
 // element l * 16 + h) are element for element the half-locus view's (2l + h / 8) * 8 + h % 8, so nothing outside the layout
 // moves; a read that aligns to both halves of a locus has two words in its row, and the tiles run on the 8-haplotype
 // E-step kernel (theta row and sums in registers, 0/1 doubles from the LDS tables, six waves per SIMD) instead of the

@@ -1072,15 +1072,126 @@ __global__ void ec_indptr_kernel(uint32_t L, uint32_t H, uint64_t n, const uint6
     colptr[c] = lo;
 }
 
+// ---- what compress_device and build_tile_layout share -------------------------------------------------------------------
+namespace {
+
+// exclusive scan of n counts; `total` is their sum, which `close` also writes behind the offsets (out[n])
+template <typename T>
+int scan_total(Scratch &sc, const T *in, T *out, size_t n, T &total, hipStream_t s, bool close = false) {
+    GBRS_TRY(exclusive_scan(sc, in, out, n, s));
+    GBRS_TRY(fetch_last_plus(out, in, n, total, s));
+    if (close) GBRS_HIP_CHECK(hipMemcpyAsync(out + n, &total, sizeof(T), hipMemcpyHostToDevice, s));
+    return GBRS_OK;
+}
+
+// inclusive scan of n > 0 head flags; `total` is the number of heads
+int scan_heads(Scratch &sc, const uint32_t *head, uint32_t *incl, size_t n, uint32_t &total, hipStream_t s) {
+    GBRS_TRY(inclusive_scan(sc, head, incl, n, s));
+    GBRS_HIP_CHECK(hipMemcpyAsync(&total, incl + n - 1, 4, hipMemcpyDeviceToHost, s));
+    GBRS_HIP_CHECK(hipStreamSynchronize(s));
+    return GBRS_OK;
+}
+
+int running_max(Scratch &sc, const uint32_t *in, uint32_t *out, size_t n, hipStream_t s) {
+    size_t bytes = 0;
+    GBRS_PRIM(rocprim::inclusive_scan(nullptr, bytes, in, out, n, rocprim::maximum<uint32_t>(), s));
+    GBRS_TRY(sc.reserve(bytes));
+    GBRS_PRIM(rocprim::inclusive_scan(sc.buf.p, bytes, in, out, n, rocprim::maximum<uint32_t>(), s));
+    return GBRS_OK;
+}
+
+// the stream, the scan / sort scratch and the flags the kernels of a build raise
+struct Build {
+    hipStream_t s;
+    StageTimer *stg;             // null: no checkpoints (compress_device)
+    Scratch sc;
+    DevBuf<BuildFlags> d_flags;
+    BuildFlags hf{};
+    Build(hipStream_t stream, StageTimer *timer) : s(stream), stg(timer) {}
+    int init() {
+        GBRS_TRY(d_flags.alloc(1));
+        GBRS_HIP_CHECK(hipMemsetAsync(d_flags.p, 0, sizeof(BuildFlags), s));
+        return GBRS_OK;
+    }
+    int read_flags() {
+        GBRS_HIP_CHECK(hipMemcpyAsync(&hf, d_flags.p, sizeof(hf), hipMemcpyDeviceToHost, s));
+        GBRS_HIP_CHECK(hipStreamSynchronize(s));
+        return GBRS_OK;
+    }
+    void mark(const char *stage) { if (stg) stg->mark(stage); }
+};
+
+// the rows with at least one alignment as (locus, haplotype mask) pairs: pairs rowstart[r] .. rowstart[r + 1] of row r,
+// which is row row_orig[r] of the input
+struct RowPairs {
+    DevBuf<uint32_t> rowstart, row_orig, ploc, pmask;
+    uint64_t P = 0, R1 = 0;
+    void release() { rowstart.release(); row_orig.release(); ploc.release(); pmask.release(); }
+};
+
+// entries -> sorted (row, locus, hap) keys -> pairs -> rows (N > 0).  The keys carry the row above bit row_shift.
+// view > 1: L and H are those of the half-locus view, the CSC columns those of the caller's L / view loci with H * view
+// haplotypes.
+int build_row_pairs(Build &b, RowPairs &rp, uint64_t R, uint32_t L, uint32_t H, uint64_t N, const uint32_t *ent_row,
+                    const uint64_t *col_ptr, unsigned row_shift, uint32_t view = 1) {
+    hipStream_t s = b.s;
+    // 1. entries -> sorted (row, locus, hap) keys
+    DevBuf<uint64_t> keys, keys2;
+    GBRS_TRY(keys.alloc(N)); GBRS_TRY(keys2.alloc(N));
+    b.mark("1a key buffers");
+    hipLaunchKernelGGL(make_keys_kernel, dim3(grid_for(N, 4 * KEY_SPAN)), dim3(256), 0, s, N, H * L, L / view, R, row_shift,
+                       col_ptr, ent_row, keys.p, b.d_flags.p, view > 1 ? H : 0u);
+    b.mark("1b make keys");
+    GBRS_TRY(sort_keys64(b.sc, keys.p, keys2.p, N, row_shift + bits_for(R - 1), s));
+    b.mark("1c sort entries");
+    keys.release();
+    b.mark("1d release");
+    // 2. pairs
+    DevBuf<uint32_t> pflag, pidx;
+    GBRS_TRY(pflag.alloc(N)); GBRS_TRY(pidx.alloc(N));
+    b.mark("2a alloc flags");
+    hipLaunchKernelGGL(pair_flag_kernel, dim3(grid_for(N)), dim3(256), 0, s, N, keys2.p, pflag.p, b.d_flags.p);
+    b.mark("2b pair flags");
+    GBRS_TRY(exclusive_scan(b.sc, pflag.p, pidx.p, N, s));
+    b.mark("2c scan");
+    uint32_t P32 = 0;
+    GBRS_TRY(fetch_last_plus(pidx.p, pflag.p, N, P32, s));
+    GBRS_TRY(b.read_flags());
+    b.mark("2d fetch");
+    if (b.hf.bad_row) return fail(GBRS_ERR_INVALID, "indices hold a row id >= num_rows");
+    if (b.hf.duplicate) return fail(GBRS_ERR_INVALID, "duplicate (row, locus, haplotype) entry: the CSC arrays must be canonical");
+    rp.P = P32;
+    DevBuf<uint32_t> prow;
+    GBRS_TRY(prow.alloc(rp.P)); GBRS_TRY(rp.ploc.alloc(rp.P)); GBRS_TRY(rp.pmask.alloc(rp.P));
+    hipLaunchKernelGGL(emit_pairs_kernel, dim3(grid_for(N)), dim3(256), 0, s, N, keys2.p, pflag.p, pidx.p, row_shift,
+                       prow.p, rp.ploc.p, rp.pmask.p);
+    GBRS_HIP_CHECK(hipStreamSynchronize(s));
+    b.mark("2e emit pairs");
+    keys2.release(); pflag.release(); pidx.release();
+    b.mark("2 pairs (release)");
+    // 3. rows
+    DevBuf<uint32_t> rflag, ridx;
+    GBRS_TRY(rflag.alloc(rp.P)); GBRS_TRY(ridx.alloc(rp.P));
+    hipLaunchKernelGGL(row_flag_kernel, dim3(grid_for(rp.P)), dim3(256), 0, s, rp.P, prow.p, rflag.p);
+    uint32_t R32 = 0;
+    GBRS_TRY(scan_total(b.sc, rflag.p, ridx.p, rp.P, R32, s));
+    rp.R1 = R32;
+    GBRS_TRY(rp.rowstart.alloc((size_t)rp.R1 + 1)); GBRS_TRY(rp.row_orig.alloc(rp.R1));
+    hipLaunchKernelGGL(row_start_kernel, dim3(grid_for(rp.P)), dim3(256), 0, s, rp.P, rp.R1, rflag.p, ridx.p, prow.p,
+                       rp.rowstart.p, rp.row_orig.p);
+    GBRS_HIP_CHECK(hipStreamSynchronize(s));
+    return GBRS_OK;        // (rflag, ridx and prow go here)
+}
+
+}  // namespace
+
 int compress_device(CompressResult &out, uint64_t R, uint32_t L, uint32_t H, uint64_t N, const uint32_t *ent_row,
                     const uint64_t *col_ptr, const double *count, hipStream_t s) {
     if (H > 16 || N >= 0xFFFFFFFFull || L >= (1u << 27))
         return fail(GBRS_ERR_INVALID, "compress needs H <= 16, N < 2^32 entries and L < 2^27 loci");
-    Scratch sc;
-    DevBuf<BuildFlags> d_flags;
-    GBRS_TRY(d_flags.alloc(1));
-    GBRS_HIP_CHECK(hipMemsetAsync(d_flags.p, 0, sizeof(BuildFlags), s));
-    BuildFlags hf{};
+    Build b(s, nullptr);
+    GBRS_TRY(b.init());
+    Scratch &sc = b.sc;
     out.num_ecs = 0;
     out.n_entries = 0;
     GBRS_TRY(out.col_ptr.alloc((size_t)H * L + 1));
@@ -1090,49 +1201,19 @@ int compress_device(CompressResult &out, uint64_t R, uint32_t L, uint32_t H, uin
     GBRS_TRY(nnz_row.alloc(R));
     GBRS_HIP_CHECK(hipMemsetAsync(nnz_row.p, 0, nnz_row.bytes(), s));
     if (N) hipLaunchKernelGGL(ec_row_nnz_kernel, dim3(grid_for(N)), dim3(256), 0, s, N, ent_row, nnz_row.p);
-    uint64_t P = 0, R1 = 0, M = 0;
-    DevBuf<uint32_t> prow, ploc, pmask, rowstart, row_orig, srow, head, hincl;
+    uint64_t R1 = 0, M = 0;
+    RowPairs rp;
+    DevBuf<uint32_t> &ploc = rp.ploc, &pmask = rp.pmask, &rowstart = rp.rowstart, &row_orig = rp.row_orig;
+    DevBuf<uint32_t> srow, head, hincl;
     if (N) {
-        DevBuf<uint64_t> keys, keys2;
-        GBRS_TRY(keys.alloc(N)); GBRS_TRY(keys2.alloc(N));
-        hipLaunchKernelGGL(make_keys_kernel, dim3(grid_for(N, 4 * KEY_SPAN)), dim3(256), 0, s, N, H * L, L, R, 32u, col_ptr, ent_row, keys.p,
-                           d_flags.p);
-        GBRS_TRY(sort_keys64(sc, keys.p, keys2.p, N, 32 + bits_for(R - 1), s));
-        keys.release();
-        DevBuf<uint32_t> pflag, pidx;
-        GBRS_TRY(pflag.alloc(N)); GBRS_TRY(pidx.alloc(N));
-        hipLaunchKernelGGL(pair_flag_kernel, dim3(grid_for(N)), dim3(256), 0, s, N, keys2.p, pflag.p, d_flags.p);
-        GBRS_TRY(exclusive_scan(sc, pflag.p, pidx.p, N, s));
-        uint32_t P32 = 0;
-        GBRS_TRY(fetch_last_plus(pidx.p, pflag.p, N, P32, s));
-        GBRS_HIP_CHECK(hipMemcpyAsync(&hf, d_flags.p, sizeof(hf), hipMemcpyDeviceToHost, s));
-        GBRS_HIP_CHECK(hipStreamSynchronize(s));
-        if (hf.bad_row) return fail(GBRS_ERR_INVALID, "indices hold a row id >= num_rows");
-        if (hf.duplicate) return fail(GBRS_ERR_INVALID, "duplicate (row, locus, haplotype) entry: the CSC arrays must be canonical");
-        P = P32;
-        GBRS_TRY(prow.alloc(P)); GBRS_TRY(ploc.alloc(P)); GBRS_TRY(pmask.alloc(P));
-        hipLaunchKernelGGL(emit_pairs_kernel, dim3(grid_for(N)), dim3(256), 0, s, N, keys2.p, pflag.p, pidx.p, 32u, prow.p, ploc.p,
-                           pmask.p);
-        GBRS_HIP_CHECK(hipStreamSynchronize(s));
-        keys2.release(); pflag.release(); pidx.release();
-        DevBuf<uint32_t> rflag, ridx;
-        GBRS_TRY(rflag.alloc(P)); GBRS_TRY(ridx.alloc(P));
-        hipLaunchKernelGGL(row_flag_kernel, dim3(grid_for(P)), dim3(256), 0, s, P, prow.p, rflag.p);
-        GBRS_TRY(exclusive_scan(sc, rflag.p, ridx.p, P, s));
-        uint32_t R32 = 0;
-        GBRS_TRY(fetch_last_plus(ridx.p, rflag.p, P, R32, s));
-        R1 = R32;
-        GBRS_TRY(rowstart.alloc(R1 + 1)); GBRS_TRY(row_orig.alloc(R1));
-        hipLaunchKernelGGL(row_start_kernel, dim3(grid_for(P)), dim3(256), 0, s, P, R1, rflag.p, ridx.p, prow.p, rowstart.p,
-                           row_orig.p);
-        GBRS_HIP_CHECK(hipStreamSynchronize(s));
-        rflag.release(); ridx.release(); prow.release();
+        GBRS_TRY(build_row_pairs(b, rp, R, L, H, N, ent_row, col_ptr, 32u));
+        R1 = rp.R1;
         DevBuf<uint64_t> rkey, skey;
         DevBuf<uint32_t> ident;
         GBRS_TRY(rkey.alloc(R1)); GBRS_TRY(skey.alloc(R1)); GBRS_TRY(ident.alloc(R1)); GBRS_TRY(srow.alloc(R1));
         const unsigned lbits = bits_for(L - 1);
         hipLaunchKernelGGL(row_key_kernel, dim3(grid_for(R1)), dim3(256), 0, s, R1, 0xFFFFFFFFu, lbits > 24 ? lbits - 24 : 0u,
-                           rowstart.p, ploc.p, pmask.p, rkey.p, ident.p, d_flags.p);
+                           rowstart.p, ploc.p, pmask.p, rkey.p, ident.p, b.d_flags.p);
         GBRS_TRY(sort_pairs<uint64_t>(sc, rkey.p, skey.p, ident.p, srow.p, R1, 64, s));
         GBRS_TRY(head.alloc(R1)); GBRS_TRY(hincl.alloc(R1));
         hipLaunchKernelGGL(merge_flag_kernel, dim3(grid_for(R1)), dim3(256), 0, s, R1, 1, skey.p, srow.p, rowstart.p, ploc.p,
@@ -1153,8 +1234,7 @@ int compress_device(CompressResult &out, uint64_t R, uint32_t L, uint32_t H, uin
             hipLaunchKernelGGL(ec_segment_pos_kernel, dim3(grid_for(R1)), dim3(256), 0, s, R1, head.p, hincl.p, segpos.p);
             hipLaunchKernelGGL(ec_segment_alias_kernel, dim3(grid_for(M)), dim3(256), 0, s, M, segpos.p, skey.p, srow.p, rowstart.p,
                                ploc.p, pmask.p, alias.p, keep.p);
-            GBRS_TRY(exclusive_scan(sc, keep.p, kidx.p, M, s));
-            GBRS_TRY(fetch_last_plus(kidx.p, keep.p, M, m32, s));
+            GBRS_TRY(scan_total(sc, keep.p, kidx.p, M, m32, s));
             hipLaunchKernelGGL(ec_regroup_kernel, dim3(grid_for(R1)), dim3(256), 0, s, R1, alias.p, kidx.p, head.p, hincl.p);
             GBRS_HIP_CHECK(hipStreamSynchronize(s));
             M = m32;
@@ -1198,9 +1278,8 @@ int compress_device(CompressResult &out, uint64_t R, uint32_t L, uint32_t H, uin
     GBRS_TRY(nent.alloc(R1)); GBRS_TRY(eoff.alloc(R1));
     hipLaunchKernelGGL(ec_count_entries_kernel, dim3(grid_for(R1)), dim3(256), 0, s, R1, head.p, srow.p, rowstart.p, pmask.p,
                        nent.p);
-    GBRS_TRY(exclusive_scan(sc, nent.p, eoff.p, R1, s));
     uint32_t E32 = 0;
-    GBRS_TRY(fetch_last_plus(eoff.p, nent.p, R1, E32, s));
+    GBRS_TRY(scan_total(sc, nent.p, eoff.p, R1, E32, s));
     const uint64_t E = E32;
     out.n_entries = E;
     DevBuf<uint64_t> ekeys, ekeys2;
@@ -1217,579 +1296,453 @@ int compress_device(CompressResult &out, uint64_t R, uint32_t L, uint32_t H, uin
     return GBRS_OK;
 }
 
-int build_tile_layout(TileLayout &out, uint64_t R, uint32_t L_in, uint32_t H, uint64_t N,
-                      const uint32_t *ent_row, const uint64_t *col_ptr, const double *count,
-                      bool merge, int row_order, bool deterministic, hipStream_t s, unsigned side_by_side, bool locus_sets,
-                      uint32_t dict_cap, uint32_t view_factor, bool run_words) {
-    uint32_t L = L_in;                     // grows by the number of locus sets in step 3b
-    out.n_sets = 0;
-    out.n_dest_rows = 0;
-    const bool interleave = row_order == 1, streams = row_order == 2;
-    const bool keep_row_ids = out.keep_row_ids && !merge;      // (a merged row has no single file row)
-    if (H > 16) return fail(GBRS_ERR_INVALID, "the tiled layout packs the haplotype mask in 16 bits (H <= 16)");
-    if (N >= 0xFFFFFFFFull || L >= (1u << 27))
-        return fail(GBRS_ERR_INVALID, "the tiled layout needs N < 2^32 entries and L < 2^27 loci per handle");
-    // (common.h) the temporaries are parked while the build runs - a hipMalloc that follows a large hipFree stalls on
-    // some hosts - and go back in one pass when it ends; a one-shot process leaves them to the layout's destructor
-    DeferFrees park_temporaries(out.retain_temporaries ? &out.retired : nullptr, &out.retired_bytes);
-    StageTimer stg("layout");
-    Scratch sc;
-    DevBuf<BuildFlags> d_flags;
-    GBRS_TRY(d_flags.alloc(1));
-    GBRS_HIP_CHECK(hipMemsetAsync(d_flags.p, 0, sizeof(BuildFlags), s));
-    BuildFlags hf{};
-    auto read_flags = [&]() -> int {
-        GBRS_HIP_CHECK(hipMemcpyAsync(&hf, d_flags.p, sizeof(hf), hipMemcpyDeviceToHost, s));
-        GBRS_HIP_CHECK(hipStreamSynchronize(s));
-        return GBRS_OK;
-    };
-    out.d_max = std::min<uint32_t>(1024, lds_theta_doubles(merge || count != nullptr, (int)H) / H);
-    out.d_max = std::min<uint32_t>(out.d_max, dict_index_limit((int)H));     // what a word's index field can hold (1024 at H = 16)
-    out.deterministic = deterministic;
-    if (deterministic) out.d_max = std::min<uint32_t>(out.d_max, det_dict_cap(H, merge || count != nullptr));
-    if (dict_cap) out.d_max = std::min<uint32_t>(out.d_max, std::max<uint32_t>(dict_cap, (uint32_t)max_row_words(H) + 1));
-    if (const char *env = std::getenv("GBRS_TUNING_DICT_CAP"); env && std::atoi(env) > max_row_words(H))
-        out.d_max = std::min<uint32_t>(out.d_max, (uint32_t)std::atoi(env));
-    if (out.d_max <= (uint32_t)max_row_words(H))
-        return fail(GBRS_ERR_UNSUPPORTED, "the deterministic tile layout has no room for a row's loci at H = %u", H);
-    const uint32_t dseg = out.d_max - max_row_words(H);
-    out.weighted = merge || count != nullptr;
-    out.n_pairs = out.n_rows = out.n_rows_in = out.n_long = out.n_tiles = out.n_batches = out.n_slots = out.n_folded = out.n_folded_two = 0;
-    GBRS_TRY(out.slot_ptr.alloc((size_t)L + 1));
-    GBRS_HIP_CHECK(hipMemsetAsync(out.slot_ptr.p, 0, out.slot_ptr.bytes(), s));
-    GBRS_TRY(out.locus_class.alloc(L));
-    GBRS_HIP_CHECK(hipMemsetAsync(out.locus_class.p, 0, out.locus_class.bytes(), s));
-    if (N == 0) { GBRS_HIP_CHECK(hipStreamSynchronize(s)); return GBRS_OK; }
+// ---- the stages of build_tile_layout ---------------------------------------------------------------------------------------
+namespace {
 
-    // 1. entries -> sorted (row, locus, hap) keys
-    DevBuf<uint64_t> keys, keys2;
-    stg.mark("0 setup");
-    GBRS_TRY(keys.alloc(N));
-    GBRS_TRY(keys2.alloc(N));
-    stg.mark("1a key buffers");
-    const unsigned row_shift = 5 + bits_for(L - 1);           // <= 32 (L < 2^27 checked above)
-    // (view_factor > 1: L_in and H are those of the half-locus view, the CSC columns those of the caller's L_in / factor loci
-    // with H * factor haplotypes)
-    hipLaunchKernelGGL(make_keys_kernel, dim3(grid_for(N, 4 * KEY_SPAN)), dim3(256), 0, s, N, H * L, L / view_factor, R, row_shift,
-                       col_ptr, ent_row, keys.p, d_flags.p, view_factor > 1 ? H : 0u);
-    stg.mark("1b make keys");
-    GBRS_TRY(sort_keys64(sc, keys.p, keys2.p, N, row_shift + bits_for(R - 1), s));
-    stg.mark("1c sort entries");
-    keys.release();
-    stg.mark("1d release");
-    // 2. pairs
-    DevBuf<uint32_t> pflag, pidx;
-    GBRS_TRY(pflag.alloc(N));
-    GBRS_TRY(pidx.alloc(N));
-    stg.mark("2a alloc flags");
-    hipLaunchKernelGGL(pair_flag_kernel, dim3(grid_for(N)), dim3(256), 0, s, N, keys2.p, pflag.p, d_flags.p);
-    stg.mark("2b pair flags");
-    GBRS_TRY(exclusive_scan(sc, pflag.p, pidx.p, N, s));
-    stg.mark("2c scan");
-    uint32_t P32 = 0;
-    GBRS_TRY(fetch_last_plus(pidx.p, pflag.p, N, P32, s));
-    GBRS_TRY(read_flags());
-    stg.mark("2d fetch");
-    if (hf.bad_row) return fail(GBRS_ERR_INVALID, "indices hold a row id >= num_rows");
-    if (hf.duplicate) return fail(GBRS_ERR_INVALID, "duplicate (row, locus, haplotype) entry: the CSC arrays must be canonical");
-    const uint64_t P = P32;
-    out.n_pairs = P;
-    DevBuf<uint32_t> prow, ploc, pmask;
-    GBRS_TRY(prow.alloc(P));
-    GBRS_TRY(ploc.alloc(P));
-    GBRS_TRY(pmask.alloc(P));
-    hipLaunchKernelGGL(emit_pairs_kernel, dim3(grid_for(N)), dim3(256), 0, s, N, keys2.p, pflag.p, pidx.p, row_shift,
-                       prow.p, ploc.p, pmask.p);
+// The tail of both forms of the locus sets.  V sets of set_len[v] member loci each have been found: their member lists
+// (`members` launches the kernel that fills out.set_members), the rows' new lengths (`row_len`, into newlen), the rows
+// rewritten with one pair per set (`rewrite`, from rowstart2 into ploc2 / pmask2), and - when `use(P2)` says that the P2
+// pairs left are worth it - the new rows in place of the old ones.
+template <typename Members, typename RowLen, typename Rewrite, typename Use>
+int finish_locus_sets(Build &b, TileLayout &out, RowPairs &rp, uint32_t V, const uint32_t *set_len, Members members,
+                      RowLen row_len, Rewrite rewrite, Use use) {
+    hipStream_t s = b.s;
+    const uint64_t R1 = rp.R1;
+    GBRS_TRY(out.set_ptr.alloc((size_t)V + 1));
+    uint32_t n_members = 0;
+    GBRS_TRY(scan_total(b.sc, set_len, out.set_ptr.p, V, n_members, s, true));
+    GBRS_TRY(out.set_members.alloc(n_members));
+    members();
+    DevBuf<uint32_t> newlen, rowstart2, ploc2, pmask2;
+    GBRS_TRY(newlen.alloc(R1)); GBRS_TRY(rowstart2.alloc((size_t)R1 + 1));
+    row_len(newlen.p);
+    uint32_t P2 = 0;
+    GBRS_TRY(scan_total(b.sc, newlen.p, rowstart2.p, R1, P2, s, true));
+    GBRS_TRY(ploc2.alloc(P2)); GBRS_TRY(pmask2.alloc(P2));
+    rewrite(rowstart2.p, ploc2.p, pmask2.p);
     GBRS_HIP_CHECK(hipStreamSynchronize(s));
-    stg.mark("2e emit pairs");
-    keys2.release(); pflag.release(); pidx.release();
-    stg.mark("2 pairs (release)");
-    // 3. rows
-    DevBuf<uint32_t> rflag, ridx;
-    GBRS_TRY(rflag.alloc(P));
-    GBRS_TRY(ridx.alloc(P));
-    hipLaunchKernelGGL(row_flag_kernel, dim3(grid_for(P)), dim3(256), 0, s, P, prow.p, rflag.p);
-    GBRS_TRY(exclusive_scan(sc, rflag.p, ridx.p, P, s));
-    uint32_t R1 = 0;
-    GBRS_TRY(fetch_last_plus(ridx.p, rflag.p, P, R1, s));
-    out.n_rows_in = R1;
-    DevBuf<uint32_t> rowstart, row_orig;
-    GBRS_TRY(rowstart.alloc((size_t)R1 + 1));
-    GBRS_TRY(row_orig.alloc(R1));
-    hipLaunchKernelGGL(row_start_kernel, dim3(grid_for(P)), dim3(256), 0, s, P, (uint64_t)R1, rflag.p, ridx.p, prow.p,
-                       rowstart.p, row_orig.p);
-    GBRS_HIP_CHECK(hipStreamSynchronize(s));
-    rflag.release(); ridx.release(); prow.release();
-    stg.mark("3 rows");
-    // 3b. locus sets, first form (round 3): a row whose pairs ALL carry one mask becomes one pair on the id of its locus set
-    // (em_layout.h), every distinct set kept.  Round 4's step 3c below finds the same sets (a whole row is a row with one mask
-    // group) and keeps the frequent ones only, which is what the samples want (C2: all 98,725 sets 0.0901 ms per iteration,
-    // the 17-42 k sets carried by >= 128 / 32 reads 0.0857); this form stays reachable with GBRS_TUNING_LOCUS_SETS=1.
-    const bool whole_row_sets_forced = [] { const char *e = std::getenv("GBRS_TUNING_LOCUS_SETS"); return e && std::atoi(e) == 1; }();
-    if (locus_sets && R1 > 0 && whole_row_sets_forced) {
-        DevBuf<uint64_t> key, ckey, skey2;
-        DevBuf<uint32_t> flag, cidx, crow, srow2;
-        GBRS_TRY(key.alloc(R1)); GBRS_TRY(flag.alloc(R1)); GBRS_TRY(cidx.alloc(R1));
-        hipLaunchKernelGGL(set_candidate_kernel, dim3(grid_for(R1)), dim3(256), 0, s, (uint64_t)R1, rowstart.p, ploc.p, pmask.p,
-                           key.p, flag.p);
-        GBRS_TRY(exclusive_scan(sc, flag.p, cidx.p, R1, s));
-        uint32_t C = 0;
-        GBRS_TRY(fetch_last_plus(cidx.p, flag.p, R1, C, s));
-        if (C > 0) {
-            GBRS_TRY(ckey.alloc(C)); GBRS_TRY(skey2.alloc(C)); GBRS_TRY(crow.alloc(C)); GBRS_TRY(srow2.alloc(C));
-            hipLaunchKernelGGL(set_compact_kernel, dim3(grid_for(R1)), dim3(256), 0, s, (uint64_t)R1, flag.p, cidx.p, key.p,
-                               ckey.p, crow.p);
-            GBRS_TRY(sort_pairs<uint64_t>(sc, ckey.p, skey2.p, crow.p, srow2.p, C, 64, s));
-            key.release(); ckey.release(); crow.release();
-            DevBuf<uint32_t> head2, hincl2, set_of_row;
-            GBRS_TRY(head2.alloc(C)); GBRS_TRY(hincl2.alloc(C)); GBRS_TRY(set_of_row.alloc(R1));
-            hipLaunchKernelGGL(set_head_kernel, dim3(grid_for(C)), dim3(256), 0, s, (uint64_t)C, skey2.p, srow2.p, rowstart.p,
-                               ploc.p, head2.p);
-            GBRS_TRY(inclusive_scan(sc, head2.p, hincl2.p, C, s));
-            uint32_t V = 0;
-            GBRS_HIP_CHECK(hipMemcpyAsync(&V, hincl2.p + C - 1, 4, hipMemcpyDeviceToHost, s));
-            GBRS_HIP_CHECK(hipStreamSynchronize(s));
-            // (ids of loci and sets share the 27 bits of a row key: a sample with that many distinct sets keeps its plain rows)
-            const bool ids_fit = (uint64_t)L_in + V < (1u << 27);
-            if (!ids_fit) V = 0;
-            DevBuf<uint32_t> set_len, set_rep;
-            if (ids_fit) {
-            GBRS_TRY(set_len.alloc(V)); GBRS_TRY(set_rep.alloc(V));
-            GBRS_HIP_CHECK(hipMemsetAsync(set_of_row.p, 0xFF, set_of_row.bytes(), s));
-            hipLaunchKernelGGL(set_assign_kernel, dim3(grid_for(C)), dim3(256), 0, s, (uint64_t)C, head2.p, hincl2.p, srow2.p,
-                               rowstart.p, set_of_row.p, set_len.p, set_rep.p);
-            GBRS_TRY(out.set_ptr.alloc((size_t)V + 1));
-            GBRS_TRY(exclusive_scan(sc, set_len.p, out.set_ptr.p, V, s));
-            uint32_t n_members = 0;
-            GBRS_TRY(fetch_last_plus(out.set_ptr.p, set_len.p, V, n_members, s));
-            GBRS_HIP_CHECK(hipMemcpyAsync(out.set_ptr.p + V, &n_members, 4, hipMemcpyHostToDevice, s));
-            GBRS_TRY(out.set_members.alloc(n_members));
-            hipLaunchKernelGGL(set_members_kernel, dim3(grid_for(V)), dim3(256), 0, s, V, out.set_ptr.p, set_rep.p, rowstart.p,
-                               ploc.p, out.set_members.p);
-            // the rows in their new form
-            DevBuf<uint32_t> newlen, rowstart2, ploc2, pmask2;
-            GBRS_TRY(newlen.alloc(R1)); GBRS_TRY(rowstart2.alloc((size_t)R1 + 1));
-            hipLaunchKernelGGL(set_row_len_kernel, dim3(grid_for(R1)), dim3(256), 0, s, (uint64_t)R1, rowstart.p, set_of_row.p,
-                               newlen.p);
-            GBRS_TRY(exclusive_scan(sc, newlen.p, rowstart2.p, R1, s));
-            uint32_t P2 = 0;
-            GBRS_TRY(fetch_last_plus(rowstart2.p, newlen.p, R1, P2, s));
-            GBRS_HIP_CHECK(hipMemcpyAsync(rowstart2.p + R1, &P2, 4, hipMemcpyHostToDevice, s));
-            GBRS_TRY(ploc2.alloc(P2)); GBRS_TRY(pmask2.alloc(P2));
-            hipLaunchKernelGGL(set_rewrite_kernel, dim3(grid_for(R1)), dim3(256), 0, s, (uint64_t)R1, L_in, rowstart.p,
-                               set_of_row.p, rowstart2.p, ploc.p, pmask.p, ploc2.p, pmask2.p);
-            GBRS_HIP_CHECK(hipStreamSynchronize(s));
-            GBRS_HIP_CHECK(hipGetLastError());
-            // Worth it?  A set entry costs its tile a longer prologue and epilogue (its members' theta summed, its sums
-            // stored once per member), which pays when the words it saves are many and every dictionary entry serves many
-            // words.  Measured (profiles/r03_estep_experiments.txt item 8): C2, 23 % fewer words at 137 words per id:
-            // E-step -11 %; the 16-haplotype shard (same saving, 62 words per id) +8 %; multi-isoform reads (9 % fewer
-            // words) +8 %.  GBRS_TUNING_LOCUS_SETS=1 / 0 forces the choice.
-            // (and no more sets than twice the loci: many thin sets fill the tiles' dictionaries, item 16 of the same file)
-            bool use = (uint64_t)P2 * 100 <= (uint64_t)P * 85 && (uint64_t)P2 >= 100ull * ((uint64_t)L_in + V) && (uint64_t)V <= 2ull * L_in;
-            if (const char *env = std::getenv("GBRS_TUNING_LOCUS_SETS"); env) use = std::atoi(env) != 0;
-            if (use) {
-                rowstart.swap(rowstart2); ploc.swap(ploc2); pmask.swap(pmask2);
-                out.n_sets = V;
-                out.n_pairs = P2;
-                L = L_in + V;              // ids of the rows' pairs, the sort keys and the dictionaries from here on
-            } else {
-                out.set_ptr.release();
-                out.set_members.release();
-            }
-            }   // ids_fit
-        }
-        stg.mark("3b locus sets");
+    GBRS_HIP_CHECK(hipGetLastError());
+    if (use(P2)) {
+        rp.rowstart.swap(rowstart2); rp.ploc.swap(ploc2); rp.pmask.swap(pmask2);
+        out.n_sets = V;            // ids of the rows' pairs, the sort keys and the dictionaries are loci + sets from here on
+        out.n_pairs = P2;
+    } else {
+        out.set_ptr.release();
+        out.set_members.release();
     }
-    // 3c. locus sets per mask group, when the rows are no whole-row sets (reads over several isoforms with differing masks):
-    // the loci of a row that share a mask become one pair on a set id, for the sets that enough rows carry
-    if (locus_sets && R1 > 0 && out.n_sets == 0) {
-        const char *genv = std::getenv("GBRS_TUNING_GROUP_SETS");
-        const bool forced_on = genv && std::atoi(genv) == 1, forced_off = genv && std::atoi(genv) == 0;
-        // rows a set must be carried by.  Iteration time, one box each: multi-isoform sample (2.35 words per read, no sets 0.1970 ms):
-        // 64 rows (39 k sets) 0.199, 128 (21 k) 0.188, 160: 0.186, 192 (13.8 k) 0.184, 256 (10 k) 0.183, 384 / 512: 0.184;
-        // C2 (whole-row sets, all 98.7 k of them 0.0901 ms): 32 rows (42.5 k) 0.0858, 128 (17 k) 0.0857, 512 (4.3 k) 0.0881
-        uint32_t min_rows = 192;
-        if (const char *e = std::getenv("GBRS_TUNING_SET_MIN_ROWS"); e && std::atoi(e) > 0) min_rows = (uint32_t)std::atoi(e);
-        DevBuf<uint32_t> gloc, gmask, nseg, segoff;
-        if (!forced_off) {
-            GBRS_TRY(gloc.alloc(P)); GBRS_TRY(gmask.alloc(P)); GBRS_TRY(nseg.alloc(R1)); GBRS_TRY(segoff.alloc((size_t)R1 + 1));
-            hipLaunchKernelGGL(group_sort_kernel, dim3(grid_for(R1)), dim3(256), 0, s, (uint64_t)R1, rowstart.p, ploc.p, pmask.p,
-                               gloc.p, gmask.p, nseg.p);
-            GBRS_TRY(exclusive_scan(sc, nseg.p, segoff.p, R1, s));
-            uint32_t S = 0;
-            GBRS_TRY(fetch_last_plus(segoff.p, nseg.p, R1, S, s));
-            GBRS_HIP_CHECK(hipMemcpyAsync(segoff.p + R1, &S, 4, hipMemcpyHostToDevice, s));
-            DevBuf<uint32_t> seg_begin, seg_len, cand, cidx;
-            DevBuf<uint64_t> key;
-            GBRS_TRY(seg_begin.alloc(S)); GBRS_TRY(seg_len.alloc(S)); GBRS_TRY(cand.alloc(S)); GBRS_TRY(cidx.alloc(S));
-            GBRS_TRY(key.alloc(S));
-            hipLaunchKernelGGL(group_segments_kernel, dim3(grid_for(R1)), dim3(256), 0, s, (uint64_t)R1, rowstart.p, gloc.p, gmask.p,
-                               segoff.p, seg_begin.p, seg_len.p, key.p, cand.p);
-            GBRS_TRY(exclusive_scan(sc, cand.p, cidx.p, S, s));
-            uint32_t C = 0;
-            GBRS_TRY(fetch_last_plus(cidx.p, cand.p, S, C, s));
-            if (C > 0 && S < P) {
-                DevBuf<uint64_t> ckey, skey2;
-                DevBuf<uint32_t> cseg, sseg, head2, hincl2;
-                GBRS_TRY(ckey.alloc(C)); GBRS_TRY(skey2.alloc(C)); GBRS_TRY(cseg.alloc(C)); GBRS_TRY(sseg.alloc(C));
-                hipLaunchKernelGGL(group_compact_kernel, dim3(grid_for(S)), dim3(256), 0, s, (uint64_t)S, cand.p, cidx.p, key.p,
-                                   ckey.p, cseg.p);
-                GBRS_TRY(sort_pairs<uint64_t>(sc, ckey.p, skey2.p, cseg.p, sseg.p, C, 64, s));
-                key.release(); ckey.release(); cseg.release(); cand.release(); cidx.release();
-                GBRS_TRY(head2.alloc(C)); GBRS_TRY(hincl2.alloc(C));
-                hipLaunchKernelGGL(group_head_kernel, dim3(grid_for(C)), dim3(256), 0, s, (uint64_t)C, skey2.p, sseg.p, seg_begin.p,
-                                   seg_len.p, gloc.p, head2.p);
-                GBRS_TRY(inclusive_scan(sc, head2.p, hincl2.p, C, s));
-                uint32_t Vp = 0;
-                GBRS_HIP_CHECK(hipMemcpyAsync(&Vp, hincl2.p + C - 1, 4, hipMemcpyDeviceToHost, s));
-                GBRS_HIP_CHECK(hipStreamSynchronize(s));
-                DevBuf<uint32_t> cnt, rep, keep, newid;
-                GBRS_TRY(cnt.alloc(Vp)); GBRS_TRY(rep.alloc(Vp)); GBRS_TRY(keep.alloc(Vp)); GBRS_TRY(newid.alloc(Vp));
-                GBRS_HIP_CHECK(hipMemsetAsync(cnt.p, 0, cnt.bytes(), s));
-                hipLaunchKernelGGL(group_count_kernel, dim3(grid_for(C)), dim3(256), 0, s, (uint64_t)C, head2.p, hincl2.p, sseg.p,
-                                   cnt.p, rep.p);
-                // the frequent sets only, and no more of them than half the loci: the threshold doubles until they fit
-                uint32_t V = 0;
-                for (int round = 0; round < 24; ++round) {
-                    hipLaunchKernelGGL(group_keep_kernel, dim3(grid_for(Vp)), dim3(256), 0, s, Vp, min_rows, cnt.p, keep.p);
-                    GBRS_TRY(exclusive_scan(sc, keep.p, newid.p, Vp, s));
-                    GBRS_TRY(fetch_last_plus(newid.p, keep.p, Vp, V, s));
-                    if ((uint64_t)V * 2 <= (uint64_t)L_in || forced_on) break;
-                    min_rows *= 2;
-                }
-                if (V > 0 && (uint64_t)L_in + V < (1u << 27)) {
-                    DevBuf<uint32_t> set_of_seg, set_len, set_rep, newlen, rowstart2, ploc2, pmask2;
-                    GBRS_TRY(set_of_seg.alloc(S)); GBRS_TRY(set_len.alloc(V)); GBRS_TRY(set_rep.alloc(V));
-                    GBRS_HIP_CHECK(hipMemsetAsync(set_of_seg.p, 0xFF, set_of_seg.bytes(), s));
-                    hipLaunchKernelGGL(group_assign_kernel, dim3(grid_for(C)), dim3(256), 0, s, (uint64_t)C, hincl2.p, sseg.p, keep.p,
-                                       newid.p, rep.p, seg_len.p, set_of_seg.p, set_len.p, set_rep.p);
-                    GBRS_TRY(out.set_ptr.alloc((size_t)V + 1));
-                    GBRS_TRY(exclusive_scan(sc, set_len.p, out.set_ptr.p, V, s));
-                    uint32_t n_members = 0;
-                    GBRS_TRY(fetch_last_plus(out.set_ptr.p, set_len.p, V, n_members, s));
-                    GBRS_HIP_CHECK(hipMemcpyAsync(out.set_ptr.p + V, &n_members, 4, hipMemcpyHostToDevice, s));
-                    GBRS_TRY(out.set_members.alloc(n_members));
-                    hipLaunchKernelGGL(group_members_kernel, dim3(grid_for(V)), dim3(256), 0, s, V, out.set_ptr.p, set_rep.p,
-                                       seg_begin.p, gloc.p, out.set_members.p);
-                    GBRS_TRY(newlen.alloc(R1)); GBRS_TRY(rowstart2.alloc((size_t)R1 + 1));
-                    hipLaunchKernelGGL(group_row_len_kernel, dim3(grid_for(R1)), dim3(256), 0, s, (uint64_t)R1, segoff.p, seg_len.p,
-                                       set_of_seg.p, newlen.p);
-                    GBRS_TRY(exclusive_scan(sc, newlen.p, rowstart2.p, R1, s));
-                    uint32_t P2 = 0;
-                    GBRS_TRY(fetch_last_plus(rowstart2.p, newlen.p, R1, P2, s));
-                    GBRS_HIP_CHECK(hipMemcpyAsync(rowstart2.p + R1, &P2, 4, hipMemcpyHostToDevice, s));
-                    GBRS_TRY(ploc2.alloc(P2)); GBRS_TRY(pmask2.alloc(P2));
-                    hipLaunchKernelGGL(group_rewrite_kernel, dim3(grid_for(R1)), dim3(256), 0, s, (uint64_t)R1, L_in, segoff.p,
-                                       seg_begin.p, seg_len.p, set_of_seg.p, rowstart2.p, gloc.p, gmask.p, ploc2.p, pmask2.p);
-                    GBRS_HIP_CHECK(hipStreamSynchronize(s));
-                    GBRS_HIP_CHECK(hipGetLastError());
-                    // worth it when the frequent sets take a twentieth of the words away (GBRS_TUNING_GROUP_SETS=1 / 0 forces the choice)
-                    const bool use = forced_on || (uint64_t)P2 * 100 <= (uint64_t)P * 95;
-                    if (use) {
-                        rowstart.swap(rowstart2); ploc.swap(ploc2); pmask.swap(pmask2);
-                        out.n_sets = V;
-                        out.n_pairs = P2;
-                        L = L_in + V;
-                    } else {
-                        out.set_ptr.release();
-                        out.set_members.release();
-                    }
-                }
-            }
-        }
-        stg.mark("3c mask-group sets");
+    return GBRS_OK;
+}
+
+// 3b. locus sets, first form (round 3): a row whose pairs ALL carry one mask becomes one pair on the id of its locus set
+// (em_layout.h), every distinct set kept.  Round 4's step 3c below finds the same sets (a whole row is a row with one mask
+// group) and keeps the frequent ones only, which is what the samples want (C2: all 98,725 sets 0.0901 ms per iteration,
+// the 17-42 k sets carried by >= 128 / 32 reads 0.0857); this form stays reachable with GBRS_TUNING_LOCUS_SETS=1.
+int whole_row_sets(Build &b, TileLayout &out, RowPairs &rp, const EmPlan &plan) {
+    hipStream_t s = b.s;
+    Scratch &sc = b.sc;
+    const uint64_t R1 = rp.R1, P = rp.P;
+    const uint32_t L_in = plan.tL;
+    const uint32_t *rowstart = rp.rowstart.p, *ploc = rp.ploc.p, *pmask = rp.pmask.p;
+    DevBuf<uint64_t> key, ckey, skey2;
+    DevBuf<uint32_t> flag, cidx, crow, srow2;
+    GBRS_TRY(key.alloc(R1)); GBRS_TRY(flag.alloc(R1)); GBRS_TRY(cidx.alloc(R1));
+    hipLaunchKernelGGL(set_candidate_kernel, dim3(grid_for(R1)), dim3(256), 0, s, R1, rowstart, ploc, pmask, key.p, flag.p);
+    uint32_t C = 0;
+    GBRS_TRY(scan_total(sc, flag.p, cidx.p, R1, C, s));
+    if (C == 0) return GBRS_OK;
+    GBRS_TRY(ckey.alloc(C)); GBRS_TRY(skey2.alloc(C)); GBRS_TRY(crow.alloc(C)); GBRS_TRY(srow2.alloc(C));
+    hipLaunchKernelGGL(set_compact_kernel, dim3(grid_for(R1)), dim3(256), 0, s, R1, flag.p, cidx.p, key.p, ckey.p, crow.p);
+    GBRS_TRY(sort_pairs<uint64_t>(sc, ckey.p, skey2.p, crow.p, srow2.p, C, 64, s));
+    key.release(); ckey.release(); crow.release();
+    DevBuf<uint32_t> head2, hincl2, set_of_row;
+    GBRS_TRY(head2.alloc(C)); GBRS_TRY(hincl2.alloc(C)); GBRS_TRY(set_of_row.alloc(R1));
+    hipLaunchKernelGGL(set_head_kernel, dim3(grid_for(C)), dim3(256), 0, s, (uint64_t)C, skey2.p, srow2.p, rowstart, ploc, head2.p);
+    uint32_t V = 0;
+    GBRS_TRY(scan_heads(sc, head2.p, hincl2.p, C, V, s));
+    // (ids of loci and sets share the 27 bits of a row key: a sample with that many distinct sets keeps its plain rows)
+    if ((uint64_t)L_in + V >= (1u << 27)) return GBRS_OK;
+    DevBuf<uint32_t> set_len, set_rep;
+    GBRS_TRY(set_len.alloc(V)); GBRS_TRY(set_rep.alloc(V));
+    GBRS_HIP_CHECK(hipMemsetAsync(set_of_row.p, 0xFF, set_of_row.bytes(), s));
+    hipLaunchKernelGGL(set_assign_kernel, dim3(grid_for(C)), dim3(256), 0, s, (uint64_t)C, head2.p, hincl2.p, srow2.p, rowstart,
+                       set_of_row.p, set_len.p, set_rep.p);
+    return finish_locus_sets(
+        b, out, rp, V, set_len.p,
+        [&] { hipLaunchKernelGGL(set_members_kernel, dim3(grid_for(V)), dim3(256), 0, s, V, out.set_ptr.p, set_rep.p, rowstart, ploc,
+                                 out.set_members.p); },
+        [&](uint32_t *newlen) { hipLaunchKernelGGL(set_row_len_kernel, dim3(grid_for(R1)), dim3(256), 0, s, R1, rowstart,
+                                                   set_of_row.p, newlen); },
+        [&](const uint32_t *rowstart2, uint32_t *ploc2, uint32_t *pmask2) {
+            hipLaunchKernelGGL(set_rewrite_kernel, dim3(grid_for(R1)), dim3(256), 0, s, R1, L_in, rowstart, set_of_row.p, rowstart2,
+                               ploc, pmask, ploc2, pmask2); },
+        [&](uint32_t P2) { return em_use_whole_row_sets(plan, P, P2, L_in, V); });
+}
+
+// 3c. locus sets per mask group, when the rows are no whole-row sets (reads over several isoforms with differing masks):
+// the loci of a row that share a mask become one pair on a set id, for the sets that enough rows carry
+int mask_group_sets(Build &b, TileLayout &out, RowPairs &rp, const EmPlan &plan) {
+    hipStream_t s = b.s;
+    Scratch &sc = b.sc;
+    const uint64_t R1 = rp.R1, P = rp.P;
+    const uint32_t L_in = plan.tL;
+    const uint32_t *rowstart = rp.rowstart.p, *ploc = rp.ploc.p, *pmask = rp.pmask.p;
+    // rows a set must be carried by.  Iteration time, one box each: multi-isoform sample (2.35 words per read, no sets 0.1970 ms):
+    // 64 rows (39 k sets) 0.199, 128 (21 k) 0.188, 160: 0.186, 192 (13.8 k) 0.184, 256 (10 k) 0.183, 384 / 512: 0.184;
+    // C2 (whole-row sets, all 98.7 k of them 0.0901 ms): 32 rows (42.5 k) 0.0858, 128 (17 k) 0.0857, 512 (4.3 k) 0.0881
+    uint32_t min_rows = plan.set_min_rows;
+    DevBuf<uint32_t> gloc, gmask, nseg, segoff;
+    GBRS_TRY(gloc.alloc(P)); GBRS_TRY(gmask.alloc(P)); GBRS_TRY(nseg.alloc(R1)); GBRS_TRY(segoff.alloc((size_t)R1 + 1));
+    hipLaunchKernelGGL(group_sort_kernel, dim3(grid_for(R1)), dim3(256), 0, s, R1, rowstart, ploc, pmask, gloc.p, gmask.p, nseg.p);
+    uint32_t S = 0;
+    GBRS_TRY(scan_total(sc, nseg.p, segoff.p, R1, S, s, true));
+    DevBuf<uint32_t> seg_begin, seg_len, cand, cidx;
+    DevBuf<uint64_t> key;
+    GBRS_TRY(seg_begin.alloc(S)); GBRS_TRY(seg_len.alloc(S)); GBRS_TRY(cand.alloc(S)); GBRS_TRY(cidx.alloc(S));
+    GBRS_TRY(key.alloc(S));
+    hipLaunchKernelGGL(group_segments_kernel, dim3(grid_for(R1)), dim3(256), 0, s, R1, rowstart, gloc.p, gmask.p, segoff.p,
+                       seg_begin.p, seg_len.p, key.p, cand.p);
+    uint32_t C = 0;
+    GBRS_TRY(scan_total(sc, cand.p, cidx.p, S, C, s));
+    if (C == 0 || S >= P) return GBRS_OK;
+    DevBuf<uint64_t> ckey, skey2;
+    DevBuf<uint32_t> cseg, sseg, head2, hincl2;
+    GBRS_TRY(ckey.alloc(C)); GBRS_TRY(skey2.alloc(C)); GBRS_TRY(cseg.alloc(C)); GBRS_TRY(sseg.alloc(C));
+    hipLaunchKernelGGL(group_compact_kernel, dim3(grid_for(S)), dim3(256), 0, s, (uint64_t)S, cand.p, cidx.p, key.p, ckey.p, cseg.p);
+    GBRS_TRY(sort_pairs<uint64_t>(sc, ckey.p, skey2.p, cseg.p, sseg.p, C, 64, s));
+    key.release(); ckey.release(); cseg.release(); cand.release(); cidx.release();
+    GBRS_TRY(head2.alloc(C)); GBRS_TRY(hincl2.alloc(C));
+    hipLaunchKernelGGL(group_head_kernel, dim3(grid_for(C)), dim3(256), 0, s, (uint64_t)C, skey2.p, sseg.p, seg_begin.p, seg_len.p,
+                       gloc.p, head2.p);
+    uint32_t Vp = 0;
+    GBRS_TRY(scan_heads(sc, head2.p, hincl2.p, C, Vp, s));
+    DevBuf<uint32_t> cnt, rep, keep, newid;
+    GBRS_TRY(cnt.alloc(Vp)); GBRS_TRY(rep.alloc(Vp)); GBRS_TRY(keep.alloc(Vp)); GBRS_TRY(newid.alloc(Vp));
+    GBRS_HIP_CHECK(hipMemsetAsync(cnt.p, 0, cnt.bytes(), s));
+    hipLaunchKernelGGL(group_count_kernel, dim3(grid_for(C)), dim3(256), 0, s, (uint64_t)C, head2.p, hincl2.p, sseg.p, cnt.p, rep.p);
+    // the frequent sets only, and no more of them than half the loci: the threshold doubles until they fit
+    uint32_t V = 0;
+    for (int round = 0; round < 24; ++round) {
+        hipLaunchKernelGGL(group_keep_kernel, dim3(grid_for(Vp)), dim3(256), 0, s, Vp, min_rows, cnt.p, keep.p);
+        GBRS_TRY(scan_total(sc, keep.p, newid.p, Vp, V, s));
+        if (em_group_sets_fit(plan, V, L_in)) break;
+        min_rows *= 2;
     }
-    // 4. order rows so that similar rows are adjacent
-    DevBuf<uint64_t> rkey, skey;
-    DevBuf<uint32_t> ident, srow;
-    GBRS_TRY(rkey.alloc(R1)); GBRS_TRY(skey.alloc(R1)); GBRS_TRY(ident.alloc(R1)); GBRS_TRY(srow.alloc(R1));
+    if (V == 0 || (uint64_t)L_in + V >= (1u << 27)) return GBRS_OK;
+    DevBuf<uint32_t> set_of_seg, set_len, set_rep;
+    GBRS_TRY(set_of_seg.alloc(S)); GBRS_TRY(set_len.alloc(V)); GBRS_TRY(set_rep.alloc(V));
+    GBRS_HIP_CHECK(hipMemsetAsync(set_of_seg.p, 0xFF, set_of_seg.bytes(), s));
+    hipLaunchKernelGGL(group_assign_kernel, dim3(grid_for(C)), dim3(256), 0, s, (uint64_t)C, hincl2.p, sseg.p, keep.p, newid.p, rep.p,
+                       seg_len.p, set_of_seg.p, set_len.p, set_rep.p);
+    return finish_locus_sets(
+        b, out, rp, V, set_len.p,
+        [&] { hipLaunchKernelGGL(group_members_kernel, dim3(grid_for(V)), dim3(256), 0, s, V, out.set_ptr.p, set_rep.p, seg_begin.p,
+                                 gloc.p, out.set_members.p); },
+        [&](uint32_t *newlen) { hipLaunchKernelGGL(group_row_len_kernel, dim3(grid_for(R1)), dim3(256), 0, s, R1, segoff.p, seg_len.p,
+                                                   set_of_seg.p, newlen); },
+        [&](const uint32_t *rowstart2, uint32_t *ploc2, uint32_t *pmask2) {
+            hipLaunchKernelGGL(group_rewrite_kernel, dim3(grid_for(R1)), dim3(256), 0, s, R1, L_in, segoff.p, seg_begin.p, seg_len.p,
+                               set_of_seg.p, rowstart2, gloc.p, gmask.p, ploc2, pmask2); },
+        [&](uint32_t P2) { return em_use_group_sets(plan, P, P2); });
+}
+
+// the rows in the order of step 4: the n_short rows of the tiles first, then the n_long rows that keep their pair form
+struct SortedRows {
+    DevBuf<uint64_t> skey;       // (step 5 only)
+    DevBuf<uint32_t> srow;
+    uint64_t n_long = 0, n_short = 0;
+};
+
+// 4. order rows so that similar rows are adjacent.  L: loci + locus sets
+int order_rows(Build &b, TileLayout &out, const RowPairs &rp, SortedRows &rows, uint32_t L, uint32_t H) {
+    hipStream_t s = b.s;
+    const uint64_t R1 = rp.R1;
+    DevBuf<uint64_t> rkey;
+    DevBuf<uint32_t> ident;
+    GBRS_TRY(rkey.alloc(R1)); GBRS_TRY(rows.skey.alloc(R1)); GBRS_TRY(ident.alloc(R1)); GBRS_TRY(rows.srow.alloc(R1));
     const unsigned lbits = bits_for(L - 1);
-    hipLaunchKernelGGL(row_key_kernel, dim3(grid_for(R1)), dim3(256), 0, s, (uint64_t)R1, (uint32_t)max_row_words(H),
-                       lbits > 24 ? lbits - 24 : 0u,
-                       rowstart.p, ploc.p, pmask.p, rkey.p, ident.p, d_flags.p);
-    GBRS_TRY(sort_pairs<uint64_t>(sc, rkey.p, skey.p, ident.p, srow.p, R1, 64, s));
-    GBRS_TRY(read_flags());
-    rkey.release(); ident.release();
-    const uint64_t n_long = hf.n_long, n_short = R1 - n_long;
-    out.n_long = n_long;
-    stg.mark("4 order rows");
-    // 5. optional merge of identical adjacent rows + weights - or the fold of identical one-word reads (em_layout.h): the
-    // reads of one (dictionary entry, mask) class that the sort left next to each other keep one row with a repeat count,
-    // cut every FOLD_CAP rows.  The fold exists where the E-step kernels read the count: the leading one-word batches of the
-    // stream order's unweighted tiles (TileHdr::n_one) of the haplotype counts with a kernel instance of their own.  Reads
-    // of exactly two words fold the same way (fold_mode 3): their run of a tile follows its one-word batches on lane pairs
-    // (TileHdr::n_two), where the lane's parity stands for a word's position and both words carry the row's count.
-    // GBRS_TUNING_RUN_WORDS: 0 no fold, 1 the one-word fold alone, 2 both folds - forced; unset: the rule below.
-    const bool counted_pairs = streams && !out.weighted && !deterministic && view_factor == 1 &&
-                               (H == 1 || H == 2 || H == 4 || H == 8);       // the kernels that read TileHdr::n_two
-    bool fold = run_words && counted_pairs;
-    const char *fold_env = std::getenv("GBRS_TUNING_RUN_WORDS");
-    if (fold_env && std::atoi(fold_env) == 0) fold = false;
-    int fold_mode = (fold_env && std::atoi(fold_env) == 1) ? 2 : 3;          // merge_flag_kernel's mode: 3 both folds, 2 one-word
-    DevBuf<unsigned long long> two_total;
-    unsigned long long folded_two = 0;
-    const uint32_t FOLD_CAP = 1u << (2 * pos_bits((int)H));
-    DevBuf<uint32_t> head, hincl, hrow, repeat;
-    uint64_t M = n_short;
+    hipLaunchKernelGGL(row_key_kernel, dim3(grid_for(R1)), dim3(256), 0, s, R1, (uint32_t)max_row_words(H),
+                       lbits > 24 ? lbits - 24 : 0u, rp.rowstart.p, rp.ploc.p, rp.pmask.p, rkey.p, ident.p, b.d_flags.p);
+    GBRS_TRY(sort_pairs<uint64_t>(b.sc, rkey.p, rows.skey.p, ident.p, rows.srow.p, R1, 64, s));
+    GBRS_TRY(b.read_flags());
+    rows.n_long = b.hf.n_long;
+    rows.n_short = R1 - rows.n_long;
+    out.n_long = rows.n_long;
+    return GBRS_OK;
+}
+
+// the short rows of the layout: row hrow[i] of the pairs, standing for 1 + repeat[i] reads where the layout folds
+struct LayoutRows {
+    DevBuf<uint32_t> hrow, repeat;
+    uint64_t M = 0;
+    bool fold = false;
+    void release() { hrow.release(); repeat.release(); }
+};
+
+// 5. optional merge of identical adjacent rows + weights - or the fold of identical one-word reads (em_layout.h): the
+// reads of one (dictionary entry, mask) class that the sort left next to each other keep one row with a repeat count,
+// cut every FOLD_CAP rows.  The fold exists where the E-step kernels read the count: the leading one-word batches of the
+// stream order's unweighted tiles (TileHdr::n_one) of the haplotype counts with a kernel instance of their own.  Reads
+// of exactly two words fold the same way (fold_mode 3): their run of a tile follows its one-word batches on lane pairs
+// (TileHdr::n_two), where the lane's parity stands for a word's position and both words carry the row's count.
+// Both folds are tried first, then the one-word fold alone, then one row per read (em_plan.h: em_take_fold).
+int merge_rows(Build &b, TileLayout &out, const RowPairs &rp, SortedRows &rows, LayoutRows &lr, const double *count,
+               const EmPlan &plan) {
+    hipStream_t s = b.s;
+    const uint64_t n_short = rows.n_short;
+    const uint32_t FOLD_CAP = 1u << (2 * pos_bits((int)plan.tH));
+    const uint32_t *srow = rows.srow.p, *rowstart = rp.rowstart.p;
+    bool fold = plan.fold;
+    int fold_mode = plan.fold_mode;          // merge_flag_kernel's mode: 3 both folds, 2 one-word
+    lr.M = n_short;
     if (n_short) {
+        DevBuf<unsigned long long> two_total;
+        DevBuf<uint32_t> head, hincl;
         GBRS_TRY(head.alloc(n_short)); GBRS_TRY(hincl.alloc(n_short));
         uint32_t m32 = 0;
         for (;;) {
-            hipLaunchKernelGGL(merge_flag_kernel, dim3(grid_for(n_short)), dim3(256), 0, s, n_short, fold ? fold_mode : (merge ? 1 : 0),
-                               skey.p, srow.p, rowstart.p, ploc.p, pmask.p, head.p);
+            hipLaunchKernelGGL(merge_flag_kernel, dim3(grid_for(n_short)), dim3(256), 0, s, n_short,
+                               fold ? fold_mode : (plan.merge ? 1 : 0), rows.skey.p, srow, rowstart, rp.ploc.p, rp.pmask.p, head.p);
             if (fold) {
                 DevBuf<uint32_t> hpos;
                 GBRS_TRY(hpos.alloc(n_short));
                 hipLaunchKernelGGL(run_head_pos_kernel, dim3(grid_for(n_short)), dim3(256), 0, s, n_short, head.p, hincl.p);
-                size_t bytes = 0;
-                GBRS_PRIM(rocprim::inclusive_scan(nullptr, bytes, hincl.p, hpos.p, (size_t)n_short, rocprim::maximum<uint32_t>(), s));
-                GBRS_TRY(sc.reserve(bytes));
-                GBRS_PRIM(rocprim::inclusive_scan(sc.buf.p, bytes, hincl.p, hpos.p, (size_t)n_short, rocprim::maximum<uint32_t>(), s));
+                GBRS_TRY(running_max(b.sc, hincl.p, hpos.p, n_short, s));
                 hipLaunchKernelGGL(run_cut_kernel, dim3(grid_for(n_short)), dim3(256), 0, s, n_short, FOLD_CAP, hpos.p, head.p);
                 GBRS_HIP_CHECK(hipStreamSynchronize(s));      // hpos goes out of scope
             }
-            GBRS_TRY(inclusive_scan(sc, head.p, hincl.p, n_short, s));
-            GBRS_HIP_CHECK(hipMemcpyAsync(&m32, hincl.p + n_short - 1, 4, hipMemcpyDeviceToHost, s));
-            GBRS_HIP_CHECK(hipStreamSynchronize(s));
+            GBRS_TRY(scan_heads(b.sc, head.p, hincl.p, n_short, m32, s));
             if (!fold) break;
-            folded_two = 0;
+            unsigned long long folded_two = 0;
             if (fold_mode == 3) {
                 if (!two_total.p) GBRS_TRY(two_total.alloc(1));
                 GBRS_HIP_CHECK(hipMemsetAsync(two_total.p, 0, 8, s));
-                hipLaunchKernelGGL(folded_two_kernel, dim3(grid_for(n_short)), dim3(256), 0, s, n_short, head.p, srow.p, rowstart.p,
+                hipLaunchKernelGGL(folded_two_kernel, dim3(grid_for(n_short)), dim3(256), 0, s, n_short, head.p, srow, rowstart,
                                    two_total.p);
                 GBRS_HIP_CHECK(hipMemcpyAsync(&folded_two, two_total.p, 8, hipMemcpyDeviceToHost, s));
                 GBRS_HIP_CHECK(hipStreamSynchronize(s));
             }
-            // Worth it?  The fold pays by the words it takes away - one for a one-word read, two for a two-word read - and a
-            // launch still wants a tile of TILE_WORDS words for every resident workgroup place of the chip (the places of the
-            // tile-size rule in step 7): a sample smaller than that is launch-bound and keeps one word per read (both folds are
-            // tried first, then the one-word fold alone).  GBRS_TUNING_RUN_WORDS=2 / 1 / 0 forces the choice.
-            const uint64_t words_in = out.n_pairs - hf.long_pairs, folded_rows = n_short - m32, folded = folded_rows + folded_two,
-                           words_left = words_in - folded;
-            int dev = 0, n_cu = 0;
-            GBRS_HIP_CHECK(hipGetDevice(&dev));
-            GBRS_HIP_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-            const uint64_t places = (uint64_t)TILE_ROUNDS_MIN * 3u * (uint64_t)std::max(n_cu, 1);
-            bool take = folded * 100 >= words_in * 15 && words_left * side_by_side / places >= (uint64_t)TILE_WORDS;
-            if (fold_env) take = true;             // (0 was handled above)
-            if (take) { out.n_folded = folded_rows - folded_two; out.n_folded_two = folded_two; break; }
+            const uint64_t words_in = out.n_pairs - b.hf.long_pairs, folded_rows = n_short - m32;
+            if (em_take_fold(plan, words_in, folded_rows + folded_two)) { out.n_folded = folded_rows - folded_two; out.n_folded_two = folded_two; break; }
             if (fold_mode == 3) fold_mode = 2;     // the flags again: the one-word fold alone,
             else fold = false;                     // then one row per read
         }
-        M = m32;
-        GBRS_TRY(hrow.alloc(M));
+        lr.M = m32;
+        GBRS_TRY(lr.hrow.alloc(lr.M));
         if (fold) {
-            GBRS_TRY(repeat.alloc(M));
-            GBRS_HIP_CHECK(hipMemsetAsync(repeat.p, 0, repeat.bytes(), s));
+            GBRS_TRY(lr.repeat.alloc(lr.M));
+            GBRS_HIP_CHECK(hipMemsetAsync(lr.repeat.p, 0, lr.repeat.bytes(), s));
         }
         if (out.weighted) {
-            GBRS_TRY(out.row_weight.alloc(M));
+            GBRS_TRY(out.row_weight.alloc(lr.M));
             GBRS_HIP_CHECK(hipMemsetAsync(out.row_weight.p, 0, out.row_weight.bytes(), s));
         }
-        hipLaunchKernelGGL(merged_rows_kernel, dim3(grid_for(n_short)), dim3(256), 0, s, n_short, head.p, hincl.p, srow.p,
-                           row_orig.p, count, hrow.p, out.weighted ? out.row_weight.p : nullptr,
-                           fold ? repeat.p : (uint32_t *)nullptr);
-        GBRS_HIP_CHECK(hipStreamSynchronize(s));
-        head.release(); hincl.release();
-    }
-    skey.release();
-    out.n_rows = M;
-    out.all_one_word = false;
-    stg.mark("5 merge");
-    // 6. long rows keep their pair form
-    if (n_long) {
-        DevBuf<uint64_t> llen;
-        GBRS_TRY(llen.alloc(n_long));
-        GBRS_TRY(out.long_ptr.alloc(n_long + 1));
-        GBRS_TRY(out.long_weight.alloc(n_long));
-        if (keep_row_ids) GBRS_TRY(out.long_row.alloc(n_long));
-        hipLaunchKernelGGL(long_rows_kernel, dim3(grid_for(n_long)), dim3(256), 0, s, n_long, n_short, srow.p, rowstart.p,
-                           row_orig.p, count, llen.p, out.long_weight.p, keep_row_ids ? out.long_row.p : (uint32_t *)nullptr);
-        GBRS_TRY(exclusive_scan(sc, llen.p, out.long_ptr.p, n_long, s));
-        uint64_t tot = 0;
-        GBRS_TRY(fetch_last_plus(out.long_ptr.p, llen.p, n_long, tot, s));
-        GBRS_HIP_CHECK(hipMemcpyAsync(out.long_ptr.p + n_long, &tot, 8, hipMemcpyHostToDevice, s));
-        GBRS_TRY(out.long_loc.alloc(tot));
-        GBRS_TRY(out.long_mask.alloc(tot));
-        hipLaunchKernelGGL(long_copy_kernel, dim3((unsigned)n_long), dim3(64), 0, s, n_long, n_short, srow.p, rowstart.p,
-                           ploc.p, pmask.p, out.long_ptr.p, out.long_loc.p, out.long_mask.p);
-        GBRS_TRY(out.acc_extra.alloc((size_t)L_in * H));
+        hipLaunchKernelGGL(merged_rows_kernel, dim3(grid_for(n_short)), dim3(256), 0, s, n_short, head.p, hincl.p, srow,
+                           rp.row_orig.p, count, lr.hrow.p, out.weighted ? out.row_weight.p : nullptr,
+                           fold ? lr.repeat.p : (uint32_t *)nullptr);
         GBRS_HIP_CHECK(hipStreamSynchronize(s));
     }
-    srow.release();
-    if (!keep_row_ids) row_orig.release();      // (a resampling handle's words remember their file rows: emit_words_kernel)
-    if (M == 0) { GBRS_HIP_CHECK(hipStreamSynchronize(s)); return GBRS_OK; }
-    stg.mark("6 long rows");
-    // 7. tiles
-    DevBuf<uint32_t> npm, dnew, wordoff, dincl, tflag, tincl;
-    GBRS_TRY(npm.alloc(M)); GBRS_TRY(dnew.alloc(M)); GBRS_TRY(wordoff.alloc(M)); GBRS_TRY(dincl.alloc(M));
-    GBRS_TRY(tflag.alloc(M)); GBRS_TRY(tincl.alloc(M));
-    hipLaunchKernelGGL(row_len_kernel, dim3(grid_for(M)), dim3(256), 0, s, M, hrow.p, rowstart.p, ploc.p, npm.p, dnew.p);
-    GBRS_TRY(exclusive_scan(sc, npm.p, wordoff.p, M, s));
-    GBRS_TRY(inclusive_scan(sc, dnew.p, dincl.p, M, s));
-    // tile size: as large as still leaves TILE_ROUNDS_MIN rounds of the chip's resident E-step workgroups (3 or 2 per CU),
-    // between TILE_WORDS and TILE_WORDS_MAX (em_layout.h); GBRS_TUNING_TILE_WORDS overrides
-    uint32_t tile_words = TILE_WORDS;
-    {
-        uint32_t total_words = 0;
-        GBRS_TRY(fetch_last_plus(wordoff.p, npm.p, M, total_words, s));
-        out.all_one_word = total_words == M && n_long == 0;
-        int dev = 0, n_cu = 0;
-        GBRS_HIP_CHECK(hipGetDevice(&dev));
-        GBRS_HIP_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-        // (handles that run side by side - the locus ranges of one sample, GBRS_EM_SIDE_BY_SIDE - fill the rounds together)
-        const unsigned per_cu = (out.weighted || H > 8) ? 2u : 3u;      // resident E-step workgroups per CU (tile_estep_kernel's launch bounds)
-        const uint64_t fit = (uint64_t)total_words * side_by_side / ((uint64_t)TILE_ROUNDS_MIN * per_cu * (uint64_t)std::max(n_cu, 1));
-        // (weighted rows - merged reads, EC counts - stay at 16,320: the merged C2 sample reads 0.0345 ms there, 0.0357 at 20,900)
-        const uint64_t cap = out.weighted ? std::min<uint64_t>(TILE_WORDS_MAX, 16320) : (uint64_t)TILE_WORDS_MAX;
-        tile_words = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(fit, TILE_WORDS), cap) & ~63u;
-        if (const char *env = std::getenv("GBRS_TUNING_TILE_WORDS"); env && std::atoi(env) >= 64)
-            tile_words = (uint32_t)std::min(std::atoi(env), GBRS_TILE_CAP - 64);
-    }
-    hipLaunchKernelGGL(tile_flag_kernel, dim3(grid_for(M)), dim3(256), 0, s, M, tile_words, dseg, npm.p,
-                       wordoff.p, dincl.p, tflag.p);
-    GBRS_TRY(inclusive_scan(sc, tflag.p, tincl.p, M, s));
-    uint32_t T32 = 0;
-    GBRS_HIP_CHECK(hipMemcpyAsync(&T32, tincl.p + M - 1, 4, hipMemcpyDeviceToHost, s));
+    rows.skey.release();
+    lr.fold = fold;
+    out.n_rows = lr.M;
+    return GBRS_OK;
+}
+
+// 6. long rows keep their pair form
+int long_rows(Build &b, TileLayout &out, const RowPairs &rp, const SortedRows &rows, const double *count, bool keep_row_ids,
+              const EmPlan &plan) {
+    hipStream_t s = b.s;
+    const uint64_t n_long = rows.n_long, n_short = rows.n_short;
+    DevBuf<uint64_t> llen;
+    GBRS_TRY(llen.alloc(n_long));
+    GBRS_TRY(out.long_ptr.alloc(n_long + 1));
+    GBRS_TRY(out.long_weight.alloc(n_long));
+    if (keep_row_ids) GBRS_TRY(out.long_row.alloc(n_long));
+    hipLaunchKernelGGL(long_rows_kernel, dim3(grid_for(n_long)), dim3(256), 0, s, n_long, n_short, rows.srow.p, rp.rowstart.p,
+                       rp.row_orig.p, count, llen.p, out.long_weight.p, keep_row_ids ? out.long_row.p : (uint32_t *)nullptr);
+    uint64_t tot = 0;
+    GBRS_TRY(scan_total(b.sc, llen.p, out.long_ptr.p, n_long, tot, s, true));
+    GBRS_TRY(out.long_loc.alloc(tot)); GBRS_TRY(out.long_mask.alloc(tot));
+    hipLaunchKernelGGL(long_copy_kernel, dim3((unsigned)n_long), dim3(64), 0, s, n_long, n_short, rows.srow.p, rp.rowstart.p,
+                       rp.ploc.p, rp.pmask.p, out.long_ptr.p, out.long_loc.p, out.long_mask.p);
+    GBRS_TRY(out.acc_extra.alloc((size_t)plan.tL * plan.tH));
     GBRS_HIP_CHECK(hipStreamSynchronize(s));
-    const uint64_t T = T32;
-    out.n_tiles = T;
+    return GBRS_OK;
+}
+
+// the layout's rows cut into T tiles: npm[i] words of row i from word wordoff[i] on, in tile tincl[i] - 1; rows
+// tile_row[t] .. tile_row[t + 1] are tile t's
+struct Tiles {
+    DevBuf<uint32_t> npm, dnew, wordoff, tflag, tincl, tile_row;     // (dnew and tflag: steps 7 and 7b only)
+    uint64_t T = 0;
+    void release() { tincl.release(); npm.release(); wordoff.release(); tile_row.release(); }
+};
+
+// 7. tiles
+int cut_tiles(Build &b, TileLayout &out, const RowPairs &rp, const LayoutRows &lr, Tiles &t, const EmPlan &plan) {
+    hipStream_t s = b.s;
+    const uint64_t M = lr.M;
+    DevBuf<uint32_t> dincl;
+    GBRS_TRY(t.npm.alloc(M)); GBRS_TRY(t.dnew.alloc(M)); GBRS_TRY(t.wordoff.alloc(M)); GBRS_TRY(dincl.alloc(M));
+    GBRS_TRY(t.tflag.alloc(M)); GBRS_TRY(t.tincl.alloc(M));
+    hipLaunchKernelGGL(row_len_kernel, dim3(grid_for(M)), dim3(256), 0, s, M, lr.hrow.p, rp.rowstart.p, rp.ploc.p, t.npm.p, t.dnew.p);
+    GBRS_TRY(exclusive_scan(b.sc, t.npm.p, t.wordoff.p, M, s));
+    GBRS_TRY(inclusive_scan(b.sc, t.dnew.p, dincl.p, M, s));
+    uint32_t total_words = 0;
+    GBRS_TRY(fetch_last_plus(t.wordoff.p, t.npm.p, M, total_words, s));
+    out.all_one_word = total_words == M && out.n_long == 0;
+    hipLaunchKernelGGL(tile_flag_kernel, dim3(grid_for(M)), dim3(256), 0, s, M, em_tile_words(plan, total_words), plan.dseg, t.npm.p,
+                       t.wordoff.p, dincl.p, t.tflag.p);
+    uint32_t T32 = 0;
+    GBRS_TRY(scan_heads(b.sc, t.tflag.p, t.tincl.p, M, T32, s));
+    t.T = T32;
+    out.n_tiles = t.T;
     dincl.release();
-    DevBuf<uint32_t> tile_row;
-    GBRS_TRY(tile_row.alloc(T + 1));
-    hipLaunchKernelGGL(tile_start_kernel, dim3(grid_for(M)), dim3(256), 0, s, M, T, tflag.p, tincl.p, tile_row.p);
-    stg.mark("7 tiles");
-    // 7b. interleave the locus lists inside each tile (tile membership and sizes are unchanged)
-    if (interleave || streams) {
-        DevBuf<uint32_t> gflag, gpos, gstart, gord, ident, perm, hrow2, npm2, repeat2;
-        DevBuf<uint64_t> ikey, ikey2;
-        DevBuf<double> weight2;
-        if (interleave) {
-            GBRS_TRY(gflag.alloc(M)); GBRS_TRY(gpos.alloc(M)); GBRS_TRY(gstart.alloc(M)); GBRS_TRY(gord.alloc(M));
-            hipLaunchKernelGGL(group_flag_kernel, dim3(grid_for(M)), dim3(256), 0, s, M, dnew.p, tflag.p, gflag.p, gpos.p);
-            {
-                size_t bytes = 0;
-                GBRS_PRIM(rocprim::inclusive_scan(nullptr, bytes, gpos.p, gstart.p, (size_t)M, rocprim::maximum<uint32_t>(), s));
-                GBRS_TRY(sc.reserve(bytes));
-                GBRS_PRIM(rocprim::inclusive_scan(sc.buf.p, bytes, gpos.p, gstart.p, (size_t)M, rocprim::maximum<uint32_t>(), s));
-            }
-            GBRS_TRY(inclusive_scan(sc, gflag.p, gord.p, M, s));
-            GBRS_HIP_CHECK(hipStreamSynchronize(s));
-            gflag.release(); gpos.release();
-        }
-        GBRS_TRY(ikey.alloc(M)); GBRS_TRY(ikey2.alloc(M)); GBRS_TRY(ident.alloc(M)); GBRS_TRY(perm.alloc(M));
-        stg.mark("7b-a alloc");
-        if (interleave)
-            hipLaunchKernelGGL(interleave_key_kernel, dim3(grid_for(M)), dim3(256), 0, s, M, tincl.p, gstart.p, gord.p,
-                               ikey.p, ident.p);
-        else
-            hipLaunchKernelGGL(stream_key_kernel, dim3(grid_for(M)), dim3(256), 0, s, M, tincl.p, npm.p, ikey.p, ident.p);
-        stg.mark("7b-b keys");
-        GBRS_TRY(sort_pairs<uint64_t>(sc, ikey.p, ikey2.p, ident.p, perm.p, M, 40 + bits_for(T), s));
+    GBRS_TRY(t.tile_row.alloc(t.T + 1));
+    hipLaunchKernelGGL(tile_start_kernel, dim3(grid_for(M)), dim3(256), 0, s, M, t.T, t.tflag.p, t.tincl.p, t.tile_row.p);
+    return GBRS_OK;
+}
+
+// 7b. interleave the locus lists inside each tile, or lay the tile's rows out as streams (tile membership and sizes are
+// unchanged)
+int order_rows_in_tiles(Build &b, TileLayout &out, LayoutRows &lr, Tiles &t, bool interleave) {
+    hipStream_t s = b.s;
+    Scratch &sc = b.sc;
+    const uint64_t M = lr.M;
+    const bool fold = lr.fold;
+    DevBuf<uint32_t> gflag, gpos, gstart, gord, ident, perm, hrow2, npm2, repeat2;
+    DevBuf<uint64_t> ikey, ikey2;
+    DevBuf<double> weight2;
+    if (interleave) {
+        GBRS_TRY(gflag.alloc(M)); GBRS_TRY(gpos.alloc(M)); GBRS_TRY(gstart.alloc(M)); GBRS_TRY(gord.alloc(M));
+        hipLaunchKernelGGL(group_flag_kernel, dim3(grid_for(M)), dim3(256), 0, s, M, t.dnew.p, t.tflag.p, gflag.p, gpos.p);
+        GBRS_TRY(running_max(sc, gpos.p, gstart.p, M, s));
+        GBRS_TRY(inclusive_scan(sc, gflag.p, gord.p, M, s));
         GBRS_HIP_CHECK(hipStreamSynchronize(s));
-        stg.mark("7b-c sort");
-        ikey.release(); ikey2.release(); ident.release(); gstart.release(); gord.release();
-        stg.mark("7b-d release");
-        GBRS_TRY(hrow2.alloc(M)); GBRS_TRY(npm2.alloc(M));
-        if (out.weighted) GBRS_TRY(weight2.alloc(M));
-        if (fold) GBRS_TRY(repeat2.alloc(M));
-        hipLaunchKernelGGL(permute_rows_kernel, dim3(grid_for(M)), dim3(256), 0, s, M, perm.p, hrow.p, npm.p,
-                           out.weighted ? out.row_weight.p : (const double *)nullptr, fold ? repeat.p : (const uint32_t *)nullptr,
-                           hrow2.p, npm2.p, out.weighted ? weight2.p : (double *)nullptr, fold ? repeat2.p : (uint32_t *)nullptr);
-        if (fold) GBRS_HIP_CHECK(hipMemcpyAsync(repeat.p, repeat2.p, M * 4, hipMemcpyDeviceToDevice, s));
-        GBRS_HIP_CHECK(hipMemcpyAsync(hrow.p, hrow2.p, M * 4, hipMemcpyDeviceToDevice, s));
-        GBRS_HIP_CHECK(hipMemcpyAsync(npm.p, npm2.p, M * 4, hipMemcpyDeviceToDevice, s));
-        if (out.weighted)
-            GBRS_HIP_CHECK(hipMemcpyAsync(out.row_weight.p, weight2.p, M * 8, hipMemcpyDeviceToDevice, s));
-        GBRS_TRY(exclusive_scan(sc, npm.p, wordoff.p, M, s));
-        GBRS_HIP_CHECK(hipStreamSynchronize(s));
+        gflag.release(); gpos.release();
     }
-    dnew.release();
-    tflag.release();
-    stg.mark("7b row order");
-    // 8. padding so that no row straddles a batch, batch offsets
-    DevBuf<uint32_t> rowpad, nbatch, n_one, n_two, batch_base;
-    GBRS_TRY(rowpad.alloc(M)); GBRS_TRY(nbatch.alloc(T)); GBRS_TRY(n_one.alloc(T)); GBRS_TRY(n_two.alloc(T)); GBRS_TRY(batch_base.alloc(T));
-    hipLaunchKernelGGL(tile_pad_kernel, dim3(grid_for(T, 64)), dim3(64), 0, s, T, streams ? 1 : 0, tile_row.p, npm.p, rowpad.p,
-                       nbatch.p, n_one.p, n_two.p);
+    GBRS_TRY(ikey.alloc(M)); GBRS_TRY(ikey2.alloc(M)); GBRS_TRY(ident.alloc(M)); GBRS_TRY(perm.alloc(M));
+    b.mark("7b-a alloc");
+    if (interleave)
+        hipLaunchKernelGGL(interleave_key_kernel, dim3(grid_for(M)), dim3(256), 0, s, M, t.tincl.p, gstart.p, gord.p, ikey.p, ident.p);
+    else
+        hipLaunchKernelGGL(stream_key_kernel, dim3(grid_for(M)), dim3(256), 0, s, M, t.tincl.p, t.npm.p, ikey.p, ident.p);
+    b.mark("7b-b keys");
+    GBRS_TRY(sort_pairs<uint64_t>(sc, ikey.p, ikey2.p, ident.p, perm.p, M, 40 + bits_for(t.T), s));
+    GBRS_HIP_CHECK(hipStreamSynchronize(s));
+    b.mark("7b-c sort");
+    ikey.release(); ikey2.release(); ident.release(); gstart.release(); gord.release();
+    b.mark("7b-d release");
+    GBRS_TRY(hrow2.alloc(M)); GBRS_TRY(npm2.alloc(M));
+    if (out.weighted) GBRS_TRY(weight2.alloc(M));
+    if (fold) GBRS_TRY(repeat2.alloc(M));
+    hipLaunchKernelGGL(permute_rows_kernel, dim3(grid_for(M)), dim3(256), 0, s, M, perm.p, lr.hrow.p, t.npm.p,
+                       out.weighted ? out.row_weight.p : (const double *)nullptr, fold ? lr.repeat.p : (const uint32_t *)nullptr,
+                       hrow2.p, npm2.p, out.weighted ? weight2.p : (double *)nullptr, fold ? repeat2.p : (uint32_t *)nullptr);
+    if (fold) GBRS_HIP_CHECK(hipMemcpyAsync(lr.repeat.p, repeat2.p, M * 4, hipMemcpyDeviceToDevice, s));
+    GBRS_HIP_CHECK(hipMemcpyAsync(lr.hrow.p, hrow2.p, M * 4, hipMemcpyDeviceToDevice, s));
+    GBRS_HIP_CHECK(hipMemcpyAsync(t.npm.p, npm2.p, M * 4, hipMemcpyDeviceToDevice, s));
+    if (out.weighted)
+        GBRS_HIP_CHECK(hipMemcpyAsync(out.row_weight.p, weight2.p, M * 8, hipMemcpyDeviceToDevice, s));
+    GBRS_TRY(exclusive_scan(sc, t.npm.p, t.wordoff.p, M, s));
+    GBRS_HIP_CHECK(hipStreamSynchronize(s));
+    return GBRS_OK;
+}
+
+// per row its padding, per tile its batches and where its dictionary starts
+struct TileParts {
+    DevBuf<uint32_t> rowpad, nbatch, n_one, n_two, batch_base, dict_base;
+    uint32_t NB = 0, NS = 0;     // batches and dictionary entries (slots) of the layout
+    void release() { dict_base.release(); batch_base.release(); nbatch.release(); n_one.release(); n_two.release(); rowpad.release(); }
+};
+
+// 8. padding so that no row straddles a batch, batch offsets
+int pad_rows(Build &b, TileLayout &out, const Tiles &t, TileParts &tp, uint64_t M, const EmPlan &plan) {
+    hipStream_t s = b.s;
+    const uint64_t T = t.T;
+    GBRS_TRY(tp.rowpad.alloc(M)); GBRS_TRY(tp.nbatch.alloc(T)); GBRS_TRY(tp.n_one.alloc(T)); GBRS_TRY(tp.n_two.alloc(T));
+    GBRS_TRY(tp.batch_base.alloc(T));
+    hipLaunchKernelGGL(tile_pad_kernel, dim3(grid_for(T, 64)), dim3(64), 0, s, T, plan.row_order == 2 ? 1 : 0, t.tile_row.p, t.npm.p,
+                       tp.rowpad.p, tp.nbatch.p, tp.n_one.p, tp.n_two.p);
     // (the weighted kernels do not split their batch loop: their headers say nothing about the leading batches)
-    if (out.weighted) GBRS_HIP_CHECK(hipMemsetAsync(n_one.p, 0, T * 4, s));
-    if (!counted_pairs) GBRS_HIP_CHECK(hipMemsetAsync(n_two.p, 0, T * 4, s));
-    GBRS_TRY(exclusive_scan(sc, nbatch.p, batch_base.p, T, s));
-    uint32_t NB = 0;
-    GBRS_TRY(fetch_last_plus(batch_base.p, nbatch.p, T, NB, s));
-    out.n_batches = NB;
-    stg.mark("8 padding");
-    // 9. per-tile dictionaries: one sort of (tile, id) keys over all the pairs (see tile_pair_keys_kernel)
-    const uint32_t dcap = out.d_max;
-    uint32_t NS = 0;
-    DevBuf<uint32_t> dict_base;
-    GBRS_TRY(dict_base.alloc(T));
-    {
-        uint32_t W = 0;
-        GBRS_TRY(fetch_last_plus(wordoff.p, npm.p, M, W, s));
-        DevBuf<uint64_t> dkey, dkey2;
-        DevBuf<uint32_t> dflag, dpos;
-        GBRS_TRY(dkey.alloc(W)); GBRS_TRY(dkey2.alloc(W)); GBRS_TRY(dflag.alloc(W)); GBRS_TRY(dpos.alloc(W));
-        hipLaunchKernelGGL(tile_pair_keys_kernel, dim3(grid_for(M)), dim3(256), 0, s, M, tincl.p, hrow.p, rowstart.p, ploc.p,
-                           wordoff.p, dkey.p);
-        GBRS_TRY(sort_keys64(sc, dkey.p, dkey2.p, W, 32 + bits_for(T), s));
-        hipLaunchKernelGGL(dict_flag_kernel, dim3(grid_for(W)), dim3(256), 0, s, (uint64_t)W, dkey2.p, dflag.p);
-        GBRS_TRY(exclusive_scan(sc, dflag.p, dpos.p, W, s));
-        GBRS_TRY(fetch_last_plus(dpos.p, dflag.p, W, NS, s));
-        out.n_slots = NS;
-        GBRS_TRY(out.tiles.alloc(T));
-        GBRS_TRY(out.dict.alloc(std::max<uint32_t>(NS, 1)));
-        hipLaunchKernelGGL(dict_emit_kernel, dim3(grid_for(W)), dim3(256), 0, s, (uint64_t)W, dkey2.p, dflag.p, dpos.p, out.dict.p,
-                           dict_base.p);
-        hipLaunchKernelGGL(tile_hdr_kernel, dim3(grid_for(T)), dim3(256), 0, s, T, dcap, NS, batch_base.p, nbatch.p, n_one.p, n_two.p,
-                           dict_base.p, out.tiles.p, d_flags.p);
-        GBRS_TRY(read_flags());
-        if (hf.dict_overflow) return fail(GBRS_ERR_INVALID, "internal error: a tile dictionary overflowed its capacity");
-    }
-    stg.mark("9 dictionaries");
-    // 10. words
-    GBRS_TRY(out.words.alloc((size_t)NB * 64));
+    if (out.weighted) GBRS_HIP_CHECK(hipMemsetAsync(tp.n_one.p, 0, T * 4, s));
+    if (!plan.counted_pairs) GBRS_HIP_CHECK(hipMemsetAsync(tp.n_two.p, 0, T * 4, s));
+    GBRS_TRY(scan_total(b.sc, tp.nbatch.p, tp.batch_base.p, T, tp.NB, s));
+    out.n_batches = tp.NB;
+    return GBRS_OK;
+}
+
+// 9. per-tile dictionaries: one sort of (tile, id) keys over all the pairs (see tile_pair_keys_kernel)
+int tile_dictionaries(Build &b, TileLayout &out, const RowPairs &rp, const LayoutRows &lr, const Tiles &t, TileParts &tp) {
+    hipStream_t s = b.s;
+    const uint64_t M = lr.M, T = t.T;
+    GBRS_TRY(tp.dict_base.alloc(T));
+    uint32_t W = 0;
+    GBRS_TRY(fetch_last_plus(t.wordoff.p, t.npm.p, M, W, s));
+    DevBuf<uint64_t> dkey, dkey2;
+    DevBuf<uint32_t> dflag, dpos;
+    GBRS_TRY(dkey.alloc(W)); GBRS_TRY(dkey2.alloc(W)); GBRS_TRY(dflag.alloc(W)); GBRS_TRY(dpos.alloc(W));
+    hipLaunchKernelGGL(tile_pair_keys_kernel, dim3(grid_for(M)), dim3(256), 0, s, M, t.tincl.p, lr.hrow.p, rp.rowstart.p, rp.ploc.p,
+                       t.wordoff.p, dkey.p);
+    GBRS_TRY(sort_keys64(b.sc, dkey.p, dkey2.p, W, 32 + bits_for(T), s));
+    hipLaunchKernelGGL(dict_flag_kernel, dim3(grid_for(W)), dim3(256), 0, s, (uint64_t)W, dkey2.p, dflag.p);
+    GBRS_TRY(scan_total(b.sc, dflag.p, dpos.p, W, tp.NS, s));
+    out.n_slots = tp.NS;
+    GBRS_TRY(out.tiles.alloc(T));
+    GBRS_TRY(out.dict.alloc(std::max<uint32_t>(tp.NS, 1)));
+    hipLaunchKernelGGL(dict_emit_kernel, dim3(grid_for(W)), dim3(256), 0, s, (uint64_t)W, dkey2.p, dflag.p, dpos.p, out.dict.p,
+                       tp.dict_base.p);
+    hipLaunchKernelGGL(tile_hdr_kernel, dim3(grid_for(T)), dim3(256), 0, s, T, out.d_max, tp.NS, tp.batch_base.p, tp.nbatch.p,
+                       tp.n_one.p, tp.n_two.p, tp.dict_base.p, out.tiles.p, b.d_flags.p);
+    GBRS_TRY(b.read_flags());
+    if (b.hf.dict_overflow) return fail(GBRS_ERR_INVALID, "internal error: a tile dictionary overflowed its capacity");
+    return GBRS_OK;
+}
+
+// 10. words
+int emit_words(Build &b, TileLayout &out, const RowPairs &rp, const LayoutRows &lr, const Tiles &t, const TileParts &tp,
+               bool keep_row_ids, const EmPlan &plan) {
+    hipStream_t s = b.s;
+    const uint64_t M = lr.M, T = t.T;
+    GBRS_TRY(out.words.alloc((size_t)tp.NB * 64));
     GBRS_HIP_CHECK(hipMemsetAsync(out.words.p, 0, out.words.bytes(), s));
     if (out.weighted) {
-        GBRS_TRY(out.word_weight.alloc((size_t)NB * 64));
+        GBRS_TRY(out.word_weight.alloc((size_t)tp.NB * 64));
         GBRS_HIP_CHECK(hipMemsetAsync(out.word_weight.p, 0, out.word_weight.bytes(), s));
     }
     if (keep_row_ids) {
-        GBRS_TRY(out.word_row.alloc((size_t)NB * 64));
+        GBRS_TRY(out.word_row.alloc((size_t)tp.NB * 64));
         GBRS_HIP_CHECK(hipMemsetAsync(out.word_row.p, 0xFF, out.word_row.bytes(), s));      // padding cells: no row
     }
-    hipLaunchKernelGGL(emit_words_kernel, dim3(grid_for(M)), dim3(256), 0, s, M, H, tincl.p, out.tiles.p, out.dict.p,
-                       hrow.p, rowstart.p, ploc.p, pmask.p, rowpad.p, out.words.p,
+    hipLaunchKernelGGL(emit_words_kernel, dim3(grid_for(M)), dim3(256), 0, s, M, plan.tH, t.tincl.p, out.tiles.p, out.dict.p,
+                       lr.hrow.p, rp.rowstart.p, rp.ploc.p, rp.pmask.p, tp.rowpad.p, out.words.p,
                        out.weighted ? out.row_weight.p : (const double *)nullptr,
                        out.weighted ? out.word_weight.p : (double *)nullptr,
-                       keep_row_ids ? row_orig.p : (const uint32_t *)nullptr, keep_row_ids ? out.word_row.p : (uint32_t *)nullptr,
-                       fold ? repeat.p : (const uint32_t *)nullptr);
-    if (streams && !out.weighted)
-        hipLaunchKernelGGL(fill_one_word_cells_kernel, dim3(grid_for(T * 64)), dim3(256), 0, s, T, H, out.tiles.p, out.words.p);
+                       keep_row_ids ? rp.row_orig.p : (const uint32_t *)nullptr, keep_row_ids ? out.word_row.p : (uint32_t *)nullptr,
+                       lr.fold ? lr.repeat.p : (const uint32_t *)nullptr);
+    if (plan.row_order == 2 && !out.weighted)
+        hipLaunchKernelGGL(fill_one_word_cells_kernel, dim3(grid_for(T * 64)), dim3(256), 0, s, T, plan.tH, out.tiles.p, out.words.p);
     GBRS_HIP_CHECK(hipStreamSynchronize(s));
-    dict_base.release(); batch_base.release(); nbatch.release(); n_one.release(); n_two.release();
-    rowpad.release(); tincl.release(); npm.release(); wordoff.release(); tile_row.release();
-    hrow.release(); rowstart.release(); ploc.release(); pmask.release(); row_orig.release(); repeat.release();
-    out.row_weight.release();
-    // Launch order of the tiles: the ones with the most batches first, so that the launch's last round - when most
-    // of the chip has run out of tiles - is made of the short ones (tiles that end at the dictionary limit have
-    // fewer words; C2: E-step 0.0998-0.1008 -> 0.0960-0.0962 ms).  Nothing but the E-step reads the header array by
-    // position.  GBRS_TUNING_TILE_ORDER=0 keeps the locus order.
-    const char *order_env = std::getenv("GBRS_TUNING_TILE_ORDER");
-    if (!(order_env && std::atoi(order_env) == 0) && T > 1) {
-        std::vector<TileHdr> hdr(T);
-        GBRS_HIP_CHECK(hipMemcpy(hdr.data(), out.tiles.p, T * sizeof(TileHdr), hipMemcpyDeviceToHost));
-        std::stable_sort(hdr.begin(), hdr.end(), [](const TileHdr &a, const TileHdr &b) { return a.n_batches > b.n_batches; });
-        GBRS_HIP_CHECK(hipMemcpy(out.tiles.p, hdr.data(), T * sizeof(TileHdr), hipMemcpyHostToDevice));
-    }
-    stg.mark("10 words");
-    // 11. inverted index locus -> destination rows.  A slot (tile, dictionary entry) of a locus delivers one row of sums
-    // to that locus; the slot of a locus set delivers the same row to every member locus.  The rows are numbered by
-    // locus (ascending slot inside a locus: the radix sort is stable), so that the rows of a locus are consecutive in
-    // `partials` and the gather streams them without an indirection.
+    return GBRS_OK;
+}
+
+// Launch order of the tiles: the ones with the most batches first, so that the launch's last round - when most
+// of the chip has run out of tiles - is made of the short ones (tiles that end at the dictionary limit have
+// fewer words; C2: E-step 0.0998-0.1008 -> 0.0960-0.0962 ms).  Nothing but the E-step reads the header array by
+// position.  GBRS_TUNING_TILE_ORDER=0 keeps the locus order.
+int reorder_tiles(TileLayout &out, uint64_t T) {
+    std::vector<TileHdr> hdr(T);
+    GBRS_HIP_CHECK(hipMemcpy(hdr.data(), out.tiles.p, T * sizeof(TileHdr), hipMemcpyDeviceToHost));
+    std::stable_sort(hdr.begin(), hdr.end(), [](const TileHdr &a, const TileHdr &b) { return a.n_batches > b.n_batches; });
+    GBRS_HIP_CHECK(hipMemcpy(out.tiles.p, hdr.data(), T * sizeof(TileHdr), hipMemcpyHostToDevice));
+    return GBRS_OK;
+}
+
+// 11. inverted index locus -> destination rows.  A slot (tile, dictionary entry) of a locus delivers one row of sums
+// to that locus; the slot of a locus set delivers the same row to every member locus.  The rows are numbered by
+// locus (ascending slot inside a locus: the radix sort is stable), so that the rows of a locus are consecutive in
+// `partials` and the gather streams them without an indirection.
+int inverted_index(Build &b, TileLayout &out, uint32_t NS, uint32_t L_in, uint32_t H) {
+    hipStream_t s = b.s;
     GBRS_TRY(out.slot_dest.alloc(std::max<uint32_t>(NS, 1)));
     uint32_t NE = 0, n_rows_real = 0;
     if (NS) {
@@ -1797,8 +1750,7 @@ int build_tile_layout(TileLayout &out, uint64_t R, uint32_t L_in, uint32_t H, ui
         GBRS_TRY(ecnt.alloc(NS)); GBRS_TRY(eoff.alloc(NS));
         hipLaunchKernelGGL(dest_count_kernel, dim3(grid_for(NS)), dim3(256), 0, s, (uint64_t)NS, L_in, out.dict.p,
                            out.n_sets ? out.set_ptr.p : (const uint32_t *)nullptr, ecnt.p);
-        GBRS_TRY(exclusive_scan(sc, ecnt.p, eoff.p, NS, s));
-        GBRS_TRY(fetch_last_plus(eoff.p, ecnt.p, NS, NE, s));
+        GBRS_TRY(scan_total(b.sc, ecnt.p, eoff.p, NS, NE, s));
         // (SLOT_PAIR is the lowest flag bit of a destination: checked here, before anything is sized by NE or indexed with it)
         if (NE >= SLOT_PAIR) return fail(GBRS_ERR_INVALID, "the tiled layout needs fewer than 2^29 destination rows");
         DevBuf<uint32_t> eloc, eidx, sloc;
@@ -1809,7 +1761,7 @@ int build_tile_layout(TileLayout &out, uint64_t R, uint32_t L_in, uint32_t H, ui
                            out.n_sets ? out.set_ptr.p : (const uint32_t *)nullptr, out.set_members.p, eoff.p, eloc.p, eidx.p,
                            out.slot_dest.p, out.dest_list.p);
         // (the header entry of a set slot carries locus id L_in: behind every real locus, never looked at)
-        GBRS_TRY(sort_pairs<uint32_t>(sc, eloc.p, sloc.p, eidx.p, out.slot_list.p, NE, bits_for(L_in), s));
+        GBRS_TRY(sort_pairs<uint32_t>(b.sc, eloc.p, sloc.p, eidx.p, out.slot_list.p, NE, bits_for(L_in), s));
         hipLaunchKernelGGL(slot_ptr_kernel, dim3(grid_for((uint64_t)L_in + 1)), dim3(256), 0, s, L_in, (uint64_t)NE, sloc.p,
                            out.slot_ptr.p);
         // the rows that receive sums: the entries of real loci (a set slot's header entry sorts behind them)
@@ -1830,42 +1782,126 @@ int build_tile_layout(TileLayout &out, uint64_t R, uint32_t L_in, uint32_t H, ui
         hipLaunchKernelGGL(encode_sets_kernel, dim3(grid_for(NS)), dim3(256), 0, s, (uint64_t)NS, L_in, out.set_ptr.p,
                            out.set_members.p, out.dest_list.p, out.dict.p, out.dict_b.p, out.slot_dest.p, out.dest_b.p);
     }
-    stg.mark("11 inverted index");
-    // 12. loci with many slots get a whole wave in the gather kernel
-    {
-        std::vector<uint32_t> sp((size_t)L_in + 1), heavy, lightv;
-        GBRS_HIP_CHECK(hipMemcpyAsync(sp.data(), out.slot_ptr.p, sp.size() * 4, hipMemcpyDeviceToHost, s));
-        GBRS_HIP_CHECK(hipStreamSynchronize(s));
-        for (uint32_t l = 0; l < L_in; ++l)
-            if (sp[l + 1] - sp[l] > (uint32_t)HEAVY_SLOTS) heavy.push_back(l);
-            else if (sp[l + 1] - sp[l] >= 2) lightv.push_back(l);
-        out.n_heavy = heavy.size();
-        out.n_light = lightv.size();
-        for (int which = 0; which < 2; ++which) {
-            const std::vector<uint32_t> &loci = which == 0 ? heavy : lightv;
-            DevBuf<uint32_t> &dst = which == 0 ? out.heavy_range : out.light_range;
-            std::vector<uint32_t> rng;
-            rng.reserve(loci.size() * 3);
-            for (uint32_t l : loci) {
-                rng.push_back(l);
-                rng.push_back(sp[l]);
-                rng.push_back(sp[l + 1]);
-            }
-            GBRS_TRY(dst.alloc(std::max<size_t>(rng.size(), 3)));
-            if (!rng.empty()) GBRS_HIP_CHECK(hipMemcpyAsync(dst.p, rng.data(), rng.size() * 4, hipMemcpyHostToDevice, s));
-            GBRS_HIP_CHECK(hipStreamSynchronize(s));          // rng goes out of scope
+    return GBRS_OK;
+}
+
+// 12. loci with many slots get a whole wave in the gather kernel
+int heavy_light_lists(TileLayout &out, uint32_t L_in, hipStream_t s) {
+    std::vector<uint32_t> sp((size_t)L_in + 1), heavy, lightv;
+    GBRS_HIP_CHECK(hipMemcpyAsync(sp.data(), out.slot_ptr.p, sp.size() * 4, hipMemcpyDeviceToHost, s));
+    GBRS_HIP_CHECK(hipStreamSynchronize(s));
+    for (uint32_t l = 0; l < L_in; ++l)
+        if (sp[l + 1] - sp[l] > (uint32_t)HEAVY_SLOTS) heavy.push_back(l);
+        else if (sp[l + 1] - sp[l] >= 2) lightv.push_back(l);
+    out.n_heavy = heavy.size();
+    out.n_light = lightv.size();
+    for (int which = 0; which < 2; ++which) {
+        const std::vector<uint32_t> &loci = which == 0 ? heavy : lightv;
+        DevBuf<uint32_t> &dst = which == 0 ? out.heavy_range : out.light_range;
+        std::vector<uint32_t> rng;
+        rng.reserve(loci.size() * 3);
+        for (uint32_t l : loci) {
+            rng.push_back(l);
+            rng.push_back(sp[l]);
+            rng.push_back(sp[l + 1]);
         }
-        GBRS_TRY(out.light_loci.alloc(std::max<size_t>(lightv.size(), 1)));
-        if (!lightv.empty())
-            GBRS_HIP_CHECK(hipMemcpyAsync(out.light_loci.p, lightv.data(), lightv.size() * 4, hipMemcpyHostToDevice, s));
-        GBRS_TRY(out.heavy_loci.alloc(std::max<size_t>(heavy.size(), 1)));
-        if (!heavy.empty())
-            GBRS_HIP_CHECK(hipMemcpyAsync(out.heavy_loci.p, heavy.data(), heavy.size() * 4, hipMemcpyHostToDevice, s));
-        GBRS_HIP_CHECK(hipStreamSynchronize(s));
+        GBRS_TRY(dst.alloc(std::max<size_t>(rng.size(), 3)));
+        if (!rng.empty()) GBRS_HIP_CHECK(hipMemcpyAsync(dst.p, rng.data(), rng.size() * 4, hipMemcpyHostToDevice, s));
+        GBRS_HIP_CHECK(hipStreamSynchronize(s));          // rng goes out of scope
     }
+    GBRS_TRY(out.light_loci.alloc(std::max<size_t>(lightv.size(), 1)));
+    if (!lightv.empty())
+        GBRS_HIP_CHECK(hipMemcpyAsync(out.light_loci.p, lightv.data(), lightv.size() * 4, hipMemcpyHostToDevice, s));
+    GBRS_TRY(out.heavy_loci.alloc(std::max<size_t>(heavy.size(), 1)));
+    if (!heavy.empty())
+        GBRS_HIP_CHECK(hipMemcpyAsync(out.heavy_loci.p, heavy.data(), heavy.size() * 4, hipMemcpyHostToDevice, s));
+    GBRS_HIP_CHECK(hipStreamSynchronize(s));
+    return GBRS_OK;
+}
+
+}  // namespace
+
+int build_tile_layout(TileLayout &out, uint64_t R, uint64_t N, const uint32_t *ent_row, const uint64_t *col_ptr,
+                      const double *count, hipStream_t s, const EmPlan &plan) {
+    const uint32_t L_in = plan.tL, H = plan.tH;
+    out.n_sets = 0;
+    out.n_dest_rows = 0;
+    const bool keep_row_ids = out.keep_row_ids && !plan.merge;      // (a merged row has no single file row)
+    if (H > 16) return fail(GBRS_ERR_INVALID, "the tiled layout packs the haplotype mask in 16 bits (H <= 16)");
+    if (N >= 0xFFFFFFFFull || L_in >= (1u << 27))
+        return fail(GBRS_ERR_INVALID, "the tiled layout needs N < 2^32 entries and L < 2^27 loci per handle");
+    // (common.h) the temporaries are parked while the build runs - a hipMalloc that follows a large hipFree stalls on
+    // some hosts - and go back in one pass when it ends; a one-shot process leaves them to the layout's destructor
+    DeferFrees park_temporaries(out.retain_temporaries ? &out.retired : nullptr, &out.retired_bytes);
+    StageTimer stg("layout");
+    Build b(s, &stg);
+    GBRS_TRY(b.init());
+    out.d_max = plan.d_max;
+    out.deterministic = plan.deterministic;
+    if (!plan.dict_room)
+        return fail(GBRS_ERR_UNSUPPORTED, "the deterministic tile layout has no room for a row's loci at H = %u", H);
+    out.weighted = plan.weighted;
+    out.n_pairs = out.n_rows = out.n_rows_in = out.n_long = out.n_tiles = out.n_batches = out.n_slots = out.n_folded = out.n_folded_two = 0;
+    GBRS_TRY(out.slot_ptr.alloc((size_t)L_in + 1));
+    GBRS_HIP_CHECK(hipMemsetAsync(out.slot_ptr.p, 0, out.slot_ptr.bytes(), s));
+    GBRS_TRY(out.locus_class.alloc(L_in));
+    GBRS_HIP_CHECK(hipMemsetAsync(out.locus_class.p, 0, out.locus_class.bytes(), s));
+    if (N == 0) { GBRS_HIP_CHECK(hipStreamSynchronize(s)); return GBRS_OK; }
+
+    // 1-3. entries -> pairs -> rows
+    RowPairs rp;
+    stg.mark("0 setup");
+    GBRS_TRY(build_row_pairs(b, rp, R, L_in, H, N, ent_row, col_ptr, 5 + bits_for(L_in - 1) /* <= 32: L < 2^27 */, plan.view));
+    out.n_pairs = rp.P;
+    out.n_rows_in = rp.R1;
+    stg.mark("3 rows");
+    // 3b, 3c. locus sets
+    if (plan.whole_row_sets && rp.R1 > 0) {
+        GBRS_TRY(whole_row_sets(b, out, rp, plan));
+        stg.mark("3b locus sets");
+    }
+    if (plan.locus_sets && rp.R1 > 0 && out.n_sets == 0) {
+        if (plan.group_sets) GBRS_TRY(mask_group_sets(b, out, rp, plan));
+        stg.mark("3c mask-group sets");
+    }
+    // 4-6. the rows in their order, merged or folded; the long ones apart
+    SortedRows rows;
+    LayoutRows lr;
+    GBRS_TRY(order_rows(b, out, rp, rows, L_in + out.n_sets, H));
+    stg.mark("4 order rows");
+    GBRS_TRY(merge_rows(b, out, rp, rows, lr, count, plan));
+    out.all_one_word = false;
+    stg.mark("5 merge");
+    if (rows.n_long) GBRS_TRY(long_rows(b, out, rp, rows, count, keep_row_ids, plan));
+    rows.srow.release();
+    if (!keep_row_ids) rp.row_orig.release();      // (a resampling handle's words remember their file rows: emit_words_kernel)
+    if (lr.M == 0) { GBRS_HIP_CHECK(hipStreamSynchronize(s)); return GBRS_OK; }
+    stg.mark("6 long rows");
+    // 7-10. tiles, their row order, batches, dictionaries and words
+    Tiles tiles;
+    TileParts parts;
+    GBRS_TRY(cut_tiles(b, out, rp, lr, tiles, plan));
+    stg.mark("7 tiles");
+    if (plan.row_order != 0) GBRS_TRY(order_rows_in_tiles(b, out, lr, tiles, plan.row_order == 1));
+    tiles.dnew.release();
+    tiles.tflag.release();
+    stg.mark("7b row order");
+    GBRS_TRY(pad_rows(b, out, tiles, parts, lr.M, plan));
+    stg.mark("8 padding");
+    GBRS_TRY(tile_dictionaries(b, out, rp, lr, tiles, parts));
+    stg.mark("9 dictionaries");
+    GBRS_TRY(emit_words(b, out, rp, lr, tiles, parts, keep_row_ids, plan));
+    parts.release(); tiles.release(); lr.release(); rp.release();
+    out.row_weight.release();
+    if (plan.reorder_tiles && tiles.T > 1) GBRS_TRY(reorder_tiles(out, tiles.T));
+    stg.mark("10 words");
+    // 11-12. what the gather reads
+    GBRS_TRY(inverted_index(b, out, parts.NS, L_in, H));
+    stg.mark("11 inverted index");
+    GBRS_TRY(heavy_light_lists(out, L_in, s));
     stg.mark("12 heavy / light lists");
     GBRS_HIP_CHECK(hipGetLastError());
-return GBRS_OK;
+    return GBRS_OK;
 }
 
 }  // namespace gbrs

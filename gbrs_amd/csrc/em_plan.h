@@ -1,0 +1,237 @@
+// What gbrs_em_create* decides before any device work (em.hip) and the rules the tile layout's build applies to the
+// numbers it reads back from the device (em_layout.hip): the GBRS_TUNING_* variables of the EM handle, read from the
+// environment once per create, and the plan a pure function resolves from them and the handle's shape.  This is the one
+// place that reads those variables.  Host only - no HIP include, so a plain C++ compiler builds it
+// (tests/native/em_plan_driver.cpp).
+#pragma once
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdlib>
+
+#include "../../include/gbrs_hip.h"
+
+namespace gbrs {
+
+// ---- tuning: every GBRS_TUNING_* value that create and the layout build read ------------------------------------------
+
+struct EmTuning {
+    struct Int {   // a variable and whether it was set at all
+        bool set = false;
+        int v = 0;
+        bool is(int x) const { return set && v == x; }
+        bool nonzero() const { return set && v != 0; }
+    };
+    int dict_cap = 0;           // DICT_CAP: at most this many loci per tile dictionary (taken when above a row's words)
+    Int locus_sets;             // LOCUS_SETS=1: the whole-row form of the locus sets, taken; 0: that form is not taken
+    Int group_sets;             // GROUP_SETS=1 / 0: the mask-group sets taken whatever they save / not looked for
+    uint32_t set_min_rows = 192;   // SET_MIN_ROWS (> 0): rows a mask-group set must be carried by
+    Int run_words;              // RUN_WORDS=0 no fold, 1 the one-word fold alone, 2 both folds - forced
+    int tile_words = 0;         // TILE_WORDS (>= 64): words per tile instead of the rule's
+    bool tile_order = true;     // TILE_ORDER=0 keeps the tiles in locus order
+    bool half_loci = false;     // HALF_LOCI=1: 16 haplotypes as half-loci of 8
+    bool persistent = false;    // PERSISTENT=1: persistent E-step workgroups
+    unsigned persistent_groups = 0;   // PERSISTENT_GROUPS (> 0): that many of them
+    bool no_phase_split = false;      // NO_PHASE_SPLIT=1: one batch loop for every batch
+    uint32_t resample_cut = 256;      // RESAMPLE_CUT (> 0): rows with a larger count get a workgroup in the draw
+};
+
+namespace em_env {
+inline EmTuning::Int integer(const char *name) {
+    EmTuning::Int i;
+    if (const char *e = std::getenv(name); e) { i.set = true; i.v = std::atoi(e); }
+    return i;
+}
+// a value taken only when it is at least `lo`
+template <typename T>
+inline void at_least(const char *name, int lo, T &v) {
+    if (const char *e = std::getenv(name); e && std::atoi(e) >= lo) v = (T)std::atoi(e);
+}
+}  // namespace em_env
+
+// Read at every gbrs_em_create* and never kept: the tests change the variables between handles of one process.
+inline EmTuning em_tuning_from_env() {
+    using namespace em_env;
+    EmTuning t;
+    at_least("GBRS_TUNING_DICT_CAP", 1, t.dict_cap);
+    t.locus_sets = integer("GBRS_TUNING_LOCUS_SETS");
+    t.group_sets = integer("GBRS_TUNING_GROUP_SETS");
+    at_least("GBRS_TUNING_SET_MIN_ROWS", 1, t.set_min_rows);
+    t.run_words = integer("GBRS_TUNING_RUN_WORDS");
+    at_least("GBRS_TUNING_TILE_WORDS", 64, t.tile_words);
+    t.tile_order = !integer("GBRS_TUNING_TILE_ORDER").is(0);
+    t.half_loci = integer("GBRS_TUNING_HALF_LOCI").nonzero();
+    t.persistent = integer("GBRS_TUNING_PERSISTENT").nonzero();
+    at_least("GBRS_TUNING_PERSISTENT_GROUPS", 1, t.persistent_groups);
+    t.no_phase_split = integer("GBRS_TUNING_NO_PHASE_SPLIT").nonzero();
+    at_least("GBRS_TUNING_RESAMPLE_CUT", 1, t.resample_cut);
+    return t;
+}
+
+// ---- shape ----------------------------------------------------------------------------------------------------------------
+
+// the dictionary limits of em_layout.h for one (weighted, haplotypes) pair: those functions are __host__ __device__, so
+// the caller evaluates them
+struct EmDictLimits {
+    uint32_t max_row_words = 0;   // max_row_words(H)
+    uint32_t index_limit = 0;     // dict_index_limit(H)
+    uint32_t lds_doubles = 0;     // lds_theta_doubles(weighted, H)
+    uint32_t det_cap = 0;         // det_dict_cap(H, weighted)
+};
+
+struct EmShape {
+    uint32_t H = 0, L = 0;
+    uint64_t R = 0, N = 0;        // N: the entries after the upload (masked handles: the masked count)
+    uint32_t flags = 0;           // GBRS_EM_*
+    bool counts_given = false;    // the caller passed row counts
+    int n_cu = 0;                 // compute units of the handle's device
+    uint32_t tile_words = 0, tile_words_max = 0, tile_rounds_min = 1;   // TILE_WORDS, TILE_WORDS_MAX, TILE_ROUNDS_MIN
+    EmDictLimits dict;            // at H haplotypes, weighted as em_weighted() says
+    EmDictLimits dict_half;       // at H / 2 haplotypes, unweighted: the half-locus view's (read at H = 16 only)
+};
+
+// per-row weights: counts given, a resampling handle (base weights of counts or ones) or identical rows merged
+inline bool em_weighted(uint32_t flags, bool counts_given) {
+    return counts_given || (flags & (GBRS_EM_RESAMPLE | GBRS_EM_MERGE_IDENTICAL_ROWS)) != 0;
+}
+
+// ---- plan -----------------------------------------------------------------------------------------------------------------
+
+struct EmPlan {
+    bool tiled = false;              // the tile layout; false: the CSC kernels (nothing below is used)
+    // 16 haplotypes as half-loci on the 8-haplotype kernels (em_layout.h; the review's "two halves of 8"): built, parity-green,
+    // NO gain - one GPU's shard of config 5: E-step 0.1518 ms against 0.1525 (the words double, the cost per word halves) and
+    // the iteration 0.1997 against 0.1744 (gather and M-step as two launches over every element).  GBRS_TUNING_HALF_LOCI=1
+    // switches it on; weighted rows and the deterministic mode never take it.
+    uint32_t view = 1;               // 2: the layout is built over tL = 2 L half-loci of tH = H / 2 haplotypes
+    uint32_t tH = 0, tL = 0;
+    // Row order inside a tile: the stream order (gbrs_hip.h) by default - every lane walks a contiguous piece of the
+    // tile's sorted rows, so it stays on one locus list for long stretches (E-step on C2: raw reads 0.158 -> 0.152 ms,
+    // merged distinct rows 0.110 -> 0.056 ms against the interleaved order that used to be their default).
+    int row_order = 2;               // 0 sorted, 1 interleaved, 2 streams
+    bool merge = false, deterministic = false, weighted = false;
+    unsigned side_by_side = 1;       // handles that share the device (GBRS_EM_SIDE_BY_SIDE: 2)
+    // locus sets (weighted rows never: their tiles are dictionary-bound)
+    bool locus_sets = false;
+    bool whole_row_sets = false;     // step 3b's first form instead of step 3c's mask groups
+    bool group_sets = false;         // step 3c is looked at
+    bool group_sets_forced = false;
+    int sets_forced = -1;            // whole-row form: 1 / 0 the choice is forced, -1 the rule decides
+    uint32_t set_min_rows = 192;
+    // folds of identical one- and two-word reads
+    bool counted_pairs = false;      // the layout's kernels read TileHdr::n_two
+    bool fold = false;               // the fold is tried ...
+    int fold_mode = 3;               // ... first as merge_flag_kernel's mode 3 (both folds) or 2 (one-word reads)
+    bool fold_forced = false;        // what is tried is taken
+    // resident E-step workgroups per CU (tile_estep_kernel's launch bounds: 3 for unweighted rows of <= 8 haplotypes,
+    // else 2) and the places the chip has for them in TILE_ROUNDS_MIN rounds
+    unsigned per_cu = 3;
+    uint64_t places = 0;
+    uint32_t tile_words = 0, tile_words_cap = 0;   // the tile-size rule's bounds (cap: a multiple of 64 follows from the rule)
+    uint32_t tile_words_forced = 0;  // > 0: GBRS_TUNING_TILE_WORDS, clamped
+    bool reorder_tiles = true;       // launch order: most batches first
+    uint32_t d_max = 0, dseg = 0;    // dictionary capacity; what is left of it beside one row's loci
+    bool dict_room = false;          // false: d_max leaves no room for a row's loci - the build refuses
+    // persistent E-step workgroups: one per place the chip has for them, shared between handles that run side by side.
+    // GBRS_TUNING_PERSISTENT=1 switches them on: built, parity-green and measured in round 4 - 8-10 % SLOWER than one
+    // workgroup per tile on the C2 sample (profiles/r04_estep_experiments.txt), so off by default
+    uint32_t persist_groups = 0;
+    // GBRS_TUNING_NO_PHASE_SPLIT=1: the E-step takes every tile's n_one and n_two as 0 - one batch loop, as before the headers
+    // had the field (A/B in one build, and the cross-check of the two-loop form in the tests)
+    uint32_t lead_mask = ~0u;
+    uint32_t resample_cut = 256;     // (the variable is read by a resampling handle with counts only)
+};
+
+inline EmPlan em_plan(const EmShape &s, const EmTuning &t) {
+    EmPlan p;
+    const uint32_t f = s.flags;
+    p.merge = (f & GBRS_EM_MERGE_IDENTICAL_ROWS) != 0;
+    p.deterministic = (f & GBRS_EM_DETERMINISTIC) != 0;
+    p.weighted = em_weighted(f, s.counts_given);
+    p.side_by_side = (f & GBRS_EM_SIDE_BY_SIDE) ? 2u : 1u;
+    if ((f & GBRS_EM_RESAMPLE) && s.counts_given) p.resample_cut = t.resample_cut;
+    p.tiled = !(f & GBRS_EM_LAYOUT_CSC) && s.H <= 16 && s.N < 0xFFFFFFFFull;
+    p.tH = s.H;
+    p.tL = s.L;
+    if (!p.tiled) return p;
+
+    if (f & GBRS_EM_FORCE_INTERLEAVE) p.row_order = 1;
+    else if (f & GBRS_EM_NO_STREAMS) p.row_order = (p.weighted && !(f & GBRS_EM_NO_INTERLEAVE)) ? 1 : 0;
+    if (s.H == 16 && t.half_loci && !p.weighted && !p.deterministic && (uint64_t)s.L * 2 < (1u << 27)) p.view = 2;
+    p.tH = s.H / p.view;
+    p.tL = s.L * p.view;
+    const EmDictLimits &d = p.view == 2 ? s.dict_half : s.dict;
+
+    p.locus_sets = !(f & GBRS_EM_NO_LOCUS_SETS) && !p.weighted;
+    p.whole_row_sets = p.locus_sets && t.locus_sets.is(1);
+    if (t.locus_sets.set) p.sets_forced = t.locus_sets.v != 0;
+    p.group_sets = p.locus_sets && !t.group_sets.is(0);      // (and only when step 3b took no sets)
+    p.group_sets_forced = t.group_sets.is(1);
+    p.set_min_rows = t.set_min_rows;
+
+    p.counted_pairs = p.row_order == 2 && !p.weighted && !p.deterministic && p.view == 1 &&
+                      (p.tH == 1 || p.tH == 2 || p.tH == 4 || p.tH == 8);
+    p.fold = !(f & GBRS_EM_NO_RUN_WORDS) && p.counted_pairs && !t.run_words.is(0);
+    p.fold_mode = t.run_words.is(1) ? 2 : 3;
+    p.fold_forced = t.run_words.set;
+
+    p.per_cu = (p.weighted || p.tH > 8) ? 2u : 3u;
+    const unsigned n_cu = (unsigned)std::max(s.n_cu, 1);
+    p.places = (uint64_t)s.tile_rounds_min * p.per_cu * n_cu;
+    p.tile_words = s.tile_words;
+    // (weighted rows - merged reads, EC counts - stay at 16,320: the merged C2 sample reads 0.0345 ms there, 0.0357 at 20,900)
+    p.tile_words_cap = p.weighted ? std::min<uint32_t>(s.tile_words_max, 16320) : s.tile_words_max;
+    if (t.tile_words) p.tile_words_forced = std::min<uint32_t>((uint32_t)t.tile_words, s.tile_words_max);
+    p.reorder_tiles = t.tile_order;
+
+    p.d_max = std::min<uint32_t>(1024, d.lds_doubles / p.tH);
+    p.d_max = std::min(p.d_max, d.index_limit);     // what a word's index field can hold (1024 at H = 16)
+    if (p.deterministic) p.d_max = std::min(p.d_max, d.det_cap);
+    if (t.dict_cap > (int)d.max_row_words) p.d_max = std::min(p.d_max, (uint32_t)t.dict_cap);
+    p.dict_room = p.d_max > d.max_row_words;
+    p.dseg = p.dict_room ? p.d_max - d.max_row_words : 0;
+
+    unsigned groups = p.per_cu * n_cu / p.side_by_side;
+    if (t.persistent_groups) groups = t.persistent_groups;
+    p.persist_groups = t.persistent ? std::max(groups, 1u) : 0u;
+    p.lead_mask = t.no_phase_split ? 0u : ~0u;
+    return p;
+}
+
+// ---- the rules that need a number from the device -----------------------------------------------------------------------
+
+// Tile size: as large as still leaves TILE_ROUNDS_MIN rounds of the chip's resident E-step workgroups, between TILE_WORDS
+// and the cap (em_layout.h), a multiple of 64; GBRS_TUNING_TILE_WORDS overrides.  Handles that run side by side - the
+// locus ranges of one sample - fill the rounds together.
+inline uint32_t em_tile_words(const EmPlan &p, uint64_t total_words) {
+    if (p.tile_words_forced) return p.tile_words_forced;
+    const uint64_t fit = total_words * p.side_by_side / p.places;
+    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(fit, p.tile_words), p.tile_words_cap) & ~63u;
+}
+
+// The fold pays by the words it takes away - one for a one-word read, two for a two-word read - and a launch still wants
+// a tile of TILE_WORDS words for every resident workgroup place of the chip: a sample smaller than that is launch-bound
+// and keeps one word per read.  GBRS_TUNING_RUN_WORDS=2 / 1 forces the choice (0 never gets here).
+inline bool em_take_fold(const EmPlan &p, uint64_t words_in, uint64_t folded) {
+    if (p.fold_forced) return true;
+    return folded * 100 >= words_in * 15 && (words_in - folded) * p.side_by_side / p.places >= (uint64_t)p.tile_words;
+}
+
+// Whole-row sets (step 3b).  A set entry costs its tile a longer prologue and epilogue (its members' theta summed, its
+// sums stored once per member), which pays when the words it saves are many and every dictionary entry serves many
+// words.  Measured (profiles/r03_estep_experiments.txt item 8): C2, 23 % fewer words at 137 words per id: E-step -11 %;
+// the 16-haplotype shard (same saving, 62 words per id) +8 %; multi-isoform reads (9 % fewer words) +8 %.  And no more
+// sets than twice the loci: many thin sets fill the tiles' dictionaries (item 16 of the same file).
+// P / P2: the pairs before and after, V: the sets, L: the loci.  GBRS_TUNING_LOCUS_SETS=1 / 0 forces the choice.
+inline bool em_use_whole_row_sets(const EmPlan &p, uint64_t P, uint64_t P2, uint64_t L, uint64_t V) {
+    if (p.sets_forced >= 0) return p.sets_forced != 0;
+    return P2 * 100 <= P * 85 && P2 >= 100 * (L + V) && V <= 2 * L;
+}
+
+// Mask-group sets (step 3c): the frequent sets only, and no more of them than half the loci - the rows a set must be
+// carried by double until they fit (GBRS_TUNING_GROUP_SETS=1: whatever the first threshold keeps)
+inline bool em_group_sets_fit(const EmPlan &p, uint64_t V, uint64_t L) { return V * 2 <= L || p.group_sets_forced; }
+// ... and worth it when they take a twentieth of the words away
+inline bool em_use_group_sets(const EmPlan &p, uint64_t P, uint64_t P2) { return p.group_sets_forced || P2 * 100 <= P * 95; }
+
+}  // namespace gbrs

@@ -326,6 +326,34 @@ def test_em_tile_sizes_vs_oracle(tile_words, monkeypatch):
         em.close()
 
 
+def test_tuning_variables_are_read_at_every_create(monkeypatch):
+    """Two handles of one process over the smoke problem, GBRS_TUNING_TILE_WORDS changed between them: the second handle
+    is cut by the second value (em_plan.h reads the variables at every gbrs_em_create*; a plan kept in a static fails here)."""
+    from gbrs_amd import synth
+    from gbrs_amd.alignment import AlignmentPropertyMatrix
+    from gbrs_amd.em import EMfactory
+    from oracle.em_oracle import EMOracle
+    inc = synth.make_em_problem(R=20_000, H=8, L=400, seed=3)
+    eff = inc.effective_length(100)
+    o = EMOracle(inc.num_rows, inc.num_loci, inc.num_haps, inc.indptr, inc.indices, None)
+    o.prepare(0.0, eff)
+    n = o.run(tol=1e-4, max_iters=999)
+    apm = AlignmentPropertyMatrix(shape=(inc.num_loci, inc.num_haps, inc.num_rows), indptr=inc.indptr,
+                                  indices=inc.indices, haplotype_names=inc.hap_names, locus_names=inc.locus_names)
+    num_tiles = []
+    for tile_words in (64, 1000):
+        monkeypatch.setenv("GBRS_TUNING_TILE_WORDS", str(tile_words))
+        em = EMfactory(apm)
+        em.target_lengths = eff
+        em.prepare(0.0)
+        num_tiles.append(em.info().num_tiles)
+        em.run(model=4, tol=1e-4, max_iters=999, verbose=False)
+        assert em.num_iters == n
+        close(em.allelic_expression, o.theta, rtol=1e-9)
+        em.close()
+    assert num_tiles[0] != num_tiles[1], num_tiles
+
+
 def test_em_properties_h8():
     """Size-independent properties on a DO-shaped (H=8) problem: conservation of read mass,
     row-permutation invariance, and EC-compression invariance (duplicated rows == count)."""

@@ -293,7 +293,9 @@ pseudo_scale_kernel(uint64_t n, int nblocks, double *__restrict__ theta,
     double a = reduce_partials(partials, nblocks, lds);
     double b = reduce_partials(partials + RED_BLOCKS, nblocks, lds);
     if (threadIdx.x == 0) {
-        s_f = a / b;
+        // (a handle without entries: no locus got the pseudocount, every element is 0 and stays 0 - the reference's
+        // 0 / 0 hands back NaN under a numpy warning)
+        s_f = b != 0.0 ? a / b : 1.0;
         if (blockIdx.x == 0) {
             sc->pc_before = a;
             sc->pc_after = b;

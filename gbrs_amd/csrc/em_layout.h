@@ -4,7 +4,7 @@
 //   word   = one (row, locus) pair of a read: [ local locus index | rem | pos | hap mask ]
 //            bits [0,H) mask; PB bits pos = words of the row before this one; PB bits rem = words
 //            of the row after it; the rest = index into the tile's dictionary.  PB = 5 (rows of up
-//            to 32 loci) for H <= 8, 4 (16 loci) for H <= 16.
+//            to 32 loci) for H <= 8, 3 (8 loci) for H <= 16 (pos_bits() below).
 //            A one-word row has pos = rem = 0, and in a tile's leading one-word batches (TileHdr::n_one) those 2 PB bits
 //            are ONE field: the number of FURTHER identical reads - same dictionary entry, same mask - the word stands
 //            for (the fold of build_tile_layout's step 5; it adds (1 + count) / den once).  0 everywhere in a layout that

@@ -192,7 +192,10 @@ int gbrs_em_create_masked_device(uint64_t num_rows, uint32_t num_loci, uint32_t 
 int gbrs_em_set_initial_values(gbrs_em_t *em, const double *const *values);
 
 /* Replaces EMfactory.prepare (EMfactory.py:95-111): theta0 = sum_r count[r]/nnz_row / eff_len,
- * then the optional pseudocount rule (:105-111). */
+ * then the optional pseudocount rule (:105-111).  A handle without entries (empty columns, or a mask that
+ * removes every entry) gets theta = 0 whatever the pseudocount - no locus has a value to add it to, and
+ * there is no total to rescale to; a step or a run on it is GBRS_ERR_FLOAT, the reference's division by
+ * the zero total. */
 int gbrs_em_prepare(gbrs_em_t *em, double pseudocount);
 
 /* n_iters EM steps (EMfactory.update_allelic_expression, EMfactory.py:214-232) without looking

@@ -674,7 +674,7 @@ def test_two_rank_pipelined_hip_engines(tmp_path, name):
 
 def _random_rows_problem(R, H, L, seed, min_loci, max_loci, with_count):
     """Rows with many loci each and no repetition structure: exercises cold tiles (dictionary cuts),
-    multi-word row sums and, above 32 loci (16 for H > 8), the long-row kernel."""
+    multi-word row sums and, above 32 loci (8 for H > 8), the long-row kernel."""
     rng = np.random.default_rng(seed)
     nl = rng.integers(min_loci, max_loci + 1, size=R)
     rows = np.repeat(np.arange(R, dtype=np.int64), nl)

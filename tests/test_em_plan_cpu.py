@@ -5,41 +5,16 @@ host compiler and run once per row with the row's environment.  The expected val
 em_create_impl and build_tile_layout as they stood before the plan existed, with the constants of em_layout.h:
 TILE_WORDS 2048, GBRS_TILE_CAP 32768, 3072 / 4608 / 4800 doubles of theta in LDS (unweighted / weighted / 16 haplotypes),
 rows of up to 32 (H <= 8) or 8 words, 8 waves per workgroup."""
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
-from conftest import ROOT
+from em_plan_tool import N_CU, build_driver, plan
 
-with open(os.path.join(ROOT, "include", "gbrs_hip.h")) as _f:
-    FLAG = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define GBRS_EM_(\w+) (\d+)u", _f.read())}
-N_CU = 256
 TILE_WORDS, TILE_WORDS_MAX = 2048, 32768 - 64
 
 
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    exe = tmp_path_factory.mktemp("em_plan") / "em_plan_driver"
-    cmd = [cxx, "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror",
-           os.path.join(ROOT, "tests", "native", "em_plan_driver.cpp"), "-o", str(exe)]
-    build = subprocess.run(cmd, capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr[-3000:]
-    return str(exe)
-
-
-def plan(driver, H=8, L=400, R=20000, N=100000, flags=(), counts=0, n_cu=N_CU, rule=None, **tuning):
-    env = {k: v for k, v in os.environ.items() if not k.startswith("GBRS_TUNING_")}
-    env.update({"GBRS_TUNING_" + k: str(v) for k, v in tuning.items()})
-    args = [driver, H, L, R, N, sum(FLAG[f] for f in flags), counts, n_cu] + ([rule] if rule else [])
-    run = subprocess.run([str(a) for a in args], capture_output=True, text=True, env=env, timeout=60)
-    assert run.returncode == 0, run.stderr
-    return {k: int(v) for k, v in (kv.split("=") for kv in run.stdout.split())}
+    return build_driver(tmp_path_factory.mktemp("em_plan"))
 
 
 # an unweighted handle of 8 haplotypes on 256 CUs, no flag, no variable

@@ -27,7 +27,8 @@ EXPORTS = [
     "gbrs_counts_create", "gbrs_counts_get", "gbrs_counts_destroy", "gbrs_em_destroy",
     "gbrs_shard_plan", "gbrs_shard_index", "gbrs_shard_gather",
     "gbrs_hmm_create", "gbrs_hmm_set_expression", "gbrs_hmm_set_eprob", "gbrs_hmm_run",
-    "gbrs_hmm_get", "gbrs_hmm_info", "gbrs_hmm_destroy", "gbrs_interpolate", "gbrs_genoprob_dosage",
+    "gbrs_hmm_get", "gbrs_hmm_info", "gbrs_hmm_destroy",
+    "gbrs_grid_knots", "gbrs_hmm_set_grid", "gbrs_hmm_grid", "gbrs_hmm_grid_info", "gbrs_interpolate", "gbrs_genoprob_dosage",
     "gbrs_ri_transition_tables", "gbrs_alignment_spec",
     "gbrs_compress_create", "gbrs_compress_get", "gbrs_compress_destroy",
     "gbrs_bam_open", "gbrs_bam_references", "gbrs_bam_set_reference_map", "gbrs_bam_convert", "gbrs_bam_get",
@@ -170,6 +171,10 @@ def load():
         "gbrs_hmm_get": [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
         "gbrs_hmm_info": [vp, C.POINTER(HmmInfo)],
         "gbrs_hmm_destroy": [vp],
+        "gbrs_grid_knots": [i32, vp, i32, vp, vp, vp],
+        "gbrs_hmm_set_grid": [vp, vp, pp, vp, pp],
+        "gbrs_hmm_grid": [vp, i32, vp, vp],
+        "gbrs_hmm_grid_info": [vp, C.POINTER(i64), C.POINTER(dbl)],
         "gbrs_interpolate": [i32, i32, vp, vp, i32, vp, vp, i32],
         "gbrs_genoprob_dosage": [i32, i64, vp, vp, i32],
         "gbrs_ri_transition_tables": [vp, vp, vp, i64, dbl, dbl, i32, vp],

@@ -70,7 +70,17 @@ def build_parser():
     q.add_argument('--dist-backend', choices=('nccl', 'gloo'), default='nccl',
                    help='with --gpus: collective backend, nccl = RCCL (default); gloo allows two ranks on one GPU')
     r = sub.add_parser('reconstruct', help='reconstruct the genome based upon gene-level TPM quantities')
-    r.add_argument('-e', '--expr-file', dest='expression_file', required=True, type=_existing)
+    samples = r.add_mutually_exclusive_group(required=True)
+    samples.add_argument('-e', '--expr-file', dest='expression_file', type=_existing, default=None)
+    samples.add_argument('--sample-file', type=_existing, default=None,
+                         help='(extension, instead of -e) a cohort: tab separated lines `genes.tpm<TAB>outbase`, blank and '
+                              '# lines skipped; the samples go through the device in launches of --batch-size')
+    r.add_argument('--batch-size', type=int, default=64, help='with --sample-file: samples per device launch (default 64)')
+    r.add_argument('--grid-file', type=_existing, default=None,
+                   help='(extension) marker grid: also write <outbase>.interpolated.genoprobs.tsv, the founder dosages '
+                        '`gbrs export` writes after `gbrs interpolate`, from the posteriors on the device')
+    r.add_argument('--grid-genoprobs', action='store_true',
+                   help='with --grid-file: also write <outbase>.interpolated.genoprobs.npz, the file of `gbrs interpolate`')
     r.add_argument('-t', '--tprob-file', required=True, type=_existing)
     r.add_argument('-x', '--avec-file', type=_existing, default=None)
     r.add_argument('-g', '--gpos-file', type=_existing, default=None)
@@ -324,12 +334,20 @@ def main(argv=None) -> int:
             strains = [s for x in args.strains for s in x.split(',')]
             export(genoprob_file=args.genoprob_file, strains=strains, grid_file=args.grid_file,
                    output_file=args.output_file, device=args.device)
+        elif args.sample_file is not None:
+            from .hmm import read_sample_file, reconstruct_many
+            samples = read_sample_file(args.sample_file)
+            reconstruct_many([f for f, _ in samples], [o for _, o in samples], tprob_file=args.tprob_file,
+                             avec_file=args.avec_file, gpos_file=args.gpos_file, expr_threshold=args.expr_threshold,
+                             sigma=args.sigma, device=args.device, batch_size=args.batch_size, grid_file=args.grid_file,
+                             grid_genoprobs=args.grid_genoprobs, stage_times=stages)
         else:
             from .hmm import reconstruct
             reconstruct(expression_file=args.expression_file, tprob_file=args.tprob_file,
                         avec_file=args.avec_file, gpos_file=args.gpos_file,
                         expr_threshold=args.expr_threshold, sigma=args.sigma, outbase=args.outbase,
-                        device=args.device, stage_times=stages)
+                        device=args.device, stage_times=stages, grid_file=args.grid_file,
+                        grid_genoprobs=args.grid_genoprobs)
     except Exception as e:   # noqa: BLE001 - mirror of the reference's catch-all
         failure = e
         if logger.level == logging.DEBUG:

@@ -9,6 +9,7 @@
 // and latency bound.
 #include "common.h"
 #include "hmm_route.h"
+#include "grid_knots.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -2482,6 +2483,8 @@ __global__ void dosage_kernel(int H, int S, int64_t rows, const double *__restri
     out[id] = acc;
 }
 
+#include "hmm_grid.inc"
+
 }  // namespace gbrs
 
 using namespace gbrs;
@@ -2546,6 +2549,16 @@ struct gbrs_hmm {
                gev_done[2] = {nullptr, nullptr}, gev_start = nullptr;
     DevBuf<double> g_f, g_b, g_d, inj_f, inj_b, inj_d;   // block operators [sample][block][36][36], boundary vectors [sample][block][36]
     DevBuf<int32_t> e_f, e_b;                 // power-of-two exponents of the operators' columns
+    // Grid pass (hmm_grid.inc): the marker grid is sample independent and stays here like avecs; the two output buffers
+    // are sized by the last call that asked for them.
+    bool have_grid = false;
+    int grid_tiles = 0;
+    int64_t grid_points = 0;                  // grid points of the handle's chromosomes
+    DevBuf<GridChrom> d_grid_chroms;
+    DevBuf<GridTile> d_grid_tiles;
+    DevBuf<double> grid_knot_x, grid_x, grid_dosage, grid_gamma;
+    DevBuf<int32_t> grid_knot_gene;
+    double t_grid = 0;
 };
 
 namespace {
@@ -3644,6 +3657,115 @@ int gbrs_genoprob_dosage(int num_haps, int64_t n_rows, const double *gprob, doub
                        d_p.p, d_o.p);
     GBRS_HIP_CHECK(hipGetLastError());
     GBRS_HIP_CHECK(hipMemcpy(out, d_o.p, d_o.bytes(), hipMemcpyDeviceToHost));
+    return GBRS_OK;
+}
+
+int gbrs_grid_knots(int n_genes, const double *gene_pos, int n_grid, const double *grid, double *knots,
+                    int32_t *knot_gene) {
+    char msg[256];
+    if (grid_knots(n_genes, gene_pos, n_grid, grid, knots, knot_gene, msg, sizeof msg) != 0)
+        return fail(GBRS_ERR_INVALID, "%s", msg);
+    return GBRS_OK;
+}
+
+int gbrs_hmm_set_grid(gbrs_hmm_t *h, const int32_t *n_pos, const double *const *gene_pos, const int32_t *n_grid,
+                      const double *const *grid) {
+    if (!h || !n_pos || !gene_pos || !n_grid || !grid) return fail(GBRS_ERR_INVALID, "bad argument");
+    // everything is prepared and checked on the host before the handle changes
+    const int P = grid_tile_points(h->S);
+    std::vector<GridChrom> gc(h->n_chrom);
+    std::vector<GridTile> tiles;
+    std::vector<double> knot_x, x;
+    std::vector<int32_t> knot_gene;
+    for (int c = 0; c < h->n_chrom; ++c) {
+        const ChromDesc &cd = h->chroms[c];
+        GridChrom &g = gc[c];
+        g.gene_off = cd.gene_off;
+        g.knot_off = (int32_t)knot_x.size();
+        g.point_off = (int32_t)x.size();
+        g.n_knots = g.n_points = 0;
+        if (n_grid[c] < 0) return fail(GBRS_ERR_INVALID, "n_grid[%d] is negative", c);
+        if (n_grid[c] == 0) continue;
+        if (n_pos[c] == 0)
+            return fail(GBRS_ERR_INVALID, "index -1 is out of bounds for axis 1 with size 0 (grid chromosome %d has no genes)", c);
+        if (n_pos[c] != cd.n_genes)
+            return fail(GBRS_ERR_INVALID, "chromosome %d: %d gene positions for %d genes", c, n_pos[c], cd.n_genes);
+        if ((int64_t)x.size() + n_grid[c] > INT32_MAX) return fail(GBRS_ERR_INVALID, "too many grid points");
+        g.n_knots = cd.n_genes + 2;
+        g.n_points = n_grid[c];
+        knot_x.resize(knot_x.size() + g.n_knots);
+        knot_gene.resize(knot_x.size());
+        GBRS_TRY(gbrs_grid_knots(cd.n_genes, gene_pos[c], n_grid[c], grid[c], knot_x.data() + g.knot_off,
+                                 knot_gene.data() + g.knot_off));
+        x.insert(x.end(), grid[c], grid[c] + n_grid[c]);
+        for (int32_t first = 0; first < g.n_points; first += P) tiles.push_back(GridTile{c, first});
+    }
+    GBRS_TRY(select_device(h->device));
+    DevBuf<GridChrom> d_gc;
+    DevBuf<GridTile> d_tiles;
+    DevBuf<double> d_knot_x, d_x;
+    DevBuf<int32_t> d_knot_gene;
+    GBRS_TRY(d_gc.alloc(gc.size()));
+    GBRS_TRY(d_tiles.alloc(tiles.size()));
+    GBRS_TRY(d_knot_x.alloc(knot_x.size()));
+    GBRS_TRY(d_knot_gene.alloc(knot_gene.size()));
+    GBRS_TRY(d_x.alloc(x.size()));
+    GBRS_HIP_CHECK(hipMemcpy(d_gc.p, gc.data(), d_gc.bytes(), hipMemcpyHostToDevice));
+    if (!tiles.empty()) {
+        GBRS_HIP_CHECK(hipMemcpy(d_tiles.p, tiles.data(), d_tiles.bytes(), hipMemcpyHostToDevice));
+        GBRS_HIP_CHECK(hipMemcpy(d_knot_x.p, knot_x.data(), d_knot_x.bytes(), hipMemcpyHostToDevice));
+        GBRS_HIP_CHECK(hipMemcpy(d_knot_gene.p, knot_gene.data(), d_knot_gene.bytes(), hipMemcpyHostToDevice));
+        GBRS_HIP_CHECK(hipMemcpy(d_x.p, x.data(), d_x.bytes(), hipMemcpyHostToDevice));
+    }
+    h->d_grid_chroms.swap(d_gc);
+    h->d_grid_tiles.swap(d_tiles);
+    h->grid_knot_x.swap(d_knot_x);
+    h->grid_knot_gene.swap(d_knot_gene);
+    h->grid_x.swap(d_x);
+    h->grid_tiles = (int)tiles.size();
+    h->grid_points = (int64_t)x.size();
+    h->have_grid = true;
+    return GBRS_OK;
+}
+
+int gbrs_hmm_grid(gbrs_hmm_t *h, int sample, double *dosage, double *gamma_grid) {
+    RoctxRange roctx_range("gbrs_hmm_grid");
+    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (!h->ran) return fail(GBRS_ERR_STATE, "run() has not been called");
+    if (!h->have_grid) return fail(GBRS_ERR_INVALID, "no grid on the handle: call gbrs_hmm_set_grid first");
+    if (sample < -1 || sample >= h->n_samples) return fail(GBRS_ERR_INVALID, "sample out of range");
+    if ((!dosage && !gamma_grid) || h->grid_tiles == 0) return GBRS_OK;
+    GBRS_TRY(select_device(h->device));
+    const int S = h->S, H = h->H;
+    const int n = sample < 0 ? h->n_samples : 1;
+    const size_t n_dosage = (size_t)n * h->grid_points * H, n_gamma = (size_t)n * h->grid_points * S;
+    if (dosage && h->grid_dosage.n != n_dosage) GBRS_TRY(h->grid_dosage.alloc(n_dosage));
+    if (gamma_grid && h->grid_gamma.n != n_gamma) GBRS_TRY(h->grid_gamma.alloc(n_gamma));
+    const dim3 grid((unsigned)h->grid_tiles, (unsigned)n);
+    const size_t lds = grid_tile_lds(S);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(64), lds, h->stream, H, S, grid_tile_points(S), h->total_genes, h->grid_points,
+                           std::max(sample, 0), h->d_grid_chroms.p, h->d_grid_tiles.p, h->grid_knot_x.p, h->grid_knot_gene.p,
+                           h->grid_x.p, h->gamma.p, dosage ? h->grid_dosage.p : nullptr, gamma_grid ? h->grid_gamma.p : nullptr);
+    };
+    GBRS_HIP_CHECK(hipEventRecord(h->ev[0], h->stream));
+    if (S <= 64) launch(grid_kernel<1>);
+    else if (S <= 128) launch(grid_kernel<2>);
+    else launch(grid_kernel<3>);          // S <= 136 (MAX_H = 16)
+    GBRS_HIP_CHECK(hipEventRecord(h->ev[1], h->stream));
+    GBRS_HIP_CHECK(hipGetLastError());
+    GBRS_HIP_CHECK(hipStreamSynchronize(h->stream));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, h->ev[0], h->ev[1]) == hipSuccess) h->t_grid = ms;
+    if (dosage) GBRS_HIP_CHECK(hipMemcpy(dosage, h->grid_dosage.p, n_dosage * sizeof(double), hipMemcpyDeviceToHost));
+    if (gamma_grid) GBRS_HIP_CHECK(hipMemcpy(gamma_grid, h->grid_gamma.p, n_gamma * sizeof(double), hipMemcpyDeviceToHost));
+    return GBRS_OK;
+}
+
+int gbrs_hmm_grid_info(gbrs_hmm_t *h, int64_t *n_points, double *last_ms) {
+    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (n_points) *n_points = h->have_grid ? h->grid_points : 0;
+    if (last_ms) *last_ms = h->t_grid;
     return GBRS_OK;
 }
 

@@ -114,10 +114,83 @@ class DiplotypeHMM:
         _lib.check(_lib.load().gbrs_hmm_get(self._h, sample, c, *args))
         return {k: bufs[k] for k in want}
 
+    def set_grid(self, gene_positions, grid):
+        """The marker grid of the handle (sample independent, uploaded once).  Both arguments go by handle chromosome:
+        a sequence in the handle's order or a dict by chromosome name.  grid[c]: grid positions in file order, None,
+        empty or absent for a chromosome that is not on the grid; gene_positions[c]: the positions of its genes in
+        genome order.  The knots are made as postproc.interpolate_arrays makes them; a grid point outside them raises
+        interp1d's ValueError, a grid chromosome without gene positions the chain's IndexError."""
+        def by_chrom(table):
+            if isinstance(table, dict):
+                return [table.get(c) for c in self.chroms]
+            return list(table) + [None] * (len(self.chroms) - len(table))
+        points = [np.zeros(0) if g is None else np.ascontiguousarray(g, dtype=np.float64) for g in by_chrom(grid)]
+        where = [np.zeros(0) if len(g) == 0 or x is None else np.ascontiguousarray(x, dtype=np.float64)
+                 for g, x in zip(points, by_chrom(gene_positions))]
+        n_grid = np.asarray([len(g) for g in points], dtype=np.int32)
+        n_pos = np.asarray([len(x) for x in where], dtype=np.int32)
+        lib = _lib.load()
+        status = lib.gbrs_hmm_set_grid(self._h, _lib.ptr(n_pos), _lib.ptr_table(where), _lib.ptr(n_grid),
+                                       _lib.ptr_table(points))
+        _raise_grid_error(lib, status)
+        self.grid_points = [int(m) for m in n_grid]
+        self.grid_offsets = [int(o) for o in np.concatenate(([0], np.cumsum(n_grid)[:-1]))]
+
+    def grid(self, sample=None, want=('dosage',)):
+        """The last run on the handle's grid, one device pass: `dosage` [n, M, H] founder dosages, the grid points of the
+        handle's chromosomes one after the other (chromosome c: rows grid_offsets[c] .. + grid_points[c]); `gamma_grid`
+        per sample a list over the handle's chromosomes of (S x grid_points[c]) arrays, None off the grid.  sample=None:
+        every sample of the run (n of them); an index: that sample, without the leading axis / list."""
+        n = self.n_samples if sample is None else 1
+        M = sum(getattr(self, 'grid_points', ()))
+        out = {}
+        dosage = np.empty((n, M, self.H)) if 'dosage' in want else None
+        flat = np.empty((n, self.S * M)) if 'gamma_grid' in want else None
+        _lib.check(_lib.load().gbrs_hmm_grid(self._h, -1 if sample is None else int(sample), _lib.ptr(dosage),
+                                             _lib.ptr(flat)))
+        if dosage is not None:
+            out['dosage'] = dosage if sample is None else dosage[0]
+        if flat is not None:
+            per_sample = [[flat[k, self.S * o:self.S * (o + m)].reshape(self.S, m) if m else None
+                           for o, m in zip(self.grid_offsets, self.grid_points)] for k in range(n)]
+            out['gamma_grid'] = per_sample if sample is None else per_sample[0]
+        return out
+
+    def grid_info(self):
+        """(grid points on the handle, device milliseconds of the last grid pass)."""
+        m, ms = C.c_int64(), C.c_double()
+        _lib.check(_lib.load().gbrs_hmm_grid_info(self._h, C.byref(m), C.byref(ms)))
+        return m.value, ms.value
+
     def info(self):
         inf = _lib.HmmInfo()
         _lib.check(_lib.load().gbrs_hmm_info(self._h, C.byref(inf)))
         return inf
+
+
+def _raise_grid_error(lib, status):
+    """The exceptions `gbrs interpolate` raises for the same grid: interp1d's ValueError, numpy's IndexError."""
+    if status == _lib.GBRS_ERR_INVALID:
+        message = lib.gbrs_last_error()
+        if b'interpolation range' in message:
+            raise ValueError(message.decode())
+        if b'is out of bounds' in message:
+            raise IndexError(message.decode())
+    _lib.check(status)
+
+
+def grid_knots(gene_positions, grid):
+    """(knots, gene of each knot) of one chromosome, as the grid pass uses them: [0.0, gene positions..., last grid
+    point + 1.0] sorted stably, the two end knots carrying the first and the last gene's column
+    (postproc.interpolate_arrays).  Host code only."""
+    where = np.ascontiguousarray(gene_positions, dtype=np.float64)
+    points = np.ascontiguousarray(grid, dtype=np.float64)
+    knots = np.empty(len(where) + 2)
+    gene = np.empty(len(where) + 2, dtype=np.int32)
+    lib = _lib.load()
+    _raise_grid_error(lib, lib.gbrs_grid_knots(len(where), _lib.ptr(where), len(points), _lib.ptr(points),
+                                               _lib.ptr(knots), _lib.ptr(gene)))
+    return knots, gene
 
 
 def get_chromosome_info(data_dir=None):
@@ -185,21 +258,41 @@ def read_gene_order(gpos_file):
     return order
 
 
+def read_gene_positions(gpos_file):
+    """{chromosome: positions of its genes in genome order, float64} from `ref.gene_pos.ordered.npz`: the second field
+    of its (gene id, position) records, which is what `gbrs interpolate` takes (gbrs_utils.py:664)."""
+    where = {}
+    z = FastNpz(gpos_file)
+    for c in z.files:
+        a = z[c]
+        if a.dtype.names:
+            where[c] = a[a.dtype.names[1]].astype(np.float64)
+        else:
+            where[c] = np.asarray([record[1] for record in a], dtype=np.float64)
+    z.close()
+    return where
+
+
 class ReconstructContext:
     """Everything `gbrs reconstruct` reads that does not depend on the sample - genome order, gene order, transition
-    tables, specificity blocks - and the device handle that holds the tables.  One command builds one and drops it; a
-    resident process (gbrs_amd.worker) keeps it across samples, so that a sample costs its expression rows only."""
+    tables, specificity blocks, and with `grid_file` the marker grid - and the device handle that holds the tables.
+    One command builds one and drops it; a resident process (gbrs_amd.worker) keeps it across samples, so that a sample
+    costs its expression rows only."""
 
-    def __init__(self, tprob_file, avec_file=None, gpos_file=None, device=0):
+    def __init__(self, tprob_file, avec_file=None, gpos_file=None, device=0, grid_file=None):
         data_dir = os.getenv('GBRS_DATA', '.')
         self.tprob_file = tprob_file
         self.avec_file = avec_file or os.path.join(data_dir, 'avecs.npz')
         self.gpos_file = gpos_file or os.path.join(data_dir, 'ref.gene_pos.ordered.npz')
+        self.grid_file = grid_file
         self.device = device
         self.data_dir = data_dir
         self.loaded = False
         self.hmm = None
         self.num_haps = None
+        self.grid = None                  # {chromosome: positions} in the grid file's order
+        self.grid_uploads = 0             # times the grid went to a device handle
+        self.grid_slices = {}             # chromosome on the handle and on the grid -> (handle index, first dosage row, rows)
 
     def load(self, marks=None):
         """The files (the big transition tables inflate on the library's threads while the small files are parsed)."""
@@ -216,6 +309,11 @@ class ReconstructContext:
         self.avecs = FastNpz(self.avec_file)
         logger.info(f'Loading gene meta data: {self.gpos_file}')
         self.gene_order = read_gene_order(self.gpos_file)
+        if self.grid_file is not None:
+            from .postproc import read_grid
+            logger.info(f'Loading grid file: {self.grid_file}')
+            self.grid = read_grid(self.grid_file)
+            self.gene_positions = read_gene_positions(self.gpos_file)
         self._tables_pending, self._reader = tables_pending, reader
         self.loaded = True
 
@@ -244,59 +342,142 @@ class ReconstructContext:
             self.avecs.close()
         return self._spec
 
+    def handle(self, num_haps):
+        """(the device handle for `num_haps` founders, whether this call made it).  A new handle gets the transition
+        tables and, with a grid file, the grid; the caller passes the specificity blocks with its first samples."""
+        first_use = self.hmm is None or self.hmm.H != num_haps
+        if first_use:
+            tables = self.tables()
+            self.close()
+            self.hmm = DiplotypeHMM(num_haps, self.chroms, [len(self.gene_order[c]) for c in self.chroms], tables,
+                                    device=self.device)
+            if self.grid is not None:
+                self.hmm.set_grid(self.gene_positions, {c: self.grid[c] for c in self.chroms if c in self.grid})
+                self.grid_uploads += 1
+                self.grid_slices = {c: (k, self.hmm.grid_offsets[k], self.hmm.grid_points[k])
+                                    for k, c in enumerate(self.chroms) if c in self.grid}
+        return self.hmm, first_use
+
     def close(self):
         if self.hmm is not None:
             self.hmm.close()
             self.hmm = None
 
 
+def _expression_rows(ctx, expr_row, expr_table, num_haps):
+    """A sample's TPM rows per chromosome of the context, in gene order.  KeyError: a gene without TPM."""
+    rows = []
+    for c in ctx.chroms:
+        ids = ctx.gene_order[c]
+        r = expr_table[[expr_row[g] for g in ids]] if len(ids) else np.zeros((0, num_haps))
+        rows.append(np.ascontiguousarray(r, dtype=np.float64).reshape(len(ids), num_haps))
+    return rows
+
+
+def _collect(ctx, hmm, sample, diplotypes):
+    """(posterior, ordered path names, calls) of one sample of the last run, by chromosome name / gene id."""
+    posterior, path_names, calls = {}, {}, {}
+    for k, c in enumerate(ctx.chroms):
+        res = hmm.get(k, sample=sample)
+        posterior[c] = res['gamma']
+        path_names[c] = [diplotypes[s] for s in res['states']]
+        calls.update((gid, diplotypes[s]) for gid, s in zip(ctx.gene_order[c], res['calls']) if s >= 0)
+    return posterior, path_names, calls
+
+
+def _save_reconstruction(stem, posterior, path_names, calls, threads=None):
+    """The three files of `gbrs reconstruct` (gbrs_utils.py:600-609)."""
+    out_calls, out_post, out_path = f'{stem}.genotypes.tsv', f'{stem}.genoprobs.npz', f'{stem}.genotypes.npz'
+    logger.info(f'Saving Reconstructed Genotype Probabilities: {out_post}')
+    savez_compressed(out_post, posterior, threads=threads)
+    logger.info(f'Saving Reconstructed Genotypes: {out_calls}')
+    with open(out_calls, 'w') as out:
+        out.write('#Gene_ID\tDiplotype\n')
+        out.writelines(f'{gid}\t{calls[gid]}\n' for gid in sorted(calls))
+    logger.info(f'Saving Reconstructed Ordered Genotypes: {out_path}')
+    savez_compressed(out_path, {c: np.asarray(v) for c, v in path_names.items()}, threads=threads)
+
+
+def write_dosage_table(path, rows, haplotypes):
+    """The text np.savetxt(path, rows, fmt='%.6f', delimiter='\\t', header='\\t'.join(haplotypes)) writes, which is
+    `gbrs export`'s file (gbrs_utils.py:931), byte for byte: one format operation for the table instead of one per row
+    (64,000 rows per sample, and a cohort's samples are written side by side)."""
+    rows = np.asarray(rows, dtype=np.float64)
+    line = '\t'.join(['%.6f'] * rows.shape[1]) + '\n'
+    with open(path, 'w') as fh:
+        fh.write('# ' + '\t'.join(haplotypes) + '\n')
+        fh.write((line * rows.shape[0]) % tuple(rows.ravel().tolist()))
+
+
+def _save_grid(stem, ctx, haplotypes, dosage, gamma_grid, threads=None):
+    """A sample's grid files.  `<stem>.interpolated.genoprobs.npz` (only with gamma_grid): what `gbrs interpolate`
+    saves - the grid's chromosomes that have gene positions and posteriors, in grid order.
+    `<stem>.interpolated.genoprobs.tsv`: what `gbrs export -s <haplotypes>` writes from that file, rows in the grid
+    file's order.  A grid chromosome without posteriors ends `export` with a KeyError; so it does here, after the
+    .npz."""
+    slices = ctx.grid_slices
+    on_grid = [c for c in ctx.grid if c in slices]
+    if gamma_grid is not None:
+        out_npz = f'{stem}.interpolated.genoprobs.npz'
+        logger.info(f'Saving interpolate probability file: {out_npz}')
+        savez_compressed(out_npz, {c: gamma_grid[slices[c][0]] for c in on_grid}, threads=threads)
+    for c in ctx.grid:
+        if c not in slices:
+            raise KeyError(f'{c} is not a file in the archive')
+    rows = np.concatenate([dosage[slices[c][1]:slices[c][1] + slices[c][2]] for c in on_grid], axis=0) \
+        if on_grid else np.zeros((0, len(haplotypes)))
+    out_tsv = f'{stem}.interpolated.genoprobs.tsv'
+    logger.info(f'Saving GBRS quant format: {out_tsv}')
+    write_dosage_table(out_tsv, rows, haplotypes)
+
+
 def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gpos_file: str = None,
                 expr_threshold: float = 1.5, sigma: float = 0.12, outbase: str = None,
-                device: int = 0, stage_times: dict = None, context: ReconstructContext = None) -> None:
+                device: int = 0, stage_times: dict = None, context: ReconstructContext = None,
+                grid_file: str = None, grid_genoprobs: bool = False) -> None:
     """`gbrs reconstruct`: diplotype posteriors and Viterbi calls along every chromosome from
     gene-level TPMs.  Same inputs, defaults and three output files as gbrs_utils.reconstruct
     (gbrs_utils.py:382-609); the emission model and the three recursions run on the device.
     `stage_times` (optional dict) receives wall-clock seconds per stage.  `context` (extension,
     gbrs_amd.worker): the sample-independent inputs and the device handle of an earlier call on the same
     tables - the transition and specificity tables then stay where they are and the sample moves its expression
-    rows only."""
+    rows only.  `grid_file` (extension; with a context, the context's): the posteriors also go onto the marker grid
+    on the device and `<outbase>.interpolated.genoprobs.tsv` holds the founder dosages `gbrs export` would write after
+    `gbrs interpolate`; with `grid_genoprobs` `<outbase>.interpolated.genoprobs.npz` holds what `gbrs interpolate`
+    writes."""
     clock = time.perf_counter
     marks = stage_times if stage_times is not None else {}
     stem = 'gbrs.reconstructed' if outbase is None else outbase
-    out_calls, out_post, out_path = f'{stem}.genotypes.tsv', f'{stem}.genoprobs.npz', f'{stem}.genotypes.npz'
-    ctx = context if context is not None else ReconstructContext(tprob_file, avec_file, gpos_file, device)
+    ctx = context if context is not None else ReconstructContext(tprob_file, avec_file, gpos_file, device, grid_file)
     for label, value in (('Expression File', expression_file), ('Transition Probabilities File', tprob_file),
                          ('Alignment Specificity File', ctx.avec_file), ('Gene Position File', ctx.gpos_file),
                          ('Expression Threshold', expr_threshold), ('Sigma', sigma), ('Outbase', outbase)):
         logger.info(f'{label}: {value}')
+    if ctx.grid_file is not None:
+        logger.info(f'Grid File: {ctx.grid_file}')
 
     _lib.warm_up_device_async(device)      # HIP start-up overlaps with reading the files
     t0 = clock()
     # the transition tables are the big read (0.4 GB of deflate streams at DO size): it starts on the library's
     # threads and is collected when the tables are needed, after the small files have been parsed
     ctx.load()
-    chroms, gene_order = ctx.chroms, ctx.gene_order
+    chroms = ctx.chroms
     logger.info(f'Loading expression level data: {expression_file}')
     haplotypes, expr_row, expr_table = read_gene_tpm(expression_file)
     num_haps = len(haplotypes)
     diplotypes = [a + b for a, b in combinations_with_replacement(haplotypes, 2)]
-    rows = []
-    for c in chroms:
-        ids = gene_order[c]
-        r = expr_table[[expr_row[g] for g in ids]] if len(ids) else np.zeros((0, num_haps))   # KeyError: gene without TPM
-        rows.append(np.ascontiguousarray(r, dtype=np.float64).reshape(len(ids), num_haps))
+    rows = _expression_rows(ctx, expr_row, expr_table, num_haps)
     first_use = ctx.hmm is None or ctx.hmm.H != num_haps
     spec = ctx.specificity(num_haps) if first_use else None
-    tables = ctx.tables() if first_use else None
+    if first_use:
+        ctx.tables()
     marks['load'] = clock() - t0
 
     posterior, path_names, calls = {}, {}, {}
+    on_grid = None
     if chroms:
         t0 = clock()
-        if first_use:
-            ctx.close()
-            ctx.hmm = DiplotypeHMM(num_haps, chroms, [len(gene_order[c]) for c in chroms], tables, device=device)
-        hmm = ctx.hmm
+        hmm, _ = ctx.handle(num_haps)
         marks['tables_to_device'] = clock() - t0
         t0 = clock()
         logger.info('Getting forward probability')
@@ -307,23 +488,146 @@ def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gp
         logger.info('Getting backward probability')
         hmm.run()
         logger.info('Getting forward-backward probability')
-        for k, c in enumerate(chroms):
-            res = hmm.get(k)
-            posterior[c] = res['gamma']
-            path_names[c] = [diplotypes[s] for s in res['states']]
-            calls.update((gid, diplotypes[s]) for gid, s in zip(gene_order[c], res['calls']) if s >= 0)
-        if context is None:
+        posterior, path_names, calls = _collect(ctx, hmm, 0, diplotypes)
+        if context is None and ctx.grid is None:
             ctx.close()
         marks['hmm'] = clock() - t0
+        if ctx.grid is not None:
+            t0 = clock()
+            logger.info('Converting genotype probability on the grid')
+            on_grid = hmm.grid(sample=0, want=('dosage', 'gamma_grid') if grid_genoprobs else ('dosage',))
+            if context is None:
+                ctx.close()
+            marks['grid'] = clock() - t0
+    elif ctx.grid is not None:
+        on_grid = {'dosage': np.zeros((0, num_haps)), 'gamma_grid': [] if grid_genoprobs else None}
 
     t0 = clock()
-    logger.info(f'Saving Reconstructed Genotype Probabilities: {out_post}')
-    savez_compressed(out_post, posterior)
-    logger.info(f'Saving Reconstructed Genotypes: {out_calls}')
-    with open(out_calls, 'w') as out:
-        out.write('#Gene_ID\tDiplotype\n')
-        out.writelines(f'{gid}\t{calls[gid]}\n' for gid in sorted(calls))
-    logger.info(f'Saving Reconstructed Ordered Genotypes: {out_path}')
-    savez_compressed(out_path, {c: np.asarray(v) for c, v in path_names.items()})
+    _save_reconstruction(stem, posterior, path_names, calls)
+    if on_grid is not None:
+        _save_grid(stem, ctx, haplotypes, on_grid['dosage'], on_grid.get('gamma_grid'))
     marks['save'] = clock() - t0
     logger.info('Done')
+
+
+def read_sample_file(sample_file):
+    """[(genes.tpm, outbase)] from a file of tab separated lines `genes.tpm<TAB>outbase`; blank lines and lines that
+    start with # are skipped."""
+    samples = []
+    with open(sample_file) as fh:
+        for number, line in enumerate(fh, 1):
+            line = line.strip()
+            if not line or line.startswith('#'):
+                continue
+            fields = line.split('\t')
+            if len(fields) != 2:
+                raise RuntimeError(f'{sample_file}, line {number}: expected genes.tpm<TAB>outbase')
+            samples.append((fields[0], fields[1]))
+    return samples
+
+
+def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str = None, gpos_file: str = None,
+                     expr_threshold: float = 1.5, sigma: float = 0.12, device: int = 0, batch_size: int = 64,
+                     grid_file: str = None, grid_genoprobs: bool = False, stage_times: dict = None,
+                     context: ReconstructContext = None) -> list:
+    """`gbrs reconstruct` for a cohort whose genes.tpm files exist (extension): one context, the tables on the device
+    once, the samples through the HMM in launches of up to `batch_size`, and with `grid_file` one grid pass per launch.
+    Every sample gets the files the single-sample call writes for its outbase.  All samples must carry the same
+    haplotype header (RuntimeError before anything runs otherwise).  A sample whose file cannot be read or lacks a gene
+    is logged and left out, and the others go on.  Returns one dict per sample: its outbase and, if it failed,
+    `error`."""
+    clock = time.perf_counter
+    marks = stage_times if stage_times is not None else {}
+    if len(expression_files) != len(outbases):
+        raise ValueError('one outbase per expression file')
+    if batch_size < 1:
+        raise ValueError('batch_size must be at least 1')
+    done = [{'outbase': o} for o in outbases]
+
+    def failed(k, error):
+        logger.error(f'{expression_files[k]}: {error}')
+        done[k]['error'] = f'{type(error).__name__}: {error}'
+
+    headers = {}
+    for k, f in enumerate(expression_files):
+        try:
+            with open(f) as fh:
+                headers[k] = tuple(fh.readline().rstrip().split('\t')[1:-1])
+        except OSError as e:
+            failed(k, e)
+    if len(set(headers.values())) > 1:
+        raise RuntimeError('the samples do not carry the same haplotypes: ' +
+                           ' / '.join(','.join(h) for h in sorted(set(headers.values()))))
+    if not headers:
+        return done
+    haplotypes = list(next(iter(headers.values())))
+    num_haps = len(haplotypes)
+    diplotypes = [a + b for a, b in combinations_with_replacement(haplotypes, 2)]
+    ctx = context if context is not None else ReconstructContext(tprob_file, avec_file, gpos_file, device, grid_file)
+    _lib.warm_up_device_async(device)
+    t0 = clock()
+    ctx.load()
+    marks['load'] = clock() - t0
+    for key in ('read', 'hmm', 'grid', 'save'):
+        marks[key] = 0.0
+    from concurrent.futures import ThreadPoolExecutor
+    writers = ThreadPoolExecutor(max_workers=min(16, batch_size))
+    pending = []
+
+    def save(k, results, on_grid):
+        _save_reconstruction(outbases[k], *results, threads=1)
+        if on_grid is not None:
+            _save_grid(outbases[k], ctx, haplotypes, on_grid[0], on_grid[1], threads=1)
+
+    try:
+        order = sorted(headers)
+        for lo in range(0, len(order), batch_size):
+            t0 = clock()
+            members, rows = [], []
+            for k in order[lo:lo + batch_size]:
+                try:
+                    _, expr_row, expr_table = read_gene_tpm(expression_files[k])
+                    rows.append(_expression_rows(ctx, expr_row, expr_table, num_haps))
+                    members.append(k)
+                except Exception as e:   # noqa: BLE001 - one bad sample does not end the cohort
+                    failed(k, e)
+            marks['read'] += clock() - t0
+            if not members or not ctx.chroms:
+                for k in members:
+                    pending.append((k, writers.submit(save, k, ({}, {}, {}), None)))
+                continue
+            t0 = clock()
+            first_use = ctx.hmm is None or ctx.hmm.H != num_haps
+            spec = ctx.specificity(num_haps) if first_use else None
+            hmm, _ = ctx.handle(num_haps)
+            stacked = [np.stack([r[ci] for r in rows]) for ci in range(len(ctx.chroms))]
+            if first_use:
+                hmm.set_expression(stacked, [x[0] for x in spec], [x[1] for x in spec], expr_threshold, sigma)
+            else:
+                hmm.set_expression(stacked, expr_threshold=expr_threshold, sigma=sigma)
+            hmm.run()
+            results = [_collect(ctx, hmm, s, diplotypes) for s in range(len(members))]
+            marks['hmm'] += clock() - t0
+            on_grid = None
+            if ctx.grid is not None:
+                t0 = clock()
+                on_grid = hmm.grid(want=('dosage', 'gamma_grid') if grid_genoprobs else ('dosage',))
+                marks['grid'] += clock() - t0
+            t0 = clock()
+            for s, k in enumerate(members):
+                grid_of = None if on_grid is None else (on_grid['dosage'][s], on_grid['gamma_grid'][s] if grid_genoprobs else None)
+                pending.append((k, writers.submit(save, k, results[s], grid_of)))
+            marks['save'] += clock() - t0
+        t0 = clock()
+        for k, job in pending:
+            try:
+                job.result()
+            except Exception as e:   # noqa: BLE001
+                failed(k, e)
+        marks['save'] += clock() - t0
+    finally:
+        writers.shutdown(wait=True)
+        if context is None:
+            ctx.close()
+    logger.info('Done')
+    return done

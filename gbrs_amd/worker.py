@@ -9,7 +9,9 @@ order; gbrs_utils.py:420-447) for every sample.  The three steps are the very fu
     python -m gbrs_amd worker --jobs jobs.json --devices 0,1,2,3,4,5,6,7     # one worker process per GPU, samples dealt round-robin
 
 jobs.json: a list of objects {"alignment_file", "outbase", "tprob_file", and optionally "group_file", "length_file",
-"avec_file", "gpos_file", "expr_threshold", "sigma", "pseudocount", "max_iters", "tolerance", "diploid": true|false};
+"avec_file", "gpos_file", "grid_file", "grid_genoprobs", "expr_threshold", "sigma", "pseudocount", "max_iters", "tolerance",
+"diploid": true|false}; with "grid_file" the sample's reconstruction also leaves `<outbase>.interpolated.genoprobs.tsv`
+(and with "grid_genoprobs" the `.npz`), see `gbrs reconstruct --grid-file`;
 the stage times of every sample are printed as one JSON line per sample.
 """
 from __future__ import annotations
@@ -33,11 +35,12 @@ class SampleWorker:
 
     def _context(self, job):
         from .hmm import ReconstructContext
-        key = (job['tprob_file'], job.get('avec_file'), job.get('gpos_file'))
+        key = (job['tprob_file'], job.get('avec_file'), job.get('gpos_file'), job.get('grid_file'))
         if key != self._ctx_key:
             if self._ctx is not None:
                 self._ctx.close()
-            self._ctx = ReconstructContext(job['tprob_file'], job.get('avec_file'), job.get('gpos_file'), self.device)
+            self._ctx = ReconstructContext(job['tprob_file'], job.get('avec_file'), job.get('gpos_file'), self.device,
+                                           job.get('grid_file'))
             self._ctx_key = key
         return self._ctx
 
@@ -77,7 +80,8 @@ class SampleWorker:
         reconstruct(expression_file=f"{job['outbase']}.multiway.genes.tpm", tprob_file=job['tprob_file'],
                     avec_file=job.get('avec_file'), gpos_file=job.get('gpos_file'),
                     expr_threshold=job.get('expr_threshold', 1.5), sigma=job.get('sigma', 0.12),
-                    outbase=job['outbase'], device=self.device, stage_times=st, context=self._context(job))
+                    outbase=job['outbase'], device=self.device, stage_times=st, context=self._context(job),
+                    grid_file=job.get('grid_file'), grid_genoprobs=bool(job.get('grid_genoprobs', False)))
         out['reconstruct'] = dict(st, wall=clock() - t0)
         if job.get('diploid', True):
             st = {}

@@ -681,6 +681,37 @@ typedef struct gbrs_hmm_info {
 } gbrs_hmm_info_t;
 int gbrs_hmm_info(gbrs_hmm_t *hmm, gbrs_hmm_info_t *info);
 
+/* Grid pass: `gbrs interpolate` + `gbrs export` on the posteriors the last run left on the device.
+ *
+ * The knots of one chromosome as `gbrs interpolate` hands them to interp1d (gbrs_utils.py:664-688), host only:
+ * [0.0, gene_pos..., grid[n_grid-1] + 1.0] sorted stably (n_genes + 2 knots) and, per knot, the gene whose posterior
+ * column it carries (the two end knots repeat the first and the last gene).  A grid point outside the knots fails with
+ * scipy's ValueError text, n_genes < 1 with the IndexError the command would raise; both GBRS_ERR_INVALID. */
+int gbrs_grid_knots(int n_genes, const double *gene_pos, int n_grid, const double *grid, double *knots,
+                    int32_t *knot_gene);
+
+/* The marker grid of the handle; sample independent, it stays on the device like the specificity blocks.
+ *   n_grid[c]    grid points of handle chromosome c, 0: the chromosome is not on the grid (grid[c], gene_pos[c] unused)
+ *   grid[c]      double[n_grid[c]] positions in file order
+ *   n_pos[c]     number of gene positions given: must equal n_genes[c] of the handle
+ *   gene_pos[c]  double[n_pos[c]] gene positions in genome order
+ * On failure the handle keeps the grid it had. */
+int gbrs_hmm_set_grid(gbrs_hmm_t *hmm, const int32_t *n_pos, const double *const *gene_pos, const int32_t *n_grid,
+                      const double *const *grid);
+
+/* One device pass over every (sample, chromosome on the grid) of the last run.  sample = -1: all n samples of the run,
+ * else that one (n = 1).  M = sum of n_grid[c].  Both outputs are nullable:
+ *   dosage      double[n][M][H]   founder dosages (the rows `gbrs export` writes), the chromosomes' grid points in
+ *                                 handle order; one device-to-host copy for all samples
+ *   gamma_grid  double[n][S * M]  per sample the (S x n_grid[c]) C-order blocks `gbrs interpolate` saves, one after the
+ *                                 other in handle order
+ * With dosage alone the interpolated states never reach device memory.  GBRS_ERR_STATE before the first run,
+ * GBRS_ERR_INVALID without a grid or for a sample out of range; the outputs are untouched on failure. */
+int gbrs_hmm_grid(gbrs_hmm_t *hmm, int sample, double *dosage, double *gamma_grid);
+
+/* M of the handle's grid (0 without one) and the device time of the last gbrs_hmm_grid kernel; both nullable. */
+int gbrs_hmm_grid_info(gbrs_hmm_t *hmm, int64_t *n_points, double *last_ms);
+
 int gbrs_hmm_destroy(gbrs_hmm_t *hmm);
 
 /* `gbrs interpolate` numeric body (gbrs/gbrs_utils.py:684-688): the rows of y (S x n_points, C

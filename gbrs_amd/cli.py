@@ -81,6 +81,11 @@ def build_parser():
                         '`gbrs export` writes after `gbrs interpolate`, from the posteriors on the device')
     r.add_argument('--grid-genoprobs', action='store_true',
                    help='with --grid-file: also write <outbase>.interpolated.genoprobs.npz, the file of `gbrs interpolate`')
+    r.add_argument('--sim-geno', type=int, default=None, metavar='K',
+                   help='(extension) K >= 1 diplotype paths per chromosome drawn from the joint posterior on the device: '
+                        'writes <outbase>.sim_geno.npz (state indices, K x genes per chromosome) and '
+                        '<outbase>.sim_geno.crossovers.tsv (founder changes of the draws beside the Viterbi path\'s)')
+    r.add_argument('--sim-geno-seed', type=int, default=0, metavar='S', help='with --sim-geno: seed of the draws (default 0)')
     r.add_argument('-t', '--tprob-file', required=True, type=_existing)
     r.add_argument('-x', '--avec-file', type=_existing, default=None)
     r.add_argument('-g', '--gpos-file', type=_existing, default=None)
@@ -230,6 +235,9 @@ def main(argv=None) -> int:
                 raise RuntimeError('-M, --multiread-model must be one of 1, 2, 3, or 4')
             from .quantify import check_bootstrap_args
             check_bootstrap_args(args.bootstrap, args.merge_identical_rows, args.gpus)
+        if args.command == 'reconstruct':
+            from .hmm import check_sim_geno_args
+            check_sim_geno_args(args.sim_geno, args.sim_geno_seed)
         if args.command == 'quantify' and args.gpus is not None:
             # N child processes, one per rank; this process opens no device
             from .sharded import launch
@@ -340,14 +348,15 @@ def main(argv=None) -> int:
             reconstruct_many([f for f, _ in samples], [o for _, o in samples], tprob_file=args.tprob_file,
                              avec_file=args.avec_file, gpos_file=args.gpos_file, expr_threshold=args.expr_threshold,
                              sigma=args.sigma, device=args.device, batch_size=args.batch_size, grid_file=args.grid_file,
-                             grid_genoprobs=args.grid_genoprobs, stage_times=stages)
+                             grid_genoprobs=args.grid_genoprobs, stage_times=stages, sim_geno=args.sim_geno,
+                             sim_geno_seed=args.sim_geno_seed)
         else:
             from .hmm import reconstruct
             reconstruct(expression_file=args.expression_file, tprob_file=args.tprob_file,
                         avec_file=args.avec_file, gpos_file=args.gpos_file,
                         expr_threshold=args.expr_threshold, sigma=args.sigma, outbase=args.outbase,
                         device=args.device, stage_times=stages, grid_file=args.grid_file,
-                        grid_genoprobs=args.grid_genoprobs)
+                        grid_genoprobs=args.grid_genoprobs, sim_geno=args.sim_geno, sim_geno_seed=args.sim_geno_seed)
     except Exception as e:   # noqa: BLE001 - mirror of the reference's catch-all
         failure = e
         if logger.level == logging.DEBUG:

@@ -7,17 +7,7 @@
 // so w is Poisson(c_r) up to the 2^-32 grain of the table, an integer, and a function of (seed, b, r, c_r) alone - however
 // the c_r draws of a row are split over lanes, the same numbers are added.
 
-__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int round = 0; round < 10; ++round) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
+#include "philox.h"      // philox4x32_10, shared with hmm_sample.inc
 
 // P(u): how many of the 13 thresholds u reaches
 __device__ __forceinline__ uint32_t poisson1_by_inversion(uint32_t u) {

@@ -2484,6 +2484,7 @@ __global__ void dosage_kernel(int H, int S, int64_t rows, const double *__restri
 }
 
 #include "hmm_grid.inc"
+#include "hmm_sample.inc"
 
 }  // namespace gbrs
 
@@ -2559,6 +2560,12 @@ struct gbrs_hmm {
     DevBuf<double> grid_knot_x, grid_x, grid_dosage, grid_gamma;
     DevBuf<int32_t> grid_knot_gene;
     double t_grid = 0;
+    // Path draws (hmm_sample.inc): the change table is made on the first call; the other buffers hold one slab of draws
+    DevBuf<uint8_t> smp_change_tab, smp_cols, smp_paths;
+    DevBuf<int32_t> smp_changes;
+    DevBuf<uint32_t> smp_streams;
+    DevBuf<unsigned long long> smp_degenerate;
+    double t_sample = 0;
 };
 
 namespace {
@@ -3766,6 +3773,87 @@ int gbrs_hmm_grid_info(gbrs_hmm_t *h, int64_t *n_points, double *last_ms) {
     if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
     if (n_points) *n_points = h->have_grid ? h->grid_points : 0;
     if (last_ms) *last_ms = h->t_grid;
+    return GBRS_OK;
+}
+
+int gbrs_hmm_sample_paths(gbrs_hmm_t *h, int sample, int n_draws, uint64_t seed, const uint32_t *streams, uint8_t *paths,
+                          int32_t *changes, uint64_t *degenerate) {
+    RoctxRange roctx_range("gbrs_hmm_sample_paths");
+    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (!h->ran) return fail(GBRS_ERR_STATE, "run() has not been called");
+    if (n_draws < 1) return fail(GBRS_ERR_INVALID, "n_draws must be at least 1");
+    if (sample < -1 || sample >= h->n_samples) return fail(GBRS_ERR_INVALID, "sample out of range");
+    if (!paths) return fail(GBRS_ERR_INVALID, "paths is NULL");
+    GBRS_TRY(select_device(h->device));
+    GBRS_TRY(hmm_make_logs(h));
+    const int S = h->S, n = sample < 0 ? h->n_samples : 1, sample0 = std::max(sample, 0);
+    const size_t G = (size_t)h->total_genes;
+    // draws per slab: two byte images of n x slab x G (gene-major as drawn, draw-major as returned) within 1 GiB, whole
+    // workgroups of draws where that many fit; GBRS_TUNING_SAMPLE_SLAB names a count instead.  The draws are keyed by their
+    // number, so the cut changes no value.
+    size_t slab = std::max<size_t>(((size_t)1 << 30) / (2 * (size_t)n * G), 1);
+    if (slab >= SAMPLE_BLOCK) slab -= slab % SAMPLE_BLOCK;
+    if (const char *e = std::getenv("GBRS_TUNING_SAMPLE_SLAB"); e && std::atoi(e) > 0) slab = (size_t)std::atoi(e);
+    slab = std::min<size_t>(slab, (size_t)n_draws);
+    if (!h->smp_change_tab.p) {
+        const std::vector<uint8_t> tab = sample_change_table(h->H);
+        GBRS_TRY(h->smp_change_tab.alloc(tab.size()));
+        GBRS_HIP_CHECK(hipMemcpy(h->smp_change_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice));
+    }
+    if (h->smp_cols.n < (size_t)n * slab * G) GBRS_TRY(h->smp_cols.alloc((size_t)n * slab * G));
+    if (h->smp_paths.n < (size_t)n * slab * G) GBRS_TRY(h->smp_paths.alloc((size_t)n * slab * G));
+    if (changes && h->smp_changes.n < (size_t)n * slab * h->n_chrom) GBRS_TRY(h->smp_changes.alloc((size_t)n * slab * h->n_chrom));
+    if (h->smp_streams.n < (size_t)n) GBRS_TRY(h->smp_streams.alloc((size_t)n));
+    if (!h->smp_degenerate.p) GBRS_TRY(h->smp_degenerate.alloc(1));
+    std::vector<uint32_t> ids((size_t)n);
+    for (int k = 0; k < n; ++k) ids[k] = streams ? streams[k] : (uint32_t)(sample0 + k);
+    GBRS_HIP_CHECK(hipMemcpy(h->smp_streams.p, ids.data(), ids.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    GBRS_HIP_CHECK(hipMemsetAsync(h->smp_degenerate.p, 0, sizeof(unsigned long long), h->stream));
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    const size_t lds = sample_lds(S);
+    h->t_sample = 0;
+    for (size_t d0 = 0; d0 < (size_t)n_draws; d0 += slab) {
+        const int ks = (int)std::min<size_t>(slab, (size_t)n_draws - d0);
+        const dim3 grid((unsigned)((ks + SAMPLE_BLOCK - 1) / SAMPLE_BLOCK), (unsigned)h->n_chrom, (unsigned)n);
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, dim3(SAMPLE_BLOCK), lds, h->stream, S, h->n_chrom, h->total_genes, sample0,
+                               (uint32_t)d0, ks, h->d_chroms.p, h->d_order.p, h->alpha.p, h->tprob.p, h->smp_change_tab.p,
+                               h->smp_streams.p, k0, k1, h->smp_cols.p, changes ? h->smp_changes.p : nullptr,
+                               h->smp_degenerate.p);
+        };
+        GBRS_HIP_CHECK(hipEventRecord(h->ev[0], h->stream));
+        if (sample_table_in_lds(S)) launch(sample_paths_kernel<true>);
+        else launch(sample_paths_kernel<false>);
+        hipLaunchKernelGGL(sample_transpose_kernel, dim3((unsigned)((G + 63) / 64), (unsigned)((ks + 63) / 64), (unsigned)n),
+                           dim3(256), 0, h->stream, h->total_genes, ks, h->smp_cols.p, h->smp_paths.p);
+        GBRS_HIP_CHECK(hipEventRecord(h->ev[1], h->stream));
+        GBRS_HIP_CHECK(hipGetLastError());
+        GBRS_HIP_CHECK(hipStreamSynchronize(h->stream));
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, h->ev[0], h->ev[1]) == hipSuccess) h->t_sample += ms;
+        for (int k = 0; k < n; ++k) {       // a sample's draws of this slab are contiguous on both sides
+            GBRS_HIP_CHECK(hipMemcpy(paths + ((size_t)k * n_draws + d0) * G, h->smp_paths.p + (size_t)k * ks * G,
+                                     (size_t)ks * G, hipMemcpyDeviceToHost));
+            if (changes)
+                GBRS_HIP_CHECK(hipMemcpy(changes + ((size_t)k * n_draws + d0) * h->n_chrom,
+                                         h->smp_changes.p + (size_t)k * ks * h->n_chrom,
+                                         (size_t)ks * h->n_chrom * sizeof(int32_t), hipMemcpyDeviceToHost));
+        }
+    }
+    if (degenerate) {
+        unsigned long long count = 0;
+        GBRS_HIP_CHECK(hipMemcpy(&count, h->smp_degenerate.p, sizeof(count), hipMemcpyDeviceToHost));
+        *degenerate = count;
+    }
+    return GBRS_OK;
+}
+
+int gbrs_hmm_sample_info(gbrs_hmm_t *h, double *last_ms, uint64_t *device_bytes) {
+    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (last_ms) *last_ms = h->t_sample;
+    if (device_bytes)
+        *device_bytes = h->smp_change_tab.bytes() + h->smp_cols.bytes() + h->smp_paths.bytes() + h->smp_changes.bytes() +
+                        h->smp_streams.bytes() + h->smp_degenerate.bytes();
     return GBRS_OK;
 }
 

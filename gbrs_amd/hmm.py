@@ -162,6 +162,39 @@ class DiplotypeHMM:
         _lib.check(_lib.load().gbrs_hmm_grid_info(self._h, C.byref(m), C.byref(ms)))
         return m.value, ms.value
 
+    def sample_paths(self, n_draws, seed=0, sample=None, streams=None):
+        """Diplotype paths drawn from the joint posterior of the last run, one device pass per slab of
+        draws.  sample=None: every sample of the run (n of them); an index: that sample, without the leading axis.
+        streams: one 32-bit id per sample of the call (default: the sample's index in the run); a sample's draws depend
+        on (seed, its stream), not on where in a batch it ran.  Returns `paths`, per chromosome a uint8 array
+        (n?, n_draws, n_c) of state indices; `changes`, int32 (n?, n_draws, n_chrom) founder changes along each draw;
+        `degenerate`, the decisions that fell back to the argmax."""
+        n = self.n_samples if sample is None else 1
+        n_draws = int(n_draws)
+        ids = None
+        if streams is not None:
+            ids = np.ascontiguousarray(streams, dtype=np.uint32).reshape(-1)
+            if len(ids) != n:
+                raise ValueError(f'{len(ids)} streams for {n} samples')
+        total = int(self.n_genes.sum())
+        flat = np.empty((n, max(n_draws, 0), total), dtype=np.uint8)
+        changes = np.empty((n, max(n_draws, 0), len(self.chroms)), dtype=np.int32)
+        degenerate = C.c_uint64(0)
+        _lib.check(_lib.load().gbrs_hmm_sample_paths(self._h, -1 if sample is None else int(sample), n_draws,
+                                                     int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(ids), _lib.ptr(flat),
+                                                     _lib.ptr(changes), C.byref(degenerate)))
+        offs = np.concatenate(([0], np.cumsum(self.n_genes)))
+        paths = [flat[:, :, offs[c]:offs[c + 1]] for c in range(len(self.chroms))]
+        if sample is not None:
+            paths, changes = [p[0] for p in paths], changes[0]
+        return {'paths': paths, 'changes': changes, 'degenerate': int(degenerate.value)}
+
+    def sample_info(self):
+        """(device milliseconds of the last sample_paths call's kernels, device bytes its buffers hold)."""
+        ms, nbytes = C.c_double(), C.c_uint64()
+        _lib.check(_lib.load().gbrs_hmm_sample_info(self._h, C.byref(ms), C.byref(nbytes)))
+        return ms.value, nbytes.value
+
     def info(self):
         inf = _lib.HmmInfo()
         _lib.check(_lib.load().gbrs_hmm_info(self._h, C.byref(inf)))
@@ -431,10 +464,78 @@ def _save_grid(stem, ctx, haplotypes, dosage, gamma_grid, threads=None):
     write_dosage_table(out_tsv, rows, haplotypes)
 
 
+def change_table(num_haps):
+    """uint8 (S x S): founder changes between two diplotypes read as multisets, 2 - |{a,b} n {c,d}| (AA -> AB is 1,
+    AB -> CC is 2), states in combinations_with_replacement order."""
+    a, b = np.array(list(combinations_with_replacement(range(num_haps), 2))).T
+    first = a[:, None] == a[None, :]                  # states are sorted pairs: a <= b
+    cross = a[:, None] == b[None, :]
+    shared = np.where(first, 1 + (b[:, None] == b[None, :]),
+                      np.where(cross, 1 + (b[:, None] == a[None, :]),
+                               (b[:, None] == a[None, :]) | (b[:, None] == b[None, :])))
+    return (2 - shared).astype(np.uint8)
+
+
+def check_sim_geno_args(sim_geno, sim_geno_seed=0):
+    """`--sim-geno K`: K >= 1, the seed a 64-bit unsigned number.  Refused before a file is read."""
+    if sim_geno is None:
+        return
+    if isinstance(sim_geno, bool) or int(sim_geno) != sim_geno or sim_geno < 1:
+        raise RuntimeError('--sim-geno must be at least 1')
+    if not 0 <= int(sim_geno_seed) < 1 << 64:
+        raise RuntimeError('--sim-geno-seed must be in 0 .. 2^64 - 1')
+
+
+def viterbi_changes(calls, table):
+    """Founder changes along a Viterbi path: the change table over consecutive genes that both have a call (>= 0)."""
+    calls = np.asarray(calls, dtype=np.int64)
+    both = (calls[:-1] >= 0) & (calls[1:] >= 0)
+    return int(table[calls[:-1][both], calls[1:][both]].sum())
+
+
+def _save_sim_geno(stem, ctx, diplotypes, drawn, seed, stream, threads=None):
+    """A sample's two files of `--sim-geno`: `<stem>.sim_geno.npz` (per chromosome the (K x n_c) uint8 state indices of the
+    draws, `diplotypes`, `seed`, `stream`) and `<stem>.sim_geno.crossovers.tsv` (per chromosome: genes, the founder changes
+    of the Viterbi path, and mean, sd, min, max of the draws' founder changes).  drawn: per chromosome (K x n_c) paths,
+    the (K x n_chrom) changes and the Viterbi path's count per chromosome (_draw_paths)."""
+    paths, changes, viterbi = drawn
+    out_npz, out_tsv = f'{stem}.sim_geno.npz', f'{stem}.sim_geno.crossovers.tsv'
+    logger.info(f'Saving Simulated Genotypes: {out_npz}')
+    arrays = {c: np.ascontiguousarray(paths[k]) for k, c in enumerate(ctx.chroms)}
+    arrays.update(diplotypes=np.asarray(diplotypes), seed=np.uint64(seed), stream=np.uint32(stream))
+    savez_compressed(out_npz, arrays, threads=threads)
+    logger.info(f'Saving Crossover Counts: {out_tsv}')
+    with open(out_tsv, 'w') as out:
+        out.write('#Chromosome\tGenes\tViterbi\tMean\tSD\tMin\tMax\n')
+        for k, c in enumerate(ctx.chroms):
+            x = changes[:, k].astype(np.float64)
+            sd = x.std(ddof=1) if len(x) > 1 else float('nan')
+            out.write('%s\t%d\t%d\t%.6f\t%.6f\t%d\t%d\n' % (c, paths[k].shape[1], viterbi[k], x.mean(), sd,
+                                                             int(x.min()), int(x.max())))
+
+
+def _draw_paths(hmm, n_draws, seed, streams, sample=None):
+    """Per sample of the call (paths per chromosome, changes, the Viterbi path's founder changes per chromosome)."""
+    drawn = hmm.sample_paths(n_draws, seed=seed, sample=sample, streams=streams)
+    if drawn['degenerate']:
+        logger.warning(f"{drawn['degenerate']} draws met a step without a finite positive weight and took its most likely state")
+    table = change_table(hmm.H)
+    picked = [sample] if sample is not None else list(range(hmm.n_samples))
+    out = []
+    for j, s in enumerate(picked):
+        viterbi = [viterbi_changes(hmm.get(k, sample=s, want=('calls',))['calls'], table) for k in range(len(hmm.chroms))]
+        if sample is not None:
+            out.append((drawn['paths'], drawn['changes'], viterbi))
+        else:
+            out.append(([p[j] for p in drawn['paths']], drawn['changes'][j], viterbi))
+    return out
+
+
 def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gpos_file: str = None,
                 expr_threshold: float = 1.5, sigma: float = 0.12, outbase: str = None,
                 device: int = 0, stage_times: dict = None, context: ReconstructContext = None,
-                grid_file: str = None, grid_genoprobs: bool = False) -> None:
+                grid_file: str = None, grid_genoprobs: bool = False, sim_geno: int = None,
+                sim_geno_seed: int = 0) -> None:
     """`gbrs reconstruct`: diplotype posteriors and Viterbi calls along every chromosome from
     gene-level TPMs.  Same inputs, defaults and three output files as gbrs_utils.reconstruct
     (gbrs_utils.py:382-609); the emission model and the three recursions run on the device.
@@ -444,7 +545,10 @@ def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gp
     rows only.  `grid_file` (extension; with a context, the context's): the posteriors also go onto the marker grid
     on the device and `<outbase>.interpolated.genoprobs.tsv` holds the founder dosages `gbrs export` would write after
     `gbrs interpolate`; with `grid_genoprobs` `<outbase>.interpolated.genoprobs.npz` holds what `gbrs interpolate`
-    writes."""
+    writes.  `sim_geno` = K (extension): K diplotype paths per chromosome drawn from the joint posterior on the device
+    (stream 0, seed `sim_geno_seed`) go to `<outbase>.sim_geno.npz`, their founder changes beside the Viterbi path's to
+    `<outbase>.sim_geno.crossovers.tsv`; without it the run makes no log-domain arrays and reaches none of that code."""
+    check_sim_geno_args(sim_geno, sim_geno_seed)
     clock = time.perf_counter
     marks = stage_times if stage_times is not None else {}
     stem = 'gbrs.reconstructed' if outbase is None else outbase
@@ -474,7 +578,7 @@ def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gp
     marks['load'] = clock() - t0
 
     posterior, path_names, calls = {}, {}, {}
-    on_grid = None
+    on_grid = drawn = None
     if chroms:
         t0 = clock()
         hmm, _ = ctx.handle(num_haps)
@@ -489,9 +593,16 @@ def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gp
         hmm.run()
         logger.info('Getting forward-backward probability')
         posterior, path_names, calls = _collect(ctx, hmm, 0, diplotypes)
-        if context is None and ctx.grid is None:
+        if context is None and ctx.grid is None and sim_geno is None:
             ctx.close()
         marks['hmm'] = clock() - t0
+        if sim_geno is not None:
+            t0 = clock()
+            logger.info(f'Drawing {sim_geno} paths from the posterior')
+            drawn = _draw_paths(hmm, sim_geno, sim_geno_seed, [0], sample=0)[0]
+            if context is None and ctx.grid is None:
+                ctx.close()
+            marks['sim_geno'] = clock() - t0
         if ctx.grid is not None:
             t0 = clock()
             logger.info('Converting genotype probability on the grid')
@@ -501,11 +612,15 @@ def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gp
             marks['grid'] = clock() - t0
     elif ctx.grid is not None:
         on_grid = {'dosage': np.zeros((0, num_haps)), 'gamma_grid': [] if grid_genoprobs else None}
+    if sim_geno is not None and drawn is None:
+        drawn = ([], np.zeros((sim_geno, 0), dtype=np.int32), [])
 
     t0 = clock()
     _save_reconstruction(stem, posterior, path_names, calls)
     if on_grid is not None:
         _save_grid(stem, ctx, haplotypes, on_grid['dosage'], on_grid.get('gamma_grid'))
+    if drawn is not None:
+        _save_sim_geno(stem, ctx, diplotypes, drawn, sim_geno_seed, 0)
     marks['save'] = clock() - t0
     logger.info('Done')
 
@@ -529,13 +644,15 @@ def read_sample_file(sample_file):
 def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str = None, gpos_file: str = None,
                      expr_threshold: float = 1.5, sigma: float = 0.12, device: int = 0, batch_size: int = 64,
                      grid_file: str = None, grid_genoprobs: bool = False, stage_times: dict = None,
-                     context: ReconstructContext = None) -> list:
+                     context: ReconstructContext = None, sim_geno: int = None, sim_geno_seed: int = 0) -> list:
     """`gbrs reconstruct` for a cohort whose genes.tpm files exist (extension): one context, the tables on the device
     once, the samples through the HMM in launches of up to `batch_size`, and with `grid_file` one grid pass per launch.
     Every sample gets the files the single-sample call writes for its outbase.  All samples must carry the same
     haplotype header (RuntimeError before anything runs otherwise).  A sample whose file cannot be read or lacks a gene
     is logged and left out, and the others go on.  Returns one dict per sample: its outbase and, if it failed,
-    `error`."""
+    `error`.  `sim_geno` = K: one more device pass per launch draws K paths per sample and chromosome; a sample's stream
+    is its 0-based position in `expression_files`, so its draws do not depend on the batch it ran in."""
+    check_sim_geno_args(sim_geno, sim_geno_seed)
     clock = time.perf_counter
     marks = stage_times if stage_times is not None else {}
     if len(expression_files) != len(outbases):
@@ -574,10 +691,12 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
     writers = ThreadPoolExecutor(max_workers=min(16, batch_size))
     pending = []
 
-    def save(k, results, on_grid):
+    def save(k, results, on_grid, drawn=None):
         _save_reconstruction(outbases[k], *results, threads=1)
         if on_grid is not None:
             _save_grid(outbases[k], ctx, haplotypes, on_grid[0], on_grid[1], threads=1)
+        if drawn is not None:
+            _save_sim_geno(outbases[k], ctx, diplotypes, drawn, sim_geno_seed, k, threads=1)
 
     try:
         order = sorted(headers)
@@ -593,8 +712,9 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
                     failed(k, e)
             marks['read'] += clock() - t0
             if not members or not ctx.chroms:
+                nothing = None if sim_geno is None else ([], np.zeros((sim_geno, 0), dtype=np.int32), [])
                 for k in members:
-                    pending.append((k, writers.submit(save, k, ({}, {}, {}), None)))
+                    pending.append((k, writers.submit(save, k, ({}, {}, {}), None, nothing)))
                 continue
             t0 = clock()
             first_use = ctx.hmm is None or ctx.hmm.H != num_haps
@@ -613,10 +733,15 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
                 t0 = clock()
                 on_grid = hmm.grid(want=('dosage', 'gamma_grid') if grid_genoprobs else ('dosage',))
                 marks['grid'] += clock() - t0
+            drawn = None
+            if sim_geno is not None:
+                t0 = clock()
+                drawn = _draw_paths(hmm, sim_geno, sim_geno_seed, members)
+                marks['sim_geno'] = marks.get('sim_geno', 0.0) + clock() - t0
             t0 = clock()
             for s, k in enumerate(members):
                 grid_of = None if on_grid is None else (on_grid['dosage'][s], on_grid['gamma_grid'][s] if grid_genoprobs else None)
-                pending.append((k, writers.submit(save, k, results[s], grid_of)))
+                pending.append((k, writers.submit(save, k, results[s], grid_of, None if drawn is None else drawn[s])))
             marks['save'] += clock() - t0
         t0 = clock()
         for k, job in pending:

@@ -11,7 +11,8 @@ order; gbrs_utils.py:420-447) for every sample.  The three steps are the very fu
 jobs.json: a list of objects {"alignment_file", "outbase", "tprob_file", and optionally "group_file", "length_file",
 "avec_file", "gpos_file", "grid_file", "grid_genoprobs", "expr_threshold", "sigma", "pseudocount", "max_iters", "tolerance",
 "diploid": true|false}; with "grid_file" the sample's reconstruction also leaves `<outbase>.interpolated.genoprobs.tsv`
-(and with "grid_genoprobs" the `.npz`), see `gbrs reconstruct --grid-file`;
+(and with "grid_genoprobs" the `.npz`), see `gbrs reconstruct --grid-file`; with "sim_geno": K (and "sim_geno_seed")
+its two `--sim-geno` files, drawn with stream 0;
 the stage times of every sample are printed as one JSON line per sample.
 """
 from __future__ import annotations
@@ -81,7 +82,8 @@ class SampleWorker:
                     avec_file=job.get('avec_file'), gpos_file=job.get('gpos_file'),
                     expr_threshold=job.get('expr_threshold', 1.5), sigma=job.get('sigma', 0.12),
                     outbase=job['outbase'], device=self.device, stage_times=st, context=self._context(job),
-                    grid_file=job.get('grid_file'), grid_genoprobs=bool(job.get('grid_genoprobs', False)))
+                    grid_file=job.get('grid_file'), grid_genoprobs=bool(job.get('grid_genoprobs', False)),
+                    sim_geno=job.get('sim_geno'), sim_geno_seed=job.get('sim_geno_seed', 0))
         out['reconstruct'] = dict(st, wall=clock() - t0)
         if job.get('diploid', True):
             st = {}

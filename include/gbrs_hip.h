@@ -712,6 +712,29 @@ int gbrs_hmm_grid(gbrs_hmm_t *hmm, int sample, double *dosage, double *gamma_gri
 /* M of the handle's grid (0 without one) and the device time of the last gbrs_hmm_grid kernel; both nullable. */
 int gbrs_hmm_grid_info(gbrs_hmm_t *hmm, int64_t *n_points, double *last_ms);
 
+/* Diplotype paths drawn from the joint posterior of the last run (extension; forward-filter / backward-sample on the
+ * run's filtered forward values, which the first call makes like gbrs_hmm_get(alpha)).  sample = -1: all n samples of
+ * the run, else that one (n = 1).  Draw d of a sample, chromosome c, genes i = n_c - 1 .. 0:
+ *   l_k = alpha[k][i] (+ T[i][z_{i+1}][k] below the last gene), w_k = exp(l_k), c_k = w_0 + .. + w_k, t = u * c_{S-1};
+ *   z_i = the smallest k with c_k > t; none by rounding: the largest k with w_k > 0; c_{S-1} zero or not finite: the first
+ *   argmax of l_k, counted in `degenerate`.
+ *   u = ((a >> 5) * 2^26 + (b >> 6)) * 2^-53 with a, b the words 2 (i & 1) and 2 (i & 1) + 1 of Philox4x32-10 on the
+ *   counter (i >> 1, c, d, stream) and the key (seed lo, seed hi).
+ *   streams     uint32[n] ids of the samples of this call; NULL: the sample's index in the run.  A sample's draws are a
+ *               function of (seed, its stream, c, d, i) and of its run alone: not of its slot, the batch or the slabs.
+ *   paths       uint8[n][n_draws][total_genes] state indices, a draw's chromosomes one after the other in handle order
+ *   changes     int32[n][n_draws][n_chrom], nullable: founder changes along the draw, 2 - |{a,b} n {c,d}| (multisets)
+ *               summed over neighbouring genes
+ *   degenerate  nullable: decisions of this call that fell back to the argmax
+ * Large requests go through the device in slabs of draws (about 1 GiB of device memory).  GBRS_ERR_STATE before the
+ * first run; GBRS_ERR_INVALID for n_draws < 1, a sample out of range or paths == NULL; outputs untouched on failure. */
+int gbrs_hmm_sample_paths(gbrs_hmm_t *hmm, int sample, int n_draws, uint64_t seed, const uint32_t *streams, uint8_t *paths,
+                          int32_t *changes, uint64_t *degenerate);
+
+/* Device time of the last gbrs_hmm_sample_paths call's kernels (all slabs) and the device memory its buffers hold; both
+ * nullable. */
+int gbrs_hmm_sample_info(gbrs_hmm_t *hmm, double *last_ms, uint64_t *device_bytes);
+
 int gbrs_hmm_destroy(gbrs_hmm_t *hmm);
 
 /* `gbrs interpolate` numeric body (gbrs/gbrs_utils.py:684-688): the rows of y (S x n_points, C

@@ -9,6 +9,7 @@
 // of that E-step are theta[h,l] * A[h,l].  Everything below computes den and A.
 #include "common.h"
 #include "em_layout.h"
+#include "em_step.h"
 
 #include <algorithm>
 #include <chrono>
@@ -532,19 +533,13 @@ struct gbrs_em {
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = true;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
     uint64_t R = 0, N = 0;
     uint32_t L = 0, H = 0;
     bool has_count = false, has_len = false, prepared = false;
     uint32_t flags = 0;
 
     int layout = 0;               // 0 = csc-direct, 1 = packed row tiles
-    uint32_t lead_mask = ~0u;     // ANDed with a tile header's n_one by tile_estep_kernel; 0: one batch loop for every batch
-    uint32_t persist_groups = 0;  // > 0: the E-step of a step runs on this many persistent workgroups (em_tiles.inc)
-    uint32_t view = 1;            // 2: the tile layout is built over half-loci (em_layout.h): tL() loci of tH() haplotypes
-    uint32_t tH() const { return H / view; }
-    uint32_t tL() const { return L * view; }
-    bool acc_needs_extra = false; // last E-step left the long-row sums in tl.acc_extra for the M-step to add
+    EmPlan plan;                  // what create resolved (em_plan.h); a pass's route is resolved from it (em_step.h, em_route)
     bool acc_external = false;    // the caller all-reduces acc (sharded): always materialise all of it
     TileLayout tl;
 
@@ -576,8 +571,7 @@ struct gbrs_em {
     // flushed as its own launch before anything reads the scalars.
     bool err_pending = false;
     double err_pending_target = -1.0;
-    hipEvent_t ev_after_estep = nullptr;      // timed step: recorded between the E-step kernels and the gather
-    std::vector<hipEvent_t> ev_pool;                   // 3 events per timed step of gbrs_em_step
+    std::vector<hipEvent_t> ev_pool;          // 3 events per timed step of a call (em_one_step); create makes the first 3
 
     // Pair mode (gbrs_em_pair_*): this handle and a partner hold the two locus ranges of one sample; the stopping rule is
     // evaluated over both on the device.  The first handle of the pair owns the state.
@@ -609,7 +603,7 @@ struct gbrs_em {
     // big_rows the rows whose count is above resample_cut (a workgroup each in the draw).
     bool resample = false, has_base = false;
     DevBuf<uint32_t> base_count, big_rows;
-    uint32_t n_big = 0, resample_cut = 256;
+    uint32_t n_big = 0;
     // replicate statistics (gbrs_em_bootstrap_begin / _add / _get): level 0 isoforms, 1 genes; quantity 0 TPM, 1 counts
     struct Stats {
         bool active = false;
@@ -637,127 +631,175 @@ struct gbrs_counts {
 
 namespace {
 
-int em_flush_err(gbrs_em *em);
+// ---- the error pass -----------------------------------------------------------------------------------------------------
+ErrArgs em_err_args(gbrs_em *em, double target_err) {
+    ErrArgs ea;
+    ea.L = em->L;
+    ea.nblocks = (int)em->msum_blocks;
+    ea.cap = em->msum_cap;
+    ea.tot_prev = em->tot_prev.p;
+    ea.tot_new = em->tot_new.p;
+    ea.partials = em->msums.p;
+    ea.sc = em->scalars.p;
+    ea.target_err = target_err;
+    ea.err_hist = em->err_hist.p;
+    ea.err_hist_cap = em->err_hist_cap;
+    ea.n_err_blocks = (uint32_t)std::min<uint64_t>(ERR_BLOCKS, (em->L + RED_THREADS - 1) / RED_THREADS);
+    return ea;
+}
+
+int em_launch_err(gbrs_em *em, double target_err) {
+    const ErrArgs ea = em_err_args(em, target_err);
+    hipLaunchKernelGGL(err_finish_kernel, dim3(ea.n_err_blocks), dim3(RED_THREADS), 0, em->stream, ea);
+    GBRS_HIP_CHECK(hipGetLastError());
+    return GBRS_OK;
+}
+
+// Runs a deferred error pass now (before anything that reads or resets the step scalars).
+int em_flush_err(gbrs_em *em) {
+    if (!em->err_pending) return GBRS_OK;
+    em->err_pending = false;
+    return em_launch_err(em, em->err_pending_target);
+}
 
 int em_check_float(gbrs_em *em, EmScalars &host) {
     GBRS_TRY(em_flush_err(em));
     GBRS_HIP_CHECK(hipMemcpyAsync(&host, em->scalars.p, sizeof(EmScalars), hipMemcpyDeviceToHost, em->stream));
     GBRS_HIP_CHECK(hipStreamSynchronize(em->stream));
     em->stopped = host.stop != 0;
-    static const bool no_check = std::getenv("GBRS_TUNING_NO_FLOAT_CHECK") != nullptr;   // ablation builds only
-    if (host.float_error && !no_check)
+    if (host.float_error && !em->plan.no_float_check)
         return fail(GBRS_ERR_FLOAT, "invalid value encountered in divide (a read's alignments all have zero abundance)");
     return GBRS_OK;
 }
 
-// E-step over the tiled layout: tiles -> partials, long rows -> acc_extra, gather -> acc.
-ErrArgs em_err_args(gbrs_em *em, double target_err);
-int em_flush_err(gbrs_em *em);
+// ---- one pass: what it launches (em_step.h), then one function per launch ---------------------------------------------------
 
-template <int HT, bool ONES>
-int em_estep_tiles_h(gbrs_em *em) {
+// The route of a pass of this kind over the handle as it stands.  Resolved once per API call, outside any loop over steps.
+EmStepRoute em_route(const gbrs_em *em, EmPass pass) {
     const TileLayout &tl = em->tl;
-    if (tl.n_tiles) {
-        // a deferred error pass of the previous step rides on this launch as extra workgroups
-        ErrArgs ea = em_err_args(em, em->err_pending_target);
-        if (ONES || !em->err_pending) ea.n_err_blocks = 0;
-        em->err_pending = false;
-        const dim3 grid((unsigned)tl.n_tiles + ea.n_err_blocks), block(TILE_THREADS);
-        const double *ww = tl.weighted ? tl.word_weight.p : (const double *)nullptr;
-        const SetArgs sets{em->tL(), tl.n_sets ? tl.set_ptr.p : nullptr, tl.set_members.p, tl.dest_list.p, tl.dict_b.p, tl.dest_b.p,
-                           em->resample ? 1u : 0u};
-        const uint32_t lead_mask = em->lead_mask;
-#define GBRS_LAUNCH_TILES(W, D)                                                                                        \
-        hipLaunchKernelGGL((tile_estep_kernel<HT, W, ONES, D>), grid, block, 0, em->stream, em->tH(), tl.tiles.p, tl.words.p, \
-                           tl.dict.p, ww, em->theta.p, tl.partials.p, tl.slot_dest.p, em->acc.p, em->scalars.p,       \
-                           (uint32_t)tl.n_tiles, ea, sets, lead_mask)
-        if (!ONES && !tl.deterministic && em->persist_groups > 0 && HT > 0 && HT <= 8) {
+    EmStepShape s;
+    s.tiled = em->layout == 1;
+    s.H = em->H; s.tH = em->plan.tH; s.view = em->plan.view;
+    s.no_tiles = tl.n_tiles == 0; s.no_long = tl.n_long == 0; s.no_entries = em->N == 0;
+    s.weighted = tl.weighted; s.deterministic = tl.deterministic; s.all_one_word = tl.all_one_word;
+    s.persist_groups = em->plan.persist_groups;
+    s.acc_handed_out = em->acc_external;
+    s.no_fused_mstep = em->plan.no_fused_mstep;
+    return em_step_route(s, pass);
+}
+
+// Tiles -> partials (a locus with a single slot: straight into acc).
+template <int HT, bool ONES>
+int em_launch_tiles_h(gbrs_em *em, const EmStepRoute &r) {
+    const TileLayout &tl = em->tl;
+    const uint32_t tH = em->plan.tH;
+    // a deferred error pass of the previous step rides on this launch as extra workgroups
+    ErrArgs ea = em_err_args(em, em->err_pending_target);
+    if (!r.err_rides || !em->err_pending) ea.n_err_blocks = 0;
+    em->err_pending = false;
+    const dim3 grid((unsigned)tl.n_tiles + ea.n_err_blocks), block(TILE_THREADS);
+    const double *ww = tl.weighted ? tl.word_weight.p : (const double *)nullptr;
+    const SetArgs sets{em->plan.tL, tl.n_sets ? tl.set_ptr.p : nullptr, tl.set_members.p, tl.dest_list.p, tl.dict_b.p, tl.dest_b.p,
+                       em->resample ? 1u : 0u};
+    const uint32_t lead_mask = em->plan.lead_mask;
+#define GBRS_LAUNCH_TILES(W, D)                                                                                            \
+    hipLaunchKernelGGL((tile_estep_kernel<HT, W, ONES, D>), grid, block, 0, em->stream, tH, tl.tiles.p, tl.words.p,        \
+                       tl.dict.p, ww, em->theta.p, tl.partials.p, tl.slot_dest.p, em->acc.p, em->scalars.p,               \
+                       (uint32_t)tl.n_tiles, ea, sets, lead_mask)
+    switch (r.estep) {
+        case EmEstep::Persistent:
+        case EmEstep::PersistentOneWord: {
             // persistent workgroups (em_tiles.inc): as many as the chip holds at once, each walking several tiles with the
             // next tile's header, dictionary and theta fetched under the current tile's batch loop
-            const uint32_t G = std::min<uint32_t>(em->persist_groups, (uint32_t)tl.n_tiles);
+            const uint32_t G = std::min<uint32_t>(em->plan.persist_groups, (uint32_t)tl.n_tiles);
             const dim3 pgrid(G + ea.n_err_blocks);
-#define GBRS_LAUNCH_PERSISTENT(HH, W, OW)                                                                              \
-            hipLaunchKernelGGL((tile_estep_persistent_kernel<HH, W, OW>), pgrid, block, 0, em->stream, em->tH(), tl.tiles.p,  \
-                               tl.words.p, tl.dict.p, ww, em->theta.p, tl.partials.p, tl.slot_dest.p,                  \
+#define GBRS_LAUNCH_PERSISTENT(HH, W, OW)                                                                                  \
+            hipLaunchKernelGGL((tile_estep_persistent_kernel<HH, W, OW>), pgrid, block, 0, em->stream, tH, tl.tiles.p,     \
+                               tl.words.p, tl.dict.p, ww, em->theta.p, tl.partials.p, tl.slot_dest.p,                      \
                                (int64_t)(em->acc.p - tl.partials.p), em->scalars.p, (uint32_t)tl.n_tiles, G, ea, sets)
-            if (HT == 8 && !tl.weighted && tl.all_one_word) GBRS_LAUNCH_PERSISTENT(HT == 8 ? 8 : 1, false, HT == 8);
-            else if (tl.weighted) GBRS_LAUNCH_PERSISTENT(HT, true, false);
+            if (r.estep == EmEstep::PersistentOneWord) GBRS_LAUNCH_PERSISTENT(HT == 8 ? 8 : 1, false, HT == 8);
+            else if (r.weighted) GBRS_LAUNCH_PERSISTENT(HT, true, false);
             else GBRS_LAUNCH_PERSISTENT(HT, false, false);
 #undef GBRS_LAUNCH_PERSISTENT
-        } else if (tl.deterministic) {           // fixed-order sums instead of LDS float atomics (GBRS_EM_DETERMINISTIC)
-            if (tl.weighted) GBRS_LAUNCH_TILES(true, true); else GBRS_LAUNCH_TILES(false, true);
+            break;
+        }
+        case EmEstep::TilesDeterministic:        // fixed-order sums instead of LDS float atomics (GBRS_EM_DETERMINISTIC)
+            if (r.weighted) GBRS_LAUNCH_TILES(true, true); else GBRS_LAUNCH_TILES(false, true);
+            break;
 #if !defined(GBRS_NO_ONEWORD)
-        } else if (HT == 8 && !tl.weighted && tl.all_one_word) {
+        case EmEstep::TilesOneWord:
             // no row of the layout has more than one word (single-locus reads, or locus sets): no row sums at all
-            hipLaunchKernelGGL((tile_estep_kernel<HT == 8 ? 8 : 1, false, ONES, false, HT == 8>), grid, block, 0, em->stream, em->tH(),
+            hipLaunchKernelGGL((tile_estep_kernel<HT == 8 ? 8 : 1, false, ONES, false, HT == 8>), grid, block, 0, em->stream, tH,
                                tl.tiles.p, tl.words.p, tl.dict.p, ww, em->theta.p, tl.partials.p, tl.slot_dest.p, em->acc.p,
                                em->scalars.p, (uint32_t)tl.n_tiles, ea, sets, lead_mask);
+            break;
 #endif
-        } else {
-            if (tl.weighted) GBRS_LAUNCH_TILES(true, false); else GBRS_LAUNCH_TILES(false, false);
-        }
-#undef GBRS_LAUNCH_TILES
+        default:
+            if (r.weighted) GBRS_LAUNCH_TILES(true, false); else GBRS_LAUNCH_TILES(false, false);
     }
+#undef GBRS_LAUNCH_TILES
     return GBRS_OK;
 }
-template <bool ONES>
-int em_estep_tiles(gbrs_em *em, bool materialize, bool skip_gather = false) {
-    if (ONES || !em->tl.n_tiles) GBRS_TRY(em_flush_err(em));   // prepare / no tile launch to ride on
+int em_launch_tiles(gbrs_em *em, const EmStepRoute &r) {
+#define GBRS_TILES_OF(HT) (r.pass == EmPass::Prepare ? em_launch_tiles_h<HT, true>(em, r) : em_launch_tiles_h<HT, false>(em, r))
+    switch (r.width) {
+        case 1: return GBRS_TILES_OF(1);
+        case 2: return GBRS_TILES_OF(2);
+        case 4: return GBRS_TILES_OF(4);
+        case 8: return GBRS_TILES_OF(8);
+        case 16: return GBRS_TILES_OF(16);
+        default: return GBRS_TILES_OF(0);
+    }
+#undef GBRS_TILES_OF
+}
 
-    TileLayout &tl = em->tl;
-    switch (em->tH()) {
-        case 1: GBRS_TRY((em_estep_tiles_h<1, ONES>(em))); break;
-        case 2: GBRS_TRY((em_estep_tiles_h<2, ONES>(em))); break;
-        case 4: GBRS_TRY((em_estep_tiles_h<4, ONES>(em))); break;
-        case 8: GBRS_TRY((em_estep_tiles_h<8, ONES>(em))); break;
-        case 16: GBRS_TRY((em_estep_tiles_h<16, ONES>(em))); break;
-        default: GBRS_TRY((em_estep_tiles_h<0, ONES>(em))); break;
+// Long rows -> acc_extra.
+int em_launch_long_rows(gbrs_em *em, const EmStepRoute &r) {
+    const TileLayout &tl = em->tl;
+    const bool ones = r.pass == EmPass::Prepare;
+    GBRS_HIP_CHECK(hipMemsetAsync(tl.acc_extra.p, 0, tl.acc_extra.bytes(), em->stream));
+#define GBRS_LAUNCH_LONG(KERNEL, GRID, BLOCK)                                                                              \
+    hipLaunchKernelGGL(KERNEL, GRID, BLOCK, 0, em->stream, tl.n_long, em->plan.tH, tl.long_ptr.p, tl.long_loc.p,          \
+                       tl.long_mask.p, tl.long_weight.p, em->theta.p, tl.acc_extra.p, em->scalars.p, em->resample ? 1u : 0u)
+    const dim3 grid((unsigned)((tl.n_long + 3) / 4));
+    if (r.long_rows == EmLongRows::Serial) {
+        if (ones) GBRS_LAUNCH_LONG(long_rows_estep_serial_kernel<true>, dim3(1), dim3(64));
+        else GBRS_LAUNCH_LONG(long_rows_estep_serial_kernel<false>, dim3(1), dim3(64));
+    } else {
+        if (ones) GBRS_LAUNCH_LONG(long_rows_estep_kernel<true>, grid, dim3(256));
+        else GBRS_LAUNCH_LONG(long_rows_estep_kernel<false>, grid, dim3(256));
     }
-    if (tl.n_long) {
-        GBRS_HIP_CHECK(hipMemsetAsync(tl.acc_extra.p, 0, tl.acc_extra.bytes(), em->stream));
-        if (tl.deterministic)
-            hipLaunchKernelGGL(long_rows_estep_serial_kernel<ONES>, dim3(1), dim3(64), 0, em->stream, tl.n_long, em->tH(),
-                               tl.long_ptr.p, tl.long_loc.p, tl.long_mask.p, tl.long_weight.p, em->theta.p,
-                               tl.acc_extra.p, em->scalars.p, em->resample ? 1u : 0u);
-        else
-            hipLaunchKernelGGL(long_rows_estep_kernel<ONES>, dim3((unsigned)((tl.n_long + 3) / 4)), dim3(256), 0, em->stream,
-                               tl.n_long, em->tH(), tl.long_ptr.p, tl.long_loc.p, tl.long_mask.p, tl.long_weight.p,
-                               em->theta.p, tl.acc_extra.p, em->scalars.p, em->resample ? 1u : 0u);
-    }
-    if (em->ev_after_estep) {
-        GBRS_HIP_CHECK(hipEventRecord(em->ev_after_estep, em->stream));
-        em->ev_after_estep = nullptr;
-    }
-    // (the gather walks the layout's loci: half-loci of tH() haplotypes under the half-locus view - the same elements of acc)
-    const uint32_t gH = em->tH(), gL = em->tL();
+#undef GBRS_LAUNCH_LONG
+    return GBRS_OK;
+}
+
+// Partials [+ acc_extra] -> acc: the loci the tiles wrote more than one slot for, or every element.
+int em_launch_gather(gbrs_em *em, const EmStepRoute &r) {
+    const TileLayout &tl = em->tl;
+    // (the gather walks the layout's loci: half-loci of tH haplotypes under the half-locus view - the same elements of acc)
+    const uint32_t gH = em->plan.tH, gL = em->plan.tL;
     uint32_t HP = 1;
     while (HP < gH) HP <<= 1;
-    const bool pow2 = (gH & (gH - 1)) == 0;
-    const bool all = materialize || em->acc_external || !pow2 || em->view > 1;     // write every element of acc
+    const bool all = r.gather == EmGather::All;
     const uint64_t elems = all ? (uint64_t)gL * gH : (uint64_t)tl.n_light * gH;
     const unsigned light = (unsigned)((elems + 255) / 256);
     const unsigned heavy = (unsigned)((tl.n_heavy + 3) / 4);
-    em->acc_needs_extra = !all && tl.n_long > 0;
-    if (skip_gather) return GBRS_OK;           // the fused gather + M-step kernel follows (em_one_step)
     if (light + heavy > 0)
         hipLaunchKernelGGL(gather_kernel, dim3(light + heavy), dim3(256), 0, em->stream, gL, gH,
                            HP, light, heavy, (uint32_t)tl.n_heavy, all ? 1 : 0, (uint32_t)tl.n_light, tl.light_loci.p,
                            tl.slot_ptr.p, tl.heavy_loci.p, tl.locus_class.p, tl.partials.p,
                            (tl.n_long && all) ? tl.acc_extra.p : (const double *)nullptr, em->acc.p, em->scalars.p,
-                           ONES ? 0 : 1);
-    GBRS_HIP_CHECK(hipGetLastError());
+                           r.pass == EmPass::Prepare ? 0 : 1);
     return GBRS_OK;
 }
 
-// E-step: fills em->acc with A (sum of count/den per column).  ONES: theta treated as 1.
+// E-step on the CSC arrays: acc = A, zero where there is no entry.
 template <bool ONES>
-int em_estep(gbrs_em *em, bool materialize = false) {
-    if (em->layout == 1) return em_estep_tiles<ONES>(em, materialize);
-    em->acc_needs_extra = false;
+int em_launch_csc(gbrs_em *em, const EmStepRoute &r) {
     const uint64_t n = em->N;
     const uint32_t ncols = em->H * em->L;
     GBRS_HIP_CHECK(hipMemsetAsync(em->acc.p, 0, em->acc.bytes(), em->stream));
-    if (n == 0) return GBRS_OK;
+    if (r.estep != EmEstep::Csc) return GBRS_OK;
     GBRS_HIP_CHECK(hipMemsetAsync(em->den.p, 0, em->den.bytes(), em->stream));
     const unsigned grid = (unsigned)((n + 255) / 256);
     hipLaunchKernelGGL(csc_den_kernel<ONES>, dim3(grid), dim3(256), 0, em->stream, n, ncols, em->L,
@@ -765,6 +807,45 @@ int em_estep(gbrs_em *em, bool materialize = false) {
     hipLaunchKernelGGL(csc_acc_kernel<ONES>, dim3(grid), dim3(256), 0, em->stream, n, ncols, em->L,
                        em->H, em->col_ptr.p, em->ent_row.p, em->has_count ? em->count.p : nullptr,
                        em->den.p, em->acc.p, em->scalars.p, em->resample ? 1u : 0u);
+    return GBRS_OK;
+}
+
+// E-step of model 1, 2 or 3 (the order must be built): acc = A.
+int em_launch_models(gbrs_em *em, int model) {
+    const GroupedOrder &o = model == 1 ? em->order_m1 : em->order_m23;
+    const uint32_t nt = std::max(em->L, em->n_genes);
+    hipLaunchKernelGGL(model_totals_kernel, dim3((nt + 255) / 256), dim3(256), 0, em->stream, em->L, em->H, em->n_genes,
+                       em->gene_ptr.p, em->gene_mem.p, em->theta.p, em->gene_tot.p, em->gene_hap_tot.p, em->locus_tot.p,
+                       em->scalars.p);
+    GBRS_HIP_CHECK(hipMemsetAsync(em->acc.p, 0, em->acc.bytes(), em->stream));
+    if (em->N) {
+        const dim3 rgrid((unsigned)((em->R + 255) / 256));
+        const double *cnt = em->has_count ? em->count.p : (const double *)nullptr;
+#define GBRS_LAUNCH_ROWS(M)                                                                                             \
+        hipLaunchKernelGGL(model_row_kernel<M>, rgrid, dim3(256), 0, em->stream, em->R, em->H, em->row_ptr.p, o.lh.p,   \
+                           o.src.p, em->locus_gene.p, em->theta.p, em->gene_tot.p, em->gene_hap_tot.p, em->locus_tot.p, \
+                           cnt, em->fac.p, em->scalars.p)
+        if (model == 1) GBRS_LAUNCH_ROWS(1);
+        else if (model == 2) GBRS_LAUNCH_ROWS(2);
+        else GBRS_LAUNCH_ROWS(3);
+#undef GBRS_LAUNCH_ROWS
+        hipLaunchKernelGGL(model_col_kernel, dim3((unsigned)((em->N + 255) / 256)), dim3(256), 0, em->stream, em->N,
+                           em->H * em->L, em->L, em->H, em->col_ptr.p, em->fac.p, em->acc.p, em->scalars.p);
+    }
+    GBRS_HIP_CHECK(hipGetLastError());
+    return GBRS_OK;
+}
+
+// The E-step half of a pass: fills em->acc with A - all of it, or (r.gather) what the M-step that follows does not add up
+// itself.  `after_kernels` (nullable) is recorded behind the E-step kernels themselves, before the gather.
+int em_estep(gbrs_em *em, const EmStepRoute &r, int model = 4, hipEvent_t after_kernels = nullptr) {
+    if (!r.err_rides) GBRS_TRY(em_flush_err(em));        // prepare / no tile launch to ride on
+    if (r.estep == EmEstep::Models) GBRS_TRY(em_launch_models(em, model));
+    else if (em->layout != 1) GBRS_TRY(r.pass == EmPass::Prepare ? em_launch_csc<true>(em, r) : em_launch_csc<false>(em, r));
+    else if (r.estep != EmEstep::None) GBRS_TRY(em_launch_tiles(em, r));
+    if (r.long_rows != EmLongRows::None) GBRS_TRY(em_launch_long_rows(em, r));
+    if (after_kernels) GBRS_HIP_CHECK(hipEventRecord(after_kernels, em->stream));
+    if (r.gather != EmGather::None) GBRS_TRY(em_launch_gather(em, r));
     GBRS_HIP_CHECK(hipGetLastError());
     return GBRS_OK;
 }
@@ -929,12 +1010,29 @@ mstep_gather_kernel(uint32_t L, uint32_t H, uint32_t HP, uint32_t heavy_blocks, 
     }
 }
 
-// M-step launch: element-parallel when H is a power of two, thread-per-locus otherwise.
+int em_launch_mstep_gather(gbrs_em *em, const EmStepRoute &r) {
+    const TileLayout &tl = em->tl;
+    uint32_t HP = 1;
+    while (HP < em->H) HP <<= 1;
+    const uint64_t n = (uint64_t)em->L * em->H;
+    const unsigned elem_blocks = (unsigned)((n + (uint64_t)RED_THREADS * MSTEP_EPT - 1) / ((uint64_t)RED_THREADS * MSTEP_EPT));
+    const unsigned heavy_blocks = (unsigned)tl.n_heavy;         // one workgroup per many-slot locus
+    const unsigned light_blocks = (unsigned)((tl.n_light * em->H + RED_THREADS - 1) / RED_THREADS);
+    em->msum_blocks = elem_blocks + heavy_blocks + light_blocks;
+    hipLaunchKernelGGL(mstep_gather_kernel, dim3(em->msum_blocks), dim3(RED_THREADS), 0, em->stream, em->L,
+                       em->H, HP, heavy_blocks, light_blocks, (uint32_t)tl.n_light, tl.heavy_range.p, tl.light_range.p,
+                       tl.locus_class.p, tl.partials.p, em->acc.p,
+                       r.long_rows != EmLongRows::None ? tl.acc_extra.p : (const double *)nullptr, em->theta.p,
+                       em->has_len ? em->eff_len.p : (const double *)nullptr, em->counts.p, em->tot_prev.p,
+                       em->tot_new.p, em->msums.p, em->msum_cap, em->scalars.p);
+    return GBRS_OK;
+}
+
+// M-step launch: with the gather, element-parallel (H a power of two) or thread-per-locus.  MODE 1: prepare.
 template <int MODE>
-int em_launch_mstep(gbrs_em *em) {
-    const bool pow2 = (em->H & (em->H - 1)) == 0;
+int em_launch_mstep_plain(gbrs_em *em, const EmStepRoute &r) {
     const double *len = em->has_len ? em->eff_len.p : nullptr;
-    if (!pow2) {
+    if (r.mstep == EmMstep::PerLocus) {
         const int nb = em->red_blocks();
         em->msum_blocks = nb;
         hipLaunchKernelGGL(mstep_kernel<MODE>, dim3(nb), dim3(RED_THREADS), 0, em->stream, em->L, em->H,
@@ -946,9 +1044,13 @@ int em_launch_mstep(gbrs_em *em) {
     const unsigned nb = (unsigned)((n + RED_THREADS - 1) / RED_THREADS);
     em->msum_blocks = nb;
     hipLaunchKernelGGL(mstep_elem_kernel<MODE>, dim3(nb), dim3(RED_THREADS), 0, em->stream, em->L, em->H, em->theta.p,
-                       em->acc.p, em->acc_needs_extra ? em->tl.acc_extra.p : (const double *)nullptr, len,
+                       em->acc.p, r.mstep_adds_extra ? em->tl.acc_extra.p : (const double *)nullptr, len,
                        em->counts.p, em->tot_prev.p, em->tot_new.p, em->msums.p, em->msum_cap, em->scalars.p);
     return GBRS_OK;
+}
+int em_launch_mstep(gbrs_em *em, const EmStepRoute &r) {
+    if (r.mstep == EmMstep::Fused) return em_launch_mstep_gather(em, r);
+    return r.pass == EmPass::Prepare ? em_launch_mstep_plain<1>(em, r) : em_launch_mstep_plain<0>(em, r);
 }
 
 // The expected read counts theta * A of the last iteration (EMfactory.py:302: the last E-step's posterior summed over the
@@ -970,74 +1072,18 @@ int em_refresh_counts(gbrs_em *em) {
     return GBRS_OK;
 }
 
-// Everything after the E-step of one EM iteration.
-ErrArgs em_err_args(gbrs_em *em, double target_err) {
-    ErrArgs ea;
-    ea.L = em->L;
-    ea.nblocks = (int)em->msum_blocks;
-    ea.cap = em->msum_cap;
-    ea.tot_prev = em->tot_prev.p;
-    ea.tot_new = em->tot_new.p;
-    ea.partials = em->msums.p;
-    ea.sc = em->scalars.p;
-    ea.target_err = target_err;
-    ea.err_hist = em->err_hist.p;
-    ea.err_hist_cap = em->err_hist_cap;
-    ea.n_err_blocks = (uint32_t)std::min<uint64_t>(ERR_BLOCKS, (em->L + RED_THREADS - 1) / RED_THREADS);
-    return ea;
-}
-
-// Runs a deferred error pass now (before anything that reads or resets the step scalars).
-int em_flush_err(gbrs_em *em) {
-    if (!em->err_pending) return GBRS_OK;
-    em->err_pending = false;
-    const ErrArgs ea = em_err_args(em, em->err_pending_target);
-    hipLaunchKernelGGL(err_finish_kernel, dim3(ea.n_err_blocks), dim3(RED_THREADS), 0, em->stream, ea);
-    GBRS_HIP_CHECK(hipGetLastError());
-    return GBRS_OK;
-}
-
-// Everything after the E-step of one EM iteration.  `defer`: leave the error pass to the next
-// step's gather launch (em_estep_tiles) or to em_flush_err.
-// tile layout, H a power of two, A not handed out for an all-reduce: gather and M-step share a launch
-bool em_can_fuse_mstep(const gbrs_em *em) {
-    static const bool off = [] { const char *e = std::getenv("GBRS_TUNING_NO_FUSED_MSTEP"); return e && std::atoi(e) != 0; }();
-    // (half-locus view: the fused kernel's per-locus totals would be per half; gather and M-step stay two launches there)
-    return !off && em->layout == 1 && (em->H & (em->H - 1)) == 0 && !em->acc_external && em->view == 1;
-}
-
-int em_launch_mstep_gather(gbrs_em *em) {
-    const TileLayout &tl = em->tl;
-    uint32_t HP = 1;
-    while (HP < em->H) HP <<= 1;
-    const uint64_t n = (uint64_t)em->L * em->H;
-    const unsigned elem_blocks = (unsigned)((n + (uint64_t)RED_THREADS * MSTEP_EPT - 1) / ((uint64_t)RED_THREADS * MSTEP_EPT));
-    const unsigned heavy_blocks = (unsigned)tl.n_heavy;         // one workgroup per many-slot locus
-    const unsigned light_blocks = (unsigned)((tl.n_light * em->H + RED_THREADS - 1) / RED_THREADS);
-    em->msum_blocks = elem_blocks + heavy_blocks + light_blocks;
-    hipLaunchKernelGGL(mstep_gather_kernel, dim3(em->msum_blocks), dim3(RED_THREADS), 0, em->stream, em->L,
-                       em->H, HP, heavy_blocks, light_blocks, (uint32_t)tl.n_light, tl.heavy_range.p, tl.light_range.p,
-                       tl.locus_class.p, tl.partials.p, em->acc.p,
-                       tl.n_long ? tl.acc_extra.p : (const double *)nullptr, em->theta.p,
-                       em->has_len ? em->eff_len.p : (const double *)nullptr, em->counts.p, em->tot_prev.p,
-                       em->tot_new.p, em->msums.p, em->msum_cap, em->scalars.p);
-    return GBRS_OK;
-}
-
-int em_finish_step(gbrs_em *em, double target_err, bool defer = false, bool fused = false) {
+// The M-step half of a pass and its error pass.  `defer_err`: leave the error pass to the next pass's tile launch
+// (em_launch_tiles_h) or to em_flush_err, where the route allows it.
+int em_finish_step(gbrs_em *em, const EmStepRoute &r, double target_err, bool defer_err) {
     GBRS_TRY(em_flush_err(em));
-    if (fused) GBRS_TRY(em_launch_mstep_gather(em));
-    else GBRS_TRY(em_launch_mstep<0>(em));
-    em->counts_stale = fused;
-    if (defer && em->layout == 1) {
+    GBRS_TRY(em_launch_mstep(em, r));
+    em->counts_stale = r.counts_stale;
+    if (defer_err && r.err_defer) {
         em->err_pending = true;
         em->err_pending_target = target_err;
         return GBRS_OK;
     }
-    const ErrArgs ea = em_err_args(em, target_err);
-    hipLaunchKernelGGL(err_finish_kernel, dim3(ea.n_err_blocks), dim3(RED_THREADS), 0, em->stream, ea);
-    GBRS_HIP_CHECK(hipGetLastError());
-    return GBRS_OK;
+    return em_launch_err(em, target_err);
 }
 
 // GBRS_EM_POSTERIOR: theta before the step that is about to be enqueued.  The deferred error pass of the previous step
@@ -1054,36 +1100,39 @@ int em_keep_theta(gbrs_em *em, int model) {
     return GBRS_OK;
 }
 
-// One iteration; `ev` (3 events) times it.  An event record is a barrier packet that costs the
-// queue ~4 us of idle time on this hardware, so callers time a sample of the iterations (every
-// EM_TIME_STRIDE-th), not each one.
+// One iteration of `model` (r: EmPass::Step for 4, else EmPass::Model with the order built); `ev` (3 events, nullable)
+// times it: ev[1] closes the E-step kernels themselves.  An event record is a barrier packet that costs the queue ~4 us of
+// idle time on this hardware, so callers time a sample of the iterations (every EM_TIME_STRIDE-th), not each one.
 constexpr int EM_TIME_STRIDE = 8, EM_TIME_SAMPLES = 16;
-int em_one_step(gbrs_em *em, double target_err, hipEvent_t *ev = nullptr, bool defer_err = false) {
-    GBRS_TRY(em_keep_theta(em, 4));
-    const bool timed = ev != nullptr && em->time_steps;
-    if (timed) GBRS_HIP_CHECK(hipEventRecord(ev[0], em->stream));
-    // ev[1] closes the E-step kernel itself (tile layout: before the gather; CSC layout: after the pass)
-    em->ev_after_estep = timed && em->layout == 1 ? ev[1] : nullptr;
-    const bool fused = em_can_fuse_mstep(em);
-    if (fused) GBRS_TRY(em_estep_tiles<false>(em, false, /* skip_gather */ true));
-    else GBRS_TRY(em_estep<false>(em));
-    em->ev_after_estep = nullptr;
-    if (timed && em->layout != 1) GBRS_HIP_CHECK(hipEventRecord(ev[1], em->stream));
-    GBRS_TRY(em_finish_step(em, target_err, defer_err, fused));
-    if (timed) GBRS_HIP_CHECK(hipEventRecord(ev[2], em->stream));
+int em_one_step(gbrs_em *em, const EmStepRoute &r, int model, double target_err, hipEvent_t *ev, bool defer_err) {
+    GBRS_TRY(em_keep_theta(em, model));
+    if (!em->time_steps) ev = nullptr;
+    if (ev) GBRS_HIP_CHECK(hipEventRecord(ev[0], em->stream));
+    GBRS_TRY(em_estep(em, r, model, ev ? ev[1] : nullptr));
+    GBRS_TRY(em_finish_step(em, r, target_err, defer_err));
+    // the tile layout's Model-4 steps write A only for the loci they have sums for and expect 0 elsewhere
+    if (r.pass == EmPass::Model && em->layout == 1) GBRS_HIP_CHECK(hipMemsetAsync(em->acc.p, 0, em->acc.bytes(), em->stream));
+    if (ev) GBRS_HIP_CHECK(hipEventRecord(ev[2], em->stream));
     return GBRS_OK;
 }
 
-int em_read_times(gbrs_em *em) {
-    if (!em->time_steps) return GBRS_OK;
-    float a = 0.f, b = 0.f;
-    if (hipEventElapsedTime(&a, em->ev0, em->ev1) == hipSuccess) em->last_estep_ms = a;
-    if (hipEventElapsedTime(&b, em->ev0, em->ev2) == hipSuccess) em->last_step_ms = b;
-    return GBRS_OK;
+// last_estep_ms / last_step_ms: the means over the n timed steps of a call, whose events lead em->ev_pool
+void em_read_times(gbrs_em *em, int n) {
+    if (!em->time_steps || n <= 0) return;
+    double se = 0.0, ss = 0.0;
+    for (int i = 0; i < n; ++i) {
+        float a = 0.f, b = 0.f;
+        if (hipEventElapsedTime(&a, em->ev_pool[3 * i], em->ev_pool[3 * i + 1]) != hipSuccess) return;   // (never recorded)
+        if (hipEventElapsedTime(&b, em->ev_pool[3 * i], em->ev_pool[3 * i + 2]) != hipSuccess) return;
+        se += a;
+        ss += b;
+    }
+    em->last_estep_ms = se / n;
+    em->last_step_ms = ss / n;
 }
 
 int em_finish_prepare(gbrs_em *em, double pseudocount) {
-    GBRS_TRY(em_launch_mstep<1>(em));
+    GBRS_TRY(em_launch_mstep(em, em_route(em, EmPass::Prepare)));
     em->counts_stale = false;
     const int nb = em->red_blocks();
     if (pseudocount > 0.0) {
@@ -1144,42 +1193,6 @@ int em_ensure_order(gbrs_em *em, int model) {
     return build_grouped_order(o, em->R, em->L, em->H, em->N, em->ent_row.p, em->col_ptr.p,
                                model == 1 ? em->rank_m1.p : em->rank_m23.p, model == 1 ? em->inv_m1.p : em->inv_m23.p,
                                em->stream);
-}
-
-// One step of model 1, 2 or 3 (the order must be built); `ev` (3 events, nullable) times it as em_one_step does.
-int em_model_step(gbrs_em *em, int model, double target_err, hipEvent_t *ev = nullptr) {
-    GBRS_TRY(em_flush_err(em));
-    GBRS_TRY(em_keep_theta(em, model));
-    const GroupedOrder &o = model == 1 ? em->order_m1 : em->order_m23;
-    const bool timed = ev != nullptr && em->time_steps;
-    if (timed) GBRS_HIP_CHECK(hipEventRecord(ev[0], em->stream));
-    const uint32_t nt = std::max(em->L, em->n_genes);
-    hipLaunchKernelGGL(model_totals_kernel, dim3((nt + 255) / 256), dim3(256), 0, em->stream, em->L, em->H, em->n_genes,
-                       em->gene_ptr.p, em->gene_mem.p, em->theta.p, em->gene_tot.p, em->gene_hap_tot.p, em->locus_tot.p,
-                       em->scalars.p);
-    GBRS_HIP_CHECK(hipMemsetAsync(em->acc.p, 0, em->acc.bytes(), em->stream));
-    if (em->N) {
-        const dim3 rgrid((unsigned)((em->R + 255) / 256));
-        const double *cnt = em->has_count ? em->count.p : (const double *)nullptr;
-#define GBRS_LAUNCH_ROWS(M)                                                                                             \
-        hipLaunchKernelGGL(model_row_kernel<M>, rgrid, dim3(256), 0, em->stream, em->R, em->H, em->row_ptr.p, o.lh.p,   \
-                           o.src.p, em->locus_gene.p, em->theta.p, em->gene_tot.p, em->gene_hap_tot.p, em->locus_tot.p, \
-                           cnt, em->fac.p, em->scalars.p)
-        if (model == 1) GBRS_LAUNCH_ROWS(1);
-        else if (model == 2) GBRS_LAUNCH_ROWS(2);
-        else GBRS_LAUNCH_ROWS(3);
-#undef GBRS_LAUNCH_ROWS
-        hipLaunchKernelGGL(model_col_kernel, dim3((unsigned)((em->N + 255) / 256)), dim3(256), 0, em->stream, em->N,
-                           em->H * em->L, em->L, em->H, em->col_ptr.p, em->fac.p, em->acc.p, em->scalars.p);
-    }
-    GBRS_HIP_CHECK(hipGetLastError());
-    if (timed) GBRS_HIP_CHECK(hipEventRecord(ev[1], em->stream));
-    em->acc_needs_extra = false;
-    GBRS_TRY(em_finish_step(em, target_err, /* defer */ false, /* fused */ false));
-    // the tile layout's Model-4 steps write A only for the loci they have sums for and expect 0 elsewhere
-    if (em->layout == 1) GBRS_HIP_CHECK(hipMemsetAsync(em->acc.p, 0, em->acc.bytes(), em->stream));
-    if (timed) GBRS_HIP_CHECK(hipEventRecord(ev[2], em->stream));
-    return GBRS_OK;
 }
 
 // Concatenate the per-haplotype CSC arrays on the device: column id c = h*L + l, col_ptr[c] is the
@@ -1288,9 +1301,10 @@ int em_create_impl(uint64_t R, uint32_t L, uint32_t H, const uint32_t *const *in
     em->has_base = resample && count != nullptr;
     em->has_len = eff_len != nullptr;
     GBRS_HIP_CHECK(hipStreamCreateWithFlags(&em->stream, hipStreamDefault));
-    GBRS_HIP_CHECK(hipEventCreate(&em->ev0));
-    GBRS_HIP_CHECK(hipEventCreate(&em->ev1));
-    GBRS_HIP_CHECK(hipEventCreate(&em->ev2));
+    for (int i = 0; i < 3; ++i) {
+        em->ev_pool.push_back(nullptr);
+        GBRS_HIP_CHECK(hipEventCreate(&em->ev_pool.back()));
+    }
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     uint64_t n = 0;
     StageTimer stg("create");
@@ -1306,8 +1320,7 @@ int em_create_impl(uint64_t R, uint32_t L, uint32_t H, const uint32_t *const *in
     shape.tile_words = TILE_WORDS; shape.tile_words_max = TILE_WORDS_MAX; shape.tile_rounds_min = TILE_ROUNDS_MIN;
     if (H <= 16) shape.dict = dict_limits(em_weighted(flags, count != nullptr), (int)H);     // (more: the CSC kernels)
     if (H == 16) shape.dict_half = dict_limits(false, 8);
-    const EmPlan plan = em_plan(shape, em_tuning_from_env());
-    em->view = plan.view; em->persist_groups = plan.persist_groups; em->lead_mask = plan.lead_mask; em->resample_cut = plan.resample_cut;
+    const EmPlan &plan = em->plan = em_plan(shape, em_tuning_from_env());
     const size_t LH = (size_t)L * H;
     GBRS_TRY(em->den.alloc(R));
     GBRS_TRY(em->theta.alloc(LH));
@@ -1350,7 +1363,7 @@ int em_create_impl(uint64_t R, uint32_t L, uint32_t H, const uint32_t *const *in
             for (int pass = 0; pass < 2; ++pass) {
                 GBRS_HIP_CHECK(hipMemsetAsync(n_big.p, 0, 4, em->stream));
                 hipLaunchKernelGGL(resample_big_rows_kernel, dim3(rgrid), dim3(256), 0, em->stream, R, em->base_count.p,
-                                   em->resample_cut, n_big.p, pass ? em->big_rows.p : (uint32_t *)nullptr);
+                                   em->plan.resample_cut, n_big.p, pass ? em->big_rows.p : (uint32_t *)nullptr);
                 GBRS_HIP_CHECK(hipMemcpyAsync(&em->n_big, n_big.p, 4, hipMemcpyDeviceToHost, em->stream));
                 GBRS_HIP_CHECK(hipStreamSynchronize(em->stream));
                 if (em->n_big == 0) break;
@@ -1514,10 +1527,9 @@ int em_prepare_partial(gbrs_em *em) {
     em->post_model = 0;                       // no E-step since this prepare: nothing for gbrs_em_posterior
     if (em->has_init) {                       // stored alignment values: their normalised column sums
         GBRS_HIP_CHECK(hipMemcpyAsync(em->acc.p, em->acc_init.p, em->acc.bytes(), hipMemcpyDeviceToDevice, em->stream));
-        em->acc_needs_extra = false;
         return GBRS_OK;
     }
-    return em_estep<true>(em, true);
+    return em_estep(em, em_route(em, EmPass::Prepare));
 }
 }  // namespace
 
@@ -1617,8 +1629,8 @@ int gbrs_em_estep_partial(gbrs_em_t *em, void **partial_dev, uint64_t *n_elems) 
     // a run that met its stopping rule (gbrs_em_run, or the pair's rule: gbrs_em_pair_check) left the device's stop flag
     // set, which turns every step kernel into a no-op; a step asked for by hand is applied anyway, as in gbrs_em_step
     if (em->stopped) GBRS_TRY(em_reset_scalars(em, true));
-    em->acc_external = true;
-    GBRS_TRY(em_estep<false>(em, true));
+    em->acc_external = true;                  // acc is handed out: every route of the handle gathers all of it from here on
+    GBRS_TRY(em_estep(em, em_route(em, EmPass::Partial)));
     if (partial_dev) *partial_dev = em->acc.p;
     if (n_elems) *n_elems = (uint64_t)em->L * em->H;
     return GBRS_OK;
@@ -1628,7 +1640,7 @@ int gbrs_em_finish_step(gbrs_em_t *em, double *err_sum_out) {
     if (!em) return fail(GBRS_ERR_INVALID, "handle is NULL");
     GBRS_TRY(select_device(em->device));
     // without a request for err_sum the error pass is deferred into the next E-step launch
-    GBRS_TRY(em_finish_step(em, -1.0, /* defer */ err_sum_out == nullptr));
+    GBRS_TRY(em_finish_step(em, em_route(em, EmPass::Partial), -1.0, /* defer_err */ err_sum_out == nullptr));
     if (em->pair_ev_mstep) GBRS_HIP_CHECK(hipEventRecord(em->pair_ev_mstep, em->stream));
     if (err_sum_out) {
         EmScalars host;
@@ -1655,25 +1667,15 @@ int gbrs_em_step(gbrs_em_t *em, int n_iters, double *err_sum_out) {
         GBRS_HIP_CHECK(hipEventCreate(&e));
         em->ev_pool.push_back(e);
     }
+    const EmStepRoute route = em_route(em, EmPass::Step);
     for (int i = 0; i < n_iters; ++i) {
         const int slot = i / stride;
         const bool t = i % stride == 0 && slot < timed;
-        GBRS_TRY(em_one_step(em, -1.0, t ? &em->ev_pool[3 * slot] : nullptr, i + 1 < n_iters));
+        GBRS_TRY(em_one_step(em, route, 4, -1.0, t ? &em->ev_pool[3 * slot] : nullptr, i + 1 < n_iters));
     }
     EmScalars host;
     GBRS_TRY(em_check_float(em, host));
-    if (timed > 0) {
-        double se = 0.0, ss = 0.0;
-        for (int i = 0; i < timed; ++i) {
-            float a = 0.f, b = 0.f;
-            (void)hipEventElapsedTime(&a, em->ev_pool[3 * i], em->ev_pool[3 * i + 1]);
-            (void)hipEventElapsedTime(&b, em->ev_pool[3 * i], em->ev_pool[3 * i + 2]);
-            se += a;
-            ss += b;
-        }
-        em->last_estep_ms = se / timed;
-        em->last_step_ms = ss / timed;
-    }
+    em_read_times(em, timed);
     if (err_sum_out) *err_sum_out = host.err_sum;
     return GBRS_OK;
 }
@@ -1687,11 +1689,11 @@ int gbrs_em_step_model(gbrs_em_t *em, int model, int n_iters, double *err_sum_ou
     GBRS_TRY(select_device(em->device));
     if (em->stopped) GBRS_TRY(em_reset_scalars(em, true));     // as gbrs_em_step: a step asked for is applied
     GBRS_TRY(em_ensure_order(em, model));
-    hipEvent_t ev[3] = {em->ev0, em->ev1, em->ev2};
-    for (int i = 0; i < n_iters; ++i) GBRS_TRY(em_model_step(em, model, -1.0, i == 0 ? ev : nullptr));
+    const EmStepRoute route = em_route(em, EmPass::Model);
+    for (int i = 0; i < n_iters; ++i) GBRS_TRY(em_one_step(em, route, model, -1.0, i == 0 ? em->ev_pool.data() : nullptr, false));
     EmScalars host;
     GBRS_TRY(em_check_float(em, host));
-    if (n_iters > 0) em_read_times(em);
+    em_read_times(em, n_iters > 0 ? 1 : 0);
     if (err_sum_out) *err_sum_out = host.err_sum;
     return GBRS_OK;
 }
@@ -1786,6 +1788,7 @@ int gbrs_em_run(gbrs_em_t *em, int model, double tol, int max_iters, int *n_iter
     GBRS_TRY(em_ensure_hist(em, std::max(max_iters, 1)));
     GBRS_TRY(em_reset_scalars(em, false));
     const double target = 1000000.0 * tol;
+    const EmStepRoute route = em_route(em, model == 4 ? EmPass::Step : EmPass::Model);
     // the reference tests `err_sum > target` with err_sum = 1e6 before the first step
     int done = 0;
     EmScalars host;
@@ -1799,10 +1802,8 @@ int gbrs_em_run(gbrs_em_t *em, int model, double tol, int max_iters, int *n_iter
         const auto t_start = std::chrono::steady_clock::now();
         while (done < max_iters) {
             const int nb = std::min(batch, max_iters - done);
-            hipEvent_t ev[3] = {em->ev0, em->ev1, em->ev2};
             for (int i = 0; i < nb; ++i) {     // the run's first step is timed; a batch's last error pass is not deferred
-                if (model == 4) GBRS_TRY(em_one_step(em, target, first ? ev : nullptr, i + 1 < nb));
-                else GBRS_TRY(em_model_step(em, model, target, first ? ev : nullptr));
+                GBRS_TRY(em_one_step(em, route, model, target, first ? em->ev_pool.data() : nullptr, i + 1 < nb));
                 first = false;
             }
             GBRS_TRY(em_check_float(em, host));
@@ -1814,7 +1815,7 @@ int gbrs_em_run(gbrs_em_t *em, int model, double tol, int max_iters, int *n_iter
             if (host.stop) break;
         }
     }
-    em_read_times(em);
+    em_read_times(em, 1);
     if (n_iters_out) *n_iters_out = done;
     if (err_hist && err_hist_cap > 0 && done > 0) {
         const int ncopy = std::min(done, err_hist_cap);
@@ -2040,14 +2041,14 @@ int gbrs_em_info(gbrs_em_t *em, gbrs_em_info_t *info) {
         // rows = theta rows gathered and sum rows stored by the tiles: one per slot, one per (slot, member) for a locus set
         const uint64_t rows = tl.n_dest_rows ? tl.n_dest_rows : tl.n_slots;
         info->bytes_per_iter = 4 * tl.n_batches * 64 + 16 * tl.n_tiles + 4 * tl.n_slots +
-                               8 * rows * em->tH() * 3 + 4 * rows + 4 * ((uint64_t)em->tL() + 1) +
+                               8 * rows * em->plan.tH * 3 + 4 * rows + 4 * ((uint64_t)em->plan.tL + 1) +
                                (tl.weighted ? 8 * tl.n_batches * 64 : 0) + 8 * HL * 6;
         info->num_heavy_loci = tl.n_heavy;
         info->num_light_loci = tl.n_light;
         // the E-step launch alone: words, tile headers, dictionary + slot destinations, theta gathered
         // once per slot, one partial-sum row stored per slot [, the per-word row weights]
         info->estep_bytes = 4 * tl.n_batches * 64 + 16 * tl.n_tiles + 4 * tl.n_slots + 4 * rows +
-                            8 * rows * em->tH() * 2 + (tl.weighted ? 8 * tl.n_batches * 64 : 0) +
+                            8 * rows * em->plan.tH * 2 + (tl.weighted ? 8 * tl.n_batches * 64 : 0) +
                             (tl.n_sets ? 8 * tl.n_slots : 0);       // dict_b / dest_b beside the dictionary
         if (tl.n_sets) info->bytes_per_iter += 8 * tl.n_slots;
     }
@@ -2159,7 +2160,7 @@ int gbrs_em_resample(gbrs_em_t *em, uint64_t seed, uint32_t replicate) {
     if (replicate == GBRS_RESAMPLE_BASE) {
         hipLaunchKernelGGL(resample_draw_kernel<true>, dim3(rgrid), dim3(256), 0, em->stream, R, base, 0u, 0u, 0u, 0u, em->count.p);
     } else {
-        hipLaunchKernelGGL(resample_draw_kernel<false>, dim3(rgrid), dim3(256), 0, em->stream, R, base, em->resample_cut,
+        hipLaunchKernelGGL(resample_draw_kernel<false>, dim3(rgrid), dim3(256), 0, em->stream, R, base, em->plan.resample_cut,
                            replicate, k0, k1, em->count.p);
         if (em->n_big)
             hipLaunchKernelGGL(resample_big_kernel, dim3(em->n_big), dim3(256), 0, em->stream, em->n_big, em->big_rows.p, base,
@@ -2197,7 +2198,7 @@ int gbrs_em_resample_info(gbrs_em_t *em, uint64_t *extra_device_bytes, uint64_t 
         *extra_device_bytes = em->base_count.bytes() + em->big_rows.bytes() + em->tl.word_row.bytes() + em->tl.long_row.bytes() +
                               (em->has_base ? 0 : em->count.bytes() + em->tl.word_weight.bytes() + em->tl.long_weight.bytes());
     if (num_big_rows) *num_big_rows = em->n_big;
-    if (cut) *cut = em->resample_cut;
+    if (cut) *cut = em->plan.resample_cut;
     return GBRS_OK;
 }
 
@@ -2306,10 +2307,7 @@ int gbrs_em_destroy(gbrs_em_t *em) {
     if (!em) return GBRS_OK;
     (void)hipSetDevice(em->device);
     if (em->stream) (void)hipStreamSynchronize(em->stream);
-    if (em->ev0) (void)hipEventDestroy(em->ev0);
-    if (em->ev1) (void)hipEventDestroy(em->ev1);
-    if (em->ev2) (void)hipEventDestroy(em->ev2);
-    for (auto e : em->ev_pool) (void)hipEventDestroy(e);
+    for (auto e : em->ev_pool) if (e) (void)hipEventDestroy(e);
     if (em->pair_ev_mstep) (void)hipEventDestroy(em->pair_ev_mstep);
     if (em->pair_ev_err) (void)hipEventDestroy(em->pair_ev_err);
     if (em->stream && em->own_stream) (void)hipStreamDestroy(em->stream);

@@ -1,7 +1,8 @@
 // What gbrs_em_create* decides before any device work (em.hip) and the rules the tile layout's build applies to the
 // numbers it reads back from the device (em_layout.hip): the GBRS_TUNING_* variables of the EM handle, read from the
 // environment once per create, and the plan a pure function resolves from them and the handle's shape.  This is the one
-// place that reads those variables.  Host only - no HIP include, so a plain C++ compiler builds it
+// place that reads those variables; the handle keeps the plan, and what each of its steps launches is resolved from it in
+// em_step.h.  Host only - no HIP include, so a plain C++ compiler builds it
 // (tests/native/em_plan_driver.cpp).
 #pragma once
 
@@ -34,6 +35,8 @@ struct EmTuning {
     unsigned persistent_groups = 0;   // PERSISTENT_GROUPS (> 0): that many of them
     bool no_phase_split = false;      // NO_PHASE_SPLIT=1: one batch loop for every batch
     uint32_t resample_cut = 256;      // RESAMPLE_CUT (> 0): rows with a larger count get a workgroup in the draw
+    bool no_fused_mstep = false;      // NO_FUSED_MSTEP=1: gather and M-step as separate launches (em_step.h)
+    bool no_float_check = false;      // NO_FLOAT_CHECK set at all: no "row without abundance" error (ablation builds of the E-step)
 };
 
 namespace em_env {
@@ -65,6 +68,8 @@ inline EmTuning em_tuning_from_env() {
     at_least("GBRS_TUNING_PERSISTENT_GROUPS", 1, t.persistent_groups);
     t.no_phase_split = integer("GBRS_TUNING_NO_PHASE_SPLIT").nonzero();
     at_least("GBRS_TUNING_RESAMPLE_CUT", 1, t.resample_cut);
+    t.no_fused_mstep = integer("GBRS_TUNING_NO_FUSED_MSTEP").nonzero();
+    t.no_float_check = integer("GBRS_TUNING_NO_FLOAT_CHECK").set;
     return t;
 }
 
@@ -140,6 +145,7 @@ struct EmPlan {
     // had the field (A/B in one build, and the cross-check of the two-loop form in the tests)
     uint32_t lead_mask = ~0u;
     uint32_t resample_cut = 256;     // (the variable is read by a resampling handle with counts only)
+    bool no_fused_mstep = false, no_float_check = false;   // EmTuning's, for the handle's steps (em_step.h, em_check_float)
 };
 
 inline EmPlan em_plan(const EmShape &s, const EmTuning &t) {
@@ -149,6 +155,8 @@ inline EmPlan em_plan(const EmShape &s, const EmTuning &t) {
     p.deterministic = (f & GBRS_EM_DETERMINISTIC) != 0;
     p.weighted = em_weighted(f, s.counts_given);
     p.side_by_side = (f & GBRS_EM_SIDE_BY_SIDE) ? 2u : 1u;
+    p.no_fused_mstep = t.no_fused_mstep;
+    p.no_float_check = t.no_float_check;
     if ((f & GBRS_EM_RESAMPLE) && s.counts_given) p.resample_cut = t.resample_cut;
     p.tiled = !(f & GBRS_EM_LAYOUT_CSC) && s.H <= 16 && s.N < 0xFFFFFFFFull;
     p.tH = s.H;

@@ -37,6 +37,7 @@ CONFIGS = [
     ("tile_words_64", 0, dict(TILE_WORDS=64)),
     ("persistent", 0, dict(PERSISTENT=1, PERSISTENT_GROUPS=2)),
     ("half_loci", 0, dict(HALF_LOCI=1)),            # 16 haplotypes only
+    ("two_launch_mstep", 0, dict(NO_FUSED_MSTEP=1)),
 ]
 
 
@@ -159,6 +160,40 @@ def test_no_entries(name, monkeypatch):
             eng.run(model=4, tol=0.0, max_iters=tc.STEPS)
         assert np.isfinite(eng.theta()).all() and np.isfinite(eng.expected_counts()).all(), label
         eng.close()
+
+
+# ---- one shard of a sharded run: the caller all-reduces acc between the two halves of a pass --------------------------------
+
+# the long rows' sums added by the gather, no tile to launch, the per-locus M-step, the width-16 tiles, the CSC kernels
+SINGLE_SHARD = ["row_of_33_words_h8", "only_a_long_row_h8", "sweep_h3", "sweep_h16", "sweep_h24"]
+
+
+@pytest.mark.parametrize("name", SINGLE_SHARD)
+def test_single_shard_partial_sequence(name, monkeypatch):
+    """prepare_partial -> finish_prepare, then three times estep_partial -> finish_step with its err_sum, as one shard that
+    has nothing to add to its own acc; a step of the handle's own after that gathers all of acc as well."""
+    case = CASES[name]
+    want = tc.expected_of(case)
+    eng = create(case, 0, {}, monkeypatch)
+    ptr, n = eng.prepare_partial()
+    assert ptr and n == case.H * case.L
+    eng.finish_prepare(0.0)
+    close(eng.theta(), want.theta0)
+    errs = []
+    for k in range(tc.STEPS):
+        assert eng.estep_partial() == (ptr, n)
+        errs.append(eng.finish_step(want_err=True))
+        theta = eng.theta()
+        print(f"SHARD_DEVIATION {name} step={k} theta={deviation(theta, want.theta[k]):.3e} "
+              f"err_abs={abs(errs[k] - want.err[k]):.3e}")
+        close(theta, want.theta[k])
+    close(eng.expected_counts(), want.counts)
+    np.testing.assert_allclose(errs, want.err, rtol=ERR_RTOL, atol=ERR_ATOL)
+    if name == "row_of_33_words_h8":
+        eng.step(1)
+        one_more = tc.dense(tc.exact_of(case).prepare(0.0).step(tc.STEPS + 1).theta, case.H, case.L)
+        close(eng.theta(), one_more)
+    eng.close()
 
 
 # ---- device arrays -----------------------------------------------------------------------------------------------------------

@@ -86,6 +86,14 @@ def build_parser():
                         'writes <outbase>.sim_geno.npz (state indices, K x genes per chromosome) and '
                         '<outbase>.sim_geno.crossovers.tsv (founder changes of the draws beside the Viterbi path\'s)')
     r.add_argument('--sim-geno-seed', type=int, default=0, metavar='S', help='with --sim-geno: seed of the draws (default 0)')
+    r.add_argument('--diagnostics', action='store_true',
+                   help='(extension) writes <outbase>.diagnostics.npz (per gene interval the expected founder changes and the '
+                        'probability of a diplotype change, per gene the error LOD and the most likely diplotype) and '
+                        '<outbase>.diagnostics.tsv (a summary per chromosome), from the posteriors on the device')
+    r.add_argument('--error-lod-threshold', type=float, default=2.0, metavar='T',
+                   help='with --diagnostics: an expressed gene whose error LOD is above T counts as flagged (default 2.0)')
+    r.add_argument('--gene-report', default=None, metavar='PATH',
+                   help='with --diagnostics and --sample-file: one line per gene over the samples of the cohort')
     r.add_argument('-t', '--tprob-file', required=True, type=_existing)
     r.add_argument('-x', '--avec-file', type=_existing, default=None)
     r.add_argument('-g', '--gpos-file', type=_existing, default=None)
@@ -238,6 +246,9 @@ def main(argv=None) -> int:
         if args.command == 'reconstruct':
             from .hmm import check_sim_geno_args
             check_sim_geno_args(args.sim_geno, args.sim_geno_seed)
+            from .hmm import check_diagnostics_args
+            check_diagnostics_args(args.diagnostics, args.error_lod_threshold, args.gene_report,
+                                   cohort=args.sample_file is not None)
         if args.command == 'quantify' and args.gpus is not None:
             # N child processes, one per rank; this process opens no device
             from .sharded import launch
@@ -349,14 +360,16 @@ def main(argv=None) -> int:
                              avec_file=args.avec_file, gpos_file=args.gpos_file, expr_threshold=args.expr_threshold,
                              sigma=args.sigma, device=args.device, batch_size=args.batch_size, grid_file=args.grid_file,
                              grid_genoprobs=args.grid_genoprobs, stage_times=stages, sim_geno=args.sim_geno,
-                             sim_geno_seed=args.sim_geno_seed)
+                             sim_geno_seed=args.sim_geno_seed, diagnostics=args.diagnostics,
+                             error_lod_threshold=args.error_lod_threshold, gene_report=args.gene_report)
         else:
             from .hmm import reconstruct
             reconstruct(expression_file=args.expression_file, tprob_file=args.tprob_file,
                         avec_file=args.avec_file, gpos_file=args.gpos_file,
                         expr_threshold=args.expr_threshold, sigma=args.sigma, outbase=args.outbase,
                         device=args.device, stage_times=stages, grid_file=args.grid_file,
-                        grid_genoprobs=args.grid_genoprobs, sim_geno=args.sim_geno, sim_geno_seed=args.sim_geno_seed)
+                        grid_genoprobs=args.grid_genoprobs, sim_geno=args.sim_geno, sim_geno_seed=args.sim_geno_seed,
+                        diagnostics=args.diagnostics, error_lod_threshold=args.error_lod_threshold)
     except Exception as e:   # noqa: BLE001 - mirror of the reference's catch-all
         failure = e
         if logger.level == logging.DEBUG:

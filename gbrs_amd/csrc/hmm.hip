@@ -2485,6 +2485,7 @@ __global__ void dosage_kernel(int H, int S, int64_t rows, const double *__restri
 
 #include "hmm_grid.inc"
 #include "hmm_sample.inc"
+#include "hmm_diag.inc"
 
 }  // namespace gbrs
 
@@ -2566,6 +2567,11 @@ struct gbrs_hmm {
     DevBuf<uint32_t> smp_streams;
     DevBuf<unsigned long long> smp_degenerate;
     double t_sample = 0;
+    // Diagnostics (hmm_diag.inc): the device images of the five outputs, [n][total_genes] each, and the pair posteriors
+    // of one (sample, chromosome); sized by the last call that asked for them
+    DevBuf<double> diag_xo, diag_pswitch, diag_errlod, diag_maxprob, diag_xi;
+    DevBuf<int32_t> diag_maxmarg;
+    double t_diag = 0;
 };
 
 namespace {
@@ -3854,6 +3860,110 @@ int gbrs_hmm_sample_info(gbrs_hmm_t *h, double *last_ms, uint64_t *device_bytes)
     if (device_bytes)
         *device_bytes = h->smp_change_tab.bytes() + h->smp_cols.bytes() + h->smp_paths.bytes() + h->smp_changes.bytes() +
                         h->smp_streams.bytes() + h->smp_degenerate.bytes();
+    return GBRS_OK;
+}
+
+namespace {
+
+// the founder-change table of the path draws serves the pair pass too
+int diag_change_table(gbrs_hmm *h) {
+    if (h->smp_change_tab.p) return GBRS_OK;
+    const std::vector<uint8_t> tab = sample_change_table(h->H);
+    GBRS_TRY(h->smp_change_tab.alloc(tab.size()));
+    GBRS_HIP_CHECK(hipMemcpy(h->smp_change_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice));
+    return GBRS_OK;
+}
+
+}  // namespace
+
+int gbrs_hmm_diagnostics(gbrs_hmm_t *h, int sample, double *xo, double *pswitch, double *errlod, double *maxprob,
+                         int32_t *maxmarg) {
+    RoctxRange roctx_range("gbrs_hmm_diagnostics");
+    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (!h->ran) return fail(GBRS_ERR_STATE, "run() has not been called");
+    if (sample < -1 || sample >= h->n_samples) return fail(GBRS_ERR_INVALID, "sample out of range");
+    GBRS_TRY(select_device(h->device));
+    const int S = h->S, n = sample < 0 ? h->n_samples : 1, sample0 = std::max(sample, 0);
+    const size_t G = (size_t)h->total_genes, cells = (size_t)n * G;
+    const bool pair = xo || pswitch, gene = errlod || maxprob || maxmarg;
+    h->t_diag = 0;
+    if (cells == 0 || !(pair || gene)) return GBRS_OK;
+    if (pair || errlod) GBRS_TRY(hmm_make_logs(h));
+    if (pair) GBRS_TRY(diag_change_table(h));
+    if (xo && h->diag_xo.n < cells) GBRS_TRY(h->diag_xo.alloc(cells));
+    if (pswitch && h->diag_pswitch.n < cells) GBRS_TRY(h->diag_pswitch.alloc(cells));
+    if (errlod && h->diag_errlod.n < cells) GBRS_TRY(h->diag_errlod.alloc(cells));
+    if (maxprob && h->diag_maxprob.n < cells) GBRS_TRY(h->diag_maxprob.alloc(cells));
+    if (maxmarg && h->diag_maxmarg.n < cells) GBRS_TRY(h->diag_maxmarg.alloc(cells));
+    GBRS_HIP_CHECK(hipEventRecord(h->ev[0], h->stream));
+    if (pair) {
+        // samples of one workgroup: it reads a table block once for all of them.  Four per wavefront keep the grid wide
+        // at cohort sizes; GBRS_TUNING_DIAG_SLAB names a count instead.  A value does not depend on the cut.
+        int slab = 4 * DIAG_WAVES;
+        if (const char *e = std::getenv("GBRS_TUNING_DIAG_SLAB"); e && std::atoi(e) > 0) slab = std::atoi(e);
+        slab = std::min(slab, n);
+        const dim3 grid((unsigned)((G + DIAG_RUN - 1) / DIAG_RUN), (unsigned)((n + slab - 1) / slab));
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, dim3(DIAG_BLOCK), diag_pair_lds(S), h->stream, S, h->n_chrom, h->total_genes,
+                               (int64_t)0, h->total_genes, sample0, n, slab, h->d_chroms.p, h->alpha.p, h->beta.p, h->eprob.p,
+                               h->tprob.p, h->smp_change_tab.p, xo ? h->diag_xo.p : nullptr,
+                               pswitch ? h->diag_pswitch.p : nullptr, (double *)nullptr);
+        };
+        if (diag_table_in_lds(S)) launch(diag_pair_kernel<true, false>);
+        else launch(diag_pair_kernel<false, false>);
+    }
+    if (gene) {
+        const int64_t rows = (int64_t)cells;
+        hipLaunchKernelGGL(diag_gene_kernel, dim3((unsigned)((rows + DIAG_WAVES - 1) / DIAG_WAVES)), dim3(DIAG_BLOCK), 0,
+                           h->stream, S, h->total_genes, sample0, rows, h->init_vec.p, h->alpha.p, h->beta.p, h->eprob.p,
+                           h->gamma.p, errlod ? h->diag_errlod.p : nullptr, maxprob ? h->diag_maxprob.p : nullptr,
+                           maxmarg ? h->diag_maxmarg.p : nullptr);
+    }
+    GBRS_HIP_CHECK(hipEventRecord(h->ev[1], h->stream));
+    GBRS_HIP_CHECK(hipGetLastError());
+    GBRS_HIP_CHECK(hipStreamSynchronize(h->stream));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, h->ev[0], h->ev[1]) == hipSuccess) h->t_diag = ms;
+    if (xo) GBRS_HIP_CHECK(hipMemcpy(xo, h->diag_xo.p, cells * sizeof(double), hipMemcpyDeviceToHost));
+    if (pswitch) GBRS_HIP_CHECK(hipMemcpy(pswitch, h->diag_pswitch.p, cells * sizeof(double), hipMemcpyDeviceToHost));
+    if (errlod) GBRS_HIP_CHECK(hipMemcpy(errlod, h->diag_errlod.p, cells * sizeof(double), hipMemcpyDeviceToHost));
+    if (maxprob) GBRS_HIP_CHECK(hipMemcpy(maxprob, h->diag_maxprob.p, cells * sizeof(double), hipMemcpyDeviceToHost));
+    if (maxmarg) GBRS_HIP_CHECK(hipMemcpy(maxmarg, h->diag_maxmarg.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return GBRS_OK;
+}
+
+int gbrs_hmm_pair_posterior(gbrs_hmm_t *h, int sample, int chrom, double *xi) {
+    RoctxRange roctx_range("gbrs_hmm_pair_posterior");
+    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (!h->ran) return fail(GBRS_ERR_STATE, "run() has not been called");
+    if (sample < 0 || sample >= h->n_samples || chrom < 0 || chrom >= h->n_chrom)
+        return fail(GBRS_ERR_INVALID, "sample/chromosome out of range");
+    if (!xi) return fail(GBRS_ERR_INVALID, "xi is NULL");
+    const ChromDesc &cd = h->chroms[chrom];
+    if (cd.n_genes < 2) return GBRS_OK;                  // no interval
+    GBRS_TRY(select_device(h->device));
+    GBRS_TRY(hmm_make_logs(h));
+    GBRS_TRY(diag_change_table(h));
+    const int S = h->S;
+    const size_t cells = (size_t)(cd.n_genes - 1) * S * S;
+    if (h->diag_xi.n < cells) GBRS_TRY(h->diag_xi.alloc(cells));
+    const dim3 grid((unsigned)((cd.n_genes + DIAG_RUN - 1) / DIAG_RUN), 1u);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(DIAG_BLOCK), diag_pair_lds(S), h->stream, S, h->n_chrom, h->total_genes,
+                           cd.gene_off, cd.gene_off + cd.n_genes, sample, 1, 1, h->d_chroms.p, h->alpha.p, h->beta.p,
+                           h->eprob.p, h->tprob.p, h->smp_change_tab.p, (double *)nullptr, (double *)nullptr, h->diag_xi.p);
+    };
+    if (diag_table_in_lds(S)) launch(diag_pair_kernel<true, true>);
+    else launch(diag_pair_kernel<false, true>);
+    GBRS_HIP_CHECK(hipGetLastError());
+    GBRS_HIP_CHECK(hipStreamSynchronize(h->stream));
+    GBRS_HIP_CHECK(hipMemcpy(xi, h->diag_xi.p, cells * sizeof(double), hipMemcpyDeviceToHost));
+    return GBRS_OK;
+}
+
+int gbrs_hmm_diagnostics_info(gbrs_hmm_t *h, double *last_ms) {
+    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (last_ms) *last_ms = h->t_diag;
     return GBRS_OK;
 }
 

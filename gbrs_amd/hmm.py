@@ -195,6 +195,47 @@ class DiplotypeHMM:
         _lib.check(_lib.load().gbrs_hmm_sample_info(self._h, C.byref(ms), C.byref(nbytes)))
         return ms.value, nbytes.value
 
+    DIAGNOSTICS = ('xo', 'pswitch', 'errlod', 'maxprob', 'maxmarg')
+
+    def diagnostics(self, sample=None, want=DIAGNOSTICS):
+        """Diagnostics of the last run, one device pass over the pair posteriors for `xo` / `pswitch` and
+        one over the genes for the rest; only what `want` names is computed.  sample=None: every sample of the run (n of
+        them); an index: that sample, without the leading axis.  Returns per name a list over the handle's chromosomes of
+        arrays (n?, n_c) - `xo` (expected founder changes between genes i and i + 1) and `pswitch` (the probability that
+        the diplotype changes there) cut to n_c - 1; `errlod` the error LOD of every gene, `maxmarg` (int32) the first
+        most likely diplotype and `maxprob` its posterior."""
+        unknown = [k for k in want if k not in self.DIAGNOSTICS]
+        if unknown:
+            raise ValueError(f'unknown diagnostics: {unknown}')
+        n = self.n_samples if sample is None else 1
+        total = int(self.n_genes.sum())
+        flat = {k: np.empty((n, total), dtype=np.int32 if k == 'maxmarg' else np.float64) if k in want else None
+                for k in self.DIAGNOSTICS}
+        _lib.check(_lib.load().gbrs_hmm_diagnostics(self._h, -1 if sample is None else int(sample),
+                                                    *[_lib.ptr(flat[k]) for k in self.DIAGNOSTICS]))
+        offs = np.concatenate(([0], np.cumsum(self.n_genes)))
+        out = {}
+        for k in want:
+            cut = 1 if k in ('xo', 'pswitch') else 0
+            per = [flat[k][:, offs[c]:max(offs[c + 1] - cut, offs[c])] for c in range(len(self.chroms))]
+            out[k] = per if sample is None else [a[0] for a in per]
+        return out
+
+    def pair_posterior(self, chrom, sample=0):
+        """(n_c - 1, S, S): xi[i][k][j], the posterior that the sample has diplotype k at gene i and j at gene i + 1 of
+        the chromosome (an index or a name), from the last run."""
+        c = chrom if isinstance(chrom, int) else self.chroms.index(chrom)
+        n = int(self.n_genes[c]) if 0 <= c < len(self.chroms) else 1     # out of range: the library says so
+        xi = np.empty((max(n - 1, 1), self.S, self.S))
+        _lib.check(_lib.load().gbrs_hmm_pair_posterior(self._h, int(sample), c, _lib.ptr(xi)))
+        return xi[:max(n - 1, 0)]
+
+    def diagnostics_info(self):
+        """Device milliseconds of the last diagnostics call's kernels."""
+        ms = C.c_double()
+        _lib.check(_lib.load().gbrs_hmm_diagnostics_info(self._h, C.byref(ms)))
+        return ms.value
+
     def info(self):
         inf = _lib.HmmInfo()
         _lib.check(_lib.load().gbrs_hmm_info(self._h, C.byref(inf)))
@@ -531,11 +572,132 @@ def _draw_paths(hmm, n_draws, seed, streams, sample=None):
     return out
 
 
+def check_diagnostics_args(diagnostics=False, error_lod_threshold=2.0, gene_report=None, cohort=False):
+    """`--diagnostics [--error-lod-threshold T] [--gene-report PATH]`: T a finite number; the gene report needs the
+    diagnostics and a cohort (`--sample-file`).  Refused before a file is read."""
+    try:
+        finite = bool(np.isfinite(float(error_lod_threshold)))
+    except (TypeError, ValueError):
+        finite = False
+    if not finite:
+        raise RuntimeError('--error-lod-threshold must be a finite number')
+    if gene_report is not None and not (diagnostics and cohort):
+        raise RuntimeError('--gene-report needs --diagnostics and --sample-file')
+
+
+def expressed_genes(rows, expr_threshold):
+    """bool per gene of a chromosome's TPM rows (n_c x H): the emission's own test - the founders' TPMs added left to
+    right are not below the threshold.  A gene that fails it carries the prior as its emission."""
+    rows = np.asarray(rows, dtype=np.float64)
+    total = np.zeros(rows.shape[0])
+    for x in range(rows.shape[1]):
+        total = total + rows[:, x]
+    return ~(total < expr_threshold)
+
+
+def _diagnose(hmm, rows_of, expr_threshold, sample=None):
+    """Per sample of the call what `--diagnostics` saves: per chromosome the five arrays of DiplotypeHMM.diagnostics and
+    the expressed flags of the sample's TPM rows (rows_of[j]: sample j's rows per chromosome), and the Viterbi path's
+    founder changes per chromosome."""
+    got = hmm.diagnostics(sample=sample)
+    table = change_table(hmm.H)
+    picked = [sample] if sample is not None else list(range(hmm.n_samples))
+    out = []
+    for j, s in enumerate(picked):
+        per = {k: [a if sample is not None else a[j] for a in got[k]] for k in got}
+        per['expressed'] = [expressed_genes(r, expr_threshold) for r in rows_of[j]]
+        per['viterbi'] = [viterbi_changes(hmm.get(k, sample=s, want=('calls',))['calls'], table)
+                          for k in range(len(hmm.chroms))]
+        out.append(per)
+    return out
+
+
+def _no_diagnostics():
+    return dict({k: [] for k in DiplotypeHMM.DIAGNOSTICS}, expressed=[], viterbi=[])
+
+
+def _save_diagnostics(stem, ctx, diplotypes, diag, threshold, threads=None):
+    """A sample's two files of `--diagnostics`: `<stem>.diagnostics.npz` (per chromosome c `xo_<c>`, `pswitch_<c>`
+    (n_c - 1), `errlod_<c>`, `maxprob_<c>`, `maxmarg_<c>`, `expressed_<c>` (n_c), and `diplotypes`) and
+    `<stem>.diagnostics.tsv` (per chromosome and in total: genes, expressed genes, the founder changes of the Viterbi
+    path, the expected founder changes, the expressed genes whose error LOD is above the threshold, the largest error LOD
+    among the expressed genes and the mean posterior of the most likely diplotype; nan where there is nothing to take
+    them over).  Unexpressed genes carry the prior as their emission: their error LOD is saved and counted nowhere."""
+    out_npz, out_tsv = f'{stem}.diagnostics.npz', f'{stem}.diagnostics.tsv'
+    logger.info(f'Saving Diagnostics: {out_npz}')
+    arrays = {}
+    for k, c in enumerate(ctx.chroms[:len(diag['errlod'])]):
+        for name in DiplotypeHMM.DIAGNOSTICS + ('expressed',):
+            arrays[f'{name}_{c}'] = np.ascontiguousarray(diag[name][k])
+    arrays['diplotypes'] = np.asarray(diplotypes)
+    savez_compressed(out_npz, arrays, threads=threads)
+    logger.info(f'Saving Diagnostics Summary: {out_tsv}')
+
+    def line(name, genes, expressed, viterbi, xo, errlod, maxprob):
+        lods = errlod[expressed]
+        return '%s\t%d\t%d\t%d\t%.6f\t%d\t%.6f\t%.6f\n' % (
+            name, genes, int(expressed.sum()), viterbi, float(xo.sum()), int((lods > threshold).sum()),
+            float(lods.max()) if len(lods) else float('nan'), float(maxprob.mean()) if genes else float('nan'))
+
+    with open(out_tsv, 'w') as out:
+        out.write('#Chromosome\tGenes\tExpressed\tViterbi\tExpectedCrossovers\tFlagged\tMaxErrorLOD\tMeanMaxProb\n')
+        n_chrom = len(diag['errlod'])
+        for k, c in enumerate(ctx.chroms[:n_chrom]):
+            out.write(line(c, len(diag['errlod'][k]), diag['expressed'][k], diag['viterbi'][k], diag['xo'][k],
+                           diag['errlod'][k], diag['maxprob'][k]))
+
+        def whole(name, dtype=np.float64):                 # over the chromosomes; a sample without any: empty
+            return np.concatenate([np.zeros(0, dtype=dtype)] + [np.asarray(a, dtype=dtype) for a in diag[name]])
+
+        out.write(line('total', len(whole('errlod')), whole('expressed', bool), int(sum(diag['viterbi'])), whole('xo'),
+                       whole('errlod'), whole('maxprob')))
+
+
+class GeneReport:
+    """`--gene-report`: per gene of the handle, over the samples of a cohort that ran, how many express it, in how many of
+    those its error LOD is above the threshold, and the mean and the largest error LOD among them.  Added up on the host
+    from the arrays every launch copies out."""
+
+    def __init__(self, ctx, threshold):
+        self.ids = [g for c in ctx.chroms for g in ctx.gene_order[c]]
+        self.chrom_of = [c for c in ctx.chroms for _ in ctx.gene_order[c]]
+        n = len(self.ids)
+        self.threshold = threshold
+        self.samples = 0
+        self.expressed = np.zeros(n, dtype=np.int64)
+        self.flagged = np.zeros(n, dtype=np.int64)
+        self.total = np.zeros(n)
+        self.largest = np.full(n, -np.inf)
+
+    def add(self, diag):
+        if not diag['errlod']:
+            return
+        lod = np.concatenate(diag['errlod'])
+        on = np.concatenate(diag['expressed'])
+        self.samples += 1
+        self.expressed += on
+        self.flagged += on & (lod > self.threshold)
+        self.total += np.where(on, lod, 0.0)
+        self.largest = np.where(on, np.maximum(self.largest, lod), self.largest)
+
+    def write(self, path):
+        logger.info(f'Saving Gene Report: {path}')
+        with np.errstate(invalid='ignore', divide='ignore'):
+            mean = np.where(self.expressed > 0, self.total / self.expressed, np.nan)
+        largest = np.where(self.expressed > 0, self.largest, np.nan)
+        with open(path, 'w') as out:
+            out.write('#Gene_ID\tChromosome\tSamples\tExpressed\tFlagged\tMeanErrorLOD\tMaxErrorLOD\n')
+            for k, gid in enumerate(self.ids):
+                out.write('%s\t%s\t%d\t%d\t%d\t%.6f\t%.6f\n' % (gid, self.chrom_of[k], self.samples, self.expressed[k],
+                                                                self.flagged[k], mean[k], largest[k]))
+
+
 def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gpos_file: str = None,
                 expr_threshold: float = 1.5, sigma: float = 0.12, outbase: str = None,
                 device: int = 0, stage_times: dict = None, context: ReconstructContext = None,
                 grid_file: str = None, grid_genoprobs: bool = False, sim_geno: int = None,
-                sim_geno_seed: int = 0) -> None:
+                sim_geno_seed: int = 0, diagnostics: bool = False, error_lod_threshold: float = 2.0,
+                gene_report: str = None) -> None:
     """`gbrs reconstruct`: diplotype posteriors and Viterbi calls along every chromosome from
     gene-level TPMs.  Same inputs, defaults and three output files as gbrs_utils.reconstruct
     (gbrs_utils.py:382-609); the emission model and the three recursions run on the device.
@@ -547,8 +709,13 @@ def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gp
     `gbrs interpolate`; with `grid_genoprobs` `<outbase>.interpolated.genoprobs.npz` holds what `gbrs interpolate`
     writes.  `sim_geno` = K (extension): K diplotype paths per chromosome drawn from the joint posterior on the device
     (stream 0, seed `sim_geno_seed`) go to `<outbase>.sim_geno.npz`, their founder changes beside the Viterbi path's to
-    `<outbase>.sim_geno.crossovers.tsv`; without it the run makes no log-domain arrays and reaches none of that code."""
+    `<outbase>.sim_geno.crossovers.tsv`; without it the run makes no log-domain arrays and reaches none of that code.
+    `diagnostics` (extension): the expected founder changes and the switch probability of every gene interval, and per
+    gene the error LOD and the most likely diplotype, go to `<outbase>.diagnostics.npz`, a summary per chromosome with the
+    expressed genes whose error LOD is above `error_lod_threshold` to `<outbase>.diagnostics.tsv` (DESIGN.md §23);
+    `gene_report` belongs to a cohort (reconstruct_many) and is refused here."""
     check_sim_geno_args(sim_geno, sim_geno_seed)
+    check_diagnostics_args(diagnostics, error_lod_threshold, gene_report, cohort=False)
     clock = time.perf_counter
     marks = stage_times if stage_times is not None else {}
     stem = 'gbrs.reconstructed' if outbase is None else outbase
@@ -578,7 +745,7 @@ def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gp
     marks['load'] = clock() - t0
 
     posterior, path_names, calls = {}, {}, {}
-    on_grid = drawn = None
+    on_grid = drawn = diag = None
     if chroms:
         t0 = clock()
         hmm, _ = ctx.handle(num_haps)
@@ -593,16 +760,23 @@ def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gp
         hmm.run()
         logger.info('Getting forward-backward probability')
         posterior, path_names, calls = _collect(ctx, hmm, 0, diplotypes)
-        if context is None and ctx.grid is None and sim_geno is None:
+        if context is None and ctx.grid is None and sim_geno is None and not diagnostics:
             ctx.close()
         marks['hmm'] = clock() - t0
         if sim_geno is not None:
             t0 = clock()
             logger.info(f'Drawing {sim_geno} paths from the posterior')
             drawn = _draw_paths(hmm, sim_geno, sim_geno_seed, [0], sample=0)[0]
-            if context is None and ctx.grid is None:
+            if context is None and ctx.grid is None and not diagnostics:
                 ctx.close()
             marks['sim_geno'] = clock() - t0
+        if diagnostics:
+            t0 = clock()
+            logger.info('Getting crossover expectations and gene error LODs')
+            diag = _diagnose(hmm, [rows], expr_threshold, sample=0)[0]
+            if context is None and ctx.grid is None:
+                ctx.close()
+            marks['diagnostics'] = clock() - t0
         if ctx.grid is not None:
             t0 = clock()
             logger.info('Converting genotype probability on the grid')
@@ -614,6 +788,8 @@ def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gp
         on_grid = {'dosage': np.zeros((0, num_haps)), 'gamma_grid': [] if grid_genoprobs else None}
     if sim_geno is not None and drawn is None:
         drawn = ([], np.zeros((sim_geno, 0), dtype=np.int32), [])
+    if diagnostics and diag is None:
+        diag = _no_diagnostics()
 
     t0 = clock()
     _save_reconstruction(stem, posterior, path_names, calls)
@@ -621,6 +797,8 @@ def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gp
         _save_grid(stem, ctx, haplotypes, on_grid['dosage'], on_grid.get('gamma_grid'))
     if drawn is not None:
         _save_sim_geno(stem, ctx, diplotypes, drawn, sim_geno_seed, 0)
+    if diag is not None:
+        _save_diagnostics(stem, ctx, diplotypes, diag, error_lod_threshold)
     marks['save'] = clock() - t0
     logger.info('Done')
 
@@ -644,15 +822,19 @@ def read_sample_file(sample_file):
 def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str = None, gpos_file: str = None,
                      expr_threshold: float = 1.5, sigma: float = 0.12, device: int = 0, batch_size: int = 64,
                      grid_file: str = None, grid_genoprobs: bool = False, stage_times: dict = None,
-                     context: ReconstructContext = None, sim_geno: int = None, sim_geno_seed: int = 0) -> list:
+                     context: ReconstructContext = None, sim_geno: int = None, sim_geno_seed: int = 0,
+                     diagnostics: bool = False, error_lod_threshold: float = 2.0, gene_report: str = None) -> list:
     """`gbrs reconstruct` for a cohort whose genes.tpm files exist (extension): one context, the tables on the device
     once, the samples through the HMM in launches of up to `batch_size`, and with `grid_file` one grid pass per launch.
     Every sample gets the files the single-sample call writes for its outbase.  All samples must carry the same
     haplotype header (RuntimeError before anything runs otherwise).  A sample whose file cannot be read or lacks a gene
     is logged and left out, and the others go on.  Returns one dict per sample: its outbase and, if it failed,
     `error`.  `sim_geno` = K: one more device pass per launch draws K paths per sample and chromosome; a sample's stream
-    is its 0-based position in `expression_files`, so its draws do not depend on the batch it ran in."""
+    is its 0-based position in `expression_files`, so its draws do not depend on the batch it ran in.  `diagnostics`: two
+    more device passes per launch and every sample's two diagnostics files; `gene_report`: one line per gene of the handle
+    over the samples that ran (how many express it, in how many of those its error LOD is above `error_lod_threshold`)."""
     check_sim_geno_args(sim_geno, sim_geno_seed)
+    check_diagnostics_args(diagnostics, error_lod_threshold, gene_report, cohort=True)
     clock = time.perf_counter
     marks = stage_times if stage_times is not None else {}
     if len(expression_files) != len(outbases):
@@ -691,12 +873,16 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
     writers = ThreadPoolExecutor(max_workers=min(16, batch_size))
     pending = []
 
-    def save(k, results, on_grid, drawn=None):
+    def save(k, results, on_grid, drawn=None, diag=None):
         _save_reconstruction(outbases[k], *results, threads=1)
         if on_grid is not None:
             _save_grid(outbases[k], ctx, haplotypes, on_grid[0], on_grid[1], threads=1)
         if drawn is not None:
             _save_sim_geno(outbases[k], ctx, diplotypes, drawn, sim_geno_seed, k, threads=1)
+        if diag is not None:
+            _save_diagnostics(outbases[k], ctx, diplotypes, diag, error_lod_threshold, threads=1)
+
+    report = None
 
     try:
         order = sorted(headers)
@@ -714,7 +900,8 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
             if not members or not ctx.chroms:
                 nothing = None if sim_geno is None else ([], np.zeros((sim_geno, 0), dtype=np.int32), [])
                 for k in members:
-                    pending.append((k, writers.submit(save, k, ({}, {}, {}), None, nothing)))
+                    pending.append((k, writers.submit(save, k, ({}, {}, {}), None, nothing,
+                                                      _no_diagnostics() if diagnostics else None)))
                 continue
             t0 = clock()
             first_use = ctx.hmm is None or ctx.hmm.H != num_haps
@@ -738,10 +925,21 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
                 t0 = clock()
                 drawn = _draw_paths(hmm, sim_geno, sim_geno_seed, members)
                 marks['sim_geno'] = marks.get('sim_geno', 0.0) + clock() - t0
+            diags = None
+            if diagnostics:
+                t0 = clock()
+                diags = _diagnose(hmm, rows, expr_threshold)
+                if gene_report is not None:
+                    if report is None:
+                        report = GeneReport(ctx, error_lod_threshold)
+                    for d in diags:
+                        report.add(d)
+                marks['diagnostics'] = marks.get('diagnostics', 0.0) + clock() - t0
             t0 = clock()
             for s, k in enumerate(members):
                 grid_of = None if on_grid is None else (on_grid['dosage'][s], on_grid['gamma_grid'][s] if grid_genoprobs else None)
-                pending.append((k, writers.submit(save, k, results[s], grid_of, None if drawn is None else drawn[s])))
+                pending.append((k, writers.submit(save, k, results[s], grid_of, None if drawn is None else drawn[s],
+                                                  None if diags is None else diags[s])))
             marks['save'] += clock() - t0
         t0 = clock()
         for k, job in pending:
@@ -749,6 +947,8 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
                 job.result()
             except Exception as e:   # noqa: BLE001
                 failed(k, e)
+        if gene_report is not None:
+            (report if report is not None else GeneReport(ctx, error_lod_threshold)).write(gene_report)
         marks['save'] += clock() - t0
     finally:
         writers.shutdown(wait=True)

@@ -12,7 +12,8 @@ jobs.json: a list of objects {"alignment_file", "outbase", "tprob_file", and opt
 "avec_file", "gpos_file", "grid_file", "grid_genoprobs", "expr_threshold", "sigma", "pseudocount", "max_iters", "tolerance",
 "diploid": true|false}; with "grid_file" the sample's reconstruction also leaves `<outbase>.interpolated.genoprobs.tsv`
 (and with "grid_genoprobs" the `.npz`), see `gbrs reconstruct --grid-file`; with "sim_geno": K (and "sim_geno_seed")
-its two `--sim-geno` files, drawn with stream 0;
+its two `--sim-geno` files, drawn with stream 0; with "diagnostics": true (and "error_lod_threshold") its two
+`--diagnostics` files ("gene_report" belongs to a cohort and is refused as `gbrs reconstruct -e` refuses it);
 the stage times of every sample are printed as one JSON line per sample.
 """
 from __future__ import annotations
@@ -83,7 +84,9 @@ class SampleWorker:
                     expr_threshold=job.get('expr_threshold', 1.5), sigma=job.get('sigma', 0.12),
                     outbase=job['outbase'], device=self.device, stage_times=st, context=self._context(job),
                     grid_file=job.get('grid_file'), grid_genoprobs=bool(job.get('grid_genoprobs', False)),
-                    sim_geno=job.get('sim_geno'), sim_geno_seed=job.get('sim_geno_seed', 0))
+                    sim_geno=job.get('sim_geno'), sim_geno_seed=job.get('sim_geno_seed', 0),
+                    diagnostics=bool(job.get('diagnostics', False)),
+                    error_lod_threshold=job.get('error_lod_threshold', 2.0), gene_report=job.get('gene_report'))
         out['reconstruct'] = dict(st, wall=clock() - t0)
         if job.get('diploid', True):
             st = {}

@@ -735,6 +735,31 @@ int gbrs_hmm_sample_paths(gbrs_hmm_t *hmm, int sample, int n_draws, uint64_t see
  * nullable. */
 int gbrs_hmm_sample_info(gbrs_hmm_t *hmm, double *last_ms, uint64_t *device_bytes);
 
+/* Diagnostics of the last run (extension; R/qtl2's count_xo / locate_xo without the draws, and calc_errorlod per gene).
+ * sample = -1: all n samples of the run, else that one (n = 1).  Every output is [n][total_genes], a sample's chromosomes
+ * one after the other in handle order, and nullable; a pass none of whose outputs is asked for is not launched.
+ * With k the state at gene i and j the state at gene i + 1 of a chromosome, E the log emission rows, iv the prior:
+ *   lx[k][j]  = alpha[k][i] + T[i][j][k] + E[i+1][j] + beta[j][i+1],  x = exp(lx - max lx)  (0 where lx is -inf)
+ *   xo        [i]: sum x * change[k][j] / sum x, the expected founder changes (2 - |{a,b} n {c,d}|, multisets) between
+ *             genes i and i + 1; the slot of a chromosome's last gene is 0.0
+ *   pswitch   [i]: sum over k != j of x / sum x, the probability that the diplotype changes; last gene's slot 0.0
+ *   errlod    [i]: (lse(iv + E[i]) - (lse(alpha[:,i] + beta[:,i]) - lse((alpha[:,i] - E[i]) + beta[:,i]))) / ln 10 with
+ *             lse(v) = max v + log sum exp(v - max v), an entry whose alpha is -inf carrying weight 0: log10 of how much
+ *             better the prior predicts gene i's data than the chromosome's other genes do
+ *   maxmarg   [i]: the first index of the largest gamma[:, i];  maxprob [i]: that value
+ * Only T[0 .. n_c - 2] of a chromosome are read.  GBRS_ERR_STATE before the first run, GBRS_ERR_INVALID for a sample out
+ * of range: both before any launch, the outputs untouched. */
+int gbrs_hmm_diagnostics(gbrs_hmm_t *hmm, int sample, double *xo, double *pswitch, double *errlod, double *maxprob,
+                         int32_t *maxmarg);
+
+/* The pair posteriors of one (sample, chromosome) of the last run: xi[i][k][j] = x[k][j] / sum x of the interval
+ * i -> i + 1 as above, double[n_c - 1][S][S]; nothing is written for a chromosome of one gene.  GBRS_ERR_STATE before the
+ * first run; GBRS_ERR_INVALID for a sample or chromosome out of range or xi == NULL; xi untouched on failure. */
+int gbrs_hmm_pair_posterior(gbrs_hmm_t *hmm, int sample, int chrom, double *xi);
+
+/* Device time of the last gbrs_hmm_diagnostics call's kernels (0 if none ran); nullable. */
+int gbrs_hmm_diagnostics_info(gbrs_hmm_t *hmm, double *last_ms);
+
 int gbrs_hmm_destroy(gbrs_hmm_t *hmm);
 
 /* `gbrs interpolate` numeric body (gbrs/gbrs_utils.py:684-688): the rows of y (S x n_points, C

@@ -29,7 +29,8 @@ EXPORTS = [
     "gbrs_hmm_create", "gbrs_hmm_set_expression", "gbrs_hmm_set_eprob", "gbrs_hmm_run",
     "gbrs_hmm_get", "gbrs_hmm_info", "gbrs_hmm_destroy",
     "gbrs_grid_knots", "gbrs_hmm_set_grid", "gbrs_hmm_grid", "gbrs_hmm_grid_info", "gbrs_hmm_sample_paths", "gbrs_hmm_sample_info",
-    "gbrs_hmm_diagnostics", "gbrs_hmm_pair_posterior", "gbrs_hmm_diagnostics_info", "gbrs_interpolate", "gbrs_genoprob_dosage",
+    "gbrs_hmm_diagnostics", "gbrs_hmm_pair_posterior", "gbrs_hmm_diagnostics_info",
+    "gbrs_hmm_loglik", "gbrs_hmm_loglik_tables", "gbrs_hmm_loglik_info", "gbrs_interpolate", "gbrs_genoprob_dosage",
     "gbrs_ri_transition_tables", "gbrs_alignment_spec",
     "gbrs_compress_create", "gbrs_compress_get", "gbrs_compress_destroy",
     "gbrs_bam_open", "gbrs_bam_references", "gbrs_bam_set_reference_map", "gbrs_bam_convert", "gbrs_bam_get",
@@ -181,6 +182,9 @@ def load():
         "gbrs_hmm_diagnostics": [vp, i32, vp, vp, vp, vp, vp],
         "gbrs_hmm_pair_posterior": [vp, i32, i32, vp],
         "gbrs_hmm_diagnostics_info": [vp, C.POINTER(dbl)],
+        "gbrs_hmm_loglik": [vp, i32, vp],
+        "gbrs_hmm_loglik_tables": [vp, i32, i32, vp, pp, i32, vp],
+        "gbrs_hmm_loglik_info": [vp, C.POINTER(dbl), C.POINTER(u64)],
         "gbrs_interpolate": [i32, i32, vp, vp, i32, vp, vp, i32],
         "gbrs_genoprob_dosage": [i32, i64, vp, vp, i32],
         "gbrs_ri_transition_tables": [vp, vp, vp, i64, dbl, dbl, i32, vp],

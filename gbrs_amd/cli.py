@@ -94,6 +94,16 @@ def build_parser():
                    help='with --diagnostics: an expressed gene whose error LOD is above T counts as flagged (default 2.0)')
     r.add_argument('--gene-report', default=None, metavar='PATH',
                    help='with --diagnostics and --sample-file: one line per gene over the samples of the cohort')
+    r.add_argument('--loglik', action='store_true',
+                   help='(extension) also writes <outbase>.loglik.tsv: the data log-likelihood of the sample under the '
+                        'transition tables, per chromosome and in total, from what the forward pass kept on the device')
+    r.add_argument('--alt-tprob-file', action='append', type=_existing, default=None, metavar='PATH',
+                   help='(extension, repeatable, implies --loglik) another transition table file, e.g. the other sex or '
+                        'generation: the sample is scored under every candidate on the device and reconstructed under '
+                        'the one with the largest log-likelihood (-t first on ties)')
+    r.add_argument('--model-report', default=None, metavar='PATH',
+                   help='with --sample-file and --alt-tprob-file: one line per sample with the selected file, the margin '
+                        'and the total per candidate')
     r.add_argument('-t', '--tprob-file', required=True, type=_existing)
     r.add_argument('-x', '--avec-file', type=_existing, default=None)
     r.add_argument('-g', '--gpos-file', type=_existing, default=None)
@@ -249,6 +259,9 @@ def main(argv=None) -> int:
             from .hmm import check_diagnostics_args
             check_diagnostics_args(args.diagnostics, args.error_lod_threshold, args.gene_report,
                                    cohort=args.sample_file is not None)
+            from .hmm import check_loglik_args
+            check_loglik_args(args.loglik, args.alt_tprob_file, args.model_report, cohort=args.sample_file is not None,
+                              tprob_file=args.tprob_file)
         if args.command == 'quantify' and args.gpus is not None:
             # N child processes, one per rank; this process opens no device
             from .sharded import launch
@@ -361,7 +374,8 @@ def main(argv=None) -> int:
                              sigma=args.sigma, device=args.device, batch_size=args.batch_size, grid_file=args.grid_file,
                              grid_genoprobs=args.grid_genoprobs, stage_times=stages, sim_geno=args.sim_geno,
                              sim_geno_seed=args.sim_geno_seed, diagnostics=args.diagnostics,
-                             error_lod_threshold=args.error_lod_threshold, gene_report=args.gene_report)
+                             error_lod_threshold=args.error_lod_threshold, gene_report=args.gene_report,
+                             loglik=args.loglik, alt_tprob_files=args.alt_tprob_file, model_report=args.model_report)
         else:
             from .hmm import reconstruct
             reconstruct(expression_file=args.expression_file, tprob_file=args.tprob_file,
@@ -369,7 +383,8 @@ def main(argv=None) -> int:
                         expr_threshold=args.expr_threshold, sigma=args.sigma, outbase=args.outbase,
                         device=args.device, stage_times=stages, grid_file=args.grid_file,
                         grid_genoprobs=args.grid_genoprobs, sim_geno=args.sim_geno, sim_geno_seed=args.sim_geno_seed,
-                        diagnostics=args.diagnostics, error_lod_threshold=args.error_lod_threshold)
+                        diagnostics=args.diagnostics, error_lod_threshold=args.error_lod_threshold,
+                        loglik=args.loglik, alt_tprob_files=args.alt_tprob_file)
     except Exception as e:   # noqa: BLE001 - mirror of the reference's catch-all
         failure = e
         if logger.level == logging.DEBUG:

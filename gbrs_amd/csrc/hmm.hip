@@ -2486,6 +2486,7 @@ __global__ void dosage_kernel(int H, int S, int64_t rows, const double *__restri
 #include "hmm_grid.inc"
 #include "hmm_sample.inc"
 #include "hmm_diag.inc"
+#include "hmm_loglik.inc"
 
 }  // namespace gbrs
 
@@ -2572,6 +2573,10 @@ struct gbrs_hmm {
     DevBuf<double> diag_xo, diag_pswitch, diag_errlod, diag_maxprob, diag_xi;
     DevBuf<int32_t> diag_maxmarg;
     double t_diag = 0;
+    // Log-likelihood (hmm_loglik.inc): the sums of the last call, and the candidate tables of one chromosome as uploaded
+    // (ll_t) and as exp() transposed per block (ll_pt); they grow to the largest call and are reused
+    DevBuf<double> ll_out, ll_t, ll_pt;
+    double t_loglik = 0;
 };
 
 namespace {
@@ -3964,6 +3969,88 @@ int gbrs_hmm_pair_posterior(gbrs_hmm_t *h, int sample, int chrom, double *xi) {
 int gbrs_hmm_diagnostics_info(gbrs_hmm_t *h, double *last_ms) {
     if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
     if (last_ms) *last_ms = h->t_diag;
+    return GBRS_OK;
+}
+
+int gbrs_hmm_loglik(gbrs_hmm_t *h, int sample, double *loglik) {
+    RoctxRange roctx_range("gbrs_hmm_loglik");
+    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (!h->ran) return fail(GBRS_ERR_STATE, "run() has not been called");
+    if (sample < -1 || sample >= h->n_samples) return fail(GBRS_ERR_INVALID, "sample out of range");
+    if (!loglik) return fail(GBRS_ERR_INVALID, "loglik is NULL");
+    if (h->last.chain_interleaved) return fail(GBRS_ERR_UNSUPPORTED, "the last run left its rows as [gene][sample]");
+    GBRS_TRY(select_device(h->device));
+    const int n = sample < 0 ? h->n_samples : 1, sample0 = std::max(sample, 0);
+    const size_t cells = (size_t)n * h->n_chrom;
+    if (h->ll_out.n < cells) GBRS_TRY(h->ll_out.alloc(cells));
+    GBRS_HIP_CHECK(hipEventRecord(h->ev[0], h->stream));
+    hipLaunchKernelGGL(loglik_reduce_kernel, dim3((unsigned)((h->n_chrom + LL_RED_WAVES - 1) / LL_RED_WAVES), (unsigned)n),
+                       dim3(64 * LL_RED_WAVES), 0, h->stream, h->n_chrom, h->total_genes, sample0, h->d_chroms.p, h->invz.p,
+                       h->ll_out.p);
+    GBRS_HIP_CHECK(hipEventRecord(h->ev[1], h->stream));
+    GBRS_HIP_CHECK(hipGetLastError());
+    GBRS_HIP_CHECK(hipStreamSynchronize(h->stream));
+    float ms = 0.f;
+    h->t_loglik = hipEventElapsedTime(&ms, h->ev[0], h->ev[1]) == hipSuccess ? ms : 0.0;
+    GBRS_HIP_CHECK(hipMemcpy(loglik, h->ll_out.p, cells * sizeof(double), hipMemcpyDeviceToHost));
+    return GBRS_OK;
+}
+
+int gbrs_hmm_loglik_tables(gbrs_hmm_t *h, int chrom, int n_tables, const int32_t *n_trans, const double *const *tprob,
+                           int sample, double *loglik) {
+    RoctxRange roctx_range("gbrs_hmm_loglik_tables");
+    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (!h->ran) return fail(GBRS_ERR_STATE, "run() has not been called");
+    if (sample < -1 || sample >= h->n_samples || chrom < 0 || chrom >= h->n_chrom)
+        return fail(GBRS_ERR_INVALID, "sample/chromosome out of range");
+    if (n_tables < 1) return fail(GBRS_ERR_INVALID, "n_tables must be at least 1");
+    if (!n_trans || !tprob || !loglik) return fail(GBRS_ERR_INVALID, "NULL argument");
+    const ChromDesc &cd = h->chroms[chrom];
+    const int n_steps = cd.n_genes - 1;                    // only T[0 .. n_c - 2] are read
+    for (int k = 0; k < n_tables; ++k) {
+        if (n_trans[k] < n_steps)
+            return fail(GBRS_ERR_INVALID, "index %d is out of bounds for axis 0 with size %d (table %d)", n_steps - 1,
+                        n_trans[k], k);
+        if (n_steps > 0 && !tprob[k]) return fail(GBRS_ERR_INVALID, "tprob[%d] is NULL", k);
+    }
+    if (h->last.chain_interleaved) return fail(GBRS_ERR_UNSUPPORTED, "the last run left its rows as [gene][sample]");
+    GBRS_TRY(select_device(h->device));
+    const int S = h->S, n = sample < 0 ? h->n_samples : 1, sample0 = std::max(sample, 0);
+    const size_t per_table = (size_t)n_steps * S * S, cells = (size_t)n_tables * n;
+    if (h->ll_out.n < cells) GBRS_TRY(h->ll_out.alloc(cells));
+    if (per_table > 0) {
+        if (h->ll_t.n < per_table * n_tables) GBRS_TRY(h->ll_t.alloc(per_table * n_tables));
+        if (h->ll_pt.n < per_table * n_tables) GBRS_TRY(h->ll_pt.alloc(per_table * n_tables));
+        for (int k = 0; k < n_tables; ++k)
+            GBRS_HIP_CHECK(hipMemcpy(h->ll_t.p + per_table * k, tprob[k], per_table * sizeof(double), hipMemcpyHostToDevice));
+    }
+    GBRS_HIP_CHECK(hipEventRecord(h->ev[0], h->stream));
+    if (per_table > 0)          // P = exp(T) once per candidate table, for every sample of the call
+        hipLaunchKernelGGL(exp_blocks_t_kernel, dim3(2048), dim3(256), 0, h->stream, S, (int64_t)n_steps * n_tables, h->ll_t.p,
+                           h->ll_pt.p, S == 36);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)cells), dim3(64), 0, h->stream, S, cd.n_genes, cd.gene_off, h->total_genes,
+                           sample0, n, (int)cells, h->ll_pt.p, h->peprob.p, h->init_vec.p, h->ll_out.p);
+    };
+    if (S <= 8) launch(loglik_tables_kernel<1, 8, 3>);
+    else if (S <= 16) launch(loglik_tables_kernel<1, 16, 3>);
+    else if (S == 36) launch(loglik_tables_kernel<1, 36, 4, 36>);   // 8 founders: the paired layout
+    else if (S < 36) launch(loglik_tables_kernel<1, 36, 3>);
+    else if (S <= 64) launch(loglik_tables_kernel<1, 64, 2>);
+    else launch(loglik_tables_kernel<3, 0, 1>);            // S <= 136 (MAX_H = 16)
+    GBRS_HIP_CHECK(hipEventRecord(h->ev[1], h->stream));
+    GBRS_HIP_CHECK(hipGetLastError());
+    GBRS_HIP_CHECK(hipStreamSynchronize(h->stream));
+    float ms = 0.f;
+    h->t_loglik = hipEventElapsedTime(&ms, h->ev[0], h->ev[1]) == hipSuccess ? ms : 0.0;
+    GBRS_HIP_CHECK(hipMemcpy(loglik, h->ll_out.p, cells * sizeof(double), hipMemcpyDeviceToHost));
+    return GBRS_OK;
+}
+
+int gbrs_hmm_loglik_info(gbrs_hmm_t *h, double *last_ms, uint64_t *device_bytes) {
+    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (last_ms) *last_ms = h->t_loglik;
+    if (device_bytes) *device_bytes = h->ll_out.bytes() + h->ll_t.bytes() + h->ll_pt.bytes();
     return GBRS_OK;
 }
 

@@ -236,6 +236,37 @@ class DiplotypeHMM:
         _lib.check(_lib.load().gbrs_hmm_diagnostics_info(self._h, C.byref(ms)))
         return ms.value
 
+    def loglik(self, sample=None):
+        """float64 (n, n_chrom): the data log-likelihood of the last run per sample and chromosome under the handle's own
+        tables, minus the sum of the run's `scaler` row; one reduction over what the forward pass kept.
+        sample=None: every sample of the run (n of them); an index: that sample (n = 1)."""
+        n = self.n_samples if sample is None else 1
+        out = np.empty((n, len(self.chroms)))
+        _lib.check(_lib.load().gbrs_hmm_loglik(self._h, -1 if sample is None else int(sample), _lib.ptr(out)))
+        return out
+
+    def loglik_tables(self, chrom, tables, sample=None):
+        """float64 (K, n): the data log-likelihood of the last run's emissions on one chromosome (an index or a name) under
+        each of K other transition tables, float64 (n_t, S, S) in natural log with n_t >= n_c - 1; one launch runs the
+        forward recursion for all (table, sample) pairs.  The handle's tables and results stay as they are."""
+        c = chrom if isinstance(chrom, int) else self.chroms.index(chrom)
+        tabs = [np.ascontiguousarray(t, dtype=np.float64) for t in tables]
+        for k, t in enumerate(tabs):
+            if t.ndim != 3 or t.shape[1:] != (self.S, self.S):
+                raise ValueError(f'table {k} has shape {t.shape}, expected (n, {self.S}, {self.S})')
+        n = self.n_samples if sample is None else 1
+        n_trans = np.asarray([len(t) for t in tabs], dtype=np.int32)
+        out = np.empty((len(tabs), n))
+        _lib.check(_lib.load().gbrs_hmm_loglik_tables(self._h, c, len(tabs), _lib.ptr(n_trans), _lib.ptr_table(tabs),
+                                                      -1 if sample is None else int(sample), _lib.ptr(out)))
+        return out
+
+    def loglik_info(self):
+        """(device milliseconds of the last loglik / loglik_tables call's kernels, device bytes their buffers hold)."""
+        ms, nbytes = C.c_double(), C.c_uint64()
+        _lib.check(_lib.load().gbrs_hmm_loglik_info(self._h, C.byref(ms), C.byref(nbytes)))
+        return ms.value, nbytes.value
+
     def info(self):
         inf = _lib.HmmInfo()
         _lib.check(_lib.load().gbrs_hmm_info(self._h, C.byref(inf)))
@@ -353,9 +384,11 @@ class ReconstructContext:
     One command builds one and drops it; a resident process (gbrs_amd.worker) keeps it across samples, so that a sample
     costs its expression rows only."""
 
-    def __init__(self, tprob_file, avec_file=None, gpos_file=None, device=0, grid_file=None):
+    def __init__(self, tprob_file, avec_file=None, gpos_file=None, device=0, grid_file=None, alt_tprob_files=None):
         data_dir = os.getenv('GBRS_DATA', '.')
         self.tprob_file = tprob_file
+        self.alt_tprob_files = list(alt_tprob_files or ())     # candidates beside `tprob_file` (--alt-tprob-file)
+        self.loglik_launches = 0          # device passes made for likelihoods: reductions + candidate chains
         self.avec_file = avec_file or os.path.join(data_dir, 'avecs.npz')
         self.gpos_file = gpos_file or os.path.join(data_dir, 'ref.gene_pos.ordered.npz')
         self.grid_file = grid_file
@@ -379,6 +412,15 @@ class ReconstructContext:
         self.chroms = [c for c in genome if c in tprob]              # chromosomes without a table are skipped (:495)
         reader = ThreadPoolExecutor(max_workers=1)
         tables_pending = reader.submit(tprob.read_many, self.chroms)
+        self._alts_pending = []
+        for f in self.alt_tprob_files:    # behind the base tables on the reader thread
+            z = FastNpz(f)
+            for c in genome:              # the candidates are compared, and a sample may be run again, on the same chromosomes
+                if (c in z) != (c in tprob):
+                    reader.shutdown(wait=False, cancel_futures=True)
+                    raise RuntimeError(f'{f}: ' + (f'no transition table for chromosome {c}' if c in tprob else
+                                                  f'a transition table for chromosome {c}, which {self.tprob_file} lacks'))
+            self._alts_pending.append(reader.submit(z.read_many, self.chroms))
         logger.info(f'Loading alignment specificity: {self.avec_file}')
         self.avecs = FastNpz(self.avec_file)
         logger.info(f'Loading gene meta data: {self.gpos_file}')
@@ -398,6 +440,42 @@ class ReconstructContext:
             self._reader.shutdown(wait=False)
             self._tables_pending = None
         return self._tables
+
+    def alt_tables(self, num_haps):
+        """Per alternative file its tables by handle chromosome, checked against the base: the state count of `num_haps`
+        founders and at least n_genes - 1 blocks, else a RuntimeError that names the file and the chromosome.
+        `alt_same[a][ci]`: the table is np.array_equal to the base's, so its likelihood is the base run's own."""
+        if getattr(self, '_alt_tables', None) is None:
+            base = self.tables()
+            S = num_haps * (num_haps + 1) // 2
+            found, same = [], []
+            for f, job in zip(self.alt_tprob_files, self._alts_pending):
+                logger.info(f'Loading alternative transition probabilities: {f}')
+                tabs = job.result()
+                for c, t in zip(self.chroms, tabs):
+                    n = len(self.gene_order[c])
+                    if t.ndim != 3 or t.shape[1:] != (S, S):
+                        raise RuntimeError(f'{f}: the table of chromosome {c} has shape {t.shape}, expected (n, {S}, {S})')
+                    if len(t) < n - 1:
+                        raise RuntimeError(f'{f}: the table of chromosome {c} has {len(t)} blocks for {n} genes')
+                found.append(tabs)
+                same.append([np.array_equal(t, b) for t, b in zip(tabs, base)])
+            self._alt_tables, self.alt_same, self._alts_pending = found, same, []
+        return self._alt_tables
+
+    def alt_context(self, a):
+        """The context of alternative file `a`: its own device handle on this context's chromosomes, gene order,
+        specificity blocks and grid.  Made at first need and kept until close()."""
+        subs = self.__dict__.setdefault('_alt_contexts', {})
+        if a not in subs:
+            sub = ReconstructContext(self.alt_tprob_files[a], self.avec_file, self.gpos_file, self.device, self.grid_file)
+            sub.chroms, sub.gene_order, sub.grid = self.chroms, self.gene_order, self.grid
+            sub.gene_positions = getattr(self, 'gene_positions', None)
+            sub._spec, sub.num_haps = self._spec, self.num_haps
+            sub._tables, sub._tables_pending = self._alt_tables[a], None
+            sub.loaded = True
+            subs[a] = sub
+        return subs[a]
 
     def specificity(self, num_haps):
         """Per chromosome (blocks [n, H, H], present flags [n]): sample independent, made once."""
@@ -436,6 +514,8 @@ class ReconstructContext:
         if self.hmm is not None:
             self.hmm.close()
             self.hmm = None
+        for sub in self.__dict__.get('_alt_contexts', {}).values():
+            sub.close()
 
 
 def _expression_rows(ctx, expr_row, expr_table, num_haps):
@@ -692,12 +772,97 @@ class GeneReport:
                                                                 self.flagged[k], mean[k], largest[k]))
 
 
+def choose_tables(total):
+    """(index of the first largest total, best minus second best) per sample from float64 (K, n) totals per candidate
+    table file.  NaN never wins; all -inf (or NaN) selects candidate 0 with margin 0.0; K = 1 gives margin inf."""
+    total = np.asarray(total, dtype=np.float64)
+    if total.ndim != 2 or total.shape[0] < 1:
+        raise ValueError('total must be (K, n) with K >= 1')
+    K, n = total.shape
+    key = np.where(np.isnan(total), -np.inf, total)
+    best = key.argmax(axis=0)
+    at = np.arange(n)
+    top = key[best, at]
+    if K == 1:
+        return best, np.full(n, np.inf)
+    rest = key.copy()
+    rest[best, at] = -np.inf
+    with np.errstate(invalid='ignore'):
+        margin = top - rest.max(axis=0)
+    return best, np.where(np.isnan(margin), 0.0, margin)
+
+
+def check_loglik_args(loglik=False, alt_tprob_files=None, model_report=None, cohort=False, tprob_file=None):
+    """`--loglik [--alt-tprob-file PATH ...] [--model-report PATH]`: the model report needs a cohort (`--sample-file`) and
+    at least one alternative file; an alternative that is the `-t` file or another alternative (by realpath) is refused.
+    Refused before a file is read."""
+    alts = list(alt_tprob_files or ())
+    if model_report is not None and not (cohort and alts):
+        raise RuntimeError('--model-report needs --sample-file and at least one --alt-tprob-file')
+    seen = {} if tprob_file is None else {os.path.realpath(tprob_file): '-t'}
+    for f in alts:
+        real = os.path.realpath(f)
+        if real in seen:
+            raise RuntimeError(f'--alt-tprob-file {f} is the same file as ' +
+                               ('-t' if seen[real] == '-t' else f'--alt-tprob-file {seen[real]}'))
+        seen[real] = f
+
+
+def _model_logliks(ctx, hmm, num_haps):
+    """float64 (K, n, n_chrom): the last run's data log-likelihood per candidate (`-t` first, then the alternatives as
+    given), sample and chromosome.  The base's come from one reduction; an alternative's chromosome whose table equals the
+    base's takes the base's value, the others take one forward-only launch per chromosome for all such alternatives."""
+    alts = ctx.alt_tables(num_haps) if ctx.alt_tprob_files else []
+    base = hmm.loglik()
+    ctx.loglik_launches += 1
+    per = np.repeat(base[None], 1 + len(alts), axis=0)
+    for ci in range(len(ctx.chroms)):
+        need = [a for a in range(len(alts)) if not ctx.alt_same[a][ci]]
+        if need:
+            per[[a + 1 for a in need], :, ci] = hmm.loglik_tables(ci, [alts[a][ci] for a in need])
+            ctx.loglik_launches += 1
+    return per
+
+
+def loglik_totals(per):
+    """The chromosomes' values added in handle order: (K, n, n_chrom) -> (K, n), or (K, n_chrom) -> (K,)."""
+    per = np.asarray(per, dtype=np.float64)
+    total = np.zeros(per.shape[:-1])
+    for ci in range(per.shape[-1]):
+        total = total + per[..., ci]
+    return total
+
+
+def write_loglik_table(path, chroms, n_genes, names, per, selected):
+    """`<outbase>.loglik.tsv`: per chromosome its genes and one log-likelihood per candidate (`names`: the table files as
+    given; per: (K, n_chrom)), a `total` line and `# selected: <name>`.  Numbers as repr(float)."""
+    per = np.asarray(per, dtype=np.float64).reshape(len(names), len(chroms))
+    logger.info(f'Saving Log-Likelihoods: {path}')
+    with open(path, 'w') as out:
+        out.write('chromosome\tgenes\t' + '\t'.join(names) + '\n')
+        for ci, c in enumerate(chroms):
+            out.write(f'{c}\t{int(n_genes[ci])}\t' + '\t'.join(repr(float(v)) for v in per[:, ci]) + '\n')
+        out.write(f'total\t{int(sum(int(g) for g in n_genes))}\t' + '\t'.join(repr(float(v)) for v in loglik_totals(per)) + '\n')
+        out.write(f'# selected: {names[selected]}\n')
+
+
+def write_model_report(path, names, lines):
+    """`--model-report`: per sample that ran its outbase, the selected table file, the margin of the choice (best minus
+    second best total) and one total per candidate.  lines: (outbase, selected index, margin, totals)."""
+    logger.info(f'Saving Model Report: {path}')
+    with open(path, 'w') as out:
+        out.write('#outbase\tselected\tmargin\t' + '\t'.join(names) + '\n')
+        for outbase, selected, margin, totals in lines:
+            out.write(f'{outbase}\t{names[selected]}\t{repr(float(margin))}\t' +
+                      '\t'.join(repr(float(v)) for v in totals) + '\n')
+
+
 def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gpos_file: str = None,
                 expr_threshold: float = 1.5, sigma: float = 0.12, outbase: str = None,
                 device: int = 0, stage_times: dict = None, context: ReconstructContext = None,
                 grid_file: str = None, grid_genoprobs: bool = False, sim_geno: int = None,
                 sim_geno_seed: int = 0, diagnostics: bool = False, error_lod_threshold: float = 2.0,
-                gene_report: str = None) -> None:
+                gene_report: str = None, loglik: bool = False, alt_tprob_files=None, model_report: str = None) -> None:
     """`gbrs reconstruct`: diplotype posteriors and Viterbi calls along every chromosome from
     gene-level TPMs.  Same inputs, defaults and three output files as gbrs_utils.reconstruct
     (gbrs_utils.py:382-609); the emission model and the three recursions run on the device.
@@ -713,13 +878,23 @@ def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gp
     `diagnostics` (extension): the expected founder changes and the switch probability of every gene interval, and per
     gene the error LOD and the most likely diplotype, go to `<outbase>.diagnostics.npz`, a summary per chromosome with the
     expressed genes whose error LOD is above `error_lod_threshold` to `<outbase>.diagnostics.tsv` (DESIGN.md §23);
-    `gene_report` belongs to a cohort (reconstruct_many) and is refused here."""
+    `gene_report` belongs to a cohort (reconstruct_many) and is refused here.
+    `loglik` (extension): `<outbase>.loglik.tsv` holds the data log-likelihood of the run per chromosome
+    and in total.  `alt_tprob_files` (implies `loglik`; with a context, the context's): the sample's emissions are also
+    scored under these table files on the device; if one of them explains the sample better than `tprob_file` (the first
+    largest total, `tprob_file` first), the sample is run again under it and every file is the one a plain call with that
+    table file writes.  `model_report` belongs to a cohort and is refused here."""
     check_sim_geno_args(sim_geno, sim_geno_seed)
     check_diagnostics_args(diagnostics, error_lod_threshold, gene_report, cohort=False)
+    if context is not None and alt_tprob_files is None:
+        alt_tprob_files = context.alt_tprob_files
+    check_loglik_args(loglik, alt_tprob_files, model_report, cohort=False, tprob_file=tprob_file)
+    loglik = bool(loglik or alt_tprob_files)
     clock = time.perf_counter
     marks = stage_times if stage_times is not None else {}
     stem = 'gbrs.reconstructed' if outbase is None else outbase
-    ctx = context if context is not None else ReconstructContext(tprob_file, avec_file, gpos_file, device, grid_file)
+    ctx = context if context is not None else ReconstructContext(tprob_file, avec_file, gpos_file, device, grid_file,
+                                                                 alt_tprob_files)
     for label, value in (('Expression File', expression_file), ('Transition Probabilities File', tprob_file),
                          ('Alignment Specificity File', ctx.avec_file), ('Gene Position File', ctx.gpos_file),
                          ('Expression Threshold', expr_threshold), ('Sigma', sigma), ('Outbase', outbase)):
@@ -742,10 +917,14 @@ def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gp
     spec = ctx.specificity(num_haps) if first_use else None
     if first_use:
         ctx.tables()
+    if loglik and ctx.alt_tprob_files:
+        ctx.alt_tables(num_haps)           # a file that does not fit is refused before the sample runs
     marks['load'] = clock() - t0
 
     posterior, path_names, calls = {}, {}, {}
     on_grid = drawn = diag = None
+    names = [tprob_file] + list(ctx.alt_tprob_files) if loglik else None
+    scores = np.zeros((len(names), 0)) if loglik else None       # (candidates, chromosomes) of this sample
     if chroms:
         t0 = clock()
         hmm, _ = ctx.handle(num_haps)
@@ -758,11 +937,35 @@ def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gp
             hmm.set_expression(rows, expr_threshold=expr_threshold, sigma=sigma)
         logger.info('Getting backward probability')
         hmm.run()
+        scoring = 0.0
+        if loglik:
+            t1 = clock()
+            logger.info('Getting the log-likelihood of the data')
+            scores = _model_logliks(ctx, hmm, num_haps)[:, 0, :]
+            selected = int(choose_tables(loglik_totals(scores)[:, None])[0][0])
+            scoring = clock() - t1
+            if selected != 0:
+                # the sample goes through a handle on the better-fitting file: what a plain call with that file does
+                logger.info(f'Selected {names[selected]}: running the sample under it')
+                try:
+                    reconstruct(expression_file, names[selected], expr_threshold=expr_threshold, sigma=sigma,
+                                outbase=outbase, device=device, stage_times=marks, context=ctx.alt_context(selected - 1),
+                                grid_genoprobs=grid_genoprobs, sim_geno=sim_geno, sim_geno_seed=sim_geno_seed,
+                                diagnostics=diagnostics, error_lod_threshold=error_lod_threshold)
+                finally:
+                    if context is None:
+                        ctx.close()
+                marks['loglik'] = scoring
+                write_loglik_table(f'{stem}.loglik.tsv', chroms, [len(ctx.gene_order[c]) for c in chroms], names, scores,
+                                   selected)
+                return
         logger.info('Getting forward-backward probability')
         posterior, path_names, calls = _collect(ctx, hmm, 0, diplotypes)
         if context is None and ctx.grid is None and sim_geno is None and not diagnostics:
             ctx.close()
-        marks['hmm'] = clock() - t0
+        marks['hmm'] = clock() - t0 - scoring
+        if loglik:
+            marks['loglik'] = scoring
         if sim_geno is not None:
             t0 = clock()
             logger.info(f'Drawing {sim_geno} paths from the posterior')
@@ -799,6 +1002,8 @@ def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gp
         _save_sim_geno(stem, ctx, diplotypes, drawn, sim_geno_seed, 0)
     if diag is not None:
         _save_diagnostics(stem, ctx, diplotypes, diag, error_lod_threshold)
+    if loglik:
+        write_loglik_table(f'{stem}.loglik.tsv', chroms, [len(ctx.gene_order[c]) for c in chroms], names, scores, 0)
     marks['save'] = clock() - t0
     logger.info('Done')
 
@@ -823,7 +1028,8 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
                      expr_threshold: float = 1.5, sigma: float = 0.12, device: int = 0, batch_size: int = 64,
                      grid_file: str = None, grid_genoprobs: bool = False, stage_times: dict = None,
                      context: ReconstructContext = None, sim_geno: int = None, sim_geno_seed: int = 0,
-                     diagnostics: bool = False, error_lod_threshold: float = 2.0, gene_report: str = None) -> list:
+                     diagnostics: bool = False, error_lod_threshold: float = 2.0, gene_report: str = None,
+                     loglik: bool = False, alt_tprob_files=None, model_report: str = None) -> list:
     """`gbrs reconstruct` for a cohort whose genes.tpm files exist (extension): one context, the tables on the device
     once, the samples through the HMM in launches of up to `batch_size`, and with `grid_file` one grid pass per launch.
     Every sample gets the files the single-sample call writes for its outbase.  All samples must carry the same
@@ -832,9 +1038,19 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
     `error`.  `sim_geno` = K: one more device pass per launch draws K paths per sample and chromosome; a sample's stream
     is its 0-based position in `expression_files`, so its draws do not depend on the batch it ran in.  `diagnostics`: two
     more device passes per launch and every sample's two diagnostics files; `gene_report`: one line per gene of the handle
-    over the samples that ran (how many express it, in how many of those its error LOD is above `error_lod_threshold`)."""
+    over the samples that ran (how many express it, in how many of those its error LOD is above `error_lod_threshold`).
+    `loglik`: every sample's `<outbase>.loglik.tsv`, from one more device pass per launch.  `alt_tprob_files` (implies
+    `loglik`; with a context, the context's): each launch is also scored under these table files; a sample that one of
+    them explains better than `tprob_file` is run again, in a launch of its own, under a handle on that file (made at
+    first need, kept for the cohort) and all of its files come from that run - the files of the single-sample command
+    under that file - its path draws on its usual stream.
+    `model_report`: one line per sample that ran - outbase, selected file, margin, the totals per candidate."""
     check_sim_geno_args(sim_geno, sim_geno_seed)
     check_diagnostics_args(diagnostics, error_lod_threshold, gene_report, cohort=True)
+    if context is not None and alt_tprob_files is None:
+        alt_tprob_files = context.alt_tprob_files
+    check_loglik_args(loglik, alt_tprob_files, model_report, cohort=True, tprob_file=tprob_file)
+    loglik = bool(loglik or alt_tprob_files)
     clock = time.perf_counter
     marks = stage_times if stage_times is not None else {}
     if len(expression_files) != len(outbases):
@@ -862,27 +1078,99 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
     haplotypes = list(next(iter(headers.values())))
     num_haps = len(haplotypes)
     diplotypes = [a + b for a, b in combinations_with_replacement(haplotypes, 2)]
-    ctx = context if context is not None else ReconstructContext(tprob_file, avec_file, gpos_file, device, grid_file)
+    ctx = context if context is not None else ReconstructContext(tprob_file, avec_file, gpos_file, device, grid_file,
+                                                                 alt_tprob_files)
     _lib.warm_up_device_async(device)
     t0 = clock()
     ctx.load()
+    if loglik and ctx.alt_tprob_files and ctx.chroms:
+        ctx.alt_tables(num_haps)           # a file that does not fit is refused before any sample runs
     marks['load'] = clock() - t0
-    for key in ('read', 'hmm', 'grid', 'save'):
+    for key in ('read', 'hmm', 'grid', 'save') + (('loglik',) if loglik else ()):
         marks[key] = 0.0
+    names = [tprob_file] + list(ctx.alt_tprob_files) if loglik else None
+    choices = {}                           # sample -> (selected candidate, margin, totals per candidate)
     from concurrent.futures import ThreadPoolExecutor
     writers = ThreadPoolExecutor(max_workers=min(16, batch_size))
     pending = []
 
-    def save(k, results, on_grid, drawn=None, diag=None):
+    def save(k, results, on_grid, drawn=None, diag=None, on=None, scores=None):
+        on = ctx if on is None else on     # the context the sample ran under
         _save_reconstruction(outbases[k], *results, threads=1)
         if on_grid is not None:
-            _save_grid(outbases[k], ctx, haplotypes, on_grid[0], on_grid[1], threads=1)
+            _save_grid(outbases[k], on, haplotypes, on_grid[0], on_grid[1], threads=1)
         if drawn is not None:
-            _save_sim_geno(outbases[k], ctx, diplotypes, drawn, sim_geno_seed, k, threads=1)
+            _save_sim_geno(outbases[k], on, diplotypes, drawn, sim_geno_seed, k, threads=1)
         if diag is not None:
-            _save_diagnostics(outbases[k], ctx, diplotypes, diag, error_lod_threshold, threads=1)
+            _save_diagnostics(outbases[k], on, diplotypes, diag, error_lod_threshold, threads=1)
+        if scores is not None:
+            write_loglik_table(f'{outbases[k]}.loglik.tsv', ctx.chroms, [len(ctx.gene_order[c]) for c in ctx.chroms], names,
+                               scores, choices[k][0])
 
     report = None
+
+    def launch(on, members, rows, scores_of=None):
+        """The samples `members` (their TPM rows in `rows`) through the handle of context `on` and out to their files.
+        With candidates to weigh (`on` is ctx): returns {alternative: [positions in members]} of the samples that one of
+        them explains better; those are not saved here.  scores_of: the (K, n_chrom) likelihoods of samples that were
+        weighed in an earlier launch."""
+        nonlocal report
+        t0 = clock()
+        first_use = on.hmm is None or on.hmm.H != num_haps
+        spec = on.specificity(num_haps) if first_use else None
+        hmm, _ = on.handle(num_haps)
+        stacked = [np.stack([r[ci] for r in rows]) for ci in range(len(on.chroms))]
+        if first_use:
+            hmm.set_expression(stacked, [x[0] for x in spec], [x[1] for x in spec], expr_threshold, sigma)
+        else:
+            hmm.set_expression(stacked, expr_threshold=expr_threshold, sigma=sigma)
+        hmm.run()
+        moved, stay = {}, list(range(len(members)))
+        if loglik and on is ctx:
+            t1 = clock()
+            per = _model_logliks(ctx, hmm, num_haps)
+            totals = loglik_totals(per)
+            best, margin = choose_tables(totals)
+            scores_of = {}
+            for s, k in enumerate(members):
+                choices[k] = (int(best[s]), float(margin[s]), totals[:, s].copy())
+                scores_of[k] = per[:, s, :].copy()
+                if best[s] != 0:
+                    moved.setdefault(int(best[s]) - 1, []).append(s)
+            stay = [s for s in stay if best[s] == 0]
+            marks['loglik'] += clock() - t1
+            t0 += clock() - t1
+        results = {s: _collect(on, hmm, s, diplotypes) for s in stay}
+        marks['hmm'] += clock() - t0
+        on_grid = None
+        if on.grid is not None and stay:
+            t0 = clock()
+            on_grid = hmm.grid(want=('dosage', 'gamma_grid') if grid_genoprobs else ('dosage',))
+            marks['grid'] += clock() - t0
+        drawn = None
+        if sim_geno is not None and stay:
+            t0 = clock()
+            drawn = _draw_paths(hmm, sim_geno, sim_geno_seed, members)
+            marks['sim_geno'] = marks.get('sim_geno', 0.0) + clock() - t0
+        diags = None
+        if diagnostics and stay:
+            t0 = clock()
+            diags = _diagnose(hmm, rows, expr_threshold)
+            if gene_report is not None:
+                if report is None:
+                    report = GeneReport(ctx, error_lod_threshold)
+                for s in stay:
+                    report.add(diags[s])
+            marks['diagnostics'] = marks.get('diagnostics', 0.0) + clock() - t0
+        t0 = clock()
+        for s in stay:
+            k = members[s]
+            grid_of = None if on_grid is None else (on_grid['dosage'][s], on_grid['gamma_grid'][s] if grid_genoprobs else None)
+            pending.append((k, writers.submit(save, k, results[s], grid_of, None if drawn is None else drawn[s],
+                                              None if diags is None else diags[s], on,
+                                              None if scores_of is None else scores_of[k])))
+        marks['save'] += clock() - t0
+        return moved, scores_of
 
     try:
         order = sorted(headers)
@@ -900,47 +1188,17 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
             if not members or not ctx.chroms:
                 nothing = None if sim_geno is None else ([], np.zeros((sim_geno, 0), dtype=np.int32), [])
                 for k in members:
+                    if loglik:
+                        choices[k] = (0, 0.0 if len(names) > 1 else np.inf, np.zeros(len(names)))
                     pending.append((k, writers.submit(save, k, ({}, {}, {}), None, nothing,
-                                                      _no_diagnostics() if diagnostics else None)))
+                                                      _no_diagnostics() if diagnostics else None, None,
+                                                      np.zeros((len(names), 0)) if loglik else None)))
                 continue
-            t0 = clock()
-            first_use = ctx.hmm is None or ctx.hmm.H != num_haps
-            spec = ctx.specificity(num_haps) if first_use else None
-            hmm, _ = ctx.handle(num_haps)
-            stacked = [np.stack([r[ci] for r in rows]) for ci in range(len(ctx.chroms))]
-            if first_use:
-                hmm.set_expression(stacked, [x[0] for x in spec], [x[1] for x in spec], expr_threshold, sigma)
-            else:
-                hmm.set_expression(stacked, expr_threshold=expr_threshold, sigma=sigma)
-            hmm.run()
-            results = [_collect(ctx, hmm, s, diplotypes) for s in range(len(members))]
-            marks['hmm'] += clock() - t0
-            on_grid = None
-            if ctx.grid is not None:
-                t0 = clock()
-                on_grid = hmm.grid(want=('dosage', 'gamma_grid') if grid_genoprobs else ('dosage',))
-                marks['grid'] += clock() - t0
-            drawn = None
-            if sim_geno is not None:
-                t0 = clock()
-                drawn = _draw_paths(hmm, sim_geno, sim_geno_seed, members)
-                marks['sim_geno'] = marks.get('sim_geno', 0.0) + clock() - t0
-            diags = None
-            if diagnostics:
-                t0 = clock()
-                diags = _diagnose(hmm, rows, expr_threshold)
-                if gene_report is not None:
-                    if report is None:
-                        report = GeneReport(ctx, error_lod_threshold)
-                    for d in diags:
-                        report.add(d)
-                marks['diagnostics'] = marks.get('diagnostics', 0.0) + clock() - t0
-            t0 = clock()
-            for s, k in enumerate(members):
-                grid_of = None if on_grid is None else (on_grid['dosage'][s], on_grid['gamma_grid'][s] if grid_genoprobs else None)
-                pending.append((k, writers.submit(save, k, results[s], grid_of, None if drawn is None else drawn[s],
-                                                  None if diags is None else diags[s])))
-            marks['save'] += clock() - t0
+            moved, scores_of = launch(ctx, members, rows)
+            # The samples an alternative explains better, under a handle on that file: each in a launch of its own, which
+            # is the single-sample command's launch, so its files do not depend on who else moved or on the batch size.
+            for s, a in sorted((s, a) for a in moved for s in moved[a]):
+                launch(ctx.alt_context(a), [members[s]], [rows[s]], scores_of)
         t0 = clock()
         for k, job in pending:
             try:
@@ -949,6 +1207,8 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
                 failed(k, e)
         if gene_report is not None:
             (report if report is not None else GeneReport(ctx, error_lod_threshold)).write(gene_report)
+        if model_report is not None:
+            write_model_report(model_report, names, [(outbases[k],) + choices[k] for k in sorted(choices)])
         marks['save'] += clock() - t0
     finally:
         writers.shutdown(wait=True)

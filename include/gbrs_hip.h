@@ -760,6 +760,31 @@ int gbrs_hmm_pair_posterior(gbrs_hmm_t *hmm, int sample, int chrom, double *xi);
 /* Device time of the last gbrs_hmm_diagnostics call's kernels (0 if none ran); nullable. */
 int gbrs_hmm_diagnostics_info(gbrs_hmm_t *hmm, double *last_ms);
 
+/* Data log-likelihood of the last run under the handle's own tables (extension): per (sample,
+ * chromosome) the sum over the chromosome's genes of log Z_i, Z_i the normaliser of gene i in the scaled forward recursion,
+ * i.e. minus the sum of the `scaler` row gbrs_hmm_get returns.  One reduction over what the forward pass kept; the order
+ * of the sum depends on the chromosome's length alone, so a value is the same bits in every batch and slot.
+ * sample = -1: all n samples of the run, else that one (n = 1).  loglik is double[n][n_chrom].  GBRS_ERR_STATE before the
+ * first run; GBRS_ERR_INVALID for a sample out of range or loglik == NULL; both before any launch, loglik untouched. */
+int gbrs_hmm_loglik(gbrs_hmm_t *hmm, int sample, double *loglik);
+
+/* Data log-likelihood of the last run's emissions on chromosome `chrom` under n_tables other transition tables: table k
+ * is double[n_trans[k]][S][S] in natural log, T[i][to][from] as for gbrs_hmm_create (-inf entries are legal); only
+ * T[0 .. n_c - 2] are read, none for a chromosome of one gene (tprob[k] may then be NULL).  One launch runs the forward
+ * recursion alone for every (table, sample) pair:
+ *   gene 0: y_j = exp(init_j) * pe_0[j];  gene i: x_j = (sum_k y_{i-1}[k] * exp(T[i-1][j][k])) / Z_{i-1} + tiny,
+ *   y_j = x_j * pe_i[j], Z_i = sum_j y_j;  result = sum_i log Z_i added in gene order, -inf if a Z_i is 0 or not finite.
+ * loglik is double[n_tables][n] (sample = -1: n = all samples of the run, else 1).  The handle's tables and the run's
+ * results are not touched.  Device memory: n_tables x (n_c - 1) x S^2 x 16 bytes, kept for later calls.
+ * GBRS_ERR_STATE before the first run; GBRS_ERR_INVALID for a sample or chromosome out of range, n_tables < 1, an
+ * n_trans[k] < n_c - 1, or a NULL n_trans, tprob, needed tprob[k] or loglik; all before any launch, loglik untouched. */
+int gbrs_hmm_loglik_tables(gbrs_hmm_t *hmm, int chrom, int n_tables, const int32_t *n_trans, const double *const *tprob,
+                           int sample, double *loglik);
+
+/* Device time of the last gbrs_hmm_loglik / gbrs_hmm_loglik_tables call's kernels (0 if none ran) and the device memory
+ * the two calls' buffers hold; both nullable. */
+int gbrs_hmm_loglik_info(gbrs_hmm_t *hmm, double *last_ms, uint64_t *device_bytes);
+
 int gbrs_hmm_destroy(gbrs_hmm_t *hmm);
 
 /* `gbrs interpolate` numeric body (gbrs/gbrs_utils.py:684-688): the rows of y (S x n_points, C

@@ -104,6 +104,24 @@ def build_parser():
     r.add_argument('--model-report', default=None, metavar='PATH',
                    help='with --sample-file and --alt-tprob-file: one line per sample with the selected file, the margin '
                         'and the total per candidate')
+    r.add_argument('--match-panel', type=_existing, default=None, metavar='FILE',
+                   help='(extension, needs --grid-file) a panel of reference genotypes: tab separated lines `id<TAB>path`, each '
+                        'path a dosage table on the grid as --grid-file writes it (`gbrs export` format).  The founder '
+                        'dosages of every sample are compared with every entry on the device; writes <outbase>.match.tsv, '
+                        'the entries by mean squared dosage difference per grid point')
+    r.add_argument('--match-labels', type=_existing, default=None, metavar='FILE',
+                   help='with --match-panel and --sample-file: lines `outbase<TAB>panel id`, the entry each sample should be')
+    r.add_argument('--match-expected', default=None, metavar='ID',
+                   help='with --match-panel and -e: the panel id the sample should be')
+    r.add_argument('--match-chromosomes', default=None, metavar='LIST',
+                   help='with --match-panel: comma list of the chromosomes that are compared (default: every chromosome on '
+                        'the grid), e.g. the autosomes when the X chromosome of males would dominate')
+    r.add_argument('--match-report', default=None, metavar='PATH',
+                   help='with --match-panel and --sample-file: one line per sample with its status (match, mismatch, '
+                        'unlabelled, unknown-label), the best and second entry, their distances and the margin')
+    r.add_argument('--match-matrix', default=None, metavar='PATH',
+                   help='with --match-panel and --sample-file: an .npz with the distances and similarities of all samples '
+                        'against all entries and the sums they were made from')
     r.add_argument('-t', '--tprob-file', required=True, type=_existing)
     r.add_argument('-x', '--avec-file', type=_existing, default=None)
     r.add_argument('-g', '--gpos-file', type=_existing, default=None)
@@ -262,6 +280,9 @@ def main(argv=None) -> int:
             from .hmm import check_loglik_args
             check_loglik_args(args.loglik, args.alt_tprob_file, args.model_report, cohort=args.sample_file is not None,
                               tprob_file=args.tprob_file)
+            from .hmm import check_match_args
+            check_match_args(args.match_panel, args.match_labels, args.match_expected, args.match_chromosomes,
+                             args.match_report, args.match_matrix, args.grid_file, cohort=args.sample_file is not None)
         if args.command == 'quantify' and args.gpus is not None:
             # N child processes, one per rank; this process opens no device
             from .sharded import launch
@@ -375,7 +396,10 @@ def main(argv=None) -> int:
                              grid_genoprobs=args.grid_genoprobs, stage_times=stages, sim_geno=args.sim_geno,
                              sim_geno_seed=args.sim_geno_seed, diagnostics=args.diagnostics,
                              error_lod_threshold=args.error_lod_threshold, gene_report=args.gene_report,
-                             loglik=args.loglik, alt_tprob_files=args.alt_tprob_file, model_report=args.model_report)
+                             loglik=args.loglik, alt_tprob_files=args.alt_tprob_file, model_report=args.model_report,
+                             match_panel=args.match_panel, match_labels=args.match_labels,
+                             match_chromosomes=args.match_chromosomes, match_report=args.match_report,
+                             match_matrix=args.match_matrix)
         else:
             from .hmm import reconstruct
             reconstruct(expression_file=args.expression_file, tprob_file=args.tprob_file,
@@ -384,7 +408,8 @@ def main(argv=None) -> int:
                         device=args.device, stage_times=stages, grid_file=args.grid_file,
                         grid_genoprobs=args.grid_genoprobs, sim_geno=args.sim_geno, sim_geno_seed=args.sim_geno_seed,
                         diagnostics=args.diagnostics, error_lod_threshold=args.error_lod_threshold,
-                        loglik=args.loglik, alt_tprob_files=args.alt_tprob_file)
+                        loglik=args.loglik, alt_tprob_files=args.alt_tprob_file, match_panel=args.match_panel,
+                        match_expected=args.match_expected, match_chromosomes=args.match_chromosomes)
     except Exception as e:   # noqa: BLE001 - mirror of the reference's catch-all
         failure = e
         if logger.level == logging.DEBUG:

@@ -2484,6 +2484,7 @@ __global__ void dosage_kernel(int H, int S, int64_t rows, const double *__restri
 }
 
 #include "hmm_grid.inc"
+#include "hmm_match.inc"
 #include "hmm_sample.inc"
 #include "hmm_diag.inc"
 #include "hmm_loglik.inc"
@@ -2562,6 +2563,15 @@ struct gbrs_hmm {
     DevBuf<double> grid_knot_x, grid_x, grid_dosage, grid_gamma;
     DevBuf<int32_t> grid_knot_gene;
     double t_grid = 0;
+    bool grid_dosage_ready = false;           // grid_dosage holds the last run's dosages for `grid_dosage_sample` (-1: all)
+    int grid_dosage_sample = -1;
+    // Match pass (hmm_match.inc): the panel's dosages in grid_dosage's row layout, its norms, the outputs of the last call
+    int n_panel = 0;
+    bool match_vec2 = false;                  // rows and chromosome starts are 16-byte aligned (even H)
+    DevBuf<double> match_panel, match_cross, match_snorm;
+    DevBuf<MatchChrom> d_match_chroms;
+    std::vector<double> panel_norm;           // [n_panel][n_chrom]
+    double t_match = 0;
     // Path draws (hmm_sample.inc): the change table is made on the first call; the other buffers hold one slab of draws
     DevBuf<uint8_t> smp_change_tab, smp_cols, smp_paths;
     DevBuf<int32_t> smp_changes;
@@ -2583,6 +2593,13 @@ namespace {
 
 static_assert(MF_S == 36, "hmm_route.h names the 36-state kernels' state count by its number");
 HmmShape hmm_shape(const gbrs_hmm *h) { return HmmShape{h->S, h->H, h->n_samples, h->n_chrom, h->total_trans}; }
+
+void match_clear_panel(gbrs_hmm *h) {
+    h->match_panel.release();
+    h->d_match_chroms.release();
+    h->panel_norm.clear();
+    h->n_panel = 0;
+}
 
 int hmm_alloc_samples(gbrs_hmm *h, int n_samples) {
     if (n_samples == h->n_samples && h->eprob.p) return GBRS_OK;
@@ -3485,6 +3502,7 @@ int gbrs_hmm_set_expression(gbrs_hmm_t *h, int n_samples, const double *const *e
     h->have_eprob = true;
     h->pe_ready = !h->emission_pending;
     h->ran = false;
+    h->grid_dosage_ready = false;
     return GBRS_OK;
 }
 
@@ -3504,6 +3522,7 @@ int gbrs_hmm_set_eprob(gbrs_hmm_t *h, int n_samples, const double *const *eprob)
     h->emission_pending = false;
     h->pe_ready = false;
     h->ran = false;
+    h->grid_dosage_ready = false;
     h->t_emis = 0;
     return GBRS_OK;
 }
@@ -3516,6 +3535,7 @@ int gbrs_hmm_run(gbrs_hmm_t *h) {
     const int S = h->S;
     const HmmTuning t = hmm_tuning_from_env();
     const HmmRoute r = hmm_route(hmm_shape(h), t, h->emission_pending);
+    h->grid_dosage_ready = false;
     int rc;
     if (r.grouped) {
         rc = hmm_launch_groups(h, r, t);
@@ -3743,6 +3763,39 @@ int gbrs_hmm_set_grid(gbrs_hmm_t *h, const int32_t *n_pos, const double *const *
     h->grid_tiles = (int)tiles.size();
     h->grid_points = (int64_t)x.size();
     h->have_grid = true;
+    h->grid_dosage_ready = false;
+    match_clear_panel(h);
+    return GBRS_OK;
+}
+
+// The grid kernel for `sample` (-1: all n) into grid_dosage and / or grid_gamma, timed into t_grid; returns when it is done.
+static int hmm_grid_launch(gbrs_hmm *h, int sample, bool want_dosage, bool want_gamma) {
+    const int S = h->S, H = h->H;
+    const int n = sample < 0 ? h->n_samples : 1;
+    const size_t n_dosage = (size_t)n * h->grid_points * H, n_gamma = (size_t)n * h->grid_points * S;
+    if (want_dosage) h->grid_dosage_ready = false;
+    if (want_dosage && h->grid_dosage.n != n_dosage) GBRS_TRY(h->grid_dosage.alloc(n_dosage));
+    if (want_gamma && h->grid_gamma.n != n_gamma) GBRS_TRY(h->grid_gamma.alloc(n_gamma));
+    const dim3 grid((unsigned)h->grid_tiles, (unsigned)n);
+    const size_t lds = grid_tile_lds(S);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(64), lds, h->stream, H, S, grid_tile_points(S), h->total_genes, h->grid_points,
+                           std::max(sample, 0), h->d_grid_chroms.p, h->d_grid_tiles.p, h->grid_knot_x.p, h->grid_knot_gene.p,
+                           h->grid_x.p, h->gamma.p, want_dosage ? h->grid_dosage.p : nullptr, want_gamma ? h->grid_gamma.p : nullptr);
+    };
+    GBRS_HIP_CHECK(hipEventRecord(h->ev[0], h->stream));
+    if (S <= 64) launch(grid_kernel<1>);
+    else if (S <= 128) launch(grid_kernel<2>);
+    else launch(grid_kernel<3>);          // S <= 136 (MAX_H = 16)
+    GBRS_HIP_CHECK(hipEventRecord(h->ev[1], h->stream));
+    GBRS_HIP_CHECK(hipGetLastError());
+    GBRS_HIP_CHECK(hipStreamSynchronize(h->stream));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, h->ev[0], h->ev[1]) == hipSuccess) h->t_grid = ms;
+    if (want_dosage) {
+        h->grid_dosage_ready = true;
+        h->grid_dosage_sample = sample;
+    }
     return GBRS_OK;
 }
 
@@ -3754,27 +3807,9 @@ int gbrs_hmm_grid(gbrs_hmm_t *h, int sample, double *dosage, double *gamma_grid)
     if (sample < -1 || sample >= h->n_samples) return fail(GBRS_ERR_INVALID, "sample out of range");
     if ((!dosage && !gamma_grid) || h->grid_tiles == 0) return GBRS_OK;
     GBRS_TRY(select_device(h->device));
-    const int S = h->S, H = h->H;
     const int n = sample < 0 ? h->n_samples : 1;
-    const size_t n_dosage = (size_t)n * h->grid_points * H, n_gamma = (size_t)n * h->grid_points * S;
-    if (dosage && h->grid_dosage.n != n_dosage) GBRS_TRY(h->grid_dosage.alloc(n_dosage));
-    if (gamma_grid && h->grid_gamma.n != n_gamma) GBRS_TRY(h->grid_gamma.alloc(n_gamma));
-    const dim3 grid((unsigned)h->grid_tiles, (unsigned)n);
-    const size_t lds = grid_tile_lds(S);
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, grid, dim3(64), lds, h->stream, H, S, grid_tile_points(S), h->total_genes, h->grid_points,
-                           std::max(sample, 0), h->d_grid_chroms.p, h->d_grid_tiles.p, h->grid_knot_x.p, h->grid_knot_gene.p,
-                           h->grid_x.p, h->gamma.p, dosage ? h->grid_dosage.p : nullptr, gamma_grid ? h->grid_gamma.p : nullptr);
-    };
-    GBRS_HIP_CHECK(hipEventRecord(h->ev[0], h->stream));
-    if (S <= 64) launch(grid_kernel<1>);
-    else if (S <= 128) launch(grid_kernel<2>);
-    else launch(grid_kernel<3>);          // S <= 136 (MAX_H = 16)
-    GBRS_HIP_CHECK(hipEventRecord(h->ev[1], h->stream));
-    GBRS_HIP_CHECK(hipGetLastError());
-    GBRS_HIP_CHECK(hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, h->ev[0], h->ev[1]) == hipSuccess) h->t_grid = ms;
+    const size_t n_dosage = (size_t)n * h->grid_points * h->H, n_gamma = (size_t)n * h->grid_points * h->S;
+    GBRS_TRY(hmm_grid_launch(h, sample, dosage != nullptr, gamma_grid != nullptr));
     if (dosage) GBRS_HIP_CHECK(hipMemcpy(dosage, h->grid_dosage.p, n_dosage * sizeof(double), hipMemcpyDeviceToHost));
     if (gamma_grid) GBRS_HIP_CHECK(hipMemcpy(gamma_grid, h->grid_gamma.p, n_gamma * sizeof(double), hipMemcpyDeviceToHost));
     return GBRS_OK;
@@ -3784,6 +3819,104 @@ int gbrs_hmm_grid_info(gbrs_hmm_t *h, int64_t *n_points, double *last_ms) {
     if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
     if (n_points) *n_points = h->have_grid ? h->grid_points : 0;
     if (last_ms) *last_ms = h->t_grid;
+    return GBRS_OK;
+}
+
+int gbrs_hmm_set_panel(gbrs_hmm_t *h, int n_panel, const double *const *panel) {
+    RoctxRange roctx_range("gbrs_hmm_set_panel");
+    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (n_panel < 0 || (n_panel > 0 && !panel)) return fail(GBRS_ERR_INVALID, "bad argument");
+    if (!h->have_grid) return fail(GBRS_ERR_INVALID, "no grid on the handle: call gbrs_hmm_set_grid first");
+    if (n_panel == 0) {
+        match_clear_panel(h);
+        return GBRS_OK;
+    }
+    // everything is prepared and checked before the handle changes
+    const int64_t ld = h->grid_points * h->H;
+    for (int j = 0; j < n_panel; ++j) {
+        if (!panel[j]) return fail(GBRS_ERR_INVALID, "panel[%d] is NULL", j);
+        for (int64_t k = 0; k < ld; ++k)
+            if (!std::isfinite(panel[j][k]))
+                return fail(GBRS_ERR_INVALID, "panel entry %d holds a value that is not finite (grid point %lld, founder %d)", j,
+                            (long long)(k / h->H), (int)(k % h->H));
+    }
+    std::vector<GridChrom> gc(h->n_chrom);
+    std::vector<MatchChrom> mc;
+    GBRS_TRY(select_device(h->device));
+    GBRS_HIP_CHECK(hipMemcpy(gc.data(), h->d_grid_chroms.p, gc.size() * sizeof(GridChrom), hipMemcpyDeviceToHost));
+    for (int c = 0; c < h->n_chrom; ++c)
+        if (gc[c].n_points > 0)
+            mc.push_back(MatchChrom{(int64_t)gc[c].point_off * h->H, (int64_t)gc[c].n_points * h->H, c});
+    DevBuf<double> d_panel, d_norm;
+    DevBuf<MatchChrom> d_mc;
+    GBRS_TRY(d_panel.alloc((size_t)n_panel * ld));
+    GBRS_TRY(d_norm.alloc((size_t)n_panel * h->n_chrom));
+    GBRS_TRY(d_mc.alloc(mc.size()));
+    std::vector<double> norm((size_t)n_panel * h->n_chrom, 0.0);
+    if (ld > 0) {
+        for (int j = 0; j < n_panel; ++j)
+            GBRS_HIP_CHECK(hipMemcpy(d_panel.p + (size_t)j * ld, panel[j], (size_t)ld * sizeof(double), hipMemcpyHostToDevice));
+        GBRS_HIP_CHECK(hipMemcpy(d_mc.p, mc.data(), d_mc.bytes(), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(match_norm_kernel, dim3((unsigned)n_panel, (unsigned)h->n_chrom), dim3(64), 0, h->stream, h->H, ld,
+                           h->d_grid_chroms.p, d_panel.p, d_norm.p);
+        GBRS_HIP_CHECK(hipGetLastError());
+        GBRS_HIP_CHECK(hipStreamSynchronize(h->stream));
+        GBRS_HIP_CHECK(hipMemcpy(norm.data(), d_norm.p, d_norm.bytes(), hipMemcpyDeviceToHost));
+    }
+    h->match_panel.swap(d_panel);
+    h->d_match_chroms.swap(d_mc);
+    h->panel_norm.swap(norm);
+    h->n_panel = n_panel;
+    h->match_vec2 = h->H % 2 == 0;           // ld and every chromosome's first column are multiples of H
+    return GBRS_OK;
+}
+
+int gbrs_hmm_match(gbrs_hmm_t *h, int sample, double *cross, double *sample_norm) {
+    RoctxRange roctx_range("gbrs_hmm_match");
+    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (!h->ran) return fail(GBRS_ERR_STATE, "run() has not been called");
+    if (!h->have_grid || h->n_panel == 0) return fail(GBRS_ERR_INVALID, "no panel on the handle: call gbrs_hmm_set_panel first");
+    if (sample < -1 || sample >= h->n_samples) return fail(GBRS_ERR_INVALID, "sample out of range");
+    GBRS_TRY(select_device(h->device));
+    const int n = sample < 0 ? h->n_samples : 1, M = h->n_panel, n_chrom = h->n_chrom;
+    const int64_t ld = h->grid_points * h->H;
+    const size_t n_cross = (size_t)n * n_chrom * M, n_norm = (size_t)n * n_chrom;
+    if (h->match_cross.n != n_cross) GBRS_TRY(h->match_cross.alloc(n_cross));
+    if (h->match_snorm.n != n_norm) GBRS_TRY(h->match_snorm.alloc(n_norm));
+    const unsigned on_grid = (unsigned)h->d_match_chroms.n;
+    if (on_grid && !(h->grid_dosage_ready && h->grid_dosage_sample == sample))
+        GBRS_TRY(hmm_grid_launch(h, sample, true, false));
+    GBRS_HIP_CHECK(hipEventRecord(h->ev[0], h->stream));
+    GBRS_HIP_CHECK(hipMemsetAsync(h->match_cross.p, 0, h->match_cross.bytes(), h->stream));    // chromosomes off the grid: 0.0
+    GBRS_HIP_CHECK(hipMemsetAsync(h->match_snorm.p, 0, h->match_snorm.bytes(), h->stream));
+    if (on_grid) {
+        hipLaunchKernelGGL(match_norm_kernel, dim3((unsigned)n, (unsigned)n_chrom), dim3(64), 0, h->stream, h->H, ld,
+                           h->d_grid_chroms.p, h->grid_dosage.p, h->match_snorm.p);
+        const dim3 grid((unsigned)((n + MT_ROWS - 1) / MT_ROWS), (unsigned)((M + MT_COLS - 1) / MT_COLS), on_grid);
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, dim3(MT_THREADS), 0, h->stream, n, M, n_chrom, ld, h->d_match_chroms.p,
+                               h->grid_dosage.p, h->match_panel.p, h->match_cross.p);
+        };
+        if (h->match_vec2) launch(match_cross_kernel<true>);
+        else launch(match_cross_kernel<false>);
+    }
+    GBRS_HIP_CHECK(hipEventRecord(h->ev[1], h->stream));
+    GBRS_HIP_CHECK(hipGetLastError());
+    GBRS_HIP_CHECK(hipStreamSynchronize(h->stream));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, h->ev[0], h->ev[1]) == hipSuccess) h->t_match = ms;
+    if (cross) GBRS_HIP_CHECK(hipMemcpy(cross, h->match_cross.p, h->match_cross.bytes(), hipMemcpyDeviceToHost));
+    if (sample_norm) GBRS_HIP_CHECK(hipMemcpy(sample_norm, h->match_snorm.p, h->match_snorm.bytes(), hipMemcpyDeviceToHost));
+    return GBRS_OK;
+}
+
+int gbrs_hmm_match_info(gbrs_hmm_t *h, int *n_panel, double *panel_norm, double *last_ms, uint64_t *device_bytes) {
+    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (n_panel) *n_panel = h->n_panel;
+    if (panel_norm && !h->panel_norm.empty()) std::memcpy(panel_norm, h->panel_norm.data(), h->panel_norm.size() * sizeof(double));
+    if (last_ms) *last_ms = h->t_match;
+    if (device_bytes)
+        *device_bytes = h->match_panel.bytes() + h->match_cross.bytes() + h->match_snorm.bytes() + h->d_match_chroms.bytes();
     return GBRS_OK;
 }
 

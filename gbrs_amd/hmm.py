@@ -162,6 +162,39 @@ class DiplotypeHMM:
         _lib.check(_lib.load().gbrs_hmm_grid_info(self._h, C.byref(m), C.byref(ms)))
         return m.value, ms.value
 
+    def set_panel(self, arrays):
+        """The reference panel of the handle: one (M x H) dosage array per entry on the handle's grid
+        points, rows as `grid()['dosage']` has them (handle chromosome c: rows grid_offsets[c] .. + grid_points[c]).
+        Uploaded once; an empty sequence drops the panel.  set_grid drops it too."""
+        M = sum(getattr(self, 'grid_points', ()))
+        panel = [np.ascontiguousarray(a, dtype=np.float64) for a in arrays]
+        for j, a in enumerate(panel):
+            if a.shape != (M, self.H):
+                raise ValueError(f'panel entry {j} has shape {a.shape}, expected ({M}, {self.H})')
+        _lib.check(_lib.load().gbrs_hmm_set_panel(self._h, len(panel), _lib.ptr_table(panel)))
+
+    def match(self, sample=None):
+        """The last run against the panel, one device pass: `cross` [n, n_chrom, n_panel], the sums of products of a
+        sample's and an entry's grid dosages per handle chromosome, and `sample_norm` [n, n_chrom], the sums of the
+        sample's squares.  sample=None: every sample of the run; an index: that sample, without the leading axis."""
+        n = self.n_samples if sample is None else 1
+        n_panel = self.match_info()['n_panel']
+        cross, norm = np.empty((n, len(self.chroms), n_panel)), np.empty((n, len(self.chroms)))
+        _lib.check(_lib.load().gbrs_hmm_match(self._h, -1 if sample is None else int(sample), _lib.ptr(cross),
+                                              _lib.ptr(norm)))
+        return {'cross': cross if sample is None else cross[0], 'sample_norm': norm if sample is None else norm[0]}
+
+    def match_info(self):
+        """n_panel, panel_norm [n_panel, n_chrom], the device milliseconds of the last match pass's kernels and the
+        device bytes the panel and the pass's outputs hold."""
+        lib = _lib.load()
+        m, ms, nbytes = C.c_int32(), C.c_double(), C.c_uint64()
+        _lib.check(lib.gbrs_hmm_match_info(self._h, C.byref(m), None, C.byref(ms), C.byref(nbytes)))
+        norm = np.zeros((m.value, len(self.chroms)))
+        if m.value:
+            _lib.check(lib.gbrs_hmm_match_info(self._h, None, _lib.ptr(norm), None, None))
+        return {'n_panel': m.value, 'panel_norm': norm, 'last_ms': ms.value, 'device_bytes': nbytes.value}
+
     def sample_paths(self, n_draws, seed=0, sample=None, streams=None):
         """Diplotype paths drawn from the joint posterior of the last run, one device pass per slab of
         draws.  sample=None: every sample of the run (n of them); an index: that sample, without the leading axis.
@@ -400,6 +433,10 @@ class ReconstructContext:
         self.grid = None                  # {chromosome: positions} in the grid file's order
         self.grid_uploads = 0             # times the grid went to a device handle
         self.grid_slices = {}             # chromosome on the handle and on the grid -> (handle index, first dosage row, rows)
+        self.panel = None                 # (ids, dosage arrays in handle order) of --match-panel (_load_panel)
+        self.panel_file = None
+        self.panel_uploads = 0            # times the panel went to a device handle, alternative-table handles included
+        self._panel_on_handle = False
 
     def load(self, marks=None):
         """The files (the big transition tables inflate on the library's threads while the small files are parsed)."""
@@ -474,7 +511,10 @@ class ReconstructContext:
             sub._spec, sub.num_haps = self._spec, self.num_haps
             sub._tables, sub._tables_pending = self._alt_tables[a], None
             sub.loaded = True
+            sub._panel_owner = self
             subs[a] = sub
+        if subs[a].panel_file != self.panel_file:
+            subs[a].panel, subs[a].panel_file, subs[a]._panel_on_handle = self.panel, self.panel_file, False
         return subs[a]
 
     def specificity(self, num_haps):
@@ -508,12 +548,17 @@ class ReconstructContext:
                 self.grid_uploads += 1
                 self.grid_slices = {c: (k, self.hmm.grid_offsets[k], self.hmm.grid_points[k])
                                     for k, c in enumerate(self.chroms) if c in self.grid}
+        if self.panel is not None and not self._panel_on_handle:
+            self.hmm.set_panel(self.panel[1])
+            self._panel_on_handle = True
+            self.__dict__.get('_panel_owner', self).panel_uploads += 1
         return self.hmm, first_use
 
     def close(self):
         if self.hmm is not None:
             self.hmm.close()
             self.hmm = None
+            self._panel_on_handle = False
         for sub in self.__dict__.get('_alt_contexts', {}).values():
             sub.close()
 
@@ -857,12 +902,254 @@ def write_model_report(path, names, lines):
                       '\t'.join(repr(float(v)) for v in totals) + '\n')
 
 
+# ---- matching the samples against a panel of reference genotypes (`--match-panel`) ------------------------
+
+def check_match_args(match_panel=None, match_labels=None, match_expected=None, match_chromosomes=None, match_report=None,
+                     match_matrix=None, grid_file=None, cohort=False):
+    """`--match-panel FILE [--match-labels FILE | --match-expected ID] [--match-chromosomes LIST] [--match-report PATH]
+    [--match-matrix PATH]`: every option needs the panel, the panel needs `--grid-file`; labels, report and matrix belong
+    to a cohort (`--sample-file`), the expected id to a single sample (`-e`).  Refused before a file is read."""
+    given = {'--match-labels': match_labels, '--match-expected': match_expected, '--match-chromosomes': match_chromosomes,
+             '--match-report': match_report, '--match-matrix': match_matrix}
+    if match_panel is None:
+        for name, value in given.items():
+            if value is not None:
+                raise RuntimeError(f'{name} needs --match-panel')
+        return
+    if grid_file is None:
+        raise RuntimeError('--match-panel needs --grid-file')
+    if cohort and match_expected is not None:
+        raise RuntimeError('--match-expected belongs to -e; with --sample-file use --match-labels')
+    if not cohort:
+        for name in ('--match-labels', '--match-report', '--match-matrix'):
+            if given[name] is not None:
+                raise RuntimeError(f'{name} needs --sample-file')
+
+
+def _match_lines(path, what):
+    """[(line number, first field, second field)] of a two-column tab separated file; blank and # lines skipped."""
+    found = []
+    with open(path) as fh:
+        for number, line in enumerate(fh, 1):
+            line = line.strip()
+            if not line or line.startswith('#'):
+                continue
+            fields = line.split('\t')
+            if len(fields) != 2:
+                raise RuntimeError(f'{path}, line {number}: expected {what}')
+            found.append((number, fields[0], fields[1]))
+    return found
+
+
+def read_match_labels(path):
+    """{outbase: panel id} from lines `outbase<TAB>panel id` (`--match-labels`); an outbase given twice is refused."""
+    labels, where = {}, {}
+    for number, outbase, panel_id in _match_lines(path, 'outbase<TAB>panel id'):
+        if outbase in labels:
+            raise RuntimeError(f'{path}, line {number}: outbase {outbase} is already on line {where[outbase]}')
+        labels[outbase], where[outbase] = panel_id, number
+    return labels
+
+
+def grid_layout(ctx):
+    """{chromosome on the handle and on the grid: (handle index, first dosage row, rows)}: ctx.grid_slices, which the
+    handle fills in when it gets the grid, worked out from the loaded files for use before there is a handle."""
+    if ctx.grid_slices:
+        return ctx.grid_slices
+    slices, row = {}, 0
+    for k, c in enumerate(ctx.chroms):
+        if c in ctx.grid:
+            slices[c] = (k, row, len(ctx.grid[c]))
+            row += len(ctx.grid[c])
+    return slices
+
+
+def read_dosage_table(path, haplotypes, n_rows):
+    """The (n_rows x H) numbers of a dosage table in `gbrs export` format (write_dosage_table) whose header names
+    `haplotypes`.  RuntimeError naming the file for another header, row count or column count."""
+    with open(path) as fh:
+        header = fh.readline()
+        body = fh.read()
+    if header.rstrip('\n') != '# ' + '\t'.join(haplotypes):
+        raise RuntimeError(f'{path}: the header {header.rstrip()!r} does not name the haplotypes {",".join(haplotypes)}')
+    lines = body.splitlines()
+    if len(lines) != n_rows:
+        raise RuntimeError(f'{path}: {len(lines)} rows for the {n_rows} grid points of the grid file')
+    width = len(haplotypes)
+    for number, line in enumerate(lines, 2):
+        if line.count('\t') != width - 1:
+            raise RuntimeError(f'{path}, line {number}: {line.count(chr(9)) + 1} columns for {width} haplotypes')
+    table = np.empty((n_rows, width), dtype=np.float64)
+    if n_rows:
+        # the library's parser takes `label TAB numbers`: every row gets an empty label
+        raw = ('\t' + '\n\t'.join(lines) + '\n').encode()
+        try:
+            status = _lib.load().gbrs_parse_number_table(raw, len(raw), n_rows, width, _lib.ptr(table))
+        except (ImportError, OSError):
+            status = 1
+        if status != 0:
+            try:        # spellings the plain parser leaves to the caller (nan, inf): refused by the upload, not here
+                table = np.array([[float(x) for x in line.split('\t')] for line in lines], dtype=np.float64)
+            except ValueError as e:
+                raise RuntimeError(f'{path}: {e}') from None
+    return table
+
+
+def read_match_panel(path, ctx, haplotypes):
+    """(panel ids, one (M x H) dosage array per entry in handle order) from a panel file: tab separated lines
+    `id<TAB>path`, blank and # lines skipped, ids unique; each path a dosage table in `gbrs export` format - what
+    `--grid-file` writes - with one row per grid point of the context's grid file in that file's order, which is
+    permuted here to the handle's (ctx.grid_slices).  KeyError: a grid chromosome that is not on the handle."""
+    entries, where = [], {}
+    for number, panel_id, table in _match_lines(path, 'id<TAB>path'):
+        if panel_id in where:
+            raise RuntimeError(f'{path}, line {number}: panel id {panel_id} is already on line {where[panel_id]}')
+        where[panel_id] = number
+        entries.append((panel_id, table))
+    if not entries:
+        raise RuntimeError(f'{path}: no panel entries')
+    slices = grid_layout(ctx)
+    for c in ctx.grid:
+        if c not in slices:
+            raise KeyError(f'{c} is not a file in the archive')
+    first, row = {}, 0
+    for c in ctx.grid:
+        first[c] = row
+        row += len(ctx.grid[c])
+    order = [c for c in ctx.chroms if c in slices]
+    arrays = []
+    for panel_id, table in entries:
+        if not os.path.isfile(table):
+            raise RuntimeError(f"{path}: the dosage table '{table}' of panel id {panel_id} does not exist")
+        rows = read_dosage_table(table, haplotypes, row)
+        arrays.append(np.ascontiguousarray(np.concatenate([rows[first[c]:first[c] + slices[c][2]] for c in order], axis=0)
+                                           if order else np.zeros((0, len(haplotypes)))))
+    return [e[0] for e in entries], arrays
+
+
+def match_chromosome_mask(chroms, points_per_chrom, names=None):
+    """bool per handle chromosome: on the grid and, with `names` (a comma list or a sequence), named there.  An unknown
+    name, or a selection without a grid point, is a RuntimeError."""
+    points = np.asarray(points_per_chrom, dtype=np.int64)
+    use = points > 0
+    if names is not None:
+        wanted = [x for x in (names.split(',') if isinstance(names, str) else list(names)) if x != '']
+        for name in wanted:
+            if name not in chroms:
+                raise RuntimeError(f'--match-chromosomes: {name} is not a chromosome of the transition tables')
+        use = use & np.array([c in wanted for c in chroms], dtype=bool)
+    if int(points[use].sum()) == 0:
+        raise RuntimeError('--match-panel: the selected chromosomes have no grid points')
+    return use
+
+
+def match_scores(cross, sample_norm, panel_norm, points_per_chrom, use):
+    """(distance, similarity), each (..., n_panel), from the device's sums: cross (..., n_chrom, n_panel), sample_norm
+    (..., n_chrom), panel_norm (n_panel, n_chrom).  The chromosomes of the mask `use` are added left to right in handle
+    order into X, A, B and n grid points; distance = max(A + B - 2 X, 0) / n, the mean squared dosage difference per grid
+    point, in [0, 2]; similarity = X / sqrt(A B), 0.0 where A B == 0.  RuntimeError when n == 0."""
+    cross = np.asarray(cross, dtype=np.float64)
+    sample_norm = np.asarray(sample_norm, dtype=np.float64)
+    panel_norm = np.asarray(panel_norm, dtype=np.float64)
+    X = np.zeros(cross.shape[:-2] + cross.shape[-1:])
+    A = np.zeros(sample_norm.shape[:-1])
+    B = np.zeros(panel_norm.shape[0])
+    n = 0
+    for c in range(cross.shape[-2]):
+        if use[c]:
+            X = X + cross[..., c, :]
+            A = A + sample_norm[..., c]
+            B = B + panel_norm[:, c]
+            n += int(points_per_chrom[c])
+    if n == 0:
+        raise RuntimeError('no grid points on the chromosomes that are matched')
+    A = A[..., None]
+    distance = np.maximum(A + B - 2.0 * X, 0.0) / n
+    product = A * B
+    with np.errstate(invalid='ignore', divide='ignore'):
+        similarity = np.where(product == 0.0, 0.0, X / np.sqrt(product))
+    return distance, similarity
+
+
+def rank_matches(panel_ids, distance, expected=None):
+    """The panel entries by ascending distance, ties in panel order, for one sample.  Returns `order` (indices), `best`,
+    `best_distance`, `second` ('' for a one-entry panel, its distance and the margin then nan), `margin` = second
+    distance - best distance, `expected` ('' if none), `status` - `match` (the expected id is the best), `mismatch` (it is
+    not), `unlabelled` (no expected id), `unknown-label` (it is not in the panel) - and `expected_distance` (nan) and
+    `expected_rank` (1-based, 0) of an expected id that is in the panel.  No threshold decides anything."""
+    distance = np.asarray(distance, dtype=np.float64)
+    order = np.argsort(distance, kind='stable')
+    best = int(order[0])
+    out = {'order': order, 'best': panel_ids[best], 'best_distance': float(distance[best]), 'second': '',
+           'second_distance': float('nan'), 'margin': float('nan'), 'expected': '' if expected is None else expected,
+           'expected_distance': float('nan'), 'expected_rank': 0}
+    if len(order) > 1:
+        second = int(order[1])
+        out.update(second=panel_ids[second], second_distance=float(distance[second]),
+                   margin=float(distance[second]) - float(distance[best]))
+    if expected is None:
+        out['status'] = 'unlabelled'
+    elif expected not in panel_ids:
+        out['status'] = 'unknown-label'
+    else:
+        j = panel_ids.index(expected)
+        out.update(status='match' if j == best else 'mismatch', expected_distance=float(distance[j]),
+                   expected_rank=int(np.flatnonzero(order == j)[0]) + 1)
+    return out
+
+
+def write_match_table(path, panel_ids, distance, similarity, order):
+    """`<outbase>.match.tsv`: one line per panel entry in rank order, numbers as repr(float)."""
+    logger.info(f'Saving Panel Matches: {path}')
+    with open(path, 'w') as out:
+        out.write('#panel_id\tdistance\tsimilarity\n')
+        out.writelines(f'{panel_ids[j]}\t{repr(float(distance[j]))}\t{repr(float(similarity[j]))}\n' for j in order)
+
+
+def write_match_report(path, lines):
+    """`--match-report`: one line per sample that ran.  lines: (outbase, rank_matches' dict)."""
+    logger.info(f'Saving Match Report: {path}')
+    with open(path, 'w') as out:
+        out.write('#outbase\texpected\tstatus\tbest\tbest_distance\tsecond\tsecond_distance\tmargin\texpected_distance\t'
+                  'expected_rank\n')
+        for outbase, r in lines:
+            out.write('\t'.join([outbase, r['expected'], r['status'], r['best'], repr(r['best_distance']), r['second'],
+                                 repr(r['second_distance']), repr(r['margin']), repr(r['expected_distance']),
+                                 str(r['expected_rank'])]) + '\n')
+
+
+def write_match_matrix(path, outbases, panel_ids, chroms, points, distance, similarity, cross, sample_norm, panel_norm):
+    """`--match-matrix`: an .npz with `distance` and `similarity` (N x M), the device's sums per chromosome - `cross`
+    (N x n_chrom x M), `sample_norm` (N x n_chrom), `panel_norm` (M x n_chrom) - and `outbases`, `panel_ids`,
+    `chromosomes`, `points` (grid points per chromosome)."""
+    logger.info(f'Saving Match Matrix: {path}')
+    with open(path, 'wb') as out:
+        np.savez(out, distance=distance, similarity=similarity, cross=cross, sample_norm=sample_norm, panel_norm=panel_norm,
+                 outbases=np.asarray(outbases), panel_ids=np.asarray(panel_ids), chromosomes=np.asarray(chroms),
+                 points=np.asarray(points, dtype=np.int64))
+
+
+def _load_panel(ctx, match_panel, haplotypes, match_chromosomes):
+    """The panel of `--match-panel` onto the context (read once per context and panel file) and the chromosome mask and
+    grid points per handle chromosome of the sums; every refusal comes from here, before a sample runs."""
+    if ctx.panel is None or ctx.panel_file != match_panel:
+        logger.info(f'Loading match panel: {match_panel}')
+        ctx.panel = read_match_panel(match_panel, ctx, haplotypes)
+        ctx.panel_file = match_panel
+        ctx._panel_on_handle = False
+    slices = grid_layout(ctx)
+    points = [slices[c][2] if c in slices else 0 for c in ctx.chroms]
+    return match_chromosome_mask(ctx.chroms, points, match_chromosomes), points
+
+
 def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gpos_file: str = None,
                 expr_threshold: float = 1.5, sigma: float = 0.12, outbase: str = None,
                 device: int = 0, stage_times: dict = None, context: ReconstructContext = None,
                 grid_file: str = None, grid_genoprobs: bool = False, sim_geno: int = None,
                 sim_geno_seed: int = 0, diagnostics: bool = False, error_lod_threshold: float = 2.0,
-                gene_report: str = None, loglik: bool = False, alt_tprob_files=None, model_report: str = None) -> None:
+                gene_report: str = None, loglik: bool = False, alt_tprob_files=None, model_report: str = None,
+                match_panel: str = None, match_expected: str = None, match_chromosomes=None, match_labels: str = None,
+                match_report: str = None, match_matrix: str = None) -> None:
     """`gbrs reconstruct`: diplotype posteriors and Viterbi calls along every chromosome from
     gene-level TPMs.  Same inputs, defaults and three output files as gbrs_utils.reconstruct
     (gbrs_utils.py:382-609); the emission model and the three recursions run on the device.
@@ -883,9 +1170,15 @@ def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gp
     and in total.  `alt_tprob_files` (implies `loglik`; with a context, the context's): the sample's emissions are also
     scored under these table files on the device; if one of them explains the sample better than `tprob_file` (the first
     largest total, `tprob_file` first), the sample is run again under it and every file is the one a plain call with that
-    table file writes.  `model_report` belongs to a cohort and is refused here."""
+    table file writes.  `model_report` belongs to a cohort and is refused here.
+    `match_panel` (extension; needs a grid file): the sample's grid dosages are compared on the device with
+    those of every entry of the panel file and `<outbase>.match.tsv` lists the entries by distance; `match_expected`: the
+    panel id the sample should be (logged with its status), `match_chromosomes`: the chromosomes that are compared.
+    `match_labels`, `match_report` and `match_matrix` belong to a cohort and are refused here."""
     check_sim_geno_args(sim_geno, sim_geno_seed)
     check_diagnostics_args(diagnostics, error_lod_threshold, gene_report, cohort=False)
+    check_match_args(match_panel, match_labels, match_expected, match_chromosomes, match_report, match_matrix,
+                     grid_file if context is None else context.grid_file, cohort=False)
     if context is not None and alt_tprob_files is None:
         alt_tprob_files = context.alt_tprob_files
     check_loglik_args(loglik, alt_tprob_files, model_report, cohort=False, tprob_file=tprob_file)
@@ -919,10 +1212,12 @@ def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gp
         ctx.tables()
     if loglik and ctx.alt_tprob_files:
         ctx.alt_tables(num_haps)           # a file that does not fit is refused before the sample runs
+    if match_panel is not None:            # so is a panel that does not fit the grid
+        match_use, match_points = _load_panel(ctx, match_panel, haplotypes, match_chromosomes)
     marks['load'] = clock() - t0
 
     posterior, path_names, calls = {}, {}, {}
-    on_grid = drawn = diag = None
+    on_grid = drawn = diag = matched = None
     names = [tprob_file] + list(ctx.alt_tprob_files) if loglik else None
     scores = np.zeros((len(names), 0)) if loglik else None       # (candidates, chromosomes) of this sample
     if chroms:
@@ -951,7 +1246,8 @@ def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gp
                     reconstruct(expression_file, names[selected], expr_threshold=expr_threshold, sigma=sigma,
                                 outbase=outbase, device=device, stage_times=marks, context=ctx.alt_context(selected - 1),
                                 grid_genoprobs=grid_genoprobs, sim_geno=sim_geno, sim_geno_seed=sim_geno_seed,
-                                diagnostics=diagnostics, error_lod_threshold=error_lod_threshold)
+                                diagnostics=diagnostics, error_lod_threshold=error_lod_threshold,
+                                match_panel=match_panel, match_expected=match_expected, match_chromosomes=match_chromosomes)
                 finally:
                     if context is None:
                         ctx.close()
@@ -984,9 +1280,19 @@ def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gp
             t0 = clock()
             logger.info('Converting genotype probability on the grid')
             on_grid = hmm.grid(sample=0, want=('dosage', 'gamma_grid') if grid_genoprobs else ('dosage',))
-            if context is None:
+            if context is None and match_panel is None:
                 ctx.close()
             marks['grid'] = clock() - t0
+        if match_panel is not None:
+            t0 = clock()
+            logger.info('Matching the sample against the panel')
+            got = hmm.match(sample=0)
+            panel_norm = hmm.match_info()['panel_norm']
+            if context is None:
+                ctx.close()
+            distance, similarity = match_scores(got['cross'], got['sample_norm'], panel_norm, match_points, match_use)
+            matched = (distance, similarity, rank_matches(ctx.panel[0], distance, match_expected))
+            marks['match'] = clock() - t0
     elif ctx.grid is not None:
         on_grid = {'dosage': np.zeros((0, num_haps)), 'gamma_grid': [] if grid_genoprobs else None}
     if sim_geno is not None and drawn is None:
@@ -1004,6 +1310,10 @@ def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gp
         _save_diagnostics(stem, ctx, diplotypes, diag, error_lod_threshold)
     if loglik:
         write_loglik_table(f'{stem}.loglik.tsv', chroms, [len(ctx.gene_order[c]) for c in chroms], names, scores, 0)
+    if matched is not None:
+        distance, similarity, rank = matched
+        write_match_table(f'{stem}.match.tsv', ctx.panel[0], distance, similarity, rank['order'])
+        logger.info(f"Panel match: {rank['status']}, best {rank['best']} at {rank['best_distance']!r}")
     marks['save'] = clock() - t0
     logger.info('Done')
 
@@ -1029,7 +1339,9 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
                      grid_file: str = None, grid_genoprobs: bool = False, stage_times: dict = None,
                      context: ReconstructContext = None, sim_geno: int = None, sim_geno_seed: int = 0,
                      diagnostics: bool = False, error_lod_threshold: float = 2.0, gene_report: str = None,
-                     loglik: bool = False, alt_tprob_files=None, model_report: str = None) -> list:
+                     loglik: bool = False, alt_tprob_files=None, model_report: str = None,
+                     match_panel: str = None, match_labels: str = None, match_chromosomes=None, match_report: str = None,
+                     match_matrix: str = None, match_expected: str = None) -> list:
     """`gbrs reconstruct` for a cohort whose genes.tpm files exist (extension): one context, the tables on the device
     once, the samples through the HMM in launches of up to `batch_size`, and with `grid_file` one grid pass per launch.
     Every sample gets the files the single-sample call writes for its outbase.  All samples must carry the same
@@ -1044,9 +1356,17 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
     them explains better than `tprob_file` is run again, in a launch of its own, under a handle on that file (made at
     first need, kept for the cohort) and all of its files come from that run - the files of the single-sample command
     under that file - its path draws on its usual stream.
-    `model_report`: one line per sample that ran - outbase, selected file, margin, the totals per candidate."""
+    `model_report`: one line per sample that ran - outbase, selected file, margin, the totals per candidate.
+    `match_panel` (needs a grid file): one more device pass per launch compares every sample's grid dosages
+    with every entry of the panel file; every sample gets `<outbase>.match.tsv`.  `match_labels`: a file of lines
+    `outbase<TAB>panel id`, the entry each sample should be; `match_chromosomes`: the chromosomes that are compared;
+    `match_report`: one line per sample that ran with its status, best and second entry and margin; `match_matrix`: an
+    .npz with the distances, similarities and the device's sums of all samples that ran.  A sample that moved to another
+    table file is matched under that handle."""
     check_sim_geno_args(sim_geno, sim_geno_seed)
     check_diagnostics_args(diagnostics, error_lod_threshold, gene_report, cohort=True)
+    check_match_args(match_panel, match_labels, match_expected, match_chromosomes, match_report, match_matrix,
+                     grid_file if context is None else context.grid_file, cohort=True)
     if context is not None and alt_tprob_files is None:
         alt_tprob_files = context.alt_tprob_files
     check_loglik_args(loglik, alt_tprob_files, model_report, cohort=True, tprob_file=tprob_file)
@@ -1085,8 +1405,12 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
     ctx.load()
     if loglik and ctx.alt_tprob_files and ctx.chroms:
         ctx.alt_tables(num_haps)           # a file that does not fit is refused before any sample runs
+    matches = {}                           # sample -> (cross, sample_norm, distance, similarity, rank_matches' dict)
+    if match_panel is not None:
+        labels = read_match_labels(match_labels) if match_labels is not None else {}
+        match_use, match_points = _load_panel(ctx, match_panel, haplotypes, match_chromosomes)
     marks['load'] = clock() - t0
-    for key in ('read', 'hmm', 'grid', 'save') + (('loglik',) if loglik else ()):
+    for key in ('read', 'hmm', 'grid', 'save') + (('loglik',) if loglik else ()) + (('match',) if match_panel is not None else ()):
         marks[key] = 0.0
     names = [tprob_file] + list(ctx.alt_tprob_files) if loglik else None
     choices = {}                           # sample -> (selected candidate, margin, totals per candidate)
@@ -1094,7 +1418,7 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
     writers = ThreadPoolExecutor(max_workers=min(16, batch_size))
     pending = []
 
-    def save(k, results, on_grid, drawn=None, diag=None, on=None, scores=None):
+    def save(k, results, on_grid, drawn=None, diag=None, on=None, scores=None, matched=None):
         on = ctx if on is None else on     # the context the sample ran under
         _save_reconstruction(outbases[k], *results, threads=1)
         if on_grid is not None:
@@ -1106,6 +1430,8 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
         if scores is not None:
             write_loglik_table(f'{outbases[k]}.loglik.tsv', ctx.chroms, [len(ctx.gene_order[c]) for c in ctx.chroms], names,
                                scores, choices[k][0])
+        if matched is not None:
+            write_match_table(f'{outbases[k]}.match.tsv', ctx.panel[0], matched[2], matched[3], matched[4]['order'])
 
     report = None
 
@@ -1147,6 +1473,17 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
             t0 = clock()
             on_grid = hmm.grid(want=('dosage', 'gamma_grid') if grid_genoprobs else ('dosage',))
             marks['grid'] += clock() - t0
+        if match_panel is not None and stay:
+            t0 = clock()
+            got = hmm.match()
+            panel_norm = hmm.match_info()['panel_norm']
+            distance, similarity = match_scores(got['cross'], got['sample_norm'], panel_norm, match_points, match_use)
+            for s in stay:
+                k = members[s]
+                matches[k] = (got['cross'][s], got['sample_norm'][s], distance[s], similarity[s],
+                              rank_matches(ctx.panel[0], distance[s], labels.get(outbases[k])))
+            matches['panel_norm'] = panel_norm
+            marks['match'] += clock() - t0
         drawn = None
         if sim_geno is not None and stay:
             t0 = clock()
@@ -1168,7 +1505,7 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
             grid_of = None if on_grid is None else (on_grid['dosage'][s], on_grid['gamma_grid'][s] if grid_genoprobs else None)
             pending.append((k, writers.submit(save, k, results[s], grid_of, None if drawn is None else drawn[s],
                                               None if diags is None else diags[s], on,
-                                              None if scores_of is None else scores_of[k])))
+                                              None if scores_of is None else scores_of[k], matches.get(k))))
         marks['save'] += clock() - t0
         return moved, scores_of
 
@@ -1209,6 +1546,16 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
             (report if report is not None else GeneReport(ctx, error_lod_threshold)).write(gene_report)
         if model_report is not None:
             write_model_report(model_report, names, [(outbases[k],) + choices[k] for k in sorted(choices)])
+        if match_panel is not None:
+            ran = sorted(k for k in matches if k != 'panel_norm')
+            if match_report is not None:
+                write_match_report(match_report, [(outbases[k], matches[k][4]) for k in ran])
+            if match_matrix is not None:
+                M, nc = len(ctx.panel[0]), len(ctx.chroms)
+                stack = lambda i, shape: np.stack([matches[k][i] for k in ran]) if ran else np.zeros(shape)
+                write_match_matrix(match_matrix, [outbases[k] for k in ran], ctx.panel[0], ctx.chroms, match_points,
+                                   stack(2, (0, M)), stack(3, (0, M)), stack(0, (0, nc, M)), stack(1, (0, nc)),
+                                   matches.get('panel_norm', np.zeros((M, nc))))
         marks['save'] += clock() - t0
     finally:
         writers.shutdown(wait=True)

@@ -712,6 +712,32 @@ int gbrs_hmm_grid(gbrs_hmm_t *hmm, int sample, double *dosage, double *gamma_gri
 /* M of the handle's grid (0 without one) and the device time of the last gbrs_hmm_grid kernel; both nullable. */
 int gbrs_hmm_grid_info(gbrs_hmm_t *hmm, int64_t *n_points, double *last_ms);
 
+/* Matching the run's samples against a panel of reference animals (extension; `gbrs reconstruct --match-panel`).
+ * With a[s][p][h] the grid dosage of sample s (gbrs_hmm_grid's `dosage`) and b[j][p][h] the dosage of panel entry j on
+ * the same grid points, the device forms, for every chromosome c of the handle,
+ *   cross[s][c][j]     = sum over the grid points p of c and the founders h of a[s][p][h] * b[j][p][h]
+ *   sample_norm[s][c]  = sum of a[s][p][h]^2          panel_norm[j][c] = sum of b[j][p][h]^2
+ * and nothing else; a chromosome without grid points gives 0.0 three times.  Every sum is formed by one wavefront in an
+ * order that depends on the chromosome alone: a sample's numbers do not depend on the launch it ran in or on whether it
+ * was asked for alone, an entry's column not on the entries after it.
+ *
+ * gbrs_hmm_set_panel: panel[j] is double[M][H] in the layout of `dosage` (grid points of the handle's chromosomes in
+ * handle order).  The panel is copied to the device and panel_norm computed there.  Needs a grid (GBRS_ERR_INVALID);
+ * a value that is not finite is refused with GBRS_ERR_INVALID naming the entry; n_panel = 0 drops the panel.  On
+ * failure the handle keeps the panel it had.  gbrs_hmm_set_grid drops the panel. */
+int gbrs_hmm_set_panel(gbrs_hmm_t *hmm, int n_panel, const double *const *panel);
+
+/* sample = -1: all n samples of the run, else that one (n = 1).  cross is double[n][n_chrom][n_panel], sample_norm
+ * double[n][n_chrom]; both nullable, one device-to-host copy each.  The dosages are those of the last gbrs_hmm_grid call
+ * if it produced dosages for the same `sample` argument since the last run; otherwise the grid kernel runs first, dosage
+ * only.  GBRS_ERR_STATE before the first run, GBRS_ERR_INVALID without a panel or for a sample out of range; the outputs
+ * are untouched on failure. */
+int gbrs_hmm_match(gbrs_hmm_t *hmm, int sample, double *cross, double *sample_norm);
+
+/* Entries of the panel (0 without one), panel_norm double[n_panel][n_chrom], the device time of the last
+ * gbrs_hmm_match call's own kernels, and the device memory the panel and the outputs hold; all nullable. */
+int gbrs_hmm_match_info(gbrs_hmm_t *hmm, int *n_panel, double *panel_norm, double *last_ms, uint64_t *device_bytes);
+
 /* Diplotype paths drawn from the joint posterior of the last run (extension; forward-filter / backward-sample on the
  * run's filtered forward values, which the first call makes like gbrs_hmm_get(alpha)).  sample = -1: all n samples of
  * the run, else that one (n = 1).  Draw d of a sample, chromosome c, genes i = n_c - 1 .. 0:

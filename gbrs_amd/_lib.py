@@ -31,6 +31,7 @@ EXPORTS = [
     "gbrs_grid_knots", "gbrs_hmm_set_grid", "gbrs_hmm_grid", "gbrs_hmm_grid_info", "gbrs_hmm_sample_paths", "gbrs_hmm_sample_info",
     "gbrs_hmm_diagnostics", "gbrs_hmm_pair_posterior", "gbrs_hmm_diagnostics_info",
     "gbrs_hmm_set_panel", "gbrs_hmm_match", "gbrs_hmm_match_info",
+    "gbrs_hmm_set_snps", "gbrs_hmm_impute", "gbrs_hmm_impute_info", "gbrs_hmm_impute_times",
     "gbrs_hmm_loglik", "gbrs_hmm_loglik_tables", "gbrs_hmm_loglik_info", "gbrs_interpolate", "gbrs_genoprob_dosage",
     "gbrs_ri_transition_tables", "gbrs_alignment_spec",
     "gbrs_compress_create", "gbrs_compress_get", "gbrs_compress_destroy",
@@ -181,6 +182,10 @@ def load():
         "gbrs_hmm_set_panel": [vp, i32, pp],
         "gbrs_hmm_match": [vp, i32, vp, vp],
         "gbrs_hmm_match_info": [vp, C.POINTER(i32), vp, C.POINTER(dbl), C.POINTER(u64)],
+        "gbrs_hmm_set_snps": [vp, vp, pp, vp, pp, pp],
+        "gbrs_hmm_impute": [vp, i32, i64, i64, vp],
+        "gbrs_hmm_impute_info": [vp, C.POINTER(i64), C.POINTER(dbl), C.POINTER(u64)],
+        "gbrs_hmm_impute_times": [vp, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)],
         "gbrs_hmm_sample_paths": [vp, i32, i32, u64, vp, vp, vp, C.POINTER(u64)],
         "gbrs_hmm_sample_info": [vp, C.POINTER(dbl), C.POINTER(u64)],
         "gbrs_hmm_diagnostics": [vp, i32, vp, vp, vp, vp, vp],

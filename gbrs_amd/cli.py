@@ -122,6 +122,14 @@ def build_parser():
     r.add_argument('--match-matrix', default=None, metavar='PATH',
                    help='with --match-panel and --sample-file: an .npz with the distances and similarities of all samples '
                         'against all entries and the sums they were made from')
+    r.add_argument('--snp-file', type=_existing, default=None, metavar='FILE',
+                   help='(extension) SNPs to impute from the founder haplotypes: one header line, then tab separated '
+                        '`id, chr, bp, cM, pattern`, the pattern one 0/1 character per haplotype (1: the founder carries the '
+                        'alternative allele); a cM of NA is filled from bp over the rows of --grid-file.  Writes '
+                        '<outbase>.snp_dosage.npz: the expected number of alternative alleles at every SNP, in file order')
+    r.add_argument('--snp-matrix', default=None, metavar='PATH',
+                   help='with --snp-file and --sample-file: an .npz with the SNP dosages of all samples (samples x SNPs) '
+                        'and the columns of the SNP file')
     r.add_argument('-t', '--tprob-file', required=True, type=_existing)
     r.add_argument('-x', '--avec-file', type=_existing, default=None)
     r.add_argument('-g', '--gpos-file', type=_existing, default=None)
@@ -283,6 +291,8 @@ def main(argv=None) -> int:
             from .hmm import check_match_args
             check_match_args(args.match_panel, args.match_labels, args.match_expected, args.match_chromosomes,
                              args.match_report, args.match_matrix, args.grid_file, cohort=args.sample_file is not None)
+            from .hmm import check_snp_args
+            check_snp_args(args.snp_file, args.snp_matrix, cohort=args.sample_file is not None)
         if args.command == 'quantify' and args.gpus is not None:
             # N child processes, one per rank; this process opens no device
             from .sharded import launch
@@ -399,7 +409,7 @@ def main(argv=None) -> int:
                              loglik=args.loglik, alt_tprob_files=args.alt_tprob_file, model_report=args.model_report,
                              match_panel=args.match_panel, match_labels=args.match_labels,
                              match_chromosomes=args.match_chromosomes, match_report=args.match_report,
-                             match_matrix=args.match_matrix)
+                             match_matrix=args.match_matrix, snp_file=args.snp_file, snp_matrix=args.snp_matrix)
         else:
             from .hmm import reconstruct
             reconstruct(expression_file=args.expression_file, tprob_file=args.tprob_file,
@@ -409,7 +419,8 @@ def main(argv=None) -> int:
                         grid_genoprobs=args.grid_genoprobs, sim_geno=args.sim_geno, sim_geno_seed=args.sim_geno_seed,
                         diagnostics=args.diagnostics, error_lod_threshold=args.error_lod_threshold,
                         loglik=args.loglik, alt_tprob_files=args.alt_tprob_file, match_panel=args.match_panel,
-                        match_expected=args.match_expected, match_chromosomes=args.match_chromosomes)
+                        match_expected=args.match_expected, match_chromosomes=args.match_chromosomes,
+                        snp_file=args.snp_file)
     except Exception as e:   # noqa: BLE001 - mirror of the reference's catch-all
         failure = e
         if logger.level == logging.DEBUG:

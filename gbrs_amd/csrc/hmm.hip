@@ -2485,6 +2485,7 @@ __global__ void dosage_kernel(int H, int S, int64_t rows, const double *__restri
 
 #include "hmm_grid.inc"
 #include "hmm_match.inc"
+#include "hmm_impute.inc"
 #include "hmm_sample.inc"
 #include "hmm_diag.inc"
 #include "hmm_loglik.inc"
@@ -2572,6 +2573,17 @@ struct gbrs_hmm {
     DevBuf<MatchChrom> d_match_chroms;
     std::vector<double> panel_norm;           // [n_panel][n_chrom]
     double t_match = 0;
+    // SNP imputation (hmm_impute.inc): positions, patterns and the knot above every SNP stay here like the grid (16 B per
+    // SNP), with the knots and their gene rows; snp_d is D[n][total_genes][H], the founder dosages at the genes of the
+    // last run, made by the first gbrs_hmm_impute call after a run and kept for its later chunks; snp_out holds one chunk
+    int64_t n_snps = 0;
+    DevBuf<SnpChrom> d_snp_chroms;
+    DevBuf<double> snp_knot_x, snp_x, snp_d, snp_out;
+    DevBuf<int32_t> snp_knot_row, snp_idx;
+    DevBuf<uint32_t> snp_mask;
+    bool snp_d_ready = false;                 // snp_d holds the last run's dosages for `snp_d_sample` (-1: all)
+    int snp_d_sample = -1;
+    double t_snp_setup = 0, t_snp_d = 0, t_snp_kernel = 0;   // device ms: the last set_snps; D and the kernel of the last pass
     // Path draws (hmm_sample.inc): the change table is made on the first call; the other buffers hold one slab of draws
     DevBuf<uint8_t> smp_change_tab, smp_cols, smp_paths;
     DevBuf<int32_t> smp_changes;
@@ -3503,6 +3515,7 @@ int gbrs_hmm_set_expression(gbrs_hmm_t *h, int n_samples, const double *const *e
     h->pe_ready = !h->emission_pending;
     h->ran = false;
     h->grid_dosage_ready = false;
+    h->snp_d_ready = false;
     return GBRS_OK;
 }
 
@@ -3523,6 +3536,7 @@ int gbrs_hmm_set_eprob(gbrs_hmm_t *h, int n_samples, const double *const *eprob)
     h->pe_ready = false;
     h->ran = false;
     h->grid_dosage_ready = false;
+    h->snp_d_ready = false;
     h->t_emis = 0;
     return GBRS_OK;
 }
@@ -3536,6 +3550,7 @@ int gbrs_hmm_run(gbrs_hmm_t *h) {
     const HmmTuning t = hmm_tuning_from_env();
     const HmmRoute r = hmm_route(hmm_shape(h), t, h->emission_pending);
     h->grid_dosage_ready = false;
+    h->snp_d_ready = false;
     int rc;
     if (r.grouped) {
         rc = hmm_launch_groups(h, r, t);
@@ -3917,6 +3932,159 @@ int gbrs_hmm_match_info(gbrs_hmm_t *h, int *n_panel, double *panel_norm, double 
     if (last_ms) *last_ms = h->t_match;
     if (device_bytes)
         *device_bytes = h->match_panel.bytes() + h->match_cross.bytes() + h->match_snorm.bytes() + h->d_match_chroms.bytes();
+    return GBRS_OK;
+}
+
+int gbrs_hmm_set_snps(gbrs_hmm_t *h, const int32_t *n_pos, const double *const *gene_pos, const int32_t *n_snps,
+                      const double *const *snp_pos, const uint32_t *const *snp_mask) {
+    RoctxRange roctx_range("gbrs_hmm_set_snps");
+    if (!h || !n_pos || !gene_pos || !n_snps || !snp_pos || !snp_mask) return fail(GBRS_ERR_INVALID, "bad argument");
+    // everything is prepared and checked before the handle changes
+    std::vector<SnpChrom> sc(h->n_chrom);
+    std::vector<double> knot_x;
+    std::vector<int32_t> knot_gene, knot_row;
+    int64_t total = 0;
+    const uint32_t beyond = h->H >= 32 ? 0u : ~0u << h->H;
+    if (h->total_genes + 2 * (int64_t)h->n_chrom > INT32_MAX) return fail(GBRS_ERR_INVALID, "too many genes for SNP knots");
+    for (int c = 0; c < h->n_chrom; ++c) {
+        const ChromDesc &cd = h->chroms[c];
+        SnpChrom &s = sc[c];
+        s.gene_off = cd.gene_off;
+        s.knot_off = (int32_t)knot_x.size();
+        s.n_knots = 0;
+        s.snp_off = total;
+        if (n_snps[c] < 0) return fail(GBRS_ERR_INVALID, "n_snps[%d] is negative", c);
+        if (n_snps[c] == 0) continue;
+        if (!snp_pos[c] || !snp_mask[c]) return fail(GBRS_ERR_INVALID, "chromosome %d: SNP positions or patterns are NULL", c);
+        if (n_pos[c] == 0)
+            return fail(GBRS_ERR_INVALID, "index -1 is out of bounds for axis 1 with size 0 (SNP chromosome %d has no genes)", c);
+        if (n_pos[c] != cd.n_genes)
+            return fail(GBRS_ERR_INVALID, "chromosome %d: %d gene positions for %d genes", c, n_pos[c], cd.n_genes);
+        for (int32_t k = 0; k < n_snps[c]; ++k)
+            if (snp_mask[c][k] & beyond)
+                return fail(GBRS_ERR_INVALID, "chromosome %d, SNP %d: the pattern 0x%x names a founder at or above %d", c, k,
+                            snp_mask[c][k], h->H);
+        s.n_knots = cd.n_genes + 2;
+        knot_x.resize(knot_x.size() + s.n_knots);
+        knot_gene.resize(knot_x.size());
+        GBRS_TRY(gbrs_grid_knots(cd.n_genes, gene_pos[c], n_snps[c], snp_pos[c], knot_x.data() + s.knot_off,
+                                 knot_gene.data() + s.knot_off));
+        total += n_snps[c];
+    }
+    if (total == 0) {
+        h->d_snp_chroms.release();
+        h->snp_knot_x.release();
+        h->snp_knot_row.release();
+        h->snp_x.release();
+        h->snp_mask.release();
+        h->snp_idx.release();
+        h->snp_out.release();
+        h->n_snps = 0;
+        return GBRS_OK;
+    }
+    knot_row.resize(knot_gene.size());
+    for (int c = 0; c < h->n_chrom; ++c)
+        for (int32_t k = 0; k < sc[c].n_knots; ++k)
+            knot_row[sc[c].knot_off + k] = (int32_t)(sc[c].gene_off + knot_gene[sc[c].knot_off + k]);
+    GBRS_TRY(select_device(h->device));
+    DevBuf<SnpChrom> d_sc;
+    DevBuf<double> d_knot_x, d_x;
+    DevBuf<int32_t> d_knot_row, d_idx;
+    DevBuf<uint32_t> d_mask;
+    GBRS_TRY(d_sc.alloc(sc.size()));
+    GBRS_TRY(d_knot_x.alloc(knot_x.size()));
+    GBRS_TRY(d_knot_row.alloc(knot_row.size()));
+    GBRS_TRY(d_x.alloc((size_t)total));
+    GBRS_TRY(d_mask.alloc((size_t)total));
+    GBRS_TRY(d_idx.alloc((size_t)total));
+    GBRS_HIP_CHECK(hipMemcpy(d_sc.p, sc.data(), d_sc.bytes(), hipMemcpyHostToDevice));
+    GBRS_HIP_CHECK(hipMemcpy(d_knot_x.p, knot_x.data(), d_knot_x.bytes(), hipMemcpyHostToDevice));
+    GBRS_HIP_CHECK(hipMemcpy(d_knot_row.p, knot_row.data(), d_knot_row.bytes(), hipMemcpyHostToDevice));
+    for (int c = 0; c < h->n_chrom; ++c) {
+        if (n_snps[c] == 0) continue;
+        GBRS_HIP_CHECK(hipMemcpy(d_x.p + sc[c].snp_off, snp_pos[c], (size_t)n_snps[c] * sizeof(double), hipMemcpyHostToDevice));
+        GBRS_HIP_CHECK(hipMemcpy(d_mask.p + sc[c].snp_off, snp_mask[c], (size_t)n_snps[c] * sizeof(uint32_t),
+                                 hipMemcpyHostToDevice));
+    }
+    GBRS_HIP_CHECK(hipEventRecord(h->ev[0], h->stream));
+    hipLaunchKernelGGL(snp_setup_kernel, dim3((unsigned)((total + IMPUTE_THREADS - 1) / IMPUTE_THREADS)), dim3(IMPUTE_THREADS), 0,
+                       h->stream, h->n_chrom, total, d_sc.p, d_knot_x.p, d_x.p, d_idx.p);
+    GBRS_HIP_CHECK(hipEventRecord(h->ev[1], h->stream));
+    GBRS_HIP_CHECK(hipGetLastError());
+    GBRS_HIP_CHECK(hipStreamSynchronize(h->stream));
+    float ms = 0.f;
+    h->t_snp_setup = hipEventElapsedTime(&ms, h->ev[0], h->ev[1]) == hipSuccess ? ms : 0.0;
+    h->d_snp_chroms.swap(d_sc);
+    h->snp_knot_x.swap(d_knot_x);
+    h->snp_knot_row.swap(d_knot_row);
+    h->snp_x.swap(d_x);
+    h->snp_mask.swap(d_mask);
+    h->snp_idx.swap(d_idx);
+    h->n_snps = total;
+    return GBRS_OK;
+}
+
+int gbrs_hmm_impute(gbrs_hmm_t *h, int sample, int64_t first, int64_t count, double *out) {
+    RoctxRange roctx_range("gbrs_hmm_impute");
+    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (!h->ran) return fail(GBRS_ERR_STATE, "run() has not been called");
+    if (h->n_snps == 0) return fail(GBRS_ERR_INVALID, "no SNPs on the handle: call gbrs_hmm_set_snps first");
+    if (sample < -1 || sample >= h->n_samples) return fail(GBRS_ERR_INVALID, "sample out of range");
+    if (first < 0 || count < 0 || first > h->n_snps || count > h->n_snps - first)
+        return fail(GBRS_ERR_INVALID, "SNPs %lld .. %lld are outside 0 .. %lld", (long long)first, (long long)first + count,
+                    (long long)h->n_snps);
+    if (count == 0) return GBRS_OK;
+    if (!out) return fail(GBRS_ERR_INVALID, "out is NULL");
+    GBRS_TRY(select_device(h->device));
+    const int S = h->S, H = h->H;
+    const int n = sample < 0 ? h->n_samples : 1;
+    const size_t n_out = (size_t)n * count;
+    if (h->snp_out.n < n_out) GBRS_TRY(h->snp_out.alloc(n_out));
+    const bool make_d = !(h->snp_d_ready && h->snp_d_sample == sample);
+    GBRS_HIP_CHECK(hipEventRecord(h->ev[0], h->stream));
+    if (make_d) {
+        const int64_t rows = (int64_t)n * h->total_genes;
+        h->snp_d_ready = false;
+        if (h->snp_d.n != (size_t)rows * H) GBRS_TRY(h->snp_d.alloc((size_t)rows * H));
+        hipLaunchKernelGGL(dosage_kernel, dim3((unsigned)((rows * H + 255) / 256)), dim3(256), 0, h->stream, H, S, rows,
+                           h->gamma.p + (int64_t)std::max(sample, 0) * h->total_genes * S, h->snp_d.p);
+    }
+    GBRS_HIP_CHECK(hipEventRecord(h->ev[1], h->stream));
+    const dim3 grid((unsigned)((count + IMPUTE_THREADS - 1) / IMPUTE_THREADS), (unsigned)((n + IMPUTE_SAMPLES - 1) / IMPUTE_SAMPLES));
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(IMPUTE_THREADS), 0, h->stream, H, n, h->total_genes, first, count, h->snp_knot_x.p,
+                           h->snp_knot_row.p, h->snp_x.p, h->snp_mask.p, h->snp_idx.p, h->snp_d.p, h->snp_out.p);
+    };
+    if (H == 8) launch(impute_kernel<true, 8>);
+    else if (H % 2 == 0) launch(impute_kernel<true, 0>);
+    else launch(impute_kernel<false, 0>);
+    GBRS_HIP_CHECK(hipEventRecord(h->ev[2], h->stream));
+    GBRS_HIP_CHECK(hipGetLastError());
+    GBRS_HIP_CHECK(hipStreamSynchronize(h->stream));
+    float ms = 0.f;
+    h->t_snp_d = make_d && hipEventElapsedTime(&ms, h->ev[0], h->ev[1]) == hipSuccess ? ms : 0.0;
+    h->t_snp_kernel = hipEventElapsedTime(&ms, h->ev[1], h->ev[2]) == hipSuccess ? ms : 0.0;
+    h->snp_d_ready = true;
+    h->snp_d_sample = sample;
+    GBRS_HIP_CHECK(hipMemcpy(out, h->snp_out.p, n_out * sizeof(double), hipMemcpyDeviceToHost));
+    return GBRS_OK;
+}
+
+int gbrs_hmm_impute_info(gbrs_hmm_t *h, int64_t *n_snps, double *last_ms, uint64_t *device_bytes) {
+    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (n_snps) *n_snps = h->n_snps;
+    if (last_ms) *last_ms = h->t_snp_d + h->t_snp_kernel;
+    if (device_bytes)
+        *device_bytes = h->d_snp_chroms.bytes() + h->snp_knot_x.bytes() + h->snp_knot_row.bytes() + h->snp_x.bytes() +
+                        h->snp_mask.bytes() + h->snp_idx.bytes() + h->snp_d.bytes() + h->snp_out.bytes();
+    return GBRS_OK;
+}
+
+int gbrs_hmm_impute_times(gbrs_hmm_t *h, double *setup_ms, double *dosage_ms, double *kernel_ms) {
+    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (setup_ms) *setup_ms = h->t_snp_setup;
+    if (dosage_ms) *dosage_ms = h->t_snp_d;
+    if (kernel_ms) *kernel_ms = h->t_snp_kernel;
     return GBRS_OK;
 }
 

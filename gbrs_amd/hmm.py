@@ -195,6 +195,66 @@ class DiplotypeHMM:
             _lib.check(lib.gbrs_hmm_match_info(self._h, None, _lib.ptr(norm), None, None))
         return {'n_panel': m.value, 'panel_norm': norm, 'last_ms': ms.value, 'device_bytes': nbytes.value}
 
+    def set_snps(self, gene_positions, positions, masks):
+        """The SNPs of the handle (sample independent, uploaded once).  The arguments go by handle
+        chromosome like set_grid's: a sequence in the handle's order or a dict by chromosome name.  positions[c]: the
+        SNP positions of the chromosome in file order (None, empty or absent: it has none), masks[c]: their founder
+        allele patterns as uint32, bit h set when founder h carries the alternative allele; gene_positions[c]: the
+        positions of its genes.  The SNPs of a chromosome are a grid: a SNP outside the knots raises the grid's
+        ValueError.  All empty drops the SNPs.  Independent of set_grid and set_panel."""
+        def by_chrom(table):
+            if isinstance(table, dict):
+                return [table.get(c) for c in self.chroms]
+            return list(table) + [None] * (len(self.chroms) - len(table))
+        points = [np.zeros(0) if x is None else np.ascontiguousarray(x, dtype=np.float64) for x in by_chrom(positions)]
+        bits = [np.zeros(0, dtype=np.uint32) if m is None else np.ascontiguousarray(m, dtype=np.uint32) for m in by_chrom(masks)]
+        for c, x, m in zip(self.chroms, points, bits):
+            if x.shape != m.shape or x.ndim != 1:
+                raise ValueError(f'chromosome {c}: {x.shape} SNP positions and {m.shape} patterns')
+        where = [np.zeros(0) if len(x) == 0 or g is None else np.ascontiguousarray(g, dtype=np.float64)
+                 for x, g in zip(points, by_chrom(gene_positions))]
+        n_snps = np.asarray([len(x) for x in points], dtype=np.int32)
+        n_pos = np.asarray([len(g) for g in where], dtype=np.int32)
+        lib = _lib.load()
+        status = lib.gbrs_hmm_set_snps(self._h, _lib.ptr(n_pos), _lib.ptr_table(where), _lib.ptr(n_snps),
+                                       _lib.ptr_table(points), _lib.ptr_table(bits))
+        _raise_grid_error(lib, status)
+        self.snp_points = [int(m) for m in n_snps]
+        self.snp_offsets = [int(o) for o in np.concatenate(([0], np.cumsum(n_snps)[:-1]))]
+
+    def impute(self, sample=None, chunk=1 << 20):
+        """The expected number of alternative alleles at every SNP of the handle from the last run: [n, M], the SNPs of
+        the handle's chromosomes one after the other (chromosome c: columns snp_offsets[c] .. + snp_points[c]).
+        sample=None: every sample of the run (n of them); an index: that sample, [M].  The range is walked in chunks of
+        `chunk` SNPs, one device pass and one copy each; the founder dosages at the genes are made by the first."""
+        if chunk < 1:
+            raise ValueError('chunk must be at least 1')
+        lib = _lib.load()
+        n = self.n_samples if sample is None else 1
+        which = -1 if sample is None else int(sample)
+        M = self.impute_info()['n_snps']
+        out = np.empty((n, M))
+        if M <= chunk:
+            _lib.check(lib.gbrs_hmm_impute(self._h, which, 0, M, _lib.ptr(out)))
+        else:
+            for first in range(0, M, chunk):
+                part = np.empty((n, min(chunk, M - first)))
+                _lib.check(lib.gbrs_hmm_impute(self._h, which, first, part.shape[1], _lib.ptr(part)))
+                out[:, first:first + part.shape[1]] = part
+        return out if sample is None else out[0]
+
+    def impute_info(self):
+        """n_snps on the handle, the device milliseconds of the last imputation pass's kernels (`last_ms`; its parts
+        `dosage_ms` and `kernel_ms`, and `setup_ms` of the last set_snps) and the device bytes the SNPs, the gene
+        dosages and the output chunk hold."""
+        lib = _lib.load()
+        m, ms, nbytes = C.c_int64(), C.c_double(), C.c_uint64()
+        setup, dosage, kernel = C.c_double(), C.c_double(), C.c_double()
+        _lib.check(lib.gbrs_hmm_impute_info(self._h, C.byref(m), C.byref(ms), C.byref(nbytes)))
+        _lib.check(lib.gbrs_hmm_impute_times(self._h, C.byref(setup), C.byref(dosage), C.byref(kernel)))
+        return {'n_snps': m.value, 'last_ms': ms.value, 'device_bytes': nbytes.value, 'setup_ms': setup.value,
+                'dosage_ms': dosage.value, 'kernel_ms': kernel.value}
+
     def sample_paths(self, n_draws, seed=0, sample=None, streams=None):
         """Diplotype paths drawn from the joint posterior of the last run, one device pass per slab of
         draws.  sample=None: every sample of the run (n of them); an index: that sample, without the leading axis.
@@ -437,6 +497,10 @@ class ReconstructContext:
         self.panel_file = None
         self.panel_uploads = 0            # times the panel went to a device handle, alternative-table handles included
         self._panel_on_handle = False
+        self.snps = None                  # read_snp_file's dict of --snp-file (_load_snps)
+        self.snp_file = None
+        self.snp_uploads = 0              # times the SNPs went to a device handle, alternative-table handles included
+        self._snps_on_handle = False
 
     def load(self, marks=None):
         """The files (the big transition tables inflate on the library's threads while the small files are parsed)."""
@@ -515,6 +579,9 @@ class ReconstructContext:
             subs[a] = sub
         if subs[a].panel_file != self.panel_file:
             subs[a].panel, subs[a].panel_file, subs[a]._panel_on_handle = self.panel, self.panel_file, False
+        if subs[a].snp_file != self.snp_file:
+            subs[a].snps, subs[a].snp_file, subs[a]._snps_on_handle = self.snps, self.snp_file, False
+            subs[a].gene_positions = self.gene_positions
         return subs[a]
 
     def specificity(self, num_haps):
@@ -552,6 +619,12 @@ class ReconstructContext:
             self.hmm.set_panel(self.panel[1])
             self._panel_on_handle = True
             self.__dict__.get('_panel_owner', self).panel_uploads += 1
+        if self.snps is not None and not self._snps_on_handle:
+            by = self.snps['by_chrom']
+            self.hmm.set_snps(self.gene_positions, {c: self.snps['cM'][by[c]] for c in self.chroms},
+                              {c: self.snps['mask'][by[c]] for c in self.chroms})
+            self._snps_on_handle = True
+            self.__dict__.get('_panel_owner', self).snp_uploads += 1
         return self.hmm, first_use
 
     def close(self):
@@ -559,6 +632,7 @@ class ReconstructContext:
             self.hmm.close()
             self.hmm = None
             self._panel_on_handle = False
+            self._snps_on_handle = False
         for sub in self.__dict__.get('_alt_contexts', {}).values():
             sub.close()
 
@@ -1142,6 +1216,144 @@ def _load_panel(ctx, match_panel, haplotypes, match_chromosomes):
     return match_chromosome_mask(ctx.chroms, points, match_chromosomes), points
 
 
+# ---- SNP dosages imputed from the founder haplotypes (`--snp-file`) ---------------------------------------
+
+def check_snp_args(snp_file=None, snp_matrix=None, cohort=False):
+    """`--snp-file FILE [--snp-matrix PATH]`: the matrix needs the SNP file and belongs to a cohort (`--sample-file`).
+    Refused before a file is read."""
+    if snp_matrix is None:
+        return
+    if snp_file is None:
+        raise RuntimeError('--snp-matrix needs --snp-file')
+    if not cohort:
+        raise RuntimeError('--snp-matrix needs --sample-file')
+
+
+def _grid_bp_cm(grid_file):
+    """{chromosome: (bp ascending, cM in that order)} of a grid file, for filling SNP positions."""
+    rows = {}
+    with open(grid_file) as fh:
+        fh.readline()
+        for line in fh:
+            fields = line.rstrip('\n').split('\t')
+            if len(fields) > 3:
+                rows.setdefault(fields[1], []).append((float(fields[2]), float(fields[3])))
+    table = {}
+    for c, pairs in rows.items():
+        a = np.asarray(pairs, dtype=np.float64)
+        order = np.argsort(a[:, 0], kind='stable')
+        table[c] = (a[order, 0], a[order, 1])
+    return table
+
+
+def read_snp_file(path, haplotypes, chroms, grid_file=None):
+    """The SNPs of `--snp-file`: one header line, then tab separated `id, chr, bp, cM, pattern` - the grid file's four
+    columns and one character per haplotype of `haplotypes`, `1` where that founder carries the alternative allele, else
+    `0`.  A cM of `NA` or empty is filled from bp by np.interp over that chromosome's rows of `grid_file` sorted by bp
+    (clamped at the ends); without a grid file, or when the grid file lacks the chromosome, the line is refused.  Every
+    other line - too few columns, a pattern of another length or with another character, a position that is no number -
+    is a ValueError naming the line number and the reason.
+    Returns a dict: `snp_id`, `chrom`, `bp`, `cM`, `pattern` (arrays in file order, bp nan where it is NA), `mask`
+    (uint32, bit h: haplotype h), `by_chrom` {c: file rows of chromosome c, file order} for the chromosomes of `chroms`,
+    `order` (those rows, chromosomes in the order of `chroms`: the handle's SNP order) and `foreign`, the number of
+    SNPs on other chromosomes, which one log warning counts."""
+    H = len(haplotypes)
+    ids, chrom, bp, cm, patterns, fill = [], [], [], [], [], []
+    with open(path) as fh:
+        fh.readline()
+        for number, line in enumerate(fh, 2):
+            line = line.rstrip('\r\n')
+            if not line:
+                continue
+            fields = line.split('\t')
+            if len(fields) < 5:
+                raise ValueError(f'{path}, line {number}: {len(fields)} columns, expected id, chr, bp, cM, pattern')
+            pattern = fields[4]
+            if len(pattern) != H:
+                raise ValueError(f'{path}, line {number}: the pattern {pattern!r} has {len(pattern)} characters for '
+                                 f'{H} haplotypes')
+            if pattern.strip('01'):
+                raise ValueError(f'{path}, line {number}: the pattern {pattern!r} holds a character other than 0 and 1')
+            try:
+                where = float('nan') if fields[2] in ('NA', '') else float(fields[2])
+                x = None if fields[3] in ('NA', '') else float(fields[3])
+            except ValueError:
+                raise ValueError(f'{path}, line {number}: the position {fields[2]!r} / {fields[3]!r} is not a number') from None
+            if x is None:
+                if grid_file is None:
+                    raise ValueError(f'{path}, line {number}: no cM position; filling it from bp needs --grid-file')
+                if where != where:
+                    raise ValueError(f'{path}, line {number}: neither a cM nor a bp position')
+                fill.append((len(ids), number))
+                x = float('nan')
+            ids.append(fields[0])
+            chrom.append(fields[1])
+            bp.append(where)
+            cm.append(x)
+            patterns.append(pattern)
+    chrom = np.asarray(chrom, dtype=str)
+    bp, cm = np.asarray(bp, dtype=np.float64), np.asarray(cm, dtype=np.float64)
+    if fill:
+        table = _grid_bp_cm(grid_file)
+        for row, number in fill:
+            if chrom[row] not in table:
+                raise ValueError(f'{path}, line {number}: no cM position, and {grid_file} has no rows for chromosome '
+                                 f'{chrom[row]} to fill it from')
+        rows = np.asarray([row for row, _ in fill])
+        for c in dict.fromkeys(chrom[rows].tolist()):
+            sel = rows[chrom[rows] == c]
+            cm[sel] = np.interp(bp[sel], *table[c])
+    mask = np.zeros(len(ids), dtype=np.uint32)
+    if ids:
+        bits = (np.frombuffer(''.join(patterns).encode(), dtype=np.uint8).reshape(len(ids), H) == ord('1'))
+        mask = (bits.astype(np.uint32) << np.arange(H, dtype=np.uint32)).sum(axis=1, dtype=np.uint32)
+    by_chrom = {c: np.flatnonzero(chrom == c) for c in chroms}
+    order = np.concatenate([by_chrom[c] for c in chroms]) if len(chroms) else np.zeros(0, dtype=np.int64)
+    foreign = len(ids) - len(order)
+    if foreign:
+        logger.warning(f'{path}: {foreign} SNPs on chromosomes without a transition table get nan')
+    return {'snp_id': np.asarray(ids, dtype=str), 'chrom': chrom, 'bp': bp, 'cM': cm, 'pattern': np.asarray(patterns, dtype=str),
+            'mask': mask, 'by_chrom': by_chrom, 'order': order.astype(np.int64), 'foreign': foreign}
+
+
+def snp_dosage_in_file_order(snps, imputed):
+    """impute()'s columns (handle order) as (..., M) in the SNP file's order, nan for the SNPs of foreign chromosomes."""
+    imputed = np.asarray(imputed, dtype=np.float64)
+    out = np.full(imputed.shape[:-1] + (len(snps['snp_id']),), np.nan)
+    out[..., snps['order']] = imputed
+    return out
+
+
+def write_snp_dosage(path, dosage, snps):
+    """`<outbase>.snp_dosage.npz`: `dosage` float64[M], the expected alternative allele counts in SNP file order, and
+    `snp_id`."""
+    logger.info(f'Saving SNP Dosages: {path}')
+    with open(path, 'wb') as out:
+        np.savez(out, dosage=np.asarray(dosage, dtype=np.float64), snp_id=snps['snp_id'])
+
+
+def write_snp_matrix(path, outbases, dosage, snps):
+    """`--snp-matrix`: an .npz with `dosage` (samples x M) of the samples that ran, `outbases`, and the SNP file's
+    columns `snp_id`, `chrom`, `bp`, `cM` (as used, filled ones included), `pattern`."""
+    logger.info(f'Saving SNP Matrix: {path}')
+    with open(path, 'wb') as out:
+        np.savez(out, dosage=np.asarray(dosage, dtype=np.float64), outbases=np.asarray(outbases, dtype=str),
+                 snp_id=snps['snp_id'], chrom=snps['chrom'], bp=snps['bp'], cM=snps['cM'], pattern=snps['pattern'])
+
+
+def _load_snps(ctx, snp_file, haplotypes):
+    """The SNPs of `--snp-file` onto the context (read once per context and file); every refusal of the file comes from
+    here, before a sample runs."""
+    if ctx.snps is None or ctx.snp_file != snp_file:
+        logger.info(f'Loading SNP file: {snp_file}')
+        ctx.snps = read_snp_file(snp_file, haplotypes, ctx.chroms, ctx.grid_file)
+        ctx.snp_file = snp_file
+        ctx._snps_on_handle = False
+        if getattr(ctx, 'gene_positions', None) is None:
+            ctx.gene_positions = read_gene_positions(ctx.gpos_file)
+    return ctx.snps
+
+
 def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gpos_file: str = None,
                 expr_threshold: float = 1.5, sigma: float = 0.12, outbase: str = None,
                 device: int = 0, stage_times: dict = None, context: ReconstructContext = None,
@@ -1149,7 +1361,7 @@ def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gp
                 sim_geno_seed: int = 0, diagnostics: bool = False, error_lod_threshold: float = 2.0,
                 gene_report: str = None, loglik: bool = False, alt_tprob_files=None, model_report: str = None,
                 match_panel: str = None, match_expected: str = None, match_chromosomes=None, match_labels: str = None,
-                match_report: str = None, match_matrix: str = None) -> None:
+                match_report: str = None, match_matrix: str = None, snp_file: str = None, snp_matrix: str = None) -> None:
     """`gbrs reconstruct`: diplotype posteriors and Viterbi calls along every chromosome from
     gene-level TPMs.  Same inputs, defaults and three output files as gbrs_utils.reconstruct
     (gbrs_utils.py:382-609); the emission model and the three recursions run on the device.
@@ -1174,8 +1386,12 @@ def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gp
     `match_panel` (extension; needs a grid file): the sample's grid dosages are compared on the device with
     those of every entry of the panel file and `<outbase>.match.tsv` lists the entries by distance; `match_expected`: the
     panel id the sample should be (logged with its status), `match_chromosomes`: the chromosomes that are compared.
-    `match_labels`, `match_report` and `match_matrix` belong to a cohort and are refused here."""
+    `match_labels`, `match_report` and `match_matrix` belong to a cohort and are refused here.
+    `snp_file` (extension): the expected number of alternative alleles of the sample at every SNP of the
+    file, from the founder dosages at the genes around it and the SNP's founder allele pattern, on the device;
+    `<outbase>.snp_dosage.npz` holds them in the file's order.  `snp_matrix` belongs to a cohort and is refused here."""
     check_sim_geno_args(sim_geno, sim_geno_seed)
+    check_snp_args(snp_file, snp_matrix, cohort=False)
     check_diagnostics_args(diagnostics, error_lod_threshold, gene_report, cohort=False)
     check_match_args(match_panel, match_labels, match_expected, match_chromosomes, match_report, match_matrix,
                      grid_file if context is None else context.grid_file, cohort=False)
@@ -1214,10 +1430,12 @@ def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gp
         ctx.alt_tables(num_haps)           # a file that does not fit is refused before the sample runs
     if match_panel is not None:            # so is a panel that does not fit the grid
         match_use, match_points = _load_panel(ctx, match_panel, haplotypes, match_chromosomes)
+    snps = _load_snps(ctx, snp_file, haplotypes) if snp_file is not None else None
     marks['load'] = clock() - t0
 
     posterior, path_names, calls = {}, {}, {}
     on_grid = drawn = diag = matched = None
+    imputed = np.zeros(0) if snps is not None else None
     names = [tprob_file] + list(ctx.alt_tprob_files) if loglik else None
     scores = np.zeros((len(names), 0)) if loglik else None       # (candidates, chromosomes) of this sample
     if chroms:
@@ -1247,7 +1465,8 @@ def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gp
                                 outbase=outbase, device=device, stage_times=marks, context=ctx.alt_context(selected - 1),
                                 grid_genoprobs=grid_genoprobs, sim_geno=sim_geno, sim_geno_seed=sim_geno_seed,
                                 diagnostics=diagnostics, error_lod_threshold=error_lod_threshold,
-                                match_panel=match_panel, match_expected=match_expected, match_chromosomes=match_chromosomes)
+                                match_panel=match_panel, match_expected=match_expected, match_chromosomes=match_chromosomes,
+                                snp_file=snp_file)
                 finally:
                     if context is None:
                         ctx.close()
@@ -1257,6 +1476,12 @@ def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gp
                 return
         logger.info('Getting forward-backward probability')
         posterior, path_names, calls = _collect(ctx, hmm, 0, diplotypes)
+        if snps is not None and len(snps['order']):
+            t1 = clock()
+            logger.info('Imputing SNP dosages')
+            imputed = hmm.impute(sample=0)
+            marks['snp'] = clock() - t1
+            t0 += marks['snp']
         if context is None and ctx.grid is None and sim_geno is None and not diagnostics:
             ctx.close()
         marks['hmm'] = clock() - t0 - scoring
@@ -1314,6 +1539,8 @@ def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gp
         distance, similarity, rank = matched
         write_match_table(f'{stem}.match.tsv', ctx.panel[0], distance, similarity, rank['order'])
         logger.info(f"Panel match: {rank['status']}, best {rank['best']} at {rank['best_distance']!r}")
+    if snps is not None:
+        write_snp_dosage(f'{stem}.snp_dosage.npz', snp_dosage_in_file_order(snps, imputed), snps)
     marks['save'] = clock() - t0
     logger.info('Done')
 
@@ -1341,7 +1568,8 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
                      diagnostics: bool = False, error_lod_threshold: float = 2.0, gene_report: str = None,
                      loglik: bool = False, alt_tprob_files=None, model_report: str = None,
                      match_panel: str = None, match_labels: str = None, match_chromosomes=None, match_report: str = None,
-                     match_matrix: str = None, match_expected: str = None) -> list:
+                     match_matrix: str = None, match_expected: str = None, snp_file: str = None,
+                     snp_matrix: str = None) -> list:
     """`gbrs reconstruct` for a cohort whose genes.tpm files exist (extension): one context, the tables on the device
     once, the samples through the HMM in launches of up to `batch_size`, and with `grid_file` one grid pass per launch.
     Every sample gets the files the single-sample call writes for its outbase.  All samples must carry the same
@@ -1362,8 +1590,12 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
     `outbase<TAB>panel id`, the entry each sample should be; `match_chromosomes`: the chromosomes that are compared;
     `match_report`: one line per sample that ran with its status, best and second entry and margin; `match_matrix`: an
     .npz with the distances, similarities and the device's sums of all samples that ran.  A sample that moved to another
-    table file is matched under that handle."""
+    table file is matched under that handle.
+    `snp_file`: one more device pass per launch imputes every sample's expected alternative allele counts
+    at the SNPs of the file; every sample gets `<outbase>.snp_dosage.npz`.  `snp_matrix`: an .npz with the rows of all
+    samples that ran and the SNP file's columns.  The SNPs go to a handle once, not per launch."""
     check_sim_geno_args(sim_geno, sim_geno_seed)
+    check_snp_args(snp_file, snp_matrix, cohort=True)
     check_diagnostics_args(diagnostics, error_lod_threshold, gene_report, cohort=True)
     check_match_args(match_panel, match_labels, match_expected, match_chromosomes, match_report, match_matrix,
                      grid_file if context is None else context.grid_file, cohort=True)
@@ -1409,8 +1641,11 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
     if match_panel is not None:
         labels = read_match_labels(match_labels) if match_labels is not None else {}
         match_use, match_points = _load_panel(ctx, match_panel, haplotypes, match_chromosomes)
+    snps = _load_snps(ctx, snp_file, haplotypes) if snp_file is not None else None
+    snp_rows = {}                          # sample -> its dosages in SNP file order
     marks['load'] = clock() - t0
-    for key in ('read', 'hmm', 'grid', 'save') + (('loglik',) if loglik else ()) + (('match',) if match_panel is not None else ()):
+    for key in ('read', 'hmm', 'grid', 'save') + (('loglik',) if loglik else ()) + \
+            (('match',) if match_panel is not None else ()) + (('snp',) if snps is not None else ()):
         marks[key] = 0.0
     names = [tprob_file] + list(ctx.alt_tprob_files) if loglik else None
     choices = {}                           # sample -> (selected candidate, margin, totals per candidate)
@@ -1432,6 +1667,8 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
                                scores, choices[k][0])
         if matched is not None:
             write_match_table(f'{outbases[k]}.match.tsv', ctx.panel[0], matched[2], matched[3], matched[4]['order'])
+        if k in snp_rows:
+            write_snp_dosage(f'{outbases[k]}.snp_dosage.npz', snp_rows[k], snps)
 
     report = None
 
@@ -1484,6 +1721,12 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
                               rank_matches(ctx.panel[0], distance[s], labels.get(outbases[k])))
             matches['panel_norm'] = panel_norm
             marks['match'] += clock() - t0
+        if snps is not None and stay:
+            t0 = clock()
+            got = snp_dosage_in_file_order(snps, hmm.impute() if len(snps['order']) else np.zeros((len(members), 0)))
+            for s in stay:
+                snp_rows[members[s]] = got[s]
+            marks['snp'] += clock() - t0
         drawn = None
         if sim_geno is not None and stay:
             t0 = clock()
@@ -1525,6 +1768,8 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
             if not members or not ctx.chroms:
                 nothing = None if sim_geno is None else ([], np.zeros((sim_geno, 0), dtype=np.int32), [])
                 for k in members:
+                    if snps is not None:
+                        snp_rows[k] = np.full(len(snps['snp_id']), np.nan)
                     if loglik:
                         choices[k] = (0, 0.0 if len(names) > 1 else np.inf, np.zeros(len(names)))
                     pending.append((k, writers.submit(save, k, ({}, {}, {}), None, nothing,
@@ -1556,6 +1801,10 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
                 write_match_matrix(match_matrix, [outbases[k] for k in ran], ctx.panel[0], ctx.chroms, match_points,
                                    stack(2, (0, M)), stack(3, (0, M)), stack(0, (0, nc, M)), stack(1, (0, nc)),
                                    matches.get('panel_norm', np.zeros((M, nc))))
+        if snp_matrix is not None:
+            ran = sorted(snp_rows)
+            write_snp_matrix(snp_matrix, [outbases[k] for k in ran],
+                             np.stack([snp_rows[k] for k in ran]) if ran else np.zeros((0, len(snps['snp_id']))), snps)
         marks['save'] += clock() - t0
     finally:
         writers.shutdown(wait=True)

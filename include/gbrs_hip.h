@@ -738,6 +738,43 @@ int gbrs_hmm_match(gbrs_hmm_t *hmm, int sample, double *cross, double *sample_no
  * gbrs_hmm_match call's own kernels, and the device memory the panel and the outputs hold; all nullable. */
 int gbrs_hmm_match_info(gbrs_hmm_t *hmm, int *n_panel, double *panel_norm, double *last_ms, uint64_t *device_bytes);
 
+/* SNP dosages imputed from the founder haplotypes (extension; `gbrs reconstruct --snp-file`).  A SNP has a chromosome,
+ * a position x in the units of the gene positions, and a founder allele pattern m: bit h set when founder h (haplotype
+ * order of the handle) carries the alternative allele.  The SNPs of one handle chromosome, in the caller's order, are
+ * a grid: their knots and knot_gene are gbrs_grid_knots(n_genes, gene_pos, n_snps_c, snp_pos_c, ...), the end knot the
+ * last SNP in that order + 1.0.  With D[i][h] the founder dosage of a sample at gene i (gbrs_genoprob_dosage's loop over
+ * the posterior row of gene i), a SNP gives
+ *   idx = clip(searchsorted(knots, x, 'left'), 1, n_knots - 1)    g_lo = knot_gene[idx-1], g_hi = knot_gene[idx]
+ *   a_lo = 0.0; for h ascending: if bit h of m: a_lo += D[g_lo][h]       a_hi likewise from D[g_hi]
+ *   slope = (a_hi - a_lo) / (x_hi - x_lo)      y = slope * (x - x_lo) + a_lo      out = 2.0 * y
+ * the expected number of alternative alleles, in [0, 2] up to rounding; no fused multiply-add.  Founders are reduced
+ * first and the interpolation comes second; gbrs_hmm_grid interpolates the S states first, so the two differ by
+ * reassociation.
+ *
+ * gbrs_hmm_set_snps: the arguments go per handle chromosome like gbrs_hmm_set_grid's; n_snps[c] = 0: the chromosome has
+ * none (its other entries are not read), all zeros drops the SNPs.  Positions, patterns and the int32 knot index of every
+ * SNP, found here by one kernel, stay on the device: 16 bytes per SNP.  A pattern with a bit at or above num_haps is
+ * GBRS_ERR_INVALID naming chromosome and index; a SNP outside the knots is refused with gbrs_grid_knots' text.  On
+ * failure the handle keeps the SNPs it had.  Independent of the handle's grid and panel: neither call disturbs the
+ * other. */
+int gbrs_hmm_set_snps(gbrs_hmm_t *hmm, const int32_t *n_pos, const double *const *gene_pos, const int32_t *n_snps,
+                      const double *const *snp_pos, const uint32_t *const *snp_mask);
+
+/* sample = -1: all n samples of the run, else that one (n = 1).  SNPs first .. first + count in handle order
+ * (chromosomes in handle order, the caller's order within); out is double[n][count], one device-to-host copy.  D is made
+ * by the first call after a run for a `sample` argument and reused by the calls that follow with the same argument, so
+ * a range may be walked in chunks.  count = 0 is accepted and does nothing.  GBRS_ERR_STATE before the first run,
+ * GBRS_ERR_INVALID without SNPs, for a range outside 0 .. M or a sample out of range; out is untouched on failure. */
+int gbrs_hmm_impute(gbrs_hmm_t *hmm, int sample, int64_t first, int64_t count, double *out);
+
+/* M of the handle's SNPs (0 without any), the device time of the last gbrs_hmm_impute call's kernels (0.0 until a pass
+ * has run on the handle), and the device memory the SNPs, D and the output chunk hold; all nullable. */
+int gbrs_hmm_impute_info(gbrs_hmm_t *hmm, int64_t *n_snps, double *last_ms, uint64_t *device_bytes);
+
+/* The parts of those times, in device milliseconds: the search kernel of the last gbrs_hmm_set_snps, and of the last
+ * gbrs_hmm_impute call the kernel that made D (0.0 when D was reused) and the imputation kernel; all nullable. */
+int gbrs_hmm_impute_times(gbrs_hmm_t *hmm, double *setup_ms, double *dosage_ms, double *kernel_ms);
+
 /* Diplotype paths drawn from the joint posterior of the last run (extension; forward-filter / backward-sample on the
  * run's filtered forward values, which the first call makes like gbrs_hmm_get(alpha)).  sample = -1: all n samples of
  * the run, else that one (n = 1).  Draw d of a sample, chromosome c, genes i = n_c - 1 .. 0:

@@ -34,6 +34,8 @@ EXPORTS = [
     "gbrs_hmm_set_snps", "gbrs_hmm_impute", "gbrs_hmm_impute_info", "gbrs_hmm_impute_times",
     "gbrs_hmm_loglik", "gbrs_hmm_loglik_tables", "gbrs_hmm_loglik_info", "gbrs_interpolate", "gbrs_genoprob_dosage",
     "gbrs_ri_transition_tables", "gbrs_alignment_spec",
+    "gbrs_scan_create", "gbrs_scan_destroy", "gbrs_scan_append", "gbrs_scan_append_hmm", "gbrs_scan_prepare", "gbrs_scan_run",
+    "gbrs_scan_info",
     "gbrs_compress_create", "gbrs_compress_get", "gbrs_compress_destroy",
     "gbrs_bam_open", "gbrs_bam_references", "gbrs_bam_set_reference_map", "gbrs_bam_convert", "gbrs_bam_get",
     "gbrs_bam_scan_records", "gbrs_bam_destroy",
@@ -97,6 +99,14 @@ class HmmInfo(C.Structure):
         ("last_run_ms", C.c_double),
         ("last_delta_blocks", C.c_int32), ("last_delta_longest_fixup", C.c_int32),
         ("last_delta_fallbacks", C.c_int32), ("last_delta_tie_fallbacks", C.c_int32),
+    ]
+
+
+class ScanInfo(C.Structure):
+    _fields_ = [
+        ("n", C.c_int64), ("M", C.c_int64), ("H", C.c_int32), ("c", C.c_int32),
+        ("last_prepare_ms", C.c_double), ("last_run_ms", C.c_double), ("last_product_ms", C.c_double),
+        ("device_bytes", C.c_uint64),
     ]
 
 
@@ -198,6 +208,13 @@ def load():
         "gbrs_genoprob_dosage": [i32, i64, vp, vp, i32],
         "gbrs_ri_transition_tables": [vp, vp, vp, i64, dbl, dbl, i32, vp],
         "gbrs_alignment_spec": [vp, vp, vp, i64, i32, dbl, i32, vp, vp, vp, vp],
+        "gbrs_scan_create": [i32, i32, vp, i32, pp],
+        "gbrs_scan_destroy": [vp],
+        "gbrs_scan_append": [vp, i32, vp],
+        "gbrs_scan_append_hmm": [vp, vp, i32],
+        "gbrs_scan_prepare": [vp, i32, vp],
+        "gbrs_scan_run": [vp, i64, vp, vp, vp, vp],
+        "gbrs_scan_info": [vp, C.POINTER(ScanInfo), vp],
         "gbrs_compress_create": [u64, u32, u32, pp, pp, vp, i32, pp, C.POINTER(u64), vp],
         "gbrs_compress_get": [vp, pp, pp, vp],
         "gbrs_compress_destroy": [vp],

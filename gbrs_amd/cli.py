@@ -130,6 +130,12 @@ def build_parser():
     r.add_argument('--snp-matrix', default=None, metavar='PATH',
                    help='with --snp-file and --sample-file: an .npz with the SNP dosages of all samples (samples x SNPs) '
                         'and the columns of the SNP file')
+    r.add_argument('--scan-pheno', type=_existing, default=None, metavar='FILE',
+                   help='(extension; needs --grid-file and --sample-file) genome scan: a tab separated table with the header '
+                        '`id<TAB>name...`, rows keyed by outbase, one column per phenotype.  Every phenotype is regressed on '
+                        'the founder dosages of the samples that ran at every grid point (Haley-Knott, on the device); writes '
+                        '<PREFIX>.scan.npz and <PREFIX>.scan.peaks.tsv')
+    _scan_options(r)
     r.add_argument('-t', '--tprob-file', required=True, type=_existing)
     r.add_argument('-x', '--avec-file', type=_existing, default=None)
     r.add_argument('-g', '--gpos-file', type=_existing, default=None)
@@ -138,6 +144,17 @@ def build_parser():
     r.add_argument('-o', '--outbase', default=None)
     r.add_argument('-v', '--verbose', action='count', default=0)
     r.add_argument('--device', type=int, default=0, help='HIP device ordinal (extension)')
+    sc = sub.add_parser('scan', help='(extension) genome scan of phenotypes on exported founder dosages')
+    sc.add_argument('--dosage-list', required=True, type=_existing, metavar='FILE',
+                    help='lines `id<TAB>dosage table`: the samples and their tables in `gbrs export` format on the grid file')
+    sc.add_argument('--grid-file', required=True, type=_existing)
+    sc.add_argument('--pheno', required=True, type=_existing, metavar='FILE',
+                    help='tab separated table with the header `id<TAB>name...`, rows keyed by the ids of --dosage-list')
+    sc.add_argument('--covar', dest='scan_covar', type=_existing, default=None, metavar='FILE',
+                    help='additive covariates: the same layout, numeric; the intercept is added')
+    _scan_options(sc, covar=False)
+    sc.add_argument('-v', '--verbose', action='count', default=0)
+    sc.add_argument('--device', type=int, default=0)
     it = sub.add_parser('interpolate', help='interpolate probability on a decently-spaced grid')
     it.add_argument('-i', '--genoprob-file', required=True, type=_existing)
     it.add_argument('-g', '--grid-file', type=_existing, default=None)
@@ -262,6 +279,19 @@ def _write_stage_times(stages, error):
         json.dump(stages, fh)
 
 
+def _scan_options(parser, covar=True):
+    if covar:
+        parser.add_argument('--scan-covar', type=_existing, default=None, metavar='FILE',
+                            help='with --scan-pheno: additive covariates, the same layout, numeric; the intercept is added')
+    parser.add_argument('--scan-rankz', action='store_true',
+                        help='rank-based inverse normal transform of every phenotype (average ranks on ties)')
+    parser.add_argument('--scan-out', default=None, metavar='PREFIX', help='prefix of the two scan files (default: gbrs)')
+    parser.add_argument('--scan-min-lod', type=float, default=None, metavar='X',
+                        help='only peaks of at least this LOD go to the peaks file (default: 0.0)')
+    parser.add_argument('--scan-lod-matrix', action='store_true',
+                        help='keep the phenotypes x grid points LOD matrix in the .npz however large it is')
+
+
 def main(argv=None) -> int:
     import time
     t_main = time.time()
@@ -293,6 +323,9 @@ def main(argv=None) -> int:
                              args.match_report, args.match_matrix, args.grid_file, cohort=args.sample_file is not None)
             from .hmm import check_snp_args
             check_snp_args(args.snp_file, args.snp_matrix, cohort=args.sample_file is not None)
+            from .scan import check_scan_args
+            check_scan_args(args.scan_pheno, args.scan_covar, args.scan_rankz, args.scan_out, args.scan_min_lod,
+                            args.scan_lod_matrix, args.grid_file, cohort=args.sample_file is not None)
         if args.command == 'quantify' and args.gpus is not None:
             # N child processes, one per rank; this process opens no device
             from .sharded import launch
@@ -388,6 +421,11 @@ def main(argv=None) -> int:
             strains = [s for x in args.haplotypes for s in x.split(',')]
             get_alignment_spec(sample_file=args.sample_file, haplotypes=strains, min_expr=args.min_expr,
                                device=args.device, stage_times=stages)
+        elif args.command == 'scan':
+            from .scan import scan_tables
+            scan_tables(dosage_list=args.dosage_list, grid_file=args.grid_file, pheno_file=args.pheno,
+                        covar_file=args.scan_covar, use_rankz=args.scan_rankz, out=args.scan_out, min_lod=args.scan_min_lod,
+                        lod_matrix=args.scan_lod_matrix, device=args.device)
         elif args.command == 'interpolate':
             from .postproc import interpolate
             interpolate(genoprob_file=args.genoprob_file, grid_file=args.grid_file, gpos_file=args.gpos_file,
@@ -409,7 +447,9 @@ def main(argv=None) -> int:
                              loglik=args.loglik, alt_tprob_files=args.alt_tprob_file, model_report=args.model_report,
                              match_panel=args.match_panel, match_labels=args.match_labels,
                              match_chromosomes=args.match_chromosomes, match_report=args.match_report,
-                             match_matrix=args.match_matrix, snp_file=args.snp_file, snp_matrix=args.snp_matrix)
+                             match_matrix=args.match_matrix, snp_file=args.snp_file, snp_matrix=args.snp_matrix,
+                             scan_pheno=args.scan_pheno, scan_covar=args.scan_covar, scan_rankz=args.scan_rankz,
+                             scan_out=args.scan_out, scan_min_lod=args.scan_min_lod, scan_lod_matrix=args.scan_lod_matrix)
         else:
             from .hmm import reconstruct
             reconstruct(expression_file=args.expression_file, tprob_file=args.tprob_file,

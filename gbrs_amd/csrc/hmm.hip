@@ -10,6 +10,7 @@
 #include "common.h"
 #include "hmm_route.h"
 #include "grid_knots.h"
+#include "scan_hmm.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -4384,3 +4385,24 @@ namespace gbrs {
 __global__ void warm_hmm_kernel() {}
 void warm_hmm(hipStream_t st) { hipLaunchKernelGGL(warm_hmm_kernel, dim3(1), dim3(64), 0, st); }
 }  // namespace gbrs
+
+// The genome scan's read-only view of the grid dosages (scan_hmm.h).
+int gbrs::hmm_grid_view(gbrs_hmm *h, int sample, HmmGridView *view, bool make_dosage) {
+    if (!h) return fail(GBRS_ERR_INVALID, "hmm handle is NULL");
+    if (!h->ran) return fail(GBRS_ERR_STATE, "run() has not been called");
+    if (!h->have_grid) return fail(GBRS_ERR_INVALID, "no grid on the handle: call gbrs_hmm_set_grid first");
+    if (sample < -1 || sample >= h->n_samples) return fail(GBRS_ERR_INVALID, "sample out of range");
+    GBRS_TRY(select_device(h->device));
+    std::vector<GridChrom> gc(h->n_chrom);
+    GBRS_HIP_CHECK(hipMemcpy(gc.data(), h->d_grid_chroms.p, gc.size() * sizeof(GridChrom), hipMemcpyDeviceToHost));
+    if (make_dosage && h->grid_tiles > 0 && !(h->grid_dosage_ready && h->grid_dosage_sample == sample))
+        GBRS_TRY(hmm_grid_launch(h, sample, true, false));
+    view->device = h->device;
+    view->H = h->H;
+    view->n = sample < 0 ? h->n_samples : 1;
+    view->grid_points = h->grid_points;
+    view->points.resize(h->n_chrom);
+    for (int c = 0; c < h->n_chrom; ++c) view->points[c] = gc[c].n_points;
+    view->dosage = make_dosage ? h->grid_dosage.p : nullptr;
+    return GBRS_OK;
+}

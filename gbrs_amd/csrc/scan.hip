@@ -1,0 +1,567 @@
+// Genome scan (gbrs_scan_*): Haley-Knott regression of phenotypes on the founder dosages of a cohort at
+// every grid point, with additive covariates.  gfx950 only.
+//
+// prepare: one workgroup per grid point turns the point's dosage columns into W_m = L^-1 X~' (scan_prepare_kernel), so
+// that the explained sum of squares of a phenotype at the point is |W_m y~|^2.  run: the phenotypes are projected and
+// transposed (scan_pheno_kernel), and one product kernel (scan_lod_kernel) multiplies W [M Hp][n_ld] with the phenotype
+// block [P][n_ld] on v_mfma_f64_16x16x4_f64, squares and sums the Hp rows of every grid point in its epilogue and stores
+// LODs only.  Both operands are row-major with the sample axis (K) contiguous and zero filled up to n_ld, a multiple of
+// the K chunk: the operand maps, the LDS stride and the prefetch are those of match_cross_kernel (hmm_match.inc), without
+// its K tail and its 8-byte staging.
+#include "common.h"
+#include "scan_hmm.h"
+
+#include <algorithm>
+#include <cmath>
+#include <limits>
+
+namespace gbrs {
+
+typedef double scan_d4 __attribute__((ext_vector_type(4)));
+
+constexpr int SC_ROWS = 64, SC_COLS = 64, SC_KC = 32, SC_LD = SC_KC + 2, SC_THREADS = 256;
+constexpr int SC_PER = SC_ROWS * SC_KC / SC_THREADS;
+constexpr int SC_MAX_C = 64;               // covariate columns, intercept included
+constexpr int64_t SC_PCHUNK = 512;         // phenotype columns on the device at a time
+constexpr double SC_PIVOT = 1e-10;         // the skip rule's threshold: d_j > SC_PIVOT * G_jj
+static_assert(SC_LD % 32 == 2 && SC_KC % 4 == 0, "the bank argument of match_cross_kernel");
+static_assert(SC_ROWS == 16 * (SC_THREADS / 64) && SC_COLS == 64 && SC_PCHUNK % SC_COLS == 0, "tile shape");
+
+// ---- prepare ----------------------------------------------------------------------------------------------------------------
+
+// One workgroup per grid point m; the point's Hp rows of W are its workspace.  Every sum over the samples is formed by
+// one wavefront, lane l adding the samples l, l + 64, ... in order and the 64 partial sums meeting in a butterfly: the
+// order depends on n alone.  The factorisation is one thread's, in the column order of the rule.
+//   1  w[j][s] = D[s][m][j] for the H - 1 kept founders, zeros in the padding rows and past sample n
+//   2  qtx[k][j] = sum_s qz[s][k] w[j][s], raw[j] = sum_s w[j][s]^2
+//   3  w[j][s] -= sum_k qz[s][k] qtx[k][j]                  (X~, transposed)
+//   4  G[j][i] = sum_s w[j][s] w[i][s], i <= j
+//   5  Cholesky with the skip rule -> L, keep[], rank[m].  The covariates are the columns before column 0: a column that
+//      the projection took to rounding (G_jj <= SC_PIVOT raw[j]) counts as G_jj = 0, by the rule's own threshold
+//   6  per sample, forward substitution down the kept columns: w[j][s] = (w[j][s] - sum_{kept i<j} L[j][i] w[i][s]) / L[j][j]
+template <int HP>
+__global__ void __launch_bounds__(SC_THREADS)
+scan_prepare_kernel(int n, int64_t M, int H, int c, int64_t n_ld, const double *__restrict__ D, const double *__restrict__ qz,
+                    double *__restrict__ W, int32_t *__restrict__ rank) {
+    __shared__ double qtx[SC_MAX_C * HP];
+    __shared__ double G[HP * HP], L[HP * HP], raw[HP];
+    __shared__ int keep[HP];
+    const int64_t m = blockIdx.x;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, Hx = H - 1;
+    double *w = W + m * HP * n_ld;
+    for (int idx = tid; idx < n * Hx; idx += SC_THREADS) {
+        const int s = idx / Hx, j = idx % Hx;
+        w[j * n_ld + s] = D[((int64_t)s * M + m) * H + j];
+    }
+    for (int64_t idx = tid; idx < HP * n_ld; idx += SC_THREADS)
+        if (idx / n_ld >= Hx || idx % n_ld >= n) w[idx] = 0.0;
+    __syncthreads();
+    for (int q = wave; q < (c + 1) * Hx; q += SC_THREADS / 64) {
+        const int k = q / Hx, j = q % Hx;
+        double acc = 0.0;
+        if (k < c)
+            for (int s = lane; s < n; s += 64) acc += qz[(int64_t)s * c + k] * w[j * n_ld + s];
+        else
+            for (int s = lane; s < n; s += 64) acc += w[j * n_ld + s] * w[j * n_ld + s];
+        acc = wave_sum_all(acc);
+        if (lane == 0) (k < c ? qtx[k * HP + j] : raw[j]) = acc;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < n * Hx; idx += SC_THREADS) {
+        const int j = idx / n, s = idx % n;
+        double p = 0.0;
+        for (int k = 0; k < c; ++k) p += qz[(int64_t)s * c + k] * qtx[k * HP + j];
+        w[j * n_ld + s] -= p;
+    }
+    __syncthreads();
+    for (int q = wave; q < Hx * (Hx + 1) / 2; q += SC_THREADS / 64) {
+        int j = 0;
+        while ((j + 1) * (j + 2) / 2 <= q) ++j;
+        const int i = q - j * (j + 1) / 2;
+        double acc = 0.0;
+        for (int s = lane; s < n; s += 64) acc += w[j * n_ld + s] * w[i * n_ld + s];
+        acc = wave_sum_all(acc);
+        if (lane == 0) G[j * HP + i] = acc;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int kept = 0;
+        for (int j = 0; j < Hx; ++j) {
+            const double gjj = G[j * HP + j];
+            double d = gjj;
+            for (int i = 0; i < j; ++i) {
+                double v = 0.0;
+                if (keep[i]) {
+                    v = G[j * HP + i];
+                    for (int k = 0; k < i; ++k)
+                        if (keep[k]) v -= L[j * HP + k] * L[i * HP + k];
+                    v /= L[i * HP + i];
+                    d -= v * v;
+                }
+                L[j * HP + i] = v;
+            }
+            const int ok = gjj > SC_PIVOT * raw[j] && d > SC_PIVOT * gjj;
+            keep[j] = ok;
+            kept += ok;
+            if (ok) L[j * HP + j] = sqrt(d);
+            else
+                for (int i = 0; i <= j; ++i) L[j * HP + i] = 0.0;
+        }
+        rank[m] = kept;
+    }
+    __syncthreads();
+    for (int s = tid; s < n; s += SC_THREADS) {
+        double x[HP];
+#pragma unroll
+        for (int j = 0; j < HP; ++j) {
+            double v = 0.0;
+            if (j < Hx && keep[j]) {
+                v = w[j * n_ld + s];
+#pragma unroll
+                for (int i = 0; i < j; ++i)
+                    if (keep[i]) v -= L[j * HP + i] * x[i];
+                v /= L[j * HP + j];
+            }
+            x[j] = v;
+            if (j < Hx) w[j * n_ld + s] = v;
+        }
+    }
+}
+
+// ---- phenotypes --------------------------------------------------------------------------------------------------------------
+
+// One wavefront per phenotype of the chunk: y~ = y - qz qz' y into row p of yt ([columns][n_ld], zeros past sample n) and
+// rss0[p] = |y~|^2, the sums in the order of scan_prepare_kernel's.  y is [n][ld_y], the chunk's columns of the upload.
+__global__ void __launch_bounds__(64)
+scan_pheno_kernel(int n, int c, int64_t n_ld, int64_t ld_y, const double *__restrict__ y, const double *__restrict__ qz,
+                  double *__restrict__ yt, double *__restrict__ rss0) {
+    __shared__ double qty[SC_MAX_C];
+    const int64_t p = blockIdx.x;
+    const int lane = threadIdx.x;
+    for (int k = 0; k < c; ++k) {
+        double acc = 0.0;
+        for (int s = lane; s < n; s += 64) acc += qz[(int64_t)s * c + k] * y[(int64_t)s * ld_y + p];
+        acc = wave_sum_all(acc);
+        if (lane == 0) qty[k] = acc;
+    }
+    __syncthreads();
+    double ss = 0.0;
+    for (int64_t s = lane; s < n_ld; s += 64) {
+        double v = 0.0;
+        if (s < n) {
+            double proj = 0.0;
+            for (int k = 0; k < c; ++k) proj += qz[s * c + k] * qty[k];
+            v = y[s * ld_y + p] - proj;
+        }
+        yt[p * n_ld + s] = v;
+        ss += v * v;
+    }
+    ss = wave_sum_all(ss);
+    if (lane == 0) rss0[p] = ss;
+}
+
+// ---- the product -------------------------------------------------------------------------------------------------------------
+
+// One 64 x SC_KC operand block on its way to LDS: sixteen lanes across the 256 contiguous bytes of a row, one aligned
+// 16-byte load and one 16-byte LDS store per pair of columns.  Rows past the last one shadow it.
+__device__ __forceinline__ void scan_fetch(double (&v)[SC_PER], const double *__restrict__ src, int64_t ld, int64_t first,
+                                           int64_t n_rows) {
+    const int t = threadIdx.x;
+#pragma unroll
+    for (int i = 0; i < SC_PER / 2; ++i) {
+        const int idx = t + SC_THREADS * i, r = idx / (SC_KC / 2), k = 2 * (idx % (SC_KC / 2));
+        const double2 x = *reinterpret_cast<const double2 *>(src + std::min(first + r, n_rows - 1) * ld + k);
+        v[2 * i] = x.x;
+        v[2 * i + 1] = x.y;
+    }
+}
+
+__device__ __forceinline__ void scan_put(double *dst, const double (&v)[SC_PER]) {
+    const int t = threadIdx.x;
+#pragma unroll
+    for (int i = 0; i < SC_PER / 2; ++i) {
+        const int idx = t + SC_THREADS * i, r = idx / (SC_KC / 2), k = 2 * (idx % (SC_KC / 2));
+        *reinterpret_cast<double2 *>(dst + r * SC_LD + k) = double2{v[2 * i], v[2 * i + 1]};
+    }
+}
+
+__device__ __forceinline__ double scan_lod(double rss0, double ess, double half_n) {
+    if (rss0 == 0.0) return 0.0;
+    const double rss1 = rss0 - ess;
+    if (rss1 <= 0.0) return __builtin_huge_val();
+    return half_n * log10(rss0 / rss1);
+}
+
+// blockIdx.x: block of 64 rows of W = 64 / HP grid points (fastest, so the row blocks that share a phenotype block run side
+// by side), blockIdx.y: block of 64 phenotypes of the chunk.  Wavefront w multiplies rows 16 w .. 16 w + 15 with the 64
+// columns: four 16x16 accumulators, register r of lane (g = lane >> 4, i = lane & 15) is row g + 4 r, column 16 t + i.
+// K = n_ld is one chain of MFMAs per accumulator, chunk after chunk, not split and without atomics; the loads of chunk
+// k + 1 are in flight during the MFMAs of chunk k.
+// Epilogue: a grid point's HP rows lie within one wavefront's 16.  At HP = 8 the registers 0, 1 of a lane are rows of the
+// wavefront's first point and 2, 3 of its second; at HP = 16 all four are the one point's.  Squares are added in the lane
+// in register order, then across the four lane groups (xor 16, xor 32: a fixed tree), so ess depends on nothing but the
+// rows and the column.  ess goes to LDS as [column][point]; every thread then turns two of the 64 x 64 / HP values into
+// LODs and stores them, consecutive threads consecutive grid points of one phenotype's row.  Rows past M HP and columns
+// past P shadow the last valid one and are not stored.  lod is the chunk's [P][M].
+template <int HP>
+__global__ void __launch_bounds__(SC_THREADS)
+scan_lod_kernel(int64_t M, int64_t P, int64_t n_ld, double half_n, const double *__restrict__ W, const double *__restrict__ yt,
+                const double *__restrict__ rss0, double *__restrict__ lod) {
+    constexpr int PTS = SC_ROWS / HP, PPW = 16 / HP;      // grid points per workgroup and per wavefront
+    __shared__ __attribute__((aligned(16))) double lds_a[SC_ROWS * SC_LD];
+    __shared__ __attribute__((aligned(16))) double lds_b[SC_COLS * SC_LD];
+    const int64_t row0 = (int64_t)blockIdx.x * SC_ROWS, col0 = (int64_t)blockIdx.y * SC_COLS, rows = M * HP;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, i = lane & 15, g = lane >> 4;
+    scan_d4 acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[t] = scan_d4{0.0, 0.0, 0.0, 0.0};
+    const double *ra = lds_a + (wave * 16 + i) * SC_LD + g, *rb = lds_b + i * SC_LD + g;
+    auto multiply = [&]() {
+#pragma unroll
+        for (int kk = 0; kk < SC_KC; kk += 4) {
+            const double av = ra[kk];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, rb[t * 16 * SC_LD + kk], acc[t], 0, 0, 0);
+        }
+    };
+    const int64_t chunks = n_ld / SC_KC;       // >= 1
+    double va[SC_PER], vb[SC_PER];
+    scan_fetch(va, W, n_ld, row0, rows);
+    scan_fetch(vb, yt, n_ld, col0, P);
+    for (int64_t k = 1; k < chunks; ++k) {
+        scan_put(lds_a, va);
+        scan_put(lds_b, vb);
+        __syncthreads();
+        scan_fetch(va, W + k * SC_KC, n_ld, row0, rows);
+        scan_fetch(vb, yt + k * SC_KC, n_ld, col0, P);
+        multiply();
+        __syncthreads();
+    }
+    scan_put(lds_a, va);
+    scan_put(lds_b, vb);
+    __syncthreads();
+    multiply();
+    __syncthreads();
+    double *ess = lds_a;                       // [64 columns][PTS]
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        double e[PPW];
+        if constexpr (HP == 8) {
+            e[0] = acc[t][0] * acc[t][0] + acc[t][1] * acc[t][1];
+            e[1] = acc[t][2] * acc[t][2] + acc[t][3] * acc[t][3];
+        } else {
+            e[0] = ((acc[t][0] * acc[t][0] + acc[t][1] * acc[t][1]) + acc[t][2] * acc[t][2]) + acc[t][3] * acc[t][3];
+        }
+#pragma unroll
+        for (int q = 0; q < PPW; ++q) {
+            e[q] += __shfl_xor(e[q], 16, WAVE);
+            e[q] += __shfl_xor(e[q], 32, WAVE);
+            if (g == 0) ess[(t * 16 + i) * PTS + wave * PPW + q] = e[q];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < SC_COLS * PTS / SC_THREADS; ++u) {
+        const int idx = threadIdx.x + SC_THREADS * u, col = idx / PTS, pt = idx % PTS;
+        const int64_t m = (int64_t)blockIdx.x * PTS + pt, p = col0 + col;
+        if (m < M && p < P) lod[p * M + m] = scan_lod(rss0[p], ess[idx], half_n);
+    }
+}
+
+// ---- peaks -------------------------------------------------------------------------------------------------------------------
+
+// One wavefront per (chromosome, phenotype of the chunk): lane l looks at the chromosome's points l, l + 64, ... in order
+// and keeps the first of its largest; the 64 candidates meet in a butterfly that prefers the larger value and, among
+// equal ones, the lower index.  No atomics.  A chromosome without points gives NaN and -1.
+__global__ void __launch_bounds__(64)
+scan_peak_kernel(int64_t M, int n_chrom, const int64_t *__restrict__ point_off, const double *__restrict__ lod,
+                 double *__restrict__ peak_lod, int64_t *__restrict__ peak_index) {
+    const int c = blockIdx.x;
+    const int64_t p = blockIdx.y, lo = point_off[c], hi = point_off[c + 1];
+    double best = -__builtin_huge_val();
+    int64_t at = -1;
+    for (int64_t m = lo + threadIdx.x; m < hi; m += 64) {
+        const double v = lod[p * M + m];
+        if (at < 0 || v > best) {
+            best = v;
+            at = m;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double ov = __shfl_xor(best, off, WAVE);
+        const int64_t oa = __shfl_xor((long long)at, off, WAVE);
+        if (oa >= 0 && (at < 0 || ov > best || (ov == best && oa < at))) {
+            best = ov;
+            at = oa;
+        }
+    }
+    if (threadIdx.x == 0) {
+        peak_lod[p * n_chrom + c] = at < 0 ? __builtin_nan("") : best;
+        peak_index[p * n_chrom + c] = at;
+    }
+}
+
+}  // namespace gbrs
+
+using namespace gbrs;
+
+struct gbrs_scan {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    int n_chrom = 0, H = 0, Hp = 0;
+    int64_t M = 0;
+    std::vector<int32_t> points;              // per chromosome
+    std::vector<int64_t> point_off;           // n_chrom + 1
+    DevBuf<int64_t> d_point_off;
+    // the cohort: [capacity][M][H], the first n rows in use
+    int64_t n = 0, capacity = 0;
+    DevBuf<double> dosage;
+    // what gbrs_scan_prepare made
+    int c = 0;                                // 0: not prepared
+    int64_t n_ld = 0;
+    DevBuf<double> qz, W;
+    DevBuf<int32_t> d_rank;
+    std::vector<int32_t> rank;
+    // one chunk of gbrs_scan_run
+    DevBuf<double> y, yt, rss0, lod, peak_lod;
+    DevBuf<int64_t> peak_index;
+    double t_prepare = 0, t_run = 0, t_product = 0;
+};
+
+namespace {
+
+// Room for `more` samples after the n in use; the samples in use move with the buffer.
+int scan_reserve(gbrs_scan *s, int64_t more) {
+    if (s->n + more <= s->capacity) return GBRS_OK;
+    const int64_t want = std::max(s->n + more, 2 * s->capacity);
+    const size_t row = (size_t)s->M * s->H;
+    DevBuf<double> grown;
+    GBRS_TRY(grown.alloc((size_t)want * row));
+    if (s->n > 0) {        // on the handle's stream and waited for: a device-to-device hipMemcpy need not be done when it returns
+        GBRS_HIP_CHECK(hipMemcpyAsync(grown.p, s->dosage.p, (size_t)s->n * row * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
+        GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
+    }
+    s->dosage.swap(grown);
+    s->capacity = want;
+    return GBRS_OK;
+}
+
+void scan_unprepare(gbrs_scan *s) {
+    s->c = 0;
+    s->rank.clear();
+}
+
+}  // namespace
+
+extern "C" {
+
+int gbrs_scan_create(int device, int n_chrom, const int32_t *points_per_chrom, int num_haps, gbrs_scan_t **out) {
+    if (!out) return fail(GBRS_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (num_haps < 2) return fail(GBRS_ERR_INVALID, "a scan needs at least 2 founders, got %d: the last one is dropped from the design", num_haps);
+    if (num_haps > 17) return fail(GBRS_ERR_INVALID, "a scan takes at most 17 founders, got %d", num_haps);
+    if (n_chrom < 1 || !points_per_chrom) return fail(GBRS_ERR_INVALID, "bad argument");
+    int64_t M = 0;
+    for (int c = 0; c < n_chrom; ++c) {
+        if (points_per_chrom[c] < 0) return fail(GBRS_ERR_INVALID, "chromosome %d has a negative number of grid points", c);
+        M += points_per_chrom[c];
+    }
+    if (M == 0) return fail(GBRS_ERR_INVALID, "the grid has no points");
+    if (M > std::numeric_limits<int32_t>::max()) return fail(GBRS_ERR_INVALID, "too many grid points");     // one workgroup per point
+    GBRS_TRY(select_device(device));
+    gbrs_scan *s = new gbrs_scan;
+    s->device = device;
+    s->n_chrom = n_chrom;
+    s->H = num_haps;
+    s->Hp = num_haps <= 9 ? 8 : 16;
+    s->M = M;
+    s->points.assign(points_per_chrom, points_per_chrom + n_chrom);
+    s->point_off.assign(n_chrom + 1, 0);
+    for (int c = 0; c < n_chrom; ++c) s->point_off[c + 1] = s->point_off[c] + points_per_chrom[c];
+    auto build = [&]() -> int {
+        GBRS_HIP_CHECK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+        for (auto &e : s->ev) GBRS_HIP_CHECK(hipEventCreate(&e));
+        GBRS_TRY(s->d_point_off.alloc(s->point_off.size()));
+        GBRS_HIP_CHECK(hipMemcpy(s->d_point_off.p, s->point_off.data(), s->d_point_off.bytes(), hipMemcpyHostToDevice));
+        return GBRS_OK;
+    };
+    const int status = build();
+    if (status != GBRS_OK) {
+        gbrs_scan_destroy(s);
+        return status;
+    }
+    *out = s;
+    return GBRS_OK;
+}
+
+int gbrs_scan_destroy(gbrs_scan_t *s) {
+    if (!s) return GBRS_OK;
+    (void)hipSetDevice(s->device);
+    if (s->stream) (void)hipStreamSynchronize(s->stream);
+    for (auto &e : s->ev)
+        if (e) (void)hipEventDestroy(e);
+    if (s->stream) (void)hipStreamDestroy(s->stream);
+    delete s;
+    return GBRS_OK;
+}
+
+int gbrs_scan_append(gbrs_scan_t *s, int n, const double *dosage) {
+    RoctxRange roctx_range("gbrs_scan_append");
+    if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (n < 0 || (n > 0 && !dosage)) return fail(GBRS_ERR_INVALID, "bad argument");
+    if (n == 0) return GBRS_OK;
+    if (s->n + n > std::numeric_limits<int32_t>::max() / 16) return fail(GBRS_ERR_INVALID, "too many samples");
+    const size_t row = (size_t)s->M * s->H;
+    for (size_t k = 0; k < (size_t)n * row; ++k)
+        if (!std::isfinite(dosage[k]))
+            return fail(GBRS_ERR_INVALID, "dosage of sample %lld holds a value that is not finite (grid point %lld, founder %d)",
+                        (long long)(s->n + (int64_t)(k / row)), (long long)(k % row / s->H), (int)(k % s->H));
+    GBRS_TRY(select_device(s->device));
+    GBRS_TRY(scan_reserve(s, n));
+    GBRS_HIP_CHECK(hipMemcpy(s->dosage.p + (size_t)s->n * row, dosage, (size_t)n * row * sizeof(double), hipMemcpyHostToDevice));
+    s->n += n;
+    scan_unprepare(s);
+    return GBRS_OK;
+}
+
+int gbrs_scan_append_hmm(gbrs_scan_t *s, gbrs_hmm_t *hmm, int sample) {
+    RoctxRange roctx_range("gbrs_scan_append_hmm");
+    if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    HmmGridView view;
+    GBRS_TRY(hmm_grid_view(hmm, sample, &view, false));      // what the handle holds, checked before anything runs on it
+    if (view.device != s->device) return fail(GBRS_ERR_INVALID, "the HMM handle is on device %d, the scan on device %d", view.device, s->device);
+    if (view.H != s->H) return fail(GBRS_ERR_INVALID, "the HMM handle has %d founders, the scan %d", view.H, s->H);
+    if ((int)view.points.size() != s->n_chrom)
+        return fail(GBRS_ERR_INVALID, "the HMM handle has %d chromosomes, the scan %d", (int)view.points.size(), s->n_chrom);
+    for (int c = 0; c < s->n_chrom; ++c)
+        if (view.points[c] != s->points[c])
+            return fail(GBRS_ERR_INVALID, "grid mismatch: chromosome %d has %d grid points on the HMM handle, %d on the scan", c,
+                        view.points[c], s->points[c]);
+    if (s->n + view.n > std::numeric_limits<int32_t>::max() / 16) return fail(GBRS_ERR_INVALID, "too many samples");
+    GBRS_TRY(hmm_grid_view(hmm, sample, &view, true));
+    GBRS_TRY(scan_reserve(s, view.n));
+    const size_t row = (size_t)s->M * s->H;
+    GBRS_HIP_CHECK(hipMemcpyAsync(s->dosage.p + (size_t)s->n * row, view.dosage, (size_t)view.n * row * sizeof(double),
+                                  hipMemcpyDeviceToDevice, s->stream));
+    GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
+    s->n += view.n;
+    scan_unprepare(s);
+    return GBRS_OK;
+}
+
+int gbrs_scan_prepare(gbrs_scan_t *s, int c, const double *qz) {
+    RoctxRange roctx_range("gbrs_scan_prepare");
+    if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (c < 1 || c > SC_MAX_C) return fail(GBRS_ERR_INVALID, "covariate columns must be 1..%d (the intercept included), got %d", SC_MAX_C, c);
+    if (!qz) return fail(GBRS_ERR_INVALID, "qz is NULL");
+    if (s->n <= (int64_t)c + s->H - 1)
+        return fail(GBRS_ERR_INVALID, "%lld samples are too few for %d covariate columns and %d founders: need more than %d",
+                    (long long)s->n, c, s->H, c + s->H - 1);
+    const int n = (int)s->n;
+    for (int64_t k = 0; k < (int64_t)n * c; ++k)
+        if (!std::isfinite(qz[k]))
+            return fail(GBRS_ERR_INVALID, "covariate basis holds a value that is not finite (sample %lld, column %d)", (long long)(k / c),
+                        (int)(k % c));
+    GBRS_TRY(select_device(s->device));
+    scan_unprepare(s);                  // the arguments are good: from here on W is being overwritten
+    const int64_t n_ld = ((int64_t)n + SC_KC - 1) / SC_KC * SC_KC;
+    const size_t n_w = (size_t)s->M * s->Hp * n_ld;
+    if (s->qz.n != (size_t)n * c) GBRS_TRY(s->qz.alloc((size_t)n * c));
+    if (s->W.n != n_w) GBRS_TRY(s->W.alloc(n_w));
+    if (s->d_rank.n != (size_t)s->M) GBRS_TRY(s->d_rank.alloc((size_t)s->M));
+    GBRS_HIP_CHECK(hipMemcpy(s->qz.p, qz, s->qz.bytes(), hipMemcpyHostToDevice));
+    GBRS_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)s->M), dim3(SC_THREADS), 0, s->stream, n, s->M, s->H, c, n_ld, s->dosage.p, s->qz.p,
+                           s->W.p, s->d_rank.p);
+    };
+    if (s->Hp == 8) launch(scan_prepare_kernel<8>);
+    else launch(scan_prepare_kernel<16>);
+    GBRS_HIP_CHECK(hipEventRecord(s->ev[1], s->stream));
+    GBRS_HIP_CHECK(hipGetLastError());
+    GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) s->t_prepare = ms;
+    std::vector<int32_t> rank((size_t)s->M);
+    GBRS_HIP_CHECK(hipMemcpy(rank.data(), s->d_rank.p, s->d_rank.bytes(), hipMemcpyDeviceToHost));
+    s->rank.swap(rank);
+    s->n_ld = n_ld;
+    s->c = c;
+    return GBRS_OK;
+}
+
+int gbrs_scan_run(gbrs_scan_t *s, int64_t P, const double *pheno, double *lod, double *peak_lod, int64_t *peak_index) {
+    RoctxRange roctx_range("gbrs_scan_run");
+    if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (s->c == 0) return fail(GBRS_ERR_INVALID, "no covariates on the handle: call gbrs_scan_prepare first");
+    if (P < 1 || !pheno) return fail(GBRS_ERR_INVALID, "bad argument");
+    const int n = (int)s->n;
+    for (int64_t k = 0; k < (int64_t)n * P; ++k)
+        if (!std::isfinite(pheno[k]))
+            return fail(GBRS_ERR_INVALID, "phenotype %lld holds a value that is not finite (sample %lld)", (long long)(k % P),
+                        (long long)(k / P));
+    GBRS_TRY(select_device(s->device));
+    const int64_t pc_max = std::min(P, SC_PCHUNK), M = s->M, n_ld = s->n_ld;
+    if (s->y.n != (size_t)n * pc_max) GBRS_TRY(s->y.alloc((size_t)n * pc_max));
+    if (s->yt.n != (size_t)pc_max * n_ld) GBRS_TRY(s->yt.alloc((size_t)pc_max * n_ld));
+    if (s->rss0.n != (size_t)pc_max) GBRS_TRY(s->rss0.alloc((size_t)pc_max));
+    if (s->lod.n != (size_t)pc_max * M) GBRS_TRY(s->lod.alloc((size_t)pc_max * M));
+    if (s->peak_lod.n != (size_t)pc_max * s->n_chrom) GBRS_TRY(s->peak_lod.alloc((size_t)pc_max * s->n_chrom));
+    if (s->peak_index.n != (size_t)pc_max * s->n_chrom) GBRS_TRY(s->peak_index.alloc((size_t)pc_max * s->n_chrom));
+    const unsigned row_blocks = (unsigned)((M * s->Hp + SC_ROWS - 1) / SC_ROWS);
+    double t_product = 0.0;
+    GBRS_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
+    for (int64_t p0 = 0; p0 < P; p0 += SC_PCHUNK) {
+        const int64_t pc = std::min(SC_PCHUNK, P - p0);
+        GBRS_HIP_CHECK(hipMemcpy2DAsync(s->y.p, (size_t)pc * sizeof(double), pheno + p0, (size_t)P * sizeof(double),
+                                        (size_t)pc * sizeof(double), (size_t)n, hipMemcpyHostToDevice, s->stream));
+        hipLaunchKernelGGL(scan_pheno_kernel, dim3((unsigned)pc), dim3(64), 0, s->stream, n, s->c, n_ld, pc, s->y.p, s->qz.p, s->yt.p,
+                           s->rss0.p);
+        GBRS_HIP_CHECK(hipEventRecord(s->ev[2], s->stream));
+        const dim3 grid(row_blocks, (unsigned)((pc + SC_COLS - 1) / SC_COLS));
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, dim3(SC_THREADS), 0, s->stream, M, pc, n_ld, 0.5 * n, s->W.p, s->yt.p, s->rss0.p, s->lod.p);
+        };
+        if (s->Hp == 8) launch(scan_lod_kernel<8>);
+        else launch(scan_lod_kernel<16>);
+        GBRS_HIP_CHECK(hipEventRecord(s->ev[3], s->stream));
+        hipLaunchKernelGGL(scan_peak_kernel, dim3((unsigned)s->n_chrom, (unsigned)pc), dim3(64), 0, s->stream, M, s->n_chrom,
+                           s->d_point_off.p, s->lod.p, s->peak_lod.p, s->peak_index.p);
+        GBRS_HIP_CHECK(hipGetLastError());
+        GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, s->ev[2], s->ev[3]) == hipSuccess) t_product += ms;
+        if (lod) GBRS_HIP_CHECK(hipMemcpy(lod + p0 * M, s->lod.p, (size_t)pc * M * sizeof(double), hipMemcpyDeviceToHost));
+        if (peak_lod)
+            GBRS_HIP_CHECK(hipMemcpy(peak_lod + p0 * s->n_chrom, s->peak_lod.p, (size_t)pc * s->n_chrom * sizeof(double), hipMemcpyDeviceToHost));
+        if (peak_index)
+            GBRS_HIP_CHECK(hipMemcpy(peak_index + p0 * s->n_chrom, s->peak_index.p, (size_t)pc * s->n_chrom * sizeof(int64_t), hipMemcpyDeviceToHost));
+    }
+    GBRS_HIP_CHECK(hipEventRecord(s->ev[1], s->stream));
+    GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) s->t_run = ms;
+    s->t_product = t_product;
+    return GBRS_OK;
+}
+
+int gbrs_scan_info(gbrs_scan_t *s, gbrs_scan_info_t *info, int32_t *rank) {
+    if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (info) {
+        info->n = s->n;
+        info->M = s->M;
+        info->H = s->H;
+        info->c = s->c;
+        info->last_prepare_ms = s->t_prepare;
+        info->last_run_ms = s->t_run;
+        info->last_product_ms = s->t_product;
+        info->device_bytes = s->d_point_off.bytes() + s->dosage.bytes() + s->qz.bytes() + s->W.bytes() + s->d_rank.bytes() +
+                             s->y.bytes() + s->yt.bytes() + s->rss0.bytes() + s->lod.bytes() + s->peak_lod.bytes() + s->peak_index.bytes();
+    }
+    if (rank && s->c > 0) std::memcpy(rank, s->rank.data(), s->rank.size() * sizeof(int32_t));
+    return GBRS_OK;
+}
+
+}  // extern "C"

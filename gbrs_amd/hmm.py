@@ -1569,7 +1569,8 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
                      loglik: bool = False, alt_tprob_files=None, model_report: str = None,
                      match_panel: str = None, match_labels: str = None, match_chromosomes=None, match_report: str = None,
                      match_matrix: str = None, match_expected: str = None, snp_file: str = None,
-                     snp_matrix: str = None) -> list:
+                     snp_matrix: str = None, scan_pheno: str = None, scan_covar: str = None, scan_rankz: bool = False,
+                     scan_out: str = None, scan_min_lod: float = None, scan_lod_matrix: bool = False) -> list:
     """`gbrs reconstruct` for a cohort whose genes.tpm files exist (extension): one context, the tables on the device
     once, the samples through the HMM in launches of up to `batch_size`, and with `grid_file` one grid pass per launch.
     Every sample gets the files the single-sample call writes for its outbase.  All samples must carry the same
@@ -1593,7 +1594,14 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
     table file is matched under that handle.
     `snp_file`: one more device pass per launch imputes every sample's expected alternative allele counts
     at the SNPs of the file; every sample gets `<outbase>.snp_dosage.npz`.  `snp_matrix`: an .npz with the rows of all
-    samples that ran and the SNP file's columns.  The SNPs go to a handle once, not per launch."""
+    samples that ran and the SNP file's columns.  The SNPs go to a handle once, not per launch.
+    `scan_pheno` (needs a grid file): a table of phenotypes keyed by outbase.  The grid dosages of every
+    sample that ran and has a phenotype row (and, with `scan_covar`, a covariate row) are collected on the device in the
+    order of `expression_files`; after the last launch the phenotypes are regressed on them at every grid point and
+    `<scan_out>.scan.npz` and `<scan_out>.scan.peaks.tsv` are written (gbrs_amd/scan.py)."""
+    from . import scan as scan_mod
+    scan_mod.check_scan_args(scan_pheno, scan_covar, scan_rankz, scan_out, scan_min_lod, scan_lod_matrix,
+                             grid_file if context is None else context.grid_file, cohort=True)
     check_sim_geno_args(sim_geno, sim_geno_seed)
     check_snp_args(snp_file, snp_matrix, cohort=True)
     check_diagnostics_args(diagnostics, error_lod_threshold, gene_report, cohort=True)
@@ -1643,9 +1651,17 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
         match_use, match_points = _load_panel(ctx, match_panel, haplotypes, match_chromosomes)
     snps = _load_snps(ctx, snp_file, haplotypes) if snp_file is not None else None
     snp_rows = {}                          # sample -> its dosages in SNP file order
+    scan = scan_ids = None                 # the cohort's GenomeScan (made with the first launch) and its samples' outbases
+    if scan_pheno is not None:
+        scan_tables = (scan_mod.read_scan_pheno(scan_pheno),
+                       scan_mod.read_scan_covar(scan_covar) if scan_covar is not None else None)
+        scan_ids, scan_held = [], {}       # scan_held: sample -> its host dosage rows, until its batch is appended
+        scan_unsaved = set()               # samples whose files could not be written: reported once, left out of the scan
+        scan_keep = set(scan_mod.scan_design(outbases, *scan_tables)[0])
     marks['load'] = clock() - t0
     for key in ('read', 'hmm', 'grid', 'save') + (('loglik',) if loglik else ()) + \
-            (('match',) if match_panel is not None else ()) + (('snp',) if snps is not None else ()):
+            (('match',) if match_panel is not None else ()) + (('snp',) if snps is not None else ()) + \
+            (('scan',) if scan_pheno is not None else ()):
         marks[key] = 0.0
     names = [tprob_file] + list(ctx.alt_tprob_files) if loglik else None
     choices = {}                           # sample -> (selected candidate, margin, totals per candidate)
@@ -1710,6 +1726,10 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
             t0 = clock()
             on_grid = hmm.grid(want=('dosage', 'gamma_grid') if grid_genoprobs else ('dosage',))
             marks['grid'] += clock() - t0
+        if scan_pheno is not None and on_grid is not None:
+            for s in stay:
+                if members[s] in scan_keep:
+                    scan_held[members[s]] = on_grid['dosage'][s]
         if match_panel is not None and stay:
             t0 = clock()
             got = hmm.match()
@@ -1781,8 +1801,37 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
             # is the single-sample command's launch, so its files do not depend on who else moved or on the batch size.
             for s, a in sorted((s, a) for a in moved for s in moved[a]):
                 launch(ctx.alt_context(a), [members[s]], [rows[s]], scores_of)
+            if scan_pheno is not None and scan_held:
+                # A sample that failed is left out, and a sample has not succeeded before its files are written: the
+                # batch's writes are waited for here (with the scan they do not overlap the next launch).  Then the
+                # batch's samples in file order: device to device when the whole launch goes in (no sample moved to
+                # another handle, failed or lacks a row), else the rows the grid pass already brought to the host - the
+                # same bits either way.
+                t0 = clock()
+                for k, job in pending:
+                    if k in scan_held:
+                        try:
+                            job.result()
+                        except Exception as e:   # noqa: BLE001
+                            failed(k, e)
+                            scan_unsaved.add(k)
+                            del scan_held[k]
+                marks['save'] += clock() - t0
+            if scan_pheno is not None and scan_held:
+                t0 = clock()
+                if scan is None:
+                    scan = scan_mod.GenomeScan(num_haps, ctx.hmm.grid_points, device=ctx.device)
+                if not moved and sorted(scan_held) == members:
+                    scan.append_from(ctx.hmm)
+                else:
+                    scan.append(np.stack([scan_held[k] for k in sorted(scan_held)]))
+                scan_ids += [outbases[k] for k in sorted(scan_held)]
+                scan_held.clear()
+                marks['scan'] += clock() - t0
         t0 = clock()
         for k, job in pending:
+            if scan_pheno is not None and k in scan_unsaved:
+                continue
             try:
                 job.result()
             except Exception as e:   # noqa: BLE001
@@ -1806,8 +1855,20 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
             write_snp_matrix(snp_matrix, [outbases[k] for k in ran],
                              np.stack([snp_rows[k] for k in ran]) if ran else np.zeros((0, len(snps['snp_id']))), snps)
         marks['save'] += clock() - t0
+        if scan_pheno is not None:
+            t0 = clock()
+            if scan is None:
+                raise RuntimeError('scan: no sample that ran has a phenotype row')
+            slices = sorted((v[1], v[2], c) for c, v in ctx.grid_slices.items())
+            scan_mod.finish_scan(scan, scan_out if scan_out is not None else 'gbrs', scan_ids, scan_tables[0], scan_tables[1],
+                                 scan_rankz, np.concatenate([[c] * m for _, m, c in slices]),
+                                 np.concatenate([np.asarray(ctx.grid[c], dtype=np.float64) for _, _, c in slices]),
+                                 list(ctx.chroms), scan_min_lod, scan_lod_matrix)
+            marks['scan'] += clock() - t0
     finally:
         writers.shutdown(wait=True)
+        if scan is not None:
+            scan.close()
         if context is None:
             ctx.close()
     logger.info('Done')

@@ -1,0 +1,297 @@
+"""Genome scan of phenotypes on founder dosages (extension): `gbrs reconstruct --scan-pheno` and
+`gbrs scan`.  Haley-Knott regression with additive covariates on the device (gbrs_scan_*, gbrs_amd/csrc/scan.hip); the
+host side here is the covariates' QR, the file readers and the writers.  No mixed model."""
+from __future__ import annotations
+
+import ctypes as C
+import logging
+
+import numpy as np
+
+from . import _lib
+
+logger = logging.getLogger('gbrs')
+
+COVARIATE_RANK_TOL = 1e-10        # a covariate column whose |R_jj| is below this share of its norm depends on the columns before it
+LOD_MATRIX_LIMIT = 1 << 27        # P x M up to which <out>.scan.npz holds the LOD matrix without being asked
+
+
+class GenomeScan:
+    """Device handle of one cohort on one grid.  append / append_from collect the samples' grid dosages in order,
+    prepare(covariates) builds the phenotype-independent part once, run(pheno) scans any number of phenotypes."""
+
+    def __init__(self, num_haps, points_per_chrom, device=0):
+        self.H = int(num_haps)
+        self.points = np.ascontiguousarray(points_per_chrom, dtype=np.int32)
+        self.M = int(self.points.sum())
+        self.n = 0
+        self.prepared = False
+        h = C.c_void_p()
+        _lib.check(_lib.load().gbrs_scan_create(int(device), len(self.points), _lib.ptr(self.points), self.H, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, '_h', None) is not None:
+            _lib.load().gbrs_scan_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def append(self, dosage):
+        """[n, M, H] (or [M, H]) founder dosages, rows as `DiplotypeHMM.grid()['dosage']` has them."""
+        d = np.ascontiguousarray(dosage, dtype=np.float64)
+        if d.ndim == 2:
+            d = d[None]
+        if d.ndim != 3 or d.shape[1:] != (self.M, self.H):
+            raise ValueError(f'dosage has shape {np.shape(dosage)}, expected (n, {self.M}, {self.H})')
+        _lib.check(_lib.load().gbrs_scan_append(self._h, len(d), _lib.ptr(d)))
+        self.n += len(d)
+        self.prepared = False
+
+    def append_from(self, hmm, sample=None):
+        """The grid dosages of `hmm`'s last run, device to device: every sample of the run, or the one given."""
+        _lib.check(_lib.load().gbrs_scan_append_hmm(self._h, hmm._h, -1 if sample is None else int(sample)))
+        self.n += hmm.n_samples if sample is None else 1
+        self.prepared = False
+
+    def prepare(self, covariates=None, names=None):
+        """covariates: [n, c] with the intercept (a column of ones) first, or None for the intercept alone."""
+        z = np.ones((self.n, 1)) if covariates is None else np.ascontiguousarray(covariates, dtype=np.float64)
+        if z.ndim != 2 or z.shape[0] != self.n:
+            raise ValueError(f'covariates have shape {z.shape} for {self.n} samples')
+        qz = covariate_basis(z, names)
+        self.prepared = False
+        _lib.check(_lib.load().gbrs_scan_prepare(self._h, qz.shape[1], _lib.ptr(qz)))
+        self.prepared = True
+
+    def run(self, pheno, want_lod=True):
+        """pheno: [n, P] (or [n]).  Returns `peak_lod` [P, n_chrom], `peak_index` [P, n_chrom] and, with want_lod, `lod`
+        [P, M].  A column whose values are all equal lies in the intercept's span: it goes to the device as zeros, so its
+        rss0 is exactly 0 and its LODs are 0.0 whatever the rounding of the projection."""
+        y = np.array(pheno, dtype=np.float64, order='C')
+        if y.ndim == 1:
+            y = y[:, None]
+        if y.ndim != 2 or y.shape[0] != self.n or y.shape[1] < 1:
+            raise ValueError(f'phenotypes have shape {np.shape(pheno)} for {self.n} samples')
+        if self.n:
+            y[:, (y == y[0]).all(axis=0)] = 0.0
+        P, nc = y.shape[1], len(self.points)
+        lod = np.empty((P, self.M)) if want_lod else None
+        peak, index = np.empty((P, nc)), np.empty((P, nc), dtype=np.int64)
+        _lib.check(_lib.load().gbrs_scan_run(self._h, P, _lib.ptr(y), _lib.ptr(lod), _lib.ptr(peak), _lib.ptr(index)))
+        out = {'peak_lod': peak, 'peak_index': index}
+        if want_lod:
+            out['lod'] = lod
+        return out
+
+    def info(self):
+        raw = _lib.ScanInfo()
+        _lib.check(_lib.load().gbrs_scan_info(self._h, C.byref(raw), None))
+        rank = None
+        if raw.c > 0:
+            rank = np.empty(raw.M, dtype=np.int32)
+            _lib.check(_lib.load().gbrs_scan_info(self._h, None, _lib.ptr(rank)))
+        return {'n': raw.n, 'M': raw.M, 'H': raw.H, 'c': raw.c, 'rank': rank, 'prepare_ms': raw.last_prepare_ms,
+                'run_ms': raw.last_run_ms, 'product_ms': raw.last_product_ms, 'device_bytes': raw.device_bytes}
+
+
+def covariate_basis(z, names=None):
+    """The orthonormal basis Qz [n, c] of the covariates (numpy QR; c is small).  The first column must be the intercept.
+    A value that is not finite is refused naming the entry; a column that depends on the ones before it - |R_jj| at most
+    COVARIATE_RANK_TOL times the column's norm - is refused by name."""
+    z = np.ascontiguousarray(z, dtype=np.float64)
+    label = lambda j: f'{j}' if names is None else f'{j} ({names[j]})'
+    bad = np.argwhere(~np.isfinite(z))
+    if len(bad):
+        raise ValueError(f'covariate column {label(int(bad[0][1]))} holds a value that is not finite (sample {int(bad[0][0])})')
+    if z.shape[1] < 1 or not (z[:, 0] == 1.0).all():
+        raise ValueError('the first covariate column must be the intercept (all ones)')
+    if z.shape[0] < z.shape[1]:
+        raise ValueError(f'{z.shape[0]} samples are too few for {z.shape[1]} covariate columns')
+    q, r = np.linalg.qr(z)
+    norms = np.sqrt((z * z).sum(axis=0))
+    for j in range(z.shape[1]):
+        if abs(r[j, j]) <= COVARIATE_RANK_TOL * norms[j]:
+            raise ValueError(f'covariate column {label(j)} is a linear combination of the columns before it: '
+                             'the covariates do not have full column rank')
+    return np.ascontiguousarray(q)
+
+
+def rankz(y):
+    """Rank-based inverse normal transform of one phenotype: Phi^-1((r - 1/2) / n) of the 1-based ranks r, ties sharing
+    the average of their ranks."""
+    from statistics import NormalDist
+    y = np.asarray(y, dtype=np.float64)
+    n = len(y)
+    order = np.argsort(y, kind='stable')
+    ranks = np.empty(n)
+    sorted_y = y[order]
+    lo = 0
+    while lo < n:
+        hi = lo
+        while hi + 1 < n and sorted_y[hi + 1] == sorted_y[lo]:
+            hi += 1
+        ranks[order[lo:hi + 1]] = 0.5 * (lo + hi) + 1.0
+        lo = hi + 1
+    inv = NormalDist().inv_cdf
+    return np.array([inv((r - 0.5) / n) for r in ranks])
+
+
+# ---- files ---------------------------------------------------------------------------------------------------------------
+
+def check_scan_args(scan_pheno=None, scan_covar=None, scan_rankz=False, scan_out=None, scan_min_lod=None,
+                    scan_lod_matrix=False, grid_file=None, cohort=False):
+    """`--scan-pheno FILE [--scan-covar FILE] [--scan-rankz] [--scan-out PREFIX] [--scan-min-lod X] [--scan-lod-matrix]`:
+    every option needs the phenotypes, the phenotypes need `--grid-file` and a cohort (`--sample-file`): one sample
+    cannot be scanned.  Refused before a file is read."""
+    given = {'--scan-covar': scan_covar, '--scan-rankz': scan_rankz or None, '--scan-out': scan_out,
+             '--scan-min-lod': scan_min_lod, '--scan-lod-matrix': scan_lod_matrix or None}
+    if scan_pheno is None:
+        for name, value in given.items():
+            if value is not None:
+                raise RuntimeError(f'{name} needs --scan-pheno')
+        return
+    if not cohort:
+        raise RuntimeError('--scan-pheno needs --sample-file: one sample (-e) cannot be scanned')
+    if grid_file is None:
+        raise RuntimeError('--scan-pheno needs --grid-file')
+    if scan_min_lod is not None and not scan_min_lod >= 0.0:
+        raise RuntimeError('--scan-min-lod must be a number that is not negative')
+
+
+def read_number_table(path, what):
+    """(column names, {id: row of floats}) of a tab separated table with the header `id<TAB>name...`; blank and # lines
+    after the header are skipped; an id given twice, a short row and a field that is no number are refused by line."""
+    with open(path) as fh:
+        header = fh.readline().rstrip('\n').split('\t')
+        if len(header) < 2 or header[0] != 'id':
+            raise RuntimeError(f'{path}: the header must be id<TAB>{what} name...')
+        names = header[1:]
+        if len(set(names)) != len(names):
+            raise RuntimeError(f'{path}: a {what} is named twice in the header')
+        rows, where = {}, {}
+        for number, line in enumerate(fh, 2):
+            line = line.rstrip('\n')
+            if not line.strip() or line.startswith('#'):
+                continue
+            fields = line.split('\t')
+            if len(fields) != len(header):
+                raise RuntimeError(f'{path}, line {number}: {len(fields) - 1} values for {len(names)} {what}s')
+            if fields[0] in rows:
+                raise RuntimeError(f'{path}, line {number}: id {fields[0]} is already on line {where[fields[0]]}')
+            try:
+                rows[fields[0]] = np.array([float(x) for x in fields[1:]])
+            except ValueError as e:
+                raise RuntimeError(f'{path}, line {number}: {e}') from None
+            where[fields[0]] = number
+    return names, rows
+
+
+def read_scan_pheno(path):
+    """`--scan-pheno`: rows keyed by the sample's outbase, one column per phenotype."""
+    return read_number_table(path, 'phenotype')
+
+
+def read_scan_covar(path):
+    """`--scan-covar`: rows keyed by the sample's outbase, one numeric column per covariate.  The intercept is not in
+    the file: scan_design adds it."""
+    return read_number_table(path, 'covariate')
+
+
+def scan_design(ids, pheno, covar=None, use_rankz=False):
+    """(kept positions in `ids`, Y [n, P], Z [n, c] with the intercept first, covariate names) for the ids that have a
+    phenotype row and, with covariates, a covariate row; the others are logged and left out."""
+    kept = []
+    for k, i in enumerate(ids):
+        if i not in pheno[1]:
+            logger.warning(f'scan: {i} has no phenotype row and is left out')
+        elif covar is not None and i not in covar[1]:
+            logger.warning(f'scan: {i} has no covariate row and is left out')
+        else:
+            kept.append(k)
+    P = len(pheno[0])
+    y = np.array([pheno[1][ids[k]] for k in kept]).reshape(len(kept), P)
+    if use_rankz:
+        y = np.column_stack([rankz(y[:, p]) for p in range(P)]) if len(kept) else y
+    names = ['intercept'] + (list(covar[0]) if covar is not None else [])
+    z = np.ones((len(kept), len(names)))
+    if covar is not None and kept:
+        z[:, 1:] = np.array([covar[1][ids[k]] for k in kept])
+    return kept, y, z, names
+
+
+def write_scan(prefix, phenotypes, samples, covariates, chrom, pos, chrom_names, result, rank, min_lod=0.0):
+    """`<prefix>.scan.npz` and `<prefix>.scan.peaks.tsv`.  chrom / pos: per grid point, in the scan's point order;
+    chrom_names: the scan's chromosomes, as peak_lod's columns."""
+    arrays = dict(phenotypes=np.array(phenotypes), samples=np.array(samples), covariates=np.array(covariates),
+                  chrom=np.array(chrom), pos=np.asarray(pos, dtype=np.float64), rank=np.asarray(rank),
+                  peak_lod=result['peak_lod'], peak_index=result['peak_index'])
+    if 'lod' in result:
+        arrays['lod'] = result['lod']
+    np.savez(f'{prefix}.scan.npz', **arrays)
+    peak, index = result['peak_lod'], result['peak_index']
+    with open(f'{prefix}.scan.peaks.tsv', 'w') as out:
+        out.write('#phenotype\tchromosome\tposition\tlod\tgenome_wide_max\n')
+        for p, name in enumerate(phenotypes):
+            on = [c for c in range(len(chrom_names)) if index[p, c] >= 0]
+            top = max(on, key=lambda c: (peak[p, c], -c)) if on else None
+            for c in on:
+                if peak[p, c] >= min_lod:
+                    out.write(f'{name}\t{chrom_names[c]}\t{repr(float(pos[index[p, c]]))}\t{repr(float(peak[p, c]))}\t'
+                              f'{int(c == top)}\n')
+
+
+def finish_scan(scan, prefix, ids, pheno, covar, use_rankz, chrom, pos, chrom_names, min_lod=None, lod_matrix=False):
+    """prepare + run + the two files for the cohort `scan` holds, whose samples are `ids` in append order (every one with
+    its rows in the tables).  Returns GenomeScan.info() after the run."""
+    kept, y, z, names = scan_design(ids, pheno, covar, use_rankz)
+    assert len(kept) == len(ids) == scan.n
+    scan.prepare(z, names)
+    want_lod = bool(lod_matrix) or y.shape[1] * scan.M <= LOD_MATRIX_LIMIT
+    result = scan.run(y, want_lod=want_lod)
+    info = scan.info()
+    write_scan(prefix, pheno[0], ids, names, chrom, pos, chrom_names, result, info['rank'],
+               0.0 if min_lod is None else min_lod)
+    logger.info(f'scan: {len(ids)} samples, {y.shape[1]} phenotypes, {scan.M} grid points; prepare '
+                f'{info["prepare_ms"]:.1f} ms, run {info["run_ms"]:.1f} ms on the device')
+    return info
+
+
+def scan_tables(dosage_list, grid_file, pheno_file, covar_file=None, use_rankz=False, out=None, min_lod=None,
+                lod_matrix=False, device=0):
+    """`gbrs scan`: the cohort from dosage tables in `gbrs export` format (lines `id<TAB>dosage table`), rows in the grid
+    file's order, without the HMM."""
+    from .hmm import _match_lines, read_dosage_table
+    from .postproc import read_grid
+    if min_lod is not None and not min_lod >= 0.0:
+        raise RuntimeError('--scan-min-lod must be a number that is not negative')
+    grid = read_grid(grid_file)
+    chrom_names = list(grid)
+    points = [len(grid[c]) for c in chrom_names]
+    entries, seen = [], set()
+    for number, sample_id, path in _match_lines(dosage_list, 'id<TAB>dosage table'):
+        if sample_id in seen:
+            raise RuntimeError(f'{dosage_list}, line {number}: id {sample_id} is given twice')
+        seen.add(sample_id)
+        entries.append((sample_id, path))
+    pheno = read_scan_pheno(pheno_file)
+    covar = read_scan_covar(covar_file) if covar_file is not None else None
+    kept, _, _, _ = scan_design([i for i, _ in entries], pheno, covar)
+    if not kept:
+        raise RuntimeError('scan: no sample of the dosage list has a phenotype row')
+    with open(entries[kept[0]][1]) as fh:
+        haplotypes = fh.readline().rstrip('\n')[2:].split('\t')
+    scan = GenomeScan(len(haplotypes), points, device=device)
+    try:
+        for k in kept:
+            scan.append(read_dosage_table(entries[k][1], haplotypes, sum(points)))
+        chrom = np.repeat(chrom_names, points)
+        pos = np.concatenate([np.asarray(grid[c], dtype=np.float64) for c in chrom_names])
+        return finish_scan(scan, out if out is not None else 'gbrs', [entries[k][0] for k in kept], pheno, covar, use_rankz,
+                           chrom, pos, chrom_names, min_lod, lod_matrix)
+    finally:
+        scan.close()

@@ -888,6 +888,72 @@ int gbrs_alignment_spec(const double *tables, const int64_t *strain_ptr /* num_s
                         int device, double *axes, double *ases, double *avecs, uint8_t *has_avec);
 
 /* ------------------------------------------------------------------------------------------
+ * Genome scan (extension; `gbrs reconstruct --scan-pheno`, `gbrs scan`): Haley-Knott regression of
+ * phenotypes on the founder dosages of a cohort at every grid point, with additive covariates.
+ * ---------------------------------------------------------------------------------------- */
+
+typedef struct gbrs_scan gbrs_scan_t;
+
+/* The handle of one cohort on one grid: n_chrom chromosomes of points_per_chrom[c] >= 0 grid points (M their sum, in
+ * that order, as gbrs_hmm_grid lays them out) and num_haps founders.  num_haps < 2 or > 17, n_chrom < 1 and M = 0 are
+ * GBRS_ERR_INVALID.  The handle is independent of any HMM handle. */
+int gbrs_scan_create(int device, int n_chrom, const int32_t *points_per_chrom, int num_haps, gbrs_scan_t **out);
+int gbrs_scan_destroy(gbrs_scan_t *scan);
+
+/* n more samples at the end of the cohort: dosage is double[n][M][H] on the host (gbrs_hmm_grid's `dosage`).  A value
+ * that is not finite is refused with GBRS_ERR_INVALID naming the entry; the cohort is then as it was.  An append drops
+ * what gbrs_scan_prepare made. */
+int gbrs_scan_append(gbrs_scan_t *scan, int n, const double *dosage);
+
+/* The same from the grid dosages an HMM handle holds for its last run, device to device: sample = -1 appends all samples
+ * of the run in their order, else that one.  The grid kernel runs first under gbrs_hmm_match's condition (the handle
+ * holds no dosages of the last run for the same `sample` argument), and only after every check below has passed: a
+ * refused call launches nothing on the HMM handle.  GBRS_ERR_STATE before the first run;
+ * GBRS_ERR_INVALID without a grid, for a sample out of range, for another device, and for a handle whose grid has other
+ * points per chromosome or whose founder count differs.  What the cohort holds afterwards is, bit for bit, what
+ * gbrs_scan_append of gbrs_hmm_grid's output would have left. */
+int gbrs_scan_append_hmm(gbrs_scan_t *scan, gbrs_hmm_t *hmm, int sample);
+
+/* The phenotype-independent part, once per (cohort, covariates).  qz is double[n][c]: an orthonormal basis of the
+ * covariates' columns (the caller's QR; its span holds the intercept).  Per grid point m, with X_m = D[:, m, 0:H-1]:
+ *   X~ = X_m - qz qz' X_m,  G = X~' X~,
+ *   Cholesky of G in column order j = 0 .. H-2 with the skip rule: the pivot is d_j = G_jj - sum over the kept i < j of
+ *   L_ji^2; column j is kept iff G_jj > 0 and d_j > 1e-10 G_jj; a skipped column has a zero row in L and takes no part
+ *   in anything after it.  The covariates count as the columns before column 0: G_jj <= 1e-10 |X_m[:, j]|^2 (the
+ *   projection left rounding: a founder with the same dosage in every sample) is taken as G_jj = 0,
+ *   W_m = L^-1 X~' (zero rows for skipped columns), rank[m] = number of kept columns.
+ * W is kept on the device as [M * Hp][n_ld], Hp = 8 for H <= 9 and 16 otherwise, n_ld = n rounded up to 32 and zero
+ * filled.  GBRS_ERR_INVALID for c < 1 or c > 64, n <= c + H - 1, and a qz value that is not finite (the message names
+ * the entry); such a refusal leaves the handle as it was, an earlier preparation included.  A failure after these
+ * checks (device memory, the kernel) leaves it unprepared. */
+int gbrs_scan_prepare(gbrs_scan_t *scan, int c, const double *qz);
+
+/* P phenotypes of the prepared cohort: pheno is double[n][P], rows in append order.  Per phenotype p
+ *   y~ = y - qz qz' y,  rss0 = |y~|^2,  ess[m] = |W_m y~|^2,  rss1 = rss0 - ess[m],
+ *   lod[p][m] = (n / 2) log10(rss0 / rss1); 0.0 where rss0 == 0; +inf where rss1 <= 0 < rss0.
+ * lod is double[P][M] (nullable), peak_lod double[P][n_chrom] the maximum over a chromosome's points, peak_index
+ * int64[P][n_chrom] its grid index among the M points, the lowest on ties (NaN and -1 for a chromosome without points);
+ * both nullable.  The phenotypes go through the device in chunks of 512 columns; the products W_m y~ never reach memory.
+ * A phenotype's numbers are the same bits alone or among others, at any column, in any chunk, and however the cohort
+ * was appended.  Nothing here looks for a phenotype that lies in the covariates' span: a column whose values are all
+ * equal projects to rounding, not to zeros, unless the projection happens to be exact, and its LODs are then noise; the
+ * caller sends such a column as zeros (gbrs_amd.scan.GenomeScan.run does), which gives rss0 == 0 and 0.0 throughout.
+ * GBRS_ERR_INVALID before gbrs_scan_prepare, for P < 1 and for a value that is not finite (the message
+ * names the entry); the outputs are untouched on failure. */
+int gbrs_scan_run(gbrs_scan_t *scan, int64_t P, const double *pheno, double *lod, double *peak_lod, int64_t *peak_index);
+
+typedef struct gbrs_scan_info {
+    int64_t  n, M;               /* samples appended, grid points                                              */
+    int32_t  H, c;               /* founders; covariate columns of the last prepare (0: not prepared)          */
+    double   last_prepare_ms;    /* device time of the last gbrs_scan_prepare's kernel                         */
+    double   last_run_ms;        /* device time of the last gbrs_scan_run: its kernels and copies, all chunks  */
+    double   last_product_ms;    /* of that, the product kernel alone, summed over the chunks                  */
+    uint64_t device_bytes;       /* what the handle holds on the device                                        */
+} gbrs_scan_info_t;
+/* rank is int32[M] of the last prepare, nullable; untouched when the handle is not prepared. */
+int gbrs_scan_info(gbrs_scan_t *scan, gbrs_scan_info_t *info, int32_t *rank);
+
+/* ------------------------------------------------------------------------------------------
  * Report text (host side, no device work): the `locus <haplotypes> total [notes]` tables of
  * EMfactory.report_read_counts / report_depths (emase/EMfactory.py:289-380).
  * ---------------------------------------------------------------------------------------- */

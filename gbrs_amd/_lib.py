@@ -35,7 +35,7 @@ EXPORTS = [
     "gbrs_hmm_loglik", "gbrs_hmm_loglik_tables", "gbrs_hmm_loglik_info", "gbrs_interpolate", "gbrs_genoprob_dosage",
     "gbrs_ri_transition_tables", "gbrs_alignment_spec",
     "gbrs_scan_create", "gbrs_scan_destroy", "gbrs_scan_append", "gbrs_scan_append_hmm", "gbrs_scan_prepare", "gbrs_scan_run",
-    "gbrs_scan_info",
+    "gbrs_scan_info", "gbrs_scan_permute", "gbrs_scan_perm_info",
     "gbrs_compress_create", "gbrs_compress_get", "gbrs_compress_destroy",
     "gbrs_bam_open", "gbrs_bam_references", "gbrs_bam_set_reference_map", "gbrs_bam_convert", "gbrs_bam_get",
     "gbrs_bam_scan_records", "gbrs_bam_destroy",
@@ -107,6 +107,13 @@ class ScanInfo(C.Structure):
         ("n", C.c_int64), ("M", C.c_int64), ("H", C.c_int32), ("c", C.c_int32),
         ("last_prepare_ms", C.c_double), ("last_run_ms", C.c_double), ("last_product_ms", C.c_double),
         ("device_bytes", C.c_uint64),
+    ]
+
+
+class ScanPermInfo(C.Structure):
+    _fields_ = [
+        ("P", C.c_int64), ("B", C.c_int64), ("last_permute_ms", C.c_double), ("last_product_ms", C.c_double),
+        ("peak_device_bytes", C.c_uint64),
     ]
 
 
@@ -215,6 +222,8 @@ def load():
         "gbrs_scan_prepare": [vp, i32, vp],
         "gbrs_scan_run": [vp, i64, vp, vp, vp, vp],
         "gbrs_scan_info": [vp, C.POINTER(ScanInfo), vp],
+        "gbrs_scan_permute": [vp, i64, vp, i64, u64, vp, vp, vp],
+        "gbrs_scan_perm_info": [vp, C.POINTER(ScanPermInfo)],
         "gbrs_compress_create": [u64, u32, u32, pp, pp, vp, i32, pp, C.POINTER(u64), vp],
         "gbrs_compress_get": [vp, pp, pp, vp],
         "gbrs_compress_destroy": [vp],

@@ -290,6 +290,18 @@ def _scan_options(parser, covar=True):
                         help='only peaks of at least this LOD go to the peaks file (default: 0.0)')
     parser.add_argument('--scan-lod-matrix', action='store_true',
                         help='keep the phenotypes x grid points LOD matrix in the .npz however large it is')
+    parser.add_argument('--scan-perms', type=int, default=None, metavar='B',
+                        help='permutation test on the device: B permutations of the covariate model\'s residuals '
+                             '(Freedman-Lane), the same for every phenotype; the .npz gains perm_max, the levels\' genome-wide '
+                             'thresholds and their inputs, the peaks file the columns pvalue and threshold_<first level>')
+    parser.add_argument('--scan-perm-seed', type=int, default=None, metavar='S', help='with --scan-perms: 64-bit seed (default: 0)')
+    parser.add_argument('--scan-perm-alpha', default=None, metavar='A,...',
+                        help='with --scan-perms: genome-wide levels, comma separated (default: 0.05,0.1)')
+    parser.add_argument('--scan-perm-chromosomes', default=None, metavar='C,...',
+                        help='with --scan-perms: the maximum is taken over these chromosomes only, named as in the grid file '
+                             '(default: all)')
+    parser.add_argument('--scan-perm-pheno', type=_existing, default=None, metavar='FILE',
+                        help='with --scan-perms: one phenotype name per line; only those are permuted (default: all)')
 
 
 def main(argv=None) -> int:
@@ -325,7 +337,9 @@ def main(argv=None) -> int:
             check_snp_args(args.snp_file, args.snp_matrix, cohort=args.sample_file is not None)
             from .scan import check_scan_args
             check_scan_args(args.scan_pheno, args.scan_covar, args.scan_rankz, args.scan_out, args.scan_min_lod,
-                            args.scan_lod_matrix, args.grid_file, cohort=args.sample_file is not None)
+                            args.scan_lod_matrix, args.grid_file, cohort=args.sample_file is not None,
+                            scan_perms=args.scan_perms, scan_perm_seed=args.scan_perm_seed, scan_perm_alpha=args.scan_perm_alpha,
+                            scan_perm_chromosomes=args.scan_perm_chromosomes, scan_perm_pheno=args.scan_perm_pheno)
         if args.command == 'quantify' and args.gpus is not None:
             # N child processes, one per rank; this process opens no device
             from .sharded import launch
@@ -425,7 +439,10 @@ def main(argv=None) -> int:
             from .scan import scan_tables
             scan_tables(dosage_list=args.dosage_list, grid_file=args.grid_file, pheno_file=args.pheno,
                         covar_file=args.scan_covar, use_rankz=args.scan_rankz, out=args.scan_out, min_lod=args.scan_min_lod,
-                        lod_matrix=args.scan_lod_matrix, device=args.device)
+                        lod_matrix=args.scan_lod_matrix, device=args.device, scan_perms=args.scan_perms,
+                        scan_perm_seed=args.scan_perm_seed, scan_perm_alpha=args.scan_perm_alpha,
+                        scan_perm_chromosomes=args.scan_perm_chromosomes, scan_perm_pheno=args.scan_perm_pheno,
+                        stage_times=stages)
         elif args.command == 'interpolate':
             from .postproc import interpolate
             interpolate(genoprob_file=args.genoprob_file, grid_file=args.grid_file, gpos_file=args.gpos_file,
@@ -449,7 +466,10 @@ def main(argv=None) -> int:
                              match_chromosomes=args.match_chromosomes, match_report=args.match_report,
                              match_matrix=args.match_matrix, snp_file=args.snp_file, snp_matrix=args.snp_matrix,
                              scan_pheno=args.scan_pheno, scan_covar=args.scan_covar, scan_rankz=args.scan_rankz,
-                             scan_out=args.scan_out, scan_min_lod=args.scan_min_lod, scan_lod_matrix=args.scan_lod_matrix)
+                             scan_out=args.scan_out, scan_min_lod=args.scan_min_lod, scan_lod_matrix=args.scan_lod_matrix,
+                             scan_perms=args.scan_perms, scan_perm_seed=args.scan_perm_seed,
+                             scan_perm_alpha=args.scan_perm_alpha, scan_perm_chromosomes=args.scan_perm_chromosomes,
+                             scan_perm_pheno=args.scan_perm_pheno)
         else:
             from .hmm import reconstruct
             reconstruct(expression_file=args.expression_file, tprob_file=args.tprob_file,

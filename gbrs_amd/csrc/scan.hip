@@ -7,7 +7,9 @@
 // block [P][n_ld] on v_mfma_f64_16x16x4_f64, squares and sums the Hp rows of every grid point in its epilogue and stores
 // LODs only.  Both operands are row-major with the sample axis (K) contiguous and zero filled up to n_ld, a multiple of
 // the K chunk: the operand maps, the LDS stride and the prefetch are those of match_cross_kernel (hmm_match.inc), without
-// its K tail and its 8-byte staging.
+// its K tail and its 8-byte staging.  permute (kernels in scan_perm.inc): permutations of the projected
+// phenotypes, drawn and gathered on the device, pass through the same product and peak kernels as further columns, and
+// one maximum per (phenotype, permutation) comes back.
 #include "common.h"
 #include "scan_hmm.h"
 
@@ -302,6 +304,11 @@ scan_peak_kernel(int64_t M, int n_chrom, const int64_t *__restrict__ point_off, 
     }
 }
 
+// ---- permutation thresholds ----------------------------------------------------------------------------------------------------
+
+#include "philox.h"
+#include "scan_perm.inc"
+
 }  // namespace gbrs
 
 using namespace gbrs;
@@ -328,6 +335,10 @@ struct gbrs_scan {
     DevBuf<double> y, yt, rss0, lod, peak_lod;
     DevBuf<int64_t> peak_index;
     double t_prepare = 0, t_run = 0, t_product = 0;
+    // the last gbrs_scan_permute: its buffers are the call's own and are gone when it returns
+    int64_t perm_P = 0, perm_B = 0;
+    double t_permute = 0, t_perm_product = 0;
+    uint64_t perm_peak_bytes = 0;
 };
 
 namespace {
@@ -352,6 +363,39 @@ void scan_unprepare(gbrs_scan *s) {
     s->c = 0;
     s->rank.clear();
 }
+
+// Pairs of events around the product kernel of consecutive chunks, so that a pass times it without waiting per chunk: a
+// pair is read when its turn comes round again, and the rest after the pass.
+struct EventRing {
+    static constexpr int PAIRS = 8;
+    hipEvent_t ev[2 * PAIRS] = {};
+    int64_t used = 0;
+    double ms = 0.0;
+    ~EventRing() {
+        for (auto e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    int create() {
+        for (auto &e : ev) GBRS_HIP_CHECK(hipEventCreate(&e));
+        return GBRS_OK;
+    }
+    int read(int slot) {
+        float t = 0.f;
+        GBRS_HIP_CHECK(hipEventSynchronize(ev[2 * slot + 1]));
+        if (hipEventElapsedTime(&t, ev[2 * slot], ev[2 * slot + 1]) == hipSuccess) ms += t;
+        return GBRS_OK;
+    }
+    int next(int *slot) {           // the slot of the next chunk, its earlier use read
+        *slot = (int)(used % PAIRS);
+        if (used >= PAIRS) GBRS_TRY(read(*slot));
+        ++used;
+        return GBRS_OK;
+    }
+    int drain() {                   // after the stream was waited for
+        for (int64_t k = std::max<int64_t>(0, used - PAIRS); k < used; ++k) GBRS_TRY(read((int)(k % PAIRS)));
+        return GBRS_OK;
+    }
+};
 
 }  // namespace
 
@@ -544,6 +588,110 @@ int gbrs_scan_run(gbrs_scan_t *s, int64_t P, const double *pheno, double *lod, d
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) s->t_run = ms;
     s->t_product = t_product;
+    return GBRS_OK;
+}
+
+int gbrs_scan_permute(gbrs_scan_t *s, int64_t P, const double *pheno, int64_t B, uint64_t seed, const uint8_t *chrom_mask,
+                      double *perm_max, int32_t *perm_index) {
+    RoctxRange roctx_range("gbrs_scan_permute");
+    if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (s->c == 0) return fail(GBRS_ERR_INVALID, "no covariates on the handle: call gbrs_scan_prepare first");
+    if (P < 1) return fail(GBRS_ERR_INVALID, "a permutation pass needs at least 1 phenotype, got %lld", (long long)P);
+    if (B < 1) return fail(GBRS_ERR_INVALID, "a permutation pass needs at least 1 permutation, got %lld", (long long)B);
+    if (!pheno || !perm_max) return fail(GBRS_ERR_INVALID, "bad argument");
+    const int n = (int)s->n;
+    const int tiles = (n + SP_THREADS - 1) / SP_THREADS;
+    if (B > std::numeric_limits<int32_t>::max() / tiles || P > std::numeric_limits<int64_t>::max() / 8 / B)
+        return fail(GBRS_ERR_INVALID, "too many permutations: %lld of %d samples for %lld phenotypes", (long long)B, n, (long long)P);
+    int64_t selected = 0;
+    for (int c = 0; c < s->n_chrom; ++c)
+        if (!chrom_mask || chrom_mask[c]) selected += s->points[c];
+    if (selected == 0) return fail(GBRS_ERR_INVALID, "the chromosome mask selects no grid point");
+    for (int64_t k = 0; k < (int64_t)n * P; ++k)
+        if (!std::isfinite(pheno[k]))
+            return fail(GBRS_ERR_INVALID, "phenotype %lld holds a value that is not finite (sample %lld)", (long long)(k % P),
+                        (long long)(k / P));
+    GBRS_TRY(select_device(s->device));
+    const int64_t cols = P * B, pc_max = std::min(cols, SC_PCHUNK), yc_max = std::min(P, SC_PCHUNK), M = s->M, n_ld = s->n_ld;
+    DevBuf<double> y, yt_all, rss_all, yt, rss0, lod, peak_lod, pmax;
+    DevBuf<int64_t> peak_index;
+    DevBuf<int32_t> perm;
+    DevBuf<uint8_t> mask;
+    GBRS_TRY(y.alloc((size_t)n * yc_max));
+    GBRS_TRY(yt_all.alloc((size_t)P * n_ld));
+    GBRS_TRY(rss_all.alloc((size_t)P));
+    GBRS_TRY(yt.alloc((size_t)pc_max * n_ld));
+    GBRS_TRY(rss0.alloc((size_t)pc_max));
+    GBRS_TRY(lod.alloc((size_t)pc_max * M));
+    GBRS_TRY(peak_lod.alloc((size_t)pc_max * s->n_chrom));
+    GBRS_TRY(peak_index.alloc((size_t)pc_max * s->n_chrom));
+    GBRS_TRY(pmax.alloc((size_t)cols));
+    GBRS_TRY(perm.alloc((size_t)B * n));
+    GBRS_TRY(mask.alloc((size_t)s->n_chrom));
+    std::vector<uint8_t> h_mask((size_t)s->n_chrom, 1);
+    if (chrom_mask)
+        for (int c = 0; c < s->n_chrom; ++c) h_mask[c] = chrom_mask[c] ? 1 : 0;
+    GBRS_HIP_CHECK(hipMemcpy(mask.p, h_mask.data(), mask.bytes(), hipMemcpyHostToDevice));
+    EventRing ring;
+    GBRS_TRY(ring.create());
+    GBRS_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
+    // y~ of every phenotype, by gbrs_scan_run's kernel in gbrs_scan_run's chunks; it stays on the device for the pass
+    for (int64_t p0 = 0; p0 < P; p0 += SC_PCHUNK) {
+        const int64_t pc = std::min(SC_PCHUNK, P - p0);
+        GBRS_HIP_CHECK(hipMemcpy2DAsync(y.p, (size_t)pc * sizeof(double), pheno + p0, (size_t)P * sizeof(double),
+                                        (size_t)pc * sizeof(double), (size_t)n, hipMemcpyHostToDevice, s->stream));
+        hipLaunchKernelGGL(scan_pheno_kernel, dim3((unsigned)pc), dim3(64), 0, s->stream, n, s->c, n_ld, pc, y.p, s->qz.p,
+                           yt_all.p + p0 * n_ld, rss_all.p + p0);
+        GBRS_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(scan_perm_rank_kernel, dim3((unsigned)(B * tiles)), dim3(SP_THREADS), 0, s->stream, n, tiles,
+                       (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), perm.p);
+    GBRS_HIP_CHECK(hipGetLastError());
+    const unsigned row_blocks = (unsigned)((M * s->Hp + SC_ROWS - 1) / SC_ROWS);
+    for (int64_t col0 = 0; col0 < cols; col0 += SC_PCHUNK) {
+        const int64_t pc = std::min(SC_PCHUNK, cols - col0);
+        int slot = 0;
+        GBRS_TRY(ring.next(&slot));
+        hipLaunchKernelGGL(scan_perm_pheno_kernel, dim3((unsigned)pc), dim3(64), 0, s->stream, n, s->c, n_ld, B, col0, yt_all.p,
+                           perm.p, s->qz.p, yt.p, rss0.p);
+        GBRS_HIP_CHECK(hipEventRecord(ring.ev[2 * slot], s->stream));
+        const dim3 grid(row_blocks, (unsigned)((pc + SC_COLS - 1) / SC_COLS));
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, dim3(SC_THREADS), 0, s->stream, M, pc, n_ld, 0.5 * n, s->W.p, yt.p, rss0.p, lod.p);
+        };
+        if (s->Hp == 8) launch(scan_lod_kernel<8>);
+        else launch(scan_lod_kernel<16>);
+        GBRS_HIP_CHECK(hipEventRecord(ring.ev[2 * slot + 1], s->stream));
+        hipLaunchKernelGGL(scan_peak_kernel, dim3((unsigned)s->n_chrom, (unsigned)pc), dim3(64), 0, s->stream, M, s->n_chrom,
+                           s->d_point_off.p, lod.p, peak_lod.p, peak_index.p);
+        hipLaunchKernelGGL(scan_perm_max_kernel, dim3((unsigned)((pc + SP_THREADS - 1) / SP_THREADS)), dim3(SP_THREADS), 0, s->stream,
+                           pc, s->n_chrom, s->d_point_off.p, mask.p, peak_lod.p, pmax.p + col0);
+        GBRS_HIP_CHECK(hipGetLastError());
+    }
+    GBRS_HIP_CHECK(hipEventRecord(s->ev[1], s->stream));
+    GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
+    GBRS_TRY(ring.drain());
+    GBRS_HIP_CHECK(hipMemcpy(perm_max, pmax.p, pmax.bytes(), hipMemcpyDeviceToHost));
+    if (perm_index) GBRS_HIP_CHECK(hipMemcpy(perm_index, perm.p, perm.bytes(), hipMemcpyDeviceToHost));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) s->t_permute = ms;
+    s->t_perm_product = ring.ms;
+    s->perm_P = P;
+    s->perm_B = B;
+    s->perm_peak_bytes = s->d_point_off.bytes() + s->dosage.bytes() + s->qz.bytes() + s->W.bytes() + s->d_rank.bytes() + s->y.bytes() +
+                         s->yt.bytes() + s->rss0.bytes() + s->lod.bytes() + s->peak_lod.bytes() + s->peak_index.bytes() + y.bytes() +
+                         yt_all.bytes() + rss_all.bytes() + yt.bytes() + rss0.bytes() + lod.bytes() + peak_lod.bytes() +
+                         peak_index.bytes() + pmax.bytes() + perm.bytes() + mask.bytes();
+    return GBRS_OK;
+}
+
+int gbrs_scan_perm_info(gbrs_scan_t *s, gbrs_scan_perm_info_t *info) {
+    if (!s || !info) return fail(GBRS_ERR_INVALID, "bad argument");
+    info->P = s->perm_P;
+    info->B = s->perm_B;
+    info->last_permute_ms = s->t_permute;
+    info->last_product_ms = s->t_perm_product;
+    info->peak_device_bytes = s->perm_peak_bytes;
     return GBRS_OK;
 }
 

@@ -1570,7 +1570,9 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
                      match_panel: str = None, match_labels: str = None, match_chromosomes=None, match_report: str = None,
                      match_matrix: str = None, match_expected: str = None, snp_file: str = None,
                      snp_matrix: str = None, scan_pheno: str = None, scan_covar: str = None, scan_rankz: bool = False,
-                     scan_out: str = None, scan_min_lod: float = None, scan_lod_matrix: bool = False) -> list:
+                     scan_out: str = None, scan_min_lod: float = None, scan_lod_matrix: bool = False,
+                     scan_perms: int = None, scan_perm_seed: int = None, scan_perm_alpha=None, scan_perm_chromosomes=None,
+                     scan_perm_pheno: str = None) -> list:
     """`gbrs reconstruct` for a cohort whose genes.tpm files exist (extension): one context, the tables on the device
     once, the samples through the HMM in launches of up to `batch_size`, and with `grid_file` one grid pass per launch.
     Every sample gets the files the single-sample call writes for its outbase.  All samples must carry the same
@@ -1598,10 +1600,15 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
     `scan_pheno` (needs a grid file): a table of phenotypes keyed by outbase.  The grid dosages of every
     sample that ran and has a phenotype row (and, with `scan_covar`, a covariate row) are collected on the device in the
     order of `expression_files`; after the last launch the phenotypes are regressed on them at every grid point and
-    `<scan_out>.scan.npz` and `<scan_out>.scan.peaks.tsv` are written (gbrs_amd/scan.py)."""
+    `<scan_out>.scan.npz` and `<scan_out>.scan.peaks.tsv` are written (gbrs_amd/scan.py).  `scan_perms`:
+    that many permutations follow the scan on the device and both files gain genome-wide thresholds and p-values; the
+    other `scan_perm_*` are scan.perm_options'."""
     from . import scan as scan_mod
     scan_mod.check_scan_args(scan_pheno, scan_covar, scan_rankz, scan_out, scan_min_lod, scan_lod_matrix,
-                             grid_file if context is None else context.grid_file, cohort=True)
+                             grid_file if context is None else context.grid_file, cohort=True, scan_perms=scan_perms,
+                             scan_perm_seed=scan_perm_seed, scan_perm_alpha=scan_perm_alpha,
+                             scan_perm_chromosomes=scan_perm_chromosomes, scan_perm_pheno=scan_perm_pheno)
+    scan_perm = scan_mod.perm_options(scan_perms, scan_perm_seed, scan_perm_alpha, scan_perm_chromosomes, scan_perm_pheno)
     check_sim_geno_args(sim_geno, sim_geno_seed)
     check_snp_args(snp_file, snp_matrix, cohort=True)
     check_diagnostics_args(diagnostics, error_lod_threshold, gene_report, cohort=True)
@@ -1658,10 +1665,12 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
         scan_ids, scan_held = [], {}       # scan_held: sample -> its host dosage rows, until its batch is appended
         scan_unsaved = set()               # samples whose files could not be written: reported once, left out of the scan
         scan_keep = set(scan_mod.scan_design(outbases, *scan_tables)[0])
+        if scan_perm is not None:          # a name the table or the grid does not have is refused before a sample runs
+            scan_mod.perm_plan(scan_perm, scan_tables[0][0], [str(c) for c in ctx.chroms])
     marks['load'] = clock() - t0
     for key in ('read', 'hmm', 'grid', 'save') + (('loglik',) if loglik else ()) + \
             (('match',) if match_panel is not None else ()) + (('snp',) if snps is not None else ()) + \
-            (('scan',) if scan_pheno is not None else ()):
+            (('scan',) if scan_pheno is not None else ()) + (('scan_perm',) if scan_perm is not None else ()):
         marks[key] = 0.0
     names = [tprob_file] + list(ctx.alt_tprob_files) if loglik else None
     choices = {}                           # sample -> (selected candidate, margin, totals per candidate)
@@ -1863,8 +1872,8 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
             scan_mod.finish_scan(scan, scan_out if scan_out is not None else 'gbrs', scan_ids, scan_tables[0], scan_tables[1],
                                  scan_rankz, np.concatenate([[c] * m for _, m, c in slices]),
                                  np.concatenate([np.asarray(ctx.grid[c], dtype=np.float64) for _, _, c in slices]),
-                                 list(ctx.chroms), scan_min_lod, scan_lod_matrix)
-            marks['scan'] += clock() - t0
+                                 list(ctx.chroms), scan_min_lod, scan_lod_matrix, perm=scan_perm, stage_times=marks)
+            marks['scan'] += clock() - t0 - (marks['scan_perm'] if scan_perm is not None else 0.0)
     finally:
         writers.shutdown(wait=True)
         if scan is not None:

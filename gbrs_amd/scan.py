@@ -14,6 +14,7 @@ logger = logging.getLogger('gbrs')
 
 COVARIATE_RANK_TOL = 1e-10        # a covariate column whose |R_jj| is below this share of its norm depends on the columns before it
 LOD_MATRIX_LIMIT = 1 << 27        # P x M up to which <out>.scan.npz holds the LOD matrix without being asked
+DEFAULT_PERM_ALPHA = (0.05, 0.1)  # the levels of --scan-perm-alpha
 
 
 class GenomeScan:
@@ -88,6 +89,39 @@ class GenomeScan:
             out['lod'] = lod
         return out
 
+    def permute(self, pheno, n_perm, seed=0, chromosomes=None, want_index=False):
+        """Permutation maxima of the prepared cohort (Freedman-Lane: the residuals of the covariate model
+        are permuted).  pheno: [n, P] (or [n]), with run()'s constant-column-to-zeros step; chromosomes: a mask [n_chrom]
+        of the chromosomes the maximum is taken over (default: all).  Returns `perm_max` [P, n_perm] and, with
+        want_index, `perm_index` [n_perm, n] - the permutations, which depend on (seed, permutation, n) alone."""
+        y = np.array(pheno, dtype=np.float64, order='C')
+        if y.ndim == 1:
+            y = y[:, None]
+        if y.ndim != 2 or y.shape[0] != self.n:
+            raise ValueError(f'phenotypes have shape {np.shape(pheno)} for {self.n} samples')
+        if self.n:
+            y[:, (y == y[0]).all(axis=0)] = 0.0
+        P, B = y.shape[1], int(n_perm)
+        mask = None
+        if chromosomes is not None:
+            mask = np.ascontiguousarray(chromosomes, dtype=bool).astype(np.uint8)
+            if mask.shape != (len(self.points),):
+                raise ValueError(f'the chromosome mask has shape {mask.shape} for {len(self.points)} chromosomes')
+        perm_max = np.empty((P, max(B, 0)))
+        index = np.empty((max(B, 0), self.n), dtype=np.int32) if want_index else None
+        _lib.check(_lib.load().gbrs_scan_permute(self._h, P, _lib.ptr(y), B, int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(mask),
+                                                 _lib.ptr(perm_max), _lib.ptr(index)))
+        out = {'perm_max': perm_max}
+        if want_index:
+            out['perm_index'] = index
+        return out
+
+    def perm_info(self):
+        raw = _lib.ScanPermInfo()
+        _lib.check(_lib.load().gbrs_scan_perm_info(self._h, C.byref(raw)))
+        return {'P': raw.P, 'B': raw.B, 'permute_ms': raw.last_permute_ms, 'product_ms': raw.last_product_ms,
+                'peak_device_bytes': raw.peak_device_bytes}
+
     def info(self):
         raw = _lib.ScanInfo()
         _lib.check(_lib.load().gbrs_scan_info(self._h, C.byref(raw), None))
@@ -141,15 +175,113 @@ def rankz(y):
     return np.array([inv((r - 0.5) / n) for r in ranks])
 
 
+def perm_thresholds(perm_max, alphas):
+    """threshold[p][a]: the ceil((1 - alpha_a) B)-th smallest of perm_max[p][:], an order statistic without
+    interpolation.  (1 - alpha) B is rounded at the ninth decimal before the ceiling, so that 0.95 x 20 is 19."""
+    import math
+    pm = np.asarray(perm_max, dtype=np.float64)
+    if pm.ndim != 2 or pm.shape[1] < 1:
+        raise ValueError(f'perm_max has shape {pm.shape}, expected (phenotypes, permutations >= 1)')
+    B = pm.shape[1]
+    ordered = np.sort(pm, axis=1)
+    out = np.empty((pm.shape[0], len(alphas)))
+    for a, alpha in enumerate(alphas):
+        if not 0.0 < alpha < 1.0:
+            raise ValueError(f'a level must lie in (0, 1), got {alpha}')
+        k = min(max(math.ceil(round((1.0 - alpha) * B, 9)), 1), B)
+        out[:, a] = ordered[:, k - 1]
+    return out
+
+
+def perm_pvalues(perm_max, peak_lod, selected=None):
+    """(1 + #{b : perm_max[p][b] >= x}) / (B + 1) for every observed peak x = peak_lod[p][...]; +inf compares as numpy
+    compares it.  NaN for a peak that is NaN (a chromosome without points) and, with `selected` (a mask over peak_lod's
+    last axis), for the chromosomes the permutations did not look at."""
+    pm = np.asarray(perm_max, dtype=np.float64)
+    peak = np.asarray(peak_lod, dtype=np.float64)
+    if pm.ndim != 2 or peak.shape[:1] != pm.shape[:1]:
+        raise ValueError(f'perm_max has shape {pm.shape}, the peaks {peak.shape}')
+    flat = peak.reshape(len(pm), -1)
+    with np.errstate(invalid='ignore'):
+        count = (pm[:, None, :] >= flat[:, :, None]).sum(axis=2)
+    p = np.where(np.isnan(flat), np.nan, (1.0 + count) / (pm.shape[1] + 1.0)).reshape(peak.shape)
+    if selected is not None:
+        p[..., ~np.asarray(selected, dtype=bool)] = np.nan
+    return p
+
+
 # ---- files ---------------------------------------------------------------------------------------------------------------
 
+def perm_options(scan_perms=None, scan_perm_seed=None, scan_perm_alpha=None, scan_perm_chromosomes=None,
+                 scan_perm_pheno=None):
+    """`--scan-perms B [--scan-perm-seed S] [--scan-perm-alpha 0.05,0.1] [--scan-perm-chromosomes 1,2,...]
+    [--scan-perm-pheno FILE]` as one dict, or None without `--scan-perms`; the other options are then refused.  Levels
+    and chromosome names come as the command's comma separated text or as sequences.  Refused before a file is read."""
+    if scan_perms is None:
+        for name, value in (('--scan-perm-seed', scan_perm_seed), ('--scan-perm-alpha', scan_perm_alpha),
+                            ('--scan-perm-chromosomes', scan_perm_chromosomes), ('--scan-perm-pheno', scan_perm_pheno)):
+            if value is not None:
+                raise RuntimeError(f'{name} needs --scan-perms')
+        return None
+    if int(scan_perms) != scan_perms or scan_perms < 1:
+        raise RuntimeError(f'--scan-perms must be a whole number of at least 1, got {scan_perms}')
+    seed = 0 if scan_perm_seed is None else int(scan_perm_seed)
+    if not 0 <= seed < 1 << 64:
+        raise RuntimeError(f'--scan-perm-seed must lie in 0 .. 2^64 - 1, got {scan_perm_seed}')
+    split = lambda v: [x.strip() for x in v.split(',')] if isinstance(v, str) else list(v)
+    try:
+        alphas = [float(a) for a in split(DEFAULT_PERM_ALPHA if scan_perm_alpha is None else scan_perm_alpha)]
+    except ValueError:
+        raise RuntimeError(f'--scan-perm-alpha must be numbers separated by commas, got {scan_perm_alpha}') from None
+    if not alphas or not all(0.0 < a < 1.0 for a in alphas):
+        raise RuntimeError(f'--scan-perm-alpha: every level must lie in (0, 1), got {scan_perm_alpha}')
+    chromosomes = None
+    if scan_perm_chromosomes is not None:
+        chromosomes = [str(c) for c in split(scan_perm_chromosomes)]
+        if not chromosomes or '' in chromosomes:
+            raise RuntimeError(f'--scan-perm-chromosomes must be names separated by commas, got {scan_perm_chromosomes}')
+    return {'n_perm': int(scan_perms), 'seed': seed, 'alphas': alphas, 'chromosomes': chromosomes, 'pheno_file': scan_perm_pheno}
+
+
+def perm_plan(perm, phenotypes, chrom_names=None):
+    """(columns of `phenotypes` that are permuted, mask over `chrom_names`) of perm_options' dict: the names of
+    `--scan-perm-pheno` (one per line; default: every phenotype) in the table's order and the chromosomes of
+    `--scan-perm-chromosomes` (default: all).  A name the table or the grid does not have is refused.  Without
+    chrom_names only the phenotypes are looked at and the mask is None."""
+    columns = list(range(len(phenotypes)))
+    if perm['pheno_file'] is not None:
+        with open(perm['pheno_file']) as fh:
+            wanted = [line.strip() for line in fh if line.strip()]
+        unknown = [w for w in wanted if w not in phenotypes]
+        if unknown:
+            raise RuntimeError(f'{perm["pheno_file"]}: {unknown[0]} is no phenotype of the table')
+        if not wanted:
+            raise RuntimeError(f'{perm["pheno_file"]}: no phenotype is named')
+        columns = [p for p, name in enumerate(phenotypes) if name in set(wanted)]
+    if chrom_names is None:
+        return columns, None
+    mask = np.ones(len(chrom_names), dtype=bool)
+    if perm['chromosomes'] is not None:
+        unknown = [c for c in perm['chromosomes'] if c not in chrom_names]
+        if unknown:
+            raise RuntimeError(f'--scan-perm-chromosomes: {unknown[0]} is no chromosome of the grid '
+                               f'({", ".join(str(c) for c in chrom_names)})')
+        mask = np.array([str(c) in perm['chromosomes'] for c in chrom_names])
+    return columns, mask
+
+
 def check_scan_args(scan_pheno=None, scan_covar=None, scan_rankz=False, scan_out=None, scan_min_lod=None,
-                    scan_lod_matrix=False, grid_file=None, cohort=False):
-    """`--scan-pheno FILE [--scan-covar FILE] [--scan-rankz] [--scan-out PREFIX] [--scan-min-lod X] [--scan-lod-matrix]`:
+                    scan_lod_matrix=False, grid_file=None, cohort=False, scan_perms=None, scan_perm_seed=None,
+                    scan_perm_alpha=None, scan_perm_chromosomes=None, scan_perm_pheno=None):
+    """`--scan-pheno FILE [--scan-covar FILE] [--scan-rankz] [--scan-out PREFIX] [--scan-min-lod X] [--scan-lod-matrix]`
+    and the `--scan-perm*` options (perm_options):
     every option needs the phenotypes, the phenotypes need `--grid-file` and a cohort (`--sample-file`): one sample
     cannot be scanned.  Refused before a file is read."""
     given = {'--scan-covar': scan_covar, '--scan-rankz': scan_rankz or None, '--scan-out': scan_out,
-             '--scan-min-lod': scan_min_lod, '--scan-lod-matrix': scan_lod_matrix or None}
+             '--scan-min-lod': scan_min_lod, '--scan-lod-matrix': scan_lod_matrix or None, '--scan-perms': scan_perms,
+             '--scan-perm-seed': scan_perm_seed, '--scan-perm-alpha': scan_perm_alpha,
+             '--scan-perm-chromosomes': scan_perm_chromosomes, '--scan-perm-pheno': scan_perm_pheno}
+    perm_options(scan_perms, scan_perm_seed, scan_perm_alpha, scan_perm_chromosomes, scan_perm_pheno)
     if scan_pheno is None:
         for name, value in given.items():
             if value is not None:
@@ -224,16 +356,22 @@ def scan_design(ids, pheno, covar=None, use_rankz=False):
     return kept, y, z, names
 
 
-def write_scan(prefix, phenotypes, samples, covariates, chrom, pos, chrom_names, result, rank, min_lod=0.0):
+def write_scan(prefix, phenotypes, samples, covariates, chrom, pos, chrom_names, result, rank, min_lod=0.0, perm=None):
     """`<prefix>.scan.npz` and `<prefix>.scan.peaks.tsv`.  chrom / pos: per grid point, in the scan's point order;
-    chrom_names: the scan's chromosomes, as peak_lod's columns."""
+    chrom_names: the scan's chromosomes, as peak_lod's columns.  perm (with `--scan-perms`): `perm_max` [Pp, B] of the
+    phenotypes `columns`, `alphas`, `seed` and `mask` over chrom_names; the .npz gains the perm_* arrays and the peaks
+    file the columns `pvalue` and `threshold_<first level>`, NA where nothing was permuted.  Without it both files are
+    what they were before the permutations existed."""
     arrays = dict(phenotypes=np.array(phenotypes), samples=np.array(samples), covariates=np.array(covariates),
                   chrom=np.array(chrom), pos=np.asarray(pos, dtype=np.float64), rank=np.asarray(rank),
                   peak_lod=result['peak_lod'], peak_index=result['peak_index'])
     if 'lod' in result:
         arrays['lod'] = result['lod']
-    np.savez(f'{prefix}.scan.npz', **arrays)
     peak, index = result['peak_lod'], result['peak_index']
+    if perm is not None:
+        write_scan_perm(prefix, phenotypes, pos, chrom_names, peak, index, min_lod, perm, arrays)
+        return
+    np.savez(f'{prefix}.scan.npz', **arrays)
     with open(f'{prefix}.scan.peaks.tsv', 'w') as out:
         out.write('#phenotype\tchromosome\tposition\tlod\tgenome_wide_max\n')
         for p, name in enumerate(phenotypes):
@@ -245,30 +383,71 @@ def write_scan(prefix, phenotypes, samples, covariates, chrom, pos, chrom_names,
                               f'{int(c == top)}\n')
 
 
-def finish_scan(scan, prefix, ids, pheno, covar, use_rankz, chrom, pos, chrom_names, min_lod=None, lod_matrix=False):
+def write_scan_perm(prefix, phenotypes, pos, chrom_names, peak, index, min_lod, perm, arrays):
+    """write_scan's two files with the permutation results in them."""
+    columns, mask, alphas = list(perm['columns']), np.asarray(perm['mask'], dtype=bool), list(perm['alphas'])
+    threshold = perm_thresholds(perm['perm_max'], alphas)
+    pvalue = perm_pvalues(perm['perm_max'], peak[columns], selected=mask)
+    arrays.update(perm_max=perm['perm_max'], perm_phenotypes=np.array([phenotypes[p] for p in columns]),
+                  perm_alpha=np.array(alphas), perm_threshold=threshold, perm_seed=np.uint64(perm['seed']),
+                  perm_chromosomes=np.array([str(c) for c, on in zip(chrom_names, mask) if on]))
+    np.savez(f'{prefix}.scan.npz', **arrays)
+    row_of = {p: k for k, p in enumerate(columns)}
+    with open(f'{prefix}.scan.peaks.tsv', 'w') as out:
+        out.write(f'#phenotype\tchromosome\tposition\tlod\tgenome_wide_max\tpvalue\tthreshold_{repr(float(alphas[0]))}\n')
+        for p, name in enumerate(phenotypes):
+            on = [c for c in range(len(chrom_names)) if index[p, c] >= 0]
+            top = max(on, key=lambda c: (peak[p, c], -c)) if on else None
+            for c in on:
+                if peak[p, c] >= min_lod:
+                    judged = p in row_of and mask[c]
+                    out.write(f'{name}\t{chrom_names[c]}\t{repr(float(pos[index[p, c]]))}\t{repr(float(peak[p, c]))}\t'
+                              f'{int(c == top)}\t{repr(float(pvalue[row_of[p], c])) if judged else "NA"}\t'
+                              f'{repr(float(threshold[row_of[p], 0])) if judged else "NA"}\n')
+
+
+def finish_scan(scan, prefix, ids, pheno, covar, use_rankz, chrom, pos, chrom_names, min_lod=None, lod_matrix=False,
+                perm=None, stage_times=None):
     """prepare + run + the two files for the cohort `scan` holds, whose samples are `ids` in append order (every one with
-    its rows in the tables).  Returns GenomeScan.info() after the run."""
+    its rows in the tables).  perm: perm_options' dict, or None; with it the permutation pass runs after the scan on the
+    phenotypes and chromosomes it names and its wall-clock seconds go to stage_times['scan_perm'].  Returns
+    GenomeScan.info() after the run."""
     kept, y, z, names = scan_design(ids, pheno, covar, use_rankz)
     assert len(kept) == len(ids) == scan.n
+    if perm is not None:
+        columns, mask = perm_plan(perm, pheno[0], [str(c) for c in chrom_names])     # refused before the device runs
     scan.prepare(z, names)
     want_lod = bool(lod_matrix) or y.shape[1] * scan.M <= LOD_MATRIX_LIMIT
     result = scan.run(y, want_lod=want_lod)
     info = scan.info()
+    done = None
+    if perm is not None:
+        import time
+        t0 = time.perf_counter()
+        got = scan.permute(y[:, columns], perm['n_perm'], seed=perm['seed'], chromosomes=mask)
+        if stage_times is not None:
+            stage_times['scan_perm'] = stage_times.get('scan_perm', 0.0) + time.perf_counter() - t0
+        done = {'perm_max': got['perm_max'], 'columns': columns, 'mask': mask, 'alphas': perm['alphas'], 'seed': perm['seed']}
+        timing = scan.perm_info()
+        logger.info(f'scan: {perm["n_perm"]} permutations of {len(columns)} phenotypes; {timing["permute_ms"]:.1f} ms on the '
+                    f'device, {timing["product_ms"]:.1f} ms of them in the product kernel')
     write_scan(prefix, pheno[0], ids, names, chrom, pos, chrom_names, result, info['rank'],
-               0.0 if min_lod is None else min_lod)
+               0.0 if min_lod is None else min_lod, perm=done)
     logger.info(f'scan: {len(ids)} samples, {y.shape[1]} phenotypes, {scan.M} grid points; prepare '
                 f'{info["prepare_ms"]:.1f} ms, run {info["run_ms"]:.1f} ms on the device')
     return info
 
 
 def scan_tables(dosage_list, grid_file, pheno_file, covar_file=None, use_rankz=False, out=None, min_lod=None,
-                lod_matrix=False, device=0):
+                lod_matrix=False, device=0, scan_perms=None, scan_perm_seed=None, scan_perm_alpha=None,
+                scan_perm_chromosomes=None, scan_perm_pheno=None, stage_times=None):
     """`gbrs scan`: the cohort from dosage tables in `gbrs export` format (lines `id<TAB>dosage table`), rows in the grid
     file's order, without the HMM."""
     from .hmm import _match_lines, read_dosage_table
     from .postproc import read_grid
     if min_lod is not None and not min_lod >= 0.0:
         raise RuntimeError('--scan-min-lod must be a number that is not negative')
+    perm = perm_options(scan_perms, scan_perm_seed, scan_perm_alpha, scan_perm_chromosomes, scan_perm_pheno)
     grid = read_grid(grid_file)
     chrom_names = list(grid)
     points = [len(grid[c]) for c in chrom_names]
@@ -280,6 +459,8 @@ def scan_tables(dosage_list, grid_file, pheno_file, covar_file=None, use_rankz=F
         entries.append((sample_id, path))
     pheno = read_scan_pheno(pheno_file)
     covar = read_scan_covar(covar_file) if covar_file is not None else None
+    if perm is not None:
+        perm_plan(perm, pheno[0], [str(c) for c in chrom_names])          # refused before a dosage table is read
     kept, _, _, _ = scan_design([i for i, _ in entries], pheno, covar)
     if not kept:
         raise RuntimeError('scan: no sample of the dosage list has a phenotype row')
@@ -292,6 +473,6 @@ def scan_tables(dosage_list, grid_file, pheno_file, covar_file=None, use_rankz=F
         chrom = np.repeat(chrom_names, points)
         pos = np.concatenate([np.asarray(grid[c], dtype=np.float64) for c in chrom_names])
         return finish_scan(scan, out if out is not None else 'gbrs', [entries[k][0] for k in kept], pheno, covar, use_rankz,
-                           chrom, pos, chrom_names, min_lod, lod_matrix)
+                           chrom, pos, chrom_names, min_lod, lod_matrix, perm=perm, stage_times=stage_times)
     finally:
         scan.close()

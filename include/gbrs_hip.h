@@ -953,6 +953,37 @@ typedef struct gbrs_scan_info {
 /* rank is int32[M] of the last prepare, nullable; untouched when the handle is not prepared. */
 int gbrs_scan_info(gbrs_scan_t *scan, gbrs_scan_info_t *info, int32_t *rank);
 
+/* Permutation thresholds of the scan: perm_max[p][b], the largest LOD phenotype p reaches anywhere on the
+ * selected chromosomes under permutation b = 0 .. B-1.  Freedman-Lane: the residuals of the reduced model are permuted,
+ * not the dosage rows, so W of gbrs_scan_prepare serves every permutation.  Per (p, b):
+ *   y~ = y - qz qz' y, as gbrs_scan_run forms it (the same kernel);
+ *   key of sample s: k_s = (w0 << 32) | w1, the words 0 and 1 of Philox4x32-10 on the counter
+ *   (s & 0xFFFFFFFF, s >> 32, b & 0xFFFFFFFF, b >> 32) with the key (seed & 0xFFFFFFFF, seed >> 32);
+ *   perm_b(s) = the rank of (k_s, s) among the n pairs in lexicographic order: it depends on (seed, b, n) alone and is the
+ *   same for every phenotype;
+ *   y*[s] = y~[perm_b(s)],  y*~ = y* - qz qz' y*,  rss0* = |y*~|^2,  ess*[m] = |W_m y*~|^2, and the LOD by gbrs_scan_run's
+ *   formula with its two edge rules;
+ *   perm_max[p][b] = the maximum over the grid points of the chromosomes c with chrom_mask[c] != 0 (NULL: all).
+ * pheno is double[n][P] as for gbrs_scan_run (a constant column goes in as zeros and gives 0.0 throughout), perm_max
+ * double[P][B], perm_index int32[B][n] the permutations themselves (nullable).  Nothing per permutation is uploaded and
+ * no LOD leaves the device: the columns p B + b pass through the product kernel in gbrs_scan_run's chunks of 512, and
+ * the device holds y~ [P][n_ld], the permutations [B][n], perm_max and one chunk's buffers next to what the handle
+ * holds.  The ranks are found by counting, n^2 comparisons per permutation.  perm_max[p][b] is the same bits for any P,
+ * B > b, column and chunk, and however the cohort was appended.  GBRS_ERR_INVALID before gbrs_scan_prepare, for P < 1,
+ * for B < 1, for a mask that selects no grid point and for a phenotype value that is not finite (the message names the
+ * entry); the outputs are untouched on failure.  The call allocates and frees its own buffers: what the handle holds,
+ * gbrs_scan_run's bits and gbrs_scan_info_t are as before. */
+int gbrs_scan_permute(gbrs_scan_t *scan, int64_t P, const double *pheno, int64_t B, uint64_t seed,
+                      const uint8_t *chrom_mask /* [n_chrom], nullable */, double *perm_max, int32_t *perm_index);
+
+typedef struct gbrs_scan_perm_info {
+    int64_t  P, B;               /* of the last gbrs_scan_permute (0: none yet)                                  */
+    double   last_permute_ms;    /* device time of the pass: uploads, projections, ranks, all chunks            */
+    double   last_product_ms;    /* of that, the product kernel alone, summed over the chunks                   */
+    uint64_t peak_device_bytes;  /* what the handle held during the pass, the call's own buffers included       */
+} gbrs_scan_perm_info_t;
+int gbrs_scan_perm_info(gbrs_scan_t *scan, gbrs_scan_perm_info_t *info);
+
 /* ------------------------------------------------------------------------------------------
  * Report text (host side, no device work): the `locus <haplotypes> total [notes]` tables of
  * EMfactory.report_read_counts / report_depths (emase/EMfactory.py:289-380).

@@ -54,19 +54,20 @@ def run_samples(H, style, samples, p0=None):
     return hmm, p0
 
 
-def assert_equals_the_restatement(hmm, p0, n):
+def assert_equals_the_restatement(hmm, p0, n, samples=None, with_xi=None):
     """Every output of every sample and chromosome; xi for the first, the middle and the last sample (the pass takes one
-    sample at a time: the index only moves the rows it reads).  Returns the worst differences met."""
+    sample at a time: the index only moves the rows it reads).  samples: the samples compared (default: all n);
+    with_xi: those among them whose xi is compared (default: those three).  Returns the worst differences met."""
     got = hmm.diagnostics()
     ch, iv = restate.change_table(hmm.H), restate.init_vec(hmm.H)
     worst = dict(xo=0.0, pswitch=0.0, xi=0.0, errlod=0.0)
-    with_xi = sorted({0, n // 2, n - 1})
+    with_xi = sorted({0, n // 2, n - 1}) if with_xi is None else list(with_xi)
     for ci, c in enumerate(p0.chroms):
         genes = len(p0.gene_ids[c])
         for k in NAMES:
             assert got[k][ci].shape == (n, genes - 1 if k in ("xo", "pswitch") else genes), (k, c)
         assert got["maxmarg"][ci].dtype == np.int32
-        for s in range(n):
+        for s in (range(n) if samples is None else samples):
             at = f"sample {s} chromosome {c}"
             own = hmm.get(ci, sample=s, want=("alpha", "beta", "eprob", "gamma"))
             want = restate.all_of(own, p0.tprob[c], ch, iv)

@@ -57,17 +57,17 @@ def run_samples(H, style, samples, p0=None):
     return hmm, p0
 
 
-def assert_equals_the_restatement(hmm, p0, n, seed, streams=None):
-    """Every DRAWS count against the restatement of max(DRAWS) draws (a draw is keyed by its number, so fewer draws are a
-    prefix).  Returns the smallest margin met."""
-    K = max(DRAWS)
+def assert_equals_the_restatement(hmm, p0, n, seed, streams=None, samples=None, draws=DRAWS):
+    """Every count of `draws` against the restatement of max(draws) draws (a draw is keyed by its number, so fewer draws
+    are a prefix), for the given samples of the launch (default: all n).  Returns the smallest margin met."""
+    K = max(draws)
     table = restate.change_table(hmm.H)
-    got = {k: hmm.sample_paths(k, seed=seed, streams=streams) for k in DRAWS}
+    got = {k: hmm.sample_paths(k, seed=seed, streams=streams) for k in draws}
     smallest = np.inf
-    for k in DRAWS:
+    for k in draws:
         assert got[k]["degenerate"] == 0
         assert got[k]["changes"].shape == (n, k, len(p0.chroms)) and got[k]["changes"].dtype == np.int32
-    for s in range(n):
+    for s in (range(n) if samples is None else samples):
         stream = s if streams is None else streams[s]
         for ci, c in enumerate(p0.chroms):
             alpha = hmm.get(ci, sample=s, want=("alpha",))["alpha"]
@@ -75,7 +75,7 @@ def assert_equals_the_restatement(hmm, p0, n, seed, streams=None):
             genes, whole = restate.comparable(margins, FLOOR)
             smallest = min(smallest, float(margins.min()))
             assert degenerate == 0
-            for k in DRAWS:
+            for k in draws:
                 at = f"sample {s} chromosome {c} K={k}"
                 dev = got[k]["paths"][ci]
                 assert dev.shape == (n, k, alpha.shape[1]) and dev.dtype == np.uint8, at

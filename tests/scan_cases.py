@@ -20,8 +20,13 @@ UNDECIDED = (1e-13, 1e-7)                  # a pivot ratio d_j / G_jj in this ba
 MEASURED_FLOOR = 1.91e-14
 MEASURED_SATURATED = {'H3-n7-c4-P63-M17': 1.21e-10, 'H8-n9-c1-P64-M17': 2.82e-9, 'H9-n13-c4-P65-M17': 6.81e-11,
                       'H10-n11-c1-P1-M17': 4.32e-13, 'H16-n18-c2-P130-M17': 1.43e-8}
+# The same figure of every case of LARGE_CASES, each its own: the absolute rounding of (n / 2) log10(rss0 / rss1) grows
+# with n, and the last degree of freedom of H17-n19 and H16-n80-c64 costs what it costs above.
+MEASURED_LARGE = {'H8-n256-c1-P1-M17': 1.18e-14, 'H8-n257-c2-P65-M17': 9.83e-14, 'H9-n512-c2-P130-M75': 3.93e-13,
+                  'H4-n129-c2-P64-M17': 5.54e-14, 'H17-n33-c1-P63-M17': 5.46e-15, 'H17-n300-c4-P65-M17': 9.56e-14,
+                  'H17-n19-c2-P1-M17': 5.5e-13, 'H8-n130-c64-P64-M17': 3.63e-14, 'H16-n80-c64-P1-M17': 1.75e-12}
 # The device against each host route: ten times the measured floor - the device adds the samples in another, fixed order
-# (up to 70 of them here) and fuses nothing.
+# (up to 70 of them in CASES, up to 512 in LARGE_CASES) and fuses nothing.
 DEVICE_FACTOR = 10
 # What test_scan_cpu.py allows the two host routes between themselves: the measured floor with headroom for another
 # LAPACK build's rounding.  It bounds nothing on the device.
@@ -29,7 +34,7 @@ CPU_HEADROOM = 1.3
 
 
 def measured_floor(case):
-    return max(MEASURED_FLOOR, MEASURED_SATURATED.get(case_id(case), 0.0))
+    return max(MEASURED_FLOOR, MEASURED_SATURATED.get(case_id(case), 0.0), MEASURED_LARGE.get(case_id(case), 0.0))
 
 
 def cpu_bound(case):
@@ -60,6 +65,19 @@ CASES = [
     (16, 70, 4, 65, POINTS),
     (16, 18, 2, 130, POINTS),
     (16, 32, 1, 63, POINTS),
+]
+# Cohorts past the 256-thread stride of scan_prepare_kernel's per-sample solve, the founder limit (H = 17: Hx = HP = 16,
+# no padding row) and the covariate limit (c = 64), apart from CASES so that what is measured over CASES stays as it is.
+LARGE_CASES = [
+    (8, 256, 1, 1, POINTS),                # the solve's stride exactly full; 8 K chunks
+    (8, 257, 2, 65, POINTS),               # one sample past it; 9 chunks
+    (9, 512, 2, 130, (1, 65, 9)),          # two full laps of the solve; 16 chunks; Hx = HP = 8
+    (4, 129, 2, 64, POINTS),               # a third lap of the lane sums (s = lane + 128)
+    (17, 33, 1, 63, POINTS),               # H = 17
+    (17, 300, 4, 65, POINTS),              # the same with the second lap of the solve
+    (17, 19, 2, 1, POINTS),                # H = 17 at n = c + H
+    (8, 130, 64, 64, POINTS),              # c = 64
+    (16, 80, 64, 1, POINTS),               # c = 64 at n = c + H
 ]
 
 

@@ -25,6 +25,22 @@ SEED_HIGH = (1 << 40) + 977               # a seed whose upper word is in use
 # permuted residual comes to the design's span (scan_cases.MEASURED_SATURATED), so those stay out of the tolerance
 # tests and in the exact ones.  Pivot ratios depend on D alone: no grid point is undecided here either.
 ORDINARY = [case for case in cases.CASES if case[1] > case[2] + case[0]]
+# The same of scan_cases.LARGE_CASES, and the same figure of each (B = N_PERM, SEED), its own as in
+# scan_cases.MEASURED_LARGE: the absolute rounding of (n / 2) log10(rss0 / rss1) grows with n.
+ORDINARY_LARGE = [case for case in cases.LARGE_CASES if case[1] > case[2] + case[0]]
+MEASURED_PERM_LARGE = {'H8-n256-c1-P1-M17': 5.95e-14, 'H8-n257-c2-P65-M17': 1.23e-13, 'H9-n512-c2-P130-M75': 4.16e-13,
+                       'H4-n129-c2-P64-M17': 4.34e-14, 'H17-n33-c1-P63-M17': 5.19e-15, 'H17-n300-c4-P65-M17': 8.65e-14,
+                       'H8-n130-c64-P64-M17': 3.66e-14}
+# The event ring's pass (test_scan_perm_gpu.py): the first RING_PHENO phenotypes of RING under RING_PERM permutations
+# are nine chunks of 512 columns.  The figure is the same quantity over all 4,608 columns of that very run, and the
+# device is held to scan_cases.DEVICE_FACTOR times it alone.
+RING, RING_PHENO, RING_PERM = (3, 33, 1, 65, cases.POINTS), 9, 512
+MEASURED_RING = 8.66e-15
+
+
+def measured_floor_perm(case):
+    """As scan_cases.measured_floor: the larger of the floor over ORDINARY and the case's own figure."""
+    return max(MEASURED_FLOOR_PERM, MEASURED_PERM_LARGE.get(cases.case_id(case), 0.0))
 
 
 def permutations(seed, B, n):
@@ -68,6 +84,18 @@ def expected(case, B=N_PERM, seed=SEED):
     D, Z, Y, _ = cases.build(case)
     perm = permutations(seed, B, case[1])
     columns = permuted_columns(Z, Y, perm)
+    out = (perm, cases.scan_rule(D, Z, columns)[0], cases.scan_lstsq(D, Z, columns)[0])
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def expected_ring():
+    """expected() of the event ring's pass: RING's first RING_PHENO phenotypes, RING_PERM permutations under SEED."""
+    D, Z, Y, _ = cases.build(RING)
+    perm = permutations(SEED, RING_PERM, RING[1])
+    columns = permuted_columns(Z, Y[:, :RING_PHENO], perm)
     out = (perm, cases.scan_rule(D, Z, columns)[0], cases.scan_lstsq(D, Z, columns)[0])
     for a in out:
         a.setflags(write=False)

@@ -6,7 +6,7 @@ import pytest
 import scan_cases as cases
 
 
-@pytest.mark.parametrize("case", cases.CASES, ids=cases.case_id)
+@pytest.mark.parametrize("case", cases.CASES + cases.LARGE_CASES, ids=cases.case_id)
 def test_the_rule_agrees_with_lstsq(case):
     """The restatement of the rule against np.linalg.lstsq, which knows nothing of it: the LODs within the case's measured floor (with headroom), the
     ranks equal, and the constructed points have the ranks their construction says."""
@@ -35,7 +35,7 @@ def test_no_fixture_has_an_undecided_pivot():
     lo, hi = cases.UNDECIDED
     undecided = total = 0
     smallest_kept, largest_skipped = np.inf, 0.0
-    for case in cases.CASES:
+    for case in cases.CASES + cases.LARGE_CASES:
         ratios = cases.expected(case)[2]
         with np.errstate(invalid="ignore"):
             undecided += int(((ratios >= lo) & (ratios <= hi)).any(axis=1).sum())

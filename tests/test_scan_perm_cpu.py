@@ -7,7 +7,7 @@ import scan_cases as cases
 import scan_perm_restate as restate
 
 
-@pytest.mark.parametrize("n", [1, 3, 64, 65, 300])
+@pytest.mark.parametrize("n", [1, 3, 64, 65, 300, 256, 257, 512, 513])
 def test_every_row_is_a_permutation_that_depends_on_seed_row_and_n_alone(n):
     few, many = restate.permutations(restate.SEED, 3, n), restate.permutations(restate.SEED, 8, n)
     assert many.dtype == np.int32 and many.shape == (8, n)
@@ -40,16 +40,29 @@ def test_with_the_intercept_alone_it_is_a_plain_scan_of_the_permuted_phenotypes(
     assert worst <= cases.CPU_HEADROOM * restate.MEASURED_FLOOR_PERM
 
 
-@pytest.mark.parametrize("case", restate.ORDINARY, ids=cases.case_id)
+@pytest.mark.parametrize("case", restate.ORDINARY + restate.ORDINARY_LARGE, ids=cases.case_id)
 def test_the_two_host_routes_agree_on_the_permuted_columns(case):
+    """Within the floor over ORDINARY, a large case within its own recorded figure (measured_floor_perm is
+    MEASURED_FLOOR_PERM for every case of ORDINARY), with the headroom."""
     perm, rule, lstsq = restate.expected(case)
     assert perm.shape == (restate.N_PERM, case[1]) and rule.shape == lstsq.shape == (case[3] * restate.N_PERM, sum(case[4]))
     worst = cases.deviation(rule, lstsq)
     print(f"DEVIATION scan_rule against scan_lstsq on permuted columns, {cases.case_id(case)}: {worst:.3g}, largest LOD "
           f"{rule[np.isfinite(rule)].max():.3g}")
-    assert worst <= cases.CPU_HEADROOM * restate.MEASURED_FLOOR_PERM
+    assert worst <= cases.CPU_HEADROOM * restate.measured_floor_perm(case)
     by_rule, by_lstsq = restate.expected_max(case)
     assert by_rule.shape == (case[3], restate.N_PERM) and cases.deviation(by_rule, by_lstsq) <= worst
+
+
+def test_the_two_host_routes_agree_on_the_columns_of_the_event_ring():
+    """All 4,608 columns of the pass that wraps the device's event ring, not only their maxima."""
+    perm, rule, lstsq = restate.expected_ring()
+    assert perm.shape == (restate.RING_PERM, restate.RING[1])
+    assert rule.shape == lstsq.shape == (restate.RING_PHENO * restate.RING_PERM, sum(restate.RING[4])) and rule.shape[0] > 8 * 512
+    np.testing.assert_array_equal(perm[:restate.N_PERM], restate.expected(restate.RING)[0])
+    worst = cases.deviation(rule, lstsq)
+    print(f"DEVIATION scan_rule against scan_lstsq on the event ring's columns: {worst:.3g}, largest LOD {rule.max():.3g}")
+    assert np.isfinite(rule).all() and worst <= cases.CPU_HEADROOM * restate.MEASURED_RING
 
 
 def test_the_ordinary_cases_are_those_with_more_than_one_residual_degree():
@@ -57,6 +70,11 @@ def test_the_ordinary_cases_are_those_with_more_than_one_residual_degree():
     assert all(n == c + H for H, n, c, _, _ in left_out) and len(left_out) == 6 and len(restate.ORDINARY) == 9
     assert {c[0] for c in restate.ORDINARY} == {2, 3, 4, 8, 9, 10, 16} and {c[2] for c in restate.ORDINARY} == {1, 2, 4}
     assert any(65 in c[4] for c in restate.ORDINARY)
+    left_out = [c for c in cases.LARGE_CASES if c not in restate.ORDINARY_LARGE]
+    assert [(H, n, c) for H, n, c, _, _ in left_out] == [(17, 19, 2), (16, 80, 64)] and len(restate.ORDINARY_LARGE) == 7
+    assert sorted(restate.MEASURED_PERM_LARGE) == sorted(cases.case_id(c) for c in restate.ORDINARY_LARGE)
+    assert sorted(cases.MEASURED_LARGE) == sorted(cases.case_id(c) for c in cases.LARGE_CASES)
+    assert not set(cases.LARGE_CASES) & set(cases.CASES)
 
 
 def test_thresholds_are_order_statistics():

@@ -22,10 +22,10 @@ TOL = cases.DEVICE_FACTOR * restate.MEASURED_FLOOR_PERM
 BITS = (8, 70, 4, 130, (1, 65, 9))
 
 
-@pytest.mark.parametrize("n", [3, 31, 32, 33, 63, 64, 65, 70, 300])
+@pytest.mark.parametrize("n", [3, 31, 32, 33, 63, 64, 65, 70, 300, 256, 257, 512, 513])
 def test_the_permutations_equal_the_restatement(n):
-    """Both sides of the K chunk (32), of a wavefront (64) and of the rank kernel's 256-sample tile; B = 1 and 7; a seed
-    whose upper word is in use."""
+    """Both sides of the K chunk (32), of a wavefront (64) and of the rank kernel's 256-sample tile - exactly one tile,
+    one sample past it, exactly two and one past two; B = 1 and 7; a seed whose upper word is in use."""
     from gbrs_amd.scan import GenomeScan
     rng = np.random.default_rng(n)
     scan = GenomeScan(2, [3])
@@ -40,8 +40,10 @@ def test_the_permutations_equal_the_restatement(n):
     scan.close()
 
 
-@pytest.mark.parametrize("case", restate.ORDINARY, ids=cases.case_id)
+@pytest.mark.parametrize("case", restate.ORDINARY + restate.ORDINARY_LARGE, ids=cases.case_id)
 def test_perm_max_against_both_host_routes(case):
+    """A case of ORDINARY within TOL, a large case within the device factor of its own recorded floor (measured_floor_perm
+    is MEASURED_FLOOR_PERM for every case of ORDINARY)."""
     _, _, Y, _ = cases.build(case)
     perm = restate.expected(case)[0]
     by_rule, by_lstsq = restate.expected_max(case)
@@ -50,10 +52,12 @@ def test_perm_max_against_both_host_routes(case):
     timing, info = scan.perm_info(), scan.info()
     scan.close()
     np.testing.assert_array_equal(got["perm_index"], perm)
+    tol = cases.DEVICE_FACTOR * restate.measured_floor_perm(case)
+    assert tol == TOL or case in restate.ORDINARY_LARGE
     worst, worst_ls = cases.deviation(got["perm_max"], by_rule), cases.deviation(got["perm_max"], by_lstsq)
-    print(f"DEVIATION device perm_max against scan_rule {worst:.3g}, against scan_lstsq {worst_ls:.3g}, tolerance {TOL:.3g}, "
+    print(f"DEVIATION device perm_max against scan_rule {worst:.3g}, against scan_lstsq {worst_ls:.3g}, tolerance {tol:.3g}, "
           f"{cases.case_id(case)}")
-    assert worst <= TOL and worst_ls <= TOL
+    assert worst <= tol and worst_ls <= tol
     assert (timing["P"], timing["B"]) == (case[3], restate.N_PERM)
     assert timing["permute_ms"] >= timing["product_ms"] > 0 and timing["peak_device_bytes"] > info["device_bytes"]
     assert info["run_ms"] == 0.0                                   # the pass is not a run: gbrs_scan_info_t is as it was

@@ -80,47 +80,7 @@ __device__ __forceinline__ double reduce_partials(const double *__restrict__ p, 
     return block_sum(v, lds);
 }
 
-// Element-parallel M-step for H a power of two: one thread per (locus, haplotype), the H lanes of
-// a locus are adjacent, so every access is a coalesced 8-byte stream; per-locus totals by shuffles.
-// A comes from `acc` (tile epilogues for single-tile loci, gather_kernel for the rest; loci without
-// any read stay 0).  Block sums of theta before/after go to RED_BLOCKS accumulator slots.
-template <int MODE>
-__global__ void __launch_bounds__(RED_THREADS)
-mstep_elem_kernel(uint32_t L, uint32_t H, double *__restrict__ theta, const double *__restrict__ acc,
-                  const double *__restrict__ acc_extra, const double *__restrict__ eff_len,
-                  double *__restrict__ counts, double *__restrict__ tot_prev, double *__restrict__ tot_new,
-                  double *__restrict__ msums, uint32_t cap, const EmScalars *__restrict__ sc) {
-    __shared__ double lds[16];
-    if (MODE == 0 && sc->stop) return;
-    const uint64_t n = (uint64_t)L * H;
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    double t = 0.0, tn = 0.0;
-    if (i < n) {
-        const uint32_t l = (uint32_t)(i / H), h = (uint32_t)(i & (H - 1));
-        double a = acc[i];
-        if (acc_extra) a += acc_extra[i];
-        t = MODE == 0 ? theta[i] : 1.0;
-        const double c = t * a;
-        tn = eff_len ? c / eff_len[i] : c;
-        counts[i] = c;
-        theta[i] = tn;
-        double tp = t, tq = tn;
-        for (uint32_t off = 1; off < H; off <<= 1) {
-            tp += __shfl_xor(tp, off, WAVE);
-            tq += __shfl_xor(tq, off, WAVE);
-        }
-        if (h == 0) {
-            tot_prev[l] = tp;
-            tot_new[l] = tq;
-        }
-    }
-    double a = block_sum(t, lds);
-    double b = block_sum(tn, lds);
-    if (threadIdx.x == 0) {                 // one slot per workgroup: no atomics, and a fixed summation order
-        msums[blockIdx.x] = a;
-        msums[cap + blockIdx.x] = b;
-    }
-}
+#include "em_mstep.inc"      // mstep_elem_kernel<MODE, H>, mstep_gather_kernel<H, EXTRA, LEN>: H a power of two
 
 constexpr int ERR_BLOCKS = 64;
 // err_sum = sum_l | tot_new[l]*1e6/S_new - tot_prev[l]*1e6/S_prev |  (EMfactory.py:268-278), then the
@@ -850,184 +810,49 @@ int em_estep(gbrs_em *em, const EmStepRoute &r, int model = 4, hipEvent_t after_
     return GBRS_OK;
 }
 
-// Gather + M-step in one launch (tile layout, H a power of two, single GPU): an element of a locus
-// with at most one slot takes A straight from `acc` (written by the tile epilogue), a locus with a
-// few slots sums them in place, and the loci with many slots get one workgroup each (the leading
-// workgroups), which reduces the slots in fixed order and applies the M-step to that locus itself.
-// No intermediate A vector is written for the gathered loci and there is one launch less per step.
-//
-// Round 3: the launch was ~13 us of a ~115 us iteration and none of it was bandwidth - it is the number of
-// DEPENDENT global loads on its longest path (a round trip is ~0.7 us): stop flag -> locus list -> slot_ptr ->
-// four slot rows at a time -> ... .  Now every path is two round trips: (1) the stop flag, the (locus, first row,
-// end row) record of a heavy / light locus, or class, theta, A and length of a plain element, all in flight
-// together; (2) all the slot rows of the locus at once (a light locus has at most HEAVY_SLOTS of them; a heavy
-// workgroup takes 16 rows per thread and round).  The stop flag only guards the stores.
-#ifndef GBRS_MSTEP_EPT
-#define GBRS_MSTEP_EPT 4
-#endif
-constexpr int MSTEP_EPT = GBRS_MSTEP_EPT;       // elements per thread of the elementwise workgroups (measured 1, 2, 4, 8)
-constexpr int HEAVY_ROWS = 16;     // slot rows a thread of a heavy workgroup has in flight
-__global__ void __launch_bounds__(RED_THREADS)
-mstep_gather_kernel(uint32_t L, uint32_t H, uint32_t HP, uint32_t heavy_blocks, uint32_t light_blocks, uint32_t n_light,
-                    const uint32_t *__restrict__ heavy_range, const uint32_t *__restrict__ light_range,
-                    const uint8_t *__restrict__ locus_class,
-                    const double *__restrict__ slot_sums, const double *__restrict__ acc,
-                    const double *__restrict__ acc_extra, double *__restrict__ theta,
-                    const double *__restrict__ eff_len, double *__restrict__ counts, double *__restrict__ tot_prev,
-                    double *__restrict__ tot_new, double *__restrict__ msums, uint32_t cap,
-                    const EmScalars *__restrict__ sc) {
-    __shared__ double lds[16];
-    __shared__ double heavy_part[RED_THREADS / 64][16];
-    const int stop = sc->stop;          // scalar load, in flight beside the vector loads below; looked at before the stores
-    double t = 0.0, tn = 0.0;
-    if (blockIdx.x < heavy_blocks) {
-        // one workgroup per many-slot locus: the largest loci of a deep sample have hundreds of slots whose rows
-        // were written by tiles all over the chip a moment ago
-        const uint32_t l = heavy_range[3 * blockIdx.x], k0 = heavy_range[3 * blockIdx.x + 1], k1 = heavy_range[3 * blockIdx.x + 2];
-        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-        const uint32_t h = threadIdx.x & (HP - 1), sub = threadIdx.x / HP, nsub = blockDim.x / HP;
-        const bool live = h < H;
-        const size_t il = (size_t)l * H + (live ? h : 0);
-        const double t_old = theta[il], ax = acc_extra ? acc_extra[il] : 0.0, ln = eff_len ? eff_len[il] : 1.0;
-        double a = 0.0;
-        for (uint32_t k = k0 + sub; k < k1; k += HEAVY_ROWS * nsub) {          // fixed order: rounds, then rows of a round
-            double r[HEAVY_ROWS];
-#pragma unroll
-            for (int m = 0; m < HEAVY_ROWS; ++m) {
-                const uint32_t km = k + (uint32_t)m * nsub;
-                r[m] = (live && km < k1) ? slot_sums[(size_t)km * H + h] : 0.0;
-            }
-#pragma unroll
-            for (int w = 1; w < HEAVY_ROWS; w <<= 1)
-#pragma unroll
-                for (int m = 0; m + w < HEAVY_ROWS; m += 2 * w) r[m] += r[m + w];
-            a += r[0];
-        }
-        for (uint32_t off = HP; off < 64; off <<= 1) a += __shfl_xor(a, off, WAVE);
-        if (lane < (int)HP) heavy_part[wv][lane] = a;        // the wavefronts' partial sums, added in a fixed order
-        __syncthreads();
-        if (wv == 0) {
-            a = 0.0;
-            if (lane < (int)HP)
-                for (uint32_t w2 = 0; w2 < blockDim.x / 64; ++w2) a += heavy_part[w2][lane];
-            const bool mine = lane < (int)HP && live;
-            if (mine) {
-                t = t_old;
-                const double c = t * (a + ax);
-                tn = eff_len ? c / ln : c;
-                if (!stop) theta[il] = tn;             // (the expected counts are theta' * len: made when asked for)
-            }
-            double tp = t, tq = tn;                       // lanes 0 .. H-1 hold the locus, the others 0
-            for (uint32_t off = 1; off < HP; off <<= 1) {
-                tp += __shfl_xor(tp, off, WAVE);
-                tq += __shfl_xor(tq, off, WAVE);
-            }
-            if (lane == 0 && !stop) {
-                tot_prev[l] = tp;
-                tot_new[l] = tq;
-            }
-        }
-    } else if (blockIdx.x < heavy_blocks + light_blocks) {
-        // one thread per (light locus, haplotype): the locus's 2..HEAVY_SLOTS slot rows all at once, added in slot order
-        const uint64_t i = (uint64_t)(blockIdx.x - heavy_blocks) * blockDim.x + threadIdx.x;
-        const bool live = i < (uint64_t)n_light * H;
-        const uint32_t li = live ? (uint32_t)(i / H) : 0, h = (uint32_t)(i & (H - 1));
-        const uint32_t l = light_range[3 * li], k0 = light_range[3 * li + 1], k1 = light_range[3 * li + 2];
-        const size_t il = (size_t)l * H + h;
-        const double t_old = theta[il], ax = acc_extra ? acc_extra[il] : 0.0, ln = eff_len ? eff_len[il] : 1.0;
-        double r[HEAVY_SLOTS];
-#pragma unroll
-        for (int m = 0; m < HEAVY_SLOTS; ++m) r[m] = k0 + m < k1 ? slot_sums[(size_t)(k0 + m) * H + h] : 0.0;
-        double a = ax;
-#pragma unroll
-        for (int m = 0; m < HEAVY_SLOTS; ++m) a += r[m];
-        if (live) {
-            t = t_old;
-            const double c = t * a;
-            tn = eff_len ? c / ln : c;
-            if (!stop) theta[il] = tn;
-        }
-        double tp = t, tq = tn;                           // the H lanes of a locus are adjacent
-        for (uint32_t off = 1; off < H; off <<= 1) {
-            tp += __shfl_xor(tp, off, WAVE);
-            tq += __shfl_xor(tq, off, WAVE);
-        }
-        if (live && h == 0 && !stop) {
-            tot_prev[l] = tp;
-            tot_new[l] = tq;
-        }
-    } else {
-        // MSTEP_EPT elements per thread of the loci with at most one slot: class, theta, A and length in one batch of
-        // loads, no second round trip
-        const uint64_t n = (uint64_t)L * H;
-        const uint64_t i0 = (uint64_t)(blockIdx.x - heavy_blocks - light_blocks) * MSTEP_EPT * blockDim.x + threadIdx.x;
-        uint32_t cls[MSTEP_EPT];
-        double av[MSTEP_EPT], tv[MSTEP_EPT], lv[MSTEP_EPT];
-#pragma unroll
-        for (int e = 0; e < MSTEP_EPT; ++e) {
-            const uint64_t i = i0 + (uint64_t)e * blockDim.x;
-            cls[e] = 3;
-            av[e] = tv[e] = 0.0;
-            lv[e] = 1.0;
-            if (i < n) {
-                cls[e] = locus_class[(uint32_t)(i / H)];
-                tv[e] = theta[i];
-                av[e] = acc[i];                           // one slot: stored by its tile; none: stays 0
-                if (acc_extra) av[e] += acc_extra[i];
-                if (eff_len) lv[e] = eff_len[i];
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < MSTEP_EPT; ++e) {
-            const uint64_t i = i0 + (uint64_t)e * blockDim.x;
-            const uint32_t l = (uint32_t)(i / H), h = (uint32_t)(i & (H - 1));
-            const bool mine = i < n && cls[e] < 2;        // classes 2 and 3: the workgroups above
-            double te = 0.0, tne = 0.0;
-            if (mine) {
-                te = tv[e];
-                const double c = te * av[e];
-                tne = eff_len ? c / lv[e] : c;
-                if (!stop) theta[i] = tne;
-            }
-            double tp = te, tq = tne;                     // the H lanes of a locus are adjacent, same class
-            for (uint32_t off = 1; off < H; off <<= 1) {
-                tp += __shfl_xor(tp, off, WAVE);
-                tq += __shfl_xor(tq, off, WAVE);
-            }
-            if (mine && h == 0 && !stop) {
-                tot_prev[l] = tp;
-                tot_new[l] = tq;
-            }
-            t += te;
-            tn += tne;
-        }
-    }
-    const double a = block_sum(t, lds);
-    const double b = block_sum(tn, lds);
-    if (threadIdx.x == 0 && !stop) {
-        msums[blockIdx.x] = a;
-        msums[cap + blockIdx.x] = b;
-    }
-}
-
-int em_launch_mstep_gather(gbrs_em *em, const EmStepRoute &r) {
+// The fused launch: the elementwise workgroups take MSTEP_EPT pairs of haplotypes per thread (one haplotype at H = 1),
+// a light locus takes H / 2 threads.  msum_cap (gbrs_em_create) covers this grid: it is never larger than one workgroup per
+// RED_THREADS elements plus one per RED_THREADS light elements plus one per heavy locus.
+template <int H, bool EXTRA, bool LEN>
+void em_launch_mstep_gather_h(gbrs_em *em) {
     const TileLayout &tl = em->tl;
-    uint32_t HP = 1;
-    while (HP < em->H) HP <<= 1;
-    const uint64_t n = (uint64_t)em->L * em->H;
-    const unsigned elem_blocks = (unsigned)((n + (uint64_t)RED_THREADS * MSTEP_EPT - 1) / ((uint64_t)RED_THREADS * MSTEP_EPT));
+    const uint64_t npair = (uint64_t)em->L * MstepRow<H>::LANES, per = (uint64_t)RED_THREADS * MSTEP_EPT;
+    const unsigned elem_blocks = (unsigned)((npair + per - 1) / per);
     const unsigned heavy_blocks = (unsigned)tl.n_heavy;         // one workgroup per many-slot locus
-    const unsigned light_blocks = (unsigned)((tl.n_light * em->H + RED_THREADS - 1) / RED_THREADS);
+    const unsigned light_blocks = (unsigned)((tl.n_light * MstepRow<H>::LANES + RED_THREADS - 1) / RED_THREADS);
     em->msum_blocks = elem_blocks + heavy_blocks + light_blocks;
-    hipLaunchKernelGGL(mstep_gather_kernel, dim3(em->msum_blocks), dim3(RED_THREADS), 0, em->stream, em->L,
-                       em->H, HP, heavy_blocks, light_blocks, (uint32_t)tl.n_light, tl.heavy_range.p, tl.light_range.p,
-                       tl.locus_class.p, tl.partials.p, em->acc.p,
-                       r.long_rows != EmLongRows::None ? tl.acc_extra.p : (const double *)nullptr, em->theta.p,
-                       em->has_len ? em->eff_len.p : (const double *)nullptr, em->counts.p, em->tot_prev.p,
-                       em->tot_new.p, em->msums.p, em->msum_cap, em->scalars.p);
+    hipLaunchKernelGGL((mstep_gather_kernel<H, EXTRA, LEN>), dim3(em->msum_blocks), dim3(RED_THREADS), 0, em->stream, em->L,
+                       heavy_blocks, light_blocks, (uint32_t)tl.n_light, tl.heavy_range.p, tl.light_range.p,
+                       tl.locus_class.p, tl.partials.p, em->acc.p, EXTRA ? tl.acc_extra.p : (const double *)nullptr,
+                       em->theta.p, LEN ? em->eff_len.p : (const double *)nullptr, em->tot_prev.p, em->tot_new.p,
+                       em->msums.p, em->msum_cap, em->scalars.p);
+}
+template <int H>
+void em_launch_mstep_gather_opts(gbrs_em *em, bool extra) {
+    if (extra) em->has_len ? em_launch_mstep_gather_h<H, true, true>(em) : em_launch_mstep_gather_h<H, true, false>(em);
+    else em->has_len ? em_launch_mstep_gather_h<H, false, true>(em) : em_launch_mstep_gather_h<H, false, false>(em);
+}
+int em_launch_mstep_gather(gbrs_em *em, const EmStepRoute &r) {
+    const bool extra = r.long_rows != EmLongRows::None;
+    switch (em->H) {
+    case 1: em_launch_mstep_gather_opts<1>(em, extra); break;
+    case 2: em_launch_mstep_gather_opts<2>(em, extra); break;
+    case 4: em_launch_mstep_gather_opts<4>(em, extra); break;
+    case 8: em_launch_mstep_gather_opts<8>(em, extra); break;
+    case 16: em_launch_mstep_gather_opts<16>(em, extra); break;
+    default: return fail(GBRS_ERR_UNSUPPORTED, "the fused M-step has no instance for this haplotype count");
+    }
     return GBRS_OK;
 }
 
+template <int MODE, int H>
+void em_launch_mstep_elem(gbrs_em *em, const double *extra, const double *len) {
+    const uint64_t npair = (uint64_t)em->L * MstepRow<H>::LANES;
+    const unsigned nb = (unsigned)((npair + RED_THREADS - 1) / RED_THREADS);
+    em->msum_blocks = nb;
+    hipLaunchKernelGGL((mstep_elem_kernel<MODE, H>), dim3(nb), dim3(RED_THREADS), 0, em->stream, em->L, em->theta.p, em->acc.p,
+                       extra, len, em->counts.p, em->tot_prev.p, em->tot_new.p, em->msums.p, em->msum_cap, em->scalars.p);
+}
 // M-step launch: with the gather, element-parallel (H a power of two) or thread-per-locus.  MODE 1: prepare.
 template <int MODE>
 int em_launch_mstep_plain(gbrs_em *em, const EmStepRoute &r) {
@@ -1040,12 +865,16 @@ int em_launch_mstep_plain(gbrs_em *em, const EmStepRoute &r) {
                            em->msums.p, em->msum_cap, em->scalars.p);
         return GBRS_OK;
     }
-    const uint64_t n = (uint64_t)em->L * em->H;
-    const unsigned nb = (unsigned)((n + RED_THREADS - 1) / RED_THREADS);
-    em->msum_blocks = nb;
-    hipLaunchKernelGGL(mstep_elem_kernel<MODE>, dim3(nb), dim3(RED_THREADS), 0, em->stream, em->L, em->H, em->theta.p,
-                       em->acc.p, r.mstep_adds_extra ? em->tl.acc_extra.p : (const double *)nullptr, len,
-                       em->counts.p, em->tot_prev.p, em->tot_new.p, em->msums.p, em->msum_cap, em->scalars.p);
+    const double *extra = r.mstep_adds_extra ? em->tl.acc_extra.p : (const double *)nullptr;
+    switch (em->H) {
+    case 1: em_launch_mstep_elem<MODE, 1>(em, extra, len); break;
+    case 2: em_launch_mstep_elem<MODE, 2>(em, extra, len); break;
+    case 4: em_launch_mstep_elem<MODE, 4>(em, extra, len); break;
+    case 8: em_launch_mstep_elem<MODE, 8>(em, extra, len); break;
+    case 16: em_launch_mstep_elem<MODE, 16>(em, extra, len); break;
+    case 32: em_launch_mstep_elem<MODE, 32>(em, extra, len); break;
+    default: return fail(GBRS_ERR_UNSUPPORTED, "the element-parallel M-step has no instance for this haplotype count");
+    }
     return GBRS_OK;
 }
 int em_launch_mstep(gbrs_em *em, const EmStepRoute &r) {

@@ -322,24 +322,9 @@ def main(argv=None) -> int:
             from .quantify import check_bootstrap_args
             check_bootstrap_args(args.bootstrap, args.merge_identical_rows, args.gpus)
         if args.command == 'reconstruct':
-            from .hmm import check_sim_geno_args
-            check_sim_geno_args(args.sim_geno, args.sim_geno_seed)
-            from .hmm import check_diagnostics_args
-            check_diagnostics_args(args.diagnostics, args.error_lod_threshold, args.gene_report,
-                                   cohort=args.sample_file is not None)
-            from .hmm import check_loglik_args
-            check_loglik_args(args.loglik, args.alt_tprob_file, args.model_report, cohort=args.sample_file is not None,
-                              tprob_file=args.tprob_file)
-            from .hmm import check_match_args
-            check_match_args(args.match_panel, args.match_labels, args.match_expected, args.match_chromosomes,
-                             args.match_report, args.match_matrix, args.grid_file, cohort=args.sample_file is not None)
-            from .hmm import check_snp_args
-            check_snp_args(args.snp_file, args.snp_matrix, cohort=args.sample_file is not None)
-            from .scan import check_scan_args
-            check_scan_args(args.scan_pheno, args.scan_covar, args.scan_rankz, args.scan_out, args.scan_min_lod,
-                            args.scan_lod_matrix, args.grid_file, cohort=args.sample_file is not None,
-                            scan_perms=args.scan_perms, scan_perm_seed=args.scan_perm_seed, scan_perm_alpha=args.scan_perm_alpha,
-                            scan_perm_chromosomes=args.scan_perm_chromosomes, scan_perm_pheno=args.scan_perm_pheno)
+            from .hmm import ReconstructOptions      # refused here, before any file is opened
+            options = ReconstructOptions.of(dict(vars(args), alt_tprob_files=args.alt_tprob_file))
+            options.check(args.sample_file is not None, args.grid_file, args.tprob_file)
         if args.command == 'quantify' and args.gpus is not None:
             # N child processes, one per rank; this process opens no device
             from .sharded import launch
@@ -456,31 +441,15 @@ def main(argv=None) -> int:
             from .hmm import read_sample_file, reconstruct_many
             samples = read_sample_file(args.sample_file)
             reconstruct_many([f for f, _ in samples], [o for _, o in samples], tprob_file=args.tprob_file,
-                             avec_file=args.avec_file, gpos_file=args.gpos_file, expr_threshold=args.expr_threshold,
-                             sigma=args.sigma, device=args.device, batch_size=args.batch_size, grid_file=args.grid_file,
-                             grid_genoprobs=args.grid_genoprobs, stage_times=stages, sim_geno=args.sim_geno,
-                             sim_geno_seed=args.sim_geno_seed, diagnostics=args.diagnostics,
-                             error_lod_threshold=args.error_lod_threshold, gene_report=args.gene_report,
-                             loglik=args.loglik, alt_tprob_files=args.alt_tprob_file, model_report=args.model_report,
-                             match_panel=args.match_panel, match_labels=args.match_labels,
-                             match_chromosomes=args.match_chromosomes, match_report=args.match_report,
-                             match_matrix=args.match_matrix, snp_file=args.snp_file, snp_matrix=args.snp_matrix,
-                             scan_pheno=args.scan_pheno, scan_covar=args.scan_covar, scan_rankz=args.scan_rankz,
-                             scan_out=args.scan_out, scan_min_lod=args.scan_min_lod, scan_lod_matrix=args.scan_lod_matrix,
-                             scan_perms=args.scan_perms, scan_perm_seed=args.scan_perm_seed,
-                             scan_perm_alpha=args.scan_perm_alpha, scan_perm_chromosomes=args.scan_perm_chromosomes,
-                             scan_perm_pheno=args.scan_perm_pheno)
+                             avec_file=args.avec_file, gpos_file=args.gpos_file, device=args.device,
+                             batch_size=args.batch_size, grid_file=args.grid_file, stage_times=stages,
+                             **options.keywords(cohort=True))
         else:
             from .hmm import reconstruct
             reconstruct(expression_file=args.expression_file, tprob_file=args.tprob_file,
-                        avec_file=args.avec_file, gpos_file=args.gpos_file,
-                        expr_threshold=args.expr_threshold, sigma=args.sigma, outbase=args.outbase,
+                        avec_file=args.avec_file, gpos_file=args.gpos_file, outbase=args.outbase,
                         device=args.device, stage_times=stages, grid_file=args.grid_file,
-                        grid_genoprobs=args.grid_genoprobs, sim_geno=args.sim_geno, sim_geno_seed=args.sim_geno_seed,
-                        diagnostics=args.diagnostics, error_lod_threshold=args.error_lod_threshold,
-                        loglik=args.loglik, alt_tprob_files=args.alt_tprob_file, match_panel=args.match_panel,
-                        match_expected=args.match_expected, match_chromosomes=args.match_chromosomes,
-                        snp_file=args.snp_file)
+                        **options.keywords(cohort=False))
     except Exception as e:   # noqa: BLE001 - mirror of the reference's catch-all
         failure = e
         if logger.level == logging.DEBUG:

@@ -6,9 +6,11 @@ No CPU fallback: without libgbrs_hip.so / a gfx950 device every entry point rais
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import logging
 import os
 import time
+import types
 from collections import OrderedDict
 from itertools import combinations_with_replacement
 
@@ -114,19 +116,22 @@ class DiplotypeHMM:
         _lib.check(_lib.load().gbrs_hmm_get(self._h, sample, c, *args))
         return {k: bufs[k] for k in want}
 
+    def _by_chrom(self, table):
+        """A per-chromosome argument - a sequence in the handle's order or a dict by chromosome name - as a list over
+        the handle's chromosomes, None where it has nothing."""
+        if isinstance(table, dict):
+            return [table.get(c) for c in self.chroms]
+        return list(table) + [None] * (len(self.chroms) - len(table))
+
     def set_grid(self, gene_positions, grid):
         """The marker grid of the handle (sample independent, uploaded once).  Both arguments go by handle chromosome:
         a sequence in the handle's order or a dict by chromosome name.  grid[c]: grid positions in file order, None,
         empty or absent for a chromosome that is not on the grid; gene_positions[c]: the positions of its genes in
         genome order.  The knots are made as postproc.interpolate_arrays makes them; a grid point outside them raises
         interp1d's ValueError, a grid chromosome without gene positions the chain's IndexError."""
-        def by_chrom(table):
-            if isinstance(table, dict):
-                return [table.get(c) for c in self.chroms]
-            return list(table) + [None] * (len(self.chroms) - len(table))
-        points = [np.zeros(0) if g is None else np.ascontiguousarray(g, dtype=np.float64) for g in by_chrom(grid)]
+        points = [np.zeros(0) if g is None else np.ascontiguousarray(g, dtype=np.float64) for g in self._by_chrom(grid)]
         where = [np.zeros(0) if len(g) == 0 or x is None else np.ascontiguousarray(x, dtype=np.float64)
-                 for g, x in zip(points, by_chrom(gene_positions))]
+                 for g, x in zip(points, self._by_chrom(gene_positions))]
         n_grid = np.asarray([len(g) for g in points], dtype=np.int32)
         n_pos = np.asarray([len(x) for x in where], dtype=np.int32)
         lib = _lib.load()
@@ -202,17 +207,14 @@ class DiplotypeHMM:
         allele patterns as uint32, bit h set when founder h carries the alternative allele; gene_positions[c]: the
         positions of its genes.  The SNPs of a chromosome are a grid: a SNP outside the knots raises the grid's
         ValueError.  All empty drops the SNPs.  Independent of set_grid and set_panel."""
-        def by_chrom(table):
-            if isinstance(table, dict):
-                return [table.get(c) for c in self.chroms]
-            return list(table) + [None] * (len(self.chroms) - len(table))
-        points = [np.zeros(0) if x is None else np.ascontiguousarray(x, dtype=np.float64) for x in by_chrom(positions)]
-        bits = [np.zeros(0, dtype=np.uint32) if m is None else np.ascontiguousarray(m, dtype=np.uint32) for m in by_chrom(masks)]
+        points = [np.zeros(0) if x is None else np.ascontiguousarray(x, dtype=np.float64) for x in self._by_chrom(positions)]
+        bits = [np.zeros(0, dtype=np.uint32) if m is None else np.ascontiguousarray(m, dtype=np.uint32)
+                for m in self._by_chrom(masks)]
         for c, x, m in zip(self.chroms, points, bits):
             if x.shape != m.shape or x.ndim != 1:
                 raise ValueError(f'chromosome {c}: {x.shape} SNP positions and {m.shape} patterns')
         where = [np.zeros(0) if len(x) == 0 or g is None else np.ascontiguousarray(g, dtype=np.float64)
-                 for x, g in zip(points, by_chrom(gene_positions))]
+                 for x, g in zip(points, self._by_chrom(gene_positions))]
         n_snps = np.asarray([len(x) for x in points], dtype=np.int32)
         n_pos = np.asarray([len(g) for g in where], dtype=np.int32)
         lib = _lib.load()
@@ -1354,6 +1356,298 @@ def _load_snps(ctx, snp_file, haplotypes):
     return ctx.snps
 
 
+# ---- the two drivers: one sample (`-e`) and a cohort (`--sample-file`) ---------------------------------------------------
+
+@dataclasses.dataclass(frozen=True)
+class ReconstructOptions:
+    """The keywords of reconstruct (one sample) and reconstruct_many (a cohort) after `device`, apart from `stage_times`,
+    `context` and `grid_file`.  All but `expr_threshold` and `sigma`, the emission model's as in gbrs_utils.reconstruct,
+    are extensions; one that is off makes no device pass, no buffer and no file.
+    `grid_genoprobs` (with a grid file): beside `<outbase>.interpolated.genoprobs.tsv`, the founder dosages `gbrs export`
+    would write after `gbrs interpolate`, `<outbase>.interpolated.genoprobs.npz` holds what `gbrs interpolate` writes.
+    `sim_geno` = K: K diplotype paths per chromosome drawn from the joint posterior on the device with
+    seed `sim_geno_seed` go to `<outbase>.sim_geno.npz`, their founder changes beside the Viterbi path's to
+    `<outbase>.sim_geno.crossovers.tsv`.  The one sample draws on stream 0, a cohort's sample on its 0-based position in
+    `expression_files`, so its draws do not depend on the launch it ran in.
+    `diagnostics`: the expected founder changes and the switch probability of every gene interval, and per
+    gene the error LOD and the most likely diplotype, go to `<outbase>.diagnostics.npz`, a summary per chromosome with the
+    expressed genes whose error LOD is above `error_lod_threshold` to `<outbase>.diagnostics.tsv`.  `gene_report` (cohort
+    only): one line per gene of the handle over the samples that ran - how many express it, in how many of those its
+    error LOD is above the threshold.
+    `loglik`: `<outbase>.loglik.tsv` holds the data log-likelihood of the run per chromosome and in total.
+    `alt_tprob_files` (implies `loglik`; with a context, the context's): the emissions are also scored under these table
+    files on the device.  A sample that one of them explains better than `tprob_file` (the first largest total,
+    `tprob_file` first) is run again, alone, under a handle on that file (made at first need, kept with the context), and
+    all of its files are the ones a plain single-sample call with that file writes; a cohort's sample keeps its stream.
+    `model_report` (cohort only): one line per sample that ran - outbase, selected file, margin, totals per candidate.
+    `match_panel` (needs a grid file): the grid dosages are compared on the device with those of every entry
+    of the panel file and `<outbase>.match.tsv` lists the entries by distance; a sample that moved to another table file
+    is matched under that handle.  `match_chromosomes`: the chromosomes that are compared.  `match_expected` (one sample
+    only): the panel id the sample should be, logged with its status.  Cohort only: `match_labels`, a file of lines
+    `outbase<TAB>panel id` saying the same per sample; `match_report`, one line per sample that ran with its status, best
+    and second entry and margin; `match_matrix`, an .npz with the distances, similarities and the device's sums.
+    `snp_file`: the expected number of alternative alleles at every SNP of the file, from the founder
+    dosages at the genes around it and the SNP's founder allele pattern, on the device; `<outbase>.snp_dosage.npz` holds
+    them in the file's order.  The SNPs go to a handle once.  `snp_matrix` (cohort only): an .npz with the rows of all
+    samples that ran and the SNP file's columns.
+    `scan_pheno` (cohort only; needs a grid file): a table of phenotypes keyed by outbase.  The grid dosages
+    of every sample that ran and has a phenotype row (and, with `scan_covar`, a covariate row) are collected on the device
+    in the order of `expression_files`; after the last launch the phenotypes are regressed on them at every grid point
+    and `<scan_out>.scan.npz` and `<scan_out>.scan.peaks.tsv` are written (gbrs_amd/scan.py, which documents `scan_rankz`,
+    `scan_min_lod` and `scan_lod_matrix`).  `scan_perms`: that many permutations follow the scan on the
+    device and both files gain genome-wide thresholds and p-values; the other `scan_perm_*` are scan.perm_options'."""
+    expr_threshold: float = 1.5
+    sigma: float = 0.12
+    grid_genoprobs: bool = False
+    sim_geno: int = None
+    sim_geno_seed: int = 0
+    diagnostics: bool = False
+    error_lod_threshold: float = 2.0
+    gene_report: str = None
+    loglik: bool = False
+    alt_tprob_files: list = None
+    model_report: str = None
+    match_panel: str = None
+    match_expected: str = None
+    match_chromosomes: object = None
+    match_labels: str = None
+    match_report: str = None
+    match_matrix: str = None
+    snp_file: str = None
+    snp_matrix: str = None
+    scan_pheno: str = None
+    scan_covar: str = None
+    scan_rankz: bool = False
+    scan_out: str = None
+    scan_min_lod: float = None
+    scan_lod_matrix: bool = False
+    scan_perms: int = None
+    scan_perm_seed: int = None
+    scan_perm_alpha: object = None
+    scan_perm_chromosomes: object = None
+    scan_perm_pheno: str = None
+
+    @classmethod
+    def of(cls, keywords):
+        """The options among `keywords` (a driver's locals(), a parser's vars(args)), the others at their defaults; a
+        context's alternative table files stand in for none given, and alternatives turn `loglik` on."""
+        options = cls(**{f.name: keywords[f.name] for f in dataclasses.fields(cls) if f.name in keywords})
+        alts, context = options.alt_tprob_files, keywords.get('context')
+        if alts is None and context is not None:
+            alts = context.alt_tprob_files
+        return dataclasses.replace(options, alt_tprob_files=alts, loglik=bool(options.loglik or alts))
+
+    def keywords(self, cohort):
+        """The options as keywords of reconstruct_many (cohort) or of reconstruct, which has no `scan_*`."""
+        return {f.name: getattr(self, f.name) for f in dataclasses.fields(self) if cohort or not f.name.startswith('scan_')}
+
+    def check(self, cohort, grid_file, tprob_file):
+        """Every refusal that needs no file, in the command's order.  cohort: `--sample-file`, not `-e`."""
+        from .scan import check_scan_args
+        check_sim_geno_args(self.sim_geno, self.sim_geno_seed)
+        check_diagnostics_args(self.diagnostics, self.error_lod_threshold, self.gene_report, cohort=cohort)
+        check_loglik_args(self.loglik, self.alt_tprob_files, self.model_report, cohort=cohort, tprob_file=tprob_file)
+        check_match_args(self.match_panel, self.match_labels, self.match_expected, self.match_chromosomes, self.match_report,
+                         self.match_matrix, grid_file, cohort=cohort)
+        check_snp_args(self.snp_file, self.snp_matrix, cohort=cohort)
+        check_scan_args(self.scan_pheno, self.scan_covar, self.scan_rankz, self.scan_out, self.scan_min_lod,
+                        self.scan_lod_matrix, grid_file, cohort=cohort, scan_perms=self.scan_perms,
+                        scan_perm_seed=self.scan_perm_seed, scan_perm_alpha=self.scan_perm_alpha,
+                        scan_perm_chromosomes=self.scan_perm_chromosomes, scan_perm_pheno=self.scan_perm_pheno)
+
+
+class _Shared:
+    """What the launches of one driver call share: the options, the names of the samples' header, what the options had
+    read once (panel, SNPs; every refusal of those files comes from here, before a sample runs) and what outlives a
+    launch, keyed by the sample's position in `expression_files` (0 for the single-sample command)."""
+
+    def __init__(self, ctx, options, haplotypes, tprob_file, marks, say, handle_key, expected):
+        self.ctx, self.options, self.marks = ctx, options, marks
+        self.say = say                     # logs a line of the single-sample command; a cohort stays quiet
+        self.handle_key = handle_key       # the stage_times key a new handle's seconds go to
+        self.haplotypes, self.num_haps = haplotypes, len(haplotypes)
+        self.diplotypes = [a + b for a, b in combinations_with_replacement(haplotypes, 2)]
+        self.names = [tprob_file] + list(ctx.alt_tprob_files) if options.loglik else None    # the candidates
+        self.expected = expected           # sample -> the panel id it should be
+        if options.match_panel is not None:
+            self.match_use, self.match_points = _load_panel(ctx, options.match_panel, haplotypes, options.match_chromosomes)
+        self.snps = _load_snps(ctx, options.snp_file, haplotypes) if options.snp_file is not None else None
+        self.choices = {}                  # sample -> (selected candidate, margin, totals per candidate)
+        self.scores = {}                   # sample -> its (candidates, chromosomes) log-likelihoods
+        self.matches = {}                  # sample -> (cross, sample_norm, distance, similarity, rank_matches' dict)
+        self.panel_norm = None
+        self.snp_rows = {}                 # sample -> its dosages in SNP file order
+        self.scan_keep = set()             # the samples the genome scan takes
+        self.scan_held = {}                # sample -> its host dosage rows, until its batch is appended to the scan
+        self.report = None                 # the GeneReport, made with the first launch that feeds it
+
+    def spend(self, key, seconds):
+        self.marks[key] = self.marks.get(key, 0.0) + seconds
+
+
+def _pass_grid(job):
+    genoprobs = job.options.grid_genoprobs
+    got = job.hmm.grid(sample=job.sample, want=('dosage', 'gamma_grid') if genoprobs else ('dosage',))
+    if job.sample is not None:
+        got = {k: [v] for k, v in got.items()}
+    per = [(got['dosage'][s], got['gamma_grid'][s] if genoprobs else None) for s in range(len(job.members))]
+    for s in job.stay:
+        if job.members[s] in job.shared.scan_keep:
+            job.shared.scan_held[job.members[s]] = per[s][0]
+    return per
+
+
+def _pass_match(job):
+    shared = job.shared
+    got = job.hmm.match(sample=job.sample)
+    shared.panel_norm = job.hmm.match_info()['panel_norm']
+    cross, norm = (got['cross'], got['sample_norm']) if job.sample is None else (got['cross'][None], got['sample_norm'][None])
+    distance, similarity = match_scores(cross, norm, shared.panel_norm, shared.match_points, shared.match_use)
+    per = {}
+    for s in job.stay:
+        k = job.members[s]
+        per[s] = shared.matches[k] = (cross[s], norm[s], distance[s], similarity[s],
+                                      rank_matches(shared.ctx.panel[0], distance[s], shared.expected.get(k)))
+    return per
+
+
+def _pass_snp(job):
+    snps = job.shared.snps
+    got = np.atleast_2d(job.hmm.impute(sample=job.sample)) if len(snps['order']) else np.zeros((len(job.members), 0))
+    rows = snp_dosage_in_file_order(snps, got)
+    for s in job.stay:
+        job.shared.snp_rows[job.members[s]] = rows[s]
+    return rows
+
+
+def _pass_sim_geno(job):               # a sample's stream is its position in `expression_files`
+    return _draw_paths(job.hmm, job.options.sim_geno, job.options.sim_geno_seed, job.members, sample=job.sample)
+
+
+def _pass_diagnostics(job):
+    shared, options = job.shared, job.options
+    got = _diagnose(job.hmm, job.rows, options.expr_threshold, sample=job.sample)
+    if options.gene_report is not None:
+        if shared.report is None:
+            shared.report = GeneReport(shared.ctx, options.error_lod_threshold)
+        for s in job.stay:
+            shared.report.add(got[s])
+    return got
+
+
+# The optional device passes that follow run(), the likelihoods and the collection of the posteriors, in the order both
+# drivers make them.  Each reads what gbrs_hmm_run left and buffers of its own (match: the dosages of the grid pass before
+# it), so the order changes no bit.  Per pass: its stage_times key, which is also its key in a sample's bundle; what turns
+# it on; the function above that makes it, through DiplotypeHMM.grid / .match and .match_info / .impute / .sample_paths
+# (_draw_paths) / .diagnostics (_diagnose); the line the single-sample command logs before it.
+_PASSES = (
+    ('grid', lambda job: job.on.grid is not None, _pass_grid, 'Converting genotype probability on the grid'),
+    ('match', lambda job: job.options.match_panel is not None, _pass_match, 'Matching the sample against the panel'),
+    ('snp', lambda job: job.shared.snps is not None, _pass_snp, 'Imputing SNP dosages'),
+    ('sim_geno', lambda job: job.options.sim_geno is not None, _pass_sim_geno, 'Drawing {0.sim_geno} paths from the posterior'),
+    ('diagnostics', lambda job: job.options.diagnostics, _pass_diagnostics, 'Getting crossover expectations and gene error LODs'),
+)
+
+
+def _launch(on, members, rows, shared, sample=None):
+    """The samples `members` (their TPM rows per chromosome in `rows`) through the handle of context `on` - the shared
+    context or one of its alternatives - in one launch, then the passes the options ask for.  sample: None asks the handle
+    for every sample of the launch (a cohort), 0 for the one sample of the single-sample command.
+    Returns ({sample: its bundle - what _save_sample writes}, {alternative: [samples]}): with candidates to weigh (`on` is
+    the shared context) the samples that an alternative explains better get no bundle; the caller runs them under it."""
+    options, say, clock = shared.options, shared.say, time.perf_counter
+    t0 = clock()
+    hmm, first_use = on.handle(shared.num_haps)
+    spec = on.specificity(shared.num_haps) if first_use else None      # stays on a handle once given
+    shared.spend(shared.handle_key, clock() - t0)
+    t0 = clock()
+    say('Getting forward probability')
+    stacked = [np.stack([r[ci] for r in rows]) for ci in range(len(on.chroms))]
+    if first_use:
+        hmm.set_expression(stacked, [x[0] for x in spec], [x[1] for x in spec], options.expr_threshold, options.sigma)
+    else:
+        hmm.set_expression(stacked, expr_threshold=options.expr_threshold, sigma=options.sigma)
+    say('Getting backward probability')
+    hmm.run()
+    shared.spend('hmm', clock() - t0)
+    moved, stay = {}, list(range(len(members)))
+    if options.loglik and on is shared.ctx:
+        t0 = clock()
+        say('Getting the log-likelihood of the data')
+        per = _model_logliks(on, hmm, shared.num_haps)
+        totals = loglik_totals(per)
+        best, margin = choose_tables(totals)
+        for s, k in enumerate(members):
+            shared.choices[k] = (int(best[s]), float(margin[s]), totals[:, s].copy())
+            shared.scores[k] = per[:, s, :].copy()
+            if best[s] != 0:
+                moved.setdefault(int(best[s]) - 1, []).append(k)
+        stay = [s for s in stay if best[s] == 0]
+        shared.spend('loglik', clock() - t0)
+    t0 = clock()
+    if stay:
+        say('Getting forward-backward probability')
+    bundles = {s: {'reconstruction': _collect(on, hmm, s, shared.diplotypes), 'stream': members[s],
+                   'scores': shared.scores.get(members[s])} for s in stay}
+    shared.spend('hmm', clock() - t0)
+    job = types.SimpleNamespace(on=on, hmm=hmm, members=members, rows=rows, stay=stay, sample=sample, shared=shared,
+                                options=options)
+    for key, enabled, make, line in _PASSES:
+        if stay and enabled(job):
+            t0 = clock()
+            say(line.format(options))
+            got = make(job)
+            for s in stay:
+                bundles[s][key] = got[s]
+            shared.spend(key, clock() - t0)
+    return {members[s]: bundle for s, bundle in bundles.items()}, moved
+
+
+def _nothing_ran(on, shared, k):
+    """The bundle of sample `k` when no chromosome has a transition table: every file the options ask for, empty."""
+    options = shared.options
+    bundle = {'reconstruction': ({}, {}, {}), 'stream': k}
+    if on.grid is not None:
+        bundle['grid'] = (np.zeros((0, shared.num_haps)), [] if options.grid_genoprobs else None)
+    if options.sim_geno is not None:
+        bundle['sim_geno'] = ([], np.zeros((options.sim_geno, 0), dtype=np.int32), [])
+    if options.diagnostics:
+        bundle['diagnostics'] = _no_diagnostics()
+    if options.loglik:
+        K = len(shared.names)
+        shared.choices[k] = (0, 0.0 if K > 1 else np.inf, np.zeros(K))
+        bundle['scores'] = shared.scores[k] = np.zeros((K, 0))
+    if shared.snps is not None:
+        bundle['snp'] = shared.snp_rows[k] = np.full(len(shared.snps['snp_id']), np.nan)
+    return bundle
+
+
+def _save_loglik(stem, on, shared, k):
+    write_loglik_table(f'{stem}.loglik.tsv', on.chroms, [len(on.gene_order[c]) for c in on.chroms], shared.names,
+                       shared.scores[k], shared.choices[k][0])
+
+
+def _save_sample(stem, on, bundle, shared, threads=None):
+    """The files of one sample that ran under context `on`, from its bundle.  threads: of the .npz writers; None lets
+    them use every core (the single-sample command), a cohort's writer pool gives each sample one."""
+    options = shared.options
+    _save_reconstruction(stem, *bundle['reconstruction'], threads=threads)
+    if 'grid' in bundle:
+        _save_grid(stem, on, shared.haplotypes, *bundle['grid'], threads=threads)
+    if 'sim_geno' in bundle:
+        _save_sim_geno(stem, on, shared.diplotypes, bundle['sim_geno'], options.sim_geno_seed, bundle['stream'], threads=threads)
+    if 'diagnostics' in bundle:
+        _save_diagnostics(stem, on, shared.diplotypes, bundle['diagnostics'], options.error_lod_threshold, threads=threads)
+    if bundle.get('scores') is not None:
+        _save_loglik(stem, on, shared, bundle['stream'])
+    if 'match' in bundle:
+        _, _, distance, similarity, rank = bundle['match']
+        write_match_table(f'{stem}.match.tsv', shared.ctx.panel[0], distance, similarity, rank['order'])
+        shared.say(f"Panel match: {rank['status']}, best {rank['best']} at {rank['best_distance']!r}")
+    if 'snp' in bundle:
+        write_snp_dosage(f'{stem}.snp_dosage.npz', bundle['snp'], shared.snps)
+
+
 def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gpos_file: str = None,
                 expr_threshold: float = 1.5, sigma: float = 0.12, outbase: str = None,
                 device: int = 0, stage_times: dict = None, context: ReconstructContext = None,
@@ -1369,41 +1663,15 @@ def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gp
     gbrs_amd.worker): the sample-independent inputs and the device handle of an earlier call on the same
     tables - the transition and specificity tables then stay where they are and the sample moves its expression
     rows only.  `grid_file` (extension; with a context, the context's): the posteriors also go onto the marker grid
-    on the device and `<outbase>.interpolated.genoprobs.tsv` holds the founder dosages `gbrs export` would write after
-    `gbrs interpolate`; with `grid_genoprobs` `<outbase>.interpolated.genoprobs.npz` holds what `gbrs interpolate`
-    writes.  `sim_geno` = K (extension): K diplotype paths per chromosome drawn from the joint posterior on the device
-    (stream 0, seed `sim_geno_seed`) go to `<outbase>.sim_geno.npz`, their founder changes beside the Viterbi path's to
-    `<outbase>.sim_geno.crossovers.tsv`; without it the run makes no log-domain arrays and reaches none of that code.
-    `diagnostics` (extension): the expected founder changes and the switch probability of every gene interval, and per
-    gene the error LOD and the most likely diplotype, go to `<outbase>.diagnostics.npz`, a summary per chromosome with the
-    expressed genes whose error LOD is above `error_lod_threshold` to `<outbase>.diagnostics.tsv` (DESIGN.md §23);
-    `gene_report` belongs to a cohort (reconstruct_many) and is refused here.
-    `loglik` (extension): `<outbase>.loglik.tsv` holds the data log-likelihood of the run per chromosome
-    and in total.  `alt_tprob_files` (implies `loglik`; with a context, the context's): the sample's emissions are also
-    scored under these table files on the device; if one of them explains the sample better than `tprob_file` (the first
-    largest total, `tprob_file` first), the sample is run again under it and every file is the one a plain call with that
-    table file writes.  `model_report` belongs to a cohort and is refused here.
-    `match_panel` (extension; needs a grid file): the sample's grid dosages are compared on the device with
-    those of every entry of the panel file and `<outbase>.match.tsv` lists the entries by distance; `match_expected`: the
-    panel id the sample should be (logged with its status), `match_chromosomes`: the chromosomes that are compared.
-    `match_labels`, `match_report` and `match_matrix` belong to a cohort and are refused here.
-    `snp_file` (extension): the expected number of alternative alleles of the sample at every SNP of the
-    file, from the founder dosages at the genes around it and the SNP's founder allele pattern, on the device;
-    `<outbase>.snp_dosage.npz` holds them in the file's order.  `snp_matrix` belongs to a cohort and is refused here."""
-    check_sim_geno_args(sim_geno, sim_geno_seed)
-    check_snp_args(snp_file, snp_matrix, cohort=False)
-    check_diagnostics_args(diagnostics, error_lod_threshold, gene_report, cohort=False)
-    check_match_args(match_panel, match_labels, match_expected, match_chromosomes, match_report, match_matrix,
-                     grid_file if context is None else context.grid_file, cohort=False)
-    if context is not None and alt_tprob_files is None:
-        alt_tprob_files = context.alt_tprob_files
-    check_loglik_args(loglik, alt_tprob_files, model_report, cohort=False, tprob_file=tprob_file)
-    loglik = bool(loglik or alt_tprob_files)
+    on the device.  Every keyword from `grid_genoprobs` on is described on ReconstructOptions
+    (DESIGN.md §22-§26); those it marks as cohort only are refused here."""
+    options = ReconstructOptions.of(locals())
+    options.check(False, grid_file if context is None else context.grid_file, tprob_file)
     clock = time.perf_counter
     marks = stage_times if stage_times is not None else {}
     stem = 'gbrs.reconstructed' if outbase is None else outbase
     ctx = context if context is not None else ReconstructContext(tprob_file, avec_file, gpos_file, device, grid_file,
-                                                                 alt_tprob_files)
+                                                                 options.alt_tprob_files)
     for label, value in (('Expression File', expression_file), ('Transition Probabilities File', tprob_file),
                          ('Alignment Specificity File', ctx.avec_file), ('Gene Position File', ctx.gpos_file),
                          ('Expression Threshold', expr_threshold), ('Sigma', sigma), ('Outbase', outbase)):
@@ -1416,131 +1684,39 @@ def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gp
     # the transition tables are the big read (0.4 GB of deflate streams at DO size): it starts on the library's
     # threads and is collected when the tables are needed, after the small files have been parsed
     ctx.load()
-    chroms = ctx.chroms
     logger.info(f'Loading expression level data: {expression_file}')
     haplotypes, expr_row, expr_table = read_gene_tpm(expression_file)
-    num_haps = len(haplotypes)
-    diplotypes = [a + b for a, b in combinations_with_replacement(haplotypes, 2)]
-    rows = _expression_rows(ctx, expr_row, expr_table, num_haps)
-    first_use = ctx.hmm is None or ctx.hmm.H != num_haps
-    spec = ctx.specificity(num_haps) if first_use else None
-    if first_use:
-        ctx.tables()
-    if loglik and ctx.alt_tprob_files:
-        ctx.alt_tables(num_haps)           # a file that does not fit is refused before the sample runs
-    if match_panel is not None:            # so is a panel that does not fit the grid
-        match_use, match_points = _load_panel(ctx, match_panel, haplotypes, match_chromosomes)
-    snps = _load_snps(ctx, snp_file, haplotypes) if snp_file is not None else None
+    rows = _expression_rows(ctx, expr_row, expr_table, len(haplotypes))
+    ctx.specificity(len(haplotypes))       # what a new handle takes is read here, not while it is made
+    ctx.tables()
+    if options.loglik and ctx.alt_tprob_files:
+        ctx.alt_tables(len(haplotypes))    # a file that does not fit is refused before the sample runs
+    spent = {}                             # the launch's seconds: they replace, not add to, an earlier call's
+    shared = _Shared(ctx, options, haplotypes, tprob_file, spent, logger.info, 'tables_to_device',
+                     {} if match_expected is None else {0: match_expected})
     marks['load'] = clock() - t0
 
-    posterior, path_names, calls = {}, {}, {}
-    on_grid = drawn = diag = matched = None
-    imputed = np.zeros(0) if snps is not None else None
-    names = [tprob_file] + list(ctx.alt_tprob_files) if loglik else None
-    scores = np.zeros((len(names), 0)) if loglik else None       # (candidates, chromosomes) of this sample
-    if chroms:
-        t0 = clock()
-        hmm, _ = ctx.handle(num_haps)
-        marks['tables_to_device'] = clock() - t0
-        t0 = clock()
-        logger.info('Getting forward probability')
-        if first_use:
-            hmm.set_expression(rows, [x[0] for x in spec], [x[1] for x in spec], expr_threshold, sigma)
+    moved = {}
+    try:
+        if ctx.chroms:
+            bundles, moved = _launch(ctx, [0], [rows], shared, sample=0)
+            marks.update(spent)
         else:
-            hmm.set_expression(rows, expr_threshold=expr_threshold, sigma=sigma)
-        logger.info('Getting backward probability')
-        hmm.run()
-        scoring = 0.0
-        if loglik:
-            t1 = clock()
-            logger.info('Getting the log-likelihood of the data')
-            scores = _model_logliks(ctx, hmm, num_haps)[:, 0, :]
-            selected = int(choose_tables(loglik_totals(scores)[:, None])[0][0])
-            scoring = clock() - t1
-            if selected != 0:
-                # the sample goes through a handle on the better-fitting file: what a plain call with that file does
-                logger.info(f'Selected {names[selected]}: running the sample under it')
-                try:
-                    reconstruct(expression_file, names[selected], expr_threshold=expr_threshold, sigma=sigma,
-                                outbase=outbase, device=device, stage_times=marks, context=ctx.alt_context(selected - 1),
-                                grid_genoprobs=grid_genoprobs, sim_geno=sim_geno, sim_geno_seed=sim_geno_seed,
-                                diagnostics=diagnostics, error_lod_threshold=error_lod_threshold,
-                                match_panel=match_panel, match_expected=match_expected, match_chromosomes=match_chromosomes,
-                                snp_file=snp_file)
-                finally:
-                    if context is None:
-                        ctx.close()
-                marks['loglik'] = scoring
-                write_loglik_table(f'{stem}.loglik.tsv', chroms, [len(ctx.gene_order[c]) for c in chroms], names, scores,
-                                   selected)
-                return
-        logger.info('Getting forward-backward probability')
-        posterior, path_names, calls = _collect(ctx, hmm, 0, diplotypes)
-        if snps is not None and len(snps['order']):
-            t1 = clock()
-            logger.info('Imputing SNP dosages')
-            imputed = hmm.impute(sample=0)
-            marks['snp'] = clock() - t1
-            t0 += marks['snp']
-        if context is None and ctx.grid is None and sim_geno is None and not diagnostics:
-            ctx.close()
-        marks['hmm'] = clock() - t0 - scoring
-        if loglik:
-            marks['loglik'] = scoring
-        if sim_geno is not None:
-            t0 = clock()
-            logger.info(f'Drawing {sim_geno} paths from the posterior')
-            drawn = _draw_paths(hmm, sim_geno, sim_geno_seed, [0], sample=0)[0]
-            if context is None and ctx.grid is None and not diagnostics:
-                ctx.close()
-            marks['sim_geno'] = clock() - t0
-        if diagnostics:
-            t0 = clock()
-            logger.info('Getting crossover expectations and gene error LODs')
-            diag = _diagnose(hmm, [rows], expr_threshold, sample=0)[0]
-            if context is None and ctx.grid is None:
-                ctx.close()
-            marks['diagnostics'] = clock() - t0
-        if ctx.grid is not None:
-            t0 = clock()
-            logger.info('Converting genotype probability on the grid')
-            on_grid = hmm.grid(sample=0, want=('dosage', 'gamma_grid') if grid_genoprobs else ('dosage',))
-            if context is None and match_panel is None:
-                ctx.close()
-            marks['grid'] = clock() - t0
-        if match_panel is not None:
-            t0 = clock()
-            logger.info('Matching the sample against the panel')
-            got = hmm.match(sample=0)
-            panel_norm = hmm.match_info()['panel_norm']
-            if context is None:
-                ctx.close()
-            distance, similarity = match_scores(got['cross'], got['sample_norm'], panel_norm, match_points, match_use)
-            matched = (distance, similarity, rank_matches(ctx.panel[0], distance, match_expected))
-            marks['match'] = clock() - t0
-    elif ctx.grid is not None:
-        on_grid = {'dosage': np.zeros((0, num_haps)), 'gamma_grid': [] if grid_genoprobs else None}
-    if sim_geno is not None and drawn is None:
-        drawn = ([], np.zeros((sim_geno, 0), dtype=np.int32), [])
-    if diagnostics and diag is None:
-        diag = _no_diagnostics()
-
+            bundles = {0: _nothing_ran(ctx, shared, 0)}
+        for a in moved:
+            # the sample goes through a handle on the better-fitting file: what a plain call with that file does
+            logger.info(f'Selected {shared.names[a + 1]}: running the sample under it')
+            reconstruct(expression_file, shared.names[a + 1], outbase=outbase, device=device, stage_times=marks,
+                        context=ctx.alt_context(a),
+                        **dataclasses.replace(options, loglik=False, alt_tprob_files=None).keywords(cohort=False))
+    finally:
+        if context is None:
+            ctx.close()                    # the device is free before the seconds spent writing files
+    if moved:
+        _save_loglik(stem, ctx, shared, 0)
+        return
     t0 = clock()
-    _save_reconstruction(stem, posterior, path_names, calls)
-    if on_grid is not None:
-        _save_grid(stem, ctx, haplotypes, on_grid['dosage'], on_grid.get('gamma_grid'))
-    if drawn is not None:
-        _save_sim_geno(stem, ctx, diplotypes, drawn, sim_geno_seed, 0)
-    if diag is not None:
-        _save_diagnostics(stem, ctx, diplotypes, diag, error_lod_threshold)
-    if loglik:
-        write_loglik_table(f'{stem}.loglik.tsv', chroms, [len(ctx.gene_order[c]) for c in chroms], names, scores, 0)
-    if matched is not None:
-        distance, similarity, rank = matched
-        write_match_table(f'{stem}.match.tsv', ctx.panel[0], distance, similarity, rank['order'])
-        logger.info(f"Panel match: {rank['status']}, best {rank['best']} at {rank['best_distance']!r}")
-    if snps is not None:
-        write_snp_dosage(f'{stem}.snp_dosage.npz', snp_dosage_in_file_order(snps, imputed), snps)
+    _save_sample(stem, ctx, bundles[0], shared)
     marks['save'] = clock() - t0
     logger.info('Done')
 
@@ -1548,17 +1724,7 @@ def reconstruct(expression_file: str, tprob_file: str, avec_file: str = None, gp
 def read_sample_file(sample_file):
     """[(genes.tpm, outbase)] from a file of tab separated lines `genes.tpm<TAB>outbase`; blank lines and lines that
     start with # are skipped."""
-    samples = []
-    with open(sample_file) as fh:
-        for number, line in enumerate(fh, 1):
-            line = line.strip()
-            if not line or line.startswith('#'):
-                continue
-            fields = line.split('\t')
-            if len(fields) != 2:
-                raise RuntimeError(f'{sample_file}, line {number}: expected genes.tpm<TAB>outbase')
-            samples.append((fields[0], fields[1]))
-    return samples
+    return [(tpm, outbase) for _, tpm, outbase in _match_lines(sample_file, 'genes.tpm<TAB>outbase')]
 
 
 def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str = None, gpos_file: str = None,
@@ -1574,50 +1740,16 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
                      scan_perms: int = None, scan_perm_seed: int = None, scan_perm_alpha=None, scan_perm_chromosomes=None,
                      scan_perm_pheno: str = None) -> list:
     """`gbrs reconstruct` for a cohort whose genes.tpm files exist (extension): one context, the tables on the device
-    once, the samples through the HMM in launches of up to `batch_size`, and with `grid_file` one grid pass per launch.
-    Every sample gets the files the single-sample call writes for its outbase.  All samples must carry the same
+    once, the samples through the HMM in launches of up to `batch_size`, and every pass the options ask for once per
+    launch.  Every sample gets the files the single-sample call writes for its outbase.  All samples must carry the same
     haplotype header (RuntimeError before anything runs otherwise).  A sample whose file cannot be read or lacks a gene
     is logged and left out, and the others go on.  Returns one dict per sample: its outbase and, if it failed,
-    `error`.  `sim_geno` = K: one more device pass per launch draws K paths per sample and chromosome; a sample's stream
-    is its 0-based position in `expression_files`, so its draws do not depend on the batch it ran in.  `diagnostics`: two
-    more device passes per launch and every sample's two diagnostics files; `gene_report`: one line per gene of the handle
-    over the samples that ran (how many express it, in how many of those its error LOD is above `error_lod_threshold`).
-    `loglik`: every sample's `<outbase>.loglik.tsv`, from one more device pass per launch.  `alt_tprob_files` (implies
-    `loglik`; with a context, the context's): each launch is also scored under these table files; a sample that one of
-    them explains better than `tprob_file` is run again, in a launch of its own, under a handle on that file (made at
-    first need, kept for the cohort) and all of its files come from that run - the files of the single-sample command
-    under that file - its path draws on its usual stream.
-    `model_report`: one line per sample that ran - outbase, selected file, margin, the totals per candidate.
-    `match_panel` (needs a grid file): one more device pass per launch compares every sample's grid dosages
-    with every entry of the panel file; every sample gets `<outbase>.match.tsv`.  `match_labels`: a file of lines
-    `outbase<TAB>panel id`, the entry each sample should be; `match_chromosomes`: the chromosomes that are compared;
-    `match_report`: one line per sample that ran with its status, best and second entry and margin; `match_matrix`: an
-    .npz with the distances, similarities and the device's sums of all samples that ran.  A sample that moved to another
-    table file is matched under that handle.
-    `snp_file`: one more device pass per launch imputes every sample's expected alternative allele counts
-    at the SNPs of the file; every sample gets `<outbase>.snp_dosage.npz`.  `snp_matrix`: an .npz with the rows of all
-    samples that ran and the SNP file's columns.  The SNPs go to a handle once, not per launch.
-    `scan_pheno` (needs a grid file): a table of phenotypes keyed by outbase.  The grid dosages of every
-    sample that ran and has a phenotype row (and, with `scan_covar`, a covariate row) are collected on the device in the
-    order of `expression_files`; after the last launch the phenotypes are regressed on them at every grid point and
-    `<scan_out>.scan.npz` and `<scan_out>.scan.peaks.tsv` are written (gbrs_amd/scan.py).  `scan_perms`:
-    that many permutations follow the scan on the device and both files gain genome-wide thresholds and p-values; the
-    other `scan_perm_*` are scan.perm_options'."""
+    `error`.  `stage_times`, `context` and `grid_file` as in reconstruct; every other keyword from `expr_threshold` on is
+    described on ReconstructOptions, with what it means for a cohort."""
+    options = ReconstructOptions.of(locals())
+    options.check(True, grid_file if context is None else context.grid_file, tprob_file)
     from . import scan as scan_mod
-    scan_mod.check_scan_args(scan_pheno, scan_covar, scan_rankz, scan_out, scan_min_lod, scan_lod_matrix,
-                             grid_file if context is None else context.grid_file, cohort=True, scan_perms=scan_perms,
-                             scan_perm_seed=scan_perm_seed, scan_perm_alpha=scan_perm_alpha,
-                             scan_perm_chromosomes=scan_perm_chromosomes, scan_perm_pheno=scan_perm_pheno)
     scan_perm = scan_mod.perm_options(scan_perms, scan_perm_seed, scan_perm_alpha, scan_perm_chromosomes, scan_perm_pheno)
-    check_sim_geno_args(sim_geno, sim_geno_seed)
-    check_snp_args(snp_file, snp_matrix, cohort=True)
-    check_diagnostics_args(diagnostics, error_lod_threshold, gene_report, cohort=True)
-    check_match_args(match_panel, match_labels, match_expected, match_chromosomes, match_report, match_matrix,
-                     grid_file if context is None else context.grid_file, cohort=True)
-    if context is not None and alt_tprob_files is None:
-        alt_tprob_files = context.alt_tprob_files
-    check_loglik_args(loglik, alt_tprob_files, model_report, cohort=True, tprob_file=tprob_file)
-    loglik = bool(loglik or alt_tprob_files)
     clock = time.perf_counter
     marks = stage_times if stage_times is not None else {}
     if len(expression_files) != len(outbases):
@@ -1644,142 +1776,40 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
         return done
     haplotypes = list(next(iter(headers.values())))
     num_haps = len(haplotypes)
-    diplotypes = [a + b for a, b in combinations_with_replacement(haplotypes, 2)]
     ctx = context if context is not None else ReconstructContext(tprob_file, avec_file, gpos_file, device, grid_file,
-                                                                 alt_tprob_files)
+                                                                 options.alt_tprob_files)
     _lib.warm_up_device_async(device)
     t0 = clock()
     ctx.load()
-    if loglik and ctx.alt_tprob_files and ctx.chroms:
+    if options.loglik and ctx.alt_tprob_files and ctx.chroms:
         ctx.alt_tables(num_haps)           # a file that does not fit is refused before any sample runs
-    matches = {}                           # sample -> (cross, sample_norm, distance, similarity, rank_matches' dict)
-    if match_panel is not None:
-        labels = read_match_labels(match_labels) if match_labels is not None else {}
-        match_use, match_points = _load_panel(ctx, match_panel, haplotypes, match_chromosomes)
-    snps = _load_snps(ctx, snp_file, haplotypes) if snp_file is not None else None
-    snp_rows = {}                          # sample -> its dosages in SNP file order
+    labels = read_match_labels(match_labels) if match_labels is not None else {}
+    shared = _Shared(ctx, options, haplotypes, tprob_file, marks, lambda line: None, 'hmm',
+                     {k: labels[o] for k, o in enumerate(outbases) if o in labels})
     scan = scan_ids = None                 # the cohort's GenomeScan (made with the first launch) and its samples' outbases
+    scan_held = shared.scan_held
     if scan_pheno is not None:
         scan_tables = (scan_mod.read_scan_pheno(scan_pheno),
                        scan_mod.read_scan_covar(scan_covar) if scan_covar is not None else None)
-        scan_ids, scan_held = [], {}       # scan_held: sample -> its host dosage rows, until its batch is appended
+        scan_ids = []
         scan_unsaved = set()               # samples whose files could not be written: reported once, left out of the scan
-        scan_keep = set(scan_mod.scan_design(outbases, *scan_tables)[0])
+        shared.scan_keep = set(scan_mod.scan_design(outbases, *scan_tables)[0])
         if scan_perm is not None:          # a name the table or the grid does not have is refused before a sample runs
             scan_mod.perm_plan(scan_perm, scan_tables[0][0], [str(c) for c in ctx.chroms])
     marks['load'] = clock() - t0
-    for key in ('read', 'hmm', 'grid', 'save') + (('loglik',) if loglik else ()) + \
-            (('match',) if match_panel is not None else ()) + (('snp',) if snps is not None else ()) + \
+    for key in ('read', 'hmm', 'grid', 'save') + (('loglik',) if options.loglik else ()) + \
+            (('match',) if match_panel is not None else ()) + (('snp',) if snp_file is not None else ()) + \
             (('scan',) if scan_pheno is not None else ()) + (('scan_perm',) if scan_perm is not None else ()):
         marks[key] = 0.0
-    names = [tprob_file] + list(ctx.alt_tprob_files) if loglik else None
-    choices = {}                           # sample -> (selected candidate, margin, totals per candidate)
     from concurrent.futures import ThreadPoolExecutor
     writers = ThreadPoolExecutor(max_workers=min(16, batch_size))
     pending = []
 
-    def save(k, results, on_grid, drawn=None, diag=None, on=None, scores=None, matched=None):
-        on = ctx if on is None else on     # the context the sample ran under
-        _save_reconstruction(outbases[k], *results, threads=1)
-        if on_grid is not None:
-            _save_grid(outbases[k], on, haplotypes, on_grid[0], on_grid[1], threads=1)
-        if drawn is not None:
-            _save_sim_geno(outbases[k], on, diplotypes, drawn, sim_geno_seed, k, threads=1)
-        if diag is not None:
-            _save_diagnostics(outbases[k], on, diplotypes, diag, error_lod_threshold, threads=1)
-        if scores is not None:
-            write_loglik_table(f'{outbases[k]}.loglik.tsv', ctx.chroms, [len(ctx.gene_order[c]) for c in ctx.chroms], names,
-                               scores, choices[k][0])
-        if matched is not None:
-            write_match_table(f'{outbases[k]}.match.tsv', ctx.panel[0], matched[2], matched[3], matched[4]['order'])
-        if k in snp_rows:
-            write_snp_dosage(f'{outbases[k]}.snp_dosage.npz', snp_rows[k], snps)
-
-    report = None
-
-    def launch(on, members, rows, scores_of=None):
-        """The samples `members` (their TPM rows in `rows`) through the handle of context `on` and out to their files.
-        With candidates to weigh (`on` is ctx): returns {alternative: [positions in members]} of the samples that one of
-        them explains better; those are not saved here.  scores_of: the (K, n_chrom) likelihoods of samples that were
-        weighed in an earlier launch."""
-        nonlocal report
+    def write_out(on, bundles):
         t0 = clock()
-        first_use = on.hmm is None or on.hmm.H != num_haps
-        spec = on.specificity(num_haps) if first_use else None
-        hmm, _ = on.handle(num_haps)
-        stacked = [np.stack([r[ci] for r in rows]) for ci in range(len(on.chroms))]
-        if first_use:
-            hmm.set_expression(stacked, [x[0] for x in spec], [x[1] for x in spec], expr_threshold, sigma)
-        else:
-            hmm.set_expression(stacked, expr_threshold=expr_threshold, sigma=sigma)
-        hmm.run()
-        moved, stay = {}, list(range(len(members)))
-        if loglik and on is ctx:
-            t1 = clock()
-            per = _model_logliks(ctx, hmm, num_haps)
-            totals = loglik_totals(per)
-            best, margin = choose_tables(totals)
-            scores_of = {}
-            for s, k in enumerate(members):
-                choices[k] = (int(best[s]), float(margin[s]), totals[:, s].copy())
-                scores_of[k] = per[:, s, :].copy()
-                if best[s] != 0:
-                    moved.setdefault(int(best[s]) - 1, []).append(s)
-            stay = [s for s in stay if best[s] == 0]
-            marks['loglik'] += clock() - t1
-            t0 += clock() - t1
-        results = {s: _collect(on, hmm, s, diplotypes) for s in stay}
-        marks['hmm'] += clock() - t0
-        on_grid = None
-        if on.grid is not None and stay:
-            t0 = clock()
-            on_grid = hmm.grid(want=('dosage', 'gamma_grid') if grid_genoprobs else ('dosage',))
-            marks['grid'] += clock() - t0
-        if scan_pheno is not None and on_grid is not None:
-            for s in stay:
-                if members[s] in scan_keep:
-                    scan_held[members[s]] = on_grid['dosage'][s]
-        if match_panel is not None and stay:
-            t0 = clock()
-            got = hmm.match()
-            panel_norm = hmm.match_info()['panel_norm']
-            distance, similarity = match_scores(got['cross'], got['sample_norm'], panel_norm, match_points, match_use)
-            for s in stay:
-                k = members[s]
-                matches[k] = (got['cross'][s], got['sample_norm'][s], distance[s], similarity[s],
-                              rank_matches(ctx.panel[0], distance[s], labels.get(outbases[k])))
-            matches['panel_norm'] = panel_norm
-            marks['match'] += clock() - t0
-        if snps is not None and stay:
-            t0 = clock()
-            got = snp_dosage_in_file_order(snps, hmm.impute() if len(snps['order']) else np.zeros((len(members), 0)))
-            for s in stay:
-                snp_rows[members[s]] = got[s]
-            marks['snp'] += clock() - t0
-        drawn = None
-        if sim_geno is not None and stay:
-            t0 = clock()
-            drawn = _draw_paths(hmm, sim_geno, sim_geno_seed, members)
-            marks['sim_geno'] = marks.get('sim_geno', 0.0) + clock() - t0
-        diags = None
-        if diagnostics and stay:
-            t0 = clock()
-            diags = _diagnose(hmm, rows, expr_threshold)
-            if gene_report is not None:
-                if report is None:
-                    report = GeneReport(ctx, error_lod_threshold)
-                for s in stay:
-                    report.add(diags[s])
-            marks['diagnostics'] = marks.get('diagnostics', 0.0) + clock() - t0
-        t0 = clock()
-        for s in stay:
-            k = members[s]
-            grid_of = None if on_grid is None else (on_grid['dosage'][s], on_grid['gamma_grid'][s] if grid_genoprobs else None)
-            pending.append((k, writers.submit(save, k, results[s], grid_of, None if drawn is None else drawn[s],
-                                              None if diags is None else diags[s], on,
-                                              None if scores_of is None else scores_of[k], matches.get(k))))
+        for k, bundle in bundles.items():
+            pending.append((k, writers.submit(_save_sample, outbases[k], on, bundle, shared, 1)))
         marks['save'] += clock() - t0
-        return moved, scores_of
 
     try:
         order = sorted(headers)
@@ -1795,21 +1825,14 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
                     failed(k, e)
             marks['read'] += clock() - t0
             if not members or not ctx.chroms:
-                nothing = None if sim_geno is None else ([], np.zeros((sim_geno, 0), dtype=np.int32), [])
-                for k in members:
-                    if snps is not None:
-                        snp_rows[k] = np.full(len(snps['snp_id']), np.nan)
-                    if loglik:
-                        choices[k] = (0, 0.0 if len(names) > 1 else np.inf, np.zeros(len(names)))
-                    pending.append((k, writers.submit(save, k, ({}, {}, {}), None, nothing,
-                                                      _no_diagnostics() if diagnostics else None, None,
-                                                      np.zeros((len(names), 0)) if loglik else None)))
+                write_out(ctx, {k: _nothing_ran(ctx, shared, k) for k in members})
                 continue
-            moved, scores_of = launch(ctx, members, rows)
+            bundles, moved = _launch(ctx, members, rows, shared)
+            write_out(ctx, bundles)
             # The samples an alternative explains better, under a handle on that file: each in a launch of its own, which
             # is the single-sample command's launch, so its files do not depend on who else moved or on the batch size.
-            for s, a in sorted((s, a) for a in moved for s in moved[a]):
-                launch(ctx.alt_context(a), [members[s]], [rows[s]], scores_of)
+            for k, a in sorted((k, a) for a in moved for k in moved[a]):
+                write_out(ctx.alt_context(a), _launch(ctx.alt_context(a), [k], [rows[members.index(k)]], shared)[0])
             if scan_pheno is not None and scan_held:
                 # A sample that failed is left out, and a sample has not succeeded before its files are written: the
                 # batch's writes are waited for here (with the scan they do not overlap the next launch).  Then the
@@ -1846,23 +1869,24 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
             except Exception as e:   # noqa: BLE001
                 failed(k, e)
         if gene_report is not None:
-            (report if report is not None else GeneReport(ctx, error_lod_threshold)).write(gene_report)
+            (shared.report if shared.report is not None else GeneReport(ctx, error_lod_threshold)).write(gene_report)
         if model_report is not None:
-            write_model_report(model_report, names, [(outbases[k],) + choices[k] for k in sorted(choices)])
+            write_model_report(model_report, shared.names, [(outbases[k],) + shared.choices[k] for k in sorted(shared.choices)])
         if match_panel is not None:
-            ran = sorted(k for k in matches if k != 'panel_norm')
+            matches, ran = shared.matches, sorted(shared.matches)
             if match_report is not None:
                 write_match_report(match_report, [(outbases[k], matches[k][4]) for k in ran])
             if match_matrix is not None:
                 M, nc = len(ctx.panel[0]), len(ctx.chroms)
                 stack = lambda i, shape: np.stack([matches[k][i] for k in ran]) if ran else np.zeros(shape)
-                write_match_matrix(match_matrix, [outbases[k] for k in ran], ctx.panel[0], ctx.chroms, match_points,
+                write_match_matrix(match_matrix, [outbases[k] for k in ran], ctx.panel[0], ctx.chroms, shared.match_points,
                                    stack(2, (0, M)), stack(3, (0, M)), stack(0, (0, nc, M)), stack(1, (0, nc)),
-                                   matches.get('panel_norm', np.zeros((M, nc))))
+                                   shared.panel_norm if shared.panel_norm is not None else np.zeros((M, nc)))
         if snp_matrix is not None:
-            ran = sorted(snp_rows)
+            ran = sorted(shared.snp_rows)
             write_snp_matrix(snp_matrix, [outbases[k] for k in ran],
-                             np.stack([snp_rows[k] for k in ran]) if ran else np.zeros((0, len(snps['snp_id']))), snps)
+                             np.stack([shared.snp_rows[k] for k in ran]) if ran else np.zeros((0, len(shared.snps['snp_id']))),
+                             shared.snps)
         marks['save'] += clock() - t0
         if scan_pheno is not None:
             t0 = clock()
@@ -1882,3 +1906,5 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
             ctx.close()
     logger.info('Done')
     return done
+
+

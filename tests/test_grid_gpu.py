@@ -372,6 +372,47 @@ def test_reconstruct_many_in_partial_batches(tmp_path, tables, caplog):
         assert read_calls(tmp_path / f"many{k}.genotypes.tsv") == read_calls(tmp_path / f"chain{k}.genotypes.tsv")
 
 
+def test_the_command_and_a_cohort_write_the_same_files_with_every_option_on(tmp_path, tables):
+    """`--grid-file --grid-genoprobs --sim-geno 3 --diagnostics --loglik --match-panel --snp-file` together: the
+    single-sample command on sample 0 and a `--sample-file` cohort whose first line is that sample (three samples in
+    launches of two) write byte-identical files for every suffix the sample gets; the cohort's first sample draws on stream
+    0, so `sim_geno.npz` is among them.  `snp_dosage.npz` is compared array by array: np.savez stamps every member of the
+    archive with the time of writing."""
+    import impute_cases
+    import match_cases
+    from gbrs_amd import cli
+    p0 = grid_cases.problem(H_FILES, STYLE_FILES)
+    grid = grid_cases.grids()["b"]
+    rng = np.random.default_rng(grid_cases.SEED + 7)
+    panel = match_cases.write_panel(tmp_path, [f"entry{k}" for k in range(5)],
+                                    match_cases.random_panel(rng, 5, sum(len(x) for x in grid.points.values()), H_FILES),
+                                    p0.hap_names)
+    snps = impute_cases.snp_sets()["b"]                             # the positions of grid "b": the same gene positions
+    snp_file = impute_cases.write_snp_file(tmp_path / "snps.tsv", H_FILES, snps.points, impute_cases.masks_for("b", H_FILES),
+                                           extra=[("MT", 1.0, "10000000")])
+    tpms = [sample_tpm(tmp_path, s) for s in range(3)]
+    (tmp_path / "samples.txt").write_text("".join(f"{tpms[s]}\t{tmp_path / f'many{s}'}\n" for s in range(3)))
+    options = ["-t", tables["tprob"], "-x", tables["avecs"], "-g", tables["gpos"], "--grid-file", tables["grid"],
+               "--grid-genoprobs", "--sim-geno", "3", "--diagnostics", "--loglik", "--match-panel", panel, "--snp-file", snp_file]
+    assert cli.main(["reconstruct", "-e", tpms[0], "-o", str(tmp_path / "one")] + options) == 0
+    assert cli.main(["reconstruct", "--sample-file", str(tmp_path / "samples.txt"), "--batch-size", "2"] + options) == 0
+    suffixes = ("genotypes.tsv", "genoprobs.npz", "genotypes.npz", "interpolated.genoprobs.tsv", "interpolated.genoprobs.npz",
+                "sim_geno.npz", "sim_geno.crossovers.tsv", "diagnostics.npz", "diagnostics.tsv", "loglik.tsv", "match.tsv",
+                "snp_dosage.npz")
+    for stem in ("one", "many0", "many1", "many2"):
+        assert sorted(f.name for f in tmp_path.glob(f"{stem}.*")) == sorted(f"{stem}.{s}" for s in suffixes)
+    for suffix in suffixes:
+        one, many = tmp_path / f"one.{suffix}", tmp_path / f"many0.{suffix}"
+        if suffix == "snp_dosage.npz":
+            a, b = np.load(one), np.load(many)
+            assert a.files == b.files
+            for k in a.files:
+                np.testing.assert_array_equal(a[k], b[k], err_msg=k)
+        else:
+            assert one.read_bytes() == many.read_bytes(), suffix
+    assert np.load(tmp_path / "one.sim_geno.npz")["stream"] == 0
+
+
 def test_reconstruct_many_header_mismatch(tmp_path, tables):
     from gbrs_amd.hmm import reconstruct_many
     first = sample_tpm(tmp_path, 0)

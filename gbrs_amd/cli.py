@@ -136,6 +136,10 @@ def build_parser():
                         'the founder dosages of the samples that ran at every grid point (Haley-Knott, on the device); writes '
                         '<PREFIX>.scan.npz and <PREFIX>.scan.peaks.tsv')
     _scan_options(r)
+    r.add_argument('--scan-snps', action='store_true',
+                   help='with --snp-file, --scan-pheno, --grid-file and --sample-file: every SNP of the file is tested with '
+                        'one degree of freedom on the allele dosage its founder pattern implies, on the device (the cM column '
+                        'in the grid file\'s position units); writes <PREFIX>.scan.snps.npz and <PREFIX>.scan.snps.peaks.tsv')
     r.add_argument('-t', '--tprob-file', required=True, type=_existing)
     r.add_argument('-x', '--avec-file', type=_existing, default=None)
     r.add_argument('-g', '--gpos-file', type=_existing, default=None)
@@ -153,6 +157,10 @@ def build_parser():
     sc.add_argument('--covar', dest='scan_covar', type=_existing, default=None, metavar='FILE',
                     help='additive covariates: the same layout, numeric; the intercept is added')
     _scan_options(sc, covar=False)
+    sc.add_argument('--snp-file', type=_existing, default=None, metavar='FILE',
+                    help='SNP association after the scan: `id, chr, bp, cM, pattern` as for reconstruct --snp-file, the '
+                         'haplotypes those of the dosage tables\' header, cM in the grid file\'s position units; writes '
+                         '<PREFIX>.scan.snps.npz and <PREFIX>.scan.snps.peaks.tsv')
     sc.add_argument('-v', '--verbose', action='count', default=0)
     sc.add_argument('--device', type=int, default=0)
     it = sub.add_parser('interpolate', help='interpolate probability on a decently-spaced grid')
@@ -427,7 +435,7 @@ def main(argv=None) -> int:
                         lod_matrix=args.scan_lod_matrix, device=args.device, scan_perms=args.scan_perms,
                         scan_perm_seed=args.scan_perm_seed, scan_perm_alpha=args.scan_perm_alpha,
                         scan_perm_chromosomes=args.scan_perm_chromosomes, scan_perm_pheno=args.scan_perm_pheno,
-                        stage_times=stages)
+                        stage_times=stages, snp_file=args.snp_file)
         elif args.command == 'interpolate':
             from .postproc import interpolate
             interpolate(genoprob_file=args.genoprob_file, grid_file=args.grid_file, gpos_file=args.gpos_file,

@@ -9,7 +9,9 @@
 // the K chunk: the operand maps, the LDS stride and the prefetch are those of match_cross_kernel (hmm_match.inc), without
 // its K tail and its 8-byte staging.  permute (kernels in scan_perm.inc): permutations of the projected
 // phenotypes, drawn and gathered on the device, pass through the same product and peak kernels as further columns, and
-// one maximum per (phenotype, permutation) comes back.
+// one maximum per (phenotype, permutation) comes back.  SNP association (kernels and the rule in
+// scan_snp.inc): a row kernel builds one normalised row per founder SNP from two grid points and a bit pattern, and a
+// sibling of the product kernel with one row per SNP turns the rows into LODs.
 #include "common.h"
 #include "scan_hmm.h"
 
@@ -309,6 +311,10 @@ scan_peak_kernel(int64_t M, int n_chrom, const int64_t *__restrict__ point_off, 
 #include "philox.h"
 #include "scan_perm.inc"
 
+// ---- SNP association ---------------------------------------------------------------------------------------------------------
+
+#include "scan_snp.inc"
+
 }  // namespace gbrs
 
 using namespace gbrs;
@@ -339,6 +345,21 @@ struct gbrs_scan {
     int64_t perm_P = 0, perm_B = 0;
     double t_permute = 0, t_perm_product = 0;
     uint64_t perm_peak_bytes = 0;
+    // the SNPs of gbrs_scan_set_snps in handle order (chromosome after chromosome): SS_TABLE_BYTES per SNP
+    int64_t M_snp = 0;
+    std::vector<int64_t> snp_off;             // n_chrom + 1
+    DevBuf<int64_t> d_snp_off;
+    DevBuf<int32_t> snp_lo, snp_hi;           // global point indices
+    DevBuf<uint32_t> snp_mask;
+    DevBuf<double> snp_t;
+    // the last gbrs_scan_snps: its buffers are the call's own, as gbrs_scan_permute's
+    int64_t snp_P = 0;
+    int snp_staged = 0;
+    double t_snp_pass = 0, t_snp_row = 0, t_snp_product = 0;
+    uint64_t snp_peak_bytes = 0;
+    uint64_t snp_bytes() const {
+        return d_snp_off.bytes() + snp_lo.bytes() + snp_hi.bytes() + snp_mask.bytes() + snp_t.bytes();
+    }
 };
 
 namespace {
@@ -692,6 +713,233 @@ int gbrs_scan_perm_info(gbrs_scan_t *s, gbrs_scan_perm_info_t *info) {
     info->last_permute_ms = s->t_permute;
     info->last_product_ms = s->t_perm_product;
     info->peak_device_bytes = s->perm_peak_bytes;
+    return GBRS_OK;
+}
+
+int gbrs_scan_set_snps(gbrs_scan_t *s, const double *const *grid_pos, const int64_t *n_snps, const double *const *snp_pos,
+                       const uint32_t *const *snp_mask) {
+    RoctxRange roctx_range("gbrs_scan_set_snps");
+    if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (!n_snps) return fail(GBRS_ERR_INVALID, "n_snps is NULL");
+    std::vector<int64_t> off((size_t)s->n_chrom + 1, 0);
+    for (int c = 0; c < s->n_chrom; ++c) {
+        if (n_snps[c] < 0) return fail(GBRS_ERR_INVALID, "chromosome %d has a negative number of SNPs", c);
+        off[c + 1] = off[c] + n_snps[c];
+    }
+    const int64_t M_snp = off[s->n_chrom];
+    if (M_snp == 0) {                   // all-zero counts drop the SNPs
+        s->M_snp = 0;
+        s->snp_off.clear();
+        s->d_snp_off.release();
+        s->snp_lo.release();
+        s->snp_hi.release();
+        s->snp_mask.release();
+        s->snp_t.release();
+        return GBRS_OK;
+    }
+    if (!grid_pos || !snp_pos || !snp_mask) return fail(GBRS_ERR_INVALID, "bad argument");
+    const uint32_t beyond = s->H >= 32 ? 0u : ~0u << s->H;
+    for (int c = 0; c < s->n_chrom; ++c) {
+        const int64_t k = s->points[c];
+        if (k > 0 && !grid_pos[c]) return fail(GBRS_ERR_INVALID, "chromosome %d has no grid positions", c);
+        for (int64_t i = 0; i < k; ++i) {
+            if (!std::isfinite(grid_pos[c][i]))
+                return fail(GBRS_ERR_INVALID, "grid position %lld of chromosome %d is not finite", (long long)i, c);
+            if (i > 0 && grid_pos[c][i] < grid_pos[c][i - 1])
+                return fail(GBRS_ERR_INVALID, "the grid positions of chromosome %d decrease at index %lld", c, (long long)i);
+        }
+        if (n_snps[c] == 0) continue;
+        if (k == 0) return fail(GBRS_ERR_INVALID, "chromosome %d has %lld SNPs and no grid point", c, (long long)n_snps[c]);
+        if (!snp_pos[c] || !snp_mask[c]) return fail(GBRS_ERR_INVALID, "chromosome %d has SNPs and no positions or patterns", c);
+        for (int64_t i = 0; i < n_snps[c]; ++i) {
+            if (!std::isfinite(snp_pos[c][i]))
+                return fail(GBRS_ERR_INVALID, "SNP %lld of chromosome %d has a position that is not finite", (long long)i, c);
+            if (snp_mask[c][i] & beyond)
+                return fail(GBRS_ERR_INVALID, "SNP %lld of chromosome %d has a pattern bit at or above the %d founders", (long long)i, c,
+                            s->H);
+        }
+    }
+    GBRS_TRY(select_device(s->device));
+    // everything is built beside what the handle holds and swapped in at the end: a failure leaves the handle as it was
+    std::vector<double> h_grid((size_t)s->M), h_pos((size_t)M_snp);
+    std::vector<uint32_t> h_mask((size_t)M_snp);
+    for (int c = 0; c < s->n_chrom; ++c) {
+        if (s->points[c] > 0) std::memcpy(h_grid.data() + s->point_off[c], grid_pos[c], (size_t)s->points[c] * sizeof(double));
+        if (n_snps[c] > 0) {
+            std::memcpy(h_pos.data() + off[c], snp_pos[c], (size_t)n_snps[c] * sizeof(double));
+            std::memcpy(h_mask.data() + off[c], snp_mask[c], (size_t)n_snps[c] * sizeof(uint32_t));
+        }
+    }
+    DevBuf<double> d_grid, d_pos, d_t;
+    DevBuf<int64_t> d_off;
+    DevBuf<int32_t> d_lo, d_hi;
+    DevBuf<uint32_t> d_mask;
+    GBRS_TRY(d_grid.alloc(h_grid.size()));
+    GBRS_TRY(d_pos.alloc(h_pos.size()));
+    GBRS_TRY(d_t.alloc((size_t)M_snp));
+    GBRS_TRY(d_off.alloc(off.size()));
+    GBRS_TRY(d_lo.alloc((size_t)M_snp));
+    GBRS_TRY(d_hi.alloc((size_t)M_snp));
+    GBRS_TRY(d_mask.alloc((size_t)M_snp));
+    GBRS_HIP_CHECK(hipMemcpy(d_grid.p, h_grid.data(), d_grid.bytes(), hipMemcpyHostToDevice));
+    GBRS_HIP_CHECK(hipMemcpy(d_pos.p, h_pos.data(), d_pos.bytes(), hipMemcpyHostToDevice));
+    GBRS_HIP_CHECK(hipMemcpy(d_mask.p, h_mask.data(), d_mask.bytes(), hipMemcpyHostToDevice));
+    GBRS_HIP_CHECK(hipMemcpy(d_off.p, off.data(), d_off.bytes(), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(scan_snp_locate_kernel, dim3((unsigned)((M_snp + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0, s->stream,
+                       M_snp, s->n_chrom, d_off.p, s->d_point_off.p, d_grid.p, d_pos.p, d_lo.p, d_hi.p, d_t.p);
+    GBRS_HIP_CHECK(hipGetLastError());
+    GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
+    s->d_snp_off.swap(d_off);
+    s->snp_lo.swap(d_lo);
+    s->snp_hi.swap(d_hi);
+    s->snp_mask.swap(d_mask);
+    s->snp_t.swap(d_t);
+    s->snp_off.swap(off);
+    s->M_snp = M_snp;
+    return GBRS_OK;
+}
+
+int gbrs_scan_snp_dosage(gbrs_scan_t *s, int64_t first, int64_t count, double *out) {
+    RoctxRange roctx_range("gbrs_scan_snp_dosage");
+    if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (s->M_snp == 0) return fail(GBRS_ERR_INVALID, "no SNPs on the handle: call gbrs_scan_set_snps first");
+    if (s->n == 0) return fail(GBRS_ERR_INVALID, "no samples on the handle");
+    if (first < 0 || count < 0 || first > s->M_snp || count > s->M_snp - first)
+        return fail(GBRS_ERR_INVALID, "SNPs %lld .. %lld are out of range: the handle has %lld", (long long)first,
+                    (long long)(first + count), (long long)s->M_snp);
+    if (count == 0) return GBRS_OK;
+    if (!out) return fail(GBRS_ERR_INVALID, "out is NULL");
+    GBRS_TRY(select_device(s->device));
+    const int n = (int)s->n;
+    const int64_t step = std::max<int64_t>(1, std::min(count, ((int64_t)1 << 24) / n));     // at most 128 MB of workspace
+    DevBuf<double> buf;
+    GBRS_TRY(buf.alloc((size_t)n * step));
+    for (int64_t j0 = 0; j0 < count; j0 += step) {
+        const int64_t jc = std::min(step, count - j0);
+        hipLaunchKernelGGL(scan_snp_dosage_kernel, dim3((unsigned)((n * jc + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0,
+                           s->stream, n, s->M, s->H, first + j0, jc, s->dosage.p, s->snp_lo.p, s->snp_hi.p, s->snp_mask.p, s->snp_t.p,
+                           buf.p);
+        GBRS_HIP_CHECK(hipGetLastError());
+        GBRS_HIP_CHECK(hipMemcpy2DAsync(out + j0, (size_t)count * sizeof(double), buf.p, (size_t)jc * sizeof(double),
+                                        (size_t)jc * sizeof(double), (size_t)n, hipMemcpyDeviceToHost, s->stream));
+        GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
+    }
+    return GBRS_OK;
+}
+
+int gbrs_scan_snps(gbrs_scan_t *s, int64_t P, const double *pheno, double *lod, uint8_t *used, double *peak_lod,
+                   int64_t *peak_index) {
+    RoctxRange roctx_range("gbrs_scan_snps");
+    if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (s->c == 0) return fail(GBRS_ERR_INVALID, "no covariates on the handle: call gbrs_scan_prepare first");
+    if (s->M_snp == 0) return fail(GBRS_ERR_INVALID, "no SNPs on the handle: call gbrs_scan_set_snps first");
+    if (P < 1) return fail(GBRS_ERR_INVALID, "a SNP pass needs at least 1 phenotype, got %lld", (long long)P);
+    if (!pheno) return fail(GBRS_ERR_INVALID, "bad argument");
+    const int n = (int)s->n;
+    for (int64_t k = 0; k < (int64_t)n * P; ++k)
+        if (!std::isfinite(pheno[k]))
+            return fail(GBRS_ERR_INVALID, "phenotype %lld holds a value that is not finite (sample %lld)", (long long)(k % P),
+                        (long long)(k / P));
+    GBRS_TRY(select_device(s->device));
+    const int64_t M_snp = s->M_snp, n_ld = s->n_ld, yc_max = std::min(P, SC_PCHUNK), lc_max = std::min(M_snp, SS_CHUNK);
+    const int nc = s->n_chrom;
+    // the two points of a run in LDS when the device has the room
+    int lds_max = 0;
+    GBRS_HIP_CHECK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, s->device));
+    const size_t pair_bytes = (size_t)2 * s->H * (n | 1) * sizeof(double);
+    const int staged = pair_bytes <= (size_t)lds_max;
+    if (staged)
+        GBRS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(scan_snp_row_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)pair_bytes));
+    DevBuf<double> y, yt_all, rss_all, w, d_lod, d_peak;
+    DevBuf<int64_t> d_index;
+    DevBuf<uint8_t> d_used;
+    GBRS_TRY(y.alloc((size_t)n * yc_max));
+    GBRS_TRY(yt_all.alloc((size_t)P * n_ld));
+    GBRS_TRY(rss_all.alloc((size_t)P));
+    GBRS_TRY(w.alloc((size_t)lc_max * n_ld));
+    GBRS_TRY(d_lod.alloc((size_t)yc_max * lc_max));
+    GBRS_TRY(d_used.alloc((size_t)lc_max));
+    GBRS_TRY(d_peak.alloc((size_t)P * nc));
+    GBRS_TRY(d_index.alloc((size_t)P * nc));
+    EventRing row_ring, product_ring;
+    GBRS_TRY(row_ring.create());
+    GBRS_TRY(product_ring.create());
+    GBRS_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
+    GBRS_HIP_CHECK(hipMemsetAsync(d_index.p, 0xFF, d_index.bytes(), s->stream));         // -1: nothing yet
+    // y~ of every phenotype, by gbrs_scan_run's kernel in gbrs_scan_run's chunks; it stays on the device for the pass
+    for (int64_t p0 = 0; p0 < P; p0 += SC_PCHUNK) {
+        const int64_t pc = std::min(SC_PCHUNK, P - p0);
+        GBRS_HIP_CHECK(hipMemcpy2DAsync(y.p, (size_t)pc * sizeof(double), pheno + p0, (size_t)P * sizeof(double),
+                                        (size_t)pc * sizeof(double), (size_t)n, hipMemcpyHostToDevice, s->stream));
+        hipLaunchKernelGGL(scan_pheno_kernel, dim3((unsigned)pc), dim3(64), 0, s->stream, n, s->c, n_ld, pc, y.p, s->qz.p,
+                           yt_all.p + p0 * n_ld, rss_all.p + p0);
+        GBRS_HIP_CHECK(hipGetLastError());
+    }
+    for (int64_t j0 = 0; j0 < M_snp; j0 += SS_CHUNK) {
+        const int64_t jc = std::min(SS_CHUNK, M_snp - j0);
+        int slot = 0;
+        GBRS_TRY(row_ring.next(&slot));
+        GBRS_HIP_CHECK(hipEventRecord(row_ring.ev[2 * slot], s->stream));
+        hipLaunchKernelGGL(scan_snp_row_kernel, dim3((unsigned)((jc + SS_BLOCK - 1) / SS_BLOCK)), dim3(SC_THREADS),
+                           staged ? pair_bytes : 0, s->stream, n, s->M, s->H, s->c, n_ld, j0, jc, staged, s->dosage.p, s->qz.p,
+                           s->snp_lo.p, s->snp_hi.p, s->snp_mask.p, s->snp_t.p, w.p, d_used.p);
+        GBRS_HIP_CHECK(hipEventRecord(row_ring.ev[2 * slot + 1], s->stream));
+        GBRS_HIP_CHECK(hipGetLastError());
+        if (used) GBRS_HIP_CHECK(hipMemcpyAsync(used + j0, d_used.p, (size_t)jc, hipMemcpyDeviceToHost, s->stream));
+        for (int64_t p0 = 0; p0 < P; p0 += SC_PCHUNK) {
+            const int64_t pc = std::min(SC_PCHUNK, P - p0);
+            GBRS_TRY(product_ring.next(&slot));
+            GBRS_HIP_CHECK(hipEventRecord(product_ring.ev[2 * slot], s->stream));
+            hipLaunchKernelGGL(scan_snp_lod_kernel, dim3((unsigned)((jc + SC_ROWS - 1) / SC_ROWS), (unsigned)((pc + SC_COLS - 1) / SC_COLS)),
+                               dim3(SC_THREADS), 0, s->stream, jc, pc, n_ld, jc, 0.5 * n, w.p, yt_all.p + p0 * n_ld, rss_all.p + p0,
+                               d_lod.p);
+            GBRS_HIP_CHECK(hipEventRecord(product_ring.ev[2 * slot + 1], s->stream));
+            hipLaunchKernelGGL(scan_snp_peak_kernel, dim3((unsigned)nc, (unsigned)pc), dim3(64), 0, s->stream, j0, jc, jc, nc,
+                               s->d_snp_off.p, d_used.p, d_lod.p, d_peak.p + p0 * nc, d_index.p + p0 * nc);
+            GBRS_HIP_CHECK(hipGetLastError());
+            if (lod)        // waits for the kernels before it on the stream; the next chunk's product overwrites d_lod after it
+                GBRS_HIP_CHECK(hipMemcpy2DAsync(lod + p0 * M_snp + j0, (size_t)M_snp * sizeof(double), d_lod.p,
+                                                (size_t)jc * sizeof(double), (size_t)jc * sizeof(double), (size_t)pc,
+                                                hipMemcpyDeviceToHost, s->stream));
+        }
+    }
+    GBRS_HIP_CHECK(hipEventRecord(s->ev[1], s->stream));
+    GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
+    GBRS_TRY(row_ring.drain());
+    GBRS_TRY(product_ring.drain());
+    std::vector<double> h_peak((size_t)P * nc);
+    std::vector<int64_t> h_index((size_t)P * nc);
+    GBRS_HIP_CHECK(hipMemcpy(h_peak.data(), d_peak.p, d_peak.bytes(), hipMemcpyDeviceToHost));
+    GBRS_HIP_CHECK(hipMemcpy(h_index.data(), d_index.p, d_index.bytes(), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < h_peak.size(); ++k)
+        if (h_index[k] < 0) h_peak[k] = std::numeric_limits<double>::quiet_NaN();
+    if (peak_lod) std::memcpy(peak_lod, h_peak.data(), h_peak.size() * sizeof(double));
+    if (peak_index) std::memcpy(peak_index, h_index.data(), h_index.size() * sizeof(int64_t));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) s->t_snp_pass = ms;
+    s->t_snp_row = row_ring.ms;
+    s->t_snp_product = product_ring.ms;
+    s->snp_P = P;
+    s->snp_staged = staged;
+    s->snp_peak_bytes = s->d_point_off.bytes() + s->dosage.bytes() + s->qz.bytes() + s->W.bytes() + s->d_rank.bytes() + s->y.bytes() +
+                        s->yt.bytes() + s->rss0.bytes() + s->lod.bytes() + s->peak_lod.bytes() + s->peak_index.bytes() + s->snp_bytes() +
+                        y.bytes() + yt_all.bytes() + rss_all.bytes() + w.bytes() + d_lod.bytes() + d_used.bytes() + d_peak.bytes() +
+                        d_index.bytes();
+    return GBRS_OK;
+}
+
+int gbrs_scan_snp_info(gbrs_scan_t *s, gbrs_scan_snp_info_t *info) {
+    if (!s || !info) return fail(GBRS_ERR_INVALID, "bad argument");
+    info->M_snp = s->M_snp;
+    info->chunk = SS_CHUNK;
+    info->P = s->snp_P;
+    info->staged = s->snp_staged;
+    info->last_pass_ms = s->t_snp_pass;
+    info->last_row_ms = s->t_snp_row;
+    info->last_product_ms = s->t_snp_product;
+    info->device_bytes = s->snp_bytes();
+    info->peak_device_bytes = s->snp_peak_bytes;
     return GBRS_OK;
 }
 

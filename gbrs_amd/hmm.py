@@ -1395,7 +1395,9 @@ class ReconstructOptions:
     in the order of `expression_files`; after the last launch the phenotypes are regressed on them at every grid point
     and `<scan_out>.scan.npz` and `<scan_out>.scan.peaks.tsv` are written (gbrs_amd/scan.py, which documents `scan_rankz`,
     `scan_min_lod` and `scan_lod_matrix`).  `scan_perms`: that many permutations follow the scan on the
-    device and both files gain genome-wide thresholds and p-values; the other `scan_perm_*` are scan.perm_options'."""
+    device and both files gain genome-wide thresholds and p-values; the other `scan_perm_*` are scan.perm_options'.
+    `scan_snps` (needs `snp_file`, `scan_pheno` and a grid file): every SNP of the file is then tested with one
+    degree of freedom on the prepared cohort, and `<scan_out>.scan.snps.npz` and `<scan_out>.scan.snps.peaks.tsv` are written."""
     expr_threshold: float = 1.5
     sigma: float = 0.12
     grid_genoprobs: bool = False
@@ -1426,6 +1428,7 @@ class ReconstructOptions:
     scan_perm_alpha: object = None
     scan_perm_chromosomes: object = None
     scan_perm_pheno: str = None
+    scan_snps: bool = False
 
     @classmethod
     def of(cls, keywords):
@@ -1443,7 +1446,7 @@ class ReconstructOptions:
 
     def check(self, cohort, grid_file, tprob_file):
         """Every refusal that needs no file, in the command's order.  cohort: `--sample-file`, not `-e`."""
-        from .scan import check_scan_args
+        from .scan import check_scan_args, check_scan_snp_args
         check_sim_geno_args(self.sim_geno, self.sim_geno_seed)
         check_diagnostics_args(self.diagnostics, self.error_lod_threshold, self.gene_report, cohort=cohort)
         check_loglik_args(self.loglik, self.alt_tprob_files, self.model_report, cohort=cohort, tprob_file=tprob_file)
@@ -1454,6 +1457,7 @@ class ReconstructOptions:
                         self.scan_lod_matrix, grid_file, cohort=cohort, scan_perms=self.scan_perms,
                         scan_perm_seed=self.scan_perm_seed, scan_perm_alpha=self.scan_perm_alpha,
                         scan_perm_chromosomes=self.scan_perm_chromosomes, scan_perm_pheno=self.scan_perm_pheno)
+        check_scan_snp_args(self.scan_snps, self.snp_file, self.scan_pheno, grid_file, cohort=cohort)
 
 
 class _Shared:
@@ -1738,14 +1742,14 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
                      snp_matrix: str = None, scan_pheno: str = None, scan_covar: str = None, scan_rankz: bool = False,
                      scan_out: str = None, scan_min_lod: float = None, scan_lod_matrix: bool = False,
                      scan_perms: int = None, scan_perm_seed: int = None, scan_perm_alpha=None, scan_perm_chromosomes=None,
-                     scan_perm_pheno: str = None) -> list:
+                     scan_perm_pheno: str = None, scan_snps: bool = False) -> list:
     """`gbrs reconstruct` for a cohort whose genes.tpm files exist (extension): one context, the tables on the device
     once, the samples through the HMM in launches of up to `batch_size`, and every pass the options ask for once per
     launch.  Every sample gets the files the single-sample call writes for its outbase.  All samples must carry the same
     haplotype header (RuntimeError before anything runs otherwise).  A sample whose file cannot be read or lacks a gene
     is logged and left out, and the others go on.  Returns one dict per sample: its outbase and, if it failed,
     `error`.  `stage_times`, `context` and `grid_file` as in reconstruct; every other keyword from `expr_threshold` on is
-    described on ReconstructOptions (DESIGN.md §21-§28), with what it means for a cohort."""
+    described on ReconstructOptions (DESIGN.md §21-§29), with what it means for a cohort."""
     options = ReconstructOptions.of(locals())
     options.check(True, grid_file if context is None else context.grid_file, tprob_file)
     from . import scan as scan_mod
@@ -1799,7 +1803,8 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
     marks['load'] = clock() - t0
     for key in ('read', 'hmm', 'grid', 'save') + (('loglik',) if options.loglik else ()) + \
             (('match',) if match_panel is not None else ()) + (('snp',) if snp_file is not None else ()) + \
-            (('scan',) if scan_pheno is not None else ()) + (('scan_perm',) if scan_perm is not None else ()):
+            (('scan',) if scan_pheno is not None else ()) + (('scan_perm',) if scan_perm is not None else ()) + \
+            (('scan_snps',) if scan_snps else ()):
         marks[key] = 0.0
     from concurrent.futures import ThreadPoolExecutor
     writers = ThreadPoolExecutor(max_workers=min(16, batch_size))
@@ -1896,8 +1901,10 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
             scan_mod.finish_scan(scan, scan_out if scan_out is not None else 'gbrs', scan_ids, scan_tables[0], scan_tables[1],
                                  scan_rankz, np.concatenate([[c] * m for _, m, c in slices]),
                                  np.concatenate([np.asarray(ctx.grid[c], dtype=np.float64) for _, _, c in slices]),
-                                 list(ctx.chroms), scan_min_lod, scan_lod_matrix, perm=scan_perm, stage_times=marks)
-            marks['scan'] += clock() - t0 - (marks['scan_perm'] if scan_perm is not None else 0.0)
+                                 list(ctx.chroms), scan_min_lod, scan_lod_matrix, perm=scan_perm, stage_times=marks,
+                                 snps=shared.snps if scan_snps else None, snp_grid=ctx.grid)
+            marks['scan'] += clock() - t0 - (marks['scan_perm'] if scan_perm is not None else 0.0) - \
+                (marks['scan_snps'] if scan_snps else 0.0)
     finally:
         writers.shutdown(wait=True)
         if scan is not None:

@@ -1,6 +1,7 @@
 """Genome scan of phenotypes on founder dosages (extension): `gbrs reconstruct --scan-pheno` and
 `gbrs scan`.  Haley-Knott regression with additive covariates on the device (gbrs_scan_*, gbrs_amd/csrc/scan.hip); the
-host side here is the covariates' QR, the file readers and the writers.  No mixed model."""
+host side here is the covariates' QR, the file readers and the writers.  No mixed model.  `--scan-snps` / `gbrs scan
+--snp-file`: the 1-df test of founder SNPs on the same prepared cohort (gbrs_scan_set_snps, gbrs_scan_snps)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -19,7 +20,8 @@ DEFAULT_PERM_ALPHA = (0.05, 0.1)  # the levels of --scan-perm-alpha
 
 class GenomeScan:
     """Device handle of one cohort on one grid.  append / append_from collect the samples' grid dosages in order,
-    prepare(covariates) builds the phenotype-independent part once, run(pheno) scans any number of phenotypes."""
+    prepare(covariates) builds the phenotype-independent part once, run(pheno) scans any number of phenotypes;
+    set_snps + run_snps(pheno) test founder SNPs with one degree of freedom on the same cohort."""
 
     def __init__(self, num_haps, points_per_chrom, device=0):
         self.H = int(num_haps)
@@ -121,6 +123,68 @@ class GenomeScan:
         _lib.check(_lib.load().gbrs_scan_perm_info(self._h, C.byref(raw)))
         return {'P': raw.P, 'B': raw.B, 'permute_ms': raw.last_permute_ms, 'product_ms': raw.last_product_ms,
                 'peak_device_bytes': raw.peak_device_bytes}
+
+    def set_snps(self, grid_pos, snp_pos, masks):
+        """The SNPs of the handle, per chromosome in the handle's order: grid_pos[c] the positions of
+        the chromosome's grid points, snp_pos[c] the SNP positions in the same units (None or empty: it has none),
+        masks[c] their founder patterns as uint32, bit h set when founder h carries the alternative allele.  The SNPs
+        are numbered chromosome after chromosome, each in the order given.  All empty drops the SNPs.  Independent of
+        prepare; appending samples keeps them."""
+        nc = len(self.points)
+        if len(grid_pos) != nc or len(snp_pos) != nc or len(masks) != nc:
+            raise ValueError(f'{len(grid_pos)} grids, {len(snp_pos)} SNP position arrays and {len(masks)} pattern arrays for '
+                             f'{nc} chromosomes')
+        grid = [np.zeros(0) if g is None else np.ascontiguousarray(g, dtype=np.float64) for g in grid_pos]
+        where = [np.zeros(0) if x is None else np.ascontiguousarray(x, dtype=np.float64) for x in snp_pos]
+        bits = [np.zeros(0, dtype=np.uint32) if m is None else np.ascontiguousarray(m, dtype=np.uint32) for m in masks]
+        for c, (g, x, m) in enumerate(zip(grid, where, bits)):
+            if g.shape != (int(self.points[c]),):
+                raise ValueError(f'chromosome {c}: {g.shape} grid positions for {int(self.points[c])} grid points')
+            if x.shape != m.shape or x.ndim != 1:
+                raise ValueError(f'chromosome {c}: {x.shape} SNP positions and {m.shape} patterns')
+        n_snps = np.asarray([len(x) for x in where], dtype=np.int64)
+        _lib.check(_lib.load().gbrs_scan_set_snps(self._h, _lib.ptr_table(grid), _lib.ptr(n_snps), _lib.ptr_table(where),
+                                                  _lib.ptr_table(bits)))
+        self.snp_points = [int(m) for m in n_snps]
+        self.M_snp = int(n_snps.sum())
+
+    def snp_dosage(self, first=0, count=None):
+        """x_s of the SNPs first .. first + count - 1 (default: to the last) in handle order: [n, count]."""
+        total = self.snp_info()['M_snp']
+        count = total - int(first) if count is None else int(count)
+        out = np.empty((self.n, max(count, 0)))
+        _lib.check(_lib.load().gbrs_scan_snp_dosage(self._h, int(first), count, _lib.ptr(out)))
+        return out
+
+    def run_snps(self, pheno, want_lod=True):
+        """The 1-df test of every SNP of the handle on the prepared cohort.  pheno: [n, P] (or [n]), with run()'s
+        constant-column-to-zeros step.  Returns `used` [M_snp] (bool), `peak_lod` [P, n_chrom], `peak_index`
+        [P, n_chrom] (the SNP's index in handle order; NaN and -1 without a used SNP) and, with want_lod, `lod`
+        [P, M_snp]."""
+        y = np.array(pheno, dtype=np.float64, order='C')
+        if y.ndim == 1:
+            y = y[:, None]
+        if y.ndim != 2 or y.shape[0] != self.n:
+            raise ValueError(f'phenotypes have shape {np.shape(pheno)} for {self.n} samples')
+        if self.n:
+            y[:, (y == y[0]).all(axis=0)] = 0.0
+        P, nc, M_snp = y.shape[1], len(self.points), self.snp_info()['M_snp']
+        lod = np.empty((P, M_snp)) if want_lod else None
+        used = np.zeros(M_snp, dtype=np.uint8)
+        peak, index = np.empty((P, nc)), np.empty((P, nc), dtype=np.int64)
+        _lib.check(_lib.load().gbrs_scan_snps(self._h, P, _lib.ptr(y), _lib.ptr(lod), _lib.ptr(used), _lib.ptr(peak),
+                                              _lib.ptr(index)))
+        out = {'used': used.astype(bool), 'peak_lod': peak, 'peak_index': index}
+        if want_lod:
+            out['lod'] = lod
+        return out
+
+    def snp_info(self):
+        raw = _lib.ScanSnpInfo()
+        _lib.check(_lib.load().gbrs_scan_snp_info(self._h, C.byref(raw)))
+        return {'M_snp': raw.M_snp, 'chunk': raw.chunk, 'P': raw.P, 'pass_ms': raw.last_pass_ms, 'row_ms': raw.last_row_ms,
+                'product_ms': raw.last_product_ms, 'device_bytes': raw.device_bytes,
+                'peak_device_bytes': raw.peak_device_bytes, 'staged': bool(raw.staged)}
 
     def info(self):
         raw = _lib.ScanInfo()
@@ -295,6 +359,17 @@ def check_scan_args(scan_pheno=None, scan_covar=None, scan_rankz=False, scan_out
         raise RuntimeError('--scan-min-lod must be a number that is not negative')
 
 
+def check_scan_snp_args(scan_snps=False, snp_file=None, scan_pheno=None, grid_file=None, cohort=False):
+    """`--scan-snps` needs `--snp-file`, `--scan-pheno`, `--grid-file` and a cohort (`--sample-file`).  Refused before a
+    file is read and before any device work."""
+    if not scan_snps:
+        return
+    for name, value in (('--snp-file', snp_file), ('--scan-pheno', scan_pheno), ('--grid-file', grid_file),
+                        ('--sample-file', cohort or None)):
+        if value is None:
+            raise RuntimeError(f'--scan-snps needs {name}')
+
+
 def read_number_table(path, what):
     """(column names, {id: row of floats}) of a tab separated table with the header `id<TAB>name...`; blank and # lines
     after the header are skipped; an id given twice, a short row and a field that is no number are refused by line."""
@@ -406,8 +481,91 @@ def write_scan_perm(prefix, phenotypes, pos, chrom_names, peak, index, min_lod, 
                               f'{repr(float(threshold[row_of[p], 0])) if judged else "NA"}\n')
 
 
+def snp_plan(snps, chrom_names, points, grid):
+    """The SNPs of read_snp_file's dict (read with `chrom_names` as its chromosomes) as GenomeScan.set_snps takes them:
+    (grid positions, SNP positions, patterns - each per chromosome of the scan -, file rows in handle order).  grid:
+    {chromosome: positions}.  The cM column is in the grid's position units.  A chromosome of the scan without grid
+    points takes no SNPs: its SNPs, like those of chromosomes the scan does not have, stay out of the handle."""
+    grid_pos, snp_pos, masks, rows = [], [], [], []
+    pointless = 0
+    for c, k in zip(chrom_names, points):
+        by = snps['by_chrom'][c]
+        if k == 0:
+            pointless += len(by)
+            by = by[:0]
+        grid_pos.append(np.asarray(grid[c], dtype=np.float64) if k else np.zeros(0))
+        snp_pos.append(snps['cM'][by])
+        masks.append(snps['mask'][by])
+        rows.append(by)
+    if pointless:
+        logger.warning(f'scan: {pointless} SNPs on chromosomes without grid points are not tested')
+    return grid_pos, snp_pos, masks, np.concatenate(rows).astype(np.int64) if rows else np.zeros(0, dtype=np.int64)
+
+
+def snps_in_file_order(result, rows, n_file):
+    """GenomeScan.run_snps' dict (handle order) in the SNP file's order: `used` [n_file] (False for SNPs that are not on
+    the handle), `peak_lod`, `peak_snp` [P, n_chrom] (the SNP's file row, -1 without a used SNP) and, if present, `lod`
+    [P, n_file], NaN for the SNPs that are not on the handle."""
+    used = np.zeros(n_file, dtype=bool)
+    used[rows] = result['used']
+    index = result['peak_index']
+    out = {'used': used, 'peak_lod': result['peak_lod'],
+           'peak_snp': np.where(index >= 0, rows[np.maximum(index, 0)] if len(rows) else -1, -1).astype(np.int64)}
+    if 'lod' in result:
+        out['lod'] = np.full((len(result['lod']), n_file), np.nan)
+        out['lod'][:, rows] = result['lod']
+    return out
+
+
+def write_scan_snps(prefix, phenotypes, samples, covariates, snps, chrom_names, result, min_lod=0.0):
+    """`<prefix>.scan.snps.npz` and `<prefix>.scan.snps.peaks.tsv` from snps_in_file_order's dict: everything per SNP in
+    the SNP file's order; one peaks line per (phenotype, chromosome of the scan) whose peak reaches min_lod."""
+    arrays = dict(phenotypes=np.array(phenotypes), samples=np.array(samples), covariates=np.array(covariates),
+                  snp_id=snps['snp_id'], chrom=snps['chrom'], bp=snps['bp'], cM=snps['cM'], pattern=snps['pattern'],
+                  used=result['used'], peak_lod=result['peak_lod'], peak_snp=result['peak_snp'])
+    if 'lod' in result:
+        arrays['lod'] = result['lod']
+    np.savez(f'{prefix}.scan.snps.npz', **arrays)
+    peak, at = result['peak_lod'], result['peak_snp']
+    with open(f'{prefix}.scan.snps.peaks.tsv', 'w') as out:
+        out.write('#phenotype\tchromosome\tsnp_id\tbp\tcM\tpattern\tlod\tgenome_wide_max\n')
+        for p, name in enumerate(phenotypes):
+            on = [c for c in range(len(chrom_names)) if at[p, c] >= 0]
+            top = max(on, key=lambda c: (peak[p, c], -c)) if on else None
+            for c in on:
+                if peak[p, c] >= min_lod:
+                    j = at[p, c]
+                    out.write(f'{name}\t{chrom_names[c]}\t{snps["snp_id"][j]}\t{repr(float(snps["bp"][j]))}\t'
+                              f'{repr(float(snps["cM"][j]))}\t{snps["pattern"][j]}\t{repr(float(peak[p, c]))}\t{int(c == top)}\n')
+
+
+def finish_scan_snps(scan, prefix, ids, phenotypes, covariates, y, snps, chrom_names, grid, min_lod=None, lod_matrix=False,
+                     stage_times=None):
+    """The SNP association pass on the prepared cohort `scan` holds and its two files.  y: the
+    phenotypes as the scan saw them (after `--scan-rankz`).  Its wall-clock seconds go to stage_times['scan_snps']."""
+    import time
+    t0 = time.perf_counter()
+    grid_pos, snp_pos, masks, rows = snp_plan(snps, chrom_names, scan.points, grid)
+    n_file = len(snps['snp_id'])
+    if len(rows):
+        scan.set_snps(grid_pos, snp_pos, masks)
+        got = scan.run_snps(y, want_lod=bool(lod_matrix) or y.shape[1] * len(rows) <= LOD_MATRIX_LIMIT)
+        timing = scan.snp_info()
+        logger.info(f'scan: {len(rows)} SNPs, {y.shape[1]} phenotypes; {timing["pass_ms"]:.1f} ms on the device, '
+                    f'{timing["row_ms"]:.1f} ms of them in the row kernel and {timing["product_ms"]:.1f} ms in the product kernel')
+    else:
+        logger.warning('scan: no SNP of the file lies on a chromosome with grid points')
+        nc = len(chrom_names)
+        got = {'used': np.zeros(0, dtype=bool), 'peak_lod': np.full((y.shape[1], nc), np.nan),
+               'peak_index': np.full((y.shape[1], nc), -1, dtype=np.int64), 'lod': np.zeros((y.shape[1], 0))}
+    write_scan_snps(prefix, phenotypes, ids, covariates, snps, [str(c) for c in chrom_names],
+                    snps_in_file_order(got, rows, n_file), 0.0 if min_lod is None else min_lod)
+    if stage_times is not None:
+        stage_times['scan_snps'] = stage_times.get('scan_snps', 0.0) + time.perf_counter() - t0
+
+
 def finish_scan(scan, prefix, ids, pheno, covar, use_rankz, chrom, pos, chrom_names, min_lod=None, lod_matrix=False,
-                perm=None, stage_times=None):
+                perm=None, stage_times=None, snps=None, snp_grid=None):
     """prepare + run + the two files for the cohort `scan` holds, whose samples are `ids` in append order (every one with
     its rows in the tables).  perm: perm_options' dict, or None; with it the permutation pass runs after the scan on the
     phenotypes and chromosomes it names and its wall-clock seconds go to stage_times['scan_perm'].  Returns
@@ -435,15 +593,18 @@ def finish_scan(scan, prefix, ids, pheno, covar, use_rankz, chrom, pos, chrom_na
                0.0 if min_lod is None else min_lod, perm=done)
     logger.info(f'scan: {len(ids)} samples, {y.shape[1]} phenotypes, {scan.M} grid points; prepare '
                 f'{info["prepare_ms"]:.1f} ms, run {info["run_ms"]:.1f} ms on the device')
+    if snps is not None:        # read_snp_file's dict: the SNP association pass follows on the same preparation
+        finish_scan_snps(scan, prefix, ids, pheno[0], names, y, snps, chrom_names, snp_grid, min_lod, lod_matrix, stage_times)
     return info
 
 
 def scan_tables(dosage_list, grid_file, pheno_file, covar_file=None, use_rankz=False, out=None, min_lod=None,
                 lod_matrix=False, device=0, scan_perms=None, scan_perm_seed=None, scan_perm_alpha=None,
-                scan_perm_chromosomes=None, scan_perm_pheno=None, stage_times=None):
+                scan_perm_chromosomes=None, scan_perm_pheno=None, stage_times=None, snp_file=None):
     """`gbrs scan`: the cohort from dosage tables in `gbrs export` format (lines `id<TAB>dosage table`), rows in the grid
-    file's order, without the HMM."""
-    from .hmm import _match_lines, read_dosage_table
+    file's order, without the HMM.  snp_file (`--snp-file`): the SNP association pass follows the scan (DESIGN.md §29);
+    the haplotypes of the patterns are those of the dosage tables' header."""
+    from .hmm import _match_lines, read_dosage_table, read_snp_file
     from .postproc import read_grid
     if min_lod is not None and not min_lod >= 0.0:
         raise RuntimeError('--scan-min-lod must be a number that is not negative')
@@ -466,6 +627,7 @@ def scan_tables(dosage_list, grid_file, pheno_file, covar_file=None, use_rankz=F
         raise RuntimeError('scan: no sample of the dosage list has a phenotype row')
     with open(entries[kept[0]][1]) as fh:
         haplotypes = fh.readline().rstrip('\n')[2:].split('\t')
+    snps = read_snp_file(snp_file, haplotypes, chrom_names, grid_file) if snp_file is not None else None
     scan = GenomeScan(len(haplotypes), points, device=device)
     try:
         for k in kept:
@@ -473,6 +635,7 @@ def scan_tables(dosage_list, grid_file, pheno_file, covar_file=None, use_rankz=F
         chrom = np.repeat(chrom_names, points)
         pos = np.concatenate([np.asarray(grid[c], dtype=np.float64) for c in chrom_names])
         return finish_scan(scan, out if out is not None else 'gbrs', [entries[k][0] for k in kept], pheno, covar, use_rankz,
-                           chrom, pos, chrom_names, min_lod, lod_matrix, perm=perm, stage_times=stage_times)
+                           chrom, pos, chrom_names, min_lod, lod_matrix, perm=perm, stage_times=stage_times, snps=snps,
+                           snp_grid=grid)
     finally:
         scan.close()

@@ -984,6 +984,73 @@ typedef struct gbrs_scan_perm_info {
 } gbrs_scan_perm_info_t;
 int gbrs_scan_perm_info(gbrs_scan_t *scan, gbrs_scan_perm_info_t *info);
 
+/* SNP association on the scan handle: every founder SNP is tested with one degree of freedom on the allele
+ * dosage that its founder pattern implies, from the cohort's grid dosages where they lie.  No fused multiply-add anywhere.
+ *
+ * Where a SNP lies.  A SNP has a chromosome c of the handle, a position x in the units of the grid positions and a founder
+ * pattern m: bit h of m is set when founder h carries the alternative allele.  With g[0..k-1] the grid positions of
+ * chromosome c in the handle's point order:
+ *   lo = clip(searchsorted(g, x, 'right') - 1, 0, k-1),  hi = min(lo + 1, k-1),
+ *   t = (x - g[lo]) / (g[hi] - g[lo]) if g[hi] > g[lo] and x > g[lo], else 0.0;  then t = min(t, 1.0).
+ * A SNP outside the grid takes the end point's dosage, as np.interp does; a SNP on a duplicated grid position takes the
+ * last of the equal points.
+ * Its dosage for sample s:  a_lo = 0.0; for h ascending: if bit h of m: a_lo += D[s][lo][h];  a_hi likewise from D[s][hi];
+ *   x_s = 2.0 * (a_lo + t * (a_hi - a_lo)).
+ *
+ * gbrs_scan_set_snps: the arguments go per chromosome, as gbrs_hmm_set_snps takes them: grid_pos[c] is double[points of c]
+ * (nullable for a chromosome without points), n_snps[c] >= 0, snp_pos[c] double[n_snps[c]], snp_mask[c] uint32[n_snps[c]].
+ * The SNPs are numbered in handle order: chromosome after chromosome, each in the order given (sorted by position they
+ * share grid intervals, which the pass makes use of; any order is valid and gives the same bits per SNP).  The host checks
+ * everything first: GBRS_ERR_INVALID for a grid or SNP position that is not finite, grid positions that decrease (naming
+ * chromosome and index), a pattern bit at or above H (naming chromosome and index) and a SNP on a chromosome without grid
+ * points.  Positions and patterns are uploaded and one kernel finds lo (the global point index), hi and t per SNP; 20 bytes
+ * per SNP stay on the device (lo, hi, pattern: 4 each; t: 8).  All-zero counts drop the SNPs.  On failure the handle
+ * keeps what it had.  The call is independent of gbrs_scan_prepare, and appending samples does not drop the SNPs. */
+int gbrs_scan_set_snps(gbrs_scan_t *scan, const double *const *grid_pos, const int64_t *n_snps,
+                       const double *const *snp_pos, const uint32_t *const *snp_mask);
+
+/* x_s of the SNPs first .. first + count - 1 for every sample: out is double[n][count].  Needs SNPs and a cohort, not a
+ * preparation; GBRS_ERR_INVALID without either and for a range outside the handle's SNPs. */
+int gbrs_scan_snp_dosage(gbrs_scan_t *scan, int64_t first, int64_t count, double *out);
+
+/* The test of every SNP on the prepared cohort (qz, c of gbrs_scan_prepare).  Every sum over the samples is one
+ * wavefront's, in gbrs_scan_prepare's order: lane l adds the samples l, l + 64, ... in order, and the 64 partial sums meet
+ * in a butterfly.
+ *   raw = sum x_s^2,  qtx[k] = sum_s qz[s][k] x_s,
+ *   x~_s = x_s - sum_k (k ascending) qz[s][k] qtx[k],  G = sum x~_s^2;
+ *   the SNP is used iff G > 0 and G > 1e-10 raw (gbrs_scan_prepare's threshold with its meaning: a SNP that is monomorphic
+ *   in the cohort, the all-zeros and the all-ones pattern project to rounding and are not tested);
+ *   w = x~ / sqrt(G), a true division; zeros for an unused SNP;
+ *   per phenotype p, y~ and rss0 as gbrs_scan_run forms them (the same kernel): ess = (w . y~_p)^2 and the LOD by
+ *   gbrs_scan_run's formula with its two edge rules; an unused SNP has LOD 0.0 for every phenotype.
+ * pheno is double[n][P] as for gbrs_scan_run.  lod is double[P][M_snp], used uint8[M_snp], peak_lod double[P][n_chrom] the
+ * largest LOD over the used SNPs of a chromosome, peak_index int64[P][n_chrom] that SNP's index in handle order, the
+ * lowest on ties (NaN and -1 for a chromosome without a used SNP); all four nullable.  SNP chunks (gbrs_scan_snp_info's
+ * `chunk`) are the outer loop and phenotype chunks of 512 the inner one: a SNP's row w is built once per call, y~ of all P
+ * stays on the device as [P][n_ld], and neither the dosage matrix [n][M_snp] nor the products reach memory beyond one
+ * chunk's rows.  A SNP's LODs are the same bits alone or among others, at any place in its 64-row tile, in any chunk, for
+ * any P, column and phenotype chunk, and however the cohort was appended.  GBRS_ERR_INVALID before gbrs_scan_prepare,
+ * without SNPs, for P < 1 and for a value that is not finite (the message names the entry); the outputs are untouched on
+ * such a failure.  The call allocates and frees its own buffers: the handle's W, gbrs_scan_run's bits and
+ * gbrs_scan_info_t are as before.  The allele effect, permutations of the SNP scan and SNP x covariate interactions are
+ * not computed. */
+int gbrs_scan_snps(gbrs_scan_t *scan, int64_t P, const double *pheno, double *lod, uint8_t *used, double *peak_lod,
+                   int64_t *peak_index);
+
+typedef struct gbrs_scan_snp_info {
+    int64_t  M_snp;              /* SNPs on the handle                                                           */
+    int64_t  chunk;              /* SNPs whose rows are on the device at a time in gbrs_scan_snps                */
+    int64_t  P;                  /* of the last gbrs_scan_snps (0: none yet)                                     */
+    double   last_pass_ms;       /* device time of the last pass: uploads, projections, all chunks, copies       */
+    double   last_row_ms;        /* of that, the row kernel, summed over the SNP chunks                          */
+    double   last_product_ms;    /* of that, the product kernel, summed over the chunks                          */
+    uint64_t device_bytes;       /* what the SNPs hold on the device (not part of gbrs_scan_info_t's figure)     */
+    uint64_t peak_device_bytes;  /* what the handle held during the last pass, the call's own buffers included   */
+    int32_t  staged;             /* the last pass's row kernel: 1 the two grid points of a run of SNPs in LDS, 0 (they  */
+    int32_t  reserved;           /* do not fit a workgroup's share) every SNP read the cohort itself; the same bits     */
+} gbrs_scan_snp_info_t;
+int gbrs_scan_snp_info(gbrs_scan_t *scan, gbrs_scan_snp_info_t *info);
+
 /* ------------------------------------------------------------------------------------------
  * Report text (host side, no device work): the `locus <haplotypes> total [notes]` tables of
  * EMfactory.report_read_counts / report_depths (emase/EMfactory.py:289-380).

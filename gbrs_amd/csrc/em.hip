@@ -1147,6 +1147,7 @@ int em_create_impl(uint64_t R, uint32_t L, uint32_t H, const uint32_t *const *in
     shape.H = H; shape.L = L; shape.R = R; shape.N = n; shape.flags = flags; shape.counts_given = count != nullptr;
     GBRS_HIP_CHECK(hipDeviceGetAttribute(&shape.n_cu, hipDeviceAttributeMultiprocessorCount, device));
     shape.tile_words = TILE_WORDS; shape.tile_words_max = TILE_WORDS_MAX; shape.tile_rounds_min = TILE_ROUNDS_MIN;
+    shape.err_blocks = (uint32_t)std::min<uint64_t>(ERR_BLOCKS, ((uint64_t)L + RED_THREADS - 1) / RED_THREADS);   // (estep_err_args)
     if (H <= 16) shape.dict = dict_limits(em_weighted(flags, count != nullptr), (int)H);     // (more: the CSC kernels)
     if (H == 16) shape.dict_half = dict_limits(false, 8);
     const EmPlan &plan = em->plan = em_plan(shape, em_tuning_from_env());
@@ -1895,6 +1896,26 @@ int gbrs_em_fold_counts(gbrs_em_t *em, uint64_t *one_word_reads, uint64_t *two_w
     if (!em || !one_word_reads || !two_word_reads) return fail(GBRS_ERR_INVALID, "NULL argument");
     *one_word_reads = em->layout == 1 ? em->tl.n_folded : 0;
     *two_word_reads = em->layout == 1 ? em->tl.n_folded_two : 0;
+    return GBRS_OK;
+}
+
+int gbrs_em_tile_cut(gbrs_em_t *em, uint32_t *passes, uint32_t *tile_words) {
+    if (!em || !passes || !tile_words) return fail(GBRS_ERR_INVALID, "NULL argument");
+    *passes = em->layout == 1 ? em->tl.cut_passes : 0;
+    *tile_words = em->layout == 1 ? em->tl.cut_tile_words : 0;
+    return GBRS_OK;
+}
+
+int gbrs_em_tile_shapes(gbrs_em_t *em, uint32_t *n_batches, uint32_t *dict_entries, uint64_t n) {
+    if (!em || !n_batches || !dict_entries) return fail(GBRS_ERR_INVALID, "NULL argument");
+    if (em->layout != 1 || n != em->tl.n_tiles) return fail(GBRS_ERR_INVALID, "n is not the handle's number of tiles");
+    (void)hipSetDevice(em->device);
+    std::vector<TileHdr> hdr(n);
+    if (n) GBRS_HIP_CHECK(hipMemcpy(hdr.data(), em->tl.tiles.p, n * sizeof(TileHdr), hipMemcpyDeviceToHost));
+    for (uint64_t t = 0; t < n; ++t) {
+        n_batches[t] = hdr[t].n_batches;
+        dict_entries[t] = hdr[t].dict_count();
+    }
     return GBRS_OK;
 }
 

@@ -50,6 +50,14 @@ constexpr int TILE_WAVES = TILE_THREADS / 64;
 // 11,008: 0.0464, 16,320: 0.0449 at 1.2 rounds; 6,016: 0.0476, 4,096: 0.0501, 2,816: 0.0528), so what is left of the
 // rule is that a launch should not have fewer tiles than the chip has places for them: build_tile_layout takes the
 // largest size between TILE_WORDS and TILE_WORDS_MAX that leaves TILE_ROUNDS_MIN round(s).
+// Since the run-word folds (5.5 M words on that sample) the fixed part of a tile - header, dictionary, theta gather, barriers,
+// slot stores: 4.3 of a mean tile's 10.9 us - weighs what the loop used to, and the rule above never gave one round: the
+// cut was the union of the word grid and a dictionary grid that counted every locus list anew, 1,496 tiles where the size
+// asks for 775.  The exact cut (cut_tiles_exact, em_plan.h) ends a tile at its words or at d_max DISTINCT ids and aims at
+// places - 64 tiles: 700 of 7,744 words, one round, the step 39.36 -> 37.99 us (profiles/estep_tile_cut.txt).  It is taken
+// when the words fit one round under the cap; samples of several rounds (the one-round finding of 52,096 words above was one)
+// are slower with tiles of the full cap and keep the two-grid cut.  A round is as long as its slowest CU: 640 tiles (2.5 per
+// CU) are slower than 1,496, 763 (3 per CU) a little faster than 700 - within the runs' ranges, so not the default.
 #ifndef GBRS_TILE_WORDS
 #define GBRS_TILE_WORDS 2048
 #endif
@@ -140,6 +148,8 @@ struct TileLayout {
     uint64_t n_long = 0;         // rows with more than MAX_ROW_WORDS loci
     uint64_t n_tiles = 0, n_batches = 0, n_slots = 0, n_heavy = 0, n_light = 0;
     uint32_t d_max = 0;          // dictionary capacity used when cutting tiles
+    uint32_t cut_passes = 0;     // passes of the exact cut (0: the two-grid cut), and the tile size that cut the tiles
+    uint32_t cut_tile_words = 0;
     bool weighted = false;       // per-row weights present (count given or rows merged)
     bool deterministic = false;  // dictionaries capped at det_dict_cap(H): one private sum copy per wavefront
     bool all_one_word = false;   // every row of the layout is a single word (and there are no long rows)

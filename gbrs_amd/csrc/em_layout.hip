@@ -6,7 +6,9 @@
 //   entries (h, l, r)  --sort by (r, l, h)-->  (row, locus) pairs with a haplotype mask
 //   rows  --sort by (first locus, hash of locus list, hash of masks)-->  similar rows adjacent
 //   [optional] identical adjacent rows merged into one weighted row (what `gbrs compress` does)
-//   tiles cut where the running count of distinct locus lists or of words crosses a chunk border
+//   tiles cut where a tile's words or its distinct ids reach their limit, sized for one round of the chip's workgroup
+//   places (cut_tiles_exact); under a forced size or for a sample of several rounds: where the running count of words
+//   or of the loci of distinct locus lists crosses a chunk border
 //   per tile: locus dictionary (LDS bitonic sort + unique), rows padded so none straddles a
 //   64-word batch, words emitted with dictionary-local indices
 //   inverted index locus -> slots for the gather kernel
@@ -513,6 +515,55 @@ __global__ void tile_flag_kernel(uint64_t m_rows, uint32_t tile_words, uint32_t 
         const uint32_t dc = dincl[m] - npm[m], dp = dincl[m - 1] - npm[m - 1];
         f = (wordoff[m] / tile_words != wordoff[m - 1] / tile_words) || (dc / dseg != dp / dseg);
     }
+    tflag[m] = f;
+}
+
+// ---- the exact cut (cut_tiles_exact) ----
+// ids of row m that the row before it does not have: a tile of rows a .. b holds at most npm[a] + the sum of these over
+// a + 1 .. b distinct ids (an id's first row in the tile is a, or a row whose predecessor lacks it).  The rows are sorted
+// by locus list, so the list (l1, l2) behind l1's single-locus reads counts l2 alone - row_len_kernel's dnew counts both
+__global__ void row_new_ids_kernel(uint64_t m_rows, const uint32_t *__restrict__ hrow, const uint32_t *__restrict__ rowstart,
+                                   const uint32_t *__restrict__ ploc, uint32_t *__restrict__ fresh) {
+    const uint64_t m = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= m_rows) return;
+    const uint32_t r = hrow[m], p0 = rowstart[r], p1 = rowstart[r + 1];
+    uint32_t n = p1 - p0;
+    if (m > 0) {
+        const uint32_t q = hrow[m - 1], q0 = rowstart[q], q1 = rowstart[q + 1];
+        for (uint32_t p = p0; p < p1; ++p) {
+            const uint32_t id = ploc[p];
+            for (uint32_t k = q0; k < q1; ++k)
+                if (ploc[k] == id) { --n; break; }
+        }
+    }
+    fresh[m] = n;
+}
+
+// candidates: a new one where the word offset passes a multiple of tile_words
+__global__ void cand_flag_kernel(uint64_t m_rows, uint32_t tile_words, const uint32_t *__restrict__ wordoff,
+                                 uint32_t *__restrict__ cflag) {
+    const uint64_t m = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= m_rows) return;
+    cflag[m] = (m == 0 || wordoff[m] / tile_words != wordoff[m - 1] / tile_words) ? 1u : 0u;
+}
+
+// distinct ids per candidate from the sorted (candidate, id) keys and their head flags
+__global__ void cand_count_kernel(uint64_t n, const uint64_t *__restrict__ skeys, const uint32_t *__restrict__ flag,
+                                  uint32_t *__restrict__ cnt) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && flag[i]) atomicAdd(&cnt[skeys[i] >> 32], 1u);
+}
+
+// a candidate whose distinct ids fit d_max is a tile; any other is split where the running count of fresh ids passes a
+// multiple of dseg: the rows between two such lines bring fewer than dseg fresh ids, the first of them at most a row's
+// words more - below d_max = dseg + max_row_words whatever the tile's first row is
+__global__ void cut_flag_kernel(uint64_t m_rows, uint32_t dseg, uint32_t d_max, const uint32_t *__restrict__ cflag,
+                                const uint32_t *__restrict__ cincl, const uint32_t *__restrict__ cnt,
+                                const uint32_t *__restrict__ fincl, uint32_t *__restrict__ tflag) {
+    const uint64_t m = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= m_rows) return;
+    uint32_t f = cflag[m];
+    if (!f && cnt[cincl[m] - 1] > d_max) f = fincl[m] / dseg != fincl[m - 1] / dseg;
     tflag[m] = f;
 }
 
@@ -1577,6 +1628,57 @@ struct Tiles {
     void release() { tincl.release(); npm.release(); wordoff.release(); tile_row.release(); }
 };
 
+// 7 (plan.exact_cut). One rule: a tile ends at tile_words words or at d_max distinct ids, whichever comes first, and the
+// next starts fresh.  A pass cuts candidates on the word grid, counts each candidate's distinct ids the way stage 9 will
+// (one sort of (candidate, id) keys over the W words) and splits only the candidates above d_max (cut_flag_kernel).  A
+// pass that ends above plan.tile_target tiles is repeated at a size larger in proportion (em_plan.h), TILE_CUT_PASSES
+// times at most; the pass with the fewest tiles stands.  Fills t.tflag / t.tincl, T: the tiles.
+int cut_tiles_exact(Build &b, TileLayout &out, const RowPairs &rp, const LayoutRows &lr, Tiles &t, const EmPlan &plan,
+                    uint32_t W, uint32_t &T) {
+    hipStream_t s = b.s;
+    const uint64_t M = lr.M;
+    DevBuf<uint32_t> fresh, fincl, cflag, cincl, cnt, dflag, kept;
+    DevBuf<uint64_t> key, key2;
+    GBRS_TRY(fresh.alloc(M)); GBRS_TRY(fincl.alloc(M)); GBRS_TRY(cflag.alloc(M)); GBRS_TRY(cincl.alloc(M));
+    GBRS_TRY(key.alloc(W)); GBRS_TRY(key2.alloc(W)); GBRS_TRY(dflag.alloc(W));
+    hipLaunchKernelGGL(row_new_ids_kernel, dim3(grid_for(M)), dim3(256), 0, s, M, lr.hrow.p, rp.rowstart.p, rp.ploc.p, fresh.p);
+    GBRS_TRY(inclusive_scan(b.sc, fresh.p, fincl.p, M, s));
+    uint32_t tw = em_cut_tile_words(plan, W), kept_T = 0;
+    for (int pass = 1;; ++pass) {
+        uint32_t C = 0;
+        hipLaunchKernelGGL(cand_flag_kernel, dim3(grid_for(M)), dim3(256), 0, s, M, tw, t.wordoff.p, cflag.p);
+        GBRS_TRY(scan_heads(b.sc, cflag.p, cincl.p, M, C, s));
+        GBRS_TRY(cnt.alloc(C));
+        GBRS_HIP_CHECK(hipMemsetAsync(cnt.p, 0, cnt.bytes(), s));
+        hipLaunchKernelGGL(tile_pair_keys_kernel, dim3(grid_for(M)), dim3(256), 0, s, M, cincl.p, lr.hrow.p, rp.rowstart.p, rp.ploc.p,
+                           t.wordoff.p, key.p);
+        GBRS_TRY(sort_keys64(b.sc, key.p, key2.p, W, 32 + bits_for(C), s));
+        hipLaunchKernelGGL(dict_flag_kernel, dim3(grid_for(W)), dim3(256), 0, s, (uint64_t)W, key2.p, dflag.p);
+        hipLaunchKernelGGL(cand_count_kernel, dim3(grid_for(W)), dim3(256), 0, s, (uint64_t)W, key2.p, dflag.p, cnt.p);
+        hipLaunchKernelGGL(cut_flag_kernel, dim3(grid_for(M)), dim3(256), 0, s, M, plan.dseg, plan.d_max, cflag.p, cincl.p, cnt.p,
+                           fincl.p, t.tflag.p);
+        GBRS_TRY(scan_heads(b.sc, t.tflag.p, t.tincl.p, M, T, s));
+        out.cut_passes = (uint32_t)pass;
+        const uint32_t next = em_cut_rescale(plan, tw, T);
+        const bool last = next == tw || pass == TILE_CUT_PASSES;
+        if (kept_T == 0 || T < kept_T) {
+            kept_T = T;
+            out.cut_tile_words = tw;
+            if (!last) {       // (a later pass may do worse: more of its larger candidates pass d_max)
+                if (!kept.p) GBRS_TRY(kept.alloc(M));
+                GBRS_HIP_CHECK(hipMemcpyAsync(kept.p, t.tflag.p, M * 4, hipMemcpyDeviceToDevice, s));
+            }
+        } else if (last) {
+            GBRS_HIP_CHECK(hipMemcpyAsync(t.tflag.p, kept.p, M * 4, hipMemcpyDeviceToDevice, s));
+            GBRS_TRY(scan_heads(b.sc, t.tflag.p, t.tincl.p, M, T, s));
+        }
+        if (last) break;
+        tw = next;
+    }
+    GBRS_HIP_CHECK(hipStreamSynchronize(s));
+    return GBRS_OK;
+}
+
 // 7. tiles
 int cut_tiles(Build &b, TileLayout &out, const RowPairs &rp, const LayoutRows &lr, Tiles &t, const EmPlan &plan) {
     hipStream_t s = b.s;
@@ -1590,10 +1692,17 @@ int cut_tiles(Build &b, TileLayout &out, const RowPairs &rp, const LayoutRows &l
     uint32_t total_words = 0;
     GBRS_TRY(fetch_last_plus(t.wordoff.p, t.npm.p, M, total_words, s));
     out.all_one_word = total_words == M && out.n_long == 0;
-    hipLaunchKernelGGL(tile_flag_kernel, dim3(grid_for(M)), dim3(256), 0, s, M, em_tile_words(plan, total_words), plan.dseg, t.npm.p,
-                       t.wordoff.p, dincl.p, t.tflag.p);
     uint32_t T32 = 0;
-    GBRS_TRY(scan_heads(b.sc, t.tflag.p, t.tincl.p, M, T32, s));
+    out.cut_passes = 0;
+    out.cut_tile_words = em_tile_words(plan, total_words);
+    if (em_take_exact_cut(plan, total_words)) {
+        dincl.release();
+        GBRS_TRY(cut_tiles_exact(b, out, rp, lr, t, plan, total_words, T32));
+    } else {
+        hipLaunchKernelGGL(tile_flag_kernel, dim3(grid_for(M)), dim3(256), 0, s, M, out.cut_tile_words, plan.dseg, t.npm.p,
+                           t.wordoff.p, dincl.p, t.tflag.p);
+        GBRS_TRY(scan_heads(b.sc, t.tflag.p, t.tincl.p, M, T32, s));
+    }
     t.T = T32;
     out.n_tiles = t.T;
     dincl.release();

@@ -29,6 +29,8 @@ struct EmTuning {
     uint32_t set_min_rows = 192;   // SET_MIN_ROWS (> 0): rows a mask-group set must be carried by
     Int run_words;              // RUN_WORDS=0 no fold, 1 the one-word fold alone, 2 both folds - forced
     int tile_words = 0;         // TILE_WORDS (>= 64): words per tile instead of the rule's
+    bool tile_cut = true;       // TILE_CUT=0: the two-grid cut even where the rule chooses the tile size
+    int tile_target = 0;        // TILE_TARGET (>= 1): the cut aims at this many tiles instead of the chip's places
     bool tile_order = true;     // TILE_ORDER=0 keeps the tiles in locus order
     bool half_loci = false;     // HALF_LOCI=1: 16 haplotypes as half-loci of 8
     bool persistent = false;    // PERSISTENT=1: persistent E-step workgroups
@@ -62,6 +64,8 @@ inline EmTuning em_tuning_from_env() {
     at_least("GBRS_TUNING_SET_MIN_ROWS", 1, t.set_min_rows);
     t.run_words = integer("GBRS_TUNING_RUN_WORDS");
     at_least("GBRS_TUNING_TILE_WORDS", 64, t.tile_words);
+    t.tile_cut = !integer("GBRS_TUNING_TILE_CUT").is(0);
+    at_least("GBRS_TUNING_TILE_TARGET", 1, t.tile_target);
     t.tile_order = !integer("GBRS_TUNING_TILE_ORDER").is(0);
     t.half_loci = integer("GBRS_TUNING_HALF_LOCI").nonzero();
     t.persistent = integer("GBRS_TUNING_PERSISTENT").nonzero();
@@ -91,6 +95,7 @@ struct EmShape {
     bool counts_given = false;    // the caller passed row counts
     int n_cu = 0;                 // compute units of the handle's device
     uint32_t tile_words = 0, tile_words_max = 0, tile_rounds_min = 1;   // TILE_WORDS, TILE_WORDS_MAX, TILE_ROUNDS_MIN
+    uint32_t err_blocks = 0;      // error-pass workgroups that ride a step's tile launch (em.hip, ERR_BLOCKS)
     EmDictLimits dict;            // at H haplotypes, weighted as em_weighted() says
     EmDictLimits dict_half;       // at H / 2 haplotypes, unweighted: the half-locus view's (read at H = 16 only)
 };
@@ -134,6 +139,14 @@ struct EmPlan {
     uint64_t places = 0;
     uint32_t tile_words = 0, tile_words_cap = 0;   // the tile-size rule's bounds (cap: a multiple of 64 follows from the rule)
     uint32_t tile_words_forced = 0;  // > 0: GBRS_TUNING_TILE_WORDS, clamped
+    // The cut (em_layout.hip, stage 7).  exact_cut: tiles end at tile_words words or at d_max DISTINCT dictionary ids,
+    // whichever comes first, and the size is rescaled until about tile_target tiles come out - one round of the chip's
+    // places beside the error-pass workgroups.  false (GBRS_TUNING_TILE_WORDS forces the size, or GBRS_TUNING_TILE_CUT=0):
+    // the two-grid cut - a tile starts where the word offset passes a multiple of the tile size or the per-list entry
+    // count a multiple of dseg.
+    bool exact_cut = false;
+    uint64_t tile_target = 0;
+    bool tile_target_forced = false; // GBRS_TUNING_TILE_TARGET: the exact cut whatever the sample's size (em_take_exact_cut)
     bool reorder_tiles = true;       // launch order: most batches first
     uint32_t d_max = 0, dseg = 0;    // dictionary capacity; what is left of it beside one row's loci
     bool dict_room = false;          // false: d_max leaves no room for a row's loci - the build refuses
@@ -147,6 +160,15 @@ struct EmPlan {
     uint32_t resample_cut = 256;     // (the variable is read by a resampling handle with counts only)
     bool no_fused_mstep = false, no_float_check = false;   // EmTuning's, for the handle's steps (em_step.h, em_check_float)
 };
+
+// Tiles the exact cut aims at: one round of the places a handle has - its share when handles run side by side - less the
+// error-pass workgroups that ride the same launch (a chip with no more places than those keeps them all).
+// GBRS_TUNING_TILE_TARGET overrides.
+inline uint64_t em_tile_target(uint64_t places, unsigned side_by_side, uint32_t err_blocks, int forced) {
+    if (forced > 0) return (uint64_t)forced;
+    const uint64_t n = std::max<uint64_t>(places / std::max(side_by_side, 1u), 1);
+    return n > err_blocks ? n - err_blocks : n;
+}
 
 inline EmPlan em_plan(const EmShape &s, const EmTuning &t) {
     EmPlan p;
@@ -190,6 +212,9 @@ inline EmPlan em_plan(const EmShape &s, const EmTuning &t) {
     // (weighted rows - merged reads, EC counts - stay at 16,320: the merged C2 sample reads 0.0345 ms there, 0.0357 at 20,900)
     p.tile_words_cap = p.weighted ? std::min<uint32_t>(s.tile_words_max, 16320) : s.tile_words_max;
     if (t.tile_words) p.tile_words_forced = std::min<uint32_t>((uint32_t)t.tile_words, s.tile_words_max);
+    p.exact_cut = t.tile_cut && !p.tile_words_forced;
+    p.tile_target = em_tile_target(p.places, p.side_by_side, s.err_blocks, t.tile_target);
+    p.tile_target_forced = t.tile_target > 0;
     p.reorder_tiles = t.tile_order;
 
     p.d_max = std::min<uint32_t>(1024, d.lds_doubles / p.tH);
@@ -215,6 +240,34 @@ inline uint32_t em_tile_words(const EmPlan &p, uint64_t total_words) {
     if (p.tile_words_forced) return p.tile_words_forced;
     const uint64_t fit = total_words * p.side_by_side / p.places;
     return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(fit, p.tile_words), p.tile_words_cap) & ~63u;
+}
+
+// The exact cut's sizes.  A pass cuts candidates on the word grid and splits those whose distinct ids pass d_max, so it can
+// end with more tiles than it aimed at; the next pass enlarges the size in proportion.  At most TILE_CUT_PASSES passes.
+constexpr int TILE_CUT_PASSES = 3;
+// The exact cut is for the samples whose words fit ONE round under the cap.  A sample of several rounds keeps the two-grid
+// cut: its tiles, about half as long, fill the last round better than tiles of the full cap do.  Measured
+// (profiles/estep_tile_cut.txt, five alternations, iterations/s, two-grid against exact cut): multi-isoform reads, 59.6 M
+// words, 3,497 against 1,835 tiles: 6,594-6,627 against 6,121-6,133; 25 M reads x 16 haplotypes, 28.5 M words, 2,261
+// against 1,009 tiles: 6,618-6,645 against 5,913-5,947.  In one round: the bench sample 25,372-25,529 against
+// 26,282-26,622, merged rows 24,402-24,594 against 25,226-25,469, deterministic 1,196-1,198 against 1,372-1,375.
+// GBRS_TUNING_TILE_TARGET takes the exact cut whatever the size.
+inline bool em_take_exact_cut(const EmPlan &p, uint64_t total_words) {
+    if (!p.exact_cut) return false;
+    return p.tile_target_forced || (total_words + p.tile_target - 1) / p.tile_target <= p.tile_words_cap;
+}
+inline uint32_t em_cut_clamp(const EmPlan &p, uint64_t words) {
+    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((words + 63) & ~63ull, p.tile_words), p.tile_words_cap);
+}
+// first pass: the smallest multiple of 64 that fits total_words into tile_target tiles, in [TILE_WORDS, cap]
+inline uint32_t em_cut_tile_words(const EmPlan &p, uint64_t total_words) {
+    return em_cut_clamp(p, (total_words + p.tile_target - 1) / p.tile_target);
+}
+// after a pass at tile_words that gave `tiles`: the size of the next pass, or tile_words itself when the pass met the
+// target or no larger size is left
+inline uint32_t em_cut_rescale(const EmPlan &p, uint32_t tile_words, uint64_t tiles) {
+    if (tiles <= p.tile_target) return tile_words;
+    return std::max(tile_words, em_cut_clamp(p, ((uint64_t)tile_words * tiles + p.tile_target - 1) / p.tile_target));
 }
 
 // The fold pays by the words it takes away - one for a one-word read, two for a two-word read - and a launch still wants

@@ -135,6 +135,19 @@ class EmEngine:
         _lib.check(_lib.load().gbrs_em_fold_counts(self._h, C.byref(one), C.byref(two)))
         return int(one.value), int(two.value)
 
+    def tile_cut(self):
+        """(passes of the exact tile cut - 0: the two-grid cut -, words per tile that cut the tiles) (gbrs_em_tile_cut)."""
+        passes, words = C.c_uint32(0), C.c_uint32(0)
+        _lib.check(_lib.load().gbrs_em_tile_cut(self._h, C.byref(passes), C.byref(words)))
+        return int(passes.value), int(words.value)
+
+    def tile_shapes(self):
+        """Per tile, in launch order: (batches, dictionary entries) as two uint32 arrays (gbrs_em_tile_shapes)."""
+        n = int(self.info().num_tiles)
+        batches, entries = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        _lib.check(_lib.load().gbrs_em_tile_shapes(self._h, batches.ctypes.data, entries.ctypes.data, n))
+        return batches, entries
+
     # ---- multi-GPU building blocks -----------------------------------------------------------
     def _partial(self, fn):
         p = C.c_void_p()

@@ -359,6 +359,14 @@ int gbrs_em_info(gbrs_em_t *em, gbrs_em_info_t *info);
  * locus or one locus set counted by an identical read's word); two_word_reads are reads of exactly two (locus, mask) pairs
  * counted by an identical read's two words.  Both 0 when the fold was not taken and for the CSC layout. */
 int gbrs_em_fold_counts(gbrs_em_t *em, uint64_t *one_word_reads, uint64_t *two_word_reads);
+/* How the tile layout was cut.  passes: the passes of the exact cut - a tile ends at tile_words words or at its dictionary's
+ * capacity in DISTINCT ids, and the size is rescaled towards one round of the device's workgroup places - or 0 for the
+ * two-grid cut (GBRS_TUNING_TILE_WORDS forces the size, or GBRS_TUNING_TILE_CUT=0); tile_words: the size that cut the
+ * tiles.  Both 0 for the CSC layout. */
+int gbrs_em_tile_cut(gbrs_em_t *em, uint32_t *passes, uint32_t *tile_words);
+/* Per tile, in launch order: its batches of 64 words and its dictionary entries.  n must be gbrs_em_info.num_tiles; one
+ * device-to-host copy of the headers (profiling scripts and tests). */
+int gbrs_em_tile_shapes(gbrs_em_t *em, uint32_t *n_batches, uint32_t *dict_entries, uint64_t n);
 
 /* `--report-alignment-counts` (emase/AlignmentPropertyMatrix.py:389-459), stand-alone (the
  * reference reloads the alignment file for it, gbrs/emase_utils.py:318-331).  Inputs as for

@@ -66,6 +66,23 @@ last_start = t0.max()
 print(f"last tile starts at {last_start / 100:.1f} us; after that {np.sum(t3 > last_start)} tiles still run; "
       f"time from the moment fewer than 90 % of the places are busy to the end: "
       f"{(span - np.argmax(occ[::-1] >= 0.9 * places) * 100 if False else (len(occ) - 1 - np.argmax(occ[::-1] >= 0.9 * places)) ) } us mark")
-per_cu_busy = {}
+def spread(name, v):
+    q = np.percentile(v, [0, 5, 25, 50, 75, 95, 100]).astype(int)
+    print(f"{name}: min {q[0]}  5 % {q[1]}  25 % {q[2]}  median {q[3]}  75 % {q[4]}  95 % {q[5]}  max {q[6]}  mean {np.mean(v):.1f}")
+
+
+spread("batches per tile", nb)
+shapes = getattr(lib, "gbrs_em_tile_shapes", None)       # (a variant built before the call existed has no dictionary counts)
+if shapes is not None:
+    batches, entries = np.zeros(n_tiles, np.uint32), np.zeros(n_tiles, np.uint32)
+    _lib.check(shapes(eng._h, batches.ctypes.data, entries.ctypes.data, n_tiles))
+    spread("dictionary entries per tile", entries)
+    print(f"tiles with <= 96 entries (4 sum copies) {int(np.sum(entries <= 96))}, <= 195 (2) {int(np.sum((entries > 96) & (entries <= 195)))}, "
+          f"more (1) {int(np.sum(entries > 195))}")
+    cut = eng.tile_cut()
+    print(f"cut: passes {cut[0]} (0: the two-grid cut), tile words {cut[1]}")
+inf = eng.info()
+print(f"slots {int(inf.num_slots)}  light loci {int(inf.num_light_loci)}  heavy loci {int(inf.num_heavy_loci)}")
 order = np.argsort(t0)
-print("start order == tile order for the first 768:", bool(np.all(np.sort(order[:768]) == np.arange(768))))
+first = min(768, n_tiles)
+print(f"start order == tile order for the first {first}:", bool(np.all(np.sort(order[:first]) == np.arange(first))))

@@ -142,6 +142,42 @@ __device__ __forceinline__ double wave_sum_all(double v) {
     return v;  // same value in every lane (butterfly: fixed association)
 }
 
+// ---- cross-lane helpers on DPP (no LDS crossbar on a recursion's critical path) --------------
+template <int CTRL>
+__device__ __forceinline__ double dpp_f64(double x) {
+    int lo = __double2loint(x), hi = __double2hiint(x);
+    lo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xf, 0xf, false);
+    hi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+constexpr int DPP_QUAD_XOR1 = 0xB1;      // quad_perm:[1,0,3,2]
+constexpr int DPP_QUAD_XOR2 = 0x4E;      // quad_perm:[2,3,0,1]
+constexpr int DPP_ROW_HALF_MIRROR = 0x141;
+constexpr int DPP_ROW_MIRROR = 0x140;
+
+// sum over all 64 lanes, same value in every lane: quad, half-row and row steps on DPP, the four
+// row totals through v_readlane
+__device__ __forceinline__ double wave_sum_dpp(double v) {
+    v += dpp_f64<DPP_QUAD_XOR1>(v);
+    v += dpp_f64<DPP_QUAD_XOR2>(v);
+    v += dpp_f64<DPP_ROW_HALF_MIRROR>(v);
+    v += dpp_f64<DPP_ROW_MIRROR>(v);
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    double t = __hiloint2double(__builtin_amdgcn_readlane(hi, 0), __builtin_amdgcn_readlane(lo, 0));
+    t += __hiloint2double(__builtin_amdgcn_readlane(hi, 16), __builtin_amdgcn_readlane(lo, 16));
+    t += __hiloint2double(__builtin_amdgcn_readlane(hi, 32), __builtin_amdgcn_readlane(lo, 32));
+    t += __hiloint2double(__builtin_amdgcn_readlane(hi, 48), __builtin_amdgcn_readlane(lo, 48));
+    return t;
+}
+
+__device__ __forceinline__ double fast_recip_pos(double d) {
+    double r = __builtin_amdgcn_rcp(d);
+    double e = fma(-d, r, 1.0);
+    r = fma(r, e, r);
+    e = fma(-d, r, 1.0);
+    return fma(r, e, r);
+}
+
 // Block-wide sum, fixed association order (deterministic).  blockDim.x multiple of 64, <= 1024.
 __device__ __forceinline__ double block_sum(double v, double *lds /* >= 16 doubles */) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;

@@ -111,7 +111,7 @@ int select_device(int device) {
 
 // One trivial launch per translation unit: every .hip file carries its own code object, which the runtime loads on
 // the first launch of one of its kernels (~20 ms for the largest).
-namespace gbrs { void warm_em(hipStream_t); void warm_layout(hipStream_t); void warm_hmm(hipStream_t); }
+namespace gbrs { void warm_em(hipStream_t); void warm_layout(hipStream_t); void warm_hmm(hipStream_t); void warm_hmm_passes(hipStream_t); }
 
 extern "C" {
 
@@ -126,6 +126,7 @@ int gbrs_warm_up(int device) {
     gbrs::warm_em(nullptr);
     gbrs::warm_layout(nullptr);
     gbrs::warm_hmm(nullptr);
+    gbrs::warm_hmm_passes(nullptr);
     GBRS_HIP_CHECK(hipMemcpy(&h, d, sizeof(int), hipMemcpyDeviceToHost));     // also sets up the staging path of small copies
     GBRS_HIP_CHECK(hipFree(d));
     return GBRS_OK;

@@ -7,10 +7,10 @@
 // block is prefetched into registers while the current one is being reduced, and there is one
 // workgroup barrier per gene.  No dense contraction is reshaped for MFMA: the path is exp/log
 // and latency bound.
-#include "common.h"
-#include "hmm_route.h"
-#include "grid_knots.h"
-#include "scan_hmm.h"
+//
+// The passes over a finished run (grid dosages, panel matching, SNP imputation, path draws, diagnostics,
+// log-likelihoods) are hmm_passes.hip; both files share the handle of hmm_handle.h.
+#include "hmm_handle.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -19,9 +19,6 @@
 #include <cstdlib>
 
 namespace gbrs {
-
-constexpr double TINY = 4.9406564584124654e-324;   // np.nextafter(0, 1)
-constexpr int MAX_H = 16;   // S <= 136 (CC-style 16 founders); DO is H = 8, S = 36
 
 // ------------------------------------------------------------------------------------------
 // Emission.  Operation order follows get_genotype_probability:
@@ -356,26 +353,6 @@ struct RowMap {
     }
 };
 
-struct ChromDesc {
-    int64_t gene_off;     // offset of the chromosome's first gene in the per-sample gene axis
-    int64_t trans_off;    // offset (in S*S blocks) of tprob[c][0] in the transition buffer
-    int64_t bp_off;       // offset (in S entries) of the chromosome's backpointer rows
-    int64_t chunk_off;    // offset (in BT_B-row chunks) of the chromosome's backtrace chunk maps
-    int32_t n_genes, n_trans;
-    // Blocked scan (hmm_blocked.inc): a descriptor may stand for a run of genes of a chromosome whose recursion starts
-    // from an injected boundary vector instead of the chromosome's own start / end.
-    int32_t inject;       // -1: the natural start; else the slot of the block's boundary vector
-    int32_t real_chrom;   // the chromosome whose last gene this descriptor ends on (forward / delta), else -1
-};
-
-// ---- cross-lane helpers on DPP (no LDS crossbar on the recursion's critical path) ------------
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double x) {
-    int lo = __double2loint(x), hi = __double2hiint(x);
-    lo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xf, 0xf, false);
-    hi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
 #if defined(HMM_ABLATE_SAMEBLOCK)
 #define HMM_BLK(i) 0
 #else
@@ -386,11 +363,8 @@ __device__ __forceinline__ double dpp_f64(double x) {
 #else
 #define HMM_LOAD_PRED
 #endif
-constexpr int DPP_QUAD_XOR1 = 0xB1;      // quad_perm:[1,0,3,2]
-constexpr int DPP_QUAD_XOR2 = 0x4E;      // quad_perm:[2,3,0,1]
-constexpr int DPP_ROW_HALF_MIRROR = 0x141;
-constexpr int DPP_ROW_MIRROR = 0x140;
 
+// ---- cross-lane helpers on DPP (dpp_f64, wave_sum_dpp: common.h) ------------------------------
 // sum over the 4 lanes of a quad (LPS = 4 lanes per state); result in every lane of the quad
 __device__ __forceinline__ double quad_sum(double v) {
     v += dpp_f64<DPP_QUAD_XOR1>(v);
@@ -410,21 +384,6 @@ __device__ __forceinline__ void quad_argmax(double &v, int &k) {
         const int ok = __builtin_amdgcn_update_dpp(k, k, DPP_QUAD_XOR2, 0xf, 0xf, false);
         if (ov > v || (ov == v && ok < k)) { v = ov; k = ok; }
     }
-}
-
-// sum over all 64 lanes, same value in every lane: quad, half-row and row steps on DPP, the four
-// row totals through v_readlane
-__device__ __forceinline__ double wave_sum_dpp(double v) {
-    v += dpp_f64<DPP_QUAD_XOR1>(v);
-    v += dpp_f64<DPP_QUAD_XOR2>(v);
-    v += dpp_f64<DPP_ROW_HALF_MIRROR>(v);
-    v += dpp_f64<DPP_ROW_MIRROR>(v);
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    double t = __hiloint2double(__builtin_amdgcn_readlane(hi, 0), __builtin_amdgcn_readlane(lo, 0));
-    t += __hiloint2double(__builtin_amdgcn_readlane(hi, 16), __builtin_amdgcn_readlane(lo, 16));
-    t += __hiloint2double(__builtin_amdgcn_readlane(hi, 32), __builtin_amdgcn_readlane(lo, 32));
-    t += __hiloint2double(__builtin_amdgcn_readlane(hi, 48), __builtin_amdgcn_readlane(lo, 48));
-    return t;
 }
 
 // Workgroup barrier for the recursion loops: waits for this wave's LDS traffic only.  A plain
@@ -484,14 +443,6 @@ __global__ void lane_blocks_kernel(int S, int LPS, int KPL, int64_t n_blocks, co
         p_q[x] = exp(v);
         pt_q[x] = exp(t[b * bs + (int64_t)kk * S + jj]);
     }
-}
-
-__device__ __forceinline__ double fast_recip_pos(double d) {
-    double r = __builtin_amdgcn_rcp(d);
-    double e = fma(-d, r, 1.0);
-    r = fma(r, e, r);
-    e = fma(-d, r, 1.0);
-    return fma(r, e, r);
 }
 
 // pe = exp(eprob): every gene at once, before the sequential sweeps
@@ -1620,7 +1571,6 @@ backward_wave_kernel(int n_samples, int64_t genes_per_sample, const ChromDesc *_
 // delta_lanes_kernel (below) the tie at 64 samples turns into a small win (7.07 vs 7.31 ms per pass with the
 // emission), so hmm_launch switches both at 64 samples (HMM_MFMA_MIN, HMM_DLANES_MIN).
 // ------------------------------------------------------------------------------------------
-typedef double mfma_d4 __attribute__((ext_vector_type(4)));
 struct __attribute__((aligned(8))) mf_pair { double x, y; };     // 16 bytes at 8-byte alignment (a lane's row piece starts at 72 g)
 constexpr int MF_S = 36, MF_RB = 3, MF_KB = 9, MF_OPS = MF_RB * MF_KB, MF_PAIRS = (MF_OPS + 1) / 2;
 constexpr int MF_BLK = MF_PAIRS * 128;                           // doubles per block: [pair][lane][2]
@@ -2444,175 +2394,14 @@ viterbi_bp_lanes_kernel(int n_samples, RowMap drows /* of delta */, int64_t bp_p
     }
 }
 
-// ---- post-processing of the posteriors (gbrs_utils.py:612-697 interpolate, :863-938 export) ---
-
-// Linear interpolation of the rows of y (S x n points at ascending x) onto xq, operation order of
-// scipy interp1d(kind='linear'):  slope = (y_hi - y_lo) / (x_hi - x_lo);  y = slope * (x - x_lo) + y_lo
-__global__ void interpolate_kernel(int S, int n, const double *__restrict__ xs, const double *__restrict__ y,
-                                   int m, const double *__restrict__ xq, double *__restrict__ out) {
-    const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (id >= (int64_t)S * m) return;
-    const int s = (int)(id / m), g = (int)(id - (int64_t)s * m);
-    const double x = xq[g];
-    int lo = 0, hi = n;                        // searchsorted(xs, x, side='left')
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (xs[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    const int idx = min(max(lo, 1), n - 1);
-    const double x_lo = xs[idx - 1], x_hi = xs[idx];
-    const double y_lo = y[(int64_t)s * n + idx - 1], y_hi = y[(int64_t)s * n + idx];
-    const double slope = (y_hi - y_lo) / (x_hi - x_lo);
-    out[(int64_t)s * m + g] = slope * (x - x_lo) + y_lo;
-}
-
-// 36 -> 8 dosage: out[r][h] = sum_g gprob[r][g] * 0.5 * (#h in genotype g)  (convmat, :896-901, :927)
-__global__ void dosage_kernel(int H, int S, int64_t rows, const double *__restrict__ gprob,
-                              double *__restrict__ out) {
-    const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (id >= rows * H) return;
-    const int64_t r = id / H;
-    const int h = (int)(id - r * H);
-    const double *p = gprob + r * S;
-    double acc = 0.0;
-    int g = 0;
-    for (int a = 0; a < H; ++a)
-        for (int b = a; b < H; ++b, ++g) {
-            const double w = 0.5 * ((a == h) + (b == h));
-            acc += p[g] * w;
-        }
-    out[id] = acc;
-}
-
-#include "hmm_grid.inc"
-#include "hmm_match.inc"
-#include "hmm_impute.inc"
-#include "hmm_sample.inc"
-#include "hmm_diag.inc"
-#include "hmm_loglik.inc"
-
 }  // namespace gbrs
 
 using namespace gbrs;
-
-struct gbrs_hmm {
-    int device = 0;
-    hipStream_t stream = nullptr, stream_b = nullptr, stream_c = nullptr;   // see hmm_launch
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ev_fork = nullptr, ev_b = nullptr, ev_c1 = nullptr, ev_c = nullptr;
-    hipEvent_t ev_ops[2] = {nullptr, nullptr};   // blocked scan: the alpha / backward operator kernels are done
-    int H = 0, S = 0, n_chrom = 0, n_samples = 0;
-    std::vector<ChromDesc> chroms;
-    int64_t total_genes = 0, total_trans = 0, total_bp = 0, total_chunks = 0;
-    int max_bp_rows = 0;                      // max over chromosomes of min(n_genes, n_trans)
-    bool have_eprob = false, ran = false;
-    bool pe_ready = false;                    // peprob = exp(eprob) is current (the emission kernels write both)
-    bool logs_ready = false;                  // alpha / beta / scaler of the last run have been made (hmm_make_logs)
-    DevBuf<ChromDesc> d_chroms;
-    DevBuf<int32_t> d_order;                  // chromosome indices, longest first
-    DevBuf<double> tprob, pprob, pprob_t, init_vec;   // log T, exp(T), exp(T) transposed per block
-    DevBuf<double> tprob_q;                   // S = 36 / 136: log T in the chain kernels' lane order (pprob, pprob_t too)
-    bool quad = false;                        // tables are in lane order
-    DevBuf<double> amat_f, amat_b;            // S = 36, large batches: the MFMA operands of exp(T) and its transpose (made on first use)
-    DevBuf<double> expr, avecs, eprob, peprob, xsum, bhat, alpha, beta, gamma, delta, scaler, invz;
-    double *expr_stage = nullptr;      // pinned host image of `expr` for small batches (gbrs_hmm_set_expression)
-    size_t expr_stage_n = 0;
-    DevBuf<double> bscale, bcorr;             // free-running backward: per-gene scale and log correction
-    DevBuf<uint8_t> has_avec;
-    DevBuf<uint16_t> bp, bt_exit;             // backpointers; per-chunk exit maps of the backtrace
-    DevBuf<int32_t> last_state, states, calls;
-    double t_emis = 0, t_fwd = 0, t_bwd = 0, t_bt = 0, t_run = 0;
-    // blocked scan (hmm_blocked.inc; 36 states, up to HMM_BLOCKED_MAX samples): the chromosomes cut into blocks
-    // Two block structures (round 4): the forward one (alpha, delta) may open every chromosome with a long block that is
-    // chained DIRECTLY from the chromosome's start while the other blocks' operators are being built (no operator for it);
-    // the backward one closes every chromosome with such a block.  [0] forward, [1] backward.
-    int n_vb = 0, blk_samples = 0;            // n_vb: the larger of the two block counts (buffers are sized by it)
-    int n_blk[2] = {0, 0}, n_head[2] = {0, 0};
-    // The last run's route.  What later calls read from it: free_backward() - beta needs bcorr; Blocked - the backward chains
-    // started from injected vectors; BlockedRank - gbrs_hmm_info reports how the fix-ups went; tie_check - dspec_tie holds
-    // the flags of the backtrace's margin check; delta_interleaved - how `delta` is laid out.
-    HmmRoute last;
-    DevBuf<BlockRange> d_ranges[2];
-    DevBuf<int32_t> d_first_block[2];         // blocks of chromosome c: first_block[c] .. first_block[c+1]
-    DevBuf<int32_t> d_vorder[2];              // block indices, the directly chained ones first (n_head of them)
-    DevBuf<ChromDesc> d_vfwd, d_vbwd;         // the blocks as descriptors of the forward / delta and of the backward chains
-    std::vector<BlockRange> h_ranges0;        // host copy of d_ranges[0]
-    DevBuf<double> dspec_c;                   // rank-convergence delta: every block's constant against the block before it,
-    DevBuf<int32_t> dspec_g, dspec_fail;      // the gene from which its stored values stand, per (sample, chromosome) failure flags
-    DevBuf<int32_t> dspec_tie;                // per (sample, chromosome): a decision of the path inside the error of the blocks' vectors
-    hipStream_t stream_h[3] = {nullptr, nullptr, nullptr};   // the direct chains of alpha / backward / delta
-    hipEvent_t ev_head[3] = {nullptr, nullptr, nullptr};
-    // Pipelined batch pass (round 4, hmm_launch_groups): the chromosomes in two groups of consecutive chromosomes, each with
-    // its own emission -> chains -> posterior / backtrace pipeline on its own three streams, so that the emission of the
-    // second group and the posteriors / backtraces of whichever group is done run beside the chains that set the pass's length.
-    bool emission_pending = false;            // gbrs_hmm_set_expression left the emission kernel to the next run
-    double em_thr = 0.0, em_sigma = 0.0;
-    int n_groups = 0;
-    int grp_lo[2] = {0, 0}, grp_hi[2] = {0, 0}, grp_order_off[2] = {0, 0}, grp_max_bp[2] = {0, 0};
-    DevBuf<int32_t> d_order_grp;              // per group: its chromosomes, longest first
-    hipStream_t stream_g[3] = {nullptr, nullptr, nullptr};   // the second group's streams (the first uses stream / stream_b / stream_c)
-    hipEvent_t gev_em[2] = {nullptr, nullptr}, gev_b[2] = {nullptr, nullptr}, gev_c[2] = {nullptr, nullptr},
-               gev_done[2] = {nullptr, nullptr}, gev_start = nullptr;
-    DevBuf<double> g_f, g_b, g_d, inj_f, inj_b, inj_d;   // block operators [sample][block][36][36], boundary vectors [sample][block][36]
-    DevBuf<int32_t> e_f, e_b;                 // power-of-two exponents of the operators' columns
-    // Grid pass (hmm_grid.inc): the marker grid is sample independent and stays here like avecs; the two output buffers
-    // are sized by the last call that asked for them.
-    bool have_grid = false;
-    int grid_tiles = 0;
-    int64_t grid_points = 0;                  // grid points of the handle's chromosomes
-    DevBuf<GridChrom> d_grid_chroms;
-    DevBuf<GridTile> d_grid_tiles;
-    DevBuf<double> grid_knot_x, grid_x, grid_dosage, grid_gamma;
-    DevBuf<int32_t> grid_knot_gene;
-    double t_grid = 0;
-    bool grid_dosage_ready = false;           // grid_dosage holds the last run's dosages for `grid_dosage_sample` (-1: all)
-    int grid_dosage_sample = -1;
-    // Match pass (hmm_match.inc): the panel's dosages in grid_dosage's row layout, its norms, the outputs of the last call
-    int n_panel = 0;
-    bool match_vec2 = false;                  // rows and chromosome starts are 16-byte aligned (even H)
-    DevBuf<double> match_panel, match_cross, match_snorm;
-    DevBuf<MatchChrom> d_match_chroms;
-    std::vector<double> panel_norm;           // [n_panel][n_chrom]
-    double t_match = 0;
-    // SNP imputation (hmm_impute.inc): positions, patterns and the knot above every SNP stay here like the grid (16 B per
-    // SNP), with the knots and their gene rows; snp_d is D[n][total_genes][H], the founder dosages at the genes of the
-    // last run, made by the first gbrs_hmm_impute call after a run and kept for its later chunks; snp_out holds one chunk
-    int64_t n_snps = 0;
-    DevBuf<SnpChrom> d_snp_chroms;
-    DevBuf<double> snp_knot_x, snp_x, snp_d, snp_out;
-    DevBuf<int32_t> snp_knot_row, snp_idx;
-    DevBuf<uint32_t> snp_mask;
-    bool snp_d_ready = false;                 // snp_d holds the last run's dosages for `snp_d_sample` (-1: all)
-    int snp_d_sample = -1;
-    double t_snp_setup = 0, t_snp_d = 0, t_snp_kernel = 0;   // device ms: the last set_snps; D and the kernel of the last pass
-    // Path draws (hmm_sample.inc): the change table is made on the first call; the other buffers hold one slab of draws
-    DevBuf<uint8_t> smp_change_tab, smp_cols, smp_paths;
-    DevBuf<int32_t> smp_changes;
-    DevBuf<uint32_t> smp_streams;
-    DevBuf<unsigned long long> smp_degenerate;
-    double t_sample = 0;
-    // Diagnostics (hmm_diag.inc): the device images of the five outputs, [n][total_genes] each, and the pair posteriors
-    // of one (sample, chromosome); sized by the last call that asked for them
-    DevBuf<double> diag_xo, diag_pswitch, diag_errlod, diag_maxprob, diag_xi;
-    DevBuf<int32_t> diag_maxmarg;
-    double t_diag = 0;
-    // Log-likelihood (hmm_loglik.inc): the sums of the last call, and the candidate tables of one chromosome as uploaded
-    // (ll_t) and as exp() transposed per block (ll_pt); they grow to the largest call and are reused
-    DevBuf<double> ll_out, ll_t, ll_pt;
-    double t_loglik = 0;
-};
 
 namespace {
 
 static_assert(MF_S == 36, "hmm_route.h names the 36-state kernels' state count by its number");
 HmmShape hmm_shape(const gbrs_hmm *h) { return HmmShape{h->S, h->H, h->n_samples, h->n_chrom, h->total_trans}; }
-
-void match_clear_panel(gbrs_hmm *h) {
-    h->match_panel.release();
-    h->d_match_chroms.release();
-    h->panel_norm.clear();
-    h->n_panel = 0;
-}
 
 int hmm_alloc_samples(gbrs_hmm *h, int n_samples) {
     if (n_samples == h->n_samples && h->eprob.p) return GBRS_OK;
@@ -2660,11 +2449,13 @@ void launch_logs(gbrs_hmm *h, int parts, hipStream_t st) {
                        h->alpha.p, h->scaler.p, h->beta.p);
 }
 
+}  // namespace
+
 // The log-domain intermediates of the reference (alpha, scaler, beta).  gbrs reconstruct saves none of
 // them, so a run leaves them out (three of the seven per-state arrays the outputs pass would move, and the
-// suffix sum of the backward sweep's scale constants); the first gbrs_hmm_get() that asks makes them
+// suffix sum of the backward sweep's scale constants); the first gbrs_hmm_get() or pass that asks makes them
 // for every sample of the last run.
-int hmm_make_logs(gbrs_hmm *h) {
+int gbrs::hmm_make_logs(gbrs_hmm *h) {
     if (h->logs_ready) return GBRS_OK;
     const size_t gs = (size_t)h->total_genes * h->n_samples;
     if (gs == 0) { h->logs_ready = true; return GBRS_OK; }
@@ -2685,6 +2476,8 @@ int hmm_make_logs(gbrs_hmm *h) {
     h->logs_ready = true;
     return GBRS_OK;
 }
+
+namespace {
 
 #ifndef HMM_NSET
 #define HMM_NSET 3        // register sets of the one-sample-per-wave recursions
@@ -2941,7 +2734,7 @@ int hmm_launch_groups(gbrs_hmm *h, const HmmRoute &r, const HmmTuning &t) {
     GBRS_TRY(hmm_prepare_groups(h, t));
     hipStream_t sa = h->stream;
     GBRS_TRY(hmm_prepare_mfma_tables(h));
-    h->logs_ready = false;
+    hmm_invalidate_run(h);
     h->last = r;
     GBRS_HIP_CHECK(hipEventRecord(h->gev_start, sa));
     GBRS_HIP_CHECK(hipEventRecord(h->ev[1], sa));
@@ -3229,7 +3022,7 @@ int hmm_launch(gbrs_hmm *h, const HmmRoute &r, const HmmTuning &t) {
     hipStream_t sa = h->stream, sb = r.serial ? sa : h->stream_b, sc = r.serial ? sa : h->stream_c;
     if (r.sweep == HmmSweep::Blocked) GBRS_TRY(hmm_prepare_blocks(h, t));
     if (r.sweep == HmmSweep::Blocked || r.sweep == HmmSweep::Mfma) GBRS_TRY(hmm_prepare_mfma_tables(h));
-    h->logs_ready = false;
+    hmm_invalidate_run(h);
     h->last = r;
     GBRS_HIP_CHECK(hipEventRecord(h->ev[1], sa));
     if (!h->pe_ready) {                               // caller-supplied emissions (gbrs_hmm_set_eprob)
@@ -3515,8 +3308,7 @@ int gbrs_hmm_set_expression(gbrs_hmm_t *h, int n_samples, const double *const *e
     h->have_eprob = true;
     h->pe_ready = !h->emission_pending;
     h->ran = false;
-    h->grid_dosage_ready = false;
-    h->snp_d_ready = false;
+    hmm_invalidate_dosages(h);
     return GBRS_OK;
 }
 
@@ -3536,8 +3328,7 @@ int gbrs_hmm_set_eprob(gbrs_hmm_t *h, int n_samples, const double *const *eprob)
     h->emission_pending = false;
     h->pe_ready = false;
     h->ran = false;
-    h->grid_dosage_ready = false;
-    h->snp_d_ready = false;
+    hmm_invalidate_dosages(h);
     h->t_emis = 0;
     return GBRS_OK;
 }
@@ -3550,8 +3341,7 @@ int gbrs_hmm_run(gbrs_hmm_t *h) {
     const int S = h->S;
     const HmmTuning t = hmm_tuning_from_env();
     const HmmRoute r = hmm_route(hmm_shape(h), t, h->emission_pending);
-    h->grid_dosage_ready = false;
-    h->snp_d_ready = false;
+    hmm_invalidate_dosages(h);
     int rc;
     if (r.grouped) {
         rc = hmm_launch_groups(h, r, t);
@@ -3664,698 +3454,6 @@ int gbrs_hmm_info(gbrs_hmm_t *h, gbrs_hmm_info_t *info) {
     return GBRS_OK;
 }
 
-int gbrs_interpolate(int S, int n_points, const double *x, const double *y, int n_grid,
-                     const double *x_grid, double *out, int device) {
-    if (S < 1 || n_points < 2 || n_grid < 0 || !x || !y || (n_grid && (!x_grid || !out)))
-        return fail(GBRS_ERR_INVALID, "bad argument");
-    for (int i = 0; i + 1 < n_points; ++i)
-        if (!(x[i] <= x[i + 1])) return fail(GBRS_ERR_INVALID, "x must be ascending");
-    for (int g = 0; g < n_grid; ++g) {
-        if (x_grid[g] < x[0])
-            return fail(GBRS_ERR_INVALID, "A value (%.17g) in x_new is below the interpolation range's minimum value (%.17g).",
-                        x_grid[g], x[0]);
-        if (x_grid[g] > x[n_points - 1])
-            return fail(GBRS_ERR_INVALID, "A value (%.17g) in x_new is above the interpolation range's maximum value (%.17g).",
-                        x_grid[g], x[n_points - 1]);
-    }
-    if (n_grid == 0) return GBRS_OK;
-    GBRS_TRY(select_device(device));
-    DevBuf<double> d_x, d_y, d_q, d_o;
-    GBRS_TRY(d_x.alloc(n_points));
-    GBRS_TRY(d_y.alloc((size_t)S * n_points));
-    GBRS_TRY(d_q.alloc(n_grid));
-    GBRS_TRY(d_o.alloc((size_t)S * n_grid));
-    GBRS_HIP_CHECK(hipMemcpy(d_x.p, x, d_x.bytes(), hipMemcpyHostToDevice));
-    GBRS_HIP_CHECK(hipMemcpy(d_y.p, y, d_y.bytes(), hipMemcpyHostToDevice));
-    GBRS_HIP_CHECK(hipMemcpy(d_q.p, x_grid, d_q.bytes(), hipMemcpyHostToDevice));
-    const int64_t total = (int64_t)S * n_grid;
-    hipLaunchKernelGGL(interpolate_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, S, n_points,
-                       d_x.p, d_y.p, n_grid, d_q.p, d_o.p);
-    GBRS_HIP_CHECK(hipGetLastError());
-    GBRS_HIP_CHECK(hipMemcpy(out, d_o.p, d_o.bytes(), hipMemcpyDeviceToHost));
-    return GBRS_OK;
-}
-
-int gbrs_genoprob_dosage(int num_haps, int64_t n_rows, const double *gprob, double *out, int device) {
-    if (num_haps < 1 || num_haps > MAX_H || n_rows < 0 || (n_rows && (!gprob || !out)))
-        return fail(GBRS_ERR_INVALID, "bad argument");
-    if (n_rows == 0) return GBRS_OK;
-    GBRS_TRY(select_device(device));
-    const int S = num_haps * (num_haps + 1) / 2;
-    DevBuf<double> d_p, d_o;
-    GBRS_TRY(d_p.alloc((size_t)n_rows * S));
-    GBRS_TRY(d_o.alloc((size_t)n_rows * num_haps));
-    GBRS_HIP_CHECK(hipMemcpy(d_p.p, gprob, d_p.bytes(), hipMemcpyHostToDevice));
-    const int64_t total = n_rows * num_haps;
-    hipLaunchKernelGGL(dosage_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, num_haps, S, n_rows,
-                       d_p.p, d_o.p);
-    GBRS_HIP_CHECK(hipGetLastError());
-    GBRS_HIP_CHECK(hipMemcpy(out, d_o.p, d_o.bytes(), hipMemcpyDeviceToHost));
-    return GBRS_OK;
-}
-
-int gbrs_grid_knots(int n_genes, const double *gene_pos, int n_grid, const double *grid, double *knots,
-                    int32_t *knot_gene) {
-    char msg[256];
-    if (grid_knots(n_genes, gene_pos, n_grid, grid, knots, knot_gene, msg, sizeof msg) != 0)
-        return fail(GBRS_ERR_INVALID, "%s", msg);
-    return GBRS_OK;
-}
-
-int gbrs_hmm_set_grid(gbrs_hmm_t *h, const int32_t *n_pos, const double *const *gene_pos, const int32_t *n_grid,
-                      const double *const *grid) {
-    if (!h || !n_pos || !gene_pos || !n_grid || !grid) return fail(GBRS_ERR_INVALID, "bad argument");
-    // everything is prepared and checked on the host before the handle changes
-    const int P = grid_tile_points(h->S);
-    std::vector<GridChrom> gc(h->n_chrom);
-    std::vector<GridTile> tiles;
-    std::vector<double> knot_x, x;
-    std::vector<int32_t> knot_gene;
-    for (int c = 0; c < h->n_chrom; ++c) {
-        const ChromDesc &cd = h->chroms[c];
-        GridChrom &g = gc[c];
-        g.gene_off = cd.gene_off;
-        g.knot_off = (int32_t)knot_x.size();
-        g.point_off = (int32_t)x.size();
-        g.n_knots = g.n_points = 0;
-        if (n_grid[c] < 0) return fail(GBRS_ERR_INVALID, "n_grid[%d] is negative", c);
-        if (n_grid[c] == 0) continue;
-        if (n_pos[c] == 0)
-            return fail(GBRS_ERR_INVALID, "index -1 is out of bounds for axis 1 with size 0 (grid chromosome %d has no genes)", c);
-        if (n_pos[c] != cd.n_genes)
-            return fail(GBRS_ERR_INVALID, "chromosome %d: %d gene positions for %d genes", c, n_pos[c], cd.n_genes);
-        if ((int64_t)x.size() + n_grid[c] > INT32_MAX) return fail(GBRS_ERR_INVALID, "too many grid points");
-        g.n_knots = cd.n_genes + 2;
-        g.n_points = n_grid[c];
-        knot_x.resize(knot_x.size() + g.n_knots);
-        knot_gene.resize(knot_x.size());
-        GBRS_TRY(gbrs_grid_knots(cd.n_genes, gene_pos[c], n_grid[c], grid[c], knot_x.data() + g.knot_off,
-                                 knot_gene.data() + g.knot_off));
-        x.insert(x.end(), grid[c], grid[c] + n_grid[c]);
-        for (int32_t first = 0; first < g.n_points; first += P) tiles.push_back(GridTile{c, first});
-    }
-    GBRS_TRY(select_device(h->device));
-    DevBuf<GridChrom> d_gc;
-    DevBuf<GridTile> d_tiles;
-    DevBuf<double> d_knot_x, d_x;
-    DevBuf<int32_t> d_knot_gene;
-    GBRS_TRY(d_gc.alloc(gc.size()));
-    GBRS_TRY(d_tiles.alloc(tiles.size()));
-    GBRS_TRY(d_knot_x.alloc(knot_x.size()));
-    GBRS_TRY(d_knot_gene.alloc(knot_gene.size()));
-    GBRS_TRY(d_x.alloc(x.size()));
-    GBRS_HIP_CHECK(hipMemcpy(d_gc.p, gc.data(), d_gc.bytes(), hipMemcpyHostToDevice));
-    if (!tiles.empty()) {
-        GBRS_HIP_CHECK(hipMemcpy(d_tiles.p, tiles.data(), d_tiles.bytes(), hipMemcpyHostToDevice));
-        GBRS_HIP_CHECK(hipMemcpy(d_knot_x.p, knot_x.data(), d_knot_x.bytes(), hipMemcpyHostToDevice));
-        GBRS_HIP_CHECK(hipMemcpy(d_knot_gene.p, knot_gene.data(), d_knot_gene.bytes(), hipMemcpyHostToDevice));
-        GBRS_HIP_CHECK(hipMemcpy(d_x.p, x.data(), d_x.bytes(), hipMemcpyHostToDevice));
-    }
-    h->d_grid_chroms.swap(d_gc);
-    h->d_grid_tiles.swap(d_tiles);
-    h->grid_knot_x.swap(d_knot_x);
-    h->grid_knot_gene.swap(d_knot_gene);
-    h->grid_x.swap(d_x);
-    h->grid_tiles = (int)tiles.size();
-    h->grid_points = (int64_t)x.size();
-    h->have_grid = true;
-    h->grid_dosage_ready = false;
-    match_clear_panel(h);
-    return GBRS_OK;
-}
-
-// The grid kernel for `sample` (-1: all n) into grid_dosage and / or grid_gamma, timed into t_grid; returns when it is done.
-static int hmm_grid_launch(gbrs_hmm *h, int sample, bool want_dosage, bool want_gamma) {
-    const int S = h->S, H = h->H;
-    const int n = sample < 0 ? h->n_samples : 1;
-    const size_t n_dosage = (size_t)n * h->grid_points * H, n_gamma = (size_t)n * h->grid_points * S;
-    if (want_dosage) h->grid_dosage_ready = false;
-    if (want_dosage && h->grid_dosage.n != n_dosage) GBRS_TRY(h->grid_dosage.alloc(n_dosage));
-    if (want_gamma && h->grid_gamma.n != n_gamma) GBRS_TRY(h->grid_gamma.alloc(n_gamma));
-    const dim3 grid((unsigned)h->grid_tiles, (unsigned)n);
-    const size_t lds = grid_tile_lds(S);
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, grid, dim3(64), lds, h->stream, H, S, grid_tile_points(S), h->total_genes, h->grid_points,
-                           std::max(sample, 0), h->d_grid_chroms.p, h->d_grid_tiles.p, h->grid_knot_x.p, h->grid_knot_gene.p,
-                           h->grid_x.p, h->gamma.p, want_dosage ? h->grid_dosage.p : nullptr, want_gamma ? h->grid_gamma.p : nullptr);
-    };
-    GBRS_HIP_CHECK(hipEventRecord(h->ev[0], h->stream));
-    if (S <= 64) launch(grid_kernel<1>);
-    else if (S <= 128) launch(grid_kernel<2>);
-    else launch(grid_kernel<3>);          // S <= 136 (MAX_H = 16)
-    GBRS_HIP_CHECK(hipEventRecord(h->ev[1], h->stream));
-    GBRS_HIP_CHECK(hipGetLastError());
-    GBRS_HIP_CHECK(hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, h->ev[0], h->ev[1]) == hipSuccess) h->t_grid = ms;
-    if (want_dosage) {
-        h->grid_dosage_ready = true;
-        h->grid_dosage_sample = sample;
-    }
-    return GBRS_OK;
-}
-
-int gbrs_hmm_grid(gbrs_hmm_t *h, int sample, double *dosage, double *gamma_grid) {
-    RoctxRange roctx_range("gbrs_hmm_grid");
-    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
-    if (!h->ran) return fail(GBRS_ERR_STATE, "run() has not been called");
-    if (!h->have_grid) return fail(GBRS_ERR_INVALID, "no grid on the handle: call gbrs_hmm_set_grid first");
-    if (sample < -1 || sample >= h->n_samples) return fail(GBRS_ERR_INVALID, "sample out of range");
-    if ((!dosage && !gamma_grid) || h->grid_tiles == 0) return GBRS_OK;
-    GBRS_TRY(select_device(h->device));
-    const int n = sample < 0 ? h->n_samples : 1;
-    const size_t n_dosage = (size_t)n * h->grid_points * h->H, n_gamma = (size_t)n * h->grid_points * h->S;
-    GBRS_TRY(hmm_grid_launch(h, sample, dosage != nullptr, gamma_grid != nullptr));
-    if (dosage) GBRS_HIP_CHECK(hipMemcpy(dosage, h->grid_dosage.p, n_dosage * sizeof(double), hipMemcpyDeviceToHost));
-    if (gamma_grid) GBRS_HIP_CHECK(hipMemcpy(gamma_grid, h->grid_gamma.p, n_gamma * sizeof(double), hipMemcpyDeviceToHost));
-    return GBRS_OK;
-}
-
-int gbrs_hmm_grid_info(gbrs_hmm_t *h, int64_t *n_points, double *last_ms) {
-    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
-    if (n_points) *n_points = h->have_grid ? h->grid_points : 0;
-    if (last_ms) *last_ms = h->t_grid;
-    return GBRS_OK;
-}
-
-int gbrs_hmm_set_panel(gbrs_hmm_t *h, int n_panel, const double *const *panel) {
-    RoctxRange roctx_range("gbrs_hmm_set_panel");
-    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
-    if (n_panel < 0 || (n_panel > 0 && !panel)) return fail(GBRS_ERR_INVALID, "bad argument");
-    if (!h->have_grid) return fail(GBRS_ERR_INVALID, "no grid on the handle: call gbrs_hmm_set_grid first");
-    if (n_panel == 0) {
-        match_clear_panel(h);
-        return GBRS_OK;
-    }
-    // everything is prepared and checked before the handle changes
-    const int64_t ld = h->grid_points * h->H;
-    for (int j = 0; j < n_panel; ++j) {
-        if (!panel[j]) return fail(GBRS_ERR_INVALID, "panel[%d] is NULL", j);
-        for (int64_t k = 0; k < ld; ++k)
-            if (!std::isfinite(panel[j][k]))
-                return fail(GBRS_ERR_INVALID, "panel entry %d holds a value that is not finite (grid point %lld, founder %d)", j,
-                            (long long)(k / h->H), (int)(k % h->H));
-    }
-    std::vector<GridChrom> gc(h->n_chrom);
-    std::vector<MatchChrom> mc;
-    GBRS_TRY(select_device(h->device));
-    GBRS_HIP_CHECK(hipMemcpy(gc.data(), h->d_grid_chroms.p, gc.size() * sizeof(GridChrom), hipMemcpyDeviceToHost));
-    for (int c = 0; c < h->n_chrom; ++c)
-        if (gc[c].n_points > 0)
-            mc.push_back(MatchChrom{(int64_t)gc[c].point_off * h->H, (int64_t)gc[c].n_points * h->H, c});
-    DevBuf<double> d_panel, d_norm;
-    DevBuf<MatchChrom> d_mc;
-    GBRS_TRY(d_panel.alloc((size_t)n_panel * ld));
-    GBRS_TRY(d_norm.alloc((size_t)n_panel * h->n_chrom));
-    GBRS_TRY(d_mc.alloc(mc.size()));
-    std::vector<double> norm((size_t)n_panel * h->n_chrom, 0.0);
-    if (ld > 0) {
-        for (int j = 0; j < n_panel; ++j)
-            GBRS_HIP_CHECK(hipMemcpy(d_panel.p + (size_t)j * ld, panel[j], (size_t)ld * sizeof(double), hipMemcpyHostToDevice));
-        GBRS_HIP_CHECK(hipMemcpy(d_mc.p, mc.data(), d_mc.bytes(), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(match_norm_kernel, dim3((unsigned)n_panel, (unsigned)h->n_chrom), dim3(64), 0, h->stream, h->H, ld,
-                           h->d_grid_chroms.p, d_panel.p, d_norm.p);
-        GBRS_HIP_CHECK(hipGetLastError());
-        GBRS_HIP_CHECK(hipStreamSynchronize(h->stream));
-        GBRS_HIP_CHECK(hipMemcpy(norm.data(), d_norm.p, d_norm.bytes(), hipMemcpyDeviceToHost));
-    }
-    h->match_panel.swap(d_panel);
-    h->d_match_chroms.swap(d_mc);
-    h->panel_norm.swap(norm);
-    h->n_panel = n_panel;
-    h->match_vec2 = h->H % 2 == 0;           // ld and every chromosome's first column are multiples of H
-    return GBRS_OK;
-}
-
-int gbrs_hmm_match(gbrs_hmm_t *h, int sample, double *cross, double *sample_norm) {
-    RoctxRange roctx_range("gbrs_hmm_match");
-    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
-    if (!h->ran) return fail(GBRS_ERR_STATE, "run() has not been called");
-    if (!h->have_grid || h->n_panel == 0) return fail(GBRS_ERR_INVALID, "no panel on the handle: call gbrs_hmm_set_panel first");
-    if (sample < -1 || sample >= h->n_samples) return fail(GBRS_ERR_INVALID, "sample out of range");
-    GBRS_TRY(select_device(h->device));
-    const int n = sample < 0 ? h->n_samples : 1, M = h->n_panel, n_chrom = h->n_chrom;
-    const int64_t ld = h->grid_points * h->H;
-    const size_t n_cross = (size_t)n * n_chrom * M, n_norm = (size_t)n * n_chrom;
-    if (h->match_cross.n != n_cross) GBRS_TRY(h->match_cross.alloc(n_cross));
-    if (h->match_snorm.n != n_norm) GBRS_TRY(h->match_snorm.alloc(n_norm));
-    const unsigned on_grid = (unsigned)h->d_match_chroms.n;
-    if (on_grid && !(h->grid_dosage_ready && h->grid_dosage_sample == sample))
-        GBRS_TRY(hmm_grid_launch(h, sample, true, false));
-    GBRS_HIP_CHECK(hipEventRecord(h->ev[0], h->stream));
-    GBRS_HIP_CHECK(hipMemsetAsync(h->match_cross.p, 0, h->match_cross.bytes(), h->stream));    // chromosomes off the grid: 0.0
-    GBRS_HIP_CHECK(hipMemsetAsync(h->match_snorm.p, 0, h->match_snorm.bytes(), h->stream));
-    if (on_grid) {
-        hipLaunchKernelGGL(match_norm_kernel, dim3((unsigned)n, (unsigned)n_chrom), dim3(64), 0, h->stream, h->H, ld,
-                           h->d_grid_chroms.p, h->grid_dosage.p, h->match_snorm.p);
-        const dim3 grid((unsigned)((n + MT_ROWS - 1) / MT_ROWS), (unsigned)((M + MT_COLS - 1) / MT_COLS), on_grid);
-        auto launch = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, grid, dim3(MT_THREADS), 0, h->stream, n, M, n_chrom, ld, h->d_match_chroms.p,
-                               h->grid_dosage.p, h->match_panel.p, h->match_cross.p);
-        };
-        if (h->match_vec2) launch(match_cross_kernel<true>);
-        else launch(match_cross_kernel<false>);
-    }
-    GBRS_HIP_CHECK(hipEventRecord(h->ev[1], h->stream));
-    GBRS_HIP_CHECK(hipGetLastError());
-    GBRS_HIP_CHECK(hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, h->ev[0], h->ev[1]) == hipSuccess) h->t_match = ms;
-    if (cross) GBRS_HIP_CHECK(hipMemcpy(cross, h->match_cross.p, h->match_cross.bytes(), hipMemcpyDeviceToHost));
-    if (sample_norm) GBRS_HIP_CHECK(hipMemcpy(sample_norm, h->match_snorm.p, h->match_snorm.bytes(), hipMemcpyDeviceToHost));
-    return GBRS_OK;
-}
-
-int gbrs_hmm_match_info(gbrs_hmm_t *h, int *n_panel, double *panel_norm, double *last_ms, uint64_t *device_bytes) {
-    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
-    if (n_panel) *n_panel = h->n_panel;
-    if (panel_norm && !h->panel_norm.empty()) std::memcpy(panel_norm, h->panel_norm.data(), h->panel_norm.size() * sizeof(double));
-    if (last_ms) *last_ms = h->t_match;
-    if (device_bytes)
-        *device_bytes = h->match_panel.bytes() + h->match_cross.bytes() + h->match_snorm.bytes() + h->d_match_chroms.bytes();
-    return GBRS_OK;
-}
-
-int gbrs_hmm_set_snps(gbrs_hmm_t *h, const int32_t *n_pos, const double *const *gene_pos, const int32_t *n_snps,
-                      const double *const *snp_pos, const uint32_t *const *snp_mask) {
-    RoctxRange roctx_range("gbrs_hmm_set_snps");
-    if (!h || !n_pos || !gene_pos || !n_snps || !snp_pos || !snp_mask) return fail(GBRS_ERR_INVALID, "bad argument");
-    // everything is prepared and checked before the handle changes
-    std::vector<SnpChrom> sc(h->n_chrom);
-    std::vector<double> knot_x;
-    std::vector<int32_t> knot_gene, knot_row;
-    int64_t total = 0;
-    const uint32_t beyond = h->H >= 32 ? 0u : ~0u << h->H;
-    if (h->total_genes + 2 * (int64_t)h->n_chrom > INT32_MAX) return fail(GBRS_ERR_INVALID, "too many genes for SNP knots");
-    for (int c = 0; c < h->n_chrom; ++c) {
-        const ChromDesc &cd = h->chroms[c];
-        SnpChrom &s = sc[c];
-        s.gene_off = cd.gene_off;
-        s.knot_off = (int32_t)knot_x.size();
-        s.n_knots = 0;
-        s.snp_off = total;
-        if (n_snps[c] < 0) return fail(GBRS_ERR_INVALID, "n_snps[%d] is negative", c);
-        if (n_snps[c] == 0) continue;
-        if (!snp_pos[c] || !snp_mask[c]) return fail(GBRS_ERR_INVALID, "chromosome %d: SNP positions or patterns are NULL", c);
-        if (n_pos[c] == 0)
-            return fail(GBRS_ERR_INVALID, "index -1 is out of bounds for axis 1 with size 0 (SNP chromosome %d has no genes)", c);
-        if (n_pos[c] != cd.n_genes)
-            return fail(GBRS_ERR_INVALID, "chromosome %d: %d gene positions for %d genes", c, n_pos[c], cd.n_genes);
-        for (int32_t k = 0; k < n_snps[c]; ++k)
-            if (snp_mask[c][k] & beyond)
-                return fail(GBRS_ERR_INVALID, "chromosome %d, SNP %d: the pattern 0x%x names a founder at or above %d", c, k,
-                            snp_mask[c][k], h->H);
-        s.n_knots = cd.n_genes + 2;
-        knot_x.resize(knot_x.size() + s.n_knots);
-        knot_gene.resize(knot_x.size());
-        GBRS_TRY(gbrs_grid_knots(cd.n_genes, gene_pos[c], n_snps[c], snp_pos[c], knot_x.data() + s.knot_off,
-                                 knot_gene.data() + s.knot_off));
-        total += n_snps[c];
-    }
-    if (total == 0) {
-        h->d_snp_chroms.release();
-        h->snp_knot_x.release();
-        h->snp_knot_row.release();
-        h->snp_x.release();
-        h->snp_mask.release();
-        h->snp_idx.release();
-        h->snp_out.release();
-        h->n_snps = 0;
-        return GBRS_OK;
-    }
-    knot_row.resize(knot_gene.size());
-    for (int c = 0; c < h->n_chrom; ++c)
-        for (int32_t k = 0; k < sc[c].n_knots; ++k)
-            knot_row[sc[c].knot_off + k] = (int32_t)(sc[c].gene_off + knot_gene[sc[c].knot_off + k]);
-    GBRS_TRY(select_device(h->device));
-    DevBuf<SnpChrom> d_sc;
-    DevBuf<double> d_knot_x, d_x;
-    DevBuf<int32_t> d_knot_row, d_idx;
-    DevBuf<uint32_t> d_mask;
-    GBRS_TRY(d_sc.alloc(sc.size()));
-    GBRS_TRY(d_knot_x.alloc(knot_x.size()));
-    GBRS_TRY(d_knot_row.alloc(knot_row.size()));
-    GBRS_TRY(d_x.alloc((size_t)total));
-    GBRS_TRY(d_mask.alloc((size_t)total));
-    GBRS_TRY(d_idx.alloc((size_t)total));
-    GBRS_HIP_CHECK(hipMemcpy(d_sc.p, sc.data(), d_sc.bytes(), hipMemcpyHostToDevice));
-    GBRS_HIP_CHECK(hipMemcpy(d_knot_x.p, knot_x.data(), d_knot_x.bytes(), hipMemcpyHostToDevice));
-    GBRS_HIP_CHECK(hipMemcpy(d_knot_row.p, knot_row.data(), d_knot_row.bytes(), hipMemcpyHostToDevice));
-    for (int c = 0; c < h->n_chrom; ++c) {
-        if (n_snps[c] == 0) continue;
-        GBRS_HIP_CHECK(hipMemcpy(d_x.p + sc[c].snp_off, snp_pos[c], (size_t)n_snps[c] * sizeof(double), hipMemcpyHostToDevice));
-        GBRS_HIP_CHECK(hipMemcpy(d_mask.p + sc[c].snp_off, snp_mask[c], (size_t)n_snps[c] * sizeof(uint32_t),
-                                 hipMemcpyHostToDevice));
-    }
-    GBRS_HIP_CHECK(hipEventRecord(h->ev[0], h->stream));
-    hipLaunchKernelGGL(snp_setup_kernel, dim3((unsigned)((total + IMPUTE_THREADS - 1) / IMPUTE_THREADS)), dim3(IMPUTE_THREADS), 0,
-                       h->stream, h->n_chrom, total, d_sc.p, d_knot_x.p, d_x.p, d_idx.p);
-    GBRS_HIP_CHECK(hipEventRecord(h->ev[1], h->stream));
-    GBRS_HIP_CHECK(hipGetLastError());
-    GBRS_HIP_CHECK(hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    h->t_snp_setup = hipEventElapsedTime(&ms, h->ev[0], h->ev[1]) == hipSuccess ? ms : 0.0;
-    h->d_snp_chroms.swap(d_sc);
-    h->snp_knot_x.swap(d_knot_x);
-    h->snp_knot_row.swap(d_knot_row);
-    h->snp_x.swap(d_x);
-    h->snp_mask.swap(d_mask);
-    h->snp_idx.swap(d_idx);
-    h->n_snps = total;
-    return GBRS_OK;
-}
-
-int gbrs_hmm_impute(gbrs_hmm_t *h, int sample, int64_t first, int64_t count, double *out) {
-    RoctxRange roctx_range("gbrs_hmm_impute");
-    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
-    if (!h->ran) return fail(GBRS_ERR_STATE, "run() has not been called");
-    if (h->n_snps == 0) return fail(GBRS_ERR_INVALID, "no SNPs on the handle: call gbrs_hmm_set_snps first");
-    if (sample < -1 || sample >= h->n_samples) return fail(GBRS_ERR_INVALID, "sample out of range");
-    if (first < 0 || count < 0 || first > h->n_snps || count > h->n_snps - first)
-        return fail(GBRS_ERR_INVALID, "SNPs %lld .. %lld are outside 0 .. %lld", (long long)first, (long long)first + count,
-                    (long long)h->n_snps);
-    if (count == 0) return GBRS_OK;
-    if (!out) return fail(GBRS_ERR_INVALID, "out is NULL");
-    GBRS_TRY(select_device(h->device));
-    const int S = h->S, H = h->H;
-    const int n = sample < 0 ? h->n_samples : 1;
-    const size_t n_out = (size_t)n * count;
-    if (h->snp_out.n < n_out) GBRS_TRY(h->snp_out.alloc(n_out));
-    const bool make_d = !(h->snp_d_ready && h->snp_d_sample == sample);
-    GBRS_HIP_CHECK(hipEventRecord(h->ev[0], h->stream));
-    if (make_d) {
-        const int64_t rows = (int64_t)n * h->total_genes;
-        h->snp_d_ready = false;
-        if (h->snp_d.n != (size_t)rows * H) GBRS_TRY(h->snp_d.alloc((size_t)rows * H));
-        hipLaunchKernelGGL(dosage_kernel, dim3((unsigned)((rows * H + 255) / 256)), dim3(256), 0, h->stream, H, S, rows,
-                           h->gamma.p + (int64_t)std::max(sample, 0) * h->total_genes * S, h->snp_d.p);
-    }
-    GBRS_HIP_CHECK(hipEventRecord(h->ev[1], h->stream));
-    const dim3 grid((unsigned)((count + IMPUTE_THREADS - 1) / IMPUTE_THREADS), (unsigned)((n + IMPUTE_SAMPLES - 1) / IMPUTE_SAMPLES));
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, grid, dim3(IMPUTE_THREADS), 0, h->stream, H, n, h->total_genes, first, count, h->snp_knot_x.p,
-                           h->snp_knot_row.p, h->snp_x.p, h->snp_mask.p, h->snp_idx.p, h->snp_d.p, h->snp_out.p);
-    };
-    if (H == 8) launch(impute_kernel<true, 8>);
-    else if (H % 2 == 0) launch(impute_kernel<true, 0>);
-    else launch(impute_kernel<false, 0>);
-    GBRS_HIP_CHECK(hipEventRecord(h->ev[2], h->stream));
-    GBRS_HIP_CHECK(hipGetLastError());
-    GBRS_HIP_CHECK(hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    h->t_snp_d = make_d && hipEventElapsedTime(&ms, h->ev[0], h->ev[1]) == hipSuccess ? ms : 0.0;
-    h->t_snp_kernel = hipEventElapsedTime(&ms, h->ev[1], h->ev[2]) == hipSuccess ? ms : 0.0;
-    h->snp_d_ready = true;
-    h->snp_d_sample = sample;
-    GBRS_HIP_CHECK(hipMemcpy(out, h->snp_out.p, n_out * sizeof(double), hipMemcpyDeviceToHost));
-    return GBRS_OK;
-}
-
-int gbrs_hmm_impute_info(gbrs_hmm_t *h, int64_t *n_snps, double *last_ms, uint64_t *device_bytes) {
-    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
-    if (n_snps) *n_snps = h->n_snps;
-    if (last_ms) *last_ms = h->t_snp_d + h->t_snp_kernel;
-    if (device_bytes)
-        *device_bytes = h->d_snp_chroms.bytes() + h->snp_knot_x.bytes() + h->snp_knot_row.bytes() + h->snp_x.bytes() +
-                        h->snp_mask.bytes() + h->snp_idx.bytes() + h->snp_d.bytes() + h->snp_out.bytes();
-    return GBRS_OK;
-}
-
-int gbrs_hmm_impute_times(gbrs_hmm_t *h, double *setup_ms, double *dosage_ms, double *kernel_ms) {
-    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
-    if (setup_ms) *setup_ms = h->t_snp_setup;
-    if (dosage_ms) *dosage_ms = h->t_snp_d;
-    if (kernel_ms) *kernel_ms = h->t_snp_kernel;
-    return GBRS_OK;
-}
-
-int gbrs_hmm_sample_paths(gbrs_hmm_t *h, int sample, int n_draws, uint64_t seed, const uint32_t *streams, uint8_t *paths,
-                          int32_t *changes, uint64_t *degenerate) {
-    RoctxRange roctx_range("gbrs_hmm_sample_paths");
-    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
-    if (!h->ran) return fail(GBRS_ERR_STATE, "run() has not been called");
-    if (n_draws < 1) return fail(GBRS_ERR_INVALID, "n_draws must be at least 1");
-    if (sample < -1 || sample >= h->n_samples) return fail(GBRS_ERR_INVALID, "sample out of range");
-    if (!paths) return fail(GBRS_ERR_INVALID, "paths is NULL");
-    GBRS_TRY(select_device(h->device));
-    GBRS_TRY(hmm_make_logs(h));
-    const int S = h->S, n = sample < 0 ? h->n_samples : 1, sample0 = std::max(sample, 0);
-    const size_t G = (size_t)h->total_genes;
-    // draws per slab: two byte images of n x slab x G (gene-major as drawn, draw-major as returned) within 1 GiB, whole
-    // workgroups of draws where that many fit; GBRS_TUNING_SAMPLE_SLAB names a count instead.  The draws are keyed by their
-    // number, so the cut changes no value.
-    size_t slab = std::max<size_t>(((size_t)1 << 30) / (2 * (size_t)n * G), 1);
-    if (slab >= SAMPLE_BLOCK) slab -= slab % SAMPLE_BLOCK;
-    if (const char *e = std::getenv("GBRS_TUNING_SAMPLE_SLAB"); e && std::atoi(e) > 0) slab = (size_t)std::atoi(e);
-    slab = std::min<size_t>(slab, (size_t)n_draws);
-    if (!h->smp_change_tab.p) {
-        const std::vector<uint8_t> tab = sample_change_table(h->H);
-        GBRS_TRY(h->smp_change_tab.alloc(tab.size()));
-        GBRS_HIP_CHECK(hipMemcpy(h->smp_change_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice));
-    }
-    if (h->smp_cols.n < (size_t)n * slab * G) GBRS_TRY(h->smp_cols.alloc((size_t)n * slab * G));
-    if (h->smp_paths.n < (size_t)n * slab * G) GBRS_TRY(h->smp_paths.alloc((size_t)n * slab * G));
-    if (changes && h->smp_changes.n < (size_t)n * slab * h->n_chrom) GBRS_TRY(h->smp_changes.alloc((size_t)n * slab * h->n_chrom));
-    if (h->smp_streams.n < (size_t)n) GBRS_TRY(h->smp_streams.alloc((size_t)n));
-    if (!h->smp_degenerate.p) GBRS_TRY(h->smp_degenerate.alloc(1));
-    std::vector<uint32_t> ids((size_t)n);
-    for (int k = 0; k < n; ++k) ids[k] = streams ? streams[k] : (uint32_t)(sample0 + k);
-    GBRS_HIP_CHECK(hipMemcpy(h->smp_streams.p, ids.data(), ids.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    GBRS_HIP_CHECK(hipMemsetAsync(h->smp_degenerate.p, 0, sizeof(unsigned long long), h->stream));
-    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-    const size_t lds = sample_lds(S);
-    h->t_sample = 0;
-    for (size_t d0 = 0; d0 < (size_t)n_draws; d0 += slab) {
-        const int ks = (int)std::min<size_t>(slab, (size_t)n_draws - d0);
-        const dim3 grid((unsigned)((ks + SAMPLE_BLOCK - 1) / SAMPLE_BLOCK), (unsigned)h->n_chrom, (unsigned)n);
-        auto launch = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, grid, dim3(SAMPLE_BLOCK), lds, h->stream, S, h->n_chrom, h->total_genes, sample0,
-                               (uint32_t)d0, ks, h->d_chroms.p, h->d_order.p, h->alpha.p, h->tprob.p, h->smp_change_tab.p,
-                               h->smp_streams.p, k0, k1, h->smp_cols.p, changes ? h->smp_changes.p : nullptr,
-                               h->smp_degenerate.p);
-        };
-        GBRS_HIP_CHECK(hipEventRecord(h->ev[0], h->stream));
-        if (sample_table_in_lds(S)) launch(sample_paths_kernel<true>);
-        else launch(sample_paths_kernel<false>);
-        hipLaunchKernelGGL(sample_transpose_kernel, dim3((unsigned)((G + 63) / 64), (unsigned)((ks + 63) / 64), (unsigned)n),
-                           dim3(256), 0, h->stream, h->total_genes, ks, h->smp_cols.p, h->smp_paths.p);
-        GBRS_HIP_CHECK(hipEventRecord(h->ev[1], h->stream));
-        GBRS_HIP_CHECK(hipGetLastError());
-        GBRS_HIP_CHECK(hipStreamSynchronize(h->stream));
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, h->ev[0], h->ev[1]) == hipSuccess) h->t_sample += ms;
-        for (int k = 0; k < n; ++k) {       // a sample's draws of this slab are contiguous on both sides
-            GBRS_HIP_CHECK(hipMemcpy(paths + ((size_t)k * n_draws + d0) * G, h->smp_paths.p + (size_t)k * ks * G,
-                                     (size_t)ks * G, hipMemcpyDeviceToHost));
-            if (changes)
-                GBRS_HIP_CHECK(hipMemcpy(changes + ((size_t)k * n_draws + d0) * h->n_chrom,
-                                         h->smp_changes.p + (size_t)k * ks * h->n_chrom,
-                                         (size_t)ks * h->n_chrom * sizeof(int32_t), hipMemcpyDeviceToHost));
-        }
-    }
-    if (degenerate) {
-        unsigned long long count = 0;
-        GBRS_HIP_CHECK(hipMemcpy(&count, h->smp_degenerate.p, sizeof(count), hipMemcpyDeviceToHost));
-        *degenerate = count;
-    }
-    return GBRS_OK;
-}
-
-int gbrs_hmm_sample_info(gbrs_hmm_t *h, double *last_ms, uint64_t *device_bytes) {
-    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
-    if (last_ms) *last_ms = h->t_sample;
-    if (device_bytes)
-        *device_bytes = h->smp_change_tab.bytes() + h->smp_cols.bytes() + h->smp_paths.bytes() + h->smp_changes.bytes() +
-                        h->smp_streams.bytes() + h->smp_degenerate.bytes();
-    return GBRS_OK;
-}
-
-namespace {
-
-// the founder-change table of the path draws serves the pair pass too
-int diag_change_table(gbrs_hmm *h) {
-    if (h->smp_change_tab.p) return GBRS_OK;
-    const std::vector<uint8_t> tab = sample_change_table(h->H);
-    GBRS_TRY(h->smp_change_tab.alloc(tab.size()));
-    GBRS_HIP_CHECK(hipMemcpy(h->smp_change_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice));
-    return GBRS_OK;
-}
-
-}  // namespace
-
-int gbrs_hmm_diagnostics(gbrs_hmm_t *h, int sample, double *xo, double *pswitch, double *errlod, double *maxprob,
-                         int32_t *maxmarg) {
-    RoctxRange roctx_range("gbrs_hmm_diagnostics");
-    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
-    if (!h->ran) return fail(GBRS_ERR_STATE, "run() has not been called");
-    if (sample < -1 || sample >= h->n_samples) return fail(GBRS_ERR_INVALID, "sample out of range");
-    GBRS_TRY(select_device(h->device));
-    const int S = h->S, n = sample < 0 ? h->n_samples : 1, sample0 = std::max(sample, 0);
-    const size_t G = (size_t)h->total_genes, cells = (size_t)n * G;
-    const bool pair = xo || pswitch, gene = errlod || maxprob || maxmarg;
-    h->t_diag = 0;
-    if (cells == 0 || !(pair || gene)) return GBRS_OK;
-    if (pair || errlod) GBRS_TRY(hmm_make_logs(h));
-    if (pair) GBRS_TRY(diag_change_table(h));
-    if (xo && h->diag_xo.n < cells) GBRS_TRY(h->diag_xo.alloc(cells));
-    if (pswitch && h->diag_pswitch.n < cells) GBRS_TRY(h->diag_pswitch.alloc(cells));
-    if (errlod && h->diag_errlod.n < cells) GBRS_TRY(h->diag_errlod.alloc(cells));
-    if (maxprob && h->diag_maxprob.n < cells) GBRS_TRY(h->diag_maxprob.alloc(cells));
-    if (maxmarg && h->diag_maxmarg.n < cells) GBRS_TRY(h->diag_maxmarg.alloc(cells));
-    GBRS_HIP_CHECK(hipEventRecord(h->ev[0], h->stream));
-    if (pair) {
-        // samples of one workgroup: it reads a table block once for all of them.  Four per wavefront keep the grid wide
-        // at cohort sizes; GBRS_TUNING_DIAG_SLAB names a count instead.  A value does not depend on the cut.
-        int slab = 4 * DIAG_WAVES;
-        if (const char *e = std::getenv("GBRS_TUNING_DIAG_SLAB"); e && std::atoi(e) > 0) slab = std::atoi(e);
-        slab = std::min(slab, n);
-        const dim3 grid((unsigned)((G + DIAG_RUN - 1) / DIAG_RUN), (unsigned)((n + slab - 1) / slab));
-        auto launch = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, grid, dim3(DIAG_BLOCK), diag_pair_lds(S), h->stream, S, h->n_chrom, h->total_genes,
-                               (int64_t)0, h->total_genes, sample0, n, slab, h->d_chroms.p, h->alpha.p, h->beta.p, h->eprob.p,
-                               h->tprob.p, h->smp_change_tab.p, xo ? h->diag_xo.p : nullptr,
-                               pswitch ? h->diag_pswitch.p : nullptr, (double *)nullptr);
-        };
-        if (diag_table_in_lds(S)) launch(diag_pair_kernel<true, false>);
-        else launch(diag_pair_kernel<false, false>);
-    }
-    if (gene) {
-        const int64_t rows = (int64_t)cells;
-        hipLaunchKernelGGL(diag_gene_kernel, dim3((unsigned)((rows + DIAG_WAVES - 1) / DIAG_WAVES)), dim3(DIAG_BLOCK), 0,
-                           h->stream, S, h->total_genes, sample0, rows, h->init_vec.p, h->alpha.p, h->beta.p, h->eprob.p,
-                           h->gamma.p, errlod ? h->diag_errlod.p : nullptr, maxprob ? h->diag_maxprob.p : nullptr,
-                           maxmarg ? h->diag_maxmarg.p : nullptr);
-    }
-    GBRS_HIP_CHECK(hipEventRecord(h->ev[1], h->stream));
-    GBRS_HIP_CHECK(hipGetLastError());
-    GBRS_HIP_CHECK(hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, h->ev[0], h->ev[1]) == hipSuccess) h->t_diag = ms;
-    if (xo) GBRS_HIP_CHECK(hipMemcpy(xo, h->diag_xo.p, cells * sizeof(double), hipMemcpyDeviceToHost));
-    if (pswitch) GBRS_HIP_CHECK(hipMemcpy(pswitch, h->diag_pswitch.p, cells * sizeof(double), hipMemcpyDeviceToHost));
-    if (errlod) GBRS_HIP_CHECK(hipMemcpy(errlod, h->diag_errlod.p, cells * sizeof(double), hipMemcpyDeviceToHost));
-    if (maxprob) GBRS_HIP_CHECK(hipMemcpy(maxprob, h->diag_maxprob.p, cells * sizeof(double), hipMemcpyDeviceToHost));
-    if (maxmarg) GBRS_HIP_CHECK(hipMemcpy(maxmarg, h->diag_maxmarg.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return GBRS_OK;
-}
-
-int gbrs_hmm_pair_posterior(gbrs_hmm_t *h, int sample, int chrom, double *xi) {
-    RoctxRange roctx_range("gbrs_hmm_pair_posterior");
-    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
-    if (!h->ran) return fail(GBRS_ERR_STATE, "run() has not been called");
-    if (sample < 0 || sample >= h->n_samples || chrom < 0 || chrom >= h->n_chrom)
-        return fail(GBRS_ERR_INVALID, "sample/chromosome out of range");
-    if (!xi) return fail(GBRS_ERR_INVALID, "xi is NULL");
-    const ChromDesc &cd = h->chroms[chrom];
-    if (cd.n_genes < 2) return GBRS_OK;                  // no interval
-    GBRS_TRY(select_device(h->device));
-    GBRS_TRY(hmm_make_logs(h));
-    GBRS_TRY(diag_change_table(h));
-    const int S = h->S;
-    const size_t cells = (size_t)(cd.n_genes - 1) * S * S;
-    if (h->diag_xi.n < cells) GBRS_TRY(h->diag_xi.alloc(cells));
-    const dim3 grid((unsigned)((cd.n_genes + DIAG_RUN - 1) / DIAG_RUN), 1u);
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, grid, dim3(DIAG_BLOCK), diag_pair_lds(S), h->stream, S, h->n_chrom, h->total_genes,
-                           cd.gene_off, cd.gene_off + cd.n_genes, sample, 1, 1, h->d_chroms.p, h->alpha.p, h->beta.p,
-                           h->eprob.p, h->tprob.p, h->smp_change_tab.p, (double *)nullptr, (double *)nullptr, h->diag_xi.p);
-    };
-    if (diag_table_in_lds(S)) launch(diag_pair_kernel<true, true>);
-    else launch(diag_pair_kernel<false, true>);
-    GBRS_HIP_CHECK(hipGetLastError());
-    GBRS_HIP_CHECK(hipStreamSynchronize(h->stream));
-    GBRS_HIP_CHECK(hipMemcpy(xi, h->diag_xi.p, cells * sizeof(double), hipMemcpyDeviceToHost));
-    return GBRS_OK;
-}
-
-int gbrs_hmm_diagnostics_info(gbrs_hmm_t *h, double *last_ms) {
-    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
-    if (last_ms) *last_ms = h->t_diag;
-    return GBRS_OK;
-}
-
-int gbrs_hmm_loglik(gbrs_hmm_t *h, int sample, double *loglik) {
-    RoctxRange roctx_range("gbrs_hmm_loglik");
-    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
-    if (!h->ran) return fail(GBRS_ERR_STATE, "run() has not been called");
-    if (sample < -1 || sample >= h->n_samples) return fail(GBRS_ERR_INVALID, "sample out of range");
-    if (!loglik) return fail(GBRS_ERR_INVALID, "loglik is NULL");
-    if (h->last.chain_interleaved) return fail(GBRS_ERR_UNSUPPORTED, "the last run left its rows as [gene][sample]");
-    GBRS_TRY(select_device(h->device));
-    const int n = sample < 0 ? h->n_samples : 1, sample0 = std::max(sample, 0);
-    const size_t cells = (size_t)n * h->n_chrom;
-    if (h->ll_out.n < cells) GBRS_TRY(h->ll_out.alloc(cells));
-    GBRS_HIP_CHECK(hipEventRecord(h->ev[0], h->stream));
-    hipLaunchKernelGGL(loglik_reduce_kernel, dim3((unsigned)((h->n_chrom + LL_RED_WAVES - 1) / LL_RED_WAVES), (unsigned)n),
-                       dim3(64 * LL_RED_WAVES), 0, h->stream, h->n_chrom, h->total_genes, sample0, h->d_chroms.p, h->invz.p,
-                       h->ll_out.p);
-    GBRS_HIP_CHECK(hipEventRecord(h->ev[1], h->stream));
-    GBRS_HIP_CHECK(hipGetLastError());
-    GBRS_HIP_CHECK(hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    h->t_loglik = hipEventElapsedTime(&ms, h->ev[0], h->ev[1]) == hipSuccess ? ms : 0.0;
-    GBRS_HIP_CHECK(hipMemcpy(loglik, h->ll_out.p, cells * sizeof(double), hipMemcpyDeviceToHost));
-    return GBRS_OK;
-}
-
-int gbrs_hmm_loglik_tables(gbrs_hmm_t *h, int chrom, int n_tables, const int32_t *n_trans, const double *const *tprob,
-                           int sample, double *loglik) {
-    RoctxRange roctx_range("gbrs_hmm_loglik_tables");
-    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
-    if (!h->ran) return fail(GBRS_ERR_STATE, "run() has not been called");
-    if (sample < -1 || sample >= h->n_samples || chrom < 0 || chrom >= h->n_chrom)
-        return fail(GBRS_ERR_INVALID, "sample/chromosome out of range");
-    if (n_tables < 1) return fail(GBRS_ERR_INVALID, "n_tables must be at least 1");
-    if (!n_trans || !tprob || !loglik) return fail(GBRS_ERR_INVALID, "NULL argument");
-    const ChromDesc &cd = h->chroms[chrom];
-    const int n_steps = cd.n_genes - 1;                    // only T[0 .. n_c - 2] are read
-    for (int k = 0; k < n_tables; ++k) {
-        if (n_trans[k] < n_steps)
-            return fail(GBRS_ERR_INVALID, "index %d is out of bounds for axis 0 with size %d (table %d)", n_steps - 1,
-                        n_trans[k], k);
-        if (n_steps > 0 && !tprob[k]) return fail(GBRS_ERR_INVALID, "tprob[%d] is NULL", k);
-    }
-    if (h->last.chain_interleaved) return fail(GBRS_ERR_UNSUPPORTED, "the last run left its rows as [gene][sample]");
-    GBRS_TRY(select_device(h->device));
-    const int S = h->S, n = sample < 0 ? h->n_samples : 1, sample0 = std::max(sample, 0);
-    const size_t per_table = (size_t)n_steps * S * S, cells = (size_t)n_tables * n;
-    if (h->ll_out.n < cells) GBRS_TRY(h->ll_out.alloc(cells));
-    if (per_table > 0) {
-        if (h->ll_t.n < per_table * n_tables) GBRS_TRY(h->ll_t.alloc(per_table * n_tables));
-        if (h->ll_pt.n < per_table * n_tables) GBRS_TRY(h->ll_pt.alloc(per_table * n_tables));
-        for (int k = 0; k < n_tables; ++k)
-            GBRS_HIP_CHECK(hipMemcpy(h->ll_t.p + per_table * k, tprob[k], per_table * sizeof(double), hipMemcpyHostToDevice));
-    }
-    GBRS_HIP_CHECK(hipEventRecord(h->ev[0], h->stream));
-    if (per_table > 0)          // P = exp(T) once per candidate table, for every sample of the call
-        hipLaunchKernelGGL(exp_blocks_t_kernel, dim3(2048), dim3(256), 0, h->stream, S, (int64_t)n_steps * n_tables, h->ll_t.p,
-                           h->ll_pt.p, S == 36);
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3((unsigned)cells), dim3(64), 0, h->stream, S, cd.n_genes, cd.gene_off, h->total_genes,
-                           sample0, n, (int)cells, h->ll_pt.p, h->peprob.p, h->init_vec.p, h->ll_out.p);
-    };
-    if (S <= 8) launch(loglik_tables_kernel<1, 8, 3>);
-    else if (S <= 16) launch(loglik_tables_kernel<1, 16, 3>);
-    else if (S == 36) launch(loglik_tables_kernel<1, 36, 4, 36>);   // 8 founders: the paired layout
-    else if (S < 36) launch(loglik_tables_kernel<1, 36, 3>);
-    else if (S <= 64) launch(loglik_tables_kernel<1, 64, 2>);
-    else launch(loglik_tables_kernel<3, 0, 1>);            // S <= 136 (MAX_H = 16)
-    GBRS_HIP_CHECK(hipEventRecord(h->ev[1], h->stream));
-    GBRS_HIP_CHECK(hipGetLastError());
-    GBRS_HIP_CHECK(hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    h->t_loglik = hipEventElapsedTime(&ms, h->ev[0], h->ev[1]) == hipSuccess ? ms : 0.0;
-    GBRS_HIP_CHECK(hipMemcpy(loglik, h->ll_out.p, cells * sizeof(double), hipMemcpyDeviceToHost));
-    return GBRS_OK;
-}
-
-int gbrs_hmm_loglik_info(gbrs_hmm_t *h, double *last_ms, uint64_t *device_bytes) {
-    if (!h) return fail(GBRS_ERR_INVALID, "handle is NULL");
-    if (last_ms) *last_ms = h->t_loglik;
-    if (device_bytes) *device_bytes = h->ll_out.bytes() + h->ll_t.bytes() + h->ll_pt.bytes();
-    return GBRS_OK;
-}
-
 int gbrs_hmm_destroy(gbrs_hmm_t *h) {
     if (!h) return GBRS_OK;
     (void)hipSetDevice(h->device);
@@ -4385,24 +3483,3 @@ namespace gbrs {
 __global__ void warm_hmm_kernel() {}
 void warm_hmm(hipStream_t st) { hipLaunchKernelGGL(warm_hmm_kernel, dim3(1), dim3(64), 0, st); }
 }  // namespace gbrs
-
-// The genome scan's read-only view of the grid dosages (scan_hmm.h).
-int gbrs::hmm_grid_view(gbrs_hmm *h, int sample, HmmGridView *view, bool make_dosage) {
-    if (!h) return fail(GBRS_ERR_INVALID, "hmm handle is NULL");
-    if (!h->ran) return fail(GBRS_ERR_STATE, "run() has not been called");
-    if (!h->have_grid) return fail(GBRS_ERR_INVALID, "no grid on the handle: call gbrs_hmm_set_grid first");
-    if (sample < -1 || sample >= h->n_samples) return fail(GBRS_ERR_INVALID, "sample out of range");
-    GBRS_TRY(select_device(h->device));
-    std::vector<GridChrom> gc(h->n_chrom);
-    GBRS_HIP_CHECK(hipMemcpy(gc.data(), h->d_grid_chroms.p, gc.size() * sizeof(GridChrom), hipMemcpyDeviceToHost));
-    if (make_dosage && h->grid_tiles > 0 && !(h->grid_dosage_ready && h->grid_dosage_sample == sample))
-        GBRS_TRY(hmm_grid_launch(h, sample, true, false));
-    view->device = h->device;
-    view->H = h->H;
-    view->n = sample < 0 ? h->n_samples : 1;
-    view->grid_points = h->grid_points;
-    view->points.resize(h->n_chrom);
-    for (int c = 0; c < h->n_chrom; ++c) view->points[c] = gc[c].n_points;
-    view->dosage = make_dosage ? h->grid_dosage.p : nullptr;
-    return GBRS_OK;
-}

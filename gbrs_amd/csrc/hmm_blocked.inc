@@ -19,16 +19,6 @@
 // forward step) is added by the chains as before; a boundary vector carries exact zeros where the sequential chain
 // would carry a denormal, which matters only for states of probability below 1e-320.
 
-struct BlockRange {
-    int64_t gene_off, trans_off;   // of the chromosome
-    int32_t lo, hi, n;             // genes [lo, hi) of a chromosome of n genes
-    int32_t chrom;
-    int32_t direct;                // 1: chained directly from the chromosome's own start (forward structure: its first block) /
-                                   // end (backward structure: its last block) while the other blocks' operators are built:
-                                   // it has no operator, and the combine takes its boundary vector from what the chain stored
-    int64_t bp_off;                // of the chromosome's backpointer rows
-};
-
 constexpr int BS_S = 36;
 #ifndef HMM_COMBINE_SETS
 #define HMM_COMBINE_SETS 2        // operators in flight in combine_sumprod_kernel (measured 2 / 3 / 4: 0.658 / 0.656 / 0.663 ms per pass)

@@ -1,7 +1,7 @@
 // Diagnostics of the last run (gbrs_hmm_diagnostics, gbrs_hmm_pair_posterior; DESIGN.md §23): the pair posteriors of
 // neighbouring genes reduced to the expected founder changes and the switch probability of every interval, and per gene
 // the error LOD and the most likely diplotype.  Reads what hmm_make_logs leaves - alpha, beta ([sample][gene][S], logs) -
-// with eprob, gamma and the handle's log tables T[i][to][from] in their uploaded order.  Included by hmm.hip inside
+// with eprob, gamma and the handle's log tables T[i][to][from] in their uploaded order.  Included by hmm_passes.hip inside
 // namespace gbrs.
 //
 // Interval i -> i+1 of sample s on chromosome c (k the state at gene i, j at gene i+1):

@@ -1,17 +1,7 @@
 // Grid pass of the HMM handle (gbrs_hmm_set_grid / gbrs_hmm_grid; DESIGN.md §21): the posteriors that gbrs_hmm_run left
 // in HBM, interpolated onto the marker grid (`gbrs interpolate`, gbrs_utils.py:664-688) and reduced to founder dosages
-// (`gbrs export`, :888-927) for every (sample, chromosome) of the run in one launch.  Included by hmm.hip inside
+// (`gbrs export`, :888-927) for every (sample, chromosome) of the run in one launch.  Included by hmm_passes.hip inside
 // namespace gbrs.
-
-struct GridChrom {               // one per chromosome of the handle
-    int64_t gene_off;            // its first gene row within a sample's gamma
-    int32_t knot_off, n_knots;   // its knots in the handle's knot arrays; n_knots = 0: the chromosome is not on the grid
-    int32_t point_off, n_points; // its grid points among the grid points of the handle's chromosomes, handle order
-};
-
-struct GridTile {                // a run of at most P consecutive grid points of one chromosome: one wavefront's work
-    int32_t chrom, first;
-};
 
 // Grid points per tile: 64 where a tile of 64 rows of S | 1 doubles stays under 32 KB of LDS (S <= 63), else 32
 // (S = 136: 35 KB, four workgroups per CU).

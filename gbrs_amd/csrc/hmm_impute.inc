@@ -1,13 +1,7 @@
 // SNP imputation of the HMM handle (gbrs_hmm_set_snps / gbrs_hmm_impute; DESIGN.md §26): the expected number of
 // alternative alleles of every sample at every SNP, from the posteriors that gbrs_hmm_run left in HBM and the SNP's
 // founder allele pattern.  The SNPs of a chromosome are a grid (grid_knots.h); the pattern folds the founder axis away
-// before the interpolation, so no H-wide or S-wide value of a SNP reaches HBM.  Included by hmm.hip inside namespace gbrs.
-
-struct SnpChrom {                // one per chromosome of the handle
-    int64_t gene_off;            // its first gene row within a sample's gamma
-    int32_t knot_off, n_knots;   // its knots in the handle's SNP knot arrays; n_knots = 0: the chromosome has no SNP
-    int64_t snp_off;             // its first SNP among the handle's SNPs (handle order)
-};
+// before the interpolation, so no H-wide or S-wide value of a SNP reaches HBM.  Included by hmm_passes.hip inside namespace gbrs.
 
 constexpr int IMPUTE_THREADS = 256;
 

@@ -1,5 +1,5 @@
 // Data log-likelihood of the last run (gbrs_hmm_loglik) and of the run's emissions under other transition tables
-// (gbrs_hmm_loglik_tables); DESIGN.md §24.  Included by hmm.hip inside namespace gbrs.
+// (gbrs_hmm_loglik_tables); DESIGN.md §24.  Included by hmm_passes.hip inside namespace gbrs.
 //
 // With Z_i the normaliser of gene i in the scaled forward recursion documented above forward_viterbi_kernel,
 //   log P(data of a chromosome) = sum_i log Z_i.

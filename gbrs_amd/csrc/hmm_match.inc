@@ -1,16 +1,11 @@
 // Match pass of the HMM handle (gbrs_hmm_set_panel / gbrs_hmm_match; DESIGN.md §25): the grid dosages of a launch's samples
 // against the dosages of a panel of reference animals on the same grid, per chromosome
 //   cross[s][c][j] = sum over the grid points p of c and the founders h of a[s][p][h] * b[j][p][h]
-// and the two squared norms.  Included by hmm.hip inside namespace gbrs.
+// and the two squared norms.  Included by hmm_passes.hip inside namespace gbrs.
 //
 // Both operands are row-major with K contiguous: a sample's row is its `grid_dosage` block ([grid point][H], the
 // chromosomes in handle order), a panel entry's row has the same layout, so chromosome c is the columns
 // [point_off * H, (point_off + n_points) * H) of both and the product is A_c (n x K_c) * B_c^T (K_c x M).
-
-struct MatchChrom {              // one per chromosome ON the grid: a chromosome without grid points gets no tile
-    int64_t k_off, k_len;        // its columns within a row
-    int32_t chrom;               // its index on the handle
-};
 
 // A workgroup of four wavefronts owns a block of 64 samples x 64 panel entries of one chromosome and walks K_c in chunks
 // of MT_KC columns: the two 64 x MT_KC operand blocks go to LDS (rows MT_LD doubles apart), wavefront w multiplies the

@@ -1,6 +1,6 @@
 // Diplotype paths drawn from the joint posterior of the last run (gbrs_hmm_sample_paths; DESIGN.md §22): forward-filter /
 // backward-sample on the filtered forward values that hmm_make_logs leaves as `alpha` ([sample][gene][S], logs) and the
-// handle's log transition tables T[i][to][from] in their uploaded order.  Included by hmm.hip inside namespace gbrs.
+// handle's log transition tables T[i][to][from] in their uploaded order.  Included by hmm_passes.hip inside namespace gbrs.
 //
 // Draw d of sample s on chromosome c, genes i = n-1 .. 0:
 //   l_k = alpha[i][k]                            at the last gene,

@@ -1,4 +1,4 @@
-// What the genome scan (scan.hip) reads from an HMM handle (hmm.hip): the grid dosages of the last run, on the device.
+// What the genome scan (scan.hip) reads from an HMM handle (hmm_passes.hip): the grid dosages of the last run, on the device.
 #pragma once
 #include "common.h"
 

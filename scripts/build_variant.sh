@@ -8,7 +8,7 @@ NAME=$1; EXTRA=$2; UNITS=${3:-em em_layout}
 ROOT=$(cd "$(dirname "$0")/.." && pwd); C=$ROOT/gbrs_amd/csrc; B=$C/build/variant_$NAME; mkdir -p $B $ROOT/gbrs_amd/variants
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -ffp-contract=off -Wall"
 OBJS=""
-for f in common em em_layout hmm hmm_inputs hostio bamio bam matops tensor scan; do
+for f in common em em_layout hmm hmm_passes hmm_inputs hostio bamio bam matops tensor scan; do
   if [[ " $UNITS " == *" $f "* ]]; then /opt/rocm/bin/hipcc $FLAGS $EXTRA -c -o $B/$f.o $C/$f.hip & OBJS="$OBJS $B/$f.o"; else OBJS="$OBJS $C/build/$f.o"; fi
 done; wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -pthread -o $ROOT/gbrs_amd/variants/libgbrs_hip_$NAME.so $OBJS -ldl

@@ -39,12 +39,12 @@ def constant(filename, pattern):
 
 
 def test_65_is_one_past_every_partition():
-    """IMPUTE_SAMPLES (hmm_impute.inc), the pair pass's slab of 4 * DIAG_WAVES samples (hmm.hip, hmm_diag.inc) - the size
+    """IMPUTE_SAMPLES (hmm_impute.inc), the pair pass's slab of 4 * DIAG_WAVES samples (hmm_passes.hip, hmm_diag.inc) - the size
     of an MFMA group too - and MT_ROWS (hmm_match.inc, sixteen rows per wavefront), read from the sources."""
     impute = constant("hmm_impute.inc", r"^constexpr\s+int\s+IMPUTE_SAMPLES\s*=\s*(\d+)\s*;")
     block = constant("hmm_diag.inc", r"^constexpr\s+int\s+DIAG_BLOCK\s*=\s*(\d+)\s*;")
     assert constant("hmm_diag.inc", r"^constexpr\s+int\s+DIAG_WAVES\s*=\s*DIAG_BLOCK\s*/\s*(\d+)\s*;") == 64
-    slab = constant("hmm.hip", r"^\s*int\s+slab\s*=\s*(\d+)\s*\*\s*DIAG_WAVES\s*;") * (block // 64)
+    slab = constant("hmm_passes.hip", r"^\s*int\s+slab\s*=\s*(\d+)\s*\*\s*DIAG_WAVES\s*;") * (block // 64)
     rows = constant("hmm_match.inc", r"^constexpr\s+int\s+MT_ROWS\s*=\s*(\d+)\s*,")
     assert dict(IMPUTE_SAMPLES=impute, DIAG_SLAB=slab, MT_ROWS=rows) == cases.PARTITIONS
     sizes = (impute, slab, rows)

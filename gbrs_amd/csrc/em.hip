@@ -574,6 +574,17 @@ struct gbrs_em {
         DevBuf<double> cur[2][2], mean[2][2], m2[2][2], tot_mean[2][2], tot_m2[2][2];
     } stats;
 
+    // The gather-side M-step (em_step.h em_gather_mstep, em_gather_steps below): three A vectors in rotation (`acc` and
+    // these two), a second theta, second totals and block sums.  Made at the first call that takes the route.
+    struct Gather {
+        bool ready = false;
+        DevBuf<double> acc_b[2], theta_b, tot_prev_b, tot_new_b, msums_b;
+        int rot = 0;             // the A vector the next launch adds into; its several-slot rows are zero (clean)
+        bool clean = false;      // the A invariant holds and the totals of the loci without a slot are 0 in both sets
+        bool primed = false;     // theta of the loci without a slot is 0: an M-step has run since theta was last set
+        std::vector<const double *> wrote;   // last call: wrote[m], the vector that holds theta of its iteration m (0: at its start)
+    } gm;
+
     int red_blocks() const { return (int)std::min<uint64_t>(RED_BLOCKS, (L + RED_THREADS - 1) / RED_THREADS); }
 };
 
@@ -635,7 +646,7 @@ int em_check_float(gbrs_em *em, EmScalars &host) {
 // ---- one pass: what it launches (em_step.h), then one function per launch ---------------------------------------------------
 
 // The route of a pass of this kind over the handle as it stands.  Resolved once per API call, outside any loop over steps.
-EmStepRoute em_route(const gbrs_em *em, EmPass pass) {
+EmStepShape em_step_shape(const gbrs_em *em) {
     const TileLayout &tl = em->tl;
     EmStepShape s;
     s.tiled = em->layout == 1;
@@ -645,8 +656,9 @@ EmStepRoute em_route(const gbrs_em *em, EmPass pass) {
     s.persist_groups = em->plan.persist_groups;
     s.acc_handed_out = em->acc_external;
     s.no_fused_mstep = em->plan.no_fused_mstep;
-    return em_step_route(s, pass);
+    return s;
 }
+EmStepRoute em_route(const gbrs_em *em, EmPass pass) { return em_step_route(em_step_shape(em), pass); }
 
 // Tiles -> partials (a locus with a single slot: straight into acc).
 template <int HT, bool ONES>
@@ -665,7 +677,7 @@ int em_launch_tiles_h(gbrs_em *em, const EmStepRoute &r) {
 #define GBRS_LAUNCH_TILES(W, D)                                                                                            \
     hipLaunchKernelGGL((tile_estep_kernel<HT, W, ONES, D>), grid, block, 0, em->stream, tH, tl.tiles.p, tl.words.p,        \
                        tl.dict.p, ww, em->theta.p, tl.partials.p, tl.slot_dest.p, em->acc.p, em->scalars.p,               \
-                       (uint32_t)tl.n_tiles, ea, sets, lead_mask)
+                       (uint32_t)tl.n_tiles, ea, sets, lead_mask, GatherArgs{})
     switch (r.estep) {
         case EmEstep::Persistent:
         case EmEstep::PersistentOneWord: {
@@ -691,7 +703,7 @@ int em_launch_tiles_h(gbrs_em *em, const EmStepRoute &r) {
             // no row of the layout has more than one word (single-locus reads, or locus sets): no row sums at all
             hipLaunchKernelGGL((tile_estep_kernel<HT == 8 ? 8 : 1, false, ONES, false, HT == 8>), grid, block, 0, em->stream, tH,
                                tl.tiles.p, tl.words.p, tl.dict.p, ww, em->theta.p, tl.partials.p, tl.slot_dest.p, em->acc.p,
-                               em->scalars.p, (uint32_t)tl.n_tiles, ea, sets, lead_mask);
+                               em->scalars.p, (uint32_t)tl.n_tiles, ea, sets, lead_mask, GatherArgs{});
             break;
 #endif
         default:
@@ -846,11 +858,11 @@ int em_launch_mstep_gather(gbrs_em *em, const EmStepRoute &r) {
 }
 
 template <int MODE, int H>
-void em_launch_mstep_elem(gbrs_em *em, const double *extra, const double *len) {
+void em_launch_mstep_elem(gbrs_em *em, double *theta, const double *acc, const double *extra, const double *len) {
     const uint64_t npair = (uint64_t)em->L * MstepRow<H>::LANES;
     const unsigned nb = (unsigned)((npair + RED_THREADS - 1) / RED_THREADS);
     em->msum_blocks = nb;
-    hipLaunchKernelGGL((mstep_elem_kernel<MODE, H>), dim3(nb), dim3(RED_THREADS), 0, em->stream, em->L, em->theta.p, em->acc.p,
+    hipLaunchKernelGGL((mstep_elem_kernel<MODE, H>), dim3(nb), dim3(RED_THREADS), 0, em->stream, em->L, theta, acc,
                        extra, len, em->counts.p, em->tot_prev.p, em->tot_new.p, em->msums.p, em->msum_cap, em->scalars.p);
 }
 // M-step launch: with the gather, element-parallel (H a power of two) or thread-per-locus.  MODE 1: prepare.
@@ -867,12 +879,12 @@ int em_launch_mstep_plain(gbrs_em *em, const EmStepRoute &r) {
     }
     const double *extra = r.mstep_adds_extra ? em->tl.acc_extra.p : (const double *)nullptr;
     switch (em->H) {
-    case 1: em_launch_mstep_elem<MODE, 1>(em, extra, len); break;
-    case 2: em_launch_mstep_elem<MODE, 2>(em, extra, len); break;
-    case 4: em_launch_mstep_elem<MODE, 4>(em, extra, len); break;
-    case 8: em_launch_mstep_elem<MODE, 8>(em, extra, len); break;
-    case 16: em_launch_mstep_elem<MODE, 16>(em, extra, len); break;
-    case 32: em_launch_mstep_elem<MODE, 32>(em, extra, len); break;
+    case 1: em_launch_mstep_elem<MODE, 1>(em, em->theta.p, em->acc.p, extra, len); break;
+    case 2: em_launch_mstep_elem<MODE, 2>(em, em->theta.p, em->acc.p, extra, len); break;
+    case 4: em_launch_mstep_elem<MODE, 4>(em, em->theta.p, em->acc.p, extra, len); break;
+    case 8: em_launch_mstep_elem<MODE, 8>(em, em->theta.p, em->acc.p, extra, len); break;
+    case 16: em_launch_mstep_elem<MODE, 16>(em, em->theta.p, em->acc.p, extra, len); break;
+    case 32: em_launch_mstep_elem<MODE, 32>(em, em->theta.p, em->acc.p, extra, len); break;
     default: return fail(GBRS_ERR_UNSUPPORTED, "the element-parallel M-step has no instance for this haplotype count");
     }
     return GBRS_OK;
@@ -907,6 +919,8 @@ int em_finish_step(gbrs_em *em, const EmStepRoute &r, double target_err, bool de
     GBRS_TRY(em_flush_err(em));
     GBRS_TRY(em_launch_mstep(em, r));
     em->counts_stale = r.counts_stale;
+    em->gm.primed = true;        // theta * A: 0 wherever the tiles have no slot
+    em->gm.clean = false;        // (acc and the totals are this route's again)
     if (defer_err && r.err_defer) {
         em->err_pending = true;
         em->err_pending_target = target_err;
@@ -960,6 +974,165 @@ void em_read_times(gbrs_em *em, int n) {
     em->last_step_ms = ss / n;
 }
 
+// ---- the gather-side M-step: iteration n's M-step in launch n + 1's prologues (em_step.h, em_layout.h GatherArgs) -------
+
+// Do this handle's Model-4 steps take the route, as it stands?
+bool em_gather_route(const gbrs_em *em) {
+    if (em->layout != 1 || em->N == 0) return false;
+    const TileLayout &tl = em->tl;
+    const EmStepShape s = em_step_shape(em);
+    EmGatherShape g;
+    g.no_heavy = tl.n_heavy == 0;
+    g.n_tiles = (uint32_t)tl.n_tiles; g.tile_waves = TILE_WAVES; g.msum_cap = em->msum_cap;
+    g.posterior = (em->flags & GBRS_EM_POSTERIOR) != 0;
+    g.resample = em->resample;
+    g.pair_mode = em->pair_ev_mstep != nullptr;
+    EmTuning t;
+    t.no_gather_mstep = em->plan.no_gather_mstep;
+    return em_gather_mstep(s, g, EmPass::Step, t);
+}
+
+int em_gather_setup(gbrs_em *em) {
+    gbrs_em::Gather &gm = em->gm;
+    const size_t LH = (size_t)em->L * em->H;
+    if (!gm.ready) {
+        GBRS_TRY(build_gather_slots(em->tl, em->plan.tL, em->stream));
+        for (DevBuf<double> *b : {&gm.acc_b[0], &gm.acc_b[1], &gm.theta_b}) {
+            GBRS_TRY(b->alloc(LH));
+            GBRS_HIP_CHECK(hipMemsetAsync(b->p, 0, b->bytes(), em->stream));      // (theta_b: the loci without a slot stay 0)
+        }
+        GBRS_TRY(gm.tot_prev_b.alloc(em->L));
+        GBRS_TRY(gm.tot_new_b.alloc(em->L));
+        GBRS_TRY(gm.msums_b.alloc(em->msums.n));
+        GBRS_HIP_CHECK(hipMemsetAsync(gm.msums_b.p, 0, gm.msums_b.bytes(), em->stream));
+        gm.ready = true;
+        gm.clean = false;
+    }
+    if (!gm.clean) {
+        // another route has used acc and the totals since (or a stop left a launch half done): the several-slot rows of all
+        // three A vectors are zero again, the rotation starts over, and the totals of the loci without a slot are 0
+        for (double *p : {em->acc.p, gm.acc_b[0].p, gm.acc_b[1].p}) GBRS_HIP_CHECK(hipMemsetAsync(p, 0, LH * sizeof(double), em->stream));
+        for (double *p : {em->tot_prev.p, em->tot_new.p, gm.tot_prev_b.p, gm.tot_new_b.p})
+            GBRS_HIP_CHECK(hipMemsetAsync(p, 0, (size_t)em->L * sizeof(double), em->stream));
+        gm.rot = 0;
+        gm.clean = true;
+    }
+    return GBRS_OK;
+}
+
+template <int HT>
+void em_launch_gather_tiles(gbrs_em *em, bool one_word, const double *theta, const ErrArgs &ea, const GatherArgs &ga) {
+    const TileLayout &tl = em->tl;
+    const dim3 grid((unsigned)tl.n_tiles + ea.n_err_blocks), block(TILE_THREADS);
+    const SetArgs sets{em->plan.tL, tl.n_sets ? tl.set_ptr.p : nullptr, tl.set_members.p, tl.dest_list.p, tl.dict_b.p, tl.dest_b.p, 0u};
+#define GBRS_LAUNCH_GATHER(OW)                                                                                             \
+    hipLaunchKernelGGL((tile_estep_kernel<HT, false, false, false, OW, true>), grid, block, 0, em->stream, em->plan.tH,    \
+                       tl.tiles.p, tl.words.p, tl.dict.p, (const double *)nullptr, theta, (double *)nullptr, tl.slot_dest.p, \
+                       (double *)nullptr, em->scalars.p, (uint32_t)tl.n_tiles, ea, sets, em->plan.lead_mask, ga)
+    if constexpr (HT == 8) {
+        if (one_word) { GBRS_LAUNCH_GATHER(true); return; }
+    }
+    GBRS_LAUNCH_GATHER(false);
+#undef GBRS_LAUNCH_GATHER
+}
+
+// k iterations (k >= 1) on the route: k launches - the first with theta current, every later one applying the M-step of
+// the one before - then the error pass of iteration k - 1, one elementwise M-step on the last A vector and its error pass.
+// It leaves the handle as k two-launch steps do: theta current (in em->theta), counts fresh.  ev / stride / timed: as in
+// gbrs_em_step (launch 1 + i * stride is timed).  A stop inside the call: em_gather_settle.
+int em_gather_steps(gbrs_em *em, int k, double target_err, int stride, int timed) {
+    GBRS_TRY(em_flush_err(em));
+    GBRS_TRY(em_gather_setup(em));
+    gbrs_em::Gather &gm = em->gm;
+    const TileLayout &tl = em->tl;
+    const EmStepRoute route = em_route(em, EmPass::Step);
+    const bool one_word = route.estep == EmEstep::TilesOneWord;
+    double *accs[3] = {em->acc.p, gm.acc_b[0].p, gm.acc_b[1].p};
+    double *thetas[2] = {em->theta.p, gm.theta_b.p};
+    double *tps[2] = {em->tot_prev.p, gm.tot_prev_b.p}, *tns[2] = {em->tot_new.p, gm.tot_new_b.p}, *mss[2] = {em->msums.p, gm.msums_b.p};
+    gm.wrote.assign((size_t)k + 1, nullptr);
+    gm.wrote[0] = em->theta.p;
+    ErrArgs waiting = em_err_args(em, target_err);     // the error pass of the last M-step a launch applied
+    waiting.nblocks = (int)(tl.n_tiles * TILE_WAVES);
+    const uint32_t n_err = waiting.n_err_blocks;
+    bool have_waiting = false;
+    int src = 0;
+    if (!em->time_steps) timed = 0;
+    for (int j = 1; j <= k; ++j) {
+        const bool pending = j > 1;
+        const int set = j & 1, dst = src ^ 1;
+        GatherArgs ga;
+        ga.acc_old = accs[(gm.rot + 2) % 3];
+        ga.eff_len = em->has_len ? em->eff_len.p : nullptr;
+        ga.theta_new = thetas[dst];
+        ga.tot_prev = tps[set]; ga.tot_new = tns[set]; ga.msums = mss[set]; ga.cap = em->msum_cap;
+        ga.acc_cur = accs[gm.rot]; ga.acc_next = accs[(gm.rot + 1) % 3];
+        ga.gdest = tl.gdest.p; ga.gdest_b = tl.gdest_b.p; ga.gdest_list = tl.gdest_list.p;
+        ga.pending = pending ? 1u : 0u;
+        ErrArgs ea = waiting;
+        ea.n_err_blocks = have_waiting ? n_err : 0u;
+        const int slot = (j - 1) / stride;
+        hipEvent_t *ev = ((j - 1) % stride == 0 && slot < timed) ? &em->ev_pool[3 * slot] : nullptr;
+        if (ev) GBRS_HIP_CHECK(hipEventRecord(ev[0], em->stream));
+        switch (em->H) {
+        case 1: em_launch_gather_tiles<1>(em, one_word, thetas[src], ea, ga); break;
+        case 2: em_launch_gather_tiles<2>(em, one_word, thetas[src], ea, ga); break;
+        case 4: em_launch_gather_tiles<4>(em, one_word, thetas[src], ea, ga); break;
+        case 8: em_launch_gather_tiles<8>(em, one_word, thetas[src], ea, ga); break;
+        default: return fail(GBRS_ERR_UNSUPPORTED, "the gather-side M-step has no instance for this haplotype count");
+        }
+        if (ev) {
+            GBRS_HIP_CHECK(hipEventRecord(ev[1], em->stream));
+            GBRS_HIP_CHECK(hipEventRecord(ev[2], em->stream));
+        }
+        if (pending) {
+            gm.wrote[j - 1] = thetas[dst];
+            waiting.tot_prev = tps[set]; waiting.tot_new = tns[set]; waiting.partials = mss[set];
+            have_waiting = true;
+            src = dst;
+        }
+        gm.rot = (gm.rot + 1) % 3;
+    }
+    GBRS_HIP_CHECK(hipGetLastError());
+    if (have_waiting) {
+        waiting.n_err_blocks = n_err;
+        hipLaunchKernelGGL(err_finish_kernel, dim3(n_err), dim3(RED_THREADS), 0, em->stream, waiting);
+    }
+    // M(k), in place on the vector that holds theta of iteration k - 1, from the A vector the last launch added into
+    {
+        double *theta = thetas[src];
+        const double *acc = accs[(gm.rot + 2) % 3], *len = em->has_len ? em->eff_len.p : nullptr;
+        switch (em->H) {
+        case 1: em_launch_mstep_elem<0, 1>(em, theta, acc, nullptr, len); break;
+        case 2: em_launch_mstep_elem<0, 2>(em, theta, acc, nullptr, len); break;
+        case 4: em_launch_mstep_elem<0, 4>(em, theta, acc, nullptr, len); break;
+        default: em_launch_mstep_elem<0, 8>(em, theta, acc, nullptr, len); break;      // (1, 2, 4, 8: checked at the launches above)
+        }
+    }
+    gm.wrote[k] = thetas[src];
+    if (src == 1) em->theta.swap(gm.theta_b);
+    em->counts_stale = false;
+    GBRS_TRY(em_launch_err(em, target_err));
+    GBRS_HIP_CHECK(hipGetLastError());
+    return GBRS_OK;
+}
+
+// After a batch of k gather-side iterations that began at iters_done = it0 and met the stopping rule at iteration `done`
+// (device scalars read, stream idle): the error pass of iteration m = done - it0 raised the flag while launch m + 2 was
+// running or before it, so theta of iteration m - stored by launch m + 1, or by the closing M-step when m = k - is intact
+// in its vector while the other one may hold a part of iteration m + 1.  That vector becomes em->theta (a swap, no copy).
+void em_gather_settle(gbrs_em *em, int it0, int done) {
+    gbrs_em::Gather &gm = em->gm;
+    const int k = (int)gm.wrote.size() - 1, m = done - it0;
+    // m = k: the call ran to its end and left theta current itself.  m = 0: the flag was up before the call began, every
+    // launch of it was a no-op, and theta is still in the vector the call started from (wrote[0]) - settled like any m < k,
+    // because the call's closing swap may have made the other vector current.
+    if (k < 1 || m < 0 || m >= k) return;
+    if (gm.wrote[m] != em->theta.p) em->theta.swap(gm.theta_b);
+    em->counts_stale = true;                       // the closing M-step stored nothing: counts are theta * len when asked for
+    gm.clean = false;                              // launch m + 2 may have added into and zeroed a part of its A vectors
+}
+
 int em_finish_prepare(gbrs_em *em, double pseudocount) {
     GBRS_TRY(em_launch_mstep(em, em_route(em, EmPass::Prepare)));
     em->counts_stale = false;
@@ -976,6 +1149,7 @@ int em_finish_prepare(gbrs_em *em, double pseudocount) {
     GBRS_HIP_CHECK(hipMemsetAsync(em->acc.p, 0, em->acc.bytes(), em->stream));
     GBRS_HIP_CHECK(hipGetLastError());
     em->prepared = true;
+    em->gm.primed = em->gm.clean = false;     // (the loci without reads carry theta again)
     return GBRS_OK;
 }
 
@@ -1498,6 +1672,27 @@ int gbrs_em_step(gbrs_em_t *em, int n_iters, double *err_sum_out) {
         em->ev_pool.push_back(e);
     }
     const EmStepRoute route = em_route(em, EmPass::Step);
+    if (em_gather_route(em) && n_iters > 0) {
+        // the gather-side M-step (em_gather_steps); the first M-step since theta was set runs on the route above, once: the
+        // loci without reads still carry theta there, and count in that iteration's totals
+        int left = n_iters;
+        if (!em->gm.primed) {
+            GBRS_TRY(em_one_step(em, route, 4, -1.0, left == 1 ? em->ev_pool.data() : nullptr, false));
+            --left;
+        }
+        const int gtimed = left == 0 ? 1 : std::min(timed, (left + stride - 1) / stride);
+        if (left > 0) GBRS_TRY(em_gather_steps(em, left, -1.0, stride, gtimed));
+        EmScalars host;
+        std::memset(&host, 0, sizeof(host));
+        const int float_rc = em_check_float(em, host);
+        // (only a NaN error sum stops a step asked for by hand, and a float error comes with it: the next call starts over
+        // on the plain route, from whatever theta the caller sets)
+        if (host.stop || float_rc != GBRS_OK) em->gm.clean = em->gm.primed = false;
+        GBRS_TRY(float_rc);
+        em_read_times(em, gtimed);
+        if (err_sum_out) *err_sum_out = host.err_sum;
+        return GBRS_OK;
+    }
     for (int i = 0; i < n_iters; ++i) {
         const int slot = i / stride;
         const bool t = i % stride == 0 && slot < timed;
@@ -1632,11 +1827,30 @@ int gbrs_em_run(gbrs_em_t *em, int model, double tol, int max_iters, int *n_iter
         const auto t_start = std::chrono::steady_clock::now();
         while (done < max_iters) {
             const int nb = std::min(batch, max_iters - done);
-            for (int i = 0; i < nb; ++i) {     // the run's first step is timed; a batch's last error pass is not deferred
+            // (the gather-side M-step, em_gather_steps: the first M-step since theta was set on the route above, once)
+            const bool gather = model == 4 && em_gather_route(em);
+            int left = nb;
+            if (gather && !em->gm.primed) {
+                GBRS_TRY(em_one_step(em, route, model, target, first ? em->ev_pool.data() : nullptr, false));
+                first = false;
+                --left;
+            }
+            const int gk = gather ? left : 0, g_it0 = done + (nb - left);
+            if (gk > 0) {
+                // (a stop raised by the step above turns every launch of this call into a no-op)
+                GBRS_TRY(em_gather_steps(em, gk, target, gk, first ? 1 : 0));
+                first = false;
+                left = 0;
+            }
+            for (int i = 0; i < left; ++i) {     // the run's first step is timed; a batch's last error pass is not deferred
                 GBRS_TRY(em_one_step(em, route, model, target, first ? em->ev_pool.data() : nullptr, i + 1 < nb));
                 first = false;
             }
-            GBRS_TRY(em_check_float(em, host));
+            // (a float error is reported after the handle is settled: a stop raised with it must not leave the half-written
+            // theta vector current)
+            const int float_rc = em_check_float(em, host);
+            if (gk > 0 && host.stop) em_gather_settle(em, g_it0, host.iters_done);
+            GBRS_TRY(float_rc);
             if (elapsed_s) {       // the host sees a batch at a time: its iterations share the batch's completion time
                 const double t = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
                 for (int i = done; i < host.iters_done && i < err_hist_cap; ++i) elapsed_s[i] = t;
@@ -1735,6 +1949,7 @@ int gbrs_em_set_theta(gbrs_em_t *em, const double *theta) {
                        em->scratch_hl.p, em->theta.p);
     GBRS_HIP_CHECK(hipStreamSynchronize(em->stream));
     em->prepared = true;
+    em->gm.primed = false;
     return GBRS_OK;
 }
 
@@ -1881,6 +2096,19 @@ int gbrs_em_info(gbrs_em_t *em, gbrs_em_info_t *info) {
                             8 * rows * em->plan.tH * 2 + (tl.weighted ? 8 * tl.n_batches * 64 : 0) +
                             (tl.n_sets ? 8 * tl.n_slots : 0);       // dict_b / dest_b beside the dictionary
         if (tl.n_sets) info->bytes_per_iter += 8 * tl.n_slots;
+        if (em_gather_route(em)) {
+            // the gather-side route, one launch per iteration: words, headers, dictionary + the (slot, member) words of
+            // prologue and epilogue, theta, A and length rows gathered per (slot, member), the sums added per (slot,
+            // member); per locus with a slot theta' and two totals stored and - several slots - a row zeroed; block sums.
+            // No slot rows, no M-step vectors.
+            const uint64_t tH = em->plan.tH;
+            const uint64_t with_slot = tl.n_dest_rows ? std::min<uint64_t>(rows, em->L) : std::min<uint64_t>(tl.n_slots, em->L);
+            info->estep_bytes = 4 * tl.n_batches * 64 + 16 * tl.n_tiles + 4 * tl.n_slots * 3 + 4 * rows * 2 +
+                                8 * rows * tH * ((em->has_len ? 3 : 2) + 1) + 8 * with_slot * tH + 16 * with_slot +
+                                8 * (tl.n_light) * tH + 16 * tl.n_tiles * TILE_WAVES +
+                                (tl.n_sets ? 8 * tl.n_slots : 0);
+            info->bytes_per_iter = info->estep_bytes;
+        }
     }
     info->last_estep_ms = em->last_estep_ms;
     info->last_step_ms = em->last_step_ms;
@@ -1903,6 +2131,12 @@ int gbrs_em_tile_cut(gbrs_em_t *em, uint32_t *passes, uint32_t *tile_words) {
     if (!em || !passes || !tile_words) return fail(GBRS_ERR_INVALID, "NULL argument");
     *passes = em->layout == 1 ? em->tl.cut_passes : 0;
     *tile_words = em->layout == 1 ? em->tl.cut_tile_words : 0;
+    return GBRS_OK;
+}
+
+int gbrs_em_gather_mstep(gbrs_em_t *em, uint32_t *taken) {
+    if (!em || !taken) return fail(GBRS_ERR_INVALID, "NULL argument");
+    *taken = em_gather_route(em) ? 1u : 0u;
     return GBRS_OK;
 }
 

@@ -138,6 +138,25 @@ struct SetArgs {
     uint32_t relax_zero_weight;      // resampling handle (GBRS_EM_RESAMPLE): a zero-weight row's zero denominator is no float error
 };
 
+// The gather-side M-step (em_tiles.inc, tile_estep_kernel<..., GATHER>): launch n's prologues apply iteration n-1's M-step
+// to the loci they gather anyway - theta' = theta * A / len made in registers on the way into LDS - and its epilogues add
+// their sums straight into an A vector.  Every locus with a slot has one OWNING (slot, member): the first in slot order.
+// The owner stores theta' and the locus's totals, adds it to the tile's block sums, and zeroes the locus's row of the A vector
+// the NEXT launch adds into.  A locus with one (slot, member) is DIRECT: its sums are stored, not added, and its row is
+// never zeroed.
+constexpr uint32_t GSLOT_OWNER = 0x80000000u, GSLOT_DIRECT = 0x40000000u, GSLOT_LOCUS = 0x3FFFFFFFu;
+struct GatherArgs {
+    const double *acc_old;           // A of the iteration before (read beside theta)
+    const double *eff_len;           // nullable
+    double *theta_new;               // the other theta vector
+    double *tot_prev, *tot_new;      // the current totals
+    double *msums;                   // the current block sums: [2][cap], TILE_WAVES slots per tile
+    uint32_t cap;
+    double *acc_cur, *acc_next;      // A of this launch; the one the next launch adds into
+    const uint32_t *gdest, *gdest_b, *gdest_list;
+    uint32_t pending;                // 0: theta is current (the first launch of a call) - only the zeroing is stored
+};
+
 struct TileLayout {
     // sizes
     uint64_t n_pairs = 0;        // (row, locus) pairs = unpadded words
@@ -192,6 +211,10 @@ struct TileLayout {
     DevBuf<uint32_t> set_ptr, set_members;   // n_sets + 1 offsets; member loci of every set, ascending
     DevBuf<uint32_t> dest_list;              // per set slot: [n, dest_1 .. dest_n] at slot_dest[slot] & ~SLOT_SET
     DevBuf<uint32_t> dict_b, dest_b;         // n_slots: second member / second destination of the two-member sets
+    // Gather-side M-step (GatherArgs below, build_gather_slots): locus | GSLOT_* of every (slot, member), in the shapes of
+    // slot_dest, dest_b and dest_list (a set slot's list sits at the same offset, its header is the member count)
+    bool gather_slots = false;
+    DevBuf<uint32_t> gdest, gdest_b, gdest_list;
     // GBRS_EM_ONE_SHOT: the build temporaries stay allocated until the layout goes (common.h, DeferFrees): a
     // process that handles one sample and exits never pays for returning them.  Without the flag they are freed in
     // one pass when the build ends.
@@ -216,6 +239,9 @@ inline EmDictLimits dict_limits(bool weighted, int H) {
 // and haplotypes are plan.tL and plan.tH.  Returns GBRS_OK or a status with the message set.
 int build_tile_layout(TileLayout &out, uint64_t R, uint64_t N, const uint32_t *ent_row, const uint64_t *col_ptr,
                       const double *count, hipStream_t stream, const EmPlan &plan);
+// The per-(slot, member) words of the gather-side M-step (GatherArgs), from the finished layout: once per handle that takes
+// that route.  L: the layout's loci.
+int build_gather_slots(TileLayout &tl, uint32_t L, hipStream_t stream);
 // plan.view = 2 (round 4, 16 haplotypes): the layout is built over HALF-LOCI - locus l's haplotypes 0-7 are "locus" 2l,
 // its haplotypes 8-15 "locus" 2l + 1, plan.tL and plan.tH are 2 L and 8.  The locus-major vectors (theta, A, lengths:
 // element l * 16 + h) are element for element the half-locus view's (2l + h / 8) * 8 + h % 8, so nothing outside the layout

@@ -1930,6 +1930,68 @@ int heavy_light_lists(TileLayout &out, uint32_t L_in, hipStream_t s) {
 
 }  // namespace
 
+// 13. the gather-side M-step's words (em_layout.h, GatherArgs): the locus of every (slot, member) with its owner and
+// direct flags, beside slot_dest, dest_b and dest_list.  The owner of a locus is its first (slot, member) in slot order,
+// members in member order; a locus is direct when that is its only one.  On the host: once per handle, a few words per slot.
+int build_gather_slots(TileLayout &tl, uint32_t L, hipStream_t s) {
+    if (tl.gather_slots) return GBRS_OK;
+    const size_t NS = tl.n_slots;
+    const bool sets = tl.n_sets != 0;
+    std::vector<uint32_t> dict(NS), dict_b, sdest, set_ptr, members;
+    std::vector<uint32_t> gdest(std::max<size_t>(NS, 1), 0u), gdest_b, glist(std::max<size_t>(tl.dest_list.n, 1), 0u);
+    GBRS_HIP_CHECK(hipStreamSynchronize(s));
+    if (NS) GBRS_HIP_CHECK(hipMemcpy(dict.data(), tl.dict.p, NS * 4, hipMemcpyDeviceToHost));
+    if (sets && NS) {
+        dict_b.resize(NS); sdest.resize(NS); gdest_b.assign(NS, 0u);
+        set_ptr.resize((size_t)tl.n_sets + 1); members.resize(tl.set_members.n);
+        GBRS_HIP_CHECK(hipMemcpy(dict_b.data(), tl.dict_b.p, NS * 4, hipMemcpyDeviceToHost));
+        GBRS_HIP_CHECK(hipMemcpy(sdest.data(), tl.slot_dest.p, NS * 4, hipMemcpyDeviceToHost));
+        GBRS_HIP_CHECK(hipMemcpy(set_ptr.data(), tl.set_ptr.p, set_ptr.size() * 4, hipMemcpyDeviceToHost));
+        if (!members.empty()) GBRS_HIP_CHECK(hipMemcpy(members.data(), tl.set_members.p, members.size() * 4, hipMemcpyDeviceToHost));
+    }
+    // every (slot, member) in order: fn(locus, where its word goes)
+    auto walk = [&](auto &&fn) -> int {
+        for (size_t p = 0; p < NS; ++p) {
+            const uint32_t e = dict[p];
+            if (!sets || !(e & (DICT_PAIR | DICT_SET))) {
+                if (e >= L) return fail(GBRS_ERR_STATE, "a dictionary entry is no locus");
+                fn(e, gdest[p]);
+            } else if (e & DICT_PAIR) {
+                const uint32_t a = e & ~DICT_PAIR, b2 = dict_b[p];
+                if (a >= L || b2 >= L) return fail(GBRS_ERR_STATE, "a two-member set's entry is no locus");
+                fn(a, gdest[p]);
+                fn(b2, gdest_b[p]);
+            } else {
+                const uint32_t k = e & ~DICT_SET;
+                if (k >= tl.n_sets || !(sdest[p] & SLOT_SET)) return fail(GBRS_ERR_STATE, "a set entry without a destination list");
+                const size_t off = sdest[p] & ~SLOT_SET, m0 = set_ptr[k], n = set_ptr[k + 1] - m0;
+                if (off + n >= glist.size() || m0 + n > members.size()) return fail(GBRS_ERR_STATE, "a set's destination list is out of range");
+                glist[off] = (uint32_t)n;
+                for (size_t q = 0; q < n; ++q) {
+                    if (members[m0 + q] >= L) return fail(GBRS_ERR_STATE, "a set member is no locus");
+                    fn(members[m0 + q], glist[off + 1 + q]);
+                }
+            }
+        }
+        return GBRS_OK;
+    };
+    std::vector<uint32_t> uses(L, 0u);
+    GBRS_TRY(walk([&](uint32_t l, uint32_t &) { ++uses[l]; }));
+    std::vector<uint8_t> owned(L, 0);
+    GBRS_TRY(walk([&](uint32_t l, uint32_t &w) {
+        w = l | (owned[l] ? 0u : GSLOT_OWNER) | (uses[l] == 1 ? GSLOT_DIRECT : 0u);
+        owned[l] = 1;
+    }));
+    GBRS_TRY(tl.gdest.alloc(gdest.size()));
+    GBRS_TRY(tl.gdest_b.alloc(std::max<size_t>(gdest_b.size(), 1)));
+    GBRS_TRY(tl.gdest_list.alloc(glist.size()));
+    GBRS_HIP_CHECK(hipMemcpy(tl.gdest.p, gdest.data(), gdest.size() * 4, hipMemcpyHostToDevice));
+    if (!gdest_b.empty()) GBRS_HIP_CHECK(hipMemcpy(tl.gdest_b.p, gdest_b.data(), gdest_b.size() * 4, hipMemcpyHostToDevice));
+    GBRS_HIP_CHECK(hipMemcpy(tl.gdest_list.p, glist.data(), glist.size() * 4, hipMemcpyHostToDevice));
+    tl.gather_slots = true;
+    return GBRS_OK;
+}
+
 int build_tile_layout(TileLayout &out, uint64_t R, uint64_t N, const uint32_t *ent_row, const uint64_t *col_ptr,
                       const double *count, hipStream_t s, const EmPlan &plan) {
     const uint32_t L_in = plan.tL, H = plan.tH;

@@ -39,6 +39,7 @@ struct EmTuning {
     uint32_t resample_cut = 256;      // RESAMPLE_CUT (> 0): rows with a larger count get a workgroup in the draw
     bool no_fused_mstep = false;      // NO_FUSED_MSTEP=1: gather and M-step as separate launches (em_step.h)
     bool no_float_check = false;      // NO_FLOAT_CHECK set at all: no "row without abundance" error (ablation builds of the E-step)
+    bool no_gather_mstep = false;     // NO_GATHER_MSTEP=1: the M-step stays a launch of its own (em_step.h, em_gather_mstep)
 };
 
 namespace em_env {
@@ -74,6 +75,7 @@ inline EmTuning em_tuning_from_env() {
     at_least("GBRS_TUNING_RESAMPLE_CUT", 1, t.resample_cut);
     t.no_fused_mstep = integer("GBRS_TUNING_NO_FUSED_MSTEP").nonzero();
     t.no_float_check = integer("GBRS_TUNING_NO_FLOAT_CHECK").set;
+    t.no_gather_mstep = integer("GBRS_TUNING_NO_GATHER_MSTEP").nonzero();
     return t;
 }
 
@@ -159,6 +161,7 @@ struct EmPlan {
     uint32_t lead_mask = ~0u;
     uint32_t resample_cut = 256;     // (the variable is read by a resampling handle with counts only)
     bool no_fused_mstep = false, no_float_check = false;   // EmTuning's, for the handle's steps (em_step.h, em_check_float)
+    bool no_gather_mstep = false;
 };
 
 // Tiles the exact cut aims at: one round of the places a handle has - its share when handles run side by side - less the
@@ -179,6 +182,7 @@ inline EmPlan em_plan(const EmShape &s, const EmTuning &t) {
     p.side_by_side = (f & GBRS_EM_SIDE_BY_SIDE) ? 2u : 1u;
     p.no_fused_mstep = t.no_fused_mstep;
     p.no_float_check = t.no_float_check;
+    p.no_gather_mstep = t.no_gather_mstep;
     if ((f & GBRS_EM_RESAMPLE) && s.counts_given) p.resample_cut = t.resample_cut;
     p.tiled = !(f & GBRS_EM_LAYOUT_CSC) && s.H <= 16 && s.N < 0xFFFFFFFFull;
     p.tH = s.H;

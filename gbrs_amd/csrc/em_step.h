@@ -85,4 +85,27 @@ inline EmStepRoute em_step_route(const EmStepShape &s, EmPass pass) {
     return r;
 }
 
+// The gather-side M-step (em_layout.h, GatherArgs): a third way to run a Model-4 step on the tile layout, beside "fused
+// gather + M-step launch" and "two launches".  Iteration n's M-step is applied by launch n + 1's tile prologues and a plain
+// elementwise M-step closes an API call; no slot rows, no gather, one launch per iteration.  Which passes take it is
+// decided here, beside the route and from the same shape, by what the route does not know:
+struct EmGatherShape {
+    bool no_heavy = true;         // TileLayout::n_heavy is zero: no locus has more than HEAVY_SLOTS slots
+    uint32_t n_tiles = 0, tile_waves = 0, msum_cap = 0;   // the block sums take tile_waves slots per tile
+    bool posterior = false, resample = false, pair_mode = false;   // GBRS_EM_POSTERIOR, GBRS_EM_RESAMPLE, gbrs_em_pair_begin
+};
+
+inline bool em_gather_mstep(const EmStepShape &s, const EmGatherShape &g, EmPass pass, const EmTuning &t) {
+    if (pass != EmPass::Step || !s.tiled || s.no_tiles) return false;
+    const EmStepRoute r = em_step_route(s, pass);
+    if (r.estep != EmEstep::Tiles && r.estep != EmEstep::TilesOneWord) return false;     // not deterministic, not persistent
+    if (s.weighted) return false;
+    if (!(s.H == 1 || s.H == 2 || s.H == 4 || s.H == 8) || s.tH != s.H || s.view != 1) return false;
+    if (!s.no_long || !g.no_heavy) return false;
+    if (s.acc_handed_out) return false;
+    if (g.posterior || g.resample || g.pair_mode) return false;
+    if ((uint64_t)g.n_tiles * g.tile_waves > g.msum_cap) return false;
+    return !t.no_gather_mstep;
+}
+
 }  // namespace gbrs

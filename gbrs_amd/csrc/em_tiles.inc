@@ -527,7 +527,103 @@ __device__ __forceinline__ void diag_stamp(int slot, unsigned long long extra = 
 #define GBRS_DIAG_PSTAMP(t, slot) do { } while (0)
 #endif
 
-template <int HT, bool WEIGHTED, bool ONES, bool DET = false, bool ONEWORD = false>
+// ---- the gather-side M-step (em_layout.h, GatherArgs) -----------------------------------------------------------------
+// One (slot, member) of a tile's dictionary at haplotype h: theta, A of the iteration before and the length are loaded
+// together (gm_load), then theta' = theta * A / len - the arithmetic and order of mstep_row (em_mstep.inc) - is what the tile
+// puts into LDS.  The owner's H adjacent lanes store theta', the locus's totals (locus_total's pairing tree, one haplotype
+// per lane: xor 1, 2, 4) and add to the tile's block sums; they zero the locus's row of the A vector the next launch adds
+// into.  Without `pending` theta is current and only the zeroing is stored.
+struct GatherMember { double t, a, ln; };
+template <int H>
+__device__ __forceinline__ GatherMember gm_load(const GatherArgs &ga, const double *__restrict__ theta, uint32_t g, uint32_t h) {
+    const size_t i = (size_t)(g & GSLOT_LOCUS) * H + h;
+    GatherMember m;
+    m.t = theta[i];
+    m.a = ga.acc_old[i];
+    m.ln = ga.eff_len ? ga.eff_len[i] : 1.0;
+    return m;
+}
+// locus_total's tree (em_mstep.inc) over one haplotype per lane.  locus_total asks for every lane of the wavefront active;
+// here the calls sit in divergent code (the prologue's loop tail, the branches on the kind of entry), which is fine because a
+// DPP step only reads lanes of the locus's own group of H: element i = j * H + h of the dictionary goes to thread i mod
+// TILE_THREADS, H divides 64, so the H lanes of an entry are an aligned group, take every branch together (the branches test
+// the entry, not the haplotype) and are active or inactive as one.
+template <int H>
+__device__ __forceinline__ double gm_total(double x) {
+    if (H >= 2) x += mstep_dpp<0xB1>(x);         // quad_perm:[1,0,3,2]
+    if (H >= 4) x += mstep_dpp<0x4E>(x);         // quad_perm:[2,3,0,1]
+    if (H >= 8) x += mstep_dpp<0x141>(x);        // row_half_mirror
+    return x;
+}
+template <int H>
+__device__ __forceinline__ double gm_apply(const GatherArgs &ga, uint32_t g, uint32_t h, const GatherMember &m, bool live,
+                                           double &sum_old, double &sum_new) {
+    const uint32_t l = g & GSLOT_LOCUS;
+    const size_t i = (size_t)l * H + h;
+    const bool owner = (g & GSLOT_OWNER) != 0 && live;
+    double tn = m.t;
+    if (ga.pending) {                            // (a kernel argument: uniform)
+        const double c = m.t * m.a;
+        tn = c / m.ln;                           // (no lengths: c / 1.0 is c)
+        const double tp = gm_total<H>(m.t), tq = gm_total<H>(tn);
+        if (owner) {
+            ga.theta_new[i] = tn;
+            if (h == 0) {
+                ga.tot_prev[l] = tp;
+                ga.tot_new[l] = tq;
+            }
+            sum_old += m.t;
+            sum_new += tn;
+        }
+    }
+    if (owner && !(g & GSLOT_DIRECT)) ga.acc_next[i] = 0.0;
+    return tn;
+}
+
+// The tile prologue of the gather-side route: the same dependent trips as the plain gather (header -> dictionary -> theta),
+// A and the length fetched in the last one.  A two-member set does both members and stores their sum, a larger set its
+// members in member order.  The tile's two block sums go to one slot per wavefront (fixed order, no atomics).
+template <int H, bool WEIGHTED>
+__device__ __forceinline__ void tile_gather_prologue(const TileHdr &th, uint32_t DH, const uint32_t *__restrict__ dict,
+                                                     const uint32_t *__restrict__ slot_dest, const double *__restrict__ theta,
+                                                     const SetArgs &sets, const GatherArgs &ga, bool live, int wave,
+                                                     double *__restrict__ s_theta) {
+    double sum_old = 0.0, sum_new = 0.0;
+    for (uint32_t i = threadIdx.x; i < DH; i += TILE_THREADS) {
+        const uint32_t j = i / H, h = i - j * H, p = th.dict_base + j;
+        const uint32_t e = dict[p], g = ga.gdest[p];
+        double tv;
+        if (sets.set_ptr == nullptr || !(e & (DICT_PAIR | DICT_SET))) {
+            tv = gm_apply<H>(ga, g, h, gm_load<H>(ga, theta, g, h), live, sum_old, sum_new);
+        } else if (e & DICT_PAIR) {
+            const uint32_t g2 = ga.gdest_b[p];
+            const GatherMember m0 = gm_load<H>(ga, theta, g, h), m1 = gm_load<H>(ga, theta, g2, h);
+            const double t0 = gm_apply<H>(ga, g, h, m0, live, sum_old, sum_new);
+            const double t1 = gm_apply<H>(ga, g2, h, m1, live, sum_old, sum_new);
+            tv = t0 + t1;
+        } else {
+            const uint32_t *gl = ga.gdest_list + (slot_dest[p] & ~SLOT_SET);
+            const uint32_t n = gl[0];
+            tv = 0.0;
+            for (uint32_t q = 1; q <= n; ++q) {
+                const uint32_t gq = gl[q];
+                tv += gm_apply<H>(ga, gq, h, gm_load<H>(ga, theta, gq, h), live, sum_old, sum_new);
+            }
+        }
+        constexpr uint32_t DP = theta_planar(H) ? lds_theta_doubles(WEIGHTED, H) / H : 0;
+        s_theta[theta_planar(H) ? (((h >> 1) * DP + j) << 1) + (h & 1u) : i] = tv;
+    }
+    if (ga.pending) {
+        sum_old = wave_sum_all(sum_old);
+        sum_new = wave_sum_all(sum_new);
+        if ((threadIdx.x & 63) == 0 && live) {
+            ga.msums[(size_t)blockIdx.x * TILE_WAVES + wave] = sum_old;
+            ga.msums[(size_t)ga.cap + (size_t)blockIdx.x * TILE_WAVES + wave] = sum_new;
+        }
+    }
+}
+
+template <int HT, bool WEIGHTED, bool ONES, bool DET = false, bool ONEWORD = false, bool GATHER = false>
 // (the deterministic 8-haplotype form spills 12-16 B per lane at 6 waves per SIMD - 80 registers + its flush tree.  Compiled
 // for 4 waves it needs 84 registers and no scratch, and is SLOWER: 0.949 against 0.82 ms per iteration on C2 (round 4) - the
 // spill sits in the rare ordered-flush path, the occupancy pays on every batch.  So the scratch stays.)
@@ -540,7 +636,9 @@ tile_estep_kernel(uint32_t Hrt, const TileHdr *__restrict__ tiles, const uint32_
                   const double *__restrict__ theta, double *__restrict__ partials,
                   const uint32_t *__restrict__ slot_dest, double *__restrict__ acc_direct,
                   EmScalars *__restrict__ sc, uint32_t n_tiles, ErrArgs ea, SetArgs sets,
-                  uint32_t lead_mask /* ~0: the headers' n_one is used; 0: one loop for every batch */) {
+                  uint32_t lead_mask /* ~0: the headers' n_one is used; 0: one loop for every batch */,
+                  GatherArgs ga /* GATHER: the M-step of the iteration before rides the prologue; else not read */) {
+    static_assert(!GATHER || (HT > 0 && HT <= 8 && !WEIGHTED && !ONES && !DET), "the gather-side M-step: unweighted, 1-8 haplotypes");
     constexpr int LDS_ACC_DOUBLES = lds_acc_doubles(WEIGHTED, HT);
     __shared__ __attribute__((aligned(16))) double s_theta[lds_theta_doubles(WEIGHTED, HT)];
     __shared__ __attribute__((aligned(16))) double2 s_ftab[32];      // [16] pairs (bit0, bit1) of a nibble, [16] pairs (bit2, bit3)
@@ -636,6 +734,9 @@ tile_estep_kernel(uint32_t Hrt, const TileHdr *__restrict__ tiles, const uint32_
 #endif
     for (uint32_t i = threadIdx.x; i < K * stride; i += TILE_THREADS) s_acc[i] = 0.0;
     GBRS_DIAG_STAMP(7);
+    // (GATHER: a stopped launch stores nothing at all - the flag is waited for in front of the prologue's first store)
+    if constexpr (GATHER) tile_gather_prologue<HT, WEIGHTED>(th, DH, dict, slot_dest, theta, sets, ga, stop_flag == 0, wave, s_theta);
+    else
     for (uint32_t i = threadIdx.x; i < DH; i += TILE_THREADS) {
         const uint32_t j = i / H, h = i - j * H;
         constexpr uint32_t DP = theta_planar(HT) ? lds_theta_doubles(WEIGHTED, HT) / (HT > 0 ? HT : 1) : 0;
@@ -815,6 +916,28 @@ tile_estep_kernel(uint32_t Hrt, const TileHdr *__restrict__ tiles, const uint32_
         const uint32_t j = i / H, h = i - j * H;
         const uint32_t d = slot_dest[th.dict_base + j];
         const uint32_t d2 = sets.set_ptr ? sets.dest_b[th.dict_base + j] : 0u;      // (fetched beside d, not after it)
+        if constexpr (GATHER) {
+            // no slot rows and no gather: a locus that lives in this tile only is stored, every other one added with a
+            // global float atomic into its row of this launch's A vector, which the launch before zeroed
+            const uint32_t g = ga.gdest[th.dict_base + j];
+            const uint32_t g2 = sets.set_ptr ? ga.gdest_b[th.dict_base + j] : 0u;
+            auto add = [&](uint32_t gq) {
+                double *dst = ga.acc_cur + (size_t)(gq & GSLOT_LOCUS) * H + h;
+                if (gq & GSLOT_DIRECT) *dst = a;
+                else atomicAdd(dst, a);
+            };
+            if (sets.set_ptr == nullptr || !(d & (SLOT_SET | SLOT_PAIR))) {
+                add(g);
+            } else if (d & SLOT_PAIR) {
+                add(g);
+                add(g2);
+            } else {
+                const uint32_t *gl = ga.gdest_list + (d & ~SLOT_SET);
+                const uint32_t n = gl[0];
+                for (uint32_t q = 1; q <= n; ++q) add(gl[q]);
+            }
+            continue;
+        }
         auto put = [&](uint32_t dq) {
             if (dq & SLOT_DIRECT) acc_direct[(size_t)(dq & ~SLOT_DIRECT) * H + h] = a;
             else partials[(size_t)dq * H + h] = a;

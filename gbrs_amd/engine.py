@@ -141,6 +141,12 @@ class EmEngine:
         _lib.check(_lib.load().gbrs_em_tile_cut(self._h, C.byref(passes), C.byref(words)))
         return int(passes.value), int(words.value)
 
+    def gather_mstep(self):
+        """Do the handle's Model-4 steps take the gather-side M-step, as it stands (gbrs_em_gather_mstep)?"""
+        taken = C.c_uint32(0)
+        _lib.check(_lib.load().gbrs_em_gather_mstep(self._h, C.byref(taken)))
+        return bool(taken.value)
+
     def tile_shapes(self):
         """Per tile, in launch order: (batches, dictionary entries) as two uint32 arrays (gbrs_em_tile_shapes)."""
         n = int(self.info().num_tiles)

@@ -334,7 +334,9 @@ typedef struct gbrs_em_info {
     uint64_t bytes_per_iter;    /* bytes the E+M step kernels move per iteration (layout)   */
     uint64_t algorithmic_bytes; /* 4N + 4(R+1) [+8R] + 8HL*2 [+8HL]             */
     double   last_estep_ms;     /* HIP-event time of the E-step launch (mean of the timed    */
-    double   last_step_ms;      /* steps: every 8th of a gbrs_em_step call) / of a full step */
+    double   last_step_ms;      /* steps: every 8th of a gbrs_em_step call) / of a full step.
+                                   On the gather-side route (gbrs_em_gather_mstep) a step IS its one
+                                   launch: last_estep_ms is that launch, last_step_ms the same     */
     uint32_t num_loci, num_haps;
     uint32_t layout;            /* 0 = csc-direct, 1 = packed row tiles                     */
     uint32_t num_folded_rows;   /* layout 1: one-word reads counted by an identical read's word instead of a word of
@@ -364,6 +366,11 @@ int gbrs_em_fold_counts(gbrs_em_t *em, uint64_t *one_word_reads, uint64_t *two_w
  * two-grid cut (GBRS_TUNING_TILE_WORDS forces the size, or GBRS_TUNING_TILE_CUT=0); tile_words: the size that cut the
  * tiles.  Both 0 for the CSC layout. */
 int gbrs_em_tile_cut(gbrs_em_t *em, uint32_t *passes, uint32_t *tile_words);
+/* Do the handle's Model-4 steps (gbrs_em_step, gbrs_em_run), as it stands, take the gather-side M-step: iteration n's
+ * M-step applied by the tile prologues of launch n + 1, one launch per iteration and one elementwise M-step at the end of a
+ * call?  taken: 1 / 0 (GBRS_TUNING_NO_GATHER_MSTEP=1 at create, heavy loci, long rows, weights, the deterministic mode,
+ * 16 haplotypes, posteriors, resampling, pair mode or a handed-out acc: 0). */
+int gbrs_em_gather_mstep(gbrs_em_t *em, uint32_t *taken);
 /* Per tile, in launch order: its batches of 64 words and its dictionary entries.  n must be gbrs_em_info.num_tiles; one
  * device-to-host copy of the headers (profiling scripts and tests). */
 int gbrs_em_tile_shapes(gbrs_em_t *em, uint32_t *n_batches, uint32_t *dict_entries, uint64_t n);

@@ -38,6 +38,7 @@ EXPORTS = [
     "gbrs_scan_create", "gbrs_scan_destroy", "gbrs_scan_append", "gbrs_scan_append_hmm", "gbrs_scan_prepare", "gbrs_scan_run",
     "gbrs_scan_info", "gbrs_scan_permute", "gbrs_scan_perm_info",
     "gbrs_scan_set_snps", "gbrs_scan_snp_dosage", "gbrs_scan_snps", "gbrs_scan_snp_info",
+    "gbrs_scan_mediate", "gbrs_scan_mediate_info",
     "gbrs_compress_create", "gbrs_compress_get", "gbrs_compress_destroy",
     "gbrs_bam_open", "gbrs_bam_references", "gbrs_bam_set_reference_map", "gbrs_bam_convert", "gbrs_bam_get",
     "gbrs_bam_scan_records", "gbrs_bam_destroy",
@@ -124,6 +125,13 @@ class ScanSnpInfo(C.Structure):
         ("M_snp", C.c_int64), ("chunk", C.c_int64), ("P", C.c_int64), ("last_pass_ms", C.c_double),
         ("last_row_ms", C.c_double), ("last_product_ms", C.c_double), ("device_bytes", C.c_uint64),
         ("peak_device_bytes", C.c_uint64), ("staged", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+class ScanMediateInfo(C.Structure):
+    _fields_ = [
+        ("T", C.c_int64), ("Q", C.c_int64), ("last_pass_ms", C.c_double), ("last_product_ms", C.c_double),
+        ("peak_device_bytes", C.c_uint64),
     ]
 
 
@@ -241,6 +249,8 @@ def load():
         "gbrs_scan_snp_dosage": [vp, i64, i64, vp],
         "gbrs_scan_snps": [vp, i64, vp, vp, vp, vp, vp],
         "gbrs_scan_snp_info": [vp, C.POINTER(ScanSnpInfo)],
+        "gbrs_scan_mediate": [vp, i64, vp, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp],
+        "gbrs_scan_mediate_info": [vp, C.POINTER(ScanMediateInfo)],
         "gbrs_compress_create": [u64, u32, u32, pp, pp, vp, i32, pp, C.POINTER(u64), vp],
         "gbrs_compress_get": [vp, pp, pp, vp],
         "gbrs_compress_destroy": [vp],

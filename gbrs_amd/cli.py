@@ -310,6 +310,20 @@ def _scan_options(parser, covar=True):
                              '(default: all)')
     parser.add_argument('--scan-perm-pheno', type=_existing, default=None, metavar='FILE',
                         help='with --scan-perms: one phenotype name per line; only those are permuted (default: all)')
+    parser.add_argument('--scan-mediate', action='store_true',
+                        help='mediation analysis on the device: for every (phenotype, chromosome) peak of the scan every '
+                             'mediator joins the covariates in turn and the peak\'s LOD is formed again; a mediator that makes '
+                             'it collapse is a candidate for what lies between the locus and the phenotype.  Writes '
+                             '<PREFIX>.scan.mediation.npz and <PREFIX>.scan.mediation.tsv')
+    parser.add_argument('--scan-mediate-min-lod', type=float, default=None, metavar='X',
+                        help='with --scan-mediate: the peaks of at least this LOD are mediated (default: 6.0, a convention '
+                             'for picking peaks worth a look, not a significance threshold)')
+    parser.add_argument('--scan-mediate-top', type=int, default=None, metavar='K',
+                        help='with --scan-mediate: the K mediators with the lowest mediated LOD are listed per peak '
+                             '(default: 5, at most 64)')
+    parser.add_argument('--scan-mediator-file', type=_existing, default=None, metavar='FILE',
+                        help='with --scan-mediate: the mediators, a table in the phenotypes\' format with the same ids '
+                             '(default: the phenotypes themselves); --scan-rankz applies to it too')
 
 
 def main(argv=None) -> int:
@@ -435,7 +449,9 @@ def main(argv=None) -> int:
                         lod_matrix=args.scan_lod_matrix, device=args.device, scan_perms=args.scan_perms,
                         scan_perm_seed=args.scan_perm_seed, scan_perm_alpha=args.scan_perm_alpha,
                         scan_perm_chromosomes=args.scan_perm_chromosomes, scan_perm_pheno=args.scan_perm_pheno,
-                        stage_times=stages, snp_file=args.snp_file)
+                        stage_times=stages, snp_file=args.snp_file, scan_mediate=args.scan_mediate,
+                        scan_mediate_min_lod=args.scan_mediate_min_lod, scan_mediate_top=args.scan_mediate_top,
+                        scan_mediator_file=args.scan_mediator_file)
         elif args.command == 'interpolate':
             from .postproc import interpolate
             interpolate(genoprob_file=args.genoprob_file, grid_file=args.grid_file, gpos_file=args.gpos_file,

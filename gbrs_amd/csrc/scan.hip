@@ -11,7 +11,9 @@
 // phenotypes, drawn and gathered on the device, pass through the same product and peak kernels as further columns, and
 // one maximum per (phenotype, permutation) comes back.  SNP association (kernels and the rule in
 // scan_snp.inc): a row kernel builds one normalised row per founder SNP from two grid points and a bit pattern, and a
-// sibling of the product kernel with one row per SNP turns the rows into LODs.
+// sibling of the product kernel with one row per SNP turns the rows into LODs.  Mediation (kernels and the
+// rule in scan_mediate.inc): a sibling of the product kernel gathers the W rows of each target's point, multiplies them
+// with the projected mediators and applies the conditional regression's rule in its epilogue.
 #include "common.h"
 #include "scan_hmm.h"
 
@@ -315,6 +317,10 @@ scan_peak_kernel(int64_t M, int n_chrom, const int64_t *__restrict__ point_off, 
 
 #include "scan_snp.inc"
 
+// ---- mediation ---------------------------------------------------------------------------------------------------------------
+
+#include "scan_mediate.inc"
+
 }  // namespace gbrs
 
 using namespace gbrs;
@@ -357,6 +363,10 @@ struct gbrs_scan {
     int snp_staged = 0;
     double t_snp_pass = 0, t_snp_row = 0, t_snp_product = 0;
     uint64_t snp_peak_bytes = 0;
+    // the last gbrs_scan_mediate: its buffers are the call's own, as gbrs_scan_permute's
+    int64_t med_T = 0, med_Q = 0;
+    double t_med_pass = 0, t_med_product = 0;
+    uint64_t med_peak_bytes = 0;
     uint64_t snp_bytes() const {
         return d_snp_off.bytes() + snp_lo.bytes() + snp_hi.bytes() + snp_mask.bytes() + snp_t.bytes();
     }
@@ -940,6 +950,133 @@ int gbrs_scan_snp_info(gbrs_scan_t *s, gbrs_scan_snp_info_t *info) {
     info->last_product_ms = s->t_snp_product;
     info->device_bytes = s->snp_bytes();
     info->peak_device_bytes = s->snp_peak_bytes;
+    return GBRS_OK;
+}
+
+int gbrs_scan_mediate(gbrs_scan_t *s, int64_t T, const double *target, const int64_t *point, int64_t Q, const double *mediator,
+                      int K, double *lod0, double *lod_med, uint8_t *used, double *best_lod, int64_t *best_index, double *mean,
+                      double *sd, int64_t *n_used) {
+    RoctxRange roctx_range("gbrs_scan_mediate");
+    if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (s->c == 0) return fail(GBRS_ERR_INVALID, "no covariates on the handle: call gbrs_scan_prepare first");
+    if (T < 1) return fail(GBRS_ERR_INVALID, "a mediation pass needs at least 1 target, got %lld", (long long)T);
+    if (Q < 1) return fail(GBRS_ERR_INVALID, "a mediation pass needs at least 1 mediator, got %lld", (long long)Q);
+    if (K < 0 || K > SM_MAX_K) return fail(GBRS_ERR_INVALID, "the top list has 0..%d places, got %d", SM_MAX_K, K);
+    if (!target || !point || !mediator || (K > 0 && (!best_lod || !best_index))) return fail(GBRS_ERR_INVALID, "bad argument");
+    if (s->n <= (int64_t)s->c + s->H)
+        return fail(GBRS_ERR_INVALID, "%lld samples are too few to mediate with %d covariate columns and %d founders: the mediator "
+                    "takes one more degree of freedom, need more than %d", (long long)s->n, s->c, s->H, s->c + s->H);
+    if (Q > std::numeric_limits<int64_t>::max() / 16 / std::min(T, SM_TCHUNK) || (Q + SC_COLS - 1) / SC_COLS > std::numeric_limits<int32_t>::max())
+        return fail(GBRS_ERR_INVALID, "too many mediators: %lld", (long long)Q);
+    for (int64_t t = 0; t < T; ++t)
+        if (point[t] < 0 || point[t] >= s->M)
+            return fail(GBRS_ERR_INVALID, "target %lld is at grid point %lld: the handle has the points 0 .. %lld", (long long)t,
+                        (long long)point[t], (long long)(s->M - 1));
+    const int n = (int)s->n;
+    for (int64_t k = 0; k < (int64_t)n * T; ++k)
+        if (!std::isfinite(target[k]))
+            return fail(GBRS_ERR_INVALID, "target %lld holds a value that is not finite (sample %lld)", (long long)(k % T),
+                        (long long)(k / T));
+    for (int64_t k = 0; k < (int64_t)n * Q; ++k)
+        if (!std::isfinite(mediator[k]))
+            return fail(GBRS_ERR_INVALID, "mediator %lld holds a value that is not finite (sample %lld)", (long long)(k % Q),
+                        (long long)(k / Q));
+    GBRS_TRY(select_device(s->device));
+    const int64_t n_ld = s->n_ld, tc_max = std::min(T, SM_TCHUNK), yc_max = std::max(std::min(Q, SC_PCHUNK), tc_max);
+    const int Hp = s->Hp, pts = SC_ROWS / Hp;
+    DevBuf<double> y, zt, szz, yt, syy, a, rss1, d_lod0, d_lod, d_best, d_mean, d_sd;
+    DevBuf<int64_t> d_point, d_index, d_count;
+    DevBuf<uint8_t> d_used;
+    GBRS_TRY(y.alloc((size_t)n * yc_max));
+    GBRS_TRY(zt.alloc((size_t)Q * n_ld));
+    GBRS_TRY(szz.alloc((size_t)Q));
+    GBRS_TRY(yt.alloc((size_t)tc_max * n_ld));
+    GBRS_TRY(syy.alloc((size_t)tc_max));
+    GBRS_TRY(a.alloc((size_t)tc_max * Hp));
+    GBRS_TRY(rss1.alloc((size_t)tc_max));
+    GBRS_TRY(d_lod0.alloc((size_t)T));
+    GBRS_TRY(d_lod.alloc((size_t)tc_max * Q));
+    GBRS_TRY(d_used.alloc((size_t)tc_max * Q));
+    GBRS_TRY(d_best.alloc((size_t)T * K));
+    GBRS_TRY(d_index.alloc((size_t)T * K));
+    GBRS_TRY(d_mean.alloc((size_t)T));
+    GBRS_TRY(d_sd.alloc((size_t)T));
+    GBRS_TRY(d_count.alloc((size_t)T));
+    GBRS_TRY(d_point.alloc((size_t)T));
+    GBRS_HIP_CHECK(hipMemcpy(d_point.p, point, d_point.bytes(), hipMemcpyHostToDevice));
+    EventRing ring;
+    GBRS_TRY(ring.create());
+    GBRS_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
+    // z~ of every mediator, by gbrs_scan_run's kernel in gbrs_scan_run's chunks; it stays on the device for the pass
+    for (int64_t q0 = 0; q0 < Q; q0 += SC_PCHUNK) {
+        const int64_t qc = std::min(SC_PCHUNK, Q - q0);
+        GBRS_HIP_CHECK(hipMemcpy2DAsync(y.p, (size_t)qc * sizeof(double), mediator + q0, (size_t)Q * sizeof(double),
+                                        (size_t)qc * sizeof(double), (size_t)n, hipMemcpyHostToDevice, s->stream));
+        hipLaunchKernelGGL(scan_pheno_kernel, dim3((unsigned)qc), dim3(64), 0, s->stream, n, s->c, n_ld, qc, y.p, s->qz.p,
+                           zt.p + q0 * n_ld, szz.p + q0);
+        GBRS_HIP_CHECK(hipGetLastError());
+    }
+    for (int64_t t0 = 0; t0 < T; t0 += SM_TCHUNK) {
+        const int64_t tc = std::min(SM_TCHUNK, T - t0);
+        GBRS_HIP_CHECK(hipMemcpy2DAsync(y.p, (size_t)tc * sizeof(double), target + t0, (size_t)T * sizeof(double),
+                                        (size_t)tc * sizeof(double), (size_t)n, hipMemcpyHostToDevice, s->stream));
+        hipLaunchKernelGGL(scan_pheno_kernel, dim3((unsigned)tc), dim3(64), 0, s->stream, n, s->c, n_ld, tc, y.p, s->qz.p, yt.p, syy.p);
+        auto targets = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)tc), dim3(64), 0, s->stream, n_ld, 0.5 * n, s->W.p, d_point.p + t0, yt.p, syy.p,
+                               a.p, rss1.p, d_lod0.p + t0);
+        };
+        if (Hp == 8) targets(scan_med_target_kernel<8>);
+        else targets(scan_med_target_kernel<16>);
+        int slot = 0;
+        GBRS_TRY(ring.next(&slot));
+        GBRS_HIP_CHECK(hipEventRecord(ring.ev[2 * slot], s->stream));
+        const dim3 grid((unsigned)((Q + SC_COLS - 1) / SC_COLS), (unsigned)((tc + pts - 1) / pts));
+        auto product = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, dim3(SC_THREADS), 0, s->stream, tc, Q, n_ld, 0.5 * n, s->W.p, d_point.p + t0, yt.p, zt.p,
+                               syy.p, rss1.p, a.p, szz.p, d_lod.p, d_used.p);
+        };
+        if (Hp == 8) product(scan_med_kernel<8>);
+        else product(scan_med_kernel<16>);
+        GBRS_HIP_CHECK(hipEventRecord(ring.ev[2 * slot + 1], s->stream));
+        hipLaunchKernelGGL(scan_med_select_kernel, dim3((unsigned)tc), dim3(64), 0, s->stream, Q, K, d_lod.p, d_used.p,
+                           d_best.p + t0 * K, d_index.p + t0 * K, d_mean.p + t0, d_sd.p + t0, d_count.p + t0);
+        GBRS_HIP_CHECK(hipGetLastError());
+        // the copies wait for the kernels before them on the stream; the next chunk's product overwrites d_lod after them
+        if (lod_med)
+            GBRS_HIP_CHECK(hipMemcpyAsync(lod_med + t0 * Q, d_lod.p, (size_t)tc * Q * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        if (used) GBRS_HIP_CHECK(hipMemcpyAsync(used + t0 * Q, d_used.p, (size_t)tc * Q, hipMemcpyDeviceToHost, s->stream));
+    }
+    GBRS_HIP_CHECK(hipEventRecord(s->ev[1], s->stream));
+    GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
+    GBRS_TRY(ring.drain());
+    if (lod0) GBRS_HIP_CHECK(hipMemcpy(lod0, d_lod0.p, d_lod0.bytes(), hipMemcpyDeviceToHost));
+    if (K > 0) {
+        GBRS_HIP_CHECK(hipMemcpy(best_lod, d_best.p, d_best.bytes(), hipMemcpyDeviceToHost));
+        GBRS_HIP_CHECK(hipMemcpy(best_index, d_index.p, d_index.bytes(), hipMemcpyDeviceToHost));
+    }
+    if (mean) GBRS_HIP_CHECK(hipMemcpy(mean, d_mean.p, d_mean.bytes(), hipMemcpyDeviceToHost));
+    if (sd) GBRS_HIP_CHECK(hipMemcpy(sd, d_sd.p, d_sd.bytes(), hipMemcpyDeviceToHost));
+    if (n_used) GBRS_HIP_CHECK(hipMemcpy(n_used, d_count.p, d_count.bytes(), hipMemcpyDeviceToHost));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) s->t_med_pass = ms;
+    s->t_med_product = ring.ms;
+    s->med_T = T;
+    s->med_Q = Q;
+    s->med_peak_bytes = s->d_point_off.bytes() + s->dosage.bytes() + s->qz.bytes() + s->W.bytes() + s->d_rank.bytes() + s->y.bytes() +
+                        s->yt.bytes() + s->rss0.bytes() + s->lod.bytes() + s->peak_lod.bytes() + s->peak_index.bytes() + s->snp_bytes() +
+                        y.bytes() + zt.bytes() + szz.bytes() + yt.bytes() + syy.bytes() + a.bytes() + rss1.bytes() + d_lod0.bytes() +
+                        d_lod.bytes() + d_used.bytes() + d_best.bytes() + d_index.bytes() + d_mean.bytes() + d_sd.bytes() +
+                        d_count.bytes() + d_point.bytes();
+    return GBRS_OK;
+}
+
+int gbrs_scan_mediate_info(gbrs_scan_t *s, gbrs_scan_mediate_info_t *info) {
+    if (!s || !info) return fail(GBRS_ERR_INVALID, "bad argument");
+    info->T = s->med_T;
+    info->Q = s->med_Q;
+    info->last_pass_ms = s->t_med_pass;
+    info->last_product_ms = s->t_med_product;
+    info->peak_device_bytes = s->med_peak_bytes;
     return GBRS_OK;
 }
 

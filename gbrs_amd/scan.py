@@ -1,7 +1,8 @@
 """Genome scan of phenotypes on founder dosages (extension): `gbrs reconstruct --scan-pheno` and
 `gbrs scan`.  Haley-Knott regression with additive covariates on the device (gbrs_scan_*, gbrs_amd/csrc/scan.hip); the
 host side here is the covariates' QR, the file readers and the writers.  No mixed model.  `--scan-snps` / `gbrs scan
---snp-file`: the 1-df test of founder SNPs on the same prepared cohort (gbrs_scan_set_snps, gbrs_scan_snps)."""
+--snp-file`: the 1-df test of founder SNPs on the same prepared cohort (gbrs_scan_set_snps, gbrs_scan_snps).
+`--scan-mediate`: the scan's peaks conditioned on every other phenotype in turn (gbrs_scan_mediate)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -16,12 +17,16 @@ logger = logging.getLogger('gbrs')
 COVARIATE_RANK_TOL = 1e-10        # a covariate column whose |R_jj| is below this share of its norm depends on the columns before it
 LOD_MATRIX_LIMIT = 1 << 27        # P x M up to which <out>.scan.npz holds the LOD matrix without being asked
 DEFAULT_PERM_ALPHA = (0.05, 0.1)  # the levels of --scan-perm-alpha
+DEFAULT_MEDIATE_MIN_LOD = 6.0     # --scan-mediate-min-lod: the peaks that are mediated; a convention, not a threshold
+DEFAULT_MEDIATE_TOP = 5           # --scan-mediate-top: the mediators listed per peak
+MEDIATE_MAX_TOP = 64              # the places gbrs_scan_mediate's top list has
 
 
 class GenomeScan:
     """Device handle of one cohort on one grid.  append / append_from collect the samples' grid dosages in order,
     prepare(covariates) builds the phenotype-independent part once, run(pheno) scans any number of phenotypes;
-    set_snps + run_snps(pheno) test founder SNPs with one degree of freedom on the same cohort."""
+    set_snps + run_snps(pheno) test founder SNPs with one degree of freedom on the same cohort (DESIGN.md §29);
+    mediate(target, point, mediator) conditions peaks on mediators."""
 
     def __init__(self, num_haps, points_per_chrom, device=0):
         self.H = int(num_haps)
@@ -186,6 +191,47 @@ class GenomeScan:
                 'product_ms': raw.last_product_ms, 'device_bytes': raw.device_bytes,
                 'peak_device_bytes': raw.peak_device_bytes, 'staged': bool(raw.staged)}
 
+    def mediate(self, target, point, mediator, top=5, want_lod=False):
+        """Mediation of the targets' LODs by every mediator on the prepared cohort.  target: [n, T] (or
+        [n]) phenotype columns, point: [T] grid point indices (a target's peak), mediator: [n, Q] (or [n]); both tables
+        with run()'s constant-column-to-zeros step.  Returns `lod0` [T], `n_used`, `mean`, `sd` [T] over the used
+        mediators, `best_index`, `best_lod` [T, top] - the used mediators with the lowest mediated LOD in ascending
+        (LOD, index) order, -1 / NaN in the missing places - and, with want_lod, `lod_med` [T, Q] and `used` [T, Q]
+        (bool)."""
+        tables = []
+        for what, table in (('targets', target), ('mediators', mediator)):
+            y = np.array(table, dtype=np.float64, order='C')
+            if y.ndim == 1:
+                y = y[:, None]
+            if y.ndim != 2 or y.shape[0] != self.n:
+                raise ValueError(f'{what} have shape {np.shape(table)} for {self.n} samples')
+            if self.n:
+                y[:, (y == y[0]).all(axis=0)] = 0.0
+            tables.append(y)
+        y, z = tables
+        T, Q, K = y.shape[1], z.shape[1], int(top)
+        at = np.ascontiguousarray(np.atleast_1d(point), dtype=np.int64)
+        if at.shape != (T,):
+            raise ValueError(f'{at.shape} grid points for {T} targets')
+        lod0, mean, sd, count = np.empty(T), np.empty(T), np.empty(T), np.empty(T, dtype=np.int64)
+        best, index = np.empty((T, max(K, 0))), np.empty((T, max(K, 0)), dtype=np.int64)
+        lod = np.empty((T, Q)) if want_lod else None
+        used = np.empty((T, Q), dtype=np.uint8) if want_lod else None
+        _lib.check(_lib.load().gbrs_scan_mediate(self._h, T, _lib.ptr(y), _lib.ptr(at), Q, _lib.ptr(z), K, _lib.ptr(lod0),
+                                                 _lib.ptr(lod), _lib.ptr(used), _lib.ptr(best), _lib.ptr(index), _lib.ptr(mean),
+                                                 _lib.ptr(sd), _lib.ptr(count)))
+        out = {'lod0': lod0, 'n_used': count, 'mean': mean, 'sd': sd, 'best_index': index, 'best_lod': best}
+        if want_lod:
+            out['lod_med'] = lod
+            out['used'] = used.astype(bool)
+        return out
+
+    def mediate_info(self):
+        raw = _lib.ScanMediateInfo()
+        _lib.check(_lib.load().gbrs_scan_mediate_info(self._h, C.byref(raw)))
+        return {'T': raw.T, 'Q': raw.Q, 'pass_ms': raw.last_pass_ms, 'product_ms': raw.last_product_ms,
+                'peak_device_bytes': raw.peak_device_bytes}
+
     def info(self):
         raw = _lib.ScanInfo()
         _lib.check(_lib.load().gbrs_scan_info(self._h, C.byref(raw), None))
@@ -334,18 +380,40 @@ def perm_plan(perm, phenotypes, chrom_names=None):
     return columns, mask
 
 
+def mediate_options(scan_mediate=False, scan_mediate_min_lod=None, scan_mediate_top=None, scan_mediator_file=None):
+    """`--scan-mediate [--scan-mediate-min-lod X] [--scan-mediate-top K] [--scan-mediator-file FILE]` as one dict, or None
+    without `--scan-mediate`; the other options are then refused.  Refused before a file is read."""
+    if not scan_mediate:
+        for name, value in (('--scan-mediate-min-lod', scan_mediate_min_lod), ('--scan-mediate-top', scan_mediate_top),
+                            ('--scan-mediator-file', scan_mediator_file)):
+            if value is not None:
+                raise RuntimeError(f'{name} needs --scan-mediate')
+        return None
+    min_lod = DEFAULT_MEDIATE_MIN_LOD if scan_mediate_min_lod is None else float(scan_mediate_min_lod)
+    if not min_lod >= 0.0:
+        raise RuntimeError(f'--scan-mediate-min-lod must be a number that is not negative, got {scan_mediate_min_lod}')
+    top = DEFAULT_MEDIATE_TOP if scan_mediate_top is None else scan_mediate_top
+    if int(top) != top or not 1 <= top <= MEDIATE_MAX_TOP:
+        raise RuntimeError(f'--scan-mediate-top must be a whole number in 1 .. {MEDIATE_MAX_TOP}, got {scan_mediate_top}')
+    return {'min_lod': min_lod, 'top': int(top), 'mediator_file': scan_mediator_file}
+
+
 def check_scan_args(scan_pheno=None, scan_covar=None, scan_rankz=False, scan_out=None, scan_min_lod=None,
                     scan_lod_matrix=False, grid_file=None, cohort=False, scan_perms=None, scan_perm_seed=None,
-                    scan_perm_alpha=None, scan_perm_chromosomes=None, scan_perm_pheno=None):
-    """`--scan-pheno FILE [--scan-covar FILE] [--scan-rankz] [--scan-out PREFIX] [--scan-min-lod X] [--scan-lod-matrix]`
-    and the `--scan-perm*` options (perm_options):
+                    scan_perm_alpha=None, scan_perm_chromosomes=None, scan_perm_pheno=None, scan_mediate=False,
+                    scan_mediate_min_lod=None, scan_mediate_top=None, scan_mediator_file=None):
+    """`--scan-pheno FILE [--scan-covar FILE] [--scan-rankz] [--scan-out PREFIX] [--scan-min-lod X] [--scan-lod-matrix]`,
+    the `--scan-perm*` options (perm_options) and the `--scan-mediat*` options (mediate_options):
     every option needs the phenotypes, the phenotypes need `--grid-file` and a cohort (`--sample-file`): one sample
     cannot be scanned.  Refused before a file is read."""
     given = {'--scan-covar': scan_covar, '--scan-rankz': scan_rankz or None, '--scan-out': scan_out,
              '--scan-min-lod': scan_min_lod, '--scan-lod-matrix': scan_lod_matrix or None, '--scan-perms': scan_perms,
              '--scan-perm-seed': scan_perm_seed, '--scan-perm-alpha': scan_perm_alpha,
-             '--scan-perm-chromosomes': scan_perm_chromosomes, '--scan-perm-pheno': scan_perm_pheno}
+             '--scan-perm-chromosomes': scan_perm_chromosomes, '--scan-perm-pheno': scan_perm_pheno,
+             '--scan-mediate': scan_mediate or None, '--scan-mediate-min-lod': scan_mediate_min_lod,
+             '--scan-mediate-top': scan_mediate_top, '--scan-mediator-file': scan_mediator_file}
     perm_options(scan_perms, scan_perm_seed, scan_perm_alpha, scan_perm_chromosomes, scan_perm_pheno)
+    mediate_options(scan_mediate, scan_mediate_min_lod, scan_mediate_top, scan_mediator_file)
     if scan_pheno is None:
         for name, value in given.items():
             if value is not None:
@@ -564,12 +632,89 @@ def finish_scan_snps(scan, prefix, ids, phenotypes, covariates, y, snps, chrom_n
         stage_times['scan_snps'] = stage_times.get('scan_snps', 0.0) + time.perf_counter() - t0
 
 
+def mediation_targets(peak_lod, peak_index, min_lod):
+    """(phenotype, chromosome) of every peak of the scan with a LOD of at least min_lod, phenotype after phenotype: [T, 2]."""
+    with np.errstate(invalid='ignore'):
+        on = (np.asarray(peak_index) >= 0) & (np.asarray(peak_lod) >= min_lod)
+    return np.argwhere(on).astype(np.int64).reshape(-1, 2)
+
+
+def write_scan_mediation(prefix, phenotypes, mediators, samples, covariates, chrom_names, pos, targets, points, result,
+                         min_lod):
+    """`<prefix>.scan.mediation.npz` and `<prefix>.scan.mediation.tsv` from GenomeScan.mediate's dict.  targets: [T, 2]
+    (phenotype, chromosome) indices, points: [T] grid points.  One line per (target, rank) whose place is filled; drop is
+    lod - lod_mediated and z is (lod_mediated - mean) / sd over the target's used mediators, NA without a spread."""
+    targets = np.asarray(targets, dtype=np.int64).reshape(-1, 2)
+    arrays = dict(phenotypes=np.array(phenotypes), mediators=np.array(mediators), samples=np.array(samples),
+                  covariates=np.array(covariates), targets=np.array([phenotypes[p] for p in targets[:, 0]], dtype=np.str_),
+                  target_phenotype=targets[:, 0], target_chromosome=np.array([chrom_names[c] for c in targets[:, 1]], dtype=np.str_),
+                  points=np.asarray(points, dtype=np.int64), position=np.asarray(pos, dtype=np.float64)[np.asarray(points, dtype=np.int64)],
+                  min_lod=np.float64(min_lod))
+    for key in ('lod0', 'best_index', 'best_lod', 'mean', 'sd', 'n_used', 'lod_med', 'used'):
+        if key in result:
+            arrays[key] = result[key]
+    np.savez(f'{prefix}.scan.mediation.npz', **arrays)
+    with open(f'{prefix}.scan.mediation.tsv', 'w') as out:
+        out.write('#phenotype\tchromosome\tposition\tlod\tmediator\tlod_mediated\tdrop\tz\n')
+        for t, (p, c) in enumerate(targets):
+            lod0, mean, sd = float(result['lod0'][t]), float(result['mean'][t]), float(result['sd'][t])
+            for q, v in zip(result['best_index'][t], result['best_lod'][t]):
+                if q < 0:
+                    break
+                v = float(v)
+                z = repr((v - mean) / sd) if sd > 0.0 else 'NA'
+                out.write(f'{phenotypes[p]}\t{chrom_names[c]}\t{repr(float(arrays["position"][t]))}\t{repr(lod0)}\t{mediators[q]}\t'
+                          f'{repr(v)}\t{repr(lod0 - v)}\t{z}\n')
+
+
+def mediator_table(mediate, ids, pheno, y, use_rankz):
+    """(names, values [n, Q]) of the mediators: the phenotypes as the scan saw them, or the table of `--scan-mediator-file`
+    (mediate['table'] when it was read before, else read here) with `--scan-rankz` applied like the phenotypes'.  Every
+    sample of the scan needs a row."""
+    if mediate.get('mediator_file') is None:
+        return list(pheno[0]), y
+    table = mediate['table'] if mediate.get('table') is not None else read_scan_pheno(mediate['mediator_file'])
+    missing = [i for i in ids if i not in table[1]]
+    if missing:
+        raise RuntimeError(f'{mediate["mediator_file"]}: {missing[0]} has no row: the mediators need the ids of the phenotypes')
+    return list(table[0]), scan_design(ids, table, None, use_rankz)[1]
+
+
+def finish_scan_mediation(scan, prefix, ids, pheno, covariates, y, mediate, result, chrom_names, pos, lod_matrix=False,
+                          stage_times=None):
+    """The mediation pass on the prepared cohort `scan` holds and its two files.  y: the phenotypes as the
+    scan saw them; result: GenomeScan.run's dict, whose peaks of at least mediate['min_lod'] are the targets.  Its
+    wall-clock seconds go to stage_times['mediate']."""
+    import time
+    t0 = time.perf_counter()
+    names, z = mediator_table(mediate, ids, pheno, y, mediate.get('rankz', False))
+    targets = mediation_targets(result['peak_lod'], result['peak_index'], mediate['min_lod'])
+    points = result['peak_index'][targets[:, 0], targets[:, 1]]
+    T, Q, K = len(targets), len(names), mediate['top']
+    want_lod = bool(lod_matrix) or T * Q <= LOD_MATRIX_LIMIT
+    if T:
+        got = scan.mediate(y[:, targets[:, 0]], points, z, top=K, want_lod=want_lod)
+        timing = scan.mediate_info()
+        logger.info(f'scan: {T} peaks mediated by {Q} mediators; {timing["pass_ms"]:.1f} ms on the device, '
+                    f'{timing["product_ms"]:.1f} ms of them in the product kernel')
+    else:
+        logger.warning(f'scan: no peak reaches a LOD of {mediate["min_lod"]}: nothing to mediate')
+        got = {'lod0': np.zeros(0), 'n_used': np.zeros(0, dtype=np.int64), 'mean': np.zeros(0), 'sd': np.zeros(0),
+               'best_index': np.zeros((0, K), dtype=np.int64), 'best_lod': np.zeros((0, K)), 'lod_med': np.zeros((0, Q)),
+               'used': np.zeros((0, Q), dtype=bool)}
+    write_scan_mediation(prefix, pheno[0], names, ids, covariates, [str(c) for c in chrom_names], pos, targets, points, got,
+                         mediate['min_lod'])
+    if stage_times is not None:
+        stage_times['mediate'] = stage_times.get('mediate', 0.0) + time.perf_counter() - t0
+
+
 def finish_scan(scan, prefix, ids, pheno, covar, use_rankz, chrom, pos, chrom_names, min_lod=None, lod_matrix=False,
-                perm=None, stage_times=None, snps=None, snp_grid=None):
+                perm=None, stage_times=None, snps=None, snp_grid=None, mediate=None):
     """prepare + run + the two files for the cohort `scan` holds, whose samples are `ids` in append order (every one with
     its rows in the tables).  perm: perm_options' dict, or None; with it the permutation pass runs after the scan on the
-    phenotypes and chromosomes it names and its wall-clock seconds go to stage_times['scan_perm'].  Returns
-    GenomeScan.info() after the run."""
+    phenotypes and chromosomes it names and its wall-clock seconds go to stage_times['scan_perm'].  mediate:
+    mediate_options' dict, or None; with it the scan's peaks are mediated after everything else (finish_scan_mediation).
+    Returns GenomeScan.info() after the run."""
     kept, y, z, names = scan_design(ids, pheno, covar, use_rankz)
     assert len(kept) == len(ids) == scan.n
     if perm is not None:
@@ -595,20 +740,26 @@ def finish_scan(scan, prefix, ids, pheno, covar, use_rankz, chrom, pos, chrom_na
                 f'{info["prepare_ms"]:.1f} ms, run {info["run_ms"]:.1f} ms on the device')
     if snps is not None:        # read_snp_file's dict: the SNP association pass follows on the same preparation
         finish_scan_snps(scan, prefix, ids, pheno[0], names, y, snps, chrom_names, snp_grid, min_lod, lod_matrix, stage_times)
+    if mediate is not None:     # mediate_options' dict: the scan's peaks are mediated on the same preparation
+        finish_scan_mediation(scan, prefix, ids, pheno, names, y, dict(mediate, rankz=use_rankz), result, chrom_names, pos,
+                              lod_matrix, stage_times)
     return info
 
 
 def scan_tables(dosage_list, grid_file, pheno_file, covar_file=None, use_rankz=False, out=None, min_lod=None,
                 lod_matrix=False, device=0, scan_perms=None, scan_perm_seed=None, scan_perm_alpha=None,
-                scan_perm_chromosomes=None, scan_perm_pheno=None, stage_times=None, snp_file=None):
+                scan_perm_chromosomes=None, scan_perm_pheno=None, stage_times=None, snp_file=None, scan_mediate=False,
+                scan_mediate_min_lod=None, scan_mediate_top=None, scan_mediator_file=None):
     """`gbrs scan`: the cohort from dosage tables in `gbrs export` format (lines `id<TAB>dosage table`), rows in the grid
     file's order, without the HMM.  snp_file (`--snp-file`): the SNP association pass follows the scan (DESIGN.md §29);
-    the haplotypes of the patterns are those of the dosage tables' header."""
+    the haplotypes of the patterns are those of the dosage tables' header.  scan_mediate (`--scan-mediate`): the scan's
+    peaks are mediated by the phenotypes or by the table of scan_mediator_file."""
     from .hmm import _match_lines, read_dosage_table, read_snp_file
     from .postproc import read_grid
     if min_lod is not None and not min_lod >= 0.0:
         raise RuntimeError('--scan-min-lod must be a number that is not negative')
     perm = perm_options(scan_perms, scan_perm_seed, scan_perm_alpha, scan_perm_chromosomes, scan_perm_pheno)
+    mediate = mediate_options(scan_mediate, scan_mediate_min_lod, scan_mediate_top, scan_mediator_file)
     grid = read_grid(grid_file)
     chrom_names = list(grid)
     points = [len(grid[c]) for c in chrom_names]
@@ -620,6 +771,8 @@ def scan_tables(dosage_list, grid_file, pheno_file, covar_file=None, use_rankz=F
         entries.append((sample_id, path))
     pheno = read_scan_pheno(pheno_file)
     covar = read_scan_covar(covar_file) if covar_file is not None else None
+    if mediate is not None and mediate['mediator_file'] is not None:
+        mediate['table'] = read_scan_pheno(mediate['mediator_file'])      # refused before a dosage table is read
     if perm is not None:
         perm_plan(perm, pheno[0], [str(c) for c in chrom_names])          # refused before a dosage table is read
     kept, _, _, _ = scan_design([i for i, _ in entries], pheno, covar)
@@ -636,6 +789,6 @@ def scan_tables(dosage_list, grid_file, pheno_file, covar_file=None, use_rankz=F
         pos = np.concatenate([np.asarray(grid[c], dtype=np.float64) for c in chrom_names])
         return finish_scan(scan, out if out is not None else 'gbrs', [entries[k][0] for k in kept], pheno, covar, use_rankz,
                            chrom, pos, chrom_names, min_lod, lod_matrix, perm=perm, stage_times=stage_times, snps=snps,
-                           snp_grid=grid)
+                           snp_grid=grid, mediate=mediate)
     finally:
         scan.close()

@@ -1066,6 +1066,49 @@ typedef struct gbrs_scan_snp_info {
 } gbrs_scan_snp_info_t;
 int gbrs_scan_snp_info(gbrs_scan_t *scan, gbrs_scan_snp_info_t *info);
 
+/* Mediation of QTL peaks on the scan handle: for target t - a phenotype column y_t and a grid point
+ * m = point[t] in [0, M) - every mediator column z_q joins the covariates in turn and the LOD of y_t at m is formed again.
+ * A mediator whose inclusion makes the LOD collapse is a candidate for what lies between the locus and the target.  W_m of
+ * gbrs_scan_prepare serves every pair: no new factorisation.  No fused multiply-add anywhere.
+ *   y~_t, z~_q = v - qz qz' v as gbrs_scan_run forms y~ (the same kernel); a constant column goes in as zeros
+ *   s_yy = |y~_t|^2        s_zz = |z~_q|^2        s_yz = y~_t . z~_q
+ *   a = W_m y~_t           b = W_m z~_q
+ *   rss1 = s_yy - |a|^2                           lod0[t] = (n/2) log10(s_yy / rss1), gbrs_scan_run's formula and edge rules
+ *   e_zz = s_zz - |b|^2    e_yz = s_yz - a . b
+ *   rss0' = s_yy - s_yz^2 / s_zz                  (the target given covariates + mediator)
+ *   rss1' = rss1 - e_yz^2 / e_zz                  (given covariates + mediator + founders at m)
+ *   lod_med[t][q] = (n/2) log10(rss0' / rss1'), 0.0 where rss0' == 0, +inf where rss1' <= 0 < rss0'
+ * used[t][q] = 0 and lod_med[t][q] = NaN when s_zz == 0 (the mediator lies in the covariates' span), when
+ * e_zz <= 1e-10 s_zz (it lies in the span of covariates + founders at m: gbrs_scan_prepare's threshold) or when
+ * rss0' <= 1e-10 s_yy (the target lies in the span of covariates + mediator, as for q = the target itself).
+ * Per target over its used mediators only: n_used[t]; mean[t] and sd[t] of lod_med (two passes, n_used - 1 in the
+ * denominator, NaN below 2 used mediators; the order of the sums depends on Q alone); best_index[t][k], best_lod[t][k] for
+ * k < K <= 64: the K used mediators with the lowest lod_med in ascending (lod_med, mediator index) order, -1 / NaN in the
+ * places past n_used.
+ * target is double[n][T], point int64[T], mediator double[n][Q]; lod0 double[T], lod_med double[T][Q], used uint8[T][Q],
+ * best_lod double[T][K], best_index int64[T][K], mean, sd double[T], n_used int64[T]; lod0, lod_med, used, mean, sd and
+ * n_used are nullable, best_* with K = 0.  The projected mediators stay on the device as [Q][n_ld]; the targets pass in
+ * chunks of 512, whose [512][Q] LODs live on the device only unless lod_med / used ask for them, so device memory is
+ * bounded for any T.  The sums over the samples of a and of the projections are one wavefront's in gbrs_scan_prepare's
+ * order; b, a . b and s_yz come from one f64 MFMA product of the gathered W rows with the mediators, each a fixed chain.
+ * The numbers of a pair are the same bits alone or among others, at any target and mediator position, in any chunk, for
+ * any K and however the cohort was appended.  GBRS_ERR_INVALID before gbrs_scan_prepare, for T < 1, Q < 1, K < 0 or
+ * K > 64, a point outside [0, M), n <= c + H (the mediator takes one more degree of freedom than the scan) and a value
+ * that is not finite (the message names the entry); the outputs are untouched on such a failure.  The call allocates and
+ * frees its own buffers: what the handle holds, gbrs_scan_run's bits and gbrs_scan_info_t are as before.  No mixed model,
+ * no more than one mediator at a time, no mediation at SNPs. */
+int gbrs_scan_mediate(gbrs_scan_t *scan, int64_t T, const double *target, const int64_t *point, int64_t Q,
+                      const double *mediator, int K, double *lod0, double *lod_med, uint8_t *used, double *best_lod,
+                      int64_t *best_index, double *mean, double *sd, int64_t *n_used);
+
+typedef struct gbrs_scan_mediate_info {
+    int64_t  T, Q;               /* of the last gbrs_scan_mediate (0: none yet)                                  */
+    double   last_pass_ms;       /* device time of the pass: uploads, projections, all chunks, copies            */
+    double   last_product_ms;    /* of that, the product kernel alone, summed over the target chunks             */
+    uint64_t peak_device_bytes;  /* what the handle held during the pass, the call's own buffers included        */
+} gbrs_scan_mediate_info_t;
+int gbrs_scan_mediate_info(gbrs_scan_t *scan, gbrs_scan_mediate_info_t *info);
+
 /* ------------------------------------------------------------------------------------------
  * Report text (host side, no device work): the `locus <haplotypes> total [notes]` tables of
  * EMfactory.report_read_counts / report_depths (emase/EMfactory.py:289-380).

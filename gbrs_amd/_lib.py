@@ -39,6 +39,7 @@ EXPORTS = [
     "gbrs_scan_info", "gbrs_scan_permute", "gbrs_scan_perm_info",
     "gbrs_scan_set_snps", "gbrs_scan_snp_dosage", "gbrs_scan_snps", "gbrs_scan_snp_info",
     "gbrs_scan_mediate", "gbrs_scan_mediate_info",
+    "gbrs_scan_effects", "gbrs_scan_effects_info", "gbrs_scan_run_support",
     "gbrs_compress_create", "gbrs_compress_get", "gbrs_compress_destroy",
     "gbrs_bam_open", "gbrs_bam_references", "gbrs_bam_set_reference_map", "gbrs_bam_convert", "gbrs_bam_get",
     "gbrs_bam_scan_records", "gbrs_bam_destroy",
@@ -132,6 +133,12 @@ class ScanMediateInfo(C.Structure):
     _fields_ = [
         ("T", C.c_int64), ("Q", C.c_int64), ("last_pass_ms", C.c_double), ("last_product_ms", C.c_double),
         ("peak_device_bytes", C.c_uint64),
+    ]
+
+
+class ScanEffectsInfo(C.Structure):
+    _fields_ = [
+        ("T", C.c_int64), ("P", C.c_int64), ("last_pass_ms", C.c_double), ("peak_device_bytes", C.c_uint64),
     ]
 
 
@@ -251,6 +258,9 @@ def load():
         "gbrs_scan_snp_info": [vp, C.POINTER(ScanSnpInfo)],
         "gbrs_scan_mediate": [vp, i64, vp, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp],
         "gbrs_scan_mediate_info": [vp, C.POINTER(ScanMediateInfo)],
+        "gbrs_scan_effects": [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp],
+        "gbrs_scan_effects_info": [vp, C.POINTER(ScanEffectsInfo)],
+        "gbrs_scan_run_support": [vp, i64, vp, dbl, vp, vp, vp, vp, vp],
         "gbrs_compress_create": [u64, u32, u32, pp, pp, vp, i32, pp, C.POINTER(u64), vp],
         "gbrs_compress_get": [vp, pp, pp, vp],
         "gbrs_compress_destroy": [vp],

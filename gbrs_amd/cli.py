@@ -324,6 +324,18 @@ def _scan_options(parser, covar=True):
     parser.add_argument('--scan-mediator-file', type=_existing, default=None, metavar='FILE',
                         help='with --scan-mediate: the mediators, a table in the phenotypes\' format with the same ids '
                              '(default: the phenotypes themselves); --scan-rankz applies to it too')
+    parser.add_argument('--scan-lod-drop', type=float, default=None, metavar='X',
+                        help='LOD support intervals on the device: for every peak the nearest grid points on either side whose '
+                             'LOD is at most the peak\'s minus X (the chromosome\'s ends where there is none; 1.5 is the usual '
+                             'choice).  <PREFIX>.scan.npz gains support_lo, support_hi and lod_drop, the peaks file the '
+                             'columns support_lo and support_hi')
+    parser.add_argument('--scan-effects', action='store_true',
+                        help='founder effects on the device: for every (phenotype, chromosome) peak of the scan the zero-sum '
+                             'effects of all founders and their standard errors.  Writes <PREFIX>.scan.effects.npz and '
+                             '<PREFIX>.scan.effects.tsv.  No mixed model, no BLUP shrinkage')
+    parser.add_argument('--scan-effects-min-lod', type=float, default=None, metavar='X',
+                        help='with --scan-effects: the peaks of at least this LOD get their effects (default: 6.0, as '
+                             '--scan-mediate-min-lod)')
 
 
 def main(argv=None) -> int:
@@ -451,7 +463,8 @@ def main(argv=None) -> int:
                         scan_perm_chromosomes=args.scan_perm_chromosomes, scan_perm_pheno=args.scan_perm_pheno,
                         stage_times=stages, snp_file=args.snp_file, scan_mediate=args.scan_mediate,
                         scan_mediate_min_lod=args.scan_mediate_min_lod, scan_mediate_top=args.scan_mediate_top,
-                        scan_mediator_file=args.scan_mediator_file)
+                        scan_mediator_file=args.scan_mediator_file, scan_effects=args.scan_effects,
+                        scan_effects_min_lod=args.scan_effects_min_lod, scan_lod_drop=args.scan_lod_drop)
         elif args.command == 'interpolate':
             from .postproc import interpolate
             interpolate(genoprob_file=args.genoprob_file, grid_file=args.grid_file, gpos_file=args.gpos_file,

@@ -13,7 +13,10 @@
 // scan_snp.inc): a row kernel builds one normalised row per founder SNP from two grid points and a bit pattern, and a
 // sibling of the product kernel with one row per SNP turns the rows into LODs.  Mediation (kernels and the
 // rule in scan_mediate.inc): a sibling of the product kernel gathers the W rows of each target's point, multiplies them
-// with the projected mediators and applies the conditional regression's rule in its epilogue.
+// with the projected mediators and applies the conditional regression's rule in its epilogue.  Founder effects and LOD
+// support intervals (kernels and the rules in scan_effects.inc): one workgroup per peak forms the founder
+// effects and their standard errors from W_m and the point's dosage columns, and one wavefront per (chromosome,
+// phenotype) walks outward from the peak over the chunk's LOD rows while they are on the device.
 #include "common.h"
 #include "scan_hmm.h"
 
@@ -321,6 +324,10 @@ scan_peak_kernel(int64_t M, int n_chrom, const int64_t *__restrict__ point_off, 
 
 #include "scan_mediate.inc"
 
+// ---- founder effects and support intervals -------------------------------------------------------------------------------------
+
+#include "scan_effects.inc"
+
 }  // namespace gbrs
 
 using namespace gbrs;
@@ -367,6 +374,10 @@ struct gbrs_scan {
     int64_t med_T = 0, med_Q = 0;
     double t_med_pass = 0, t_med_product = 0;
     uint64_t med_peak_bytes = 0;
+    // the last gbrs_scan_effects: its buffers are the call's own, as gbrs_scan_permute's
+    int64_t eff_T = 0, eff_P = 0;
+    double t_eff_pass = 0;
+    uint64_t eff_peak_bytes = 0;
     uint64_t snp_bytes() const {
         return d_snp_off.bytes() + snp_lo.bytes() + snp_hi.bytes() + snp_mask.bytes() + snp_t.bytes();
     }
@@ -567,11 +578,19 @@ int gbrs_scan_prepare(gbrs_scan_t *s, int c, const double *qz) {
     return GBRS_OK;
 }
 
-int gbrs_scan_run(gbrs_scan_t *s, int64_t P, const double *pheno, double *lod, double *peak_lod, int64_t *peak_index) {
-    RoctxRange roctx_range("gbrs_scan_run");
+}  // extern "C"
+
+namespace {
+
+// The pass of gbrs_scan_run.  With support, gbrs_scan_run_support's: the intervals of every chunk follow its peaks while
+// its LOD rows are on the device; the two tables of a chunk are the call's own, so the handle holds what it held.
+int scan_run_pass(gbrs_scan *s, int64_t P, const double *pheno, bool support, double drop, double *lod, double *peak_lod,
+                  int64_t *peak_index, int64_t *support_lo, int64_t *support_hi) {
     if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
     if (s->c == 0) return fail(GBRS_ERR_INVALID, "no covariates on the handle: call gbrs_scan_prepare first");
     if (P < 1 || !pheno) return fail(GBRS_ERR_INVALID, "bad argument");
+    if (support && !(drop >= 0.0 && std::isfinite(drop)))
+        return fail(GBRS_ERR_INVALID, "the LOD drop of a support interval must be a finite number that is not negative, got %g", drop);
     const int n = (int)s->n;
     for (int64_t k = 0; k < (int64_t)n * P; ++k)
         if (!std::isfinite(pheno[k]))
@@ -585,6 +604,11 @@ int gbrs_scan_run(gbrs_scan_t *s, int64_t P, const double *pheno, double *lod, d
     if (s->lod.n != (size_t)pc_max * M) GBRS_TRY(s->lod.alloc((size_t)pc_max * M));
     if (s->peak_lod.n != (size_t)pc_max * s->n_chrom) GBRS_TRY(s->peak_lod.alloc((size_t)pc_max * s->n_chrom));
     if (s->peak_index.n != (size_t)pc_max * s->n_chrom) GBRS_TRY(s->peak_index.alloc((size_t)pc_max * s->n_chrom));
+    DevBuf<int64_t> d_lo, d_hi;
+    if (support) {
+        GBRS_TRY(d_lo.alloc((size_t)pc_max * s->n_chrom));
+        GBRS_TRY(d_hi.alloc((size_t)pc_max * s->n_chrom));
+    }
     const unsigned row_blocks = (unsigned)((M * s->Hp + SC_ROWS - 1) / SC_ROWS);
     double t_product = 0.0;
     GBRS_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
@@ -604,6 +628,9 @@ int gbrs_scan_run(gbrs_scan_t *s, int64_t P, const double *pheno, double *lod, d
         GBRS_HIP_CHECK(hipEventRecord(s->ev[3], s->stream));
         hipLaunchKernelGGL(scan_peak_kernel, dim3((unsigned)s->n_chrom, (unsigned)pc), dim3(64), 0, s->stream, M, s->n_chrom,
                            s->d_point_off.p, s->lod.p, s->peak_lod.p, s->peak_index.p);
+        if (support)
+            hipLaunchKernelGGL(scan_support_kernel, dim3((unsigned)s->n_chrom, (unsigned)pc), dim3(64), 0, s->stream, M, s->n_chrom,
+                               drop, s->d_point_off.p, s->lod.p, s->peak_lod.p, s->peak_index.p, d_lo.p, d_hi.p);
         GBRS_HIP_CHECK(hipGetLastError());
         GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
         float ms = 0.f;
@@ -613,6 +640,10 @@ int gbrs_scan_run(gbrs_scan_t *s, int64_t P, const double *pheno, double *lod, d
             GBRS_HIP_CHECK(hipMemcpy(peak_lod + p0 * s->n_chrom, s->peak_lod.p, (size_t)pc * s->n_chrom * sizeof(double), hipMemcpyDeviceToHost));
         if (peak_index)
             GBRS_HIP_CHECK(hipMemcpy(peak_index + p0 * s->n_chrom, s->peak_index.p, (size_t)pc * s->n_chrom * sizeof(int64_t), hipMemcpyDeviceToHost));
+        if (support_lo)
+            GBRS_HIP_CHECK(hipMemcpy(support_lo + p0 * s->n_chrom, d_lo.p, (size_t)pc * s->n_chrom * sizeof(int64_t), hipMemcpyDeviceToHost));
+        if (support_hi)
+            GBRS_HIP_CHECK(hipMemcpy(support_hi + p0 * s->n_chrom, d_hi.p, (size_t)pc * s->n_chrom * sizeof(int64_t), hipMemcpyDeviceToHost));
     }
     GBRS_HIP_CHECK(hipEventRecord(s->ev[1], s->stream));
     GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
@@ -620,6 +651,21 @@ int gbrs_scan_run(gbrs_scan_t *s, int64_t P, const double *pheno, double *lod, d
     if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) s->t_run = ms;
     s->t_product = t_product;
     return GBRS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gbrs_scan_run(gbrs_scan_t *s, int64_t P, const double *pheno, double *lod, double *peak_lod, int64_t *peak_index) {
+    RoctxRange roctx_range("gbrs_scan_run");
+    return scan_run_pass(s, P, pheno, false, 0.0, lod, peak_lod, peak_index, nullptr, nullptr);
+}
+
+int gbrs_scan_run_support(gbrs_scan_t *s, int64_t P, const double *pheno, double drop, double *lod, double *peak_lod,
+                          int64_t *peak_index, int64_t *support_lo, int64_t *support_hi) {
+    RoctxRange roctx_range("gbrs_scan_run_support");
+    return scan_run_pass(s, P, pheno, true, drop, lod, peak_lod, peak_index, support_lo, support_hi);
 }
 
 int gbrs_scan_permute(gbrs_scan_t *s, int64_t P, const double *pheno, int64_t B, uint64_t seed, const uint8_t *chrom_mask,
@@ -1077,6 +1123,104 @@ int gbrs_scan_mediate_info(gbrs_scan_t *s, gbrs_scan_mediate_info_t *info) {
     info->last_pass_ms = s->t_med_pass;
     info->last_product_ms = s->t_med_product;
     info->peak_device_bytes = s->med_peak_bytes;
+    return GBRS_OK;
+}
+
+int gbrs_scan_effects(gbrs_scan_t *s, int64_t P, const double *pheno, int64_t T, const int64_t *column, const int64_t *point,
+                      double *effect, double *se, double *lod, double *sigma2, int32_t *rank) {
+    RoctxRange roctx_range("gbrs_scan_effects");
+    if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (s->c == 0) return fail(GBRS_ERR_INVALID, "no covariates on the handle: call gbrs_scan_prepare first");
+    if (P < 1) return fail(GBRS_ERR_INVALID, "an effects pass needs at least 1 phenotype, got %lld", (long long)P);
+    if (T < 1) return fail(GBRS_ERR_INVALID, "an effects pass needs at least 1 target, got %lld", (long long)T);
+    if (!pheno || !column || !point) return fail(GBRS_ERR_INVALID, "bad argument");
+    for (int64_t t = 0; t < T; ++t) {
+        if (column[t] < 0 || column[t] >= P)
+            return fail(GBRS_ERR_INVALID, "target %lld is phenotype column %lld: the table has the columns 0 .. %lld", (long long)t,
+                        (long long)column[t], (long long)(P - 1));
+        if (point[t] < 0 || point[t] >= s->M)
+            return fail(GBRS_ERR_INVALID, "target %lld is at grid point %lld: the handle has the points 0 .. %lld", (long long)t,
+                        (long long)point[t], (long long)(s->M - 1));
+    }
+    const int n = (int)s->n;
+    for (int64_t k = 0; k < (int64_t)n * P; ++k)
+        if (!std::isfinite(pheno[k]))
+            return fail(GBRS_ERR_INVALID, "phenotype %lld holds a value that is not finite (sample %lld)", (long long)(k % P),
+                        (long long)(k / P));
+    GBRS_TRY(select_device(s->device));
+    const int64_t n_ld = s->n_ld, tc_max = std::min(T, SE_TCHUNK), yc_max = std::min(P, SC_PCHUNK);
+    const int H = s->H, Hp = s->Hp;
+    DevBuf<double> y, yt_all, rss_all, x, d_effect, d_se, d_lod, d_sigma2;
+    DevBuf<int64_t> d_column, d_point;
+    DevBuf<int32_t> d_rank;
+    GBRS_TRY(y.alloc((size_t)n * yc_max));
+    GBRS_TRY(yt_all.alloc((size_t)P * n_ld));
+    GBRS_TRY(rss_all.alloc((size_t)P));
+    GBRS_TRY(x.alloc((size_t)tc_max * Hp * n_ld));
+    GBRS_TRY(d_effect.alloc((size_t)tc_max * H));
+    GBRS_TRY(d_se.alloc((size_t)tc_max * H));
+    GBRS_TRY(d_lod.alloc((size_t)tc_max));
+    GBRS_TRY(d_sigma2.alloc((size_t)tc_max));
+    GBRS_TRY(d_column.alloc((size_t)tc_max));
+    GBRS_TRY(d_point.alloc((size_t)tc_max));
+    GBRS_TRY(d_rank.alloc((size_t)tc_max));
+    GBRS_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
+    // y~ of every phenotype, by gbrs_scan_run's kernel in gbrs_scan_run's chunks; it stays on the device for the pass
+    for (int64_t p0 = 0; p0 < P; p0 += SC_PCHUNK) {
+        const int64_t pc = std::min(SC_PCHUNK, P - p0);
+        GBRS_HIP_CHECK(hipMemcpy2DAsync(y.p, (size_t)pc * sizeof(double), pheno + p0, (size_t)P * sizeof(double),
+                                        (size_t)pc * sizeof(double), (size_t)n, hipMemcpyHostToDevice, s->stream));
+        hipLaunchKernelGGL(scan_pheno_kernel, dim3((unsigned)pc), dim3(64), 0, s->stream, n, s->c, n_ld, pc, y.p, s->qz.p,
+                           yt_all.p + p0 * n_ld, rss_all.p + p0);
+        GBRS_HIP_CHECK(hipGetLastError());
+    }
+    // the results of a chunk come to the host before the next chunk's kernel overwrites them: the stream orders the two
+    std::vector<double> h_effect(effect ? (size_t)T * H : 0), h_se(se ? (size_t)T * H : 0), h_lod(lod ? (size_t)T : 0),
+        h_sigma2(sigma2 ? (size_t)T : 0);
+    std::vector<int32_t> h_rank(rank ? (size_t)T : 0);
+    for (int64_t t0 = 0; t0 < T; t0 += SE_TCHUNK) {
+        const int64_t tc = std::min(SE_TCHUNK, T - t0);
+        GBRS_HIP_CHECK(hipMemcpyAsync(d_column.p, column + t0, (size_t)tc * sizeof(int64_t), hipMemcpyHostToDevice, s->stream));
+        GBRS_HIP_CHECK(hipMemcpyAsync(d_point.p, point + t0, (size_t)tc * sizeof(int64_t), hipMemcpyHostToDevice, s->stream));
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)tc), dim3(SC_THREADS), 0, s->stream, n, s->M, H, s->c, n_ld, 0.5 * n, s->dosage.p,
+                               s->qz.p, s->W.p, s->d_rank.p, d_column.p, d_point.p, yt_all.p, rss_all.p, x.p, d_effect.p, d_se.p,
+                               d_lod.p, d_sigma2.p, d_rank.p);
+        };
+        if (Hp == 8) launch(scan_effects_kernel<8>);
+        else launch(scan_effects_kernel<16>);
+        GBRS_HIP_CHECK(hipGetLastError());
+        if (effect) GBRS_HIP_CHECK(hipMemcpyAsync(h_effect.data() + t0 * H, d_effect.p, (size_t)tc * H * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        if (se) GBRS_HIP_CHECK(hipMemcpyAsync(h_se.data() + t0 * H, d_se.p, (size_t)tc * H * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        if (lod) GBRS_HIP_CHECK(hipMemcpyAsync(h_lod.data() + t0, d_lod.p, (size_t)tc * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        if (sigma2) GBRS_HIP_CHECK(hipMemcpyAsync(h_sigma2.data() + t0, d_sigma2.p, (size_t)tc * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        if (rank) GBRS_HIP_CHECK(hipMemcpyAsync(h_rank.data() + t0, d_rank.p, (size_t)tc * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+    }
+    GBRS_HIP_CHECK(hipEventRecord(s->ev[1], s->stream));
+    GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
+    // the caller's arrays are written once the whole pass has succeeded
+    if (effect) std::memcpy(effect, h_effect.data(), h_effect.size() * sizeof(double));
+    if (se) std::memcpy(se, h_se.data(), h_se.size() * sizeof(double));
+    if (lod) std::memcpy(lod, h_lod.data(), h_lod.size() * sizeof(double));
+    if (sigma2) std::memcpy(sigma2, h_sigma2.data(), h_sigma2.size() * sizeof(double));
+    if (rank) std::memcpy(rank, h_rank.data(), h_rank.size() * sizeof(int32_t));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) s->t_eff_pass = ms;
+    s->eff_T = T;
+    s->eff_P = P;
+    s->eff_peak_bytes = s->d_point_off.bytes() + s->dosage.bytes() + s->qz.bytes() + s->W.bytes() + s->d_rank.bytes() + s->y.bytes() +
+                        s->yt.bytes() + s->rss0.bytes() + s->lod.bytes() + s->peak_lod.bytes() + s->peak_index.bytes() + s->snp_bytes() +
+                        y.bytes() + yt_all.bytes() + rss_all.bytes() + x.bytes() + d_effect.bytes() + d_se.bytes() + d_lod.bytes() +
+                        d_sigma2.bytes() + d_column.bytes() + d_point.bytes() + d_rank.bytes();
+    return GBRS_OK;
+}
+
+int gbrs_scan_effects_info(gbrs_scan_t *s, gbrs_scan_effects_info_t *info) {
+    if (!s || !info) return fail(GBRS_ERR_INVALID, "bad argument");
+    info->T = s->eff_T;
+    info->P = s->eff_P;
+    info->last_pass_ms = s->t_eff_pass;
+    info->peak_device_bytes = s->eff_peak_bytes;
     return GBRS_OK;
 }
 

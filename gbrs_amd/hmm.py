@@ -1400,7 +1400,10 @@ class ReconstructOptions:
     degree of freedom on the prepared cohort, and `<scan_out>.scan.snps.npz` and `<scan_out>.scan.snps.peaks.tsv` are written.
     `scan_mediate`: the scan's peaks are mediated by the phenotypes, or by the table of `scan_mediator_file`,
     and `<scan_out>.scan.mediation.npz` and `<scan_out>.scan.mediation.tsv` are written; `scan_mediate_min_lod` and
-    `scan_mediate_top` are scan.mediate_options'."""
+    `scan_mediate_top` are scan.mediate_options'.
+    `scan_effects`, `scan_lod_drop`: the founder effects of the scan's peaks of at least
+    `scan_effects_min_lod` go to `<scan_out>.scan.effects.npz` and `<scan_out>.scan.effects.tsv`, named by the samples'
+    haplotype header; the peaks' LOD support intervals join the scan's two files (scan.effects_options)."""
     expr_threshold: float = 1.5
     sigma: float = 0.12
     grid_genoprobs: bool = False
@@ -1436,6 +1439,9 @@ class ReconstructOptions:
     scan_mediate_min_lod: float = None
     scan_mediate_top: int = None
     scan_mediator_file: str = None
+    scan_effects: bool = False
+    scan_effects_min_lod: float = None
+    scan_lod_drop: float = None
 
     @classmethod
     def of(cls, keywords):
@@ -1465,7 +1471,9 @@ class ReconstructOptions:
                         scan_perm_seed=self.scan_perm_seed, scan_perm_alpha=self.scan_perm_alpha,
                         scan_perm_chromosomes=self.scan_perm_chromosomes, scan_perm_pheno=self.scan_perm_pheno,
                         scan_mediate=self.scan_mediate, scan_mediate_min_lod=self.scan_mediate_min_lod,
-                        scan_mediate_top=self.scan_mediate_top, scan_mediator_file=self.scan_mediator_file)
+                        scan_mediate_top=self.scan_mediate_top, scan_mediator_file=self.scan_mediator_file,
+                        scan_effects=self.scan_effects, scan_effects_min_lod=self.scan_effects_min_lod,
+                        scan_lod_drop=self.scan_lod_drop)
         check_scan_snp_args(self.scan_snps, self.snp_file, self.scan_pheno, grid_file, cohort=cohort)
 
 
@@ -1752,19 +1760,22 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
                      scan_out: str = None, scan_min_lod: float = None, scan_lod_matrix: bool = False,
                      scan_perms: int = None, scan_perm_seed: int = None, scan_perm_alpha=None, scan_perm_chromosomes=None,
                      scan_perm_pheno: str = None, scan_snps: bool = False, scan_mediate: bool = False,
-                     scan_mediate_min_lod: float = None, scan_mediate_top: int = None, scan_mediator_file: str = None) -> list:
+                     scan_mediate_min_lod: float = None, scan_mediate_top: int = None, scan_mediator_file: str = None,
+                     scan_effects: bool = False, scan_effects_min_lod: float = None, scan_lod_drop: float = None) -> list:
     """`gbrs reconstruct` for a cohort whose genes.tpm files exist (extension): one context, the tables on the device
     once, the samples through the HMM in launches of up to `batch_size`, and every pass the options ask for once per
     launch.  Every sample gets the files the single-sample call writes for its outbase.  All samples must carry the same
     haplotype header (RuntimeError before anything runs otherwise).  A sample whose file cannot be read or lacks a gene
     is logged and left out, and the others go on.  Returns one dict per sample: its outbase and, if it failed,
     `error`.  `stage_times`, `context` and `grid_file` as in reconstruct; every other keyword from `expr_threshold` on is
-    described on ReconstructOptions (DESIGN.md §21-§30), with what it means for a cohort."""
+    described on ReconstructOptions (DESIGN.md §21-§31), with what it means for a cohort."""
     options = ReconstructOptions.of(locals())
     options.check(True, grid_file if context is None else context.grid_file, tprob_file)
     from . import scan as scan_mod
     scan_perm = scan_mod.perm_options(scan_perms, scan_perm_seed, scan_perm_alpha, scan_perm_chromosomes, scan_perm_pheno)
     scan_med = scan_mod.mediate_options(scan_mediate, scan_mediate_min_lod, scan_mediate_top, scan_mediator_file)
+    scan_eff = scan_mod.effects_options(scan_effects, scan_effects_min_lod, scan_lod_drop)
+    with_effects = scan_eff is not None and scan_eff['min_lod'] is not None
     clock = time.perf_counter
     marks = stage_times if stage_times is not None else {}
     if len(expression_files) != len(outbases):
@@ -1817,7 +1828,8 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
     for key in ('read', 'hmm', 'grid', 'save') + (('loglik',) if options.loglik else ()) + \
             (('match',) if match_panel is not None else ()) + (('snp',) if snp_file is not None else ()) + \
             (('scan',) if scan_pheno is not None else ()) + (('scan_perm',) if scan_perm is not None else ()) + \
-            (('scan_snps',) if scan_snps else ()) + (('mediate',) if scan_med is not None else ()):
+            (('scan_snps',) if scan_snps else ()) + (('mediate',) if scan_med is not None else ()) + \
+            (('effects',) if with_effects else ()):
         marks[key] = 0.0
     from concurrent.futures import ThreadPoolExecutor
     writers = ThreadPoolExecutor(max_workers=min(16, batch_size))
@@ -1915,9 +1927,11 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
                                  scan_rankz, np.concatenate([[c] * m for _, m, c in slices]),
                                  np.concatenate([np.asarray(ctx.grid[c], dtype=np.float64) for _, _, c in slices]),
                                  list(ctx.chroms), scan_min_lod, scan_lod_matrix, perm=scan_perm, stage_times=marks,
-                                 snps=shared.snps if scan_snps else None, snp_grid=ctx.grid, mediate=scan_med)
+                                 snps=shared.snps if scan_snps else None, snp_grid=ctx.grid, mediate=scan_med,
+                                 effects=scan_eff, founders=haplotypes)
             marks['scan'] += clock() - t0 - (marks['scan_perm'] if scan_perm is not None else 0.0) - \
-                (marks['scan_snps'] if scan_snps else 0.0) - (marks['mediate'] if scan_med is not None else 0.0)
+                (marks['scan_snps'] if scan_snps else 0.0) - (marks['mediate'] if scan_med is not None else 0.0) - \
+                (marks['effects'] if with_effects else 0.0)
     finally:
         writers.shutdown(wait=True)
         if scan is not None:

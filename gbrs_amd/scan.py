@@ -2,7 +2,9 @@
 `gbrs scan`.  Haley-Knott regression with additive covariates on the device (gbrs_scan_*, gbrs_amd/csrc/scan.hip); the
 host side here is the covariates' QR, the file readers and the writers.  No mixed model.  `--scan-snps` / `gbrs scan
 --snp-file`: the 1-df test of founder SNPs on the same prepared cohort (gbrs_scan_set_snps, gbrs_scan_snps).
-`--scan-mediate`: the scan's peaks conditioned on every other phenotype in turn (gbrs_scan_mediate)."""
+`--scan-mediate`: the scan's peaks conditioned on every other phenotype in turn (gbrs_scan_mediate).
+`--scan-effects`, `--scan-lod-drop`: the founder effects at the scan's peaks with their standard errors
+(gbrs_scan_effects) and the peaks' LOD support intervals (gbrs_scan_run_support)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -20,13 +22,15 @@ DEFAULT_PERM_ALPHA = (0.05, 0.1)  # the levels of --scan-perm-alpha
 DEFAULT_MEDIATE_MIN_LOD = 6.0     # --scan-mediate-min-lod: the peaks that are mediated; a convention, not a threshold
 DEFAULT_MEDIATE_TOP = 5           # --scan-mediate-top: the mediators listed per peak
 MEDIATE_MAX_TOP = 64              # the places gbrs_scan_mediate's top list has
+DEFAULT_EFFECTS_MIN_LOD = DEFAULT_MEDIATE_MIN_LOD     # --scan-effects-min-lod: the peaks whose founder effects are formed
 
 
 class GenomeScan:
     """Device handle of one cohort on one grid.  append / append_from collect the samples' grid dosages in order,
     prepare(covariates) builds the phenotype-independent part once, run(pheno) scans any number of phenotypes;
     set_snps + run_snps(pheno) test founder SNPs with one degree of freedom on the same cohort (DESIGN.md §29);
-    mediate(target, point, mediator) conditions peaks on mediators."""
+    mediate(target, point, mediator) conditions peaks on mediators; effects(pheno, column, point) gives
+    the founder effects at chosen points and run(pheno, lod_drop=d) the peaks' LOD support intervals."""
 
     def __init__(self, num_haps, points_per_chrom, device=0):
         self.H = int(num_haps)
@@ -76,10 +80,13 @@ class GenomeScan:
         _lib.check(_lib.load().gbrs_scan_prepare(self._h, qz.shape[1], _lib.ptr(qz)))
         self.prepared = True
 
-    def run(self, pheno, want_lod=True):
+    def run(self, pheno, want_lod=True, lod_drop=None):
         """pheno: [n, P] (or [n]).  Returns `peak_lod` [P, n_chrom], `peak_index` [P, n_chrom] and, with want_lod, `lod`
         [P, M].  A column whose values are all equal lies in the intercept's span: it goes to the device as zeros, so its
-        rss0 is exactly 0 and its LODs are 0.0 whatever the rounding of the projection."""
+        rss0 is exactly 0 and its LODs are 0.0 whatever the rounding of the projection.  With lod_drop (a number that is
+        not negative) the same pass also returns `support_lo` and `support_hi` [P, n_chrom]: the nearest
+        grid points on either side of a peak whose LOD is at most the peak's minus lod_drop, the chromosome's ends where
+        there is none, -1 for a chromosome without points."""
         y = np.array(pheno, dtype=np.float64, order='C')
         if y.ndim == 1:
             y = y[:, None]
@@ -90,8 +97,14 @@ class GenomeScan:
         P, nc = y.shape[1], len(self.points)
         lod = np.empty((P, self.M)) if want_lod else None
         peak, index = np.empty((P, nc)), np.empty((P, nc), dtype=np.int64)
-        _lib.check(_lib.load().gbrs_scan_run(self._h, P, _lib.ptr(y), _lib.ptr(lod), _lib.ptr(peak), _lib.ptr(index)))
-        out = {'peak_lod': peak, 'peak_index': index}
+        if lod_drop is None:
+            _lib.check(_lib.load().gbrs_scan_run(self._h, P, _lib.ptr(y), _lib.ptr(lod), _lib.ptr(peak), _lib.ptr(index)))
+            out = {'peak_lod': peak, 'peak_index': index}
+        else:
+            lo, hi = np.empty((P, nc), dtype=np.int64), np.empty((P, nc), dtype=np.int64)
+            _lib.check(_lib.load().gbrs_scan_run_support(self._h, P, _lib.ptr(y), float(lod_drop), _lib.ptr(lod), _lib.ptr(peak),
+                                                         _lib.ptr(index), _lib.ptr(lo), _lib.ptr(hi)))
+            out = {'peak_lod': peak, 'peak_index': index, 'support_lo': lo, 'support_hi': hi}
         if want_lod:
             out['lod'] = lod
         return out
@@ -231,6 +244,34 @@ class GenomeScan:
         _lib.check(_lib.load().gbrs_scan_mediate_info(self._h, C.byref(raw)))
         return {'T': raw.T, 'Q': raw.Q, 'pass_ms': raw.last_pass_ms, 'product_ms': raw.last_product_ms,
                 'peak_device_bytes': raw.peak_device_bytes}
+
+    def effects(self, pheno, column, point):
+        """Founder effects at chosen points of the prepared cohort.  pheno: [n, P] (or [n]), with run()'s
+        constant-column-to-zeros step; column: [T] phenotype columns; point: [T] grid point indices (a column's peak).
+        Returns `effect` and `se` [T, H] - the zero-sum effects of all H founders and their standard errors -, `lod` [T]
+        (within rounding of run()'s LOD at the point), `sigma2` [T] (the residual variance) and `rank` [T]."""
+        y = np.array(pheno, dtype=np.float64, order='C')
+        if y.ndim == 1:
+            y = y[:, None]
+        if y.ndim != 2 or y.shape[0] != self.n:
+            raise ValueError(f'phenotypes have shape {np.shape(pheno)} for {self.n} samples')
+        if self.n:
+            y[:, (y == y[0]).all(axis=0)] = 0.0
+        col = np.ascontiguousarray(np.atleast_1d(column), dtype=np.int64)
+        at = np.ascontiguousarray(np.atleast_1d(point), dtype=np.int64)
+        if col.ndim != 1 or at.shape != col.shape:
+            raise ValueError(f'{col.shape} phenotype columns and {at.shape} grid points')
+        P, T = y.shape[1], len(col)
+        effect, se = np.empty((T, self.H)), np.empty((T, self.H))
+        lod, sigma2, rank = np.empty(T), np.empty(T), np.empty(T, dtype=np.int32)
+        _lib.check(_lib.load().gbrs_scan_effects(self._h, P, _lib.ptr(y), T, _lib.ptr(col), _lib.ptr(at), _lib.ptr(effect),
+                                                 _lib.ptr(se), _lib.ptr(lod), _lib.ptr(sigma2), _lib.ptr(rank)))
+        return {'effect': effect, 'se': se, 'lod': lod, 'sigma2': sigma2, 'rank': rank}
+
+    def effects_info(self):
+        raw = _lib.ScanEffectsInfo()
+        _lib.check(_lib.load().gbrs_scan_effects_info(self._h, C.byref(raw)))
+        return {'T': raw.T, 'P': raw.P, 'pass_ms': raw.last_pass_ms, 'peak_device_bytes': raw.peak_device_bytes}
 
     def info(self):
         raw = _lib.ScanInfo()
@@ -398,12 +439,35 @@ def mediate_options(scan_mediate=False, scan_mediate_min_lod=None, scan_mediate_
     return {'min_lod': min_lod, 'top': int(top), 'mediator_file': scan_mediator_file}
 
 
+def effects_options(scan_effects=False, scan_effects_min_lod=None, scan_lod_drop=None):
+    """`--scan-effects [--scan-effects-min-lod X]` and `--scan-lod-drop X` as one dict `{'min_lod': X or None without
+    --scan-effects, 'lod_drop': X or None}`, or None with neither; `--scan-effects-min-lod` alone is refused.  Refused
+    before a file is read."""
+    if not scan_effects and scan_effects_min_lod is not None:
+        raise RuntimeError('--scan-effects-min-lod needs --scan-effects')
+    min_lod = None
+    if scan_effects:
+        min_lod = DEFAULT_EFFECTS_MIN_LOD if scan_effects_min_lod is None else float(scan_effects_min_lod)
+        if not min_lod >= 0.0:
+            raise RuntimeError(f'--scan-effects-min-lod must be a number that is not negative, got {scan_effects_min_lod}')
+    drop = None
+    if scan_lod_drop is not None:
+        drop = float(scan_lod_drop)
+        if not (drop >= 0.0 and np.isfinite(drop)):
+            raise RuntimeError(f'--scan-lod-drop must be a finite number that is not negative, got {scan_lod_drop}')
+    if min_lod is None and drop is None:
+        return None
+    return {'min_lod': min_lod, 'lod_drop': drop}
+
+
 def check_scan_args(scan_pheno=None, scan_covar=None, scan_rankz=False, scan_out=None, scan_min_lod=None,
                     scan_lod_matrix=False, grid_file=None, cohort=False, scan_perms=None, scan_perm_seed=None,
                     scan_perm_alpha=None, scan_perm_chromosomes=None, scan_perm_pheno=None, scan_mediate=False,
-                    scan_mediate_min_lod=None, scan_mediate_top=None, scan_mediator_file=None):
+                    scan_mediate_min_lod=None, scan_mediate_top=None, scan_mediator_file=None, scan_effects=False,
+                    scan_effects_min_lod=None, scan_lod_drop=None):
     """`--scan-pheno FILE [--scan-covar FILE] [--scan-rankz] [--scan-out PREFIX] [--scan-min-lod X] [--scan-lod-matrix]`,
-    the `--scan-perm*` options (perm_options) and the `--scan-mediat*` options (mediate_options):
+    the `--scan-perm*` options (perm_options), the `--scan-mediat*` options (mediate_options) and `--scan-effects`,
+    `--scan-effects-min-lod`, `--scan-lod-drop` (effects_options):
     every option needs the phenotypes, the phenotypes need `--grid-file` and a cohort (`--sample-file`): one sample
     cannot be scanned.  Refused before a file is read."""
     given = {'--scan-covar': scan_covar, '--scan-rankz': scan_rankz or None, '--scan-out': scan_out,
@@ -411,9 +475,12 @@ def check_scan_args(scan_pheno=None, scan_covar=None, scan_rankz=False, scan_out
              '--scan-perm-seed': scan_perm_seed, '--scan-perm-alpha': scan_perm_alpha,
              '--scan-perm-chromosomes': scan_perm_chromosomes, '--scan-perm-pheno': scan_perm_pheno,
              '--scan-mediate': scan_mediate or None, '--scan-mediate-min-lod': scan_mediate_min_lod,
-             '--scan-mediate-top': scan_mediate_top, '--scan-mediator-file': scan_mediator_file}
+             '--scan-mediate-top': scan_mediate_top, '--scan-mediator-file': scan_mediator_file,
+             '--scan-effects': scan_effects or None, '--scan-effects-min-lod': scan_effects_min_lod,
+             '--scan-lod-drop': scan_lod_drop}
     perm_options(scan_perms, scan_perm_seed, scan_perm_alpha, scan_perm_chromosomes, scan_perm_pheno)
     mediate_options(scan_mediate, scan_mediate_min_lod, scan_mediate_top, scan_mediator_file)
+    effects_options(scan_effects, scan_effects_min_lod, scan_lod_drop)
     if scan_pheno is None:
         for name, value in given.items():
             if value is not None:
@@ -499,35 +566,46 @@ def scan_design(ids, pheno, covar=None, use_rankz=False):
     return kept, y, z, names
 
 
-def write_scan(prefix, phenotypes, samples, covariates, chrom, pos, chrom_names, result, rank, min_lod=0.0, perm=None):
+def write_scan(prefix, phenotypes, samples, covariates, chrom, pos, chrom_names, result, rank, min_lod=0.0, perm=None,
+               lod_drop=None):
     """`<prefix>.scan.npz` and `<prefix>.scan.peaks.tsv`.  chrom / pos: per grid point, in the scan's point order;
     chrom_names: the scan's chromosomes, as peak_lod's columns.  perm (with `--scan-perms`): `perm_max` [Pp, B] of the
     phenotypes `columns`, `alphas`, `seed` and `mask` over chrom_names; the .npz gains the perm_* arrays and the peaks
     file the columns `pvalue` and `threshold_<first level>`, NA where nothing was permuted.  Without it both files are
-    what they were before the permutations existed."""
+    what they were before the permutations existed.  lod_drop (with `--scan-lod-drop`; result then holds `support_lo`
+    and `support_hi`): the .npz gains both and `lod_drop`, the peaks file the columns `support_lo` and `support_hi` - the
+    positions of the interval's ends - after every other column."""
     arrays = dict(phenotypes=np.array(phenotypes), samples=np.array(samples), covariates=np.array(covariates),
                   chrom=np.array(chrom), pos=np.asarray(pos, dtype=np.float64), rank=np.asarray(rank),
                   peak_lod=result['peak_lod'], peak_index=result['peak_index'])
     if 'lod' in result:
         arrays['lod'] = result['lod']
     peak, index = result['peak_lod'], result['peak_index']
+    if lod_drop is None:
+        ends, ends_header = lambda p, c: '', ''
+    else:
+        arrays.update(support_lo=result['support_lo'], support_hi=result['support_hi'], lod_drop=np.float64(lod_drop))
+        ends = lambda p, c: (f'\t{repr(float(pos[result["support_lo"][p, c]]))}'
+                             f'\t{repr(float(pos[result["support_hi"][p, c]]))}')
+        ends_header = '\tsupport_lo\tsupport_hi'
     if perm is not None:
-        write_scan_perm(prefix, phenotypes, pos, chrom_names, peak, index, min_lod, perm, arrays)
+        write_scan_perm(prefix, phenotypes, pos, chrom_names, peak, index, min_lod, perm, arrays, ends, ends_header)
         return
     np.savez(f'{prefix}.scan.npz', **arrays)
     with open(f'{prefix}.scan.peaks.tsv', 'w') as out:
-        out.write('#phenotype\tchromosome\tposition\tlod\tgenome_wide_max\n')
+        out.write(f'#phenotype\tchromosome\tposition\tlod\tgenome_wide_max{ends_header}\n')
         for p, name in enumerate(phenotypes):
             on = [c for c in range(len(chrom_names)) if index[p, c] >= 0]
             top = max(on, key=lambda c: (peak[p, c], -c)) if on else None
             for c in on:
                 if peak[p, c] >= min_lod:
                     out.write(f'{name}\t{chrom_names[c]}\t{repr(float(pos[index[p, c]]))}\t{repr(float(peak[p, c]))}\t'
-                              f'{int(c == top)}\n')
+                              f'{int(c == top)}{ends(p, c)}\n')
 
 
-def write_scan_perm(prefix, phenotypes, pos, chrom_names, peak, index, min_lod, perm, arrays):
-    """write_scan's two files with the permutation results in them."""
+def write_scan_perm(prefix, phenotypes, pos, chrom_names, peak, index, min_lod, perm, arrays, ends=lambda p, c: '',
+                    ends_header=''):
+    """write_scan's two files with the permutation results in them; ends / ends_header: write_scan's support columns."""
     columns, mask, alphas = list(perm['columns']), np.asarray(perm['mask'], dtype=bool), list(perm['alphas'])
     threshold = perm_thresholds(perm['perm_max'], alphas)
     pvalue = perm_pvalues(perm['perm_max'], peak[columns], selected=mask)
@@ -537,7 +615,8 @@ def write_scan_perm(prefix, phenotypes, pos, chrom_names, peak, index, min_lod, 
     np.savez(f'{prefix}.scan.npz', **arrays)
     row_of = {p: k for k, p in enumerate(columns)}
     with open(f'{prefix}.scan.peaks.tsv', 'w') as out:
-        out.write(f'#phenotype\tchromosome\tposition\tlod\tgenome_wide_max\tpvalue\tthreshold_{repr(float(alphas[0]))}\n')
+        out.write(f'#phenotype\tchromosome\tposition\tlod\tgenome_wide_max\tpvalue\tthreshold_{repr(float(alphas[0]))}'
+                  f'{ends_header}\n')
         for p, name in enumerate(phenotypes):
             on = [c for c in range(len(chrom_names)) if index[p, c] >= 0]
             top = max(on, key=lambda c: (peak[p, c], -c)) if on else None
@@ -546,7 +625,7 @@ def write_scan_perm(prefix, phenotypes, pos, chrom_names, peak, index, min_lod, 
                     judged = p in row_of and mask[c]
                     out.write(f'{name}\t{chrom_names[c]}\t{repr(float(pos[index[p, c]]))}\t{repr(float(peak[p, c]))}\t'
                               f'{int(c == top)}\t{repr(float(pvalue[row_of[p], c])) if judged else "NA"}\t'
-                              f'{repr(float(threshold[row_of[p], 0])) if judged else "NA"}\n')
+                              f'{repr(float(threshold[row_of[p], 0])) if judged else "NA"}{ends(p, c)}\n')
 
 
 def snp_plan(snps, chrom_names, points, grid):
@@ -708,12 +787,59 @@ def finish_scan_mediation(scan, prefix, ids, pheno, covariates, y, mediate, resu
         stage_times['mediate'] = stage_times.get('mediate', 0.0) + time.perf_counter() - t0
 
 
+def write_scan_effects(prefix, phenotypes, founders, samples, covariates, chrom_names, pos, targets, points, result, min_lod):
+    """`<prefix>.scan.effects.npz` and `<prefix>.scan.effects.tsv` from GenomeScan.effects' dict.  targets: [T, 2]
+    (phenotype, chromosome) indices, points: [T] grid points, founders: the H labels.  One line per peak: phenotype,
+    chromosome, position, lod, rank, then effect_<founder> and se_<founder> per founder."""
+    targets = np.asarray(targets, dtype=np.int64).reshape(-1, 2)
+    points = np.asarray(points, dtype=np.int64)
+    founders = [str(f) for f in founders]
+    arrays = dict(phenotypes=np.array(phenotypes), founders=np.array(founders, dtype=np.str_), samples=np.array(samples),
+                  covariates=np.array(covariates), targets=np.array([phenotypes[p] for p in targets[:, 0]], dtype=np.str_),
+                  target_phenotype=targets[:, 0], target_chromosome=np.array([chrom_names[c] for c in targets[:, 1]], dtype=np.str_),
+                  points=points, position=np.asarray(pos, dtype=np.float64)[points], min_lod=np.float64(min_lod))
+    for key in ('effect', 'se', 'lod', 'sigma2', 'rank'):
+        arrays[key] = result[key]
+    np.savez(f'{prefix}.scan.effects.npz', **arrays)
+    with open(f'{prefix}.scan.effects.tsv', 'w') as out:
+        out.write('#phenotype\tchromosome\tposition\tlod\trank' + ''.join(f'\teffect_{f}\tse_{f}' for f in founders) + '\n')
+        for t, (p, c) in enumerate(targets):
+            out.write(f'{phenotypes[p]}\t{chrom_names[c]}\t{repr(float(arrays["position"][t]))}\t{repr(float(result["lod"][t]))}\t'
+                      f'{int(result["rank"][t])}' +
+                      ''.join(f'\t{repr(float(e))}\t{repr(float(s))}' for e, s in zip(result['effect'][t], result['se'][t])) + '\n')
+
+
+def finish_scan_effects(scan, prefix, ids, pheno, covariates, y, min_lod, result, chrom_names, pos, founders=None,
+                        stage_times=None):
+    """The effects pass on the prepared cohort `scan` holds and its two files.  y: the phenotypes as the
+    scan saw them; result: GenomeScan.run's dict, whose peaks of at least min_lod are the targets (mediation_targets);
+    founders: their labels, the founder's index without them.  Its wall-clock seconds go to stage_times['effects']."""
+    import time
+    t0 = time.perf_counter()
+    targets = mediation_targets(result['peak_lod'], result['peak_index'], min_lod)
+    points = result['peak_index'][targets[:, 0], targets[:, 1]]
+    T, H = len(targets), scan.H
+    if T:
+        got = scan.effects(y, targets[:, 0], points)
+        logger.info(f'scan: founder effects at {T} peaks; {scan.effects_info()["pass_ms"]:.1f} ms on the device')
+    else:
+        logger.warning(f'scan: no peak reaches a LOD of {min_lod}: no founder effects')
+        got = {'effect': np.zeros((0, H)), 'se': np.zeros((0, H)), 'lod': np.zeros(0), 'sigma2': np.zeros(0),
+               'rank': np.zeros(0, dtype=np.int32)}
+    write_scan_effects(prefix, pheno[0], list(range(H)) if founders is None else founders, ids, covariates,
+                       [str(c) for c in chrom_names], pos, targets, points, got, min_lod)
+    if stage_times is not None:
+        stage_times['effects'] = stage_times.get('effects', 0.0) + time.perf_counter() - t0
+
+
 def finish_scan(scan, prefix, ids, pheno, covar, use_rankz, chrom, pos, chrom_names, min_lod=None, lod_matrix=False,
-                perm=None, stage_times=None, snps=None, snp_grid=None, mediate=None):
+                perm=None, stage_times=None, snps=None, snp_grid=None, mediate=None, effects=None, founders=None):
     """prepare + run + the two files for the cohort `scan` holds, whose samples are `ids` in append order (every one with
     its rows in the tables).  perm: perm_options' dict, or None; with it the permutation pass runs after the scan on the
     phenotypes and chromosomes it names and its wall-clock seconds go to stage_times['scan_perm'].  mediate:
     mediate_options' dict, or None; with it the scan's peaks are mediated after everything else (finish_scan_mediation).
+    effects: effects_options' dict, or None; its lod_drop makes the run form the support intervals, its min_lod makes
+    the founder effects of the peaks follow (finish_scan_effects), named by `founders`.
     Returns GenomeScan.info() after the run."""
     kept, y, z, names = scan_design(ids, pheno, covar, use_rankz)
     assert len(kept) == len(ids) == scan.n
@@ -721,7 +847,8 @@ def finish_scan(scan, prefix, ids, pheno, covar, use_rankz, chrom, pos, chrom_na
         columns, mask = perm_plan(perm, pheno[0], [str(c) for c in chrom_names])     # refused before the device runs
     scan.prepare(z, names)
     want_lod = bool(lod_matrix) or y.shape[1] * scan.M <= LOD_MATRIX_LIMIT
-    result = scan.run(y, want_lod=want_lod)
+    lod_drop = effects['lod_drop'] if effects is not None else None
+    result = scan.run(y, want_lod=want_lod, lod_drop=lod_drop)
     info = scan.info()
     done = None
     if perm is not None:
@@ -735,7 +862,7 @@ def finish_scan(scan, prefix, ids, pheno, covar, use_rankz, chrom, pos, chrom_na
         logger.info(f'scan: {perm["n_perm"]} permutations of {len(columns)} phenotypes; {timing["permute_ms"]:.1f} ms on the '
                     f'device, {timing["product_ms"]:.1f} ms of them in the product kernel')
     write_scan(prefix, pheno[0], ids, names, chrom, pos, chrom_names, result, info['rank'],
-               0.0 if min_lod is None else min_lod, perm=done)
+               0.0 if min_lod is None else min_lod, perm=done, lod_drop=lod_drop)
     logger.info(f'scan: {len(ids)} samples, {y.shape[1]} phenotypes, {scan.M} grid points; prepare '
                 f'{info["prepare_ms"]:.1f} ms, run {info["run_ms"]:.1f} ms on the device')
     if snps is not None:        # read_snp_file's dict: the SNP association pass follows on the same preparation
@@ -743,23 +870,30 @@ def finish_scan(scan, prefix, ids, pheno, covar, use_rankz, chrom, pos, chrom_na
     if mediate is not None:     # mediate_options' dict: the scan's peaks are mediated on the same preparation
         finish_scan_mediation(scan, prefix, ids, pheno, names, y, dict(mediate, rankz=use_rankz), result, chrom_names, pos,
                               lod_matrix, stage_times)
+    if effects is not None and effects['min_lod'] is not None:      # effects_options' dict: the peaks' founder effects
+        finish_scan_effects(scan, prefix, ids, pheno, names, y, effects['min_lod'], result, chrom_names, pos, founders,
+                            stage_times)
     return info
 
 
 def scan_tables(dosage_list, grid_file, pheno_file, covar_file=None, use_rankz=False, out=None, min_lod=None,
                 lod_matrix=False, device=0, scan_perms=None, scan_perm_seed=None, scan_perm_alpha=None,
                 scan_perm_chromosomes=None, scan_perm_pheno=None, stage_times=None, snp_file=None, scan_mediate=False,
-                scan_mediate_min_lod=None, scan_mediate_top=None, scan_mediator_file=None):
+                scan_mediate_min_lod=None, scan_mediate_top=None, scan_mediator_file=None, scan_effects=False,
+                scan_effects_min_lod=None, scan_lod_drop=None):
     """`gbrs scan`: the cohort from dosage tables in `gbrs export` format (lines `id<TAB>dosage table`), rows in the grid
     file's order, without the HMM.  snp_file (`--snp-file`): the SNP association pass follows the scan (DESIGN.md §29);
     the haplotypes of the patterns are those of the dosage tables' header.  scan_mediate (`--scan-mediate`): the scan's
-    peaks are mediated by the phenotypes or by the table of scan_mediator_file."""
+    peaks are mediated by the phenotypes or by the table of scan_mediator_file.  scan_effects
+    (`--scan-effects`) and scan_lod_drop (`--scan-lod-drop`): the peaks' founder effects, named by the dosage tables'
+    header, and their LOD support intervals."""
     from .hmm import _match_lines, read_dosage_table, read_snp_file
     from .postproc import read_grid
     if min_lod is not None and not min_lod >= 0.0:
         raise RuntimeError('--scan-min-lod must be a number that is not negative')
     perm = perm_options(scan_perms, scan_perm_seed, scan_perm_alpha, scan_perm_chromosomes, scan_perm_pheno)
     mediate = mediate_options(scan_mediate, scan_mediate_min_lod, scan_mediate_top, scan_mediator_file)
+    effects = effects_options(scan_effects, scan_effects_min_lod, scan_lod_drop)
     grid = read_grid(grid_file)
     chrom_names = list(grid)
     points = [len(grid[c]) for c in chrom_names]
@@ -789,6 +923,6 @@ def scan_tables(dosage_list, grid_file, pheno_file, covar_file=None, use_rankz=F
         pos = np.concatenate([np.asarray(grid[c], dtype=np.float64) for c in chrom_names])
         return finish_scan(scan, out if out is not None else 'gbrs', [entries[k][0] for k in kept], pheno, covar, use_rankz,
                            chrom, pos, chrom_names, min_lod, lod_matrix, perm=perm, stage_times=stage_times, snps=snps,
-                           snp_grid=grid, mediate=mediate)
+                           snp_grid=grid, mediate=mediate, effects=effects, founders=haplotypes)
     finally:
         scan.close()

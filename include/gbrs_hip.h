@@ -1109,6 +1109,59 @@ typedef struct gbrs_scan_mediate_info {
 } gbrs_scan_mediate_info_t;
 int gbrs_scan_mediate_info(gbrs_scan_t *scan, gbrs_scan_mediate_info_t *info);
 
+/* Founder effects at QTL peaks on the scan handle (R/qtl2's scan1coef at chosen points): for target t - the
+ * phenotype column y = column[t] in [0, P) and the grid point m = point[t] in [0, M) - the effects of all H founders and
+ * their standard errors.  W_m of gbrs_scan_prepare serves, as it does for mediation: no new factorisation of the design.
+ * No fused multiply-add anywhere.
+ *   y~, rss0 as gbrs_scan_run forms them (the same kernel); a constant column goes in as zeros
+ *   S = the kept rows of W_m,  r = rank[m],  a = W_S y~
+ *   X~_j, j < H-1: founder j's dosage column at m with the covariates projected out, by gbrs_scan_prepare's steps and in
+ *   their order;  X~_{H-1} = -sum_{j<H-1} X~_j (j ascending) by definition: the sum constraint the scan assumes when it
+ *   drops founder H-1, which keeps the rule well defined for dosage rows that do not add up to a constant
+ *   R = W_S [X~_0 .. X~_{H-1}] (r x H; its last column is minus the sum of the others, in the same order),  C = R R',
+ *   symmetric positive definite because R has full row rank: a plain Cholesky without a skip rule
+ *   effect = R' C^-1 a: the minimum-norm least-squares solution over all H founder columns, pinv([X~_0 .. X~_{H-1}]) y~.
+ *   At full rank the effects add up to zero (qtl2's zero-sum founder effects); a founder j < H-1 without dosage in the
+ *   cohort at m gets exactly 0.0 with se 0.0; founders with identical dosages share their effect equally; with r = 0
+ *   every effect and se is 0.0
+ *   rss1 = max(rss0 - |a|^2, 0),  sigma2 = rss1 / (n - c - r) (the divisor is positive under gbrs_scan_prepare's check),
+ *   se[h] = sqrt(sigma2) |C^-1 R[:, h]|
+ *   lod[t] by gbrs_scan_run's formula with its two edge rules on this pass's rss0 and |a|^2.  It lies within rounding of
+ *   gbrs_scan_run's value at (y, m) and does not carry its bits: that one is an MFMA chain, this one a wavefront sum.
+ * pheno is double[n][P] as for gbrs_scan_run; effect and se double[T][H], lod and sigma2 double[T], rank int32[T] (rank[m]
+ * of gbrs_scan_info); every output nullable.  y~ of all P columns stays on the device as [P][n_ld]; the targets pass in
+ * chunks of 512, one workgroup each, so device memory is bounded for any T.  Every sum over the samples is one
+ * wavefront's in gbrs_scan_prepare's order and the small dense steps run in a fixed order, without atomics: a target's
+ * numbers are the same bits alone or among others, at any place in the list, in any chunk, for any P and any position of
+ * its column, given twice, and however the cohort was appended.  GBRS_ERR_INVALID before gbrs_scan_prepare, for P < 1 or
+ * T < 1, for a column outside [0, P) or a point outside [0, M) and for a value that is not finite (the message names the
+ * entry); the outputs are untouched on such a failure.  The call allocates and frees its own buffers: what the handle
+ * holds, gbrs_scan_run's bits and gbrs_scan_info_t are as before.  No mixed model, no BLUP shrinkage of the effects, no
+ * Bayes credible interval. */
+int gbrs_scan_effects(gbrs_scan_t *scan, int64_t P, const double *pheno /* [n][P] */, int64_t T,
+                      const int64_t *column /* [T], in [0,P) */, const int64_t *point /* [T], in [0,M) */,
+                      double *effect /* [T][H] */, double *se /* [T][H] */, double *lod /* [T] */,
+                      double *sigma2 /* [T] */, int32_t *rank /* [T] */);
+
+typedef struct gbrs_scan_effects_info {
+    int64_t  T, P;               /* of the last gbrs_scan_effects (0: none yet)                                  */
+    double   last_pass_ms;       /* device time of the pass: uploads, projections, all chunks, copies            */
+    uint64_t peak_device_bytes;  /* what the handle held during the pass, the call's own buffers included        */
+} gbrs_scan_effects_info_t;
+int gbrs_scan_effects_info(gbrs_scan_t *scan, gbrs_scan_effects_info_t *info);
+
+/* gbrs_scan_run with LOD support intervals (R/qtl2's lod_int): the pass of gbrs_scan_run - the same kernels,
+ * the same bits in lod, peak_lod and peak_index - and one more kernel after the peaks on each chunk's LOD rows while they
+ * are on the device.  For phenotype p on a chromosome with peak index k and peak value v:
+ *   support_lo = the largest index i < k of the chromosome with lod[i] <= v - drop, its first point if there is none;
+ *   support_hi = the smallest index i > k with lod[i] <= v - drop, its last point if there is none.
+ * Both are grid indices among the M points - the flanking points where the LOD has fallen - int64[P][n_chrom], nullable,
+ * and -1 for a chromosome without points.  There is no arithmetic beyond the one subtraction.  GBRS_ERR_INVALID for a
+ * drop that is negative or not finite; the other refusals are gbrs_scan_run's, and the outputs are untouched on failure.
+ * The two tables of a chunk are the call's own: gbrs_scan_info_t's device_bytes is what gbrs_scan_run leaves. */
+int gbrs_scan_run_support(gbrs_scan_t *scan, int64_t P, const double *pheno, double drop, double *lod, double *peak_lod,
+                          int64_t *peak_index, int64_t *support_lo, int64_t *support_hi /* [P][n_chrom] */);
+
 /* ------------------------------------------------------------------------------------------
  * Report text (host side, no device work): the `locus <haplotypes> total [notes]` tables of
  * EMfactory.report_read_counts / report_depths (emase/EMfactory.py:289-380).

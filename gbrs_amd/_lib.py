@@ -23,7 +23,7 @@ EXPORTS = [
     "gbrs_em_get", "gbrs_em_set_theta", "gbrs_em_group_sums", "gbrs_em_estep_partial",
     "gbrs_em_finish_step", "gbrs_em_prepare_partial", "gbrs_em_finish_prepare", "gbrs_em_stream",
     "gbrs_em_set_stream",
-    "gbrs_em_sync", "gbrs_em_pair_begin", "gbrs_em_pair_check", "gbrs_em_pair_status", "gbrs_em_info", "gbrs_em_fold_counts", "gbrs_em_tile_cut", "gbrs_em_gather_mstep", "gbrs_em_tile_shapes",
+    "gbrs_em_sync", "gbrs_em_pair_begin", "gbrs_em_pair_check", "gbrs_em_pair_status", "gbrs_em_info", "gbrs_em_fold_counts", "gbrs_em_tile_cut", "gbrs_em_gather_mstep", "gbrs_em_tile_shapes", "gbrs_em_stripe_census",
     "gbrs_alignment_counts",
     "gbrs_counts_create", "gbrs_counts_get", "gbrs_counts_destroy", "gbrs_em_destroy",
     "gbrs_shard_plan", "gbrs_shard_index", "gbrs_shard_gather",
@@ -205,6 +205,7 @@ def load():
         "gbrs_em_tile_cut": [vp, C.POINTER(u32), C.POINTER(u32)],
         "gbrs_em_gather_mstep": [vp, C.POINTER(u32)],
         "gbrs_em_tile_shapes": [vp, vp, vp, u64],
+        "gbrs_em_stripe_census": [vp, u32, vp],
         "gbrs_alignment_counts": [u64, u32, u32, pp, pp, vp, vp, u32, i32, vp, vp, vp],
         "gbrs_counts_create": [u64, u32, u32, pp, pp, vp, i32, pp],
         "gbrs_counts_get": [vp, vp, u32, vp, vp, vp],
@@ -300,7 +301,7 @@ def load():
     }
     sigs.update(_host_signatures())
     for name, args in sigs.items():
-        if name in ("gbrs_em_fold_counts", "gbrs_em_tile_cut", "gbrs_em_gather_mstep", "gbrs_em_tile_shapes") and os.environ.get("GBRS_TUNING_LIB") and not hasattr(lib, name):
+        if name in ("gbrs_em_fold_counts", "gbrs_em_tile_cut", "gbrs_em_gather_mstep", "gbrs_em_tile_shapes", "gbrs_em_stripe_census") and os.environ.get("GBRS_TUNING_LIB") and not hasattr(lib, name):
             continue        # an A/B variant built from a commit before the call existed
         fn = getattr(lib, name)
         fn.restype = i32

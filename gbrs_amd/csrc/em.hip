@@ -2153,6 +2153,43 @@ int gbrs_em_tile_shapes(gbrs_em_t *em, uint32_t *n_batches, uint32_t *dict_entri
     return GBRS_OK;
 }
 
+// A host walk over the counted batches of every tile, as the wavefronts' shares of em_tiles.inc see them: wavefront w of
+// a tile takes batches [nb w / 8, nb (w + 1) / 8), and its lanes know no dictionary entry when it starts.
+int gbrs_em_stripe_census(gbrs_em_t *em, uint32_t S, uint64_t *out) {
+    if (!em || !out) return fail(GBRS_ERR_INVALID, "NULL argument");
+    for (int k = 0; k < 6; ++k) out[k] = 0;
+    if (em->layout != 1 || em->tl.n_tiles == 0) return GBRS_OK;
+    (void)hipSetDevice(em->device);
+    const TileLayout &tl = em->tl;
+    std::vector<TileHdr> hdr(tl.n_tiles);
+    std::vector<uint32_t> words((size_t)tl.n_batches * 64);
+    GBRS_HIP_CHECK(hipMemcpy(hdr.data(), tl.tiles.p, hdr.size() * sizeof(TileHdr), hipMemcpyDeviceToHost));
+    if (!words.empty()) GBRS_HIP_CHECK(hipMemcpy(words.data(), tl.words.p, words.size() * 4, hipMemcpyDeviceToHost));
+    const uint32_t H = em->plan.tH, shift = H + 2 * pos_bits((int)H), hmask = (1u << H) - 1u;
+    for (const TileHdr &th : hdr) {
+        const uint32_t nb = th.n_batches, lead = std::min<uint32_t>(th.n_one + th.n_two(), nb);
+        if ((uint64_t)th.batch_base + nb > tl.n_batches) return fail(GBRS_ERR_STATE, "a tile header is out of range");
+        const uint32_t *w = words.data() + (size_t)th.batch_base * 64;
+        for (uint32_t b = 0; b < lead; ++b)
+            for (int l = 0; l < 64; ++l) out[4] += (w[(size_t)b * 64 + l] & hmask) == 0u;
+        out[0] += lead;
+        for (int wave = 0; wave < TILE_WAVES; ++wave) {
+            const uint32_t b0 = (uint32_t)(((uint64_t)nb * wave) / TILE_WAVES), b1 = (uint32_t)(((uint64_t)nb * (wave + 1)) / TILE_WAVES);
+            if (b0 < b1 && b0 < lead) ++out[1];
+            for (uint32_t b = b0 + 1; b < std::min(b1, lead); ++b) {
+                uint32_t lanes = 0;
+                for (int l = 0; l < 64; ++l) lanes += (w[(size_t)b * 64 + l] >> shift) != (w[(size_t)(b - 1) * 64 + l] >> shift);
+                if (!lanes) continue;
+                ++out[2];
+                out[3] += lanes;
+                const uint32_t first = b < th.n_one ? 0u : th.n_one;
+                if (S != 0 && (b - first) % S != 0) ++out[5];
+            }
+        }
+    }
+    return GBRS_OK;
+}
+
 int gbrs_counts_create(uint64_t R, uint32_t L, uint32_t H, const uint32_t *const *indptr,
                        const uint32_t *const *indices, const double *count, int device, gbrs_counts_t **out) {
     if (!out) return fail(GBRS_ERR_INVALID, "out is NULL");

@@ -108,7 +108,9 @@ struct TileHdr {
                            // tile_pad_kernel's run of one-word rows; 0: nothing is known about the tile's batches).  An empty
                            // cell of these batches carries the dictionary index of the cell above it (same lane, batch
                            // before) and no haplotype bit, see fill_one_word_cells_kernel.  In these batches a word's pos /
-                           // rem bits are a repeat count (the word format above)
+                           // rem bits are a repeat count (the word format above).  With stripes (em_plan.h) the rows of
+                           // one dictionary id start at a batch that is a multiple of S from the run's first and the
+                           // empty cells are the ends of the ids' last stripes; the same on lane pairs in the n_two run
     uint32_t dict_base;    // first slot / dictionary entry of the tile
     uint32_t dict_n_two;   // D in the low 16 bits, n_two in the high 16 (dict_count(), n_two()).  n_two INVARIANT: every batch with index in [n_one, n_one + n_two) holds only two-word rows on (even, odd)
                            // lane pairs, or padding pairs, and its words' 2 PB bits are a repeat count, not positions (the B of
@@ -172,6 +174,7 @@ struct TileLayout {
     bool weighted = false;       // per-row weights present (count given or rows merged)
     bool deterministic = false;  // dictionaries capped at det_dict_cap(H): one private sum copy per wavefront
     bool all_one_word = false;   // every row of the layout is a single word (and there are no long rows)
+    bool stripes = false;        // the counted runs were laid out in stripes (em_plan.h, em_take_stripes)
 
     DevBuf<uint32_t> words;          // n_batches * 64
     DevBuf<TileHdr> tiles;           // n_tiles

@@ -620,6 +620,33 @@ __global__ void tile_start_kernel(uint64_t m_rows, uint64_t n_tiles, const uint3
     tile_row[tincl[m] - 1] = (uint32_t)m;
 }
 
+// Stripes (em_plan.h): head[m] = 1 when row m - a one- or two-word row, in the tiles' stream order - does not continue the
+// group of the row before it: another length, another first id or, in a two-word row, another second id.  (Rows of one
+// group are neighbours in that order up to a collision of the row key's hashes, which only makes two groups of one.)
+__global__ void stripe_head_kernel(uint64_t m_rows, const uint32_t *__restrict__ npm, const uint32_t *__restrict__ hrow,
+                                   const uint32_t *__restrict__ rowstart, const uint32_t *__restrict__ ploc,
+                                   uint8_t *__restrict__ head) {
+    const uint64_t m = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= m_rows) return;
+    const uint32_t cnt = npm[m];
+    uint8_t h = 1;
+    if (m > 0 && cnt <= 2u && npm[m - 1] == cnt) {
+        const uint32_t a = rowstart[hrow[m - 1]], b = rowstart[hrow[m]];
+        h = (ploc[a] != ploc[b] || (cnt == 2u && ploc[a + 1] != ploc[b + 1])) ? 1 : 0;
+    }
+    head[m] = h;
+}
+
+// cells of a run of n rows whose groups (head) each start at a multiple of S and take whole stripes of S cells
+__device__ __forceinline__ uint32_t stripe_cells(const uint8_t *__restrict__ head, uint32_t n, uint32_t S) {
+    uint32_t c = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+        if (head[k]) c = (c + S - 1u) & ~(S - 1u);
+        ++c;
+    }
+    return (c + S - 1u) & ~(S - 1u);
+}
+
 // one thread per tile: padded offset of every row so that no row straddles a 64-word batch.
 // streams: the tile's rows arrive grouped by length; a run of n rows of length w (w | 64) takes
 // B = ceil(n / (64/w)) whole batches in which lane group g (w lanes) holds rows g*B .. g*B+B-1 of the
@@ -628,9 +655,15 @@ __global__ void tile_start_kernel(uint64_t m_rows, uint64_t n_tiles, const uint3
 // n_one[t]: the batches of the tile's run of one-word rows - the rows sort by length, so they are the tile's first
 // (TileHdr::n_one); 0 in the other row orders.  n_two[t]: the batches of the run of two-word rows when it starts exactly at
 // batch n_one[t] (TileHdr::n_two; the caller clears it for the layouts whose kernels do not read counts).
+// head (stripes, em_plan.h; null: none): those two runs are laid out in CELLS - a group of rows starts at a cell that is a
+// multiple of the run's stripe S and its last stripe is filled up with empty cells, B is rounded up to a multiple of S, and
+// cell c sits on lane group c / B at batch c % B as a row of the plain run does.  A lane group therefore changes id only at
+// batches that are a multiple of S from the run's first, and an empty cell has a word of its own group above it on its
+// lane (fill_one_word_cells_kernel).  S is chosen per tile and run by em_stripe_pick; S = 0 is the plain placement.
 __global__ void tile_pad_kernel(uint64_t n_tiles, int streams, const uint32_t *__restrict__ tile_row,
                                 const uint32_t *__restrict__ npm, uint32_t *__restrict__ rowpad,
-                                uint32_t *__restrict__ nbatch, uint32_t *__restrict__ n_one, uint32_t *__restrict__ n_two) {
+                                uint32_t *__restrict__ nbatch, uint32_t *__restrict__ n_one, uint32_t *__restrict__ n_two,
+                                const uint8_t *__restrict__ head, int stripes_one, int stripes_two) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_tiles) return;
     uint32_t off = 0, one = 0, two = 0;
@@ -641,11 +674,29 @@ __global__ void tile_pad_kernel(uint64_t n_tiles, int streams, const uint32_t *_
         if (streams && cnt <= 32u && (64u % cnt) == 0u) {
             uint32_t e = m + 1;
             while (e < end && npm[e] == cnt) ++e;
-            const uint32_t n = e - m, G = 64u / cnt, B = (n + G - 1) / G;
+            const uint32_t n = e - m, G = 64u / cnt;
+            uint32_t B = (n + G - 1) / G;
             off = (off + 63u) & ~63u;
-            if (cnt == 1u && off == 0u) one = B;
-            if (cnt == 2u && off == one * 64u) two = B;
-            for (uint32_t k = 0; k < n; ++k) rowpad[m + k] = off + (k % B) * 64u + (k / B) * cnt;
+            const bool lead_one = cnt == 1u && off == 0u, lead_two = cnt == 2u && off == one * 64u;
+            uint32_t S = 0;
+            if (head && (lead_one || lead_two)) {
+                const int forced = lead_one ? stripes_one : stripes_two;
+                S = forced >= 0 ? (uint32_t)forced : em_stripe_pick(forced, n, stripe_cells(head + m, n, 4u), stripe_cells(head + m, n, 2u));
+            }
+            if (S != 0u) {
+                B = (stripe_cells(head + m, n, S) + G - 1) / G;
+                B = (B + S - 1u) & ~(S - 1u);
+                uint32_t c = 0;
+                for (uint32_t k = 0; k < n; ++k) {
+                    if (head[m + k]) c = (c + S - 1u) & ~(S - 1u);
+                    rowpad[m + k] = off + (c % B) * 64u + (c / B) * cnt;
+                    ++c;
+                }
+            } else {
+                for (uint32_t k = 0; k < n; ++k) rowpad[m + k] = off + (k % B) * 64u + (k / B) * cnt;
+            }
+            if (lead_one) one = B;
+            if (lead_two) two = B;
             off += B * 64u;
             m = e;
         } else {
@@ -734,10 +785,11 @@ __global__ void emit_words_kernel(uint64_t m_rows, uint32_t H, const uint32_t *_
 }
 
 // The empty cells of a tile's leading one-word batches (TileHdr::n_one).  Lane g of the run holds its rows g*B .. g*B+B-1
-// at batches 0 .. B-1, so only the lane of the run's last row ends early (the lanes after it are empty altogether and
-// stay all-zero words: dictionary entry 0).  That lane's empty cells take the dictionary index of its last row and no
-// haplotype bit: still padding to every reader (no bit, nothing added), and a lane that walks down the run never meets
-// a change of entry that is not one.  Their pos / rem field - a repeat count in these batches - is 0: the first loop
+// at batches 0 .. B-1, so without stripes only the lane of the run's last row ends early (the lanes after it are empty
+// altogether and stay all-zero words: dictionary entry 0); with stripes (tile_pad_kernel) every group's last stripe can
+// end in empty cells, each below a word of its own group on the same lane.  An empty cell takes the dictionary index of
+// the word above it and no haplotype bit: still padding to every reader (no bit, nothing added), and a lane that walks
+// down the run never meets a change of entry that is not one.  Their pos / rem field - a repeat count in these batches - is 0: the first loop
 // multiplies a padding word's 4.49e307 by 1 + count, and inf times the 0.0 of a clear haplotype bit would be NaN.
 // One thread per (tile, lane).
 __global__ void fill_one_word_cells_kernel(uint64_t n_tiles, uint32_t H, const TileHdr *__restrict__ hdr,
@@ -751,11 +803,14 @@ __global__ void fill_one_word_cells_kernel(uint64_t n_tiles, uint32_t H, const T
         const uint32_t B = run == 0 ? th.n_one : th.n_two();
         if (B < 2) continue;
         uint32_t *w = words + ((uint64_t)th.batch_base + (run == 0 ? 0u : th.n_one)) * 64 + (i & 63u);
-        if (w[0] == 0u || w[(uint64_t)(B - 1) * 64] != 0u) continue;      // an empty lane / a full one
-        uint32_t b = B - 1;
-        while (w[(uint64_t)(b - 1) * 64] == 0u) --b;                      // (ends at batch 0 at the latest: its word is not zero)
-        const uint32_t fill = w[(uint64_t)(b - 1) * 64] & ~((1u << (H + 2 * pos_bits(H))) - 1u);
-        for (; b < B; ++b) w[(uint64_t)b * 64] = fill;
+        // from the top: a real word has a haplotype bit, every other cell takes the index of the last real word above it
+        // (none above: the lane is empty altogether - a stripe's first cell is never empty - and stays on entry 0)
+        uint32_t fill = 0;
+        for (uint32_t b = 0; b < B; ++b) {
+            const uint32_t x = w[(uint64_t)b * 64];
+            if (x & ((1u << H) - 1u)) fill = x & ~((1u << (H + 2 * pos_bits(H))) - 1u);
+            else if (x != fill) w[(uint64_t)b * 64] = fill;
+        }
     }
 }
 
@@ -1765,13 +1820,24 @@ struct TileParts {
 };
 
 // 8. padding so that no row straddles a batch, batch offsets
-int pad_rows(Build &b, TileLayout &out, const Tiles &t, TileParts &tp, uint64_t M, const EmPlan &plan) {
+int pad_rows(Build &b, TileLayout &out, const RowPairs &rp, const LayoutRows &lr, const Tiles &t, TileParts &tp,
+             const EmPlan &plan) {
     hipStream_t s = b.s;
-    const uint64_t T = t.T;
+    const uint64_t T = t.T, M = lr.M;
     GBRS_TRY(tp.rowpad.alloc(M)); GBRS_TRY(tp.nbatch.alloc(T)); GBRS_TRY(tp.n_one.alloc(T)); GBRS_TRY(tp.n_two.alloc(T));
     GBRS_TRY(tp.batch_base.alloc(T));
+    // stripes (em_plan.h): where the layout takes them, the rows that start a group
+    DevBuf<uint8_t> head;
+    uint32_t W = 0;
+    if (plan.counted_pairs && (plan.stripes_one != 0 || plan.stripes_two != 0)) GBRS_TRY(fetch_last_plus(t.wordoff.p, t.npm.p, M, W, s));
+    out.stripes = em_take_stripes(plan, W);
+    if (out.stripes) {
+        GBRS_TRY(head.alloc(M));
+        hipLaunchKernelGGL(stripe_head_kernel, dim3(grid_for(M)), dim3(256), 0, s, M, t.npm.p, lr.hrow.p, rp.rowstart.p, rp.ploc.p, head.p);
+    }
     hipLaunchKernelGGL(tile_pad_kernel, dim3(grid_for(T, 64)), dim3(64), 0, s, T, plan.row_order == 2 ? 1 : 0, t.tile_row.p, t.npm.p,
-                       tp.rowpad.p, tp.nbatch.p, tp.n_one.p, tp.n_two.p);
+                       tp.rowpad.p, tp.nbatch.p, tp.n_one.p, tp.n_two.p, out.stripes ? head.p : (const uint8_t *)nullptr,
+                       plan.stripes_one, plan.stripes_two);
     // (the weighted kernels do not split their batch loop: their headers say nothing about the leading batches)
     if (out.weighted) GBRS_HIP_CHECK(hipMemsetAsync(tp.n_one.p, 0, T * 4, s));
     if (!plan.counted_pairs) GBRS_HIP_CHECK(hipMemsetAsync(tp.n_two.p, 0, T * 4, s));
@@ -2057,7 +2123,7 @@ int build_tile_layout(TileLayout &out, uint64_t R, uint64_t N, const uint32_t *e
     tiles.dnew.release();
     tiles.tflag.release();
     stg.mark("7b row order");
-    GBRS_TRY(pad_rows(b, out, tiles, parts, lr.M, plan));
+    GBRS_TRY(pad_rows(b, out, rp, lr, tiles, parts, plan));
     stg.mark("8 padding");
     GBRS_TRY(tile_dictionaries(b, out, rp, lr, tiles, parts));
     stg.mark("9 dictionaries");

@@ -40,6 +40,9 @@ struct EmTuning {
     bool no_fused_mstep = false;      // NO_FUSED_MSTEP=1: gather and M-step as separate launches (em_step.h)
     bool no_float_check = false;      // NO_FLOAT_CHECK set at all: no "row without abundance" error (ablation builds of the E-step)
     bool no_gather_mstep = false;     // NO_GATHER_MSTEP=1: the M-step stays a launch of its own (em_step.h, em_gather_mstep)
+    // STRIPES=S (2, 4 or 8): that stripe on every counted run whatever the size or the cap; 0: no stripes; "S1,S2": the
+    // one-word runs and the pair runs apart (the measurements of profiles/estep_stripes.txt).  -1: the rule (em_take_stripes)
+    int stripes_one = -1, stripes_two = -1;
 };
 
 namespace em_env {
@@ -52,6 +55,11 @@ inline EmTuning::Int integer(const char *name) {
 template <typename T>
 inline void at_least(const char *name, int lo, T &v) {
     if (const char *e = std::getenv(name); e && std::atoi(e) >= lo) v = (T)std::atoi(e);
+}
+// a stripe: 0, 2, 4 or 8; anything else leaves the rule in charge
+inline int stripe_value(const char *e) {
+    const int v = std::atoi(e);
+    return (v == 0 && *e == '0') || v == 2 || v == 4 || v == 8 ? v : -1;
 }
 }  // namespace em_env
 
@@ -76,6 +84,11 @@ inline EmTuning em_tuning_from_env() {
     t.no_fused_mstep = integer("GBRS_TUNING_NO_FUSED_MSTEP").nonzero();
     t.no_float_check = integer("GBRS_TUNING_NO_FLOAT_CHECK").set;
     t.no_gather_mstep = integer("GBRS_TUNING_NO_GATHER_MSTEP").nonzero();
+    if (const char *e = std::getenv("GBRS_TUNING_STRIPES"); e) {
+        t.stripes_one = t.stripes_two = stripe_value(e);
+        for (const char *c = e; *c; ++c)
+            if (*c == ',') { t.stripes_two = stripe_value(c + 1); break; }
+    }
     return t;
 }
 
@@ -162,6 +175,12 @@ struct EmPlan {
     uint32_t resample_cut = 256;     // (the variable is read by a resampling handle with counts only)
     bool no_fused_mstep = false, no_float_check = false;   // EmTuning's, for the handle's steps (em_step.h, em_check_float)
     bool no_gather_mstep = false;
+    // Stripes (em_layout.hip, tile_pad_kernel; em_take_stripes below): in a tile's counted runs a group of rows - one
+    // dictionary id, or one (first id, second id) pair - starts only at a cell that is a multiple of S, so that the lanes
+    // of a wavefront change id in the same batches.  -1: S per tile and run by em_stripe_pick; 0: none; 2, 4, 8: forced.
+    // Both 0 in every layout without counted_pairs.
+    int stripes_one = 0, stripes_two = 0;
+    bool stripes_forced = false;     // GBRS_TUNING_STRIPES asked for a stripe: taken whatever the sample's size
 };
 
 // Tiles the exact cut aims at: one round of the places a handle has - its share when handles run side by side - less the
@@ -208,6 +227,11 @@ inline EmPlan em_plan(const EmShape &s, const EmTuning &t) {
     p.fold = !(f & GBRS_EM_NO_RUN_WORDS) && p.counted_pairs && !t.run_words.is(0);
     p.fold_mode = t.run_words.is(1) ? 2 : 3;
     p.fold_forced = t.run_words.set;
+    if (p.counted_pairs) {
+        p.stripes_one = t.stripes_one;
+        p.stripes_two = t.stripes_two;
+        p.stripes_forced = t.stripes_one > 0 || t.stripes_two > 0;
+    }
 
     p.per_cu = (p.weighted || p.tH > 8) ? 2u : 3u;
     const unsigned n_cu = (unsigned)std::max(s.n_cu, 1);
@@ -280,6 +304,30 @@ inline uint32_t em_cut_rescale(const EmPlan &p, uint32_t tile_words, uint64_t ti
 inline bool em_take_fold(const EmPlan &p, uint64_t words_in, uint64_t folded) {
     if (p.fold_forced) return true;
     return folded * 100 >= words_in * 15 && (words_in - folded) * p.side_by_side / p.places >= (uint64_t)p.tile_words;
+}
+
+// Stripes (EmPlan::stripes_one).  They pad, so they are for the samples the batch loop dominates: the layouts whose kernels
+// read the counted runs, and - em_take_fold's own size clause - not the launch-bound ones, which keep their layout cell for
+// cell.  words: the layout's words after the folds.  GBRS_TUNING_STRIPES=2 / 4 / 8 forces them, 0 switches them off.
+inline bool em_take_stripes(const EmPlan &p, uint64_t words) {
+    if (!p.counted_pairs || (p.stripes_one == 0 && p.stripes_two == 0)) return false;
+    if (p.stripes_forced) return true;
+    return words * p.side_by_side / p.places >= (uint64_t)p.tile_words;
+}
+// Which S a run of `words` rows takes in one tile: the largest of 4 and 2 whose padded cells (cells4, cells2: every
+// group rounded up to the stripe) stay within (1 + STRIPE_CAP) x the run's rows - a sample whose ids carry a word or two
+// each would double otherwise.  forced: 0, 2, 4, 8 as the plan says, -1 the rule.  (constexpr: the build's kernel calls it.)
+// Measured on the bench sample (profiles/estep_stripes.txt; iterations/s, three runs each, taken in turn; S of the one-word
+// runs, S of the pair runs): (0, 0) 30,696-30,765; (4, 0) 32,776-33,233; (0, 4) 33,394-33,477; (2, 2) 33,964-34,118;
+// (8, 2) 34,243-34,357; (4, 2) 34,610-34,810; (4, 4) 35,105-35,133 at 1.059 and 1.146 cells per word.  A cap of 1/8 gave
+// the pair runs S = 4 in some tiles and 2 in most; 1/4 gives every run of that sample S = 4.
+constexpr uint32_t STRIPE_CAP_NUM = 1, STRIPE_CAP_DEN = 4;
+constexpr bool em_stripe_fits(uint64_t cells, uint64_t words) {
+    return cells * STRIPE_CAP_DEN <= words * (STRIPE_CAP_DEN + STRIPE_CAP_NUM);
+}
+constexpr uint32_t em_stripe_pick(int forced, uint64_t words, uint64_t cells4, uint64_t cells2) {
+    if (forced >= 0) return (uint32_t)forced;
+    return em_stripe_fits(cells4, words) ? 4u : em_stripe_fits(cells2, words) ? 2u : 0u;
 }
 
 // Whole-row sets (step 3b).  A set entry costs its tile a longer prologue and epilogue (its members' theta summed, its

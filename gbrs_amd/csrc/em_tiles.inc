@@ -56,6 +56,11 @@ __host__ __device__ constexpr bool estep_uses_ftab(int ub, int ht) { return GBRS
 // come from the pending set: a lane that leaves a locus sends its sums to LDS at once instead of parking them (with the
 // LDS pipe no longer busy reading theta the atomics are cheap; with the reads in place the same change cost +23 %).
 // 74 VGPRs, E-step on C2 0.098 -> 0.089 ms (profiles/r03_estep_experiments.txt).
+// "Long stretches" held while a locus had hundreds of reads behind it.  Since the run-word folds a dictionary id has a few
+// dozen words and a lane's share of a tile about 15 batches: on the bench sample 85 % of a wavefront's later batches have
+// two or three lanes changing id, and the whole wavefront takes the miss path below for them.  The layout answers that, not
+// this file: in the counted runs the rows of one id start at multiples of a stripe S (em_plan.h, em_take_stripes;
+// tile_pad_kernel), so the lanes change in the same batches - a quarter of them at S = 4 (profiles/estep_stripes.txt).
 #ifndef GBRS_THETA_REGS
 #define GBRS_THETA_REGS 1
 #endif

@@ -154,6 +154,14 @@ class EmEngine:
         _lib.check(_lib.load().gbrs_em_tile_shapes(self._h, batches.ctypes.data, entries.ctypes.data, n))
         return batches, entries
 
+    def stripe_census(self, S=0):
+        """How the lanes change dictionary entry in the tiles' counted batches (gbrs_em_stripe_census): (counted batches,
+        the wavefronts' first batches among them, later batches with a change, lanes changing in those, padding cells,
+        changes off a multiple of S) as a uint64 array."""
+        out = np.zeros(6, np.uint64)
+        _lib.check(_lib.load().gbrs_em_stripe_census(self._h, int(S), out.ctypes.data))
+        return out
+
     # ---- multi-GPU building blocks -----------------------------------------------------------
     def _partial(self, fn):
         p = C.c_void_p()

@@ -374,6 +374,15 @@ int gbrs_em_gather_mstep(gbrs_em_t *em, uint32_t *taken);
 /* Per tile, in launch order: its batches of 64 words and its dictionary entries.  n must be gbrs_em_info.num_tiles; one
  * device-to-host copy of the headers (profiling scripts and tests). */
 int gbrs_em_tile_shapes(gbrs_em_t *em, uint32_t *n_batches, uint32_t *dict_entries, uint64_t n);
+/* How often the lanes of a wavefront change dictionary entry in the tiles' counted batches (the leading runs of one-word
+ * rows and of two-word rows; GBRS_TUNING_STRIPES lays their groups out in stripes of S cells).  A host walk over a copy of
+ * the headers and words, batch by batch as the E-step's wavefronts take them: wavefront w of a tile has batches
+ * [nb w / 8, nb (w + 1) / 8) and starts on no entry.  out[0] counted batches; out[1] the wavefronts' first batches among
+ * them; out[2] later batches in which at least one lane's dictionary index differs from the cell above it; out[3] the
+ * lanes that change in those; out[4] cells of counted batches without a haplotype bit (padding); out[5] the batches of
+ * out[2] that are not a multiple of S from their run's first batch (S = 0: 0).  All 0 for the CSC layout.  Off the hot
+ * path (profiling scripts and tests). */
+int gbrs_em_stripe_census(gbrs_em_t *em, uint32_t S, uint64_t *out);
 
 /* `--report-alignment-counts` (emase/AlignmentPropertyMatrix.py:389-459), stand-alone (the
  * reference reloads the alignment file for it, gbrs/emase_utils.py:318-331).  Inputs as for

@@ -336,6 +336,14 @@ def _scan_options(parser, covar=True):
     parser.add_argument('--scan-effects-min-lod', type=float, default=None, metavar='X',
                         help='with --scan-effects: the peaks of at least this LOD get their effects (default: 6.0, as '
                              '--scan-mediate-min-lod)')
+    parser.add_argument('--scan-kinship', default=None, metavar='MODE',
+                        help='linear mixed model on the device: MODE loco scans every chromosome with the kinship of the '
+                             'cohort\'s dosages on the other chromosomes, MODE overall with the kinship of all of them; every '
+                             'phenotype\'s heritability is fitted by REML.  <PREFIX>.scan.npz gains hsq and kinship_mode, the '
+                             'peaks file the column hsq.  Not with --scan-perms, --scan-snps / --snp-file, --scan-mediate, '
+                             '--scan-effects or --scan-lod-drop')
+    parser.add_argument('--scan-kinship-out', action='store_true',
+                        help='with --scan-kinship: write the kinship matrices and the sample ids to <PREFIX>.scan.kinship.npz')
 
 
 def main(argv=None) -> int:
@@ -464,7 +472,8 @@ def main(argv=None) -> int:
                         stage_times=stages, snp_file=args.snp_file, scan_mediate=args.scan_mediate,
                         scan_mediate_min_lod=args.scan_mediate_min_lod, scan_mediate_top=args.scan_mediate_top,
                         scan_mediator_file=args.scan_mediator_file, scan_effects=args.scan_effects,
-                        scan_effects_min_lod=args.scan_effects_min_lod, scan_lod_drop=args.scan_lod_drop)
+                        scan_effects_min_lod=args.scan_effects_min_lod, scan_lod_drop=args.scan_lod_drop,
+                        scan_kinship=args.scan_kinship, scan_kinship_out=args.scan_kinship_out)
         elif args.command == 'interpolate':
             from .postproc import interpolate
             interpolate(genoprob_file=args.genoprob_file, grid_file=args.grid_file, gpos_file=args.gpos_file,

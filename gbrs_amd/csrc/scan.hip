@@ -16,7 +16,10 @@
 // with the projected mediators and applies the conditional regression's rule in its epilogue.  Founder effects and LOD
 // support intervals (kernels and the rules in scan_effects.inc): one workgroup per peak forms the founder
 // effects and their standard errors from W_m and the point's dosage columns, and one wavefront per (chromosome,
-// phenotype) walks outward from the peak over the chunk's LOD rows while they are on the device.
+// phenotype) walks outward from the peak over the chunk's LOD rows while they are on the device.  Linear mixed model
+// (kernels and the rule in scan_lmm.inc): the kinship of the cohort per chromosome, the rotation of the
+// cohort by a kinship's eigenvectors, the REML fit of every phenotype's heritability and a weighted scan that forms each
+// (grid point, phenotype) pair's explained sum of squares without a W.
 #include "common.h"
 #include "scan_hmm.h"
 
@@ -328,6 +331,10 @@ scan_peak_kernel(int64_t M, int n_chrom, const int64_t *__restrict__ point_off, 
 
 #include "scan_effects.inc"
 
+// ---- linear mixed model --------------------------------------------------------------------------------------------------------
+
+#include "scan_lmm.inc"
+
 }  // namespace gbrs
 
 using namespace gbrs;
@@ -378,6 +385,24 @@ struct gbrs_scan {
     int64_t eff_T = 0, eff_P = 0;
     double t_eff_pass = 0;
     uint64_t eff_peak_bytes = 0;
+    // the per-chromosome products S_c of gbrs_scan_kinship, [n_chrom][n][n]: kept until the next append
+    DevBuf<double> kin_S;
+    bool kin_valid = false;
+    double t_kinship = 0;
+    // what gbrs_scan_lmm_prepare made (lmm_cz 0: not prepared): the decompositions, the rotated covariates [n_eig][cz][n_ld]
+    // and the rotated cohort [M][Hp][n_ld]
+    int lmm_cz = 0, lmm_n_eig = 0;
+    int64_t lmm_n_ld = 0;
+    DevBuf<double> lmm_U, lmm_lam, lmm_Zs, lmm_R;
+    DevBuf<int32_t> lmm_eig_of_point;
+    // the last gbrs_scan_lmm_run: its buffers are the call's own, as gbrs_scan_permute's
+    int64_t lmm_P = 0;
+    std::vector<int32_t> lmm_rank_min, lmm_rank_max;
+    double t_lmm_rotate = 0, t_lmm_null = 0, t_lmm_point = 0, t_lmm_run = 0;
+    uint64_t lmm_peak_bytes = 0;
+    uint64_t lmm_bytes() const {
+        return lmm_U.bytes() + lmm_lam.bytes() + lmm_Zs.bytes() + lmm_R.bytes() + lmm_eig_of_point.bytes();
+    }
     uint64_t snp_bytes() const {
         return d_snp_off.bytes() + snp_lo.bytes() + snp_hi.bytes() + snp_mask.bytes() + snp_t.bytes();
     }
@@ -404,6 +429,14 @@ int scan_reserve(gbrs_scan *s, int64_t more) {
 void scan_unprepare(gbrs_scan *s) {
     s->c = 0;
     s->rank.clear();
+}
+
+// An append drops what gbrs_scan_kinship and gbrs_scan_lmm_prepare made, as it drops W.
+void scan_lmm_unprepare(gbrs_scan *s) {
+    s->lmm_cz = 0;
+    s->lmm_n_eig = 0;
+    s->kin_valid = false;
+    s->kin_S.release();
 }
 
 // Pairs of events around the product kernel of consecutive chunks, so that a pass times it without waiting per chunk: a
@@ -509,6 +542,7 @@ int gbrs_scan_append(gbrs_scan_t *s, int n, const double *dosage) {
     GBRS_HIP_CHECK(hipMemcpy(s->dosage.p + (size_t)s->n * row, dosage, (size_t)n * row * sizeof(double), hipMemcpyHostToDevice));
     s->n += n;
     scan_unprepare(s);
+    scan_lmm_unprepare(s);
     return GBRS_OK;
 }
 
@@ -534,6 +568,7 @@ int gbrs_scan_append_hmm(gbrs_scan_t *s, gbrs_hmm_t *hmm, int sample) {
     GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
     s->n += view.n;
     scan_unprepare(s);
+    scan_lmm_unprepare(s);
     return GBRS_OK;
 }
 
@@ -1238,6 +1273,299 @@ int gbrs_scan_info(gbrs_scan_t *s, gbrs_scan_info_t *info, int32_t *rank) {
                              s->y.bytes() + s->yt.bytes() + s->rss0.bytes() + s->lod.bytes() + s->peak_lod.bytes() + s->peak_index.bytes();
     }
     if (rank && s->c > 0) std::memcpy(rank, s->rank.data(), s->rank.size() * sizeof(int32_t));
+    return GBRS_OK;
+}
+
+}  // extern "C"
+
+// ---- linear mixed model ----------------------------------------------------------------------------------------
+
+namespace {
+
+// S_c of every chromosome, once per cohort: kept on the handle until the next append.
+int scan_kinship_products(gbrs_scan *s) {
+    if (s->kin_valid) return GBRS_OK;
+    const int n = (int)s->n;
+    const int64_t ld = s->M * s->H;
+    GBRS_TRY(s->kin_S.alloc((size_t)s->n_chrom * n * n));
+    bool vec2 = ld % 2 == 0;
+    for (int c = 0; c < s->n_chrom; ++c) vec2 = vec2 && s->point_off[c] * s->H % 2 == 0;
+    const unsigned blocks = (unsigned)((n + SC_ROWS - 1) / SC_ROWS);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(blocks, blocks, (unsigned)s->n_chrom), dim3(SC_THREADS), 0, s->stream, n, s->H, ld,
+                           s->d_point_off.p, s->dosage.p, s->kin_S.p);
+    };
+    if (vec2) launch(lmm_kinship_kernel<true>);
+    else launch(lmm_kinship_kernel<false>);
+    GBRS_HIP_CHECK(hipGetLastError());
+    s->kin_valid = true;
+    return GBRS_OK;
+}
+
+// One launch of lmm_rotate_kernel: out [rows][n_ld] = (U' src)' on the handle's stream.
+void scan_lmm_rotate(gbrs_scan *s, int64_t n_ld, int64_t rows, int HP, int keep, int64_t hs, int64_t ld_s, const double *U,
+                     const double *src, double *out) {
+    if (rows == 0) return;
+    const dim3 grid((unsigned)((rows + 63) / 64), (unsigned)((n_ld + 63) / 64));
+    hipLaunchKernelGGL(lmm_rotate_kernel, grid, dim3(SC_THREADS), 0, s->stream, (int)s->n, n_ld, rows, HP, keep, hs, ld_s, U, src, out);
+}
+
+}  // namespace
+
+extern "C" {
+
+int gbrs_scan_kinship(gbrs_scan_t *s, int leave_out, double scale, double *K) {
+    RoctxRange roctx_range("gbrs_scan_kinship");
+    if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (!K) return fail(GBRS_ERR_INVALID, "K is NULL");
+    if (s->n < 1) return fail(GBRS_ERR_INVALID, "the cohort has no samples");
+    if (s->n > LM_MAX_N) return fail(GBRS_ERR_INVALID, "a kinship takes at most %d samples, the cohort has %lld", LM_MAX_N, (long long)s->n);
+    if (leave_out < -1 || leave_out >= s->n_chrom)
+        return fail(GBRS_ERR_INVALID, "chromosome %d to leave out is not one of the handle's %d (-1: none)", leave_out, s->n_chrom);
+    if (!std::isfinite(scale)) return fail(GBRS_ERR_INVALID, "the kinship's scale is not finite");
+    int64_t count = 0;
+    for (int c = 0; c < s->n_chrom; ++c)
+        if (c != leave_out) count += s->points[c];
+    if (count == 0)
+        return fail(GBRS_ERR_INVALID, "chromosome %d holds every grid point: its leave-one-chromosome-out kinship has nothing to be formed from", leave_out);
+    GBRS_TRY(select_device(s->device));
+    const int64_t nn = s->n * s->n;
+    DevBuf<double> d_K;
+    GBRS_TRY(d_K.alloc((size_t)nn));
+    GBRS_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
+    GBRS_TRY(scan_kinship_products(s));
+    hipLaunchKernelGGL(lmm_kinship_sum_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, s->stream, nn, s->n_chrom, leave_out,
+                       scale, (double)count, s->kin_S.p, d_K.p);
+    GBRS_HIP_CHECK(hipEventRecord(s->ev[1], s->stream));
+    GBRS_HIP_CHECK(hipGetLastError());
+    const hipError_t done = hipStreamSynchronize(s->stream);
+    if (done != hipSuccess) {
+        s->kin_valid = false;
+        return fail(GBRS_ERR_HIP, "the kinship kernels failed: %s", hipGetErrorString(done));
+    }
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) s->t_kinship = ms;
+    GBRS_HIP_CHECK(hipMemcpy(K, d_K.p, d_K.bytes(), hipMemcpyDeviceToHost));
+    return GBRS_OK;
+}
+
+int gbrs_scan_lmm_prepare(gbrs_scan_t *s, int cz, const double *Z, int n_eig, const double *const *U, const double *const *lambda,
+                          const int32_t *eig_of_chrom) {
+    RoctxRange roctx_range("gbrs_scan_lmm_prepare");
+    if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (cz < 1 || cz > LM_MAX_C)
+        return fail(GBRS_ERR_INVALID, "covariate columns of the mixed model must be 1..%d (the intercept included), got %d", LM_MAX_C, cz);
+    if (!Z || !U || !lambda || !eig_of_chrom) return fail(GBRS_ERR_INVALID, "bad argument");
+    if (n_eig < 1 || n_eig > s->n_chrom)
+        return fail(GBRS_ERR_INVALID, "the decompositions must number 1..%d (one per chromosome at most), got %d", s->n_chrom, n_eig);
+    if (s->n <= (int64_t)cz + s->H - 1)
+        return fail(GBRS_ERR_INVALID, "%lld samples are too few for %d covariate columns and %d founders: need more than %d",
+                    (long long)s->n, cz, s->H, cz + s->H - 1);
+    if (s->n > LM_MAX_N)
+        return fail(GBRS_ERR_INVALID, "the mixed model takes at most %d samples, the cohort has %lld", LM_MAX_N, (long long)s->n);
+    const int n = (int)s->n;
+    for (int c = 0; c < s->n_chrom; ++c)
+        if (eig_of_chrom[c] < 0 || eig_of_chrom[c] >= n_eig)
+            return fail(GBRS_ERR_INVALID, "chromosome %d is mapped to decomposition %d of %d", c, eig_of_chrom[c], n_eig);
+    for (int64_t k = 0; k < (int64_t)n * cz; ++k)
+        if (!std::isfinite(Z[k]))
+            return fail(GBRS_ERR_INVALID, "covariates hold a value that is not finite (sample %lld, column %d)", (long long)(k / cz), (int)(k % cz));
+    for (int e = 0; e < n_eig; ++e) {
+        if (!U[e] || !lambda[e]) return fail(GBRS_ERR_INVALID, "decomposition %d is NULL", e);
+        double top = 0.0;
+        for (int i = 0; i < n; ++i) {
+            if (!std::isfinite(lambda[e][i]))
+                return fail(GBRS_ERR_INVALID, "decomposition %d: eigenvalue %d is not finite", e, i);
+            top = std::max(top, lambda[e][i]);
+        }
+        for (int i = 0; i < n; ++i)
+            if (!(lambda[e][i] > LM_LAMBDA * top))
+                return fail(GBRS_ERR_INVALID, "decomposition %d: eigenvalue %d is %g, not above %g of the largest (%g): the kinship is "
+                            "singular - the cohort has fewer independent dosage columns than samples", e, i, lambda[e][i], LM_LAMBDA, top);
+        for (int64_t k = 0; k < (int64_t)n * n; ++k)
+            if (!std::isfinite(U[e][k]))
+                return fail(GBRS_ERR_INVALID, "decomposition %d: the eigenvectors hold a value that is not finite (row %lld, column %lld)", e,
+                            (long long)(k / n), (long long)(k % n));
+    }
+    GBRS_TRY(select_device(s->device));
+    // staged in the call's own buffers: an earlier preparation stands until everything below has succeeded
+    const int64_t n_ld = ((int64_t)n + SC_KC - 1) / SC_KC * SC_KC;
+    DevBuf<double> d_U, d_lam, d_Z, d_Zs, d_R;
+    DevBuf<int32_t> d_eop;
+    GBRS_TRY(d_U.alloc((size_t)n_eig * n * n));
+    GBRS_TRY(d_lam.alloc((size_t)n_eig * n));
+    GBRS_TRY(d_Z.alloc((size_t)n * cz));
+    GBRS_TRY(d_Zs.alloc((size_t)n_eig * cz * n_ld));
+    GBRS_TRY(d_R.alloc((size_t)s->M * s->Hp * n_ld));
+    GBRS_TRY(d_eop.alloc((size_t)s->M));
+    std::vector<int32_t> eop((size_t)s->M);
+    for (int c = 0; c < s->n_chrom; ++c)
+        for (int64_t m = s->point_off[c]; m < s->point_off[c + 1]; ++m) eop[m] = eig_of_chrom[c];
+    for (int e = 0; e < n_eig; ++e) {
+        GBRS_HIP_CHECK(hipMemcpy(d_U.p + (size_t)e * n * n, U[e], (size_t)n * n * sizeof(double), hipMemcpyHostToDevice));
+        GBRS_HIP_CHECK(hipMemcpy(d_lam.p + (size_t)e * n, lambda[e], (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    }
+    GBRS_HIP_CHECK(hipMemcpy(d_Z.p, Z, d_Z.bytes(), hipMemcpyHostToDevice));
+    GBRS_HIP_CHECK(hipMemcpy(d_eop.p, eop.data(), d_eop.bytes(), hipMemcpyHostToDevice));
+    GBRS_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
+    for (int e = 0; e < n_eig; ++e)
+        scan_lmm_rotate(s, n_ld, cz, 1, 1, 1, cz, d_U.p + (size_t)e * n * n, d_Z.p, d_Zs.p + (size_t)e * cz * n_ld);
+    for (int c = 0; c < s->n_chrom; ++c)
+        scan_lmm_rotate(s, n_ld, (int64_t)s->points[c] * s->Hp, s->Hp, s->H - 1, s->H, s->M * s->H,
+                        d_U.p + (size_t)eig_of_chrom[c] * n * n, s->dosage.p + s->point_off[c] * s->H,
+                        d_R.p + s->point_off[c] * s->Hp * n_ld);
+    GBRS_HIP_CHECK(hipEventRecord(s->ev[1], s->stream));
+    GBRS_HIP_CHECK(hipGetLastError());
+    GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) s->t_lmm_rotate = ms;
+    s->lmm_U.swap(d_U);
+    s->lmm_lam.swap(d_lam);
+    s->lmm_Zs.swap(d_Zs);
+    s->lmm_R.swap(d_R);
+    s->lmm_eig_of_point.swap(d_eop);
+    s->lmm_cz = cz;
+    s->lmm_n_eig = n_eig;
+    s->lmm_n_ld = n_ld;
+    return GBRS_OK;
+}
+
+int gbrs_scan_lmm_run(gbrs_scan_t *s, int64_t P, const double *pheno, const double *hsq_in, double *lod, double *peak_lod,
+                      int64_t *peak_index, double *hsq, double *sigma2) {
+    RoctxRange roctx_range("gbrs_scan_lmm_run");
+    if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (s->lmm_cz == 0) return fail(GBRS_ERR_INVALID, "no mixed model on the handle: call gbrs_scan_lmm_prepare first");
+    if (P < 1 || !pheno) return fail(GBRS_ERR_INVALID, "bad argument");
+    const int n = (int)s->n, cz = s->lmm_cz, n_eig = s->lmm_n_eig;
+    for (int64_t k = 0; k < (int64_t)n * P; ++k)
+        if (!std::isfinite(pheno[k]))
+            return fail(GBRS_ERR_INVALID, "phenotype %lld holds a value that is not finite (sample %lld)", (long long)(k % P),
+                        (long long)(k / P));
+    if (hsq_in)
+        for (int64_t k = 0; k < P * n_eig; ++k)
+            if (!(hsq_in[k] >= 0.0 && hsq_in[k] <= 1.0))
+                return fail(GBRS_ERR_INVALID, "the heritability given for phenotype %lld and decomposition %d is %g, outside [0, 1]",
+                            (long long)(k / n_eig), (int)(k % n_eig), hsq_in[k]);
+    GBRS_TRY(select_device(s->device));
+    const int64_t pc_max = std::min(P, SC_PCHUNK), M = s->M, n_ld = s->lmm_n_ld;
+    const int Hp = s->Hp;
+    const size_t pe = (size_t)pc_max * n_eig;
+    DevBuf<double> y, ys, d_hin, d_hsq, d_sigma2, sw, qz, yt, rss0, d_lod, d_peak, ws;
+    DevBuf<int64_t> d_index;
+    DevBuf<int32_t> d_rmin, d_rmax;
+    GBRS_TRY(y.alloc((size_t)n * pc_max));
+    GBRS_TRY(ys.alloc(pe * n_ld));
+    if (hsq_in) GBRS_TRY(d_hin.alloc(pe));
+    GBRS_TRY(d_hsq.alloc(pe));
+    GBRS_TRY(d_sigma2.alloc(pe));
+    GBRS_TRY(sw.alloc(pe * n_ld));
+    GBRS_TRY(qz.alloc(pe * cz * n_ld));
+    GBRS_TRY(yt.alloc(pe * n_ld));
+    GBRS_TRY(rss0.alloc(pe));
+    GBRS_TRY(d_lod.alloc((size_t)pc_max * M));
+    GBRS_TRY(d_peak.alloc((size_t)pc_max * s->n_chrom));
+    GBRS_TRY(d_index.alloc((size_t)pc_max * s->n_chrom));
+    GBRS_TRY(d_rmin.alloc((size_t)pc_max));
+    GBRS_TRY(d_rmax.alloc((size_t)pc_max));
+    // a point's weighted columns: the workgroup's LDS, or past LM_LDS_BYTES a workspace and the points in batches
+    const size_t w_bytes = (size_t)Hp * n_ld * sizeof(double);
+    const bool in_lds = w_bytes <= LM_LDS_BYTES;
+    const int64_t tiles_max = (pc_max + LM_TILE - 1) / LM_TILE;
+    const int64_t batch = in_lds ? M : std::max<int64_t>(1, std::min<int64_t>(M, (int64_t)(LM_WS_BYTES / (w_bytes * tiles_max))));
+    if (!in_lds) GBRS_TRY(ws.alloc((size_t)batch * tiles_max * Hp * n_ld));
+    std::vector<int32_t> rmin((size_t)P), rmax((size_t)P);
+    double t_rotate = 0.0, t_null = 0.0, t_point = 0.0;
+    hipEvent_t mark[4] = {};
+    struct Marks {
+        hipEvent_t *ev;
+        ~Marks() {
+            for (int k = 0; k < 4; ++k)
+                if (ev[k]) (void)hipEventDestroy(ev[k]);
+        }
+    } marks{mark};
+    for (auto &e : mark) GBRS_HIP_CHECK(hipEventCreate(&e));
+    GBRS_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
+    for (int64_t p0 = 0; p0 < P; p0 += SC_PCHUNK) {
+        const int64_t pc = std::min(SC_PCHUNK, P - p0);
+        GBRS_HIP_CHECK(hipMemcpy2DAsync(y.p, (size_t)pc * sizeof(double), pheno + p0, (size_t)P * sizeof(double),
+                                        (size_t)pc * sizeof(double), (size_t)n, hipMemcpyHostToDevice, s->stream));
+        if (hsq_in)
+            GBRS_HIP_CHECK(hipMemcpyAsync(d_hin.p, hsq_in + p0 * n_eig, (size_t)pc * n_eig * sizeof(double), hipMemcpyHostToDevice, s->stream));
+        GBRS_HIP_CHECK(hipEventRecord(mark[0], s->stream));
+        for (int e = 0; e < n_eig; ++e)
+            scan_lmm_rotate(s, n_ld, pc, 1, 1, 1, pc, s->lmm_U.p + (size_t)e * n * n, y.p, ys.p + (size_t)e * pc * n_ld);
+        GBRS_HIP_CHECK(hipEventRecord(mark[1], s->stream));
+        hipLaunchKernelGGL(lmm_null_kernel, dim3((unsigned)pc, (unsigned)n_eig), dim3(64), 0, s->stream, n, cz, n_ld, pc, n_eig, ys.p,
+                           s->lmm_Zs.p, s->lmm_lam.p, hsq_in ? d_hin.p : nullptr, d_hsq.p, d_sigma2.p, sw.p, qz.p, yt.p, rss0.p,
+                           d_rmin.p, d_rmax.p);
+        GBRS_HIP_CHECK(hipEventRecord(mark[2], s->stream));
+        const unsigned tiles = (unsigned)((pc + LM_TILE - 1) / LM_TILE);
+        for (int64_t m0 = 0; m0 < M; m0 += batch) {
+            const dim3 grid((unsigned)std::min(batch, M - m0), tiles);
+            auto launch = [&](auto kernel) {
+                hipLaunchKernelGGL(kernel, grid, dim3(SC_THREADS), in_lds ? w_bytes : 0, s->stream, n, M, m0, s->H, cz, n_ld, pc, n_eig,
+                                   LM_TILE, 0.5 * n, s->lmm_eig_of_point.p, s->lmm_R.p, sw.p, qz.p, yt.p, rss0.p,
+                                   in_lds ? nullptr : ws.p, d_lod.p, d_rmin.p, d_rmax.p);
+            };
+            if (Hp == 8) launch(lmm_point_kernel<8>);
+            else launch(lmm_point_kernel<16>);
+        }
+        GBRS_HIP_CHECK(hipEventRecord(mark[3], s->stream));
+        hipLaunchKernelGGL(scan_peak_kernel, dim3((unsigned)s->n_chrom, (unsigned)pc), dim3(64), 0, s->stream, M, s->n_chrom,
+                           s->d_point_off.p, d_lod.p, d_peak.p, d_index.p);
+        GBRS_HIP_CHECK(hipGetLastError());
+        GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, mark[0], mark[1]) == hipSuccess) t_rotate += ms;
+        if (hipEventElapsedTime(&ms, mark[1], mark[2]) == hipSuccess) t_null += ms;
+        if (hipEventElapsedTime(&ms, mark[2], mark[3]) == hipSuccess) t_point += ms;
+        if (lod) GBRS_HIP_CHECK(hipMemcpy(lod + p0 * M, d_lod.p, (size_t)pc * M * sizeof(double), hipMemcpyDeviceToHost));
+        if (peak_lod)
+            GBRS_HIP_CHECK(hipMemcpy(peak_lod + p0 * s->n_chrom, d_peak.p, (size_t)pc * s->n_chrom * sizeof(double), hipMemcpyDeviceToHost));
+        if (peak_index)
+            GBRS_HIP_CHECK(hipMemcpy(peak_index + p0 * s->n_chrom, d_index.p, (size_t)pc * s->n_chrom * sizeof(int64_t), hipMemcpyDeviceToHost));
+        if (hsq) GBRS_HIP_CHECK(hipMemcpy(hsq + p0 * n_eig, d_hsq.p, (size_t)pc * n_eig * sizeof(double), hipMemcpyDeviceToHost));
+        if (sigma2) GBRS_HIP_CHECK(hipMemcpy(sigma2 + p0 * n_eig, d_sigma2.p, (size_t)pc * n_eig * sizeof(double), hipMemcpyDeviceToHost));
+        GBRS_HIP_CHECK(hipMemcpy(rmin.data() + p0, d_rmin.p, (size_t)pc * sizeof(int32_t), hipMemcpyDeviceToHost));
+        GBRS_HIP_CHECK(hipMemcpy(rmax.data() + p0, d_rmax.p, (size_t)pc * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    GBRS_HIP_CHECK(hipEventRecord(s->ev[1], s->stream));
+    GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) s->t_lmm_run = ms;
+    s->t_lmm_null = t_null;
+    s->t_lmm_point = t_point;
+    s->lmm_P = P;
+    s->lmm_rank_min.swap(rmin);
+    s->lmm_rank_max.swap(rmax);
+    (void)t_rotate;
+    s->lmm_peak_bytes = s->d_point_off.bytes() + s->dosage.bytes() + s->qz.bytes() + s->W.bytes() + s->d_rank.bytes() + s->y.bytes() +
+                        s->yt.bytes() + s->rss0.bytes() + s->lod.bytes() + s->peak_lod.bytes() + s->peak_index.bytes() + s->snp_bytes() +
+                        s->kin_S.bytes() + s->lmm_bytes() + y.bytes() + ys.bytes() + d_hin.bytes() + d_hsq.bytes() + d_sigma2.bytes() +
+                        sw.bytes() + qz.bytes() + yt.bytes() + rss0.bytes() + d_lod.bytes() + d_peak.bytes() + d_index.bytes() +
+                        d_rmin.bytes() + d_rmax.bytes() + ws.bytes();
+    return GBRS_OK;
+}
+
+int gbrs_scan_lmm_ranks(gbrs_scan_t *s, int32_t *rank_min, int32_t *rank_max) {
+    if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (rank_min) std::memcpy(rank_min, s->lmm_rank_min.data(), s->lmm_rank_min.size() * sizeof(int32_t));
+    if (rank_max) std::memcpy(rank_max, s->lmm_rank_max.data(), s->lmm_rank_max.size() * sizeof(int32_t));
+    return GBRS_OK;
+}
+
+int gbrs_scan_lmm_info(gbrs_scan_t *s, gbrs_scan_lmm_info_t *info) {
+    if (!s || !info) return fail(GBRS_ERR_INVALID, "bad argument");
+    info->cz = s->lmm_cz;
+    info->n_eig = s->lmm_n_eig;
+    info->P = s->lmm_P;
+    info->last_kinship_ms = s->t_kinship;
+    info->last_rotate_ms = s->t_lmm_rotate;
+    info->last_null_ms = s->t_lmm_null;
+    info->last_point_ms = s->t_lmm_point;
+    info->last_run_ms = s->t_lmm_run;
+    info->device_bytes = s->kin_S.bytes() + s->lmm_bytes();
+    info->peak_device_bytes = s->lmm_peak_bytes;
     return GBRS_OK;
 }
 

@@ -1403,7 +1403,9 @@ class ReconstructOptions:
     `scan_mediate_top` are scan.mediate_options'.
     `scan_effects`, `scan_lod_drop`: the founder effects of the scan's peaks of at least
     `scan_effects_min_lod` go to `<scan_out>.scan.effects.npz` and `<scan_out>.scan.effects.tsv`, named by the samples'
-    haplotype header; the peaks' LOD support intervals join the scan's two files (scan.effects_options)."""
+    haplotype header; the peaks' LOD support intervals join the scan's two files (scan.effects_options).
+    `scan_kinship`, `scan_kinship_out`: the scan is the linear mixed model's with the cohort's own
+    leave-one-chromosome-out or overall kinship (scan.kinship_options); the other scan passes are then refused."""
     expr_threshold: float = 1.5
     sigma: float = 0.12
     grid_genoprobs: bool = False
@@ -1442,6 +1444,8 @@ class ReconstructOptions:
     scan_effects: bool = False
     scan_effects_min_lod: float = None
     scan_lod_drop: float = None
+    scan_kinship: str = None
+    scan_kinship_out: bool = False
 
     @classmethod
     def of(cls, keywords):
@@ -1473,7 +1477,8 @@ class ReconstructOptions:
                         scan_mediate=self.scan_mediate, scan_mediate_min_lod=self.scan_mediate_min_lod,
                         scan_mediate_top=self.scan_mediate_top, scan_mediator_file=self.scan_mediator_file,
                         scan_effects=self.scan_effects, scan_effects_min_lod=self.scan_effects_min_lod,
-                        scan_lod_drop=self.scan_lod_drop)
+                        scan_lod_drop=self.scan_lod_drop, scan_kinship=self.scan_kinship,
+                        scan_kinship_out=self.scan_kinship_out, scan_snps=self.scan_snps)
         check_scan_snp_args(self.scan_snps, self.snp_file, self.scan_pheno, grid_file, cohort=cohort)
 
 
@@ -1761,7 +1766,8 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
                      scan_perms: int = None, scan_perm_seed: int = None, scan_perm_alpha=None, scan_perm_chromosomes=None,
                      scan_perm_pheno: str = None, scan_snps: bool = False, scan_mediate: bool = False,
                      scan_mediate_min_lod: float = None, scan_mediate_top: int = None, scan_mediator_file: str = None,
-                     scan_effects: bool = False, scan_effects_min_lod: float = None, scan_lod_drop: float = None) -> list:
+                     scan_effects: bool = False, scan_effects_min_lod: float = None, scan_lod_drop: float = None,
+                     scan_kinship: str = None, scan_kinship_out: bool = False) -> list:
     """`gbrs reconstruct` for a cohort whose genes.tpm files exist (extension): one context, the tables on the device
     once, the samples through the HMM in launches of up to `batch_size`, and every pass the options ask for once per
     launch.  Every sample gets the files the single-sample call writes for its outbase.  All samples must carry the same
@@ -1776,6 +1782,8 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
     scan_med = scan_mod.mediate_options(scan_mediate, scan_mediate_min_lod, scan_mediate_top, scan_mediator_file)
     scan_eff = scan_mod.effects_options(scan_effects, scan_effects_min_lod, scan_lod_drop)
     with_effects = scan_eff is not None and scan_eff['min_lod'] is not None
+    scan_kin = scan_mod.kinship_options(scan_kinship, scan_kinship_out, scan_perms, scan_snps, scan_mediate, scan_effects,
+                                        scan_lod_drop)
     clock = time.perf_counter
     marks = stage_times if stage_times is not None else {}
     if len(expression_files) != len(outbases):
@@ -1928,7 +1936,7 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
                                  np.concatenate([np.asarray(ctx.grid[c], dtype=np.float64) for _, _, c in slices]),
                                  list(ctx.chroms), scan_min_lod, scan_lod_matrix, perm=scan_perm, stage_times=marks,
                                  snps=shared.snps if scan_snps else None, snp_grid=ctx.grid, mediate=scan_med,
-                                 effects=scan_eff, founders=haplotypes)
+                                 effects=scan_eff, founders=haplotypes, kinship=scan_kin)
             marks['scan'] += clock() - t0 - (marks['scan_perm'] if scan_perm is not None else 0.0) - \
                 (marks['scan_snps'] if scan_snps else 0.0) - (marks['mediate'] if scan_med is not None else 0.0) - \
                 (marks['effects'] if with_effects else 0.0)

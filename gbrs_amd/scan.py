@@ -1,6 +1,8 @@
 """Genome scan of phenotypes on founder dosages (extension): `gbrs reconstruct --scan-pheno` and
 `gbrs scan`.  Haley-Knott regression with additive covariates on the device (gbrs_scan_*, gbrs_amd/csrc/scan.hip); the
-host side here is the covariates' QR, the file readers and the writers.  No mixed model.  `--scan-snps` / `gbrs scan
+host side here is the covariates' QR, the file readers and the writers.  `--scan-kinship loco|overall`: the
+linear mixed model with a kinship of the cohort's own dosages (gbrs_scan_kinship, gbrs_scan_lmm_prepare, gbrs_scan_lmm_run);
+the host side is the kinships' eigendecomposition.  `--scan-snps` / `gbrs scan
 --snp-file`: the 1-df test of founder SNPs on the same prepared cohort (gbrs_scan_set_snps, gbrs_scan_snps).
 `--scan-mediate`: the scan's peaks conditioned on every other phenotype in turn (gbrs_scan_mediate).
 `--scan-effects`, `--scan-lod-drop`: the founder effects at the scan's peaks with their standard errors
@@ -23,6 +25,8 @@ DEFAULT_MEDIATE_MIN_LOD = 6.0     # --scan-mediate-min-lod: the peaks that are m
 DEFAULT_MEDIATE_TOP = 5           # --scan-mediate-top: the mediators listed per peak
 MEDIATE_MAX_TOP = 64              # the places gbrs_scan_mediate's top list has
 DEFAULT_EFFECTS_MIN_LOD = DEFAULT_MEDIATE_MIN_LOD     # --scan-effects-min-lod: the peaks whose founder effects are formed
+KINSHIP_MODES = ('loco', 'overall')                   # --scan-kinship
+LMM_MAX_COVARIATES = 16                               # covariate columns of the mixed model, the intercept included
 
 
 class GenomeScan:
@@ -30,7 +34,9 @@ class GenomeScan:
     prepare(covariates) builds the phenotype-independent part once, run(pheno) scans any number of phenotypes;
     set_snps + run_snps(pheno) test founder SNPs with one degree of freedom on the same cohort (DESIGN.md §29);
     mediate(target, point, mediator) conditions peaks on mediators; effects(pheno, column, point) gives
-    the founder effects at chosen points and run(pheno, lod_drop=d) the peaks' LOD support intervals."""
+    the founder effects at chosen points and run(pheno, lod_drop=d) the peaks' LOD support intervals (DESIGN.md §31);
+    kinship() gives the cohort's kinship matrices, prepare_lmm(covariates, kinship) + run_lmm(pheno) scan under the linear
+    mixed model, independent of prepare / run."""
 
     def __init__(self, num_haps, points_per_chrom, device=0):
         self.H = int(num_haps)
@@ -38,6 +44,9 @@ class GenomeScan:
         self.M = int(self.points.sum())
         self.n = 0
         self.prepared = False
+        self.lmm_prepared = False
+        self.eig_of_chrom = None
+        self._dosage_total = 1.0
         h = C.c_void_p()
         _lib.check(_lib.load().gbrs_scan_create(int(device), len(self.points), _lib.ptr(self.points), self.H, C.byref(h)))
         self._h = h
@@ -61,14 +70,18 @@ class GenomeScan:
         if d.ndim != 3 or d.shape[1:] != (self.M, self.H):
             raise ValueError(f'dosage has shape {np.shape(dosage)}, expected (n, {self.M}, {self.H})')
         _lib.check(_lib.load().gbrs_scan_append(self._h, len(d), _lib.ptr(d)))
+        if self.n == 0 and len(d):
+            self._dosage_total = float(np.round(d[0, 0].sum(), 12))     # 1.0 for rows that add up to 1 within rounding
         self.n += len(d)
         self.prepared = False
+        self.lmm_prepared = False
 
     def append_from(self, hmm, sample=None):
         """The grid dosages of `hmm`'s last run, device to device: every sample of the run, or the one given."""
         _lib.check(_lib.load().gbrs_scan_append_hmm(self._h, hmm._h, -1 if sample is None else int(sample)))
         self.n += hmm.n_samples if sample is None else 1
         self.prepared = False
+        self.lmm_prepared = False
 
     def prepare(self, covariates=None, names=None):
         """covariates: [n, c] with the intercept (a column of ones) first, or None for the intercept alone."""
@@ -273,6 +286,106 @@ class GenomeScan:
         _lib.check(_lib.load().gbrs_scan_effects_info(self._h, C.byref(raw)))
         return {'T': raw.T, 'P': raw.P, 'pass_ms': raw.last_pass_ms, 'peak_device_bytes': raw.peak_device_bytes}
 
+    def kinship(self, leave_out=None, scale=None):
+        """The cohort's kinship [n, n] from its dosages on the device: scale x (sum over the chromosomes
+        other than `leave_out` - an index, None: all of them - of A_c A_c') / (their grid points).  scale: default
+        2 / t^2 with t the total of a grid point's dosages (R/qtl2's doubled kinship of allele probabilities): the first
+        appended sample's first grid point, rounded at the twelfth decimal; 1 for a cohort appended from an HMM handle."""
+        t = self._dosage_total
+        scale = 2.0 / (t * t) if scale is None else float(scale)
+        out = np.empty((self.n, self.n))
+        _lib.check(_lib.load().gbrs_scan_kinship(self._h, -1 if leave_out is None else int(leave_out), scale, _lib.ptr(out)))
+        return out
+
+    def prepare_lmm(self, covariates=None, kinship='loco', names=None):
+        """The mixed model's phenotype-independent part.  covariates: as for prepare(), at most 16 columns.
+        kinship: 'loco' (one matrix per chromosome, from the other chromosomes), 'overall' (one, from all), an [n, n]
+        array (the caller's, for every chromosome) or a list of one array per chromosome.  The matrices are factored here
+        (numpy.linalg.eigh); one whose smallest eigenvalue is not above 1e-10 of its largest is refused.  Returns the
+        matrices that were used, in the order of their decompositions; `eig_of_chrom` maps the chromosomes to them."""
+        z = np.ones((self.n, 1)) if covariates is None else np.ascontiguousarray(covariates, dtype=np.float64)
+        if z.ndim != 2 or z.shape[0] != self.n:
+            raise ValueError(f'covariates have shape {z.shape} for {self.n} samples')
+        if z.shape[1] > LMM_MAX_COVARIATES:
+            raise ValueError(f'the mixed model takes at most {LMM_MAX_COVARIATES} covariate columns (the intercept included), '
+                             f'got {z.shape[1]}')
+        covariate_basis(z, names)               # its checks: finite values, the intercept first, full column rank
+        nc = len(self.points)
+        if isinstance(kinship, str):
+            if kinship not in KINSHIP_MODES:
+                raise ValueError(f'kinship must be one of {", ".join(KINSHIP_MODES)}, an array or a list of arrays, got {kinship}')
+            if kinship == 'loco':
+                matrices, eig_of_chrom = [self.kinship(leave_out=c) for c in range(nc)], list(range(nc))
+            else:
+                matrices, eig_of_chrom = [self.kinship()], [0] * nc
+        elif isinstance(kinship, (list, tuple)):
+            if len(kinship) != nc:
+                raise ValueError(f'{len(kinship)} kinship matrices for {nc} chromosomes')
+            matrices, eig_of_chrom = [np.asarray(k, dtype=np.float64) for k in kinship], list(range(nc))
+        else:
+            matrices, eig_of_chrom = [np.asarray(kinship, dtype=np.float64)], [0] * nc
+        vectors, values = [], []
+        for e, k in enumerate(matrices):
+            if k.shape != (self.n, self.n):
+                raise ValueError(f'kinship {e} has shape {k.shape} for {self.n} samples')
+            if not np.isfinite(k).all():
+                raise ValueError(f'kinship {e} holds a value that is not finite')
+            lam, u = np.linalg.eigh(k)
+            vectors.append(np.ascontiguousarray(u))
+            values.append(np.ascontiguousarray(lam))
+        mapping = np.asarray(eig_of_chrom, dtype=np.int32)
+        _lib.check(_lib.load().gbrs_scan_lmm_prepare(self._h, z.shape[1], _lib.ptr(z), len(matrices), _lib.ptr_table(vectors),
+                                                     _lib.ptr_table(values), _lib.ptr(mapping)))
+        self.lmm_prepared = True
+        self.eig_of_chrom = mapping
+        return matrices
+
+    def run_lmm(self, pheno, want_lod=True, hsq=None):
+        """pheno: [n, P] (or [n]) under the prepared mixed model.  Every column's mean is subtracted before the upload (the
+        intercept absorbs it) and a constant column goes as zeros: hsq 0 and LODs 0.0.  hsq: [P, n_chrom] heritabilities
+        in [0, 1] to scan with instead of fitting them (chromosomes that share a decomposition must agree; the first
+        one's value is taken).  Returns `peak_lod`, `peak_index` [P, n_chrom], `hsq` and `sigma2` [P, n_chrom] (per
+        chromosome, through `eig_of_chrom`), `rank_min`, `rank_max` [P] and, with want_lod, `lod` [P, M]."""
+        if not self.lmm_prepared:
+            raise _lib.GbrsHipError(_lib.GBRS_ERR_INVALID, 'no mixed model on the handle: call prepare_lmm first')
+        y = np.array(pheno, dtype=np.float64, order='C')
+        if y.ndim == 1:
+            y = y[:, None]
+        if y.ndim != 2 or y.shape[0] != self.n or y.shape[1] < 1:
+            raise ValueError(f'phenotypes have shape {np.shape(pheno)} for {self.n} samples')
+        constant = (y == y[0]).all(axis=0)
+        if np.isfinite(y).all():        # a column's mean from the column alone, whatever stands beside it: its own contiguous row
+            y = np.ascontiguousarray(y - np.ascontiguousarray(y.T).sum(axis=1) / self.n)
+        y[:, constant] = 0.0
+        P, nc, mapping = y.shape[1], len(self.points), self.eig_of_chrom
+        n_eig = int(mapping.max()) + 1
+        given = None
+        if hsq is not None:
+            by_chrom = np.asarray(hsq, dtype=np.float64)
+            if by_chrom.shape != (P, nc):
+                raise ValueError(f'hsq has shape {by_chrom.shape}, expected ({P}, {nc})')
+            first = [int(np.flatnonzero(mapping == e)[0]) for e in range(n_eig)]
+            given = np.ascontiguousarray(by_chrom[:, first])
+        lod = np.empty((P, self.M)) if want_lod else None
+        peak, index = np.empty((P, nc)), np.empty((P, nc), dtype=np.int64)
+        fitted, sigma2 = np.empty((P, n_eig)), np.empty((P, n_eig))
+        _lib.check(_lib.load().gbrs_scan_lmm_run(self._h, P, _lib.ptr(y), _lib.ptr(given), _lib.ptr(lod), _lib.ptr(peak),
+                                                 _lib.ptr(index), _lib.ptr(fitted), _lib.ptr(sigma2)))
+        rank_min, rank_max = np.empty(P, dtype=np.int32), np.empty(P, dtype=np.int32)
+        _lib.check(_lib.load().gbrs_scan_lmm_ranks(self._h, _lib.ptr(rank_min), _lib.ptr(rank_max)))
+        out = {'peak_lod': peak, 'peak_index': index, 'hsq': fitted[:, mapping], 'sigma2': sigma2[:, mapping],
+               'rank_min': rank_min, 'rank_max': rank_max}
+        if want_lod:
+            out['lod'] = lod
+        return out
+
+    def lmm_info(self):
+        raw = _lib.ScanLmmInfo()
+        _lib.check(_lib.load().gbrs_scan_lmm_info(self._h, C.byref(raw)))
+        return {'cz': raw.cz, 'n_eig': raw.n_eig, 'P': raw.P, 'kinship_ms': raw.last_kinship_ms, 'rotate_ms': raw.last_rotate_ms,
+                'null_ms': raw.last_null_ms, 'point_ms': raw.last_point_ms, 'run_ms': raw.last_run_ms,
+                'device_bytes': raw.device_bytes, 'peak_device_bytes': raw.peak_device_bytes}
+
     def info(self):
         raw = _lib.ScanInfo()
         _lib.check(_lib.load().gbrs_scan_info(self._h, C.byref(raw), None))
@@ -460,14 +573,33 @@ def effects_options(scan_effects=False, scan_effects_min_lod=None, scan_lod_drop
     return {'min_lod': min_lod, 'lod_drop': drop}
 
 
+def kinship_options(scan_kinship=None, scan_kinship_out=False, scan_perms=None, scan_snps=False, scan_mediate=False,
+                    scan_effects=False, scan_lod_drop=None):
+    """`--scan-kinship loco|overall [--scan-kinship-out]` as one dict, or None without `--scan-kinship`;
+    `--scan-kinship-out` alone is refused.  The passes that work on the unweighted W are refused next to the mixed model,
+    one line each.  Refused before a file is read."""
+    if scan_kinship is None:
+        if scan_kinship_out:
+            raise RuntimeError('--scan-kinship-out needs --scan-kinship')
+        return None
+    if scan_kinship not in KINSHIP_MODES:
+        raise RuntimeError(f'--scan-kinship must be one of {", ".join(KINSHIP_MODES)}, got {scan_kinship}')
+    for name, value in (('--scan-perms', scan_perms), ('--scan-snps', scan_snps or None), ('--scan-mediate', scan_mediate or None),
+                        ('--scan-effects', scan_effects or None), ('--scan-lod-drop', scan_lod_drop)):
+        if value is not None:
+            raise RuntimeError(f'{name} cannot be combined with --scan-kinship: its pass uses the unweighted scan')
+    return {'mode': scan_kinship, 'out': bool(scan_kinship_out)}
+
+
 def check_scan_args(scan_pheno=None, scan_covar=None, scan_rankz=False, scan_out=None, scan_min_lod=None,
                     scan_lod_matrix=False, grid_file=None, cohort=False, scan_perms=None, scan_perm_seed=None,
                     scan_perm_alpha=None, scan_perm_chromosomes=None, scan_perm_pheno=None, scan_mediate=False,
                     scan_mediate_min_lod=None, scan_mediate_top=None, scan_mediator_file=None, scan_effects=False,
-                    scan_effects_min_lod=None, scan_lod_drop=None):
+                    scan_effects_min_lod=None, scan_lod_drop=None, scan_kinship=None, scan_kinship_out=False, scan_snps=False):
     """`--scan-pheno FILE [--scan-covar FILE] [--scan-rankz] [--scan-out PREFIX] [--scan-min-lod X] [--scan-lod-matrix]`,
-    the `--scan-perm*` options (perm_options), the `--scan-mediat*` options (mediate_options) and `--scan-effects`,
-    `--scan-effects-min-lod`, `--scan-lod-drop` (effects_options):
+    the `--scan-perm*` options (perm_options), the `--scan-mediat*` options (mediate_options), `--scan-effects`,
+    `--scan-effects-min-lod`, `--scan-lod-drop` (effects_options) and `--scan-kinship`, `--scan-kinship-out`
+    (kinship_options):
     every option needs the phenotypes, the phenotypes need `--grid-file` and a cohort (`--sample-file`): one sample
     cannot be scanned.  Refused before a file is read."""
     given = {'--scan-covar': scan_covar, '--scan-rankz': scan_rankz or None, '--scan-out': scan_out,
@@ -477,10 +609,11 @@ def check_scan_args(scan_pheno=None, scan_covar=None, scan_rankz=False, scan_out
              '--scan-mediate': scan_mediate or None, '--scan-mediate-min-lod': scan_mediate_min_lod,
              '--scan-mediate-top': scan_mediate_top, '--scan-mediator-file': scan_mediator_file,
              '--scan-effects': scan_effects or None, '--scan-effects-min-lod': scan_effects_min_lod,
-             '--scan-lod-drop': scan_lod_drop}
+             '--scan-lod-drop': scan_lod_drop, '--scan-kinship': scan_kinship, '--scan-kinship-out': scan_kinship_out or None}
     perm_options(scan_perms, scan_perm_seed, scan_perm_alpha, scan_perm_chromosomes, scan_perm_pheno)
     mediate_options(scan_mediate, scan_mediate_min_lod, scan_mediate_top, scan_mediator_file)
     effects_options(scan_effects, scan_effects_min_lod, scan_lod_drop)
+    kinship_options(scan_kinship, scan_kinship_out, scan_perms, scan_snps, scan_mediate, scan_effects, scan_lod_drop)
     if scan_pheno is None:
         for name, value in given.items():
             if value is not None:
@@ -567,14 +700,19 @@ def scan_design(ids, pheno, covar=None, use_rankz=False):
 
 
 def write_scan(prefix, phenotypes, samples, covariates, chrom, pos, chrom_names, result, rank, min_lod=0.0, perm=None,
-               lod_drop=None):
+               lod_drop=None, kinship_mode=None):
     """`<prefix>.scan.npz` and `<prefix>.scan.peaks.tsv`.  chrom / pos: per grid point, in the scan's point order;
     chrom_names: the scan's chromosomes, as peak_lod's columns.  perm (with `--scan-perms`): `perm_max` [Pp, B] of the
     phenotypes `columns`, `alphas`, `seed` and `mask` over chrom_names; the .npz gains the perm_* arrays and the peaks
     file the columns `pvalue` and `threshold_<first level>`, NA where nothing was permuted.  Without it both files are
     what they were before the permutations existed.  lod_drop (with `--scan-lod-drop`; result then holds `support_lo`
     and `support_hi`): the .npz gains both and `lod_drop`, the peaks file the columns `support_lo` and `support_hi` - the
-    positions of the interval's ends - after every other column."""
+    positions of the interval's ends - after every other column.  kinship_mode (with `--scan-kinship`; result is
+    GenomeScan.run_lmm's and rank is None): the .npz holds `hsq`, `sigma2`, `rank_min`, `rank_max` and `kinship_mode`
+    instead of `rank`, and the peaks file gains the column `hsq`, the heritability the chromosome was scanned with."""
+    if kinship_mode is not None:
+        write_scan_lmm(prefix, phenotypes, samples, covariates, chrom, pos, chrom_names, result, min_lod, kinship_mode)
+        return
     arrays = dict(phenotypes=np.array(phenotypes), samples=np.array(samples), covariates=np.array(covariates),
                   chrom=np.array(chrom), pos=np.asarray(pos, dtype=np.float64), rank=np.asarray(rank),
                   peak_lod=result['peak_lod'], peak_index=result['peak_index'])
@@ -601,6 +739,34 @@ def write_scan(prefix, phenotypes, samples, covariates, chrom, pos, chrom_names,
                 if peak[p, c] >= min_lod:
                     out.write(f'{name}\t{chrom_names[c]}\t{repr(float(pos[index[p, c]]))}\t{repr(float(peak[p, c]))}\t'
                               f'{int(c == top)}{ends(p, c)}\n')
+
+
+def write_scan_lmm(prefix, phenotypes, samples, covariates, chrom, pos, chrom_names, result, min_lod, kinship_mode):
+    """write_scan's two files for the mixed model."""
+    arrays = dict(phenotypes=np.array(phenotypes), samples=np.array(samples), covariates=np.array(covariates),
+                  chrom=np.array(chrom), pos=np.asarray(pos, dtype=np.float64), peak_lod=result['peak_lod'],
+                  peak_index=result['peak_index'], hsq=result['hsq'], sigma2=result['sigma2'], rank_min=result['rank_min'],
+                  rank_max=result['rank_max'], kinship_mode=np.array(kinship_mode))
+    if 'lod' in result:
+        arrays['lod'] = result['lod']
+    np.savez(f'{prefix}.scan.npz', **arrays)
+    peak, index, hsq = result['peak_lod'], result['peak_index'], result['hsq']
+    with open(f'{prefix}.scan.peaks.tsv', 'w') as out:
+        out.write('#phenotype\tchromosome\tposition\tlod\tgenome_wide_max\thsq\n')
+        for p, name in enumerate(phenotypes):
+            on = [c for c in range(len(chrom_names)) if index[p, c] >= 0]
+            top = max(on, key=lambda c: (peak[p, c], -c)) if on else None
+            for c in on:
+                if peak[p, c] >= min_lod:
+                    out.write(f'{name}\t{chrom_names[c]}\t{repr(float(pos[index[p, c]]))}\t{repr(float(peak[p, c]))}\t'
+                              f'{int(c == top)}\t{repr(float(hsq[p, c]))}\n')
+
+
+def write_scan_kinship(prefix, samples, chrom_names, matrices, eig_of_chrom, kinship_mode):
+    """`<prefix>.scan.kinship.npz` (`--scan-kinship-out`): `kinship` [k, n, n], the matrix of each chromosome
+    (`kinship_of_chromosome`, over `chromosomes`), the sample ids and the mode."""
+    np.savez(f'{prefix}.scan.kinship.npz', kinship=np.stack(matrices), kinship_of_chromosome=np.asarray(eig_of_chrom, dtype=np.int32),
+             chromosomes=np.array([str(c) for c in chrom_names]), samples=np.array(samples), kinship_mode=np.array(kinship_mode))
 
 
 def write_scan_perm(prefix, phenotypes, pos, chrom_names, peak, index, min_lod, perm, arrays, ends=lambda p, c: '',
@@ -833,16 +999,29 @@ def finish_scan_effects(scan, prefix, ids, pheno, covariates, y, min_lod, result
 
 
 def finish_scan(scan, prefix, ids, pheno, covar, use_rankz, chrom, pos, chrom_names, min_lod=None, lod_matrix=False,
-                perm=None, stage_times=None, snps=None, snp_grid=None, mediate=None, effects=None, founders=None):
+                perm=None, stage_times=None, snps=None, snp_grid=None, mediate=None, effects=None, founders=None, kinship=None):
     """prepare + run + the two files for the cohort `scan` holds, whose samples are `ids` in append order (every one with
     its rows in the tables).  perm: perm_options' dict, or None; with it the permutation pass runs after the scan on the
     phenotypes and chromosomes it names and its wall-clock seconds go to stage_times['scan_perm'].  mediate:
     mediate_options' dict, or None; with it the scan's peaks are mediated after everything else (finish_scan_mediation).
     effects: effects_options' dict, or None; its lod_drop makes the run form the support intervals, its min_lod makes
     the founder effects of the peaks follow (finish_scan_effects), named by `founders`.
-    Returns GenomeScan.info() after the run."""
+    kinship: kinship_options' dict, or None; with it the scan is the mixed model's and none of the other
+    passes runs.  Returns GenomeScan.info() after the run."""
     kept, y, z, names = scan_design(ids, pheno, covar, use_rankz)
     assert len(kept) == len(ids) == scan.n
+    if kinship is not None:
+        matrices = scan.prepare_lmm(z, kinship['mode'], names)
+        result = scan.run_lmm(y, want_lod=bool(lod_matrix) or y.shape[1] * scan.M <= LOD_MATRIX_LIMIT)
+        write_scan(prefix, pheno[0], ids, names, chrom, pos, chrom_names, result, None, 0.0 if min_lod is None else min_lod,
+                   kinship_mode=kinship['mode'])
+        if kinship['out']:
+            write_scan_kinship(prefix, ids, chrom_names, matrices, scan.eig_of_chrom, kinship['mode'])
+        timing = scan.lmm_info()
+        logger.info(f'scan: {len(ids)} samples, {y.shape[1]} phenotypes, {scan.M} grid points under the mixed model '
+                    f'({kinship["mode"]} kinship); kinship {timing["kinship_ms"]:.1f} ms, rotation {timing["rotate_ms"]:.1f} ms, '
+                    f'null fits {timing["null_ms"]:.1f} ms, weighted scan {timing["point_ms"]:.1f} ms on the device')
+        return scan.info()
     if perm is not None:
         columns, mask = perm_plan(perm, pheno[0], [str(c) for c in chrom_names])     # refused before the device runs
     scan.prepare(z, names)
@@ -880,13 +1059,14 @@ def scan_tables(dosage_list, grid_file, pheno_file, covar_file=None, use_rankz=F
                 lod_matrix=False, device=0, scan_perms=None, scan_perm_seed=None, scan_perm_alpha=None,
                 scan_perm_chromosomes=None, scan_perm_pheno=None, stage_times=None, snp_file=None, scan_mediate=False,
                 scan_mediate_min_lod=None, scan_mediate_top=None, scan_mediator_file=None, scan_effects=False,
-                scan_effects_min_lod=None, scan_lod_drop=None):
+                scan_effects_min_lod=None, scan_lod_drop=None, scan_kinship=None, scan_kinship_out=False):
     """`gbrs scan`: the cohort from dosage tables in `gbrs export` format (lines `id<TAB>dosage table`), rows in the grid
     file's order, without the HMM.  snp_file (`--snp-file`): the SNP association pass follows the scan (DESIGN.md §29);
     the haplotypes of the patterns are those of the dosage tables' header.  scan_mediate (`--scan-mediate`): the scan's
     peaks are mediated by the phenotypes or by the table of scan_mediator_file.  scan_effects
     (`--scan-effects`) and scan_lod_drop (`--scan-lod-drop`): the peaks' founder effects, named by the dosage tables'
-    header, and their LOD support intervals."""
+    header, and their LOD support intervals.  scan_kinship (`--scan-kinship loco|overall`): the scan is the
+    linear mixed model's; scan_kinship_out writes the kinship matrices."""
     from .hmm import _match_lines, read_dosage_table, read_snp_file
     from .postproc import read_grid
     if min_lod is not None and not min_lod >= 0.0:
@@ -894,6 +1074,8 @@ def scan_tables(dosage_list, grid_file, pheno_file, covar_file=None, use_rankz=F
     perm = perm_options(scan_perms, scan_perm_seed, scan_perm_alpha, scan_perm_chromosomes, scan_perm_pheno)
     mediate = mediate_options(scan_mediate, scan_mediate_min_lod, scan_mediate_top, scan_mediator_file)
     effects = effects_options(scan_effects, scan_effects_min_lod, scan_lod_drop)
+    kinship = kinship_options(scan_kinship, scan_kinship_out, scan_perms, snp_file is not None, scan_mediate, scan_effects,
+                              scan_lod_drop)
     grid = read_grid(grid_file)
     chrom_names = list(grid)
     points = [len(grid[c]) for c in chrom_names]
@@ -923,6 +1105,6 @@ def scan_tables(dosage_list, grid_file, pheno_file, covar_file=None, use_rankz=F
         pos = np.concatenate([np.asarray(grid[c], dtype=np.float64) for c in chrom_names])
         return finish_scan(scan, out if out is not None else 'gbrs', [entries[k][0] for k in kept], pheno, covar, use_rankz,
                            chrom, pos, chrom_names, min_lod, lod_matrix, perm=perm, stage_times=stage_times, snps=snps,
-                           snp_grid=grid, mediate=mediate, effects=effects, founders=haplotypes)
+                           snp_grid=grid, mediate=mediate, effects=effects, founders=haplotypes, kinship=kinship)
     finally:
         scan.close()

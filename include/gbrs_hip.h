@@ -1171,6 +1171,82 @@ int gbrs_scan_effects_info(gbrs_scan_t *scan, gbrs_scan_effects_info_t *info);
 int gbrs_scan_run_support(gbrs_scan_t *scan, int64_t P, const double *pheno, double drop, double *lod, double *peak_lod,
                           int64_t *peak_index, int64_t *support_lo, int64_t *support_hi /* [P][n_chrom] */);
 
+/* Linear mixed model with leave-one-chromosome-out kinship on the scan handle (R/qtl2's scan1 with
+ * kinship = calc_kinship(probs, "loco")): the phenotype has a polygenic random effect whose covariance is the kinship of
+ * the chromosomes other than the scanned one, y ~ N(Z b + X_m a, s2 (h K + (1 - h) I)).  No fused multiply-add anywhere.
+ *
+ * Kinship.  With A_c the cohort's dosages on chromosome c as [n][M_c H] and S_c = A_c A_c',
+ *   K = scale * (sum over the chromosomes c != leave_out of S_c, added in chromosome order) / (sum of their M_c);
+ * leave_out = -1 leaves none out (the overall kinship).  K is double[n][n] and symmetric bit for bit.  S_c is an f64 MFMA
+ * product, one chain per entry over the columns in order, without atomics; all S_c are formed at the first call and stay
+ * on the device until the next append.  The LODs below do not depend on scale, the heritabilities do; gbrs_amd passes
+ * 2 / t^2 with t the total of a point's dosages (qtl2's doubled kinship of allele probabilities).  GBRS_ERR_INVALID for a
+ * cohort without samples or of more than 4096, for a leave_out outside -1 .. n_chrom-1, for a scale that is not finite
+ * and for a chromosome whose complement has no grid points; K is untouched on failure. */
+int gbrs_scan_kinship(gbrs_scan_t *scan, int leave_out /* -1: none */, double scale, double *K /* [n][n] */);
+
+/* The phenotype-independent part of the mixed model, once per (cohort, covariates, kinships).  The caller factors each
+ * distinct kinship K_e = U_e diag(lambda_e) U_e' (gbrs_amd: numpy.linalg.eigh) and passes n_eig pairs - U[e] double[n][n]
+ * with the eigenvectors in its columns, lambda[e] double[n] - and eig_of_chrom[c] in [0, n_eig), the pair chromosome c is
+ * scanned with: one pair per chromosome and the identity map for leave-one-chromosome-out, one pair for an overall
+ * kinship.  Z is double[n][cz], the covariates themselves with the intercept first (not a basis: the weights change it
+ * per phenotype); cz <= 16.  On the device, by one f64 MFMA kernel with K = n in one chain per entry:
+ *   Z*_e = U_e' Z;  R_m = U_e' D[:, m, 0:H-1] for every grid point m of the chromosomes mapped to e, kept as
+ *   [M][Hp][n_ld] (gbrs_scan_prepare's layout).
+ * GBRS_ERR_INVALID for cz < 1 or cz > 16, n <= cz + H - 1, n > 4096, n_eig < 1 or > n_chrom, a map entry outside
+ * [0, n_eig), a value of Z, U or lambda that is not finite (the message names the entry), and an eigenvalue that is not
+ * above 1e-10 of its decomposition's largest (the message names the decomposition: the cohort has fewer independent
+ * dosage columns than samples).  Such a refusal, and a failure after the checks, leaves the handle as it was, an earlier
+ * preparation included.  An append drops the preparation and the kinship products, as it drops W.  gbrs_scan_prepare and
+ * this preparation are independent: a handle may hold both, and neither changes the other's bits. */
+int gbrs_scan_lmm_prepare(gbrs_scan_t *scan, int cz, const double *Z /* [n][cz] */, int n_eig, const double *const *U,
+                          const double *const *lambda, const int32_t *eig_of_chrom /* [n_chrom] */);
+
+/* P phenotypes under the prepared mixed model: pheno is double[n][P].  A caller should subtract each column's mean before
+ * the call (gbrs_amd does): the model is the same, the intercept absorbs it, and y' O y - b' A^-1 b below loses fewer
+ * digits; a constant column goes in as zeros.  Per (phenotype p, decomposition e), y* = U_e' y and the null fit by REML:
+ * for h in [0, 1]
+ *   v_i = h lambda_i + 1 - h,  o_i = 1 / v_i,  A = Z*' O Z*,  b = Z*' O y*,  rss = y*' O y* - b' A^-1 b,
+ *   f(h) = (n - cz) log rss + sum log v_i + log det A  (+inf where rss <= 0),
+ * minimised by a search whose steps are fixed: f at k / 20, k = 0 .. 20, the lowest wins and the lowest k among equals;
+ * the bracket is its two neighbours clipped to [0, 1]; exactly 48 golden-section steps, the left point staying on equal
+ * f; then the bracket's midpoint, unless the bracket still touches 0 or 1 and f there is not above f at the midpoint:
+ * boundary optima are exactly 0.0 or 1.0.  hsq[p][e] is the result and sigma2[p][e] = rss / (n - cz) at it.  With hsq_in
+ * (double[P][n_eig], every value in [0, 1]) the search is skipped.  rss <= 0 at h = 0 (the column of zeros): hsq 0,
+ * sigma2 0 and LODs 0.0.  Then the weighted scan at the h found, with w = v^-1/2:
+ *   y^ = w . y*,  Z^ = w . Z*,  X^_m = w . R_m;  Qz = Z^ after modified Gram-Schmidt in column order, each column swept
+ *   twice over the ones before it and then normalised;  y~ = y^ - Qz Qz' y^,  rss0 = |y~|^2;
+ *   X~ = X^_m - Qz Qz' X^_m,  G = X~' X~,  the Cholesky factor with gbrs_scan_prepare's skip rule (both of its lines),
+ *   ess = |L^-1 X~' y~|^2 over the kept columns,  lod[p][m] = (n / 2) log10(rss0 / (rss0 - ess)) with gbrs_scan_run's
+ *   two edge rules, and the peaks by its first-index rule.
+ * lod double[P][M], peak_lod double[P][n_chrom], peak_index int64[P][n_chrom], hsq and sigma2 double[P][n_eig]; every
+ * output nullable.  The phenotypes pass in chunks of 512; no W is formed: a workgroup owns a grid point and walks 64
+ * phenotypes.  Every sum over the samples is one wavefront's in gbrs_scan_prepare's order: a phenotype's numbers are the
+ * same bits alone or among others, at any column, in any chunk, and however the cohort was appended.  GBRS_ERR_INVALID
+ * before gbrs_scan_lmm_prepare, for P < 1, for a phenotype value that is not finite (the message names the entry) and
+ * for a value of hsq_in outside [0, 1]; the outputs are untouched on such a failure.  The call allocates and frees its
+ * own buffers: what the handle holds, gbrs_scan_run's bits and gbrs_scan_info_t are as before.  No permutations, SNP
+ * tests, mediation, effects or support intervals under the mixed model, REML only, additive covariates only. */
+int gbrs_scan_lmm_run(gbrs_scan_t *scan, int64_t P, const double *pheno, const double *hsq_in /* [P][n_eig], nullable */,
+                      double *lod, double *peak_lod, int64_t *peak_index, double *hsq /* [P][n_eig] */, double *sigma2);
+
+/* The smallest and the largest number of kept columns over the grid points, per phenotype of the last gbrs_scan_lmm_run:
+ * int32[P] each, nullable.  (The weights depend on the phenotype, so there is no rank[m] as gbrs_scan_info has it.) */
+int gbrs_scan_lmm_ranks(gbrs_scan_t *scan, int32_t *rank_min, int32_t *rank_max);
+
+typedef struct gbrs_scan_lmm_info {
+    int32_t  cz, n_eig;          /* of the last gbrs_scan_lmm_prepare (0: not prepared)                          */
+    int64_t  P;                  /* of the last gbrs_scan_lmm_run (0: none yet)                                  */
+    double   last_kinship_ms;    /* device time of the last gbrs_scan_kinship: the products, if formed, and the sum */
+    double   last_rotate_ms;     /* device time of the last preparation's rotations                              */
+    double   last_null_ms;       /* of the last run: the null fits, summed over the chunks                       */
+    double   last_point_ms;      /* of the last run: the weighted scan's kernel, summed over the chunks          */
+    double   last_run_ms;        /* of the last run: its kernels and copies, all chunks                          */
+    uint64_t device_bytes;       /* what the kinship products and the preparation hold on the device             */
+    uint64_t peak_device_bytes;  /* what the handle held during the last run, the call's own buffers included    */
+} gbrs_scan_lmm_info_t;
+int gbrs_scan_lmm_info(gbrs_scan_t *scan, gbrs_scan_lmm_info_t *info);
+
 /* ------------------------------------------------------------------------------------------
  * Report text (host side, no device work): the `locus <haplotypes> total [notes]` tables of
  * EMfactory.report_read_counts / report_depths (emase/EMfactory.py:289-380).

@@ -341,9 +341,14 @@ def _scan_options(parser, covar=True):
                              'cohort\'s dosages on the other chromosomes, MODE overall with the kinship of all of them; every '
                              'phenotype\'s heritability is fitted by REML.  <PREFIX>.scan.npz gains hsq and kinship_mode, the '
                              'peaks file the column hsq.  Not with --scan-perms, --scan-snps / --snp-file, --scan-mediate, '
-                             '--scan-effects or --scan-lod-drop')
+                             '--scan-effects or --scan-lod-drop; the SNP pass under the mixed model is --scan-kinship-snps')
     parser.add_argument('--scan-kinship-out', action='store_true',
                         help='with --scan-kinship: write the kinship matrices and the sample ids to <PREFIX>.scan.kinship.npz')
+    parser.add_argument('--scan-kinship-snps', type=_existing, default=None, metavar='FILE',
+                        help='with --scan-kinship: SNP association under the mixed model on the device.  FILE has the format of '
+                             '--snp-file; after the scan every SNP of it is tested with one degree of freedom under the same '
+                             'kinship and the heritabilities the scan fitted.  Writes <PREFIX>.scan.snps.npz (with hsq, n_used '
+                             'and kinship_mode) and <PREFIX>.scan.snps.peaks.tsv (with the column hsq)')
 
 
 def main(argv=None) -> int:
@@ -473,7 +478,8 @@ def main(argv=None) -> int:
                         scan_mediate_min_lod=args.scan_mediate_min_lod, scan_mediate_top=args.scan_mediate_top,
                         scan_mediator_file=args.scan_mediator_file, scan_effects=args.scan_effects,
                         scan_effects_min_lod=args.scan_effects_min_lod, scan_lod_drop=args.scan_lod_drop,
-                        scan_kinship=args.scan_kinship, scan_kinship_out=args.scan_kinship_out)
+                        scan_kinship=args.scan_kinship, scan_kinship_out=args.scan_kinship_out,
+                        scan_kinship_snps=args.scan_kinship_snps)
         elif args.command == 'interpolate':
             from .postproc import interpolate
             interpolate(genoprob_file=args.genoprob_file, grid_file=args.grid_file, gpos_file=args.gpos_file,

@@ -19,7 +19,9 @@
 // phenotype) walks outward from the peak over the chunk's LOD rows while they are on the device.  Linear mixed model
 // (kernels and the rule in scan_lmm.inc): the kinship of the cohort per chromosome, the rotation of the
 // cohort by a kinship's eigenvectors, the REML fit of every phenotype's heritability and a weighted scan that forms each
-// (grid point, phenotype) pair's explained sum of squares without a W.
+// (grid point, phenotype) pair's explained sum of squares without a W.  SNP association under the mixed model (DESIGN.md §33;
+// kernels and the rule in scan_lmm_snp.inc): the SNP dosages of §29 rotated as the cohort is, and a sibling of the SNP product
+// kernel that multiplies them with the weighted columns of every phenotype's null fit and applies the test in its epilogue.
 #include "common.h"
 #include "scan_hmm.h"
 
@@ -335,6 +337,10 @@ scan_peak_kernel(int64_t M, int n_chrom, const int64_t *__restrict__ point_off, 
 
 #include "scan_lmm.inc"
 
+// ---- SNP association under the mixed model -------------------------------------------------------------------------------------
+
+#include "scan_lmm_snp.inc"
+
 }  // namespace gbrs
 
 using namespace gbrs;
@@ -395,11 +401,16 @@ struct gbrs_scan {
     int64_t lmm_n_ld = 0;
     DevBuf<double> lmm_U, lmm_lam, lmm_Zs, lmm_R;
     DevBuf<int32_t> lmm_eig_of_point;
+    std::vector<int32_t> lmm_eig_of_chrom;
     // the last gbrs_scan_lmm_run: its buffers are the call's own, as gbrs_scan_permute's
     int64_t lmm_P = 0;
     std::vector<int32_t> lmm_rank_min, lmm_rank_max;
     double t_lmm_rotate = 0, t_lmm_null = 0, t_lmm_point = 0, t_lmm_run = 0;
     uint64_t lmm_peak_bytes = 0;
+    // the last gbrs_scan_lmm_snps: its buffers are the call's own, as gbrs_scan_permute's
+    int64_t lsnp_P = 0;
+    double t_lsnp_pass = 0, t_lsnp_null = 0, t_lsnp_rotate = 0, t_lsnp_product = 0;
+    uint64_t lsnp_column_bytes = 0, lsnp_peak_bytes = 0;
     uint64_t lmm_bytes() const {
         return lmm_U.bytes() + lmm_lam.bytes() + lmm_Zs.bytes() + lmm_R.bytes() + lmm_eig_of_point.bytes();
     }
@@ -1424,6 +1435,7 @@ int gbrs_scan_lmm_prepare(gbrs_scan_t *s, int cz, const double *Z, int n_eig, co
     s->lmm_Zs.swap(d_Zs);
     s->lmm_R.swap(d_R);
     s->lmm_eig_of_point.swap(d_eop);
+    s->lmm_eig_of_chrom.assign(eig_of_chrom, eig_of_chrom + s->n_chrom);
     s->lmm_cz = cz;
     s->lmm_n_eig = n_eig;
     s->lmm_n_ld = n_ld;
@@ -1566,6 +1578,182 @@ int gbrs_scan_lmm_info(gbrs_scan_t *s, gbrs_scan_lmm_info_t *info) {
     info->last_run_ms = s->t_lmm_run;
     info->device_bytes = s->kin_S.bytes() + s->lmm_bytes();
     info->peak_device_bytes = s->lmm_peak_bytes;
+    return GBRS_OK;
+}
+
+// SNP association under the mixed model.  Two phases on the handle's stream: the null fits of every
+// phenotype by gbrs_scan_lmm_run's kernels in its chunks of 512, their weighted columns kept on the device for all P;
+// then the SNP chunks, each one's dosages formed and rotated once and multiplied with every phenotype chunk's columns.
+int gbrs_scan_lmm_snps(gbrs_scan_t *s, int64_t P, const double *pheno, const double *hsq_in, double *lod, uint8_t *used,
+                       double *peak_lod, int64_t *peak_index, int64_t *n_used, double *hsq, double *sigma2) {
+    RoctxRange roctx_range("gbrs_scan_lmm_snps");
+    if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (s->M_snp == 0) return fail(GBRS_ERR_INVALID, "no SNPs on the handle: call gbrs_scan_set_snps first");
+    if (s->lmm_cz == 0) return fail(GBRS_ERR_INVALID, "no mixed model on the handle: call gbrs_scan_lmm_prepare first");
+    if (P < 1) return fail(GBRS_ERR_INVALID, "a SNP pass needs at least 1 phenotype, got %lld", (long long)P);
+    if (!pheno) return fail(GBRS_ERR_INVALID, "bad argument");
+    const int n = (int)s->n, cz = s->lmm_cz, n_eig = s->lmm_n_eig, nc = s->n_chrom;
+    for (int64_t k = 0; k < (int64_t)n * P; ++k)
+        if (!std::isfinite(pheno[k]))
+            return fail(GBRS_ERR_INVALID, "phenotype %lld holds a value that is not finite (sample %lld)", (long long)(k % P),
+                        (long long)(k / P));
+    if (hsq_in)
+        for (int64_t k = 0; k < P * n_eig; ++k)
+            if (!(hsq_in[k] >= 0.0 && hsq_in[k] <= 1.0))
+                return fail(GBRS_ERR_INVALID, "the heritability given for phenotype %lld and decomposition %d is %g, outside [0, 1]",
+                            (long long)(k / n_eig), (int)(k % n_eig), hsq_in[k]);
+    GBRS_TRY(select_device(s->device));
+    int lds_max = 0;
+    GBRS_HIP_CHECK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, s->device));
+    if ((size_t)lds_max < LS_LDS_BYTES)
+        return fail(GBRS_ERR_INVALID, "the device gives a workgroup %d bytes of LDS, the SNP product needs %lld", lds_max, (long long)LS_LDS_BYTES);
+    GBRS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(lmm_snp_lod_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)LS_LDS_BYTES));
+    const int64_t M_snp = s->M_snp, n_ld = s->lmm_n_ld, pc_max = std::min(P, SC_PCHUNK), lc_max = std::min(M_snp, SS_CHUNK);
+    const size_t pe = (size_t)pc_max * n_eig;
+    const int64_t q_stride = P * n_ld;
+    DevBuf<double> y, ys, d_hin, d_hsq, d_sigma2, sw, qz, yt, rss0, cols, rss_all, dose, xs, d_lod, d_peak;
+    DevBuf<int64_t> d_index, d_count;
+    DevBuf<int32_t> d_rmin, d_rmax;
+    DevBuf<uint8_t> d_used;
+    GBRS_TRY(y.alloc((size_t)n * pc_max));
+    GBRS_TRY(ys.alloc(pe * n_ld));
+    if (hsq_in) GBRS_TRY(d_hin.alloc(pe));
+    GBRS_TRY(d_hsq.alloc(pe));
+    GBRS_TRY(d_sigma2.alloc(pe));
+    GBRS_TRY(sw.alloc(pe * n_ld));
+    GBRS_TRY(qz.alloc(pe * cz * n_ld));
+    GBRS_TRY(yt.alloc(pe * n_ld));
+    GBRS_TRY(rss0.alloc(pe));
+    GBRS_TRY(d_rmin.alloc((size_t)pc_max));
+    GBRS_TRY(d_rmax.alloc((size_t)pc_max));
+    GBRS_TRY(cols.alloc((size_t)n_eig * (cz + 2) * q_stride));
+    GBRS_TRY(rss_all.alloc((size_t)n_eig * P));
+    GBRS_TRY(dose.alloc((size_t)n * lc_max));
+    GBRS_TRY(xs.alloc((size_t)lc_max * n_ld));
+    GBRS_TRY(d_lod.alloc((size_t)pc_max * lc_max));
+    GBRS_TRY(d_used.alloc((size_t)pc_max * lc_max));
+    GBRS_TRY(d_peak.alloc((size_t)P * nc));
+    GBRS_TRY(d_index.alloc((size_t)P * nc));
+    GBRS_TRY(d_count.alloc((size_t)P * nc));
+    EventRing null_ring, rotate_ring, product_ring;
+    GBRS_TRY(null_ring.create());
+    GBRS_TRY(rotate_ring.create());
+    GBRS_TRY(product_ring.create());
+    int slot = 0;
+    GBRS_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
+    GBRS_HIP_CHECK(hipMemsetAsync(d_index.p, 0xFF, d_index.bytes(), s->stream));         // -1: nothing yet
+    GBRS_HIP_CHECK(hipMemsetAsync(d_count.p, 0, d_count.bytes(), s->stream));
+    for (int64_t p0 = 0; p0 < P; p0 += SC_PCHUNK) {
+        const int64_t pc = std::min(SC_PCHUNK, P - p0);
+        GBRS_HIP_CHECK(hipMemcpy2DAsync(y.p, (size_t)pc * sizeof(double), pheno + p0, (size_t)P * sizeof(double),
+                                        (size_t)pc * sizeof(double), (size_t)n, hipMemcpyHostToDevice, s->stream));
+        if (hsq_in)
+            GBRS_HIP_CHECK(hipMemcpyAsync(d_hin.p, hsq_in + p0 * n_eig, (size_t)pc * n_eig * sizeof(double), hipMemcpyHostToDevice, s->stream));
+        GBRS_TRY(null_ring.next(&slot));
+        GBRS_HIP_CHECK(hipEventRecord(null_ring.ev[2 * slot], s->stream));
+        for (int e = 0; e < n_eig; ++e)
+            scan_lmm_rotate(s, n_ld, pc, 1, 1, 1, pc, s->lmm_U.p + (size_t)e * n * n, y.p, ys.p + (size_t)e * pc * n_ld);
+        hipLaunchKernelGGL(lmm_null_kernel, dim3((unsigned)pc, (unsigned)n_eig), dim3(64), 0, s->stream, n, cz, n_ld, pc, n_eig, ys.p,
+                           s->lmm_Zs.p, s->lmm_lam.p, hsq_in ? d_hin.p : nullptr, d_hsq.p, d_sigma2.p, sw.p, qz.p, yt.p, rss0.p,
+                           d_rmin.p, d_rmax.p);
+        hipLaunchKernelGGL(lmm_snp_column_kernel, dim3((unsigned)((pc * n_eig * n_ld + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0,
+                           s->stream, n_ld, pc, p0, P, n_eig, cz, sw.p, qz.p, yt.p, rss0.p, cols.p, rss_all.p);
+        GBRS_HIP_CHECK(hipEventRecord(null_ring.ev[2 * slot + 1], s->stream));
+        GBRS_HIP_CHECK(hipGetLastError());
+        // waits for the kernels before it on the stream; the next chunk's null fit overwrites the two tables after it
+        if (hsq) GBRS_HIP_CHECK(hipMemcpyAsync(hsq + p0 * n_eig, d_hsq.p, (size_t)pc * n_eig * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        if (sigma2)
+            GBRS_HIP_CHECK(hipMemcpyAsync(sigma2 + p0 * n_eig, d_sigma2.p, (size_t)pc * n_eig * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    }
+    for (int64_t j0 = 0; j0 < M_snp; j0 += SS_CHUNK) {
+        const int64_t jc = std::min(SS_CHUNK, M_snp - j0);
+        // the runs of the chunk's SNPs that share a decomposition: [first, second) in the chunk, chromosome after chromosome
+        std::vector<std::pair<int64_t, int64_t>> runs;
+        std::vector<int> run_eig;
+        for (int c = 0; c < nc; ++c) {
+            const int64_t a = std::max(s->snp_off[c], j0) - j0, b = std::min(s->snp_off[c + 1], j0 + jc) - j0;
+            if (a >= b) continue;
+            if (!runs.empty() && run_eig.back() == s->lmm_eig_of_chrom[c]) runs.back().second = b;
+            else {
+                runs.emplace_back(a, b);
+                run_eig.push_back(s->lmm_eig_of_chrom[c]);
+            }
+        }
+        GBRS_TRY(rotate_ring.next(&slot));
+        GBRS_HIP_CHECK(hipEventRecord(rotate_ring.ev[2 * slot], s->stream));
+        hipLaunchKernelGGL(scan_snp_dosage_kernel, dim3((unsigned)((n * jc + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0, s->stream,
+                           n, s->M, s->H, j0, jc, s->dosage.p, s->snp_lo.p, s->snp_hi.p, s->snp_mask.p, s->snp_t.p, dose.p);
+        for (size_t r = 0; r < runs.size(); ++r)
+            scan_lmm_rotate(s, n_ld, runs[r].second - runs[r].first, 1, 1, 1, jc, s->lmm_U.p + (size_t)run_eig[r] * n * n,
+                            dose.p + runs[r].first, xs.p + runs[r].first * n_ld);
+        GBRS_HIP_CHECK(hipEventRecord(rotate_ring.ev[2 * slot + 1], s->stream));
+        GBRS_HIP_CHECK(hipGetLastError());
+        for (int64_t p0 = 0; p0 < P; p0 += SC_PCHUNK) {
+            const int64_t pc = std::min(SC_PCHUNK, P - p0);
+            GBRS_TRY(product_ring.next(&slot));
+            GBRS_HIP_CHECK(hipEventRecord(product_ring.ev[2 * slot], s->stream));
+            for (size_t r = 0; r < runs.size(); ++r) {
+                const int64_t tile0 = runs[r].first / SC_ROWS, tiles = (runs[r].second + SC_ROWS - 1) / SC_ROWS - tile0;
+                hipLaunchKernelGGL(lmm_snp_lod_kernel, dim3((unsigned)tiles, (unsigned)((pc + SC_COLS - 1) / SC_COLS)), dim3(SC_THREADS),
+                                   LS_LDS_BYTES, s->stream, jc, runs[r].first, runs[r].second, tile0, pc, n_ld, jc, cz, 0.5 * n, xs.p,
+                                   cols.p + (size_t)run_eig[r] * (cz + 2) * q_stride + p0 * n_ld, q_stride,
+                                   rss_all.p + (size_t)run_eig[r] * P + p0, d_lod.p, d_used.p);
+            }
+            GBRS_HIP_CHECK(hipEventRecord(product_ring.ev[2 * slot + 1], s->stream));
+            hipLaunchKernelGGL(lmm_snp_peak_kernel, dim3((unsigned)nc, (unsigned)pc), dim3(64), 0, s->stream, j0, jc, jc, nc,
+                               s->d_snp_off.p, d_used.p, d_lod.p, d_peak.p + p0 * nc, d_index.p + p0 * nc, d_count.p + p0 * nc);
+            GBRS_HIP_CHECK(hipGetLastError());
+            if (lod)        // waits for the kernels before it on the stream; the next chunk's product overwrites d_lod after it
+                GBRS_HIP_CHECK(hipMemcpy2DAsync(lod + p0 * M_snp + j0, (size_t)M_snp * sizeof(double), d_lod.p,
+                                                (size_t)jc * sizeof(double), (size_t)jc * sizeof(double), (size_t)pc,
+                                                hipMemcpyDeviceToHost, s->stream));
+            if (used)
+                GBRS_HIP_CHECK(hipMemcpy2DAsync(used + p0 * M_snp + j0, (size_t)M_snp, d_used.p, (size_t)jc, (size_t)jc, (size_t)pc,
+                                                hipMemcpyDeviceToHost, s->stream));
+        }
+    }
+    GBRS_HIP_CHECK(hipEventRecord(s->ev[1], s->stream));
+    GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
+    GBRS_TRY(null_ring.drain());
+    GBRS_TRY(rotate_ring.drain());
+    GBRS_TRY(product_ring.drain());
+    std::vector<double> h_peak((size_t)P * nc);
+    std::vector<int64_t> h_index((size_t)P * nc);
+    GBRS_HIP_CHECK(hipMemcpy(h_peak.data(), d_peak.p, d_peak.bytes(), hipMemcpyDeviceToHost));
+    GBRS_HIP_CHECK(hipMemcpy(h_index.data(), d_index.p, d_index.bytes(), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < h_peak.size(); ++k)
+        if (h_index[k] < 0) h_peak[k] = std::numeric_limits<double>::quiet_NaN();
+    if (peak_lod) std::memcpy(peak_lod, h_peak.data(), h_peak.size() * sizeof(double));
+    if (peak_index) std::memcpy(peak_index, h_index.data(), h_index.size() * sizeof(int64_t));
+    if (n_used) GBRS_HIP_CHECK(hipMemcpy(n_used, d_count.p, d_count.bytes(), hipMemcpyDeviceToHost));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) s->t_lsnp_pass = ms;
+    s->t_lsnp_null = null_ring.ms;
+    s->t_lsnp_rotate = rotate_ring.ms;
+    s->t_lsnp_product = product_ring.ms;
+    s->lsnp_P = P;
+    s->lsnp_column_bytes = cols.bytes() + rss_all.bytes();
+    s->lsnp_peak_bytes = s->d_point_off.bytes() + s->dosage.bytes() + s->qz.bytes() + s->W.bytes() + s->d_rank.bytes() + s->y.bytes() +
+                         s->yt.bytes() + s->rss0.bytes() + s->lod.bytes() + s->peak_lod.bytes() + s->peak_index.bytes() + s->snp_bytes() +
+                         s->kin_S.bytes() + s->lmm_bytes() + y.bytes() + ys.bytes() + d_hin.bytes() + d_hsq.bytes() + d_sigma2.bytes() +
+                         sw.bytes() + qz.bytes() + yt.bytes() + rss0.bytes() + d_rmin.bytes() + d_rmax.bytes() + cols.bytes() +
+                         rss_all.bytes() + dose.bytes() + xs.bytes() + d_lod.bytes() + d_used.bytes() + d_peak.bytes() + d_index.bytes() +
+                         d_count.bytes();
+    return GBRS_OK;
+}
+
+int gbrs_scan_lmm_snp_info(gbrs_scan_t *s, gbrs_scan_lmm_snp_info_t *info) {
+    if (!s || !info) return fail(GBRS_ERR_INVALID, "bad argument");
+    info->M_snp = s->M_snp;
+    info->chunk = SS_CHUNK;
+    info->P = s->lsnp_P;
+    info->last_pass_ms = s->t_lsnp_pass;
+    info->last_null_ms = s->t_lsnp_null;
+    info->last_rotate_ms = s->t_lsnp_rotate;
+    info->last_product_ms = s->t_lsnp_product;
+    info->column_bytes = s->lsnp_column_bytes;
+    info->peak_device_bytes = s->lsnp_peak_bytes;
     return GBRS_OK;
 }
 

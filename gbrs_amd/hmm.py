@@ -1405,7 +1405,9 @@ class ReconstructOptions:
     `scan_effects_min_lod` go to `<scan_out>.scan.effects.npz` and `<scan_out>.scan.effects.tsv`, named by the samples'
     haplotype header; the peaks' LOD support intervals join the scan's two files (scan.effects_options).
     `scan_kinship`, `scan_kinship_out`: the scan is the linear mixed model's with the cohort's own
-    leave-one-chromosome-out or overall kinship (scan.kinship_options); the other scan passes are then refused."""
+    leave-one-chromosome-out or overall kinship (scan.kinship_options); the other scan passes are then refused.
+    `scan_kinship_snps` (needs `scan_kinship`): a SNP file in `snp_file`'s format whose SNPs are tested
+    with one degree of freedom under the same mixed model after the scan, at the heritabilities it fitted."""
     expr_threshold: float = 1.5
     sigma: float = 0.12
     grid_genoprobs: bool = False
@@ -1446,6 +1448,7 @@ class ReconstructOptions:
     scan_lod_drop: float = None
     scan_kinship: str = None
     scan_kinship_out: bool = False
+    scan_kinship_snps: str = None
 
     @classmethod
     def of(cls, keywords):
@@ -1478,7 +1481,8 @@ class ReconstructOptions:
                         scan_mediate_top=self.scan_mediate_top, scan_mediator_file=self.scan_mediator_file,
                         scan_effects=self.scan_effects, scan_effects_min_lod=self.scan_effects_min_lod,
                         scan_lod_drop=self.scan_lod_drop, scan_kinship=self.scan_kinship,
-                        scan_kinship_out=self.scan_kinship_out, scan_snps=self.scan_snps)
+                        scan_kinship_out=self.scan_kinship_out, scan_snps=self.scan_snps,
+                        scan_kinship_snps=self.scan_kinship_snps)
         check_scan_snp_args(self.scan_snps, self.snp_file, self.scan_pheno, grid_file, cohort=cohort)
 
 
@@ -1767,7 +1771,7 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
                      scan_perm_pheno: str = None, scan_snps: bool = False, scan_mediate: bool = False,
                      scan_mediate_min_lod: float = None, scan_mediate_top: int = None, scan_mediator_file: str = None,
                      scan_effects: bool = False, scan_effects_min_lod: float = None, scan_lod_drop: float = None,
-                     scan_kinship: str = None, scan_kinship_out: bool = False) -> list:
+                     scan_kinship: str = None, scan_kinship_out: bool = False, scan_kinship_snps: str = None) -> list:
     """`gbrs reconstruct` for a cohort whose genes.tpm files exist (extension): one context, the tables on the device
     once, the samples through the HMM in launches of up to `batch_size`, and every pass the options ask for once per
     launch.  Every sample gets the files the single-sample call writes for its outbase.  All samples must carry the same
@@ -1832,11 +1836,13 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
             scan_mod.perm_plan(scan_perm, scan_tables[0][0], [str(c) for c in ctx.chroms])
         if scan_med is not None and scan_med['mediator_file'] is not None:      # a table that cannot be read, likewise
             scan_med['table'] = scan_mod.read_scan_pheno(scan_med['mediator_file'])
+        if scan_kinship_snps is not None:  # the mixed model's own SNP file, by --snp-file's parser, likewise
+            scan_kin_snps = read_snp_file(scan_kinship_snps, haplotypes, ctx.chroms, ctx.grid_file)
     marks['load'] = clock() - t0
     for key in ('read', 'hmm', 'grid', 'save') + (('loglik',) if options.loglik else ()) + \
             (('match',) if match_panel is not None else ()) + (('snp',) if snp_file is not None else ()) + \
             (('scan',) if scan_pheno is not None else ()) + (('scan_perm',) if scan_perm is not None else ()) + \
-            (('scan_snps',) if scan_snps else ()) + (('mediate',) if scan_med is not None else ()) + \
+            (('scan_snps',) if scan_snps or scan_kinship_snps is not None else ()) + (('mediate',) if scan_med is not None else ()) + \
             (('effects',) if with_effects else ()):
         marks[key] = 0.0
     from concurrent.futures import ThreadPoolExecutor
@@ -1936,9 +1942,10 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
                                  np.concatenate([np.asarray(ctx.grid[c], dtype=np.float64) for _, _, c in slices]),
                                  list(ctx.chroms), scan_min_lod, scan_lod_matrix, perm=scan_perm, stage_times=marks,
                                  snps=shared.snps if scan_snps else None, snp_grid=ctx.grid, mediate=scan_med,
-                                 effects=scan_eff, founders=haplotypes, kinship=scan_kin)
+                                 effects=scan_eff, founders=haplotypes, kinship=scan_kin,
+                                 kinship_snps=scan_kin_snps if scan_kinship_snps is not None else None)
             marks['scan'] += clock() - t0 - (marks['scan_perm'] if scan_perm is not None else 0.0) - \
-                (marks['scan_snps'] if scan_snps else 0.0) - (marks['mediate'] if scan_med is not None else 0.0) - \
+                (marks['scan_snps'] if scan_snps or scan_kinship_snps is not None else 0.0) - (marks['mediate'] if scan_med is not None else 0.0) - \
                 (marks['effects'] if with_effects else 0.0)
     finally:
         writers.shutdown(wait=True)

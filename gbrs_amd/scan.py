@@ -2,7 +2,8 @@
 `gbrs scan`.  Haley-Knott regression with additive covariates on the device (gbrs_scan_*, gbrs_amd/csrc/scan.hip); the
 host side here is the covariates' QR, the file readers and the writers.  `--scan-kinship loco|overall`: the
 linear mixed model with a kinship of the cohort's own dosages (gbrs_scan_kinship, gbrs_scan_lmm_prepare, gbrs_scan_lmm_run);
-the host side is the kinships' eigendecomposition.  `--scan-snps` / `gbrs scan
+the host side is the kinships' eigendecomposition; `--scan-kinship-snps FILE`: the 1-df test of founder
+SNPs under that model, after the scan and at its heritabilities (gbrs_scan_lmm_snps).  `--scan-snps` / `gbrs scan
 --snp-file`: the 1-df test of founder SNPs on the same prepared cohort (gbrs_scan_set_snps, gbrs_scan_snps).
 `--scan-mediate`: the scan's peaks conditioned on every other phenotype in turn (gbrs_scan_mediate).
 `--scan-effects`, `--scan-lod-drop`: the founder effects at the scan's peaks with their standard errors
@@ -340,12 +341,9 @@ class GenomeScan:
         self.eig_of_chrom = mapping
         return matrices
 
-    def run_lmm(self, pheno, want_lod=True, hsq=None):
-        """pheno: [n, P] (or [n]) under the prepared mixed model.  Every column's mean is subtracted before the upload (the
-        intercept absorbs it) and a constant column goes as zeros: hsq 0 and LODs 0.0.  hsq: [P, n_chrom] heritabilities
-        in [0, 1] to scan with instead of fitting them (chromosomes that share a decomposition must agree; the first
-        one's value is taken).  Returns `peak_lod`, `peak_index` [P, n_chrom], `hsq` and `sigma2` [P, n_chrom] (per
-        chromosome, through `eig_of_chrom`), `rank_min`, `rank_max` [P] and, with want_lod, `lod` [P, M]."""
+    def _lmm_inputs(self, pheno, hsq):
+        """What a pass under the mixed model uploads: (y [n, P] with every column's mean subtracted and a constant column as
+        zeros, hsq per decomposition [P, n_eig] or None, n_eig)."""
         if not self.lmm_prepared:
             raise _lib.GbrsHipError(_lib.GBRS_ERR_INVALID, 'no mixed model on the handle: call prepare_lmm first')
         y = np.array(pheno, dtype=np.float64, order='C')
@@ -366,6 +364,45 @@ class GenomeScan:
                 raise ValueError(f'hsq has shape {by_chrom.shape}, expected ({P}, {nc})')
             first = [int(np.flatnonzero(mapping == e)[0]) for e in range(n_eig)]
             given = np.ascontiguousarray(by_chrom[:, first])
+        return y, given, n_eig
+
+    def run_snps_lmm(self, pheno, want_lod=True, hsq=None):
+        """The 1-df test of every SNP of the handle under the prepared mixed model (R/qtl2's scan1snps
+        with kinship).  pheno and hsq as for run_lmm, centred by the same code; hsq is [P, n_chrom], for instance what
+        run_lmm fitted, so that both passes use the same heritability per chromosome.  Returns `peak_lod`, `peak_index`
+        (the SNP's index in handle order; NaN and -1 without a used SNP) and `n_used` [P, n_chrom], `hsq` and `sigma2`
+        [P, n_chrom] and, with want_lod, `lod` [P, M_snp] and `used` [P, M_snp] (bool: the weights, and so the test's
+        threshold, depend on the phenotype)."""
+        y, given, n_eig = self._lmm_inputs(pheno, hsq)
+        P, nc, mapping, M_snp = y.shape[1], len(self.points), self.eig_of_chrom, self.snp_info()['M_snp']
+        lod = np.empty((P, M_snp)) if want_lod else None
+        used = np.zeros((P, M_snp), dtype=np.uint8) if want_lod else None
+        peak, index, count = np.empty((P, nc)), np.empty((P, nc), dtype=np.int64), np.empty((P, nc), dtype=np.int64)
+        fitted, sigma2 = np.empty((P, n_eig)), np.empty((P, n_eig))
+        _lib.check(_lib.load().gbrs_scan_lmm_snps(self._h, P, _lib.ptr(y), _lib.ptr(given), _lib.ptr(lod), _lib.ptr(used),
+                                                  _lib.ptr(peak), _lib.ptr(index), _lib.ptr(count), _lib.ptr(fitted),
+                                                  _lib.ptr(sigma2)))
+        out = {'peak_lod': peak, 'peak_index': index, 'n_used': count, 'hsq': fitted[:, mapping], 'sigma2': sigma2[:, mapping]}
+        if want_lod:
+            out['lod'] = lod
+            out['used'] = used.astype(bool)
+        return out
+
+    def lmm_snp_info(self):
+        raw = _lib.ScanLmmSnpInfo()
+        _lib.check(_lib.load().gbrs_scan_lmm_snp_info(self._h, C.byref(raw)))
+        return {'M_snp': raw.M_snp, 'chunk': raw.chunk, 'P': raw.P, 'pass_ms': raw.last_pass_ms, 'null_ms': raw.last_null_ms,
+                'rotate_ms': raw.last_rotate_ms, 'product_ms': raw.last_product_ms, 'column_bytes': raw.column_bytes,
+                'peak_device_bytes': raw.peak_device_bytes}
+
+    def run_lmm(self, pheno, want_lod=True, hsq=None):
+        """pheno: [n, P] (or [n]) under the prepared mixed model.  Every column's mean is subtracted before the upload (the
+        intercept absorbs it) and a constant column goes as zeros: hsq 0 and LODs 0.0.  hsq: [P, n_chrom] heritabilities
+        in [0, 1] to scan with instead of fitting them (chromosomes that share a decomposition must agree; the first
+        one's value is taken).  Returns `peak_lod`, `peak_index` [P, n_chrom], `hsq` and `sigma2` [P, n_chrom] (per
+        chromosome, through `eig_of_chrom`), `rank_min`, `rank_max` [P] and, with want_lod, `lod` [P, M]."""
+        y, given, n_eig = self._lmm_inputs(pheno, hsq)
+        P, nc, mapping = y.shape[1], len(self.points), self.eig_of_chrom
         lod = np.empty((P, self.M)) if want_lod else None
         peak, index = np.empty((P, nc)), np.empty((P, nc), dtype=np.int64)
         fitted, sigma2 = np.empty((P, n_eig)), np.empty((P, n_eig))
@@ -591,11 +628,19 @@ def kinship_options(scan_kinship=None, scan_kinship_out=False, scan_perms=None, 
     return {'mode': scan_kinship, 'out': bool(scan_kinship_out)}
 
 
+def kinship_snp_options(scan_kinship_snps=None, scan_kinship=None):
+    """`--scan-kinship-snps FILE` needs `--scan-kinship`.  Refused before a file is read."""
+    if scan_kinship_snps is not None and scan_kinship is None:
+        raise RuntimeError('--scan-kinship-snps needs --scan-kinship: without a kinship the SNP pass is --scan-snps')
+    return scan_kinship_snps
+
+
 def check_scan_args(scan_pheno=None, scan_covar=None, scan_rankz=False, scan_out=None, scan_min_lod=None,
                     scan_lod_matrix=False, grid_file=None, cohort=False, scan_perms=None, scan_perm_seed=None,
                     scan_perm_alpha=None, scan_perm_chromosomes=None, scan_perm_pheno=None, scan_mediate=False,
                     scan_mediate_min_lod=None, scan_mediate_top=None, scan_mediator_file=None, scan_effects=False,
-                    scan_effects_min_lod=None, scan_lod_drop=None, scan_kinship=None, scan_kinship_out=False, scan_snps=False):
+                    scan_effects_min_lod=None, scan_lod_drop=None, scan_kinship=None, scan_kinship_out=False, scan_snps=False,
+                    scan_kinship_snps=None):
     """`--scan-pheno FILE [--scan-covar FILE] [--scan-rankz] [--scan-out PREFIX] [--scan-min-lod X] [--scan-lod-matrix]`,
     the `--scan-perm*` options (perm_options), the `--scan-mediat*` options (mediate_options), `--scan-effects`,
     `--scan-effects-min-lod`, `--scan-lod-drop` (effects_options) and `--scan-kinship`, `--scan-kinship-out`
@@ -609,11 +654,13 @@ def check_scan_args(scan_pheno=None, scan_covar=None, scan_rankz=False, scan_out
              '--scan-mediate': scan_mediate or None, '--scan-mediate-min-lod': scan_mediate_min_lod,
              '--scan-mediate-top': scan_mediate_top, '--scan-mediator-file': scan_mediator_file,
              '--scan-effects': scan_effects or None, '--scan-effects-min-lod': scan_effects_min_lod,
-             '--scan-lod-drop': scan_lod_drop, '--scan-kinship': scan_kinship, '--scan-kinship-out': scan_kinship_out or None}
+             '--scan-lod-drop': scan_lod_drop, '--scan-kinship': scan_kinship, '--scan-kinship-out': scan_kinship_out or None,
+             '--scan-kinship-snps': scan_kinship_snps}
     perm_options(scan_perms, scan_perm_seed, scan_perm_alpha, scan_perm_chromosomes, scan_perm_pheno)
     mediate_options(scan_mediate, scan_mediate_min_lod, scan_mediate_top, scan_mediator_file)
     effects_options(scan_effects, scan_effects_min_lod, scan_lod_drop)
     kinship_options(scan_kinship, scan_kinship_out, scan_perms, scan_snps, scan_mediate, scan_effects, scan_lod_drop)
+    kinship_snp_options(scan_kinship_snps, scan_kinship)
     if scan_pheno is None:
         for name, value in given.items():
             if value is not None:
@@ -877,6 +924,74 @@ def finish_scan_snps(scan, prefix, ids, phenotypes, covariates, y, snps, chrom_n
         stage_times['scan_snps'] = stage_times.get('scan_snps', 0.0) + time.perf_counter() - t0
 
 
+def snps_lmm_in_file_order(result, rows, n_file):
+    """GenomeScan.run_snps_lmm's dict (handle order) in the SNP file's order: `peak_lod`, `peak_snp` (the SNP's file row,
+    -1 without a used SNP), `n_used`, `hsq` [P, n_chrom] and, if present, `lod` [P, n_file] (NaN for the SNPs that are not
+    on the handle) with `used` [P, n_file] (False for those) beside it."""
+    index = result['peak_index']
+    out = {'peak_lod': result['peak_lod'], 'n_used': result['n_used'], 'hsq': result['hsq'],
+           'peak_snp': np.where(index >= 0, rows[np.maximum(index, 0)] if len(rows) else -1, -1).astype(np.int64)}
+    if 'lod' in result:
+        P = len(result['lod'])
+        out['lod'], out['used'] = np.full((P, n_file), np.nan), np.zeros((P, n_file), dtype=bool)
+        out['lod'][:, rows] = result['lod']
+        out['used'][:, rows] = result['used']
+    return out
+
+
+def write_scan_snps_lmm(prefix, phenotypes, samples, covariates, snps, chrom_names, result, min_lod, kinship_mode):
+    """`<prefix>.scan.snps.npz` and `<prefix>.scan.snps.peaks.tsv` of the SNP pass under the mixed model
+    from snps_lmm_in_file_order's dict: write_scan_snps' members plus `hsq`, `n_used` and `kinship_mode`; `used` depends
+    on the phenotype here and goes in only beside the LOD matrix; the peaks file gains the column hsq."""
+    arrays = dict(phenotypes=np.array(phenotypes), samples=np.array(samples), covariates=np.array(covariates),
+                  snp_id=snps['snp_id'], chrom=snps['chrom'], bp=snps['bp'], cM=snps['cM'], pattern=snps['pattern'],
+                  peak_lod=result['peak_lod'], peak_snp=result['peak_snp'], hsq=result['hsq'], n_used=result['n_used'],
+                  kinship_mode=np.array(kinship_mode))
+    if 'lod' in result:
+        arrays['lod'], arrays['used'] = result['lod'], result['used']
+    np.savez(f'{prefix}.scan.snps.npz', **arrays)
+    peak, at, hsq = result['peak_lod'], result['peak_snp'], result['hsq']
+    with open(f'{prefix}.scan.snps.peaks.tsv', 'w') as out:
+        out.write('#phenotype\tchromosome\tsnp_id\tbp\tcM\tpattern\tlod\tgenome_wide_max\thsq\n')
+        for p, name in enumerate(phenotypes):
+            on = [c for c in range(len(chrom_names)) if at[p, c] >= 0]
+            top = max(on, key=lambda c: (peak[p, c], -c)) if on else None
+            for c in on:
+                if peak[p, c] >= min_lod:
+                    j = at[p, c]
+                    out.write(f'{name}\t{chrom_names[c]}\t{snps["snp_id"][j]}\t{repr(float(snps["bp"][j]))}\t'
+                              f'{repr(float(snps["cM"][j]))}\t{snps["pattern"][j]}\t{repr(float(peak[p, c]))}\t{int(c == top)}\t'
+                              f'{repr(float(hsq[p, c]))}\n')
+
+
+def finish_scan_snps_lmm(scan, prefix, ids, phenotypes, covariates, y, snps, chrom_names, grid, hsq, kinship_mode, min_lod=None,
+                         lod_matrix=False, stage_times=None):
+    """The SNP association pass under the mixed model `scan` holds and its two files.  y: the phenotypes
+    as the scan saw them; hsq: [P, n_chrom], what the grid scan fitted, so that both passes use the same heritability per
+    chromosome.  Its wall-clock seconds go to stage_times['scan_snps']."""
+    import time
+    t0 = time.perf_counter()
+    grid_pos, snp_pos, masks, rows = snp_plan(snps, chrom_names, scan.points, grid)
+    n_file, nc = len(snps['snp_id']), len(chrom_names)
+    if len(rows):
+        scan.set_snps(grid_pos, snp_pos, masks)
+        got = scan.run_snps_lmm(y, want_lod=bool(lod_matrix) or y.shape[1] * len(rows) <= LOD_MATRIX_LIMIT, hsq=hsq)
+        timing = scan.lmm_snp_info()
+        logger.info(f'scan: {len(rows)} SNPs, {y.shape[1]} phenotypes under the mixed model; {timing["pass_ms"]:.1f} ms on the '
+                    f'device, null fits {timing["null_ms"]:.1f} ms, dosages and rotation {timing["rotate_ms"]:.1f} ms, product '
+                    f'kernel {timing["product_ms"]:.1f} ms')
+    else:
+        logger.warning('scan: no SNP of the file lies on a chromosome with grid points')
+        P = y.shape[1]
+        got = {'peak_lod': np.full((P, nc), np.nan), 'peak_index': np.full((P, nc), -1, dtype=np.int64),
+               'n_used': np.zeros((P, nc), dtype=np.int64), 'hsq': np.asarray(hsq, dtype=np.float64), 'lod': np.zeros((P, 0)),
+               'used': np.zeros((P, 0), dtype=bool)}
+    write_scan_snps_lmm(prefix, phenotypes, ids, covariates, snps, [str(c) for c in chrom_names],
+                        snps_lmm_in_file_order(got, rows, n_file), 0.0 if min_lod is None else min_lod, kinship_mode)
+    if stage_times is not None:
+        stage_times['scan_snps'] = stage_times.get('scan_snps', 0.0) + time.perf_counter() - t0
+
+
 def mediation_targets(peak_lod, peak_index, min_lod):
     """(phenotype, chromosome) of every peak of the scan with a LOD of at least min_lod, phenotype after phenotype: [T, 2]."""
     with np.errstate(invalid='ignore'):
@@ -999,7 +1114,8 @@ def finish_scan_effects(scan, prefix, ids, pheno, covariates, y, min_lod, result
 
 
 def finish_scan(scan, prefix, ids, pheno, covar, use_rankz, chrom, pos, chrom_names, min_lod=None, lod_matrix=False,
-                perm=None, stage_times=None, snps=None, snp_grid=None, mediate=None, effects=None, founders=None, kinship=None):
+                perm=None, stage_times=None, snps=None, snp_grid=None, mediate=None, effects=None, founders=None, kinship=None,
+                kinship_snps=None):
     """prepare + run + the two files for the cohort `scan` holds, whose samples are `ids` in append order (every one with
     its rows in the tables).  perm: perm_options' dict, or None; with it the permutation pass runs after the scan on the
     phenotypes and chromosomes it names and its wall-clock seconds go to stage_times['scan_perm'].  mediate:
@@ -1007,7 +1123,8 @@ def finish_scan(scan, prefix, ids, pheno, covar, use_rankz, chrom, pos, chrom_na
     effects: effects_options' dict, or None; its lod_drop makes the run form the support intervals, its min_lod makes
     the founder effects of the peaks follow (finish_scan_effects), named by `founders`.
     kinship: kinship_options' dict, or None; with it the scan is the mixed model's and none of the other
-    passes runs.  Returns GenomeScan.info() after the run."""
+    passes runs, except that of kinship_snps (read_snp_file's dict of `--scan-kinship-snps`, or None): the SNP association
+    under the same mixed model, at the heritabilities the scan fitted.  Returns GenomeScan.info() after the run."""
     kept, y, z, names = scan_design(ids, pheno, covar, use_rankz)
     assert len(kept) == len(ids) == scan.n
     if kinship is not None:
@@ -1017,6 +1134,9 @@ def finish_scan(scan, prefix, ids, pheno, covar, use_rankz, chrom, pos, chrom_na
                    kinship_mode=kinship['mode'])
         if kinship['out']:
             write_scan_kinship(prefix, ids, chrom_names, matrices, scan.eig_of_chrom, kinship['mode'])
+        if kinship_snps is not None:        # read_snp_file's dict: the SNP pass under the same kinship and heritabilities
+            finish_scan_snps_lmm(scan, prefix, ids, pheno[0], names, y, kinship_snps, chrom_names, snp_grid, result['hsq'],
+                                 kinship['mode'], min_lod, lod_matrix, stage_times)
         timing = scan.lmm_info()
         logger.info(f'scan: {len(ids)} samples, {y.shape[1]} phenotypes, {scan.M} grid points under the mixed model '
                     f'({kinship["mode"]} kinship); kinship {timing["kinship_ms"]:.1f} ms, rotation {timing["rotate_ms"]:.1f} ms, '
@@ -1059,14 +1179,15 @@ def scan_tables(dosage_list, grid_file, pheno_file, covar_file=None, use_rankz=F
                 lod_matrix=False, device=0, scan_perms=None, scan_perm_seed=None, scan_perm_alpha=None,
                 scan_perm_chromosomes=None, scan_perm_pheno=None, stage_times=None, snp_file=None, scan_mediate=False,
                 scan_mediate_min_lod=None, scan_mediate_top=None, scan_mediator_file=None, scan_effects=False,
-                scan_effects_min_lod=None, scan_lod_drop=None, scan_kinship=None, scan_kinship_out=False):
+                scan_effects_min_lod=None, scan_lod_drop=None, scan_kinship=None, scan_kinship_out=False, scan_kinship_snps=None):
     """`gbrs scan`: the cohort from dosage tables in `gbrs export` format (lines `id<TAB>dosage table`), rows in the grid
     file's order, without the HMM.  snp_file (`--snp-file`): the SNP association pass follows the scan (DESIGN.md §29);
     the haplotypes of the patterns are those of the dosage tables' header.  scan_mediate (`--scan-mediate`): the scan's
     peaks are mediated by the phenotypes or by the table of scan_mediator_file.  scan_effects
     (`--scan-effects`) and scan_lod_drop (`--scan-lod-drop`): the peaks' founder effects, named by the dosage tables'
     header, and their LOD support intervals.  scan_kinship (`--scan-kinship loco|overall`): the scan is the
-    linear mixed model's; scan_kinship_out writes the kinship matrices."""
+    linear mixed model's; scan_kinship_out writes the kinship matrices; scan_kinship_snps
+    (`--scan-kinship-snps FILE`): the SNP association pass under the mixed model follows the scan."""
     from .hmm import _match_lines, read_dosage_table, read_snp_file
     from .postproc import read_grid
     if min_lod is not None and not min_lod >= 0.0:
@@ -1076,6 +1197,7 @@ def scan_tables(dosage_list, grid_file, pheno_file, covar_file=None, use_rankz=F
     effects = effects_options(scan_effects, scan_effects_min_lod, scan_lod_drop)
     kinship = kinship_options(scan_kinship, scan_kinship_out, scan_perms, snp_file is not None, scan_mediate, scan_effects,
                               scan_lod_drop)
+    kinship_snp_options(scan_kinship_snps, scan_kinship)
     grid = read_grid(grid_file)
     chrom_names = list(grid)
     points = [len(grid[c]) for c in chrom_names]
@@ -1097,6 +1219,7 @@ def scan_tables(dosage_list, grid_file, pheno_file, covar_file=None, use_rankz=F
     with open(entries[kept[0]][1]) as fh:
         haplotypes = fh.readline().rstrip('\n')[2:].split('\t')
     snps = read_snp_file(snp_file, haplotypes, chrom_names, grid_file) if snp_file is not None else None
+    kinship_snps = read_snp_file(scan_kinship_snps, haplotypes, chrom_names, grid_file) if scan_kinship_snps is not None else None
     scan = GenomeScan(len(haplotypes), points, device=device)
     try:
         for k in kept:
@@ -1105,6 +1228,7 @@ def scan_tables(dosage_list, grid_file, pheno_file, covar_file=None, use_rankz=F
         pos = np.concatenate([np.asarray(grid[c], dtype=np.float64) for c in chrom_names])
         return finish_scan(scan, out if out is not None else 'gbrs', [entries[k][0] for k in kept], pheno, covar, use_rankz,
                            chrom, pos, chrom_names, min_lod, lod_matrix, perm=perm, stage_times=stage_times, snps=snps,
-                           snp_grid=grid, mediate=mediate, effects=effects, founders=haplotypes, kinship=kinship)
+                           snp_grid=grid, mediate=mediate, effects=effects, founders=haplotypes, kinship=kinship,
+                           kinship_snps=kinship_snps)
     finally:
         scan.close()

@@ -1225,8 +1225,9 @@ int gbrs_scan_lmm_prepare(gbrs_scan_t *scan, int cz, const double *Z /* [n][cz] 
  * same bits alone or among others, at any column, in any chunk, and however the cohort was appended.  GBRS_ERR_INVALID
  * before gbrs_scan_lmm_prepare, for P < 1, for a phenotype value that is not finite (the message names the entry) and
  * for a value of hsq_in outside [0, 1]; the outputs are untouched on such a failure.  The call allocates and frees its
- * own buffers: what the handle holds, gbrs_scan_run's bits and gbrs_scan_info_t are as before.  No permutations, SNP
- * tests, mediation, effects or support intervals under the mixed model, REML only, additive covariates only. */
+ * own buffers: what the handle holds, gbrs_scan_run's bits and gbrs_scan_info_t are as before.  No permutations,
+ * mediation, effects or support intervals under the mixed model, REML only, additive covariates only; the SNP tests
+ * under the mixed model are gbrs_scan_lmm_snps. */
 int gbrs_scan_lmm_run(gbrs_scan_t *scan, int64_t P, const double *pheno, const double *hsq_in /* [P][n_eig], nullable */,
                       double *lod, double *peak_lod, int64_t *peak_index, double *hsq /* [P][n_eig] */, double *sigma2);
 
@@ -1246,6 +1247,49 @@ typedef struct gbrs_scan_lmm_info {
     uint64_t peak_device_bytes;  /* what the handle held during the last run, the call's own buffers included    */
 } gbrs_scan_lmm_info_t;
 int gbrs_scan_lmm_info(gbrs_scan_t *scan, gbrs_scan_lmm_info_t *info);
+
+/* SNP association under the mixed model (R/qtl2's scan1snps with kinship = loco): gbrs_scan_snps' test of
+ * every SNP of gbrs_scan_set_snps with the polygenic effect of gbrs_scan_lmm_prepare.  No fused multiply-add anywhere.
+ * The rule, per SNP j and phenotype p:
+ *   1  x_s is gbrs_scan_snp_dosage's, by the same function: the same bits.
+ *   2  e = eig_of_chrom[chromosome of j], x* = U_e' x; each entry one accumulator chain over the samples in the order of
+ *      the K chunks, as gbrs_scan_lmm_prepare forms R_m.
+ *   3  the null fit of (p, e) is gbrs_scan_lmm_run's, by the same kernel, hsq_in honoured, the column centred by the
+ *      caller: sw = v^-1/2, Qz (cz columns), y~ and rss0.
+ *   4  the columns g = sw . y~,  o = sw . sw,  c_k = sw . Qz_k.
+ *   5  b = sum_i x*_i g_i,  raw = sum_i (x*_i x*_i) o_i,  qtx_k = sum_i x*_i c_k,i: each one chain over the samples in
+ *      ascending K-chunk order (f64 MFMA, chunks of 32) that depends on the SNP's row and the phenotype's column alone.
+ *   6  S = 0.0; for k ascending: S += qtx_k * qtx_k;  G = raw - S.  The pair is used iff G > 0 and G > 1e-10 raw
+ *      (gbrs_scan_snps' threshold and meaning);  ess = b * b / G, a true division;  lod = (n / 2) log10(rss0 /
+ *      (rss0 - ess)) with gbrs_scan_run's two edge rules.  A pair that is not used gives exactly 0.0, and the column of
+ *      zeros (rss0 = 0) gives 0.0 everywhere.
+ *   7  peak_lod[p][c], peak_index[p][c]: the largest LOD over the used SNPs of chromosome c and its index in handle
+ *      order, the lowest on ties; NaN and -1 when there is none.  n_used[p][c] counts the used SNPs.
+ * G is a difference of sums by the rule.  `used` depends on the phenotype, because the weights do.
+ * pheno double[n][P]; hsq_in double[P][n_eig] or NULL; lod double[P][M_snp], used uint8[P][M_snp], peak_lod
+ * double[P][n_chrom], peak_index and n_used int64[P][n_chrom], hsq and sigma2 double[P][n_eig]; every output nullable.
+ * The null fits' columns of all P stay on the device for the pass ((cz + 2) n_ld doubles per (p, e)); the SNPs pass in
+ * chunks of 65,536, each rotated once.  A number is the same bits for a SNP alone or among others, in any chunk, for a
+ * phenotype at any column, and however the cohort was appended.  GBRS_ERR_INVALID without SNPs on the handle, before
+ * gbrs_scan_lmm_prepare, for P < 1, for a phenotype value that is not finite (the message names the entry) and for a
+ * value of hsq_in outside [0, 1]; the outputs are untouched and the handle is as it was.  The call allocates and frees
+ * its own buffers: gbrs_scan_run, gbrs_scan_snps and gbrs_scan_lmm_run give the same bits before and after it. */
+int gbrs_scan_lmm_snps(gbrs_scan_t *scan, int64_t P, const double *pheno, const double *hsq_in /* [P][n_eig], nullable */,
+                       double *lod, uint8_t *used, double *peak_lod, int64_t *peak_index, int64_t *n_used,
+                       double *hsq /* [P][n_eig] */, double *sigma2);
+
+typedef struct gbrs_scan_lmm_snp_info {
+    int64_t  M_snp;              /* SNPs on the handle                                                           */
+    int64_t  chunk;              /* SNPs whose rotated rows are on the device at a time                          */
+    int64_t  P;                  /* of the last gbrs_scan_lmm_snps (0: none yet)                                 */
+    double   last_pass_ms;       /* device time of the pass: uploads, all kernels, copies                        */
+    double   last_null_ms;       /* its null fits: phenotype rotations, REML, the columns, over the chunks       */
+    double   last_rotate_ms;     /* its SNP dosages and their rotation, over the SNP chunks                      */
+    double   last_product_ms;    /* its product kernel, over (SNP chunk, phenotype chunk)                        */
+    uint64_t column_bytes;       /* the null fits' columns and rss0 of all P that the pass kept on the device    */
+    uint64_t peak_device_bytes;  /* what the handle held during the pass, the call's own buffers included        */
+} gbrs_scan_lmm_snp_info_t;
+int gbrs_scan_lmm_snp_info(gbrs_scan_t *scan, gbrs_scan_lmm_snp_info_t *info);
 
 /* ------------------------------------------------------------------------------------------
  * Report text (host side, no device work): the `locus <haplotypes> total [notes]` tables of

@@ -341,7 +341,8 @@ def _scan_options(parser, covar=True):
                              'cohort\'s dosages on the other chromosomes, MODE overall with the kinship of all of them; every '
                              'phenotype\'s heritability is fitted by REML.  <PREFIX>.scan.npz gains hsq and kinship_mode, the '
                              'peaks file the column hsq.  Not with --scan-perms, --scan-snps / --snp-file, --scan-mediate, '
-                             '--scan-effects or --scan-lod-drop; the SNP pass under the mixed model is --scan-kinship-snps')
+                             '--scan-effects or --scan-lod-drop; under the mixed model those are --scan-kinship-snps, '
+                             '--scan-kinship-effects and --scan-kinship-lod-drop')
     parser.add_argument('--scan-kinship-out', action='store_true',
                         help='with --scan-kinship: write the kinship matrices and the sample ids to <PREFIX>.scan.kinship.npz')
     parser.add_argument('--scan-kinship-snps', type=_existing, default=None, metavar='FILE',
@@ -349,6 +350,18 @@ def _scan_options(parser, covar=True):
                              '--snp-file; after the scan every SNP of it is tested with one degree of freedom under the same '
                              'kinship and the heritabilities the scan fitted.  Writes <PREFIX>.scan.snps.npz (with hsq, n_used '
                              'and kinship_mode) and <PREFIX>.scan.snps.peaks.tsv (with the column hsq)')
+    parser.add_argument('--scan-kinship-effects', action='store_true',
+                        help='with --scan-kinship: founder effects under the mixed model on the device.  For every (phenotype, '
+                             'chromosome) peak of the scan the generalised-least-squares effects of all founders and their '
+                             'standard errors, at the heritabilities the scan fitted.  Writes <PREFIX>.scan.effects.npz (with '
+                             'hsq and kinship_mode) and <PREFIX>.scan.effects.tsv (with the column hsq).  No BLUP shrinkage')
+    parser.add_argument('--scan-kinship-effects-min-lod', type=float, default=None, metavar='X',
+                        help='with --scan-kinship-effects: the peaks of at least this LOD get their effects (default: 6.0, as '
+                             '--scan-effects-min-lod)')
+    parser.add_argument('--scan-kinship-lod-drop', type=float, default=None, metavar='X',
+                        help='with --scan-kinship: LOD support intervals of the mixed model\'s peaks on the device, by '
+                             '--scan-lod-drop\'s rule.  <PREFIX>.scan.npz gains support_lo, support_hi and lod_drop, the peaks '
+                             'file the columns support_lo and support_hi after hsq')
 
 
 def main(argv=None) -> int:
@@ -479,7 +492,9 @@ def main(argv=None) -> int:
                         scan_mediator_file=args.scan_mediator_file, scan_effects=args.scan_effects,
                         scan_effects_min_lod=args.scan_effects_min_lod, scan_lod_drop=args.scan_lod_drop,
                         scan_kinship=args.scan_kinship, scan_kinship_out=args.scan_kinship_out,
-                        scan_kinship_snps=args.scan_kinship_snps)
+                        scan_kinship_snps=args.scan_kinship_snps, scan_kinship_effects=args.scan_kinship_effects,
+                        scan_kinship_effects_min_lod=args.scan_kinship_effects_min_lod,
+                        scan_kinship_lod_drop=args.scan_kinship_lod_drop)
         elif args.command == 'interpolate':
             from .postproc import interpolate
             interpolate(genoprob_file=args.genoprob_file, grid_file=args.grid_file, gpos_file=args.gpos_file,

@@ -341,6 +341,10 @@ scan_peak_kernel(int64_t M, int n_chrom, const int64_t *__restrict__ point_off, 
 
 #include "scan_lmm_snp.inc"
 
+// ---- founder effects under the mixed model -------------------------------------------------------------------------------------
+
+#include "scan_lmm_effects.inc"
+
 }  // namespace gbrs
 
 using namespace gbrs;
@@ -411,6 +415,10 @@ struct gbrs_scan {
     int64_t lsnp_P = 0;
     double t_lsnp_pass = 0, t_lsnp_null = 0, t_lsnp_rotate = 0, t_lsnp_product = 0;
     uint64_t lsnp_column_bytes = 0, lsnp_peak_bytes = 0;
+    // the last gbrs_scan_lmm_effects: its buffers are the call's own, as gbrs_scan_permute's
+    int64_t leff_T = 0, leff_P = 0, leff_columns = 0;
+    double t_leff_pass = 0, t_leff_null = 0, t_leff_target = 0;
+    uint64_t leff_peak_bytes = 0;
     uint64_t lmm_bytes() const {
         return lmm_U.bytes() + lmm_lam.bytes() + lmm_Zs.bytes() + lmm_R.bytes() + lmm_eig_of_point.bytes();
     }
@@ -1442,12 +1450,20 @@ int gbrs_scan_lmm_prepare(gbrs_scan_t *s, int cz, const double *Z, int n_eig, co
     return GBRS_OK;
 }
 
-int gbrs_scan_lmm_run(gbrs_scan_t *s, int64_t P, const double *pheno, const double *hsq_in, double *lod, double *peak_lod,
-                      int64_t *peak_index, double *hsq, double *sigma2) {
-    RoctxRange roctx_range("gbrs_scan_lmm_run");
+}  // extern "C"
+
+namespace {
+
+// The pass of gbrs_scan_lmm_run.  With support, gbrs_scan_lmm_run_support's: the intervals of every chunk follow its peaks
+// while its LOD rows are on the device, by scan_run_pass' kernel; the two tables of a chunk are the call's own.
+int scan_lmm_run_pass(gbrs_scan *s, int64_t P, const double *pheno, const double *hsq_in, bool support, double drop, double *lod,
+                      double *peak_lod, int64_t *peak_index, double *hsq, double *sigma2, int64_t *support_lo,
+                      int64_t *support_hi) {
     if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
     if (s->lmm_cz == 0) return fail(GBRS_ERR_INVALID, "no mixed model on the handle: call gbrs_scan_lmm_prepare first");
     if (P < 1 || !pheno) return fail(GBRS_ERR_INVALID, "bad argument");
+    if (support && !(drop >= 0.0 && std::isfinite(drop)))
+        return fail(GBRS_ERR_INVALID, "the LOD drop of a support interval must be a finite number that is not negative, got %g", drop);
     const int n = (int)s->n, cz = s->lmm_cz, n_eig = s->lmm_n_eig;
     for (int64_t k = 0; k < (int64_t)n * P; ++k)
         if (!std::isfinite(pheno[k]))
@@ -1479,6 +1495,11 @@ int gbrs_scan_lmm_run(gbrs_scan_t *s, int64_t P, const double *pheno, const doub
     GBRS_TRY(d_index.alloc((size_t)pc_max * s->n_chrom));
     GBRS_TRY(d_rmin.alloc((size_t)pc_max));
     GBRS_TRY(d_rmax.alloc((size_t)pc_max));
+    DevBuf<int64_t> d_lo, d_hi;
+    if (support) {
+        GBRS_TRY(d_lo.alloc((size_t)pc_max * s->n_chrom));
+        GBRS_TRY(d_hi.alloc((size_t)pc_max * s->n_chrom));
+    }
     // a point's weighted columns: the workgroup's LDS, or past LM_LDS_BYTES a workspace and the points in batches
     const size_t w_bytes = (size_t)Hp * n_ld * sizeof(double);
     const bool in_lds = w_bytes <= LM_LDS_BYTES;
@@ -1525,6 +1546,9 @@ int gbrs_scan_lmm_run(gbrs_scan_t *s, int64_t P, const double *pheno, const doub
         GBRS_HIP_CHECK(hipEventRecord(mark[3], s->stream));
         hipLaunchKernelGGL(scan_peak_kernel, dim3((unsigned)s->n_chrom, (unsigned)pc), dim3(64), 0, s->stream, M, s->n_chrom,
                            s->d_point_off.p, d_lod.p, d_peak.p, d_index.p);
+        if (support)
+            hipLaunchKernelGGL(scan_support_kernel, dim3((unsigned)s->n_chrom, (unsigned)pc), dim3(64), 0, s->stream, M, s->n_chrom,
+                               drop, s->d_point_off.p, d_lod.p, d_peak.p, d_index.p, d_lo.p, d_hi.p);
         GBRS_HIP_CHECK(hipGetLastError());
         GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
         float ms = 0.f;
@@ -1538,6 +1562,10 @@ int gbrs_scan_lmm_run(gbrs_scan_t *s, int64_t P, const double *pheno, const doub
             GBRS_HIP_CHECK(hipMemcpy(peak_index + p0 * s->n_chrom, d_index.p, (size_t)pc * s->n_chrom * sizeof(int64_t), hipMemcpyDeviceToHost));
         if (hsq) GBRS_HIP_CHECK(hipMemcpy(hsq + p0 * n_eig, d_hsq.p, (size_t)pc * n_eig * sizeof(double), hipMemcpyDeviceToHost));
         if (sigma2) GBRS_HIP_CHECK(hipMemcpy(sigma2 + p0 * n_eig, d_sigma2.p, (size_t)pc * n_eig * sizeof(double), hipMemcpyDeviceToHost));
+        if (support_lo)
+            GBRS_HIP_CHECK(hipMemcpy(support_lo + p0 * s->n_chrom, d_lo.p, (size_t)pc * s->n_chrom * sizeof(int64_t), hipMemcpyDeviceToHost));
+        if (support_hi)
+            GBRS_HIP_CHECK(hipMemcpy(support_hi + p0 * s->n_chrom, d_hi.p, (size_t)pc * s->n_chrom * sizeof(int64_t), hipMemcpyDeviceToHost));
         GBRS_HIP_CHECK(hipMemcpy(rmin.data() + p0, d_rmin.p, (size_t)pc * sizeof(int32_t), hipMemcpyDeviceToHost));
         GBRS_HIP_CHECK(hipMemcpy(rmax.data() + p0, d_rmax.p, (size_t)pc * sizeof(int32_t), hipMemcpyDeviceToHost));
     }
@@ -1555,7 +1583,210 @@ int gbrs_scan_lmm_run(gbrs_scan_t *s, int64_t P, const double *pheno, const doub
                         s->yt.bytes() + s->rss0.bytes() + s->lod.bytes() + s->peak_lod.bytes() + s->peak_index.bytes() + s->snp_bytes() +
                         s->kin_S.bytes() + s->lmm_bytes() + y.bytes() + ys.bytes() + d_hin.bytes() + d_hsq.bytes() + d_sigma2.bytes() +
                         sw.bytes() + qz.bytes() + yt.bytes() + rss0.bytes() + d_lod.bytes() + d_peak.bytes() + d_index.bytes() +
-                        d_rmin.bytes() + d_rmax.bytes() + ws.bytes();
+                        d_rmin.bytes() + d_rmax.bytes() + ws.bytes() + d_lo.bytes() + d_hi.bytes();
+    return GBRS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gbrs_scan_lmm_run(gbrs_scan_t *s, int64_t P, const double *pheno, const double *hsq_in, double *lod, double *peak_lod,
+                      int64_t *peak_index, double *hsq, double *sigma2) {
+    RoctxRange roctx_range("gbrs_scan_lmm_run");
+    return scan_lmm_run_pass(s, P, pheno, hsq_in, false, 0.0, lod, peak_lod, peak_index, hsq, sigma2, nullptr, nullptr);
+}
+
+int gbrs_scan_lmm_run_support(gbrs_scan_t *s, int64_t P, const double *pheno, const double *hsq_in, double drop, double *lod,
+                              double *peak_lod, int64_t *peak_index, double *hsq, double *sigma2, int64_t *support_lo,
+                              int64_t *support_hi) {
+    RoctxRange roctx_range("gbrs_scan_lmm_run_support");
+    return scan_lmm_run_pass(s, P, pheno, hsq_in, true, drop, lod, peak_lod, peak_index, hsq, sigma2, support_lo, support_hi);
+}
+
+// Founder effects under the mixed model.  The columns some target names are compacted on the host and pass
+// in gbrs_scan_lmm_run's chunks of 512 through its rotation and its null fits - every decomposition of a used column, hsq_in
+// honoured -; a chunk's targets, in the caller's order, follow in chunks of SE_TCHUNK while the chunk's fits are on the device.
+int gbrs_scan_lmm_effects(gbrs_scan_t *s, int64_t P, const double *pheno, const double *hsq_in, int64_t T, const int64_t *column,
+                          const int64_t *point, double *effect, double *se, double *lod, double *sigma2, int32_t *rank,
+                          double *hsq) {
+    RoctxRange roctx_range("gbrs_scan_lmm_effects");
+    if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (s->lmm_cz == 0) return fail(GBRS_ERR_INVALID, "no mixed model on the handle: call gbrs_scan_lmm_prepare first");
+    if (P < 1) return fail(GBRS_ERR_INVALID, "an effects pass needs at least 1 phenotype, got %lld", (long long)P);
+    if (T < 0) return fail(GBRS_ERR_INVALID, "the number of targets cannot be negative, got %lld", (long long)T);
+    if (!pheno || (T > 0 && (!column || !point))) return fail(GBRS_ERR_INVALID, "bad argument");
+    const int n = (int)s->n, cz = s->lmm_cz, n_eig = s->lmm_n_eig, H = s->H, Hp = s->Hp;
+    for (int64_t t = 0; t < T; ++t) {
+        if (column[t] < 0 || column[t] >= P)
+            return fail(GBRS_ERR_INVALID, "target %lld is phenotype column %lld: the table has the columns 0 .. %lld", (long long)t,
+                        (long long)column[t], (long long)(P - 1));
+        if (point[t] < 0 || point[t] >= s->M)
+            return fail(GBRS_ERR_INVALID, "target %lld is at grid point %lld: the handle has the points 0 .. %lld", (long long)t,
+                        (long long)point[t], (long long)(s->M - 1));
+    }
+    for (int64_t k = 0; k < (int64_t)n * P; ++k)
+        if (!std::isfinite(pheno[k]))
+            return fail(GBRS_ERR_INVALID, "phenotype %lld holds a value that is not finite (sample %lld)", (long long)(k % P),
+                        (long long)(k / P));
+    if (hsq_in)
+        for (int64_t k = 0; k < P * n_eig; ++k)
+            if (!(hsq_in[k] >= 0.0 && hsq_in[k] <= 1.0))
+                return fail(GBRS_ERR_INVALID, "the heritability given for phenotype %lld and decomposition %d is %g, outside [0, 1]",
+                            (long long)(k / n_eig), (int)(k % n_eig), hsq_in[k]);
+    if (T == 0) return GBRS_OK;
+    // the used columns in ascending order, and every column's targets in the caller's order
+    std::vector<int64_t> slot((size_t)P, -1), used;
+    for (int64_t t = 0; t < T; ++t) slot[column[t]] = 0;
+    for (int64_t p = 0; p < P; ++p)
+        if (slot[p] == 0) {
+            slot[p] = (int64_t)used.size();
+            used.push_back(p);
+        }
+    const int64_t Pu = (int64_t)used.size(), pc_max = std::min(Pu, SC_PCHUNK), n_ld = s->lmm_n_ld;
+    std::vector<double> y_used((size_t)n * Pu), h_used(hsq_in ? (size_t)Pu * n_eig : 0);
+    for (int64_t i = 0; i < n; ++i)
+        for (int64_t q = 0; q < Pu; ++q) y_used[i * Pu + q] = pheno[i * P + used[q]];
+    if (hsq_in)
+        for (int64_t q = 0; q < Pu; ++q)
+            for (int e = 0; e < n_eig; ++e) h_used[q * n_eig + e] = hsq_in[used[q] * n_eig + e];
+    std::vector<std::vector<int64_t>> of_chunk((size_t)((Pu + SC_PCHUNK - 1) / SC_PCHUNK));
+    for (int64_t t = 0; t < T; ++t) of_chunk[slot[column[t]] / SC_PCHUNK].push_back(t);
+    GBRS_TRY(select_device(s->device));
+    const int64_t tc_max = std::min(T, SE_TCHUNK);
+    const size_t pe = (size_t)pc_max * n_eig;
+    DevBuf<double> y, ys, d_hin, d_hsq, d_s2, sw, qz, yt, rss0, ws, d_effect, d_se, d_lod, d_sigma2, d_hout;
+    DevBuf<int64_t> d_column, d_point;
+    DevBuf<int32_t> d_rmin, d_rmax, d_rank;
+    GBRS_TRY(y.alloc((size_t)n * pc_max));
+    GBRS_TRY(ys.alloc(pe * n_ld));
+    if (hsq_in) GBRS_TRY(d_hin.alloc(pe));
+    GBRS_TRY(d_hsq.alloc(pe));
+    GBRS_TRY(d_s2.alloc(pe));
+    GBRS_TRY(sw.alloc(pe * n_ld));
+    GBRS_TRY(qz.alloc(pe * cz * n_ld));
+    GBRS_TRY(yt.alloc(pe * n_ld));
+    GBRS_TRY(rss0.alloc(pe));
+    GBRS_TRY(d_rmin.alloc((size_t)pc_max));
+    GBRS_TRY(d_rmax.alloc((size_t)pc_max));
+    GBRS_TRY(d_effect.alloc((size_t)tc_max * H));
+    GBRS_TRY(d_se.alloc((size_t)tc_max * H));
+    GBRS_TRY(d_lod.alloc((size_t)tc_max));
+    GBRS_TRY(d_sigma2.alloc((size_t)tc_max));
+    GBRS_TRY(d_hout.alloc((size_t)tc_max));
+    GBRS_TRY(d_rank.alloc((size_t)tc_max));
+    GBRS_TRY(d_column.alloc((size_t)tc_max));
+    GBRS_TRY(d_point.alloc((size_t)tc_max));
+    // a target's weighted columns: the workgroup's LDS, or past LM_LDS_BYTES its slice of a workspace
+    const size_t w_bytes = (size_t)Hp * n_ld * sizeof(double);
+    const bool in_lds = w_bytes <= LM_LDS_BYTES;
+    if (!in_lds) GBRS_TRY(ws.alloc((size_t)tc_max * Hp * n_ld));
+    std::vector<double> h_effect((size_t)T * H), h_se((size_t)T * H), h_lod((size_t)T), h_sigma2((size_t)T), h_hsq((size_t)T);
+    std::vector<int32_t> h_rank((size_t)T);
+    std::vector<double> c_effect((size_t)tc_max * H), c_se((size_t)tc_max * H), c_lod((size_t)tc_max), c_sigma2((size_t)tc_max),
+        c_hsq((size_t)tc_max);
+    std::vector<int32_t> c_rank((size_t)tc_max);
+    std::vector<int64_t> c_column((size_t)tc_max), c_point((size_t)tc_max);
+    double t_null = 0.0, t_target = 0.0;
+    hipEvent_t mark[3] = {};
+    struct Marks {
+        hipEvent_t *ev;
+        ~Marks() {
+            for (int k = 0; k < 3; ++k)
+                if (ev[k]) (void)hipEventDestroy(ev[k]);
+        }
+    } marks{mark};
+    for (auto &e : mark) GBRS_HIP_CHECK(hipEventCreate(&e));
+    GBRS_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
+    for (int64_t p0 = 0; p0 < Pu; p0 += SC_PCHUNK) {
+        const int64_t pc = std::min(SC_PCHUNK, Pu - p0);
+        const std::vector<int64_t> &mine = of_chunk[(size_t)(p0 / SC_PCHUNK)];
+        GBRS_HIP_CHECK(hipMemcpy2DAsync(y.p, (size_t)pc * sizeof(double), y_used.data() + p0, (size_t)Pu * sizeof(double),
+                                        (size_t)pc * sizeof(double), (size_t)n, hipMemcpyHostToDevice, s->stream));
+        if (hsq_in)
+            GBRS_HIP_CHECK(hipMemcpyAsync(d_hin.p, h_used.data() + p0 * n_eig, (size_t)pc * n_eig * sizeof(double), hipMemcpyHostToDevice, s->stream));
+        GBRS_HIP_CHECK(hipEventRecord(mark[0], s->stream));
+        for (int e = 0; e < n_eig; ++e)
+            scan_lmm_rotate(s, n_ld, pc, 1, 1, 1, pc, s->lmm_U.p + (size_t)e * n * n, y.p, ys.p + (size_t)e * pc * n_ld);
+        hipLaunchKernelGGL(lmm_null_kernel, dim3((unsigned)pc, (unsigned)n_eig), dim3(64), 0, s->stream, n, cz, n_ld, pc, n_eig, ys.p,
+                           s->lmm_Zs.p, s->lmm_lam.p, hsq_in ? d_hin.p : nullptr, d_hsq.p, d_s2.p, sw.p, qz.p, yt.p, rss0.p,
+                           d_rmin.p, d_rmax.p);
+        GBRS_HIP_CHECK(hipEventRecord(mark[1], s->stream));
+        GBRS_HIP_CHECK(hipGetLastError());
+        for (size_t t0 = 0; t0 < mine.size(); t0 += (size_t)SE_TCHUNK) {
+            const int64_t tc = (int64_t)std::min<size_t>((size_t)SE_TCHUNK, mine.size() - t0);
+            for (int64_t k = 0; k < tc; ++k) {
+                const int64_t t = mine[t0 + k];
+                c_column[k] = slot[column[t]] - p0;
+                c_point[k] = point[t];
+            }
+            GBRS_HIP_CHECK(hipMemcpyAsync(d_column.p, c_column.data(), (size_t)tc * sizeof(int64_t), hipMemcpyHostToDevice, s->stream));
+            GBRS_HIP_CHECK(hipMemcpyAsync(d_point.p, c_point.data(), (size_t)tc * sizeof(int64_t), hipMemcpyHostToDevice, s->stream));
+            auto launch = [&](auto kernel) {
+                hipLaunchKernelGGL(kernel, dim3((unsigned)tc), dim3(SC_THREADS), in_lds ? w_bytes : 0, s->stream, n, H, cz, n_ld, n_eig,
+                                   0.5 * n, s->lmm_eig_of_point.p, s->lmm_R.p, sw.p, qz.p, yt.p, rss0.p, d_hsq.p, d_column.p, d_point.p,
+                                   in_lds ? nullptr : ws.p, d_effect.p, d_se.p, d_lod.p, d_sigma2.p, d_rank.p, d_hout.p);
+            };
+            if (Hp == 8) launch(lmm_effects_kernel<8>);
+            else launch(lmm_effects_kernel<16>);
+            GBRS_HIP_CHECK(hipGetLastError());
+            GBRS_HIP_CHECK(hipMemcpyAsync(c_effect.data(), d_effect.p, (size_t)tc * H * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+            GBRS_HIP_CHECK(hipMemcpyAsync(c_se.data(), d_se.p, (size_t)tc * H * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+            GBRS_HIP_CHECK(hipMemcpyAsync(c_lod.data(), d_lod.p, (size_t)tc * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+            GBRS_HIP_CHECK(hipMemcpyAsync(c_sigma2.data(), d_sigma2.p, (size_t)tc * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+            GBRS_HIP_CHECK(hipMemcpyAsync(c_hsq.data(), d_hout.p, (size_t)tc * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+            GBRS_HIP_CHECK(hipMemcpyAsync(c_rank.data(), d_rank.p, (size_t)tc * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+            GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
+            for (int64_t k = 0; k < tc; ++k) {              // to the target's own place
+                const int64_t t = mine[t0 + k];
+                std::memcpy(h_effect.data() + t * H, c_effect.data() + k * H, (size_t)H * sizeof(double));
+                std::memcpy(h_se.data() + t * H, c_se.data() + k * H, (size_t)H * sizeof(double));
+                h_lod[t] = c_lod[k];
+                h_sigma2[t] = c_sigma2[k];
+                h_hsq[t] = c_hsq[k];
+                h_rank[t] = c_rank[k];
+            }
+        }
+        GBRS_HIP_CHECK(hipEventRecord(mark[2], s->stream));
+        GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, mark[0], mark[1]) == hipSuccess) t_null += ms;
+        if (hipEventElapsedTime(&ms, mark[1], mark[2]) == hipSuccess) t_target += ms;
+    }
+    GBRS_HIP_CHECK(hipEventRecord(s->ev[1], s->stream));
+    GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
+    // the caller's arrays are written once the whole pass has succeeded
+    if (effect) std::memcpy(effect, h_effect.data(), h_effect.size() * sizeof(double));
+    if (se) std::memcpy(se, h_se.data(), h_se.size() * sizeof(double));
+    if (lod) std::memcpy(lod, h_lod.data(), h_lod.size() * sizeof(double));
+    if (sigma2) std::memcpy(sigma2, h_sigma2.data(), h_sigma2.size() * sizeof(double));
+    if (rank) std::memcpy(rank, h_rank.data(), h_rank.size() * sizeof(int32_t));
+    if (hsq) std::memcpy(hsq, h_hsq.data(), h_hsq.size() * sizeof(double));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) s->t_leff_pass = ms;
+    s->t_leff_null = t_null;
+    s->t_leff_target = t_target;
+    s->leff_T = T;
+    s->leff_P = P;
+    s->leff_columns = Pu;
+    s->leff_peak_bytes = s->d_point_off.bytes() + s->dosage.bytes() + s->qz.bytes() + s->W.bytes() + s->d_rank.bytes() + s->y.bytes() +
+                         s->yt.bytes() + s->rss0.bytes() + s->lod.bytes() + s->peak_lod.bytes() + s->peak_index.bytes() + s->snp_bytes() +
+                         s->kin_S.bytes() + s->lmm_bytes() + y.bytes() + ys.bytes() + d_hin.bytes() + d_hsq.bytes() + d_s2.bytes() +
+                         sw.bytes() + qz.bytes() + yt.bytes() + rss0.bytes() + d_rmin.bytes() + d_rmax.bytes() + ws.bytes() +
+                         d_effect.bytes() + d_se.bytes() + d_lod.bytes() + d_sigma2.bytes() + d_hout.bytes() + d_rank.bytes() +
+                         d_column.bytes() + d_point.bytes();
+    return GBRS_OK;
+}
+
+int gbrs_scan_lmm_effects_info(gbrs_scan_t *s, gbrs_scan_lmm_effects_info_t *info) {
+    if (!s || !info) return fail(GBRS_ERR_INVALID, "bad argument");
+    info->T = s->leff_T;
+    info->P = s->leff_P;
+    info->columns = s->leff_columns;
+    info->last_pass_ms = s->t_leff_pass;
+    info->last_null_ms = s->t_leff_null;
+    info->last_target_ms = s->t_leff_target;
+    info->peak_device_bytes = s->leff_peak_bytes;
     return GBRS_OK;
 }
 

@@ -392,6 +392,8 @@ lmm_null_kernel(int n, int cz, int64_t n_ld, int64_t pc, int n_eig, const double
 //      columns, ess = |z|^2, the LOD by scan_lod into the chunk's [P][M] rows
 // No W is written.  w is the workgroup's LDS (ws null) or its own HP n_ld doubles of ws; the sums and their order are the
 // same either way.  The phenotype's rank range takes the point's rank by integer atomics.
+// lmm_effects_kernel (scan_lmm_effects.inc) repeats steps 1-5 line for line so that its LOD carries this kernel's bits: a
+// change of a sum, of its order or of the factorisation here must be made there too (test_scan_lmm_effects_gpu.py compares with ==).
 template <int HP>
 __global__ void __launch_bounds__(SC_THREADS)
 lmm_point_kernel(int n, int64_t M, int64_t m0, int H, int cz, int64_t n_ld, int64_t pc, int n_eig, int tile, double half_n,

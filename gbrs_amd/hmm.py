@@ -1407,7 +1407,9 @@ class ReconstructOptions:
     `scan_kinship`, `scan_kinship_out`: the scan is the linear mixed model's with the cohort's own
     leave-one-chromosome-out or overall kinship (scan.kinship_options); the other scan passes are then refused.
     `scan_kinship_snps` (needs `scan_kinship`): a SNP file in `snp_file`'s format whose SNPs are tested
-    with one degree of freedom under the same mixed model after the scan, at the heritabilities it fitted."""
+    with one degree of freedom under the same mixed model after the scan, at the heritabilities it fitted.
+    `scan_kinship_effects`, `scan_kinship_effects_min_lod`, `scan_kinship_lod_drop` (need `scan_kinship`):
+    `scan_effects`' files and `scan_lod_drop`'s columns under the mixed model (scan.kinship_effects_options)."""
     expr_threshold: float = 1.5
     sigma: float = 0.12
     grid_genoprobs: bool = False
@@ -1449,6 +1451,9 @@ class ReconstructOptions:
     scan_kinship: str = None
     scan_kinship_out: bool = False
     scan_kinship_snps: str = None
+    scan_kinship_effects: bool = False
+    scan_kinship_effects_min_lod: float = None
+    scan_kinship_lod_drop: float = None
 
     @classmethod
     def of(cls, keywords):
@@ -1482,7 +1487,9 @@ class ReconstructOptions:
                         scan_effects=self.scan_effects, scan_effects_min_lod=self.scan_effects_min_lod,
                         scan_lod_drop=self.scan_lod_drop, scan_kinship=self.scan_kinship,
                         scan_kinship_out=self.scan_kinship_out, scan_snps=self.scan_snps,
-                        scan_kinship_snps=self.scan_kinship_snps)
+                        scan_kinship_snps=self.scan_kinship_snps, scan_kinship_effects=self.scan_kinship_effects,
+                        scan_kinship_effects_min_lod=self.scan_kinship_effects_min_lod,
+                        scan_kinship_lod_drop=self.scan_kinship_lod_drop)
         check_scan_snp_args(self.scan_snps, self.snp_file, self.scan_pheno, grid_file, cohort=cohort)
 
 
@@ -1771,7 +1778,9 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
                      scan_perm_pheno: str = None, scan_snps: bool = False, scan_mediate: bool = False,
                      scan_mediate_min_lod: float = None, scan_mediate_top: int = None, scan_mediator_file: str = None,
                      scan_effects: bool = False, scan_effects_min_lod: float = None, scan_lod_drop: float = None,
-                     scan_kinship: str = None, scan_kinship_out: bool = False, scan_kinship_snps: str = None) -> list:
+                     scan_kinship: str = None, scan_kinship_out: bool = False, scan_kinship_snps: str = None,
+                     scan_kinship_effects: bool = False, scan_kinship_effects_min_lod: float = None,
+                     scan_kinship_lod_drop: float = None) -> list:
     """`gbrs reconstruct` for a cohort whose genes.tpm files exist (extension): one context, the tables on the device
     once, the samples through the HMM in launches of up to `batch_size`, and every pass the options ask for once per
     launch.  Every sample gets the files the single-sample call writes for its outbase.  All samples must carry the same
@@ -1785,7 +1794,9 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
     scan_perm = scan_mod.perm_options(scan_perms, scan_perm_seed, scan_perm_alpha, scan_perm_chromosomes, scan_perm_pheno)
     scan_med = scan_mod.mediate_options(scan_mediate, scan_mediate_min_lod, scan_mediate_top, scan_mediator_file)
     scan_eff = scan_mod.effects_options(scan_effects, scan_effects_min_lod, scan_lod_drop)
-    with_effects = scan_eff is not None and scan_eff['min_lod'] is not None
+    scan_kin_eff = scan_mod.kinship_effects_options(scan_kinship_effects, scan_kinship_effects_min_lod, scan_kinship_lod_drop,
+                                                    scan_kinship)
+    with_effects = any(e is not None and e['min_lod'] is not None for e in (scan_eff, scan_kin_eff))
     scan_kin = scan_mod.kinship_options(scan_kinship, scan_kinship_out, scan_perms, scan_snps, scan_mediate, scan_effects,
                                         scan_lod_drop)
     clock = time.perf_counter
@@ -1943,7 +1954,8 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
                                  list(ctx.chroms), scan_min_lod, scan_lod_matrix, perm=scan_perm, stage_times=marks,
                                  snps=shared.snps if scan_snps else None, snp_grid=ctx.grid, mediate=scan_med,
                                  effects=scan_eff, founders=haplotypes, kinship=scan_kin,
-                                 kinship_snps=scan_kin_snps if scan_kinship_snps is not None else None)
+                                 kinship_snps=scan_kin_snps if scan_kinship_snps is not None else None,
+                                 kinship_effects=scan_kin_eff)
             marks['scan'] += clock() - t0 - (marks['scan_perm'] if scan_perm is not None else 0.0) - \
                 (marks['scan_snps'] if scan_snps or scan_kinship_snps is not None else 0.0) - (marks['mediate'] if scan_med is not None else 0.0) - \
                 (marks['effects'] if with_effects else 0.0)

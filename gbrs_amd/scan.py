@@ -7,7 +7,8 @@ SNPs under that model, after the scan and at its heritabilities (gbrs_scan_lmm_s
 --snp-file`: the 1-df test of founder SNPs on the same prepared cohort (gbrs_scan_set_snps, gbrs_scan_snps).
 `--scan-mediate`: the scan's peaks conditioned on every other phenotype in turn (gbrs_scan_mediate).
 `--scan-effects`, `--scan-lod-drop`: the founder effects at the scan's peaks with their standard errors
-(gbrs_scan_effects) and the peaks' LOD support intervals (gbrs_scan_run_support)."""
+(gbrs_scan_effects) and the peaks' LOD support intervals (gbrs_scan_run_support); `--scan-kinship-effects`,
+`--scan-kinship-lod-drop`: both under the mixed model (gbrs_scan_lmm_effects, gbrs_scan_lmm_run_support)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -395,26 +396,62 @@ class GenomeScan:
                 'rotate_ms': raw.last_rotate_ms, 'product_ms': raw.last_product_ms, 'column_bytes': raw.column_bytes,
                 'peak_device_bytes': raw.peak_device_bytes}
 
-    def run_lmm(self, pheno, want_lod=True, hsq=None):
+    def run_lmm(self, pheno, want_lod=True, hsq=None, lod_drop=None):
         """pheno: [n, P] (or [n]) under the prepared mixed model.  Every column's mean is subtracted before the upload (the
         intercept absorbs it) and a constant column goes as zeros: hsq 0 and LODs 0.0.  hsq: [P, n_chrom] heritabilities
         in [0, 1] to scan with instead of fitting them (chromosomes that share a decomposition must agree; the first
         one's value is taken).  Returns `peak_lod`, `peak_index` [P, n_chrom], `hsq` and `sigma2` [P, n_chrom] (per
-        chromosome, through `eig_of_chrom`), `rank_min`, `rank_max` [P] and, with want_lod, `lod` [P, M]."""
+        chromosome, through `eig_of_chrom`), `rank_min`, `rank_max` [P] and, with want_lod, `lod` [P, M].  lod_drop: with
+        a number the pass also forms every peak's LOD support interval by run()'s rule and the dict gains
+        `support_lo` and `support_hi` [P, n_chrom], grid indices, -1 for a chromosome without points; everything else is
+        the same bits."""
         y, given, n_eig = self._lmm_inputs(pheno, hsq)
         P, nc, mapping = y.shape[1], len(self.points), self.eig_of_chrom
         lod = np.empty((P, self.M)) if want_lod else None
         peak, index = np.empty((P, nc)), np.empty((P, nc), dtype=np.int64)
         fitted, sigma2 = np.empty((P, n_eig)), np.empty((P, n_eig))
-        _lib.check(_lib.load().gbrs_scan_lmm_run(self._h, P, _lib.ptr(y), _lib.ptr(given), _lib.ptr(lod), _lib.ptr(peak),
-                                                 _lib.ptr(index), _lib.ptr(fitted), _lib.ptr(sigma2)))
+        if lod_drop is None:
+            _lib.check(_lib.load().gbrs_scan_lmm_run(self._h, P, _lib.ptr(y), _lib.ptr(given), _lib.ptr(lod), _lib.ptr(peak),
+                                                     _lib.ptr(index), _lib.ptr(fitted), _lib.ptr(sigma2)))
+        else:
+            lo, hi = np.empty((P, nc), dtype=np.int64), np.empty((P, nc), dtype=np.int64)
+            _lib.check(_lib.load().gbrs_scan_lmm_run_support(self._h, P, _lib.ptr(y), _lib.ptr(given), float(lod_drop),
+                                                             _lib.ptr(lod), _lib.ptr(peak), _lib.ptr(index), _lib.ptr(fitted),
+                                                             _lib.ptr(sigma2), _lib.ptr(lo), _lib.ptr(hi)))
         rank_min, rank_max = np.empty(P, dtype=np.int32), np.empty(P, dtype=np.int32)
         _lib.check(_lib.load().gbrs_scan_lmm_ranks(self._h, _lib.ptr(rank_min), _lib.ptr(rank_max)))
         out = {'peak_lod': peak, 'peak_index': index, 'hsq': fitted[:, mapping], 'sigma2': sigma2[:, mapping],
                'rank_min': rank_min, 'rank_max': rank_max}
         if want_lod:
             out['lod'] = lod
+        if lod_drop is not None:
+            out['support_lo'], out['support_hi'] = lo, hi
         return out
+
+    def effects_lmm(self, pheno, column, point, hsq=None):
+        """Founder effects at chosen points under the prepared mixed model.  pheno and hsq as for run_lmm,
+        centred by the same code; hsq is [P, n_chrom], for instance what run_lmm fitted.  column: [T] phenotype columns;
+        point: [T] grid point indices (a column's peak).  Returns `effect` and `se` [T, H] - the generalised-least-squares
+        effects of all H founders and their standard errors -, `lod` [T] (run_lmm's bits at the point), `sigma2` [T] (the
+        residual variance on the whitened scale), `hsq` [T] (the heritability the target was formed with) and `rank` [T]."""
+        y, given, n_eig = self._lmm_inputs(pheno, hsq)
+        col = np.ascontiguousarray(np.atleast_1d(column), dtype=np.int64)
+        at = np.ascontiguousarray(np.atleast_1d(point), dtype=np.int64)
+        if col.ndim != 1 or at.shape != col.shape:
+            raise ValueError(f'{col.shape} phenotype columns and {at.shape} grid points')
+        P, T = y.shape[1], len(col)
+        effect, se = np.empty((T, self.H)), np.empty((T, self.H))
+        lod, sigma2, fitted, rank = np.empty(T), np.empty(T), np.empty(T), np.empty(T, dtype=np.int32)
+        _lib.check(_lib.load().gbrs_scan_lmm_effects(self._h, P, _lib.ptr(y), _lib.ptr(given), T, _lib.ptr(col), _lib.ptr(at),
+                                                     _lib.ptr(effect), _lib.ptr(se), _lib.ptr(lod), _lib.ptr(sigma2),
+                                                     _lib.ptr(rank), _lib.ptr(fitted)))
+        return {'effect': effect, 'se': se, 'lod': lod, 'sigma2': sigma2, 'hsq': fitted, 'rank': rank}
+
+    def lmm_effects_info(self):
+        raw = _lib.ScanLmmEffectsInfo()
+        _lib.check(_lib.load().gbrs_scan_lmm_effects_info(self._h, C.byref(raw)))
+        return {'T': raw.T, 'P': raw.P, 'columns': raw.columns, 'pass_ms': raw.last_pass_ms, 'null_ms': raw.last_null_ms,
+                'target_ms': raw.last_target_ms, 'peak_device_bytes': raw.peak_device_bytes}
 
     def lmm_info(self):
         raw = _lib.ScanLmmInfo()
@@ -635,16 +672,47 @@ def kinship_snp_options(scan_kinship_snps=None, scan_kinship=None):
     return scan_kinship_snps
 
 
+def kinship_effects_options(scan_kinship_effects=False, scan_kinship_effects_min_lod=None, scan_kinship_lod_drop=None,
+                            scan_kinship=None):
+    """`--scan-kinship-effects [--scan-kinship-effects-min-lod X]` and `--scan-kinship-lod-drop X` as one
+    dict `{'min_lod': X or None without --scan-kinship-effects, 'lod_drop': X or None}`, or None with neither.  Both need
+    `--scan-kinship`; `--scan-kinship-effects-min-lod` alone is refused.  Refused before a file is read."""
+    if scan_kinship is None:
+        for name, value in (('--scan-kinship-effects', scan_kinship_effects or None),
+                            ('--scan-kinship-effects-min-lod', scan_kinship_effects_min_lod),
+                            ('--scan-kinship-lod-drop', scan_kinship_lod_drop)):
+            if value is not None:
+                raise RuntimeError(f'{name} needs --scan-kinship: without a kinship the pass is {name.replace("-kinship", "")}')
+    if not scan_kinship_effects and scan_kinship_effects_min_lod is not None:
+        raise RuntimeError('--scan-kinship-effects-min-lod needs --scan-kinship-effects')
+    min_lod = None
+    if scan_kinship_effects:
+        min_lod = DEFAULT_EFFECTS_MIN_LOD if scan_kinship_effects_min_lod is None else float(scan_kinship_effects_min_lod)
+        if not (min_lod >= 0.0 and np.isfinite(min_lod)):
+            raise RuntimeError(f'--scan-kinship-effects-min-lod must be a finite number that is not negative, got '
+                               f'{scan_kinship_effects_min_lod}')
+    drop = None
+    if scan_kinship_lod_drop is not None:
+        drop = float(scan_kinship_lod_drop)
+        if not (drop >= 0.0 and np.isfinite(drop)):
+            raise RuntimeError(f'--scan-kinship-lod-drop must be a finite number that is not negative, got {scan_kinship_lod_drop}')
+    if min_lod is None and drop is None:
+        return None
+    return {'min_lod': min_lod, 'lod_drop': drop}
+
+
 def check_scan_args(scan_pheno=None, scan_covar=None, scan_rankz=False, scan_out=None, scan_min_lod=None,
                     scan_lod_matrix=False, grid_file=None, cohort=False, scan_perms=None, scan_perm_seed=None,
                     scan_perm_alpha=None, scan_perm_chromosomes=None, scan_perm_pheno=None, scan_mediate=False,
                     scan_mediate_min_lod=None, scan_mediate_top=None, scan_mediator_file=None, scan_effects=False,
                     scan_effects_min_lod=None, scan_lod_drop=None, scan_kinship=None, scan_kinship_out=False, scan_snps=False,
-                    scan_kinship_snps=None):
+                    scan_kinship_snps=None, scan_kinship_effects=False, scan_kinship_effects_min_lod=None,
+                    scan_kinship_lod_drop=None):
     """`--scan-pheno FILE [--scan-covar FILE] [--scan-rankz] [--scan-out PREFIX] [--scan-min-lod X] [--scan-lod-matrix]`,
     the `--scan-perm*` options (perm_options), the `--scan-mediat*` options (mediate_options), `--scan-effects`,
     `--scan-effects-min-lod`, `--scan-lod-drop` (effects_options) and `--scan-kinship`, `--scan-kinship-out`
-    (kinship_options):
+    (kinship_options) with `--scan-kinship-snps` (kinship_snp_options), `--scan-kinship-effects`,
+    `--scan-kinship-effects-min-lod` and `--scan-kinship-lod-drop` (kinship_effects_options):
     every option needs the phenotypes, the phenotypes need `--grid-file` and a cohort (`--sample-file`): one sample
     cannot be scanned.  Refused before a file is read."""
     given = {'--scan-covar': scan_covar, '--scan-rankz': scan_rankz or None, '--scan-out': scan_out,
@@ -655,12 +723,14 @@ def check_scan_args(scan_pheno=None, scan_covar=None, scan_rankz=False, scan_out
              '--scan-mediate-top': scan_mediate_top, '--scan-mediator-file': scan_mediator_file,
              '--scan-effects': scan_effects or None, '--scan-effects-min-lod': scan_effects_min_lod,
              '--scan-lod-drop': scan_lod_drop, '--scan-kinship': scan_kinship, '--scan-kinship-out': scan_kinship_out or None,
-             '--scan-kinship-snps': scan_kinship_snps}
+             '--scan-kinship-snps': scan_kinship_snps, '--scan-kinship-effects': scan_kinship_effects or None,
+             '--scan-kinship-effects-min-lod': scan_kinship_effects_min_lod, '--scan-kinship-lod-drop': scan_kinship_lod_drop}
     perm_options(scan_perms, scan_perm_seed, scan_perm_alpha, scan_perm_chromosomes, scan_perm_pheno)
     mediate_options(scan_mediate, scan_mediate_min_lod, scan_mediate_top, scan_mediator_file)
     effects_options(scan_effects, scan_effects_min_lod, scan_lod_drop)
     kinship_options(scan_kinship, scan_kinship_out, scan_perms, scan_snps, scan_mediate, scan_effects, scan_lod_drop)
     kinship_snp_options(scan_kinship_snps, scan_kinship)
+    kinship_effects_options(scan_kinship_effects, scan_kinship_effects_min_lod, scan_kinship_lod_drop, scan_kinship)
     if scan_pheno is None:
         for name, value in given.items():
             if value is not None:
@@ -756,9 +826,10 @@ def write_scan(prefix, phenotypes, samples, covariates, chrom, pos, chrom_names,
     and `support_hi`): the .npz gains both and `lod_drop`, the peaks file the columns `support_lo` and `support_hi` - the
     positions of the interval's ends - after every other column.  kinship_mode (with `--scan-kinship`; result is
     GenomeScan.run_lmm's and rank is None): the .npz holds `hsq`, `sigma2`, `rank_min`, `rank_max` and `kinship_mode`
-    instead of `rank`, and the peaks file gains the column `hsq`, the heritability the chromosome was scanned with."""
+    instead of `rank`, and the peaks file gains the column `hsq`, the heritability the chromosome was scanned with; with
+    lod_drop (`--scan-kinship-lod-drop`) the support columns follow `hsq`."""
     if kinship_mode is not None:
-        write_scan_lmm(prefix, phenotypes, samples, covariates, chrom, pos, chrom_names, result, min_lod, kinship_mode)
+        write_scan_lmm(prefix, phenotypes, samples, covariates, chrom, pos, chrom_names, result, min_lod, kinship_mode, lod_drop)
         return
     arrays = dict(phenotypes=np.array(phenotypes), samples=np.array(samples), covariates=np.array(covariates),
                   chrom=np.array(chrom), pos=np.asarray(pos, dtype=np.float64), rank=np.asarray(rank),
@@ -788,25 +859,34 @@ def write_scan(prefix, phenotypes, samples, covariates, chrom, pos, chrom_names,
                               f'{int(c == top)}{ends(p, c)}\n')
 
 
-def write_scan_lmm(prefix, phenotypes, samples, covariates, chrom, pos, chrom_names, result, min_lod, kinship_mode):
-    """write_scan's two files for the mixed model."""
+def write_scan_lmm(prefix, phenotypes, samples, covariates, chrom, pos, chrom_names, result, min_lod, kinship_mode,
+                   lod_drop=None):
+    """write_scan's two files for the mixed model.  lod_drop (result then holds `support_lo` and `support_hi`): the .npz
+    gains both and `lod_drop`, the peaks file the columns `support_lo` and `support_hi` (positions) after `hsq`."""
     arrays = dict(phenotypes=np.array(phenotypes), samples=np.array(samples), covariates=np.array(covariates),
                   chrom=np.array(chrom), pos=np.asarray(pos, dtype=np.float64), peak_lod=result['peak_lod'],
                   peak_index=result['peak_index'], hsq=result['hsq'], sigma2=result['sigma2'], rank_min=result['rank_min'],
                   rank_max=result['rank_max'], kinship_mode=np.array(kinship_mode))
     if 'lod' in result:
         arrays['lod'] = result['lod']
+    if lod_drop is None:
+        ends, ends_header = lambda p, c: '', ''
+    else:
+        arrays.update(support_lo=result['support_lo'], support_hi=result['support_hi'], lod_drop=np.float64(lod_drop))
+        ends = lambda p, c: (f'\t{repr(float(pos[result["support_lo"][p, c]]))}'
+                             f'\t{repr(float(pos[result["support_hi"][p, c]]))}')
+        ends_header = '\tsupport_lo\tsupport_hi'
     np.savez(f'{prefix}.scan.npz', **arrays)
     peak, index, hsq = result['peak_lod'], result['peak_index'], result['hsq']
     with open(f'{prefix}.scan.peaks.tsv', 'w') as out:
-        out.write('#phenotype\tchromosome\tposition\tlod\tgenome_wide_max\thsq\n')
+        out.write(f'#phenotype\tchromosome\tposition\tlod\tgenome_wide_max\thsq{ends_header}\n')
         for p, name in enumerate(phenotypes):
             on = [c for c in range(len(chrom_names)) if index[p, c] >= 0]
             top = max(on, key=lambda c: (peak[p, c], -c)) if on else None
             for c in on:
                 if peak[p, c] >= min_lod:
                     out.write(f'{name}\t{chrom_names[c]}\t{repr(float(pos[index[p, c]]))}\t{repr(float(peak[p, c]))}\t'
-                              f'{int(c == top)}\t{repr(float(hsq[p, c]))}\n')
+                              f'{int(c == top)}\t{repr(float(hsq[p, c]))}{ends(p, c)}\n')
 
 
 def write_scan_kinship(prefix, samples, chrom_names, matrices, eig_of_chrom, kinship_mode):
@@ -1068,10 +1148,13 @@ def finish_scan_mediation(scan, prefix, ids, pheno, covariates, y, mediate, resu
         stage_times['mediate'] = stage_times.get('mediate', 0.0) + time.perf_counter() - t0
 
 
-def write_scan_effects(prefix, phenotypes, founders, samples, covariates, chrom_names, pos, targets, points, result, min_lod):
+def write_scan_effects(prefix, phenotypes, founders, samples, covariates, chrom_names, pos, targets, points, result, min_lod,
+                       kinship_mode=None):
     """`<prefix>.scan.effects.npz` and `<prefix>.scan.effects.tsv` from GenomeScan.effects' dict.  targets: [T, 2]
     (phenotype, chromosome) indices, points: [T] grid points, founders: the H labels.  One line per peak: phenotype,
-    chromosome, position, lod, rank, then effect_<founder> and se_<founder> per founder."""
+    chromosome, position, lod, rank, then effect_<founder> and se_<founder> per founder.  kinship_mode (with
+    `--scan-kinship-effects`; result is GenomeScan.effects_lmm's): the .npz gains `hsq` and `kinship_mode`, the table the
+    column `hsq` after `rank`."""
     targets = np.asarray(targets, dtype=np.int64).reshape(-1, 2)
     points = np.asarray(points, dtype=np.int64)
     founders = [str(f) for f in founders]
@@ -1081,12 +1164,16 @@ def write_scan_effects(prefix, phenotypes, founders, samples, covariates, chrom_
                   points=points, position=np.asarray(pos, dtype=np.float64)[points], min_lod=np.float64(min_lod))
     for key in ('effect', 'se', 'lod', 'sigma2', 'rank'):
         arrays[key] = result[key]
+    mixed = kinship_mode is not None
+    if mixed:
+        arrays.update(hsq=result['hsq'], kinship_mode=np.array(kinship_mode))
     np.savez(f'{prefix}.scan.effects.npz', **arrays)
     with open(f'{prefix}.scan.effects.tsv', 'w') as out:
-        out.write('#phenotype\tchromosome\tposition\tlod\trank' + ''.join(f'\teffect_{f}\tse_{f}' for f in founders) + '\n')
+        out.write('#phenotype\tchromosome\tposition\tlod\trank' + ('\thsq' if mixed else '') +
+                  ''.join(f'\teffect_{f}\tse_{f}' for f in founders) + '\n')
         for t, (p, c) in enumerate(targets):
             out.write(f'{phenotypes[p]}\t{chrom_names[c]}\t{repr(float(arrays["position"][t]))}\t{repr(float(result["lod"][t]))}\t'
-                      f'{int(result["rank"][t])}' +
+                      f'{int(result["rank"][t])}' + (f'\t{repr(float(result["hsq"][t]))}' if mixed else '') +
                       ''.join(f'\t{repr(float(e))}\t{repr(float(s))}' for e, s in zip(result['effect'][t], result['se'][t])) + '\n')
 
 
@@ -1113,9 +1200,34 @@ def finish_scan_effects(scan, prefix, ids, pheno, covariates, y, min_lod, result
         stage_times['effects'] = stage_times.get('effects', 0.0) + time.perf_counter() - t0
 
 
+def finish_scan_effects_lmm(scan, prefix, ids, pheno, covariates, y, min_lod, result, chrom_names, pos, kinship_mode,
+                            founders=None, stage_times=None):
+    """The effects pass under the mixed model `scan` holds and its two files.  y: the phenotypes as the
+    scan saw them; result: GenomeScan.run_lmm's dict, whose peaks of at least min_lod are the targets
+    (mediation_targets) and whose heritabilities the pass is given.  Its wall-clock seconds go to stage_times['effects']."""
+    import time
+    t0 = time.perf_counter()
+    targets = mediation_targets(result['peak_lod'], result['peak_index'], min_lod)
+    points = result['peak_index'][targets[:, 0], targets[:, 1]]
+    T, H = len(targets), scan.H
+    if T:
+        got = scan.effects_lmm(y, targets[:, 0], points, hsq=result['hsq'])
+        timing = scan.lmm_effects_info()
+        logger.info(f'scan: founder effects under the mixed model at {T} peaks of {timing["columns"]} phenotypes; '
+                    f'{timing["pass_ms"]:.1f} ms on the device, {timing["null_ms"]:.1f} ms of them in the null fits')
+    else:
+        logger.warning(f'scan: no peak reaches a LOD of {min_lod}: no founder effects')
+        got = {'effect': np.zeros((0, H)), 'se': np.zeros((0, H)), 'lod': np.zeros(0), 'sigma2': np.zeros(0),
+               'hsq': np.zeros(0), 'rank': np.zeros(0, dtype=np.int32)}
+    write_scan_effects(prefix, pheno[0], list(range(H)) if founders is None else founders, ids, covariates,
+                       [str(c) for c in chrom_names], pos, targets, points, got, min_lod, kinship_mode=kinship_mode)
+    if stage_times is not None:
+        stage_times['effects'] = stage_times.get('effects', 0.0) + time.perf_counter() - t0
+
+
 def finish_scan(scan, prefix, ids, pheno, covar, use_rankz, chrom, pos, chrom_names, min_lod=None, lod_matrix=False,
                 perm=None, stage_times=None, snps=None, snp_grid=None, mediate=None, effects=None, founders=None, kinship=None,
-                kinship_snps=None):
+                kinship_snps=None, kinship_effects=None):
     """prepare + run + the two files for the cohort `scan` holds, whose samples are `ids` in append order (every one with
     its rows in the tables).  perm: perm_options' dict, or None; with it the permutation pass runs after the scan on the
     phenotypes and chromosomes it names and its wall-clock seconds go to stage_times['scan_perm'].  mediate:
@@ -1124,19 +1236,26 @@ def finish_scan(scan, prefix, ids, pheno, covar, use_rankz, chrom, pos, chrom_na
     the founder effects of the peaks follow (finish_scan_effects), named by `founders`.
     kinship: kinship_options' dict, or None; with it the scan is the mixed model's and none of the other
     passes runs, except that of kinship_snps (read_snp_file's dict of `--scan-kinship-snps`, or None): the SNP association
-    under the same mixed model, at the heritabilities the scan fitted.  Returns GenomeScan.info() after the run."""
+    under the same mixed model, at the heritabilities the scan fitted, and those of kinship_effects
+    (kinship_effects_options' dict, or None): its lod_drop makes the run form the support intervals, its min_lod makes the
+    founder effects of the peaks follow under the same mixed model and heritabilities.  Returns GenomeScan.info() after the run."""
     kept, y, z, names = scan_design(ids, pheno, covar, use_rankz)
     assert len(kept) == len(ids) == scan.n
     if kinship is not None:
         matrices = scan.prepare_lmm(z, kinship['mode'], names)
-        result = scan.run_lmm(y, want_lod=bool(lod_matrix) or y.shape[1] * scan.M <= LOD_MATRIX_LIMIT)
+        lod_drop = kinship_effects['lod_drop'] if kinship_effects is not None else None
+        want_lod = bool(lod_matrix) or y.shape[1] * scan.M <= LOD_MATRIX_LIMIT
+        result = scan.run_lmm(y, want_lod=want_lod, lod_drop=lod_drop)
         write_scan(prefix, pheno[0], ids, names, chrom, pos, chrom_names, result, None, 0.0 if min_lod is None else min_lod,
-                   kinship_mode=kinship['mode'])
+                   lod_drop=lod_drop, kinship_mode=kinship['mode'])
         if kinship['out']:
             write_scan_kinship(prefix, ids, chrom_names, matrices, scan.eig_of_chrom, kinship['mode'])
         if kinship_snps is not None:        # read_snp_file's dict: the SNP pass under the same kinship and heritabilities
             finish_scan_snps_lmm(scan, prefix, ids, pheno[0], names, y, kinship_snps, chrom_names, snp_grid, result['hsq'],
                                  kinship['mode'], min_lod, lod_matrix, stage_times)
+        if kinship_effects is not None and kinship_effects['min_lod'] is not None:
+            finish_scan_effects_lmm(scan, prefix, ids, pheno, names, y, kinship_effects['min_lod'], result, chrom_names, pos,
+                                    kinship['mode'], founders, stage_times)
         timing = scan.lmm_info()
         logger.info(f'scan: {len(ids)} samples, {y.shape[1]} phenotypes, {scan.M} grid points under the mixed model '
                     f'({kinship["mode"]} kinship); kinship {timing["kinship_ms"]:.1f} ms, rotation {timing["rotate_ms"]:.1f} ms, '
@@ -1179,7 +1298,8 @@ def scan_tables(dosage_list, grid_file, pheno_file, covar_file=None, use_rankz=F
                 lod_matrix=False, device=0, scan_perms=None, scan_perm_seed=None, scan_perm_alpha=None,
                 scan_perm_chromosomes=None, scan_perm_pheno=None, stage_times=None, snp_file=None, scan_mediate=False,
                 scan_mediate_min_lod=None, scan_mediate_top=None, scan_mediator_file=None, scan_effects=False,
-                scan_effects_min_lod=None, scan_lod_drop=None, scan_kinship=None, scan_kinship_out=False, scan_kinship_snps=None):
+                scan_effects_min_lod=None, scan_lod_drop=None, scan_kinship=None, scan_kinship_out=False, scan_kinship_snps=None,
+                scan_kinship_effects=False, scan_kinship_effects_min_lod=None, scan_kinship_lod_drop=None):
     """`gbrs scan`: the cohort from dosage tables in `gbrs export` format (lines `id<TAB>dosage table`), rows in the grid
     file's order, without the HMM.  snp_file (`--snp-file`): the SNP association pass follows the scan (DESIGN.md §29);
     the haplotypes of the patterns are those of the dosage tables' header.  scan_mediate (`--scan-mediate`): the scan's
@@ -1187,7 +1307,9 @@ def scan_tables(dosage_list, grid_file, pheno_file, covar_file=None, use_rankz=F
     (`--scan-effects`) and scan_lod_drop (`--scan-lod-drop`): the peaks' founder effects, named by the dosage tables'
     header, and their LOD support intervals.  scan_kinship (`--scan-kinship loco|overall`): the scan is the
     linear mixed model's; scan_kinship_out writes the kinship matrices; scan_kinship_snps
-    (`--scan-kinship-snps FILE`): the SNP association pass under the mixed model follows the scan."""
+    (`--scan-kinship-snps FILE`): the SNP association pass under the mixed model follows the scan (DESIGN.md §33);
+    scan_kinship_effects, scan_kinship_effects_min_lod and scan_kinship_lod_drop: the peaks' founder effects and support
+    intervals under the mixed model."""
     from .hmm import _match_lines, read_dosage_table, read_snp_file
     from .postproc import read_grid
     if min_lod is not None and not min_lod >= 0.0:
@@ -1198,6 +1320,8 @@ def scan_tables(dosage_list, grid_file, pheno_file, covar_file=None, use_rankz=F
     kinship = kinship_options(scan_kinship, scan_kinship_out, scan_perms, snp_file is not None, scan_mediate, scan_effects,
                               scan_lod_drop)
     kinship_snp_options(scan_kinship_snps, scan_kinship)
+    kinship_effects = kinship_effects_options(scan_kinship_effects, scan_kinship_effects_min_lod, scan_kinship_lod_drop,
+                                              scan_kinship)
     grid = read_grid(grid_file)
     chrom_names = list(grid)
     points = [len(grid[c]) for c in chrom_names]
@@ -1229,6 +1353,6 @@ def scan_tables(dosage_list, grid_file, pheno_file, covar_file=None, use_rankz=F
         return finish_scan(scan, out if out is not None else 'gbrs', [entries[k][0] for k in kept], pheno, covar, use_rankz,
                            chrom, pos, chrom_names, min_lod, lod_matrix, perm=perm, stage_times=stage_times, snps=snps,
                            snp_grid=grid, mediate=mediate, effects=effects, founders=haplotypes, kinship=kinship,
-                           kinship_snps=kinship_snps)
+                           kinship_snps=kinship_snps, kinship_effects=kinship_effects)
     finally:
         scan.close()

@@ -1225,9 +1225,9 @@ int gbrs_scan_lmm_prepare(gbrs_scan_t *scan, int cz, const double *Z /* [n][cz] 
  * same bits alone or among others, at any column, in any chunk, and however the cohort was appended.  GBRS_ERR_INVALID
  * before gbrs_scan_lmm_prepare, for P < 1, for a phenotype value that is not finite (the message names the entry) and
  * for a value of hsq_in outside [0, 1]; the outputs are untouched on such a failure.  The call allocates and frees its
- * own buffers: what the handle holds, gbrs_scan_run's bits and gbrs_scan_info_t are as before.  No permutations,
- * mediation, effects or support intervals under the mixed model, REML only, additive covariates only; the SNP tests
- * under the mixed model are gbrs_scan_lmm_snps. */
+ * own buffers: what the handle holds, gbrs_scan_run's bits and gbrs_scan_info_t are as before.  No permutations or
+ * mediation under the mixed model, REML only, additive covariates only; the SNP tests under the mixed model are
+ * gbrs_scan_lmm_snps, the founder effects gbrs_scan_lmm_effects and the support intervals gbrs_scan_lmm_run_support. */
 int gbrs_scan_lmm_run(gbrs_scan_t *scan, int64_t P, const double *pheno, const double *hsq_in /* [P][n_eig], nullable */,
                       double *lod, double *peak_lod, int64_t *peak_index, double *hsq /* [P][n_eig] */, double *sigma2);
 
@@ -1290,6 +1290,64 @@ typedef struct gbrs_scan_lmm_snp_info {
     uint64_t peak_device_bytes;  /* what the handle held during the pass, the call's own buffers included        */
 } gbrs_scan_lmm_snp_info_t;
 int gbrs_scan_lmm_snp_info(gbrs_scan_t *scan, gbrs_scan_lmm_snp_info_t *info);
+
+/* Founder effects at QTL peaks under the mixed model (R/qtl2's scan1coef with kinship = loco at chosen
+ * points): gbrs_scan_effects' answer with the polygenic effect of gbrs_scan_lmm_prepare.  For target t - the phenotype
+ * column y = column[t] in [0, P) and the grid point m = point[t] in [0, M) -, with e the decomposition of m's chromosome
+ * and h the heritability of (y, e), fitted by gbrs_scan_lmm_run's search or given in hsq_in.  No fused multiply-add.
+ *   sw, Qz, y~, rss0     what gbrs_scan_lmm_run's null fit leaves for (y, e): w = v^-1/2, Z^ after Gram-Schmidt, the projected y^
+ *   X^_j = sw . R_m[j],  j < H-1;   raw_j = |X^_j|^2;   X~_j = X^_j - Qz Qz' X^_j
+ *   G = X~' X~,  b = X~' y~
+ *   L, S, r              Cholesky of G with gbrs_scan_prepare's skip rule, both lines of it; S the kept columns, r their number
+ *   a = L_S^-1 b_S,      ess = |a|^2
+ *   R = L_S^-1 G[S, 0:H-1]   (r x (H-1));   R[:, H-1] = -sum_{j<H-1} R[:, j], j ascending        -> r x H
+ *   C = R R'             r x r, symmetric positive definite: a plain Cholesky, no skip rule
+ *   effect = R' C^-1 a
+ *   rss1 = max(rss0 - ess, 0)     sigma2 = rss1 / (n - cz - r)     se[h] = sqrt(sigma2) |C^-1 R[:, h]|
+ *   lod = (n / 2) log10(rss0 / (rss0 - ess)) with gbrs_scan_run's two edge rules
+ * The last column is gbrs_scan_effects' definition carried over: the projected weighted column of founder H-1 is minus the
+ * sum of the others.  The rotated, weighted constant lies in the span of Qz, so this is what the sum constraint of the
+ * dosages implies, and it keeps the rule defined where a row does not add up.  effect is the minimum-norm generalised
+ * least-squares solution over all H founder columns (zero-sum at full rank); a founder j < H-1 without dosage at m gets
+ * exactly 0.0 with se 0.0; founders with identical dosages get identical bits; with r = 0 every effect, se and the LOD are
+ * 0.0 and sigma2 stays the null model's, rss0 / (n - cz), as the formula gives it; a column of zeros gives hsq 0, effects 0.0 and lod 0.0.  sigma2 is the residual variance on the whitened scale, the
+ * s2 of gbrs_scan_lmm_run's model.  The sums over the samples are gbrs_scan_lmm_run's in its order, so lod[t] carries the
+ * bits of its lod[column[t]][point[t]] when both are called the same way (both fitted, or both given the same hsq_in), and
+ * hsq[t] the bits of its hsq[column[t]][e].
+ * pheno is double[n][P], centred as for gbrs_scan_lmm_run; hsq_in double[P][n_eig] or NULL; effect and se double[T][H], lod,
+ * sigma2 and hsq double[T], rank int32[T] (the kept columns r); every output nullable.  The columns that some target names
+ * are compacted on the host and pass in chunks of 512 through gbrs_scan_lmm_run's rotation and null fits - every
+ * decomposition of a used column -; a chunk's targets follow in chunks of 512, one workgroup each.  A target's numbers are
+ * the same bits alone or among others, at any place in the list, in any chunk, for any P and any position of its column,
+ * given twice, and however the cohort was appended.  GBRS_ERR_INVALID before gbrs_scan_lmm_prepare, for P < 1 or T < 0, for
+ * a column outside [0, P) or a point outside [0, M), for a phenotype value that is not finite (the message names the entry)
+ * and for a value of hsq_in outside [0, 1]; the outputs are untouched and the handle is as it was.  T = 0 is GBRS_OK and
+ * writes nothing.  The call allocates and frees its own buffers: gbrs_scan_run, gbrs_scan_lmm_run and gbrs_scan_lmm_snps
+ * give the same bits before and after it.  No BLUP shrinkage, no effects at SNPs, no Bayes credible interval. */
+int gbrs_scan_lmm_effects(gbrs_scan_t *scan, int64_t P, const double *pheno /* [n][P] */,
+                          const double *hsq_in /* [P][n_eig], nullable */, int64_t T, const int64_t *column /* [T], in [0,P) */,
+                          const int64_t *point /* [T], in [0,M) */, double *effect /* [T][H] */, double *se /* [T][H] */,
+                          double *lod /* [T] */, double *sigma2 /* [T] */, int32_t *rank /* [T] */, double *hsq /* [T] */);
+
+typedef struct gbrs_scan_lmm_effects_info {
+    int64_t  T, P;               /* of the last gbrs_scan_lmm_effects with T > 0 (0: none yet)                   */
+    int64_t  columns;            /* the distinct phenotype columns its targets named: the columns that were fitted */
+    double   last_pass_ms;       /* device time of the pass: uploads, all kernels, copies                        */
+    double   last_null_ms;       /* its null fits: phenotype rotations and REML, over the column chunks          */
+    double   last_target_ms;     /* its target chunks: uploads, the effects kernel, copies                       */
+    uint64_t peak_device_bytes;  /* what the handle held during the pass, the call's own buffers included        */
+} gbrs_scan_lmm_effects_info_t;
+int gbrs_scan_lmm_effects_info(gbrs_scan_t *scan, gbrs_scan_lmm_effects_info_t *info);
+
+/* gbrs_scan_lmm_run with LOD support intervals (R/qtl2's lod_int on a scan with kinship): the pass of
+ * gbrs_scan_lmm_run - the same kernels, the same bits in lod, peak_lod, peak_index, hsq, sigma2 and gbrs_scan_lmm_ranks -
+ * and gbrs_scan_run_support's kernel after the peaks on each chunk's LOD rows while they are on the device.  support_lo
+ * and support_hi are int64[P][n_chrom] by gbrs_scan_run_support's rule, nullable, -1 for a chromosome without points.
+ * GBRS_ERR_INVALID for a drop that is negative or not finite; the other refusals are gbrs_scan_lmm_run's, and the outputs
+ * are untouched on failure.  The two tables of a chunk are the call's own. */
+int gbrs_scan_lmm_run_support(gbrs_scan_t *scan, int64_t P, const double *pheno, const double *hsq_in /* nullable */, double drop,
+                              double *lod, double *peak_lod, int64_t *peak_index, double *hsq, double *sigma2,
+                              int64_t *support_lo, int64_t *support_hi /* [P][n_chrom] */);
 
 /* ------------------------------------------------------------------------------------------
  * Report text (host side, no device work): the `locus <haplotypes> total [notes]` tables of

@@ -43,6 +43,7 @@ EXPORTS = [
     "gbrs_scan_kinship", "gbrs_scan_lmm_prepare", "gbrs_scan_lmm_run", "gbrs_scan_lmm_ranks", "gbrs_scan_lmm_info",
     "gbrs_scan_lmm_snps", "gbrs_scan_lmm_snp_info",
     "gbrs_scan_lmm_effects", "gbrs_scan_lmm_effects_info", "gbrs_scan_lmm_run_support",
+    "gbrs_scan_int_prepare", "gbrs_scan_int_run", "gbrs_scan_int_info",
     "gbrs_compress_create", "gbrs_compress_get", "gbrs_compress_destroy",
     "gbrs_bam_open", "gbrs_bam_references", "gbrs_bam_set_reference_map", "gbrs_bam_convert", "gbrs_bam_get",
     "gbrs_bam_scan_records", "gbrs_bam_destroy",
@@ -165,6 +166,14 @@ class ScanLmmEffectsInfo(C.Structure):
     _fields_ = [
         ("T", C.c_int64), ("P", C.c_int64), ("columns", C.c_int64), ("last_pass_ms", C.c_double),
         ("last_null_ms", C.c_double), ("last_target_ms", C.c_double), ("peak_device_bytes", C.c_uint64),
+    ]
+
+
+class ScanIntInfo(C.Structure):
+    _fields_ = [
+        ("n", C.c_int64), ("M", C.c_int64), ("H", C.c_int32), ("c", C.c_int32), ("k", C.c_int32), ("HPI", C.c_int32),
+        ("last_prepare_ms", C.c_double), ("last_run_ms", C.c_double), ("last_product_ms", C.c_double),
+        ("device_bytes", C.c_uint64),
     ]
 
 
@@ -298,6 +307,9 @@ def load():
         "gbrs_scan_lmm_effects": [vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp],
         "gbrs_scan_lmm_effects_info": [vp, C.POINTER(ScanLmmEffectsInfo)],
         "gbrs_scan_lmm_run_support": [vp, i64, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp, vp],
+        "gbrs_scan_int_prepare": [vp, i32, vp, i32, vp],
+        "gbrs_scan_int_run": [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "gbrs_scan_int_info": [vp, C.POINTER(ScanIntInfo), vp, vp],
         "gbrs_compress_create": [u64, u32, u32, pp, pp, vp, i32, pp, C.POINTER(u64), vp],
         "gbrs_compress_get": [vp, pp, pp, vp],
         "gbrs_compress_destroy": [vp],

@@ -362,6 +362,12 @@ def _scan_options(parser, covar=True):
                         help='with --scan-kinship: LOD support intervals of the mixed model\'s peaks on the device, by '
                              '--scan-lod-drop\'s rule.  <PREFIX>.scan.npz gains support_lo, support_hi and lod_drop, the peaks '
                              'file the columns support_lo and support_hi after hsq')
+    parser.add_argument('--scan-intcovar', default=None, metavar='NAME[,NAME...]',
+                        help='with --scan-covar: interactive covariates on the device (QTL x covariate, as R/qtl2\'s intcovar).  '
+                             'The named columns of the covariate table also multiply the founder dosages; after the scan a '
+                             'second one gives the LOD of the full model, of the additive model and of the interaction at '
+                             'every grid point.  Writes <PREFIX>.scan.int.npz and <PREFIX>.scan.int.peaks.tsv; the other '
+                             'files are what they are without it.  Not with --scan-kinship')
 
 
 def main(argv=None) -> int:
@@ -494,7 +500,7 @@ def main(argv=None) -> int:
                         scan_kinship=args.scan_kinship, scan_kinship_out=args.scan_kinship_out,
                         scan_kinship_snps=args.scan_kinship_snps, scan_kinship_effects=args.scan_kinship_effects,
                         scan_kinship_effects_min_lod=args.scan_kinship_effects_min_lod,
-                        scan_kinship_lod_drop=args.scan_kinship_lod_drop)
+                        scan_kinship_lod_drop=args.scan_kinship_lod_drop, scan_intcovar=args.scan_intcovar)
         elif args.command == 'interpolate':
             from .postproc import interpolate
             interpolate(genoprob_file=args.genoprob_file, grid_file=args.grid_file, gpos_file=args.gpos_file,

@@ -22,6 +22,9 @@
 // (grid point, phenotype) pair's explained sum of squares without a W.  SNP association under the mixed model (DESIGN.md §33;
 // kernels and the rule in scan_lmm_snp.inc): the SNP dosages of §29 rotated as the cohort is, and a sibling of the SNP product
 // kernel that multiplies them with the weighted columns of every phenotype's null fit and applies the test in its epilogue.
+// Interactive covariates (kernels and the rule in scan_int.inc): a preparation of its own that factors a point's
+// additive columns and then their products with the interactive covariates, and a sibling of the product kernel whose
+// epilogue gives the LODs of the full model, of the additive model and of the interaction from one product.
 #include "common.h"
 #include "scan_hmm.h"
 
@@ -345,6 +348,10 @@ scan_peak_kernel(int64_t M, int n_chrom, const int64_t *__restrict__ point_off, 
 
 #include "scan_lmm_effects.inc"
 
+// ---- interactive covariates ----------------------------------------------------------------------------------------------------
+
+#include "scan_int.inc"
+
 }  // namespace gbrs
 
 using namespace gbrs;
@@ -419,6 +426,15 @@ struct gbrs_scan {
     int64_t leff_T = 0, leff_P = 0, leff_columns = 0;
     double t_leff_pass = 0, t_leff_null = 0, t_leff_target = 0;
     uint64_t leff_peak_bytes = 0;
+    // what gbrs_scan_int_prepare made (int_c 0: not prepared): its own qz, the interactive covariates and the W of §35,
+    // [M * int_hpi][int_n_ld]; the ranks are [2][M] on the device, full then additive
+    int int_c = 0, int_k = 0, int_hpi = 0;
+    int64_t int_n_ld = 0;
+    DevBuf<double> int_qz, int_zint, int_W;
+    DevBuf<int32_t> int_d_rank;
+    std::vector<int32_t> int_rank_full, int_rank_add;
+    double t_int_prepare = 0, t_int_run = 0, t_int_product = 0;
+    uint64_t int_bytes() const { return int_qz.bytes() + int_zint.bytes() + int_W.bytes() + int_d_rank.bytes(); }
     uint64_t lmm_bytes() const {
         return lmm_U.bytes() + lmm_lam.bytes() + lmm_Zs.bytes() + lmm_R.bytes() + lmm_eig_of_point.bytes();
     }
@@ -456,6 +472,16 @@ void scan_lmm_unprepare(gbrs_scan *s) {
     s->lmm_n_eig = 0;
     s->kin_valid = false;
     s->kin_S.release();
+}
+
+// An append drops what gbrs_scan_int_prepare made, its W included.
+void scan_int_unprepare(gbrs_scan *s) {
+    s->int_c = 0;
+    s->int_k = 0;
+    s->int_hpi = 0;
+    s->int_rank_full.clear();
+    s->int_rank_add.clear();
+    s->int_W.release();
 }
 
 // Pairs of events around the product kernel of consecutive chunks, so that a pass times it without waiting per chunk: a
@@ -562,6 +588,7 @@ int gbrs_scan_append(gbrs_scan_t *s, int n, const double *dosage) {
     s->n += n;
     scan_unprepare(s);
     scan_lmm_unprepare(s);
+    scan_int_unprepare(s);
     return GBRS_OK;
 }
 
@@ -588,6 +615,7 @@ int gbrs_scan_append_hmm(gbrs_scan_t *s, gbrs_hmm_t *hmm, int sample) {
     s->n += view.n;
     scan_unprepare(s);
     scan_lmm_unprepare(s);
+    scan_int_unprepare(s);
     return GBRS_OK;
 }
 
@@ -1985,6 +2013,174 @@ int gbrs_scan_lmm_snp_info(gbrs_scan_t *s, gbrs_scan_lmm_snp_info_t *info) {
     info->last_product_ms = s->t_lsnp_product;
     info->column_bytes = s->lsnp_column_bytes;
     info->peak_device_bytes = s->lsnp_peak_bytes;
+    return GBRS_OK;
+}
+
+}  // extern "C"
+
+// ---- interactive covariates ------------------------------------------------------------------------------------
+
+extern "C" {
+
+int gbrs_scan_int_prepare(gbrs_scan_t *s, int c, const double *qz, int k, const double *zint) {
+    RoctxRange roctx_range("gbrs_scan_int_prepare");
+    if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (k < 1) return fail(GBRS_ERR_INVALID, "interactive covariates must be at least 1, got %d", k);
+    if (c < 1 || c > SC_MAX_C) return fail(GBRS_ERR_INVALID, "covariate columns must be 1..%d (the intercept included), got %d", SC_MAX_C, c);
+    if (!qz || !zint) return fail(GBRS_ERR_INVALID, "qz or zint is NULL");
+    const int Hx = s->H - 1;
+    if (s->Hp + (int64_t)k * Hx > 64)
+        return fail(GBRS_ERR_UNSUPPORTED, "%d interactive covariates of %d founders need %lld rows per grid point, more than 64", k, s->H,
+                    (long long)(s->Hp + (int64_t)k * Hx));
+    const int columns = Hx * (1 + k), hpi = s->Hp + k * Hx <= 16 ? 16 : s->Hp + k * Hx <= 32 ? 32 : 64;
+    if (s->n <= (int64_t)c + columns)
+        return fail(GBRS_ERR_INVALID, "%lld samples are too few for %d covariate columns and %d founders with %d interactive covariates: "
+                    "need more than %d", (long long)s->n, c, s->H, k, c + columns);
+    const int n = (int)s->n;
+    for (int64_t q = 0; q < (int64_t)n * c; ++q)
+        if (!std::isfinite(qz[q]))
+            return fail(GBRS_ERR_INVALID, "covariate basis holds a value that is not finite (sample %lld, column %d)", (long long)(q / c),
+                        (int)(q % c));
+    for (int64_t q = 0; q < (int64_t)n * k; ++q)
+        if (!std::isfinite(zint[q]))
+            return fail(GBRS_ERR_INVALID, "interactive covariate %d holds a value that is not finite (sample %lld)", (int)(q % k),
+                        (long long)(q / k));
+    GBRS_TRY(select_device(s->device));
+    scan_int_unprepare(s);              // the arguments are good: from here on the preparation is being overwritten
+    const int64_t n_ld = ((int64_t)n + SC_KC - 1) / SC_KC * SC_KC, M = s->M;
+    GBRS_TRY(s->int_qz.alloc((size_t)n * c));
+    GBRS_TRY(s->int_zint.alloc((size_t)n * k));
+    GBRS_TRY(s->int_W.alloc((size_t)M * hpi * n_ld));
+    if (s->int_d_rank.n != (size_t)2 * M) GBRS_TRY(s->int_d_rank.alloc((size_t)2 * M));
+    GBRS_HIP_CHECK(hipMemcpy(s->int_qz.p, qz, s->int_qz.bytes(), hipMemcpyHostToDevice));
+    GBRS_HIP_CHECK(hipMemcpy(s->int_zint.p, zint, s->int_zint.bytes(), hipMemcpyHostToDevice));
+    GBRS_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)M), dim3(SC_THREADS), 0, s->stream, n, M, s->H, s->Hp, c, k, n_ld, s->dosage.p,
+                           s->int_qz.p, s->int_zint.p, s->int_W.p, s->int_d_rank.p, s->int_d_rank.p + M);
+    };
+    if (hpi == 16) launch(scan_int_prepare_kernel<16>);
+    else if (hpi == 32) launch(scan_int_prepare_kernel<32>);
+    else launch(scan_int_prepare_kernel<64>);
+    GBRS_HIP_CHECK(hipEventRecord(s->ev[1], s->stream));
+    GBRS_HIP_CHECK(hipGetLastError());
+    GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) s->t_int_prepare = ms;
+    std::vector<int32_t> rank((size_t)2 * M);
+    GBRS_HIP_CHECK(hipMemcpy(rank.data(), s->int_d_rank.p, s->int_d_rank.bytes(), hipMemcpyDeviceToHost));
+    s->int_rank_full.assign(rank.begin(), rank.begin() + M);
+    s->int_rank_add.assign(rank.begin() + M, rank.end());
+    s->int_n_ld = n_ld;
+    s->int_k = k;
+    s->int_hpi = hpi;
+    s->int_c = c;
+    return GBRS_OK;
+}
+
+int gbrs_scan_int_run(gbrs_scan_t *s, int64_t P, const double *pheno, double *lod_full, double *lod_add, double *lod_int,
+                      double *peak_full, int64_t *peak_full_index, double *peak_full_add, double *peak_int, int64_t *peak_int_index) {
+    RoctxRange roctx_range("gbrs_scan_int_run");
+    if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (s->int_c == 0) return fail(GBRS_ERR_INVALID, "no interactive covariates on the handle: call gbrs_scan_int_prepare first");
+    if (P < 1 || !pheno) return fail(GBRS_ERR_INVALID, "bad argument");
+    const int n = (int)s->n, nc = s->n_chrom;
+    for (int64_t q = 0; q < (int64_t)n * P; ++q)
+        if (!std::isfinite(pheno[q]))
+            return fail(GBRS_ERR_INVALID, "phenotype %lld holds a value that is not finite (sample %lld)", (long long)(q % P),
+                        (long long)(q / P));
+    GBRS_TRY(select_device(s->device));
+    const int64_t pc_max = std::min(P, SC_PCHUNK), M = s->M, n_ld = s->int_n_ld;
+    // which of the three LOD rows a chunk needs on the device: an output's own, and those its peaks are taken from
+    const bool need_full = lod_full || peak_full || peak_full_index || peak_full_add, need_add = lod_add || peak_full_add,
+               need_int = lod_int || peak_int || peak_int_index;
+    DevBuf<double> y, yt, rss0, d_full, d_add, d_int, d_peak, d_peak_add;      // the call's own, as gbrs_scan_permute's
+    DevBuf<int64_t> d_index;
+    GBRS_TRY(y.alloc((size_t)n * pc_max));
+    GBRS_TRY(yt.alloc((size_t)pc_max * n_ld));
+    GBRS_TRY(rss0.alloc((size_t)pc_max));
+    if (need_full) GBRS_TRY(d_full.alloc((size_t)pc_max * M));
+    if (need_add) GBRS_TRY(d_add.alloc((size_t)pc_max * M));
+    if (need_int) GBRS_TRY(d_int.alloc((size_t)pc_max * M));
+    GBRS_TRY(d_peak.alloc((size_t)pc_max * nc));
+    GBRS_TRY(d_peak_add.alloc((size_t)pc_max * nc));
+    GBRS_TRY(d_index.alloc((size_t)pc_max * nc));
+    const unsigned row_blocks = (unsigned)((M * s->int_hpi + SC_ROWS - 1) / SC_ROWS);
+    double t_product = 0.0;
+    GBRS_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
+    for (int64_t p0 = 0; p0 < P; p0 += SC_PCHUNK) {
+        const int64_t pc = std::min(SC_PCHUNK, P - p0);
+        const size_t peaks = (size_t)pc * nc;
+        GBRS_HIP_CHECK(hipMemcpy2DAsync(y.p, (size_t)pc * sizeof(double), pheno + p0, (size_t)P * sizeof(double),
+                                        (size_t)pc * sizeof(double), (size_t)n, hipMemcpyHostToDevice, s->stream));
+        hipLaunchKernelGGL(scan_pheno_kernel, dim3((unsigned)pc), dim3(64), 0, s->stream, n, s->int_c, n_ld, pc, y.p, s->int_qz.p, yt.p,
+                           rss0.p);
+        GBRS_HIP_CHECK(hipEventRecord(s->ev[2], s->stream));
+        const dim3 grid(row_blocks, (unsigned)((pc + SC_COLS - 1) / SC_COLS));
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, dim3(SC_THREADS), 0, s->stream, M, pc, n_ld, s->Hp, 0.5 * n, s->int_W.p, yt.p, rss0.p,
+                               d_full.p, d_add.p, d_int.p);
+        };
+        if (s->int_hpi == 16) launch(scan_int_lod_kernel<16>);
+        else if (s->int_hpi == 32) launch(scan_int_lod_kernel<32>);
+        else launch(scan_int_lod_kernel<64>);
+        GBRS_HIP_CHECK(hipEventRecord(s->ev[3], s->stream));
+        GBRS_HIP_CHECK(hipGetLastError());
+        // the full model's peaks, lod_add at them, then the interaction's peaks through the same two tables
+        if (need_full) {
+            hipLaunchKernelGGL(scan_peak_kernel, dim3((unsigned)nc, (unsigned)pc), dim3(64), 0, s->stream, M, nc, s->d_point_off.p,
+                               d_full.p, d_peak.p, d_index.p);
+            if (peak_full_add)
+                hipLaunchKernelGGL(scan_int_peak_add_kernel, dim3((unsigned)((peaks + 63) / 64)), dim3(64), 0, s->stream, M,
+                                   (int64_t)peaks, nc, d_index.p, d_add.p, d_peak_add.p);
+            GBRS_HIP_CHECK(hipGetLastError());
+            GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
+            if (lod_full) GBRS_HIP_CHECK(hipMemcpy(lod_full + p0 * M, d_full.p, (size_t)pc * M * sizeof(double), hipMemcpyDeviceToHost));
+            if (peak_full) GBRS_HIP_CHECK(hipMemcpy(peak_full + p0 * nc, d_peak.p, peaks * sizeof(double), hipMemcpyDeviceToHost));
+            if (peak_full_index)
+                GBRS_HIP_CHECK(hipMemcpy(peak_full_index + p0 * nc, d_index.p, peaks * sizeof(int64_t), hipMemcpyDeviceToHost));
+            if (peak_full_add)
+                GBRS_HIP_CHECK(hipMemcpy(peak_full_add + p0 * nc, d_peak_add.p, peaks * sizeof(double), hipMemcpyDeviceToHost));
+        }
+        if (need_int) {
+            hipLaunchKernelGGL(scan_peak_kernel, dim3((unsigned)nc, (unsigned)pc), dim3(64), 0, s->stream, M, nc, s->d_point_off.p,
+                               d_int.p, d_peak.p, d_index.p);
+            GBRS_HIP_CHECK(hipGetLastError());
+            GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
+            if (lod_int) GBRS_HIP_CHECK(hipMemcpy(lod_int + p0 * M, d_int.p, (size_t)pc * M * sizeof(double), hipMemcpyDeviceToHost));
+            if (peak_int) GBRS_HIP_CHECK(hipMemcpy(peak_int + p0 * nc, d_peak.p, peaks * sizeof(double), hipMemcpyDeviceToHost));
+            if (peak_int_index)
+                GBRS_HIP_CHECK(hipMemcpy(peak_int_index + p0 * nc, d_index.p, peaks * sizeof(int64_t), hipMemcpyDeviceToHost));
+        }
+        GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
+        if (lod_add) GBRS_HIP_CHECK(hipMemcpy(lod_add + p0 * M, d_add.p, (size_t)pc * M * sizeof(double), hipMemcpyDeviceToHost));
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, s->ev[2], s->ev[3]) == hipSuccess) t_product += ms;
+    }
+    GBRS_HIP_CHECK(hipEventRecord(s->ev[1], s->stream));
+    GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) s->t_int_run = ms;
+    s->t_int_product = t_product;
+    return GBRS_OK;
+}
+
+int gbrs_scan_int_info(gbrs_scan_t *s, gbrs_scan_int_info_t *info, int32_t *rank_full, int32_t *rank_add) {
+    if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    if (info) {
+        info->n = s->n;
+        info->M = s->M;
+        info->H = s->H;
+        info->c = s->int_c;
+        info->k = s->int_k;
+        info->HPI = s->int_hpi;
+        info->last_prepare_ms = s->t_int_prepare;
+        info->last_run_ms = s->t_int_run;
+        info->last_product_ms = s->t_int_product;
+        info->device_bytes = s->int_c > 0 ? s->int_bytes() : 0;
+    }
+    if (rank_full && s->int_c > 0) std::memcpy(rank_full, s->int_rank_full.data(), s->int_rank_full.size() * sizeof(int32_t));
+    if (rank_add && s->int_c > 0) std::memcpy(rank_add, s->int_rank_add.data(), s->int_rank_add.size() * sizeof(int32_t));
     return GBRS_OK;
 }
 

@@ -1409,7 +1409,9 @@ class ReconstructOptions:
     `scan_kinship_snps` (needs `scan_kinship`): a SNP file in `snp_file`'s format whose SNPs are tested
     with one degree of freedom under the same mixed model after the scan, at the heritabilities it fitted.
     `scan_kinship_effects`, `scan_kinship_effects_min_lod`, `scan_kinship_lod_drop` (need `scan_kinship`):
-    `scan_effects`' files and `scan_lod_drop`'s columns under the mixed model (scan.kinship_effects_options)."""
+    `scan_effects`' files and `scan_lod_drop`'s columns under the mixed model (scan.kinship_effects_options).
+    `scan_intcovar` (needs `scan_covar`, not with `scan_kinship`): columns of the covariate table, comma
+    separated, that also interact with the QTL; their scan follows the others and writes its own two files."""
     expr_threshold: float = 1.5
     sigma: float = 0.12
     grid_genoprobs: bool = False
@@ -1454,6 +1456,7 @@ class ReconstructOptions:
     scan_kinship_effects: bool = False
     scan_kinship_effects_min_lod: float = None
     scan_kinship_lod_drop: float = None
+    scan_intcovar: str = None
 
     @classmethod
     def of(cls, keywords):
@@ -1489,7 +1492,7 @@ class ReconstructOptions:
                         scan_kinship_out=self.scan_kinship_out, scan_snps=self.scan_snps,
                         scan_kinship_snps=self.scan_kinship_snps, scan_kinship_effects=self.scan_kinship_effects,
                         scan_kinship_effects_min_lod=self.scan_kinship_effects_min_lod,
-                        scan_kinship_lod_drop=self.scan_kinship_lod_drop)
+                        scan_kinship_lod_drop=self.scan_kinship_lod_drop, scan_intcovar=self.scan_intcovar)
         check_scan_snp_args(self.scan_snps, self.snp_file, self.scan_pheno, grid_file, cohort=cohort)
 
 
@@ -1780,7 +1783,7 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
                      scan_effects: bool = False, scan_effects_min_lod: float = None, scan_lod_drop: float = None,
                      scan_kinship: str = None, scan_kinship_out: bool = False, scan_kinship_snps: str = None,
                      scan_kinship_effects: bool = False, scan_kinship_effects_min_lod: float = None,
-                     scan_kinship_lod_drop: float = None) -> list:
+                     scan_kinship_lod_drop: float = None, scan_intcovar: str = None) -> list:
     """`gbrs reconstruct` for a cohort whose genes.tpm files exist (extension): one context, the tables on the device
     once, the samples through the HMM in launches of up to `batch_size`, and every pass the options ask for once per
     launch.  Every sample gets the files the single-sample call writes for its outbase.  All samples must carry the same
@@ -1799,6 +1802,7 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
     with_effects = any(e is not None and e['min_lod'] is not None for e in (scan_eff, scan_kin_eff))
     scan_kin = scan_mod.kinship_options(scan_kinship, scan_kinship_out, scan_perms, scan_snps, scan_mediate, scan_effects,
                                         scan_lod_drop)
+    scan_int = scan_mod.intcovar_options(scan_intcovar, scan_covar, scan_kinship)
     clock = time.perf_counter
     marks = stage_times if stage_times is not None else {}
     if len(expression_files) != len(outbases):
@@ -1845,6 +1849,8 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
         shared.scan_keep = set(scan_mod.scan_design(outbases, *scan_tables)[0])
         if scan_perm is not None:          # a name the table or the grid does not have is refused before a sample runs
             scan_mod.perm_plan(scan_perm, scan_tables[0][0], [str(c) for c in ctx.chroms])
+        if scan_int is not None:           # a name the covariate table does not have, likewise
+            scan_mod.intcovar_plan(scan_int, scan_tables[1][0])
         if scan_med is not None and scan_med['mediator_file'] is not None:      # a table that cannot be read, likewise
             scan_med['table'] = scan_mod.read_scan_pheno(scan_med['mediator_file'])
         if scan_kinship_snps is not None:  # the mixed model's own SNP file, by --snp-file's parser, likewise
@@ -1955,7 +1961,7 @@ def reconstruct_many(expression_files, outbases, tprob_file: str, avec_file: str
                                  snps=shared.snps if scan_snps else None, snp_grid=ctx.grid, mediate=scan_med,
                                  effects=scan_eff, founders=haplotypes, kinship=scan_kin,
                                  kinship_snps=scan_kin_snps if scan_kinship_snps is not None else None,
-                                 kinship_effects=scan_kin_eff)
+                                 kinship_effects=scan_kin_eff, intcovar=scan_int)
             marks['scan'] += clock() - t0 - (marks['scan_perm'] if scan_perm is not None else 0.0) - \
                 (marks['scan_snps'] if scan_snps or scan_kinship_snps is not None else 0.0) - (marks['mediate'] if scan_med is not None else 0.0) - \
                 (marks['effects'] if with_effects else 0.0)

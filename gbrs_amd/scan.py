@@ -8,7 +8,9 @@ SNPs under that model, after the scan and at its heritabilities (gbrs_scan_lmm_s
 `--scan-mediate`: the scan's peaks conditioned on every other phenotype in turn (gbrs_scan_mediate).
 `--scan-effects`, `--scan-lod-drop`: the founder effects at the scan's peaks with their standard errors
 (gbrs_scan_effects) and the peaks' LOD support intervals (gbrs_scan_run_support); `--scan-kinship-effects`,
-`--scan-kinship-lod-drop`: both under the mixed model (gbrs_scan_lmm_effects, gbrs_scan_lmm_run_support)."""
+`--scan-kinship-lod-drop`: both under the mixed model (gbrs_scan_lmm_effects, gbrs_scan_lmm_run_support).
+`--scan-intcovar NAME[,NAME...]`: the scan with interactive covariates, QTL x covariate, on a preparation
+of its own (gbrs_scan_int_prepare, gbrs_scan_int_run)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -47,6 +49,7 @@ class GenomeScan:
         self.n = 0
         self.prepared = False
         self.lmm_prepared = False
+        self.int_prepared = False
         self.eig_of_chrom = None
         self._dosage_total = 1.0
         h = C.c_void_p()
@@ -77,6 +80,7 @@ class GenomeScan:
         self.n += len(d)
         self.prepared = False
         self.lmm_prepared = False
+        self.int_prepared = False
 
     def append_from(self, hmm, sample=None):
         """The grid dosages of `hmm`'s last run, device to device: every sample of the run, or the one given."""
@@ -84,6 +88,7 @@ class GenomeScan:
         self.n += hmm.n_samples if sample is None else 1
         self.prepared = False
         self.lmm_prepared = False
+        self.int_prepared = False
 
     def prepare(self, covariates=None, names=None):
         """covariates: [n, c] with the intercept (a column of ones) first, or None for the intercept alone."""
@@ -460,6 +465,69 @@ class GenomeScan:
                 'null_ms': raw.last_null_ms, 'point_ms': raw.last_point_ms, 'run_ms': raw.last_run_ms,
                 'device_bytes': raw.device_bytes, 'peak_device_bytes': raw.peak_device_bytes}
 
+    def prepare_int(self, covariates, interactive, names=None):
+        """The phenotype-independent part of the scan with interactive covariates (R/qtl2's scan1 with
+        intcovar).  covariates: as for prepare(), [n, c] with the intercept first; interactive: indices of the columns of
+        `covariates` that also interact with the QTL - not 0, the intercept, and none twice.  As in qtl2 the interactive
+        covariates are additive covariates too: they are taken from `covariates`, as given and not centred.  Independent
+        of prepare() and prepare_lmm()."""
+        z = np.ascontiguousarray(covariates, dtype=np.float64)
+        if z.ndim != 2 or z.shape[0] != self.n:
+            raise ValueError(f'covariates have shape {z.shape} for {self.n} samples')
+        which = [int(j) for j in np.atleast_1d(interactive)]
+        if not which:
+            raise ValueError('no interactive covariate was named')
+        for j in which:
+            if j == 0:
+                raise ValueError('the intercept (column 0) cannot be an interactive covariate')
+            if not 0 < j < z.shape[1]:
+                raise ValueError(f'interactive covariate {j} is not a column of the {z.shape[1]} covariates')
+        if len(set(which)) != len(which):
+            raise ValueError(f'an interactive covariate is named twice: {which}')
+        qz = covariate_basis(z, names)
+        zint = np.ascontiguousarray(z[:, which])
+        self.int_prepared = False
+        _lib.check(_lib.load().gbrs_scan_int_prepare(self._h, qz.shape[1], _lib.ptr(qz), len(which), _lib.ptr(zint)))
+        self.int_prepared = True
+
+    def run_int(self, pheno, want_lod=True):
+        """pheno: [n, P] (or [n]) under the prepared interaction model, with run()'s constant-column-to-zeros step.  Returns
+        `peak_full`, `peak_full_index` [P, n_chrom] (the peaks of the full model's LOD, additive + interaction columns
+        against the covariates), `peak_full_add` (the additive model's LOD at that index), `peak_int`, `peak_int_index`
+        (the peaks of the interaction's LOD, full against additive) and, with want_lod, `lod_full`, `lod_add` and `lod_int`
+        [P, M].  `lod_add` carries the bits of run()'s `lod` after prepare() with the same covariates; `lod_int` is never
+        negative."""
+        y = np.array(pheno, dtype=np.float64, order='C')
+        if y.ndim == 1:
+            y = y[:, None]
+        if y.ndim != 2 or y.shape[0] != self.n or y.shape[1] < 1:
+            raise ValueError(f'phenotypes have shape {np.shape(pheno)} for {self.n} samples')
+        if self.n:
+            y[:, (y == y[0]).all(axis=0)] = 0.0
+        P, nc = y.shape[1], len(self.points)
+        full, add, inter = (np.empty((P, self.M)) if want_lod else None for _ in range(3))
+        peak_full, peak_add, peak_int = np.empty((P, nc)), np.empty((P, nc)), np.empty((P, nc))
+        index_full, index_int = np.empty((P, nc), dtype=np.int64), np.empty((P, nc), dtype=np.int64)
+        _lib.check(_lib.load().gbrs_scan_int_run(self._h, P, _lib.ptr(y), _lib.ptr(full), _lib.ptr(add), _lib.ptr(inter),
+                                                 _lib.ptr(peak_full), _lib.ptr(index_full), _lib.ptr(peak_add),
+                                                 _lib.ptr(peak_int), _lib.ptr(index_int)))
+        out = {'peak_full': peak_full, 'peak_full_index': index_full, 'peak_full_add': peak_add, 'peak_int': peak_int,
+               'peak_int_index': index_int}
+        if want_lod:
+            out.update(lod_full=full, lod_add=add, lod_int=inter)
+        return out
+
+    def int_info(self):
+        raw = _lib.ScanIntInfo()
+        _lib.check(_lib.load().gbrs_scan_int_info(self._h, C.byref(raw), None, None))
+        rank_full = rank_add = None
+        if raw.c > 0:
+            rank_full, rank_add = np.empty(raw.M, dtype=np.int32), np.empty(raw.M, dtype=np.int32)
+            _lib.check(_lib.load().gbrs_scan_int_info(self._h, None, _lib.ptr(rank_full), _lib.ptr(rank_add)))
+        return {'n': raw.n, 'M': raw.M, 'H': raw.H, 'c': raw.c, 'k': raw.k, 'HPI': raw.HPI, 'rank_full': rank_full,
+                'rank_add': rank_add, 'prepare_ms': raw.last_prepare_ms, 'run_ms': raw.last_run_ms,
+                'product_ms': raw.last_product_ms, 'device_bytes': raw.device_bytes}
+
     def info(self):
         raw = _lib.ScanInfo()
         _lib.check(_lib.load().gbrs_scan_info(self._h, C.byref(raw), None))
@@ -701,18 +769,49 @@ def kinship_effects_options(scan_kinship_effects=False, scan_kinship_effects_min
     return {'min_lod': min_lod, 'lod_drop': drop}
 
 
+def intcovar_options(scan_intcovar=None, scan_covar=None, scan_kinship=None):
+    """`--scan-intcovar NAME[,NAME...]` as the list of names, or None without it.  It needs `--scan-covar`
+    (qtl2 adds intcovar to addcovar: an interactive covariate is a column of the covariate table), names no column twice
+    and cannot stand beside `--scan-kinship`.  Refused before a file is read; whether the table has the names is
+    intcovar_plan's question, asked as soon as the table's header is known."""
+    if scan_intcovar is None:
+        return None
+    if scan_covar is None:
+        raise RuntimeError('--scan-intcovar needs --scan-covar: the interactive covariates are columns of the covariate table')
+    if scan_kinship is not None:
+        raise RuntimeError('--scan-intcovar cannot be combined with --scan-kinship: the mixed model with interactions is not '
+                           'part of the scan')
+    names = [x.strip() for x in str(scan_intcovar).split(',')]
+    if any(not x for x in names):
+        raise RuntimeError(f'--scan-intcovar must be covariate names separated by commas, got {scan_intcovar!r}')
+    for x in names:
+        if names.count(x) > 1:
+            raise RuntimeError(f'--scan-intcovar names {x} twice')
+    return names
+
+
+def intcovar_plan(intcovar, covar_names):
+    """The columns of scan_design's Z (intercept first) that `intcovar` names among the covariate table's `covar_names`; a
+    name the table does not have is refused before a dosage is read or the device runs."""
+    for x in intcovar:
+        if x not in covar_names:
+            raise RuntimeError(f'--scan-intcovar: {x} is not a column of --scan-covar (its columns: {", ".join(covar_names)})')
+    return [1 + list(covar_names).index(x) for x in intcovar]
+
+
 def check_scan_args(scan_pheno=None, scan_covar=None, scan_rankz=False, scan_out=None, scan_min_lod=None,
                     scan_lod_matrix=False, grid_file=None, cohort=False, scan_perms=None, scan_perm_seed=None,
                     scan_perm_alpha=None, scan_perm_chromosomes=None, scan_perm_pheno=None, scan_mediate=False,
                     scan_mediate_min_lod=None, scan_mediate_top=None, scan_mediator_file=None, scan_effects=False,
                     scan_effects_min_lod=None, scan_lod_drop=None, scan_kinship=None, scan_kinship_out=False, scan_snps=False,
                     scan_kinship_snps=None, scan_kinship_effects=False, scan_kinship_effects_min_lod=None,
-                    scan_kinship_lod_drop=None):
+                    scan_kinship_lod_drop=None, scan_intcovar=None):
     """`--scan-pheno FILE [--scan-covar FILE] [--scan-rankz] [--scan-out PREFIX] [--scan-min-lod X] [--scan-lod-matrix]`,
     the `--scan-perm*` options (perm_options), the `--scan-mediat*` options (mediate_options), `--scan-effects`,
     `--scan-effects-min-lod`, `--scan-lod-drop` (effects_options) and `--scan-kinship`, `--scan-kinship-out`
     (kinship_options) with `--scan-kinship-snps` (kinship_snp_options), `--scan-kinship-effects`,
-    `--scan-kinship-effects-min-lod` and `--scan-kinship-lod-drop` (kinship_effects_options):
+    `--scan-kinship-effects-min-lod` and `--scan-kinship-lod-drop` (kinship_effects_options) and `--scan-intcovar`
+    (intcovar_options):
     every option needs the phenotypes, the phenotypes need `--grid-file` and a cohort (`--sample-file`): one sample
     cannot be scanned.  Refused before a file is read."""
     given = {'--scan-covar': scan_covar, '--scan-rankz': scan_rankz or None, '--scan-out': scan_out,
@@ -724,13 +823,15 @@ def check_scan_args(scan_pheno=None, scan_covar=None, scan_rankz=False, scan_out
              '--scan-effects': scan_effects or None, '--scan-effects-min-lod': scan_effects_min_lod,
              '--scan-lod-drop': scan_lod_drop, '--scan-kinship': scan_kinship, '--scan-kinship-out': scan_kinship_out or None,
              '--scan-kinship-snps': scan_kinship_snps, '--scan-kinship-effects': scan_kinship_effects or None,
-             '--scan-kinship-effects-min-lod': scan_kinship_effects_min_lod, '--scan-kinship-lod-drop': scan_kinship_lod_drop}
+             '--scan-kinship-effects-min-lod': scan_kinship_effects_min_lod, '--scan-kinship-lod-drop': scan_kinship_lod_drop,
+             '--scan-intcovar': scan_intcovar}
     perm_options(scan_perms, scan_perm_seed, scan_perm_alpha, scan_perm_chromosomes, scan_perm_pheno)
     mediate_options(scan_mediate, scan_mediate_min_lod, scan_mediate_top, scan_mediator_file)
     effects_options(scan_effects, scan_effects_min_lod, scan_lod_drop)
     kinship_options(scan_kinship, scan_kinship_out, scan_perms, scan_snps, scan_mediate, scan_effects, scan_lod_drop)
     kinship_snp_options(scan_kinship_snps, scan_kinship)
     kinship_effects_options(scan_kinship_effects, scan_kinship_effects_min_lod, scan_kinship_lod_drop, scan_kinship)
+    intcovar_options(scan_intcovar, scan_covar, scan_kinship)
     if scan_pheno is None:
         for name, value in given.items():
             if value is not None:
@@ -1225,9 +1326,65 @@ def finish_scan_effects_lmm(scan, prefix, ids, pheno, covariates, y, min_lod, re
         stage_times['effects'] = stage_times.get('effects', 0.0) + time.perf_counter() - t0
 
 
+def write_scan_int(prefix, phenotypes, samples, covariates, intcovar, chrom, pos, chrom_names, result, rank_full, rank_add,
+                   min_lod=0.0):
+    """`<prefix>.scan.int.npz` and `<prefix>.scan.int.peaks.tsv`.  result: GenomeScan.run_int's dict and
+    `peak_full_int` [P, n_chrom], lod_int at the full model's peak.  The .npz holds the names, chrom / pos per grid point,
+    `rank_full` and `rank_add`, the five peak arrays and, where result has them, `lod_full`, `lod_add` and `lod_int`.  The
+    peaks file has one line per full-model peak of at least min_lod: the peak's position, `lod_full`, `lod_add` and
+    `lod_int` at it, the degrees of freedom of the two models there (the kept columns) and the chromosome's own
+    interaction peak, its position and LOD."""
+    arrays = dict(phenotypes=np.array(phenotypes), samples=np.array(samples), covariates=np.array(covariates),
+                  intcovar=np.array(intcovar), chrom=np.array(chrom), pos=np.asarray(pos, dtype=np.float64),
+                  rank_full=np.asarray(rank_full), rank_add=np.asarray(rank_add))
+    for key in ('peak_full', 'peak_full_index', 'peak_full_add', 'peak_int', 'peak_int_index', 'lod_full', 'lod_add', 'lod_int'):
+        if key in result:
+            arrays[key] = result[key]
+    np.savez(f'{prefix}.scan.int.npz', **arrays)
+    peak, index, at_int = result['peak_full'], result['peak_full_index'], result['peak_full_int']
+    number = lambda v: repr(float(v))
+    with open(f'{prefix}.scan.int.peaks.tsv', 'w') as out:
+        out.write('#phenotype\tchromosome\tposition\tlod_full\tlod_add\tlod_int\tdf_full\tdf_add\tint_peak_position\tint_peak_lod\n')
+        for p, name in enumerate(phenotypes):
+            for c in range(len(chrom_names)):
+                if index[p, c] >= 0 and peak[p, c] >= min_lod:
+                    m = index[p, c]
+                    out.write(f'{name}\t{chrom_names[c]}\t{number(pos[m])}\t{number(peak[p, c])}\t'
+                              f'{number(result["peak_full_add"][p, c])}\t{number(at_int[p, c])}\t{int(rank_full[m])}\t'
+                              f'{int(rank_add[m])}\t{number(pos[result["peak_int_index"][p, c]])}\t'
+                              f'{number(result["peak_int"][p, c])}\n')
+
+
+def finish_scan_int(scan, prefix, ids, phenotypes, covariates, z, interactive, y, chrom, pos, chrom_names, min_lod=None,
+                    lod_matrix=False):
+    """prepare_int + run_int + write_scan_int for the cohort `scan` holds.  The three matrices go to the
+    .npz under write_scan's rule (`--scan-lod-matrix`, or P x M up to LOD_MATRIX_LIMIT); without them the phenotypes pass
+    in blocks of columns whose matrices are dropped once lod_int at the full model's peaks is read from them - a phenotype's
+    numbers are the same bits in any block."""
+    scan.prepare_int(z, interactive, covariates)
+    P, nc = y.shape[1], len(chrom_names)
+    want_lod = bool(lod_matrix) or P * scan.M <= LOD_MATRIX_LIMIT
+    block = P if want_lod else max(1, LOD_MATRIX_LIMIT // scan.M)
+    parts = []
+    for p0 in range(0, P, block):
+        got = scan.run_int(y[:, p0:p0 + block])
+        rows, at = np.arange(got['lod_int'].shape[0])[:, None], got['peak_full_index']
+        got['peak_full_int'] = np.where(at >= 0, got['lod_int'][rows, np.maximum(at, 0)], np.nan)
+        if not want_lod:
+            for key in ('lod_full', 'lod_add', 'lod_int'):
+                del got[key]
+        parts.append(got)
+    result = {key: np.concatenate([g[key] for g in parts]) for key in parts[0]}
+    info = scan.int_info()
+    write_scan_int(prefix, phenotypes, ids, covariates, [covariates[j] for j in interactive], chrom, pos, chrom_names, result,
+                   info['rank_full'], info['rank_add'], 0.0 if min_lod is None else min_lod)
+    logger.info(f'scan: {len(interactive)} interactive covariates ({", ".join(covariates[j] for j in interactive)}), '
+                f'{info["HPI"]} rows per grid point; prepare {info["prepare_ms"]:.1f} ms, run {info["run_ms"]:.1f} ms on the device')
+
+
 def finish_scan(scan, prefix, ids, pheno, covar, use_rankz, chrom, pos, chrom_names, min_lod=None, lod_matrix=False,
                 perm=None, stage_times=None, snps=None, snp_grid=None, mediate=None, effects=None, founders=None, kinship=None,
-                kinship_snps=None, kinship_effects=None):
+                kinship_snps=None, kinship_effects=None, intcovar=None):
     """prepare + run + the two files for the cohort `scan` holds, whose samples are `ids` in append order (every one with
     its rows in the tables).  perm: perm_options' dict, or None; with it the permutation pass runs after the scan on the
     phenotypes and chromosomes it names and its wall-clock seconds go to stage_times['scan_perm'].  mediate:
@@ -1238,7 +1395,10 @@ def finish_scan(scan, prefix, ids, pheno, covar, use_rankz, chrom, pos, chrom_na
     passes runs, except that of kinship_snps (read_snp_file's dict of `--scan-kinship-snps`, or None): the SNP association
     under the same mixed model, at the heritabilities the scan fitted, and those of kinship_effects
     (kinship_effects_options' dict, or None): its lod_drop makes the run form the support intervals, its min_lod makes the
-    founder effects of the peaks follow under the same mixed model and heritabilities.  Returns GenomeScan.info() after the run."""
+    founder effects of the peaks follow under the same mixed model and heritabilities.
+    intcovar: intcovar_options' list of names, or None; with it the scan with those interactive covariates follows every
+    other pass on a preparation of its own (finish_scan_int) and the other files are what they were.
+    Returns GenomeScan.info() after the run."""
     kept, y, z, names = scan_design(ids, pheno, covar, use_rankz)
     assert len(kept) == len(ids) == scan.n
     if kinship is not None:
@@ -1263,6 +1423,8 @@ def finish_scan(scan, prefix, ids, pheno, covar, use_rankz, chrom, pos, chrom_na
         return scan.info()
     if perm is not None:
         columns, mask = perm_plan(perm, pheno[0], [str(c) for c in chrom_names])     # refused before the device runs
+    if intcovar is not None:
+        interactive = intcovar_plan(intcovar, names[1:])                             # likewise
     scan.prepare(z, names)
     want_lod = bool(lod_matrix) or y.shape[1] * scan.M <= LOD_MATRIX_LIMIT
     lod_drop = effects['lod_drop'] if effects is not None else None
@@ -1291,6 +1453,8 @@ def finish_scan(scan, prefix, ids, pheno, covar, use_rankz, chrom, pos, chrom_na
     if effects is not None and effects['min_lod'] is not None:      # effects_options' dict: the peaks' founder effects
         finish_scan_effects(scan, prefix, ids, pheno, names, y, effects['min_lod'], result, chrom_names, pos, founders,
                             stage_times)
+    if intcovar is not None:    # intcovar_options' names: the interaction scan on a preparation of its own
+        finish_scan_int(scan, prefix, ids, pheno[0], names, z, interactive, y, chrom, pos, chrom_names, min_lod, lod_matrix)
     return info
 
 
@@ -1299,7 +1463,7 @@ def scan_tables(dosage_list, grid_file, pheno_file, covar_file=None, use_rankz=F
                 scan_perm_chromosomes=None, scan_perm_pheno=None, stage_times=None, snp_file=None, scan_mediate=False,
                 scan_mediate_min_lod=None, scan_mediate_top=None, scan_mediator_file=None, scan_effects=False,
                 scan_effects_min_lod=None, scan_lod_drop=None, scan_kinship=None, scan_kinship_out=False, scan_kinship_snps=None,
-                scan_kinship_effects=False, scan_kinship_effects_min_lod=None, scan_kinship_lod_drop=None):
+                scan_kinship_effects=False, scan_kinship_effects_min_lod=None, scan_kinship_lod_drop=None, scan_intcovar=None):
     """`gbrs scan`: the cohort from dosage tables in `gbrs export` format (lines `id<TAB>dosage table`), rows in the grid
     file's order, without the HMM.  snp_file (`--snp-file`): the SNP association pass follows the scan (DESIGN.md §29);
     the haplotypes of the patterns are those of the dosage tables' header.  scan_mediate (`--scan-mediate`): the scan's
@@ -1309,7 +1473,8 @@ def scan_tables(dosage_list, grid_file, pheno_file, covar_file=None, use_rankz=F
     linear mixed model's; scan_kinship_out writes the kinship matrices; scan_kinship_snps
     (`--scan-kinship-snps FILE`): the SNP association pass under the mixed model follows the scan (DESIGN.md §33);
     scan_kinship_effects, scan_kinship_effects_min_lod and scan_kinship_lod_drop: the peaks' founder effects and support
-    intervals under the mixed model."""
+    intervals under the mixed model.  scan_intcovar (`--scan-intcovar NAME[,NAME...]`): the scan with those
+    columns of the covariate table as interactive covariates follows."""
     from .hmm import _match_lines, read_dosage_table, read_snp_file
     from .postproc import read_grid
     if min_lod is not None and not min_lod >= 0.0:
@@ -1322,6 +1487,7 @@ def scan_tables(dosage_list, grid_file, pheno_file, covar_file=None, use_rankz=F
     kinship_snp_options(scan_kinship_snps, scan_kinship)
     kinship_effects = kinship_effects_options(scan_kinship_effects, scan_kinship_effects_min_lod, scan_kinship_lod_drop,
                                               scan_kinship)
+    intcovar = intcovar_options(scan_intcovar, covar_file, scan_kinship)
     grid = read_grid(grid_file)
     chrom_names = list(grid)
     points = [len(grid[c]) for c in chrom_names]
@@ -1337,6 +1503,8 @@ def scan_tables(dosage_list, grid_file, pheno_file, covar_file=None, use_rankz=F
         mediate['table'] = read_scan_pheno(mediate['mediator_file'])      # refused before a dosage table is read
     if perm is not None:
         perm_plan(perm, pheno[0], [str(c) for c in chrom_names])          # refused before a dosage table is read
+    if intcovar is not None:
+        intcovar_plan(intcovar, covar[0])                                 # likewise
     kept, _, _, _ = scan_design([i for i, _ in entries], pheno, covar)
     if not kept:
         raise RuntimeError('scan: no sample of the dosage list has a phenotype row')
@@ -1353,6 +1521,6 @@ def scan_tables(dosage_list, grid_file, pheno_file, covar_file=None, use_rankz=F
         return finish_scan(scan, out if out is not None else 'gbrs', [entries[k][0] for k in kept], pheno, covar, use_rankz,
                            chrom, pos, chrom_names, min_lod, lod_matrix, perm=perm, stage_times=stage_times, snps=snps,
                            snp_grid=grid, mediate=mediate, effects=effects, founders=haplotypes, kinship=kinship,
-                           kinship_snps=kinship_snps, kinship_effects=kinship_effects)
+                           kinship_snps=kinship_snps, kinship_effects=kinship_effects, intcovar=intcovar)
     finally:
         scan.close()

@@ -1349,6 +1349,58 @@ int gbrs_scan_lmm_run_support(gbrs_scan_t *scan, int64_t P, const double *pheno,
                               double *lod, double *peak_lod, int64_t *peak_index, double *hsq, double *sigma2,
                               int64_t *support_lo, int64_t *support_hi /* [P][n_chrom] */);
 
+/* Interactive covariates (R/qtl2's scan1 with intcovar): the scan of a QTL x covariate model.  k >= 1
+ * interactive covariates zint double[n][k] are used as given, not centred; the caller guarantees that each lies in the span
+ * of qz (it is one of the covariates the basis was made from).  With Hx = H - 1, the columns at grid point m are, in order,
+ *   additive      x_j[s] = D[s][m][j],                        j < Hx
+ *   interaction   x[s]   = D[s][m][j] zint[s][q],             q = 0 .. k-1, then j < Hx
+ * and gbrs_scan_prepare's factorisation runs over all Hx (1 + k) of them in that order: raw is the squared norm of a column
+ * as built, the projection on qz, the Gram matrix and the Cholesky factorisation with the skip rule (both lines of it, the
+ * same 1e-10) follow.  rank_add[m] counts the kept columns among the first Hx, rank_full[m] all kept columns.  Every sum
+ * over the samples is formed in gbrs_scan_prepare's order, so the additive rows of the new W carry the bits of its W and
+ * rank_add those of its rank for the same qz.
+ * W is kept as [M * HPI][n_ld]: a point's first Hp rows as gbrs_scan_prepare lays them out, the k Hx interaction rows from
+ * row Hp, zeros up to HPI, the smallest of 16, 32 and 64 that holds Hp + k Hx.  Hp + k Hx > 64 is GBRS_ERR_UNSUPPORTED.
+ * The preparation is independent of gbrs_scan_prepare and of gbrs_scan_lmm_prepare and keeps its own copy of qz; an append
+ * drops it.  GBRS_ERR_INVALID for k < 1, c < 1 or c > 64, n <= c + Hx (1 + k) and a value of qz or zint that is not finite
+ * (the message names the entry); such a refusal leaves the handle as it was, an earlier preparation included.  A failure
+ * after these checks leaves it without one. */
+int gbrs_scan_int_prepare(gbrs_scan_t *scan, int c, const double *qz /* [n][c] */, int k, const double *zint /* [n][k] */);
+
+/* P phenotypes under the prepared interaction model: pheno is double[n][P].  Per phenotype and grid point, with y~ and rss0
+ * as gbrs_scan_run forms them (the same kernel),
+ *   ess_add  = sum over the additive rows j of (W_j y~)^2           the bits of gbrs_scan_run's ess
+ *   ess_x    = the same sum over the interaction rows,   ess_full = ess_add + ess_x   (so ess_full >= ess_add exactly)
+ *   lod_full = (n / 2) log10(rss0 / (rss0 - ess_full)),  lod_add = (n / 2) log10(rss0 / (rss0 - ess_add)),
+ *              each with gbrs_scan_run's two edge rules; lod_add carries the bits of gbrs_scan_run's lod for the same qz
+ *   lod_int  = (n / 2) log10(rss_add / rss_full) with rss_add = rss0 - ess_add, rss_full = rss0 - ess_full;
+ *              0.0 where rss0 == 0 or rss_add <= 0; +inf where rss_full <= 0 < rss_add.  Never negative, never NaN.
+ * lod_full, lod_add and lod_int are double[P][M].  peak_full and peak_full_index [P][n_chrom] are gbrs_scan_run's peaks of
+ * lod_full (the first of the largest per chromosome; NaN and -1 without points), peak_full_add is lod_add at that index;
+ * peak_int and peak_int_index are the peaks of lod_int.  Every output is nullable, and a LOD row is formed only where an
+ * output needs it.  The phenotypes pass in chunks of 512 columns; a phenotype's numbers are the same bits alone or among
+ * others, at any column, in any chunk, with any subset of the outputs, and however the cohort was appended.  A column in
+ * the covariates' span is the caller's to send as zeros, as for gbrs_scan_run.  GBRS_ERR_INVALID before
+ * gbrs_scan_int_prepare, for P < 1 and for a value that is not finite (the message names the entry); the outputs are
+ * untouched on failure.  The call allocates and frees its own buffers: gbrs_scan_run gives the same bits before and after.
+ * No permutations, SNP association, mediation, effects or mixed model with interactions. */
+int gbrs_scan_int_run(gbrs_scan_t *scan, int64_t P, const double *pheno /* [n][P] */,
+                      double *lod_full, double *lod_add, double *lod_int,                   /* [P][M], each nullable */
+                      double *peak_full, int64_t *peak_full_index, double *peak_full_add,   /* [P][n_chrom] */
+                      double *peak_int, int64_t *peak_int_index);                           /* [P][n_chrom] */
+
+typedef struct gbrs_scan_int_info {
+    int64_t  n, M;               /* samples appended, grid points                                                */
+    int32_t  H, c;               /* founders; covariate columns of the last gbrs_scan_int_prepare (0: not prepared) */
+    int32_t  k, HPI;             /* its interactive covariates and the rows of W per grid point (16, 32 or 64)   */
+    double   last_prepare_ms;    /* device time of the last gbrs_scan_int_prepare's kernel                       */
+    double   last_run_ms;        /* device time of the last gbrs_scan_int_run: its kernels and copies, all chunks */
+    double   last_product_ms;    /* of that, the product kernel alone, summed over the chunks                    */
+    uint64_t device_bytes;       /* what the preparation holds on the device (0: not prepared)                   */
+} gbrs_scan_int_info_t;
+/* rank_full and rank_add are int32[M] of the last preparation, nullable; untouched when the handle has none. */
+int gbrs_scan_int_info(gbrs_scan_t *scan, gbrs_scan_int_info_t *info, int32_t *rank_full, int32_t *rank_add);
+
 /* ------------------------------------------------------------------------------------------
  * Report text (host side, no device work): the `locus <haplotypes> total [notes]` tables of
  * EMfactory.report_read_counts / report_depths (emase/EMfactory.py:289-380).

@@ -356,6 +356,8 @@ scan_peak_kernel(int64_t M, int n_chrom, const int64_t *__restrict__ point_off, 
 
 using namespace gbrs;
 
+// The handle: the grid, then one group per feature.  A group owns its device buffers, sums them in bytes() and drops what
+// an append invalidates in unprepare(); `last` holds the report of every pass as the public struct itself.
 struct gbrs_scan {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -366,123 +368,216 @@ struct gbrs_scan {
     std::vector<int64_t> point_off;           // n_chrom + 1
     DevBuf<int64_t> d_point_off;
     // the cohort: [capacity][M][H], the first n rows in use
-    int64_t n = 0, capacity = 0;
-    DevBuf<double> dosage;
-    // what gbrs_scan_prepare made
-    int c = 0;                                // 0: not prepared
-    int64_t n_ld = 0;
-    DevBuf<double> qz, W;
-    DevBuf<int32_t> d_rank;
-    std::vector<int32_t> rank;
-    // one chunk of gbrs_scan_run
-    DevBuf<double> y, yt, rss0, lod, peak_lod;
-    DevBuf<int64_t> peak_index;
-    double t_prepare = 0, t_run = 0, t_product = 0;
-    // the last gbrs_scan_permute: its buffers are the call's own and are gone when it returns
-    int64_t perm_P = 0, perm_B = 0;
-    double t_permute = 0, t_perm_product = 0;
-    uint64_t perm_peak_bytes = 0;
+    struct Cohort {
+        int64_t n = 0, capacity = 0;
+        DevBuf<double> dosage;
+    } cohort;
+    // what gbrs_scan_prepare made (c 0: not prepared), and one chunk of gbrs_scan_run
+    struct Prep {
+        int c = 0;
+        int64_t n_ld = 0;
+        DevBuf<double> qz, W;
+        DevBuf<int32_t> d_rank;
+        std::vector<int32_t> rank;
+        DevBuf<double> y, yt, rss0, lod, peak_lod;
+        DevBuf<int64_t> peak_index;
+        uint64_t bytes() const {
+            return qz.bytes() + W.bytes() + d_rank.bytes() + y.bytes() + yt.bytes() + rss0.bytes() + lod.bytes() + peak_lod.bytes() +
+                   peak_index.bytes();
+        }
+        void unprepare() {
+            c = 0;
+            rank.clear();
+        }
+    } prep;
     // the SNPs of gbrs_scan_set_snps in handle order (chromosome after chromosome): SS_TABLE_BYTES per SNP
-    int64_t M_snp = 0;
-    std::vector<int64_t> snp_off;             // n_chrom + 1
-    DevBuf<int64_t> d_snp_off;
-    DevBuf<int32_t> snp_lo, snp_hi;           // global point indices
-    DevBuf<uint32_t> snp_mask;
-    DevBuf<double> snp_t;
-    // the last gbrs_scan_snps: its buffers are the call's own, as gbrs_scan_permute's
-    int64_t snp_P = 0;
-    int snp_staged = 0;
-    double t_snp_pass = 0, t_snp_row = 0, t_snp_product = 0;
-    uint64_t snp_peak_bytes = 0;
-    // the last gbrs_scan_mediate: its buffers are the call's own, as gbrs_scan_permute's
-    int64_t med_T = 0, med_Q = 0;
-    double t_med_pass = 0, t_med_product = 0;
-    uint64_t med_peak_bytes = 0;
-    // the last gbrs_scan_effects: its buffers are the call's own, as gbrs_scan_permute's
-    int64_t eff_T = 0, eff_P = 0;
-    double t_eff_pass = 0;
-    uint64_t eff_peak_bytes = 0;
+    struct Snp {
+        int64_t M = 0;
+        std::vector<int64_t> off;             // n_chrom + 1
+        DevBuf<int64_t> d_off;
+        DevBuf<int32_t> lo, hi;               // global point indices
+        DevBuf<uint32_t> mask;
+        DevBuf<double> t;
+        uint64_t bytes() const { return d_off.bytes() + lo.bytes() + hi.bytes() + mask.bytes() + t.bytes(); }
+        void clear() {
+            M = 0;
+            off.clear();
+            d_off.release();
+            lo.release();
+            hi.release();
+            mask.release();
+            t.release();
+        }
+    } snp;
     // the per-chromosome products S_c of gbrs_scan_kinship, [n_chrom][n][n]: kept until the next append
-    DevBuf<double> kin_S;
-    bool kin_valid = false;
-    double t_kinship = 0;
-    // what gbrs_scan_lmm_prepare made (lmm_cz 0: not prepared): the decompositions, the rotated covariates [n_eig][cz][n_ld]
-    // and the rotated cohort [M][Hp][n_ld]
-    int lmm_cz = 0, lmm_n_eig = 0;
-    int64_t lmm_n_ld = 0;
-    DevBuf<double> lmm_U, lmm_lam, lmm_Zs, lmm_R;
-    DevBuf<int32_t> lmm_eig_of_point;
-    std::vector<int32_t> lmm_eig_of_chrom;
-    // the last gbrs_scan_lmm_run: its buffers are the call's own, as gbrs_scan_permute's
-    int64_t lmm_P = 0;
-    std::vector<int32_t> lmm_rank_min, lmm_rank_max;
-    double t_lmm_rotate = 0, t_lmm_null = 0, t_lmm_point = 0, t_lmm_run = 0;
-    uint64_t lmm_peak_bytes = 0;
-    // the last gbrs_scan_lmm_snps: its buffers are the call's own, as gbrs_scan_permute's
-    int64_t lsnp_P = 0;
-    double t_lsnp_pass = 0, t_lsnp_null = 0, t_lsnp_rotate = 0, t_lsnp_product = 0;
-    uint64_t lsnp_column_bytes = 0, lsnp_peak_bytes = 0;
-    // the last gbrs_scan_lmm_effects: its buffers are the call's own, as gbrs_scan_permute's
-    int64_t leff_T = 0, leff_P = 0, leff_columns = 0;
-    double t_leff_pass = 0, t_leff_null = 0, t_leff_target = 0;
-    uint64_t leff_peak_bytes = 0;
-    // what gbrs_scan_int_prepare made (int_c 0: not prepared): its own qz, the interactive covariates and the W of §35,
-    // [M * int_hpi][int_n_ld]; the ranks are [2][M] on the device, full then additive
-    int int_c = 0, int_k = 0, int_hpi = 0;
-    int64_t int_n_ld = 0;
-    DevBuf<double> int_qz, int_zint, int_W;
-    DevBuf<int32_t> int_d_rank;
-    std::vector<int32_t> int_rank_full, int_rank_add;
-    double t_int_prepare = 0, t_int_run = 0, t_int_product = 0;
-    uint64_t int_bytes() const { return int_qz.bytes() + int_zint.bytes() + int_W.bytes() + int_d_rank.bytes(); }
-    uint64_t lmm_bytes() const {
-        return lmm_U.bytes() + lmm_lam.bytes() + lmm_Zs.bytes() + lmm_R.bytes() + lmm_eig_of_point.bytes();
-    }
-    uint64_t snp_bytes() const {
-        return d_snp_off.bytes() + snp_lo.bytes() + snp_hi.bytes() + snp_mask.bytes() + snp_t.bytes();
-    }
+    struct Kin {
+        DevBuf<double> S;
+        bool valid = false;
+    } kin;
+    // what gbrs_scan_lmm_prepare made (cz 0: not prepared): the decompositions, the rotated covariates [n_eig][cz][n_ld]
+    // and the rotated cohort [M][Hp][n_ld]; the ranks are the last gbrs_scan_lmm_run's
+    struct Lmm {
+        int cz = 0, n_eig = 0;
+        int64_t n_ld = 0;
+        DevBuf<double> U, lam, Zs, R;
+        DevBuf<int32_t> eig_of_point;
+        std::vector<int32_t> eig_of_chrom, rank_min, rank_max;
+        uint64_t bytes() const { return U.bytes() + lam.bytes() + Zs.bytes() + R.bytes() + eig_of_point.bytes(); }
+        void unprepare() {
+            cz = 0;
+            n_eig = 0;
+        }
+    } lmm;
+    // what gbrs_scan_int_prepare made (c 0: not prepared): its own qz, the interactive covariates and the W of §35,
+    // [M * hpi][n_ld]; the ranks are [2][M] on the device, full then additive
+    struct Inter {
+        int c = 0, k = 0, hpi = 0;
+        int64_t n_ld = 0;
+        DevBuf<double> qz, zint, W;
+        DevBuf<int32_t> d_rank;
+        std::vector<int32_t> rank_full, rank_add;
+        uint64_t bytes() const { return qz.bytes() + zint.bytes() + W.bytes() + d_rank.bytes(); }
+        void unprepare() {                    // its W included
+            c = 0;
+            k = 0;
+            hpi = 0;
+            rank_full.clear();
+            rank_add.clear();
+            W.release();
+        }
+    } inter;
+    // The reports: a pass fills the fields of its own when it has succeeded, its getter adds the few that are read live.
+    // The buffers of a pass are the call's own and are gone when it returns.
+    struct Last {
+        gbrs_scan_info_t scan = {};
+        gbrs_scan_perm_info_t perm = {};
+        gbrs_scan_snp_info_t snp = {};
+        gbrs_scan_mediate_info_t mediate = {};
+        gbrs_scan_effects_info_t effects = {};
+        gbrs_scan_lmm_info_t lmm = {};
+        gbrs_scan_lmm_snp_info_t lmm_snp = {};
+        gbrs_scan_lmm_effects_info_t lmm_effects = {};
+        gbrs_scan_int_info_t inter = {};
+    } last;
+    // gbrs_scan_info_t's figure: the grid, the cohort, the preparation and gbrs_scan_run's chunk
+    uint64_t scan_bytes() const { return d_point_off.bytes() + cohort.dosage.bytes() + prep.bytes(); }
+    // every buffer the handle owns, whatever is prepared: with a pass's own buffers, its peak_device_bytes
+    uint64_t resident_bytes() const { return scan_bytes() + snp.bytes() + kin.S.bytes() + lmm.bytes() + inter.bytes(); }
 };
 
 namespace {
 
-// Room for `more` samples after the n in use; the samples in use move with the buffer.
-int scan_reserve(gbrs_scan *s, int64_t more) {
-    if (s->n + more <= s->capacity) return GBRS_OK;
-    const int64_t want = std::max(s->n + more, 2 * s->capacity);
-    const size_t row = (size_t)s->M * s->H;
-    DevBuf<double> grown;
-    GBRS_TRY(grown.alloc((size_t)want * row));
-    if (s->n > 0) {        // on the handle's stream and waited for: a device-to-device hipMemcpy need not be done when it returns
-        GBRS_HIP_CHECK(hipMemcpyAsync(grown.p, s->dosage.p, (size_t)s->n * row * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
-        GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
-    }
-    s->dosage.swap(grown);
-    s->capacity = want;
+// ---- what the passes do around their kernels -----------------------------------------------------------------
+// The checks are steps, not one call: the passes put their own checks between them, and the first error counts.
+
+// a table [n][cols] of the samples' values: `noun` is "phenotype", "target" or "mediator"
+int check_finite(const char *noun, const double *table, int64_t n, int64_t cols) {
+    for (int64_t k = 0; k < n * cols; ++k)
+        if (!std::isfinite(table[k]))
+            return fail(GBRS_ERR_INVALID, "%s %lld holds a value that is not finite (sample %lld)", noun, (long long)(k % cols),
+                        (long long)(k / cols));
     return GBRS_OK;
 }
 
-void scan_unprepare(gbrs_scan *s) {
-    s->c = 0;
-    s->rank.clear();
+// the heritabilities a caller gives, [P][n_eig], nullable
+int check_hsq(const double *hsq_in, int64_t P, int n_eig) {
+    if (hsq_in)
+        for (int64_t k = 0; k < P * n_eig; ++k)
+            if (!(hsq_in[k] >= 0.0 && hsq_in[k] <= 1.0))
+                return fail(GBRS_ERR_INVALID, "the heritability given for phenotype %lld and decomposition %d is %g, outside [0, 1]",
+                            (long long)(k / n_eig), (int)(k % n_eig), hsq_in[k]);
+    return GBRS_OK;
 }
 
-// An append drops what gbrs_scan_kinship and gbrs_scan_lmm_prepare made, as it drops W.
-void scan_lmm_unprepare(gbrs_scan *s) {
-    s->lmm_cz = 0;
-    s->lmm_n_eig = 0;
-    s->kin_valid = false;
-    s->kin_S.release();
+// the targets of a pass: a column of [0, P) (where the pass has columns) and a grid point each
+int check_targets(const gbrs_scan *s, int64_t T, const int64_t *column, int64_t P, const int64_t *point) {
+    for (int64_t t = 0; t < T; ++t) {
+        if (column && (column[t] < 0 || column[t] >= P))
+            return fail(GBRS_ERR_INVALID, "target %lld is phenotype column %lld: the table has the columns 0 .. %lld", (long long)t,
+                        (long long)column[t], (long long)(P - 1));
+        if (point[t] < 0 || point[t] >= s->M)
+            return fail(GBRS_ERR_INVALID, "target %lld is at grid point %lld: the handle has the points 0 .. %lld", (long long)t,
+                        (long long)point[t], (long long)(s->M - 1));
+    }
+    return GBRS_OK;
 }
 
-// An append drops what gbrs_scan_int_prepare made, its W included.
-void scan_int_unprepare(gbrs_scan *s) {
-    s->int_c = 0;
-    s->int_k = 0;
-    s->int_hpi = 0;
-    s->int_rank_full.clear();
-    s->int_rank_add.clear();
-    s->int_W.release();
+// the sample axis of every product operand: zero filled up to a multiple of the K chunk
+int64_t padded(int64_t n) { return (n + SC_KC - 1) / SC_KC * SC_KC; }
+
+// The buffers a pass allocates for itself go through its tally: resident_bytes() + own.bytes is the pass's peak, and a
+// buffer that only some calls need counts when it is there.
+struct Tally {
+    uint64_t bytes = 0;
+    template <typename T>
+    int alloc(DevBuf<T> &buf, size_t count) {
+        GBRS_TRY(buf.alloc(count));
+        bytes += buf.bytes();
+        return GBRS_OK;
+    }
+};
+
+// columns [col0, col0 + pc) of the host table [n][ld] to y [n][pc], on the handle's stream
+int upload_columns(gbrs_scan *s, DevBuf<double> &y, const double *table, int64_t ld, int64_t col0, int64_t pc) {
+    GBRS_HIP_CHECK(hipMemcpy2DAsync(y.p, (size_t)pc * sizeof(double), table + col0, (size_t)ld * sizeof(double),
+                                    (size_t)pc * sizeof(double), (size_t)s->cohort.n, hipMemcpyHostToDevice, s->stream));
+    return GBRS_OK;
 }
+
+// those columns with the covariates qz [n][c] projected out, transposed to yt [pc][n_ld], and their sums of squares to rss
+int project(gbrs_scan *s, const DevBuf<double> &qz, int c, int64_t n_ld, const double *table, int64_t ld, int64_t col0, int64_t pc,
+            DevBuf<double> &y, double *yt, double *rss) {
+    GBRS_TRY(upload_columns(s, y, table, ld, col0, pc));
+    hipLaunchKernelGGL(scan_pheno_kernel, dim3((unsigned)pc), dim3(64), 0, s->stream, (int)s->cohort.n, c, n_ld, pc, y.p, qz.p, yt, rss);
+    return GBRS_OK;
+}
+
+// y~ of every column of the table [n][P], by gbrs_scan_run's kernel in gbrs_scan_run's chunks: it stays on the device for
+// the pass as yt_all [P][n_ld] and rss_all [P]
+int project_all(gbrs_scan *s, const DevBuf<double> &qz, int c, int64_t n_ld, const double *table, int64_t P, DevBuf<double> &y,
+                DevBuf<double> &yt_all, DevBuf<double> &rss_all) {
+    for (int64_t p0 = 0; p0 < P; p0 += SC_PCHUNK) {
+        GBRS_TRY(project(s, qz, c, n_ld, table, P, p0, std::min(SC_PCHUNK, P - p0), y, yt_all.p + p0 * n_ld, rss_all.p + p0));
+        GBRS_HIP_CHECK(hipGetLastError());
+    }
+    return GBRS_OK;
+}
+
+// The pass-wide timed region of the handle's stream opens with a record of ev[0] ...
+int timed_open(gbrs_scan *s) {
+    GBRS_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
+    return GBRS_OK;
+}
+
+// ... and this closes it with ev[1] and waits for it.
+int timed_wait(gbrs_scan *s) {
+    GBRS_HIP_CHECK(hipEventRecord(s->ev[1], s->stream));
+    GBRS_HIP_CHECK(hipGetLastError());
+    GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
+    return GBRS_OK;
+}
+
+// device milliseconds between two events that were waited for; `unread` (0.0, or the time to keep) where they cannot be read
+double elapsed_ms(hipEvent_t from, hipEvent_t to, double unread) {
+    float ms = 0.f;
+    return hipEventElapsedTime(&ms, from, to) == hipSuccess ? ms : unread;
+}
+
+// the region of the handle's ev[0] and ev[1]
+double pass_ms(const gbrs_scan *s, double unread) { return elapsed_ms(s->ev[0], s->ev[1], unread); }
+
+// a few events of a call's own, for the parts of a chunk that a pass times where it waits for the chunk anyway
+struct Marks {
+    hipEvent_t ev[4] = {};
+    ~Marks() {
+        for (auto e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    int create() {
+        for (auto &e : ev) GBRS_HIP_CHECK(hipEventCreate(&e));
+        return GBRS_OK;
+    }
+};
 
 // Pairs of events around the product kernel of consecutive chunks, so that a pass times it without waiting per chunk: a
 // pair is read when its turn comes round again, and the rest after the pass.
@@ -516,6 +611,54 @@ struct EventRing {
         return GBRS_OK;
     }
 };
+
+// the first `count` elements of a result to the caller's array from element `at` on, where the caller asked for it
+template <typename T>
+int copy_out(T *dst, const DevBuf<T> &buf, size_t count, size_t at = 0) {
+    if (dst) GBRS_HIP_CHECK(hipMemcpy(dst + at, buf.p, count * sizeof(T), hipMemcpyDeviceToHost));
+    return GBRS_OK;
+}
+
+// The peaks of a SNP pass, [P][n_chrom], after the stream was waited for: NaN where a chromosome had no SNP in use.
+int snp_peaks_out(const DevBuf<double> &d_peak, const DevBuf<int64_t> &d_index, double *peak_lod, int64_t *peak_index) {
+    std::vector<double> h_peak(d_peak.n);
+    std::vector<int64_t> h_index(d_index.n);
+    GBRS_TRY(copy_out(h_peak.data(), d_peak, d_peak.n));
+    GBRS_TRY(copy_out(h_index.data(), d_index, d_index.n));
+    for (size_t k = 0; k < h_peak.size(); ++k)
+        if (h_index[k] < 0) h_peak[k] = std::numeric_limits<double>::quiet_NaN();
+    if (peak_lod) std::memcpy(peak_lod, h_peak.data(), h_peak.size() * sizeof(double));
+    if (peak_index) std::memcpy(peak_index, h_index.data(), h_index.size() * sizeof(int64_t));
+    return GBRS_OK;
+}
+
+// Room for `more` samples after the n in use; the samples in use move with the buffer.
+int scan_reserve(gbrs_scan *s, int64_t more) {
+    gbrs_scan::Cohort &co = s->cohort;
+    if (co.n + more <= co.capacity) return GBRS_OK;
+    const int64_t want = std::max(co.n + more, 2 * co.capacity);
+    const size_t row = (size_t)s->M * s->H;
+    DevBuf<double> grown;
+    GBRS_TRY(grown.alloc((size_t)want * row));
+    if (co.n > 0) {        // on the handle's stream and waited for: a device-to-device hipMemcpy need not be done when it returns
+        GBRS_HIP_CHECK(hipMemcpyAsync(grown.p, co.dosage.p, (size_t)co.n * row * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
+        GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
+    }
+    co.dosage.swap(grown);
+    co.capacity = want;
+    return GBRS_OK;
+}
+
+// `count` samples were copied behind the cohort: they count, and what was made from the cohort before them is dropped -
+// W, the kinship products with what gbrs_scan_lmm_prepare made, and what gbrs_scan_int_prepare made
+void scan_appended(gbrs_scan *s, int64_t count) {
+    s->cohort.n += count;
+    s->prep.unprepare();
+    s->lmm.unprepare();
+    s->kin.valid = false;
+    s->kin.S.release();
+    s->inter.unprepare();
+}
 
 }  // namespace
 
@@ -576,19 +719,16 @@ int gbrs_scan_append(gbrs_scan_t *s, int n, const double *dosage) {
     if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
     if (n < 0 || (n > 0 && !dosage)) return fail(GBRS_ERR_INVALID, "bad argument");
     if (n == 0) return GBRS_OK;
-    if (s->n + n > std::numeric_limits<int32_t>::max() / 16) return fail(GBRS_ERR_INVALID, "too many samples");
+    if (s->cohort.n + n > std::numeric_limits<int32_t>::max() / 16) return fail(GBRS_ERR_INVALID, "too many samples");
     const size_t row = (size_t)s->M * s->H;
     for (size_t k = 0; k < (size_t)n * row; ++k)
         if (!std::isfinite(dosage[k]))
             return fail(GBRS_ERR_INVALID, "dosage of sample %lld holds a value that is not finite (grid point %lld, founder %d)",
-                        (long long)(s->n + (int64_t)(k / row)), (long long)(k % row / s->H), (int)(k % s->H));
+                        (long long)(s->cohort.n + (int64_t)(k / row)), (long long)(k % row / s->H), (int)(k % s->H));
     GBRS_TRY(select_device(s->device));
     GBRS_TRY(scan_reserve(s, n));
-    GBRS_HIP_CHECK(hipMemcpy(s->dosage.p + (size_t)s->n * row, dosage, (size_t)n * row * sizeof(double), hipMemcpyHostToDevice));
-    s->n += n;
-    scan_unprepare(s);
-    scan_lmm_unprepare(s);
-    scan_int_unprepare(s);
+    GBRS_HIP_CHECK(hipMemcpy(s->cohort.dosage.p + (size_t)s->cohort.n * row, dosage, (size_t)n * row * sizeof(double), hipMemcpyHostToDevice));
+    scan_appended(s, n);
     return GBRS_OK;
 }
 
@@ -605,17 +745,14 @@ int gbrs_scan_append_hmm(gbrs_scan_t *s, gbrs_hmm_t *hmm, int sample) {
         if (view.points[c] != s->points[c])
             return fail(GBRS_ERR_INVALID, "grid mismatch: chromosome %d has %d grid points on the HMM handle, %d on the scan", c,
                         view.points[c], s->points[c]);
-    if (s->n + view.n > std::numeric_limits<int32_t>::max() / 16) return fail(GBRS_ERR_INVALID, "too many samples");
+    if (s->cohort.n + view.n > std::numeric_limits<int32_t>::max() / 16) return fail(GBRS_ERR_INVALID, "too many samples");
     GBRS_TRY(hmm_grid_view(hmm, sample, &view, true));
     GBRS_TRY(scan_reserve(s, view.n));
     const size_t row = (size_t)s->M * s->H;
-    GBRS_HIP_CHECK(hipMemcpyAsync(s->dosage.p + (size_t)s->n * row, view.dosage, (size_t)view.n * row * sizeof(double),
+    GBRS_HIP_CHECK(hipMemcpyAsync(s->cohort.dosage.p + (size_t)s->cohort.n * row, view.dosage, (size_t)view.n * row * sizeof(double),
                                   hipMemcpyDeviceToDevice, s->stream));
     GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
-    s->n += view.n;
-    scan_unprepare(s);
-    scan_lmm_unprepare(s);
-    scan_int_unprepare(s);
+    scan_appended(s, view.n);
     return GBRS_OK;
 }
 
@@ -624,39 +761,37 @@ int gbrs_scan_prepare(gbrs_scan_t *s, int c, const double *qz) {
     if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
     if (c < 1 || c > SC_MAX_C) return fail(GBRS_ERR_INVALID, "covariate columns must be 1..%d (the intercept included), got %d", SC_MAX_C, c);
     if (!qz) return fail(GBRS_ERR_INVALID, "qz is NULL");
-    if (s->n <= (int64_t)c + s->H - 1)
+    if (s->cohort.n <= (int64_t)c + s->H - 1)
         return fail(GBRS_ERR_INVALID, "%lld samples are too few for %d covariate columns and %d founders: need more than %d",
-                    (long long)s->n, c, s->H, c + s->H - 1);
-    const int n = (int)s->n;
+                    (long long)s->cohort.n, c, s->H, c + s->H - 1);
+    const int n = (int)s->cohort.n;
     for (int64_t k = 0; k < (int64_t)n * c; ++k)
         if (!std::isfinite(qz[k]))
             return fail(GBRS_ERR_INVALID, "covariate basis holds a value that is not finite (sample %lld, column %d)", (long long)(k / c),
                         (int)(k % c));
     GBRS_TRY(select_device(s->device));
-    scan_unprepare(s);                  // the arguments are good: from here on W is being overwritten
-    const int64_t n_ld = ((int64_t)n + SC_KC - 1) / SC_KC * SC_KC;
+    gbrs_scan::Prep &pr = s->prep;
+    pr.unprepare();                     // the arguments are good: from here on W is being overwritten
+    const int64_t n_ld = padded(n);
     const size_t n_w = (size_t)s->M * s->Hp * n_ld;
-    if (s->qz.n != (size_t)n * c) GBRS_TRY(s->qz.alloc((size_t)n * c));
-    if (s->W.n != n_w) GBRS_TRY(s->W.alloc(n_w));
-    if (s->d_rank.n != (size_t)s->M) GBRS_TRY(s->d_rank.alloc((size_t)s->M));
-    GBRS_HIP_CHECK(hipMemcpy(s->qz.p, qz, s->qz.bytes(), hipMemcpyHostToDevice));
-    GBRS_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
+    if (pr.qz.n != (size_t)n * c) GBRS_TRY(pr.qz.alloc((size_t)n * c));
+    if (pr.W.n != n_w) GBRS_TRY(pr.W.alloc(n_w));
+    if (pr.d_rank.n != (size_t)s->M) GBRS_TRY(pr.d_rank.alloc((size_t)s->M));
+    GBRS_HIP_CHECK(hipMemcpy(pr.qz.p, qz, pr.qz.bytes(), hipMemcpyHostToDevice));
+    GBRS_TRY(timed_open(s));
     auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3((unsigned)s->M), dim3(SC_THREADS), 0, s->stream, n, s->M, s->H, c, n_ld, s->dosage.p, s->qz.p,
-                           s->W.p, s->d_rank.p);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)s->M), dim3(SC_THREADS), 0, s->stream, n, s->M, s->H, c, n_ld, s->cohort.dosage.p, pr.qz.p,
+                           pr.W.p, pr.d_rank.p);
     };
     if (s->Hp == 8) launch(scan_prepare_kernel<8>);
     else launch(scan_prepare_kernel<16>);
-    GBRS_HIP_CHECK(hipEventRecord(s->ev[1], s->stream));
-    GBRS_HIP_CHECK(hipGetLastError());
-    GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) s->t_prepare = ms;
+    GBRS_TRY(timed_wait(s));
+    s->last.scan.last_prepare_ms = pass_ms(s, s->last.scan.last_prepare_ms);
     std::vector<int32_t> rank((size_t)s->M);
-    GBRS_HIP_CHECK(hipMemcpy(rank.data(), s->d_rank.p, s->d_rank.bytes(), hipMemcpyDeviceToHost));
-    s->rank.swap(rank);
-    s->n_ld = n_ld;
-    s->c = c;
+    GBRS_TRY(copy_out(rank.data(), pr.d_rank, pr.d_rank.n));
+    pr.rank.swap(rank);
+    pr.n_ld = n_ld;
+    pr.c = c;
     return GBRS_OK;
 }
 
@@ -664,74 +799,67 @@ int gbrs_scan_prepare(gbrs_scan_t *s, int c, const double *qz) {
 
 namespace {
 
+// a buffer of the handle's chunk that follows the last call's size
+template <typename T>
+int resized(DevBuf<T> &buf, size_t n) { return buf.n != n ? buf.alloc(n) : GBRS_OK; }
+
 // The pass of gbrs_scan_run.  With support, gbrs_scan_run_support's: the intervals of every chunk follow its peaks while
 // its LOD rows are on the device; the two tables of a chunk are the call's own, so the handle holds what it held.
 int scan_run_pass(gbrs_scan *s, int64_t P, const double *pheno, bool support, double drop, double *lod, double *peak_lod,
                   int64_t *peak_index, int64_t *support_lo, int64_t *support_hi) {
     if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
-    if (s->c == 0) return fail(GBRS_ERR_INVALID, "no covariates on the handle: call gbrs_scan_prepare first");
+    if (s->prep.c == 0) return fail(GBRS_ERR_INVALID, "no covariates on the handle: call gbrs_scan_prepare first");
     if (P < 1 || !pheno) return fail(GBRS_ERR_INVALID, "bad argument");
     if (support && !(drop >= 0.0 && std::isfinite(drop)))
         return fail(GBRS_ERR_INVALID, "the LOD drop of a support interval must be a finite number that is not negative, got %g", drop);
-    const int n = (int)s->n;
-    for (int64_t k = 0; k < (int64_t)n * P; ++k)
-        if (!std::isfinite(pheno[k]))
-            return fail(GBRS_ERR_INVALID, "phenotype %lld holds a value that is not finite (sample %lld)", (long long)(k % P),
-                        (long long)(k / P));
+    const int n = (int)s->cohort.n, nc = s->n_chrom;
+    GBRS_TRY(check_finite("phenotype", pheno, n, P));
     GBRS_TRY(select_device(s->device));
-    const int64_t pc_max = std::min(P, SC_PCHUNK), M = s->M, n_ld = s->n_ld;
-    if (s->y.n != (size_t)n * pc_max) GBRS_TRY(s->y.alloc((size_t)n * pc_max));
-    if (s->yt.n != (size_t)pc_max * n_ld) GBRS_TRY(s->yt.alloc((size_t)pc_max * n_ld));
-    if (s->rss0.n != (size_t)pc_max) GBRS_TRY(s->rss0.alloc((size_t)pc_max));
-    if (s->lod.n != (size_t)pc_max * M) GBRS_TRY(s->lod.alloc((size_t)pc_max * M));
-    if (s->peak_lod.n != (size_t)pc_max * s->n_chrom) GBRS_TRY(s->peak_lod.alloc((size_t)pc_max * s->n_chrom));
-    if (s->peak_index.n != (size_t)pc_max * s->n_chrom) GBRS_TRY(s->peak_index.alloc((size_t)pc_max * s->n_chrom));
+    gbrs_scan::Prep &pr = s->prep;
+    const int64_t pc_max = std::min(P, SC_PCHUNK), M = s->M, n_ld = pr.n_ld;
+    GBRS_TRY(resized(pr.y, (size_t)n * pc_max));
+    GBRS_TRY(resized(pr.yt, (size_t)pc_max * n_ld));
+    GBRS_TRY(resized(pr.rss0, (size_t)pc_max));
+    GBRS_TRY(resized(pr.lod, (size_t)pc_max * M));
+    GBRS_TRY(resized(pr.peak_lod, (size_t)pc_max * nc));
+    GBRS_TRY(resized(pr.peak_index, (size_t)pc_max * nc));
     DevBuf<int64_t> d_lo, d_hi;
     if (support) {
-        GBRS_TRY(d_lo.alloc((size_t)pc_max * s->n_chrom));
-        GBRS_TRY(d_hi.alloc((size_t)pc_max * s->n_chrom));
+        GBRS_TRY(d_lo.alloc((size_t)pc_max * nc));
+        GBRS_TRY(d_hi.alloc((size_t)pc_max * nc));
     }
     const unsigned row_blocks = (unsigned)((M * s->Hp + SC_ROWS - 1) / SC_ROWS);
     double t_product = 0.0;
-    GBRS_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
+    GBRS_TRY(timed_open(s));
     for (int64_t p0 = 0; p0 < P; p0 += SC_PCHUNK) {
         const int64_t pc = std::min(SC_PCHUNK, P - p0);
-        GBRS_HIP_CHECK(hipMemcpy2DAsync(s->y.p, (size_t)pc * sizeof(double), pheno + p0, (size_t)P * sizeof(double),
-                                        (size_t)pc * sizeof(double), (size_t)n, hipMemcpyHostToDevice, s->stream));
-        hipLaunchKernelGGL(scan_pheno_kernel, dim3((unsigned)pc), dim3(64), 0, s->stream, n, s->c, n_ld, pc, s->y.p, s->qz.p, s->yt.p,
-                           s->rss0.p);
+        const size_t peaks = (size_t)pc * nc;
+        GBRS_TRY(project(s, pr.qz, pr.c, n_ld, pheno, P, p0, pc, pr.y, pr.yt.p, pr.rss0.p));
         GBRS_HIP_CHECK(hipEventRecord(s->ev[2], s->stream));
         const dim3 grid(row_blocks, (unsigned)((pc + SC_COLS - 1) / SC_COLS));
         auto launch = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, grid, dim3(SC_THREADS), 0, s->stream, M, pc, n_ld, 0.5 * n, s->W.p, s->yt.p, s->rss0.p, s->lod.p);
+            hipLaunchKernelGGL(kernel, grid, dim3(SC_THREADS), 0, s->stream, M, pc, n_ld, 0.5 * n, pr.W.p, pr.yt.p, pr.rss0.p, pr.lod.p);
         };
         if (s->Hp == 8) launch(scan_lod_kernel<8>);
         else launch(scan_lod_kernel<16>);
         GBRS_HIP_CHECK(hipEventRecord(s->ev[3], s->stream));
-        hipLaunchKernelGGL(scan_peak_kernel, dim3((unsigned)s->n_chrom, (unsigned)pc), dim3(64), 0, s->stream, M, s->n_chrom,
-                           s->d_point_off.p, s->lod.p, s->peak_lod.p, s->peak_index.p);
+        hipLaunchKernelGGL(scan_peak_kernel, dim3((unsigned)nc, (unsigned)pc), dim3(64), 0, s->stream, M, nc, s->d_point_off.p, pr.lod.p,
+                           pr.peak_lod.p, pr.peak_index.p);
         if (support)
-            hipLaunchKernelGGL(scan_support_kernel, dim3((unsigned)s->n_chrom, (unsigned)pc), dim3(64), 0, s->stream, M, s->n_chrom,
-                               drop, s->d_point_off.p, s->lod.p, s->peak_lod.p, s->peak_index.p, d_lo.p, d_hi.p);
+            hipLaunchKernelGGL(scan_support_kernel, dim3((unsigned)nc, (unsigned)pc), dim3(64), 0, s->stream, M, nc, drop,
+                               s->d_point_off.p, pr.lod.p, pr.peak_lod.p, pr.peak_index.p, d_lo.p, d_hi.p);
         GBRS_HIP_CHECK(hipGetLastError());
         GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, s->ev[2], s->ev[3]) == hipSuccess) t_product += ms;
-        if (lod) GBRS_HIP_CHECK(hipMemcpy(lod + p0 * M, s->lod.p, (size_t)pc * M * sizeof(double), hipMemcpyDeviceToHost));
-        if (peak_lod)
-            GBRS_HIP_CHECK(hipMemcpy(peak_lod + p0 * s->n_chrom, s->peak_lod.p, (size_t)pc * s->n_chrom * sizeof(double), hipMemcpyDeviceToHost));
-        if (peak_index)
-            GBRS_HIP_CHECK(hipMemcpy(peak_index + p0 * s->n_chrom, s->peak_index.p, (size_t)pc * s->n_chrom * sizeof(int64_t), hipMemcpyDeviceToHost));
-        if (support_lo)
-            GBRS_HIP_CHECK(hipMemcpy(support_lo + p0 * s->n_chrom, d_lo.p, (size_t)pc * s->n_chrom * sizeof(int64_t), hipMemcpyDeviceToHost));
-        if (support_hi)
-            GBRS_HIP_CHECK(hipMemcpy(support_hi + p0 * s->n_chrom, d_hi.p, (size_t)pc * s->n_chrom * sizeof(int64_t), hipMemcpyDeviceToHost));
+        t_product += elapsed_ms(s->ev[2], s->ev[3], 0.0);
+        GBRS_TRY(copy_out(lod, pr.lod, (size_t)pc * M, (size_t)p0 * M));
+        GBRS_TRY(copy_out(peak_lod, pr.peak_lod, peaks, (size_t)p0 * nc));
+        GBRS_TRY(copy_out(peak_index, pr.peak_index, peaks, (size_t)p0 * nc));
+        GBRS_TRY(copy_out(support_lo, d_lo, peaks, (size_t)p0 * nc));
+        GBRS_TRY(copy_out(support_hi, d_hi, peaks, (size_t)p0 * nc));
     }
-    GBRS_HIP_CHECK(hipEventRecord(s->ev[1], s->stream));
-    GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) s->t_run = ms;
-    s->t_product = t_product;
+    GBRS_TRY(timed_wait(s));
+    s->last.scan.last_run_ms = pass_ms(s, s->last.scan.last_run_ms);
+    s->last.scan.last_product_ms = t_product;
     return GBRS_OK;
 }
 
@@ -754,55 +882,46 @@ int gbrs_scan_permute(gbrs_scan_t *s, int64_t P, const double *pheno, int64_t B,
                       double *perm_max, int32_t *perm_index) {
     RoctxRange roctx_range("gbrs_scan_permute");
     if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
-    if (s->c == 0) return fail(GBRS_ERR_INVALID, "no covariates on the handle: call gbrs_scan_prepare first");
+    if (s->prep.c == 0) return fail(GBRS_ERR_INVALID, "no covariates on the handle: call gbrs_scan_prepare first");
     if (P < 1) return fail(GBRS_ERR_INVALID, "a permutation pass needs at least 1 phenotype, got %lld", (long long)P);
     if (B < 1) return fail(GBRS_ERR_INVALID, "a permutation pass needs at least 1 permutation, got %lld", (long long)B);
     if (!pheno || !perm_max) return fail(GBRS_ERR_INVALID, "bad argument");
-    const int n = (int)s->n;
+    const int n = (int)s->cohort.n, nc = s->n_chrom;
     const int tiles = (n + SP_THREADS - 1) / SP_THREADS;
     if (B > std::numeric_limits<int32_t>::max() / tiles || P > std::numeric_limits<int64_t>::max() / 8 / B)
         return fail(GBRS_ERR_INVALID, "too many permutations: %lld of %d samples for %lld phenotypes", (long long)B, n, (long long)P);
     int64_t selected = 0;
-    for (int c = 0; c < s->n_chrom; ++c)
+    for (int c = 0; c < nc; ++c)
         if (!chrom_mask || chrom_mask[c]) selected += s->points[c];
     if (selected == 0) return fail(GBRS_ERR_INVALID, "the chromosome mask selects no grid point");
-    for (int64_t k = 0; k < (int64_t)n * P; ++k)
-        if (!std::isfinite(pheno[k]))
-            return fail(GBRS_ERR_INVALID, "phenotype %lld holds a value that is not finite (sample %lld)", (long long)(k % P),
-                        (long long)(k / P));
+    GBRS_TRY(check_finite("phenotype", pheno, n, P));
     GBRS_TRY(select_device(s->device));
-    const int64_t cols = P * B, pc_max = std::min(cols, SC_PCHUNK), yc_max = std::min(P, SC_PCHUNK), M = s->M, n_ld = s->n_ld;
+    const gbrs_scan::Prep &pr = s->prep;
+    const int64_t cols = P * B, pc_max = std::min(cols, SC_PCHUNK), yc_max = std::min(P, SC_PCHUNK), M = s->M, n_ld = pr.n_ld;
+    Tally own;
     DevBuf<double> y, yt_all, rss_all, yt, rss0, lod, peak_lod, pmax;
     DevBuf<int64_t> peak_index;
     DevBuf<int32_t> perm;
     DevBuf<uint8_t> mask;
-    GBRS_TRY(y.alloc((size_t)n * yc_max));
-    GBRS_TRY(yt_all.alloc((size_t)P * n_ld));
-    GBRS_TRY(rss_all.alloc((size_t)P));
-    GBRS_TRY(yt.alloc((size_t)pc_max * n_ld));
-    GBRS_TRY(rss0.alloc((size_t)pc_max));
-    GBRS_TRY(lod.alloc((size_t)pc_max * M));
-    GBRS_TRY(peak_lod.alloc((size_t)pc_max * s->n_chrom));
-    GBRS_TRY(peak_index.alloc((size_t)pc_max * s->n_chrom));
-    GBRS_TRY(pmax.alloc((size_t)cols));
-    GBRS_TRY(perm.alloc((size_t)B * n));
-    GBRS_TRY(mask.alloc((size_t)s->n_chrom));
-    std::vector<uint8_t> h_mask((size_t)s->n_chrom, 1);
+    GBRS_TRY(own.alloc(y, (size_t)n * yc_max));
+    GBRS_TRY(own.alloc(yt_all, (size_t)P * n_ld));
+    GBRS_TRY(own.alloc(rss_all, (size_t)P));
+    GBRS_TRY(own.alloc(yt, (size_t)pc_max * n_ld));
+    GBRS_TRY(own.alloc(rss0, (size_t)pc_max));
+    GBRS_TRY(own.alloc(lod, (size_t)pc_max * M));
+    GBRS_TRY(own.alloc(peak_lod, (size_t)pc_max * nc));
+    GBRS_TRY(own.alloc(peak_index, (size_t)pc_max * nc));
+    GBRS_TRY(own.alloc(pmax, (size_t)cols));
+    GBRS_TRY(own.alloc(perm, (size_t)B * n));
+    GBRS_TRY(own.alloc(mask, (size_t)nc));
+    std::vector<uint8_t> h_mask((size_t)nc, 1);
     if (chrom_mask)
-        for (int c = 0; c < s->n_chrom; ++c) h_mask[c] = chrom_mask[c] ? 1 : 0;
+        for (int c = 0; c < nc; ++c) h_mask[c] = chrom_mask[c] ? 1 : 0;
     GBRS_HIP_CHECK(hipMemcpy(mask.p, h_mask.data(), mask.bytes(), hipMemcpyHostToDevice));
     EventRing ring;
     GBRS_TRY(ring.create());
-    GBRS_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
-    // y~ of every phenotype, by gbrs_scan_run's kernel in gbrs_scan_run's chunks; it stays on the device for the pass
-    for (int64_t p0 = 0; p0 < P; p0 += SC_PCHUNK) {
-        const int64_t pc = std::min(SC_PCHUNK, P - p0);
-        GBRS_HIP_CHECK(hipMemcpy2DAsync(y.p, (size_t)pc * sizeof(double), pheno + p0, (size_t)P * sizeof(double),
-                                        (size_t)pc * sizeof(double), (size_t)n, hipMemcpyHostToDevice, s->stream));
-        hipLaunchKernelGGL(scan_pheno_kernel, dim3((unsigned)pc), dim3(64), 0, s->stream, n, s->c, n_ld, pc, y.p, s->qz.p,
-                           yt_all.p + p0 * n_ld, rss_all.p + p0);
-        GBRS_HIP_CHECK(hipGetLastError());
-    }
+    GBRS_TRY(timed_open(s));
+    GBRS_TRY(project_all(s, pr.qz, pr.c, n_ld, pheno, P, y, yt_all, rss_all));
     hipLaunchKernelGGL(scan_perm_rank_kernel, dim3((unsigned)(B * tiles)), dim3(SP_THREADS), 0, s->stream, n, tiles,
                        (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), perm.p);
     GBRS_HIP_CHECK(hipGetLastError());
@@ -811,46 +930,38 @@ int gbrs_scan_permute(gbrs_scan_t *s, int64_t P, const double *pheno, int64_t B,
         const int64_t pc = std::min(SC_PCHUNK, cols - col0);
         int slot = 0;
         GBRS_TRY(ring.next(&slot));
-        hipLaunchKernelGGL(scan_perm_pheno_kernel, dim3((unsigned)pc), dim3(64), 0, s->stream, n, s->c, n_ld, B, col0, yt_all.p,
-                           perm.p, s->qz.p, yt.p, rss0.p);
+        hipLaunchKernelGGL(scan_perm_pheno_kernel, dim3((unsigned)pc), dim3(64), 0, s->stream, n, pr.c, n_ld, B, col0, yt_all.p,
+                           perm.p, pr.qz.p, yt.p, rss0.p);
         GBRS_HIP_CHECK(hipEventRecord(ring.ev[2 * slot], s->stream));
         const dim3 grid(row_blocks, (unsigned)((pc + SC_COLS - 1) / SC_COLS));
         auto launch = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, grid, dim3(SC_THREADS), 0, s->stream, M, pc, n_ld, 0.5 * n, s->W.p, yt.p, rss0.p, lod.p);
+            hipLaunchKernelGGL(kernel, grid, dim3(SC_THREADS), 0, s->stream, M, pc, n_ld, 0.5 * n, pr.W.p, yt.p, rss0.p, lod.p);
         };
         if (s->Hp == 8) launch(scan_lod_kernel<8>);
         else launch(scan_lod_kernel<16>);
         GBRS_HIP_CHECK(hipEventRecord(ring.ev[2 * slot + 1], s->stream));
-        hipLaunchKernelGGL(scan_peak_kernel, dim3((unsigned)s->n_chrom, (unsigned)pc), dim3(64), 0, s->stream, M, s->n_chrom,
-                           s->d_point_off.p, lod.p, peak_lod.p, peak_index.p);
+        hipLaunchKernelGGL(scan_peak_kernel, dim3((unsigned)nc, (unsigned)pc), dim3(64), 0, s->stream, M, nc, s->d_point_off.p, lod.p,
+                           peak_lod.p, peak_index.p);
         hipLaunchKernelGGL(scan_perm_max_kernel, dim3((unsigned)((pc + SP_THREADS - 1) / SP_THREADS)), dim3(SP_THREADS), 0, s->stream,
-                           pc, s->n_chrom, s->d_point_off.p, mask.p, peak_lod.p, pmax.p + col0);
+                           pc, nc, s->d_point_off.p, mask.p, peak_lod.p, pmax.p + col0);
         GBRS_HIP_CHECK(hipGetLastError());
     }
-    GBRS_HIP_CHECK(hipEventRecord(s->ev[1], s->stream));
-    GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
+    GBRS_TRY(timed_wait(s));
     GBRS_TRY(ring.drain());
-    GBRS_HIP_CHECK(hipMemcpy(perm_max, pmax.p, pmax.bytes(), hipMemcpyDeviceToHost));
-    if (perm_index) GBRS_HIP_CHECK(hipMemcpy(perm_index, perm.p, perm.bytes(), hipMemcpyDeviceToHost));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) s->t_permute = ms;
-    s->t_perm_product = ring.ms;
-    s->perm_P = P;
-    s->perm_B = B;
-    s->perm_peak_bytes = s->d_point_off.bytes() + s->dosage.bytes() + s->qz.bytes() + s->W.bytes() + s->d_rank.bytes() + s->y.bytes() +
-                         s->yt.bytes() + s->rss0.bytes() + s->lod.bytes() + s->peak_lod.bytes() + s->peak_index.bytes() + y.bytes() +
-                         yt_all.bytes() + rss_all.bytes() + yt.bytes() + rss0.bytes() + lod.bytes() + peak_lod.bytes() +
-                         peak_index.bytes() + pmax.bytes() + perm.bytes() + mask.bytes();
+    GBRS_TRY(copy_out(perm_max, pmax, pmax.n));
+    GBRS_TRY(copy_out(perm_index, perm, perm.n));
+    gbrs_scan_perm_info_t &r = s->last.perm;
+    r.P = P;
+    r.B = B;
+    r.last_permute_ms = pass_ms(s, r.last_permute_ms);
+    r.last_product_ms = ring.ms;
+    r.peak_device_bytes = s->resident_bytes() + own.bytes;
     return GBRS_OK;
 }
 
 int gbrs_scan_perm_info(gbrs_scan_t *s, gbrs_scan_perm_info_t *info) {
     if (!s || !info) return fail(GBRS_ERR_INVALID, "bad argument");
-    info->P = s->perm_P;
-    info->B = s->perm_B;
-    info->last_permute_ms = s->t_permute;
-    info->last_product_ms = s->t_perm_product;
-    info->peak_device_bytes = s->perm_peak_bytes;
+    *info = s->last.perm;
     return GBRS_OK;
 }
 
@@ -866,13 +977,7 @@ int gbrs_scan_set_snps(gbrs_scan_t *s, const double *const *grid_pos, const int6
     }
     const int64_t M_snp = off[s->n_chrom];
     if (M_snp == 0) {                   // all-zero counts drop the SNPs
-        s->M_snp = 0;
-        s->snp_off.clear();
-        s->d_snp_off.release();
-        s->snp_lo.release();
-        s->snp_hi.release();
-        s->snp_mask.release();
-        s->snp_t.release();
+        s->snp.clear();
         return GBRS_OK;
     }
     if (!grid_pos || !snp_pos || !snp_mask) return fail(GBRS_ERR_INVALID, "bad argument");
@@ -927,36 +1032,36 @@ int gbrs_scan_set_snps(gbrs_scan_t *s, const double *const *grid_pos, const int6
                        M_snp, s->n_chrom, d_off.p, s->d_point_off.p, d_grid.p, d_pos.p, d_lo.p, d_hi.p, d_t.p);
     GBRS_HIP_CHECK(hipGetLastError());
     GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
-    s->d_snp_off.swap(d_off);
-    s->snp_lo.swap(d_lo);
-    s->snp_hi.swap(d_hi);
-    s->snp_mask.swap(d_mask);
-    s->snp_t.swap(d_t);
-    s->snp_off.swap(off);
-    s->M_snp = M_snp;
+    s->snp.d_off.swap(d_off);
+    s->snp.lo.swap(d_lo);
+    s->snp.hi.swap(d_hi);
+    s->snp.mask.swap(d_mask);
+    s->snp.t.swap(d_t);
+    s->snp.off.swap(off);
+    s->snp.M = M_snp;
     return GBRS_OK;
 }
 
 int gbrs_scan_snp_dosage(gbrs_scan_t *s, int64_t first, int64_t count, double *out) {
     RoctxRange roctx_range("gbrs_scan_snp_dosage");
     if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
-    if (s->M_snp == 0) return fail(GBRS_ERR_INVALID, "no SNPs on the handle: call gbrs_scan_set_snps first");
-    if (s->n == 0) return fail(GBRS_ERR_INVALID, "no samples on the handle");
-    if (first < 0 || count < 0 || first > s->M_snp || count > s->M_snp - first)
+    if (s->snp.M == 0) return fail(GBRS_ERR_INVALID, "no SNPs on the handle: call gbrs_scan_set_snps first");
+    if (s->cohort.n == 0) return fail(GBRS_ERR_INVALID, "no samples on the handle");
+    if (first < 0 || count < 0 || first > s->snp.M || count > s->snp.M - first)
         return fail(GBRS_ERR_INVALID, "SNPs %lld .. %lld are out of range: the handle has %lld", (long long)first,
-                    (long long)(first + count), (long long)s->M_snp);
+                    (long long)(first + count), (long long)s->snp.M);
     if (count == 0) return GBRS_OK;
     if (!out) return fail(GBRS_ERR_INVALID, "out is NULL");
     GBRS_TRY(select_device(s->device));
-    const int n = (int)s->n;
+    const int n = (int)s->cohort.n;
     const int64_t step = std::max<int64_t>(1, std::min(count, ((int64_t)1 << 24) / n));     // at most 128 MB of workspace
     DevBuf<double> buf;
     GBRS_TRY(buf.alloc((size_t)n * step));
     for (int64_t j0 = 0; j0 < count; j0 += step) {
         const int64_t jc = std::min(step, count - j0);
         hipLaunchKernelGGL(scan_snp_dosage_kernel, dim3((unsigned)((n * jc + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0,
-                           s->stream, n, s->M, s->H, first + j0, jc, s->dosage.p, s->snp_lo.p, s->snp_hi.p, s->snp_mask.p, s->snp_t.p,
-                           buf.p);
+                           s->stream, n, s->M, s->H, first + j0, jc, s->cohort.dosage.p, s->snp.lo.p, s->snp.hi.p, s->snp.mask.p,
+                           s->snp.t.p, buf.p);
         GBRS_HIP_CHECK(hipGetLastError());
         GBRS_HIP_CHECK(hipMemcpy2DAsync(out + j0, (size_t)count * sizeof(double), buf.p, (size_t)jc * sizeof(double),
                                         (size_t)jc * sizeof(double), (size_t)n, hipMemcpyDeviceToHost, s->stream));
@@ -969,17 +1074,16 @@ int gbrs_scan_snps(gbrs_scan_t *s, int64_t P, const double *pheno, double *lod, 
                    int64_t *peak_index) {
     RoctxRange roctx_range("gbrs_scan_snps");
     if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
-    if (s->c == 0) return fail(GBRS_ERR_INVALID, "no covariates on the handle: call gbrs_scan_prepare first");
-    if (s->M_snp == 0) return fail(GBRS_ERR_INVALID, "no SNPs on the handle: call gbrs_scan_set_snps first");
+    if (s->prep.c == 0) return fail(GBRS_ERR_INVALID, "no covariates on the handle: call gbrs_scan_prepare first");
+    if (s->snp.M == 0) return fail(GBRS_ERR_INVALID, "no SNPs on the handle: call gbrs_scan_set_snps first");
     if (P < 1) return fail(GBRS_ERR_INVALID, "a SNP pass needs at least 1 phenotype, got %lld", (long long)P);
     if (!pheno) return fail(GBRS_ERR_INVALID, "bad argument");
-    const int n = (int)s->n;
-    for (int64_t k = 0; k < (int64_t)n * P; ++k)
-        if (!std::isfinite(pheno[k]))
-            return fail(GBRS_ERR_INVALID, "phenotype %lld holds a value that is not finite (sample %lld)", (long long)(k % P),
-                        (long long)(k / P));
+    const int n = (int)s->cohort.n;
+    GBRS_TRY(check_finite("phenotype", pheno, n, P));
     GBRS_TRY(select_device(s->device));
-    const int64_t M_snp = s->M_snp, n_ld = s->n_ld, yc_max = std::min(P, SC_PCHUNK), lc_max = std::min(M_snp, SS_CHUNK);
+    const gbrs_scan::Prep &pr = s->prep;
+    const gbrs_scan::Snp &sn = s->snp;
+    const int64_t M_snp = sn.M, n_ld = pr.n_ld, yc_max = std::min(P, SC_PCHUNK), lc_max = std::min(M_snp, SS_CHUNK);
     const int nc = s->n_chrom;
     // the two points of a run in LDS when the device has the room
     int lds_max = 0;
@@ -989,39 +1093,32 @@ int gbrs_scan_snps(gbrs_scan_t *s, int64_t P, const double *pheno, double *lod, 
     if (staged)
         GBRS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(scan_snp_row_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                            (int)pair_bytes));
+    Tally own;
     DevBuf<double> y, yt_all, rss_all, w, d_lod, d_peak;
     DevBuf<int64_t> d_index;
     DevBuf<uint8_t> d_used;
-    GBRS_TRY(y.alloc((size_t)n * yc_max));
-    GBRS_TRY(yt_all.alloc((size_t)P * n_ld));
-    GBRS_TRY(rss_all.alloc((size_t)P));
-    GBRS_TRY(w.alloc((size_t)lc_max * n_ld));
-    GBRS_TRY(d_lod.alloc((size_t)yc_max * lc_max));
-    GBRS_TRY(d_used.alloc((size_t)lc_max));
-    GBRS_TRY(d_peak.alloc((size_t)P * nc));
-    GBRS_TRY(d_index.alloc((size_t)P * nc));
+    GBRS_TRY(own.alloc(y, (size_t)n * yc_max));
+    GBRS_TRY(own.alloc(yt_all, (size_t)P * n_ld));
+    GBRS_TRY(own.alloc(rss_all, (size_t)P));
+    GBRS_TRY(own.alloc(w, (size_t)lc_max * n_ld));
+    GBRS_TRY(own.alloc(d_lod, (size_t)yc_max * lc_max));
+    GBRS_TRY(own.alloc(d_used, (size_t)lc_max));
+    GBRS_TRY(own.alloc(d_peak, (size_t)P * nc));
+    GBRS_TRY(own.alloc(d_index, (size_t)P * nc));
     EventRing row_ring, product_ring;
     GBRS_TRY(row_ring.create());
     GBRS_TRY(product_ring.create());
-    GBRS_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
+    GBRS_TRY(timed_open(s));
     GBRS_HIP_CHECK(hipMemsetAsync(d_index.p, 0xFF, d_index.bytes(), s->stream));         // -1: nothing yet
-    // y~ of every phenotype, by gbrs_scan_run's kernel in gbrs_scan_run's chunks; it stays on the device for the pass
-    for (int64_t p0 = 0; p0 < P; p0 += SC_PCHUNK) {
-        const int64_t pc = std::min(SC_PCHUNK, P - p0);
-        GBRS_HIP_CHECK(hipMemcpy2DAsync(y.p, (size_t)pc * sizeof(double), pheno + p0, (size_t)P * sizeof(double),
-                                        (size_t)pc * sizeof(double), (size_t)n, hipMemcpyHostToDevice, s->stream));
-        hipLaunchKernelGGL(scan_pheno_kernel, dim3((unsigned)pc), dim3(64), 0, s->stream, n, s->c, n_ld, pc, y.p, s->qz.p,
-                           yt_all.p + p0 * n_ld, rss_all.p + p0);
-        GBRS_HIP_CHECK(hipGetLastError());
-    }
+    GBRS_TRY(project_all(s, pr.qz, pr.c, n_ld, pheno, P, y, yt_all, rss_all));
     for (int64_t j0 = 0; j0 < M_snp; j0 += SS_CHUNK) {
         const int64_t jc = std::min(SS_CHUNK, M_snp - j0);
         int slot = 0;
         GBRS_TRY(row_ring.next(&slot));
         GBRS_HIP_CHECK(hipEventRecord(row_ring.ev[2 * slot], s->stream));
         hipLaunchKernelGGL(scan_snp_row_kernel, dim3((unsigned)((jc + SS_BLOCK - 1) / SS_BLOCK)), dim3(SC_THREADS),
-                           staged ? pair_bytes : 0, s->stream, n, s->M, s->H, s->c, n_ld, j0, jc, staged, s->dosage.p, s->qz.p,
-                           s->snp_lo.p, s->snp_hi.p, s->snp_mask.p, s->snp_t.p, w.p, d_used.p);
+                           staged ? pair_bytes : 0, s->stream, n, s->M, s->H, pr.c, n_ld, j0, jc, staged, s->cohort.dosage.p, pr.qz.p,
+                           sn.lo.p, sn.hi.p, sn.mask.p, sn.t.p, w.p, d_used.p);
         GBRS_HIP_CHECK(hipEventRecord(row_ring.ev[2 * slot + 1], s->stream));
         GBRS_HIP_CHECK(hipGetLastError());
         if (used) GBRS_HIP_CHECK(hipMemcpyAsync(used + j0, d_used.p, (size_t)jc, hipMemcpyDeviceToHost, s->stream));
@@ -1034,7 +1131,7 @@ int gbrs_scan_snps(gbrs_scan_t *s, int64_t P, const double *pheno, double *lod, 
                                d_lod.p);
             GBRS_HIP_CHECK(hipEventRecord(product_ring.ev[2 * slot + 1], s->stream));
             hipLaunchKernelGGL(scan_snp_peak_kernel, dim3((unsigned)nc, (unsigned)pc), dim3(64), 0, s->stream, j0, jc, jc, nc,
-                               s->d_snp_off.p, d_used.p, d_lod.p, d_peak.p + p0 * nc, d_index.p + p0 * nc);
+                               sn.d_off.p, d_used.p, d_lod.p, d_peak.p + p0 * nc, d_index.p + p0 * nc);
             GBRS_HIP_CHECK(hipGetLastError());
             if (lod)        // waits for the kernels before it on the stream; the next chunk's product overwrites d_lod after it
                 GBRS_HIP_CHECK(hipMemcpy2DAsync(lod + p0 * M_snp + j0, (size_t)M_snp * sizeof(double), d_lod.p,
@@ -1042,42 +1139,26 @@ int gbrs_scan_snps(gbrs_scan_t *s, int64_t P, const double *pheno, double *lod, 
                                                 hipMemcpyDeviceToHost, s->stream));
         }
     }
-    GBRS_HIP_CHECK(hipEventRecord(s->ev[1], s->stream));
-    GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
+    GBRS_TRY(timed_wait(s));
     GBRS_TRY(row_ring.drain());
     GBRS_TRY(product_ring.drain());
-    std::vector<double> h_peak((size_t)P * nc);
-    std::vector<int64_t> h_index((size_t)P * nc);
-    GBRS_HIP_CHECK(hipMemcpy(h_peak.data(), d_peak.p, d_peak.bytes(), hipMemcpyDeviceToHost));
-    GBRS_HIP_CHECK(hipMemcpy(h_index.data(), d_index.p, d_index.bytes(), hipMemcpyDeviceToHost));
-    for (size_t k = 0; k < h_peak.size(); ++k)
-        if (h_index[k] < 0) h_peak[k] = std::numeric_limits<double>::quiet_NaN();
-    if (peak_lod) std::memcpy(peak_lod, h_peak.data(), h_peak.size() * sizeof(double));
-    if (peak_index) std::memcpy(peak_index, h_index.data(), h_index.size() * sizeof(int64_t));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) s->t_snp_pass = ms;
-    s->t_snp_row = row_ring.ms;
-    s->t_snp_product = product_ring.ms;
-    s->snp_P = P;
-    s->snp_staged = staged;
-    s->snp_peak_bytes = s->d_point_off.bytes() + s->dosage.bytes() + s->qz.bytes() + s->W.bytes() + s->d_rank.bytes() + s->y.bytes() +
-                        s->yt.bytes() + s->rss0.bytes() + s->lod.bytes() + s->peak_lod.bytes() + s->peak_index.bytes() + s->snp_bytes() +
-                        y.bytes() + yt_all.bytes() + rss_all.bytes() + w.bytes() + d_lod.bytes() + d_used.bytes() + d_peak.bytes() +
-                        d_index.bytes();
+    GBRS_TRY(snp_peaks_out(d_peak, d_index, peak_lod, peak_index));
+    gbrs_scan_snp_info_t &r = s->last.snp;
+    r.P = P;
+    r.staged = staged;
+    r.last_pass_ms = pass_ms(s, r.last_pass_ms);
+    r.last_row_ms = row_ring.ms;
+    r.last_product_ms = product_ring.ms;
+    r.peak_device_bytes = s->resident_bytes() + own.bytes;
     return GBRS_OK;
 }
 
 int gbrs_scan_snp_info(gbrs_scan_t *s, gbrs_scan_snp_info_t *info) {
     if (!s || !info) return fail(GBRS_ERR_INVALID, "bad argument");
-    info->M_snp = s->M_snp;
+    *info = s->last.snp;
+    info->M_snp = s->snp.M;
     info->chunk = SS_CHUNK;
-    info->P = s->snp_P;
-    info->staged = s->snp_staged;
-    info->last_pass_ms = s->t_snp_pass;
-    info->last_row_ms = s->t_snp_row;
-    info->last_product_ms = s->t_snp_product;
-    info->device_bytes = s->snp_bytes();
-    info->peak_device_bytes = s->snp_peak_bytes;
+    info->device_bytes = s->snp.bytes();
     return GBRS_OK;
 }
 
@@ -1086,71 +1167,54 @@ int gbrs_scan_mediate(gbrs_scan_t *s, int64_t T, const double *target, const int
                       double *sd, int64_t *n_used) {
     RoctxRange roctx_range("gbrs_scan_mediate");
     if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
-    if (s->c == 0) return fail(GBRS_ERR_INVALID, "no covariates on the handle: call gbrs_scan_prepare first");
+    if (s->prep.c == 0) return fail(GBRS_ERR_INVALID, "no covariates on the handle: call gbrs_scan_prepare first");
     if (T < 1) return fail(GBRS_ERR_INVALID, "a mediation pass needs at least 1 target, got %lld", (long long)T);
     if (Q < 1) return fail(GBRS_ERR_INVALID, "a mediation pass needs at least 1 mediator, got %lld", (long long)Q);
     if (K < 0 || K > SM_MAX_K) return fail(GBRS_ERR_INVALID, "the top list has 0..%d places, got %d", SM_MAX_K, K);
     if (!target || !point || !mediator || (K > 0 && (!best_lod || !best_index))) return fail(GBRS_ERR_INVALID, "bad argument");
-    if (s->n <= (int64_t)s->c + s->H)
+    const gbrs_scan::Prep &pr = s->prep;
+    if (s->cohort.n <= (int64_t)pr.c + s->H)
         return fail(GBRS_ERR_INVALID, "%lld samples are too few to mediate with %d covariate columns and %d founders: the mediator "
-                    "takes one more degree of freedom, need more than %d", (long long)s->n, s->c, s->H, s->c + s->H);
+                    "takes one more degree of freedom, need more than %d", (long long)s->cohort.n, pr.c, s->H, pr.c + s->H);
     if (Q > std::numeric_limits<int64_t>::max() / 16 / std::min(T, SM_TCHUNK) || (Q + SC_COLS - 1) / SC_COLS > std::numeric_limits<int32_t>::max())
         return fail(GBRS_ERR_INVALID, "too many mediators: %lld", (long long)Q);
-    for (int64_t t = 0; t < T; ++t)
-        if (point[t] < 0 || point[t] >= s->M)
-            return fail(GBRS_ERR_INVALID, "target %lld is at grid point %lld: the handle has the points 0 .. %lld", (long long)t,
-                        (long long)point[t], (long long)(s->M - 1));
-    const int n = (int)s->n;
-    for (int64_t k = 0; k < (int64_t)n * T; ++k)
-        if (!std::isfinite(target[k]))
-            return fail(GBRS_ERR_INVALID, "target %lld holds a value that is not finite (sample %lld)", (long long)(k % T),
-                        (long long)(k / T));
-    for (int64_t k = 0; k < (int64_t)n * Q; ++k)
-        if (!std::isfinite(mediator[k]))
-            return fail(GBRS_ERR_INVALID, "mediator %lld holds a value that is not finite (sample %lld)", (long long)(k % Q),
-                        (long long)(k / Q));
+    GBRS_TRY(check_targets(s, T, nullptr, 0, point));
+    const int n = (int)s->cohort.n;
+    GBRS_TRY(check_finite("target", target, n, T));
+    GBRS_TRY(check_finite("mediator", mediator, n, Q));
     GBRS_TRY(select_device(s->device));
-    const int64_t n_ld = s->n_ld, tc_max = std::min(T, SM_TCHUNK), yc_max = std::max(std::min(Q, SC_PCHUNK), tc_max);
+    const int64_t n_ld = pr.n_ld, tc_max = std::min(T, SM_TCHUNK), yc_max = std::max(std::min(Q, SC_PCHUNK), tc_max);
     const int Hp = s->Hp, pts = SC_ROWS / Hp;
+    Tally own;
     DevBuf<double> y, zt, szz, yt, syy, a, rss1, d_lod0, d_lod, d_best, d_mean, d_sd;
     DevBuf<int64_t> d_point, d_index, d_count;
     DevBuf<uint8_t> d_used;
-    GBRS_TRY(y.alloc((size_t)n * yc_max));
-    GBRS_TRY(zt.alloc((size_t)Q * n_ld));
-    GBRS_TRY(szz.alloc((size_t)Q));
-    GBRS_TRY(yt.alloc((size_t)tc_max * n_ld));
-    GBRS_TRY(syy.alloc((size_t)tc_max));
-    GBRS_TRY(a.alloc((size_t)tc_max * Hp));
-    GBRS_TRY(rss1.alloc((size_t)tc_max));
-    GBRS_TRY(d_lod0.alloc((size_t)T));
-    GBRS_TRY(d_lod.alloc((size_t)tc_max * Q));
-    GBRS_TRY(d_used.alloc((size_t)tc_max * Q));
-    GBRS_TRY(d_best.alloc((size_t)T * K));
-    GBRS_TRY(d_index.alloc((size_t)T * K));
-    GBRS_TRY(d_mean.alloc((size_t)T));
-    GBRS_TRY(d_sd.alloc((size_t)T));
-    GBRS_TRY(d_count.alloc((size_t)T));
-    GBRS_TRY(d_point.alloc((size_t)T));
+    GBRS_TRY(own.alloc(y, (size_t)n * yc_max));
+    GBRS_TRY(own.alloc(zt, (size_t)Q * n_ld));
+    GBRS_TRY(own.alloc(szz, (size_t)Q));
+    GBRS_TRY(own.alloc(yt, (size_t)tc_max * n_ld));
+    GBRS_TRY(own.alloc(syy, (size_t)tc_max));
+    GBRS_TRY(own.alloc(a, (size_t)tc_max * Hp));
+    GBRS_TRY(own.alloc(rss1, (size_t)tc_max));
+    GBRS_TRY(own.alloc(d_lod0, (size_t)T));
+    GBRS_TRY(own.alloc(d_lod, (size_t)tc_max * Q));
+    GBRS_TRY(own.alloc(d_used, (size_t)tc_max * Q));
+    GBRS_TRY(own.alloc(d_best, (size_t)T * K));
+    GBRS_TRY(own.alloc(d_index, (size_t)T * K));
+    GBRS_TRY(own.alloc(d_mean, (size_t)T));
+    GBRS_TRY(own.alloc(d_sd, (size_t)T));
+    GBRS_TRY(own.alloc(d_count, (size_t)T));
+    GBRS_TRY(own.alloc(d_point, (size_t)T));
     GBRS_HIP_CHECK(hipMemcpy(d_point.p, point, d_point.bytes(), hipMemcpyHostToDevice));
     EventRing ring;
     GBRS_TRY(ring.create());
-    GBRS_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
-    // z~ of every mediator, by gbrs_scan_run's kernel in gbrs_scan_run's chunks; it stays on the device for the pass
-    for (int64_t q0 = 0; q0 < Q; q0 += SC_PCHUNK) {
-        const int64_t qc = std::min(SC_PCHUNK, Q - q0);
-        GBRS_HIP_CHECK(hipMemcpy2DAsync(y.p, (size_t)qc * sizeof(double), mediator + q0, (size_t)Q * sizeof(double),
-                                        (size_t)qc * sizeof(double), (size_t)n, hipMemcpyHostToDevice, s->stream));
-        hipLaunchKernelGGL(scan_pheno_kernel, dim3((unsigned)qc), dim3(64), 0, s->stream, n, s->c, n_ld, qc, y.p, s->qz.p,
-                           zt.p + q0 * n_ld, szz.p + q0);
-        GBRS_HIP_CHECK(hipGetLastError());
-    }
+    GBRS_TRY(timed_open(s));
+    GBRS_TRY(project_all(s, pr.qz, pr.c, n_ld, mediator, Q, y, zt, szz));            // z~ of every mediator
     for (int64_t t0 = 0; t0 < T; t0 += SM_TCHUNK) {
         const int64_t tc = std::min(SM_TCHUNK, T - t0);
-        GBRS_HIP_CHECK(hipMemcpy2DAsync(y.p, (size_t)tc * sizeof(double), target + t0, (size_t)T * sizeof(double),
-                                        (size_t)tc * sizeof(double), (size_t)n, hipMemcpyHostToDevice, s->stream));
-        hipLaunchKernelGGL(scan_pheno_kernel, dim3((unsigned)tc), dim3(64), 0, s->stream, n, s->c, n_ld, tc, y.p, s->qz.p, yt.p, syy.p);
+        GBRS_TRY(project(s, pr.qz, pr.c, n_ld, target, T, t0, tc, y, yt.p, syy.p));
         auto targets = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, dim3((unsigned)tc), dim3(64), 0, s->stream, n_ld, 0.5 * n, s->W.p, d_point.p + t0, yt.p, syy.p,
+            hipLaunchKernelGGL(kernel, dim3((unsigned)tc), dim3(64), 0, s->stream, n_ld, 0.5 * n, pr.W.p, d_point.p + t0, yt.p, syy.p,
                                a.p, rss1.p, d_lod0.p + t0);
         };
         if (Hp == 8) targets(scan_med_target_kernel<8>);
@@ -1160,7 +1224,7 @@ int gbrs_scan_mediate(gbrs_scan_t *s, int64_t T, const double *target, const int
         GBRS_HIP_CHECK(hipEventRecord(ring.ev[2 * slot], s->stream));
         const dim3 grid((unsigned)((Q + SC_COLS - 1) / SC_COLS), (unsigned)((tc + pts - 1) / pts));
         auto product = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, grid, dim3(SC_THREADS), 0, s->stream, tc, Q, n_ld, 0.5 * n, s->W.p, d_point.p + t0, yt.p, zt.p,
+            hipLaunchKernelGGL(kernel, grid, dim3(SC_THREADS), 0, s->stream, tc, Q, n_ld, 0.5 * n, pr.W.p, d_point.p + t0, yt.p, zt.p,
                                syy.p, rss1.p, a.p, szz.p, d_lod.p, d_used.p);
         };
         if (Hp == 8) product(scan_med_kernel<8>);
@@ -1174,37 +1238,28 @@ int gbrs_scan_mediate(gbrs_scan_t *s, int64_t T, const double *target, const int
             GBRS_HIP_CHECK(hipMemcpyAsync(lod_med + t0 * Q, d_lod.p, (size_t)tc * Q * sizeof(double), hipMemcpyDeviceToHost, s->stream));
         if (used) GBRS_HIP_CHECK(hipMemcpyAsync(used + t0 * Q, d_used.p, (size_t)tc * Q, hipMemcpyDeviceToHost, s->stream));
     }
-    GBRS_HIP_CHECK(hipEventRecord(s->ev[1], s->stream));
-    GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
+    GBRS_TRY(timed_wait(s));
     GBRS_TRY(ring.drain());
-    if (lod0) GBRS_HIP_CHECK(hipMemcpy(lod0, d_lod0.p, d_lod0.bytes(), hipMemcpyDeviceToHost));
+    GBRS_TRY(copy_out(lod0, d_lod0, d_lod0.n));
     if (K > 0) {
-        GBRS_HIP_CHECK(hipMemcpy(best_lod, d_best.p, d_best.bytes(), hipMemcpyDeviceToHost));
-        GBRS_HIP_CHECK(hipMemcpy(best_index, d_index.p, d_index.bytes(), hipMemcpyDeviceToHost));
+        GBRS_TRY(copy_out(best_lod, d_best, d_best.n));
+        GBRS_TRY(copy_out(best_index, d_index, d_index.n));
     }
-    if (mean) GBRS_HIP_CHECK(hipMemcpy(mean, d_mean.p, d_mean.bytes(), hipMemcpyDeviceToHost));
-    if (sd) GBRS_HIP_CHECK(hipMemcpy(sd, d_sd.p, d_sd.bytes(), hipMemcpyDeviceToHost));
-    if (n_used) GBRS_HIP_CHECK(hipMemcpy(n_used, d_count.p, d_count.bytes(), hipMemcpyDeviceToHost));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) s->t_med_pass = ms;
-    s->t_med_product = ring.ms;
-    s->med_T = T;
-    s->med_Q = Q;
-    s->med_peak_bytes = s->d_point_off.bytes() + s->dosage.bytes() + s->qz.bytes() + s->W.bytes() + s->d_rank.bytes() + s->y.bytes() +
-                        s->yt.bytes() + s->rss0.bytes() + s->lod.bytes() + s->peak_lod.bytes() + s->peak_index.bytes() + s->snp_bytes() +
-                        y.bytes() + zt.bytes() + szz.bytes() + yt.bytes() + syy.bytes() + a.bytes() + rss1.bytes() + d_lod0.bytes() +
-                        d_lod.bytes() + d_used.bytes() + d_best.bytes() + d_index.bytes() + d_mean.bytes() + d_sd.bytes() +
-                        d_count.bytes() + d_point.bytes();
+    GBRS_TRY(copy_out(mean, d_mean, d_mean.n));
+    GBRS_TRY(copy_out(sd, d_sd, d_sd.n));
+    GBRS_TRY(copy_out(n_used, d_count, d_count.n));
+    gbrs_scan_mediate_info_t &r = s->last.mediate;
+    r.T = T;
+    r.Q = Q;
+    r.last_pass_ms = pass_ms(s, r.last_pass_ms);
+    r.last_product_ms = ring.ms;
+    r.peak_device_bytes = s->resident_bytes() + own.bytes;
     return GBRS_OK;
 }
 
 int gbrs_scan_mediate_info(gbrs_scan_t *s, gbrs_scan_mediate_info_t *info) {
     if (!s || !info) return fail(GBRS_ERR_INVALID, "bad argument");
-    info->T = s->med_T;
-    info->Q = s->med_Q;
-    info->last_pass_ms = s->t_med_pass;
-    info->last_product_ms = s->t_med_product;
-    info->peak_device_bytes = s->med_peak_bytes;
+    *info = s->last.mediate;
     return GBRS_OK;
 }
 
@@ -1212,50 +1267,34 @@ int gbrs_scan_effects(gbrs_scan_t *s, int64_t P, const double *pheno, int64_t T,
                       double *effect, double *se, double *lod, double *sigma2, int32_t *rank) {
     RoctxRange roctx_range("gbrs_scan_effects");
     if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
-    if (s->c == 0) return fail(GBRS_ERR_INVALID, "no covariates on the handle: call gbrs_scan_prepare first");
+    if (s->prep.c == 0) return fail(GBRS_ERR_INVALID, "no covariates on the handle: call gbrs_scan_prepare first");
     if (P < 1) return fail(GBRS_ERR_INVALID, "an effects pass needs at least 1 phenotype, got %lld", (long long)P);
     if (T < 1) return fail(GBRS_ERR_INVALID, "an effects pass needs at least 1 target, got %lld", (long long)T);
     if (!pheno || !column || !point) return fail(GBRS_ERR_INVALID, "bad argument");
-    for (int64_t t = 0; t < T; ++t) {
-        if (column[t] < 0 || column[t] >= P)
-            return fail(GBRS_ERR_INVALID, "target %lld is phenotype column %lld: the table has the columns 0 .. %lld", (long long)t,
-                        (long long)column[t], (long long)(P - 1));
-        if (point[t] < 0 || point[t] >= s->M)
-            return fail(GBRS_ERR_INVALID, "target %lld is at grid point %lld: the handle has the points 0 .. %lld", (long long)t,
-                        (long long)point[t], (long long)(s->M - 1));
-    }
-    const int n = (int)s->n;
-    for (int64_t k = 0; k < (int64_t)n * P; ++k)
-        if (!std::isfinite(pheno[k]))
-            return fail(GBRS_ERR_INVALID, "phenotype %lld holds a value that is not finite (sample %lld)", (long long)(k % P),
-                        (long long)(k / P));
+    GBRS_TRY(check_targets(s, T, column, P, point));
+    const int n = (int)s->cohort.n;
+    GBRS_TRY(check_finite("phenotype", pheno, n, P));
     GBRS_TRY(select_device(s->device));
-    const int64_t n_ld = s->n_ld, tc_max = std::min(T, SE_TCHUNK), yc_max = std::min(P, SC_PCHUNK);
+    const gbrs_scan::Prep &pr = s->prep;
+    const int64_t n_ld = pr.n_ld, tc_max = std::min(T, SE_TCHUNK), yc_max = std::min(P, SC_PCHUNK);
     const int H = s->H, Hp = s->Hp;
+    Tally own;
     DevBuf<double> y, yt_all, rss_all, x, d_effect, d_se, d_lod, d_sigma2;
     DevBuf<int64_t> d_column, d_point;
     DevBuf<int32_t> d_rank;
-    GBRS_TRY(y.alloc((size_t)n * yc_max));
-    GBRS_TRY(yt_all.alloc((size_t)P * n_ld));
-    GBRS_TRY(rss_all.alloc((size_t)P));
-    GBRS_TRY(x.alloc((size_t)tc_max * Hp * n_ld));
-    GBRS_TRY(d_effect.alloc((size_t)tc_max * H));
-    GBRS_TRY(d_se.alloc((size_t)tc_max * H));
-    GBRS_TRY(d_lod.alloc((size_t)tc_max));
-    GBRS_TRY(d_sigma2.alloc((size_t)tc_max));
-    GBRS_TRY(d_column.alloc((size_t)tc_max));
-    GBRS_TRY(d_point.alloc((size_t)tc_max));
-    GBRS_TRY(d_rank.alloc((size_t)tc_max));
-    GBRS_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
-    // y~ of every phenotype, by gbrs_scan_run's kernel in gbrs_scan_run's chunks; it stays on the device for the pass
-    for (int64_t p0 = 0; p0 < P; p0 += SC_PCHUNK) {
-        const int64_t pc = std::min(SC_PCHUNK, P - p0);
-        GBRS_HIP_CHECK(hipMemcpy2DAsync(y.p, (size_t)pc * sizeof(double), pheno + p0, (size_t)P * sizeof(double),
-                                        (size_t)pc * sizeof(double), (size_t)n, hipMemcpyHostToDevice, s->stream));
-        hipLaunchKernelGGL(scan_pheno_kernel, dim3((unsigned)pc), dim3(64), 0, s->stream, n, s->c, n_ld, pc, y.p, s->qz.p,
-                           yt_all.p + p0 * n_ld, rss_all.p + p0);
-        GBRS_HIP_CHECK(hipGetLastError());
-    }
+    GBRS_TRY(own.alloc(y, (size_t)n * yc_max));
+    GBRS_TRY(own.alloc(yt_all, (size_t)P * n_ld));
+    GBRS_TRY(own.alloc(rss_all, (size_t)P));
+    GBRS_TRY(own.alloc(x, (size_t)tc_max * Hp * n_ld));
+    GBRS_TRY(own.alloc(d_effect, (size_t)tc_max * H));
+    GBRS_TRY(own.alloc(d_se, (size_t)tc_max * H));
+    GBRS_TRY(own.alloc(d_lod, (size_t)tc_max));
+    GBRS_TRY(own.alloc(d_sigma2, (size_t)tc_max));
+    GBRS_TRY(own.alloc(d_column, (size_t)tc_max));
+    GBRS_TRY(own.alloc(d_point, (size_t)tc_max));
+    GBRS_TRY(own.alloc(d_rank, (size_t)tc_max));
+    GBRS_TRY(timed_open(s));
+    GBRS_TRY(project_all(s, pr.qz, pr.c, n_ld, pheno, P, y, yt_all, rss_all));
     // the results of a chunk come to the host before the next chunk's kernel overwrites them: the stream orders the two
     std::vector<double> h_effect(effect ? (size_t)T * H : 0), h_se(se ? (size_t)T * H : 0), h_lod(lod ? (size_t)T : 0),
         h_sigma2(sigma2 ? (size_t)T : 0);
@@ -1265,8 +1304,8 @@ int gbrs_scan_effects(gbrs_scan_t *s, int64_t P, const double *pheno, int64_t T,
         GBRS_HIP_CHECK(hipMemcpyAsync(d_column.p, column + t0, (size_t)tc * sizeof(int64_t), hipMemcpyHostToDevice, s->stream));
         GBRS_HIP_CHECK(hipMemcpyAsync(d_point.p, point + t0, (size_t)tc * sizeof(int64_t), hipMemcpyHostToDevice, s->stream));
         auto launch = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, dim3((unsigned)tc), dim3(SC_THREADS), 0, s->stream, n, s->M, H, s->c, n_ld, 0.5 * n, s->dosage.p,
-                               s->qz.p, s->W.p, s->d_rank.p, d_column.p, d_point.p, yt_all.p, rss_all.p, x.p, d_effect.p, d_se.p,
+            hipLaunchKernelGGL(kernel, dim3((unsigned)tc), dim3(SC_THREADS), 0, s->stream, n, s->M, H, pr.c, n_ld, 0.5 * n, s->cohort.dosage.p,
+                               pr.qz.p, pr.W.p, pr.d_rank.p, d_column.p, d_point.p, yt_all.p, rss_all.p, x.p, d_effect.p, d_se.p,
                                d_lod.p, d_sigma2.p, d_rank.p);
         };
         if (Hp == 8) launch(scan_effects_kernel<8>);
@@ -1278,48 +1317,38 @@ int gbrs_scan_effects(gbrs_scan_t *s, int64_t P, const double *pheno, int64_t T,
         if (sigma2) GBRS_HIP_CHECK(hipMemcpyAsync(h_sigma2.data() + t0, d_sigma2.p, (size_t)tc * sizeof(double), hipMemcpyDeviceToHost, s->stream));
         if (rank) GBRS_HIP_CHECK(hipMemcpyAsync(h_rank.data() + t0, d_rank.p, (size_t)tc * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
     }
-    GBRS_HIP_CHECK(hipEventRecord(s->ev[1], s->stream));
-    GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
+    GBRS_TRY(timed_wait(s));
     // the caller's arrays are written once the whole pass has succeeded
     if (effect) std::memcpy(effect, h_effect.data(), h_effect.size() * sizeof(double));
     if (se) std::memcpy(se, h_se.data(), h_se.size() * sizeof(double));
     if (lod) std::memcpy(lod, h_lod.data(), h_lod.size() * sizeof(double));
     if (sigma2) std::memcpy(sigma2, h_sigma2.data(), h_sigma2.size() * sizeof(double));
     if (rank) std::memcpy(rank, h_rank.data(), h_rank.size() * sizeof(int32_t));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) s->t_eff_pass = ms;
-    s->eff_T = T;
-    s->eff_P = P;
-    s->eff_peak_bytes = s->d_point_off.bytes() + s->dosage.bytes() + s->qz.bytes() + s->W.bytes() + s->d_rank.bytes() + s->y.bytes() +
-                        s->yt.bytes() + s->rss0.bytes() + s->lod.bytes() + s->peak_lod.bytes() + s->peak_index.bytes() + s->snp_bytes() +
-                        y.bytes() + yt_all.bytes() + rss_all.bytes() + x.bytes() + d_effect.bytes() + d_se.bytes() + d_lod.bytes() +
-                        d_sigma2.bytes() + d_column.bytes() + d_point.bytes() + d_rank.bytes();
+    gbrs_scan_effects_info_t &r = s->last.effects;
+    r.T = T;
+    r.P = P;
+    r.last_pass_ms = pass_ms(s, r.last_pass_ms);
+    r.peak_device_bytes = s->resident_bytes() + own.bytes;
     return GBRS_OK;
 }
 
 int gbrs_scan_effects_info(gbrs_scan_t *s, gbrs_scan_effects_info_t *info) {
     if (!s || !info) return fail(GBRS_ERR_INVALID, "bad argument");
-    info->T = s->eff_T;
-    info->P = s->eff_P;
-    info->last_pass_ms = s->t_eff_pass;
-    info->peak_device_bytes = s->eff_peak_bytes;
+    *info = s->last.effects;
     return GBRS_OK;
 }
 
 int gbrs_scan_info(gbrs_scan_t *s, gbrs_scan_info_t *info, int32_t *rank) {
     if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
     if (info) {
-        info->n = s->n;
+        *info = s->last.scan;
+        info->n = s->cohort.n;
         info->M = s->M;
         info->H = s->H;
-        info->c = s->c;
-        info->last_prepare_ms = s->t_prepare;
-        info->last_run_ms = s->t_run;
-        info->last_product_ms = s->t_product;
-        info->device_bytes = s->d_point_off.bytes() + s->dosage.bytes() + s->qz.bytes() + s->W.bytes() + s->d_rank.bytes() +
-                             s->y.bytes() + s->yt.bytes() + s->rss0.bytes() + s->lod.bytes() + s->peak_lod.bytes() + s->peak_index.bytes();
+        info->c = s->prep.c;
+        info->device_bytes = s->scan_bytes();
     }
-    if (rank && s->c > 0) std::memcpy(rank, s->rank.data(), s->rank.size() * sizeof(int32_t));
+    if (rank && s->prep.c > 0) std::memcpy(rank, s->prep.rank.data(), s->prep.rank.size() * sizeof(int32_t));
     return GBRS_OK;
 }
 
@@ -1331,21 +1360,21 @@ namespace {
 
 // S_c of every chromosome, once per cohort: kept on the handle until the next append.
 int scan_kinship_products(gbrs_scan *s) {
-    if (s->kin_valid) return GBRS_OK;
-    const int n = (int)s->n;
+    if (s->kin.valid) return GBRS_OK;
+    const int n = (int)s->cohort.n;
     const int64_t ld = s->M * s->H;
-    GBRS_TRY(s->kin_S.alloc((size_t)s->n_chrom * n * n));
+    GBRS_TRY(s->kin.S.alloc((size_t)s->n_chrom * n * n));
     bool vec2 = ld % 2 == 0;
     for (int c = 0; c < s->n_chrom; ++c) vec2 = vec2 && s->point_off[c] * s->H % 2 == 0;
     const unsigned blocks = (unsigned)((n + SC_ROWS - 1) / SC_ROWS);
     auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3(blocks, blocks, (unsigned)s->n_chrom), dim3(SC_THREADS), 0, s->stream, n, s->H, ld,
-                           s->d_point_off.p, s->dosage.p, s->kin_S.p);
+                           s->d_point_off.p, s->cohort.dosage.p, s->kin.S.p);
     };
     if (vec2) launch(lmm_kinship_kernel<true>);
     else launch(lmm_kinship_kernel<false>);
     GBRS_HIP_CHECK(hipGetLastError());
-    s->kin_valid = true;
+    s->kin.valid = true;
     return GBRS_OK;
 }
 
@@ -1354,8 +1383,63 @@ void scan_lmm_rotate(gbrs_scan *s, int64_t n_ld, int64_t rows, int HP, int keep,
                      const double *src, double *out) {
     if (rows == 0) return;
     const dim3 grid((unsigned)((rows + 63) / 64), (unsigned)((n_ld + 63) / 64));
-    hipLaunchKernelGGL(lmm_rotate_kernel, grid, dim3(SC_THREADS), 0, s->stream, (int)s->n, n_ld, rows, HP, keep, hs, ld_s, U, src, out);
+    hipLaunchKernelGGL(lmm_rotate_kernel, grid, dim3(SC_THREADS), 0, s->stream, (int)s->cohort.n, n_ld, rows, HP, keep, hs, ld_s, U, src,
+                       out);
 }
+
+// One chunk of the mixed model's null fits, as its three passes share it: up to pc_max phenotype columns, their rotation by
+// every decomposition and what lmm_null_kernel leaves for every (column, decomposition).  The buffers are the call's own.
+struct LmmNull {
+    DevBuf<double> y, ys, d_hin, d_hsq, d_sigma2, sw, qz, yt, rss0;
+    DevBuf<int32_t> d_rmin, d_rmax;
+
+    // d_hin only where the caller gives heritabilities
+    int alloc(Tally &own, const gbrs_scan *s, int64_t pc_max, bool given) {
+        const size_t pe = (size_t)pc_max * s->lmm.n_eig, n_ld = (size_t)s->lmm.n_ld;
+        GBRS_TRY(own.alloc(y, (size_t)s->cohort.n * pc_max));
+        GBRS_TRY(own.alloc(ys, pe * n_ld));
+        if (given) GBRS_TRY(own.alloc(d_hin, pe));
+        GBRS_TRY(own.alloc(d_hsq, pe));
+        GBRS_TRY(own.alloc(d_sigma2, pe));
+        GBRS_TRY(own.alloc(sw, pe * n_ld));
+        GBRS_TRY(own.alloc(qz, pe * s->lmm.cz * n_ld));
+        GBRS_TRY(own.alloc(yt, pe * n_ld));
+        GBRS_TRY(own.alloc(rss0, pe));
+        GBRS_TRY(own.alloc(d_rmin, (size_t)pc_max));
+        GBRS_TRY(own.alloc(d_rmax, (size_t)pc_max));
+        return GBRS_OK;
+    }
+
+    // Columns [p0, p0 + pc) of the host table [n][ld], with their rows of hsq_in [ld][n_eig] where given: uploads,
+    // rotations, lmm_null_kernel.  The passes time this differently (gbrs_hip.h), so each brings its events, both
+    // nullable: `uploaded` is recorded before the rotations and `rotated` before the null kernel; the end is the caller's.
+    int fit(gbrs_scan *s, const double *table, int64_t ld, const double *hsq_in, int64_t p0, int64_t pc, hipEvent_t uploaded,
+            hipEvent_t rotated) {
+        const gbrs_scan::Lmm &lm = s->lmm;
+        const int n = (int)s->cohort.n;
+        GBRS_TRY(upload_columns(s, y, table, ld, p0, pc));
+        if (hsq_in)
+            GBRS_HIP_CHECK(hipMemcpyAsync(d_hin.p, hsq_in + p0 * lm.n_eig, (size_t)pc * lm.n_eig * sizeof(double), hipMemcpyHostToDevice, s->stream));
+        if (uploaded) GBRS_HIP_CHECK(hipEventRecord(uploaded, s->stream));
+        for (int e = 0; e < lm.n_eig; ++e)
+            scan_lmm_rotate(s, lm.n_ld, pc, 1, 1, 1, pc, lm.U.p + (size_t)e * n * n, y.p, ys.p + (size_t)e * pc * lm.n_ld);
+        if (rotated) GBRS_HIP_CHECK(hipEventRecord(rotated, s->stream));
+        hipLaunchKernelGGL(lmm_null_kernel, dim3((unsigned)pc, (unsigned)lm.n_eig), dim3(64), 0, s->stream, n, lm.cz, lm.n_ld, pc, lm.n_eig,
+                           ys.p, lm.Zs.p, lm.lam.p, d_hin.p, d_hsq.p, d_sigma2.p, sw.p, qz.p, yt.p, rss0.p, d_rmin.p, d_rmax.p);
+        return GBRS_OK;
+    }
+};
+
+// The weighted columns [Hp][n_ld] of a point or of a target: the workgroup's LDS, or past LM_LDS_BYTES a workspace of the
+// call's own with one slice per workgroup in flight.
+struct LmmWeighted {
+    size_t w_bytes;
+    bool in_lds;
+    DevBuf<double> ws;                        // stays empty, and its pointer null, with in_lds
+    explicit LmmWeighted(const gbrs_scan *s) : w_bytes((size_t)s->Hp * s->lmm.n_ld * sizeof(double)), in_lds(w_bytes <= LM_LDS_BYTES) {}
+    int alloc(Tally &own, int64_t slices) { return in_lds ? GBRS_OK : own.alloc(ws, (size_t)slices * (w_bytes / sizeof(double))); }
+    size_t lds_bytes() const { return in_lds ? w_bytes : 0; }
+};
 
 }  // namespace
 
@@ -1365,8 +1449,9 @@ int gbrs_scan_kinship(gbrs_scan_t *s, int leave_out, double scale, double *K) {
     RoctxRange roctx_range("gbrs_scan_kinship");
     if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
     if (!K) return fail(GBRS_ERR_INVALID, "K is NULL");
-    if (s->n < 1) return fail(GBRS_ERR_INVALID, "the cohort has no samples");
-    if (s->n > LM_MAX_N) return fail(GBRS_ERR_INVALID, "a kinship takes at most %d samples, the cohort has %lld", LM_MAX_N, (long long)s->n);
+    const int64_t n = s->cohort.n;
+    if (n < 1) return fail(GBRS_ERR_INVALID, "the cohort has no samples");
+    if (n > LM_MAX_N) return fail(GBRS_ERR_INVALID, "a kinship takes at most %d samples, the cohort has %lld", LM_MAX_N, (long long)n);
     if (leave_out < -1 || leave_out >= s->n_chrom)
         return fail(GBRS_ERR_INVALID, "chromosome %d to leave out is not one of the handle's %d (-1: none)", leave_out, s->n_chrom);
     if (!std::isfinite(scale)) return fail(GBRS_ERR_INVALID, "the kinship's scale is not finite");
@@ -1376,23 +1461,22 @@ int gbrs_scan_kinship(gbrs_scan_t *s, int leave_out, double scale, double *K) {
     if (count == 0)
         return fail(GBRS_ERR_INVALID, "chromosome %d holds every grid point: its leave-one-chromosome-out kinship has nothing to be formed from", leave_out);
     GBRS_TRY(select_device(s->device));
-    const int64_t nn = s->n * s->n;
+    const int64_t nn = n * n;
     DevBuf<double> d_K;
     GBRS_TRY(d_K.alloc((size_t)nn));
-    GBRS_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
+    GBRS_TRY(timed_open(s));
     GBRS_TRY(scan_kinship_products(s));
     hipLaunchKernelGGL(lmm_kinship_sum_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, s->stream, nn, s->n_chrom, leave_out,
-                       scale, (double)count, s->kin_S.p, d_K.p);
+                       scale, (double)count, s->kin.S.p, d_K.p);
     GBRS_HIP_CHECK(hipEventRecord(s->ev[1], s->stream));
     GBRS_HIP_CHECK(hipGetLastError());
-    const hipError_t done = hipStreamSynchronize(s->stream);
+    const hipError_t done = hipStreamSynchronize(s->stream);     // not timed_wait: a failure here takes the products with it
     if (done != hipSuccess) {
-        s->kin_valid = false;
+        s->kin.valid = false;
         return fail(GBRS_ERR_HIP, "the kinship kernels failed: %s", hipGetErrorString(done));
     }
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) s->t_kinship = ms;
-    GBRS_HIP_CHECK(hipMemcpy(K, d_K.p, d_K.bytes(), hipMemcpyDeviceToHost));
+    s->last.lmm.last_kinship_ms = pass_ms(s, s->last.lmm.last_kinship_ms);
+    GBRS_TRY(copy_out(K, d_K, d_K.n));
     return GBRS_OK;
 }
 
@@ -1405,12 +1489,12 @@ int gbrs_scan_lmm_prepare(gbrs_scan_t *s, int cz, const double *Z, int n_eig, co
     if (!Z || !U || !lambda || !eig_of_chrom) return fail(GBRS_ERR_INVALID, "bad argument");
     if (n_eig < 1 || n_eig > s->n_chrom)
         return fail(GBRS_ERR_INVALID, "the decompositions must number 1..%d (one per chromosome at most), got %d", s->n_chrom, n_eig);
-    if (s->n <= (int64_t)cz + s->H - 1)
+    if (s->cohort.n <= (int64_t)cz + s->H - 1)
         return fail(GBRS_ERR_INVALID, "%lld samples are too few for %d covariate columns and %d founders: need more than %d",
-                    (long long)s->n, cz, s->H, cz + s->H - 1);
-    if (s->n > LM_MAX_N)
-        return fail(GBRS_ERR_INVALID, "the mixed model takes at most %d samples, the cohort has %lld", LM_MAX_N, (long long)s->n);
-    const int n = (int)s->n;
+                    (long long)s->cohort.n, cz, s->H, cz + s->H - 1);
+    if (s->cohort.n > LM_MAX_N)
+        return fail(GBRS_ERR_INVALID, "the mixed model takes at most %d samples, the cohort has %lld", LM_MAX_N, (long long)s->cohort.n);
+    const int n = (int)s->cohort.n;
     for (int c = 0; c < s->n_chrom; ++c)
         if (eig_of_chrom[c] < 0 || eig_of_chrom[c] >= n_eig)
             return fail(GBRS_ERR_INVALID, "chromosome %d is mapped to decomposition %d of %d", c, eig_of_chrom[c], n_eig);
@@ -1436,7 +1520,7 @@ int gbrs_scan_lmm_prepare(gbrs_scan_t *s, int cz, const double *Z, int n_eig, co
     }
     GBRS_TRY(select_device(s->device));
     // staged in the call's own buffers: an earlier preparation stands until everything below has succeeded
-    const int64_t n_ld = ((int64_t)n + SC_KC - 1) / SC_KC * SC_KC;
+    const int64_t n_ld = padded(n);
     DevBuf<double> d_U, d_lam, d_Z, d_Zs, d_R;
     DevBuf<int32_t> d_eop;
     GBRS_TRY(d_U.alloc((size_t)n_eig * n * n));
@@ -1454,27 +1538,25 @@ int gbrs_scan_lmm_prepare(gbrs_scan_t *s, int cz, const double *Z, int n_eig, co
     }
     GBRS_HIP_CHECK(hipMemcpy(d_Z.p, Z, d_Z.bytes(), hipMemcpyHostToDevice));
     GBRS_HIP_CHECK(hipMemcpy(d_eop.p, eop.data(), d_eop.bytes(), hipMemcpyHostToDevice));
-    GBRS_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
+    GBRS_TRY(timed_open(s));
     for (int e = 0; e < n_eig; ++e)
         scan_lmm_rotate(s, n_ld, cz, 1, 1, 1, cz, d_U.p + (size_t)e * n * n, d_Z.p, d_Zs.p + (size_t)e * cz * n_ld);
     for (int c = 0; c < s->n_chrom; ++c)
         scan_lmm_rotate(s, n_ld, (int64_t)s->points[c] * s->Hp, s->Hp, s->H - 1, s->H, s->M * s->H,
-                        d_U.p + (size_t)eig_of_chrom[c] * n * n, s->dosage.p + s->point_off[c] * s->H,
+                        d_U.p + (size_t)eig_of_chrom[c] * n * n, s->cohort.dosage.p + s->point_off[c] * s->H,
                         d_R.p + s->point_off[c] * s->Hp * n_ld);
-    GBRS_HIP_CHECK(hipEventRecord(s->ev[1], s->stream));
-    GBRS_HIP_CHECK(hipGetLastError());
-    GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) s->t_lmm_rotate = ms;
-    s->lmm_U.swap(d_U);
-    s->lmm_lam.swap(d_lam);
-    s->lmm_Zs.swap(d_Zs);
-    s->lmm_R.swap(d_R);
-    s->lmm_eig_of_point.swap(d_eop);
-    s->lmm_eig_of_chrom.assign(eig_of_chrom, eig_of_chrom + s->n_chrom);
-    s->lmm_cz = cz;
-    s->lmm_n_eig = n_eig;
-    s->lmm_n_ld = n_ld;
+    GBRS_TRY(timed_wait(s));
+    s->last.lmm.last_rotate_ms = pass_ms(s, s->last.lmm.last_rotate_ms);
+    gbrs_scan::Lmm &lm = s->lmm;
+    lm.U.swap(d_U);
+    lm.lam.swap(d_lam);
+    lm.Zs.swap(d_Zs);
+    lm.R.swap(d_R);
+    lm.eig_of_point.swap(d_eop);
+    lm.eig_of_chrom.assign(eig_of_chrom, eig_of_chrom + s->n_chrom);
+    lm.cz = cz;
+    lm.n_eig = n_eig;
+    lm.n_ld = n_ld;
     return GBRS_OK;
 }
 
@@ -1488,130 +1570,84 @@ int scan_lmm_run_pass(gbrs_scan *s, int64_t P, const double *pheno, const double
                       double *peak_lod, int64_t *peak_index, double *hsq, double *sigma2, int64_t *support_lo,
                       int64_t *support_hi) {
     if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
-    if (s->lmm_cz == 0) return fail(GBRS_ERR_INVALID, "no mixed model on the handle: call gbrs_scan_lmm_prepare first");
+    if (s->lmm.cz == 0) return fail(GBRS_ERR_INVALID, "no mixed model on the handle: call gbrs_scan_lmm_prepare first");
     if (P < 1 || !pheno) return fail(GBRS_ERR_INVALID, "bad argument");
     if (support && !(drop >= 0.0 && std::isfinite(drop)))
         return fail(GBRS_ERR_INVALID, "the LOD drop of a support interval must be a finite number that is not negative, got %g", drop);
-    const int n = (int)s->n, cz = s->lmm_cz, n_eig = s->lmm_n_eig;
-    for (int64_t k = 0; k < (int64_t)n * P; ++k)
-        if (!std::isfinite(pheno[k]))
-            return fail(GBRS_ERR_INVALID, "phenotype %lld holds a value that is not finite (sample %lld)", (long long)(k % P),
-                        (long long)(k / P));
-    if (hsq_in)
-        for (int64_t k = 0; k < P * n_eig; ++k)
-            if (!(hsq_in[k] >= 0.0 && hsq_in[k] <= 1.0))
-                return fail(GBRS_ERR_INVALID, "the heritability given for phenotype %lld and decomposition %d is %g, outside [0, 1]",
-                            (long long)(k / n_eig), (int)(k % n_eig), hsq_in[k]);
+    gbrs_scan::Lmm &lm = s->lmm;
+    const int n = (int)s->cohort.n, cz = lm.cz, n_eig = lm.n_eig, nc = s->n_chrom;
+    GBRS_TRY(check_finite("phenotype", pheno, n, P));
+    GBRS_TRY(check_hsq(hsq_in, P, n_eig));
     GBRS_TRY(select_device(s->device));
-    const int64_t pc_max = std::min(P, SC_PCHUNK), M = s->M, n_ld = s->lmm_n_ld;
+    const int64_t pc_max = std::min(P, SC_PCHUNK), M = s->M, n_ld = lm.n_ld;
     const int Hp = s->Hp;
-    const size_t pe = (size_t)pc_max * n_eig;
-    DevBuf<double> y, ys, d_hin, d_hsq, d_sigma2, sw, qz, yt, rss0, d_lod, d_peak, ws;
-    DevBuf<int64_t> d_index;
-    DevBuf<int32_t> d_rmin, d_rmax;
-    GBRS_TRY(y.alloc((size_t)n * pc_max));
-    GBRS_TRY(ys.alloc(pe * n_ld));
-    if (hsq_in) GBRS_TRY(d_hin.alloc(pe));
-    GBRS_TRY(d_hsq.alloc(pe));
-    GBRS_TRY(d_sigma2.alloc(pe));
-    GBRS_TRY(sw.alloc(pe * n_ld));
-    GBRS_TRY(qz.alloc(pe * cz * n_ld));
-    GBRS_TRY(yt.alloc(pe * n_ld));
-    GBRS_TRY(rss0.alloc(pe));
-    GBRS_TRY(d_lod.alloc((size_t)pc_max * M));
-    GBRS_TRY(d_peak.alloc((size_t)pc_max * s->n_chrom));
-    GBRS_TRY(d_index.alloc((size_t)pc_max * s->n_chrom));
-    GBRS_TRY(d_rmin.alloc((size_t)pc_max));
-    GBRS_TRY(d_rmax.alloc((size_t)pc_max));
-    DevBuf<int64_t> d_lo, d_hi;
+    Tally own;
+    LmmNull null;
+    DevBuf<double> d_lod, d_peak;
+    DevBuf<int64_t> d_index, d_lo, d_hi;
+    GBRS_TRY(null.alloc(own, s, pc_max, hsq_in != nullptr));
+    GBRS_TRY(own.alloc(d_lod, (size_t)pc_max * M));
+    GBRS_TRY(own.alloc(d_peak, (size_t)pc_max * nc));
+    GBRS_TRY(own.alloc(d_index, (size_t)pc_max * nc));
     if (support) {
-        GBRS_TRY(d_lo.alloc((size_t)pc_max * s->n_chrom));
-        GBRS_TRY(d_hi.alloc((size_t)pc_max * s->n_chrom));
+        GBRS_TRY(own.alloc(d_lo, (size_t)pc_max * nc));
+        GBRS_TRY(own.alloc(d_hi, (size_t)pc_max * nc));
     }
-    // a point's weighted columns: the workgroup's LDS, or past LM_LDS_BYTES a workspace and the points in batches
-    const size_t w_bytes = (size_t)Hp * n_ld * sizeof(double);
-    const bool in_lds = w_bytes <= LM_LDS_BYTES;
+    // past LM_LDS_BYTES the points go in batches through the workspace
+    LmmWeighted wc(s);
     const int64_t tiles_max = (pc_max + LM_TILE - 1) / LM_TILE;
-    const int64_t batch = in_lds ? M : std::max<int64_t>(1, std::min<int64_t>(M, (int64_t)(LM_WS_BYTES / (w_bytes * tiles_max))));
-    if (!in_lds) GBRS_TRY(ws.alloc((size_t)batch * tiles_max * Hp * n_ld));
+    const int64_t batch = wc.in_lds ? M : std::max<int64_t>(1, std::min<int64_t>(M, (int64_t)(LM_WS_BYTES / (wc.w_bytes * tiles_max))));
+    GBRS_TRY(wc.alloc(own, batch * tiles_max));
     std::vector<int32_t> rmin((size_t)P), rmax((size_t)P);
-    double t_rotate = 0.0, t_null = 0.0, t_point = 0.0;
-    hipEvent_t mark[4] = {};
-    struct Marks {
-        hipEvent_t *ev;
-        ~Marks() {
-            for (int k = 0; k < 4; ++k)
-                if (ev[k]) (void)hipEventDestroy(ev[k]);
-        }
-    } marks{mark};
-    for (auto &e : mark) GBRS_HIP_CHECK(hipEventCreate(&e));
-    GBRS_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
+    double t_null = 0.0, t_point = 0.0;
+    Marks mark;
+    GBRS_TRY(mark.create());
+    GBRS_TRY(timed_open(s));
     for (int64_t p0 = 0; p0 < P; p0 += SC_PCHUNK) {
         const int64_t pc = std::min(SC_PCHUNK, P - p0);
-        GBRS_HIP_CHECK(hipMemcpy2DAsync(y.p, (size_t)pc * sizeof(double), pheno + p0, (size_t)P * sizeof(double),
-                                        (size_t)pc * sizeof(double), (size_t)n, hipMemcpyHostToDevice, s->stream));
-        if (hsq_in)
-            GBRS_HIP_CHECK(hipMemcpyAsync(d_hin.p, hsq_in + p0 * n_eig, (size_t)pc * n_eig * sizeof(double), hipMemcpyHostToDevice, s->stream));
-        GBRS_HIP_CHECK(hipEventRecord(mark[0], s->stream));
-        for (int e = 0; e < n_eig; ++e)
-            scan_lmm_rotate(s, n_ld, pc, 1, 1, 1, pc, s->lmm_U.p + (size_t)e * n * n, y.p, ys.p + (size_t)e * pc * n_ld);
-        GBRS_HIP_CHECK(hipEventRecord(mark[1], s->stream));
-        hipLaunchKernelGGL(lmm_null_kernel, dim3((unsigned)pc, (unsigned)n_eig), dim3(64), 0, s->stream, n, cz, n_ld, pc, n_eig, ys.p,
-                           s->lmm_Zs.p, s->lmm_lam.p, hsq_in ? d_hin.p : nullptr, d_hsq.p, d_sigma2.p, sw.p, qz.p, yt.p, rss0.p,
-                           d_rmin.p, d_rmax.p);
-        GBRS_HIP_CHECK(hipEventRecord(mark[2], s->stream));
+        const size_t peaks = (size_t)pc * nc, fits = (size_t)pc * n_eig;
+        GBRS_TRY(null.fit(s, pheno, P, hsq_in, p0, pc, nullptr, mark.ev[0]));        // last_null_ms: the null kernel alone
+        GBRS_HIP_CHECK(hipEventRecord(mark.ev[1], s->stream));
         const unsigned tiles = (unsigned)((pc + LM_TILE - 1) / LM_TILE);
         for (int64_t m0 = 0; m0 < M; m0 += batch) {
             const dim3 grid((unsigned)std::min(batch, M - m0), tiles);
             auto launch = [&](auto kernel) {
-                hipLaunchKernelGGL(kernel, grid, dim3(SC_THREADS), in_lds ? w_bytes : 0, s->stream, n, M, m0, s->H, cz, n_ld, pc, n_eig,
-                                   LM_TILE, 0.5 * n, s->lmm_eig_of_point.p, s->lmm_R.p, sw.p, qz.p, yt.p, rss0.p,
-                                   in_lds ? nullptr : ws.p, d_lod.p, d_rmin.p, d_rmax.p);
+                hipLaunchKernelGGL(kernel, grid, dim3(SC_THREADS), wc.lds_bytes(), s->stream, n, M, m0, s->H, cz, n_ld, pc, n_eig, LM_TILE,
+                                   0.5 * n, lm.eig_of_point.p, lm.R.p, null.sw.p, null.qz.p, null.yt.p, null.rss0.p, wc.ws.p, d_lod.p,
+                                   null.d_rmin.p, null.d_rmax.p);
             };
             if (Hp == 8) launch(lmm_point_kernel<8>);
             else launch(lmm_point_kernel<16>);
         }
-        GBRS_HIP_CHECK(hipEventRecord(mark[3], s->stream));
-        hipLaunchKernelGGL(scan_peak_kernel, dim3((unsigned)s->n_chrom, (unsigned)pc), dim3(64), 0, s->stream, M, s->n_chrom,
-                           s->d_point_off.p, d_lod.p, d_peak.p, d_index.p);
+        GBRS_HIP_CHECK(hipEventRecord(mark.ev[2], s->stream));
+        hipLaunchKernelGGL(scan_peak_kernel, dim3((unsigned)nc, (unsigned)pc), dim3(64), 0, s->stream, M, nc, s->d_point_off.p, d_lod.p,
+                           d_peak.p, d_index.p);
         if (support)
-            hipLaunchKernelGGL(scan_support_kernel, dim3((unsigned)s->n_chrom, (unsigned)pc), dim3(64), 0, s->stream, M, s->n_chrom,
-                               drop, s->d_point_off.p, d_lod.p, d_peak.p, d_index.p, d_lo.p, d_hi.p);
+            hipLaunchKernelGGL(scan_support_kernel, dim3((unsigned)nc, (unsigned)pc), dim3(64), 0, s->stream, M, nc, drop,
+                               s->d_point_off.p, d_lod.p, d_peak.p, d_index.p, d_lo.p, d_hi.p);
         GBRS_HIP_CHECK(hipGetLastError());
         GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, mark[0], mark[1]) == hipSuccess) t_rotate += ms;
-        if (hipEventElapsedTime(&ms, mark[1], mark[2]) == hipSuccess) t_null += ms;
-        if (hipEventElapsedTime(&ms, mark[2], mark[3]) == hipSuccess) t_point += ms;
-        if (lod) GBRS_HIP_CHECK(hipMemcpy(lod + p0 * M, d_lod.p, (size_t)pc * M * sizeof(double), hipMemcpyDeviceToHost));
-        if (peak_lod)
-            GBRS_HIP_CHECK(hipMemcpy(peak_lod + p0 * s->n_chrom, d_peak.p, (size_t)pc * s->n_chrom * sizeof(double), hipMemcpyDeviceToHost));
-        if (peak_index)
-            GBRS_HIP_CHECK(hipMemcpy(peak_index + p0 * s->n_chrom, d_index.p, (size_t)pc * s->n_chrom * sizeof(int64_t), hipMemcpyDeviceToHost));
-        if (hsq) GBRS_HIP_CHECK(hipMemcpy(hsq + p0 * n_eig, d_hsq.p, (size_t)pc * n_eig * sizeof(double), hipMemcpyDeviceToHost));
-        if (sigma2) GBRS_HIP_CHECK(hipMemcpy(sigma2 + p0 * n_eig, d_sigma2.p, (size_t)pc * n_eig * sizeof(double), hipMemcpyDeviceToHost));
-        if (support_lo)
-            GBRS_HIP_CHECK(hipMemcpy(support_lo + p0 * s->n_chrom, d_lo.p, (size_t)pc * s->n_chrom * sizeof(int64_t), hipMemcpyDeviceToHost));
-        if (support_hi)
-            GBRS_HIP_CHECK(hipMemcpy(support_hi + p0 * s->n_chrom, d_hi.p, (size_t)pc * s->n_chrom * sizeof(int64_t), hipMemcpyDeviceToHost));
-        GBRS_HIP_CHECK(hipMemcpy(rmin.data() + p0, d_rmin.p, (size_t)pc * sizeof(int32_t), hipMemcpyDeviceToHost));
-        GBRS_HIP_CHECK(hipMemcpy(rmax.data() + p0, d_rmax.p, (size_t)pc * sizeof(int32_t), hipMemcpyDeviceToHost));
+        t_null += elapsed_ms(mark.ev[0], mark.ev[1], 0.0);
+        t_point += elapsed_ms(mark.ev[1], mark.ev[2], 0.0);
+        GBRS_TRY(copy_out(lod, d_lod, (size_t)pc * M, (size_t)p0 * M));
+        GBRS_TRY(copy_out(peak_lod, d_peak, peaks, (size_t)p0 * nc));
+        GBRS_TRY(copy_out(peak_index, d_index, peaks, (size_t)p0 * nc));
+        GBRS_TRY(copy_out(hsq, null.d_hsq, fits, (size_t)p0 * n_eig));
+        GBRS_TRY(copy_out(sigma2, null.d_sigma2, fits, (size_t)p0 * n_eig));
+        GBRS_TRY(copy_out(support_lo, d_lo, peaks, (size_t)p0 * nc));
+        GBRS_TRY(copy_out(support_hi, d_hi, peaks, (size_t)p0 * nc));
+        GBRS_TRY(copy_out(rmin.data(), null.d_rmin, (size_t)pc, (size_t)p0));
+        GBRS_TRY(copy_out(rmax.data(), null.d_rmax, (size_t)pc, (size_t)p0));
     }
-    GBRS_HIP_CHECK(hipEventRecord(s->ev[1], s->stream));
-    GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) s->t_lmm_run = ms;
-    s->t_lmm_null = t_null;
-    s->t_lmm_point = t_point;
-    s->lmm_P = P;
-    s->lmm_rank_min.swap(rmin);
-    s->lmm_rank_max.swap(rmax);
-    (void)t_rotate;
-    s->lmm_peak_bytes = s->d_point_off.bytes() + s->dosage.bytes() + s->qz.bytes() + s->W.bytes() + s->d_rank.bytes() + s->y.bytes() +
-                        s->yt.bytes() + s->rss0.bytes() + s->lod.bytes() + s->peak_lod.bytes() + s->peak_index.bytes() + s->snp_bytes() +
-                        s->kin_S.bytes() + s->lmm_bytes() + y.bytes() + ys.bytes() + d_hin.bytes() + d_hsq.bytes() + d_sigma2.bytes() +
-                        sw.bytes() + qz.bytes() + yt.bytes() + rss0.bytes() + d_lod.bytes() + d_peak.bytes() + d_index.bytes() +
-                        d_rmin.bytes() + d_rmax.bytes() + ws.bytes() + d_lo.bytes() + d_hi.bytes();
+    GBRS_TRY(timed_wait(s));
+    gbrs_scan_lmm_info_t &r = s->last.lmm;
+    r.P = P;
+    r.last_run_ms = pass_ms(s, r.last_run_ms);
+    r.last_null_ms = t_null;
+    r.last_point_ms = t_point;
+    r.peak_device_bytes = s->resident_bytes() + own.bytes;
+    lm.rank_min.swap(rmin);
+    lm.rank_max.swap(rmax);
     return GBRS_OK;
 }
 
@@ -1640,28 +1676,15 @@ int gbrs_scan_lmm_effects(gbrs_scan_t *s, int64_t P, const double *pheno, const 
                           double *hsq) {
     RoctxRange roctx_range("gbrs_scan_lmm_effects");
     if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
-    if (s->lmm_cz == 0) return fail(GBRS_ERR_INVALID, "no mixed model on the handle: call gbrs_scan_lmm_prepare first");
+    if (s->lmm.cz == 0) return fail(GBRS_ERR_INVALID, "no mixed model on the handle: call gbrs_scan_lmm_prepare first");
     if (P < 1) return fail(GBRS_ERR_INVALID, "an effects pass needs at least 1 phenotype, got %lld", (long long)P);
     if (T < 0) return fail(GBRS_ERR_INVALID, "the number of targets cannot be negative, got %lld", (long long)T);
     if (!pheno || (T > 0 && (!column || !point))) return fail(GBRS_ERR_INVALID, "bad argument");
-    const int n = (int)s->n, cz = s->lmm_cz, n_eig = s->lmm_n_eig, H = s->H, Hp = s->Hp;
-    for (int64_t t = 0; t < T; ++t) {
-        if (column[t] < 0 || column[t] >= P)
-            return fail(GBRS_ERR_INVALID, "target %lld is phenotype column %lld: the table has the columns 0 .. %lld", (long long)t,
-                        (long long)column[t], (long long)(P - 1));
-        if (point[t] < 0 || point[t] >= s->M)
-            return fail(GBRS_ERR_INVALID, "target %lld is at grid point %lld: the handle has the points 0 .. %lld", (long long)t,
-                        (long long)point[t], (long long)(s->M - 1));
-    }
-    for (int64_t k = 0; k < (int64_t)n * P; ++k)
-        if (!std::isfinite(pheno[k]))
-            return fail(GBRS_ERR_INVALID, "phenotype %lld holds a value that is not finite (sample %lld)", (long long)(k % P),
-                        (long long)(k / P));
-    if (hsq_in)
-        for (int64_t k = 0; k < P * n_eig; ++k)
-            if (!(hsq_in[k] >= 0.0 && hsq_in[k] <= 1.0))
-                return fail(GBRS_ERR_INVALID, "the heritability given for phenotype %lld and decomposition %d is %g, outside [0, 1]",
-                            (long long)(k / n_eig), (int)(k % n_eig), hsq_in[k]);
+    const gbrs_scan::Lmm &lm = s->lmm;
+    const int n = (int)s->cohort.n, cz = lm.cz, n_eig = lm.n_eig, H = s->H, Hp = s->Hp;
+    GBRS_TRY(check_targets(s, T, column, P, point));
+    GBRS_TRY(check_finite("phenotype", pheno, n, P));
+    GBRS_TRY(check_hsq(hsq_in, P, n_eig));
     if (T == 0) return GBRS_OK;
     // the used columns in ascending order, and every column's targets in the caller's order
     std::vector<int64_t> slot((size_t)P, -1), used;
@@ -1671,7 +1694,7 @@ int gbrs_scan_lmm_effects(gbrs_scan_t *s, int64_t P, const double *pheno, const 
             slot[p] = (int64_t)used.size();
             used.push_back(p);
         }
-    const int64_t Pu = (int64_t)used.size(), pc_max = std::min(Pu, SC_PCHUNK), n_ld = s->lmm_n_ld;
+    const int64_t Pu = (int64_t)used.size(), pc_max = std::min(Pu, SC_PCHUNK), n_ld = lm.n_ld;
     std::vector<double> y_used((size_t)n * Pu), h_used(hsq_in ? (size_t)Pu * n_eig : 0);
     for (int64_t i = 0; i < n; ++i)
         for (int64_t q = 0; q < Pu; ++q) y_used[i * Pu + q] = pheno[i * P + used[q]];
@@ -1682,33 +1705,22 @@ int gbrs_scan_lmm_effects(gbrs_scan_t *s, int64_t P, const double *pheno, const 
     for (int64_t t = 0; t < T; ++t) of_chunk[slot[column[t]] / SC_PCHUNK].push_back(t);
     GBRS_TRY(select_device(s->device));
     const int64_t tc_max = std::min(T, SE_TCHUNK);
-    const size_t pe = (size_t)pc_max * n_eig;
-    DevBuf<double> y, ys, d_hin, d_hsq, d_s2, sw, qz, yt, rss0, ws, d_effect, d_se, d_lod, d_sigma2, d_hout;
+    Tally own;
+    LmmNull null;
+    DevBuf<double> d_effect, d_se, d_lod, d_sigma2, d_hout;
     DevBuf<int64_t> d_column, d_point;
-    DevBuf<int32_t> d_rmin, d_rmax, d_rank;
-    GBRS_TRY(y.alloc((size_t)n * pc_max));
-    GBRS_TRY(ys.alloc(pe * n_ld));
-    if (hsq_in) GBRS_TRY(d_hin.alloc(pe));
-    GBRS_TRY(d_hsq.alloc(pe));
-    GBRS_TRY(d_s2.alloc(pe));
-    GBRS_TRY(sw.alloc(pe * n_ld));
-    GBRS_TRY(qz.alloc(pe * cz * n_ld));
-    GBRS_TRY(yt.alloc(pe * n_ld));
-    GBRS_TRY(rss0.alloc(pe));
-    GBRS_TRY(d_rmin.alloc((size_t)pc_max));
-    GBRS_TRY(d_rmax.alloc((size_t)pc_max));
-    GBRS_TRY(d_effect.alloc((size_t)tc_max * H));
-    GBRS_TRY(d_se.alloc((size_t)tc_max * H));
-    GBRS_TRY(d_lod.alloc((size_t)tc_max));
-    GBRS_TRY(d_sigma2.alloc((size_t)tc_max));
-    GBRS_TRY(d_hout.alloc((size_t)tc_max));
-    GBRS_TRY(d_rank.alloc((size_t)tc_max));
-    GBRS_TRY(d_column.alloc((size_t)tc_max));
-    GBRS_TRY(d_point.alloc((size_t)tc_max));
-    // a target's weighted columns: the workgroup's LDS, or past LM_LDS_BYTES its slice of a workspace
-    const size_t w_bytes = (size_t)Hp * n_ld * sizeof(double);
-    const bool in_lds = w_bytes <= LM_LDS_BYTES;
-    if (!in_lds) GBRS_TRY(ws.alloc((size_t)tc_max * Hp * n_ld));
+    DevBuf<int32_t> d_rank;
+    GBRS_TRY(null.alloc(own, s, pc_max, hsq_in != nullptr));
+    GBRS_TRY(own.alloc(d_effect, (size_t)tc_max * H));
+    GBRS_TRY(own.alloc(d_se, (size_t)tc_max * H));
+    GBRS_TRY(own.alloc(d_lod, (size_t)tc_max));
+    GBRS_TRY(own.alloc(d_sigma2, (size_t)tc_max));
+    GBRS_TRY(own.alloc(d_hout, (size_t)tc_max));
+    GBRS_TRY(own.alloc(d_rank, (size_t)tc_max));
+    GBRS_TRY(own.alloc(d_column, (size_t)tc_max));
+    GBRS_TRY(own.alloc(d_point, (size_t)tc_max));
+    LmmWeighted wc(s);                  // past LM_LDS_BYTES a target has its slice of the workspace
+    GBRS_TRY(wc.alloc(own, tc_max));
     std::vector<double> h_effect((size_t)T * H), h_se((size_t)T * H), h_lod((size_t)T), h_sigma2((size_t)T), h_hsq((size_t)T);
     std::vector<int32_t> h_rank((size_t)T);
     std::vector<double> c_effect((size_t)tc_max * H), c_se((size_t)tc_max * H), c_lod((size_t)tc_max), c_sigma2((size_t)tc_max),
@@ -1716,30 +1728,14 @@ int gbrs_scan_lmm_effects(gbrs_scan_t *s, int64_t P, const double *pheno, const 
     std::vector<int32_t> c_rank((size_t)tc_max);
     std::vector<int64_t> c_column((size_t)tc_max), c_point((size_t)tc_max);
     double t_null = 0.0, t_target = 0.0;
-    hipEvent_t mark[3] = {};
-    struct Marks {
-        hipEvent_t *ev;
-        ~Marks() {
-            for (int k = 0; k < 3; ++k)
-                if (ev[k]) (void)hipEventDestroy(ev[k]);
-        }
-    } marks{mark};
-    for (auto &e : mark) GBRS_HIP_CHECK(hipEventCreate(&e));
-    GBRS_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
+    Marks mark;
+    GBRS_TRY(mark.create());
+    GBRS_TRY(timed_open(s));
     for (int64_t p0 = 0; p0 < Pu; p0 += SC_PCHUNK) {
         const int64_t pc = std::min(SC_PCHUNK, Pu - p0);
         const std::vector<int64_t> &mine = of_chunk[(size_t)(p0 / SC_PCHUNK)];
-        GBRS_HIP_CHECK(hipMemcpy2DAsync(y.p, (size_t)pc * sizeof(double), y_used.data() + p0, (size_t)Pu * sizeof(double),
-                                        (size_t)pc * sizeof(double), (size_t)n, hipMemcpyHostToDevice, s->stream));
-        if (hsq_in)
-            GBRS_HIP_CHECK(hipMemcpyAsync(d_hin.p, h_used.data() + p0 * n_eig, (size_t)pc * n_eig * sizeof(double), hipMemcpyHostToDevice, s->stream));
-        GBRS_HIP_CHECK(hipEventRecord(mark[0], s->stream));
-        for (int e = 0; e < n_eig; ++e)
-            scan_lmm_rotate(s, n_ld, pc, 1, 1, 1, pc, s->lmm_U.p + (size_t)e * n * n, y.p, ys.p + (size_t)e * pc * n_ld);
-        hipLaunchKernelGGL(lmm_null_kernel, dim3((unsigned)pc, (unsigned)n_eig), dim3(64), 0, s->stream, n, cz, n_ld, pc, n_eig, ys.p,
-                           s->lmm_Zs.p, s->lmm_lam.p, hsq_in ? d_hin.p : nullptr, d_hsq.p, d_s2.p, sw.p, qz.p, yt.p, rss0.p,
-                           d_rmin.p, d_rmax.p);
-        GBRS_HIP_CHECK(hipEventRecord(mark[1], s->stream));
+        GBRS_TRY(null.fit(s, y_used.data(), Pu, hsq_in ? h_used.data() : nullptr, p0, pc, mark.ev[0], nullptr));  // last_null_ms: rotations and REML
+        GBRS_HIP_CHECK(hipEventRecord(mark.ev[1], s->stream));
         GBRS_HIP_CHECK(hipGetLastError());
         for (size_t t0 = 0; t0 < mine.size(); t0 += (size_t)SE_TCHUNK) {
             const int64_t tc = (int64_t)std::min<size_t>((size_t)SE_TCHUNK, mine.size() - t0);
@@ -1751,9 +1747,9 @@ int gbrs_scan_lmm_effects(gbrs_scan_t *s, int64_t P, const double *pheno, const 
             GBRS_HIP_CHECK(hipMemcpyAsync(d_column.p, c_column.data(), (size_t)tc * sizeof(int64_t), hipMemcpyHostToDevice, s->stream));
             GBRS_HIP_CHECK(hipMemcpyAsync(d_point.p, c_point.data(), (size_t)tc * sizeof(int64_t), hipMemcpyHostToDevice, s->stream));
             auto launch = [&](auto kernel) {
-                hipLaunchKernelGGL(kernel, dim3((unsigned)tc), dim3(SC_THREADS), in_lds ? w_bytes : 0, s->stream, n, H, cz, n_ld, n_eig,
-                                   0.5 * n, s->lmm_eig_of_point.p, s->lmm_R.p, sw.p, qz.p, yt.p, rss0.p, d_hsq.p, d_column.p, d_point.p,
-                                   in_lds ? nullptr : ws.p, d_effect.p, d_se.p, d_lod.p, d_sigma2.p, d_rank.p, d_hout.p);
+                hipLaunchKernelGGL(kernel, dim3((unsigned)tc), dim3(SC_THREADS), wc.lds_bytes(), s->stream, n, H, cz, n_ld, n_eig, 0.5 * n,
+                                   lm.eig_of_point.p, lm.R.p, null.sw.p, null.qz.p, null.yt.p, null.rss0.p, null.d_hsq.p, d_column.p,
+                                   d_point.p, wc.ws.p, d_effect.p, d_se.p, d_lod.p, d_sigma2.p, d_rank.p, d_hout.p);
             };
             if (Hp == 8) launch(lmm_effects_kernel<8>);
             else launch(lmm_effects_kernel<16>);
@@ -1775,14 +1771,12 @@ int gbrs_scan_lmm_effects(gbrs_scan_t *s, int64_t P, const double *pheno, const 
                 h_rank[t] = c_rank[k];
             }
         }
-        GBRS_HIP_CHECK(hipEventRecord(mark[2], s->stream));
+        GBRS_HIP_CHECK(hipEventRecord(mark.ev[2], s->stream));
         GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, mark[0], mark[1]) == hipSuccess) t_null += ms;
-        if (hipEventElapsedTime(&ms, mark[1], mark[2]) == hipSuccess) t_target += ms;
+        t_null += elapsed_ms(mark.ev[0], mark.ev[1], 0.0);
+        t_target += elapsed_ms(mark.ev[1], mark.ev[2], 0.0);
     }
-    GBRS_HIP_CHECK(hipEventRecord(s->ev[1], s->stream));
-    GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
+    GBRS_TRY(timed_wait(s));
     // the caller's arrays are written once the whole pass has succeeded
     if (effect) std::memcpy(effect, h_effect.data(), h_effect.size() * sizeof(double));
     if (se) std::memcpy(se, h_se.data(), h_se.size() * sizeof(double));
@@ -1790,53 +1784,36 @@ int gbrs_scan_lmm_effects(gbrs_scan_t *s, int64_t P, const double *pheno, const 
     if (sigma2) std::memcpy(sigma2, h_sigma2.data(), h_sigma2.size() * sizeof(double));
     if (rank) std::memcpy(rank, h_rank.data(), h_rank.size() * sizeof(int32_t));
     if (hsq) std::memcpy(hsq, h_hsq.data(), h_hsq.size() * sizeof(double));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) s->t_leff_pass = ms;
-    s->t_leff_null = t_null;
-    s->t_leff_target = t_target;
-    s->leff_T = T;
-    s->leff_P = P;
-    s->leff_columns = Pu;
-    s->leff_peak_bytes = s->d_point_off.bytes() + s->dosage.bytes() + s->qz.bytes() + s->W.bytes() + s->d_rank.bytes() + s->y.bytes() +
-                         s->yt.bytes() + s->rss0.bytes() + s->lod.bytes() + s->peak_lod.bytes() + s->peak_index.bytes() + s->snp_bytes() +
-                         s->kin_S.bytes() + s->lmm_bytes() + y.bytes() + ys.bytes() + d_hin.bytes() + d_hsq.bytes() + d_s2.bytes() +
-                         sw.bytes() + qz.bytes() + yt.bytes() + rss0.bytes() + d_rmin.bytes() + d_rmax.bytes() + ws.bytes() +
-                         d_effect.bytes() + d_se.bytes() + d_lod.bytes() + d_sigma2.bytes() + d_hout.bytes() + d_rank.bytes() +
-                         d_column.bytes() + d_point.bytes();
+    gbrs_scan_lmm_effects_info_t &r = s->last.lmm_effects;
+    r.T = T;
+    r.P = P;
+    r.columns = Pu;
+    r.last_pass_ms = pass_ms(s, r.last_pass_ms);
+    r.last_null_ms = t_null;
+    r.last_target_ms = t_target;
+    r.peak_device_bytes = s->resident_bytes() + own.bytes;
     return GBRS_OK;
 }
 
 int gbrs_scan_lmm_effects_info(gbrs_scan_t *s, gbrs_scan_lmm_effects_info_t *info) {
     if (!s || !info) return fail(GBRS_ERR_INVALID, "bad argument");
-    info->T = s->leff_T;
-    info->P = s->leff_P;
-    info->columns = s->leff_columns;
-    info->last_pass_ms = s->t_leff_pass;
-    info->last_null_ms = s->t_leff_null;
-    info->last_target_ms = s->t_leff_target;
-    info->peak_device_bytes = s->leff_peak_bytes;
+    *info = s->last.lmm_effects;
     return GBRS_OK;
 }
 
 int gbrs_scan_lmm_ranks(gbrs_scan_t *s, int32_t *rank_min, int32_t *rank_max) {
     if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
-    if (rank_min) std::memcpy(rank_min, s->lmm_rank_min.data(), s->lmm_rank_min.size() * sizeof(int32_t));
-    if (rank_max) std::memcpy(rank_max, s->lmm_rank_max.data(), s->lmm_rank_max.size() * sizeof(int32_t));
+    if (rank_min) std::memcpy(rank_min, s->lmm.rank_min.data(), s->lmm.rank_min.size() * sizeof(int32_t));
+    if (rank_max) std::memcpy(rank_max, s->lmm.rank_max.data(), s->lmm.rank_max.size() * sizeof(int32_t));
     return GBRS_OK;
 }
 
 int gbrs_scan_lmm_info(gbrs_scan_t *s, gbrs_scan_lmm_info_t *info) {
     if (!s || !info) return fail(GBRS_ERR_INVALID, "bad argument");
-    info->cz = s->lmm_cz;
-    info->n_eig = s->lmm_n_eig;
-    info->P = s->lmm_P;
-    info->last_kinship_ms = s->t_kinship;
-    info->last_rotate_ms = s->t_lmm_rotate;
-    info->last_null_ms = s->t_lmm_null;
-    info->last_point_ms = s->t_lmm_point;
-    info->last_run_ms = s->t_lmm_run;
-    info->device_bytes = s->kin_S.bytes() + s->lmm_bytes();
-    info->peak_device_bytes = s->lmm_peak_bytes;
+    *info = s->last.lmm;
+    info->cz = s->lmm.cz;
+    info->n_eig = s->lmm.n_eig;
+    info->device_bytes = s->kin.S.bytes() + s->lmm.bytes();
     return GBRS_OK;
 }
 
@@ -1847,20 +1824,15 @@ int gbrs_scan_lmm_snps(gbrs_scan_t *s, int64_t P, const double *pheno, const dou
                        double *peak_lod, int64_t *peak_index, int64_t *n_used, double *hsq, double *sigma2) {
     RoctxRange roctx_range("gbrs_scan_lmm_snps");
     if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
-    if (s->M_snp == 0) return fail(GBRS_ERR_INVALID, "no SNPs on the handle: call gbrs_scan_set_snps first");
-    if (s->lmm_cz == 0) return fail(GBRS_ERR_INVALID, "no mixed model on the handle: call gbrs_scan_lmm_prepare first");
+    if (s->snp.M == 0) return fail(GBRS_ERR_INVALID, "no SNPs on the handle: call gbrs_scan_set_snps first");
+    if (s->lmm.cz == 0) return fail(GBRS_ERR_INVALID, "no mixed model on the handle: call gbrs_scan_lmm_prepare first");
     if (P < 1) return fail(GBRS_ERR_INVALID, "a SNP pass needs at least 1 phenotype, got %lld", (long long)P);
     if (!pheno) return fail(GBRS_ERR_INVALID, "bad argument");
-    const int n = (int)s->n, cz = s->lmm_cz, n_eig = s->lmm_n_eig, nc = s->n_chrom;
-    for (int64_t k = 0; k < (int64_t)n * P; ++k)
-        if (!std::isfinite(pheno[k]))
-            return fail(GBRS_ERR_INVALID, "phenotype %lld holds a value that is not finite (sample %lld)", (long long)(k % P),
-                        (long long)(k / P));
-    if (hsq_in)
-        for (int64_t k = 0; k < P * n_eig; ++k)
-            if (!(hsq_in[k] >= 0.0 && hsq_in[k] <= 1.0))
-                return fail(GBRS_ERR_INVALID, "the heritability given for phenotype %lld and decomposition %d is %g, outside [0, 1]",
-                            (long long)(k / n_eig), (int)(k % n_eig), hsq_in[k]);
+    const gbrs_scan::Lmm &lm = s->lmm;
+    const gbrs_scan::Snp &sn = s->snp;
+    const int n = (int)s->cohort.n, cz = lm.cz, n_eig = lm.n_eig, nc = s->n_chrom;
+    GBRS_TRY(check_finite("phenotype", pheno, n, P));
+    GBRS_TRY(check_hsq(hsq_in, P, n_eig));
     GBRS_TRY(select_device(s->device));
     int lds_max = 0;
     GBRS_HIP_CHECK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, s->device));
@@ -1868,62 +1840,44 @@ int gbrs_scan_lmm_snps(gbrs_scan_t *s, int64_t P, const double *pheno, const dou
         return fail(GBRS_ERR_INVALID, "the device gives a workgroup %d bytes of LDS, the SNP product needs %lld", lds_max, (long long)LS_LDS_BYTES);
     GBRS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(lmm_snp_lod_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)LS_LDS_BYTES));
-    const int64_t M_snp = s->M_snp, n_ld = s->lmm_n_ld, pc_max = std::min(P, SC_PCHUNK), lc_max = std::min(M_snp, SS_CHUNK);
-    const size_t pe = (size_t)pc_max * n_eig;
+    const int64_t M_snp = sn.M, n_ld = lm.n_ld, pc_max = std::min(P, SC_PCHUNK), lc_max = std::min(M_snp, SS_CHUNK);
     const int64_t q_stride = P * n_ld;
-    DevBuf<double> y, ys, d_hin, d_hsq, d_sigma2, sw, qz, yt, rss0, cols, rss_all, dose, xs, d_lod, d_peak;
+    Tally own;
+    LmmNull null;
+    DevBuf<double> cols, rss_all, dose, xs, d_lod, d_peak;
     DevBuf<int64_t> d_index, d_count;
-    DevBuf<int32_t> d_rmin, d_rmax;
     DevBuf<uint8_t> d_used;
-    GBRS_TRY(y.alloc((size_t)n * pc_max));
-    GBRS_TRY(ys.alloc(pe * n_ld));
-    if (hsq_in) GBRS_TRY(d_hin.alloc(pe));
-    GBRS_TRY(d_hsq.alloc(pe));
-    GBRS_TRY(d_sigma2.alloc(pe));
-    GBRS_TRY(sw.alloc(pe * n_ld));
-    GBRS_TRY(qz.alloc(pe * cz * n_ld));
-    GBRS_TRY(yt.alloc(pe * n_ld));
-    GBRS_TRY(rss0.alloc(pe));
-    GBRS_TRY(d_rmin.alloc((size_t)pc_max));
-    GBRS_TRY(d_rmax.alloc((size_t)pc_max));
-    GBRS_TRY(cols.alloc((size_t)n_eig * (cz + 2) * q_stride));
-    GBRS_TRY(rss_all.alloc((size_t)n_eig * P));
-    GBRS_TRY(dose.alloc((size_t)n * lc_max));
-    GBRS_TRY(xs.alloc((size_t)lc_max * n_ld));
-    GBRS_TRY(d_lod.alloc((size_t)pc_max * lc_max));
-    GBRS_TRY(d_used.alloc((size_t)pc_max * lc_max));
-    GBRS_TRY(d_peak.alloc((size_t)P * nc));
-    GBRS_TRY(d_index.alloc((size_t)P * nc));
-    GBRS_TRY(d_count.alloc((size_t)P * nc));
+    GBRS_TRY(null.alloc(own, s, pc_max, hsq_in != nullptr));
+    GBRS_TRY(own.alloc(cols, (size_t)n_eig * (cz + 2) * q_stride));
+    GBRS_TRY(own.alloc(rss_all, (size_t)n_eig * P));
+    GBRS_TRY(own.alloc(dose, (size_t)n * lc_max));
+    GBRS_TRY(own.alloc(xs, (size_t)lc_max * n_ld));
+    GBRS_TRY(own.alloc(d_lod, (size_t)pc_max * lc_max));
+    GBRS_TRY(own.alloc(d_used, (size_t)pc_max * lc_max));
+    GBRS_TRY(own.alloc(d_peak, (size_t)P * nc));
+    GBRS_TRY(own.alloc(d_index, (size_t)P * nc));
+    GBRS_TRY(own.alloc(d_count, (size_t)P * nc));
     EventRing null_ring, rotate_ring, product_ring;
     GBRS_TRY(null_ring.create());
     GBRS_TRY(rotate_ring.create());
     GBRS_TRY(product_ring.create());
     int slot = 0;
-    GBRS_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
+    GBRS_TRY(timed_open(s));
     GBRS_HIP_CHECK(hipMemsetAsync(d_index.p, 0xFF, d_index.bytes(), s->stream));         // -1: nothing yet
     GBRS_HIP_CHECK(hipMemsetAsync(d_count.p, 0, d_count.bytes(), s->stream));
     for (int64_t p0 = 0; p0 < P; p0 += SC_PCHUNK) {
         const int64_t pc = std::min(SC_PCHUNK, P - p0);
-        GBRS_HIP_CHECK(hipMemcpy2DAsync(y.p, (size_t)pc * sizeof(double), pheno + p0, (size_t)P * sizeof(double),
-                                        (size_t)pc * sizeof(double), (size_t)n, hipMemcpyHostToDevice, s->stream));
-        if (hsq_in)
-            GBRS_HIP_CHECK(hipMemcpyAsync(d_hin.p, hsq_in + p0 * n_eig, (size_t)pc * n_eig * sizeof(double), hipMemcpyHostToDevice, s->stream));
         GBRS_TRY(null_ring.next(&slot));
-        GBRS_HIP_CHECK(hipEventRecord(null_ring.ev[2 * slot], s->stream));
-        for (int e = 0; e < n_eig; ++e)
-            scan_lmm_rotate(s, n_ld, pc, 1, 1, 1, pc, s->lmm_U.p + (size_t)e * n * n, y.p, ys.p + (size_t)e * pc * n_ld);
-        hipLaunchKernelGGL(lmm_null_kernel, dim3((unsigned)pc, (unsigned)n_eig), dim3(64), 0, s->stream, n, cz, n_ld, pc, n_eig, ys.p,
-                           s->lmm_Zs.p, s->lmm_lam.p, hsq_in ? d_hin.p : nullptr, d_hsq.p, d_sigma2.p, sw.p, qz.p, yt.p, rss0.p,
-                           d_rmin.p, d_rmax.p);
+        GBRS_TRY(null.fit(s, pheno, P, hsq_in, p0, pc, null_ring.ev[2 * slot], nullptr));    // last_null_ms: rotations, REML, the columns
         hipLaunchKernelGGL(lmm_snp_column_kernel, dim3((unsigned)((pc * n_eig * n_ld + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0,
-                           s->stream, n_ld, pc, p0, P, n_eig, cz, sw.p, qz.p, yt.p, rss0.p, cols.p, rss_all.p);
+                           s->stream, n_ld, pc, p0, P, n_eig, cz, null.sw.p, null.qz.p, null.yt.p, null.rss0.p, cols.p, rss_all.p);
         GBRS_HIP_CHECK(hipEventRecord(null_ring.ev[2 * slot + 1], s->stream));
         GBRS_HIP_CHECK(hipGetLastError());
         // waits for the kernels before it on the stream; the next chunk's null fit overwrites the two tables after it
-        if (hsq) GBRS_HIP_CHECK(hipMemcpyAsync(hsq + p0 * n_eig, d_hsq.p, (size_t)pc * n_eig * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        if (hsq)
+            GBRS_HIP_CHECK(hipMemcpyAsync(hsq + p0 * n_eig, null.d_hsq.p, (size_t)pc * n_eig * sizeof(double), hipMemcpyDeviceToHost, s->stream));
         if (sigma2)
-            GBRS_HIP_CHECK(hipMemcpyAsync(sigma2 + p0 * n_eig, d_sigma2.p, (size_t)pc * n_eig * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+            GBRS_HIP_CHECK(hipMemcpyAsync(sigma2 + p0 * n_eig, null.d_sigma2.p, (size_t)pc * n_eig * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     }
     for (int64_t j0 = 0; j0 < M_snp; j0 += SS_CHUNK) {
         const int64_t jc = std::min(SS_CHUNK, M_snp - j0);
@@ -1931,20 +1885,20 @@ int gbrs_scan_lmm_snps(gbrs_scan_t *s, int64_t P, const double *pheno, const dou
         std::vector<std::pair<int64_t, int64_t>> runs;
         std::vector<int> run_eig;
         for (int c = 0; c < nc; ++c) {
-            const int64_t a = std::max(s->snp_off[c], j0) - j0, b = std::min(s->snp_off[c + 1], j0 + jc) - j0;
+            const int64_t a = std::max(sn.off[c], j0) - j0, b = std::min(sn.off[c + 1], j0 + jc) - j0;
             if (a >= b) continue;
-            if (!runs.empty() && run_eig.back() == s->lmm_eig_of_chrom[c]) runs.back().second = b;
+            if (!runs.empty() && run_eig.back() == lm.eig_of_chrom[c]) runs.back().second = b;
             else {
                 runs.emplace_back(a, b);
-                run_eig.push_back(s->lmm_eig_of_chrom[c]);
+                run_eig.push_back(lm.eig_of_chrom[c]);
             }
         }
         GBRS_TRY(rotate_ring.next(&slot));
         GBRS_HIP_CHECK(hipEventRecord(rotate_ring.ev[2 * slot], s->stream));
         hipLaunchKernelGGL(scan_snp_dosage_kernel, dim3((unsigned)((n * jc + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0, s->stream,
-                           n, s->M, s->H, j0, jc, s->dosage.p, s->snp_lo.p, s->snp_hi.p, s->snp_mask.p, s->snp_t.p, dose.p);
+                           n, s->M, s->H, j0, jc, s->cohort.dosage.p, sn.lo.p, sn.hi.p, sn.mask.p, sn.t.p, dose.p);
         for (size_t r = 0; r < runs.size(); ++r)
-            scan_lmm_rotate(s, n_ld, runs[r].second - runs[r].first, 1, 1, 1, jc, s->lmm_U.p + (size_t)run_eig[r] * n * n,
+            scan_lmm_rotate(s, n_ld, runs[r].second - runs[r].first, 1, 1, 1, jc, lm.U.p + (size_t)run_eig[r] * n * n,
                             dose.p + runs[r].first, xs.p + runs[r].first * n_ld);
         GBRS_HIP_CHECK(hipEventRecord(rotate_ring.ev[2 * slot + 1], s->stream));
         GBRS_HIP_CHECK(hipGetLastError());
@@ -1961,7 +1915,7 @@ int gbrs_scan_lmm_snps(gbrs_scan_t *s, int64_t P, const double *pheno, const dou
             }
             GBRS_HIP_CHECK(hipEventRecord(product_ring.ev[2 * slot + 1], s->stream));
             hipLaunchKernelGGL(lmm_snp_peak_kernel, dim3((unsigned)nc, (unsigned)pc), dim3(64), 0, s->stream, j0, jc, jc, nc,
-                               s->d_snp_off.p, d_used.p, d_lod.p, d_peak.p + p0 * nc, d_index.p + p0 * nc, d_count.p + p0 * nc);
+                               sn.d_off.p, d_used.p, d_lod.p, d_peak.p + p0 * nc, d_index.p + p0 * nc, d_count.p + p0 * nc);
             GBRS_HIP_CHECK(hipGetLastError());
             if (lod)        // waits for the kernels before it on the stream; the next chunk's product overwrites d_lod after it
                 GBRS_HIP_CHECK(hipMemcpy2DAsync(lod + p0 * M_snp + j0, (size_t)M_snp * sizeof(double), d_lod.p,
@@ -1972,47 +1926,28 @@ int gbrs_scan_lmm_snps(gbrs_scan_t *s, int64_t P, const double *pheno, const dou
                                                 hipMemcpyDeviceToHost, s->stream));
         }
     }
-    GBRS_HIP_CHECK(hipEventRecord(s->ev[1], s->stream));
-    GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
+    GBRS_TRY(timed_wait(s));
     GBRS_TRY(null_ring.drain());
     GBRS_TRY(rotate_ring.drain());
     GBRS_TRY(product_ring.drain());
-    std::vector<double> h_peak((size_t)P * nc);
-    std::vector<int64_t> h_index((size_t)P * nc);
-    GBRS_HIP_CHECK(hipMemcpy(h_peak.data(), d_peak.p, d_peak.bytes(), hipMemcpyDeviceToHost));
-    GBRS_HIP_CHECK(hipMemcpy(h_index.data(), d_index.p, d_index.bytes(), hipMemcpyDeviceToHost));
-    for (size_t k = 0; k < h_peak.size(); ++k)
-        if (h_index[k] < 0) h_peak[k] = std::numeric_limits<double>::quiet_NaN();
-    if (peak_lod) std::memcpy(peak_lod, h_peak.data(), h_peak.size() * sizeof(double));
-    if (peak_index) std::memcpy(peak_index, h_index.data(), h_index.size() * sizeof(int64_t));
-    if (n_used) GBRS_HIP_CHECK(hipMemcpy(n_used, d_count.p, d_count.bytes(), hipMemcpyDeviceToHost));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) s->t_lsnp_pass = ms;
-    s->t_lsnp_null = null_ring.ms;
-    s->t_lsnp_rotate = rotate_ring.ms;
-    s->t_lsnp_product = product_ring.ms;
-    s->lsnp_P = P;
-    s->lsnp_column_bytes = cols.bytes() + rss_all.bytes();
-    s->lsnp_peak_bytes = s->d_point_off.bytes() + s->dosage.bytes() + s->qz.bytes() + s->W.bytes() + s->d_rank.bytes() + s->y.bytes() +
-                         s->yt.bytes() + s->rss0.bytes() + s->lod.bytes() + s->peak_lod.bytes() + s->peak_index.bytes() + s->snp_bytes() +
-                         s->kin_S.bytes() + s->lmm_bytes() + y.bytes() + ys.bytes() + d_hin.bytes() + d_hsq.bytes() + d_sigma2.bytes() +
-                         sw.bytes() + qz.bytes() + yt.bytes() + rss0.bytes() + d_rmin.bytes() + d_rmax.bytes() + cols.bytes() +
-                         rss_all.bytes() + dose.bytes() + xs.bytes() + d_lod.bytes() + d_used.bytes() + d_peak.bytes() + d_index.bytes() +
-                         d_count.bytes();
+    GBRS_TRY(snp_peaks_out(d_peak, d_index, peak_lod, peak_index));
+    GBRS_TRY(copy_out(n_used, d_count, d_count.n));
+    gbrs_scan_lmm_snp_info_t &r = s->last.lmm_snp;
+    r.P = P;
+    r.last_pass_ms = pass_ms(s, r.last_pass_ms);
+    r.last_null_ms = null_ring.ms;
+    r.last_rotate_ms = rotate_ring.ms;
+    r.last_product_ms = product_ring.ms;
+    r.column_bytes = cols.bytes() + rss_all.bytes();
+    r.peak_device_bytes = s->resident_bytes() + own.bytes;
     return GBRS_OK;
 }
 
 int gbrs_scan_lmm_snp_info(gbrs_scan_t *s, gbrs_scan_lmm_snp_info_t *info) {
     if (!s || !info) return fail(GBRS_ERR_INVALID, "bad argument");
-    info->M_snp = s->M_snp;
+    *info = s->last.lmm_snp;
+    info->M_snp = s->snp.M;
     info->chunk = SS_CHUNK;
-    info->P = s->lsnp_P;
-    info->last_pass_ms = s->t_lsnp_pass;
-    info->last_null_ms = s->t_lsnp_null;
-    info->last_rotate_ms = s->t_lsnp_rotate;
-    info->last_product_ms = s->t_lsnp_product;
-    info->column_bytes = s->lsnp_column_bytes;
-    info->peak_device_bytes = s->lsnp_peak_bytes;
     return GBRS_OK;
 }
 
@@ -2033,10 +1968,10 @@ int gbrs_scan_int_prepare(gbrs_scan_t *s, int c, const double *qz, int k, const 
         return fail(GBRS_ERR_UNSUPPORTED, "%d interactive covariates of %d founders need %lld rows per grid point, more than 64", k, s->H,
                     (long long)(s->Hp + (int64_t)k * Hx));
     const int columns = Hx * (1 + k), hpi = s->Hp + k * Hx <= 16 ? 16 : s->Hp + k * Hx <= 32 ? 32 : 64;
-    if (s->n <= (int64_t)c + columns)
+    if (s->cohort.n <= (int64_t)c + columns)
         return fail(GBRS_ERR_INVALID, "%lld samples are too few for %d covariate columns and %d founders with %d interactive covariates: "
-                    "need more than %d", (long long)s->n, c, s->H, k, c + columns);
-    const int n = (int)s->n;
+                    "need more than %d", (long long)s->cohort.n, c, s->H, k, c + columns);
+    const int n = (int)s->cohort.n;
     for (int64_t q = 0; q < (int64_t)n * c; ++q)
         if (!std::isfinite(qz[q]))
             return fail(GBRS_ERR_INVALID, "covariate basis holds a value that is not finite (sample %lld, column %d)", (long long)(q / c),
@@ -2046,35 +1981,33 @@ int gbrs_scan_int_prepare(gbrs_scan_t *s, int c, const double *qz, int k, const 
             return fail(GBRS_ERR_INVALID, "interactive covariate %d holds a value that is not finite (sample %lld)", (int)(q % k),
                         (long long)(q / k));
     GBRS_TRY(select_device(s->device));
-    scan_int_unprepare(s);              // the arguments are good: from here on the preparation is being overwritten
-    const int64_t n_ld = ((int64_t)n + SC_KC - 1) / SC_KC * SC_KC, M = s->M;
-    GBRS_TRY(s->int_qz.alloc((size_t)n * c));
-    GBRS_TRY(s->int_zint.alloc((size_t)n * k));
-    GBRS_TRY(s->int_W.alloc((size_t)M * hpi * n_ld));
-    if (s->int_d_rank.n != (size_t)2 * M) GBRS_TRY(s->int_d_rank.alloc((size_t)2 * M));
-    GBRS_HIP_CHECK(hipMemcpy(s->int_qz.p, qz, s->int_qz.bytes(), hipMemcpyHostToDevice));
-    GBRS_HIP_CHECK(hipMemcpy(s->int_zint.p, zint, s->int_zint.bytes(), hipMemcpyHostToDevice));
-    GBRS_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
+    gbrs_scan::Inter &in = s->inter;
+    in.unprepare();                     // the arguments are good: from here on the preparation is being overwritten
+    const int64_t n_ld = padded(n), M = s->M;
+    GBRS_TRY(in.qz.alloc((size_t)n * c));
+    GBRS_TRY(in.zint.alloc((size_t)n * k));
+    GBRS_TRY(in.W.alloc((size_t)M * hpi * n_ld));
+    GBRS_TRY(resized(in.d_rank, (size_t)2 * M));
+    GBRS_HIP_CHECK(hipMemcpy(in.qz.p, qz, in.qz.bytes(), hipMemcpyHostToDevice));
+    GBRS_HIP_CHECK(hipMemcpy(in.zint.p, zint, in.zint.bytes(), hipMemcpyHostToDevice));
+    GBRS_TRY(timed_open(s));
     auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3((unsigned)M), dim3(SC_THREADS), 0, s->stream, n, M, s->H, s->Hp, c, k, n_ld, s->dosage.p,
-                           s->int_qz.p, s->int_zint.p, s->int_W.p, s->int_d_rank.p, s->int_d_rank.p + M);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)M), dim3(SC_THREADS), 0, s->stream, n, M, s->H, s->Hp, c, k, n_ld, s->cohort.dosage.p,
+                           in.qz.p, in.zint.p, in.W.p, in.d_rank.p, in.d_rank.p + M);
     };
     if (hpi == 16) launch(scan_int_prepare_kernel<16>);
     else if (hpi == 32) launch(scan_int_prepare_kernel<32>);
     else launch(scan_int_prepare_kernel<64>);
-    GBRS_HIP_CHECK(hipEventRecord(s->ev[1], s->stream));
-    GBRS_HIP_CHECK(hipGetLastError());
-    GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) s->t_int_prepare = ms;
+    GBRS_TRY(timed_wait(s));
+    s->last.inter.last_prepare_ms = pass_ms(s, s->last.inter.last_prepare_ms);
     std::vector<int32_t> rank((size_t)2 * M);
-    GBRS_HIP_CHECK(hipMemcpy(rank.data(), s->int_d_rank.p, s->int_d_rank.bytes(), hipMemcpyDeviceToHost));
-    s->int_rank_full.assign(rank.begin(), rank.begin() + M);
-    s->int_rank_add.assign(rank.begin() + M, rank.end());
-    s->int_n_ld = n_ld;
-    s->int_k = k;
-    s->int_hpi = hpi;
-    s->int_c = c;
+    GBRS_TRY(copy_out(rank.data(), in.d_rank, in.d_rank.n));
+    in.rank_full.assign(rank.begin(), rank.begin() + M);
+    in.rank_add.assign(rank.begin() + M, rank.end());
+    in.n_ld = n_ld;
+    in.k = k;
+    in.hpi = hpi;
+    in.c = c;
     return GBRS_OK;
 }
 
@@ -2082,19 +2015,17 @@ int gbrs_scan_int_run(gbrs_scan_t *s, int64_t P, const double *pheno, double *lo
                       double *peak_full, int64_t *peak_full_index, double *peak_full_add, double *peak_int, int64_t *peak_int_index) {
     RoctxRange roctx_range("gbrs_scan_int_run");
     if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
-    if (s->int_c == 0) return fail(GBRS_ERR_INVALID, "no interactive covariates on the handle: call gbrs_scan_int_prepare first");
+    if (s->inter.c == 0) return fail(GBRS_ERR_INVALID, "no interactive covariates on the handle: call gbrs_scan_int_prepare first");
     if (P < 1 || !pheno) return fail(GBRS_ERR_INVALID, "bad argument");
-    const int n = (int)s->n, nc = s->n_chrom;
-    for (int64_t q = 0; q < (int64_t)n * P; ++q)
-        if (!std::isfinite(pheno[q]))
-            return fail(GBRS_ERR_INVALID, "phenotype %lld holds a value that is not finite (sample %lld)", (long long)(q % P),
-                        (long long)(q / P));
+    const gbrs_scan::Inter &in = s->inter;
+    const int n = (int)s->cohort.n, nc = s->n_chrom;
+    GBRS_TRY(check_finite("phenotype", pheno, n, P));
     GBRS_TRY(select_device(s->device));
-    const int64_t pc_max = std::min(P, SC_PCHUNK), M = s->M, n_ld = s->int_n_ld;
+    const int64_t pc_max = std::min(P, SC_PCHUNK), M = s->M, n_ld = in.n_ld;
     // which of the three LOD rows a chunk needs on the device: an output's own, and those its peaks are taken from
     const bool need_full = lod_full || peak_full || peak_full_index || peak_full_add, need_add = lod_add || peak_full_add,
                need_int = lod_int || peak_int || peak_int_index;
-    DevBuf<double> y, yt, rss0, d_full, d_add, d_int, d_peak, d_peak_add;      // the call's own, as gbrs_scan_permute's
+    DevBuf<double> y, yt, rss0, d_full, d_add, d_int, d_peak, d_peak_add;      // the call's own; the pass reports no peak
     DevBuf<int64_t> d_index;
     GBRS_TRY(y.alloc((size_t)n * pc_max));
     GBRS_TRY(yt.alloc((size_t)pc_max * n_ld));
@@ -2105,24 +2036,21 @@ int gbrs_scan_int_run(gbrs_scan_t *s, int64_t P, const double *pheno, double *lo
     GBRS_TRY(d_peak.alloc((size_t)pc_max * nc));
     GBRS_TRY(d_peak_add.alloc((size_t)pc_max * nc));
     GBRS_TRY(d_index.alloc((size_t)pc_max * nc));
-    const unsigned row_blocks = (unsigned)((M * s->int_hpi + SC_ROWS - 1) / SC_ROWS);
+    const unsigned row_blocks = (unsigned)((M * in.hpi + SC_ROWS - 1) / SC_ROWS);
     double t_product = 0.0;
-    GBRS_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
+    GBRS_TRY(timed_open(s));
     for (int64_t p0 = 0; p0 < P; p0 += SC_PCHUNK) {
         const int64_t pc = std::min(SC_PCHUNK, P - p0);
-        const size_t peaks = (size_t)pc * nc;
-        GBRS_HIP_CHECK(hipMemcpy2DAsync(y.p, (size_t)pc * sizeof(double), pheno + p0, (size_t)P * sizeof(double),
-                                        (size_t)pc * sizeof(double), (size_t)n, hipMemcpyHostToDevice, s->stream));
-        hipLaunchKernelGGL(scan_pheno_kernel, dim3((unsigned)pc), dim3(64), 0, s->stream, n, s->int_c, n_ld, pc, y.p, s->int_qz.p, yt.p,
-                           rss0.p);
+        const size_t peaks = (size_t)pc * nc, lods = (size_t)pc * M, peak0 = (size_t)p0 * nc, lod0 = (size_t)p0 * M;
+        GBRS_TRY(project(s, in.qz, in.c, n_ld, pheno, P, p0, pc, y, yt.p, rss0.p));
         GBRS_HIP_CHECK(hipEventRecord(s->ev[2], s->stream));
         const dim3 grid(row_blocks, (unsigned)((pc + SC_COLS - 1) / SC_COLS));
         auto launch = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, grid, dim3(SC_THREADS), 0, s->stream, M, pc, n_ld, s->Hp, 0.5 * n, s->int_W.p, yt.p, rss0.p,
-                               d_full.p, d_add.p, d_int.p);
+            hipLaunchKernelGGL(kernel, grid, dim3(SC_THREADS), 0, s->stream, M, pc, n_ld, s->Hp, 0.5 * n, in.W.p, yt.p, rss0.p, d_full.p,
+                               d_add.p, d_int.p);
         };
-        if (s->int_hpi == 16) launch(scan_int_lod_kernel<16>);
-        else if (s->int_hpi == 32) launch(scan_int_lod_kernel<32>);
+        if (in.hpi == 16) launch(scan_int_lod_kernel<16>);
+        else if (in.hpi == 32) launch(scan_int_lod_kernel<32>);
         else launch(scan_int_lod_kernel<64>);
         GBRS_HIP_CHECK(hipEventRecord(s->ev[3], s->stream));
         GBRS_HIP_CHECK(hipGetLastError());
@@ -2135,52 +2063,45 @@ int gbrs_scan_int_run(gbrs_scan_t *s, int64_t P, const double *pheno, double *lo
                                    (int64_t)peaks, nc, d_index.p, d_add.p, d_peak_add.p);
             GBRS_HIP_CHECK(hipGetLastError());
             GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
-            if (lod_full) GBRS_HIP_CHECK(hipMemcpy(lod_full + p0 * M, d_full.p, (size_t)pc * M * sizeof(double), hipMemcpyDeviceToHost));
-            if (peak_full) GBRS_HIP_CHECK(hipMemcpy(peak_full + p0 * nc, d_peak.p, peaks * sizeof(double), hipMemcpyDeviceToHost));
-            if (peak_full_index)
-                GBRS_HIP_CHECK(hipMemcpy(peak_full_index + p0 * nc, d_index.p, peaks * sizeof(int64_t), hipMemcpyDeviceToHost));
-            if (peak_full_add)
-                GBRS_HIP_CHECK(hipMemcpy(peak_full_add + p0 * nc, d_peak_add.p, peaks * sizeof(double), hipMemcpyDeviceToHost));
+            GBRS_TRY(copy_out(lod_full, d_full, lods, lod0));
+            GBRS_TRY(copy_out(peak_full, d_peak, peaks, peak0));
+            GBRS_TRY(copy_out(peak_full_index, d_index, peaks, peak0));
+            GBRS_TRY(copy_out(peak_full_add, d_peak_add, peaks, peak0));
         }
         if (need_int) {
             hipLaunchKernelGGL(scan_peak_kernel, dim3((unsigned)nc, (unsigned)pc), dim3(64), 0, s->stream, M, nc, s->d_point_off.p,
                                d_int.p, d_peak.p, d_index.p);
             GBRS_HIP_CHECK(hipGetLastError());
             GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
-            if (lod_int) GBRS_HIP_CHECK(hipMemcpy(lod_int + p0 * M, d_int.p, (size_t)pc * M * sizeof(double), hipMemcpyDeviceToHost));
-            if (peak_int) GBRS_HIP_CHECK(hipMemcpy(peak_int + p0 * nc, d_peak.p, peaks * sizeof(double), hipMemcpyDeviceToHost));
-            if (peak_int_index)
-                GBRS_HIP_CHECK(hipMemcpy(peak_int_index + p0 * nc, d_index.p, peaks * sizeof(int64_t), hipMemcpyDeviceToHost));
+            GBRS_TRY(copy_out(lod_int, d_int, lods, lod0));
+            GBRS_TRY(copy_out(peak_int, d_peak, peaks, peak0));
+            GBRS_TRY(copy_out(peak_int_index, d_index, peaks, peak0));
         }
         GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
-        if (lod_add) GBRS_HIP_CHECK(hipMemcpy(lod_add + p0 * M, d_add.p, (size_t)pc * M * sizeof(double), hipMemcpyDeviceToHost));
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, s->ev[2], s->ev[3]) == hipSuccess) t_product += ms;
+        GBRS_TRY(copy_out(lod_add, d_add, lods, lod0));
+        t_product += elapsed_ms(s->ev[2], s->ev[3], 0.0);
     }
-    GBRS_HIP_CHECK(hipEventRecord(s->ev[1], s->stream));
-    GBRS_HIP_CHECK(hipStreamSynchronize(s->stream));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) s->t_int_run = ms;
-    s->t_int_product = t_product;
+    GBRS_TRY(timed_wait(s));
+    s->last.inter.last_run_ms = pass_ms(s, s->last.inter.last_run_ms);
+    s->last.inter.last_product_ms = t_product;
     return GBRS_OK;
 }
 
 int gbrs_scan_int_info(gbrs_scan_t *s, gbrs_scan_int_info_t *info, int32_t *rank_full, int32_t *rank_add) {
     if (!s) return fail(GBRS_ERR_INVALID, "handle is NULL");
+    const gbrs_scan::Inter &in = s->inter;
     if (info) {
-        info->n = s->n;
+        *info = s->last.inter;
+        info->n = s->cohort.n;
         info->M = s->M;
         info->H = s->H;
-        info->c = s->int_c;
-        info->k = s->int_k;
-        info->HPI = s->int_hpi;
-        info->last_prepare_ms = s->t_int_prepare;
-        info->last_run_ms = s->t_int_run;
-        info->last_product_ms = s->t_int_product;
-        info->device_bytes = s->int_c > 0 ? s->int_bytes() : 0;
+        info->c = in.c;
+        info->k = in.k;
+        info->HPI = in.hpi;
+        info->device_bytes = in.c > 0 ? in.bytes() : 0;
     }
-    if (rank_full && s->int_c > 0) std::memcpy(rank_full, s->int_rank_full.data(), s->int_rank_full.size() * sizeof(int32_t));
-    if (rank_add && s->int_c > 0) std::memcpy(rank_add, s->int_rank_add.data(), s->int_rank_add.size() * sizeof(int32_t));
+    if (rank_full && in.c > 0) std::memcpy(rank_full, in.rank_full.data(), in.rank_full.size() * sizeof(int32_t));
+    if (rank_add && in.c > 0) std::memcpy(rank_add, in.rank_add.data(), in.rank_add.size() * sizeof(int32_t));
     return GBRS_OK;
 }
 
